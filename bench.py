@@ -10,7 +10,7 @@ reading reference DDH supports), fp32 local solves (the reference's precision), 
            against the current Krylov basis (k cycles 0..19), issued through the same C-ABI calls
            the product's gmres() makes (fused MGS stages, coefficients on the device).
   value  = 2 * g_ndof * steps / seconds   [DoF.iter/s], whole job, MAX time over ranks.
-  gmres_call = one REAL call of the product's gmres() (cuddh_gmres_ddh; with N > 1 the sharded
+  gmres_call = (--full) one REAL call of the product's gmres() (cuddh_gmres_ddh; with N > 1 the sharded
            native Arnoldi with the all-reduce hook) on the same system, m = 20, one restart cycle,
            tol 0: SURVEY 8d's definition 2 * g_ndof * num_matvec / t_gmres with num_matvec as the
            solver counts it (initial residual + 20 Arnoldi steps + true residual = 22), restart
@@ -28,18 +28,31 @@ reading reference DDH supports), fp32 local solves (the reference's precision), 
   coefficient: the headline runs the reference example's own two-valued disk coefficient (examples/DDH.cpp:74-83, a = 0.2
            inside r < 0.25).  In BASELINE's regime (32 elements per wavelength, nt = 5120) the reference's time stepping is
            UNSTABLE with it (|T| ~ 1e7: tests/test_baseline_regime.py), so fp32 results carry no meaningful digits there; the time
-           per step does not depend on the values.  `stable_coefficient` therefore times the same K steps with a = 1, where the
+           per step does not depend on the values.  `stable_coefficient` (--full) therefore times the same K steps with a = 1, where the
            local solves are non-expansive and fp32 agrees with the fp64 oracle to 1e-6 (same test file).
   N > 1 fields: `exchange` (neighbour | allreduce), `fell_back`, `exchange_bytes`, `rank_grid`, `action_ms` (per-rank local
            solves + exchange, min / max over ranks), `roofline_sharded` (the partitioned global operator apply, fraction of
            N x 8 TB/s).  An explicit `--exchange neighbour` that falls back ends non-zero.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W untimed and K timed steps, writes the
+outputs of the last step if --dump-outputs DIR is given, and prints the result line: `value`, `ms_per_step`, the
+`config` and `ddh_kernel` figures derived from the timed loop, and (N > 1) `exchange`, `fell_back`, `rank_grid`,
+`exchange_bytes`.  Everything that takes runs of its own moves behind --full: `stable_coefficient`, `gmres_call`,
+`roofline`, `cpu_baseline` and (N > 1) `action_ms` and `roofline_sharded`; the --no-* options below switch single
+ones off inside a --full run.
+
+  --dump-outputs DIR = what a caller of the timed path receives from its last step, as float32 .npy files:
+           krylov_vector.npy (v_{k+1}, the new orthonormal Arnoldi vector, all n_traces entries) and
+           hessenberg_column.npy (h_{0..k+1,k}, the Gram-Schmidt coefficients).  Above 64 MB the vector is a fixed
+           seeded sample, with its indices in krylov_vector_index.npy (float64).  The inputs depend on the arguments
+           alone, so two builds can be compared output for output.
+
 Extra objects on the same JSON line:
-  roofline     = the global operator apply (fused complex Helmholtz apply on the same mesh, in the
+  ddh_kernel   = the dominant kernel of `value` (not HBM-bound): fp32 FLOP rate vs vector peak (every run).
+  roofline     = (--full) the global operator apply (fused complex Helmholtz apply on the same mesh, in the
                  GENERAL-geometry layout), the HBM-bound kernel of the path: algorithmic bytes /
                  measured launch time; roofline.affine = labelled timing of the uniform-mesh form.
-  ddh_kernel   = the dominant kernel of `value` (not HBM-bound): fp32 FLOP rate vs vector peak.
-  cpu_baseline = the oracle's restatement of the local solves timed on the host cores on a
+  cpu_baseline = (--full) the oracle's restatement of the local solves timed on the host cores on a
                  bounded sample of subdomains (rank 0, N = 1 only).
 """
 from __future__ import annotations
@@ -137,7 +150,14 @@ def main() -> None:
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-gmres-call", action="store_true", help="skip the real gmres() call timed beside the step loop")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the a = 1 loop, the real gmres() call, the roofline, the CPU "
+                         "baseline and (N > 1) the per-rank action times and the partitioned apply")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -309,6 +329,7 @@ def main() -> None:
         def step(self) -> None:
             k = self.step_id % gmres_m
             self.step_id += 1
+            self.k_last = k
             V, hcol, ws, upd = self.V, self.hcol, self.ws, self.upd
             vk, vk1 = V[k], V[k + 1]
             if world == 1:
@@ -360,6 +381,15 @@ def main() -> None:
     stepper = Stepper(F, sh, b, partitioned)
     elapsed, finite = stepper.timed(args.steps, args.warmup)
     upd = stepper.upd
+    if args.dump_outputs:
+        k = stepper.k_last
+        vk1 = stepper.V[k + 1].clone()
+        if partitioned:  # each rank holds its own slots (zero elsewhere): the sum over the ranks is the whole vector
+            allred(vk1)
+        if rank == 0:
+            dump_outputs(Path(args.dump_outputs), {"krylov_vector": vk1.cpu().numpy(),
+                                                   "hessenberg_column": stepper.h_host[: k + 2].numpy().copy()})
+        del vk1
 
     value = 2.0 * ndof * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
@@ -430,23 +460,24 @@ def main() -> None:
     # ---------------------------------------------------------------- N > 1: what the exchange is and what a rank's action costs
     if world > 1:
         my_bytes = float(sum(i.numel() for i in send_idx.values()) * 4) if partitioned else float(n * 4)
-        lam_probe = stepper.V[0]
-        e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-        reps = 3
-        barrier()
         t_act, t_solve = 0.0, 0.0
-        for _ in range(reps):
-            e0.record()
-            if partitioned:
-                sh._solve("all", None, lam_probe, upd)  # local solves only (no exchange)
-            else:
-                F.local_traces(sh.d0, sh.d1, None, lam_probe, upd)
-            e1.record()
-            sh.traces(None, lam_probe, upd)             # local solves + exchange / reassembly, as in a step
-            e2.record()
-            torch.cuda.synchronize()
-            t_solve += e0.elapsed_time(e1) / reps
-            t_act += e1.elapsed_time(e2) / reps
+        if args.full:
+            lam_probe = stepper.V[0]
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            reps = 3
+            barrier()
+            for _ in range(reps):
+                e0.record()
+                if partitioned:
+                    sh._solve("all", None, lam_probe, upd)  # local solves only (no exchange)
+                else:
+                    F.local_traces(sh.d0, sh.d1, None, lam_probe, upd)
+                e1.record()
+                sh.traces(None, lam_probe, upd)             # local solves + exchange / reassembly, as in a step
+                e2.record()
+                torch.cuda.synchronize()
+                t_solve += e0.elapsed_time(e1) / reps
+                t_act += e1.elapsed_time(e2) / reps
         stats = torch.tensor([t_act, -t_act, t_solve, -t_solve, my_bytes, -my_bytes], dtype=torch.float64, device=dev)
         allred(stats, dist.ReduceOp.MAX)
         tot = torch.tensor([my_bytes, t_act], dtype=torch.float64, device=dev)
@@ -458,15 +489,16 @@ def main() -> None:
         result["exchange_bytes"] = {"per_action_rank_max": mx_b, "per_action_rank_min": -mn_b, "per_action_all_ranks": float(tot[0].item()),
                                     "what": "packed trace values (fp32) a rank sends to its neighbours per DDH::action" if partitioned
                                             else "the replicated trace vector all-reduced per DDH::action (bytes per rank)"}
-        result["action_ms"] = {"max": mx_act, "min": -mn_act, "mean": float(tot[1].item()) / world,
-                               "local_solves_only_max": mx_solve, "local_solves_only_min": -mn_solve,
-                               "what": "per-rank HIP-event time of one sharded DDH::action (local solves of the rank's subdomains + trace "
-                                       "exchange), outside the timed loop; min / max over ranks"}
+        if args.full:
+            result["action_ms"] = {"max": mx_act, "min": -mn_act, "mean": float(tot[1].item()) / world,
+                                   "local_solves_only_max": mx_solve, "local_solves_only_min": -mn_solve,
+                                   "what": "per-rank HIP-event time of one sharded DDH::action (local solves of the rank's subdomains + trace "
+                                           "exchange), outside the timed loop; min / max over ranks"}
     else:
         result["exchange"], result["fell_back"], result["rank_grid"] = "none", False, "1x1"
 
     # ---------------------------------------------------------------- the same K steps with a = 1 (stable local solves)
-    if args.coefficient != "one" and not args.no_stable_coefficient:
+    if args.full and args.coefficient != "one" and not args.no_stable_coefficient:
         F1 = cd.DDH(omega, coefficient("one"), fem, nx, nx, precision="f32", kernel=args.kernel)
         sh1, b1, ex1, note1 = shard(F1, check=False)
         st1 = Stepper(F1, sh1, b1, ex1 == "neighbour")
@@ -480,7 +512,7 @@ def main() -> None:
         del st1, sh1, F1
 
     # ---------------------------------------------------------------- one real gmres() call (SURVEY 8d's definition of the metric)
-    if not args.no_gmres_call:
+    if args.full and not args.no_gmres_call:
         lam = torch.zeros(n, dtype=torch.float32, device=dev)
         barrier()
         t0 = time.perf_counter()
@@ -508,11 +540,11 @@ def main() -> None:
         }
 
     # ---------------------------------------------------------------- roofline: the global operator apply
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         result["roofline"] = helmholtz_roofline(cd, torch, dev, fem, mesh, omega, ndof)
 
     # ---------------------------------------------------------------- the partitioned global apply over the N ranks
-    if world > 1 and args.sharded_apply:
+    if args.full and world > 1 and args.sharded_apply:
         try:
             result_sh = sharded_apply_rate(cd, torch, dist, dev, fem, mesh, omega, ndof, rank, world, staged, allred)
             err = 0.0
@@ -527,7 +559,7 @@ def main() -> None:
             result["roofline_sharded"] = result_sh
 
     # ---------------------------------------------------------------- CPU baseline (oracle), N = 1 only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(F, info, ndof, nb, omega, args.cpu_seconds)
 
     if dist.is_initialized():
@@ -536,6 +568,28 @@ def main() -> None:
     if rank == 0:
         assert result["n_gpus"] == args.gpus
         print(json.dumps(result), flush=True)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, arrays: dict) -> None:
+    """Writes each array as out_dir/<name>.npy in float32 (float64 stays float64).  If the whole set is larger than
+    DUMP_BUDGET_BYTES, every array above 1 MB is replaced by a fixed seeded sample of its entries, whose flat indices go to
+    <name>_index.npy (float64, exact below 2**53)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    large = [k for k, a in arrays.items() if a.nbytes > (1 << 20)]
+    share = (DUMP_BUDGET_BYTES - sum(a.nbytes for k, a in arrays.items() if k not in large)) // max(len(large), 1)
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES and name in large:
+            n_sample = min(a.size, share // (a.itemsize + 8) - 64)  # values + float64 indices (+ .npy headers) within the share
+            idx = np.sort(np.random.default_rng(20240601).choice(a.size, size=n_sample, replace=False))
+            np.save(out_dir / f"{name}_index.npy", idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a)
+    print(f"bench.py: wrote {', '.join(sorted(arrays))} to {out_dir}", file=sys.stderr)
 
 
 def sharded_apply_rate(cd, torch, dist, dev, fem, mesh, omega, ndof, rank, world, staged, allred):

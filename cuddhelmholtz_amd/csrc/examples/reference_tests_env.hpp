@@ -1,9 +1,9 @@
 // Force-included (-include) when the reference's own tests/*.cpp are compiled unchanged against csrc/include/cuddh.hpp
-// (cuddhelmholtz_amd/build.py::build_examples).  The reference's loader does `std::string dir = UNSTRUCTURED_SQUARE_MESH_DIR;`
+// (by the test infrastructure's recipe, __graft_entry__.build()).  The reference's loader does `std::string dir = UNSTRUCTURED_SQUARE_MESH_DIR;`
 // (tests/load_unstructured_square.cpp:13) and its build system defines the macro as a path literal
 // (tests/CMakeLists.txt:8).  Here the macro expands to this function, so the binary finds the fixture wherever the checkout is:
 // $CUDDH_MESH_DIR if set, else <root>/tests/golden/unstructured_square with <root> = two directories above the binary
-// (build/examples/reference_tests_driver).
+// (<root>/<dir>/<subdir>/reference_tests_driver).
 #ifndef CUDDH_AMD_REFERENCE_TESTS_ENV_HPP
 #define CUDDH_AMD_REFERENCE_TESTS_ENV_HPP
 

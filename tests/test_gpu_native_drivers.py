@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden"
 EX = ROOT / "build" / "examples"
+REF_EX = ROOT / "oracle" / "_ref"  # the reference's own drivers (oracle/ref_drivers.py)
 
 
 def python_solve(cuda, nx, nb, omega, m, maxit, tol):
@@ -85,7 +86,7 @@ def test_ddh_solve_driver_multi_gpu_host(cuda, tmp_path):
 def test_reference_ddh_example_runs_unchanged(cuda, tmp_path):
     """examples/DDH.cpp of the reference (128^2, degree 3, omega = 2 pi 12.8, GMRES(20), maxit 100, tol 1e-4),
     compiled unchanged against csrc/include/cuddh.hpp."""
-    exe = EX / "DDH_reference_driver"
+    exe = REF_EX / "DDH_reference_driver"
     if not exe.exists():
         pytest.skip("reference example was not built (reference tree absent at build time)")
     (tmp_path / "solution").mkdir()
@@ -108,7 +109,7 @@ def test_reference_test_suite_runs_unchanged(cuda, tmp_path):
     run on the GPU: every known-answer check the reference holds for this path, evaluated by the reference's own code."""
     import re
 
-    exe = EX / "reference_tests_driver"
+    exe = REF_EX / "reference_tests_driver"
     if not exe.exists():
         pytest.skip("reference test suite was not built (reference tree absent at build time)")
     r = subprocess.run([str(exe)], cwd=tmp_path, capture_output=True, text=True, timeout=600)
@@ -126,7 +127,7 @@ def test_reference_poisson_example_runs_unchanged(cuda, tmp_path):
     csrc/include/cuddh.hpp, checked against the same flow on the oracle."""
     import oracle
 
-    exe = EX / "Poisson_reference_driver"
+    exe = REF_EX / "Poisson_reference_driver"
     if not exe.exists():
         pytest.skip("reference example was not built (reference tree absent at build time)")
     (tmp_path / "solution").mkdir()

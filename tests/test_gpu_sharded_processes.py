@@ -75,12 +75,12 @@ def test_bench_two_rank_rehearsal(cuda, split, grid):
     all-reduce assembly, reduced inner products, max-over-ranks timing, one JSON line from rank 0) with two ranks
     sharing the GPU over gloo; with and without the split schedule (boundary subdomains as one listed launch with issue
     priority on a second stream -- the start-up cross-check then compares THAT assembly bitwise with the all-reduce one).
-    grid "" = bench.py's default for the rank count (2x1 for two ranks).  The N > 1 line is self-sufficient:
-    exchange kind, fell_back, bytes exchanged, per-rank action time, and the partitioned global apply as `roofline_sharded`
-    with its fraction of N x 8 TB/s.  The printed rates are not measurements."""
+    grid "" = bench.py's default for the rank count (2x1 for two ranks).  The N > 1 line of a --full run is
+    self-sufficient: exchange kind, fell_back, bytes exchanged, per-rank action time, and the partitioned global apply as
+    `roofline_sharded` with its fraction of N x 8 TB/s.  The printed rates are not measurements."""
     import json
 
-    r = run_bench_two_ranks((["--overlap"] if split else []) + (["--rank-grid", grid] if grid else []))
+    r = run_bench_two_ranks(["--full"] + (["--overlap"] if split else []) + (["--rank-grid", grid] if grid else []))
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
