@@ -406,7 +406,12 @@ def _solver_out(res: N.SolverResult, h_res, h_time) -> SolverOut:
 
 class DDH:
     """Substructured Helmholtz solver (reference include/DDH.hpp).  precision 'f32' is the
-    reference's; 'f64' is the parity mode with double traces."""
+    reference's; 'f64' is the parity mode with double traces.
+
+    kernel selects the local-solve kernel (cuddh_hip_ddh_plan_create): 0 auto, 1 generic, 2 wavefront per subdomain,
+    3 / 4 / 5 / 7 fp32 forms (5: dense element matrix on the matrix cores), 6 n_basis 8, 8 = kernel 5 in fp64
+    (precision='f64', n_basis 4, uniform metric; never picked by auto).  Requested where it does not apply, 5 to 8 raise on
+    first use."""
 
     _INT_TABLES = ("B", "gI", "sI")
 

@@ -108,7 +108,8 @@ namespace cuddh
     public:
         /// @param h_a HOST nodal coefficient a(x); @param fem space on a Mesh2D::uniform_rect(nx, ..., ny, ...) mesh
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny);
-        /// extension: pick the local-solve kernel (0 auto, 1 generic workgroup, 2 wavefront-per-subdomain)
+        /// extension: pick the local-solve kernel (0 auto, 1 generic workgroup, 2 wavefront-per-subdomain, 3-7 the fp32 forms of
+        /// cuddh_hip_ddh_plan_create; 8 is fp64 only, see DDH64).  A requested kernel that does not apply throws on first use.
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel);
         ~DDH() = default;
 
@@ -133,6 +134,8 @@ namespace cuddh
     class DDH64 : public Operator
     {
     public:
+        /// kernel: 0 auto (3 for n_basis 4), 1 generic, 2 wavefront-per-subdomain, 6 n_basis 8, 8 = the dense element matrix on
+        /// the fp64 matrix cores (n_basis 4, uniform metric; on request only).  See cuddh_hip_ddh_plan_create.
         DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel = 0);
 
         int size() const { return core.n_traces(); }

@@ -26,12 +26,14 @@ struct cuddh_ddh_plan
     cuddh_ddh_desc d;
     int is_f64;
     int kernel; // 1 block, 2 wave, 3 wave with hand-folded DPP FMAs (fp32), 4 = 3 + MFMA for the in-lane contractions,
-                // 5 dense element matrix on the matrix cores (fp32, uniform geometry)
+                // 5 dense element matrix on the matrix cores (fp32, uniform geometry), 6 / 7 nb == 8 wave (7 separable, fp32),
+                // 8 = 5 in fp64
     int nodes;  // nb*nb*nel1d*nel1d
     int wh_iters = 5; // WaveHoltz iterations per local solve (source/DDH.cpp:136); WH_ITERS_REFERENCE
     const int *gI_override = nullptr; // cuddh_hip_ddh_plan_set_vector_layout: x and y in another numbering than d.gI
     int g_ndof_override = 0;
     float *Aop = nullptr; // kernel 5: element stiffness matrix as MFMA A operands, [4 k-steps][64 lanes]
+    double *Aop64 = nullptr; // kernel 8: the same in fp64, rows in the f64 MFMA's output order (build_dense_element_matrix)
     float *Sep = nullptr; // kernel 7: [Ax | Ay | beta | gamma] of the separable nb = 8 sweep
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
 };
@@ -1016,14 +1018,195 @@ namespace
         }
     }
 
-    // is the metric tensor of every element of every subdomain identical to that of (subdomain 0, element 0)?
-    __global__ void __launch_bounds__(256) ddh_uniform_check_kernel(long long n_nodes_total, int nodes_per_elem, const float *__restrict__ G,
+    // ---------------------------------------------------------------- kernel 8: kernel 5's scheme in fp64 (v_mfma_f64_16x16x4_f64)
+    // Same lanes as ddh_mfma_kernel (lane = element + 16 k, register = l) and the same A/B operand maps; only the C/D map of
+    // the f64 instruction differs: row = (lane >> 4) + 4 reg instead of 4 (lane >> 4) + reg.  build_dense_element_matrix<double>
+    // orders K's output rows as m = k_out + 4 l_out to match, so the result again lands in lane (el, k), register l.  K is
+    // formed and kept in double: every operation of a sweep is fp64, the summation order alone differs from the
+    // sum-factorised kernels 1 and 2.
+    // CUDDH_DDH64_MFMA_PRIO=1 issues the four matrix instructions of a sweep with raised priority, as kernel 5 does.  In fp64 that
+    // grouping is 0.7-1.7 % slower than plain issue order (same-box A/B, profiles/r04/ddh64_prio_ab.txt), hence off by default;
+    // the knob stays for A/B builds (profiles/tools/build_variant.py).
+#ifndef CUDDH_DDH64_MFMA_PRIO
+#define CUDDH_DDH64_MFMA_PRIO 0
+#endif
+    __global__ void __launch_bounds__(256) ddh_mfma64_kernel(DdhArgs<double> A, const double *__restrict__ Aop, const double *__restrict__ filt,
+                                                            const double *__restrict__ cs, const double *__restrict__ sn)
+    {
+        typedef double d4 __attribute__((ext_vector_type(4)));
+        const int lane = threadIdx.x & 63;
+        const int position = A.dom_begin + blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (position >= A.dom_end)
+            return; // wave-uniform, no barriers in this kernel
+        const int s = domain_at(A, position);
+        raise_priority(A.prio);
+
+        const int k = lane >> 4, el = lane & 15, ex = el & 3, ey = el >> 2;
+        const int fdof = A.s_fdof[s];
+        const int *sI = A.sI + 256 * (size_t)s;
+        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
+
+        double invm[4], Hi[4], F[4], Gf[4], p[4], q[4], u[4], v[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+        {
+            const int d = sI[k + 4 * (l + 4 * el)];
+            const double ai = A.a[dbase + d], mi = A.m[dbase + d];
+            invm[l] = 1.0 / (ai * ai * mi);
+            double f = 0, gg = 0, h = 0;
+            if (A.x)
+            {
+                const int gidx = A.gI[dbase + d];
+                f = A.x[gidx];
+                gg = A.x[A.g_ndof + gidx];
+            }
+            if (d < fdof)
+            {
+                h = A.H[fbase + d];
+                if (A.lambda)
+                {
+                    const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
+                    if (slot >= 0)
+                    {
+                        f += h * A.lambda[slot];
+                        gg += h * A.lambda[A.n_lambda + slot];
+                    }
+                }
+                h *= ai;
+            }
+            F[l] = f;
+            Gf[l] = gg;
+            Hi[l] = h;
+            p[l] = q[l] = u[l] = v[l] = 0;
+        }
+        double Ka[4];
+#pragma unroll
+        for (int st = 0; st < 4; ++st)
+            Ka[st] = Aop[64 * st + lane];
+
+        // xi neighbours live in another 16-lane row: ds_bpermute; eta neighbours are 4 lanes away in the same row: DPP row_shl/shr:4
+        const bool hasR = (k == 3 && ex < 3), hasL = (k == 0 && ex > 0);
+        const int partner = hasR ? (el + 1) : (hasL ? (el - 1 + 48) : lane);
+        const double mX = (hasR || hasL) ? 1.0 : 0.0;
+        const double mU = (ey < 3) ? 1.0 : 0.0, mD = (ey > 0) ? 1.0 : 0.0;
+
+        auto sweep = [&](const double (&w)[4], double (&z)[4])
+        {
+            d4 acc = {0.0, 0.0, 0.0, 0.0};
+#if CUDDH_DDH64_MFMA_PRIO
+            __builtin_amdgcn_s_setprio(3);
+#endif
+#pragma unroll
+            for (int st = 0; st < 4; ++st)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ka[st], w[st], acc, 0, 0, 0);
+#if CUDDH_DDH64_MFMA_PRIO
+            if (!A.prio) // a launch that holds issue priority as a whole (multi-GPU boundary subdomains) keeps it
+                __builtin_amdgcn_s_setprio(0);
+#endif
+            double fx[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                fx[l] = __shfl(acc[l], partner, 64);
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                z[l] = acc[l] + mX * fx[l];
+            const double from_above = dpp_read<0x104>(z[0]); // row_shl:4 : lane + 4 = element above
+            const double from_below = dpp_read<0x114>(z[3]); // row_shr:4
+            z[3] += mU * from_above;
+            z[0] += mD * from_below;
+        };
+
+        const double dt = A.dt, half_dt = 0.5 * A.dt;
+        const int nt = A.nt;
+        for (int whit = 0; whit < A.wh_iters; ++whit)
+        {
+            {
+                const double k0 = filt[0];
+#pragma unroll
+                for (int l = 0; l < 4; ++l)
+                {
+                    p[l] = u[l];
+                    q[l] = v[l];
+                    u[l] *= k0;
+                    v[l] *= k0;
+                }
+            }
+            for (int it = 1; it <= nt; ++it)
+            {
+                const double c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                const double c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                const double kw = filt[it];
+                double z[4], ph[4], qh[4];
+                sweep(p, z);
+#pragma unroll
+                for (int l = 0; l < 4; ++l)
+                {
+                    const double dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
+                    ph[l] = p[l] - half_dt * q[l];
+                    qh[l] = q[l] + half_dt * dq;
+                    p[l] -= dt * qh[l];
+                }
+                sweep(ph, z);
+#pragma unroll
+                for (int l = 0; l < 4; ++l)
+                {
+                    const double dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
+                    q[l] += dt * dq;
+                    u[l] += kw * p[l];
+                    v[l] += kw * q[l];
+                }
+            }
+        }
+
+        const double rw = 1.0 / A.omega;
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+        {
+            v[l] *= rw;
+            const bool owner = !(k == 0 && ex > 0) && !(l == 0 && ey > 0);
+            if (!owner)
+                continue;
+            const int d = sI[k + 4 * (l + 4 * el)];
+            if (A.y)
+            {
+                const int gidx = A.gI[dbase + d];
+                const double M = A.m[dbase + d] * A.gmi[dbase + d];
+                atomic_add(A.y + gidx, M * u[l]);
+                atomic_add(A.y + A.g_ndof + gidx, M * v[l]);
+            }
+            if (A.update && d < fdof)
+            {
+                const int wslot = A.B[d + (size_t)A.mx_fdof * (1 + 2 * (size_t)s)];
+                if (wslot >= 0)
+                {
+                    double lam = 0, mu = 0;
+                    if (A.lambda)
+                    {
+                        const int rslot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
+                        if (rslot >= 0)
+                        {
+                            lam = A.lambda[rslot];
+                            mu = A.lambda[A.n_lambda + rslot];
+                        }
+                    }
+                    const double S = 2.0 * A.a[dbase + d] * A.omega;
+                    A.update[wslot] = -lam - S * v[l];
+                    A.update[A.n_lambda + wslot] = -mu + S * u[l];
+                }
+            }
+        }
+    }
+
+    // is the metric tensor of every element of every subdomain identical to that of (subdomain 0, element 0)?  (compared in the
+    // plan's precision: float for kernel 5, double for kernel 8)
+    template <typename Real>
+    __global__ void __launch_bounds__(256) ddh_uniform_check_kernel(long long n_nodes_total, int nodes_per_elem, const Real *__restrict__ G,
                                                                     int *__restrict__ bad)
     {
         for (long long t = blockIdx.x * 256LL + threadIdx.x; t < n_nodes_total; t += gridDim.x * 256LL)
         {
             const int node = static_cast<int>(t % nodes_per_elem); // node within its element
-            const float *g = G + 3 * t, *g0 = G + 3 * node;
+            const Real *g = G + 3 * t, *g0 = G + 3 * node;
             if (g[0] != g0[0] || g[1] != g0[1] || g[2] != g0[2])
                 atomicExch(bad, 1);
         }
@@ -1288,18 +1471,20 @@ namespace
                            static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs), static_cast<const Real *>(d.sn));
     }
 
-    // Builds plan->Aop for kernel 5.  Returns 0 on success, -1 if the geometry is not uniform, > 0 on a HIP error.
+    // Builds plan->Aop for kernel 5 (Real = float) or plan->Aop64 for kernel 8 (Real = double).  Returns 0 on success, -1 if
+    // the geometry is not uniform, > 0 on a HIP error.
+    template <typename Real>
     int build_dense_element_matrix(cuddh_ddh_plan *p)
     {
         const cuddh_ddh_desc &d = p->d;
-        const float *G = static_cast<const float *>(d.G);
+        const Real *G = static_cast<const Real *>(d.G);
         int *flag = nullptr;
         hipError_t e = hipMalloc(&flag, sizeof(int));
         if (e != hipSuccess)
             return static_cast<int>(e);
         (void)hipMemset(flag, 0, sizeof(int));
         const long long n_nodes = 256LL * d.n_domains;
-        hipLaunchKernelGGL(ddh_uniform_check_kernel, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, nullptr, n_nodes, 16, G, flag);
+        hipLaunchKernelGGL(ddh_uniform_check_kernel<Real>, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, nullptr, n_nodes, 16, G, flag);
         int bad = 1;
         e = hipMemcpy(&bad, flag, sizeof(int), hipMemcpyDeviceToHost);
         (void)hipFree(flag);
@@ -1308,7 +1493,7 @@ namespace
         if (bad)
             return -1;
 
-        float hD[16], hG[48];
+        Real hD[16], hG[48];
         e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
         if (e == hipSuccess)
             e = hipMemcpy(hG, G, sizeof hG, hipMemcpyDeviceToHost);
@@ -1332,7 +1517,7 @@ namespace
                         ux += Dm(k, i) * U[i + 4 * l];
                         uy += Dm(l, i) * U[k + 4 * i];
                     }
-                    const float *g = hG + 3 * (k + 4 * l);
+                    const Real *g = hG + 3 * (k + 4 * l);
                     f1[k + 4 * l] = g[0] * ux + g[1] * uy;
                     f2[k + 4 * l] = g[1] * ux + g[2] * uy;
                 }
@@ -1345,19 +1530,27 @@ namespace
                     K[k + 4 * l][nin] = su;
                 }
         }
-        // A operand of step st, lane ln:  A[i = ln & 15][kk = 4 st + (ln >> 4)] = K'[m = i][nu = kk],
-        // m = 4 k_out + l_out, nu = 4 l_in + k_in
-        float hA[256];
+        // A operand of step st, lane ln:  A[i = ln & 15][kk = 4 st + (ln >> 4)] = K'[m = i][nu = kk], nu = 4 l_in + k_in.
+        // The output row order follows the C/D map: m = 4 k_out + l_out for v_mfma_f32_16x16x4_f32 (row = 4 (lane >> 4) + reg),
+        // m = k_out + 4 l_out for v_mfma_f64_16x16x4_f64 (row = (lane >> 4) + 4 reg); either way lane (el, k) gets node (k, l)
+        // in register l.
+        constexpr bool F64 = sizeof(Real) == 8;
+        Real hA[256];
         for (int st = 0; st < 4; ++st)
             for (int ln = 0; ln < 64; ++ln)
             {
                 const int m = ln & 15, nu = 4 * st + (ln >> 4);
-                const int k_out = m >> 2, l_out = m & 3, l_in = nu >> 2, k_in = nu & 3;
-                hA[64 * st + ln] = static_cast<float>(K[k_out + 4 * l_out][k_in + 4 * l_in]);
+                const int k_out = F64 ? (m & 3) : (m >> 2), l_out = F64 ? (m >> 2) : (m & 3), l_in = nu >> 2, k_in = nu & 3;
+                hA[64 * st + ln] = static_cast<Real>(K[k_out + 4 * l_out][k_in + 4 * l_in]);
             }
-        e = hipMalloc(reinterpret_cast<void **>(&p->Aop), sizeof hA);
+        Real *dA = nullptr;
+        e = hipMalloc(reinterpret_cast<void **>(&dA), sizeof hA);
         if (e == hipSuccess)
-            e = hipMemcpy(p->Aop, hA, sizeof hA, hipMemcpyHostToDevice);
+            e = hipMemcpy(dA, hA, sizeof hA, hipMemcpyHostToDevice);
+        if constexpr (F64)
+            p->Aop64 = dA;
+        else
+            p->Aop = dA;
         return static_cast<int>(e);
     }
 
@@ -1373,7 +1566,7 @@ namespace
             return static_cast<int>(e);
         (void)hipMemset(flag, 0, sizeof(int));
         const long long n_nodes = 256LL * d.n_domains;
-        hipLaunchKernelGGL(ddh_uniform_check_kernel, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, nullptr, n_nodes, 64, G, flag);
+        hipLaunchKernelGGL(ddh_uniform_check_kernel<float>, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, nullptr, n_nodes, 64, G, flag);
         int bad = 1;
         e = hipMemcpy(&bad, flag, sizeof(int), hipMemcpyDeviceToHost);
         (void)hipFree(flag);
@@ -1489,6 +1682,16 @@ namespace
                 return launch_status();
             }
         }
+        if (plan->kernel == 8)
+        {
+            if constexpr (sizeof(Real) == 8)
+            {
+                hipLaunchKernelGGL(ddh_mfma64_kernel, dim3((n_local + 3) / 4), dim3(256), 0, st, A, plan->Aop64,
+                                   static_cast<const double *>(d.wh_filter), static_cast<const double *>(d.cs), static_cast<const double *>(d.sn));
+                return launch_status();
+            }
+            return static_cast<int>(hipErrorInvalidValue); // unreachable: apply() checks the plan's precision first
+        }
         if (plan->kernel == 6 || plan->kernel == 7)
         {
             const dim3 grid((n_local + 7) / 8), block(256); // four wavefronts per workgroup, two subdomains per wavefront
@@ -1593,7 +1796,7 @@ extern "C"
     int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **out, const cuddh_ddh_desc *desc, int is_f64, int kernel)
     {
         *out = nullptr;
-        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || kernel < 0 || kernel > 7)
+        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || kernel < 0 || kernel > 8)
             return static_cast<int>(hipErrorInvalidValue);
         const int nodes = desc->nb * desc->nb * desc->nel1d * desc->nel1d;
         if (nodes > 256)
@@ -1607,7 +1810,8 @@ extern "C"
 
         const bool wave_shape = (desc->nb == 4 && desc->nel1d == 4);
         const bool wave8_shape = (desc->nb == 8 && desc->nel1d == 2);
-        if ((kernel >= 2 && kernel <= 5 && !wave_shape) || (kernel >= 6 && !wave8_shape) || (kernel == 7 && is_f64))
+        if ((kernel >= 2 && kernel <= 5 && !wave_shape) || ((kernel == 6 || kernel == 7) && !wave8_shape) || (kernel == 7 && is_f64) ||
+            (kernel == 8 && (!wave_shape || !is_f64)))
         {
             delete p;
             return static_cast<int>(hipErrorInvalidValue);
@@ -1660,7 +1864,7 @@ extern "C"
             // kernel 5 (dense element matrix on the matrix cores) needs fp32 and one metric tensor for all elements
             if (!bad && !is_f64 && (kernel == 0 || kernel == 5))
             {
-                int err5 = build_dense_element_matrix(p);
+                int err5 = build_dense_element_matrix<float>(p);
                 if (err5 == 0)
                     p->kernel = 5;
                 else if (kernel == 5)
@@ -1674,6 +1878,17 @@ extern "C"
                 delete p;
                 return static_cast<int>(hipErrorInvalidValue);
             }
+            // kernel 8 (kernel 5 in fp64) only on request: auto keeps fp64 on kernel 3
+            if (!bad && kernel == 8)
+            {
+                const int err8 = build_dense_element_matrix<double>(p);
+                if (err8 != 0)
+                {
+                    cuddh_hip_ddh_plan_destroy(p);
+                    return err8 > 0 ? err8 : static_cast<int>(hipErrorInvalidValue);
+                }
+                p->kernel = 8;
+            }
         }
         *out = p;
         return 0;
@@ -1683,6 +1898,8 @@ extern "C"
     {
         if (plan && plan->Aop)
             (void)hipFree(plan->Aop);
+        if (plan && plan->Aop64)
+            (void)hipFree(plan->Aop64);
         if (plan && plan->Sep)
             (void)hipFree(plan->Sep);
         delete plan;

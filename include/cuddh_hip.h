@@ -285,10 +285,13 @@ typedef struct cuddh_ddh_plan cuddh_ddh_plan;
  *             subdomains, registers + DPP over the eight lanes of a column octet,
  *         7 = 6 in separable form (fp32): on the rectangles of a uniform mesh the metric is diagonal and a product of
  *             1-D factors, so a sweep needs ONE 8x8 contraction per direction (D^T diag D precomputed) instead of two
- *             (plan_create verifies the geometry; what auto picks for nb == 8 when it applies). */
+ *             (plan_create verifies the geometry; what auto picks for nb == 8 when it applies),
+ *         8 = 5 in fp64 (four v_mfma_f64_16x16x4_f64 per sweep, element matrix formed and kept in double; is_f64, nb == 4
+ *             and nel1d == 4 only, same metric tensor in every element, which plan_create verifies on the device;
+ *             on request only: auto keeps fp64 on 3; hipErrorInvalidValue where it does not apply, like 5). */
 int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int is_f64, int kernel);
 int cuddh_hip_ddh_plan_destroy(cuddh_ddh_plan *plan);
-/* which kernel the plan resolved to (1..7) */
+/* which kernel the plan resolved to (1..8) */
 int cuddh_hip_ddh_plan_kernel(const cuddh_ddh_plan *plan);
 /* Numbering of the forcing x and the solution y of the NEXT apply calls: d_gI (mx_dof, n_domains) DEVICE replaces desc.gI and
  * g_ndof replaces desc.g_ndof for x and y (NULL restores the descriptor's).  With the identity numbering
