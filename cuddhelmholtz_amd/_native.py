@@ -159,6 +159,7 @@ _sig("cuddh_hip_ddh_geom_setup_f64", ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_geom_from_corners_f32", ci, ci, ci, vp, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_geom_from_corners_f64", ci, ci, ci, vp, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_create", ci, C.POINTER(vp), C.POINTER(DdhDesc), ci, ci)
+_sig("cuddh_hip_ddh_plan_create_general", ci, C.POINTER(vp), C.POINTER(DdhDesc), ci, ci, ci)
 _sig("cuddh_hip_ddh_plan_destroy", ci, vp)
 _sig("cuddh_hip_ddh_plan_kernel", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_wh_iters", ci, vp, ci)
@@ -232,6 +233,7 @@ _sig("cuddh_linear_functional", ci, vp, ci, ci, cd, cd, ci, vp)
 _sig("cuddh_face_linear_functional", ci, vp, ci, ci, cd, cd, ci, vp)
 _sig("cuddh_nodal_values", ci, vp, ci, cd, vp)
 _sig("cuddh_ddh_create", vp, cd, vp, vp, ci, ci, ci, ci)
+_sig("cuddh_ddh_create_labels", vp, cd, vp, vp, ci, vp, ci, ci)
 _sig("cuddh_ddh_destroy", None, vp)
 _sig("cuddh_ddh_size", ci, vp)
 _sig("cuddh_ddh_info", ci, vp, vp, vp)

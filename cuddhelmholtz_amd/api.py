@@ -411,7 +411,7 @@ class DDH:
     kernel selects the local-solve kernel (cuddh_hip_ddh_plan_create): 0 auto, 1 generic, 2 wavefront per subdomain,
     3 / 4 / 5 / 7 fp32 forms (5: dense element matrix on the matrix cores), 6 n_basis 8, 8 = kernel 5 in fp64
     (precision='f64', n_basis 4, uniform metric; never picked by auto).  Requested where it does not apply, 5 to 8 raise on
-    first use."""
+    first use.  DDH.from_labels builds the solver on any mesh from element labels (kernels 9 and 10)."""
 
     _INT_TABLES = ("B", "gI", "sI")
 
@@ -421,6 +421,31 @@ class DDH:
         h_a = np.ascontiguousarray(h_a, dtype=np.float64)
         self._h = N.handle(lib.cuddh_ddh_create(float(omega), _h(h_a), fem._h, nx, ny, int(self.f64), kernel), "DDH")
         self.omega = float(omega)
+
+    @classmethod
+    def from_labels(cls, omega: float, h_a: np.ndarray, fem: H1Space, labels, precision: str = "f32", kernel: int = 0) -> "DDH":
+        """DDH on any mesh with subdomain s = the elements labelled s (one label per element, e.g. Mesh2D.partition), labels in
+        [0, n_domains) with n_domains = max(labels) + 1; every subdomain non-empty with at most 256 element nodes.
+        kernel: 0 auto, 9 one wavefront per subdomain (n_basis 4, <= 16 elements per subdomain), 10 one workgroup per
+        subdomain.  info()["nel1d"] is 0.  Invalid labels or kernels raise here, before anything runs on the device."""
+        labels = np.ascontiguousarray(labels)
+        n_elem = fem.mesh.n_elem()
+        if labels.ndim != 1 or labels.size != n_elem:
+            raise ValueError(f"DDH.from_labels: {labels.size} labels for {n_elem} elements")
+        if not np.issubdtype(labels.dtype, np.integer):
+            raise ValueError("DDH.from_labels: labels must be integers")
+        if labels.size and (labels.min() < 0 or labels.max() >= 2**31 - 1):
+            raise ValueError(f"DDH.from_labels: label {int(labels.min()) if labels.min() < 0 else int(labels.max())} out of range")
+        n_domains = int(labels.max()) + 1 if labels.size else 0
+        labels = labels.astype(np.int32)
+        self = cls.__new__(cls)
+        self.fem = fem
+        self.f64 = precision == "f64"
+        h_a = np.ascontiguousarray(h_a, dtype=np.float64)
+        self._h = N.handle(lib.cuddh_ddh_create_labels(float(omega), _h(h_a), fem._h, n_domains, _h(labels), int(self.f64), int(kernel)),
+                           "DDH.from_labels")
+        self.omega = float(omega)
+        return self
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

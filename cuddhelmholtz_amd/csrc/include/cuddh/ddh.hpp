@@ -23,6 +23,13 @@ struct cuddh_ddh_plan;
 
 namespace cuddh
 {
+    /// tag of the constructors that take subdomains as element labels: DDH(from_labels, omega, h_a, fem, n_domains, labels)
+    struct from_labels_t
+    {
+        explicit constexpr from_labels_t() = default;
+    };
+    inline constexpr from_labels_t from_labels{};
+
     namespace detail
     {
         /// setup shared by DDH and DDH64 (scalar = float or double)
@@ -31,6 +38,9 @@ namespace cuddh
         {
         public:
             DDHCore(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel);
+            /// subdomain s = the elements with label s (HOST, one per element, in [0, n_domains)); any connectivity.
+            /// kernel: 0 auto, 9 or 10 (cuddh_hip_ddh_plan_create_general)
+            DDHCore(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel);
             ~DDHCore();
 
             int n_traces() const { return 2 * n_lambda; }
@@ -73,9 +83,13 @@ namespace cuddh
             const HostDeviceArray<Real> &table_sn() const { return _sn; }
             int max_dof() const { return mx_dof; }
             int max_fdof() const { return mx_fdof; }
+            /// elements per block side; 0 for subdomains built from labels
             int elems_per_side() const { return nel1d; }
+            bool label_built() const { return general; }
 
         private:
+            /// everything after the element labels (time grid, slots, renumbering, masses, H, a)
+            void setup(const double *h_a, const H1Space &fem, const int *labels);
             void solve_impl(const int *d_list, int d0, int d1, const double *x, double *y, bool zero_y, const Real *lambda, Real *update) const;
 
             /// device-side part of the set-up (geometric factors, kernel plan); deferred to first use so
@@ -89,6 +103,7 @@ namespace cuddh
             const Mesh2D *fem_mesh;
             const Basis *fem_basis;
             int requested_kernel = 0;
+            bool general = false; // subdomains from labels: cuddh_hip_ddh_plan_create_general
 
             host_device_ivec _Bf, _gI, _sI;
             HostDeviceArray<Real> _D, _m, _gmi, _H, _wh_filter, _cs, _sn, _a;
@@ -111,6 +126,10 @@ namespace cuddh
         /// extension: pick the local-solve kernel (0 auto, 1 generic workgroup, 2 wavefront-per-subdomain, 3-7 the fp32 forms of
         /// cuddh_hip_ddh_plan_create; 8 is fp64 only, see DDH64).  A requested kernel that does not apply throws on first use.
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel);
+        /// extension: subdomains of any shape on any Mesh2D, given as element labels (HOST, n_elem of them, in [0, n_domains),
+        /// every subdomain non-empty and with at most 256 element nodes).  kernel: 0 auto, 9 one wavefront per subdomain
+        /// (n_basis 4, <= 16 elements per subdomain), 10 one workgroup per subdomain.  Invalid labels throw here.
+        DDH(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel = 0);
         ~DDH() = default;
 
         /// dimension of the substructured problem
@@ -137,6 +156,8 @@ namespace cuddh
         /// kernel: 0 auto (3 for n_basis 4), 1 generic, 2 wavefront-per-subdomain, 6 n_basis 8, 8 = the dense element matrix on
         /// the fp64 matrix cores (n_basis 4, uniform metric; on request only).  See cuddh_hip_ddh_plan_create.
         DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel = 0);
+        /// subdomains from element labels, as DDH(from_labels, ...)
+        DDH64(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel = 0);
 
         int size() const { return core.n_traces(); }
 

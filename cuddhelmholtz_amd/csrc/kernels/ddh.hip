@@ -16,6 +16,7 @@
 //     with the field staged in LDS, 3 barriers per stiffness sweep.
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "common.hpp"
 
@@ -27,8 +28,8 @@ struct cuddh_ddh_plan
     int is_f64;
     int kernel; // 1 block, 2 wave, 3 wave with hand-folded DPP FMAs (fp32), 4 = 3 + MFMA for the in-lane contractions,
                 // 5 dense element matrix on the matrix cores (fp32, uniform geometry), 6 / 7 nb == 8 wave (7 separable, fp32),
-                // 8 = 5 in fp64
-    int nodes;  // nb*nb*nel1d*nel1d
+                // 8 = 5 in fp64, 9 general wave (nb == 4, <= 16 elements), 10 general workgroup (CSR lists)
+    int nodes;  // nb*nb*nel1d*nel1d (general plans: nb*nb*mx_elems)
     int wh_iters = 5; // WaveHoltz iterations per local solve (source/DDH.cpp:136); WH_ITERS_REFERENCE
     const int *gI_override = nullptr; // cuddh_hip_ddh_plan_set_vector_layout: x and y in another numbering than d.gI
     int g_ndof_override = 0;
@@ -36,6 +37,8 @@ struct cuddh_ddh_plan
     double *Aop64 = nullptr; // kernel 8: the same in fp64, rows in the f64 MFMA's output order (build_dense_element_matrix)
     float *Sep = nullptr; // kernel 7: [Ax | Ay | beta | gamma] of the separable nb = 8 sweep
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
+    // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
+    int *csr_off = nullptr, *csr_src = nullptr;
 };
 
 namespace
@@ -56,6 +59,10 @@ namespace
         const Real *lambda;
         Real *update;
         const int *dom_list; // null: positions [dom_begin, dom_end) ARE the subdomains; else subdomain = dom_list[position]
+        // general plans (kernels 9, 10): per subdomain, for each dof the element nodes that contribute to it in ascending order,
+        // CSR with fixed strides: csr_off (nodes + 1, n_domains), csr_src (nodes, n_domains)
+        const int *csr_off, *csr_src;
+        int unique_y; // != 0: y entries are written by one subdomain dof each (a vector layout is set): plain adds, no atomics
     };
 
     template <typename Real>
@@ -169,10 +176,10 @@ namespace
 
     // VAR 0: plain HIP; 1: DPP reads folded into the FMAs (fp32); 2: as 1, and the in-lane (eta) contractions run on the
     // matrix pipe as v_mfma_f32_4x4x1_16b_f32 (one 4x4 block per element, exact fp32 FMA chains), beside the VALU
+    // Element-local part of one stiffness sweep: zz[l] = (S_el w)(k, l) for the element of my quad (no assembly).
     template <int VAR, typename Real>
-    __device__ inline void wave_stiffness(const Real (&w)[4], Real (&z)[4], const Real (&gx)[4], const Real (&gy)[4], const Real (&gz)[4],
-                                          const Real (&Dk)[4], const Real (&DTk)[4], const Real *__restrict__ Dm, Real mR, Real mL,
-                                          Real mU, Real mD, int lane)
+    __device__ inline void wave_element_stiffness(const Real (&w)[4], Real (&zz)[4], const Real (&gx)[4], const Real (&gy)[4],
+                                                  const Real (&gz)[4], const Real (&Dk)[4], const Real (&DTk)[4], const Real *__restrict__ Dm)
     {
         constexpr bool ASM = VAR >= 1;
         Real ux[4], uy[4];
@@ -215,7 +222,6 @@ namespace
             f2[l] = gy[l] * ux[l] + gz[l] * uy[l];
         }
         // test functions: sum_i D(i,k) f1(i,l)  +  sum_i D(i,l) f2(k,i)
-        Real zz[4];
         if constexpr (ASM)
             quad_contract_asm(f1, DTk, zz);
         else
@@ -244,6 +250,16 @@ namespace
                 zz[l] = s;
             }
         }
+    }
+
+    template <int VAR, typename Real>
+    __device__ inline void wave_stiffness(const Real (&w)[4], Real (&z)[4], const Real (&gx)[4], const Real (&gy)[4], const Real (&gz)[4],
+                                          const Real (&Dk)[4], const Real (&DTk)[4], const Real *__restrict__ Dm, Real mR, Real mL,
+                                          Real mU, Real mD, int lane)
+    {
+        constexpr bool ASM = VAR >= 1;
+        Real zz[4];
+        wave_element_stiffness<VAR>(w, zz, gx, gy, gz, Dk, DTk, Dm);
         // assembly across elements.  xi neighbours: my k==3 column meets the k==0 column of lane+1 (and vice versa)
         if constexpr (ASM)
         {
@@ -421,6 +437,241 @@ namespace
                     const Real S = Real(2) * A.a[dbase + d] * A.omega;
                     A.update[wslot] = -lam - S * v[l];
                     A.update[A.n_lambda + wslot] = -mu + S * u[l];
+                }
+            }
+        }
+    }
+
+    // ---------------------------------------------------------------- kernel 9: wavefront per unstructured subdomain (NB = 4)
+    // Element-local part as kernel 3: lane = (element, xi-node) of up to 16 elements, the four eta-nodes of the lane's column
+    // in registers, DPP quad contractions.  The RK2 state stays per element node (copies of a shared dof hold bitwise equal
+    // values: every copy reads the same assembled sum and the same per-dof coefficients).  Assembly goes through wave-private
+    // LDS: every lane writes its four element contributions, then lane j forms the sums of dofs j, j + 64, j + 128, j + 192
+    // along the plan's CSR lists (ascending element node, any valence), then every node reads its dof's sum back through sI.
+    // A wavefront owns its subdomain, so the LDS phases are ordered by wave-level fences only (DS instructions of one
+    // wavefront execute in order; the fence keeps the compiler from moving them and makes it wait for the data).
+    constexpr int GW_NODES = 256; // element nodes (and dofs) per subdomain at most
+
+    __device__ inline void wave_lds_fence()
+    {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+
+    // LDS slot of element node (k, l, el): lane-major, so a lane's four contributions are contiguous
+    __device__ inline int gw_slot(int node) { return ((node >> 4) << 4) + ((node & 3) << 2) + ((node >> 2) & 3); }
+
+    template <typename Real>
+    __device__ inline void gw_assemble(const Real (&zz)[4], Real (&z)[4], Real *__restrict__ s_c, Real *__restrict__ s_d,
+                                       const int *__restrict__ s_src, const int (&st)[4], const int (&ct)[4], const int (&dof)[4], int lane)
+    {
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            s_c[4 * lane + l] = zz[l];
+        wave_lds_fence();
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+        {
+            Real sum = 0;
+            for (int c = 0; c < ct[j]; ++c)
+                sum += s_c[s_src[st[j] + c]];
+            s_d[lane + 64 * j] = sum;
+        }
+        wave_lds_fence();
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            z[l] = s_d[dof[l]];
+    }
+
+    template <typename Real, int VAR>
+    __global__ void __launch_bounds__(256) ddh_general_wave_kernel(DdhArgs<Real> A, const Real *__restrict__ Dmat, const Real *__restrict__ filt,
+                                                                  const Real *__restrict__ cs, const Real *__restrict__ sn)
+    {
+        __shared__ Real lds_c[4][GW_NODES], lds_d[4][GW_NODES];
+        __shared__ int lds_src[4][GW_NODES];
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int position = A.dom_begin + blockIdx.x * 4 + wave;
+        if (position >= A.dom_end)
+            return; // wave-uniform: the kernel has no workgroup barriers
+        const int s = domain_at(A, position);
+        raise_priority(A.prio);
+        Real *s_c = lds_c[wave], *s_d = lds_d[wave];
+        int *s_src = lds_src[wave];
+
+        const int T = A.nodes; // 16 * mx_elems <= 256: stride of sI, G and the CSR lists
+        const int k = lane & 3, el = lane >> 2;
+        const int ndof = A.s_dof[s], fdof = A.s_fdof[s];
+        const int *sI = A.sI + (size_t)T * s;
+        const int *off = A.csr_off + (size_t)(T + 1) * s;
+        const int *src = A.csr_src + (size_t)T * s;
+        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
+
+        // CSR lists: sources as LDS slots in LDS, (start, count) of my four dofs in registers
+        int st[4], ct[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+        {
+            const int d = lane + 64 * j;
+            st[j] = ct[j] = 0;
+            if (d < ndof)
+            {
+                st[j] = off[d];
+                ct[j] = off[d + 1] - st[j];
+            }
+            if (d < T)
+                s_src[d] = d < off[ndof] ? gw_slot(src[d]) : 0;
+        }
+
+        Real gx[4], gy[4], gz[4], invm[4], Hi[4], F[4], Gf[4];
+        Real p[4], q[4], u[4], v[4];
+        int dof[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+        {
+            const int node = k + 4 * (l + 4 * el);
+            const int d = node < T ? sI[node] : -1; // -1: no element here (padding of a smaller subdomain)
+            dof[l] = d < 0 ? 0 : d;
+            gx[l] = gy[l] = gz[l] = invm[l] = Hi[l] = F[l] = Gf[l] = 0;
+            p[l] = q[l] = u[l] = v[l] = 0;
+            if (d < 0)
+                continue;
+            const Real *g = A.G + 3 * ((size_t)node + (size_t)T * s);
+            gx[l] = g[0];
+            gy[l] = g[1];
+            gz[l] = g[2];
+            const Real ai = A.a[dbase + d], mi = A.m[dbase + d];
+            invm[l] = Real(1) / (ai * ai * mi);
+            Real f = 0, gg = 0, h = 0;
+            if (A.x)
+            {
+                const int gidx = A.gI[dbase + d];
+                f = static_cast<Real>(A.x[gidx]);
+                gg = static_cast<Real>(A.x[A.g_ndof + gidx]);
+            }
+            if (d < fdof)
+            {
+                h = A.H[fbase + d];
+                if (A.lambda)
+                {
+                    const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
+                    if (slot >= 0)
+                    {
+                        f += h * A.lambda[slot];
+                        gg += h * A.lambda[A.n_lambda + slot];
+                    }
+                }
+                h *= ai;
+            }
+            F[l] = f;
+            Gf[l] = gg;
+            Hi[l] = h;
+        }
+
+        Real Dk[4], DTk[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+        {
+            Dk[i] = Dmat[k + 4 * i];  // D(k, i)
+            DTk[i] = Dmat[i + 4 * k]; // D(i, k)
+        }
+        wave_lds_fence(); // s_src complete before the first assembly reads it
+
+        const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
+        const int nt = A.nt;
+
+        for (int whit = 0; whit < A.wh_iters; ++whit)
+        {
+            {
+                const Real k0 = filt[0];
+#pragma unroll
+                for (int l = 0; l < 4; ++l)
+                {
+                    p[l] = u[l];
+                    q[l] = v[l];
+                    u[l] *= k0;
+                    v[l] *= k0;
+                }
+            }
+            for (int it = 1; it <= nt; ++it)
+            {
+                const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                const Real c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                const Real kw = filt[it];
+                Real zz[4], z[4], ph[4], qh[4];
+
+                wave_element_stiffness<VAR>(p, zz, gx, gy, gz, Dk, DTk, Dmat);
+                gw_assemble(zz, z, s_c, s_d, s_src, st, ct, dof, lane);
+#pragma unroll
+                for (int l = 0; l < 4; ++l)
+                {
+                    const Real dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
+                    ph[l] = p[l] - half_dt * q[l];
+                    qh[l] = q[l] + half_dt * dq;
+                    p[l] -= dt * qh[l];
+                }
+                wave_element_stiffness<VAR>(ph, zz, gx, gy, gz, Dk, DTk, Dmat);
+                gw_assemble(zz, z, s_c, s_d, s_src, st, ct, dof, lane);
+#pragma unroll
+                for (int l = 0; l < 4; ++l)
+                {
+                    const Real dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
+                    q[l] += dt * dq;
+                    u[l] += kw * p[l];
+                    v[l] += kw * q[l];
+                }
+            }
+        }
+
+        // outputs per dof: the copy at the dof's first contributing element node publishes u, v
+        const Real rw = Real(1) / A.omega;
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+        {
+            s_c[4 * lane + l] = u[l];
+            s_d[4 * lane + l] = v[l] * rw;
+        }
+        wave_lds_fence();
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+        {
+            const int d = lane + 64 * j;
+            if (d >= ndof)
+                continue;
+            const int first = s_src[st[j]];
+            const Real U = s_c[first], V = s_d[first];
+            if (A.y)
+            {
+                const int gidx = A.gI[dbase + d];
+                const Real M = A.m[dbase + d] * A.gmi[dbase + d];
+                if (A.unique_y)
+                {
+                    A.y[gidx] += static_cast<double>(M * U);
+                    A.y[A.g_ndof + gidx] += static_cast<double>(M * V);
+                }
+                else
+                {
+                    atomic_add(A.y + gidx, static_cast<double>(M * U));
+                    atomic_add(A.y + A.g_ndof + gidx, static_cast<double>(M * V));
+                }
+            }
+            if (A.update && d < fdof)
+            {
+                const int wslot = A.B[d + (size_t)A.mx_fdof * (1 + 2 * (size_t)s)];
+                if (wslot >= 0)
+                {
+                    Real lam = 0, mu = 0;
+                    if (A.lambda)
+                    {
+                        const int rslot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
+                        if (rslot >= 0)
+                        {
+                            lam = A.lambda[rslot];
+                            mu = A.lambda[A.n_lambda + rslot];
+                        }
+                    }
+                    const Real S = Real(2) * A.a[dbase + d] * A.omega;
+                    A.update[wslot] = -lam - S * V;
+                    A.update[A.n_lambda + wslot] = -mu + S * U;
                 }
             }
         }
@@ -1236,7 +1487,8 @@ namespace
     }
 
     // ---------------------------------------------------------------- workgroup-per-subdomain kernel (generic)
-    template <typename Real, int NB>
+    // CSR = true is kernel 10: the contributor lists come from the plan (any valence) instead of being built with atomics.
+    template <typename Real, int NB, bool CSR = false>
     __global__ void __launch_bounds__(256) ddh_block_kernel(DdhArgs<Real> A, const Real *__restrict__ Dmat, const Real *__restrict__ filt,
                                                            const Real *__restrict__ cs, const Real *__restrict__ sn)
     {
@@ -1275,30 +1527,45 @@ namespace
         const Real g0 = active ? g[0] : Real(0), g1 = active ? g[1] : Real(0), g2 = active ? g[2] : Real(0);
 
         // who contributes to dof `tid`: element nodes in increasing order (fixed summation order)
-        s_cnt[tid] = 0;
-        __syncthreads();
-        if (active)
-        {
-            const int slot = atomicAdd(&s_cnt[mydof], 1);
-            if (slot < 4)
-                s_lst[4 * mydof + slot] = tid;
-        }
-        __syncthreads();
         int nc = 0, c[4] = {0, 0, 0, 0};
-        if (tid < ndof)
+        int c_first = 0; // CSR: my list is s_lst[c_first, c_first + nc)
+        if constexpr (CSR)
         {
-            nc = s_cnt[tid];
-            if (nc > 4)
-                __builtin_trap(); // more than four elements meet at a node: not a structured subdomain
-            for (int j = 0; j < nc; ++j)
-                c[j] = s_lst[4 * tid + j];
-            for (int a = 1; a < nc; ++a) // insertion sort of at most 4 entries
-                for (int b = a; b > 0 && c[b - 1] > c[b]; --b)
-                {
-                    const int t = c[b];
-                    c[b] = c[b - 1];
-                    c[b - 1] = t;
-                }
+            const int *off = A.csr_off + (size_t)(T + 1) * s;
+            if (tid < off[ndof])
+                s_lst[tid] = A.csr_src[(size_t)T * s + tid];
+            if (tid < ndof)
+            {
+                c_first = off[tid];
+                nc = off[tid + 1] - c_first;
+            }
+        }
+        else
+        {
+            s_cnt[tid] = 0;
+            __syncthreads();
+            if (active)
+            {
+                const int slot = atomicAdd(&s_cnt[mydof], 1);
+                if (slot < 4)
+                    s_lst[4 * mydof + slot] = tid;
+            }
+            __syncthreads();
+            if (tid < ndof)
+            {
+                nc = s_cnt[tid];
+                if (nc > 4)
+                    __builtin_trap(); // more than four elements meet at a node: not a structured subdomain
+                for (int j = 0; j < nc; ++j)
+                    c[j] = s_lst[4 * tid + j];
+                for (int a = 1; a < nc; ++a) // insertion sort of at most 4 entries
+                    for (int b = a; b > 0 && c[b - 1] > c[b]; --b)
+                    {
+                        const int t = c[b];
+                        c[b] = c[b - 1];
+                        c[b - 1] = t;
+                    }
+            }
         }
 
         // per-dof data
@@ -1358,8 +1625,12 @@ namespace
             s_su[tid] = Su;
             __syncthreads();
             Real z = 0;
-            for (int j = 0; j < nc; ++j)
-                z += s_su[c[j]];
+            if constexpr (CSR)
+                for (int j = 0; j < nc; ++j)
+                    z += s_su[s_lst[c_first + j]];
+            else
+                for (int j = 0; j < nc; ++j)
+                    z += s_su[c[j]];
             return z;
         };
 
@@ -1399,8 +1670,16 @@ namespace
         if (A.y && tid < ndof)
         {
             const Real M = mi * A.gmi[dbase + tid];
-            atomic_add(A.y + g_idx, static_cast<double>(M * u));
-            atomic_add(A.y + A.g_ndof + g_idx, static_cast<double>(M * v));
+            if (CSR && A.unique_y)
+            {
+                A.y[g_idx] += static_cast<double>(M * u);
+                A.y[A.g_ndof + g_idx] += static_cast<double>(M * v);
+            }
+            else
+            {
+                atomic_add(A.y + g_idx, static_cast<double>(M * u));
+                atomic_add(A.y + A.g_ndof + g_idx, static_cast<double>(M * v));
+            }
         }
         if (A.update && tid < fdof)
         {
@@ -1462,12 +1741,12 @@ namespace
         return launch_status();
     }
 
-    template <typename Real, int NB>
+    template <typename Real, int NB, bool CSR = false>
     void launch_block(const DdhArgs<Real> &A, const cuddh_ddh_desc &d, int n_local, hipStream_t st)
     {
         const int T = A.nodes;
         const size_t lds = (size_t)T * (4 * sizeof(Real) + 5 * sizeof(int));
-        hipLaunchKernelGGL((ddh_block_kernel<Real, NB>), dim3(n_local), dim3(T), lds, st, A, static_cast<const Real *>(d.D),
+        hipLaunchKernelGGL((ddh_block_kernel<Real, NB, CSR>), dim3(n_local), dim3(T), lds, st, A, static_cast<const Real *>(d.D),
                            static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs), static_cast<const Real *>(d.sn));
     }
 
@@ -1672,7 +1951,35 @@ namespace
         A.y = y;
         A.lambda = lambda;
         A.update = update;
+        A.csr_off = plan->csr_off;
+        A.csr_src = plan->csr_src;
+        A.unique_y = plan->gI_override ? 1 : 0;
 
+        if (plan->kernel == 9)
+        {
+            constexpr int var = sizeof(Real) == 4 ? 1 : 0; // folded-DPP contractions in fp32, the plain form in fp64
+            hipLaunchKernelGGL((ddh_general_wave_kernel<Real, var>), dim3((n_local + 3) / 4), dim3(256), 0, st, A,
+                               static_cast<const Real *>(d.D), static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs),
+                               static_cast<const Real *>(d.sn));
+            return launch_status();
+        }
+        if (plan->kernel == 10)
+        {
+            switch (d.nb)
+            {
+            case 2: launch_block<Real, 2, true>(A, d, n_local, st); break;
+            case 3: launch_block<Real, 3, true>(A, d, n_local, st); break;
+            case 4: launch_block<Real, 4, true>(A, d, n_local, st); break;
+            case 5: launch_block<Real, 5, true>(A, d, n_local, st); break;
+            case 6: launch_block<Real, 6, true>(A, d, n_local, st); break;
+            case 7: launch_block<Real, 7, true>(A, d, n_local, st); break;
+            case 8: launch_block<Real, 8, true>(A, d, n_local, st); break;
+            case 9: launch_block<Real, 9, true>(A, d, n_local, st); break;
+            case 10: launch_block<Real, 10, true>(A, d, n_local, st); break;
+            default: return static_cast<int>(hipErrorInvalidValue);
+            }
+            return launch_status();
+        }
         if (plan->kernel == 5)
         {
             if constexpr (sizeof(Real) == 4)
@@ -1894,8 +2201,85 @@ extern "C"
         return 0;
     }
 
+    int cuddh_hip_ddh_plan_create_general(cuddh_ddh_plan **out, const cuddh_ddh_desc *desc, int mx_elems, int is_f64, int kernel)
+    {
+        if (!out)
+            return static_cast<int>(hipErrorInvalidValue);
+        *out = nullptr;
+        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->n_domains < 1 || mx_elems < 1 || mx_elems > 256 ||
+            (kernel != 0 && kernel != 9 && kernel != 10))
+            return static_cast<int>(hipErrorInvalidValue);
+        const int nb = desc->nb, nodes = nb * nb * mx_elems;
+        if (nodes > GW_NODES || desc->mx_dof > nodes || desc->mx_fdof > desc->mx_dof)
+            return static_cast<int>(hipErrorInvalidValue);
+        const bool wave_fits = nb == 4 && mx_elems <= 16;
+        if (kernel == 9 && !wave_fits)
+            return static_cast<int>(hipErrorInvalidValue);
+
+        // assembly lists from sI, checked entry by entry on the host: nothing the kernels index with is left unchecked
+        const int nd = desc->n_domains;
+        std::vector<int> sI((size_t)nodes * nd), s_dof(nd), s_fdof(nd);
+        hipError_t e = hipMemcpy(sI.data(), desc->sI, sizeof(int) * sI.size(), hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            e = hipMemcpy(s_dof.data(), desc->s_dof, sizeof(int) * nd, hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            e = hipMemcpy(s_fdof.data(), desc->s_fdof, sizeof(int) * nd, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return static_cast<int>(e);
+        std::vector<int> off((size_t)(nodes + 1) * nd, 0), src((size_t)nodes * nd, 0);
+        for (int s = 0; s < nd; ++s)
+        {
+            const int ndof = s_dof[s];
+            if (ndof < 1 || ndof > desc->mx_dof || s_fdof[s] < 0 || s_fdof[s] > ndof || s_fdof[s] > desc->mx_fdof)
+                return static_cast<int>(hipErrorInvalidValue);
+            const int *I = sI.data() + (size_t)nodes * s;
+            int *o = off.data() + (size_t)(nodes + 1) * s, *c = src.data() + (size_t)nodes * s;
+            for (int n = 0; n < nodes; ++n)
+            {
+                if (I[n] < -1 || I[n] >= ndof)
+                    return static_cast<int>(hipErrorInvalidValue);
+                if (I[n] >= 0)
+                    ++o[I[n] + 1];
+            }
+            for (int dd = 0; dd < nodes; ++dd)
+            {
+                if (dd < ndof && o[dd + 1] == 0)
+                    return static_cast<int>(hipErrorInvalidValue); // a dof no element node maps to
+                o[dd + 1] += o[dd];
+            }
+            std::vector<int> fill(o, o + nodes);
+            for (int n = 0; n < nodes; ++n) // ascending element node: the summation order of kernel 1
+                if (I[n] >= 0)
+                    c[fill[I[n]]++] = n;
+        }
+
+        cuddh_ddh_plan *p = new cuddh_ddh_plan;
+        p->d = *desc;
+        p->is_f64 = is_f64 ? 1 : 0;
+        p->nodes = nodes;
+        p->kernel = (kernel == 9 || (kernel == 0 && wave_fits)) ? 9 : 10;
+        e = hipMalloc(reinterpret_cast<void **>(&p->csr_off), sizeof(int) * off.size());
+        if (e == hipSuccess)
+            e = hipMalloc(reinterpret_cast<void **>(&p->csr_src), sizeof(int) * src.size());
+        if (e == hipSuccess)
+            e = hipMemcpy(p->csr_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpy(p->csr_src, src.data(), sizeof(int) * src.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+        {
+            cuddh_hip_ddh_plan_destroy(p);
+            return static_cast<int>(e);
+        }
+        *out = p;
+        return 0;
+    }
+
     int cuddh_hip_ddh_plan_destroy(cuddh_ddh_plan *plan)
     {
+        if (plan && plan->csr_off)
+            (void)hipFree(plan->csr_off);
+        if (plan && plan->csr_src)
+            (void)hipFree(plan->csr_src);
         if (plan && plan->Aop)
             (void)hipFree(plan->Aop);
         if (plan && plan->Aop64)

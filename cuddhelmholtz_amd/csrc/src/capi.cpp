@@ -607,6 +607,27 @@ extern "C"
             return h;
         });
     }
+    void *cuddh_ddh_create_labels(double omega, const double *h_a, void *fem, int n_domains, const int *h_labels, int f64, int kernel)
+    {
+        return guarded_new<DdhHandle>([&]
+        {
+            auto h = new DdhHandle;
+            const H1Space &f = *static_cast<H1Space *>(fem);
+            try
+            {
+                if (f64)
+                    h->f64.reset(new DDH64(from_labels, omega, h_a, f, n_domains, h_labels, kernel));
+                else
+                    h->f32.reset(new DDH(from_labels, omega, h_a, f, n_domains, h_labels, kernel));
+            }
+            catch (...)
+            {
+                delete h;
+                throw;
+            }
+            return h;
+        });
+    }
     void cuddh_ddh_destroy(void *d) { delete static_cast<DdhHandle *>(d); }
     int cuddh_ddh_size(void *d)
     {

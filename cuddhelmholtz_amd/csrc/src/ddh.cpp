@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -50,7 +51,6 @@ namespace cuddh
             if (nx * ny != g_elem)
                 cuddh_error("DDH error: nx * ny does not match the mesh.");
 
-            PhaseTimer timer;
             const int ndx = nx / nel1d, ndy = ny / nel1d;
             n_domains = ndx * ndy;
             std::vector<int> labels(static_cast<std::size_t>(nx) * ny);
@@ -60,8 +60,57 @@ namespace cuddh
                     for (int i = 0; i < nx; ++i)
                         labels[i + static_cast<std::size_t>(nx) * j] = (i / nel1d) + ndx * (j / nel1d);
             }, 8);
+            setup(h_a, fem, labels.data());
+            requested_kernel = kernel;
+        }
 
-            efem.reset(new EnsembleSpace(fem, n_domains, labels.data()));
+        template <typename Real>
+        DDHCore<Real>::DDHCore(from_labels_t, double omega_, const double *h_a, const H1Space &fem, int n_domains_, const int *labels,
+                               int kernel)
+            : g_ndof(fem.size()), g_elem(fem.mesh().n_elem()), n_basis(fem.basis().size()), n_domains(n_domains_), nel1d(0),
+              omega(omega_), fem_mesh(&fem.mesh()), fem_basis(&fem.basis()), requested_kernel(kernel), general(true)
+        {
+            // everything is checked here, on the host, before anything is allocated or launched
+            const int nb = n_basis;
+            if (nb < 2 || nb > 10)
+                cuddh_error("DDH error: subdomains from labels need n_basis in [2, 10].");
+            if (n_domains < 1)
+                cuddh_error("DDH error: n_domains must be at least 1.");
+            if (!labels)
+                cuddh_error("DDH error: no element labels.");
+            std::vector<int> count(n_domains, 0);
+            for (int el = 0; el < g_elem; ++el)
+            {
+                const int s = labels[el];
+                if (s < 0 || s >= n_domains)
+                    cuddh_error(("DDH error: element " + std::to_string(el) + " has label " + std::to_string(s) + ", outside [0, " +
+                                 std::to_string(n_domains) + ").").c_str());
+                ++count[s];
+            }
+            int mx_elems = 0;
+            for (int s = 0; s < n_domains; ++s)
+            {
+                if (count[s] == 0)
+                    cuddh_error(("DDH error: subdomain " + std::to_string(s) + " has no elements.").c_str());
+                if (nb * nb * count[s] > 256)
+                    cuddh_error(("DDH error: subdomain " + std::to_string(s) + " has " + std::to_string(nb * nb * count[s]) +
+                                 " element nodes (n_basis^2 * " + std::to_string(count[s]) + " elements); at most 256 fit one local solve.")
+                                    .c_str());
+                mx_elems = std::max(mx_elems, count[s]);
+            }
+            if (kernel != 0 && kernel != 9 && kernel != 10)
+                cuddh_error("DDH error: subdomains from labels run kernel 9 or 10 (0 = auto); kernels 1-8 need the block grid.");
+            if (kernel == 9 && (nb != 4 || mx_elems > 16))
+                cuddh_error("DDH error: kernel 9 needs n_basis 4 and at most 16 elements per subdomain.");
+            setup(h_a, fem, labels);
+        }
+
+        template <typename Real>
+        void DDHCore<Real>::setup(const double *h_a, const H1Space &fem, const int *labels)
+        {
+            const int nb = n_basis;
+            PhaseTimer timer;
+            efem.reset(new EnsembleSpace(fem, n_domains, labels));
             timer.lap("EnsembleSpace");
 
             // ---- WaveHoltz time grid: dt = 0.1 h / nb^2 shrunk so that nt dt is one period
@@ -133,6 +182,7 @@ namespace cuddh
             auto gI = reshape(_gI.host_write(), mx_dof, n_domains);
             _sI.resize(nb * nb * mx_elem_per_dom * n_domains);
             auto sI = reshape(_sI.host_write(), nb, nb, mx_elem_per_dom, n_domains);
+            std::fill(sI.begin(), sI.end(), -1); // element nodes past a smaller subdomain's elements
 
             parallel_for(static_cast<std::size_t>(n_domains), [&](std::size_t s0, std::size_t s1, int)
             {
@@ -292,7 +342,6 @@ namespace cuddh
             }, 16);
 
             timer.lap("lumped masses, H, a");
-            requested_kernel = kernel;
         }
 
         template <typename Real>
@@ -355,8 +404,11 @@ namespace cuddh
             d.sn = _sn.device_read();
             check_hip(cuddh_hip_stream_sync(stream()), "DDH table upload");
             timer.lap("plan: table uploads");
-            check_hip(cuddh_hip_ddh_plan_create(&plan, &d, std::is_same_v<Real, double> ? 1 : 0, requested_kernel),
-                      "DDH plan");
+            const int is_f64 = std::is_same_v<Real, double> ? 1 : 0;
+            if (general)
+                check_hip(cuddh_hip_ddh_plan_create_general(&plan, &d, mx_elem_per_dom, is_f64, requested_kernel), "DDH plan");
+            else
+                check_hip(cuddh_hip_ddh_plan_create(&plan, &d, is_f64, requested_kernel), "DDH plan");
             timer.lap("plan: structure check + kernel tables");
         }
 
@@ -501,6 +553,11 @@ namespace cuddh
     {
     }
 
+    DDH::DDH(from_labels_t tag, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel)
+        : core(tag, omega, h_a, fem, n_domains, labels, kernel)
+    {
+    }
+
     void DDH::action(const float *x, float *y) const
     {
         core.solve(0, core.num_domains(), nullptr, nullptr, false, x, y);
@@ -528,6 +585,11 @@ namespace cuddh
 
     DDH64::DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel)
         : core(omega, h_a, fem, nx, ny, kernel)
+    {
+    }
+
+    DDH64::DDH64(from_labels_t tag, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel)
+        : core(tag, omega, h_a, fem, n_domains, labels, kernel)
     {
     }
 

@@ -116,6 +116,11 @@ int cuddh_nodal_values(void *fem, int integrand, double param, double *out);
 /* h_a HOST nodal coefficient; f64 != 0 selects the fp64 parity variant (double traces);
  * kernel: 0 auto, 1 workgroup-per-subdomain, 2 wavefront-per-subdomain, 3 wavefront with DPP-folded FMAs */
 void *cuddh_ddh_create(double omega, const double *h_a, void *fem, int nx, int ny, int f64, int kernel);
+/* subdomains from element labels on any mesh: h_labels HOST (n_elem), label of every element in [0, n_domains), no empty
+ * subdomain, at most 256 element nodes per subdomain (checked before anything is allocated; NULL + cuddh_last_error otherwise).
+ * kernel: 0 auto, 9 one wavefront per subdomain (n_basis 4, <= 16 elements), 10 one workgroup per subdomain
+ * (cuddh_hip_ddh_plan_create_general).  cuddh_ddh_info reports nel1d = 0. */
+void *cuddh_ddh_create_labels(double omega, const double *h_a, void *fem, int n_domains, const int *h_labels, int f64, int kernel);
 void cuddh_ddh_destroy(void *ddh);
 int cuddh_ddh_size(void *ddh);
 /* h_info = {n_domains, nt, n_lambda, mx_dof, mx_fdof, nel1d, kernel (needs a GPU; -1 if none), is_f64}; *h_dt = time step */

@@ -290,6 +290,20 @@ typedef struct cuddh_ddh_plan cuddh_ddh_plan;
  *             and nel1d == 4 only, same metric tensor in every element, which plan_create verifies on the device;
  *             on request only: auto keeps fp64 on 3; hipErrorInvalidValue where it does not apply, like 5). */
 int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int is_f64, int kernel);
+/* Plan for subdomains of ANY element connectivity (subdomains given by element labels; desc->nel1d is ignored and
+ * should be 0).  mx_elems: elements per subdomain at most, the third extent of desc->sI and the stride of desc->G;
+ * nb*nb*mx_elems <= 256.  Element nodes past a subdomain's elements have sI == -1.  The plan builds, once and on the host,
+ * the assembly lists in CSR form: for each subdomain dof the element nodes that contribute to it, in ascending element-node
+ * order (the summation order of kernel 1), with no cap on how many elements meet at a node.  Tables the plan cannot hold
+ * (an sI entry out of range, a dof no element node maps to, sizes past the leading dimensions) are rejected here with
+ * hipErrorInvalidValue, never inside a kernel.  Allocates and synchronises.
+ * kernel: 0 = auto (9 when nb == 4 and mx_elems <= 16, else 10),
+ *         9 = one wavefront per subdomain (nb == 4, <= 16 elements): kernel 3's element-local part (DPP quad contractions;
+ *             folded into v_fmac_f32_dpp in fp32), assembly through wave-private LDS along the CSR lists,
+ *         10 = one workgroup per subdomain (kernel 1's LDS scheme) summing along the CSR lists (any 2 <= nb <= 10).
+ * Kernels 1-8 are not available on a general plan (hipErrorInvalidValue).  The apply entry points below take general
+ * plans unchanged. */
+int cuddh_hip_ddh_plan_create_general(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int mx_elems, int is_f64, int kernel);
 int cuddh_hip_ddh_plan_destroy(cuddh_ddh_plan *plan);
 /* which kernel the plan resolved to (1..8) */
 int cuddh_hip_ddh_plan_kernel(const cuddh_ddh_plan *plan);
