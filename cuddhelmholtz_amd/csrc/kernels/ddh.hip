@@ -14,6 +14,21 @@
 //     storage, no barriers, 25,600 time steps per launch;
 //   * `ddh_block_kernel` (any n_basis <= 10) runs one subdomain per workgroup
 //     with the field staged in LDS, 3 barriers per stiffness sweep.
+//
+// Shape of the file: every local solve is  load_dof (per-dof coefficients)  ->
+// wh_march (the WaveHoltz / RK2 time stepping around a callable `sweep(w, z)`,
+// z = S w)  ->  publish_dof (y and the trace update).  All five wavefront kernels
+// use load_dof.  ddh_wave8_kernel and ddh_mfma_kernel<Real> use wh_march and
+// publish_dof too and are a lane map, a sweep and an owner rule (which of the
+// copies of a shared node publishes).  ddh_wave_kernel keeps a copy of wh_march's
+// loop and of publish_dof's body (on the shared ones it measured slower), and
+// ddh_general_wave_kernel a copy of the loop (through a callable sweep it was
+// not bitwise); see there.  ddh_block_kernel holds one value per
+// thread and publishes the field to LDS before each sweep, with barriers inside
+// it: its time loop has another shape and stays its own, and so do its load and
+// publish, which keep a, m, gI and lambda in registers from one to the other
+// (on the shared pair it re-reads them and compiles to different code); its
+// CSR form (kernel 10) therefore has its own unique_y branch beside publish_dof's.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -26,9 +41,10 @@ struct cuddh_ddh_plan
 {
     cuddh_ddh_desc d;
     int is_f64;
-    int kernel; // 1 block, 2 wave, 3 wave with hand-folded DPP FMAs (fp32), 4 = 3 + MFMA for the in-lane contractions,
-                // 5 dense element matrix on the matrix cores (fp32, uniform geometry), 6 / 7 nb == 8 wave (7 separable, fp32),
-                // 8 = 5 in fp64, 9 general wave (nb == 4, <= 16 elements), 10 general workgroup (CSR lists)
+    int kernel; // which sweep:  1 ddh_block_kernel;  2 / 3 / 4 ddh_wave_kernel<Real, 0 / 1 / 2> (plain; hand-folded DPP FMAs, fp32;
+                // 3 + MFMA for the in-lane contractions);  5 / 8 ddh_mfma_kernel<float / double> (dense element matrix on the matrix
+                // cores, uniform geometry);  6 / 7 ddh_wave8_kernel (nb == 8; 7 separable, fp32);  9 ddh_general_wave_kernel
+                // (nb == 4, <= 16 elements, CSR lists);  10 ddh_block_kernel with CSR lists
     int nodes;  // nb*nb*nel1d*nel1d (general plans: nb*nb*mx_elems)
     int wh_iters = 5; // WaveHoltz iterations per local solve (source/DDH.cpp:136); WH_ITERS_REFERENCE
     const int *gI_override = nullptr; // cuddh_hip_ddh_plan_set_vector_layout: x and y in another numbering than d.gI
@@ -79,6 +95,142 @@ namespace
     {
         if (prio)
             __builtin_amdgcn_s_setprio(3);
+    }
+
+    // ---------------------------------------------------------------- the local solve around the sweep (shared by all kernels)
+    // Coefficients of dof d of subdomain s: invm = 1 / (a^2 m), the sources F, Gf = x (+ H lambda through B on the trace dofs
+    // d < fdof), Hi = H a.
+    template <typename Real>
+    __device__ inline void load_dof(const DdhArgs<Real> &A, int s, int d, int fdof, Real &invm, Real &Hi, Real &F, Real &Gf)
+    {
+        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
+        const Real ai = A.a[dbase + d], mi = A.m[dbase + d];
+        invm = Real(1) / (ai * ai * mi);
+        Real f = 0, gg = 0, h = 0;
+        if (A.x)
+        {
+            const int gidx = A.gI[dbase + d];
+            f = static_cast<Real>(A.x[gidx]);
+            gg = static_cast<Real>(A.x[A.g_ndof + gidx]);
+        }
+        if (d < fdof)
+        {
+            h = A.H[fbase + d];
+            if (A.lambda)
+            {
+                const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
+                if (slot >= 0)
+                {
+                    f += h * A.lambda[slot];
+                    gg += h * A.lambda[A.n_lambda + slot];
+                }
+            }
+            h *= ai;
+        }
+        F = f;
+        Gf = gg;
+        Hi = h;
+    }
+
+    // The WaveHoltz iterations of one local solve for the N values a lane owns: wh_iters x (restart from the filtered field,
+    // nt RK2 steps with two stiffness sweeps z = S w each, filter accumulation).  Returns the filter sums u, v (v not yet
+    // divided by omega: publish_dof does that).  -ffp-contract=fast turns the shape of these expressions into FMAs: keep it.
+    template <typename Real, int N, typename Sweep>
+    __device__ inline void wh_march(const DdhArgs<Real> &A, const Real *__restrict__ filt, const Real *__restrict__ cs,
+                                    const Real *__restrict__ sn, const Real (&invm)[N], const Real (&Hi)[N], const Real (&F)[N],
+                                    const Real (&Gf)[N], Real (&u)[N], Real (&v)[N], Sweep sweep)
+    {
+        Real p[N], q[N];
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+            p[l] = q[l] = u[l] = v[l] = 0;
+        const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
+        const int nt = A.nt;
+        for (int whit = 0; whit < A.wh_iters; ++whit)
+        {
+            {
+                const Real k0 = filt[0];
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    p[l] = u[l];
+                    q[l] = v[l];
+                    u[l] *= k0;
+                    v[l] *= k0;
+                }
+            }
+            for (int it = 1; it <= nt; ++it)
+            {
+                const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                const Real c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                const Real kw = filt[it];
+                Real z[N], ph[N], qh[N];
+
+                sweep(p, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    const Real dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
+                    ph[l] = p[l] - half_dt * q[l];
+                    qh[l] = q[l] + half_dt * dq;
+                    p[l] -= dt * qh[l];
+                }
+                sweep(ph, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    const Real dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
+                    q[l] += dt * dq;
+                    u[l] += kw * p[l];
+                    v[l] += kw * q[l];
+                }
+            }
+        }
+    }
+
+    // Outputs of dof d of subdomain s from its filter sums u, v:  v /= omega,  y += M (u, v)  and, on the trace dofs, the
+    // update -lambda -+ 2 a omega (v, u) through B.  unique_y: no other subdomain dof adds to these y entries (a vector layout
+    // is set and the kernel honours it), so plain adds do; everything else adds atomically.
+    template <typename Real>
+    __device__ inline void publish_dof(const DdhArgs<Real> &A, int s, int d, int fdof, Real u, Real v, bool unique_y)
+    {
+        const size_t dbase = (size_t)A.mx_dof * s;
+        v *= Real(1) / A.omega;
+        if (A.y)
+        {
+            const int gidx = A.gI[dbase + d];
+            const Real M = A.m[dbase + d] * A.gmi[dbase + d];
+            if (unique_y)
+            {
+                A.y[gidx] += static_cast<double>(M * u);
+                A.y[A.g_ndof + gidx] += static_cast<double>(M * v);
+            }
+            else
+            {
+                atomic_add(A.y + gidx, static_cast<double>(M * u));
+                atomic_add(A.y + A.g_ndof + gidx, static_cast<double>(M * v));
+            }
+        }
+        if (A.update && d < fdof)
+        {
+            const int wslot = A.B[d + (size_t)A.mx_fdof * (1 + 2 * (size_t)s)];
+            if (wslot >= 0)
+            {
+                Real lam = 0, mu = 0;
+                if (A.lambda)
+                {
+                    const int rslot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
+                    if (rslot >= 0)
+                    {
+                        lam = A.lambda[rslot];
+                        mu = A.lambda[A.n_lambda + rslot];
+                    }
+                }
+                const Real S = Real(2) * A.a[dbase + d] * A.omega;
+                A.update[wslot] = -lam - S * v;
+                A.update[A.n_lambda + wslot] = -mu + S * u;
+            }
+        }
     }
 
     // ---------------------------------------------------------------- DPP helpers
@@ -303,10 +455,9 @@ namespace
         const int k = lane & 3, el = lane >> 2, ex = el & 3, ey = el >> 2;
         const int fdof = A.s_fdof[s];
         const int *sI = A.sI + 256 * (size_t)s;
-        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
+        const size_t dbase = (size_t)A.mx_dof * s;
 
-        Real gx[4], gy[4], gz[4], invm[4], Hi[4], F[4], Gf[4];
-        Real p[4], q[4], u[4], v[4];
+        Real gx[4], gy[4], gz[4], invm[4], Hi[4], F[4], Gf[4], u[4], v[4];
 #pragma unroll
         for (int l = 0; l < 4; ++l)
         {
@@ -316,33 +467,7 @@ namespace
             gx[l] = g[0];
             gy[l] = g[1];
             gz[l] = g[2];
-            const Real ai = A.a[dbase + d], mi = A.m[dbase + d];
-            invm[l] = Real(1) / (ai * ai * mi);
-            Real f = 0, gg = 0, h = 0;
-            if (A.x)
-            {
-                const int gidx = A.gI[dbase + d];
-                f = static_cast<Real>(A.x[gidx]);
-                gg = static_cast<Real>(A.x[A.g_ndof + gidx]);
-            }
-            if (d < fdof)
-            {
-                h = A.H[fbase + d];
-                if (A.lambda)
-                {
-                    const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                    if (slot >= 0)
-                    {
-                        f += h * A.lambda[slot];
-                        gg += h * A.lambda[A.n_lambda + slot];
-                    }
-                }
-                h *= ai;
-            }
-            F[l] = f;
-            Gf[l] = gg;
-            Hi[l] = h;
-            p[l] = q[l] = u[l] = v[l] = 0;
+            load_dof(A, s, d, fdof, invm[l], Hi[l], F[l], Gf[l]);
         }
 
         Real Dk[4], DTk[4];
@@ -357,6 +482,17 @@ namespace
         const Real mU = (ey < 3) ? Real(1) : Real(0);
         const Real mD = (ey > 0) ? Real(1) : Real(0);
 
+        // A copy of wh_march's loop, and below it of publish_dof's body.  On wh_march (sweep as a callable) the results stay
+        // bitwise but the compiler schedules the time loop differently, and the folded-DPP form (kernel 3, what auto picks on
+        // non-uniform geometry) measured 0.6 % slower than before in five of five alternating rounds, against 0.2 % spread;
+        // with the loop written out and publish_dof, the loop's instructions are the previous ones but the registers are not,
+        // and kernel 4 measured 0.5 % slower in three of three rounds against 0.1 % (profiles/r06/ddh_rates_ab.txt).  As it
+        // stands all four instantiations compile to the previous assembly text, registers included.  Any change to wh_march
+        // or publish_dof is made here as well (and, for wh_march, in ddh_general_wave_kernel).
+        Real p[4], q[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            p[l] = q[l] = u[l] = v[l] = 0;
         const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
         const int nt = A.nt;
 
@@ -504,7 +640,6 @@ namespace
         const int *sI = A.sI + (size_t)T * s;
         const int *off = A.csr_off + (size_t)(T + 1) * s;
         const int *src = A.csr_src + (size_t)T * s;
-        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
 
         // CSR lists: sources as LDS slots in LDS, (start, count) of my four dofs in registers
         int st[4], ct[4];
@@ -539,32 +674,7 @@ namespace
             gx[l] = g[0];
             gy[l] = g[1];
             gz[l] = g[2];
-            const Real ai = A.a[dbase + d], mi = A.m[dbase + d];
-            invm[l] = Real(1) / (ai * ai * mi);
-            Real f = 0, gg = 0, h = 0;
-            if (A.x)
-            {
-                const int gidx = A.gI[dbase + d];
-                f = static_cast<Real>(A.x[gidx]);
-                gg = static_cast<Real>(A.x[A.g_ndof + gidx]);
-            }
-            if (d < fdof)
-            {
-                h = A.H[fbase + d];
-                if (A.lambda)
-                {
-                    const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                    if (slot >= 0)
-                    {
-                        f += h * A.lambda[slot];
-                        gg += h * A.lambda[A.n_lambda + slot];
-                    }
-                }
-                h *= ai;
-            }
-            F[l] = f;
-            Gf[l] = gg;
-            Hi[l] = h;
+            load_dof(A, s, d, fdof, invm[l], Hi[l], F[l], Gf[l]);
         }
 
         Real Dk[4], DTk[4];
@@ -576,6 +686,12 @@ namespace
         }
         wave_lds_fence(); // s_src complete before the first assembly reads it
 
+        // A second copy of wh_march's loop.  With this kernel's sweep as a callable, -ffp-contract=fast fuses the other of the
+        // two products of gx ux + gy uy in wave_element_stiffness and the results move in the last bits (on the GPU against the
+        // commit before: 16 of 225 output arrays, all kernel 9's; with this copy 225 of 225 are bitwise equal,
+        // profiles/r06/ddh_bitwise_vs_parent.txt).  Writing the FMA out in wave_element_stiffness does not settle it: the form
+        // the compiler picks here is not the one it picks for ddh_wave_kernel, so one explicit form moves one of the two.
+        // Any change to wh_march is made here and in ddh_wave_kernel as well.
         const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
         const int nt = A.nt;
 
@@ -623,12 +739,11 @@ namespace
         }
 
         // outputs per dof: the copy at the dof's first contributing element node publishes u, v
-        const Real rw = Real(1) / A.omega;
 #pragma unroll
         for (int l = 0; l < 4; ++l)
         {
             s_c[4 * lane + l] = u[l];
-            s_d[4 * lane + l] = v[l] * rw;
+            s_d[4 * lane + l] = v[l];
         }
         wave_lds_fence();
 #pragma unroll
@@ -638,42 +753,7 @@ namespace
             if (d >= ndof)
                 continue;
             const int first = s_src[st[j]];
-            const Real U = s_c[first], V = s_d[first];
-            if (A.y)
-            {
-                const int gidx = A.gI[dbase + d];
-                const Real M = A.m[dbase + d] * A.gmi[dbase + d];
-                if (A.unique_y)
-                {
-                    A.y[gidx] += static_cast<double>(M * U);
-                    A.y[A.g_ndof + gidx] += static_cast<double>(M * V);
-                }
-                else
-                {
-                    atomic_add(A.y + gidx, static_cast<double>(M * U));
-                    atomic_add(A.y + A.g_ndof + gidx, static_cast<double>(M * V));
-                }
-            }
-            if (A.update && d < fdof)
-            {
-                const int wslot = A.B[d + (size_t)A.mx_fdof * (1 + 2 * (size_t)s)];
-                if (wslot >= 0)
-                {
-                    Real lam = 0, mu = 0;
-                    if (A.lambda)
-                    {
-                        const int rslot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                        if (rslot >= 0)
-                        {
-                            lam = A.lambda[rslot];
-                            mu = A.lambda[A.n_lambda + rslot];
-                        }
-                    }
-                    const Real S = Real(2) * A.a[dbase + d] * A.omega;
-                    A.update[wslot] = -lam - S * V;
-                    A.update[A.n_lambda + wslot] = -mu + S * U;
-                }
-            }
+            publish_dof(A, s, d, fdof, s_c[first], s_d[first], A.unique_y != 0);
         }
     }
 
@@ -924,10 +1004,8 @@ namespace
         const int k = lane & 7, el = (lane >> 3) & 3, ex = el & 1, ey = el >> 1;
         const int fdof = A.s_fdof[s];
         const int *sI = A.sI + 256 * (size_t)s;
-        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
 
-        Real gx[8], gy[8], gz[8], invm[8], Hi[8], F[8], Gf[8];
-        Real p[8], q[8], u[8], v[8];
+        Real gx[8], gy[8], gz[8], invm[8], Hi[8], F[8], Gf[8], u[8], v[8];
 #pragma unroll
         for (int l = 0; l < 8; ++l)
         {
@@ -942,33 +1020,7 @@ namespace
             }
             else
                 gx[l] = gy[l] = gz[l] = 0;
-            const Real ai = A.a[dbase + d], mi = A.m[dbase + d];
-            invm[l] = Real(1) / (ai * ai * mi);
-            Real f = 0, gg = 0, h = 0;
-            if (A.x)
-            {
-                const int gidx = A.gI[dbase + d];
-                f = static_cast<Real>(A.x[gidx]);
-                gg = static_cast<Real>(A.x[A.g_ndof + gidx]);
-            }
-            if (d < fdof)
-            {
-                h = A.H[fbase + d];
-                if (A.lambda)
-                {
-                    const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                    if (slot >= 0)
-                    {
-                        f += h * A.lambda[slot];
-                        gg += h * A.lambda[A.n_lambda + slot];
-                    }
-                }
-                h *= ai;
-            }
-            F[l] = f;
-            Gf[l] = gg;
-            Hi[l] = h;
-            p[l] = q[l] = u[l] = v[l] = 0;
+            load_dof(A, s, d, fdof, invm[l], Hi[l], F[l], Gf[l]);
         }
 
         Real Dk[8], DTk[8];
@@ -994,116 +1046,66 @@ namespace
         const Real mU = (ey == 0) ? Real(1) : Real(0);
         const Real mD = (ey == 1) ? Real(1) : Real(0);
 
-        const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
-        const int nt = A.nt;
-
-        for (int whit = 0; whit < A.wh_iters; ++whit)
+        auto sweep = [&](const Real(&w)[8], Real(&z)[8])
         {
-            {
-                const Real k0 = filt[0];
-#pragma unroll
-                for (int l = 0; l < 8; ++l)
-                {
-                    p[l] = u[l];
-                    q[l] = v[l];
-                    u[l] *= k0;
-                    v[l] *= k0;
-                }
-            }
-            for (int it = 1; it <= nt; ++it)
-            {
-                const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
-                const Real c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
-                const Real kw = filt[it];
-                Real z[8], ph[8], qh[8];
-
-                if constexpr (SEP)
-                    wave8_stiffness_sep<ASM>(p, z, Dk, Sep, gamma, mR, mL, mU, mD, lane);
-                else
-                    wave8_stiffness<ASM>(p, z, gx, gy, gz, Dk, DTk, Dmat, mR, mL, mU, mD, lane);
-#pragma unroll
-                for (int l = 0; l < 8; ++l)
-                {
-                    const Real dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
-                    ph[l] = p[l] - half_dt * q[l];
-                    qh[l] = q[l] + half_dt * dq;
-                    p[l] -= dt * qh[l];
-                }
-                if constexpr (SEP)
-                    wave8_stiffness_sep<ASM>(ph, z, Dk, Sep, gamma, mR, mL, mU, mD, lane);
-                else
-                    wave8_stiffness<ASM>(ph, z, gx, gy, gz, Dk, DTk, Dmat, mR, mL, mU, mD, lane);
-#pragma unroll
-                for (int l = 0; l < 8; ++l)
-                {
-                    const Real dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
-                    q[l] += dt * dq;
-                    u[l] += kw * p[l];
-                    v[l] += kw * q[l];
-                }
-            }
-        }
+            if constexpr (SEP)
+                wave8_stiffness_sep<ASM>(w, z, Dk, Sep, gamma, mR, mL, mU, mD, lane);
+            else
+                wave8_stiffness<ASM>(w, z, gx, gy, gz, Dk, DTk, Dmat, mR, mL, mU, mD, lane);
+        };
+        wh_march(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
 
         if (!valid)
             return;
-        const Real rw = Real(1) / A.omega;
 #pragma unroll
         for (int l = 0; l < 8; ++l)
         {
-            v[l] *= rw;
             // every shared node is held by 2 or 4 (lane, l) pairs with identical values: the copy with
             // the smallest element-node index writes
             const bool owner = !(k == 0 && ex > 0) && !(l == 0 && ey > 0);
-            if (!owner)
-                continue;
-            const int d = sI[k + 8 * (l + 8 * el)];
-            if (A.y)
-            {
-                const int gidx = A.gI[dbase + d];
-                const Real M = A.m[dbase + d] * A.gmi[dbase + d];
-                atomic_add(A.y + gidx, static_cast<double>(M * u[l]));
-                atomic_add(A.y + A.g_ndof + gidx, static_cast<double>(M * v[l]));
-            }
-            if (A.update && d < fdof)
-            {
-                const int wslot = A.B[d + (size_t)A.mx_fdof * (1 + 2 * (size_t)s)];
-                if (wslot >= 0)
-                {
-                    Real lam = 0, mu = 0;
-                    if (A.lambda)
-                    {
-                        const int rslot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                        if (rslot >= 0)
-                        {
-                            lam = A.lambda[rslot];
-                            mu = A.lambda[A.n_lambda + rslot];
-                        }
-                    }
-                    const Real S = Real(2) * A.a[dbase + d] * A.omega;
-                    A.update[wslot] = -lam - S * v[l];
-                    A.update[A.n_lambda + wslot] = -mu + S * u[l];
-                }
-            }
+            if (owner)
+                publish_dof(A, s, sI[k + 8 * (l + 8 * el)], fdof, u[l], v[l], false);
         }
     }
 
-    // ---------------------------------------------------------------- dense element matrix on the matrix cores (NB = 4, uniform geometry)
+    // ---------------------------------------------------------------- kernels 5 and 8: dense element matrix on the matrix cores (NB = 4, uniform geometry)
     // When every element of every subdomain has the same metric tensor (always the case on the uniform_rect
     // meshes DDH supports) the element-local part of a stiffness sweep is Z = K U with one 16x16 element matrix K
     // and U = (16 nodes) x (16 elements of the subdomain): exactly one 16x16x16 product, i.e. four
-    // v_mfma_f32_16x16x4_f32 per sweep on the matrix pipe, leaving the VALU only the assembly and the RK2 update.
+    // v_mfma_f32_16x16x4_f32 (kernel 5, Real = float) or v_mfma_f64_16x16x4_f64 (kernel 8, Real = double) per sweep on the
+    // matrix pipe, leaving the VALU only the assembly and the RK2 update.
     // Lane = element + 16 * h, register index = l (eta node): the B-operand map B[kk][j] with kk = 4 s + (lane >> 4),
-    // j = lane & 15 makes register s of a lane the node (h, l = s); the rows of K are ordered m = 4 h + l so that the
-    // C/D map (row = 4 (lane >> 4) + reg) returns the result in the same layout (h = k, the xi node).
+    // j = lane & 15 makes register s of a lane the node (h, l = s).  The rows of K are ordered so that the C/D map returns the
+    // result in the same layout (h = k, the xi node): m = 4 h + l for the f32 instruction (row = 4 (lane >> 4) + reg),
+    // m = k_out + 4 l_out for the f64 instruction (row = (lane >> 4) + 4 reg); build_dense_element_matrix<Real> does both, and
+    // either way the result lands in lane (el, k), register l.  In fp64 K is formed and kept in double: every operation of a
+    // sweep is fp64, the summation order alone differs from the sum-factorised kernels 1 and 2.
     // On gfx950 the f32 MFMA runs at the vector rate and does not overlap with VALU work, so what counts is the
     // number of issue cycles: 4 MFMAs (128 cycles) replace the ~80 VALU instructions (160 cycles + DPP hazards) of the
     // sum-factorised sweep, and the xi-neighbour exchange goes through ds_bpermute (LDS pipe, no VALU slots); a
     // variant with odd elements stored mirrored in xi so that every exchange is a DPP row shift measured 24 % slower
     // (96 instead of 72 VALU instructions per time step).
-    __global__ void __launch_bounds__(256) ddh_mfma_kernel(DdhArgs<float> A, const float *__restrict__ Aop, const float *__restrict__ filt,
-                                                          const float *__restrict__ cs, const float *__restrict__ sn)
+    // PRIO: the four matrix instructions of a sweep are issued with priority over the other resident wavefronts' vector work.
+    // The fp32 matrix instructions run on the SIMD's own fp32 lanes (no co-execution with VALU: SQ_VALU_MFMA_COEXEC_CYCLES = 0,
+    // profiles/r03/pmc_ddh_kernel5_coexec.txt, mfma_valu_coexec.txt) and a vector instruction issued behind a matrix
+    // instruction waits for its passes to drain, so grouping the wavefronts' matrix instructions saves issue cycles
+    // (same-box A/B, 16,384 subdomains: 85.2 -> 83.4 ms per action; order of issue only, results bitwise unchanged): on in
+    // fp32.  In fp64 that grouping is 0.7-1.7 % slower than plain issue order (same-box A/B, profiles/r04/ddh64_prio_ab.txt),
+    // hence off unless built with CUDDH_DDH64_MFMA_PRIO=1; the knob stays for A/B builds (profiles/tools/build_variant.py).
+#ifndef CUDDH_DDH64_MFMA_PRIO
+#define CUDDH_DDH64_MFMA_PRIO 0
+#endif
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef double d4 __attribute__((ext_vector_type(4)));
+    __device__ inline f4 mfma_16x16x4(float a, float b, f4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
+    __device__ inline d4 mfma_16x16x4(double a, double b, d4 acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
+
+    template <typename Real>
+    __global__ void __launch_bounds__(256) ddh_mfma_kernel(DdhArgs<Real> A, const Real *__restrict__ Aop, const Real *__restrict__ filt,
+                                                          const Real *__restrict__ cs, const Real *__restrict__ sn)
     {
-        typedef float f4 __attribute__((ext_vector_type(4)));
+        constexpr bool PRIO = sizeof(Real) == 4 || CUDDH_DDH64_MFMA_PRIO;
+        typedef Real r4 __attribute__((ext_vector_type(4)));
         const int lane = threadIdx.x & 63;
         const int position = A.dom_begin + blockIdx.x * 4 + (threadIdx.x >> 6);
         if (position >= A.dom_end)
@@ -1114,42 +1116,12 @@ namespace
         const int k = lane >> 4, el = lane & 15, ex = el & 3, ey = el >> 2;
         const int fdof = A.s_fdof[s];
         const int *sI = A.sI + 256 * (size_t)s;
-        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
 
-        float invm[4], Hi[4], F[4], Gf[4], p[4], q[4], u[4], v[4];
+        Real invm[4], Hi[4], F[4], Gf[4], u[4], v[4];
 #pragma unroll
         for (int l = 0; l < 4; ++l)
-        {
-            const int d = sI[k + 4 * (l + 4 * el)];
-            const float ai = A.a[dbase + d], mi = A.m[dbase + d];
-            invm[l] = 1.0f / (ai * ai * mi);
-            float f = 0, gg = 0, h = 0;
-            if (A.x)
-            {
-                const int gidx = A.gI[dbase + d];
-                f = static_cast<float>(A.x[gidx]);
-                gg = static_cast<float>(A.x[A.g_ndof + gidx]);
-            }
-            if (d < fdof)
-            {
-                h = A.H[fbase + d];
-                if (A.lambda)
-                {
-                    const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                    if (slot >= 0)
-                    {
-                        f += h * A.lambda[slot];
-                        gg += h * A.lambda[A.n_lambda + slot];
-                    }
-                }
-                h *= ai;
-            }
-            F[l] = f;
-            Gf[l] = gg;
-            Hi[l] = h;
-            p[l] = q[l] = u[l] = v[l] = 0;
-        }
-        float Ka[4];
+            load_dof(A, s, sI[k + 4 * (l + 4 * el)], fdof, invm[l], Hi[l], F[l], Gf[l]);
+        Real Ka[4];
 #pragma unroll
         for (int st = 0; st < 4; ++st)
             Ka[st] = Aop[64 * st + lane];
@@ -1158,293 +1130,42 @@ namespace
         // eta neighbours are 4 lanes away in the same row: DPP row_shl/shr:4
         const bool hasR = (k == 3 && ex < 3), hasL = (k == 0 && ex > 0);
         const int partner = hasR ? (el + 1) : (hasL ? (el - 1 + 48) : lane);
-        const float mX = (hasR || hasL) ? 1.0f : 0.0f;
-        const float mU = (ey < 3) ? 1.0f : 0.0f, mD = (ey > 0) ? 1.0f : 0.0f;
+        const Real mX = (hasR || hasL) ? Real(1) : Real(0);
+        const Real mU = (ey < 3) ? Real(1) : Real(0), mD = (ey > 0) ? Real(1) : Real(0);
 
-        auto sweep = [&](const float (&w)[4], float (&z)[4])
+        auto sweep = [&](const Real(&w)[4], Real(&z)[4])
         {
-            f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-            // The four matrix instructions of a sweep are issued with priority over the other resident wavefronts' vector work: the
-            // fp32 matrix instructions run on the SIMD's own fp32 lanes (no co-execution with VALU: SQ_VALU_MFMA_COEXEC_CYCLES = 0,
-            // profiles/r03/pmc_ddh_kernel5_coexec.txt, mfma_valu_coexec.txt) and a vector instruction issued behind a matrix
-            // instruction waits for its passes to drain, so grouping the wavefronts' matrix instructions saves issue cycles
-            // (same-box A/B, 16,384 subdomains: 85.2 -> 83.4 ms per action; order of issue only, results bitwise unchanged).
-            __builtin_amdgcn_s_setprio(3);
+            r4 acc = {0, 0, 0, 0};
+            if constexpr (PRIO)
+                __builtin_amdgcn_s_setprio(3);
 #pragma unroll
             for (int st = 0; st < 4; ++st)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(Ka[st], w[st], acc, 0, 0, 0);
-            if (!A.prio) // a launch that holds issue priority as a whole (multi-GPU boundary subdomains) keeps it
-                __builtin_amdgcn_s_setprio(0);
-            float fx[4];
+                acc = mfma_16x16x4(Ka[st], w[st], acc);
+            if constexpr (PRIO)
+                if (!A.prio) // a launch that holds issue priority as a whole (multi-GPU boundary subdomains) keeps it
+                    __builtin_amdgcn_s_setprio(0);
+            Real fx[4];
 #pragma unroll
             for (int l = 0; l < 4; ++l)
                 fx[l] = __shfl(acc[l], partner, 64);
 #pragma unroll
             for (int l = 0; l < 4; ++l)
                 z[l] = acc[l] + mX * fx[l];
-            const float from_above = dpp_read<0x104>(z[0]); // row_shl:4 : lane + 4 = element above
-            const float from_below = dpp_read<0x114>(z[3]); // row_shr:4
+            const Real from_above = dpp_read<0x104>(z[0]); // row_shl:4 : lane + 4 = element above
+            const Real from_below = dpp_read<0x114>(z[3]); // row_shr:4
             z[3] += mU * from_above;
             z[0] += mD * from_below;
         };
+        wh_march(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
 
-        const float dt = A.dt, half_dt = 0.5f * A.dt;
-        const int nt = A.nt;
-        for (int whit = 0; whit < A.wh_iters; ++whit)
-        {
-            {
-                const float k0 = filt[0];
-#pragma unroll
-                for (int l = 0; l < 4; ++l)
-                {
-                    p[l] = u[l];
-                    q[l] = v[l];
-                    u[l] *= k0;
-                    v[l] *= k0;
-                }
-            }
-            for (int it = 1; it <= nt; ++it)
-            {
-                const float c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
-                const float c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
-                const float kw = filt[it];
-                float z[4], ph[4], qh[4];
-                sweep(p, z);
-#pragma unroll
-                for (int l = 0; l < 4; ++l)
-                {
-                    const float dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
-                    ph[l] = p[l] - half_dt * q[l];
-                    qh[l] = q[l] + half_dt * dq;
-                    p[l] -= dt * qh[l];
-                }
-                sweep(ph, z);
-#pragma unroll
-                for (int l = 0; l < 4; ++l)
-                {
-                    const float dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
-                    q[l] += dt * dq;
-                    u[l] += kw * p[l];
-                    v[l] += kw * q[l];
-                }
-            }
-        }
-
-        const float rw = 1.0f / A.omega;
 #pragma unroll
         for (int l = 0; l < 4; ++l)
         {
-            v[l] *= rw;
+            // every shared node is held by 2 or 4 (lane, l) pairs with identical values: the copy with
+            // the smallest element-node index writes
             const bool owner = !(k == 0 && ex > 0) && !(l == 0 && ey > 0);
-            if (!owner)
-                continue;
-            const int d = sI[k + 4 * (l + 4 * el)];
-            if (A.y)
-            {
-                const int gidx = A.gI[dbase + d];
-                const float M = A.m[dbase + d] * A.gmi[dbase + d];
-                atomic_add(A.y + gidx, static_cast<double>(M * u[l]));
-                atomic_add(A.y + A.g_ndof + gidx, static_cast<double>(M * v[l]));
-            }
-            if (A.update && d < fdof)
-            {
-                const int wslot = A.B[d + (size_t)A.mx_fdof * (1 + 2 * (size_t)s)];
-                if (wslot >= 0)
-                {
-                    float lam = 0, mu = 0;
-                    if (A.lambda)
-                    {
-                        const int rslot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                        if (rslot >= 0)
-                        {
-                            lam = A.lambda[rslot];
-                            mu = A.lambda[A.n_lambda + rslot];
-                        }
-                    }
-                    const float S = 2.0f * A.a[dbase + d] * A.omega;
-                    A.update[wslot] = -lam - S * v[l];
-                    A.update[A.n_lambda + wslot] = -mu + S * u[l];
-                }
-            }
-        }
-    }
-
-    // ---------------------------------------------------------------- kernel 8: kernel 5's scheme in fp64 (v_mfma_f64_16x16x4_f64)
-    // Same lanes as ddh_mfma_kernel (lane = element + 16 k, register = l) and the same A/B operand maps; only the C/D map of
-    // the f64 instruction differs: row = (lane >> 4) + 4 reg instead of 4 (lane >> 4) + reg.  build_dense_element_matrix<double>
-    // orders K's output rows as m = k_out + 4 l_out to match, so the result again lands in lane (el, k), register l.  K is
-    // formed and kept in double: every operation of a sweep is fp64, the summation order alone differs from the
-    // sum-factorised kernels 1 and 2.
-    // CUDDH_DDH64_MFMA_PRIO=1 issues the four matrix instructions of a sweep with raised priority, as kernel 5 does.  In fp64 that
-    // grouping is 0.7-1.7 % slower than plain issue order (same-box A/B, profiles/r04/ddh64_prio_ab.txt), hence off by default;
-    // the knob stays for A/B builds (profiles/tools/build_variant.py).
-#ifndef CUDDH_DDH64_MFMA_PRIO
-#define CUDDH_DDH64_MFMA_PRIO 0
-#endif
-    __global__ void __launch_bounds__(256) ddh_mfma64_kernel(DdhArgs<double> A, const double *__restrict__ Aop, const double *__restrict__ filt,
-                                                            const double *__restrict__ cs, const double *__restrict__ sn)
-    {
-        typedef double d4 __attribute__((ext_vector_type(4)));
-        const int lane = threadIdx.x & 63;
-        const int position = A.dom_begin + blockIdx.x * 4 + (threadIdx.x >> 6);
-        if (position >= A.dom_end)
-            return; // wave-uniform, no barriers in this kernel
-        const int s = domain_at(A, position);
-        raise_priority(A.prio);
-
-        const int k = lane >> 4, el = lane & 15, ex = el & 3, ey = el >> 2;
-        const int fdof = A.s_fdof[s];
-        const int *sI = A.sI + 256 * (size_t)s;
-        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
-
-        double invm[4], Hi[4], F[4], Gf[4], p[4], q[4], u[4], v[4];
-#pragma unroll
-        for (int l = 0; l < 4; ++l)
-        {
-            const int d = sI[k + 4 * (l + 4 * el)];
-            const double ai = A.a[dbase + d], mi = A.m[dbase + d];
-            invm[l] = 1.0 / (ai * ai * mi);
-            double f = 0, gg = 0, h = 0;
-            if (A.x)
-            {
-                const int gidx = A.gI[dbase + d];
-                f = A.x[gidx];
-                gg = A.x[A.g_ndof + gidx];
-            }
-            if (d < fdof)
-            {
-                h = A.H[fbase + d];
-                if (A.lambda)
-                {
-                    const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                    if (slot >= 0)
-                    {
-                        f += h * A.lambda[slot];
-                        gg += h * A.lambda[A.n_lambda + slot];
-                    }
-                }
-                h *= ai;
-            }
-            F[l] = f;
-            Gf[l] = gg;
-            Hi[l] = h;
-            p[l] = q[l] = u[l] = v[l] = 0;
-        }
-        double Ka[4];
-#pragma unroll
-        for (int st = 0; st < 4; ++st)
-            Ka[st] = Aop[64 * st + lane];
-
-        // xi neighbours live in another 16-lane row: ds_bpermute; eta neighbours are 4 lanes away in the same row: DPP row_shl/shr:4
-        const bool hasR = (k == 3 && ex < 3), hasL = (k == 0 && ex > 0);
-        const int partner = hasR ? (el + 1) : (hasL ? (el - 1 + 48) : lane);
-        const double mX = (hasR || hasL) ? 1.0 : 0.0;
-        const double mU = (ey < 3) ? 1.0 : 0.0, mD = (ey > 0) ? 1.0 : 0.0;
-
-        auto sweep = [&](const double (&w)[4], double (&z)[4])
-        {
-            d4 acc = {0.0, 0.0, 0.0, 0.0};
-#if CUDDH_DDH64_MFMA_PRIO
-            __builtin_amdgcn_s_setprio(3);
-#endif
-#pragma unroll
-            for (int st = 0; st < 4; ++st)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ka[st], w[st], acc, 0, 0, 0);
-#if CUDDH_DDH64_MFMA_PRIO
-            if (!A.prio) // a launch that holds issue priority as a whole (multi-GPU boundary subdomains) keeps it
-                __builtin_amdgcn_s_setprio(0);
-#endif
-            double fx[4];
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                fx[l] = __shfl(acc[l], partner, 64);
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                z[l] = acc[l] + mX * fx[l];
-            const double from_above = dpp_read<0x104>(z[0]); // row_shl:4 : lane + 4 = element above
-            const double from_below = dpp_read<0x114>(z[3]); // row_shr:4
-            z[3] += mU * from_above;
-            z[0] += mD * from_below;
-        };
-
-        const double dt = A.dt, half_dt = 0.5 * A.dt;
-        const int nt = A.nt;
-        for (int whit = 0; whit < A.wh_iters; ++whit)
-        {
-            {
-                const double k0 = filt[0];
-#pragma unroll
-                for (int l = 0; l < 4; ++l)
-                {
-                    p[l] = u[l];
-                    q[l] = v[l];
-                    u[l] *= k0;
-                    v[l] *= k0;
-                }
-            }
-            for (int it = 1; it <= nt; ++it)
-            {
-                const double c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
-                const double c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
-                const double kw = filt[it];
-                double z[4], ph[4], qh[4];
-                sweep(p, z);
-#pragma unroll
-                for (int l = 0; l < 4; ++l)
-                {
-                    const double dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
-                    ph[l] = p[l] - half_dt * q[l];
-                    qh[l] = q[l] + half_dt * dq;
-                    p[l] -= dt * qh[l];
-                }
-                sweep(ph, z);
-#pragma unroll
-                for (int l = 0; l < 4; ++l)
-                {
-                    const double dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
-                    q[l] += dt * dq;
-                    u[l] += kw * p[l];
-                    v[l] += kw * q[l];
-                }
-            }
-        }
-
-        const double rw = 1.0 / A.omega;
-#pragma unroll
-        for (int l = 0; l < 4; ++l)
-        {
-            v[l] *= rw;
-            const bool owner = !(k == 0 && ex > 0) && !(l == 0 && ey > 0);
-            if (!owner)
-                continue;
-            const int d = sI[k + 4 * (l + 4 * el)];
-            if (A.y)
-            {
-                const int gidx = A.gI[dbase + d];
-                const double M = A.m[dbase + d] * A.gmi[dbase + d];
-                atomic_add(A.y + gidx, M * u[l]);
-                atomic_add(A.y + A.g_ndof + gidx, M * v[l]);
-            }
-            if (A.update && d < fdof)
-            {
-                const int wslot = A.B[d + (size_t)A.mx_fdof * (1 + 2 * (size_t)s)];
-                if (wslot >= 0)
-                {
-                    double lam = 0, mu = 0;
-                    if (A.lambda)
-                    {
-                        const int rslot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                        if (rslot >= 0)
-                        {
-                            lam = A.lambda[rslot];
-                            mu = A.lambda[A.n_lambda + rslot];
-                        }
-                    }
-                    const double S = 2.0 * A.a[dbase + d] * A.omega;
-                    A.update[wslot] = -lam - S * v[l];
-                    A.update[A.n_lambda + wslot] = -mu + S * u[l];
-                }
-            }
+            if (owner)
+                publish_dof(A, s, sI[k + 4 * (l + 4 * el)], fdof, u[l], v[l], false);
         }
     }
 
@@ -1741,13 +1462,60 @@ namespace
         return launch_status();
     }
 
-    template <typename Real, int NB, bool CSR = false>
-    void launch_block(const DdhArgs<Real> &A, const cuddh_ddh_desc &d, int n_local, hipStream_t st)
+    // kernel 1 (CSR = false) or 10 (CSR = true) for the plan's n_basis; false if there is no instantiation for it
+    template <typename Real, bool CSR>
+    bool launch_block(int nb, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl, const Real *cs, const Real *sn)
     {
         const int T = A.nodes;
         const size_t lds = (size_t)T * (4 * sizeof(Real) + 5 * sizeof(int));
-        hipLaunchKernelGGL((ddh_block_kernel<Real, NB, CSR>), dim3(n_local), dim3(T), lds, st, A, static_cast<const Real *>(d.D),
-                           static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs), static_cast<const Real *>(d.sn));
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_local), dim3(T), lds, st, A, D, fl, cs, sn); };
+        switch (nb)
+        {
+        case 2: launch(ddh_block_kernel<Real, 2, CSR>); break;
+        case 3: launch(ddh_block_kernel<Real, 3, CSR>); break;
+        case 4: launch(ddh_block_kernel<Real, 4, CSR>); break;
+        case 5: launch(ddh_block_kernel<Real, 5, CSR>); break;
+        case 6: launch(ddh_block_kernel<Real, 6, CSR>); break;
+        case 7: launch(ddh_block_kernel<Real, 7, CSR>); break;
+        case 8: launch(ddh_block_kernel<Real, 8, CSR>); break;
+        case 9: launch(ddh_block_kernel<Real, 9, CSR>); break;
+        case 10: launch(ddh_block_kernel<Real, 10, CSR>); break;
+        default: return false;
+        }
+        return true;
+    }
+
+    // Runs a check kernel that raises a device flag on the first violation it finds (launch(flag) starts it on the null
+    // stream).  *bad = the flag, 1 if anything failed.  Returns a HIP error code.
+    template <typename Launch>
+    int device_flag_check(int *bad, Launch launch)
+    {
+        *bad = 1;
+        int *flag = nullptr;
+        hipError_t e = hipMalloc(&flag, sizeof(int));
+        if (e == hipSuccess)
+            e = hipMemset(flag, 0, sizeof(int));
+        if (e == hipSuccess)
+        {
+            launch(flag);
+            e = hipMemcpy(bad, flag, sizeof(int), hipMemcpyDeviceToHost);
+        }
+        if (flag)
+            (void)hipFree(flag);
+        return static_cast<int>(e);
+    }
+
+    // Does every element of every subdomain have the metric tensor of (subdomain 0, element 0)?  0 if so, -1 if not, > 0 on a
+    // HIP error.
+    template <typename Real>
+    int check_uniform_geometry(const cuddh_ddh_desc &d, int nodes_per_elem)
+    {
+        const long long n_nodes = 256LL * d.n_domains;
+        int bad = 1;
+        const int e = device_flag_check(&bad, [&](int *flag)
+                                        { hipLaunchKernelGGL(ddh_uniform_check_kernel<Real>, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, nullptr,
+                                                             n_nodes, nodes_per_elem, static_cast<const Real *>(d.G), flag); });
+        return e ? e : (bad ? -1 : 0);
     }
 
     // Builds plan->Aop for kernel 5 (Real = float) or plan->Aop64 for kernel 8 (Real = double).  Returns 0 on success, -1 if
@@ -1756,26 +1524,13 @@ namespace
     int build_dense_element_matrix(cuddh_ddh_plan *p)
     {
         const cuddh_ddh_desc &d = p->d;
-        const Real *G = static_cast<const Real *>(d.G);
-        int *flag = nullptr;
-        hipError_t e = hipMalloc(&flag, sizeof(int));
-        if (e != hipSuccess)
-            return static_cast<int>(e);
-        (void)hipMemset(flag, 0, sizeof(int));
-        const long long n_nodes = 256LL * d.n_domains;
-        hipLaunchKernelGGL(ddh_uniform_check_kernel<Real>, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, nullptr, n_nodes, 16, G, flag);
-        int bad = 1;
-        e = hipMemcpy(&bad, flag, sizeof(int), hipMemcpyDeviceToHost);
-        (void)hipFree(flag);
-        if (e != hipSuccess)
-            return static_cast<int>(e);
-        if (bad)
-            return -1;
+        if (const int c = check_uniform_geometry<Real>(d, 16))
+            return c;
 
         Real hD[16], hG[48];
-        e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
         if (e == hipSuccess)
-            e = hipMemcpy(hG, G, sizeof hG, hipMemcpyDeviceToHost);
+            e = hipMemcpy(hG, d.G, sizeof hG, hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             return static_cast<int>(e);
 
@@ -1838,25 +1593,12 @@ namespace
     int build_separable_tables(cuddh_ddh_plan *p)
     {
         const cuddh_ddh_desc &d = p->d;
-        const float *G = static_cast<const float *>(d.G);
-        int *flag = nullptr;
-        hipError_t e = hipMalloc(&flag, sizeof(int));
-        if (e != hipSuccess)
-            return static_cast<int>(e);
-        (void)hipMemset(flag, 0, sizeof(int));
-        const long long n_nodes = 256LL * d.n_domains;
-        hipLaunchKernelGGL(ddh_uniform_check_kernel<float>, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, nullptr, n_nodes, 64, G, flag);
-        int bad = 1;
-        e = hipMemcpy(&bad, flag, sizeof(int), hipMemcpyDeviceToHost);
-        (void)hipFree(flag);
-        if (e != hipSuccess)
-            return static_cast<int>(e);
-        if (bad)
-            return -1;
+        if (const int c = check_uniform_geometry<float>(d, 64))
+            return c;
         float hD[64], hG[192];
-        e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
         if (e == hipSuccess)
-            e = hipMemcpy(hG, G, sizeof hG, hipMemcpyDeviceToHost);
+            e = hipMemcpy(hG, d.G, sizeof hG, hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             return static_cast<int>(e);
         auto Dm = [&](int a, int b) { return static_cast<double>(hD[a + 8 * b]); }; // D(a,b)
@@ -1955,94 +1697,50 @@ namespace
         A.csr_src = plan->csr_src;
         A.unique_y = plan->gI_override ? 1 : 0;
 
-        if (plan->kernel == 9)
+        const dim3 grid((n_local + 3) / 4), block(256); // the wavefront kernels: four wavefronts per workgroup
+        const Real *D = static_cast<const Real *>(d.D), *fl = static_cast<const Real *>(d.wh_filter);
+        const Real *cs = static_cast<const Real *>(d.cs), *sn = static_cast<const Real *>(d.sn);
+        // kernels 3, 4, 7 and the folded-DPP form of 9 exist in fp32 only; fp64 always takes the plain form
+        constexpr bool f32 = sizeof(Real) == 4;
+        constexpr int v3 = f32 ? 1 : 0, v4 = f32 ? 2 : 0;
+
+        switch (plan->kernel)
         {
-            constexpr int var = sizeof(Real) == 4 ? 1 : 0; // folded-DPP contractions in fp32, the plain form in fp64
-            hipLaunchKernelGGL((ddh_general_wave_kernel<Real, var>), dim3((n_local + 3) / 4), dim3(256), 0, st, A,
-                               static_cast<const Real *>(d.D), static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs),
-                               static_cast<const Real *>(d.sn));
-            return launch_status();
-        }
-        if (plan->kernel == 10)
+        case 1:
+        case 10:
+            if (!(plan->kernel == 10 ? launch_block<Real, true>(d.nb, A, n_local, st, D, fl, cs, sn)
+                                     : launch_block<Real, false>(d.nb, A, n_local, st, D, fl, cs, sn)))
+                return static_cast<int>(hipErrorInvalidValue);
+            break;
+        case 2: hipLaunchKernelGGL((ddh_wave_kernel<Real, 0>), grid, block, 0, st, A, D, fl, cs, sn); break;
+        case 3: hipLaunchKernelGGL((ddh_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn); break;
+        case 4: hipLaunchKernelGGL((ddh_wave_kernel<Real, v4>), grid, block, 0, st, A, D, fl, cs, sn); break;
+        case 5:
+        case 8:
+            if ((plan->kernel == 5) != f32) // plan_create ties kernel 5 to fp32 (Aop) and kernel 8 to fp64 (Aop64)
+                return static_cast<int>(hipErrorInvalidValue);
+            if constexpr (f32)
+                hipLaunchKernelGGL(ddh_mfma_kernel<float>, grid, block, 0, st, A, plan->Aop, fl, cs, sn);
+            else
+                hipLaunchKernelGGL(ddh_mfma_kernel<double>, grid, block, 0, st, A, plan->Aop64, fl, cs, sn);
+            break;
+        case 6:
+        case 7:
         {
-            switch (d.nb)
-            {
-            case 2: launch_block<Real, 2, true>(A, d, n_local, st); break;
-            case 3: launch_block<Real, 3, true>(A, d, n_local, st); break;
-            case 4: launch_block<Real, 4, true>(A, d, n_local, st); break;
-            case 5: launch_block<Real, 5, true>(A, d, n_local, st); break;
-            case 6: launch_block<Real, 6, true>(A, d, n_local, st); break;
-            case 7: launch_block<Real, 7, true>(A, d, n_local, st); break;
-            case 8: launch_block<Real, 8, true>(A, d, n_local, st); break;
-            case 9: launch_block<Real, 9, true>(A, d, n_local, st); break;
-            case 10: launch_block<Real, 10, true>(A, d, n_local, st); break;
-            default: return static_cast<int>(hipErrorInvalidValue);
-            }
-            return launch_status();
-        }
-        if (plan->kernel == 5)
-        {
-            if constexpr (sizeof(Real) == 4)
-            {
-                hipLaunchKernelGGL(ddh_mfma_kernel, dim3((n_local + 3) / 4), dim3(256), 0, st, A, plan->Aop, static_cast<const float *>(d.wh_filter),
-                                   static_cast<const float *>(d.cs), static_cast<const float *>(d.sn));
-                return launch_status();
-            }
-        }
-        if (plan->kernel == 8)
-        {
-            if constexpr (sizeof(Real) == 8)
-            {
-                hipLaunchKernelGGL(ddh_mfma64_kernel, dim3((n_local + 3) / 4), dim3(256), 0, st, A, plan->Aop64,
-                                   static_cast<const double *>(d.wh_filter), static_cast<const double *>(d.cs), static_cast<const double *>(d.sn));
-                return launch_status();
-            }
-            return static_cast<int>(hipErrorInvalidValue); // unreachable: apply() checks the plan's precision first
-        }
-        if (plan->kernel == 6 || plan->kernel == 7)
-        {
-            const dim3 grid((n_local + 7) / 8), block(256); // four wavefronts per workgroup, two subdomains per wavefront
-            const Real *D = static_cast<const Real *>(d.D), *fl = static_cast<const Real *>(d.wh_filter);
-            const Real *cs = static_cast<const Real *>(d.cs), *sn = static_cast<const Real *>(d.sn);
-            if constexpr (sizeof(Real) == 4)
+            const dim3 grid8((n_local + 7) / 8); // two subdomains per wavefront
+            if constexpr (f32)
             {
                 if (plan->kernel == 7)
-                    hipLaunchKernelGGL((ddh_wave8_kernel<float, true, true>), grid, block, 0, st, A, D, fl, cs, sn, plan->Sep);
+                    hipLaunchKernelGGL((ddh_wave8_kernel<float, true, true>), grid8, block, 0, st, A, D, fl, cs, sn, plan->Sep);
                 else
-                    hipLaunchKernelGGL((ddh_wave8_kernel<float, true, false>), grid, block, 0, st, A, D, fl, cs, sn, plan->Sep);
+                    hipLaunchKernelGGL((ddh_wave8_kernel<float, true, false>), grid8, block, 0, st, A, D, fl, cs, sn, plan->Sep);
             }
             else
-                hipLaunchKernelGGL((ddh_wave8_kernel<double, false, false>), grid, block, 0, st, A, D, fl, cs, sn,
+                hipLaunchKernelGGL((ddh_wave8_kernel<double, false, false>), grid8, block, 0, st, A, D, fl, cs, sn,
                                    static_cast<const double *>(nullptr));
-            return launch_status();
+            break;
         }
-        if (plan->kernel >= 2)
-        {
-            // kernels 3 and 4 exist in fp32 only; fp64 always takes the plain form
-            constexpr int v3 = sizeof(Real) == 4 ? 1 : 0, v4 = sizeof(Real) == 4 ? 2 : 0;
-            const dim3 grid((n_local + 3) / 4), block(256);
-            const Real *D = static_cast<const Real *>(d.D), *fl = static_cast<const Real *>(d.wh_filter);
-            const Real *cs = static_cast<const Real *>(d.cs), *sn = static_cast<const Real *>(d.sn);
-            if (plan->kernel == 4)
-                hipLaunchKernelGGL((ddh_wave_kernel<Real, v4>), grid, block, 0, st, A, D, fl, cs, sn);
-            else if (plan->kernel == 3 || plan->kernel == 5)
-                hipLaunchKernelGGL((ddh_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn);
-            else
-                hipLaunchKernelGGL((ddh_wave_kernel<Real, 0>), grid, block, 0, st, A, D, fl, cs, sn);
-            return launch_status();
-        }
-
-        switch (d.nb)
-        {
-        case 2: launch_block<Real, 2>(A, d, n_local, st); break;
-        case 3: launch_block<Real, 3>(A, d, n_local, st); break;
-        case 4: launch_block<Real, 4>(A, d, n_local, st); break;
-        case 5: launch_block<Real, 5>(A, d, n_local, st); break;
-        case 6: launch_block<Real, 6>(A, d, n_local, st); break;
-        case 7: launch_block<Real, 7>(A, d, n_local, st); break;
-        case 8: launch_block<Real, 8>(A, d, n_local, st); break;
-        case 9: launch_block<Real, 9>(A, d, n_local, st); break;
-        case 10: launch_block<Real, 10>(A, d, n_local, st); break;
+        case 9: hipLaunchKernelGGL((ddh_general_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn); break;
         default: return static_cast<int>(hipErrorInvalidValue);
         }
         return launch_status();
@@ -2051,20 +1749,9 @@ namespace
     template <int NB, int NEL>
     int run_structure_check(const cuddh_ddh_desc *desc, int *bad)
     {
-        int *flag = nullptr;
-        hipError_t e = hipMalloc(&flag, sizeof(int));
-        if (e == hipSuccess)
-            e = hipMemset(flag, 0, sizeof(int));
-        *bad = 1;
-        if (e == hipSuccess)
-        {
-            hipLaunchKernelGGL((ddh_wave_check_kernel<NB, NEL>), dim3(desc->n_domains), dim3(256), 0, nullptr, desc->n_domains,
-                               desc->s_dof, desc->sI, flag);
-            e = hipMemcpy(bad, flag, sizeof(int), hipMemcpyDeviceToHost);
-        }
-        if (flag)
-            (void)hipFree(flag);
-        return static_cast<int>(e);
+        return device_flag_check(bad, [&](int *flag)
+                                 { hipLaunchKernelGGL((ddh_wave_check_kernel<NB, NEL>), dim3(desc->n_domains), dim3(256), 0, nullptr,
+                                                      desc->n_domains, desc->s_dof, desc->sI, flag); });
     }
 } // namespace
 

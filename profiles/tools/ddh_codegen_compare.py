@@ -1,0 +1,81 @@
+"""Generated-code comparison of two versions of csrc/kernels/ddh.hip, kernel by kernel, without a GPU:
+  python profiles/tools/ddh_codegen_compare.py OLD.hip NEW.hip [--keep DIR]
+Compiles both to gfx950 assembly with build.py's flags for ddh.hip and prints, for every __global__ instantiation, the
+registers, scratch, LDS, the instruction count, whether the mnemonic histogram is the same and a sequence diff (mnemonics
+left unmatched by difflib's longest-matching-blocks alignment, removed + added: 0 = the same instructions in the same order,
+registers aside; a non-zero figure is an upper bound on what moved, not a minimal edit distance), and the same three for
+the blocks that lie inside loops (the time stepping, where these kernels spend their time).  A kernel that differs is to be
+timed against the old build; same histogram does not mean same speed for kernels tuned on issue order."""
+import collections
+import difflib
+import re
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
+from cuddhelmholtz_amd import build as B  # noqa: E402
+
+# kernels whose symbol changed: demangled name (without the argument list) in OLD -> in NEW
+RENAMED = {"ddh_mfma_kernel": "ddh_mfma_kernel<float>", "ddh_mfma64_kernel": "ddh_mfma_kernel<double>"}
+FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
+
+
+def kernels(src: Path, out: Path):
+    cmd = [B.hipcc(), *B.COMMON, *[f"-I{p}" for p in B.INCLUDES], *B.HIP_FLAGS, *B.EXTRA_FLAGS["ddh.hip"], "--cuda-device-only", "-S",
+           str(src), "-o", str(out)]
+    subprocess.run(cmd, check=True)
+    text = out.read_text()
+    found = {}
+    # the metadata holds one list item per kernel under amdhsa.kernels (items start with "  - ", their fields with "    ")
+    for entry in re.split(r"\n  - (?=\.)", text.split("amdhsa.kernels:", 1)[1].split("\namdhsa.", 1)[0])[1:]:
+        sym = re.search(r"^\s*\.name:\s+(\S+)", entry, re.M).group(1)
+        meta = {f: int(re.search(rf"^\s*{re.escape(f)}:\s+(\d+)", entry, re.M).group(1)) for f in FIELDS}
+        body = text.split(f"\n{sym}:", 1)[1].split(".Lfunc_end", 1)[0]
+        ops, loop_ops, in_loop = [], [], False
+        for ln in body.splitlines():
+            if ln.startswith((".LBB", "; %bb")):  # the compiler marks every block of a loop in the label's comment
+                in_loop = "Loop" in ln
+            elif ln.startswith("\t") and ln[1:2] not in ("", ".", ";"):
+                ops.append(ln.split()[0])
+                if in_loop:
+                    loop_ops.append(ops[-1])
+        name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
+        name = name.replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0]
+        found[name] = (meta, ops, loop_ops)
+    return found
+
+
+def main():
+    keep = Path(sys.argv[sys.argv.index("--keep") + 1]) if "--keep" in sys.argv else Path(tempfile.mkdtemp())
+    keep.mkdir(parents=True, exist_ok=True)
+    old, new = kernels(Path(sys.argv[1]), keep / "old.s"), kernels(Path(sys.argv[2]), keep / "new.s")
+    print(f"{len(old)} kernels before, {len(new)} after")
+    print("kernel | vgpr sgpr scratch lds before -> after | instructions before -> after | histogram | sequence diff | inside loops")
+    same = 0
+    for name, (m0, o0, l0) in old.items():
+        succ = name if name in new else RENAMED.get(name, name)
+        if succ not in new:
+            print(f"{name} | MISSING after")
+            continue
+        m1, o1, l1 = new.pop(succ)
+        hist = collections.Counter(o0) == collections.Counter(o1)
+        # mnemonics removed + added by a longest-matching-blocks alignment (autojunk off: a few dozen distinct values repeat
+        # thousands of times); not a minimal edit distance, but 0 means identical and small means a few moved instructions
+        moved = lambda a, b: len(a) + len(b) - 2 * sum(m.size for m in difflib.SequenceMatcher(None, a, b, autojunk=False).get_matching_blocks())  # noqa: E731
+        diff = moved(o0, o1)
+        c0, c1 = collections.Counter(l0), collections.Counter(l1)
+        loops = f"{len(l0)} -> {len(l1)}, sequence diff {moved(l0, l1)}, " + ("same histogram" if c0 == c1 else
+                "DIFFERS " + " ".join(f"{k}:{c0[k]}->{c1[k]}" for k in sorted(set(c0) | set(c1)) if c0[k] != c1[k]))
+        regs = lambda m: " ".join(str(m[f]) for f in FIELDS)  # noqa: E731
+        same += m0 == m1 and hist and diff == 0
+        label = name if succ == name else f"{name} => {succ}"
+        print(f"{label} | {regs(m0)} -> {regs(m1)} | {len(o0)} -> {len(o1)} | {'same' if hist else 'DIFFERS'} | {diff} | {loops}")
+    for name in new:
+        print(f"{name} | NEW after")
+    print(f"{same} of {len(old)} kernels: same registers, same mnemonic sequence")
+
+
+if __name__ == "__main__":
+    main()
