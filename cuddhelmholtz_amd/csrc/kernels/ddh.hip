@@ -18,9 +18,11 @@
 // Shape of the file: every local solve is  load_dof (per-dof coefficients)  ->
 // wh_march (the WaveHoltz / RK2 time stepping around a callable `sweep(w, z)`,
 // z = S w)  ->  publish_dof (y and the trace update).  All five wavefront kernels
-// use load_dof.  ddh_wave8_kernel and ddh_mfma_kernel<Real> use wh_march and
+// use load_dof.  ddh_wave8_kernel and ddh_mfma_kernel<Real, ..> use wh_march and
 // publish_dof too and are a lane map, a sweep and an owner rule (which of the
-// copies of a shared node publishes).  ddh_wave_kernel keeps a copy of wh_march's
+// copies of a shared node publishes); the matrix-core kernel takes wh_march's
+// LEAN forms, which leave out what its register 0 never needs.
+// ddh_wave_kernel keeps a copy of wh_march's
 // loop and of publish_dof's body (on the shared ones it measured slower), and
 // ddh_general_wave_kernel a copy of the loop (through a callable sweep it was
 // not bitwise); see there.  ddh_block_kernel holds one value per
@@ -135,7 +137,13 @@ namespace
     // The WaveHoltz iterations of one local solve for the N values a lane owns: wh_iters x (restart from the filtered field,
     // nt RK2 steps with two stiffness sweeps z = S w each, filter accumulation).  Returns the filter sums u, v (v not yet
     // divided by omega: publish_dof does that).  -ffp-contract=fast turns the shape of these expressions into FMAs: keep it.
-    template <typename Real, int N, typename Sweep>
+    // LEAN (the matrix-core kernels; 0 is the form every other kernel compiles to, instruction for instruction):
+    //   != 0: the step sizes are folded into the per-dof constant (q + (half_dt invm) r instead of q + half_dt (r invm)), one
+    //         multiplication less per value and half step, and value 0 of every lane is known to be no trace dof: Hi[0] == 0
+    //         and its term is not computed;
+    //   1:    its sources F[0], Gf[0] are zero as well (no x given: sources sit on trace dofs only) and are not computed either;
+    //   2:    they are kept.
+    template <int LEAN = 0, typename Real, int N, typename Sweep>
     __device__ inline void wh_march(const DdhArgs<Real> &A, const Real *__restrict__ filt, const Real *__restrict__ cs,
                                     const Real *__restrict__ sn, const Real (&invm)[N], const Real (&Hi)[N], const Real (&F)[N],
                                     const Real (&Gf)[N], Real (&u)[N], Real (&v)[N], Sweep sweep)
@@ -145,6 +153,16 @@ namespace
         for (int l = 0; l < N; ++l)
             p[l] = q[l] = u[l] = v[l] = 0;
         const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
+        Real hm[N], dm[N]; // LEAN: half_dt invm, dt invm
+        if constexpr (LEAN != 0)
+        {
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                hm[l] = half_dt * invm[l];
+                dm[l] = dt * invm[l];
+            }
+        }
         const int nt = A.nt;
         for (int whit = 0; whit < A.wh_iters; ++whit)
         {
@@ -170,17 +188,25 @@ namespace
 #pragma unroll
                 for (int l = 0; l < N; ++l)
                 {
-                    const Real dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
+                    Real dq;
+                    if constexpr (LEAN != 0)
+                        dq = (l == 0 ? (LEAN == 2 ? z[l] + c0 * F[l] + s0 * Gf[l] : z[l]) : (z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]);
+                    else
+                        dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
                     ph[l] = p[l] - half_dt * q[l];
-                    qh[l] = q[l] + half_dt * dq;
+                    qh[l] = q[l] + (LEAN ? hm[l] : half_dt) * dq;
                     p[l] -= dt * qh[l];
                 }
                 sweep(ph, z);
 #pragma unroll
                 for (int l = 0; l < N; ++l)
                 {
-                    const Real dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
-                    q[l] += dt * dq;
+                    Real dq;
+                    if constexpr (LEAN != 0)
+                        dq = (l == 0 ? (LEAN == 2 ? z[l] + c1 * F[l] + s1 * Gf[l] : z[l]) : (z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]);
+                    else
+                        dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
+                    q[l] += (LEAN ? dm[l] : dt) * dq;
                     u[l] += kw * p[l];
                     v[l] += kw * q[l];
                 }
@@ -1074,12 +1100,21 @@ namespace
     // and U = (16 nodes) x (16 elements of the subdomain): exactly one 16x16x16 product, i.e. four
     // v_mfma_f32_16x16x4_f32 (kernel 5, Real = float) or v_mfma_f64_16x16x4_f64 (kernel 8, Real = double) per sweep on the
     // matrix pipe, leaving the VALU only the assembly and the RK2 update.
-    // Lane = element + 16 * h, register index = l (eta node): the B-operand map B[kk][j] with kk = 4 s + (lane >> 4),
-    // j = lane & 15 makes register s of a lane the node (h, l = s).  The rows of K are ordered so that the C/D map returns the
-    // result in the same layout (h = k, the xi node): m = 4 h + l for the f32 instruction (row = 4 (lane >> 4) + reg),
-    // m = k_out + 4 l_out for the f64 instruction (row = (lane >> 4) + 4 reg); build_dense_element_matrix<Real> does both, and
-    // either way the result lands in lane (el, k), register l.  In fp64 K is formed and kept in double: every operation of a
-    // sweep is fp64, the summation order alone differs from the sum-factorised kernels 1 and 2.
+    // Lane = element + 16 g, and register r of a lane holds element node node_of(g, r): the nodes are numbered by CLASS, not
+    // by eta index.  Register 0 = the four element-interior nodes, 1 = the xi-face nodes (xi index 0 or 3, eta index 1 or 2),
+    // 2 = the eta-face nodes, 3 = the corners; bit 0 of g picks the low / high xi side, bit 1 the eta side.  The matrix
+    // instruction does not care how the 16 nodes are numbered: the B operand of step st takes row kk = 4 st + (lane >> 4) from
+    // register st, i.e. node (g, r = st), and the C/D map returns row 4 (lane >> 4) + reg (fp32) or (lane >> 4) + 4 reg
+    // (fp64), so with K's columns ordered 4 r + g and its rows 4 g + r (fp32) or g + 4 r (fp64), build_dense_element_matrix,
+    // the result lands where the input was.  What the numbering buys is in the vector work around the matrix instructions:
+    //   * register 0 is shared with no other element: no assembly.  It is never a trace dof (checked when the plan is built,
+    //     ddh_interior_check_kernel): no Hi term, and without x no sources (wh_march's LEAN);
+    //   * register 1 needs the xi neighbour only, register 2 the eta neighbour only, register 3 both, xi first and eta on the
+    //     result, so every copy of a shared node forms the same commutative sums and stays bitwise equal to its twins;
+    //   * the xi partner of (el, g) is (el +- 1, g ^ 1), the eta partner (el +- 4, g ^ 2), the same lanes for both registers
+    //     of a direction: four ds_bpermute and four masked FMAs per sweep (before: four ds_bpermute, two DPP moves, six FMAs).
+    // In fp64 K is formed and kept in double: every operation of a sweep is fp64, the summation order alone differs from the
+    // sum-factorised kernels 1 and 2.
     // On gfx950 the f32 MFMA runs at the vector rate and does not overlap with VALU work, so what counts is the
     // number of issue cycles: 4 MFMAs (128 cycles) replace the ~80 VALU instructions (160 cycles + DPP hazards) of the
     // sum-factorised sweep, and the xi-neighbour exchange goes through ds_bpermute (LDS pipe, no VALU slots); a
@@ -1100,7 +1135,17 @@ namespace
     __device__ inline f4 mfma_16x16x4(float a, float b, f4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
     __device__ inline d4 mfma_16x16x4(double a, double b, d4 acc) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0); }
 
-    template <typename Real>
+    // element node (xi index k, eta index l), as k + 4 l, held by register r of the lanes with lane >> 4 == g
+    __host__ __device__ constexpr int node_of(int g, int r)
+    {
+        const int k = (r & 1) ? 3 * (g & 1) : 1 + (g & 1), l = (r & 2) ? 3 * (g >> 1) : 1 + (g >> 1);
+        return k + 4 * l;
+    }
+
+    // FORCED: x is given (rhs, postprocess), so dofs that are no trace dofs carry sources too.  HOLD: the launch holds issue
+    // priority as a whole (A.prio, multi-GPU boundary subdomains) and the sweeps do not give it back.  Both are properties of
+    // a launch and template parameters so that the time loop has no branch on them.
+    template <typename Real, bool FORCED, bool HOLD>
     __global__ void __launch_bounds__(256) ddh_mfma_kernel(DdhArgs<Real> A, const Real *__restrict__ Aop, const Real *__restrict__ filt,
                                                           const Real *__restrict__ cs, const Real *__restrict__ sn)
     {
@@ -1111,62 +1156,73 @@ namespace
         if (position >= A.dom_end)
             return; // wave-uniform, no barriers in this kernel
         const int s = domain_at(A, position);
-        raise_priority(A.prio);
+        if constexpr (HOLD)
+            __builtin_amdgcn_s_setprio(3);
 
-        const int k = lane >> 4, el = lane & 15, ex = el & 3, ey = el >> 2;
+        const int g = lane >> 4, el = lane & 15, ex = el & 3, ey = el >> 2;
         const int fdof = A.s_fdof[s];
         const int *sI = A.sI + 256 * (size_t)s;
 
         Real invm[4], Hi[4], F[4], Gf[4], u[4], v[4];
 #pragma unroll
-        for (int l = 0; l < 4; ++l)
-            load_dof(A, s, sI[k + 4 * (l + 4 * el)], fdof, invm[l], Hi[l], F[l], Gf[l]);
+        for (int r = 0; r < 4; ++r)
+            load_dof(A, s, sI[node_of(g, r) + 16 * el], fdof, invm[r], Hi[r], F[r], Gf[r]);
         Real Ka[4];
 #pragma unroll
         for (int st = 0; st < 4; ++st)
             Ka[st] = Aop[64 * st + lane];
 
-        // xi neighbours live in another 16-lane row (k = 3 of element ex meets k = 0 of element ex + 1): ds_bpermute;
-        // eta neighbours are 4 lanes away in the same row: DPP row_shl/shr:4
-        const bool hasR = (k == 3 && ex < 3), hasL = (k == 0 && ex > 0);
-        const int partner = hasR ? (el + 1) : (hasL ? (el - 1 + 48) : lane);
-        const Real mX = (hasR || hasL) ? Real(1) : Real(0);
-        const Real mU = (ey < 3) ? Real(1) : Real(0), mD = (ey > 0) ? Real(1) : Real(0);
+        // neighbours: the high xi side of element ex meets the low xi side of element ex + 1 (g ^ 1), and the same in eta
+        // with el + 4 and g ^ 2.  A lane without a neighbour reads itself and masks the value out.
+        const bool hiX = g & 1, hiY = g >> 1;
+        const bool hasX = hiX ? ex < 3 : ex > 0, hasY = hiY ? ey < 3 : ey > 0;
+        const int pX = hasX ? (hiX ? el + 1 : el - 1) + 16 * (g ^ 1) : lane;
+        const int pY = hasY ? (hiY ? el + 4 : el - 4) + 16 * (g ^ 2) : lane;
+        const Real mX = hasX ? Real(1) : Real(0), mY = hasY ? Real(1) : Real(0);
 
         auto sweep = [&](const Real(&w)[4], Real(&z)[4])
         {
             r4 acc = {0, 0, 0, 0};
-            if constexpr (PRIO)
+            if constexpr (PRIO && !HOLD)
                 __builtin_amdgcn_s_setprio(3);
 #pragma unroll
             for (int st = 0; st < 4; ++st)
                 acc = mfma_16x16x4(Ka[st], w[st], acc);
-            if constexpr (PRIO)
-                if (!A.prio) // a launch that holds issue priority as a whole (multi-GPU boundary subdomains) keeps it
-                    __builtin_amdgcn_s_setprio(0);
-            Real fx[4];
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                fx[l] = __shfl(acc[l], partner, 64);
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                z[l] = acc[l] + mX * fx[l];
-            const Real from_above = dpp_read<0x104>(z[0]); // row_shl:4 : lane + 4 = element above
-            const Real from_below = dpp_read<0x114>(z[3]); // row_shr:4
-            z[3] += mU * from_above;
-            z[0] += mD * from_below;
+            if constexpr (PRIO && !HOLD)
+                __builtin_amdgcn_s_setprio(0);
+            const Real x1 = __shfl(acc[1], pX, 64), x3 = __shfl(acc[3], pX, 64), y2 = __shfl(acc[2], pY, 64);
+            z[0] = acc[0];
+            z[1] = acc[1] + mX * x1;
+            z[2] = acc[2] + mY * y2;
+            const Real c = acc[3] + mX * x3;
+            z[3] = c + mY * __shfl(c, pY, 64);
         };
-        wh_march(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march<FORCED ? 2 : 1>(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
 
 #pragma unroll
-        for (int l = 0; l < 4; ++l)
+        for (int r = 0; r < 4; ++r)
         {
-            // every shared node is held by 2 or 4 (lane, l) pairs with identical values: the copy with
+            // every shared node is held by 2 or 4 (lane, register) pairs with identical values: the copy with
             // the smallest element-node index writes
+            const int n = node_of(g, r), k = n & 3, l = n >> 2;
             const bool owner = !(k == 0 && ex > 0) && !(l == 0 && ey > 0);
             if (owner)
-                publish_dof(A, s, sI[k + 4 * (l + 4 * el)], fdof, u[l], v[l], false);
+                publish_dof(A, s, sI[n + 16 * el], fdof, u[r], v[r], false);
         }
+    }
+
+    // kernels 5 and 8 leave the boundary terms out on the element-interior nodes (register 0): is none of them a trace dof
+    // (sI >= s_fdof) in any subdomain?  True for every plan built from blocks of elements, where trace dofs lie on the
+    // subdomain's boundary; a descriptor from elsewhere is checked, not trusted.
+    __global__ void __launch_bounds__(256) ddh_interior_check_kernel(int n_domains, const int *__restrict__ s_fdof, const int *__restrict__ sI,
+                                                                     int *__restrict__ bad)
+    {
+        const int s = blockIdx.x, tid = threadIdx.x;
+        if (s >= n_domains || tid >= 64)
+            return;
+        const int node = node_of(tid >> 4, 0) + 16 * (tid & 15);
+        if (sI[node + 256 * (size_t)s] < s_fdof[s])
+            atomicExch(bad, 1);
     }
 
     // is the metric tensor of every element of every subdomain identical to that of (subdomain 0, element 0)?  (compared in the
@@ -1519,13 +1575,22 @@ namespace
     }
 
     // Builds plan->Aop for kernel 5 (Real = float) or plan->Aop64 for kernel 8 (Real = double).  Returns 0 on success, -1 if
-    // the geometry is not uniform, > 0 on a HIP error.
+    // the geometry is not uniform or an element-interior node is a trace dof (the plan then stays on kernel 3), > 0 on a HIP
+    // error.
     template <typename Real>
     int build_dense_element_matrix(cuddh_ddh_plan *p)
     {
         const cuddh_ddh_desc &d = p->d;
         if (const int c = check_uniform_geometry<Real>(d, 16))
             return c;
+        {
+            int bad = 1;
+            const int e = device_flag_check(&bad, [&](int *flag)
+                                            { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(d.n_domains), dim3(256), 0, nullptr, d.n_domains,
+                                                                 d.s_fdof, d.sI, flag); });
+            if (e || bad)
+                return e ? e : -1;
+        }
 
         Real hD[16], hG[48];
         hipError_t e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
@@ -1564,18 +1629,18 @@ namespace
                     K[k + 4 * l][nin] = su;
                 }
         }
-        // A operand of step st, lane ln:  A[i = ln & 15][kk = 4 st + (ln >> 4)] = K'[m = i][nu = kk], nu = 4 l_in + k_in.
-        // The output row order follows the C/D map: m = 4 k_out + l_out for v_mfma_f32_16x16x4_f32 (row = 4 (lane >> 4) + reg),
-        // m = k_out + 4 l_out for v_mfma_f64_16x16x4_f64 (row = (lane >> 4) + 4 reg); either way lane (el, k) gets node (k, l)
-        // in register l.
+        // A operand of step st, lane ln:  A[i = ln & 15][kk = 4 st + (ln >> 4)] = K'[m = i][nu = kk].  Columns: nu = 4 r_in + g_in
+        // is node_of(g_in, r_in).  Rows follow the C/D map: m = 4 g_out + r_out for v_mfma_f32_16x16x4_f32
+        // (row = 4 (lane >> 4) + reg), m = g_out + 4 r_out for v_mfma_f64_16x16x4_f64 (row = (lane >> 4) + 4 reg); either way
+        // lane (el, g) gets node_of(g, r) in register r.
         constexpr bool F64 = sizeof(Real) == 8;
         Real hA[256];
         for (int st = 0; st < 4; ++st)
             for (int ln = 0; ln < 64; ++ln)
             {
                 const int m = ln & 15, nu = 4 * st + (ln >> 4);
-                const int k_out = F64 ? (m & 3) : (m >> 2), l_out = F64 ? (m >> 2) : (m & 3), l_in = nu >> 2, k_in = nu & 3;
-                hA[64 * st + ln] = static_cast<Real>(K[k_out + 4 * l_out][k_in + 4 * l_in]);
+                const int g_out = F64 ? (m & 3) : (m >> 2), r_out = F64 ? (m >> 2) : (m & 3), r_in = nu >> 2, g_in = nu & 3;
+                hA[64 * st + ln] = static_cast<Real>(K[node_of(g_out, r_out)][node_of(g_in, r_in)]);
             }
         Real *dA = nullptr;
         e = hipMalloc(reinterpret_cast<void **>(&dA), sizeof hA);
@@ -1642,6 +1707,28 @@ namespace
         if (e == hipSuccess)
             e = hipMemcpy(p->Sep, hS, sizeof hS, hipMemcpyHostToDevice);
         return static_cast<int>(e);
+    }
+
+    // kernels 5 and 8: the instantiation for this launch's two fixed properties (ddh_mfma_kernel)
+    template <typename Real>
+    void launch_mfma(const DdhArgs<Real> &A, const void *Aop, dim3 grid, dim3 block, hipStream_t st, const Real *fl, const Real *cs,
+                     const Real *sn)
+    {
+        const Real *K = static_cast<const Real *>(Aop);
+        if (A.x)
+        {
+            if (A.prio)
+                hipLaunchKernelGGL((ddh_mfma_kernel<Real, true, true>), grid, block, 0, st, A, K, fl, cs, sn);
+            else
+                hipLaunchKernelGGL((ddh_mfma_kernel<Real, true, false>), grid, block, 0, st, A, K, fl, cs, sn);
+        }
+        else
+        {
+            if (A.prio)
+                hipLaunchKernelGGL((ddh_mfma_kernel<Real, false, true>), grid, block, 0, st, A, K, fl, cs, sn);
+            else
+                hipLaunchKernelGGL((ddh_mfma_kernel<Real, false, false>), grid, block, 0, st, A, K, fl, cs, sn);
+        }
     }
 
     template <typename Real>
@@ -1719,10 +1806,7 @@ namespace
         case 8:
             if ((plan->kernel == 5) != f32) // plan_create ties kernel 5 to fp32 (Aop) and kernel 8 to fp64 (Aop64)
                 return static_cast<int>(hipErrorInvalidValue);
-            if constexpr (f32)
-                hipLaunchKernelGGL(ddh_mfma_kernel<float>, grid, block, 0, st, A, plan->Aop, fl, cs, sn);
-            else
-                hipLaunchKernelGGL(ddh_mfma_kernel<double>, grid, block, 0, st, A, plan->Aop64, fl, cs, sn);
+            launch_mfma(A, f32 ? static_cast<const void *>(plan->Aop) : static_cast<const void *>(plan->Aop64), grid, block, st, fl, cs, sn);
             break;
         case 6:
         case 7:

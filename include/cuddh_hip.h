@@ -279,15 +279,16 @@ typedef struct cuddh_ddh_plan cuddh_ddh_plan;
  *         3 = wave with the DPP reads folded into the FMAs by hand (fp32; what auto picks when it applies),
  *         4 = 3 with the in-lane contractions on the matrix pipe (v_mfma_f32_4x4x1_16b_f32, fp32),
  *         5 = one 16x16 element matrix applied to the 16 elements of a subdomain per sweep with four
- *             v_mfma_f32_16x16x4_f32 (fp32; needs the same metric tensor in every element, which
- *             plan_create verifies on the device; what auto picks when it applies),
+ *             v_mfma_f32_16x16x4_f32 (fp32; needs the same metric tensor in every element and no trace dof
+ *             (sI < s_fdof) on an element-interior node, both of which plan_create verifies on the device;
+ *             what auto picks when it applies, otherwise 3),
  *         6 = n_basis == 8 (2x2 elements, the reference's other supported shape): one wavefront per TWO
  *             subdomains, registers + DPP over the eight lanes of a column octet,
  *         7 = 6 in separable form (fp32): on the rectangles of a uniform mesh the metric is diagonal and a product of
  *             1-D factors, so a sweep needs ONE 8x8 contraction per direction (D^T diag D precomputed) instead of two
  *             (plan_create verifies the geometry; what auto picks for nb == 8 when it applies),
  *         8 = 5 in fp64 (four v_mfma_f64_16x16x4_f64 per sweep, element matrix formed and kept in double; is_f64, nb == 4
- *             and nel1d == 4 only, same metric tensor in every element, which plan_create verifies on the device;
+ *             and nel1d == 4 only, same two conditions as 5, which plan_create verifies on the device;
  *             on request only: auto keeps fp64 on 3; hipErrorInvalidValue where it does not apply, like 5). */
 int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int is_f64, int kernel);
 /* Plan for subdomains of ANY element connectivity (subdomains given by element labels; desc->nel1d is ignored and

@@ -18,7 +18,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 from cuddhelmholtz_amd import build as B  # noqa: E402
 
 # kernels whose symbol changed: demangled name (without the argument list) in OLD -> in NEW
-RENAMED = {"ddh_mfma_kernel": "ddh_mfma_kernel<float>", "ddh_mfma64_kernel": "ddh_mfma_kernel<double>"}
+RENAMED = {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, false>", "ddh_mfma_kernel<double>": "ddh_mfma_kernel<double, false, false>"}
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
