@@ -164,6 +164,8 @@ _sig("cuddh_hip_ddh_plan_destroy", ci, vp)
 _sig("cuddh_hip_ddh_plan_kernel", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_wh_iters", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_set_wave_priority", ci, vp, ci)
+_sig("cuddh_hip_ddh_plan_set_sweep_form", ci, vp, ci)
+_sig("cuddh_hip_ddh_plan_sweep_form", ci, vp)
 _sig("cuddh_hip_ddh_apply_list_f32", ci, vp, vp, ci, vp, vp, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_apply_list_f64", ci, vp, vp, ci, vp, vp, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_set_vector_layout", ci, vp, vp, ci)
@@ -239,6 +241,8 @@ _sig("cuddh_ddh_size", ci, vp)
 _sig("cuddh_ddh_info", ci, vp, vp, vp)
 _sig("cuddh_ddh_set_wh_iters", ci, vp, ci)
 _sig("cuddh_ddh_set_wave_priority", ci, vp, ci)
+_sig("cuddh_ddh_set_sweep_form", ci, vp, ci)
+_sig("cuddh_ddh_sweep_form", ci, vp)
 
 
 class MultiGpuResult(C.Structure):

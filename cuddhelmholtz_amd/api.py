@@ -477,6 +477,19 @@ class DDH:
         """Verification knob: WaveHoltz iterations per local solve (reference: 5, source/DDH.cpp:136)."""
         N.check_capi(lib.cuddh_ddh_set_wh_iters(self._h, int(n)), "DDH.set_wh_iters")
 
+    def set_sweep_form(self, form: int = 0):
+        """Kernel 5's sweep, for every launch of this plan: 0 auto, 1 matrix form, 2 element-lane form, 3 the same with the
+        other copy of every shared node publishing (a check: same results).  2 and 3 are refused where the plan cannot take them
+        (cuddh_hip_ddh_plan_set_sweep_form)."""
+        N.check_capi(lib.cuddh_ddh_set_sweep_form(self._h, int(form)), "DDH.set_sweep_form")
+
+    def sweep_form(self) -> int:
+        """The form in effect: 1 matrix, 2 element-lane (3 if requested); 0 when the plan is not kernel 5."""
+        form = lib.cuddh_ddh_sweep_form(self._h)
+        if form < 0:
+            N.check_capi(form, "DDH.sweep_form")
+        return form
+
     def set_wave_priority(self, high: bool):
         """The local solves launched next take issue priority over other resident wavefronts (s_setprio); results unchanged."""
         N.check_capi(lib.cuddh_ddh_set_wave_priority(self._h, 1 if high else 0), "DDH.set_wave_priority")

@@ -54,6 +54,10 @@ namespace cuddh
             /// The wavefronts of the following solve() calls take issue priority over other resident work (s_setprio): for the
             /// multi-GPU schedule that runs the subdomains other ranks wait for beside the rest (cuddh_hip_ddh_plan_set_wave_priority).
             void set_wave_priority(bool high) const;
+            /// Kernel 5's sweep form: 0 auto, 1 matrix, 2 element-lane, 3 the same with the other owner rule (cuddh_hip_ddh_plan_set_sweep_form; a form the plan
+            /// cannot take throws).  sweep_form() returns the form in effect.
+            void set_sweep_form(int form) const;
+            int sweep_form() const;
             const EnsembleSpace &ensemble() const { return *efem; }
 
             /// runs the local solves of subdomains [dom_begin, dom_end)

@@ -17,11 +17,13 @@
 //
 // Shape of the file: every local solve is  load_dof (per-dof coefficients)  ->
 // wh_march (the WaveHoltz / RK2 time stepping around a callable `sweep(w, z)`,
-// z = S w)  ->  publish_dof (y and the trace update).  All five wavefront kernels
-// use load_dof.  ddh_wave8_kernel and ddh_mfma_kernel<Real, ..> use wh_march and
-// publish_dof too and are a lane map, a sweep and an owner rule (which of the
-// copies of a shared node publishes); the matrix-core kernel takes wh_march's
-// LEAN forms, which leave out what its register 0 never needs.
+// z = S w)  ->  publish_dof (y and the trace update).  All six wavefront kernels
+// use load_dof.  ddh_wave8_kernel, ddh_mfma_kernel<Real, ..> and
+// ddh_element_lane_kernel (kernel 5's second sweep form: one element per lane,
+// four subdomains per wavefront) use wh_march and publish_dof too and are a lane
+// map, a sweep and an owner rule (which of the copies of a shared node
+// publishes); the matrix-core and element-lane kernels take wh_march's LEAN
+// forms, which leave out what their element-interior registers never need.
 // ddh_wave_kernel keeps a copy of wh_march's
 // loop and of publish_dof's body (on the shared ones it measured slower), and
 // ddh_general_wave_kernel a copy of the loop (through a callable sweep it was
@@ -54,6 +56,8 @@ struct cuddh_ddh_plan
     float *Aop = nullptr; // kernel 5: element stiffness matrix as MFMA A operands, [4 k-steps][64 lanes]
     double *Aop64 = nullptr; // kernel 8: the same in fp64, rows in the f64 MFMA's output order (build_dense_element_matrix)
     float *Sep = nullptr; // kernel 7: [Ax | Ay | beta | gamma] of the separable nb = 8 sweep
+    float *Sep4 = nullptr; // kernel 5, element-lane form: [Bx | By | Dg | W | 1 / W] (build_element_lane_tables); null: does not qualify
+    int sweep_form = 0; // kernel 5: 0 auto, 1 matrix form, 2 element-lane form, 3 the same with the other owner rule (cuddh_hip_ddh_plan_set_sweep_form)
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
     int *csr_off = nullptr, *csr_src = nullptr;
@@ -139,11 +143,12 @@ namespace
     // divided by omega: publish_dof does that).  -ffp-contract=fast turns the shape of these expressions into FMAs: keep it.
     // LEAN (the matrix-core kernels; 0 is the form every other kernel compiles to, instruction for instruction):
     //   != 0: the step sizes are folded into the per-dof constant (q + (half_dt invm) r instead of q + half_dt (r invm)), one
-    //         multiplication less per value and half step, and value 0 of every lane is known to be no trace dof: Hi[0] == 0
-    //         and its term is not computed;
-    //   1:    its sources F[0], Gf[0] are zero as well (no x given: sources sit on trace dofs only) and are not computed either;
+    //         multiplication less per value and half step, and the values l with bit l of INTERIOR set (value 0 of every lane
+    //         in the matrix-core kernels, the four element-interior registers of the element-lane kernel) are known to be no
+    //         trace dofs: Hi[l] == 0 and its term is not computed;
+    //   1:    their sources F[l], Gf[l] are zero as well (no x given: sources sit on trace dofs only) and are not computed either;
     //   2:    they are kept.
-    template <int LEAN = 0, typename Real, int N, typename Sweep>
+    template <int LEAN = 0, unsigned INTERIOR = 1u, typename Real, int N, typename Sweep>
     __device__ inline void wh_march(const DdhArgs<Real> &A, const Real *__restrict__ filt, const Real *__restrict__ cs,
                                     const Real *__restrict__ sn, const Real (&invm)[N], const Real (&Hi)[N], const Real (&F)[N],
                                     const Real (&Gf)[N], Real (&u)[N], Real (&v)[N], Sweep sweep)
@@ -190,7 +195,7 @@ namespace
                 {
                     Real dq;
                     if constexpr (LEAN != 0)
-                        dq = (l == 0 ? (LEAN == 2 ? z[l] + c0 * F[l] + s0 * Gf[l] : z[l]) : (z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]);
+                        dq = (((INTERIOR >> l) & 1u) ? (LEAN == 2 ? z[l] + c0 * F[l] + s0 * Gf[l] : z[l]) : (z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]);
                     else
                         dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
                     ph[l] = p[l] - half_dt * q[l];
@@ -203,7 +208,7 @@ namespace
                 {
                     Real dq;
                     if constexpr (LEAN != 0)
-                        dq = (l == 0 ? (LEAN == 2 ? z[l] + c1 * F[l] + s1 * Gf[l] : z[l]) : (z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]);
+                        dq = (((INTERIOR >> l) & 1u) ? (LEAN == 2 ? z[l] + c1 * F[l] + s1 * Gf[l] : z[l]) : (z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]);
                     else
                         dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
                     q[l] += (LEAN ? dm[l] : dt) * dq;
@@ -1211,6 +1216,163 @@ namespace
         }
     }
 
+    // ---------------------------------------------------------------- kernel 5, element-lane form (NB = 4, rectangles): four subdomains per wavefront
+    // On rectangles the element matrix is a sum of two Kronecker terms (the separable form of kernel 7),
+    //     z(k,l) = beta_l sum_j Ax(k,j) w(j,l) + gamma_k sum_j Ay(l,j) w(k,j):
+    // 7 non-zeros per row where the dense product of ddh_mfma_kernel multiplies 16.  Lane = one whole ELEMENT, ex + 4 ey, one
+    // subdomain per 16-lane row, four subdomains per wavefront; register n = k + 4 l holds the element's node (k, l).  Both
+    // contractions are then in-lane full-rate FMAs with scalar-register coefficients, and the matrix pipe and LDS are not
+    // used.  To keep the coefficients within the scalar registers the node weight W(k,l) = gamma_k beta_l is factored out of
+    // both terms, z = W z',
+    //     z'(k,l) = Dg(k,l) w(k,l) + sum_{j != k} Bx(k,j) w(j,l) + sum_{j != l} By(l,j) w(k,j),
+    // Bx = Ax / gamma_k, By = Ay / beta_l, Dg = Bx(k,k) + By(l,l): 12 + 12 + 16 scalars.  All copies of a shared dof carry
+    // the same W (checked when the plan is built), so the assembled sum is W sum z' and W moves into the per-dof constants:
+    // invm is multiplied by it, Hi, F and Gf are divided.  Assembly is the only cross-lane work: xi neighbours are lane +- 1,
+    // eta neighbours lane +- 4, DPP row shifts that never leave the 16-lane row, so a subdomain's result does not depend on
+    // its wave-mates.  Masked FMAs, xi first and eta on the result, so the copies of a shared node form the same commutative
+    // sums and stay bitwise equal.  Registers with k, l in {1, 2} are element-interior: wh_march's LEAN rules apply to them.
+    // A launch whose length is no multiple of 4 is handled as ddh_wave8_kernel handles its odd tail: the missing rows
+    // recompute the wavefront's first subdomain and publish nothing.
+    // The action form (no x) is compiled for three wavefronts per SIMD (167 VGPRs, no scratch), the form with x (rhs,
+    // postprocess: once per solve) needs 196 and is compiled for two.  The assembly has its DPP reads folded into the
+    // arithmetic by hand (below).  Measured at 65,536 subdomains, ms per action (profiles/r08/element_lane_variants.txt):
+    // two wavefronts and dpp_read + FMA 271.3, three wavefronts 268.2, folded 265.7, both 258.6; the matrix form 273.9.
+    // LAST_COPY (cuddh_hip_ddh_plan_set_sweep_form(plan, 3)) turns the owner rule round, so that a test can see the other
+    // copies: the results are bitwise the same.
+    // Assembly of four node pairs with the cross-lane reads folded into the arithmetic :
+    // hi[i] += mHi * (lo[i] of lane + SHIFT), lo[i] += mLo * (hi[i] of lane - SHIFT), both from the values before the call.
+    // 12 instructions where the plain form has 8 v_mov_b32_dpp and 8 FMAs; the masks are 0 or 1, so the sums are the same.
+#define CUDDH_EL_ASSEMBLE(NAME, SHL, SHR)                                                                                                  \
+    __device__ inline void NAME(float (&hi)[4], float (&lo)[4], float mHi, float mLo)                                                      \
+    {                                                                                                                                      \
+        float t0, t1, t2, t3;                                                                                                              \
+        asm volatile("s_nop 1\n\t"                                                                                                         \
+                     "v_mul_f32_dpp %8, %0, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                       \
+                     "v_mul_f32_dpp %9, %1, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                       \
+                     "v_mul_f32_dpp %10, %2, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_mul_f32_dpp %11, %3, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_fmac_f32_dpp %0, %4, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_fmac_f32_dpp %1, %5, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_fmac_f32_dpp %2, %6, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_fmac_f32_dpp %3, %7, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_add_f32 %4, %4, %8\n\t"                                                                                            \
+                     "v_add_f32 %5, %5, %9\n\t"                                                                                            \
+                     "v_add_f32 %6, %6, %10\n\t"                                                                                           \
+                     "v_add_f32 %7, %7, %11\n\t"                                                                                           \
+                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "=&v"(t0),   \
+                       "=&v"(t1), "=&v"(t2), "=&v"(t3)                                                                                     \
+                     : "v"(mHi), "v"(mLo));                                                                                                \
+    }
+    CUDDH_EL_ASSEMBLE(element_assemble_xi_asm, "row_shl:1", "row_shr:1")
+    CUDDH_EL_ASSEMBLE(element_assemble_eta_asm, "row_shl:4", "row_shr:4")
+#undef CUDDH_EL_ASSEMBLE
+    constexpr unsigned ELEMENT_INTERIOR_REGISTERS = (1u << 5) | (1u << 6) | (1u << 9) | (1u << 10);
+
+    template <bool FORCED, bool HOLD, bool LAST_COPY>
+    __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
+                                                                     const float *__restrict__ cs, const float *__restrict__ sn)
+    {
+        const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
+        if (s_first >= A.dom_end)
+            return; // wave-uniform: the kernel has no barriers
+        if constexpr (HOLD)
+            __builtin_amdgcn_s_setprio(3);
+        // where this lane works: subdomain s (valid: and publishes it), its trace dofs, the dofs of its element's nodes
+        auto locate = [&](int tid, bool &valid, int &s, int &fdof, const int *&sI)
+        {
+            const int sub = (tid >> 4) & 3;
+            valid = s_first + sub < A.dom_end;
+            s = domain_at(A, valid ? s_first + sub : s_first);
+            fdof = A.s_fdof[s];
+            sI = A.sI + 256 * (size_t)s + 16 * (tid & 15);
+        };
+        bool valid;
+        int s, fdof;
+        const int *sI;
+        locate(threadIdx.x, valid, s, fdof, sI);
+        const int el = threadIdx.x & 15, ex = el & 3, ey = el >> 2;
+
+        float invm[16], Hi[16], F[16], Gf[16], u[16], v[16];
+#pragma unroll
+        for (int n = 0; n < 16; ++n)
+        {
+            load_dof(A, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
+            const float W = Sep4[48 + n], rW = Sep4[64 + n];
+            invm[n] *= W;
+            Hi[n] *= rW;
+            F[n] *= rW;
+            Gf[n] *= rW;
+        }
+        float Bx[16], By[16], Dg[16]; // wave-uniform: scalar registers for the whole time loop
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+        {
+            Bx[i] = Sep4[i];      // Bx(k, j) at k + 4 j
+            By[i] = Sep4[16 + i]; // By(l, j) at l + 4 j
+            Dg[i] = Sep4[32 + i]; // Dg(k, l) at k + 4 l
+        }
+        const float mR = ex < 3 ? 1.0f : 0.0f, mL = ex > 0 ? 1.0f : 0.0f, mU = ey < 3 ? 1.0f : 0.0f, mD = ey > 0 ? 1.0f : 0.0f;
+
+        auto sweep = [&](const float(&w)[16], float(&z)[16])
+        {
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                {
+                    float t = Dg[k + 4 * l] * w[k + 4 * l];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                    {
+                        if (j != k)
+                            t += Bx[k + 4 * j] * w[j + 4 * l];
+                        if (j != l)
+                            t += By[l + 4 * j] * w[k + 4 * j];
+                    }
+                    z[k + 4 * l] = t;
+                }
+            // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa)
+            float hi[4] = {z[3], z[7], z[11], z[15]}, lo[4] = {z[0], z[4], z[8], z[12]};
+            element_assemble_xi_asm(hi, lo, mR, mL);
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+            {
+                z[3 + 4 * l] = hi[l];
+                z[0 + 4 * l] = lo[l];
+            }
+            // eta neighbours, on the xi-assembled values: my l == 3 row meets the l == 0 row of lane + 4
+            float up[4] = {z[12], z[13], z[14], z[15]}, dn[4] = {z[0], z[1], z[2], z[3]};
+            element_assemble_eta_asm(up, dn, mU, mD);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+            {
+                z[k + 12] = up[k];
+                z[k] = dn[k];
+            }
+        };
+        wh_march<FORCED ? 2 : 1, ELEMENT_INTERIOR_REGISTERS>(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+
+        // located a second time from a lane index the compiler cannot connect with the first: otherwise these values stay
+        // in (or are spilled from) vector registers for the whole time loop, which runs at the limit of three wavefronts per SIMD
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        locate(tid, valid, s, fdof, sI);
+        if (!valid)
+            return;
+#pragma unroll
+        for (int n = 0; n < 16; ++n)
+        {
+            // every shared node is held by 2 or 4 (lane, register) pairs with identical values: the copy with
+            // the smallest element-node index writes (with LAST_COPY the one with the largest)
+            const int k = n & 3, l = n >> 2;
+            const bool first = !(k == 0 && (tid & 3) > 0) && !(l == 0 && (tid & 12) > 0);
+            const bool last = !(k == 3 && (tid & 3) < 3) && !(l == 3 && (tid & 12) < 12);
+            const bool owner = LAST_COPY ? last : first;
+            if (owner)
+                publish_dof(A, s, sI[n], fdof, u[n], v[n], false);
+        }
+    }
+
     // kernels 5 and 8 leave the boundary terms out on the element-interior nodes (register 0): is none of them a trace dof
     // (sI >= s_fdof) in any subdomain?  True for every plan built from blocks of elements, where trace dofs lie on the
     // subdomain's boundary; a descriptor from elsewhere is checked, not trusted.
@@ -1653,60 +1815,168 @@ namespace
         return static_cast<int>(e);
     }
 
-    // kernel 7 tables: needs one metric tensor for all elements, diagonal (gy == 0) and a product of 1-D factors
-    // (rectangles).  Returns 0 on success, -1 when the geometry does not qualify, > 0 on a HIP error.
-    int build_separable_tables(cuddh_ddh_plan *p)
+    // The separable sweep's factors (kernel 7, NB = 8; kernel 5's element-lane form, NB = 4), in double, from the metric
+    // tensor of element 0, which the caller has found to be that of all elements (check_uniform_geometry): needs it
+    // diagonal (gy == 0) and a product of 1-D factors, gx(k,l) = alpha_k beta_l, gz(k,l) = gamma_k delta_l (rectangles).  Ax = D^T diag(alpha) D, Ay = D^T diag(delta) D.  Returns 0 on success, -1
+    // when the geometry does not qualify, > 0 on a HIP error.
+    template <int NB>
+    int separable_factors(const cuddh_ddh_desc &d, double (&Ax)[NB][NB], double (&Ay)[NB][NB], double (&beta)[NB], double (&gamma)[NB])
     {
-        const cuddh_ddh_desc &d = p->d;
-        if (const int c = check_uniform_geometry<float>(d, 64))
-            return c;
-        float hD[64], hG[192];
+        constexpr int NN = NB * NB;
+        float hD[NN], hG[3 * NN];
         hipError_t e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
         if (e == hipSuccess)
             e = hipMemcpy(hG, d.G, sizeof hG, hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             return static_cast<int>(e);
-        auto Dm = [&](int a, int b) { return static_cast<double>(hD[a + 8 * b]); }; // D(a,b)
-        auto g = [&](int c, int k, int l) { return static_cast<double>(hG[3 * (k + 8 * l) + c]); };
+        auto Dm = [&](int a, int b) { return static_cast<double>(hD[a + NB * b]); }; // D(a,b)
+        auto g = [&](int c, int k, int l) { return static_cast<double>(hG[3 * (k + NB * l) + c]); };
         double scale = 0.0;
-        for (int n = 0; n < 64; ++n)
+        for (int n = 0; n < NN; ++n)
             scale = std::max(scale, std::fabs(static_cast<double>(hG[3 * n])) + std::fabs(static_cast<double>(hG[3 * n + 2])));
-        double alpha[8], beta[8], gamma[8], delta[8];
-        for (int i = 0; i < 8; ++i)
+        double alpha[NB], delta[NB];
+        for (int i = 0; i < NB; ++i)
         {
             alpha[i] = g(0, i, 0);
             beta[i] = g(0, 0, i) / g(0, 0, 0);
             gamma[i] = g(2, i, 0) / g(2, 0, 0);
             delta[i] = g(2, 0, i);
         }
-        for (int l = 0; l < 8; ++l)
-            for (int k = 0; k < 8; ++k)
+        for (int l = 0; l < NB; ++l)
+            for (int k = 0; k < NB; ++k)
                 if (std::fabs(g(1, k, l)) > 1e-6 * scale || std::fabs(g(0, k, l) - alpha[k] * beta[l]) > 1e-6 * scale ||
                     std::fabs(g(2, k, l) - gamma[k] * delta[l]) > 1e-6 * scale)
                     return -1;
-        float hS[144] = {0};
-        for (int a = 0; a < 8; ++a)
-            for (int b = 0; b < 8; ++b)
+        for (int a = 0; a < NB; ++a)
+            for (int b = 0; b < NB; ++b)
             {
                 double ax = 0.0, ay = 0.0;
-                for (int i = 0; i < 8; ++i)
+                for (int i = 0; i < NB; ++i)
                 {
                     ax += Dm(i, a) * alpha[i] * Dm(i, b);
                     ay += Dm(i, a) * delta[i] * Dm(i, b);
                 }
-                hS[a + 8 * b] = static_cast<float>(ax);
+                Ax[a][b] = ax;
+                Ay[a][b] = ay;
+            }
+        return 0;
+    }
+
+    template <size_t N>
+    int upload_table(float **dst, const float (&h)[N])
+    {
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), sizeof h);
+        if (e == hipSuccess)
+            e = hipMemcpy(*dst, h, sizeof h, hipMemcpyHostToDevice);
+        return static_cast<int>(e);
+    }
+
+    // kernel 7 tables.  Returns 0 on success, -1 when the geometry does not qualify, > 0 on a HIP error.
+    int build_separable_tables(cuddh_ddh_plan *p)
+    {
+        double Ax[8][8], Ay[8][8], beta[8], gamma[8];
+        if (const int c = check_uniform_geometry<float>(p->d, 64))
+            return c;
+        if (const int c = separable_factors<8>(p->d, Ax, Ay, beta, gamma))
+            return c;
+        float hS[144] = {0};
+        for (int a = 0; a < 8; ++a)
+            for (int b = 0; b < 8; ++b)
+            {
+                hS[a + 8 * b] = static_cast<float>(Ax[a][b]);
                 if (a <= b)
-                    hS[64 + sym_index(a, b)] = static_cast<float>(ay); // Ay(a,b) == Ay(b,a)
+                    hS[64 + sym_index(a, b)] = static_cast<float>(Ay[a][b]); // Ay(a,b) == Ay(b,a)
             }
         for (int i = 0; i < 8; ++i)
         {
             hS[128 + i] = static_cast<float>(beta[i]);
             hS[136 + i] = static_cast<float>(gamma[i]);
         }
-        e = hipMalloc(reinterpret_cast<void **>(&p->Sep), sizeof hS);
-        if (e == hipSuccess)
-            e = hipMemcpy(p->Sep, hS, sizeof hS, hipMemcpyHostToDevice);
-        return static_cast<int>(e);
+        return upload_table(&p->Sep, hS);
+    }
+
+    // Tables of kernel 5's element-lane form (ddh_element_lane_kernel), n_basis 4: the same checks as kernel 7's, and that
+    // the node weight W(k,l) = gamma_k beta_l is positive and the same on both sides of every shared edge, W(3,l) = W(0,l)
+    // and W(k,3) = W(k,0) (all elements are identical, so that covers every copy of every shared dof).  The per-dof constants
+    // take the weight of the copy with index 0 in place of 3, so the copies of a dof scale by one and the same float.
+    // Sep4 = [Bx(k,j) at k + 4 j: 16 | By(l,j) at l + 4 j: 16 | Dg(k,l) at k + 4 l: 16 | W: 16 | 1 / W: 16].  Returns 0 on success,
+    // -1 when the geometry does not qualify (p->Sep4 stays null: the plan stays on the matrix form), > 0 on a HIP error.
+    // Called after build_dense_element_matrix has succeeded, which has checked that all elements share one metric.
+    int build_element_lane_tables(cuddh_ddh_plan *p)
+    {
+        double Ax[4][4], Ay[4][4], beta[4], gamma[4];
+        if (const int c = separable_factors<4>(p->d, Ax, Ay, beta, gamma))
+            return c;
+        double W[4][4], wmax = 0.0;
+        for (int k = 0; k < 4; ++k)
+            for (int l = 0; l < 4; ++l)
+            {
+                W[k][l] = gamma[k] * beta[l];
+                if (!(W[k][l] > 0.0) || !std::isfinite(W[k][l]))
+                    return -1;
+                wmax = std::max(wmax, W[k][l]);
+            }
+        for (int i = 0; i < 4; ++i)
+            if (!(std::fabs(W[3][i] - W[0][i]) <= 1e-6 * wmax) || !(std::fabs(W[i][3] - W[i][0]) <= 1e-6 * wmax))
+                return -1;
+        float hS[80];
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b)
+            {
+                const double bx = Ax[a][b] / gamma[a], by = Ay[a][b] / beta[a];
+                hS[a + 4 * b] = static_cast<float>(bx);
+                hS[16 + a + 4 * b] = static_cast<float>(by);
+                hS[32 + a + 4 * b] = static_cast<float>(Ax[a][a] / gamma[a] + Ay[b][b] / beta[b]);
+                const double w = W[a == 3 ? 0 : a][b == 3 ? 0 : b];
+                hS[48 + a + 4 * b] = static_cast<float>(w);
+                hS[64 + a + 4 * b] = static_cast<float>(1.0 / w);
+            }
+        for (int i = 0; i < 80; ++i)
+            if (!std::isfinite(hS[i]))
+                return -1;
+        return upload_table(&p->Sep4, hS);
+    }
+
+    // kernel 5 plans with fewer subdomains than this stay on the matrix form under auto: the element-lane form puts four
+    // subdomains into a wavefront, so a small plan leaves SIMDs empty that the matrix form would use.  Measured on one MI355X
+    // (profiles/r08/ddh_rates_by_form.txt, three rounds per size): 1,024 subdomains 8.8 / 20.4 ms per action (matrix /
+    // element-lane), 4,096 19.7 / 20.5, 8,192 73.8 / 71.6, 16,384 70.6 / 68.1, 65,536 273.6 / 260.4.  8,192 is the smallest
+    // measured size at which the element-lane form won every round, not a crossover: nothing was measured between 4,096 and
+    // 8,192, and the 8,192 case is another problem (256 x 512 rectangular elements, nt 10,240).  The form belongs to the plan,
+    // so a small launch of a large plan (a few subdomains, the rim launch of a multi-GPU schedule) runs four subdomains per
+    // wavefront as well, at a size where this form measured slower on its own.
+    constexpr int ELEMENT_LANE_MIN_DOMAINS = 8192;
+
+    // the form a kernel-5 plan's launches take: 1 matrix, 2 element-lane (3 on request only: the last copy publishes).  A property of the plan alone, never of a launch:
+    // differently partitioned launches of one plan are compared bitwise.
+    int effective_sweep_form(const cuddh_ddh_plan *p)
+    {
+        if (p->kernel != 5)
+            return 0;
+        if (p->sweep_form != 0)
+            return p->sweep_form;
+        return p->Sep4 && p->d.n_domains >= ELEMENT_LANE_MIN_DOMAINS ? 2 : 1;
+    }
+
+    template <bool LAST_COPY>
+    void launch_element_lane(const DdhArgs<float> &A, const float *Sep4, int n_local, hipStream_t st, const float *fl, const float *cs,
+                             const float *sn)
+    {
+        const dim3 grid((n_local + 15) / 16), block(256); // four subdomains per wavefront, four wavefronts per workgroup
+        if (A.x)
+        {
+            if (A.prio)
+                hipLaunchKernelGGL((ddh_element_lane_kernel<true, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+            else
+                hipLaunchKernelGGL((ddh_element_lane_kernel<true, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+        }
+        else
+        {
+            if (A.prio)
+                hipLaunchKernelGGL((ddh_element_lane_kernel<false, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+            else
+                hipLaunchKernelGGL((ddh_element_lane_kernel<false, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+        }
     }
 
     // kernels 5 and 8: the instantiation for this launch's two fixed properties (ddh_mfma_kernel)
@@ -1806,6 +2076,15 @@ namespace
         case 8:
             if ((plan->kernel == 5) != f32) // plan_create ties kernel 5 to fp32 (Aop) and kernel 8 to fp64 (Aop64)
                 return static_cast<int>(hipErrorInvalidValue);
+            if constexpr (f32)
+                if (const int form = effective_sweep_form(plan); form >= 2)
+                {
+                    if (form == 3)
+                        launch_element_lane<true>(A, plan->Sep4, n_local, st, fl, cs, sn);
+                    else
+                        launch_element_lane<false>(A, plan->Sep4, n_local, st, fl, cs, sn);
+                    break;
+                }
             launch_mfma(A, f32 ? static_cast<const void *>(plan->Aop) : static_cast<const void *>(plan->Aop64), grid, block, st, fl, cs, sn);
             break;
         case 6:
@@ -1944,7 +2223,15 @@ extern "C"
             {
                 int err5 = build_dense_element_matrix<float>(p);
                 if (err5 == 0)
+                {
                     p->kernel = 5;
+                    const int err_el = build_element_lane_tables(p); // -1: the plan stays on the matrix form
+                    if (err_el > 0)
+                    {
+                        cuddh_hip_ddh_plan_destroy(p);
+                        return err_el;
+                    }
+                }
                 else if (kernel == 5)
                 {
                     delete p;
@@ -2057,6 +2344,8 @@ extern "C"
             (void)hipFree(plan->Aop64);
         if (plan && plan->Sep)
             (void)hipFree(plan->Sep);
+        if (plan && plan->Sep4)
+            (void)hipFree(plan->Sep4);
         delete plan;
         return 0;
     }
@@ -2087,6 +2376,18 @@ extern "C"
         plan->wh_iters = wh_iters == 0 ? WH_ITERS_REFERENCE : wh_iters;
         return 0;
     }
+
+    int cuddh_hip_ddh_plan_set_sweep_form(cuddh_ddh_plan *plan, int form)
+    {
+        if (!plan || form < 0 || form > 3)
+            return static_cast<int>(hipErrorInvalidValue);
+        if (form >= 2 && (plan->kernel != 5 || !plan->Sep4))
+            return static_cast<int>(hipErrorInvalidValue);
+        plan->sweep_form = form;
+        return 0;
+    }
+
+    int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan) { return plan ? effective_sweep_form(plan) : 0; }
 
     int cuddh_hip_ddh_apply_f32(const cuddh_ddh_plan *plan, int dom_begin, int dom_end, const double *x, double *y, int zero_y,
                                 const float *lambda, float *update, void *stream)

@@ -786,6 +786,27 @@ extern "C"
                 h->f32->internals().set_wave_priority(high != 0);
         });
     }
+    int cuddh_ddh_set_sweep_form(void *d, int form)
+    {
+        return guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            if (h->is64())
+                h->f64->internals().set_sweep_form(form);
+            else
+                h->f32->internals().set_sweep_form(form);
+        });
+    }
+    int cuddh_ddh_sweep_form(void *d)
+    {
+        int form = 0;
+        const int err = guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            form = h->is64() ? h->f64->internals().sweep_form() : h->f32->internals().sweep_form();
+        });
+        return err ? -1 : form;
+    }
     int cuddh_ddh_rhs(void *d, const double *f, void *b)
     {
         return guarded([&]

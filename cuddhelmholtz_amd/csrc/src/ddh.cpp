@@ -427,6 +427,20 @@ namespace cuddh
         }
 
         template <typename Real>
+        void DDHCore<Real>::set_sweep_form(int form) const
+        {
+            ensure_plan();
+            check_hip(cuddh_hip_ddh_plan_set_sweep_form(plan, form), "DDH sweep form");
+        }
+
+        template <typename Real>
+        int DDHCore<Real>::sweep_form() const
+        {
+            ensure_plan();
+            return cuddh_hip_ddh_plan_sweep_form(plan);
+        }
+
+        template <typename Real>
         void DDHCore<Real>::set_wave_priority(bool high) const
         {
             ensure_plan();

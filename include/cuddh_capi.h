@@ -167,6 +167,10 @@ int cuddh_trace_exchange_query(const int *h_B, int n_domains, int mx_fdof, int n
 int cuddh_ddh_set_wh_iters(void *ddh, int n);
 /* the local solves launched next take issue priority on the device (cuddh_hip_ddh_plan_set_wave_priority); 0 restores */
 int cuddh_ddh_set_wave_priority(void *ddh, int high);
+/* kernel 5's sweep form: 0 auto, 1 matrix, 2 element-lane, 3 the same with the other owner rule (cuddh_hip_ddh_plan_set_sweep_form);
+ * the getter returns the form in effect (1, 2 or 3; 0 for a plan that is not kernel 5; -1 on error) */
+int cuddh_ddh_set_sweep_form(void *ddh, int form);
+int cuddh_ddh_sweep_form(void *ddh);
 /* traces are float for f64 == 0 and double otherwise */
 int cuddh_ddh_rhs(void *ddh, const double *f, void *b);
 int cuddh_ddh_postprocess(void *ddh, const void *lambda, const double *f, double *u);

@@ -323,6 +323,20 @@ int cuddh_hip_ddh_plan_set_wave_priority(cuddh_ddh_plan *plan, int high);
  * solves become exact and DDH converges to the Helmholtz system its transmission conditions imply
  * (tests/test_ddh_physics.py); production callers never touch it. */
 int cuddh_hip_ddh_plan_set_wh_iters(cuddh_ddh_plan *plan, int wh_iters);
+/* How a kernel-5 plan forms its stiffness sweep, for every launch of the plan (rhs, action, postprocess, listed and priority
+ * launches alike; never a property of one launch, so differently partitioned launches stay bitwise equal):
+ *   1 = matrix form: the dense 16x16 element matrix on v_mfma_f32_16x16x4_f32, one subdomain per wavefront;
+ *   2 = element-lane form: the separable sweep with one element per lane and four subdomains per wavefront, in-lane FMAs with
+ *       scalar coefficients, DPP row shifts for the assembly.  Needs rectangles (diagonal metric, a product of 1-D factors,
+ *       the same node weight on both sides of every shared edge), checked when the plan is created;
+ *   3 = form 2 with the owner rule turned round: of the 2 or 4 copies of a node that elements share, the one with the largest
+ *       element-node index writes the result, not the one with the smallest.  The copies are bitwise equal by construction, so
+ *       the results are those of form 2; the value exists so that a test can assert it, and auto never takes it;
+ *   0 = auto (the default): 2 when the geometry qualifies and the plan has enough subdomains to fill the device, else 1.
+ * 2 or 3 on a plan that is not kernel 5 or does not qualify is refused with hipErrorInvalidValue; 0 and 1 are accepted by
+ * every plan.  cuddh_hip_ddh_plan_sweep_form returns the form in effect (1, 2 or 3), 0 for a plan that is not kernel 5. */
+int cuddh_hip_ddh_plan_set_sweep_form(cuddh_ddh_plan *plan, int form);
+int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan);
 
 /* source/DDH.cpp:111-321 (ddh_action + stiffness).  x: forcing [F;G] (2*g_ndof
  * doubles) or NULL; y: solution output [u;v] (2*g_ndof doubles, zero-filled by

@@ -72,8 +72,10 @@ def main():
         same += m0 == m1 and hist and diff == 0
         label = name if succ == name else f"{name} => {succ}"
         print(f"{label} | {regs(m0)} -> {regs(m1)} | {len(o0)} -> {len(o1)} | {'same' if hist else 'DIFFERS'} | {diff} | {loops}")
-    for name in new:
-        print(f"{name} | NEW after")
+    for name, (m1, o1, l1) in new.items():  # a kernel the old file does not have: its registers and what its loops hold
+        c1 = collections.Counter(l1)
+        print(f"{name} | NEW after | {' '.join(str(m1[f]) for f in FIELDS)} | {len(o1)} instructions, {len(l1)} inside loops: "
+              + " ".join(f"{k}:{c1[k]}" for k in sorted(c1)))
     print(f"{same} of {len(old)} kernels: same registers, same mnemonic sequence")
 
 
