@@ -40,6 +40,40 @@
 
 using namespace cuddh_k;
 
+struct cuddh_helmholtz_plan;
+
+namespace
+{
+    struct HelmArgs
+    {
+        int ndof, max_loc, ncol, nfcol, nqF, n_slots, n_patches, xcd_chunk;
+        int dof_stride; // != 0: patch p's dof_list / slot_of segment starts at p * dof_stride (no offset load), padded to dof_stride entries
+        double omega;
+        const int *dof_off, *dof_list, *slot_of, *patch_nel, *face_off, *face_id;
+        const int *own_count;
+        const uint32_t *lidx;
+        const uint16_t *face_lidx;
+        const uint8_t *colour, *face_col;
+        const double *Gp, *aMp, *aF;
+        const double *x;
+        double *y, *part;
+        unsigned long long *stamps; // diagnostic: phase time stamps per patch, or null
+        int pair_mass;              // helm_patch_kernel: two mass slices per round trip
+        // plan-native vector ordering (helm_lane_kernel<..., NATIVE>): x, y and part are then arrays of (u, v) pairs
+        const int *own_off, *bpos, *bslot;
+        int bstride;
+    };
+
+    // One resolved launch: which kernel instantiation (behind `run`, the only caller of its hipLaunchKernelGGL) and its geometry.
+    // Filled once, at the end of plan creation (resolve_plan); an apply only copies the arguments and calls `run`.
+    struct PlanLaunch
+    {
+        void (*run)(const cuddh_helmholtz_plan *, const PlanLaunch &, const HelmArgs &, int accumulate, hipStream_t) = nullptr;
+        dim3 grid, block;
+        size_t lds = 0;
+    };
+} // namespace
+
 struct cuddh_helmholtz_plan
 {
     int ndof = 0, n_elem = 0, nb = 0, nqS = 0, nqM = 0, nqF = 0, n_faces = 0;
@@ -91,6 +125,11 @@ struct cuddh_helmholtz_plan
     int *global_of_native = nullptr; // [ndof] reference dof id at every native position (the permutation, for to / from native)
     int n_owned = 0;
     size_t bytes_native = 0; // bytes the native apply moves (layout figure, like bytes_actual)
+    int mfma_stage = 0;      // how helm_mfma_kernel gets its metric data (see mfma_stage())
+    // what an apply needs, resolved once by resolve_plan() from the fields above
+    HelmArgs args{};         // everything but x, y, omega
+    PlanLaunch launch[2];    // [0] reference ordering (and the single operators), [1] plan-native ordering: same flags, same code
+    char description[128] = ""; // cuddh_hip_helmholtz_plan_describe
 };
 
 namespace
@@ -132,26 +171,6 @@ namespace
         if constexpr (NV % 2 == 1)
             v[NV - 1] = metric_load<NT>(slice + 2 * VP * 64 + lane);
     }
-
-    struct HelmArgs
-    {
-        int ndof, max_loc, ncol, nfcol, nqF, n_slots, n_patches, xcd_chunk;
-        int dof_stride; // != 0: patch p's dof_list / slot_of segment starts at p * dof_stride (no offset load), padded to dof_stride entries
-        double omega;
-        const int *dof_off, *dof_list, *slot_of, *patch_nel, *face_off, *face_id;
-        const int *own_count;
-        const uint32_t *lidx;
-        const uint16_t *face_lidx;
-        const uint8_t *colour, *face_col;
-        const double *Gp, *aMp, *aF;
-        const double *x;
-        double *y, *part;
-        unsigned long long *stamps; // diagnostic: phase time stamps per patch, or null
-        int pair_mass;              // helm_patch_kernel: two mass slices per round trip
-        // plan-native vector ordering (helm_lane_kernel<..., NATIVE>): x, y and part are then arrays of (u, v) pairs
-        const int *own_off, *bpos, *bslot;
-        int bstride;
-    };
 
     // Variants measured and dropped: software-pipelined slice loads, slices split between the half-waves
     // and exchanged with ds_bpermute, three role-specialised wavefronts per patch, touch-prefetch of the metric block.
@@ -1588,104 +1607,6 @@ namespace
         return v;
     }
 
-    template <int NB, int NQS, int NQM, int PEK>
-    void launch_patch_pe(const cuddh_helmholtz_plan *p, const HelmArgs &A, hipStream_t st, bool native = false)
-    {
-        const size_t lds = (size_t)4 * p->max_loc * sizeof(double);
-        const dim3 grid(8 * A.xcd_chunk), block(2 * PEK);
-        if (native) // the same MODE as the reference-ordering launch below, so that the two orderings give bitwise the same numbers
-        {
-            constexpr bool CAN_PAIR_N = 2 * NQM <= 3 * NQS && NB <= 4;
-            if constexpr (CAN_PAIR_N)
-                if (!p->Gu && A.pair_mass)
-                {
-                    if (p->streaming)
-                        hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, true, false, PEK, 1, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    else
-                        hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, false, false, PEK, 1, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    return;
-                }
-            if (p->Gu && p->streaming)
-                hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, true, true, PEK, 0, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-            else if (p->Gu)
-                hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, false, true, PEK, 0, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-            else if (p->streaming)
-                hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, true, false, PEK, 0, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-            else
-                hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, false, false, PEK, 0, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-            return;
-        }
-        // general layout, 2 NQM <= 3 NQS (n_basis 3 and 5): the mass phase takes two slices per round trip (PM)
-        constexpr bool CAN_PAIR = 2 * NQM <= 3 * NQS && NB <= 4;
-        if (p->Gu && p->streaming)
-            hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, true, true, PEK>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-        else if (p->Gu)
-            hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, false, true, PEK>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-        else if (CAN_PAIR && A.pair_mass)
-        {
-            if constexpr (CAN_PAIR)
-            {
-                if (p->streaming)
-                    hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, true, false, PEK, 1>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                else
-                    hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, false, false, PEK, 1>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-            }
-        }
-        else if (p->streaming)
-            hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, true, false, PEK>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-        else
-            hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, false, false, PEK>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-    }
-
-    template <int NB, int NQS, int NQM>
-    void launch_patch(const cuddh_helmholtz_plan *p, const HelmArgs &A, hipStream_t st, bool native = false)
-    {
-        if constexpr (NB <= 4)
-            if (p->pe == 64 && p->lane_form)
-            {
-                const size_t lds = (size_t)2 * p->max_loc * sizeof(double);
-                const dim3 grid(8 * A.xcd_chunk), block(64);
-                if (native)
-                {
-                    if (p->Gu && p->streaming)
-                        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, true, true, false, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    else if (p->Gu)
-                        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, false, true, false, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    else if (p->streaming)
-                        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, true, false, false, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    else
-                        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, false, false, false, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    return;
-                }
-                if (p->prefetch)
-                {
-                    // whole-patch prefetch: one wavefront per SIMD, the patch's metric block requested up front
-                    if (p->Gu && p->streaming)
-                        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, true, true, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    else if (p->Gu)
-                        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, false, true, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    else if (p->streaming)
-                        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, true, false, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    else
-                        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, false, false, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                    return;
-                }
-                if (p->Gu && p->streaming)
-                    hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, true, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                else if (p->Gu)
-                    hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, false, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                else if (p->streaming)
-                    hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, true, false>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                else
-                    hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, false, false>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
-                return;
-            }
-        if (p->pe == 64)
-            launch_patch_pe<NB, NQS, NQM, 64>(p, A, st, native);
-        else
-            launch_patch_pe<NB, NQS, NQM, 32>(p, A, st, native);
-    }
-
     // fused complex apply on the fp64 matrix cores (16-element batches)
     bool helm_mfma(int nb, int nqS, int nqM) { return nb >= 6 && nb <= 8 && nqS == nb + 1 && nqM == 2 + 3 * nb / 2; }
 
@@ -1693,45 +1614,6 @@ namespace
     {
         return (nb == 3 && nqS == 4 && nqM == 6) || (nb == 4 && nqS == 5 && nqM == 8) || (nb == 5 && nqS == 6 && nqM == 9) ||
                (nb == 2 && nqS == 3 && nqM == 5) || helm_mfma(nb, nqS, nqM);
-    }
-
-    HelmArgs plan_args(const cuddh_helmholtz_plan *p, const double *x, double *y)
-    {
-        HelmArgs A;
-        A.ndof = p->ndof;
-        A.max_loc = p->max_loc;
-        A.ncol = p->ncol;
-        A.nfcol = p->nfcol;
-        A.nqF = p->nqF;
-        A.n_slots = p->n_slots;
-        A.n_patches = p->n_patches;
-        A.xcd_chunk = (p->n_patches + 7) / 8;
-        A.omega = 0.0;
-        A.dof_off = p->dof_off;
-        A.dof_list = p->dof_list;
-        A.slot_of = p->slot_of;
-        A.own_count = p->own_count;
-        A.dof_stride = p->dof_stride;
-        A.patch_nel = p->patch_nel;
-        A.face_off = p->face_off;
-        A.face_id = p->face_id;
-        A.lidx = p->lidx;
-        A.face_lidx = p->face_lidx;
-        A.colour = p->colour;
-        A.face_col = p->face_col;
-        A.Gp = p->Gp;
-        A.aMp = p->aMp;
-        A.aF = p->aF;
-        A.x = x;
-        A.y = y;
-        A.part = p->part;
-        A.stamps = p->stamps;
-        A.pair_mass = p->pair_mass;
-        A.own_off = p->own_off;
-        A.bpos = p->bpos;
-        A.bslot = p->bslot;
-        A.bstride = p->bstride;
-        return A;
     }
 
     // ---------------------------------------------------------------- one real operator through the same plan
@@ -3011,75 +2893,6 @@ namespace
         }
     }
 
-    // How helm_mfma_kernel gets its metric data: 0 = one dependent trip to memory per slice; 100 w + 10 cs + cm = in cs + cm chunks
-    // requested one ahead and parked in LDS, w wavefronts per SIMD.  Same-box A/B (profiles/r03/mfma_stage_ab.txt): n_basis 6 and 7
-    // gain 6-9 % with 2 + 2 chunks; n_basis 8 (register spills at 3 wavefronts per SIMD, 2.5 by LDS) and n_basis 5 on the matrix cores
-    // do not.  CUDDH_HELM_MFMA_STAGE overrides (measurement knob; 0 = off).
-    int mfma_stage(int nb)
-    {
-        static const int knob = [] { const char *e = std::getenv("CUDDH_HELM_MFMA_STAGE"); return e ? std::atoi(e) : -1; }();
-        if (knob >= 0)
-            return knob;
-        return (nb == 6 || nb == 7) ? 322 : 0;
-    }
-
-    template <int NB, int NQS, int NQM>
-    void launch_helm_mfma(const cuddh_helmholtz_plan *p, const HelmArgs &A, hipStream_t st, bool native)
-    {
-        const dim3 grid(8 * A.xcd_chunk), block(128); // one wavefront per component
-        const int stage = mfma_stage(NB);
-        if (stage)
-        {
-            auto go = [&](auto nat, auto ncs, auto ncm, auto occ)
-            {
-                constexpr bool NAT = decltype(nat)::value;
-                constexpr int NCS = decltype(ncs)::value, NCM = decltype(ncm)::value, OCC = decltype(occ)::value;
-                constexpr int HS = (NQS + NCS - 1) / NCS, HM = (NQM + NCM - 1) / NCM;
-                constexpr int CH = (HS * 3 * NQS > HM * NQM ? HS * 3 * NQS : HM * NQM) * 16;
-                const size_t lds_s = ((size_t)2 * ((p->max_loc + 1) & ~1) + CH) * sizeof(double) + ((NB * NB + 1) / 2 * 16 + 16) * sizeof(int);
-                hipLaunchKernelGGL((helm_mfma_kernel<NB, NQS, NQM, NAT, NCS, NCM, OCC>), grid, block, lds_s, st, A, p->PS, p->DS, p->PM, p->PF, p->Gm, p->gm_stride, p->Am,
-                                   p->am_stride);
-            };
-            using std::integral_constant;
-            using std::true_type;
-            if (!native) // reference ordering: the default form only
-            {
-                go(std::false_type{}, integral_constant<int, 2>{}, integral_constant<int, 2>{}, integral_constant<int, 3>{});
-                return;
-            }
-#define CUDDH_STAGE_CASE(o, cs, cm)                                                                                  \
-    if (stage == 100 * o + 10 * cs + cm)                                                                             \
-    {                                                                                                                \
-        go(true_type{}, integral_constant<int, cs>{}, integral_constant<int, cm>{}, integral_constant<int, o>{});   \
-        return;                                                                                                      \
-    }
-            CUDDH_STAGE_CASE(3, 2, 2)
-            CUDDH_STAGE_CASE(3, 2, 1)
-            CUDDH_STAGE_CASE(3, 3, 2)
-            CUDDH_STAGE_CASE(2, 2, 2)
-#undef CUDDH_STAGE_CASE
-            std::fprintf(stderr, "CUDDH_HELM_MFMA_STAGE=%d is not a built variant (322, 321, 332, 222)\n", stage);
-            std::abort();
-        }
-        const size_t lds = (size_t)2 * p->max_loc * sizeof(double);
-        if (native)
-            hipLaunchKernelGGL((helm_mfma_kernel<NB, NQS, NQM, true>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gm, p->gm_stride, p->Am, p->am_stride);
-        else
-            hipLaunchKernelGGL((helm_mfma_kernel<NB, NQS, NQM, false>), grid, block, lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gm, p->gm_stride, p->Am, p->am_stride);
-    }
-
-    void launch_helm_mfma_any(const cuddh_helmholtz_plan *p, const HelmArgs &A, hipStream_t st, bool native)
-    {
-        if (p->nb == 5)
-            launch_helm_mfma<5, 6, 9>(p, A, st, native);
-        else if (p->nb == 6)
-            launch_helm_mfma<6, 7, 11>(p, A, st, native);
-        else if (p->nb == 7)
-            launch_helm_mfma<7, 8, 12>(p, A, st, native);
-        else
-            launch_helm_mfma<8, 9, 14>(p, A, st, native);
-    }
-
     __global__ void __launch_bounds__(256) op_border_kernel(int n_shared, int accumulate, const int *__restrict__ shared_dof,
                                                            const int *__restrict__ shared_off,
                                                            const double *__restrict__ part, double *__restrict__ y)
@@ -3123,52 +2936,313 @@ namespace
         return kind == 1 && (nq == nb + 1 || nq == 2 + 3 * nb / 2);
     }
 
-    template <int NB, int NQ, int KIND, int PEK>
-    void launch_op_pe(const cuddh_helmholtz_plan *p, const HelmArgs &A, int accumulate, hipStream_t st)
+    // ---------------------------------------------------------------- which kernel a plan runs: resolved once per plan
+    // Measurement knobs (DESIGN.md 4.1 has the table).  read_knobs() is the only place in this file that looks at the
+    // environment, and plan creation calls it once: a plan keeps the form it was created with.
+    struct Knobs
     {
-        const size_t lds = (size_t)(PEK == 64 ? 2 : 4) * p->max_loc * sizeof(double);
-        const dim3 grid(8 * A.xcd_chunk), block(64);
-        const double *P = KIND == 0 ? p->PS : p->PM, *MU = KIND == 0 ? p->Gu : p->au;
-        if (MU)
-            hipLaunchKernelGGL((op_patch_kernel<NB, NQ, KIND, false, true, PEK>), grid, block, lds, st, A, accumulate, P, p->DS, MU);
-        else if (p->streaming)
-            hipLaunchKernelGGL((op_patch_kernel<NB, NQ, KIND, true, false, PEK>), grid, block, lds, st, A, accumulate, P, p->DS, MU);
+        bool affine = true;    // CUDDH_PLAN_AFFINE=0: per-element metric arrays even where one copy would serve all
+        int streaming = -1;    // CUDDH_PLAN_STREAMING=0/1: overrides the size rule for non-temporal metric loads
+        int helm_pe = 0;       // CUDDH_HELM_PE=32/64: patch size of helm_patch_kernel (n_basis <= 4)
+        int lane = -1;         // CUDDH_HELM_LANE=0/1: overrides the size rule for helm_lane_kernel
+        bool pre = false;      // CUDDH_HELM_PRE=1: lane form with the patch's whole metric block requested up front
+        bool pair_mass = true; // CUDDH_HELM_PAIR_MASS=0: helm_patch_kernel, n_basis 3, one mass slice per round trip
+        bool nb5_mfma = false; // CUDDH_HELM_NB5_MFMA=1: n_basis 5 in the matrix-core scheme
+        bool stamps = false;   // CUDDH_HELM_STAMPS set: phase time stamps (cuddh_hip_helmholtz_plan_read_stamps)
+        bool op_pe32 = false;  // CUDDH_OP_PE=32: single operators on two 32-element patches per wavefront
+        int mfma_stage = -1;   // CUDDH_HELM_MFMA_STAGE=0|322|321|332|222 (see mfma_stage); negative: the default
+    };
+
+    Knobs read_knobs()
+    {
+        auto env = [](const char *name, int &v)
+        {
+            const char *e = std::getenv(name);
+            if (e)
+                v = std::atoi(e);
+            return e != nullptr;
+        };
+        Knobs k;
+        int v = 0;
+        if (env("CUDDH_PLAN_AFFINE", v))
+            k.affine = v != 0;
+        if (env("CUDDH_PLAN_STREAMING", v))
+            k.streaming = v != 0;
+        if (env("CUDDH_HELM_PE", v))
+            k.helm_pe = v == 64 ? 64 : PE;
+        if (env("CUDDH_HELM_LANE", v))
+            k.lane = v == 1;
+        if (env("CUDDH_HELM_PRE", v))
+            k.pre = v != 0;
+        if (env("CUDDH_HELM_PAIR_MASS", v))
+            k.pair_mass = v != 0;
+        if (env("CUDDH_HELM_NB5_MFMA", v))
+            k.nb5_mfma = v != 0;
+        k.stamps = env("CUDDH_HELM_STAMPS", v);
+        if (env("CUDDH_OP_PE", v))
+            k.op_pe32 = v == 32;
+        if (env("CUDDH_HELM_MFMA_STAGE", v))
+            k.mfma_stage = v;
+        return k;
+    }
+
+    // How helm_mfma_kernel gets its metric data: 0 = one dependent trip to memory per slice; 100 w + 10 cs + cm = in cs + cm chunks
+    // requested one ahead and parked in LDS, w wavefronts per SIMD.  Same-box A/B (profiles/r03/mfma_stage_ab.txt): n_basis 6 and 7
+    // gain 6-9 % with 2 + 2 chunks; n_basis 8 (register spills at 3 wavefronts per SIMD, 2.5 by LDS) and n_basis 5 on the matrix cores
+    // do not.  CUDDH_HELM_MFMA_STAGE overrides (measurement knob; 0 = off).  The plan-native ordering has the four staged variants
+    // below; the reference ordering runs every staged plan as 322.
+    int mfma_stage(int nb, const Knobs &k) { return k.mfma_stage >= 0 ? k.mfma_stage : ((nb == 6 || nb == 7) ? 322 : 0); }
+    bool mfma_stage_built(int stage) { return stage == 0 || stage == 322 || stage == 321 || stage == 332 || stage == 222; }
+
+    // Runtime flags become template arguments here and nowhere else: with_flags(f, a, b, ...) calls f(A{}, B{}, ...) with
+    // std::true_type / std::false_type for each flag.
+    template <class F>
+    void with_flags(F &&f)
+    {
+        f();
+    }
+    template <class F, class... Rest>
+    void with_flags(F &&f, bool flag, Rest... rest)
+    {
+        if (flag)
+            with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
         else
-            hipLaunchKernelGGL((op_patch_kernel<NB, NQ, KIND, false, false, PEK>), grid, block, lds, st, A, accumulate, P, p->DS, MU);
+            with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+    }
+
+    // n_basis becomes a template argument here, for every kind of plan: the orders with a kernel are listed here and nowhere else
+    template <class F>
+    void with_n_basis(int nb, F &&f)
+    {
+        using std::integral_constant;
+        switch (nb)
+        {
+        case 2: return f(integral_constant<int, 2>{});
+        case 3: return f(integral_constant<int, 3>{});
+        case 4: return f(integral_constant<int, 4>{});
+        case 5: return f(integral_constant<int, 5>{});
+        case 6: return f(integral_constant<int, 6>{});
+        case 7: return f(integral_constant<int, 7>{});
+        case 8: return f(integral_constant<int, 8>{});
+        }
+    }
+
+    // The five plan kernels: each is launched from exactly one place, with the geometry resolve_plan() stored.
+    template <int NB, int NQS, int NQM, bool NT, bool UG, int PEK, int MODE, bool NATIVE>
+    void run_helm_patch(const cuddh_helmholtz_plan *p, const PlanLaunch &L, const HelmArgs &A, int, hipStream_t st)
+    {
+        hipLaunchKernelGGL((helm_patch_kernel<NB, NQS, NQM, NT, UG, PEK, MODE, NATIVE>), L.grid, L.block, L.lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
+    }
+
+    template <int NB, int NQS, int NQM, bool NT, bool UG, bool PRE, bool NATIVE>
+    void run_helm_lane(const cuddh_helmholtz_plan *p, const PlanLaunch &L, const HelmArgs &A, int, hipStream_t st)
+    {
+        hipLaunchKernelGGL((helm_lane_kernel<NB, NQS, NQM, NT, UG, PRE, NATIVE>), L.grid, L.block, L.lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gu);
+    }
+
+    template <int NB, int NQS, int NQM, bool NATIVE, int NCS, int NCM, int OCC>
+    void run_helm_mfma(const cuddh_helmholtz_plan *p, const PlanLaunch &L, const HelmArgs &A, int, hipStream_t st)
+    {
+        hipLaunchKernelGGL((helm_mfma_kernel<NB, NQS, NQM, NATIVE, NCS, NCM, OCC>), L.grid, L.block, L.lds, st, A, p->PS, p->DS, p->PM, p->PF, p->Gm, p->gm_stride,
+                           p->Am, p->am_stride);
+    }
+
+    template <int NB, int NQ, int KIND, bool NT, bool UM, int PEK>
+    void run_op_patch(const cuddh_helmholtz_plan *p, const PlanLaunch &L, const HelmArgs &A, int accumulate, hipStream_t st)
+    {
+        hipLaunchKernelGGL((op_patch_kernel<NB, NQ, KIND, NT, UM, PEK>), L.grid, L.block, L.lds, st, A, accumulate, KIND == 0 ? p->PS : p->PM, p->DS,
+                           KIND == 0 ? p->Gu : p->au);
     }
 
     template <int NB, int NQ, int KIND>
-    void launch_op_one(const cuddh_helmholtz_plan *p, const HelmArgs &A, int accumulate, hipStream_t st)
+    void run_op_mfma(const cuddh_helmholtz_plan *p, const PlanLaunch &L, const HelmArgs &A, int accumulate, hipStream_t st)
     {
-        if (p->pe == 64)
-            launch_op_pe<NB, NQ, KIND, 64>(p, A, accumulate, st);
-        else
-            launch_op_pe<NB, NQ, KIND, 32>(p, A, accumulate, st);
+        hipLaunchKernelGGL((op_mfma_kernel<NB, NQ, KIND>), L.grid, L.block, L.lds, st, A, accumulate, KIND == 0 ? p->PS : p->PM, p->DS, KIND == 0 ? p->Gm : p->Am,
+                           KIND == 0 ? p->gm_stride : p->am_stride);
     }
 
-    bool launch_op(const cuddh_helmholtz_plan *p, const HelmArgs &A, int accumulate, hipStream_t st)
+    // helm_mfma_kernel with its metric data in NCS + NCM chunks at OCC wavefronts per SIMD (0, 0, 0: slice by slice)
+    template <int NB, int NQS, int NQM, bool NATIVE, int NCS, int NCM, int OCC>
+    void set_helm_mfma(const cuddh_helmholtz_plan *p, PlanLaunch &L)
     {
-        const int kind = p->nqS > 0 ? 0 : 1, nq = kind == 0 ? p->nqS : p->nqM;
-#define CUDDH_OP_CASE(NB_, NQ_, K_)                      \
-    if (p->nb == NB_ && nq == NQ_ && kind == K_)         \
-    {                                                    \
-        launch_op_one<NB_, NQ_, K_>(p, A, accumulate, st); \
-        return true;                                     \
+        L.run = run_helm_mfma<NB, NQS, NQM, NATIVE, NCS, NCM, OCC>;
+        L.block = dim3(128); // one wavefront per component
+        L.lds = (size_t)2 * p->max_loc * sizeof(double);
+        if constexpr (NCS > 0)
+        {
+            constexpr int HS = (NQS + NCS - 1) / NCS, HM = (NQM + NCM - 1) / NCM;
+            constexpr int CH = (HS * 3 * NQS > HM * NQM ? HS * 3 * NQS : HM * NQM) * 16;
+            L.lds = ((size_t)2 * ((p->max_loc + 1) & ~1) + CH) * sizeof(double) + ((NB * NB + 1) / 2 * 16 + 16) * sizeof(int);
+        }
     }
-        CUDDH_OP_CASE(2, 3, 0)
-        CUDDH_OP_CASE(3, 4, 0)
-        CUDDH_OP_CASE(4, 5, 0)
-        CUDDH_OP_CASE(5, 6, 0)
-        CUDDH_OP_CASE(2, 3, 1)
-        CUDDH_OP_CASE(3, 4, 1)
-        CUDDH_OP_CASE(4, 5, 1)
-        CUDDH_OP_CASE(5, 6, 1)
-        CUDDH_OP_CASE(2, 5, 1)
-        CUDDH_OP_CASE(3, 6, 1)
-        CUDDH_OP_CASE(4, 8, 1)
-        CUDDH_OP_CASE(5, 9, 1)
-#undef CUDDH_OP_CASE
-        return false;
+
+    // The fused apply of a plan with these sizes, in both vector orderings.  Both records come from the same flag values through
+    // the same code, so the two orderings run the same form of the same kernel and give bitwise the same numbers.  Only
+    // combinations that are launched are instantiated: no lane form at n_basis 5, none with PRE in the native ordering, MODE 1
+    // at n_basis 3 on per-element metrics only, the staged matrix-core variants other than 322 in the native ordering only.
+    template <int NB, int NQS, int NQM>
+    void resolve_helm(cuddh_helmholtz_plan *p)
+    {
+        const bool nt = p->streaming != 0, ug = p->Gu != nullptr;
+        char *const text = p->description;
+        constexpr size_t cap = sizeof p->description;
+        auto ordering = [&](auto native)
+        {
+            constexpr bool NATIVE = decltype(native)::value;
+            PlanLaunch &L = p->launch[NATIVE];
+            L.grid = dim3(8 * p->args.xcd_chunk);
+            if constexpr (NB >= 5)
+                if (p->Gm && p->Am) // n_basis 6-8 (5 on request): fp64 matrix cores, one 16-element batch per workgroup
+                {
+                    const int stage = (NATIVE || !p->mfma_stage) ? p->mfma_stage : 322;
+                    if (stage == 0)
+                        set_helm_mfma<NB, NQS, NQM, NATIVE, 0, 0, 0>(p, L);
+                    else if (stage == 322)
+                        set_helm_mfma<NB, NQS, NQM, NATIVE, 2, 2, 3>(p, L);
+                    if constexpr (NATIVE)
+                    {
+                        if (stage == 321)
+                            set_helm_mfma<NB, NQS, NQM, true, 2, 1, 3>(p, L);
+                        else if (stage == 332)
+                            set_helm_mfma<NB, NQS, NQM, true, 3, 2, 3>(p, L);
+                        else if (stage == 222)
+                            set_helm_mfma<NB, NQS, NQM, true, 2, 2, 2>(p, L);
+                    }
+                    if (p->mfma_stage)
+                        std::snprintf(text, cap, "helm_mfma_kernel<%d,%d,%d,chunks=%d+%d> pe=16 affine=%d", NB, NQS, NQM, (p->mfma_stage / 10) % 10,
+                                      p->mfma_stage % 10, p->gm_stride == 0 ? 1 : 0);
+                    else
+                        std::snprintf(text, cap, "helm_mfma_kernel<%d,%d,%d> pe=16 affine=%d", NB, NQS, NQM, p->gm_stride == 0 ? 1 : 0);
+                    return;
+                }
+            if constexpr (NB <= 4)
+                if (p->pe == 64 && p->lane_form)
+                {
+                    L.block = dim3(64);
+                    L.lds = (size_t)2 * p->max_loc * sizeof(double);
+                    // (PRE: whole-patch prefetch, one wavefront per SIMD; the native ordering has the slice-by-slice chain only)
+                    with_flags([&](auto NT, auto UG, auto PRE) { L.run = run_helm_lane<NB, NQS, NQM, NT.value, UG.value, PRE.value && !NATIVE, NATIVE>; }, nt, ug,
+                               p->prefetch != 0);
+                    std::snprintf(text, cap, "helm_lane_kernel<%d,%d,%d,NT=%d,UG=%d%s> pe=64", NB, NQS, NQM, nt, ug, p->prefetch ? ",PRE=1" : "");
+                    return;
+                }
+            if constexpr (NB <= 5)
+            {
+                L.block = dim3(2 * p->pe);
+                L.lds = (size_t)4 * p->max_loc * sizeof(double);
+                // general layout, 2 NQM <= 3 NQS (n_basis 3): the mass phase takes two slices per round trip (MODE 1)
+                with_flags(
+                    [&](auto NT, auto UG, auto PE64, auto PAIR)
+                    {
+                        constexpr int MODE = (PAIR.value && !UG.value && 2 * NQM <= 3 * NQS && NB <= 4) ? 1 : 0;
+                        L.run = run_helm_patch<NB, NQS, NQM, NT.value, UG.value, PE64.value ? 64 : 32, MODE, NATIVE>;
+                        std::snprintf(text, cap, "helm_patch_kernel<%d,%d,%d,NT=%d,UG=%d,PEK=%d%s> pe=%d", NB, NQS, NQM, nt, ug, p->pe, MODE ? ",MODE=1" : "", p->pe);
+                    },
+                    nt, ug, p->pe == 64, p->pair_mass != 0);
+            }
+        };
+        ordering(std::false_type{});
+        ordering(std::true_type{});
+    }
+
+    // One real operator: op_mfma_kernel for n_basis 6-8 (16-element batches, one per wavefront), op_patch_kernel below that
+    template <int NB, int NQ, int KIND>
+    void resolve_op(cuddh_helmholtz_plan *p)
+    {
+        PlanLaunch &L = p->launch[0];
+        L.block = dim3(64);
+        if constexpr (NB >= 6)
+        {
+            L.run = run_op_mfma<NB, NQ, KIND>;
+            L.lds = (size_t)2 * p->max_loc * sizeof(double);
+            std::snprintf(p->description, sizeof p->description, "op_mfma_kernel<%d,%d,%d> pe=16 affine=%d", NB, NQ, KIND,
+                          (KIND == 0 ? p->gm_stride : p->am_stride) == 0 ? 1 : 0);
+        }
+        else
+        {
+            const bool um = (KIND == 0 ? p->Gu : p->au) != nullptr, nt = !um && p->streaming;
+            const int n_waves = p->pe == 64 ? p->n_patches : (p->n_patches + 1) / 2; // two 32-element patches per wavefront
+            p->args.xcd_chunk = (n_waves + 7) / 8;
+            L.lds = (size_t)(p->pe == 64 ? 2 : 4) * p->max_loc * sizeof(double);
+            with_flags(
+                [&](auto NT, auto UM, auto PE64)
+                {
+                    if constexpr (!(NT.value && UM.value)) // a uniform metric array is not streamed
+                        L.run = run_op_patch<NB, NQ, KIND, NT.value, UM.value, PE64.value ? 64 : 32>;
+                },
+                nt, um, p->pe == 64);
+            std::snprintf(p->description, sizeof p->description, "op_patch_kernel<%d,%d,%d,NT=%d,UG=%d,PEK=%d> pe=%d", NB, NQ, KIND, nt, um, p->pe, p->pe);
+        }
+        L.grid = dim3(8 * p->args.xcd_chunk);
+    }
+
+    // Called at the end of plan creation, once every flag is final: fills the arguments every apply passes, picks the kernel
+    // instantiation for each vector ordering and writes down which one that is.
+    int resolve_plan(cuddh_helmholtz_plan *p)
+    {
+        HelmArgs &A = p->args;
+        A.ndof = p->ndof;
+        A.max_loc = p->max_loc;
+        A.ncol = p->ncol;
+        A.nfcol = p->nfcol;
+        A.nqF = p->nqF;
+        A.n_slots = p->n_slots;
+        A.n_patches = p->n_patches;
+        A.xcd_chunk = (p->n_patches + 7) / 8;
+        A.omega = 0.0;
+        A.dof_off = p->dof_off;
+        A.dof_list = p->dof_list;
+        A.slot_of = p->slot_of;
+        A.own_count = p->own_count;
+        A.dof_stride = p->dof_stride;
+        A.patch_nel = p->patch_nel;
+        A.face_off = p->face_off;
+        A.face_id = p->face_id;
+        A.lidx = p->lidx;
+        A.face_lidx = p->face_lidx;
+        A.colour = p->colour;
+        A.face_col = p->face_col;
+        A.Gp = p->Gp;
+        A.aMp = p->aMp;
+        A.aF = p->aF;
+        A.x = nullptr;
+        A.y = nullptr;
+        A.part = p->part;
+        A.stamps = p->stamps;
+        A.pair_mass = p->pair_mass;
+        A.own_off = p->own_off;
+        A.bpos = p->bpos;
+        A.bslot = p->bslot;
+        A.bstride = p->bstride;
+
+        const bool fused = p->nqS > 0 && p->nqM > 0;
+        const int kind = p->nqS > 0 ? 0 : 1, nq = kind == 0 ? p->nqS : p->nqM;
+        with_n_basis(p->nb,
+                     [&](auto n_basis)
+                     {
+                         // quadrature points per direction: stiffness and plain mass; mass weighted with a coefficient
+                         constexpr int NB = n_basis.value, NQ = NB + 1, NQW = 2 + 3 * NB / 2;
+                         if (fused && p->nqS == NQ && p->nqM == NQW)
+                             resolve_helm<NB, NQ, NQW>(p);
+                         else if (!fused && nq == NQ && kind == 0)
+                             resolve_op<NB, NQ, 0>(p);
+                         else if (!fused && nq == NQ)
+                             resolve_op<NB, NQ, 1>(p);
+                         else if (!fused && nq == NQW)
+                             resolve_op<NB, NQW, 1>(p);
+                     });
+        return p->launch[0].run ? 0 : static_cast<int>(hipErrorNotSupported);
+    }
+
+    // what every apply does: the stored arguments with this call's vectors and scalar, through the stored launch
+    int run_plan(const cuddh_helmholtz_plan *p, const PlanLaunch &L, double scalar, int accumulate, const double *x, double *y, hipStream_t st)
+    {
+        HelmArgs A = p->args;
+        A.x = x;
+        A.y = y;
+        A.omega = scalar;
+        L.run(p, L, A, accumulate, st);
+        return launch_status();
     }
 } // namespace
 
@@ -3189,7 +3263,7 @@ extern "C"
     }
 
     // nqS == 0 or nqM == 0: a plan for a single real operator (the other tables are left empty)
-    static int build_plan(cuddh_helmholtz_plan **out, int ndof, int n_elem, int nb, const int *h_I, const double *h_xy, int nqS,
+    static int build_plan(cuddh_helmholtz_plan **out, const Knobs &knobs, int ndof, int n_elem, int nb, const int *h_I, const double *h_xy, int nqS,
                           const double *h_PS, const double *h_DS, const double *G_S, int nqM, const double *h_PM, const double *a_M,
                           int n_faces, const int *h_fI, const int *h_face_elem, int nqF, const double *h_PF, const double *a_F,
                           int pe = PE, bool want_pairs = false)
@@ -3498,9 +3572,7 @@ extern "C"
         int *d_perm = nullptr;
         ok(upload(&d_perm, padded_perm));
         // affine meshes: one copy of a metric array instead of one per element (CUDDH_PLAN_AFFINE=0 keeps the general form)
-        bool try_affine = true;
-        if (const char *e = std::getenv("CUDDH_PLAN_AFFINE"))
-            try_affine = std::atoi(e) != 0;
+        const bool try_affine = knobs.affine;
         bool uniform_G = false, uniform_a = false; // matrix-core plans: a uniform array becomes ONE 16-element block (stride 0)
         if (mfma && try_affine)
         {
@@ -3602,8 +3674,8 @@ extern "C"
                 p->bytes_affine = p->bytes_alg - (size_t)n_elem * ((uniform_G ? (size_t)3 * nqS * nqS * 8 : 0) + (uniform_a ? (size_t)nqM * nqM * 8 : 0));
         }
         p->streaming = p->bytes_actual > (size_t)256 << 20; // the infinity cache
-        if (const char *e = std::getenv("CUDDH_PLAN_STREAMING")) // measurement knob: 0 / 1 overrides the size rule
-            p->streaming = std::atoi(e) != 0;
+        if (knobs.streaming >= 0) // measurement knob: 0 / 1 overrides the size rule
+            p->streaming = knobs.streaming;
         *out = p;
         return 0;
     }
@@ -3616,29 +3688,33 @@ extern "C"
         *out = nullptr;
         if (!supported(nb, nqS, nqM) || n_elem <= 0)
             return static_cast<int>(hipErrorNotSupported);
+        const Knobs knobs = read_knobs();
         int pe = helm_mfma(nb, nqS, nqM) ? 16 : PE;
         // n_basis 5 sits between the two schemes: one element per lane needs more registers than 3 wavefronts per SIMD have
         // (26 spilled), the matrix-core scheme pads 5 xi-indices to 8.  Measured (profiles/r03/config5_ab.txt, 768^2): one element
         // per lane 385 us, matrix cores 479 us (reference ordering) / 425 us (native ordering) -- the default stays;
         // CUDDH_HELM_NB5_MFMA=1 selects the matrix-core scheme (tests keep it correct)
-        if (nb == 5 && nqS == 6 && nqM == 9)
-            if (const char *e = std::getenv("CUDDH_HELM_NB5_MFMA"))
-                if (std::atoi(e) != 0)
-                    pe = 16;
+        if (nb == 5 && nqS == 6 && nqM == 9 && knobs.nb5_mfma)
+            pe = 16;
+        const int stage = mfma_stage(nb, knobs);
+        if (pe == 16 && !mfma_stage_built(stage))
+        {
+            std::fprintf(stderr, "CUDDH_HELM_MFMA_STAGE=%d is not a built variant (322, 321, 332, 222)\n", stage);
+            return static_cast<int>(hipErrorInvalidValue);
+        }
         if (pe == PE && nb <= 4)
         {
             // Affine plans (uniform stiffness metric, read through scalar loads) use 64-element patches, two wavefronts sharing
             // one LDS copy: a third fewer border dofs and slots.  Measured at 1024^2: n_basis 4 331 -> 316 us, n_basis 3
             // 137 -> 130 us; with per-element metrics the larger patch is a wash on structured meshes and 6 % slower on
             // the irregular one (the two waves wait for each other at every colour phase), n_basis 5 does not change.
-            const char *a = std::getenv("CUDDH_PLAN_AFFINE");
             double *probe = nullptr;
-            if (!(a && std::atoi(a) == 0) && uniform_table(&probe, 3, nqS, n_elem, G_S) == 0 && probe)
+            if (knobs.affine && uniform_table(&probe, 3, nqS, n_elem, G_S) == 0 && probe)
                 pe = 64;
             if (probe)
                 (void)hipFree(probe);
-            if (const char *e = std::getenv("CUDDH_HELM_PE")) // measurement knob
-                pe = std::atoi(e) == 64 ? 64 : PE;
+            if (knobs.helm_pe) // measurement knob
+                pe = knobs.helm_pe;
         }
         // General geometry, n_basis 4, at least two full rounds of wavefronts (4096 patches of 64 elements = 512^2 elements):
         // helm_lane_kernel.  Same-box A/B against helm_patch_kernel: 1024^2 403 -> 382 us, 512^2 102.5 -> 91.6 us, irregular
@@ -3651,28 +3727,32 @@ extern "C"
         const bool affine_plan = pe == 64; // decided above
         const bool affine_lane = affine_plan && nb == 2;
         bool lane_form = (pe == PE && ((nb == 4 && n_elem >= 4096 * 64) || (nb <= 3 && n_elem >= 8192 * 64))) || (affine_lane && n_elem >= 8192 * 64);
-        if (const char *e = std::getenv("CUDDH_HELM_LANE"))
-            lane_form = nb <= 4 && (pe == PE || affine_lane) && std::atoi(e) == 1;
+        if (knobs.lane >= 0)
+            lane_form = nb <= 4 && (pe == PE || affine_lane) && knobs.lane == 1;
         if (lane_form)
             pe = 64;
-        const int err = build_plan(out, ndof, n_elem, nb, h_I, h_xy, nqS, h_PS, h_DS, G_S, nqM, h_PM, a_M, n_faces, h_fI, h_face_elem, nqF,
-                                   h_PF, a_F, pe, lane_form);
+        int err = build_plan(out, knobs, ndof, n_elem, nb, h_I, h_xy, nqS, h_PS, h_DS, G_S, nqM, h_PM, a_M, n_faces, h_fI, h_face_elem, nqF, h_PF,
+                             a_F, pe, lane_form);
         if (!err && *out)
         {
-            (*out)->lane_form = (*out)->pair_layout; // = lane_form && (general geometry || affine n_basis 2): decided in build_plan
+            cuddh_helmholtz_plan *p = *out;
+            p->lane_form = p->pair_layout; // = lane_form && (general geometry || affine n_basis 2): decided in build_plan
             // the lane form with the whole metric block in the register file (PRE, one wavefront per SIMD): measured SLOWER
             // than the slice-by-slice chain at two wavefronts per SIMD (1024^2, n_basis 4: 434-442 vs 373-376 us), although
             // the metric stream alone runs at 6.46 TB/s that way -- see the comment at the kernel.  CUDDH_HELM_PRE=1 selects it
             // for A/B runs; tests keep it correct.
-            (*out)->pair_mass = nb == 3 && !(*out)->Gu && !(*out)->lane_form;
-            if (const char *e = std::getenv("CUDDH_HELM_PAIR_MASS"))
-                (*out)->pair_mass = (*out)->pair_mass && std::atoi(e) != 0;
-            (*out)->prefetch = 0;
-            if (const char *e = std::getenv("CUDDH_HELM_PRE"))
-                (*out)->prefetch = (*out)->lane_form && std::atoi(e) != 0;
-            if (std::getenv("CUDDH_HELM_STAMPS") && ((*out)->lane_form || (*out)->pe == 16)) // diagnostic, see cuddh_hip_helmholtz_plan_read_stamps
-                if (hipMalloc(reinterpret_cast<void **>(&(*out)->stamps), (size_t)(*out)->n_patches * 8 * sizeof(unsigned long long)) == hipSuccess)
-                    (void)hipMemset((*out)->stamps, 0, (size_t)(*out)->n_patches * 8 * sizeof(unsigned long long));
+            p->pair_mass = nb == 3 && !p->Gu && !p->lane_form && knobs.pair_mass;
+            p->prefetch = p->lane_form && knobs.pre;
+            p->mfma_stage = stage;
+            if (knobs.stamps && (p->lane_form || p->pe == 16)) // diagnostic, see cuddh_hip_helmholtz_plan_read_stamps
+                if (hipMalloc(reinterpret_cast<void **>(&p->stamps), (size_t)p->n_patches * 8 * sizeof(unsigned long long)) == hipSuccess)
+                    (void)hipMemset(p->stamps, 0, (size_t)p->n_patches * 8 * sizeof(unsigned long long));
+            err = resolve_plan(p);
+            if (err)
+            {
+                cuddh_hip_helmholtz_plan_destroy(p);
+                *out = nullptr;
+            }
         }
         return err;
     }
@@ -3686,14 +3766,20 @@ extern "C"
         // n_basis 2-5: one 64-element patch per wavefront (8x8 elements on a structured mesh).  Two 32-element patches per
         // wavefront (CUDDH_OP_PE=32) have a third more border dofs and slots: 1024^2, n_basis 4, general layout: stiffness
         // 174-187 -> 162-171 us, mass 109 -> 97 us, weighted mass 168 -> 153 us; affine 113 / 87 / 98 -> 98 / 75 / 82 us.
-        int pe = op_mfma(kind, nb, nq) ? 16 : 64;
-        if (const char *e = std::getenv("CUDDH_OP_PE")) // measurement knob
-            pe = (pe != 16 && std::atoi(e) == 32) ? PE : pe;
-        if (kind == 0)
-            return build_plan(out, ndof, n_elem, nb, h_I, h_xy, nq, h_P, h_D, metric, 0, nullptr, nullptr, 0, nullptr, nullptr, 0,
-                              nullptr, nullptr, pe);
-        return build_plan(out, ndof, n_elem, nb, h_I, h_xy, 0, nullptr, nullptr, nullptr, nq, h_P, metric, 0, nullptr, nullptr, 0,
-                          nullptr, nullptr, pe);
+        const Knobs knobs = read_knobs();
+        const int pe = op_mfma(kind, nb, nq) ? 16 : (knobs.op_pe32 ? PE : 64); // (measurement knob)
+        int err = kind == 0 ? build_plan(out, knobs, ndof, n_elem, nb, h_I, h_xy, nq, h_P, h_D, metric, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr,
+                                         nullptr, pe)
+                            : build_plan(out, knobs, ndof, n_elem, nb, h_I, h_xy, 0, nullptr, nullptr, nullptr, nq, h_P, metric, 0, nullptr, nullptr, 0, nullptr,
+                                         nullptr, pe);
+        if (!err)
+            err = resolve_plan(*out);
+        if (err && *out)
+        {
+            cuddh_hip_helmholtz_plan_destroy(*out);
+            *out = nullptr;
+        }
+        return err;
     }
 
     int cuddh_hip_operator_plan_apply(const cuddh_helmholtz_plan *p, double c, int accumulate, const double *x, double *y, void *stream)
@@ -3701,46 +3787,8 @@ extern "C"
         if (!p || (p->nqS > 0) == (p->nqM > 0))
             return static_cast<int>(hipErrorInvalidValue);
         hipStream_t st = as_stream(stream);
-        HelmArgs A = plan_args(p, x, y);
-        A.omega = c;
-        if (p->Gm || p->Am) // 16-element batches on the fp64 matrix cores, one batch per wavefront
-        {
-            const size_t lds = (size_t)2 * p->max_loc * sizeof(double);
-            const dim3 grid(8 * A.xcd_chunk), block(64);
-            const int kind = p->nqS > 0 ? 0 : 1, nq = kind == 0 ? p->nqS : p->nqM;
-            const double *P = kind == 0 ? p->PS : p->PM;
-            bool launched = false;
-#define CUDDH_MFMA_CASE(NB_, NQ_, K_)                                                                              \
-    if (!launched && p->nb == NB_ && nq == NQ_ && kind == K_)                                                      \
-    {                                                                                                              \
-        hipLaunchKernelGGL((op_mfma_kernel<NB_, NQ_, K_>), grid, block, lds, st, A, accumulate, P, p->DS, K_ == 0 ? p->Gm : p->Am,  \
-                           K_ == 0 ? p->gm_stride : p->am_stride);  \
-        launched = true;                                                                                           \
-    }
-            CUDDH_MFMA_CASE(6, 7, 0)
-            CUDDH_MFMA_CASE(7, 8, 0)
-            CUDDH_MFMA_CASE(8, 9, 0)
-            CUDDH_MFMA_CASE(6, 7, 1)
-            CUDDH_MFMA_CASE(7, 8, 1)
-            CUDDH_MFMA_CASE(8, 9, 1)
-            CUDDH_MFMA_CASE(6, 11, 1)
-            CUDDH_MFMA_CASE(7, 12, 1)
-            CUDDH_MFMA_CASE(8, 14, 1)
-#undef CUDDH_MFMA_CASE
-            if (!launched)
-                return static_cast<int>(hipErrorNotSupported);
-        }
-        else
-        {
-            const int n_waves = p->pe == 64 ? p->n_patches : (p->n_patches + 1) / 2; // two 32-element patches per wavefront
-            A.xcd_chunk = (n_waves + 7) / 8;
-            if (!launch_op(p, A, accumulate, st))
-                return static_cast<int>(hipErrorNotSupported);
-        }
-        int err = launch_status();
-        if (err)
-            return err;
-        if (p->n_shared > 0)
+        int err = run_plan(p, p->launch[0], c, accumulate, x, y, st);
+        if (!err && p->n_shared > 0)
         {
             hipLaunchKernelGGL(op_border_kernel, dim3(stream_grid(p->n_shared, 256)), dim3(256), 0, st, p->n_shared, accumulate,
                                p->shared_dof, p->shared_off, p->part, y);
@@ -3751,26 +3799,11 @@ extern "C"
 
     int cuddh_hip_helmholtz_apply(const cuddh_helmholtz_plan *p, double omega, const double *x, double *y, void *stream)
     {
-        if (!p)
+        if (!p || p->nqS == 0 || p->nqM == 0)
             return static_cast<int>(hipErrorInvalidValue);
         hipStream_t st = as_stream(stream);
-        HelmArgs A = plan_args(p, x, y);
-        A.omega = omega;
-
-        if (p->Gm && p->Am) // n_basis 6-8 (5 on request): fp64 matrix cores, one 16-element batch per workgroup
-            launch_helm_mfma_any(p, A, st, false);
-        else if (p->nb == 4)
-            launch_patch<4, 5, 8>(p, A, st);
-        else if (p->nb == 3)
-            launch_patch<3, 4, 6>(p, A, st);
-        else if (p->nb == 5)
-            launch_patch<5, 6, 9>(p, A, st);
-        else
-            launch_patch<2, 3, 5>(p, A, st);
-        int err = launch_status();
-        if (err)
-            return err;
-        if (p->n_shared > 0)
+        int err = run_plan(p, p->launch[0], omega, 0, x, y, st);
+        if (!err && p->n_shared > 0)
         {
             hipLaunchKernelGGL(helm_border_kernel, dim3(stream_grid(p->n_shared, 256)), dim3(256), 0, st, p->n_shared, p->ndof, p->n_slots,
                                p->shared_dof, p->shared_off, p->part, y);
@@ -3812,22 +3845,8 @@ extern "C"
         if (z_in == z_out)
             return static_cast<int>(hipErrorInvalidValue);
         hipStream_t st = as_stream(stream);
-        HelmArgs A = plan_args(p, z_in, z_out);
-        A.omega = omega;
-        if (p->Gm && p->Am)
-            launch_helm_mfma_any(p, A, st, true);
-        else if (p->nb == 4)
-            launch_patch<4, 5, 8>(p, A, st, true);
-        else if (p->nb == 3)
-            launch_patch<3, 4, 6>(p, A, st, true);
-        else if (p->nb == 5)
-            launch_patch<5, 6, 9>(p, A, st, true);
-        else
-            launch_patch<2, 3, 5>(p, A, st, true);
-        int err = launch_status();
-        if (err)
-            return err;
-        if (p->n_shared > 0)
+        int err = run_plan(p, p->launch[1], omega, 0, z_in, z_out, st);
+        if (!err && p->n_shared > 0)
         {
             hipLaunchKernelGGL(helm_border_native_kernel, dim3(stream_grid(p->n_shared, 256)), dim3(256), 0, st, p->n_shared, p->n_owned, p->shared_off,
                                reinterpret_cast<const dbl2_t *>(p->part), reinterpret_cast<dbl2_t *>(z_out));
@@ -3848,30 +3867,7 @@ extern "C"
     {
         if (!p || !buf || cap <= 0)
             return static_cast<int>(hipErrorInvalidValue);
-        // mirrors the dispatch of cuddh_hip_helmholtz_apply / cuddh_hip_operator_plan_apply above
-        const bool fused = p->nqS > 0 && p->nqM > 0;
-        const int kind = p->nqS > 0 ? 0 : 1, nq = kind == 0 ? p->nqS : p->nqM;
-        const bool nt = p->streaming != 0;
-        if (fused && p->Gm && p->Am)
-            {
-                const int stg = mfma_stage(p->nb);
-                if (stg)
-                    std::snprintf(buf, cap, "helm_mfma_kernel<%d,%d,%d,chunks=%d+%d> pe=16 affine=%d", p->nb, p->nqS, p->nqM, (stg / 10) % 10, stg % 10, p->gm_stride == 0 ? 1 : 0);
-                else
-                    std::snprintf(buf, cap, "helm_mfma_kernel<%d,%d,%d> pe=16 affine=%d", p->nb, p->nqS, p->nqM, p->gm_stride == 0 ? 1 : 0);
-            }
-        else if (fused && p->nb <= 4 && p->pe == 64 && p->lane_form)
-            std::snprintf(buf, cap, "helm_lane_kernel<%d,%d,%d,NT=%d,UG=%d%s> pe=64", p->nb, p->nqS, p->nqM, nt, p->Gu ? 1 : 0, p->prefetch ? ",PRE=1" : "");
-        else if (fused)
-            std::snprintf(buf, cap, "helm_patch_kernel<%d,%d,%d,NT=%d,UG=%d,PEK=%d%s> pe=%d", p->nb, p->nqS, p->nqM, nt, p->Gu ? 1 : 0, p->pe,
-                          p->pair_mass ? ",MODE=1" : "", p->pe);
-        else if (p->Gm || p->Am)
-            std::snprintf(buf, cap, "op_mfma_kernel<%d,%d,%d> pe=16 affine=%d", p->nb, nq, kind, (kind == 0 ? p->gm_stride : p->am_stride) == 0 ? 1 : 0);
-        else
-        {
-            const bool mu = kind == 0 ? p->Gu != nullptr : p->au != nullptr;
-            std::snprintf(buf, cap, "op_patch_kernel<%d,%d,%d,NT=%d,UG=%d,PEK=%d> pe=%d", p->nb, nq, kind, (!mu && nt) ? 1 : 0, mu ? 1 : 0, p->pe, p->pe);
-        }
+        std::snprintf(buf, cap, "%s", p->description); // written by resolve_plan(), next to the choice it names
         return 0;
     }
 

@@ -1,6 +1,7 @@
-"""Generated-code comparison of two versions of csrc/kernels/ddh.hip, kernel by kernel, without a GPU:
-  python profiles/tools/ddh_codegen_compare.py OLD.hip NEW.hip [--keep DIR]
-Compiles both to gfx950 assembly with build.py's flags for ddh.hip and prints, for every __global__ instantiation, the
+"""Generated-code comparison of two versions of a file under csrc/kernels/ (written for ddh.hip), kernel by kernel, without a GPU:
+  python profiles/tools/ddh_codegen_compare.py OLD.hip NEW.hip [--keep DIR] [--flags-of NAME.hip]
+Compiles both to gfx950 assembly with build.py's flags for NEW's file name (--flags-of: for this file name instead, when
+neither copy carries the name it has in the tree) and prints, for every __global__ instantiation, the
 registers, scratch, LDS, the instruction count, whether the mnemonic histogram is the same and a sequence diff (mnemonics
 left unmatched by difflib's longest-matching-blocks alignment, removed + added: 0 = the same instructions in the same order,
 registers aside; a non-zero figure is an upper bound on what moved, not a minimal edit distance), and the same three for
@@ -17,13 +18,13 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 from cuddhelmholtz_amd import build as B  # noqa: E402
 
-# kernels whose symbol changed: demangled name (without the argument list) in OLD -> in NEW
-RENAMED = {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, false>", "ddh_mfma_kernel<double>": "ddh_mfma_kernel<double, false, false>"}
+# kernels whose symbol changed, per file: demangled name (without the argument list) in OLD -> in NEW
+RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, false>", "ddh_mfma_kernel<double>": "ddh_mfma_kernel<double, false, false>"}}
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
-def kernels(src: Path, out: Path):
-    cmd = [B.hipcc(), *B.COMMON, *[f"-I{p}" for p in B.INCLUDES], *B.HIP_FLAGS, *B.EXTRA_FLAGS["ddh.hip"], "--cuda-device-only", "-S",
+def kernels(src: Path, out: Path, flags_of: str):
+    cmd = [B.hipcc(), *B.COMMON, *[f"-I{p}" for p in B.INCLUDES], *B.HIP_FLAGS, *B.EXTRA_FLAGS.get(flags_of, []), "--cuda-device-only", "-S",
            str(src), "-o", str(out)]
     subprocess.run(cmd, check=True)
     text = out.read_text()
@@ -50,12 +51,14 @@ def kernels(src: Path, out: Path):
 def main():
     keep = Path(sys.argv[sys.argv.index("--keep") + 1]) if "--keep" in sys.argv else Path(tempfile.mkdtemp())
     keep.mkdir(parents=True, exist_ok=True)
-    old, new = kernels(Path(sys.argv[1]), keep / "old.s"), kernels(Path(sys.argv[2]), keep / "new.s")
+    flags_of = sys.argv[sys.argv.index("--flags-of") + 1] if "--flags-of" in sys.argv else Path(sys.argv[2]).name
+    renamed = RENAMED.get(flags_of, {})
+    old, new = kernels(Path(sys.argv[1]), keep / "old.s", flags_of), kernels(Path(sys.argv[2]), keep / "new.s", flags_of)
     print(f"{len(old)} kernels before, {len(new)} after")
     print("kernel | vgpr sgpr scratch lds before -> after | instructions before -> after | histogram | sequence diff | inside loops")
     same = 0
     for name, (m0, o0, l0) in old.items():
-        succ = name if name in new else RENAMED.get(name, name)
+        succ = name if name in new else renamed.get(name, name)
         if succ not in new:
             print(f"{name} | MISSING after")
             continue

@@ -4,6 +4,7 @@ on the same seeded inputs.  Tolerances (relative l2 unless noted):
   DDH fp64 mode                  1e-10
   DDH fp32 mode vs fp64 oracle   2e-4   (reference precision; reported, loosely gated)
 """
+import functools
 import math
 
 import numpy as np
@@ -567,6 +568,85 @@ def test_fused_helmholtz_apply_native_ordering(cuda, monkeypatch, kind, nx, nb, 
     assert o1.num_matvec == o2.num_matvec
     assert abs(o1.res_norm[-1] - o2.res_norm[-1]) <= 1e-10 * o1.res_norm[0]
     assert rel(x2.cpu().numpy(), x1.cpu().numpy()) < 1e-9
+
+
+@functools.lru_cache(maxsize=None)
+def _mfma_stage_case(nb):
+    """25 elements: two 16-element batches, the second partial, with border dofs between them -- the smallest shape on which
+    the staging, the partial batch and the border sum of helm_mfma_kernel can all go wrong."""
+    pm, om = meshes("structured", 5)
+    d = oracle.Discretization(om, nb)
+    faces = pm.boundary_edges()
+    ofs = oracle.FaceSpaceO(d, list(faces))
+    rng = np.random.default_rng(90 + nb)
+    a2 = 0.5 + rng.random(d.ndof)
+    ax = 0.5 + rng.random(ofs.size)
+    xh = rng.standard_normal(2 * d.ndof)
+    omega = 7.0
+    ref = oracle.helmholtz_apply(d, oracle.Stiffness(d), oracle.Mass(d, a2), oracle.FaceMass(ofs, ax), ofs, omega, xh)
+    return pm, faces, d.ndof, a2, ax, xh, omega, ref
+
+
+@pytest.mark.parametrize("nb", [6, 7])
+def test_mfma_stage_variants(cuda, monkeypatch, nb):
+    """CUDDH_HELM_MFMA_STAGE is read when a plan is created, so one process can hold plans of every built variant: unstaged
+    (0) and the four staged ones (chunks of the stiffness + mass metric, wavefronts per SIMD).  Each must report itself through
+    kernel(), match the oracle in both vector orderings (1e-12), and agree between the orderings to 1e-13 (the reference
+    ordering runs every staged plan as 2+2 chunks; the tolerance test_patch_sizes_agree uses between forms) -- bitwise where
+    both orderings run the same form (0, 322, and unset = 322)."""
+    import torch
+
+    import cuddhelmholtz_amd as cd
+
+    pm, faces, n, a2, ax, xh, omega, ref = _mfma_stage_case(nb)
+    fem = cd.H1Space(pm, cd.Basis(nb))
+    fs = cd.FaceSpace(fem, faces)
+    x = to_dev(torch, xh, cuda)
+    chunks = {"0": "", "322": ",chunks=2+2", "321": ",chunks=2+1", "332": ",chunks=3+2", "222": ",chunks=2+2", None: ",chunks=2+2"}
+    for stage in ("0", "322", "321", "332", "222", None):
+        if stage is None:
+            monkeypatch.delenv("CUDDH_HELM_MFMA_STAGE")
+        else:
+            monkeypatch.setenv("CUDDH_HELM_MFMA_STAGE", stage)
+        A = cd.HelmholtzOperator(omega, to_dev(torch, a2, cuda), to_dev(torch, ax, cuda), fem, fs)
+        assert A.fused() and A.has_native()
+        assert A.kernel() == f"helm_mfma_kernel<{nb},{nb + 1},{2 + 3 * nb // 2}{chunks[stage]}> pe=16 affine=1", (stage, A.kernel())
+        y = torch.full((2 * n,), 123.0, dtype=torch.float64, device=cuda)
+        A.action(x, y)
+        z = torch.empty_like(x)
+        A.to_native(x, z)
+        zy = torch.full((2 * n,), -5.0, dtype=torch.float64, device=cuda)
+        A.action_native(z, zy)
+        yn = torch.zeros_like(y)
+        A.from_native(zy, yn)
+        e_ref, e_nat, e_both = rel(y.cpu().numpy(), ref), rel(yn.cpu().numpy(), ref), rel(yn.cpu().numpy(), y.cpu().numpy())
+        print(f"n_basis {nb} stage {stage}: {A.kernel()} vs oracle {e_ref:.2e} (reference ordering) {e_nat:.2e} (native), between them {e_both:.2e}")
+        assert e_ref < 1e-12 and e_nat < 1e-12, stage
+        assert e_both < 1e-13, stage
+        if stage in ("0", "322", None):
+            assert torch.equal(yn, y), stage
+
+
+def test_mfma_stage_rejects_unbuilt_variant(cuda, monkeypatch):
+    """A CUDDH_HELM_MFMA_STAGE value that names no built variant fails plan creation (it used to abort the process at the
+    first native apply).  No apply runs while the bad value is set."""
+    import torch
+
+    import cuddhelmholtz_amd as cd
+
+    nb = 6
+    pm, faces, n, a2, ax, xh, omega, ref = _mfma_stage_case(nb)
+    fem = cd.H1Space(pm, cd.Basis(nb))
+    fs = cd.FaceSpace(fem, faces)
+    a2d, axd = to_dev(torch, a2, cuda), to_dev(torch, ax, cuda)
+    monkeypatch.setenv("CUDDH_HELM_MFMA_STAGE", "999")
+    with pytest.raises(RuntimeError, match="HelmholtzOperator"):
+        cd.HelmholtzOperator(omega, a2d, axd, fem, fs)
+    monkeypatch.delenv("CUDDH_HELM_MFMA_STAGE")
+    A = cd.HelmholtzOperator(omega, a2d, axd, fem, fs)
+    y = torch.empty(2 * n, dtype=torch.float64, device=cuda)
+    A.action(to_dev(torch, xh, cuda), y)
+    assert rel(y.cpu().numpy(), ref) < 1e-12
 
 
 # ------------------------------------------------------------------ GMRES
