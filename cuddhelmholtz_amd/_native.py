@@ -144,6 +144,9 @@ _sig("cuddh_hip_facemass_apply", ci, ci, ci, ci, vp, vp, vp, cd, vp, vp, vp)
 _sig("cuddh_hip_diag_facemass_setup", ci, ci, ci, ci, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_helmholtz_plan_create", ci, C.POINTER(vp), ci, ci, ci, vp, vp, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, vp, vp)
 _sig("cuddh_hip_helmholtz_plan_destroy", ci, vp)
+_sig("cuddh_patch_layout_create", ci, C.POINTER(vp), ci, ci, ci, vp, vp, ci, vp, vp, ci, ci, ci)
+_sig("cuddh_patch_layout_array", C.c_longlong, vp, cp, vp, ci)
+_sig("cuddh_patch_layout_destroy", None, vp)
 _sig("cuddh_hip_helmholtz_apply", ci, vp, cd, vp, vp, vp)
 _sig("cuddh_hip_helmholtz_plan_bytes", cs, vp, ci)
 _sig("cuddh_hip_helmholtz_plan_has_native", ci, vp)

@@ -12,7 +12,8 @@
 //                       batch's metric data in chunks requested one ahead and parked in LDS (no trip to memory inside a slice)
 //   op_mfma_kernel      n_basis 6-8, real   : the same for one operator
 //   helm_border_kernel / op_border_kernel: sums of the per-patch contributions at dofs shared by several patches
-//   repack_*, uniform_metric_kernel: plan construction
+//   repack_*, uniform_metric_kernel: plan construction (the device side; the patch layout itself -- element order, patch-local
+//                       numbering, colours, border slots, native ordering -- is host code in src/patch_layout.cpp)
 //
 // Common design (MI355X): elements are grouped into patches (Morton order of their centroids: 8x8, 4x8 or 4x4 blocks on a
 // structured mesh); one wavefront owns one patch, or two wavefronts share one.
@@ -37,6 +38,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "patch_layout.hpp"
 
 using namespace cuddh_k;
 
@@ -130,6 +132,7 @@ struct cuddh_helmholtz_plan
     HelmArgs args{};         // everything but x, y, omega
     PlanLaunch launch[2];    // [0] reference ordering (and the single operators), [1] plan-native ordering: same flags, same code
     char description[128] = ""; // cuddh_hip_helmholtz_plan_describe
+    std::vector<void *> owned;  // every device array the plan allocated, freed with it (aF is borrowed)
 };
 
 namespace
@@ -1484,16 +1487,31 @@ namespace
         }
     }
 
+    // Device arrays are allocated into an owner list (a plan's, or a local one for scratch arrays) and freed with it.
+    int device_alloc(std::vector<void *> &owner, void **dst, size_t bytes)
+    {
+        *dst = nullptr;
+        const hipError_t e = hipMalloc(dst, bytes);
+        if (e == hipSuccess)
+            owner.push_back(*dst);
+        return static_cast<int>(e);
+    }
+
+    void free_all(std::vector<void *> &owner)
+    {
+        for (void *q : owner)
+            (void)hipFree(q);
+        owner.clear();
+    }
+
     template <typename T>
-    int upload(T **dst, const std::vector<T> &v)
+    int upload(std::vector<void *> &owner, T **dst, const std::vector<T> &v)
     {
         *dst = nullptr;
         if (v.empty())
             return 0;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(dst), v.size() * sizeof(T));
-        if (e != hipSuccess)
-            return static_cast<int>(e);
-        return static_cast<int>(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        const int e = device_alloc(owner, reinterpret_cast<void **>(dst), v.size() * sizeof(T));
+        return e ? e : static_cast<int>(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     }
 
     // does every element's block of `per_elem` values equal element 0's, to the absolute tolerance tol?
@@ -1505,18 +1523,17 @@ namespace
                 atomicExch(differs, 1);
     }
 
-    // If the reference-layout metric array (comps, nq, nq, n_elem) is the same for every element (to 1e-13 of its largest
-    // entry), upload one copy as [q][c][r] and return it in *table; otherwise leave *table null.
-    int uniform_table(double **table, int comps, int nq, int n_elem, const double *d_src)
+    // Is the reference-layout metric array (comps, nq, nq, n_elem) the same for every element (to 1e-13 of its largest
+    // entry)?  Then *block is element 0's block, otherwise it is left empty.
+    int uniform_block(std::vector<double> *block, int comps, int nq, int n_elem, const double *d_src)
     {
-        *table = nullptr;
         const int per_elem = comps * nq * nq;
-        std::vector<double> block(per_elem);
-        hipError_t e = hipMemcpy(block.data(), d_src, per_elem * sizeof(double), hipMemcpyDeviceToHost);
+        std::vector<double> first(per_elem);
+        hipError_t e = hipMemcpy(first.data(), d_src, per_elem * sizeof(double), hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             return static_cast<int>(e);
         double scale = 0.0;
-        for (double v : block)
+        for (double v : first)
             scale = std::max(scale, std::fabs(v));
         int *flag = nullptr, differs = 1;
         e = hipMalloc(reinterpret_cast<void **>(&flag), sizeof(int));
@@ -1531,16 +1548,20 @@ namespace
         }
         if (flag)
             (void)hipFree(flag);
-        if (e != hipSuccess)
-            return static_cast<int>(e);
-        if (differs)
-            return 0;
-        std::vector<double> t(per_elem);
+        if (e == hipSuccess && !differs)
+            block->swap(first);
+        return static_cast<int>(e);
+    }
+
+    // one element's block (c, q, r) as the table the kernels read through scalar loads: [q][c][r]
+    int upload_uniform_table(std::vector<void *> &owner, double **table, int comps, int nq, const std::vector<double> &block)
+    {
+        std::vector<double> t(block.size());
         for (int q = 0; q < nq; ++q)
             for (int c = 0; c < comps; ++c)
                 for (int r = 0; r < nq; ++r)
                     t[(q * comps + c) * nq + r] = block[c + comps * (q + nq * r)];
-        return upload(table, t);
+        return upload(owner, table, t);
     }
 
     // reference layout (c, q, r, el) -> [batch][r][c][q][16]  (matrix-core kernels: slices over the eta index r)
@@ -1591,20 +1612,10 @@ namespace
         }
     }
 
-    int upload_raw(double **dst, const double *src, size_t n)
+    int upload_raw(std::vector<void *> &owner, double **dst, const double *src, size_t n)
     {
         std::vector<double> v(src, src + n);
-        return upload(dst, v);
-    }
-
-    inline uint32_t spread_bits(uint32_t v)
-    {
-        v &= 0xFFFF;
-        v = (v | (v << 8)) & 0x00FF00FF;
-        v = (v | (v << 4)) & 0x0F0F0F0F;
-        v = (v | (v << 2)) & 0x33333333;
-        v = (v | (v << 1)) & 0x55555555;
-        return v;
+        return upload(owner, dst, v);
     }
 
     // fused complex apply on the fp64 matrix cores (16-element batches)
@@ -3244,439 +3255,203 @@ namespace
         L.run(p, L, A, accumulate, st);
         return launch_status();
     }
-} // namespace
 
-extern "C"
-{
-    int cuddh_hip_helmholtz_plan_destroy(cuddh_helmholtz_plan *p)
+    // ---------------------------------------------------------------- plan creation
+    // One operator's share of a plan: its quadrature size (0: not part of the plan), HOST basis tables and DEVICE metric array.
+    struct OperatorInput
     {
-        if (!p)
-            return 0;
-        void *ptrs[] = {p->own_count, p->dof_off, p->dof_list, p->slot_of, p->patch_nel, p->lidx, p->colour, p->Gp, p->aMp, p->Gu, p->au, p->Gm, p->Am, p->face_off,
-                        p->face_lidx, p->face_id, p->face_col, p->PS, p->DS, p->PM, p->PF, p->shared_dof, p->shared_off,
-                        p->part, p->stamps, p->own_off, p->bpos, p->bslot, p->global_of_native};
-        for (void *q : ptrs)
-            if (q)
-                (void)hipFree(q);
-        delete p;
-        return 0;
+        int nq = 0;
+        const double *P = nullptr, *D = nullptr, *metric = nullptr;
+        std::vector<double> uniform; // element 0's block of `metric` when every element has the same and the plan stores one copy
+    };
+    struct PlanOperators
+    {
+        OperatorInput S, M, F; // stiffness (metric G), mass (weights a), boundary-face mass (weights aF, borrowed by the plan)
+    };
+    // which form of its kernel the plan runs: decided by the caller of build_plan, before the layout is built
+    struct PlanForm
+    {
+        bool lane_form = false, pair_mass = false, prefetch = false, stamps = false;
+        int mfma_stage = 0;
+    };
+
+    // affine meshes: one copy of a metric array instead of one per element (CUDDH_PLAN_AFFINE=0 keeps the general form).  The one
+    // probe of an array per plan creation: the answer picks the patch size, becomes the table of the scalar loads or the one
+    // 16-element block of a matrix-core plan.
+    int probe_uniform(const Knobs &knobs, OperatorInput &op, int comps, int n_elem)
+    {
+        return knobs.affine && op.nq > 0 ? uniform_block(&op.uniform, comps, op.nq, n_elem, op.metric) : 0;
     }
 
-    // nqS == 0 or nqM == 0: a plan for a single real operator (the other tables are left empty)
-    static int build_plan(cuddh_helmholtz_plan **out, const Knobs &knobs, int ndof, int n_elem, int nb, const int *h_I, const double *h_xy, int nqS,
-                          const double *h_PS, const double *h_DS, const double *G_S, int nqM, const double *h_PM, const double *a_M,
-                          int n_faces, const int *h_fI, const int *h_face_elem, int nqF, const double *h_PF, const double *a_F,
-                          int pe = PE, bool want_pairs = false)
+    void destroy_plan(cuddh_helmholtz_plan *p)
+    {
+        free_all(p->owned);
+        delete p;
+    }
+
+    // The device side of a plan: uploads the layout, repacks the metric arrays patch by patch, works out the byte figures and
+    // resolves the launch.  in.pe == 16: the matrix-core kernels.  ops.S.nq == 0 or ops.M.nq == 0: a plan for a single real operator.
+    int build_plan(cuddh_helmholtz_plan **out, const Knobs &knobs, const PatchLayoutInput &in, const PatchLayout &L, const PlanOperators &ops,
+                   const PlanForm &form)
     {
         *out = nullptr;
-        const bool mfma = pe == 16; // 16-element batches: the matrix-core kernels
+        const int nb = in.nb, n_elem = in.n_elem, pe = in.pe, n_patches = L.n_patches, n_faces = in.n_faces;
+        const int nqS = ops.S.nq, nqM = ops.M.nq, nqF = ops.F.nq;
+        const bool mfma = pe == 16, fused = nqS > 0 && nqM > 0;
 
         cuddh_helmholtz_plan *p = new cuddh_helmholtz_plan;
-        p->ndof = ndof;
+        p->ndof = in.ndof;
         p->n_elem = n_elem;
         p->nb = nb;
         p->nqS = nqS;
         p->nqM = nqM;
         p->nqF = nqF;
         p->n_faces = n_faces;
-        p->aF = a_F;
-        const int nn = nb * nb;
-
-        // ---- element order: Morton curve over the centroids
-        std::vector<int> perm(n_elem);
-        for (int e = 0; e < n_elem; ++e)
-            perm[e] = e;
-        if (h_xy)
-        {
-            double lo[2] = {h_xy[0], h_xy[1]}, hi[2] = {h_xy[0], h_xy[1]};
-            for (int e = 0; e < n_elem; ++e)
-                for (int a = 0; a < 2; ++a)
-                {
-                    lo[a] = std::min(lo[a], h_xy[2 * e + a]);
-                    hi[a] = std::max(hi[a], h_xy[2 * e + a]);
-                }
-            std::vector<uint64_t> key(n_elem);
-            for (int e = 0; e < n_elem; ++e)
-            {
-                uint32_t c[2];
-                for (int a = 0; a < 2; ++a)
-                {
-                    const double span = hi[a] - lo[a];
-                    const double t = span > 0 ? (h_xy[2 * e + a] - lo[a]) / span : 0.0;
-                    c[a] = static_cast<uint32_t>(std::min(65535.0, std::max(0.0, t * 65535.0 + 0.5)));
-                }
-                key[e] = (static_cast<uint64_t>(spread_bits(c[0]) | (spread_bits(c[1]) << 1)) << 32) | static_cast<uint32_t>(e);
-            }
-            std::sort(key.begin(), key.end());
-            for (int e = 0; e < n_elem; ++e)
-                perm[e] = static_cast<int>(key[e] & 0xFFFFFFFFu);
-        }
-
-        const int n_patches = (n_elem + pe - 1) / pe;
+        p->aF = ops.F.metric;
         p->n_patches = n_patches;
         p->pe = pe;
-        std::vector<int> padded_perm((size_t)n_patches * pe, -1);
-        std::copy(perm.begin(), perm.end(), padded_perm.begin());
-        std::vector<int> patch_of_elem(n_elem);
-        for (int pos = 0; pos < n_elem; ++pos)
-            patch_of_elem[perm[pos]] = pos / pe;
+        p->max_loc = L.max_loc;
+        p->ncol = L.ncol;
+        p->nfcol = L.nfcol;
+        p->n_shared = L.n_shared;
+        p->n_slots = L.n_slots;
+        p->dof_stride = L.dof_stride;
+        p->lane_form = form.lane_form;
+        // the lane form reads its metric slices with 16-byte loads
+        p->pair_layout = form.lane_form;
+        p->pair_mass = form.pair_mass;
+        p->prefetch = form.prefetch;
+        p->mfma_stage = form.mfma_stage;
 
-        // ---- faces bucketed by the patch of their element
-        std::vector<int> face_off(n_patches + 1, 0);
-        for (int f = 0; f < n_faces; ++f)
-            face_off[patch_of_elem[h_face_elem[f]] + 1]++;
-        for (int q = 0; q < n_patches; ++q)
-            face_off[q + 1] += face_off[q];
-        std::vector<int> face_id(n_faces);
-        {
-            std::vector<int> cursor(face_off.begin(), face_off.end() - 1);
-            for (int f = 0; f < n_faces; ++f)
-                face_id[cursor[patch_of_elem[h_face_elem[f]]]++] = f;
-        }
-
-        // ---- patch-local numbering, colours
-        std::vector<int> dof_off(n_patches + 1, 0), dof_list, patch_nel(n_patches);
-        const int np2 = (nn + 1) / 2;
-        std::vector<uint32_t> lidx((size_t)n_patches * np2 * pe, 0);
-        std::vector<uint16_t> face_lidx((size_t)n_faces * nb, 0);
-        std::vector<uint8_t> colour((size_t)n_patches * pe, 0), face_col(n_faces, 0);
-        std::vector<int> stamp(ndof, -1), loc(ndof, 0), touches(ndof, 0);
-        std::vector<uint32_t> used, usedF;
-        int max_loc = 0, ncol = 1, nfcol = 1;
-        dof_list.reserve((size_t)n_elem * nn / 2);
-        // how many patches touch a dof (a dof touched by one patch is OWNED by it: its result goes straight to y)
-        for (int q = 0; q < n_patches; ++q)
-        {
-            const int nel = std::min(pe, n_elem - q * pe);
-            for (int le = 0; le < nel; ++le)
-            {
-                const int *gi = h_I + (size_t)nn * perm[q * pe + le];
-                for (int n = 0; n < nn; ++n)
-                    if (stamp[gi[n]] != q)
-                    {
-                        stamp[gi[n]] = q;
-                        touches[gi[n]]++;
-                    }
-            }
-        }
-        std::fill(stamp.begin(), stamp.end(), -1);
-        // Patch-local numbering: the owned dofs first, the border dofs (shared with other patches) last, each group in the
-        // order its dofs are first met.  The write-out of an owned dof then needs no destination entry -- it is the gather index
-        // -- so a kernel that knows own_count reads only the tail of the patch's slot_of segment (helm_lane_kernel does).
-        std::vector<int> own_count(n_patches), border_first;
-        for (int q = 0; q < n_patches; ++q)
-        {
-            const int first = static_cast<int>(dof_list.size());
-            dof_off[q] = first;
-            const int nel = std::min(pe, n_elem - q * pe);
-            patch_nel[q] = nel;
-            border_first.clear();
-            for (int le = 0; le < nel; ++le)
-            {
-                const int *gi = h_I + (size_t)nn * perm[q * pe + le];
-                for (int n = 0; n < nn; ++n)
-                {
-                    const int g = gi[n];
-                    if (stamp[g] == q)
-                        continue;
-                    stamp[g] = q;
-                    if (touches[g] > 1)
-                        border_first.push_back(g);
-                    else
-                    {
-                        loc[g] = static_cast<int>(dof_list.size()) - first;
-                        dof_list.push_back(g);
-                    }
-                }
-            }
-            own_count[q] = static_cast<int>(dof_list.size()) - first;
-            for (const int g : border_first)
-            {
-                loc[g] = static_cast<int>(dof_list.size()) - first;
-                dof_list.push_back(g);
-            }
-            used.assign(dof_list.size() - first, 0);
-            for (int le = 0; le < nel; ++le)
-            {
-                const int *gi = h_I + (size_t)nn * perm[q * pe + le];
-                uint32_t taken = 0;
-                for (int n = 0; n < nn; ++n)
-                {
-                    const int g = gi[n];
-                    lidx[((size_t)q * np2 + n / 2) * pe + le] |= static_cast<uint32_t>(loc[g]) << (16 * (n & 1));
-                    taken |= used[loc[g]];
-                }
-                int c = 0;
-                while (c < 31 && (taken >> c & 1u))
-                    ++c;
-                colour[(size_t)q * pe + le] = static_cast<uint8_t>(c);
-                ncol = std::max(ncol, c + 1);
-                for (int n = 0; n < nn; ++n)
-                    used[loc[gi[n]]] |= 1u << c;
-            }
-            const int nloc = static_cast<int>(dof_list.size()) - first;
-            if (nloc > 65535)
-            {
-                cuddh_hip_helmholtz_plan_destroy(p);
-                return static_cast<int>(hipErrorInvalidValue);
-            }
-            max_loc = std::max(max_loc, nloc);
-
-            usedF.assign(nloc, 0);
-            for (int t = face_off[q]; t < face_off[q + 1]; ++t)
-            {
-                const int *fg = h_fI + (size_t)nb * face_id[t];
-                uint32_t taken = 0;
-                for (int k = 0; k < nb; ++k)
-                {
-                    if (stamp[fg[k]] != q)
-                    {
-                        cuddh_hip_helmholtz_plan_destroy(p);
-                        return static_cast<int>(hipErrorInvalidValue); // face dof not in its element's patch
-                    }
-                    face_lidx[(size_t)t * nb + k] = static_cast<uint16_t>(loc[fg[k]]);
-                    taken |= usedF[loc[fg[k]]];
-                }
-                int c = 0;
-                while (c < 31 && (taken >> c & 1u))
-                    ++c;
-                face_col[t] = static_cast<uint8_t>(c);
-                nfcol = std::max(nfcol, c + 1);
-                for (int k = 0; k < nb; ++k)
-                    usedF[loc[fg[k]]] |= 1u << c;
-            }
-        }
-        dof_off[n_patches] = static_cast<int>(dof_list.size());
-        p->max_loc = max_loc;
-        p->ncol = ncol;
-        p->nfcol = n_faces > 0 ? nfcol : 0;
-
-        // ---- dofs touched by more than one patch get one slot per touching patch
-        std::vector<int> shared_index(ndof, -1), shared_dof, shared_off(1, 0);
-        for (int g = 0; g < ndof; ++g)
-            if (touches[g] > 1)
-            {
-                shared_index[g] = static_cast<int>(shared_dof.size());
-                shared_dof.push_back(g);
-                shared_off.push_back(shared_off.back() + touches[g]);
-            }
-        const int n_shared = static_cast<int>(shared_dof.size());
-        const int n_slots = shared_off.back();
-        std::vector<int> slot_of(dof_list.size()), fill(shared_off.begin(), shared_off.end() - 1);
-        for (size_t i = 0; i < dof_list.size(); ++i)
-        {
-            const int j = shared_index[dof_list[i]];
-            // owned: the global dof itself; border: -(slot) - 1, the slots of one dof being contiguous and ordered by patch
-            slot_of[i] = j >= 0 ? -(fill[j]++) - 1 : dof_list[i];
-        }
-        p->n_shared = n_shared;
-        p->n_slots = n_slots;
-        // ---- upload
         int err = 0;
         auto ok = [&](int e)
         {
             if (e && !err)
                 err = e;
         };
-        // ---- plan-native vector ordering (lane-form plans): owned dofs patch by patch, then the border dofs in shared_dof order
-        size_t native_list_entries = 0;
-        if (nqS > 0 && nqM > 0) // every fused plan; which kernels take native vectors: cuddh_hip_helmholtz_plan_has_native
+        std::vector<void *> &own = p->owned;
+        if (L.has_native) // every fused plan whose dofs are all touched; which kernels take native vectors: cuddh_hip_helmholtz_plan_has_native
         {
-            std::vector<int> own_off(n_patches + 1, 0);
-            for (int q = 0; q < n_patches; ++q)
-                own_off[q + 1] = own_off[q] + own_count[q];
-            const int n_owned = own_off[n_patches];
-            int bstride = 1;
-            for (int q = 0; q < n_patches; ++q)
-                bstride = std::max(bstride, dof_off[q + 1] - dof_off[q] - own_count[q]);
-            std::vector<int> bpos((size_t)n_patches * bstride, 0), bslot((size_t)n_patches * bstride, 0), g_of_n(ndof, -1);
-            for (int q = 0; q < n_patches; ++q)
-            {
-                const int nloc = dof_off[q + 1] - dof_off[q], nb_q = nloc - own_count[q];
-                for (int i = 0; i < own_count[q]; ++i)
-                    g_of_n[own_off[q] + i] = dof_list[dof_off[q] + i];
-                for (int t = 0; t < bstride; ++t)
-                {
-                    const int i = own_count[q] + std::min(t, std::max(nb_q - 1, 0));
-                    if (nb_q == 0)
-                        continue; // no border dofs: the padding is never read (clamped index 0, value 0 = a valid position)
-                    bpos[(size_t)q * bstride + t] = n_owned + shared_index[dof_list[dof_off[q] + i]];
-                    bslot[(size_t)q * bstride + t] = -slot_of[dof_off[q] + i] - 1;
-                }
-                native_list_entries += nb_q;
-            }
-            for (int j = 0; j < n_shared; ++j)
-                g_of_n[n_owned + j] = shared_dof[j];
-            bool perm_ok = n_owned + n_shared == ndof;
-            for (int n = 0; n < ndof && perm_ok; ++n)
-                perm_ok = g_of_n[n] >= 0;
-            if (perm_ok) // (a dof no element touches would break the permutation: such a space keeps the reference ordering only)
-            {
-                p->n_owned = n_owned;
-                p->bstride = bstride;
-                ok(upload(&p->own_off, own_off));
-                ok(upload(&p->bpos, bpos));
-                ok(upload(&p->bslot, bslot));
-                ok(upload(&p->global_of_native, g_of_n));
-            }
+            p->n_owned = L.n_owned;
+            p->bstride = L.bstride;
+            ok(upload(own, &p->own_off, L.own_off));
+            ok(upload(own, &p->bpos, L.bpos));
+            ok(upload(own, &p->bslot, L.bslot));
+            ok(upload(own, &p->global_of_native, L.global_of_native));
         }
-        ok(upload(&p->dof_off, dof_off));
-        // Fixed stride for the per-patch lists (helm_lane_kernel, helm_patch_kernel, op_patch_kernel with one patch per wavefront):
-        // segment p starts at p * max_loc and is padded with its last entry, so a kernel can request its first indices without
-        // waiting for dof_off -- one dependent (scalar) round trip less at the head of every wavefront's chain.  The matrix-core
-        // kernels and op_patch_kernel with two patches per wavefront keep the packed lists.
-        const bool fixed_stride = !mfma && (pe == 64 || (nqS > 0 && nqM > 0));
-        if (fixed_stride)
-        {
-            std::vector<int> dl((size_t)n_patches * max_loc), so((size_t)n_patches * max_loc);
-            for (int q = 0; q < n_patches; ++q)
-            {
-                const int n = dof_off[q + 1] - dof_off[q];
-                for (int i = 0; i < max_loc; ++i)
-                {
-                    dl[(size_t)q * max_loc + i] = dof_list[dof_off[q] + std::min(i, n - 1)];
-                    so[(size_t)q * max_loc + i] = slot_of[dof_off[q] + std::min(i, n - 1)];
-                }
-            }
-            p->dof_stride = max_loc;
-            ok(upload(&p->dof_list, dl));
-            ok(upload(&p->slot_of, so));
-        }
-        else
-        {
-            ok(upload(&p->dof_list, dof_list));
-            ok(upload(&p->slot_of, slot_of));
-        }
-        ok(upload(&p->own_count, own_count));
-        ok(upload(&p->patch_nel, patch_nel));
-        ok(upload(&p->lidx, lidx));
-        ok(upload(&p->colour, colour));
-        ok(upload(&p->face_off, face_off));
-        ok(upload(&p->face_lidx, face_lidx));
-        ok(upload(&p->face_id, face_id));
-        ok(upload(&p->face_col, face_col));
-        ok(upload(&p->shared_dof, shared_dof));
-        ok(upload(&p->shared_off, shared_off));
+        ok(upload(own, &p->dof_off, L.dof_off));
+        ok(upload(own, &p->dof_list, L.dof_list));
+        ok(upload(own, &p->slot_of, L.slot_of));
+        ok(upload(own, &p->own_count, L.own_count));
+        ok(upload(own, &p->patch_nel, L.patch_nel));
+        ok(upload(own, &p->lidx, L.lidx));
+        ok(upload(own, &p->colour, L.colour));
+        ok(upload(own, &p->face_off, L.face_off));
+        ok(upload(own, &p->face_lidx, L.face_lidx));
+        ok(upload(own, &p->face_id, L.face_id));
+        ok(upload(own, &p->face_col, L.face_col));
+        ok(upload(own, &p->shared_dof, L.shared_dof));
+        ok(upload(own, &p->shared_off, L.shared_off));
         if (nqS > 0)
         {
-            ok(upload_raw(&p->PS, h_PS, (size_t)nqS * nb));
-            ok(upload_raw(&p->DS, h_DS, (size_t)nqS * nb));
+            ok(upload_raw(own, &p->PS, ops.S.P, (size_t)nqS * nb));
+            ok(upload_raw(own, &p->DS, ops.S.D, (size_t)nqS * nb));
         }
         if (nqM > 0)
-            ok(upload_raw(&p->PM, h_PM, (size_t)nqM * nb));
+            ok(upload_raw(own, &p->PM, ops.M.P, (size_t)nqM * nb));
         if (n_faces > 0)
-            ok(upload_raw(&p->PF, h_PF, (size_t)nqF * nb));
-        if (n_slots > 0)
-            ok(static_cast<int>(hipMalloc(reinterpret_cast<void **>(&p->part), (size_t)2 * n_slots * sizeof(double))));
+            ok(upload_raw(own, &p->PF, ops.F.P, (size_t)nqF * nb));
+        if (L.n_slots > 0)
+            ok(device_alloc(own, reinterpret_cast<void **>(&p->part), (size_t)2 * L.n_slots * sizeof(double)));
+        if (form.stamps) // diagnostic, see cuddh_hip_helmholtz_plan_read_stamps
+            if (device_alloc(own, reinterpret_cast<void **>(&p->stamps), (size_t)n_patches * 8 * sizeof(unsigned long long)) == 0)
+                (void)hipMemset(p->stamps, 0, (size_t)n_patches * 8 * sizeof(unsigned long long));
 
-        int *d_perm = nullptr;
-        ok(upload(&d_perm, padded_perm));
-        // affine meshes: one copy of a metric array instead of one per element (CUDDH_PLAN_AFFINE=0 keeps the general form)
-        const bool try_affine = knobs.affine;
-        bool uniform_G = false, uniform_a = false; // matrix-core plans: a uniform array becomes ONE 16-element block (stride 0)
-        if (mfma && try_affine)
+        // ---- metric arrays.  A uniform one is ONE table read through scalar loads (the fused complex kernel always reads
+        // per-element mass weights: they carry a(x)^2), on the matrix cores ONE 16-element block (stride 0).
+        const bool uniform_G = nqS > 0 && !ops.S.uniform.empty(), uniform_a = nqM > 0 && !ops.M.uniform.empty() && (mfma || nqS == 0);
+        if (uniform_G && !mfma)
+            ok(upload_uniform_table(own, &p->Gu, 3, nqS, ops.S.uniform));
+        if (uniform_a && !mfma)
+            ok(upload_uniform_table(own, &p->au, 1, nqM, ops.M.uniform));
+        std::vector<void *> scratch;
+        int *d_perm = nullptr, *d_zero = nullptr; // d_zero, "element 0 in all 16 lanes": the one block of a uniform array
+        ok(upload(scratch, &d_perm, L.perm));
+        if (mfma && (uniform_G || uniform_a))
         {
-            double *probe = nullptr;
-            if (nqS > 0)
-            {
-                ok(uniform_table(&probe, 3, nqS, n_elem, G_S));
-                uniform_G = probe != nullptr;
-                if (probe)
-                    (void)hipFree(probe);
-            }
-            if (nqM > 0)
-            {
-                probe = nullptr;
-                ok(uniform_table(&probe, 1, nqM, n_elem, a_M));
-                uniform_a = probe != nullptr;
-                if (probe)
-                    (void)hipFree(probe);
-            }
-        }
-        if (try_affine && !mfma && nqS > 0)
-            ok(uniform_table(&p->Gu, 3, nqS, n_elem, G_S));
-        if (try_affine && !mfma && nqM > 0 && nqS == 0) // the fused complex kernel always reads per-element mass weights (they carry a(x)^2)
-            ok(uniform_table(&p->au, 1, nqM, n_elem, a_M));
-        int *d_zero = nullptr; // "element 0 in all 16 lanes": the one block of a uniform array
-        if (uniform_G || uniform_a)
-        {
-            ok(static_cast<int>(hipMalloc(reinterpret_cast<void **>(&d_zero), (size_t)pe * sizeof(int))));
+            ok(device_alloc(scratch, reinterpret_cast<void **>(&d_zero), (size_t)pe * sizeof(int)));
             if (d_zero)
                 ok(static_cast<int>(hipMemset(d_zero, 0, (size_t)pe * sizeof(int))));
         }
-        // the lane form of the fused apply (64-element patches, general geometry -- or the affine n_basis-2 form, whose mass
-        // weights are still per element) reads its slices with 16-byte loads
-        p->pair_layout = (want_pairs && !mfma && pe == 64 && nqS > 0 && nqM > 0 && (!p->Gu || nb == 2)) ? 1 : 0;
         const long long nG = p->Gu ? 0 : (long long)(uniform_G ? 1 : n_patches) * 3 * nqS * nqS * pe;
         const long long nA = p->au ? 0 : (long long)(uniform_a ? 1 : n_patches) * nqM * nqM * pe;
         if (nG > 0)
-            ok(static_cast<int>(hipMalloc(reinterpret_cast<void **>(mfma ? &p->Gm : &p->Gp), nG * sizeof(double))));
+            ok(device_alloc(own, reinterpret_cast<void **>(mfma ? &p->Gm : &p->Gp), nG * sizeof(double)));
         if (nA > 0)
-            ok(static_cast<int>(hipMalloc(reinterpret_cast<void **>(mfma ? &p->Am : &p->aMp), nA * sizeof(double))));
+            ok(device_alloc(own, reinterpret_cast<void **>(mfma ? &p->Am : &p->aMp), nA * sizeof(double)));
         if (!err)
         {
             if (nG > 0 && mfma)
-                hipLaunchKernelGGL(repack_mfma_kernel, dim3(stream_grid(nG, 256)), dim3(256), 0, nullptr, nG, 3, nqS, uniform_G ? d_zero : d_perm, G_S,
+                hipLaunchKernelGGL(repack_mfma_kernel, dim3(stream_grid(nG, 256)), dim3(256), 0, nullptr, nG, 3, nqS, uniform_G ? d_zero : d_perm, ops.S.metric,
                                    p->Gm);
             else if (nG > 0)
-                hipLaunchKernelGGL(repack_kernel, dim3(stream_grid(nG, 256)), dim3(256), 0, nullptr, nG, 3, nqS, pe, d_perm, G_S, p->Gp, p->pair_layout);
+                hipLaunchKernelGGL(repack_kernel, dim3(stream_grid(nG, 256)), dim3(256), 0, nullptr, nG, 3, nqS, pe, d_perm, ops.S.metric, p->Gp, p->pair_layout);
             if (nA > 0 && mfma)
-                hipLaunchKernelGGL(repack_mfma_kernel, dim3(stream_grid(nA, 256)), dim3(256), 0, nullptr, nA, 1, nqM, uniform_a ? d_zero : d_perm, a_M,
+                hipLaunchKernelGGL(repack_mfma_kernel, dim3(stream_grid(nA, 256)), dim3(256), 0, nullptr, nA, 1, nqM, uniform_a ? d_zero : d_perm, ops.M.metric,
                                    p->Am);
             else if (nA > 0)
-                hipLaunchKernelGGL(repack_kernel, dim3(stream_grid(nA, 256)), dim3(256), 0, nullptr, nA, 1, nqM, pe, d_perm, a_M, p->aMp, p->pair_layout);
+                hipLaunchKernelGGL(repack_kernel, dim3(stream_grid(nA, 256)), dim3(256), 0, nullptr, nA, 1, nqM, pe, d_perm, ops.M.metric, p->aMp, p->pair_layout);
             ok(launch_status());
             ok(static_cast<int>(hipDeviceSynchronize()));
         }
-        if (d_zero)
-            (void)hipFree(d_zero);
-        if (d_perm)
-            (void)hipFree(d_perm);
+        free_all(scratch);
         if (err)
         {
-            cuddh_hip_helmholtz_plan_destroy(p);
+            destroy_plan(p);
             return err;
         }
 
-        const bool single = nqS == 0 || nqM == 0; // one real vector in, one out
+        // ---- byte figures
+        const int nn = nb * nb;
         p->bytes_alg = (size_t)n_elem * ((size_t)3 * nqS * nqS * 8 + (size_t)nqM * nqM * 8 + (size_t)nn * 4) +
-                       (size_t)ndof * (single ? 16 : 32) + (size_t)n_faces * ((size_t)nqF * 8 + (size_t)nb * 4);
-        size_t exclusive = 0;
-        for (int s : slot_of)
-            exclusive += s >= 0;
+                       (size_t)in.ndof * (fused ? 32 : 16) + (size_t)n_faces * ((size_t)nqF * 8 + (size_t)nb * 4); // (single: one real vector in, one out)
         // destination list of the write-out (slot_of): the plan kernels read it only for the rows of local dofs that hold border
         // dofs -- rows of 64 (helm_lane_kernel, op_patch_kernel with one patch per wavefront) or of 2 pe (helm_patch_kernel);
         // the matrix-core kernels and op_patch_kernel with two patches per wavefront read all of it
-        size_t dest_entries = dof_list.size();
-        const bool fused_plan = nqS > 0 && nqM > 0;
-        const int dest_row = mfma ? 0 : (fused_plan ? (p->pair_layout ? 64 : 2 * pe) : (pe == 64 ? 64 : 0));
-        if (dest_row > 0)
-        {
-            dest_entries = n_patches; // own_count
-            for (int q = 0; q < n_patches; ++q)
-                dest_entries += (dof_off[q + 1] - dof_off[q]) - (own_count[q] / dest_row) * dest_row;
-        }
-        const size_t dest_bytes = dest_entries * 4;
-        p->bytes_actual = (size_t)nG * 8 + (size_t)nA * 8 + lidx.size() * 4 + colour.size() + dof_list.size() * (4 + 16) + dest_bytes + // dof (gather), x
-                          exclusive * 16 + (size_t)n_slots * (16 + 16) + (size_t)n_shared * (16 + 8) +
-                          (size_t)n_faces * ((size_t)nqF * 8 + (size_t)nb * 2 + 5);
+        const int dest_row = mfma ? 0 : (fused ? (p->pair_layout ? 64 : 2 * pe) : (pe == 64 ? 64 : 0));
+        const size_t dest_bytes = L.dest_entries_for_row(dest_row) * 4, n_shared = L.n_shared, n_slots = L.n_slots;
+        p->bytes_actual = (size_t)nG * 8 + (size_t)nA * 8 + L.lidx.size() * 4 + L.colour.size() + L.list_entries * (4 + 16) + dest_bytes + // dof (gather), x
+                          L.owned_entries * 16 + n_slots * (16 + 16) + n_shared * (16 + 8) + (size_t)n_faces * ((size_t)nqF * 8 + (size_t)nb * 2 + 5);
         if (p->own_off) // the native apply: no dof list for owned dofs, two short lists for the border dofs, x gathered once per touching patch
-            p->bytes_native = (size_t)nG * 8 + (size_t)nA * 8 + lidx.size() * 4 + colour.size() + (size_t)(n_patches + 1) * 4 + native_list_entries * 8 +
-                              dof_list.size() * 16 + exclusive * 16 + (size_t)n_slots * (16 + 16) + (size_t)n_shared * (16 + 4) +
+            p->bytes_native = (size_t)nG * 8 + (size_t)nA * 8 + L.lidx.size() * 4 + L.colour.size() + (size_t)(n_patches + 1) * 4 + L.native_list_entries * 8 +
+                              L.list_entries * 16 + L.owned_entries * 16 + n_slots * (16 + 16) + n_shared * (16 + 4) +
                               (size_t)n_faces * ((size_t)nqF * 8 + (size_t)nb * 2 + 5);
-        if (p->Gu || p->au) // SURVEY 8d's "affine" figure: the uniform metric arrays are not traffic
-            p->bytes_affine = p->bytes_alg - (size_t)n_elem * ((p->Gu ? (size_t)3 * nqS * nqS * 8 : 0) + (p->au ? (size_t)nqM * nqM * 8 : 0));
+        if (uniform_G || uniform_a) // SURVEY 8d's "affine" figure: the uniform metric arrays are not traffic
+            p->bytes_affine = p->bytes_alg - (size_t)n_elem * ((uniform_G ? (size_t)3 * nqS * nqS * 8 : 0) + (uniform_a ? (size_t)nqM * nqM * 8 : 0));
         if (mfma)
         {
             p->gm_stride = uniform_G ? 0 : (long long)3 * nqS * nqS * pe;
             p->am_stride = uniform_a ? 0 : (long long)nqM * nqM * pe;
-            if (uniform_G || uniform_a)
-                p->bytes_affine = p->bytes_alg - (size_t)n_elem * ((uniform_G ? (size_t)3 * nqS * nqS * 8 : 0) + (uniform_a ? (size_t)nqM * nqM * 8 : 0));
         }
         p->streaming = p->bytes_actual > (size_t)256 << 20; // the infinity cache
         if (knobs.streaming >= 0) // measurement knob: 0 / 1 overrides the size rule
             p->streaming = knobs.streaming;
-        *out = p;
+
+        err = resolve_plan(p);
+        if (err)
+            destroy_plan(p);
+        else
+            *out = p;
+        return err;
+    }
+} // namespace
+
+extern "C"
+{
+    int cuddh_hip_helmholtz_plan_destroy(cuddh_helmholtz_plan *p)
+    {
+        if (p)
+            destroy_plan(p);
         return 0;
     }
 
@@ -3689,6 +3464,11 @@ extern "C"
         if (!supported(nb, nqS, nqM) || n_elem <= 0)
             return static_cast<int>(hipErrorNotSupported);
         const Knobs knobs = read_knobs();
+        PlanOperators ops;
+        ops.S = {nqS, h_PS, h_DS, G_S};
+        ops.M = {nqM, h_PM, nullptr, a_M};
+        ops.F = {nqF, h_PF, nullptr, a_F};
+        PlanForm form;
         int pe = helm_mfma(nb, nqS, nqM) ? 16 : PE;
         // n_basis 5 sits between the two schemes: one element per lane needs more registers than 3 wavefronts per SIMD have
         // (26 spilled), the matrix-core scheme pads 5 xi-indices to 8.  Measured (profiles/r03/config5_ab.txt, 768^2): one element
@@ -3696,23 +3476,26 @@ extern "C"
         // CUDDH_HELM_NB5_MFMA=1 selects the matrix-core scheme (tests keep it correct)
         if (nb == 5 && nqS == 6 && nqM == 9 && knobs.nb5_mfma)
             pe = 16;
-        const int stage = mfma_stage(nb, knobs);
-        if (pe == 16 && !mfma_stage_built(stage))
+        form.mfma_stage = mfma_stage(nb, knobs);
+        if (pe == 16 && !mfma_stage_built(form.mfma_stage))
         {
-            std::fprintf(stderr, "CUDDH_HELM_MFMA_STAGE=%d is not a built variant (322, 321, 332, 222)\n", stage);
+            std::fprintf(stderr, "CUDDH_HELM_MFMA_STAGE=%d is not a built variant (322, 321, 332, 222)\n", form.mfma_stage);
             return static_cast<int>(hipErrorInvalidValue);
         }
+        int err = probe_uniform(knobs, ops.S, 3, n_elem);
+        if (!err && pe == 16) // (one element per lane: the fused kernel reads per-element mass weights whatever they are)
+            err = probe_uniform(knobs, ops.M, 1, n_elem);
+        if (err)
+            return err;
+        const bool uniform_G = !ops.S.uniform.empty();
         if (pe == PE && nb <= 4)
         {
             // Affine plans (uniform stiffness metric, read through scalar loads) use 64-element patches, two wavefronts sharing
             // one LDS copy: a third fewer border dofs and slots.  Measured at 1024^2: n_basis 4 331 -> 316 us, n_basis 3
             // 137 -> 130 us; with per-element metrics the larger patch is a wash on structured meshes and 6 % slower on
             // the irregular one (the two waves wait for each other at every colour phase), n_basis 5 does not change.
-            double *probe = nullptr;
-            if (knobs.affine && uniform_table(&probe, 3, nqS, n_elem, G_S) == 0 && probe)
+            if (uniform_G)
                 pe = 64;
-            if (probe)
-                (void)hipFree(probe);
             if (knobs.helm_pe) // measurement knob
                 pe = knobs.helm_pe;
         }
@@ -3724,37 +3507,27 @@ extern "C"
         // n_basis 2 (92 VGPRs, 5 waves/SIMD): 1024^2 124 -> 103 us, 2048^2 510 -> 418-438 us.
         // Affine plans: only n_basis 2 gains from the lane form (1024^2: 80 -> 68 us); n_basis 3 loses (133 -> 154 us) and
         // n_basis 4 loses a lot (311 -> 365 us: with no metric traffic the kernel lives on occupancy).
-        const bool affine_plan = pe == 64; // decided above
-        const bool affine_lane = affine_plan && nb == 2;
-        bool lane_form = (pe == PE && ((nb == 4 && n_elem >= 4096 * 64) || (nb <= 3 && n_elem >= 8192 * 64))) || (affine_lane && n_elem >= 8192 * 64);
+        const bool affine_lane = pe == 64 && nb == 2; // (pe == 64: the affine plan, decided above)
+        bool lane_patches = (pe == PE && ((nb == 4 && n_elem >= 4096 * 64) || (nb <= 3 && n_elem >= 8192 * 64))) || (affine_lane && n_elem >= 8192 * 64);
         if (knobs.lane >= 0)
-            lane_form = nb <= 4 && (pe == PE || affine_lane) && knobs.lane == 1;
-        if (lane_form)
+            lane_patches = nb <= 4 && (pe == PE || affine_lane) && knobs.lane == 1;
+        if (lane_patches)
             pe = 64;
-        int err = build_plan(out, knobs, ndof, n_elem, nb, h_I, h_xy, nqS, h_PS, h_DS, G_S, nqM, h_PM, a_M, n_faces, h_fI, h_face_elem, nqF, h_PF,
-                             a_F, pe, lane_form);
-        if (!err && *out)
-        {
-            cuddh_helmholtz_plan *p = *out;
-            p->lane_form = p->pair_layout; // = lane_form && (general geometry || affine n_basis 2): decided in build_plan
-            // the lane form with the whole metric block in the register file (PRE, one wavefront per SIMD): measured SLOWER
-            // than the slice-by-slice chain at two wavefronts per SIMD (1024^2, n_basis 4: 434-442 vs 373-376 us), although
-            // the metric stream alone runs at 6.46 TB/s that way -- see the comment at the kernel.  CUDDH_HELM_PRE=1 selects it
-            // for A/B runs; tests keep it correct.
-            p->pair_mass = nb == 3 && !p->Gu && !p->lane_form && knobs.pair_mass;
-            p->prefetch = p->lane_form && knobs.pre;
-            p->mfma_stage = stage;
-            if (knobs.stamps && (p->lane_form || p->pe == 16)) // diagnostic, see cuddh_hip_helmholtz_plan_read_stamps
-                if (hipMalloc(reinterpret_cast<void **>(&p->stamps), (size_t)p->n_patches * 8 * sizeof(unsigned long long)) == hipSuccess)
-                    (void)hipMemset(p->stamps, 0, (size_t)p->n_patches * 8 * sizeof(unsigned long long));
-            err = resolve_plan(p);
-            if (err)
-            {
-                cuddh_hip_helmholtz_plan_destroy(p);
-                *out = nullptr;
-            }
-        }
-        return err;
+        // the lane form proper: general geometry -- or the affine n_basis-2 form, whose mass weights are still per element
+        form.lane_form = lane_patches && (!uniform_G || nb == 2);
+        // the lane form with the whole metric block in the register file (PRE, one wavefront per SIMD): measured SLOWER
+        // than the slice-by-slice chain at two wavefronts per SIMD (1024^2, n_basis 4: 434-442 vs 373-376 us), although
+        // the metric stream alone runs at 6.46 TB/s that way -- see the comment at the kernel.  CUDDH_HELM_PRE=1 selects it
+        // for A/B runs; tests keep it correct.
+        form.pair_mass = nb == 3 && !uniform_G && !form.lane_form && knobs.pair_mass;
+        form.prefetch = form.lane_form && knobs.pre;
+        form.stamps = knobs.stamps && (form.lane_form || pe == 16);
+
+        // (fixed stride: helm_lane_kernel and helm_patch_kernel start their index loads without waiting for dof_off)
+        const PatchLayoutInput in{ndof, n_elem, nb, h_I, h_xy, n_faces, h_fI, h_face_elem, pe, /*fused*/ true, /*fixed_stride*/ pe != 16};
+        PatchLayout L;
+        err = build_patch_layout(in, L);
+        return err ? err : build_plan(out, knobs, in, L, ops, form);
     }
 
     int cuddh_hip_operator_plan_create(cuddh_helmholtz_plan **out, int kind, int ndof, int n_elem, int nb, const int *h_I,
@@ -3767,19 +3540,18 @@ extern "C"
         // wavefront (CUDDH_OP_PE=32) have a third more border dofs and slots: 1024^2, n_basis 4, general layout: stiffness
         // 174-187 -> 162-171 us, mass 109 -> 97 us, weighted mass 168 -> 153 us; affine 113 / 87 / 98 -> 98 / 75 / 82 us.
         const Knobs knobs = read_knobs();
+        PlanOperators ops;
+        OperatorInput &op = kind == 0 ? ops.S : ops.M;
+        op = {nq, h_P, h_D, metric};
+        int err = probe_uniform(knobs, op, kind == 0 ? 3 : 1, n_elem);
+        if (err)
+            return err;
         const int pe = op_mfma(kind, nb, nq) ? 16 : (knobs.op_pe32 ? PE : 64); // (measurement knob)
-        int err = kind == 0 ? build_plan(out, knobs, ndof, n_elem, nb, h_I, h_xy, nq, h_P, h_D, metric, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr,
-                                         nullptr, pe)
-                            : build_plan(out, knobs, ndof, n_elem, nb, h_I, h_xy, 0, nullptr, nullptr, nullptr, nq, h_P, metric, 0, nullptr, nullptr, 0, nullptr,
-                                         nullptr, pe);
-        if (!err)
-            err = resolve_plan(*out);
-        if (err && *out)
-        {
-            cuddh_hip_helmholtz_plan_destroy(*out);
-            *out = nullptr;
-        }
-        return err;
+        // (fixed stride: op_patch_kernel with one patch per wavefront; the other two kernels keep the packed lists)
+        const PatchLayoutInput in{ndof, n_elem, nb, h_I, h_xy, 0, nullptr, nullptr, pe, /*fused*/ false, /*fixed_stride*/ pe == 64};
+        PatchLayout L;
+        err = build_patch_layout(in, L);
+        return err ? err : build_plan(out, knobs, in, L, ops, PlanForm{});
     }
 
     int cuddh_hip_operator_plan_apply(const cuddh_helmholtz_plan *p, double c, int accumulate, const double *x, double *y, void *stream)

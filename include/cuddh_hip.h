@@ -184,6 +184,20 @@ int cuddh_hip_helmholtz_plan_create(cuddh_helmholtz_plan **plan, int ndof, int n
                                     int n_faces, const int *h_fI, const int *h_face_elem, int nqF, const double *h_PF,
                                     const double *a_F);
 int cuddh_hip_helmholtz_plan_destroy(cuddh_helmholtz_plan *plan);
+/* The plan's patch layout alone, built on the host from the same HOST arrays (no device is touched): which elements form a
+ * patch of `pe`, the patch-local numbering, colours, border slots and, with fused != 0, the plan-native vector ordering
+ * ("Patch layout").  fixed_stride != 0 pads dof_list / slot_of to max_loc entries per patch.  create returns
+ * 0, 1 (more than 65,535 local dofs in a patch, or a face dof outside its element's patch) or 801 (a patch needs a 32nd colour).
+ * array copies one field to HOST memory and returns its length (count_only != 0: the length only; -1: unknown name):
+ * int: perm dof_off dof_list slot_of own_count patch_nel face_off face_id shared_dof shared_off own_off bpos bslot
+ * global_of_native; uint32: lidx; uint16: face_lidx; uint8: colour face_col; one long long each: pe n_patches dof_stride max_loc
+ * ncol nfcol n_shared n_slots has_native n_owned bstride list_entries owned_entries native_list_entries; three long long:
+ * dest_entries (slot_of entries a write-out reads with no rows, rows of 64, rows of 128 owned dofs skipped). */
+typedef struct cuddh_patch_layout cuddh_patch_layout;
+int cuddh_patch_layout_create(cuddh_patch_layout **layout, int ndof, int n_elem, int nb, const int *h_I, const double *h_xy,
+                              int n_faces, const int *h_fI, const int *h_face_elem, int pe, int fused, int fixed_stride);
+long long cuddh_patch_layout_array(const cuddh_patch_layout *layout, const char *name, void *h_out, int count_only);
+void cuddh_patch_layout_destroy(cuddh_patch_layout *layout);
 /* y = [ S u - w^2 M u - w H v ;  -(S v - w^2 M v + w H u) ],  x = [u;v], y = [Au;Av], each of length ndof */
 int cuddh_hip_helmholtz_apply(const cuddh_helmholtz_plan *plan, double omega, const double *x, double *y, void *stream);
 /* bytes the plan's apply reads+writes per call: actual == 0 the SURVEY 8d formula of the general-geometry layout,

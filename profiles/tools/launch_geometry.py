@@ -3,9 +3,12 @@
   python3 profiles/tools/launch_geometry.py compare DIR_OLD DIR_NEW
 `run` builds one plan of every form (lane form with and without PRE; helm_patch_kernel on 32- and 64-element patches with and
 without MODE=1, affine and with non-temporal loads; helm_mfma_kernel staged and unstaged; op_patch_kernel on 32- and 64-element
-patches; op_mfma_kernel), applies each once -- the fused ones in both vector orderings -- and saves the results to DIR/outputs.npz.
+patches; op_mfma_kernel), applies each once -- the fused ones in both vector orderings -- and saves the results to DIR/outputs.npz
+and, to DIR/plans.txt, the lines it prints: kernel() of every plan and, for the fused ones, the four byte figures (algorithmic, as
+laid out, affine, native ordering; the single operators expose none -- what theirs decides, the NT flag, is part of kernel()).
 `compare` reads the two traces (the rocpd database rocprofv3 leaves under DIR) and prints, dispatch by dispatch, kernel name,
-grid, workgroup and LDS bytes of both builds, whether they are the same, and whether the saved results are (np.array_equal)."""
+grid, workgroup and LDS bytes of both builds, whether they are the same, whether the saved results are (np.array_equal) and
+whether the plan lines are."""
 import csv
 import os
 import sqlite3
@@ -41,7 +44,7 @@ def run(out_dir: Path):
     cd.use_torch_stream()
     mesh = cd.Mesh2D.uniform_rect(13, -1.0, 1.0, 13, -1.0, 1.0)
     faces = mesh.boundary_edges()
-    saved = {}
+    saved, lines = {}, []
 
     def case(nb, knobs):
         for k in KNOBS:
@@ -61,7 +64,7 @@ def run(out_dir: Path):
         A.to_native(x, z)
         A.action_native(z, zy)
         torch.cuda.synchronize()
-        print(f"{label}: {A.kernel()}")
+        lines.append(f"{label}: {A.kernel()} | bytes_per_apply 0-3: {A.bytes_per_apply()} {A.bytes_per_apply(True)} {A.bytes_affine()} {A.bytes_native()}")
         saved[label + " | reference ordering"], saved[label + " | native ordering"] = y.cpu().numpy(), zy.cpu().numpy()
     for label, nb, knobs in OPS:
         fem, a2, x = case(nb, knobs)
@@ -71,9 +74,11 @@ def run(out_dir: Path):
             op.action(x[:n], y)
             op.action(0.5, x[:n], y)  # the accumulating form
             torch.cuda.synchronize()
-            print(f"{label}, {name}: {op.kernel()}")
+            lines.append(f"{label}, {name}: {op.kernel()}")
             saved[f"{label} | {name}"] = y.cpu().numpy()
     np.savez(out_dir / "outputs.npz", **saved)
+    (out_dir / "plans.txt").write_text("\n".join(lines) + "\n")
+    print(*lines, sep="\n")
 
 
 def dispatches(trace_dir: Path):
@@ -103,6 +108,11 @@ def compare(old_dir: Path, new_dir: Path):
     for k in sorted(set(ya.files) | set(yb.files)):
         print(f"result of {k}: {'bitwise equal' if k in equal else 'DIFFERS'}")
     print(f"{len(equal)} of {len(set(ya.files) | set(yb.files))} results: np.array_equal")
+    pa, pb = (old_dir / "plans.txt").read_text().splitlines(), (new_dir / "plans.txt").read_text().splitlines()
+    for i in range(max(len(pa), len(pb))):
+        a, b = (pa[i] if i < len(pa) else "MISSING"), (pb[i] if i < len(pb) else "MISSING")
+        print(f"plan {a} | {'same' if a == b else 'DIFFERS, after: ' + b}")
+    print(f"{sum(a == b for a, b in zip(pa, pb))} of {max(len(pa), len(pb))} plans: same kernel() and byte figures")
 
 
 if __name__ == "__main__":

@@ -17,4 +17,8 @@ t=time.time(); F.rhs(f,b); torch.cuda.synchronize(); print('first rhs (plan + ke
 t=time.time(); F.rhs(f,b); torch.cuda.synchronize(); print('second rhs', time.time()-t)
 fs = cd.FaceSpace(fem, mesh.boundary_edges())
 t=time.time(); A = cd.HelmholtzOperator(1.0, torch.ones(n,dtype=torch.float64,device='cuda'), torch.ones(fs.size(),dtype=torch.float64,device='cuda'), fem, fs); torch.cuda.synchronize(); print('helmholtz operator (3 operators + plan)', time.time()-t)
+x = torch.ones(n, dtype=torch.float64, device='cuda'); y = torch.zeros_like(x)
+for name, op in (('stiffness', cd.StiffnessMatrix(fem)), ('weighted mass', cd.MassMatrix(fem, torch.ones(n, dtype=torch.float64, device='cuda')))):
+    t=time.time(); op.action(x, y); torch.cuda.synchronize(); print(name, 'first action (operator plan + kernel)', time.time()-t)
+    t=time.time(); op.action(x, y); torch.cuda.synchronize(); print(name, 'second action', time.time()-t)
 print('total: mesh + H1Space + DDH constructor + plan', 'see lines above; wall clock since start', time.time()-t0)
