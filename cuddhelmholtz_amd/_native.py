@@ -169,6 +169,7 @@ _sig("cuddh_hip_ddh_plan_set_wh_iters", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_set_wave_priority", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_set_sweep_form", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_sweep_form", ci, vp)
+_sig("cuddh_hip_ddh_plan_set_owner_rule", ci, vp, ci)
 _sig("cuddh_hip_ddh_apply_list_f32", ci, vp, vp, ci, vp, vp, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_apply_list_f64", ci, vp, vp, ci, vp, vp, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_set_vector_layout", ci, vp, vp, ci)
@@ -238,6 +239,7 @@ _sig("cuddh_linear_functional", ci, vp, ci, ci, cd, cd, ci, vp)
 _sig("cuddh_face_linear_functional", ci, vp, ci, ci, cd, cd, ci, vp)
 _sig("cuddh_nodal_values", ci, vp, ci, cd, vp)
 _sig("cuddh_ddh_create", vp, cd, vp, vp, ci, ci, ci, ci)
+_sig("cuddh_ddh_create_block", vp, cd, vp, vp, ci, ci, ci, ci, ci)
 _sig("cuddh_ddh_create_labels", vp, cd, vp, vp, ci, vp, ci, ci)
 _sig("cuddh_ddh_destroy", None, vp)
 _sig("cuddh_ddh_size", ci, vp)
@@ -246,6 +248,7 @@ _sig("cuddh_ddh_set_wh_iters", ci, vp, ci)
 _sig("cuddh_ddh_set_wave_priority", ci, vp, ci)
 _sig("cuddh_ddh_set_sweep_form", ci, vp, ci)
 _sig("cuddh_ddh_sweep_form", ci, vp)
+_sig("cuddh_ddh_set_owner_rule", ci, vp, ci)
 
 
 class MultiGpuResult(C.Structure):

@@ -411,15 +411,25 @@ class DDH:
     kernel selects the local-solve kernel (cuddh_hip_ddh_plan_create): 0 auto, 1 generic, 2 wavefront per subdomain,
     3 / 4 / 5 / 7 fp32 forms (5: dense element matrix on the matrix cores), 6 n_basis 8, 8 = kernel 5 in fp64
     (precision='f64', n_basis 4, uniform metric; never picked by auto).  Requested where it does not apply, 5 to 8 raise on
-    first use.  DDH.from_labels builds the solver on any mesh from element labels (kernels 9 and 10)."""
+    first use.  DDH.from_labels builds the solver on any mesh from element labels (kernels 9 and 10).
+
+    block: elements per subdomain side.  None, 0 or 16 / n_basis is the reference's size; any block >= 1 with
+    n_basis^2 block^2 <= 1024 that divides nx and ny is accepted, anything else raises here.  Off the reference's size the
+    kernels are 1 (any block) and 11 (n_basis 4, block 8, 'f32': one 8x8 block per wavefront; what auto picks there).  Larger
+    subdomains need fewer GMRES iterations and shorter Krylov vectors but more WaveHoltz iterations (set_wh_iters) for the
+    same accuracy.  info()["nel1d"] reports the block in effect."""
 
     _INT_TABLES = ("B", "gI", "sI")
 
-    def __init__(self, omega: float, h_a: np.ndarray, fem: H1Space, nx: int, ny: int, precision: str = "f32", kernel: int = 0):
+    def __init__(self, omega: float, h_a: np.ndarray, fem: H1Space, nx: int, ny: int, precision: str = "f32", kernel: int = 0,
+                 block: int | None = None):
         self.fem = fem
         self.f64 = precision == "f64"
         h_a = np.ascontiguousarray(h_a, dtype=np.float64)
-        self._h = N.handle(lib.cuddh_ddh_create(float(omega), _h(h_a), fem._h, nx, ny, int(self.f64), kernel), "DDH")
+        if block is None:
+            self._h = N.handle(lib.cuddh_ddh_create(float(omega), _h(h_a), fem._h, nx, ny, int(self.f64), kernel), "DDH")
+        else:
+            self._h = N.handle(lib.cuddh_ddh_create_block(float(omega), _h(h_a), fem._h, nx, ny, int(block), int(self.f64), kernel), "DDH")
         self.omega = float(omega)
 
     @classmethod
@@ -489,6 +499,11 @@ class DDH:
         if form < 0:
             N.check_capi(form, "DDH.sweep_form")
         return form
+
+    def set_owner_rule(self, last: bool):
+        """Kernel 11: the last copy of every node that elements share publishes instead of the first (a check: same results).
+        Refused on any other kernel (cuddh_hip_ddh_plan_set_owner_rule)."""
+        N.check_capi(lib.cuddh_ddh_set_owner_rule(self._h, 1 if last else 0), "DDH.set_owner_rule")
 
     def set_wave_priority(self, high: bool):
         """The local solves launched next take issue priority over other resident wavefronts (s_setprio); results unchanged."""

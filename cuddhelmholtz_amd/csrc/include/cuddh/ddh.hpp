@@ -38,6 +38,9 @@ namespace cuddh
         {
         public:
             DDHCore(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel);
+            /// block x block elements per subdomain: 0 or 16 / n_basis is the size of the constructor above; else block >= 1 with
+            /// n_basis^2 block^2 <= 1024 and nx, ny multiples of block (anything else throws before any allocation or launch)
+            DDHCore(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
             /// subdomain s = the elements with label s (HOST, one per element, in [0, n_domains)); any connectivity.
             /// kernel: 0 auto, 9 or 10 (cuddh_hip_ddh_plan_create_general)
             DDHCore(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel);
@@ -58,6 +61,9 @@ namespace cuddh
             /// cannot take throws).  sweep_form() returns the form in effect.
             void set_sweep_form(int form) const;
             int sweep_form() const;
+            /// Kernel 11's owner rule: which copy of a node shared by 2 or 4 elements publishes (false: the first, the default;
+            /// true: the last).  A check that the copies are bitwise equal (cuddh_hip_ddh_plan_set_owner_rule); other kernels throw.
+            void set_last_copy_publishes(bool last) const;
             const EnsembleSpace &ensemble() const { return *efem; }
 
             /// runs the local solves of subdomains [dom_begin, dom_end)
@@ -87,13 +93,15 @@ namespace cuddh
             const HostDeviceArray<Real> &table_sn() const { return _sn; }
             int max_dof() const { return mx_dof; }
             int max_fdof() const { return mx_fdof; }
-            /// elements per block side; 0 for subdomains built from labels
+            /// elements per block side in effect; 0 for subdomains built from labels
             int elems_per_side() const { return nel1d; }
             bool label_built() const { return general; }
 
         private:
             /// everything after the element labels (time grid, slots, renumbering, masses, H, a)
             void setup(const double *h_a, const H1Space &fem, const int *labels);
+            /// the block grid's element labels, then setup()
+            void setup_blocks(const double *h_a, const H1Space &fem, int nx, int ny);
             void solve_impl(const int *d_list, int d0, int d1, const double *x, double *y, bool zero_y, const Real *lambda, Real *update) const;
 
             /// device-side part of the set-up (geometric factors, kernel plan); deferred to first use so
@@ -130,6 +138,10 @@ namespace cuddh
         /// extension: pick the local-solve kernel (0 auto, 1 generic workgroup, 2 wavefront-per-subdomain, 3-7 the fp32 forms of
         /// cuddh_hip_ddh_plan_create; 8 is fp64 only, see DDH64).  A requested kernel that does not apply throws on first use.
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel);
+        /// extension: subdomains of block x block elements (0 or 16 / n_basis: the size of the constructors above).  Needs
+        /// block >= 1, n_basis^2 block^2 <= 1024, nx and ny multiples of block; throws otherwise.  kernel: 0 auto, 1 generic
+        /// workgroup (any block), 11 one 8 x 8 block per wavefront (n_basis 4, block 8, fp32); 2-8 on their own block size only.
+        DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
         /// extension: subdomains of any shape on any Mesh2D, given as element labels (HOST, n_elem of them, in [0, n_domains),
         /// every subdomain non-empty and with at most 256 element nodes).  kernel: 0 auto, 9 one wavefront per subdomain
         /// (n_basis 4, <= 16 elements per subdomain), 10 one workgroup per subdomain.  Invalid labels throw here.
@@ -160,6 +172,8 @@ namespace cuddh
         /// kernel: 0 auto (3 for n_basis 4), 1 generic, 2 wavefront-per-subdomain, 6 n_basis 8, 8 = the dense element matrix on
         /// the fp64 matrix cores (n_basis 4, uniform metric; on request only).  See cuddh_hip_ddh_plan_create.
         DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel = 0);
+        /// subdomains of block x block elements, as DDH(..., kernel, block); kernel 0 or 1 off the default block size
+        DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
         /// subdomains from element labels, as DDH(from_labels, ...)
         DDH64(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel = 0);
 

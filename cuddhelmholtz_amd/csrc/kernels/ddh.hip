@@ -20,7 +20,8 @@
 // z = S w)  ->  publish_dof (y and the trace update).  All six wavefront kernels
 // use load_dof.  ddh_wave8_kernel, ddh_mfma_kernel<Real, ..> and
 // ddh_element_lane_kernel (kernel 5's second sweep form: one element per lane,
-// four subdomains per wavefront) use wh_march and publish_dof too and are a lane
+// four subdomains per wavefront) and ddh_element_lane8_kernel (kernel 11: the same
+// with one 8x8-element subdomain per wavefront) use wh_march and publish_dof too and are a lane
 // map, a sweep and an owner rule (which of the copies of a shared node
 // publishes); the matrix-core and element-lane kernels take wh_march's LEAN
 // forms, which leave out what their element-interior registers never need.
@@ -45,10 +46,11 @@ struct cuddh_ddh_plan
 {
     cuddh_ddh_desc d;
     int is_f64;
-    int kernel; // which sweep:  1 ddh_block_kernel;  2 / 3 / 4 ddh_wave_kernel<Real, 0 / 1 / 2> (plain; hand-folded DPP FMAs, fp32;
+    int kernel; // which sweep:  1 ddh_block_kernel (up to 1024 element nodes);  2 / 3 / 4 ddh_wave_kernel<Real, 0 / 1 / 2> (plain; hand-folded DPP FMAs, fp32;
                 // 3 + MFMA for the in-lane contractions);  5 / 8 ddh_mfma_kernel<float / double> (dense element matrix on the matrix
                 // cores, uniform geometry);  6 / 7 ddh_wave8_kernel (nb == 8; 7 separable, fp32);  9 ddh_general_wave_kernel
-                // (nb == 4, <= 16 elements, CSR lists);  10 ddh_block_kernel with CSR lists
+                // (nb == 4, <= 16 elements, CSR lists);  10 ddh_block_kernel with CSR lists;  11 ddh_element_lane8_kernel (nb == 4,
+                // 8x8 elements, fp32: one element per lane, one subdomain per wavefront)
     int nodes;  // nb*nb*nel1d*nel1d (general plans: nb*nb*mx_elems)
     int wh_iters = 5; // WaveHoltz iterations per local solve (source/DDH.cpp:136); WH_ITERS_REFERENCE
     const int *gI_override = nullptr; // cuddh_hip_ddh_plan_set_vector_layout: x and y in another numbering than d.gI
@@ -56,7 +58,8 @@ struct cuddh_ddh_plan
     float *Aop = nullptr; // kernel 5: element stiffness matrix as MFMA A operands, [4 k-steps][64 lanes]
     double *Aop64 = nullptr; // kernel 8: the same in fp64, rows in the f64 MFMA's output order (build_dense_element_matrix)
     float *Sep = nullptr; // kernel 7: [Ax | Ay | beta | gamma] of the separable nb = 8 sweep
-    float *Sep4 = nullptr; // kernel 5, element-lane form: [Bx | By | Dg | W | 1 / W] (build_element_lane_tables); null: does not qualify
+    float *Sep4 = nullptr; // kernel 5, element-lane form, and kernel 11: [Bx | By | Dg | W | 1 / W] (build_element_lane_tables); null: does not qualify
+    int last_copy = 0; // kernel 11: the last copy of a shared node publishes, not the first (cuddh_hip_ddh_plan_set_owner_rule)
     int sweep_form = 0; // kernel 5: 0 auto, 1 matrix form, 2 element-lane form, 3 the same with the other owner rule (cuddh_hip_ddh_plan_set_sweep_form)
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
@@ -1268,6 +1271,28 @@ namespace
 #undef CUDDH_EL_ASSEMBLE
     constexpr unsigned ELEMENT_INTERIOR_REGISTERS = (1u << 5) | (1u << 6) | (1u << 9) | (1u << 10);
 
+    // the in-lane part of the element-lane sweep: z' = Dg w + Bx-terms + By-terms of the lane's own element, before assembly
+    __device__ inline void element_lane_products(const float (&w)[16], float (&z)[16], const float (&Bx)[16], const float (&By)[16],
+                                                 const float (&Dg)[16])
+    {
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+            {
+                float t = Dg[k + 4 * l] * w[k + 4 * l];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                {
+                    if (j != k)
+                        t += Bx[k + 4 * j] * w[j + 4 * l];
+                    if (j != l)
+                        t += By[l + 4 * j] * w[k + 4 * j];
+                }
+                z[k + 4 * l] = t;
+            }
+    }
+
     template <bool FORCED, bool HOLD, bool LAST_COPY>
     __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
                                                                      const float *__restrict__ cs, const float *__restrict__ sn)
@@ -1315,22 +1340,7 @@ namespace
 
         auto sweep = [&](const float(&w)[16], float(&z)[16])
         {
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                {
-                    float t = Dg[k + 4 * l] * w[k + 4 * l];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                    {
-                        if (j != k)
-                            t += Bx[k + 4 * j] * w[j + 4 * l];
-                        if (j != l)
-                            t += By[l + 4 * j] * w[k + 4 * j];
-                    }
-                    z[k + 4 * l] = t;
-                }
+            element_lane_products(w, z, Bx, By, Dg);
             // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa)
             float hi[4] = {z[3], z[7], z[11], z[15]}, lo[4] = {z[0], z[4], z[8], z[12]};
             element_assemble_xi_asm(hi, lo, mR, mL);
@@ -1373,17 +1383,114 @@ namespace
         }
     }
 
-    // kernels 5 and 8 leave the boundary terms out on the element-interior nodes (register 0): is none of them a trace dof
+    // ---------------------------------------------------------------- kernel 11 (NB = 4, 8x8 elements, rectangles): one subdomain per wavefront
+    // The element-lane form with a subdomain of 64 elements: lane = element ex + 8 ey, register n = k + 4 l = node (k, l); the
+    // tables, the in-lane products, the folded weight W and wh_march's LEAN rules are those of ddh_element_lane_kernel (the
+    // element is the same rectangle whatever the subdomain).  Only the assembly differs.  xi neighbours are lane +- 1: a
+    // 16-lane DPP row holds two eta-rows of elements, so the row shift by 1 also carries ex == 7 into the next eta-row's
+    // ex == 0 (and back), which the masks mR / mL multiply by 0; past the ends of a DPP row bound_ctrl reads 0.  eta
+    // neighbours are lane +- 8, half of them in another DPP row: ds_bpermute_b32 (the __shfl of ddh_mfma_kernel), 8 per sweep
+    // on the LDS pipe, no LDS storage.  xi first, eta on the xi-assembled values, masks 0 / 1: the 2 or 4 copies of a shared
+    // node form the same commutative sums and stay bitwise equal.  Four wavefronts per workgroup, no barriers.  A wavefront
+    // holds one subdomain, so a launch of any length needs no padding rows and a subdomain's result does not depend on
+    // which others the launch holds.
+    // Compiled for three wavefronts per SIMD in the action form and two in the form with x, like the 4x4 form.
+    template <bool FORCED, bool HOLD, bool LAST_COPY>
+    __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane8_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
+                                                                                   const float *__restrict__ cs, const float *__restrict__ sn)
+    {
+        if (A.dom_begin + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6) >= A.dom_end)
+            return; // wave-uniform: the kernel has no barriers
+        if constexpr (HOLD)
+            __builtin_amdgcn_s_setprio(3);
+        // where this lane works: subdomain s, its trace dofs, the dofs of its element's nodes
+        auto locate = [&](int tid, int &s, int &fdof, const int *&sI)
+        {
+            s = domain_at(A, A.dom_begin + (int)blockIdx.x * 4 + (tid >> 6));
+            fdof = A.s_fdof[s];
+            sI = A.sI + 1024 * (size_t)s + 16 * (tid & 63);
+        };
+        int s, fdof;
+        const int *sI;
+        locate(threadIdx.x, s, fdof, sI);
+        const int lane = threadIdx.x & 63, ex = lane & 7, ey = lane >> 3;
+
+        float invm[16], Hi[16], F[16], Gf[16], u[16], v[16];
+#pragma unroll
+        for (int n = 0; n < 16; ++n)
+        {
+            load_dof(A, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
+            const float W = Sep4[48 + n], rW = Sep4[64 + n];
+            invm[n] *= W;
+            Hi[n] *= rW;
+            F[n] *= rW;
+            Gf[n] *= rW;
+        }
+        float Bx[16], By[16], Dg[16]; // wave-uniform: scalar registers for the whole time loop
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+        {
+            Bx[i] = Sep4[i];      // Bx(k, j) at k + 4 j
+            By[i] = Sep4[16 + i]; // By(l, j) at l + 4 j
+            Dg[i] = Sep4[32 + i]; // Dg(k, l) at k + 4 l
+        }
+        const float mR = ex < 7 ? 1.0f : 0.0f, mL = ex > 0 ? 1.0f : 0.0f, mU = ey < 7 ? 1.0f : 0.0f, mD = ey > 0 ? 1.0f : 0.0f;
+        const int above = (lane + 8) & 63, below = (lane + 56) & 63; // a lane without that neighbour reads a lane it masks out
+
+        auto sweep = [&](const float(&w)[16], float(&z)[16])
+        {
+            element_lane_products(w, z, Bx, By, Dg);
+            // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa)
+            float hi[4] = {z[3], z[7], z[11], z[15]}, lo[4] = {z[0], z[4], z[8], z[12]};
+            element_assemble_xi_asm(hi, lo, mR, mL);
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+            {
+                z[3 + 4 * l] = hi[l];
+                z[0 + 4 * l] = lo[l];
+            }
+            // eta neighbours, on the xi-assembled values: my l == 3 row meets the l == 0 row of lane + 8 (and vice versa)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+            {
+                const float up = z[k + 12], dn = z[k];
+                const float from_above = __shfl(dn, above, 64), from_below = __shfl(up, below, 64);
+                z[k + 12] = up + mU * from_above;
+                z[k] = dn + mD * from_below;
+            }
+        };
+        wh_march<FORCED ? 2 : 1, ELEMENT_INTERIOR_REGISTERS>(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+
+        // located a second time from a lane index the compiler cannot connect with the first, as in ddh_element_lane_kernel
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        locate(tid, s, fdof, sI);
+#pragma unroll
+        for (int n = 0; n < 16; ++n)
+        {
+            // every shared node is held by 2 or 4 (lane, register) pairs with identical values: the copy with
+            // the smallest element-node index writes (with LAST_COPY the one with the largest)
+            const int k = n & 3, l = n >> 2;
+            const bool first = !(k == 0 && (tid & 7) > 0) && !(l == 0 && (tid & 56) > 0);
+            const bool last = !(k == 3 && (tid & 7) < 7) && !(l == 3 && (tid & 56) < 56);
+            const bool owner = LAST_COPY ? last : first;
+            if (owner)
+                publish_dof(A, s, sI[n], fdof, u[n], v[n], false);
+        }
+    }
+
+    // kernels 5, 8 and 11 leave the boundary terms out on the element-interior nodes (register 0): is none of them a trace dof
     // (sI >= s_fdof) in any subdomain?  True for every plan built from blocks of elements, where trace dofs lie on the
     // subdomain's boundary; a descriptor from elsewhere is checked, not trusted.
-    __global__ void __launch_bounds__(256) ddh_interior_check_kernel(int n_domains, const int *__restrict__ s_fdof, const int *__restrict__ sI,
-                                                                     int *__restrict__ bad)
+    // n_elems (16 or 64) elements of 16 nodes per subdomain, `stride` = 16 n_elems entries of sI per subdomain.
+    __global__ void __launch_bounds__(256) ddh_interior_check_kernel(int n_domains, int n_elems, int stride, const int *__restrict__ s_fdof,
+                                                                     const int *__restrict__ sI, int *__restrict__ bad)
     {
         const int s = blockIdx.x, tid = threadIdx.x;
-        if (s >= n_domains || tid >= 64)
+        if (s >= n_domains || tid >= 4 * n_elems)
             return;
-        const int node = node_of(tid >> 4, 0) + 16 * (tid & 15);
-        if (sI[node + 256 * (size_t)s] < s_fdof[s])
+        const int node = node_of(tid / n_elems, 0) + 16 * (tid % n_elems);
+        if (sI[node + stride * (size_t)s] < s_fdof[s])
             atomicExch(bad, 1);
     }
 
@@ -1402,33 +1509,38 @@ namespace
         }
     }
 
-    // structure check for the wave kernels (NB nodes per direction, NEL x NEL elements, NB*NEL == 16): the expected
-    // number of dofs, and xi/eta neighbours share exactly the expected nodes
+    // structure check for the wave kernels (NB nodes per direction, NEL x NEL elements in the order ex + NEL ey, at most 1024
+    // element nodes): the expected number of dofs, and xi/eta neighbours share exactly the expected nodes
     template <int NB, int NEL>
     __global__ void __launch_bounds__(256) ddh_wave_check_kernel(int n_domains, const int *__restrict__ s_dof, const int *__restrict__ sI,
                                                                  int *__restrict__ bad)
     {
-        constexpr int SIDE = NB * NEL - (NEL - 1), NDOF = SIDE * SIDE, NN = NB * NB;
-        const int s = blockIdx.x, tid = threadIdx.x;
+        constexpr int SIDE = NB * NEL - (NEL - 1), NDOF = SIDE * SIDE, NN = NB * NB, NODES = NN * NEL * NEL;
+        const int s = blockIdx.x;
         if (s >= n_domains)
             return;
-        const int k = tid % NB, l = (tid / NB) % NB, el = tid / NN, ex = el % NEL, ey = el / NEL;
-        const int *I = sI + 256 * (size_t)s;
-        bool ok = I[tid] >= 0 && I[tid] < NDOF;
-        if (tid == 0)
-            ok = ok && s_dof[s] == NDOF;
-        if (k == NB - 1 && ex < NEL - 1)
-            ok = ok && I[tid] == I[0 + NB * (l + NB * (el + 1))];
-        if (l == NB - 1 && ey < NEL - 1)
-            ok = ok && I[tid] == I[k + NB * (0 + NB * (el + NEL))];
+        const int *I = sI + NODES * (size_t)s;
+        bool ok = true;
+        for (int node = threadIdx.x; node < NODES; node += 256)
+        {
+            const int k = node % NB, l = (node / NB) % NB, el = node / NN, ex = el % NEL, ey = el / NEL;
+            ok = ok && I[node] >= 0 && I[node] < NDOF;
+            if (node == 0)
+                ok = ok && s_dof[s] == NDOF;
+            if (k == NB - 1 && ex < NEL - 1)
+                ok = ok && I[node] == I[0 + NB * (l + NB * (el + 1))];
+            if (l == NB - 1 && ey < NEL - 1)
+                ok = ok && I[node] == I[k + NB * (0 + NB * (el + NEL))];
+        }
         if (!ok)
             atomicExch(bad, 1);
     }
 
     // ---------------------------------------------------------------- workgroup-per-subdomain kernel (generic)
     // CSR = true is kernel 10: the contributor lists come from the plan (any valence) instead of being built with atomics.
-    template <typename Real, int NB, bool CSR = false>
-    __global__ void __launch_bounds__(256) ddh_block_kernel(DdhArgs<Real> A, const Real *__restrict__ Dmat, const Real *__restrict__ filt,
+    // MAXT: the launch bound, 256 or, for subdomains of 257 to 1024 element nodes, 1024 (at most 128 vector registers then).
+    template <typename Real, int NB, bool CSR = false, int MAXT = 256>
+    __global__ void __launch_bounds__(MAXT) ddh_block_kernel(DdhArgs<Real> A, const Real *__restrict__ Dmat, const Real *__restrict__ filt,
                                                            const Real *__restrict__ cs, const Real *__restrict__ sn)
     {
         raise_priority(A.prio);
@@ -1687,6 +1799,25 @@ namespace
         const int T = A.nodes;
         const size_t lds = (size_t)T * (4 * sizeof(Real) + 5 * sizeof(int));
         auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_local), dim3(T), lds, st, A, D, fl, cs, sn); };
+        if (T > 1024)
+            return false;
+        if (T > 256) // 52 KB of LDS in fp64 at T = 1024: within the 64 KB a workgroup gets without asking
+        {
+            if constexpr (!CSR)
+                switch (nb)
+                {
+                case 2: launch(ddh_block_kernel<Real, 2, false, 1024>); return true;
+                case 3: launch(ddh_block_kernel<Real, 3, false, 1024>); return true;
+                case 4: launch(ddh_block_kernel<Real, 4, false, 1024>); return true;
+                case 5: launch(ddh_block_kernel<Real, 5, false, 1024>); return true;
+                case 6: launch(ddh_block_kernel<Real, 6, false, 1024>); return true;
+                case 7: launch(ddh_block_kernel<Real, 7, false, 1024>); return true;
+                case 8: launch(ddh_block_kernel<Real, 8, false, 1024>); return true;
+                case 9: launch(ddh_block_kernel<Real, 9, false, 1024>); return true;
+                case 10: launch(ddh_block_kernel<Real, 10, false, 1024>); return true;
+                }
+            return false;
+        }
         switch (nb)
         {
         case 2: launch(ddh_block_kernel<Real, 2, CSR>); break;
@@ -1726,9 +1857,9 @@ namespace
     // Does every element of every subdomain have the metric tensor of (subdomain 0, element 0)?  0 if so, -1 if not, > 0 on a
     // HIP error.
     template <typename Real>
-    int check_uniform_geometry(const cuddh_ddh_desc &d, int nodes_per_elem)
+    int check_uniform_geometry(const cuddh_ddh_desc &d, int nodes_per_elem, int nodes = 256)
     {
-        const long long n_nodes = 256LL * d.n_domains;
+        const long long n_nodes = static_cast<long long>(nodes) * d.n_domains;
         int bad = 1;
         const int e = device_flag_check(&bad, [&](int *flag)
                                         { hipLaunchKernelGGL(ddh_uniform_check_kernel<Real>, dim3(stream_grid(n_nodes, 256)), dim3(256), 0, nullptr,
@@ -1749,7 +1880,7 @@ namespace
             int bad = 1;
             const int e = device_flag_check(&bad, [&](int *flag)
                                             { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(d.n_domains), dim3(256), 0, nullptr, d.n_domains,
-                                                                 d.s_fdof, d.sI, flag); });
+                                                                 16, 256, d.s_fdof, d.sI, flag); });
             if (e || bad)
                 return e ? e : -1;
         }
@@ -1979,6 +2110,27 @@ namespace
         }
     }
 
+    // kernel 11: one subdomain per wavefront, four wavefronts per workgroup
+    template <bool LAST_COPY>
+    void launch_element_lane8(const DdhArgs<float> &A, const float *Sep4, dim3 grid, dim3 block, hipStream_t st, const float *fl,
+                              const float *cs, const float *sn)
+    {
+        if (A.x)
+        {
+            if (A.prio)
+                hipLaunchKernelGGL((ddh_element_lane8_kernel<true, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+            else
+                hipLaunchKernelGGL((ddh_element_lane8_kernel<true, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+        }
+        else
+        {
+            if (A.prio)
+                hipLaunchKernelGGL((ddh_element_lane8_kernel<false, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+            else
+                hipLaunchKernelGGL((ddh_element_lane8_kernel<false, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+        }
+    }
+
     // kernels 5 and 8: the instantiation for this launch's two fixed properties (ddh_mfma_kernel)
     template <typename Real>
     void launch_mfma(const DdhArgs<Real> &A, const void *Aop, dim3 grid, dim3 block, hipStream_t st, const Real *fl, const Real *cs,
@@ -2104,6 +2256,19 @@ namespace
             break;
         }
         case 9: hipLaunchKernelGGL((ddh_general_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn); break;
+        case 11:
+            if constexpr (f32)
+            {
+                if (!plan->Sep4) // plan_create ties kernel 11 to fp32 and its tables
+                    return static_cast<int>(hipErrorInvalidValue);
+                if (plan->last_copy)
+                    launch_element_lane8<true>(A, plan->Sep4, grid, block, st, fl, cs, sn);
+                else
+                    launch_element_lane8<false>(A, plan->Sep4, grid, block, st, fl, cs, sn);
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
         default: return static_cast<int>(hipErrorInvalidValue);
         }
         return launch_status();
@@ -2153,10 +2318,10 @@ extern "C"
     int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **out, const cuddh_ddh_desc *desc, int is_f64, int kernel)
     {
         *out = nullptr;
-        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || kernel < 0 || kernel > 8)
+        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || desc->nel1d > 16 || kernel < 0 || (kernel > 8 && kernel != 11))
             return static_cast<int>(hipErrorInvalidValue);
         const int nodes = desc->nb * desc->nb * desc->nel1d * desc->nel1d;
-        if (nodes > 256)
+        if (nodes > 1024) // one thread per element node in kernel 1
             return static_cast<int>(hipErrorInvalidValue);
 
         cuddh_ddh_plan *p = new cuddh_ddh_plan;
@@ -2167,7 +2332,8 @@ extern "C"
 
         const bool wave_shape = (desc->nb == 4 && desc->nel1d == 4);
         const bool wave8_shape = (desc->nb == 8 && desc->nel1d == 2);
-        if ((kernel >= 2 && kernel <= 5 && !wave_shape) || ((kernel == 6 || kernel == 7) && !wave8_shape) || (kernel == 7 && is_f64) ||
+        const bool lane8_shape = (desc->nb == 4 && desc->nel1d == 8);
+        if ((kernel == 11 && (!lane8_shape || is_f64)) || (kernel >= 2 && kernel <= 5 && !wave_shape) || ((kernel == 6 || kernel == 7) && !wave8_shape) || (kernel == 7 && is_f64) ||
             (kernel == 8 && (!wave_shape || !is_f64)))
         {
             delete p;
@@ -2200,6 +2366,34 @@ extern "C"
                     delete p;
                     return err7 > 0 ? err7 : static_cast<int>(hipErrorInvalidValue);
                 }
+            }
+        }
+        // kernel 11 (8x8 elements, one per lane) needs fp32, the element order ex + 8 ey, no trace dof on an element-interior
+        // node and the rectangles of the element-lane form; a plan that fails one of these runs kernel 1
+        if (lane8_shape && !is_f64 && kernel != 1)
+        {
+            int bad = 1;
+            int e = run_structure_check<4, 8>(desc, &bad);
+            if (!e && !bad)
+                e = device_flag_check(&bad, [&](int *flag)
+                                      { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(desc->n_domains), dim3(256), 0, nullptr,
+                                                           desc->n_domains, 64, 1024, desc->s_fdof, desc->sI, flag); });
+            int qualifies = -1; // 0 yes, -1 no, > 0 a HIP error
+            if (!e && !bad)
+                qualifies = check_uniform_geometry<float>(*desc, 16, 1024);
+            if (!e && qualifies == 0)
+                qualifies = build_element_lane_tables(p);
+            if (e || qualifies > 0)
+            {
+                cuddh_hip_ddh_plan_destroy(p);
+                return e ? e : qualifies;
+            }
+            if (qualifies == 0)
+                p->kernel = 11;
+            else if (kernel == 11)
+            {
+                cuddh_hip_ddh_plan_destroy(p);
+                return static_cast<int>(hipErrorInvalidValue);
             }
         }
         if (wave_shape && kernel != 1)
@@ -2388,6 +2582,14 @@ extern "C"
     }
 
     int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan) { return plan ? effective_sweep_form(plan) : 0; }
+
+    int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last)
+    {
+        if (!plan || plan->kernel != 11)
+            return static_cast<int>(hipErrorInvalidValue);
+        plan->last_copy = last ? 1 : 0;
+        return 0;
+    }
 
     int cuddh_hip_ddh_apply_f32(const cuddh_ddh_plan *plan, int dom_begin, int dom_end, const double *x, double *y, int zero_y,
                                 const float *lambda, float *update, void *stream)

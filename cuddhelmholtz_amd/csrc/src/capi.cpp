@@ -607,6 +607,27 @@ extern "C"
             return h;
         });
     }
+    void *cuddh_ddh_create_block(double omega, const double *h_a, void *fem, int nx, int ny, int block, int f64, int kernel)
+    {
+        return guarded_new<DdhHandle>([&]
+        {
+            auto h = new DdhHandle;
+            const H1Space &f = *static_cast<H1Space *>(fem);
+            try
+            {
+                if (f64)
+                    h->f64.reset(new DDH64(omega, h_a, f, nx, ny, kernel, block));
+                else
+                    h->f32.reset(new DDH(omega, h_a, f, nx, ny, kernel, block));
+            }
+            catch (...)
+            {
+                delete h;
+                throw;
+            }
+            return h;
+        });
+    }
     void *cuddh_ddh_create_labels(double omega, const double *h_a, void *fem, int n_domains, const int *h_labels, int f64, int kernel)
     {
         return guarded_new<DdhHandle>([&]
@@ -795,6 +816,17 @@ extern "C"
                 h->f64->internals().set_sweep_form(form);
             else
                 h->f32->internals().set_sweep_form(form);
+        });
+    }
+    int cuddh_ddh_set_owner_rule(void *d, int last)
+    {
+        return guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            if (h->is64())
+                h->f64->internals().set_last_copy_publishes(last != 0);
+            else
+                h->f32->internals().set_last_copy_publishes(last != 0);
         });
     }
     int cuddh_ddh_sweep_form(void *d)

@@ -48,6 +48,38 @@ namespace cuddh
             nel1d = std::max(1, 16 / nb);
             if (nx % nel1d != 0 || ny % nel1d != 0)
                 cuddh_error("DDH error: nx and ny must be multiples of 16 / n_basis.");
+            setup_blocks(h_a, fem, nx, ny);
+            requested_kernel = kernel;
+        }
+
+        template <typename Real>
+        DDHCore<Real>::DDHCore(double omega_, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block)
+            : g_ndof(fem.size()), g_elem(fem.mesh().n_elem()), n_basis(fem.basis().size()), omega(omega_), fem_mesh(&fem.mesh()),
+              fem_basis(&fem.basis())
+        {
+            // everything is checked here, on the host, before anything is allocated or launched
+            const int nb = n_basis;
+            if (nb < 2 || nb > 16)
+                cuddh_error("DDH error: n_basis must be in [2, 16].");
+            if (block < 0)
+                cuddh_error(("DDH error: block = " + std::to_string(block) + "; the elements per subdomain side must be at least 1 (0: 16 / n_basis).").c_str());
+            nel1d = block == 0 ? std::max(1, 16 / nb) : block;
+            if (static_cast<long long>(nb) * nb * nel1d * nel1d > 1024)
+                cuddh_error(("DDH error: block = " + std::to_string(nel1d) + " at n_basis " + std::to_string(nb) + " gives " +
+                             std::to_string(static_cast<long long>(nb) * nb * nel1d * nel1d) +
+                             " element nodes per subdomain (n_basis^2 * block^2); at most 1024 fit one local solve.")
+                                .c_str());
+            if (nx % nel1d != 0 || ny % nel1d != 0)
+                cuddh_error(("DDH error: nx = " + std::to_string(nx) + " and ny = " + std::to_string(ny) + " must be multiples of block = " +
+                             std::to_string(nel1d) + ".")
+                                .c_str());
+            setup_blocks(h_a, fem, nx, ny);
+            requested_kernel = kernel;
+        }
+
+        template <typename Real>
+        void DDHCore<Real>::setup_blocks(const double *h_a, const H1Space &fem, int nx, int ny)
+        {
             if (nx * ny != g_elem)
                 cuddh_error("DDH error: nx * ny does not match the mesh.");
 
@@ -61,7 +93,6 @@ namespace cuddh
                         labels[i + static_cast<std::size_t>(nx) * j] = (i / nel1d) + ndx * (j / nel1d);
             }, 8);
             setup(h_a, fem, labels.data());
-            requested_kernel = kernel;
         }
 
         template <typename Real>
@@ -441,6 +472,13 @@ namespace cuddh
         }
 
         template <typename Real>
+        void DDHCore<Real>::set_last_copy_publishes(bool last) const
+        {
+            ensure_plan();
+            check_hip(cuddh_hip_ddh_plan_set_owner_rule(plan, last ? 1 : 0), "DDH owner rule");
+        }
+
+        template <typename Real>
         void DDHCore<Real>::set_wave_priority(bool high) const
         {
             ensure_plan();
@@ -567,6 +605,11 @@ namespace cuddh
     {
     }
 
+    DDH::DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block)
+        : core(omega, h_a, fem, nx, ny, kernel, block)
+    {
+    }
+
     DDH::DDH(from_labels_t tag, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel)
         : core(tag, omega, h_a, fem, n_domains, labels, kernel)
     {
@@ -599,6 +642,11 @@ namespace cuddh
 
     DDH64::DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel)
         : core(omega, h_a, fem, nx, ny, kernel)
+    {
+    }
+
+    DDH64::DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block)
+        : core(omega, h_a, fem, nx, ny, kernel, block)
     {
     }
 

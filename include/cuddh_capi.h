@@ -116,6 +116,12 @@ int cuddh_nodal_values(void *fem, int integrand, double param, double *out);
 /* h_a HOST nodal coefficient; f64 != 0 selects the fp64 parity variant (double traces);
  * kernel: 0 auto, 1 workgroup-per-subdomain, 2 wavefront-per-subdomain, 3 wavefront with DPP-folded FMAs */
 void *cuddh_ddh_create(double omega, const double *h_a, void *fem, int nx, int ny, int f64, int kernel);
+/* the same with subdomains of block x block elements: 0 or 16 / n_basis is cuddh_ddh_create's size; else block >= 1,
+ * n_basis^2 block^2 <= 1024, nx and ny multiples of block (checked before anything is allocated; NULL + cuddh_last_error
+ * otherwise).  kernel: 0 auto, 1 workgroup-per-subdomain (any block), 11 one 8x8 block per wavefront (n_basis 4, block 8,
+ * f64 == 0; what auto picks there); cuddh_ddh_create's other kernels on its block size only.  cuddh_ddh_info reports
+ * nel1d = the block in effect. */
+void *cuddh_ddh_create_block(double omega, const double *h_a, void *fem, int nx, int ny, int block, int f64, int kernel);
 /* subdomains from element labels on any mesh: h_labels HOST (n_elem), label of every element in [0, n_domains), no empty
  * subdomain, at most 256 element nodes per subdomain (checked before anything is allocated; NULL + cuddh_last_error otherwise).
  * kernel: 0 auto, 9 one wavefront per subdomain (n_basis 4, <= 16 elements), 10 one workgroup per subdomain
@@ -171,6 +177,9 @@ int cuddh_ddh_set_wave_priority(void *ddh, int high);
  * the getter returns the form in effect (1, 2 or 3; 0 for a plan that is not kernel 5; -1 on error) */
 int cuddh_ddh_set_sweep_form(void *ddh, int form);
 int cuddh_ddh_sweep_form(void *ddh);
+/* kernel 11's owner rule: last != 0 lets the last copy of every shared node publish instead of the first; same results, a
+ * check (cuddh_hip_ddh_plan_set_owner_rule; an error on a plan that is not kernel 11) */
+int cuddh_ddh_set_owner_rule(void *ddh, int last);
 /* traces are float for f64 == 0 and double otherwise */
 int cuddh_ddh_rhs(void *ddh, const double *f, void *b);
 int cuddh_ddh_postprocess(void *ddh, const void *lambda, const double *f, double *u);

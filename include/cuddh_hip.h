@@ -303,7 +303,14 @@ typedef struct cuddh_ddh_plan cuddh_ddh_plan;
  *             (plan_create verifies the geometry; what auto picks for nb == 8 when it applies),
  *         8 = 5 in fp64 (four v_mfma_f64_16x16x4_f64 per sweep, element matrix formed and kept in double; is_f64, nb == 4
  *             and nel1d == 4 only, same two conditions as 5, which plan_create verifies on the device;
- *             on request only: auto keeps fp64 on 3; hipErrorInvalidValue where it does not apply, like 5). */
+ *             on request only: auto keeps fp64 on 3; hipErrorInvalidValue where it does not apply, like 5),
+ *         11 = one 8x8-element subdomain per wavefront (nb == 4, nel1d == 8, fp32): kernel 5's element-lane form with one
+ *             element per lane, lane = ex + 8 ey; xi neighbours through DPP row shifts, eta neighbours through ds_bpermute.
+ *             Needs rectangles like the element-lane form, the element order ex + 8 ey inside every subdomain and no trace
+ *             dof on an element-interior node, which plan_create verifies on the device; what auto picks for that shape
+ *             when it applies, otherwise 1.
+ * Subdomains hold nb^2 nel1d^2 <= 1024 element nodes.  Kernel 1 runs every such shape (one thread per element node);
+ * kernels 2-8 and 11 are refused with hipErrorInvalidValue on any shape but their own. */
 int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int is_f64, int kernel);
 /* Plan for subdomains of ANY element connectivity (subdomains given by element labels; desc->nel1d is ignored and
  * should be 0).  mx_elems: elements per subdomain at most, the third extent of desc->sI and the stride of desc->G;
@@ -320,7 +327,7 @@ int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc,
  * plans unchanged. */
 int cuddh_hip_ddh_plan_create_general(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int mx_elems, int is_f64, int kernel);
 int cuddh_hip_ddh_plan_destroy(cuddh_ddh_plan *plan);
-/* which kernel the plan resolved to (1..8) */
+/* which kernel the plan resolved to (1..11) */
 int cuddh_hip_ddh_plan_kernel(const cuddh_ddh_plan *plan);
 /* Numbering of the forcing x and the solution y of the NEXT apply calls: d_gI (mx_dof, n_domains) DEVICE replaces desc.gI and
  * g_ndof replaces desc.g_ndof for x and y (NULL restores the descriptor's).  With the identity numbering
@@ -351,6 +358,11 @@ int cuddh_hip_ddh_plan_set_wh_iters(cuddh_ddh_plan *plan, int wh_iters);
  * every plan.  cuddh_hip_ddh_plan_sweep_form returns the form in effect (1, 2 or 3), 0 for a plan that is not kernel 5. */
 int cuddh_hip_ddh_plan_set_sweep_form(cuddh_ddh_plan *plan, int form);
 int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan);
+/* Kernel 11's owner rule, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
+ * smallest element-node index publishes (last == 0, the default) or the one with the largest (last != 0).  The copies are
+ * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with
+ * hipErrorInvalidValue on a plan that is not kernel 11. */
+int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last);
 
 /* source/DDH.cpp:111-321 (ddh_action + stiffness).  x: forcing [F;G] (2*g_ndof
  * doubles) or NULL; y: solution output [u;v] (2*g_ndof doubles, zero-filled by

@@ -19,7 +19,10 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 from cuddhelmholtz_amd import build as B  # noqa: E402
 
 # kernels whose symbol changed, per file: demangled name (without the argument list) in OLD -> in NEW
-RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, false>", "ddh_mfma_kernel<double>": "ddh_mfma_kernel<double, false, false>"}}
+RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, false>", "ddh_mfma_kernel<double>": "ddh_mfma_kernel<double, false, false>",
+                       # ddh_block_kernel got its launch bound as a fourth template argument; 256 is the bound it had
+                       **{f"ddh_block_kernel<{real}, {nb}, {csr}>": f"ddh_block_kernel<{real}, {nb}, {csr}, 256>"
+                          for real in ("float", "double") for nb in range(2, 11) for csr in ("false", "true")}}}
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
