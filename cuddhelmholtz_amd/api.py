@@ -417,27 +417,61 @@ class DDH:
     n_basis^2 block^2 <= 1024 that divides nx and ny is accepted, anything else raises here.  Off the reference's size the
     kernels are 1 (any block) and 11 (n_basis 4, block 8, 'f32': one 8x8 block per wavefront; what auto picks there).  Larger
     subdomains need fewer GMRES iterations and shorter Krylov vectors but more WaveHoltz iterations (set_wh_iters) for the
-    same accuracy.  info()["nel1d"] reports the block in effect."""
+    same accuracy.  info()["nel1d"] reports the block in effect.
+
+    time_step: where the local solves take their time step from.  "mesh" (the default, the reference's): one grid from the
+    mesh width alone, dt = 0.1 h / n_basis^2, whatever the coefficient; where a < 1 (wave speed 1 / a > 1) the explicit
+    stepping then runs past its usable range and the local solves blow up.  "coefficient": subdomain s marches
+    r_s times as many steps per period, r_s = max(1, ceil(1 / min a over its dofs)); a == 1 everywhere is "mesh" bit for bit.
+    An integer array (one ratio >= 1 per subdomain): those ratios.  time_ratios() returns r; info()["nt"], info()["dt"] and
+    table("filter" | "cs" | "sn") stay the base grid's, table("filter@5") etc. are those of the grid of 5 x the mesh grid's steps.
+    A bad array, a non-finite or non-positive a under "coefficient", and a ratio above 256 raise ValueError here."""
 
     _INT_TABLES = ("B", "gI", "sI")
 
     def __init__(self, omega: float, h_a: np.ndarray, fem: H1Space, nx: int, ny: int, precision: str = "f32", kernel: int = 0,
-                 block: int | None = None):
+                 block: int | None = None, time_step="mesh"):
         self.fem = fem
         self.f64 = precision == "f64"
         h_a = np.ascontiguousarray(h_a, dtype=np.float64)
-        if block is None:
-            self._h = N.handle(lib.cuddh_ddh_create(float(omega), _h(h_a), fem._h, nx, ny, int(self.f64), kernel), "DDH")
+        if isinstance(time_step, str) and time_step == "mesh":
+            if block is None:
+                self._h = N.handle(lib.cuddh_ddh_create(float(omega), _h(h_a), fem._h, nx, ny, int(self.f64), kernel), "DDH")
+            else:
+                self._h = N.handle(lib.cuddh_ddh_create_block(float(omega), _h(h_a), fem._h, nx, ny, int(block), int(self.f64), kernel), "DDH")
         else:
-            self._h = N.handle(lib.cuddh_ddh_create_block(float(omega), _h(h_a), fem._h, nx, ny, int(block), int(self.f64), kernel), "DDH")
+            policy, ratios = self._time_step_policy(time_step)
+            h = lib.cuddh_ddh_create_timegrid(float(omega), _h(h_a), fem._h, nx, ny, int(block or 0), int(self.f64), kernel, policy,
+                                              None if ratios is None else _h(ratios), 0 if ratios is None else int(ratios.size))
+            if not h and N.last_error().startswith("DDH error: time step"):
+                raise ValueError(f"DDH: {N.last_error()}")
+            self._h = N.handle(h, "DDH")
         self.omega = float(omega)
 
+    @staticmethod
+    def _time_step_policy(time_step):
+        """(policy, ratios) of cuddh_ddh_create_timegrid; what is wrong with an array is refused here"""
+        if isinstance(time_step, str):
+            if time_step not in ("mesh", "coefficient"):
+                raise ValueError(f"DDH: time_step must be 'mesh', 'coefficient' or an integer array, not {time_step!r}")
+            return (0 if time_step == "mesh" else 1), None
+        ratios = np.asarray(time_step)
+        if ratios.ndim != 1 or not np.issubdtype(ratios.dtype, np.integer):
+            raise ValueError("DDH: time_step ratios must be a one-dimensional integer array, one entry per subdomain")
+        if ratios.size and (ratios.min() < 1 or ratios.max() > 256):
+            raise ValueError(f"DDH: time_step ratios must lie in [1, 256], got {int(ratios.min())} .. {int(ratios.max())}")
+        return 2, np.ascontiguousarray(ratios, dtype=np.int32)
+
     @classmethod
-    def from_labels(cls, omega: float, h_a: np.ndarray, fem: H1Space, labels, precision: str = "f32", kernel: int = 0) -> "DDH":
+    def from_labels(cls, omega: float, h_a: np.ndarray, fem: H1Space, labels, precision: str = "f32", kernel: int = 0,
+                    time_step="mesh") -> "DDH":
         """DDH on any mesh with subdomain s = the elements labelled s (one label per element, e.g. Mesh2D.partition), labels in
         [0, n_domains) with n_domains = max(labels) + 1; every subdomain non-empty with at most 256 element nodes.
         kernel: 0 auto, 9 one wavefront per subdomain (n_basis 4, <= 16 elements per subdomain), 10 one workgroup per
-        subdomain.  info()["nel1d"] is 0.  Invalid labels or kernels raise here, before anything runs on the device."""
+        subdomain.  info()["nel1d"] is 0.  Invalid labels or kernels raise here, before anything runs on the device.
+        Subdomains from labels march on the mesh grid: any other time_step raises ValueError."""
+        if not (isinstance(time_step, str) and time_step == "mesh"):
+            raise ValueError("DDH.from_labels: subdomains from labels take their time step from the mesh (time_step='mesh') only")
         labels = np.ascontiguousarray(labels)
         n_elem = fem.mesh.n_elem()
         if labels.ndim != 1 or labels.size != n_elem:
@@ -481,6 +515,15 @@ class DDH:
         keys = ("n_domains", "nt", "n_lambda", "mx_dof", "mx_fdof", "nel1d", "kernel", "is_f64")
         out = dict(zip(keys, map(int, info)))
         out["dt"] = dt.value
+        return out
+
+    def time_ratios(self) -> np.ndarray:
+        """per subdomain: how many times the mesh grid's steps its local solve marches per period (time_step)"""
+        n = lib.cuddh_ddh_time_ratios(self._h, None)
+        if n < 0:
+            raise RuntimeError(f"DDH.time_ratios failed: {N.last_error()}")
+        out = np.zeros(n, dtype=np.int32)
+        lib.cuddh_ddh_time_ratios(self._h, _h(out))
         return out
 
     def set_wh_iters(self, n: int = 5):

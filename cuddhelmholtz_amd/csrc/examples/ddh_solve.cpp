@@ -1,12 +1,15 @@
 // Native C++ driver for the DDH path, written against csrc/include/cuddh.hpp (the same API the reference's
 // examples/DDH.cpp uses), with a command line instead of compile-time constants:
 //   ddh_solve [nx=128] [n_basis=4] [omega_over_pi=25.6] [gmres_m=20] [maxit=100] [tol=1e-4] [out_dir=solution] [devices=0] [force_rccl=0]
+//   options, anywhere on the line: --time-step mesh|coefficient (DDHTimeStep: where the local solves take their time step from;
+//   mesh is the default, the reference's; single-process path only), --residuals (one more line: GMRES's residual history)
 // Writes <out_dir>/xy.0000 and <out_dir>/ddh.0000 (raw fp64, like the reference) and prints one summary line.
 // devices >= 1: the same solve through cuddh::ddh_solve_multi_gpu (multigpu.hpp): subdomains sharded over that many GPUs of
 // this process, RCCL neighbour exchange; devices = 1 with force_rccl = 1 runs the communicator path on a one-GPU box;
 // force_rccl = 2 is the loopback test transport (the ranks share device 0, no RCCL); + 4 selects the split schedule.
 #include <chrono>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -16,8 +19,29 @@
 
 using namespace cuddh;
 
-int main(int argc, char **argv)
+int main(int argc_all, char **argv_all)
 {
+    // options out, positional arguments stay
+    std::string time_step = "mesh";
+    bool residuals = false;
+    std::vector<char *> args;
+    for (int i = 0; i < argc_all; ++i)
+    {
+        const std::string arg = argv_all[i];
+        if (arg == "--time-step" && i + 1 < argc_all)
+            time_step = argv_all[++i];
+        else if (arg == "--residuals")
+            residuals = true;
+        else
+            args.push_back(argv_all[i]);
+    }
+    if (time_step != "mesh" && time_step != "coefficient")
+    {
+        std::cerr << "ddh_solve: --time-step takes mesh or coefficient, not " << time_step << std::endl;
+        return 2;
+    }
+    const int argc = static_cast<int>(args.size());
+    char **argv = args.data();
     const int nx = argc > 1 ? std::atoi(argv[1]) : 128;
     const int nb = argc > 2 ? std::atoi(argv[2]) : 4;
     const double omega = M_PI * (argc > 3 ? std::atof(argv[3]) : 25.6);
@@ -50,6 +74,11 @@ int main(int argc, char **argv)
 
     if (devices >= 1)
     {
+        if (time_step != "mesh")
+        {
+            std::cerr << "ddh_solve: --time-step " << time_step << " is not passed through the multi-GPU path" << std::endl;
+            return 2;
+        }
         std::vector<double> h_u(N);
         const multi_gpu_result r = ddh_solve_multi_gpu(nx, nb, omega, a.host_read(), b.host_read(), h_u.data(), devices, m, maxit, tol, force_rccl & 3,
                                                        (force_rccl & 4) != 0, (force_rccl >> 8) & 0xFF, (force_rccl >> 16) & 0xFF);
@@ -70,7 +99,9 @@ int main(int argc, char **argv)
         return 0;
     }
 
-    DDH F(omega, a.host_read(), fem, nx, nx);
+    std::unique_ptr<DDH> ddh(time_step == "mesh" ? new DDH(omega, a.host_read(), fem, nx, nx)
+                                                 : new DDH(omega, a.host_read(), fem, nx, nx, 0, 0, DDHTimeStep::from_coefficient()));
+    DDH &F = *ddh;
     const int n_lambda = F.size();
     HostDeviceArray<float> L(n_lambda), Y(n_lambda);
     float *d_L = L.device_write(), *d_Y = Y.device_write();
@@ -108,5 +139,12 @@ int main(int argc, char **argv)
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs
               << " t_gmres=" << t_gmres << " t_postprocess=" << t_post
               << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << std::endl;
+    if (residuals)
+    {
+        std::cout << "ddh_solve time_step=" << time_step << " residuals:";
+        for (const double r : out.res_norm)
+            std::cout << " " << r / out.res_norm.front();
+        std::cout << std::endl;
+    }
     return 0;
 }

@@ -11,6 +11,7 @@
 #define CUDDH_AMD_DDH_HPP
 
 #include <memory>
+#include <vector>
 
 #include "blas1.hpp"
 #include "ensemble.hpp"
@@ -30,6 +31,29 @@ namespace cuddh
     };
     inline constexpr from_labels_t from_labels{};
 
+    /// Where the local solves take their time step from (block-grid constructors; subdomains from labels march on the mesh grid).
+    /// The mesh grid is the reference's: dt = 0.1 h / n_basis^2 shrunk so that nt steps are one period, whatever the
+    /// coefficient.  The wave speed is 1 / a, so where a < 1 that step is too long for the explicit time stepping.
+    /// Subdomain s may instead march r_s nt steps of dt / r_s, r_s an integer >= 1: local solves couple through the traces
+    /// only, so every subdomain runs its own period on its own grid.
+    struct DDHTimeStep
+    {
+        enum Policy
+        {
+            mesh,        ///< one grid from the mesh alone: the default, the reference's
+            coefficient, ///< r_s = max(1, ceil((1 - 1e-9) / min a over the subdomain's dofs)), interface dofs included; a >= 1 gives 1
+            ratios       ///< r_s = h_ratios[s]
+        };
+        Policy policy = mesh;
+        const int *h_ratios = nullptr; ///< `ratios`: HOST, one per subdomain, each in [1, max_ratio]; read by the constructor only
+        int n_ratios = 0;              ///< must be the number of subdomains
+        static constexpr int max_ratio = 256;
+
+        static DDHTimeStep from_mesh() { return {}; }
+        static DDHTimeStep from_coefficient() { return {coefficient, nullptr, 0}; }
+        static DDHTimeStep from_ratios(const int *h_ratios, int n) { return {ratios, h_ratios, n}; }
+    };
+
     namespace detail
     {
         /// setup shared by DDH and DDH64 (scalar = float or double)
@@ -41,6 +65,11 @@ namespace cuddh
             /// block x block elements per subdomain: 0 or 16 / n_basis is the size of the constructor above; else block >= 1 with
             /// n_basis^2 block^2 <= 1024 and nx, ny multiples of block (anything else throws before any allocation or launch)
             DDHCore(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
+            /// the same with a time-step policy.  `coefficient` with ONE ratio r for all subdomains is a plain plan on the grid of
+            /// r nt steps (a == 1 everywhere: the constructor above, bit for bit); several ratios, and `ratios` always, give a plan
+            /// with per-subdomain time grids (cuddh_hip_ddh_plan_set_time_grids).  A non-finite or non-positive a, a ratio outside
+            /// [1, 256] and a ratio array of the wrong length throw before any allocation or launch.
+            DDHCore(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step);
             /// subdomain s = the elements with label s (HOST, one per element, in [0, n_domains)); any connectivity.
             /// kernel: 0 auto, 9 or 10 (cuddh_hip_ddh_plan_create_general)
             DDHCore(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel);
@@ -48,8 +77,16 @@ namespace cuddh
 
             int n_traces() const { return 2 * n_lambda; }
             int num_domains() const { return n_domains; }
+            /// the base grid: the mesh grid, or under `coefficient` with one ratio r for all subdomains the grid of r times its steps
             int num_steps() const { return nt; }
             double time_step() const { return dt; }
+            /// steps of subdomain s = time_ratios()[s] * mesh_steps()
+            int mesh_steps() const;
+            const std::vector<int> &time_ratios() const;
+            /// distinct ratios of a plan with per-subdomain time grids, ascending; empty for a plan on the base grid alone
+            const std::vector<int> &time_grid_ratios() const;
+            /// HOST tables of the grid of `ratio` * mesh_steps() steps: which = 0 filter, 1 cs, 2 sn.  Returns the length (0: no such grid)
+            long long time_grid_table(int ratio, int which, const Real *&table) const;
             int kernel_kind() const;
             /// WaveHoltz iterations per local solve; the reference hard-wires 5 (source/DDH.cpp:136), the default.
             /// Verification knob (tests/test_ddh_physics.py), see cuddh_hip_ddh_plan_set_wh_iters.
@@ -99,9 +136,13 @@ namespace cuddh
 
         private:
             /// everything after the element labels (time grid, slots, renumbering, masses, H, a)
-            void setup(const double *h_a, const H1Space &fem, const int *labels);
+            void setup(const double *h_a, const H1Space &fem, const int *labels, const DDHTimeStep &time_step);
+            /// nel1d from `block` (0: 16 / n_basis), or an error: n_basis, block and the divisibility of nx, ny
+            void set_block(int nx, int ny, int block);
             /// the block grid's element labels, then setup()
-            void setup_blocks(const double *h_a, const H1Space &fem, int nx, int ny);
+            void setup_blocks(const double *h_a, const H1Space &fem, int nx, int ny, const DDHTimeStep &time_step = {});
+            /// the time grid(s) and their tables; needs gI
+            void setup_time_grids(const double *h_a, const H1Space &fem, const DDHTimeStep &time_step);
             void solve_impl(const int *d_list, int d0, int d1, const double *x, double *y, bool zero_y, const Real *lambda, Real *update) const;
 
             /// device-side part of the set-up (geometric factors, kernel plan); deferred to first use so
@@ -113,7 +154,11 @@ namespace cuddh
             int g_ndof, g_elem, n_basis, n_domains, n_lambda, nt, mx_dof, mx_fdof, mx_elem_per_dom, nel1d;
             double omega, dt;
             const Mesh2D *fem_mesh;
-            const Basis *fem_basis;
+            /// The time grids' state (and the basis) behind one pointer, in the place the basis pointer had: the size of DDH /
+            /// DDH64 and the offsets of what the inline accessors read stay what they were, so a program compiled against the
+            /// header as it was before the time-step policy (a drop-in driver built once, say) runs with this library.
+            struct More;
+            std::unique_ptr<More> more;
             int requested_kernel = 0;
             bool general = false; // subdomains from labels: cuddh_hip_ddh_plan_create_general
 
@@ -142,6 +187,8 @@ namespace cuddh
         /// block >= 1, n_basis^2 block^2 <= 1024, nx and ny multiples of block; throws otherwise.  kernel: 0 auto, 1 generic
         /// workgroup (any block), 11 one 8 x 8 block per wavefront (n_basis 4, block 8, fp32); 2-8 on their own block size only.
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
+        /// extension: the same with a time-step policy (DDHTimeStep: from the mesh, from the coefficient, or given per subdomain)
+        DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step);
         /// extension: subdomains of any shape on any Mesh2D, given as element labels (HOST, n_elem of them, in [0, n_domains),
         /// every subdomain non-empty and with at most 256 element nodes).  kernel: 0 auto, 9 one wavefront per subdomain
         /// (n_basis 4, <= 16 elements per subdomain), 10 one workgroup per subdomain.  Invalid labels throw here.
@@ -174,6 +221,7 @@ namespace cuddh
         DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel = 0);
         /// subdomains of block x block elements, as DDH(..., kernel, block); kernel 0 or 1 off the default block size
         DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
+        DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step);
         /// subdomains from element labels, as DDH(from_labels, ...)
         DDH64(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel = 0);
 

@@ -64,6 +64,14 @@ struct cuddh_ddh_plan
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
     int *csr_off = nullptr, *csr_src = nullptr;
+    int requested = 0; // the kernel the caller asked for (0 auto): cuddh_hip_ddh_plan_set_time_grids moves an auto choice, never a request
+    // per-subdomain time grids (cuddh_hip_ddh_plan_set_time_grids).  n_grids == 0: every subdomain marches on the descriptor's grid
+    int n_grids = 0;
+    void *grids = nullptr;          // DdhTimeGrid<Real>[n_grids], DEVICE, the plan's
+    const int *grid_of = nullptr;   // (n_domains) DEVICE, the caller's, like the three concatenated tables
+    const void *grid_filter = nullptr, *grid_cs = nullptr, *grid_sn = nullptr;
+    int *by_steps = nullptr;        // (n_domains) DEVICE: the subdomains by step count descending, stable by index; what a full-range apply lists
+    int *by_index = nullptr;        // (n_domains) DEVICE: 0, 1, 2, ...; what an apply over a sub-range lists
 };
 
 namespace
@@ -94,6 +102,73 @@ namespace
     __device__ inline int domain_at(const DdhArgs<Real> &A, int position)
     {
         return A.dom_list ? A.dom_list[position] : position;
+    }
+
+    // ---------------------------------------------------------------- per-subdomain time grids
+    // A plan with time grids (cuddh_hip_ddh_plan_set_time_grids) gives subdomain s the grid grid_of[s]: its own step count and
+    // step size and its own filter / cs / sn tables, which lie one grid after the other in the three arrays the kernel is
+    // passed.  The kernels that hold ONE subdomain per wavefront or workgroup take a TimeGrids as a last argument (template
+    // parameter pack Grids, empty for a plain plan: those instantiations have the arguments and the code they had before).
+    // The grid is wave-uniform, but a subdomain located from the wave index looks divergent to the compiler: the grid's index
+    // and what is read of it (nt, dt, the two offsets) go through readfirstlane, so that the loop counter, the step sizes and
+    // the table bases stay in scalar registers and filt / cs / sn on scalar loads, as on the one grid (without it the time
+    // loop gains three vector instructions and its table reads become vector loads).  Wavefronts of one workgroup may run different step counts: the wavefront kernels have no
+    // workgroup barriers, and kernel 1's workgroup is one subdomain.
+    template <typename Real>
+    struct DdhTimeGrid
+    {
+        int nt, filt_off, cs_off; // steps per period; where the grid's filter (nt + 1) and its cs / sn (2 nt + 1) start
+        Real dt;
+    };
+
+    template <typename Real>
+    struct TimeGrids
+    {
+        const int *grid_of;             // (n_domains)
+        const DdhTimeGrid<Real> *grids; // (n_grids)
+    };
+
+    // every launch of a plan with time grids goes through a list (apply: the plan's own where the caller gave none), so the
+    // wavefronts need no flag that tells the two cases apart; kernel 11 has no scalar register left for one
+    template <typename Real>
+    __device__ inline int domain_at(const DdhArgs<Real> &A, int position, const TimeGrids<Real> &)
+    {
+        return A.dom_list[position];
+    }
+
+    template <typename Real>
+    struct TimeGridView
+    {
+        int nt;
+        Real dt;
+        const Real *filt, *cs, *sn;
+    };
+
+    // the grid subdomain s marches on: the launch's one grid ...
+    template <typename Real>
+    __device__ inline TimeGridView<Real> time_grid_of(const DdhArgs<Real> &A, int, const Real *filt, const Real *cs, const Real *sn)
+    {
+        return {A.nt, A.dt, filt, cs, sn};
+    }
+
+    // the value of a wave-uniform quantity in a scalar register, whatever the compiler can prove about it
+    __device__ inline int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+    __device__ inline float wave_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+    __device__ inline double wave_uniform(double v)
+    {
+        const long long bits = __double_as_longlong(v);
+        const int lo = __builtin_amdgcn_readfirstlane(static_cast<int>(bits)), hi = __builtin_amdgcn_readfirstlane(static_cast<int>(bits >> 32));
+        return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
+    }
+
+    // ... or its own
+    template <typename Real>
+    __device__ inline TimeGridView<Real> time_grid_of(const DdhArgs<Real> &, int s, const Real *filt, const Real *cs, const Real *sn,
+                                                      const TimeGrids<Real> &TG)
+    {
+        const DdhTimeGrid<Real> tg = TG.grids[wave_uniform(TG.grid_of[s])];
+        const int filt_off = wave_uniform(tg.filt_off), cs_off = wave_uniform(tg.cs_off);
+        return {wave_uniform(tg.nt), wave_uniform(tg.dt), filt + filt_off, cs + cs_off, sn + cs_off};
     }
 
     // Issue priority of the calling wavefront (s_setprio).  All wavefronts of one rank's local solves are resident at once and
@@ -142,7 +217,8 @@ namespace
     }
 
     // The WaveHoltz iterations of one local solve for the N values a lane owns: wh_iters x (restart from the filtered field,
-    // nt RK2 steps with two stiffness sweeps z = S w each, filter accumulation).  Returns the filter sums u, v (v not yet
+    // nt RK2 steps of size dt with two stiffness sweeps z = S w each, filter accumulation) on the time grid the caller passes
+    // (time_grid_of: the launch's, or the subdomain's own).  Returns the filter sums u, v (v not yet
     // divided by omega: publish_dof does that).  -ffp-contract=fast turns the shape of these expressions into FMAs: keep it.
     // LEAN (the matrix-core kernels; 0 is the form every other kernel compiles to, instruction for instruction):
     //   != 0: the step sizes are folded into the per-dof constant (q + (half_dt invm) r instead of q + half_dt (r invm)), one
@@ -152,15 +228,15 @@ namespace
     //   1:    their sources F[l], Gf[l] are zero as well (no x given: sources sit on trace dofs only) and are not computed either;
     //   2:    they are kept.
     template <int LEAN = 0, unsigned INTERIOR = 1u, typename Real, int N, typename Sweep>
-    __device__ inline void wh_march(const DdhArgs<Real> &A, const Real *__restrict__ filt, const Real *__restrict__ cs,
-                                    const Real *__restrict__ sn, const Real (&invm)[N], const Real (&Hi)[N], const Real (&F)[N],
+    __device__ inline void wh_march(const DdhArgs<Real> &A, const int nt, const Real dt, const Real *__restrict__ filt,
+                                    const Real *__restrict__ cs, const Real *__restrict__ sn, const Real (&invm)[N], const Real (&Hi)[N], const Real (&F)[N],
                                     const Real (&Gf)[N], Real (&u)[N], Real (&v)[N], Sweep sweep)
     {
         Real p[N], q[N];
 #pragma unroll
         for (int l = 0; l < N; ++l)
             p[l] = q[l] = u[l] = v[l] = 0;
-        const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
+        const Real half_dt = Real(0.5) * dt;
         Real hm[N], dm[N]; // LEAN: half_dt invm, dt invm
         if constexpr (LEAN != 0)
         {
@@ -171,7 +247,6 @@ namespace
                 dm[l] = dt * invm[l];
             }
         }
-        const int nt = A.nt;
         for (int whit = 0; whit < A.wh_iters; ++whit)
         {
             {
@@ -475,15 +550,15 @@ namespace
         }
     }
 
-    template <typename Real, int VAR>
+    template <typename Real, int VAR, typename... Grids>
     __global__ void __launch_bounds__(256) ddh_wave_kernel(DdhArgs<Real> A, const Real *__restrict__ Dmat, const Real *__restrict__ filt,
-                                                          const Real *__restrict__ cs, const Real *__restrict__ sn)
+                                                          const Real *__restrict__ cs, const Real *__restrict__ sn, Grids... grids)
     {
         const int lane = threadIdx.x & 63;
         const int position = A.dom_begin + blockIdx.x * 4 + (threadIdx.x >> 6);
         if (position >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
-        const int s = domain_at(A, position);
+        const int s = domain_at(A, position, grids...);
         raise_priority(A.prio);
 
         const int k = lane & 3, el = lane >> 2, ex = el & 3, ey = el >> 2;
@@ -527,13 +602,14 @@ namespace
 #pragma unroll
         for (int l = 0; l < 4; ++l)
             p[l] = q[l] = u[l] = v[l] = 0;
-        const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
-        const int nt = A.nt;
+        const TimeGridView<Real> tg = time_grid_of(A, s, filt, cs, sn, grids...);
+        const Real dt = tg.dt, half_dt = Real(0.5) * tg.dt;
+        const int nt = tg.nt;
 
         for (int whit = 0; whit < A.wh_iters; ++whit)
         {
             {
-                const Real k0 = filt[0];
+                const Real k0 = tg.filt[0];
 #pragma unroll
                 for (int l = 0; l < 4; ++l)
                 {
@@ -545,9 +621,9 @@ namespace
             }
             for (int it = 1; it <= nt; ++it)
             {
-                const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
-                const Real c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
-                const Real kw = filt[it];
+                const Real c0 = tg.cs[2 * it - 2], s0 = tg.sn[2 * it - 2];
+                const Real c1 = tg.cs[2 * it - 1], s1 = tg.sn[2 * it - 1];
+                const Real kw = tg.filt[it];
                 Real z[4], ph[4], qh[4];
 
                 wave_stiffness<VAR>(p, z, gx, gy, gz, Dk, DTk, Dmat, mR, mL, mU, mD, lane);
@@ -1087,7 +1163,7 @@ namespace
             else
                 wave8_stiffness<ASM>(w, z, gx, gy, gz, Dk, DTk, Dmat, mR, mL, mU, mD, lane);
         };
-        wh_march(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
 
         if (!valid)
             return;
@@ -1153,9 +1229,9 @@ namespace
     // FORCED: x is given (rhs, postprocess), so dofs that are no trace dofs carry sources too.  HOLD: the launch holds issue
     // priority as a whole (A.prio, multi-GPU boundary subdomains) and the sweeps do not give it back.  Both are properties of
     // a launch and template parameters so that the time loop has no branch on them.
-    template <typename Real, bool FORCED, bool HOLD>
+    template <typename Real, bool FORCED, bool HOLD, typename... Grids>
     __global__ void __launch_bounds__(256) ddh_mfma_kernel(DdhArgs<Real> A, const Real *__restrict__ Aop, const Real *__restrict__ filt,
-                                                          const Real *__restrict__ cs, const Real *__restrict__ sn)
+                                                          const Real *__restrict__ cs, const Real *__restrict__ sn, Grids... grids)
     {
         constexpr bool PRIO = sizeof(Real) == 4 || CUDDH_DDH64_MFMA_PRIO;
         typedef Real r4 __attribute__((ext_vector_type(4)));
@@ -1163,7 +1239,7 @@ namespace
         const int position = A.dom_begin + blockIdx.x * 4 + (threadIdx.x >> 6);
         if (position >= A.dom_end)
             return; // wave-uniform, no barriers in this kernel
-        const int s = domain_at(A, position);
+        const int s = domain_at(A, position, grids...);
         if constexpr (HOLD)
             __builtin_amdgcn_s_setprio(3);
 
@@ -1205,7 +1281,8 @@ namespace
             const Real c = acc[3] + mX * x3;
             z[3] = c + mY * __shfl(c, pY, 64);
         };
-        wh_march<FORCED ? 2 : 1>(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        const TimeGridView<Real> tg = time_grid_of(A, s, filt, cs, sn, grids...);
+        wh_march<FORCED ? 2 : 1>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
 
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -1360,7 +1437,7 @@ namespace
                 z[k] = dn[k];
             }
         };
-        wh_march<FORCED ? 2 : 1, ELEMENT_INTERIOR_REGISTERS>(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march<FORCED ? 2 : 1, ELEMENT_INTERIOR_REGISTERS>(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
 
         // located a second time from a lane index the compiler cannot connect with the first: otherwise these values stay
         // in (or are spilled from) vector registers for the whole time loop, which runs at the limit of three wavefronts per SIMD
@@ -1395,24 +1472,34 @@ namespace
     // holds one subdomain, so a launch of any length needs no padding rows and a subdomain's result does not depend on
     // which others the launch holds.
     // Compiled for three wavefronts per SIMD in the action form and two in the form with x, like the 4x4 form.
-    template <bool FORCED, bool HOLD, bool LAST_COPY>
+    template <bool FORCED, bool HOLD, bool LAST_COPY, typename... Grids>
     __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane8_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
-                                                                                   const float *__restrict__ cs, const float *__restrict__ sn)
+                                                                                   const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
     {
         if (A.dom_begin + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6) >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
         if constexpr (HOLD)
             __builtin_amdgcn_s_setprio(3);
+        // with time grids the subdomain waits in one scalar register from here to the outputs: the list pointer that finding it
+        // again would take has none left to wait in
+        [[maybe_unused]] int s_wave = 0;
+        if constexpr (sizeof...(Grids) > 0)
+            s_wave = wave_uniform(domain_at(A, A.dom_begin + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), grids...));
         // where this lane works: subdomain s, its trace dofs, the dofs of its element's nodes
         auto locate = [&](int tid, int &s, int &fdof, const int *&sI)
         {
-            s = domain_at(A, A.dom_begin + (int)blockIdx.x * 4 + (tid >> 6));
+            if constexpr (sizeof...(Grids) > 0)
+                s = s_wave;
+            else
+                s = domain_at(A, A.dom_begin + (int)blockIdx.x * 4 + (tid >> 6));
             fdof = A.s_fdof[s];
             sI = A.sI + 1024 * (size_t)s + 16 * (tid & 63);
         };
         int s, fdof;
         const int *sI;
         locate(threadIdx.x, s, fdof, sI);
+        // the time grid first, while few vector registers are live: what stays of it is scalar
+        const TimeGridView<float> tg = time_grid_of(A, s, filt, cs, sn, grids...);
         const int lane = threadIdx.x & 63, ex = lane & 7, ey = lane >> 3;
 
         float invm[16], Hi[16], F[16], Gf[16], u[16], v[16];
@@ -1459,11 +1546,14 @@ namespace
                 z[k] = dn + mD * from_below;
             }
         };
-        wh_march<FORCED ? 2 : 1, ELEMENT_INTERIOR_REGISTERS>(A, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march<FORCED ? 2 : 1, ELEMENT_INTERIOR_REGISTERS>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
 
         // located a second time from a lane index the compiler cannot connect with the first, as in ddh_element_lane_kernel
+        // (with time grids the same for the subdomain in its scalar register: nothing derived from it waits through the loop)
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
+        if constexpr (sizeof...(Grids) > 0)
+            asm volatile("" : "+s"(s_wave));
         locate(tid, s, fdof, sI);
 #pragma unroll
         for (int n = 0; n < 16; ++n)
@@ -1539,14 +1629,14 @@ namespace
     // ---------------------------------------------------------------- workgroup-per-subdomain kernel (generic)
     // CSR = true is kernel 10: the contributor lists come from the plan (any valence) instead of being built with atomics.
     // MAXT: the launch bound, 256 or, for subdomains of 257 to 1024 element nodes, 1024 (at most 128 vector registers then).
-    template <typename Real, int NB, bool CSR = false, int MAXT = 256>
+    template <typename Real, int NB, bool CSR = false, int MAXT = 256, typename... Grids>
     __global__ void __launch_bounds__(MAXT) ddh_block_kernel(DdhArgs<Real> A, const Real *__restrict__ Dmat, const Real *__restrict__ filt,
-                                                           const Real *__restrict__ cs, const Real *__restrict__ sn)
+                                                           const Real *__restrict__ cs, const Real *__restrict__ sn, Grids... grids)
     {
         raise_priority(A.prio);
         const int T = A.nodes; // == blockDim.x
         const int tid = threadIdx.x;
-        const int s = domain_at(A, A.dom_begin + blockIdx.x);
+        const int s = domain_at(A, A.dom_begin + blockIdx.x, grids...);
 
         extern __shared__ double lds_raw[];
         Real *s_p = reinterpret_cast<Real *>(lds_raw); // [T] field, indexed by subdomain dof
@@ -1685,11 +1775,12 @@ namespace
             return z;
         };
 
-        const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
-        const int nt = A.nt;
+        const TimeGridView<Real> tg = time_grid_of(A, s, filt, cs, sn, grids...);
+        const Real dt = tg.dt, half_dt = Real(0.5) * tg.dt;
+        const int nt = tg.nt;
         for (int whit = 0; whit < A.wh_iters; ++whit)
         {
-            const Real k0 = filt[0];
+            const Real k0 = tg.filt[0];
             p = u;
             q = v;
             u *= k0;
@@ -1699,7 +1790,7 @@ namespace
                 s_p[tid] = p;
                 __syncthreads();
                 Real z = sweep() - Hi * q;
-                Real dq = (z + cs[2 * it - 2] * F + sn[2 * it - 2] * G) * inv_mi;
+                Real dq = (z + tg.cs[2 * it - 2] * F + tg.sn[2 * it - 2] * G) * inv_mi;
                 const Real ph = p - half_dt * q;
                 const Real qh = q + half_dt * dq;
                 p -= dt * qh;
@@ -1707,10 +1798,10 @@ namespace
                 s_p[tid] = ph;
                 __syncthreads();
                 z = sweep() - Hi * qh;
-                dq = (z + cs[2 * it - 1] * F + sn[2 * it - 1] * G) * inv_mi;
+                dq = (z + tg.cs[2 * it - 1] * F + tg.sn[2 * it - 1] * G) * inv_mi;
                 q += dt * dq;
 
-                const Real kw = filt[it];
+                const Real kw = tg.filt[it];
                 u += kw * p;
                 v += kw * q;
             }
@@ -1793,12 +1884,14 @@ namespace
     }
 
     // kernel 1 (CSR = false) or 10 (CSR = true) for the plan's n_basis; false if there is no instantiation for it
-    template <typename Real, bool CSR>
-    bool launch_block(int nb, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl, const Real *cs, const Real *sn)
+    // (grids: nothing, or the plan's TimeGrids, which selects the instantiations with per-subdomain time grids)
+    template <typename Real, bool CSR, typename... Grids>
+    bool launch_block(int nb, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl, const Real *cs, const Real *sn,
+                      Grids... grids)
     {
         const int T = A.nodes;
         const size_t lds = (size_t)T * (4 * sizeof(Real) + 5 * sizeof(int));
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_local), dim3(T), lds, st, A, D, fl, cs, sn); };
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_local), dim3(T), lds, st, A, D, fl, cs, sn, grids...); };
         if (T > 1024)
             return false;
         if (T > 256) // 52 KB of LDS in fp64 at T = 1024: within the 64 KB a workgroup gets without asking
@@ -1806,29 +1899,29 @@ namespace
             if constexpr (!CSR)
                 switch (nb)
                 {
-                case 2: launch(ddh_block_kernel<Real, 2, false, 1024>); return true;
-                case 3: launch(ddh_block_kernel<Real, 3, false, 1024>); return true;
-                case 4: launch(ddh_block_kernel<Real, 4, false, 1024>); return true;
-                case 5: launch(ddh_block_kernel<Real, 5, false, 1024>); return true;
-                case 6: launch(ddh_block_kernel<Real, 6, false, 1024>); return true;
-                case 7: launch(ddh_block_kernel<Real, 7, false, 1024>); return true;
-                case 8: launch(ddh_block_kernel<Real, 8, false, 1024>); return true;
-                case 9: launch(ddh_block_kernel<Real, 9, false, 1024>); return true;
-                case 10: launch(ddh_block_kernel<Real, 10, false, 1024>); return true;
+                case 2: launch(ddh_block_kernel<Real, 2, false, 1024, Grids...>); return true;
+                case 3: launch(ddh_block_kernel<Real, 3, false, 1024, Grids...>); return true;
+                case 4: launch(ddh_block_kernel<Real, 4, false, 1024, Grids...>); return true;
+                case 5: launch(ddh_block_kernel<Real, 5, false, 1024, Grids...>); return true;
+                case 6: launch(ddh_block_kernel<Real, 6, false, 1024, Grids...>); return true;
+                case 7: launch(ddh_block_kernel<Real, 7, false, 1024, Grids...>); return true;
+                case 8: launch(ddh_block_kernel<Real, 8, false, 1024, Grids...>); return true;
+                case 9: launch(ddh_block_kernel<Real, 9, false, 1024, Grids...>); return true;
+                case 10: launch(ddh_block_kernel<Real, 10, false, 1024, Grids...>); return true;
                 }
             return false;
         }
         switch (nb)
         {
-        case 2: launch(ddh_block_kernel<Real, 2, CSR>); break;
-        case 3: launch(ddh_block_kernel<Real, 3, CSR>); break;
-        case 4: launch(ddh_block_kernel<Real, 4, CSR>); break;
-        case 5: launch(ddh_block_kernel<Real, 5, CSR>); break;
-        case 6: launch(ddh_block_kernel<Real, 6, CSR>); break;
-        case 7: launch(ddh_block_kernel<Real, 7, CSR>); break;
-        case 8: launch(ddh_block_kernel<Real, 8, CSR>); break;
-        case 9: launch(ddh_block_kernel<Real, 9, CSR>); break;
-        case 10: launch(ddh_block_kernel<Real, 10, CSR>); break;
+        case 2: launch(ddh_block_kernel<Real, 2, CSR, 256, Grids...>); break;
+        case 3: launch(ddh_block_kernel<Real, 3, CSR, 256, Grids...>); break;
+        case 4: launch(ddh_block_kernel<Real, 4, CSR, 256, Grids...>); break;
+        case 5: launch(ddh_block_kernel<Real, 5, CSR, 256, Grids...>); break;
+        case 6: launch(ddh_block_kernel<Real, 6, CSR, 256, Grids...>); break;
+        case 7: launch(ddh_block_kernel<Real, 7, CSR, 256, Grids...>); break;
+        case 8: launch(ddh_block_kernel<Real, 8, CSR, 256, Grids...>); break;
+        case 9: launch(ddh_block_kernel<Real, 9, CSR, 256, Grids...>); break;
+        case 10: launch(ddh_block_kernel<Real, 10, CSR, 256, Grids...>); break;
         default: return false;
         }
         return true;
@@ -2084,6 +2177,8 @@ namespace
     {
         if (p->kernel != 5)
             return 0;
+        if (p->n_grids > 0)
+            return 1; // the element-lane form holds four subdomains per wavefront: one time grid
         if (p->sweep_form != 0)
             return p->sweep_form;
         return p->Sep4 && p->d.n_domains >= ELEMENT_LANE_MIN_DOMAINS ? 2 : 1;
@@ -2111,46 +2206,138 @@ namespace
     }
 
     // kernel 11: one subdomain per wavefront, four wavefronts per workgroup
-    template <bool LAST_COPY>
+    template <bool LAST_COPY, typename... Grids>
     void launch_element_lane8(const DdhArgs<float> &A, const float *Sep4, dim3 grid, dim3 block, hipStream_t st, const float *fl,
-                              const float *cs, const float *sn)
+                              const float *cs, const float *sn, Grids... grids)
     {
         if (A.x)
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane8_kernel<true, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane8_kernel<true, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_element_lane8_kernel<true, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane8_kernel<true, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
         }
         else
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane8_kernel<false, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane8_kernel<false, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_element_lane8_kernel<false, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane8_kernel<false, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
         }
     }
 
     // kernels 5 and 8: the instantiation for this launch's two fixed properties (ddh_mfma_kernel)
-    template <typename Real>
+    template <typename Real, typename... Grids>
     void launch_mfma(const DdhArgs<Real> &A, const void *Aop, dim3 grid, dim3 block, hipStream_t st, const Real *fl, const Real *cs,
-                     const Real *sn)
+                     const Real *sn, Grids... grids)
     {
         const Real *K = static_cast<const Real *>(Aop);
         if (A.x)
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_mfma_kernel<Real, true, true>), grid, block, 0, st, A, K, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_mfma_kernel<Real, true, true, Grids...>), grid, block, 0, st, A, K, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_mfma_kernel<Real, true, false>), grid, block, 0, st, A, K, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_mfma_kernel<Real, true, false, Grids...>), grid, block, 0, st, A, K, fl, cs, sn, grids...);
         }
         else
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_mfma_kernel<Real, false, true>), grid, block, 0, st, A, K, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_mfma_kernel<Real, false, true, Grids...>), grid, block, 0, st, A, K, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_mfma_kernel<Real, false, false>), grid, block, 0, st, A, K, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_mfma_kernel<Real, false, false, Grids...>), grid, block, 0, st, A, K, fl, cs, sn, grids...);
         }
+    }
+
+    // The plan's kernel for one launch.  grids: nothing (one time grid, fl / cs / sn are the descriptor's tables) or the plan's
+    // TimeGrids (fl / cs / sn are then the concatenated per-grid tables); the kernels that hold several subdomains per
+    // wavefront, and the label-built plans' kernels, exist for one grid only.
+    template <typename Real, typename... Grids>
+    int launch_local_solves(const cuddh_ddh_plan *plan, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl,
+                            const Real *cs, const Real *sn, Grids... grids)
+    {
+        constexpr bool one_grid = sizeof...(Grids) == 0;
+        const cuddh_ddh_desc &d = plan->d;
+        const dim3 grid((n_local + 3) / 4), block(256); // the wavefront kernels: four wavefronts per workgroup
+        // kernels 3, 4, 7 and the folded-DPP form of 9 exist in fp32 only; fp64 always takes the plain form
+        constexpr bool f32 = sizeof(Real) == 4;
+        constexpr int v3 = f32 ? 1 : 0, v4 = f32 ? 2 : 0;
+
+        switch (plan->kernel)
+        {
+        case 1:
+            if (!launch_block<Real, false>(d.nb, A, n_local, st, D, fl, cs, sn, grids...))
+                return static_cast<int>(hipErrorInvalidValue);
+            break;
+        case 10:
+            if constexpr (one_grid)
+            {
+                if (!launch_block<Real, true>(d.nb, A, n_local, st, D, fl, cs, sn))
+                    return static_cast<int>(hipErrorInvalidValue);
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
+        case 2: hipLaunchKernelGGL((ddh_wave_kernel<Real, 0, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
+        case 3: hipLaunchKernelGGL((ddh_wave_kernel<Real, v3, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
+        case 4: hipLaunchKernelGGL((ddh_wave_kernel<Real, v4, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
+        case 5:
+        case 8:
+            if ((plan->kernel == 5) != f32) // plan_create ties kernel 5 to fp32 (Aop) and kernel 8 to fp64 (Aop64)
+                return static_cast<int>(hipErrorInvalidValue);
+            if constexpr (f32 && one_grid)
+                if (const int form = effective_sweep_form(plan); form >= 2)
+                {
+                    if (form == 3)
+                        launch_element_lane<true>(A, plan->Sep4, n_local, st, fl, cs, sn);
+                    else
+                        launch_element_lane<false>(A, plan->Sep4, n_local, st, fl, cs, sn);
+                    break;
+                }
+            launch_mfma(A, f32 ? static_cast<const void *>(plan->Aop) : static_cast<const void *>(plan->Aop64), grid, block, st, fl, cs, sn, grids...);
+            break;
+        case 6:
+        case 7:
+            if constexpr (one_grid)
+            {
+                const dim3 grid8((n_local + 7) / 8); // two subdomains per wavefront
+                if constexpr (f32)
+                {
+                    if (plan->kernel == 7)
+                        hipLaunchKernelGGL((ddh_wave8_kernel<float, true, true>), grid8, block, 0, st, A, D, fl, cs, sn, plan->Sep);
+                    else
+                        hipLaunchKernelGGL((ddh_wave8_kernel<float, true, false>), grid8, block, 0, st, A, D, fl, cs, sn, plan->Sep);
+                }
+                else
+                    hipLaunchKernelGGL((ddh_wave8_kernel<double, false, false>), grid8, block, 0, st, A, D, fl, cs, sn,
+                                       static_cast<const double *>(nullptr));
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
+        case 9:
+            if constexpr (one_grid)
+            {
+                hipLaunchKernelGGL((ddh_general_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn);
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
+        case 11:
+            if constexpr (f32)
+            {
+                if (!plan->Sep4) // plan_create ties kernel 11 to fp32 and its tables
+                    return static_cast<int>(hipErrorInvalidValue);
+                if (plan->last_copy)
+                    launch_element_lane8<true>(A, plan->Sep4, grid, block, st, fl, cs, sn, grids...);
+                else
+                    launch_element_lane8<false>(A, plan->Sep4, grid, block, st, fl, cs, sn, grids...);
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
+        default: return static_cast<int>(hipErrorInvalidValue);
+        }
+        return launch_status();
     }
 
     template <typename Real>
@@ -2173,6 +2360,15 @@ namespace
         const int n_local = dom_end - dom_begin;
         if (n_local == 0)
             return 0;
+        // all subdomains of a plan with time grids: the long ones first, so that the short ones fill the device behind them
+        // instead of a few long ones running on alone at the end.  Caller lists run in the caller's order, and so do ranges,
+        // through the plan's identity list (domain_at: a launch of such a plan always has a list).
+        if (plan->n_grids > 0 && !dom_list)
+        {
+            dom_list = dom_begin == 0 && dom_end == d.n_domains ? plan->by_steps : plan->by_index + dom_begin;
+            dom_begin = 0;
+            dom_end = n_local;
+        }
 
         DdhArgs<Real> A;
         A.g_ndof = g_ndof;
@@ -2206,72 +2402,13 @@ namespace
         A.csr_src = plan->csr_src;
         A.unique_y = plan->gI_override ? 1 : 0;
 
-        const dim3 grid((n_local + 3) / 4), block(256); // the wavefront kernels: four wavefronts per workgroup
-        const Real *D = static_cast<const Real *>(d.D), *fl = static_cast<const Real *>(d.wh_filter);
-        const Real *cs = static_cast<const Real *>(d.cs), *sn = static_cast<const Real *>(d.sn);
-        // kernels 3, 4, 7 and the folded-DPP form of 9 exist in fp32 only; fp64 always takes the plain form
-        constexpr bool f32 = sizeof(Real) == 4;
-        constexpr int v3 = f32 ? 1 : 0, v4 = f32 ? 2 : 0;
-
-        switch (plan->kernel)
-        {
-        case 1:
-        case 10:
-            if (!(plan->kernel == 10 ? launch_block<Real, true>(d.nb, A, n_local, st, D, fl, cs, sn)
-                                     : launch_block<Real, false>(d.nb, A, n_local, st, D, fl, cs, sn)))
-                return static_cast<int>(hipErrorInvalidValue);
-            break;
-        case 2: hipLaunchKernelGGL((ddh_wave_kernel<Real, 0>), grid, block, 0, st, A, D, fl, cs, sn); break;
-        case 3: hipLaunchKernelGGL((ddh_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn); break;
-        case 4: hipLaunchKernelGGL((ddh_wave_kernel<Real, v4>), grid, block, 0, st, A, D, fl, cs, sn); break;
-        case 5:
-        case 8:
-            if ((plan->kernel == 5) != f32) // plan_create ties kernel 5 to fp32 (Aop) and kernel 8 to fp64 (Aop64)
-                return static_cast<int>(hipErrorInvalidValue);
-            if constexpr (f32)
-                if (const int form = effective_sweep_form(plan); form >= 2)
-                {
-                    if (form == 3)
-                        launch_element_lane<true>(A, plan->Sep4, n_local, st, fl, cs, sn);
-                    else
-                        launch_element_lane<false>(A, plan->Sep4, n_local, st, fl, cs, sn);
-                    break;
-                }
-            launch_mfma(A, f32 ? static_cast<const void *>(plan->Aop) : static_cast<const void *>(plan->Aop64), grid, block, st, fl, cs, sn);
-            break;
-        case 6:
-        case 7:
-        {
-            const dim3 grid8((n_local + 7) / 8); // two subdomains per wavefront
-            if constexpr (f32)
-            {
-                if (plan->kernel == 7)
-                    hipLaunchKernelGGL((ddh_wave8_kernel<float, true, true>), grid8, block, 0, st, A, D, fl, cs, sn, plan->Sep);
-                else
-                    hipLaunchKernelGGL((ddh_wave8_kernel<float, true, false>), grid8, block, 0, st, A, D, fl, cs, sn, plan->Sep);
-            }
-            else
-                hipLaunchKernelGGL((ddh_wave8_kernel<double, false, false>), grid8, block, 0, st, A, D, fl, cs, sn,
-                                   static_cast<const double *>(nullptr));
-            break;
-        }
-        case 9: hipLaunchKernelGGL((ddh_general_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn); break;
-        case 11:
-            if constexpr (f32)
-            {
-                if (!plan->Sep4) // plan_create ties kernel 11 to fp32 and its tables
-                    return static_cast<int>(hipErrorInvalidValue);
-                if (plan->last_copy)
-                    launch_element_lane8<true>(A, plan->Sep4, grid, block, st, fl, cs, sn);
-                else
-                    launch_element_lane8<false>(A, plan->Sep4, grid, block, st, fl, cs, sn);
-                break;
-            }
-            else
-                return static_cast<int>(hipErrorInvalidValue);
-        default: return static_cast<int>(hipErrorInvalidValue);
-        }
-        return launch_status();
+        const Real *D = static_cast<const Real *>(d.D);
+        if (plan->n_grids > 0) // every subdomain on its own grid: the plan's concatenated tables
+            return launch_local_solves(plan, A, n_local, st, D, static_cast<const Real *>(plan->grid_filter), static_cast<const Real *>(plan->grid_cs),
+                                       static_cast<const Real *>(plan->grid_sn),
+                                       TimeGrids<Real>{plan->grid_of, static_cast<const DdhTimeGrid<Real> *>(plan->grids)});
+        return launch_local_solves(plan, A, n_local, st, D, static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs),
+                                   static_cast<const Real *>(d.sn));
     }
     // do all subdomains have the structured NEL x NEL element layout the wave kernels assume?  *bad = 0 if so
     template <int NB, int NEL>
@@ -2329,6 +2466,7 @@ extern "C"
         p->is_f64 = is_f64 ? 1 : 0;
         p->nodes = nodes;
         p->kernel = 1;
+        p->requested = kernel;
 
         const bool wave_shape = (desc->nb == 4 && desc->nel1d == 4);
         const bool wave8_shape = (desc->nb == 8 && desc->nel1d == 2);
@@ -2540,6 +2678,12 @@ extern "C"
             (void)hipFree(plan->Sep);
         if (plan && plan->Sep4)
             (void)hipFree(plan->Sep4);
+        if (plan && plan->grids)
+            (void)hipFree(plan->grids);
+        if (plan && plan->by_steps)
+            (void)hipFree(plan->by_steps);
+        if (plan && plan->by_index)
+            (void)hipFree(plan->by_index);
         delete plan;
         return 0;
     }
@@ -2575,13 +2719,107 @@ extern "C"
     {
         if (!plan || form < 0 || form > 3)
             return static_cast<int>(hipErrorInvalidValue);
-        if (form >= 2 && (plan->kernel != 5 || !plan->Sep4))
+        if (form >= 2 && (plan->kernel != 5 || !plan->Sep4 || plan->n_grids > 0))
             return static_cast<int>(hipErrorInvalidValue);
         plan->sweep_form = form;
         return 0;
     }
 
     int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan) { return plan ? effective_sweep_form(plan) : 0; }
+
+    int cuddh_hip_ddh_plan_set_time_grids(cuddh_ddh_plan *plan, int n_grids, const int *h_nt, const double *h_dt, const void *filter,
+                                          const void *cs, const void *sn, const int *d_grid_of)
+    {
+        if (!plan || n_grids < 1 || !h_nt || !h_dt || !filter || !cs || !sn || !d_grid_of)
+            return static_cast<int>(hipErrorInvalidValue);
+        // label-built plans (kernels 9, 10) and the element-lane forms on request have one grid; so have kernels 6 and 7, which
+        // hold two subdomains per wavefront: chosen by auto they give way to kernel 1, requested they are refused
+        if (plan->kernel == 9 || plan->kernel == 10 || plan->sweep_form >= 2)
+            return static_cast<int>(hipErrorInvalidValue);
+        if ((plan->kernel == 6 || plan->kernel == 7) && plan->requested != 0)
+            return static_cast<int>(hipErrorInvalidValue);
+        const int nd = plan->d.n_domains;
+        // every offset a kernel adds to a table base is formed and checked here
+        std::vector<int> filt_off(n_grids), cs_off(n_grids);
+        long long fo = 0, co = 0;
+        for (int g = 0; g < n_grids; ++g)
+        {
+            if (h_nt[g] < 1 || !(h_dt[g] > 0.0) || !std::isfinite(h_dt[g]))
+                return static_cast<int>(hipErrorInvalidValue);
+            filt_off[g] = static_cast<int>(fo);
+            cs_off[g] = static_cast<int>(co);
+            fo += (long long)h_nt[g] + 1;
+            co += 2LL * h_nt[g] + 1;
+            if (co > 2147483647LL)
+                return static_cast<int>(hipErrorInvalidValue);
+        }
+        std::vector<int> grid_of(nd);
+        hipError_t e = hipMemcpy(grid_of.data(), d_grid_of, sizeof(int) * nd, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return static_cast<int>(e);
+        for (int s = 0; s < nd; ++s)
+            if (grid_of[s] < 0 || grid_of[s] >= n_grids)
+                return static_cast<int>(hipErrorInvalidValue);
+        std::vector<int> order(nd);
+        for (int s = 0; s < nd; ++s)
+            order[s] = s;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return h_nt[grid_of[a]] > h_nt[grid_of[b]]; });
+
+        std::vector<int> index(nd);
+        for (int s = 0; s < nd; ++s)
+            index[s] = s;
+        void *d_grids = nullptr;
+        int *d_order = nullptr, *d_index = nullptr;
+        auto upload_grids = [&](auto real)
+        {
+            using Real = decltype(real);
+            std::vector<DdhTimeGrid<Real>> h(n_grids);
+            for (int g = 0; g < n_grids; ++g)
+                h[g] = {h_nt[g], filt_off[g], cs_off[g], static_cast<Real>(h_dt[g])};
+            hipError_t err = hipMalloc(&d_grids, sizeof(DdhTimeGrid<Real>) * n_grids);
+            if (err == hipSuccess)
+                err = hipMemcpy(d_grids, h.data(), sizeof(DdhTimeGrid<Real>) * n_grids, hipMemcpyHostToDevice);
+            return err;
+        };
+        e = plan->is_f64 ? upload_grids(double()) : upload_grids(float());
+        if (e == hipSuccess)
+            e = hipMalloc(reinterpret_cast<void **>(&d_order), sizeof(int) * nd);
+        if (e == hipSuccess)
+            e = hipMemcpy(d_order, order.data(), sizeof(int) * nd, hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMalloc(reinterpret_cast<void **>(&d_index), sizeof(int) * nd);
+        if (e == hipSuccess)
+            e = hipMemcpy(d_index, index.data(), sizeof(int) * nd, hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+        {
+            if (d_grids)
+                (void)hipFree(d_grids);
+            if (d_order)
+                (void)hipFree(d_order);
+            if (d_index)
+                (void)hipFree(d_index);
+            return static_cast<int>(e);
+        }
+        if (plan->grids)
+            (void)hipFree(plan->grids);
+        if (plan->by_steps)
+            (void)hipFree(plan->by_steps);
+        if (plan->by_index)
+            (void)hipFree(plan->by_index);
+        plan->grids = d_grids;
+        plan->by_steps = d_order;
+        plan->by_index = d_index;
+        plan->n_grids = n_grids;
+        plan->grid_of = d_grid_of;
+        plan->grid_filter = filter;
+        plan->grid_cs = cs;
+        plan->grid_sn = sn;
+        if (plan->kernel == 6 || plan->kernel == 7)
+            plan->kernel = 1;
+        return 0;
+    }
+
+    int cuddh_hip_ddh_plan_time_grids(const cuddh_ddh_plan *plan) { return plan ? plan->n_grids : 0; }
 
     int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last)
     {

@@ -164,6 +164,22 @@ namespace
         if (name == "filter") return copy_table(c.table_filter(), h_out, count_only);
         if (name == "cs") return copy_table(c.table_cs(), h_out, count_only);
         if (name == "sn") return copy_table(c.table_sn(), h_out, count_only);
+        // "filter@R", "cs@R", "sn@R": the tables of the time grid of R times the mesh grid's steps
+        if (const std::size_t at = name.find('@'); at != std::string::npos)
+        {
+            const std::string base = name.substr(0, at), ratio = name.substr(at + 1);
+            const int which = base == "filter" ? 0 : base == "cs" ? 1 : base == "sn" ? 2 : -1;
+            if (which >= 0 && !ratio.empty() && ratio.size() <= 4 && ratio.find_first_not_of("0123456789") == std::string::npos)
+            {
+                const Real *table = nullptr;
+                const long long n = c.time_grid_table(std::stoi(ratio), which, table);
+                if (n == 0)
+                    throw std::runtime_error("DDH table " + name + ": no subdomain marches on that time grid");
+                if (!count_only)
+                    std::memcpy(h_out, table, sizeof(Real) * static_cast<std::size_t>(n));
+                return n;
+            }
+        }
         throw std::runtime_error("unknown DDH table: " + name);
     }
 } // namespace
@@ -648,6 +664,46 @@ extern "C"
             }
             return h;
         });
+    }
+    void *cuddh_ddh_create_timegrid(double omega, const double *h_a, void *fem, int nx, int ny, int block, int f64, int kernel, int policy,
+                                    const int *h_ratios, int n_ratios)
+    {
+        return guarded_new<DdhHandle>([&]
+        {
+            if (policy < 0 || policy > 2)
+                cuddh_error("DDH error: time step: policy must be 0 (mesh), 1 (coefficient) or 2 (ratios).");
+            const DDHTimeStep ts = policy == 2   ? DDHTimeStep::from_ratios(h_ratios, n_ratios)
+                                   : policy == 1 ? DDHTimeStep::from_coefficient()
+                                                 : DDHTimeStep::from_mesh();
+            auto h = new DdhHandle;
+            const H1Space &f = *static_cast<H1Space *>(fem);
+            try
+            {
+                if (f64)
+                    h->f64.reset(new DDH64(omega, h_a, f, nx, ny, kernel, block, ts));
+                else
+                    h->f32.reset(new DDH(omega, h_a, f, nx, ny, kernel, block, ts));
+            }
+            catch (...)
+            {
+                delete h;
+                throw;
+            }
+            return h;
+        });
+    }
+    int cuddh_ddh_time_ratios(void *d, int *h_out)
+    {
+        int n = -1;
+        guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            const std::vector<int> &r = h->is64() ? h->f64->internals().time_ratios() : h->f32->internals().time_ratios();
+            if (h_out)
+                std::copy(r.begin(), r.end(), h_out);
+            n = static_cast<int>(r.size());
+        });
+        return n;
     }
     void cuddh_ddh_destroy(void *d) { delete static_cast<DdhHandle *>(d); }
     int cuddh_ddh_size(void *d)

@@ -33,12 +33,81 @@ namespace cuddh
                     err = cuddh_hip_ddh_geom_from_corners_f64(n_domains, mx_elems, nb, n_elems, elems, w, points, corners, G, stream());
                 check_hip(err, "DDH geometric factors");
             }
+
+            // WaveHoltz tables of the grid of nt steps of dt = T / nt: filter (nt + 1: trapezoid weights of the period
+            // average), cs and sn (2 nt + 1: -cos and sin at the half steps); computed in double, rounded to Real
+            template <typename Real>
+            void fill_time_grid(double omega, int nt, double dt, Real *filt, Real *cs, Real *sn)
+            {
+                for (int k = 0; k <= nt; ++k)
+                    filt[k] = static_cast<Real>(dt * (omega / M_PI) * (std::cos(omega * k * dt) - 0.25));
+                filt[0] = static_cast<Real>(filt[0] * 0.5); // trapezoid rule end points
+                filt[nt] = static_cast<Real>(filt[nt] * 0.5);
+                for (int k = 0; k <= 2 * nt; ++k)
+                {
+                    const double t = 0.5 * k * dt;
+                    cs[k] = static_cast<Real>(-std::cos(omega * t));
+                    sn[k] = static_cast<Real>(std::sin(omega * t));
+                }
+            }
+
+            /// what can be refused about a time-step policy without the subdomains' dofs: all of it
+            void check_time_step(const DDHTimeStep &ts, const double *h_a, int g_ndof, int n_domains)
+            {
+                if (ts.policy == DDHTimeStep::mesh)
+                    return;
+                if (ts.policy == DDHTimeStep::ratios)
+                {
+                    if (!ts.h_ratios || ts.n_ratios != n_domains)
+                        cuddh_error(("DDH error: time step: " + std::to_string(ts.h_ratios ? ts.n_ratios : 0) + " ratios for " +
+                                     std::to_string(n_domains) + " subdomains.").c_str());
+                    for (int s = 0; s < n_domains; ++s)
+                        if (ts.h_ratios[s] < 1 || ts.h_ratios[s] > DDHTimeStep::max_ratio)
+                            cuddh_error(("DDH error: time step: ratio " + std::to_string(ts.h_ratios[s]) + " of subdomain " + std::to_string(s) +
+                                         " is outside [1, " + std::to_string(DDHTimeStep::max_ratio) + "].").c_str());
+                    return;
+                }
+                if (ts.policy != DDHTimeStep::coefficient)
+                    cuddh_error("DDH error: time step: unknown policy.");
+                // every dof lies in some subdomain: the smallest a of all is some subdomain's smallest
+                double a_min = INFINITY;
+                for (int g = 0; g < g_ndof; ++g)
+                {
+                    if (!std::isfinite(h_a[g]) || !(h_a[g] > 0.0))
+                        cuddh_error(("DDH error: time step: a = " + std::to_string(h_a[g]) + " at dof " + std::to_string(g) +
+                                     "; the time step from the coefficient needs a finite and positive.").c_str());
+                    a_min = std::min(a_min, h_a[g]);
+                }
+                if (g_ndof > 0 && std::ceil((1.0 / a_min) * (1.0 - 1e-9)) > DDHTimeStep::max_ratio)
+                    cuddh_error(("DDH error: time step: min a = " + std::to_string(a_min) + " asks for more than " +
+                                 std::to_string(DDHTimeStep::max_ratio) + " times the mesh grid's steps.").c_str());
+            }
         } // namespace
+
+        template <typename Real>
+        struct DDHCore<Real>::More
+        {
+            const Basis *fem_basis;
+            int nt_mesh = 0;                                     // steps of the mesh grid; subdomain s marches ratios[s] * nt_mesh
+            std::vector<int> ratios, grid_ratio;                 // per subdomain; distinct and ascending (empty: one grid)
+            std::vector<long long> grid_filter_off, grid_cs_off; // grid g's tables within the concatenated ones below
+            host_device_ivec grid_of;
+            HostDeviceArray<Real> grid_filter, grid_cs, grid_sn;
+
+            explicit More(const Basis *basis) : fem_basis(basis) {}
+        };
+
+        template <typename Real>
+        int DDHCore<Real>::mesh_steps() const { return more->nt_mesh; }
+        template <typename Real>
+        const std::vector<int> &DDHCore<Real>::time_ratios() const { return more->ratios; }
+        template <typename Real>
+        const std::vector<int> &DDHCore<Real>::time_grid_ratios() const { return more->grid_ratio; }
 
         template <typename Real>
         DDHCore<Real>::DDHCore(double omega_, const double *h_a, const H1Space &fem, int nx, int ny, int kernel)
             : g_ndof(fem.size()), g_elem(fem.mesh().n_elem()), n_basis(fem.basis().size()), omega(omega_), fem_mesh(&fem.mesh()),
-              fem_basis(&fem.basis())
+              more(new More(&fem.basis()))
         {
             const int nb = n_basis;
             if (nb < 2 || nb > 16)
@@ -55,9 +124,17 @@ namespace cuddh
         template <typename Real>
         DDHCore<Real>::DDHCore(double omega_, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block)
             : g_ndof(fem.size()), g_elem(fem.mesh().n_elem()), n_basis(fem.basis().size()), omega(omega_), fem_mesh(&fem.mesh()),
-              fem_basis(&fem.basis())
+              more(new More(&fem.basis()))
         {
             // everything is checked here, on the host, before anything is allocated or launched
+            set_block(nx, ny, block);
+            setup_blocks(h_a, fem, nx, ny);
+            requested_kernel = kernel;
+        }
+
+        template <typename Real>
+        void DDHCore<Real>::set_block(int nx, int ny, int block)
+        {
             const int nb = n_basis;
             if (nb < 2 || nb > 16)
                 cuddh_error("DDH error: n_basis must be in [2, 16].");
@@ -73,12 +150,25 @@ namespace cuddh
                 cuddh_error(("DDH error: nx = " + std::to_string(nx) + " and ny = " + std::to_string(ny) + " must be multiples of block = " +
                              std::to_string(nel1d) + ".")
                                 .c_str());
-            setup_blocks(h_a, fem, nx, ny);
+        }
+
+        template <typename Real>
+        DDHCore<Real>::DDHCore(double omega_, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block,
+                               const DDHTimeStep &time_step)
+            : g_ndof(fem.size()), g_elem(fem.mesh().n_elem()), n_basis(fem.basis().size()), omega(omega_), fem_mesh(&fem.mesh()),
+              more(new More(&fem.basis()))
+        {
+            // the checks of the constructor above, then the policy's: all on the host, before anything is allocated or launched
+            set_block(nx, ny, block);
+            if (nx * ny != g_elem)
+                cuddh_error("DDH error: nx * ny does not match the mesh.");
+            check_time_step(time_step, h_a, g_ndof, (nx / nel1d) * (ny / nel1d));
+            setup_blocks(h_a, fem, nx, ny, time_step);
             requested_kernel = kernel;
         }
 
         template <typename Real>
-        void DDHCore<Real>::setup_blocks(const double *h_a, const H1Space &fem, int nx, int ny)
+        void DDHCore<Real>::setup_blocks(const double *h_a, const H1Space &fem, int nx, int ny, const DDHTimeStep &time_step)
         {
             if (nx * ny != g_elem)
                 cuddh_error("DDH error: nx * ny does not match the mesh.");
@@ -92,14 +182,14 @@ namespace cuddh
                     for (int i = 0; i < nx; ++i)
                         labels[i + static_cast<std::size_t>(nx) * j] = (i / nel1d) + ndx * (j / nel1d);
             }, 8);
-            setup(h_a, fem, labels.data());
+            setup(h_a, fem, labels.data(), time_step);
         }
 
         template <typename Real>
         DDHCore<Real>::DDHCore(from_labels_t, double omega_, const double *h_a, const H1Space &fem, int n_domains_, const int *labels,
                                int kernel)
             : g_ndof(fem.size()), g_elem(fem.mesh().n_elem()), n_basis(fem.basis().size()), n_domains(n_domains_), nel1d(0),
-              omega(omega_), fem_mesh(&fem.mesh()), fem_basis(&fem.basis()), requested_kernel(kernel), general(true)
+              omega(omega_), fem_mesh(&fem.mesh()), more(new More(&fem.basis())), requested_kernel(kernel), general(true)
         {
             // everything is checked here, on the host, before anything is allocated or launched
             const int nb = n_basis;
@@ -133,43 +223,118 @@ namespace cuddh
                 cuddh_error("DDH error: subdomains from labels run kernel 9 or 10 (0 = auto); kernels 1-8 need the block grid.");
             if (kernel == 9 && (nb != 4 || mx_elems > 16))
                 cuddh_error("DDH error: kernel 9 needs n_basis 4 and at most 16 elements per subdomain.");
-            setup(h_a, fem, labels);
+            setup(h_a, fem, labels, DDHTimeStep::from_mesh());
         }
 
         template <typename Real>
-        void DDHCore<Real>::setup(const double *h_a, const H1Space &fem, const int *labels)
+        void DDHCore<Real>::setup_time_grids(const double *h_a, const H1Space &fem, const DDHTimeStep &time_step)
+        {
+            const int nb = n_basis;
+            int &nt_mesh = more->nt_mesh;
+            std::vector<int> &ratios = more->ratios, &grid_ratio = more->grid_ratio;
+            std::vector<long long> &grid_filter_off = more->grid_filter_off, &grid_cs_off = more->grid_cs_off;
+            host_device_ivec &_grid_of = more->grid_of;
+            HostDeviceArray<Real> &_grid_filter = more->grid_filter, &_grid_cs = more->grid_cs, &_grid_sn = more->grid_sn;
+            // ---- the mesh grid: dt = 0.1 h / nb^2 shrunk so that nt dt is one period
+            const double T = 2.0 * M_PI / omega;
+            const double h = fem.mesh().min_h();
+            dt = 0.2 * 0.5 * h / (nb * nb);
+            nt = nt_mesh = static_cast<int>(std::ceil(T / dt));
+
+            // ---- steps of subdomain s = ratios[s] * nt_mesh
+            ratios.assign(n_domains, 1);
+            if (time_step.policy == DDHTimeStep::ratios)
+                ratios.assign(time_step.h_ratios, time_step.h_ratios + n_domains);
+            else if (time_step.policy == DDHTimeStep::coefficient)
+            {
+                // the wave speed is 1 / a: the smallest a among the subdomain's dofs, those it shares with its neighbours
+                // included, sets its step.  (1 - 1e-9) keeps 1 / a that is an integer up to rounding (a = 0.2) on that integer
+                auto sizes = efem->sizes(MemorySpace::HOST);
+                auto gI = reshape(_gI.host_read(), mx_dof, n_domains);
+                for (int s = 0; s < n_domains; ++s)
+                {
+                    double a_min = INFINITY;
+                    for (int i = 0; i < sizes(s); ++i)
+                        a_min = std::min(a_min, h_a[gI(i, s)]);
+                    ratios[s] = std::max(1, static_cast<int>(std::ceil((1.0 / a_min) * (1.0 - 1e-9))));
+                }
+            }
+            std::vector<int> distinct(ratios);
+            std::sort(distinct.begin(), distinct.end());
+            distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+            // one ratio for all under `coefficient`: a plain plan on that grid.  Ratios given one by one are honoured as given.
+            const bool per_subdomain = time_step.policy == DDHTimeStep::ratios || (time_step.policy == DDHTimeStep::coefficient && distinct.size() > 1);
+            if (time_step.policy == DDHTimeStep::coefficient && !per_subdomain)
+                nt = distinct[0] * nt_mesh;
+            dt = T / nt;
+
+            _wh_filter.resize(nt + 1);
+            _cs.resize(2 * nt + 1);
+            _sn.resize(2 * nt + 1);
+            fill_time_grid(omega, nt, dt, _wh_filter.host_write(), _cs.host_write(), _sn.host_write());
+            if (!per_subdomain)
+                return;
+
+            grid_ratio = distinct;
+            long long n_filter = 0, n_cs = 0;
+            for (const int r : grid_ratio)
+            {
+                grid_filter_off.push_back(n_filter);
+                grid_cs_off.push_back(n_cs);
+                n_filter += static_cast<long long>(r) * nt_mesh + 1;
+                n_cs += 2LL * r * nt_mesh + 1;
+            }
+            if (n_cs > 2147483647LL)
+                cuddh_error("DDH error: time step: the time grids' tables need more than 2^31 entries.");
+            _grid_filter.resize(static_cast<int>(n_filter));
+            _grid_cs.resize(static_cast<int>(n_cs));
+            _grid_sn.resize(static_cast<int>(n_cs));
+            Real *gf = _grid_filter.host_write(), *gc = _grid_cs.host_write(), *gs = _grid_sn.host_write();
+            for (std::size_t g = 0; g < grid_ratio.size(); ++g)
+            {
+                const int nt_g = grid_ratio[g] * nt_mesh;
+                fill_time_grid(omega, nt_g, T / nt_g, gf + grid_filter_off[g], gc + grid_cs_off[g], gs + grid_cs_off[g]);
+            }
+            _grid_of.resize(n_domains);
+            int *grid_of = _grid_of.host_write();
+            for (int s = 0; s < n_domains; ++s)
+                grid_of[s] = static_cast<int>(std::lower_bound(grid_ratio.begin(), grid_ratio.end(), ratios[s]) - grid_ratio.begin());
+        }
+
+        template <typename Real>
+        long long DDHCore<Real>::time_grid_table(int ratio, int which, const Real *&table) const
+        {
+            const int nt_mesh = more->nt_mesh;
+            const std::vector<int> &grid_ratio = more->grid_ratio;
+            const std::vector<long long> &grid_filter_off = more->grid_filter_off, &grid_cs_off = more->grid_cs_off;
+            const HostDeviceArray<Real> &_grid_filter = more->grid_filter, &_grid_cs = more->grid_cs, &_grid_sn = more->grid_sn;
+            if (which < 0 || which > 2 || ratio < 1)
+                return 0;
+            const long long n = (which == 0 ? 1LL : 2LL) * ratio * nt_mesh + 1;
+            if (grid_ratio.empty())
+            {
+                if (static_cast<long long>(ratio) * nt_mesh != nt)
+                    return 0;
+                table = which == 0 ? _wh_filter.host_read() : which == 1 ? _cs.host_read() : _sn.host_read();
+                return n;
+            }
+            const auto it = std::lower_bound(grid_ratio.begin(), grid_ratio.end(), ratio);
+            if (it == grid_ratio.end() || *it != ratio)
+                return 0;
+            const std::size_t g = it - grid_ratio.begin();
+            table = which == 0 ? _grid_filter.host_read() + grid_filter_off[g]
+                               : (which == 1 ? _grid_cs.host_read() : _grid_sn.host_read()) + grid_cs_off[g];
+            return n;
+        }
+
+        template <typename Real>
+        void DDHCore<Real>::setup(const double *h_a, const H1Space &fem, const int *labels, const DDHTimeStep &time_step)
         {
             const int nb = n_basis;
             PhaseTimer timer;
             efem.reset(new EnsembleSpace(fem, n_domains, labels));
             timer.lap("EnsembleSpace");
 
-            // ---- WaveHoltz time grid: dt = 0.1 h / nb^2 shrunk so that nt dt is one period
-            const double T = 2.0 * M_PI / omega;
-            const double h = fem.mesh().min_h();
-            dt = 0.2 * 0.5 * h / (nb * nb);
-            nt = static_cast<int>(std::ceil(T / dt));
-            dt = T / nt;
-
-            _wh_filter.resize(nt + 1);
-            Real *filt = _wh_filter.host_write();
-            for (int k = 0; k <= nt; ++k)
-                filt[k] = static_cast<Real>(dt * (omega / M_PI) * (std::cos(omega * k * dt) - 0.25));
-            filt[0] = static_cast<Real>(filt[0] * 0.5); // trapezoid rule end points
-            filt[nt] = static_cast<Real>(filt[nt] * 0.5);
-
-            _cs.resize(2 * nt + 1);
-            _sn.resize(2 * nt + 1);
-            Real *cs = _cs.host_write();
-            Real *sn = _sn.host_write();
-            for (int k = 0; k <= 2 * nt; ++k)
-            {
-                const double t = 0.5 * k * dt;
-                cs[k] = static_cast<Real>(-std::cos(omega * t));
-                sn[k] = static_cast<Real>(std::sin(omega * t));
-            }
-
-            timer.lap("time grid tables");
             // ---- extents
             auto sizes = efem->sizes(MemorySpace::HOST);
             auto fsizes = efem->fsizes(MemorySpace::HOST);
@@ -244,6 +409,8 @@ namespace cuddh
             }, 16);
 
             timer.lap("face-first renumbering");
+            setup_time_grids(h_a, fem, time_step);
+            timer.lap("time grid tables");
             // ---- local operators
             const Basis &basis = fem.basis();
             const QuadratureRule &q = basis.quadrature();
@@ -389,7 +556,7 @@ namespace cuddh
                 return;
             PhaseTimer timer;
             const int nb = n_basis;
-            const QuadratureRule &q = fem_basis->quadrature();
+            const QuadratureRule &q = more->fem_basis->quadrature();
 
             // geometric factors G (3, nb*nb*mx_elems, n_domains) from the Jacobians at the GLL points
             host_device_dvec w(nb);
@@ -433,6 +600,20 @@ namespace cuddh
             d.wh_filter = _wh_filter.device_read();
             d.cs = _cs.device_read();
             d.sn = _sn.device_read();
+            const int nt_mesh = more->nt_mesh;
+            const std::vector<int> &grid_ratio = more->grid_ratio;
+            const host_device_ivec &_grid_of = more->grid_of;
+            const HostDeviceArray<Real> &_grid_filter = more->grid_filter, &_grid_cs = more->grid_cs, &_grid_sn = more->grid_sn;
+            const bool per_subdomain = !grid_ratio.empty();
+            const Real *d_filter = nullptr, *d_cs = nullptr, *d_sn = nullptr;
+            const int *d_grid_of = nullptr;
+            if (per_subdomain)
+            {
+                d_filter = _grid_filter.device_read();
+                d_cs = _grid_cs.device_read();
+                d_sn = _grid_sn.device_read();
+                d_grid_of = _grid_of.device_read();
+            }
             check_hip(cuddh_hip_stream_sync(stream()), "DDH table upload");
             timer.lap("plan: table uploads");
             const int is_f64 = std::is_same_v<Real, double> ? 1 : 0;
@@ -440,6 +621,24 @@ namespace cuddh
                 check_hip(cuddh_hip_ddh_plan_create_general(&plan, &d, mx_elem_per_dom, is_f64, requested_kernel), "DDH plan");
             else
                 check_hip(cuddh_hip_ddh_plan_create(&plan, &d, is_f64, requested_kernel), "DDH plan");
+            if (per_subdomain)
+            {
+                std::vector<int> h_nt;
+                std::vector<double> h_dt;
+                for (const int r : grid_ratio)
+                {
+                    h_nt.push_back(r * nt_mesh);
+                    h_dt.push_back(2.0 * M_PI / omega / h_nt.back());
+                }
+                const int err = cuddh_hip_ddh_plan_set_time_grids(plan, static_cast<int>(h_nt.size()), h_nt.data(), h_dt.data(), d_filter, d_cs,
+                                                                  d_sn, d_grid_of);
+                if (err) // never a plan that would march every subdomain on the mesh grid instead
+                {
+                    cuddh_hip_ddh_plan_destroy(plan);
+                    plan = nullptr;
+                }
+                check_hip(err, "DDH time grids (the requested kernel holds several subdomains per wavefront?)");
+            }
             timer.lap("plan: structure check + kernel tables");
         }
 
@@ -610,6 +809,11 @@ namespace cuddh
     {
     }
 
+    DDH::DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step)
+        : core(omega, h_a, fem, nx, ny, kernel, block, time_step)
+    {
+    }
+
     DDH::DDH(from_labels_t tag, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel)
         : core(tag, omega, h_a, fem, n_domains, labels, kernel)
     {
@@ -647,6 +851,11 @@ namespace cuddh
 
     DDH64::DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block)
         : core(omega, h_a, fem, nx, ny, kernel, block)
+    {
+    }
+
+    DDH64::DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step)
+        : core(omega, h_a, fem, nx, ny, kernel, block, time_step)
     {
     }
 

@@ -127,6 +127,17 @@ void *cuddh_ddh_create_block(double omega, const double *h_a, void *fem, int nx,
  * kernel: 0 auto, 9 one wavefront per subdomain (n_basis 4, <= 16 elements), 10 one workgroup per subdomain
  * (cuddh_hip_ddh_plan_create_general).  cuddh_ddh_info reports nel1d = 0. */
 void *cuddh_ddh_create_labels(double omega, const double *h_a, void *fem, int n_domains, const int *h_labels, int f64, int kernel);
+/* cuddh_ddh_create_block with a time-step policy (cuddh::DDHTimeStep): 0 = the mesh grid, cuddh_ddh_create_block itself;
+ * 1 = from the coefficient: subdomain s marches r_s times the mesh grid's steps, r_s = max(1, ceil((1 - 1e-9) / min a over its
+ * dofs)); one ratio for all gives a plain plan on that grid, several a plan with per-subdomain time grids
+ * (cuddh_hip_ddh_plan_set_time_grids); 2 = h_ratios HOST, n_ratios = the number of subdomains, r_s = h_ratios[s], always run
+ * per subdomain.  A non-finite or non-positive a (policy 1), a ratio outside [1, 256] and a wrong n_ratios are refused before
+ * anything is allocated (NULL + cuddh_last_error, the message starts with "DDH error: time step").  cuddh_ddh_info keeps
+ * reporting the base grid (the mesh grid, or the one grid of policy 1 with one ratio). */
+void *cuddh_ddh_create_timegrid(double omega, const double *h_a, void *fem, int nx, int ny, int block, int f64, int kernel, int policy,
+                                const int *h_ratios, int n_ratios);
+/* h_out HOST (n_domains) or NULL: r_s of every subdomain (all 1 for the mesh grid).  Returns n_domains, -1 on error. */
+int cuddh_ddh_time_ratios(void *ddh, int *h_out);
 void cuddh_ddh_destroy(void *ddh);
 int cuddh_ddh_size(void *ddh);
 /* h_info = {n_domains, nt, n_lambda, mx_dof, mx_fdof, nel1d, kernel (needs a GPU; -1 if none), is_f64}; *h_dt = time step */
@@ -190,7 +201,9 @@ int cuddh_ddh_local_traces_listed(void *ddh, const int *d_domains, int n, const 
 int cuddh_ddh_local_solution_listed(void *ddh, const int *d_domains, int n, const void *lambda, const double *f, double *u, int zero_u);
 int cuddh_ddh_local_solution(void *ddh, int d0, int d1, const void *lambda, const double *f, double *u, int zero_u);
 /* HOST copies of the constructor's tables: name in {"B","gI","sI"} (int) or
- * {"D","G","m","gmi","a","H","filter","cs","sn"} (float / double by f64).  count_only != 0: just return the length. */
+ * {"D","G","m","gmi","a","H","filter","cs","sn"} (float / double by f64).  count_only != 0: just return the length.
+ * "filter", "cs" and "sn" are the base grid's; "filter@R", "cs@R", "sn@R" those of the grid of R times the mesh grid's steps,
+ * for every R some subdomain marches on (cuddh_ddh_time_ratios); -1 + cuddh_last_error for any other R. */
 long long cuddh_ddh_table(void *ddh, const char *name, void *h_out, int count_only);
 
 /* ---- GMRES (reference include/gmres.hpp).  h_res / h_time: HOST arrays of maxit + 1 entries (may be NULL). */

@@ -363,6 +363,31 @@ int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan);
  * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with
  * hipErrorInvalidValue on a plan that is not kernel 11. */
 int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last);
+/* Per-subdomain time grids.  The descriptor holds ONE grid (nt, dt, wh_filter, cs, sn), taken from the mesh alone; the wave
+ * speed 1 / a never enters it, and where a < 1 the explicit time stepping runs past its usable range.  Local
+ * solves couple through the traces only, so every subdomain may march its WaveHoltz period on a grid of its own: after this
+ * call subdomain s runs h_nt[g] steps of h_dt[g] with g = d_grid_of[s], in every later launch of the plan.
+ *   n_grids >= 1; h_nt, h_dt: HOST, one entry per grid;
+ *   filter, cs, sn: DEVICE, `real` like the descriptor's, the grids' tables one after the other: grid g's filter starts at
+ *       the sum of h_nt[j] + 1 over j < g, its cs and sn at the sum of 2 h_nt[j] + 1 (formulas of the descriptor's tables
+ *       with nt = h_nt[g], dt = h_dt[g]);
+ *   d_grid_of: DEVICE, n_domains ints in [0, n_grids), read back and checked here.
+ * The four DEVICE arrays stay the caller's and must outlive the plan, like the descriptor's.  The descriptor's own grid is
+ * then unused.  Allocates and synchronises.
+ * One subdomain per wavefront or workgroup is what makes the grid uniform where the time loop reads it, so kernels 1, 2, 3,
+ * 4, 5 in the matrix form, 8 and 11 run such a plan (instantiations of their own; a plan without grids launches the code it
+ * did before).  The kernels that hold several subdomains per wavefront do not: a kernel-5 plan takes the matrix form whatever
+ * its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan that auto resolved to kernel 6 or 7 becomes kernel 1;
+ * a plan created with kernel 6 or 7 on request, one with sweep form 2 or 3 set, and a general plan (kernels 9, 10) are
+ * refused with hipErrorInvalidValue, as are a grid with nt < 1 or dt <= 0 and an entry of d_grid_of out of range.
+ * An apply over the whole range [0, n_domains) of such a plan runs the subdomains in the order of their step counts,
+ * longest first and by index among equals (a list the plan owns), so that the short solves fill the device behind the
+ * long ones; sub-ranges and caller lists run in the caller's order.  A subdomain's result depends on nothing else in the
+ * launch, so the order changes no bit of it.
+ * cuddh_hip_ddh_plan_time_grids returns the number of grids set, 0 for a plan on the descriptor's grid. */
+int cuddh_hip_ddh_plan_set_time_grids(cuddh_ddh_plan *plan, int n_grids, const int *h_nt, const double *h_dt, const void *filter,
+                                      const void *cs, const void *sn, const int *d_grid_of);
+int cuddh_hip_ddh_plan_time_grids(const cuddh_ddh_plan *plan);
 
 /* source/DDH.cpp:111-321 (ddh_action + stiffness).  x: forcing [F;G] (2*g_ndof
  * doubles) or NULL; y: solution output [u;v] (2*g_ndof doubles, zero-filled by

@@ -23,6 +23,9 @@ RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, 
                        # ddh_block_kernel got its launch bound as a fourth template argument; 256 is the bound it had
                        **{f"ddh_block_kernel<{real}, {nb}, {csr}>": f"ddh_block_kernel<{real}, {nb}, {csr}, 256>"
                           for real in ("float", "double") for nb in range(2, 11) for csr in ("false", "true")}}}
+# instantiations that are another one plus a template argument, per file: pattern removed from the demangled name gives the base.
+# A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
+DERIVED = {"ddh.hip": r", TimeGrids<\w+> ?(?=>)"}
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
@@ -60,12 +63,14 @@ def main():
     print(f"{len(old)} kernels before, {len(new)} after")
     print("kernel | vgpr sgpr scratch lds before -> after | instructions before -> after | histogram | sequence diff | inside loops")
     same = 0
+    old_in_new = {}  # NEW's version of the kernels OLD has
     for name, (m0, o0, l0) in old.items():
         succ = name if name in new else renamed.get(name, name)
         if succ not in new:
             print(f"{name} | MISSING after")
             continue
         m1, o1, l1 = new.pop(succ)
+        old_in_new[succ] = (m1, o1, l1)
         hist = collections.Counter(o0) == collections.Counter(o1)
         # mnemonics removed + added by a longest-matching-blocks alignment (autojunk off: a few dozen distinct values repeat
         # thousands of times); not a minimal edit distance, but 0 means identical and small means a few moved instructions
@@ -78,8 +83,19 @@ def main():
         same += m0 == m1 and hist and diff == 0
         label = name if succ == name else f"{name} => {succ}"
         print(f"{label} | {regs(m0)} -> {regs(m1)} | {len(o0)} -> {len(o1)} | {'same' if hist else 'DIFFERS'} | {diff} | {loops}")
+    all_new = {**{renamed.get(k, k): v for k, v in old_in_new.items()}, **new}
+    derived = DERIVED.get(flags_of)
+    valu = lambda c: sum(v for k, v in c.items() if k.startswith("v_"))  # noqa: E731
     for name, (m1, o1, l1) in new.items():  # a kernel the old file does not have: its registers and what its loops hold
         c1 = collections.Counter(l1)
+        base = re.sub(derived, "", name) if derived else name
+        if base != name and base in all_new:
+            m0, _, l0 = all_new[base]
+            c0 = collections.Counter(l0)
+            regs = lambda m: " ".join(str(m[f]) for f in FIELDS)  # noqa: E731
+            print(f"{name} | NEW after, against {base} | {regs(m0)} -> {regs(m1)} | inside loops {len(l0)} -> {len(l1)}, vector instructions "
+                  f"{valu(c0)} -> {valu(c1)}" + ("" if c0 == c1 else ", " + " ".join(f"{k}:{c0[k]}->{c1[k]}" for k in sorted(set(c0) | set(c1)) if c0[k] != c1[k])))
+            continue
         print(f"{name} | NEW after | {' '.join(str(m1[f]) for f in FIELDS)} | {len(o1)} instructions, {len(l1)} inside loops: "
               + " ".join(f"{k}:{c1[k]}" for k in sorted(c1)))
     print(f"{same} of {len(old)} kernels: same registers, same mnemonic sequence")
