@@ -172,6 +172,8 @@ _sig("cuddh_hip_ddh_plan_sweep_form", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_owner_rule", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_set_time_grids", ci, vp, ci, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_time_grids", ci, vp)
+_sig("cuddh_hip_ddh_plan_set_integrator", ci, vp, ci)
+_sig("cuddh_hip_ddh_plan_integrator", ci, vp)
 _sig("cuddh_hip_ddh_apply_list_f32", ci, vp, vp, ci, vp, vp, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_apply_list_f64", ci, vp, vp, ci, vp, vp, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_set_vector_layout", ci, vp, vp, ci)
@@ -245,6 +247,8 @@ _sig("cuddh_ddh_create_block", vp, cd, vp, vp, ci, ci, ci, ci, ci)
 _sig("cuddh_ddh_create_labels", vp, cd, vp, vp, ci, vp, ci, ci)
 _sig("cuddh_ddh_create_timegrid", vp, cd, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci)
 _sig("cuddh_ddh_time_ratios", ci, vp, vp)
+_sig("cuddh_ddh_create_integrator", vp, cd, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, ci)
+_sig("cuddh_ddh_integrator", ci, vp, vp, vp)
 _sig("cuddh_ddh_destroy", None, vp)
 _sig("cuddh_ddh_size", ci, vp)
 _sig("cuddh_ddh_info", ci, vp, vp, vp)

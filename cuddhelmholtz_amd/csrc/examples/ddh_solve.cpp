@@ -2,7 +2,9 @@
 // examples/DDH.cpp uses), with a command line instead of compile-time constants:
 //   ddh_solve [nx=128] [n_basis=4] [omega_over_pi=25.6] [gmres_m=20] [maxit=100] [tol=1e-4] [out_dir=solution] [devices=0] [force_rccl=0]
 //   options, anywhere on the line: --time-step mesh|coefficient (DDHTimeStep: where the local solves take their time step from;
-//   mesh is the default, the reference's; single-process path only), --residuals (one more line: GMRES's residual history)
+//   mesh is the default, the reference's; single-process path only), --integrator rk2|rk4 --coarsen N (DDHIntegrator: rk2 on
+//   the mesh grid is the default; rk4 marches ceil(nt / N) steps, N in [1, 16], 4 unless given; single-process path only),
+//   --residuals (one more line: GMRES's residual history)
 // Writes <out_dir>/xy.0000 and <out_dir>/ddh.0000 (raw fp64, like the reference) and prints one summary line.
 // devices >= 1: the same solve through cuddh::ddh_solve_multi_gpu (multigpu.hpp): subdomains sharded over that many GPUs of
 // this process, RCCL neighbour exchange; devices = 1 with force_rccl = 1 runs the communicator path on a one-GPU box;
@@ -22,7 +24,8 @@ using namespace cuddh;
 int main(int argc_all, char **argv_all)
 {
     // options out, positional arguments stay
-    std::string time_step = "mesh";
+    std::string time_step = "mesh", integrator = "rk2";
+    int coarsen = 0; // 0: not given
     bool residuals = false;
     std::vector<char *> args;
     for (int i = 0; i < argc_all; ++i)
@@ -30,6 +33,10 @@ int main(int argc_all, char **argv_all)
         const std::string arg = argv_all[i];
         if (arg == "--time-step" && i + 1 < argc_all)
             time_step = argv_all[++i];
+        else if (arg == "--integrator" && i + 1 < argc_all)
+            integrator = argv_all[++i];
+        else if (arg == "--coarsen" && i + 1 < argc_all)
+            coarsen = std::atoi(argv_all[++i]);
         else if (arg == "--residuals")
             residuals = true;
         else
@@ -38,6 +45,18 @@ int main(int argc_all, char **argv_all)
     if (time_step != "mesh" && time_step != "coefficient")
     {
         std::cerr << "ddh_solve: --time-step takes mesh or coefficient, not " << time_step << std::endl;
+        return 2;
+    }
+    if (integrator != "rk2" && integrator != "rk4")
+    {
+        std::cerr << "ddh_solve: --integrator takes rk2 or rk4, not " << integrator << std::endl;
+        return 2;
+    }
+    if (coarsen == 0)
+        coarsen = integrator == "rk4" ? 4 : 1;
+    if (coarsen < 1 || coarsen > DDHIntegrator::max_coarsen || (integrator == "rk2" && coarsen != 1))
+    {
+        std::cerr << "ddh_solve: --coarsen takes 1 to " << DDHIntegrator::max_coarsen << " with --integrator rk4, and 1 with rk2" << std::endl;
         return 2;
     }
     const int argc = static_cast<int>(args.size());
@@ -79,6 +98,11 @@ int main(int argc_all, char **argv_all)
             std::cerr << "ddh_solve: --time-step " << time_step << " is not passed through the multi-GPU path" << std::endl;
             return 2;
         }
+        if (integrator != "rk2")
+        {
+            std::cerr << "ddh_solve: --integrator " << integrator << " is not passed through the multi-GPU path" << std::endl;
+            return 2;
+        }
         std::vector<double> h_u(N);
         const multi_gpu_result r = ddh_solve_multi_gpu(nx, nb, omega, a.host_read(), b.host_read(), h_u.data(), devices, m, maxit, tol, force_rccl & 3,
                                                        (force_rccl & 4) != 0, (force_rccl >> 8) & 0xFF, (force_rccl >> 16) & 0xFF);
@@ -99,8 +123,10 @@ int main(int argc_all, char **argv_all)
         return 0;
     }
 
-    std::unique_ptr<DDH> ddh(time_step == "mesh" ? new DDH(omega, a.host_read(), fem, nx, nx)
-                                                 : new DDH(omega, a.host_read(), fem, nx, nx, 0, 0, DDHTimeStep::from_coefficient()));
+    const DDHTimeStep ts = time_step == "mesh" ? DDHTimeStep::from_mesh() : DDHTimeStep::from_coefficient();
+    std::unique_ptr<DDH> ddh(integrator == "rk4"   ? new DDH(omega, a.host_read(), fem, nx, nx, 0, 0, ts, DDHIntegrator::rk4_on(coarsen))
+                             : time_step == "mesh" ? new DDH(omega, a.host_read(), fem, nx, nx)
+                                                   : new DDH(omega, a.host_read(), fem, nx, nx, 0, 0, ts));
     DDH &F = *ddh;
     const int n_lambda = F.size();
     HostDeviceArray<float> L(n_lambda), Y(n_lambda);

@@ -54,6 +54,29 @@ namespace cuddh
         static DDHTimeStep from_ratios(const int *h_ratios, int n) { return {ratios, h_ratios, n}; }
     };
 
+    /// How the local solves step in time, and on how coarse a grid (block-grid constructors).
+    /// rk2: the reference's explicit midpoint rule on the reference's grid, two stiffness sweeps per step; the default.
+    /// rk4: classical Runge-Kutta, four sweeps per step, on a base grid of ceil(nt_mesh / coarsen) steps, nt_mesh the mesh
+    /// grid's; a DDHTimeStep ratio r_s multiplies that count as it multiplies the mesh grid's.  The mesh grid is as fine as it
+    /// is because the midpoint rule amplifies every undamped mode by 1 + (mu dt)^4 / 8 per step, not for
+    /// accuracy: RK4 at coarsen 4 is closer to the exact local solve than RK2 on the mesh grid, in half the sweeps.
+    /// Stable range: with a == 1 the largest eigenvalue of a subdomain's first-order system times the mesh step is 0.12
+    /// against RK4's 2.78, so the range ends near coarsen 23; max_coarsen = 16 keeps a margin.  The range scales with min a
+    /// over a subdomain unless DDHTimeStep::coefficient compensates: with a = 0.2 and the mesh policy, coarsen <= 4.
+    struct DDHIntegrator
+    {
+        enum Scheme
+        {
+            rk2,
+            rk4
+        };
+        Scheme scheme = rk2;
+        int coarsen = 1; ///< in [1, max_coarsen]; rk2 takes 1 only, so that an rk2 plan is exactly what it was
+        static constexpr int max_coarsen = 16;
+
+        static DDHIntegrator rk4_on(int coarsen = 4) { return {rk4, coarsen}; }
+    };
+
     namespace detail
     {
         /// setup shared by DDH and DDH64 (scalar = float or double)
@@ -70,6 +93,10 @@ namespace cuddh
             /// with per-subdomain time grids (cuddh_hip_ddh_plan_set_time_grids).  A non-finite or non-positive a, a ratio outside
             /// [1, 256] and a ratio array of the wrong length throw before any allocation or launch.
             DDHCore(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step);
+            /// the same with an integrator.  An unknown scheme, a coarsen outside [1, 16] and coarsen > 1 with rk2 throw before any
+            /// allocation or launch; a kernel that has no RK4 form (cuddh_hip_ddh_plan_set_integrator) throws on first use.
+            DDHCore(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step,
+                    const DDHIntegrator &integrator);
             /// subdomain s = the elements with label s (HOST, one per element, in [0, n_domains)); any connectivity.
             /// kernel: 0 auto, 9 or 10 (cuddh_hip_ddh_plan_create_general)
             DDHCore(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel);
@@ -77,11 +104,13 @@ namespace cuddh
 
             int n_traces() const { return 2 * n_lambda; }
             int num_domains() const { return n_domains; }
-            /// the base grid: the mesh grid, or under `coefficient` with one ratio r for all subdomains the grid of r times its steps
+            /// the base grid: the mesh grid (coarsened by the integrator's factor), or under `coefficient` with one ratio r for all
+            /// subdomains the grid of r times its steps
             int num_steps() const { return nt; }
             double time_step() const { return dt; }
-            /// steps of subdomain s = time_ratios()[s] * mesh_steps()
+            /// steps of subdomain s = time_ratios()[s] * mesh_steps(); with an integrator that coarsens, ceil(mesh grid's / coarsen)
             int mesh_steps() const;
+            DDHIntegrator integrator() const;
             const std::vector<int> &time_ratios() const;
             /// distinct ratios of a plan with per-subdomain time grids, ascending; empty for a plan on the base grid alone
             const std::vector<int> &time_grid_ratios() const;
@@ -137,6 +166,8 @@ namespace cuddh
         private:
             /// everything after the element labels (time grid, slots, renumbering, masses, H, a)
             void setup(const double *h_a, const H1Space &fem, const int *labels, const DDHTimeStep &time_step);
+            /// the integrator into `more`, or an error
+            void set_integrator(const DDHIntegrator &integrator);
             /// nel1d from `block` (0: 16 / n_basis), or an error: n_basis, block and the divisibility of nx, ny
             void set_block(int nx, int ny, int block);
             /// the block grid's element labels, then setup()
@@ -189,6 +220,9 @@ namespace cuddh
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
         /// extension: the same with a time-step policy (DDHTimeStep: from the mesh, from the coefficient, or given per subdomain)
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step);
+        /// extension: the same with an integrator (DDHIntegrator: the reference's RK2, or RK4 on a coarser grid)
+        DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step,
+            const DDHIntegrator &integrator);
         /// extension: subdomains of any shape on any Mesh2D, given as element labels (HOST, n_elem of them, in [0, n_domains),
         /// every subdomain non-empty and with at most 256 element nodes).  kernel: 0 auto, 9 one wavefront per subdomain
         /// (n_basis 4, <= 16 elements per subdomain), 10 one workgroup per subdomain.  Invalid labels throw here.
@@ -222,6 +256,8 @@ namespace cuddh
         /// subdomains of block x block elements, as DDH(..., kernel, block); kernel 0 or 1 off the default block size
         DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
         DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step);
+        DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step,
+              const DDHIntegrator &integrator);
         /// subdomains from element labels, as DDH(from_labels, ...)
         DDH64(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel = 0);
 

@@ -16,7 +16,7 @@
 //     with the field staged in LDS, 3 barriers per stiffness sweep.
 //
 // Shape of the file: every local solve is  load_dof (per-dof coefficients)  ->
-// wh_march (the WaveHoltz / RK2 time stepping around a callable `sweep(w, z)`,
+// wh_march (the WaveHoltz time stepping, RK2 or for an RK4 plan RK4, around a callable `sweep(w, z)`,
 // z = S w)  ->  publish_dof (y and the trace update).  All six wavefront kernels
 // use load_dof.  ddh_wave8_kernel, ddh_mfma_kernel<Real, ..> and
 // ddh_element_lane_kernel (kernel 5's second sweep form: one element per lane,
@@ -72,6 +72,7 @@ struct cuddh_ddh_plan
     const void *grid_filter = nullptr, *grid_cs = nullptr, *grid_sn = nullptr;
     int *by_steps = nullptr;        // (n_domains) DEVICE: the subdomains by step count descending, stable by index; what a full-range apply lists
     int *by_index = nullptr;        // (n_domains) DEVICE: 0, 1, 2, ...; what an apply over a sub-range lists
+    int rk4 = 0; // cuddh_hip_ddh_plan_set_integrator: the local solves step with classical RK4 (four sweeps per step), not RK2
 };
 
 namespace
@@ -171,6 +172,37 @@ namespace
         return {wave_uniform(tg.nt), wave_uniform(tg.dt), filt + filt_off, cs + cs_off, sn + cs_off};
     }
 
+    // ---------------------------------------------------------------- the integrator of a launch
+    // A plan with cuddh_hip_ddh_plan_set_integrator(plan, 1) steps with classical RK4.  Its kernels are instantiations of their
+    // own: the tag below comes last in the same trailing pack that carries the TimeGrids, so a kernel is instantiated with
+    // nothing (RK2, one grid: the code and the symbol it had before), TimeGrids, Rk4Scheme, or TimeGrids then Rk4Scheme.
+    struct Rk4Scheme
+    {
+    };
+
+    template <typename... Opts>
+    inline constexpr int scheme_of = 0; // wh_march's SCHEME: 0 RK2, 1 RK4
+    template <typename First, typename... Rest>
+    inline constexpr int scheme_of<First, Rest...> = scheme_of<Rest...>;
+    template <>
+    inline constexpr int scheme_of<Rk4Scheme> = 1;
+
+    template <typename Real>
+    __device__ inline int domain_at(const DdhArgs<Real> &A, int position, const Rk4Scheme &) { return domain_at(A, position); }
+    template <typename Real>
+    __device__ inline int domain_at(const DdhArgs<Real> &A, int position, const TimeGrids<Real> &TG, const Rk4Scheme &) { return domain_at(A, position, TG); }
+    template <typename Real>
+    __device__ inline TimeGridView<Real> time_grid_of(const DdhArgs<Real> &A, int s, const Real *filt, const Real *cs, const Real *sn, const Rk4Scheme &)
+    {
+        return time_grid_of(A, s, filt, cs, sn);
+    }
+    template <typename Real>
+    __device__ inline TimeGridView<Real> time_grid_of(const DdhArgs<Real> &A, int s, const Real *filt, const Real *cs, const Real *sn,
+                                                      const TimeGrids<Real> &TG, const Rk4Scheme &)
+    {
+        return time_grid_of(A, s, filt, cs, sn, TG);
+    }
+
     // Issue priority of the calling wavefront (s_setprio).  All wavefronts of one rank's local solves are resident at once and
     // advance at the same rate, so a launch of the few subdomains whose traces other ranks wait for finishes no earlier than
     // the launch of all the others it shares the SIMDs with (profiles/r02/overlap_timeline.txt) -- unless its wavefronts are
@@ -227,7 +259,15 @@ namespace
     //         trace dofs: Hi[l] == 0 and its term is not computed;
     //   1:    their sources F[l], Gf[l] are zero as well (no x given: sources sit on trace dofs only) and are not computed either;
     //   2:    they are kept.
-    template <int LEAN = 0, unsigned INTERIOR = 1u, typename Real, int N, typename Sweep>
+    // SCHEME 1 (scheme_of: a plan with cuddh_hip_ddh_plan_set_integrator(plan, 1)): classical RK4 in place of the midpoint rule.
+    //   With y = (p, q) and f(t; p, q) = (-q, invm (S p - Hi q + c(t) F + s(t) Gf)), step it is
+    //       k1 = f(t[2 it - 2]; y),  k2 = f(t[2 it - 1]; y + dt/2 k1),  k3 = f(t[2 it - 1]; y + dt/2 k2),  k4 = f(t[2 it]; y + dt k3),
+    //       y += dt/6 (k1 + 2 k2 + 2 k3 + k4),
+    //   four sweeps per step; restart, filter accumulation and tables are those of RK2 (cs / sn hold every half step).  The
+    //   sum of the k is accumulated stage by stage (pa, qa), so a stage's slopes are not kept: per value two registers more than
+    //   RK2's loop.  The step size is folded into the per-dof constant in every form (e = (dt invm) r is dt times the slope
+    //   of q); LEAN's rules for the INTERIOR values hold as they do for RK2.
+    template <int LEAN = 0, unsigned INTERIOR = 1u, int SCHEME = 0, typename Real, int N, typename Sweep>
     __device__ inline void wh_march(const DdhArgs<Real> &A, const int nt, const Real dt, const Real *__restrict__ filt,
                                     const Real *__restrict__ cs, const Real *__restrict__ sn, const Real (&invm)[N], const Real (&Hi)[N], const Real (&F)[N],
                                     const Real (&Gf)[N], Real (&u)[N], Real (&v)[N], Sweep sweep)
@@ -237,8 +277,8 @@ namespace
         for (int l = 0; l < N; ++l)
             p[l] = q[l] = u[l] = v[l] = 0;
         const Real half_dt = Real(0.5) * dt;
-        Real hm[N], dm[N]; // LEAN: half_dt invm, dt invm
-        if constexpr (LEAN != 0)
+        Real hm[N], dm[N]; // LEAN: half_dt invm, dt invm;  RK4: dm alone
+        if constexpr (LEAN != 0 || SCHEME == 1)
         {
 #pragma unroll
             for (int l = 0; l < N; ++l)
@@ -260,6 +300,66 @@ namespace
                     v[l] *= k0;
                 }
             }
+            if constexpr (SCHEME == 1)
+            {
+                const Real sixth = Real(1) / Real(6), third = Real(1) / Real(3);
+                const Real sixth_dt = sixth * dt, third_dt = third * dt;
+                // r: what invm multiplies in the slope of q, for value l at the stage whose field gave z and whose q is qv
+#define CUDDH_RK4_RATE(zv, qv, c, s)                                                                                                              \
+    (dm[l] * ((LEAN != 0 && ((INTERIOR >> l) & 1u)) ? (LEAN == 2 ? zv[l] + c * F[l] + s * Gf[l] : zv[l])                                         \
+                                                    : (zv[l] - Hi[l] * qv[l]) + c * F[l] + s * Gf[l]))
+                for (int it = 1; it <= nt; ++it)
+                {
+                    const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                    const Real c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                    const Real c2 = cs[2 * it], s2 = sn[2 * it];
+                    const Real kw = filt[it];
+                    Real z[N], ps[N], qs[N], pa[N], qa[N];
+
+                    sweep(p, z);
+#pragma unroll
+                    for (int l = 0; l < N; ++l)
+                    {
+                        const Real e = CUDDH_RK4_RATE(z, q, c0, s0);
+                        pa[l] = p[l] - sixth_dt * q[l];
+                        qa[l] = q[l] + sixth * e;
+                        ps[l] = p[l] - half_dt * q[l];
+                        qs[l] = q[l] + Real(0.5) * e;
+                    }
+                    sweep(ps, z);
+#pragma unroll
+                    for (int l = 0; l < N; ++l)
+                    {
+                        const Real e = CUDDH_RK4_RATE(z, qs, c1, s1);
+                        pa[l] -= third_dt * qs[l];
+                        qa[l] += third * e;
+                        ps[l] = p[l] - half_dt * qs[l];
+                        qs[l] = q[l] + Real(0.5) * e;
+                    }
+                    sweep(ps, z);
+#pragma unroll
+                    for (int l = 0; l < N; ++l)
+                    {
+                        const Real e = CUDDH_RK4_RATE(z, qs, c1, s1);
+                        pa[l] -= third_dt * qs[l];
+                        qa[l] += third * e;
+                        ps[l] = p[l] - dt * qs[l];
+                        qs[l] = q[l] + e;
+                    }
+                    sweep(ps, z);
+#pragma unroll
+                    for (int l = 0; l < N; ++l)
+                    {
+                        const Real e = CUDDH_RK4_RATE(z, qs, c2, s2);
+                        p[l] = pa[l] - sixth_dt * qs[l];
+                        q[l] = qa[l] + sixth * e;
+                        u[l] += kw * p[l];
+                        v[l] += kw * q[l];
+                    }
+                }
+#undef CUDDH_RK4_RATE
+            }
+            else
             for (int it = 1; it <= nt; ++it)
             {
                 const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
@@ -598,11 +698,19 @@ namespace
         // and kernel 4 measured 0.5 % slower in three of three rounds against 0.1 % (profiles/r06/ddh_rates_ab.txt).  As it
         // stands all four instantiations compile to the previous assembly text, registers included.  Any change to wh_march
         // or publish_dof is made here as well (and, for wh_march, in ddh_general_wave_kernel).
+        // The RK4 form has no earlier commit to stay bitwise equal to: it is wh_march with the sweep as a callable.
         Real p[4], q[4];
 #pragma unroll
         for (int l = 0; l < 4; ++l)
             p[l] = q[l] = u[l] = v[l] = 0;
         const TimeGridView<Real> tg = time_grid_of(A, s, filt, cs, sn, grids...);
+        if constexpr (scheme_of<Grids...> == 1)
+        {
+            wh_march<0, 1u, 1>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, [&](const Real(&w)[4], Real(&z)[4])
+                               { wave_stiffness<VAR>(w, z, gx, gy, gz, Dk, DTk, Dmat, mR, mL, mU, mD, lane); });
+        }
+        else
+        {
         const Real dt = tg.dt, half_dt = Real(0.5) * tg.dt;
         const int nt = tg.nt;
 
@@ -645,6 +753,7 @@ namespace
                     v[l] += kw * q[l];
                 }
             }
+        }
         }
 
         const Real rw = Real(1) / A.omega;
@@ -1282,7 +1391,7 @@ namespace
             z[3] = c + mY * __shfl(c, pY, 64);
         };
         const TimeGridView<Real> tg = time_grid_of(A, s, filt, cs, sn, grids...);
-        wh_march<FORCED ? 2 : 1>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march<FORCED ? 2 : 1, 1u, scheme_of<Grids...>>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
 
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -1776,6 +1885,23 @@ namespace
         };
 
         const TimeGridView<Real> tg = time_grid_of(A, s, filt, cs, sn, grids...);
+        if constexpr (scheme_of<Grids...> == 1)
+        {
+            // RK4: wh_march on the thread's one value.  The sweep publishes the stage's field and is a workgroup phase like the
+            // loop below: every thread of the workgroup marches the same subdomain, so all run the same number of sweeps
+            const Real invm1[1] = {inv_mi}, Hi1[1] = {Hi}, F1[1] = {F}, G1[1] = {G};
+            Real u1[1], v1[1];
+            wh_march<0, 1u, 1>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm1, Hi1, F1, G1, u1, v1, [&](const Real(&w)[1], Real(&z)[1])
+                               {
+                                   s_p[tid] = w[0];
+                                   __syncthreads();
+                                   z[0] = sweep();
+                               });
+            u = u1[0];
+            v = v1[0];
+        }
+        else
+        {
         const Real dt = tg.dt, half_dt = Real(0.5) * tg.dt;
         const int nt = tg.nt;
         for (int whit = 0; whit < A.wh_iters; ++whit)
@@ -1805,6 +1931,7 @@ namespace
                 u += kw * p;
                 v += kw * q;
             }
+        }
         }
 
         v *= Real(1) / A.omega;
@@ -2171,6 +2298,14 @@ namespace
     // wavefront as well, at a size where this form measured slower on its own.
     constexpr int ELEMENT_LANE_MIN_DOMAINS = 8192;
 
+    // Which kernels have an RK4 form (cuddh_hip_ddh_plan_set_integrator).  Kernels 1, 2, 5 in the matrix form and 8 do.  RK4
+    // keeps two registers more per value than RK2 (wh_march); a form of the others is built only where it compiles without
+    // scratch and at the occupancy of its RK2 form, and none does ("Runge-Kutta 4", the table from the code
+    // objects): kernel 11 and kernel 5's element-lane form, sixteen values per lane, spill 216 to 236 bytes in the form without
+    // x, and kernels 3 and 4 go from 86 / 90 to 98 / 99 vector registers, five wavefronts per SIMD to four.  Kernels 6 and 7
+    // and the label-built plans' kernels 9 and 10 have none by decision.
+    constexpr bool has_rk4_form(int kernel) { return kernel == 1 || kernel == 2 || kernel == 5 || kernel == 8; }
+
     // the form a kernel-5 plan's launches take: 1 matrix, 2 element-lane (3 on request only: the last copy publishes).  A property of the plan alone, never of a launch:
     // differently partitioned launches of one plan are compared bitwise.
     int effective_sweep_form(const cuddh_ddh_plan *p)
@@ -2179,6 +2314,8 @@ namespace
             return 0;
         if (p->n_grids > 0)
             return 1; // the element-lane form holds four subdomains per wavefront: one time grid
+        if (p->rk4)
+            return 1; // no RK4 form of the element-lane kernel (has_rk4_form)
         if (p->sweep_form != 0)
             return p->sweep_form;
         return p->Sep4 && p->d.n_domains >= ELEMENT_LANE_MIN_DOMAINS ? 2 : 1;
@@ -2255,7 +2392,8 @@ namespace
     int launch_local_solves(const cuddh_ddh_plan *plan, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl,
                             const Real *cs, const Real *sn, Grids... grids)
     {
-        constexpr bool one_grid = sizeof...(Grids) == 0;
+        constexpr bool rk2_one_grid = sizeof...(Grids) == 0; // kernels 6, 7, 9, 10 and the element-lane form of 5 exist in this form alone
+        constexpr bool rk4 = scheme_of<Grids...> == 1;
         const cuddh_ddh_desc &d = plan->d;
         const dim3 grid((n_local + 3) / 4), block(256); // the wavefront kernels: four wavefronts per workgroup
         // kernels 3, 4, 7 and the folded-DPP form of 9 exist in fp32 only; fp64 always takes the plain form
@@ -2269,7 +2407,7 @@ namespace
                 return static_cast<int>(hipErrorInvalidValue);
             break;
         case 10:
-            if constexpr (one_grid)
+            if constexpr (rk2_one_grid)
             {
                 if (!launch_block<Real, true>(d.nb, A, n_local, st, D, fl, cs, sn))
                     return static_cast<int>(hipErrorInvalidValue);
@@ -2278,13 +2416,27 @@ namespace
             else
                 return static_cast<int>(hipErrorInvalidValue);
         case 2: hipLaunchKernelGGL((ddh_wave_kernel<Real, 0, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
-        case 3: hipLaunchKernelGGL((ddh_wave_kernel<Real, v3, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
-        case 4: hipLaunchKernelGGL((ddh_wave_kernel<Real, v4, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
+        case 3:
+            if constexpr (!rk4)
+            {
+                hipLaunchKernelGGL((ddh_wave_kernel<Real, v3, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...);
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
+        case 4:
+            if constexpr (!rk4)
+            {
+                hipLaunchKernelGGL((ddh_wave_kernel<Real, v4, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...);
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
         case 5:
         case 8:
             if ((plan->kernel == 5) != f32) // plan_create ties kernel 5 to fp32 (Aop) and kernel 8 to fp64 (Aop64)
                 return static_cast<int>(hipErrorInvalidValue);
-            if constexpr (f32 && one_grid)
+            if constexpr (f32 && rk2_one_grid)
                 if (const int form = effective_sweep_form(plan); form >= 2)
                 {
                     if (form == 3)
@@ -2297,7 +2449,7 @@ namespace
             break;
         case 6:
         case 7:
-            if constexpr (one_grid)
+            if constexpr (rk2_one_grid)
             {
                 const dim3 grid8((n_local + 7) / 8); // two subdomains per wavefront
                 if constexpr (f32)
@@ -2315,7 +2467,7 @@ namespace
             else
                 return static_cast<int>(hipErrorInvalidValue);
         case 9:
-            if constexpr (one_grid)
+            if constexpr (rk2_one_grid)
             {
                 hipLaunchKernelGGL((ddh_general_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn);
                 break;
@@ -2323,7 +2475,7 @@ namespace
             else
                 return static_cast<int>(hipErrorInvalidValue);
         case 11:
-            if constexpr (f32)
+            if constexpr (f32 && !rk4)
             {
                 if (!plan->Sep4) // plan_create ties kernel 11 to fp32 and its tables
                     return static_cast<int>(hipErrorInvalidValue);
@@ -2404,9 +2556,17 @@ namespace
 
         const Real *D = static_cast<const Real *>(d.D);
         if (plan->n_grids > 0) // every subdomain on its own grid: the plan's concatenated tables
-            return launch_local_solves(plan, A, n_local, st, D, static_cast<const Real *>(plan->grid_filter), static_cast<const Real *>(plan->grid_cs),
-                                       static_cast<const Real *>(plan->grid_sn),
-                                       TimeGrids<Real>{plan->grid_of, static_cast<const DdhTimeGrid<Real> *>(plan->grids)});
+        {
+            const Real *fl = static_cast<const Real *>(plan->grid_filter), *cs = static_cast<const Real *>(plan->grid_cs),
+                       *sn = static_cast<const Real *>(plan->grid_sn);
+            const TimeGrids<Real> TG{plan->grid_of, static_cast<const DdhTimeGrid<Real> *>(plan->grids)};
+            if (plan->rk4)
+                return launch_local_solves(plan, A, n_local, st, D, fl, cs, sn, TG, Rk4Scheme{});
+            return launch_local_solves(plan, A, n_local, st, D, fl, cs, sn, TG);
+        }
+        if (plan->rk4)
+            return launch_local_solves(plan, A, n_local, st, D, static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs),
+                                       static_cast<const Real *>(d.sn), Rk4Scheme{});
         return launch_local_solves(plan, A, n_local, st, D, static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs),
                                    static_cast<const Real *>(d.sn));
     }
@@ -2719,7 +2879,7 @@ extern "C"
     {
         if (!plan || form < 0 || form > 3)
             return static_cast<int>(hipErrorInvalidValue);
-        if (form >= 2 && (plan->kernel != 5 || !plan->Sep4 || plan->n_grids > 0))
+        if (form >= 2 && (plan->kernel != 5 || !plan->Sep4 || plan->n_grids > 0 || plan->rk4))
             return static_cast<int>(hipErrorInvalidValue);
         plan->sweep_form = form;
         return 0;
@@ -2820,6 +2980,32 @@ extern "C"
     }
 
     int cuddh_hip_ddh_plan_time_grids(const cuddh_ddh_plan *plan) { return plan ? plan->n_grids : 0; }
+
+    int cuddh_hip_ddh_plan_set_integrator(cuddh_ddh_plan *plan, int scheme)
+    {
+        if (!plan || scheme < 0 || scheme > 1)
+            return static_cast<int>(hipErrorInvalidValue);
+        if (scheme == 0)
+        {
+            plan->rk4 = 0; // what auto moved off a kernel stays moved: results depend on the scheme, not on the kernel
+            return 0;
+        }
+        // No RK4 form (has_rk4_form): a request is refused, and so is a label-built plan; an auto choice moves to the kernel of
+        // its block size that has one: 3 to 2 (the same lane map without the folded DPP reads), 6, 7 and 11 to 1, and a
+        // kernel-5 plan takes the matrix form whatever its size (effective_sweep_form).
+        if (plan->kernel == 9 || plan->kernel == 10 || (plan->kernel == 5 && plan->sweep_form >= 2))
+            return static_cast<int>(hipErrorInvalidValue);
+        if (!has_rk4_form(plan->kernel))
+        {
+            if (plan->requested != 0)
+                return static_cast<int>(hipErrorInvalidValue);
+            plan->kernel = plan->kernel == 3 ? 2 : 1;
+        }
+        plan->rk4 = 1;
+        return 0;
+    }
+
+    int cuddh_hip_ddh_plan_integrator(const cuddh_ddh_plan *plan) { return plan ? plan->rk4 : 0; }
 
     int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last)
     {

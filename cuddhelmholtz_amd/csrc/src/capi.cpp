@@ -692,6 +692,50 @@ extern "C"
             return h;
         });
     }
+    void *cuddh_ddh_create_integrator(double omega, const double *h_a, void *fem, int nx, int ny, int block, int f64, int kernel, int policy,
+                                      const int *h_ratios, int n_ratios, int integrator, int coarsen)
+    {
+        return guarded_new<DdhHandle>([&]
+        {
+            if (integrator < 0 || integrator > 1)
+                cuddh_error("DDH error: integrator: must be 0 (rk2) or 1 (rk4).");
+            if (policy < 0 || policy > 2)
+                cuddh_error("DDH error: time step: policy must be 0 (mesh), 1 (coefficient) or 2 (ratios).");
+            const DDHTimeStep ts = policy == 2   ? DDHTimeStep::from_ratios(h_ratios, n_ratios)
+                                   : policy == 1 ? DDHTimeStep::from_coefficient()
+                                                 : DDHTimeStep::from_mesh();
+            DDHIntegrator ig;
+            ig.scheme = integrator == 1 ? DDHIntegrator::rk4 : DDHIntegrator::rk2;
+            ig.coarsen = coarsen;
+            auto h = new DdhHandle;
+            const H1Space &f = *static_cast<H1Space *>(fem);
+            try
+            {
+                if (f64)
+                    h->f64.reset(new DDH64(omega, h_a, f, nx, ny, kernel, block, ts, ig));
+                else
+                    h->f32.reset(new DDH(omega, h_a, f, nx, ny, kernel, block, ts, ig));
+            }
+            catch (...)
+            {
+                delete h;
+                throw;
+            }
+            return h;
+        });
+    }
+    int cuddh_ddh_integrator(void *d, int *scheme, int *coarsen)
+    {
+        return guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            const DDHIntegrator ig = h->is64() ? h->f64->internals().integrator() : h->f32->internals().integrator();
+            if (scheme)
+                *scheme = ig.scheme == DDHIntegrator::rk4 ? 1 : 0;
+            if (coarsen)
+                *coarsen = ig.coarsen;
+        });
+    }
     int cuddh_ddh_time_ratios(void *d, int *h_out)
     {
         int n = -1;

@@ -94,11 +94,15 @@ namespace cuddh
             host_device_ivec grid_of;
             HostDeviceArray<Real> grid_filter, grid_cs, grid_sn;
 
+            DDHIntegrator integrator;                            // rk4: nt_mesh is the coarsened count, ceil(mesh grid's / coarsen)
+
             explicit More(const Basis *basis) : fem_basis(basis) {}
         };
 
         template <typename Real>
         int DDHCore<Real>::mesh_steps() const { return more->nt_mesh; }
+        template <typename Real>
+        DDHIntegrator DDHCore<Real>::integrator() const { return more->integrator; }
         template <typename Real>
         const std::vector<int> &DDHCore<Real>::time_ratios() const { return more->ratios; }
         template <typename Real>
@@ -165,6 +169,35 @@ namespace cuddh
             check_time_step(time_step, h_a, g_ndof, (nx / nel1d) * (ny / nel1d));
             setup_blocks(h_a, fem, nx, ny, time_step);
             requested_kernel = kernel;
+        }
+
+        template <typename Real>
+        DDHCore<Real>::DDHCore(double omega_, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block,
+                               const DDHTimeStep &time_step, const DDHIntegrator &integrator)
+            : g_ndof(fem.size()), g_elem(fem.mesh().n_elem()), n_basis(fem.basis().size()), omega(omega_), fem_mesh(&fem.mesh()),
+              more(new More(&fem.basis()))
+        {
+            // the integrator's checks first, then those of the constructor above: all on the host
+            set_integrator(integrator);
+            set_block(nx, ny, block);
+            if (nx * ny != g_elem)
+                cuddh_error("DDH error: nx * ny does not match the mesh.");
+            check_time_step(time_step, h_a, g_ndof, (nx / nel1d) * (ny / nel1d));
+            setup_blocks(h_a, fem, nx, ny, time_step);
+            requested_kernel = kernel;
+        }
+
+        template <typename Real>
+        void DDHCore<Real>::set_integrator(const DDHIntegrator &integrator)
+        {
+            if (integrator.scheme != DDHIntegrator::rk2 && integrator.scheme != DDHIntegrator::rk4)
+                cuddh_error("DDH error: integrator: the scheme must be rk2 or rk4.");
+            if (integrator.coarsen < 1 || integrator.coarsen > DDHIntegrator::max_coarsen)
+                cuddh_error(("DDH error: integrator: coarsen = " + std::to_string(integrator.coarsen) + " is outside [1, " +
+                             std::to_string(DDHIntegrator::max_coarsen) + "].").c_str());
+            if (integrator.scheme == DDHIntegrator::rk2 && integrator.coarsen != 1)
+                cuddh_error("DDH error: integrator: rk2 marches on the mesh grid (coarsen = 1) only; a coarser grid needs rk4.");
+            more->integrator = integrator;
         }
 
         template <typename Real>
@@ -240,6 +273,9 @@ namespace cuddh
             const double h = fem.mesh().min_h();
             dt = 0.2 * 0.5 * h / (nb * nb);
             nt = nt_mesh = static_cast<int>(std::ceil(T / dt));
+            // RK4 on a coarser grid: ceil(nt_mesh / coarsen) steps are the base grid, and what the ratios below multiply
+            if (const int c = more->integrator.coarsen; c > 1)
+                nt = nt_mesh = (nt_mesh + c - 1) / c;
 
             // ---- steps of subdomain s = ratios[s] * nt_mesh
             ratios.assign(n_domains, 1);
@@ -621,6 +657,16 @@ namespace cuddh
                 check_hip(cuddh_hip_ddh_plan_create_general(&plan, &d, mx_elem_per_dom, is_f64, requested_kernel), "DDH plan");
             else
                 check_hip(cuddh_hip_ddh_plan_create(&plan, &d, is_f64, requested_kernel), "DDH plan");
+            if (more->integrator.scheme == DDHIntegrator::rk4)
+            {
+                const int err = cuddh_hip_ddh_plan_set_integrator(plan, 1);
+                if (err) // never a plan that would step with RK2 instead
+                {
+                    cuddh_hip_ddh_plan_destroy(plan);
+                    plan = nullptr;
+                }
+                check_hip(err, "DDH integrator (the requested kernel has no RK4 form?)");
+            }
             if (per_subdomain)
             {
                 std::vector<int> h_nt;
@@ -814,6 +860,12 @@ namespace cuddh
     {
     }
 
+    DDH::DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step,
+             const DDHIntegrator &integrator)
+        : core(omega, h_a, fem, nx, ny, kernel, block, time_step, integrator)
+    {
+    }
+
     DDH::DDH(from_labels_t tag, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel)
         : core(tag, omega, h_a, fem, n_domains, labels, kernel)
     {
@@ -856,6 +908,12 @@ namespace cuddh
 
     DDH64::DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step)
         : core(omega, h_a, fem, nx, ny, kernel, block, time_step)
+    {
+    }
+
+    DDH64::DDH64(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step,
+                 const DDHIntegrator &integrator)
+        : core(omega, h_a, fem, nx, ny, kernel, block, time_step, integrator)
     {
     }
 

@@ -136,6 +136,17 @@ void *cuddh_ddh_create_labels(double omega, const double *h_a, void *fem, int n_
  * reporting the base grid (the mesh grid, or the one grid of policy 1 with one ratio). */
 void *cuddh_ddh_create_timegrid(double omega, const double *h_a, void *fem, int nx, int ny, int block, int f64, int kernel, int policy,
                                 const int *h_ratios, int n_ratios);
+/* cuddh_ddh_create_timegrid with an integrator (cuddh::DDHIntegrator): integrator 0 = RK2 on the mesh grid (coarsen must be 1:
+ * cuddh_ddh_create_timegrid itself), 1 = classical RK4 on the base grid of ceil(nt_mesh / coarsen) steps, coarsen in [1, 16];
+ * the ratios of `policy` multiply that count.  With a == 1 RK4 is stable up to coarsen ~ 23; the range scales with min a over
+ * a subdomain unless policy 1 compensates (a = 0.2 under policy 0: coarsen <= 4).  cuddh_ddh_info and cuddh_ddh_table report the
+ * coarsened grid.  An unknown integrator, a coarsen outside [1, 16] and coarsen > 1 with RK2 are refused before anything is
+ * allocated (NULL + cuddh_last_error, the message starts with "DDH error: integrator"); a kernel without an RK4 form (3, 4, 6,
+ * 7, 11 on request) fails on first use. */
+void *cuddh_ddh_create_integrator(double omega, const double *h_a, void *fem, int nx, int ny, int block, int f64, int kernel, int policy,
+                                  const int *h_ratios, int n_ratios, int integrator, int coarsen);
+/* *scheme = 0 (RK2) or 1 (RK4), *coarsen = the factor in effect.  Returns 0, -1 on error. */
+int cuddh_ddh_integrator(void *ddh, int *scheme, int *coarsen);
 /* h_out HOST (n_domains) or NULL: r_s of every subdomain (all 1 for the mesh grid).  Returns n_domains, -1 on error. */
 int cuddh_ddh_time_ratios(void *ddh, int *h_out);
 void cuddh_ddh_destroy(void *ddh);

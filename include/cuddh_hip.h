@@ -388,6 +388,23 @@ int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last);
 int cuddh_hip_ddh_plan_set_time_grids(cuddh_ddh_plan *plan, int n_grids, const int *h_nt, const double *h_dt, const void *filter,
                                       const void *cs, const void *sn, const int *d_grid_of);
 int cuddh_hip_ddh_plan_time_grids(const cuddh_ddh_plan *plan);
+/* The integrator of the local solves: scheme 0 = the explicit midpoint rule (RK2, two stiffness sweeps per step; the default, the
+ * reference's), 1 = classical RK4, four sweeps per step:
+ *     y = (p, q),  f(t; p, q) = (-q, invm (S p - Hi q + c(t) F + s(t) Gf)),
+ *     k1 = f(t_{it-1}; y), k2 = f(t_{it-1/2}; y + dt/2 k1), k3 = f(t_{it-1/2}; y + dt/2 k2), k4 = f(t_it; y + dt k3),
+ *     y += dt/6 (k1 + 2 k2 + 2 k3 + k4),  then the filter sums as for RK2.
+ * Restart, filter, tables (cs / sn hold every half step), load and publish, wh_iters, priority, lists and ranges and
+ * per-subdomain time grids are those of RK2.  The grid is whatever the descriptor (or cuddh_hip_ddh_plan_set_time_grids) holds:
+ * RK4 is meant for a grid 2 to 16 times coarser than the mesh grid RK2 needs; the caller builds that grid.
+ * RK4 forms exist of kernels 1, 2, 5 (matrix form) and 8 (instantiations of their own; an RK2 plan launches the code it did
+ * before).  Like cuddh_hip_ddh_plan_set_time_grids this moves an auto choice and never a request: a plan that auto resolved
+ * to kernel 3 becomes kernel 2, one that resolved to 6, 7 or 11 becomes kernel 1, a kernel-5 plan takes the matrix form
+ * whatever its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan created with kernel 3, 4, 6, 7 or 11 on
+ * request, one with sweep form 2 or 3 set, and a general plan (kernels 9, 10) are refused with hipErrorInvalidValue and stay
+ * RK2 plans.  No launch of an RK4 plan ever runs RK2 code: a kernel without an RK4 form returns hipErrorInvalidValue.
+ * cuddh_hip_ddh_plan_integrator returns the scheme in effect. */
+int cuddh_hip_ddh_plan_set_integrator(cuddh_ddh_plan *plan, int scheme);
+int cuddh_hip_ddh_plan_integrator(const cuddh_ddh_plan *plan);
 
 /* source/DDH.cpp:111-321 (ddh_action + stiffness).  x: forcing [F;G] (2*g_ndof
  * doubles) or NULL; y: solution output [u;v] (2*g_ndof doubles, zero-filled by

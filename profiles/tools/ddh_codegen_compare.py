@@ -25,7 +25,7 @@ RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, 
                           for real in ("float", "double") for nb in range(2, 11) for csr in ("false", "true")}}}
 # instantiations that are another one plus a template argument, per file: pattern removed from the demangled name gives the base.
 # A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
-DERIVED = {"ddh.hip": r", TimeGrids<\w+> ?(?=>)"}
+DERIVED = {"ddh.hip": r", Rk4Scheme ?(?=>)|, TimeGrids<\w+> ?(?=>)"}
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
