@@ -245,6 +245,7 @@ _sig("cuddh_nodal_values", ci, vp, ci, cd, vp)
 _sig("cuddh_ddh_create", vp, cd, vp, vp, ci, ci, ci, ci)
 _sig("cuddh_ddh_create_block", vp, cd, vp, vp, ci, ci, ci, ci, ci)
 _sig("cuddh_ddh_create_labels", vp, cd, vp, vp, ci, vp, ci, ci)
+_sig("cuddh_ddh_create_labels_integrator", vp, cd, vp, vp, ci, vp, ci, ci, ci, vp, ci, ci, ci)
 _sig("cuddh_ddh_create_timegrid", vp, cd, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci)
 _sig("cuddh_ddh_time_ratios", ci, vp, vp)
 _sig("cuddh_ddh_create_integrator", vp, cd, vp, vp, ci, ci, ci, ci, ci, ci, vp, ci, ci, ci)

@@ -435,8 +435,8 @@ class DDH:
     returns ("rk4", 4).  The mesh grid is as fine as it is for the midpoint rule's stability, not for accuracy: RK4 at coarsen 4
     is closer to the exact local solve than RK2 on the mesh grid, in half the sweeps.  Stable range: with
     a == 1 it ends near coarsen 23 (hence the cap of 16); it scales with min a over a subdomain unless
-    time_step="coefficient" compensates: with a = 0.2 under "mesh", coarsen <= 4.  Kernels 1, 2, 5 (matrix form) and 8 have an
-    RK4 form; auto picks among them (info()["kernel"]), any other kernel on request raises RuntimeError on first use.  A bad
+    time_step="coefficient" compensates: with a = 0.2 under "mesh", coarsen <= 4.  Kernels 1, 2, 5 (matrix form) and 8 (and
+    from_labels' 9 and 10) have an RK4 form; auto picks among them (info()["kernel"]), any other kernel on request raises RuntimeError on first use.  A bad
     name, a coarsen that is no integer in [1, 16] and coarsen > 1 with "rk2" raise ValueError here."""
 
     _INT_TABLES = ("B", "gI", "sI")
@@ -500,14 +500,30 @@ class DDH:
 
     @classmethod
     def from_labels(cls, omega: float, h_a: np.ndarray, fem: H1Space, labels, precision: str = "f32", kernel: int = 0,
-                    time_step="mesh") -> "DDH":
+                    time_step="mesh", integrator: str = "rk2", coarsen: int | None = None, time_ratios=None) -> "DDH":
         """DDH on any mesh with subdomain s = the elements labelled s (one label per element, e.g. Mesh2D.partition), labels in
         [0, n_domains) with n_domains = max(labels) + 1; every subdomain non-empty with at most 256 element nodes.
         kernel: 0 auto, 9 one wavefront per subdomain (n_basis 4, <= 16 elements per subdomain), 10 one workgroup per
         subdomain.  info()["nel1d"] is 0.  Invalid labels or kernels raise here, before anything runs on the device.
-        Subdomains from labels march on the mesh grid: any other time_step raises ValueError."""
+        integrator, coarsen: as in DDH(...), with the same ValueErrors; kernels 9 and 10 both have an RK4 form, so auto picks
+        as it does for RK2.
+        time_ratios: the per-subdomain time grids of DDH(..., time_step=).  None: every subdomain on the base grid;
+        "coefficient": r_s = max(1, ceil((1 - 1e-9) / min a over the subdomain's dofs)); or a one-dimensional integer array,
+        one ratio in [1, 256] per label.  A bad array, the wrong length, another name and a non-finite or non-positive a under
+        "coefficient" raise ValueError.  time_ratios(), integrator(), info() and table("filter@r") work as on block plans.
+        time_step accepts "mesh" alone and raises ValueError for anything else, as it always has here, which is why the
+        per-subdomain policy has a keyword of its own."""
         if not (isinstance(time_step, str) and time_step == "mesh"):
-            raise ValueError("DDH.from_labels: subdomains from labels take their time step from the mesh (time_step='mesh') only")
+            raise ValueError("DDH.from_labels: time_step is 'mesh' only; per-subdomain time grids are time_ratios='coefficient' or an integer array")
+        scheme, coarsen = cls._integrator(integrator, coarsen)
+        if time_ratios is None:
+            policy, ratios = 0, None
+        elif isinstance(time_ratios, str):
+            if time_ratios != "coefficient":
+                raise ValueError(f"DDH.from_labels: time_ratios must be None, 'coefficient' or an integer array, not {time_ratios!r}")
+            policy, ratios = 1, None
+        else:
+            policy, ratios = cls._time_step_policy(time_ratios)
         labels = np.ascontiguousarray(labels)
         n_elem = fem.mesh.n_elem()
         if labels.ndim != 1 or labels.size != n_elem:
@@ -522,8 +538,18 @@ class DDH:
         self.fem = fem
         self.f64 = precision == "f64"
         h_a = np.ascontiguousarray(h_a, dtype=np.float64)
-        self._h = N.handle(lib.cuddh_ddh_create_labels(float(omega), _h(h_a), fem._h, n_domains, _h(labels), int(self.f64), int(kernel)),
-                           "DDH.from_labels")
+        if scheme == 0 and policy == 0:
+            self._h = N.handle(lib.cuddh_ddh_create_labels(float(omega), _h(h_a), fem._h, n_domains, _h(labels), int(self.f64), int(kernel)),
+                               "DDH.from_labels")
+        else:
+            if ratios is not None and ratios.size != n_domains:
+                raise ValueError(f"DDH.from_labels: {ratios.size} time_ratios for {n_domains} subdomains")
+            h = lib.cuddh_ddh_create_labels_integrator(float(omega), _h(h_a), fem._h, n_domains, _h(labels), int(self.f64), int(kernel), policy,
+                                                       None if ratios is None else _h(ratios), 0 if ratios is None else int(ratios.size),
+                                                       scheme, coarsen)
+            if not h and N.last_error().startswith(("DDH error: time step", "DDH error: integrator")):
+                raise ValueError(f"DDH.from_labels: {N.last_error()}")
+            self._h = N.handle(h, "DDH.from_labels")
         self.omega = float(omega)
         return self
 

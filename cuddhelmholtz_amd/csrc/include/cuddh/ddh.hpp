@@ -31,7 +31,7 @@ namespace cuddh
     };
     inline constexpr from_labels_t from_labels{};
 
-    /// Where the local solves take their time step from (block-grid constructors; subdomains from labels march on the mesh grid).
+    /// Where the local solves take their time step from (block-grid constructors, and the label constructors that take one).
     /// The mesh grid is the reference's: dt = 0.1 h / n_basis^2 shrunk so that nt steps are one period, whatever the
     /// coefficient.  The wave speed is 1 / a, so where a < 1 that step is too long for the explicit time stepping.
     /// Subdomain s may instead march r_s nt steps of dt / r_s, r_s an integer >= 1: local solves couple through the traces
@@ -54,7 +54,7 @@ namespace cuddh
         static DDHTimeStep from_ratios(const int *h_ratios, int n) { return {ratios, h_ratios, n}; }
     };
 
-    /// How the local solves step in time, and on how coarse a grid (block-grid constructors).
+    /// How the local solves step in time, and on how coarse a grid (block-grid constructors, and the label constructors that take one).
     /// rk2: the reference's explicit midpoint rule on the reference's grid, two stiffness sweeps per step; the default.
     /// rk4: classical Runge-Kutta, four sweeps per step, on a base grid of ceil(nt_mesh / coarsen) steps, nt_mesh the mesh
     /// grid's; a DDHTimeStep ratio r_s multiplies that count as it multiplies the mesh grid's.  The mesh grid is as fine as it
@@ -100,6 +100,11 @@ namespace cuddh
             /// subdomain s = the elements with label s (HOST, one per element, in [0, n_domains)); any connectivity.
             /// kernel: 0 auto, 9 or 10 (cuddh_hip_ddh_plan_create_general)
             DDHCore(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel);
+            /// the same with a time-step policy and an integrator, which mean what they mean on the block grid (ratios: one per
+            /// label).  Checked in this order, on the host, before any allocation or launch: the integrator, the labels, the policy.
+            /// Kernels 9 and 10 both have every form, so nothing about the kernel is refused that the constructor above accepts.
+            DDHCore(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel,
+                    const DDHTimeStep &time_step, const DDHIntegrator &integrator);
             ~DDHCore();
 
             int n_traces() const { return 2 * n_lambda; }
@@ -227,6 +232,10 @@ namespace cuddh
         /// every subdomain non-empty and with at most 256 element nodes).  kernel: 0 auto, 9 one wavefront per subdomain
         /// (n_basis 4, <= 16 elements per subdomain), 10 one workgroup per subdomain.  Invalid labels throw here.
         DDH(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel = 0);
+        /// extension: the same with a time-step policy (ratios: one per label) and an integrator; the constructor above is
+        /// DDHTimeStep::from_mesh() and RK2
+        DDH(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel,
+            const DDHTimeStep &time_step, const DDHIntegrator &integrator);
         ~DDH() = default;
 
         /// dimension of the substructured problem
@@ -260,6 +269,8 @@ namespace cuddh
               const DDHIntegrator &integrator);
         /// subdomains from element labels, as DDH(from_labels, ...)
         DDH64(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel = 0);
+        DDH64(from_labels_t, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel,
+              const DDHTimeStep &time_step, const DDHIntegrator &integrator);
 
         int size() const { return core.n_traces(); }
 

@@ -838,9 +838,9 @@ namespace
             z[l] = s_d[dof[l]];
     }
 
-    template <typename Real, int VAR>
+    template <typename Real, int VAR, typename... Grids>
     __global__ void __launch_bounds__(256) ddh_general_wave_kernel(DdhArgs<Real> A, const Real *__restrict__ Dmat, const Real *__restrict__ filt,
-                                                                  const Real *__restrict__ cs, const Real *__restrict__ sn)
+                                                                  const Real *__restrict__ cs, const Real *__restrict__ sn, Grids... grids)
     {
         __shared__ Real lds_c[4][GW_NODES], lds_d[4][GW_NODES];
         __shared__ int lds_src[4][GW_NODES];
@@ -848,7 +848,7 @@ namespace
         const int position = A.dom_begin + blockIdx.x * 4 + wave;
         if (position >= A.dom_end)
             return; // wave-uniform: the kernel has no workgroup barriers
-        const int s = domain_at(A, position);
+        const int s = domain_at(A, position, grids...);
         raise_priority(A.prio);
         Real *s_c = lds_c[wave], *s_d = lds_d[wave];
         int *s_src = lds_src[wave];
@@ -911,13 +911,28 @@ namespace
         // profiles/r06/ddh_bitwise_vs_parent.txt).  Writing the FMA out in wave_element_stiffness does not settle it: the form
         // the compiler picks here is not the one it picks for ddh_wave_kernel, so one explicit form moves one of the two.
         // Any change to wh_march is made here and in ddh_wave_kernel as well.
-        const Real dt = A.dt, half_dt = Real(0.5) * A.dt;
-        const int nt = A.nt;
+        // The RK4 form has no earlier commit to stay bitwise equal to: it is wh_march with the sweep as a callable.  The
+        // wavefronts of a workgroup may run different step counts (time grids): the LDS is wave-private and nothing here
+        // is a workgroup barrier.
+        const TimeGridView<Real> tg = time_grid_of(A, s, filt, cs, sn, grids...);
+        if constexpr (scheme_of<Grids...> == 1)
+        {
+            wh_march<0, 1u, 1>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, [&](const Real(&w)[4], Real(&z)[4])
+                               {
+                                   Real zz[4];
+                                   wave_element_stiffness<VAR>(w, zz, gx, gy, gz, Dk, DTk, Dmat);
+                                   gw_assemble(zz, z, s_c, s_d, s_src, st, ct, dof, lane);
+                               });
+        }
+        else
+        {
+        const Real dt = tg.dt, half_dt = Real(0.5) * tg.dt;
+        const int nt = tg.nt;
 
         for (int whit = 0; whit < A.wh_iters; ++whit)
         {
             {
-                const Real k0 = filt[0];
+                const Real k0 = tg.filt[0];
 #pragma unroll
                 for (int l = 0; l < 4; ++l)
                 {
@@ -929,9 +944,9 @@ namespace
             }
             for (int it = 1; it <= nt; ++it)
             {
-                const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
-                const Real c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
-                const Real kw = filt[it];
+                const Real c0 = tg.cs[2 * it - 2], s0 = tg.sn[2 * it - 2];
+                const Real c1 = tg.cs[2 * it - 1], s1 = tg.sn[2 * it - 1];
+                const Real kw = tg.filt[it];
                 Real zz[4], z[4], ph[4], qh[4];
 
                 wave_element_stiffness<VAR>(p, zz, gx, gy, gz, Dk, DTk, Dmat);
@@ -955,6 +970,7 @@ namespace
                     v[l] += kw * q[l];
                 }
             }
+        }
         }
 
         // outputs per dof: the copy at the dof's first contributing element node publishes u, v
@@ -2303,8 +2319,9 @@ namespace
     // scratch and at the occupancy of its RK2 form, and none does ("Runge-Kutta 4", the table from the code
     // objects): kernel 11 and kernel 5's element-lane form, sixteen values per lane, spill 216 to 236 bytes in the form without
     // x, and kernels 3 and 4 go from 86 / 90 to 98 / 99 vector registers, five wavefronts per SIMD to four.  Kernels 6 and 7
-    // and the label-built plans' kernels 9 and 10 have none by decision.
-    constexpr bool has_rk4_form(int kernel) { return kernel == 1 || kernel == 2 || kernel == 5 || kernel == 8; }
+    // have none by decision.  The label-built plans' kernels 9 (wh_march around its LDS assembly, no scratch) and 10 (kernel 1's
+    // form with the plan's lists) have one.
+    constexpr bool has_rk4_form(int kernel) { return kernel == 1 || kernel == 2 || kernel == 5 || kernel == 8 || kernel == 9 || kernel == 10; }
 
     // the form a kernel-5 plan's launches take: 1 matrix, 2 element-lane (3 on request only: the last copy publishes).  A property of the plan alone, never of a launch:
     // differently partitioned launches of one plan are compared bitwise.
@@ -2387,12 +2404,12 @@ namespace
 
     // The plan's kernel for one launch.  grids: nothing (one time grid, fl / cs / sn are the descriptor's tables) or the plan's
     // TimeGrids (fl / cs / sn are then the concatenated per-grid tables); the kernels that hold several subdomains per
-    // wavefront, and the label-built plans' kernels, exist for one grid only.
+    // wavefront exist for one grid only.
     template <typename Real, typename... Grids>
     int launch_local_solves(const cuddh_ddh_plan *plan, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl,
                             const Real *cs, const Real *sn, Grids... grids)
     {
-        constexpr bool rk2_one_grid = sizeof...(Grids) == 0; // kernels 6, 7, 9, 10 and the element-lane form of 5 exist in this form alone
+        constexpr bool rk2_one_grid = sizeof...(Grids) == 0; // kernels 6, 7 and the element-lane form of 5 exist in this form alone
         constexpr bool rk4 = scheme_of<Grids...> == 1;
         const cuddh_ddh_desc &d = plan->d;
         const dim3 grid((n_local + 3) / 4), block(256); // the wavefront kernels: four wavefronts per workgroup
@@ -2407,14 +2424,9 @@ namespace
                 return static_cast<int>(hipErrorInvalidValue);
             break;
         case 10:
-            if constexpr (rk2_one_grid)
-            {
-                if (!launch_block<Real, true>(d.nb, A, n_local, st, D, fl, cs, sn))
-                    return static_cast<int>(hipErrorInvalidValue);
-                break;
-            }
-            else
+            if (!launch_block<Real, true>(d.nb, A, n_local, st, D, fl, cs, sn, grids...))
                 return static_cast<int>(hipErrorInvalidValue);
+            break;
         case 2: hipLaunchKernelGGL((ddh_wave_kernel<Real, 0, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
         case 3:
             if constexpr (!rk4)
@@ -2466,14 +2478,7 @@ namespace
             }
             else
                 return static_cast<int>(hipErrorInvalidValue);
-        case 9:
-            if constexpr (rk2_one_grid)
-            {
-                hipLaunchKernelGGL((ddh_general_wave_kernel<Real, v3>), grid, block, 0, st, A, D, fl, cs, sn);
-                break;
-            }
-            else
-                return static_cast<int>(hipErrorInvalidValue);
+        case 9: hipLaunchKernelGGL((ddh_general_wave_kernel<Real, v3, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
         case 11:
             if constexpr (f32 && !rk4)
             {
@@ -2892,9 +2897,10 @@ extern "C"
     {
         if (!plan || n_grids < 1 || !h_nt || !h_dt || !filter || !cs || !sn || !d_grid_of)
             return static_cast<int>(hipErrorInvalidValue);
-        // label-built plans (kernels 9, 10) and the element-lane forms on request have one grid; so have kernels 6 and 7, which
-        // hold two subdomains per wavefront: chosen by auto they give way to kernel 1, requested they are refused
-        if (plan->kernel == 9 || plan->kernel == 10 || plan->sweep_form >= 2)
+        // the element-lane forms on request have one grid; so have kernels 6 and 7, which hold two subdomains per wavefront:
+        // chosen by auto they give way to kernel 1, requested they are refused.  The label-built plans' kernels 9 and 10 hold
+        // one subdomain per wavefront / workgroup and take the grids as they are.
+        if (plan->sweep_form >= 2)
             return static_cast<int>(hipErrorInvalidValue);
         if ((plan->kernel == 6 || plan->kernel == 7) && plan->requested != 0)
             return static_cast<int>(hipErrorInvalidValue);
@@ -2990,10 +2996,11 @@ extern "C"
             plan->rk4 = 0; // what auto moved off a kernel stays moved: results depend on the scheme, not on the kernel
             return 0;
         }
-        // No RK4 form (has_rk4_form): a request is refused, and so is a label-built plan; an auto choice moves to the kernel of
+        // No RK4 form (has_rk4_form): a request is refused; an auto choice moves to the kernel of
         // its block size that has one: 3 to 2 (the same lane map without the folded DPP reads), 6, 7 and 11 to 1, and a
-        // kernel-5 plan takes the matrix form whatever its size (effective_sweep_form).
-        if (plan->kernel == 9 || plan->kernel == 10 || (plan->kernel == 5 && plan->sweep_form >= 2))
+        // kernel-5 plan takes the matrix form whatever its size (effective_sweep_form).  A label-built plan keeps its kernel:
+        // 9 and 10 both have the form.
+        if (plan->kernel == 5 && plan->sweep_form >= 2)
             return static_cast<int>(hipErrorInvalidValue);
         if (!has_rk4_form(plan->kernel))
         {

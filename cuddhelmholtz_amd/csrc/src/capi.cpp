@@ -665,6 +665,38 @@ extern "C"
             return h;
         });
     }
+    void *cuddh_ddh_create_labels_integrator(double omega, const double *h_a, void *fem, int n_domains, const int *h_labels, int f64, int kernel,
+                                             int policy, const int *h_ratios, int n_ratios, int integrator, int coarsen)
+    {
+        return guarded_new<DdhHandle>([&]
+        {
+            if (integrator < 0 || integrator > 1)
+                cuddh_error("DDH error: integrator: must be 0 (rk2) or 1 (rk4).");
+            if (policy < 0 || policy > 2)
+                cuddh_error("DDH error: time step: policy must be 0 (mesh), 1 (coefficient) or 2 (ratios).");
+            const DDHTimeStep ts = policy == 2   ? DDHTimeStep::from_ratios(h_ratios, n_ratios)
+                                   : policy == 1 ? DDHTimeStep::from_coefficient()
+                                                 : DDHTimeStep::from_mesh();
+            DDHIntegrator ig;
+            ig.scheme = integrator == 1 ? DDHIntegrator::rk4 : DDHIntegrator::rk2;
+            ig.coarsen = coarsen;
+            auto h = new DdhHandle;
+            const H1Space &f = *static_cast<H1Space *>(fem);
+            try
+            {
+                if (f64)
+                    h->f64.reset(new DDH64(from_labels, omega, h_a, f, n_domains, h_labels, kernel, ts, ig));
+                else
+                    h->f32.reset(new DDH(from_labels, omega, h_a, f, n_domains, h_labels, kernel, ts, ig));
+            }
+            catch (...)
+            {
+                delete h;
+                throw;
+            }
+            return h;
+        });
+    }
     void *cuddh_ddh_create_timegrid(double omega, const double *h_a, void *fem, int nx, int ny, int block, int f64, int kernel, int policy,
                                     const int *h_ratios, int n_ratios)
     {

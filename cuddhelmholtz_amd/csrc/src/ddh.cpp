@@ -219,12 +219,21 @@ namespace cuddh
         }
 
         template <typename Real>
-        DDHCore<Real>::DDHCore(from_labels_t, double omega_, const double *h_a, const H1Space &fem, int n_domains_, const int *labels,
+        DDHCore<Real>::DDHCore(from_labels_t tag, double omega_, const double *h_a, const H1Space &fem, int n_domains_, const int *labels,
                                int kernel)
+            : DDHCore(tag, omega_, h_a, fem, n_domains_, labels, kernel, DDHTimeStep::from_mesh(), DDHIntegrator{})
+        {
+        }
+
+        template <typename Real>
+        DDHCore<Real>::DDHCore(from_labels_t, double omega_, const double *h_a, const H1Space &fem, int n_domains_, const int *labels,
+                               int kernel, const DDHTimeStep &time_step, const DDHIntegrator &integrator)
             : g_ndof(fem.size()), g_elem(fem.mesh().n_elem()), n_basis(fem.basis().size()), n_domains(n_domains_), nel1d(0),
               omega(omega_), fem_mesh(&fem.mesh()), more(new More(&fem.basis())), requested_kernel(kernel), general(true)
         {
-            // everything is checked here, on the host, before anything is allocated or launched
+            // everything is checked here, on the host, before anything is allocated or launched: the integrator, the labels,
+            // then the time-step policy
+            set_integrator(integrator);
             const int nb = n_basis;
             if (nb < 2 || nb > 10)
                 cuddh_error("DDH error: subdomains from labels need n_basis in [2, 10].");
@@ -256,7 +265,8 @@ namespace cuddh
                 cuddh_error("DDH error: subdomains from labels run kernel 9 or 10 (0 = auto); kernels 1-8 need the block grid.");
             if (kernel == 9 && (nb != 4 || mx_elems > 16))
                 cuddh_error("DDH error: kernel 9 needs n_basis 4 and at most 16 elements per subdomain.");
-            setup(h_a, fem, labels, DDHTimeStep::from_mesh());
+            check_time_step(time_step, h_a, g_ndof, n_domains);
+            setup(h_a, fem, labels, time_step);
         }
 
         template <typename Real>
@@ -871,6 +881,12 @@ namespace cuddh
     {
     }
 
+    DDH::DDH(from_labels_t tag, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel,
+             const DDHTimeStep &time_step, const DDHIntegrator &integrator)
+        : core(tag, omega, h_a, fem, n_domains, labels, kernel, time_step, integrator)
+    {
+    }
+
     void DDH::action(const float *x, float *y) const
     {
         core.solve(0, core.num_domains(), nullptr, nullptr, false, x, y);
@@ -919,6 +935,12 @@ namespace cuddh
 
     DDH64::DDH64(from_labels_t tag, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel)
         : core(tag, omega, h_a, fem, n_domains, labels, kernel)
+    {
+    }
+
+    DDH64::DDH64(from_labels_t tag, double omega, const double *h_a, const H1Space &fem, int n_domains, const int *labels, int kernel,
+                 const DDHTimeStep &time_step, const DDHIntegrator &integrator)
+        : core(tag, omega, h_a, fem, n_domains, labels, kernel, time_step, integrator)
     {
     }
 

@@ -127,6 +127,13 @@ void *cuddh_ddh_create_block(double omega, const double *h_a, void *fem, int nx,
  * kernel: 0 auto, 9 one wavefront per subdomain (n_basis 4, <= 16 elements), 10 one workgroup per subdomain
  * (cuddh_hip_ddh_plan_create_general).  cuddh_ddh_info reports nel1d = 0. */
 void *cuddh_ddh_create_labels(double omega, const double *h_a, void *fem, int n_domains, const int *h_labels, int f64, int kernel);
+/* cuddh_ddh_create_labels with a time-step policy and an integrator, encoded as in cuddh_ddh_create_integrator: policy 0 mesh,
+ * 1 coefficient, 2 h_ratios HOST with n_ratios = n_domains (one ratio per label, each in [1, 256]); integrator 0 = RK2 (coarsen
+ * must be 1), 1 = RK4 on ceil(nt_mesh / coarsen) steps, coarsen in [1, 16].  Checked in this order before anything is allocated
+ * (NULL + cuddh_last_error): the integrator ("DDH error: integrator"), the labels, the policy ("DDH error: time step").  kernel:
+ * 0 / 9 / 10 as in cuddh_ddh_create_labels; both kernels have every form, so auto picks as it does there. */
+void *cuddh_ddh_create_labels_integrator(double omega, const double *h_a, void *fem, int n_domains, const int *h_labels, int f64, int kernel,
+                                         int policy, const int *h_ratios, int n_ratios, int integrator, int coarsen);
 /* cuddh_ddh_create_block with a time-step policy (cuddh::DDHTimeStep): 0 = the mesh grid, cuddh_ddh_create_block itself;
  * 1 = from the coefficient: subdomain s marches r_s times the mesh grid's steps, r_s = max(1, ceil((1 - 1e-9) / min a over its
  * dofs)); one ratio for all gives a plain plan on that grid, several a plan with per-subdomain time grids

@@ -375,10 +375,10 @@ int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last);
  * The four DEVICE arrays stay the caller's and must outlive the plan, like the descriptor's.  The descriptor's own grid is
  * then unused.  Allocates and synchronises.
  * One subdomain per wavefront or workgroup is what makes the grid uniform where the time loop reads it, so kernels 1, 2, 3,
- * 4, 5 in the matrix form, 8 and 11 run such a plan (instantiations of their own; a plan without grids launches the code it
- * did before).  The kernels that hold several subdomains per wavefront do not: a kernel-5 plan takes the matrix form whatever
+ * 4, 5 in the matrix form, 8, 11 and a general plan's 9 and 10 run such a plan (instantiations of their own; a plan without
+ * grids launches the code it did before).  The kernels that hold several subdomains per wavefront do not: a kernel-5 plan takes the matrix form whatever
  * its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan that auto resolved to kernel 6 or 7 becomes kernel 1;
- * a plan created with kernel 6 or 7 on request, one with sweep form 2 or 3 set, and a general plan (kernels 9, 10) are
+ * a plan created with kernel 6 or 7 on request and one with sweep form 2 or 3 set are
  * refused with hipErrorInvalidValue, as are a grid with nt < 1 or dt <= 0 and an entry of d_grid_of out of range.
  * An apply over the whole range [0, n_domains) of such a plan runs the subdomains in the order of their step counts,
  * longest first and by index among equals (a list the plan owns), so that the short solves fill the device behind the
@@ -396,12 +396,12 @@ int cuddh_hip_ddh_plan_time_grids(const cuddh_ddh_plan *plan);
  * Restart, filter, tables (cs / sn hold every half step), load and publish, wh_iters, priority, lists and ranges and
  * per-subdomain time grids are those of RK2.  The grid is whatever the descriptor (or cuddh_hip_ddh_plan_set_time_grids) holds:
  * RK4 is meant for a grid 2 to 16 times coarser than the mesh grid RK2 needs; the caller builds that grid.
- * RK4 forms exist of kernels 1, 2, 5 (matrix form) and 8 (instantiations of their own; an RK2 plan launches the code it did
+ * RK4 forms exist of kernels 1, 2, 5 (matrix form), 8, 9 and 10 (instantiations of their own; an RK2 plan launches the code it did
  * before).  Like cuddh_hip_ddh_plan_set_time_grids this moves an auto choice and never a request: a plan that auto resolved
  * to kernel 3 becomes kernel 2, one that resolved to 6, 7 or 11 becomes kernel 1, a kernel-5 plan takes the matrix form
  * whatever its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan created with kernel 3, 4, 6, 7 or 11 on
- * request, one with sweep form 2 or 3 set, and a general plan (kernels 9, 10) are refused with hipErrorInvalidValue and stay
- * RK2 plans.  No launch of an RK4 plan ever runs RK2 code: a kernel without an RK4 form returns hipErrorInvalidValue.
+ * request and one with sweep form 2 or 3 set are refused with hipErrorInvalidValue and stay
+ * RK2 plans; a general plan keeps its kernel, 9 or 10.  No launch of an RK4 plan ever runs RK2 code: a kernel without an RK4 form returns hipErrorInvalidValue.
  * cuddh_hip_ddh_plan_integrator returns the scheme in effect. */
 int cuddh_hip_ddh_plan_set_integrator(cuddh_ddh_plan *plan, int scheme);
 int cuddh_hip_ddh_plan_integrator(const cuddh_ddh_plan *plan);
