@@ -112,6 +112,13 @@ _sig("cuddh_hip_mgs_stage_f64", ci, ci, vp, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_mgs_stage_f32", ci, ci, vp, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_mgs_finish_f64", ci, ci, vp, vp, vp, vp)
 _sig("cuddh_hip_mgs_finish_f32", ci, ci, vp, vp, vp, vp)
+_sig("cuddh_hip_cgs_ws_bytes", cs, ci)
+_sig("cuddh_hip_cgs_partials", ci, ci)
+_cgs_pass = (ci, ci, vp, vp, C.c_longlong, ci, ci, ci, vp, ci, C.c_longlong, vp, vp, vp, vp)
+_sig("cuddh_hip_cgs_pass_f64", *_cgs_pass)
+_sig("cuddh_hip_cgs_pass_f32", *_cgs_pass)
+_sig("cuddh_hip_cgs_reduce_f64", ci, ci, ci, vp, vp, vp)
+_sig("cuddh_hip_cgs_reduce_f32", ci, ci, ci, vp, vp, vp)
 _sig("cuddh_hip_nrm2_f64", ci, ci, vp, vp, vp, vp)
 _sig("cuddh_hip_nrm2_f32", ci, ci, vp, vp, vp, vp)
 for _t in ("f64", "f32", "i32"):
@@ -288,6 +295,12 @@ _sig("cuddh_gmres_helmholtz", ci, vp, vp, vp, ci, ci, cd, ci, cd, C.POINTER(Solv
 _sig("cuddh_gmres_ddh", ci, ci, vp, vp, vp, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
 _sig("cuddh_gmres_callback", ci, ci, vp, ACTION_CB, vp, vp, ci, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
 _sig("cuddh_gmres_callback_sharded", ci, ci, vp, ACTION_CB, vp, REDUCE_CB, vp, vp, ci, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
+# (the same with `int orth` in front of the result: 0 modified Gram-Schmidt, 1 CGS2)
+_sig("cuddh_gmres_f64_orth", ci, ci, vp, vp, vp, vp, ci, ci, cd, ci, cd, ci, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_helmholtz_orth", ci, vp, vp, vp, ci, ci, cd, ci, cd, ci, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_ddh_orth", ci, ci, vp, vp, vp, ci, ci, cd, ci, cd, ci, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_callback_orth", ci, ci, vp, ACTION_CB, vp, vp, ci, ci, ci, cd, ci, cd, ci, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_callback_sharded_orth", ci, ci, vp, ACTION_CB, vp, REDUCE_CB, vp, vp, ci, ci, ci, cd, ci, cd, ci, C.POINTER(SolverResult), vp, vp)
 
 
 def last_error() -> str:

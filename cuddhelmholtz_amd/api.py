@@ -357,13 +357,15 @@ class HelmholtzOperator(_Operator):
     def action_native(self, z_in, z_out):
         N.check_capi(lib.cuddh_helmholtz_apply_native(self._h, _ptr(z_in, "f64", self._n, "z_in"), _ptr(z_out, "f64", self._n, "z_out")), "HelmholtzOperator.action_native")
 
-    def gmres(self, x, b, m: int, maxit: int, tol: float = 1e-6, verbose: int = 0, max_seconds: float = 6 * 60 * 60) -> "SolverOut":
-        """HelmholtzOperator::gmres: x, b in the reference ordering; iteration vectors in plan-native ordering when the plan has one"""
+    def gmres(self, x, b, m: int, maxit: int, tol: float = 1e-6, verbose: int = 0, max_seconds: float = 6 * 60 * 60, orth: str = "mgs") -> "SolverOut":
+        """HelmholtzOperator::gmres: x, b in the reference ordering; iteration vectors in plan-native ordering when the plan has one.
+        orth: "mgs" or "cgs2" (see gmres)"""
+        code = _orth_code(orth)
         res = N.SolverResult()
         h_res = np.zeros(maxit + 2)
         h_time = np.zeros(maxit + 2)
-        N.check_capi(lib.cuddh_gmres_helmholtz(self._h, _ptr(x, "f64", self._n, "x"), _ptr(b, "f64", self._n, "b"), m, maxit, float(tol), verbose,
-                                               float(max_seconds), C.byref(res), _h(h_res), _h(h_time)), "HelmholtzOperator.gmres")
+        N.check_capi(_gmres_entry("cuddh_gmres_helmholtz", code, (self._h, _ptr(x, "f64", self._n, "x"), _ptr(b, "f64", self._n, "b"), m, maxit, float(tol), verbose,
+                                                                   float(max_seconds)), res, h_res, h_time), "HelmholtzOperator.gmres")
         return _solver_out(res, h_res, h_time)
 
     def bytes_native(self) -> int:
@@ -661,13 +663,35 @@ class DDH:
                                                    _ptr(u, "f64", 2 * self.fem.size(), "u"), int(zero_u)), "DDH.local_solution")
 
 
+ORTHOGONALIZATIONS = {"mgs": 0, "cgs2": 1}
+
+
+def _orth_code(orth) -> int:
+    """the C API's code of an orthogonalisation name; anything but "mgs" / "cgs2" is a ValueError, before any native call"""
+    if not isinstance(orth, str) or orth not in ORTHOGONALIZATIONS:
+        raise ValueError(f"gmres: orth must be one of {sorted(ORTHOGONALIZATIONS)}, not {orth!r}")
+    return ORTHOGONALIZATIONS[orth]
+
+
+def _gmres_entry(name: str, code: int, head: tuple, res, h_res, h_time) -> int:
+    """"mgs" calls the entry point `name` itself, anything else `name`_orth with the code in front of the result"""
+    if code == 0:
+        return getattr(lib, name)(*head, C.byref(res), _h(h_res), _h(h_time))
+    return getattr(lib, name + "_orth")(*head, code, C.byref(res), _h(h_res), _h(h_time))
+
+
 def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int = 0, max_seconds: float = 6 * 60 * 60, Precond=None,
-          reduce=None) -> SolverOut:
+          reduce=None, orth: str = "mgs") -> SolverOut:
     """Restarted GMRES (reference include/gmres.hpp:33-36).  A: an operator of this module, a DDH,
     or a Python callable `A(x, y)` acting on device tensors of x's dtype.
 
     reduce (only with a callable A): `reduce(t)` sums the small device tensor `t` over all ranks in place
-    (torch.distributed.all_reduce) -- the vectors are then partitioned over the processes, see dist.py."""
+    (torch.distributed.all_reduce) -- the vectors are then partitioned over the processes, see dist.py.
+
+    orth: how an Arnoldi step orthogonalises.  "mgs" (default, the reference's): modified Gram-Schmidt, one launch per basis vector
+    and, with reduce=, k + 2 reductions of one scalar at step k.  "cgs2": classical Gram-Schmidt applied twice -- four launches
+    and three reductions (of k + 1, k + 1 and 1 scalars) per step whatever k is, and a basis orthogonal to working precision (m <= 512)."""
+    code = _orth_code(orth)
     import torch
 
     if reduce is not None and (isinstance(A, (DDH, _Operator)) or Precond is not None):
@@ -677,10 +701,11 @@ def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int =
     h_res = np.zeros(maxit + 2)
     h_time = np.zeros(maxit + 2)
     if isinstance(A, DDH):
-        N.check_capi(lib.cuddh_gmres_ddh(n, _ptr(x, A.trace_dtype, n, "x"), A._h, _ptr(b, A.trace_dtype, n, "b"), m, maxit, float(tol), verbose, float(max_seconds), C.byref(res), _h(h_res), _h(h_time)), "gmres")
+        N.check_capi(_gmres_entry("cuddh_gmres_ddh", code, (n, _ptr(x, A.trace_dtype, n, "x"), A._h, _ptr(b, A.trace_dtype, n, "b"), m, maxit, float(tol), verbose, float(max_seconds)),
+                                  res, h_res, h_time), "gmres")
     elif isinstance(A, _Operator):
-        N.check_capi(lib.cuddh_gmres_f64(n, _ptr(x, "f64", n, "x"), A._h, _ptr(b, "f64", n, "b"), Precond._h if Precond is not None else None, m, maxit, float(tol), verbose,
-                                         float(max_seconds), C.byref(res), _h(h_res), _h(h_time)), "gmres")
+        N.check_capi(_gmres_entry("cuddh_gmres_f64", code, (n, _ptr(x, "f64", n, "x"), A._h, _ptr(b, "f64", n, "b"), Precond._h if Precond is not None else None, m, maxit,
+                                                            float(tol), verbose, float(max_seconds)), res, h_res, h_time), "gmres")
     else:
         dtype = x.dtype
         is64 = dtype == torch.float64
@@ -711,12 +736,12 @@ def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int =
 
         cfun = N.ACTION_CB(cb)
         if reduce is None:
-            N.check_capi(lib.cuddh_gmres_callback(n, _ptr(x, dtype, n, "x"), cfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit, float(tol), verbose,
-                                                  float(max_seconds), C.byref(res), _h(h_res), _h(h_time)), "gmres")
+            N.check_capi(_gmres_entry("cuddh_gmres_callback", code, (n, _ptr(x, dtype, n, "x"), cfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit, float(tol), verbose,
+                                                                     float(max_seconds)), res, h_res, h_time), "gmres")
         else:
             rfun = N.REDUCE_CB(red)
-            N.check_capi(lib.cuddh_gmres_callback_sharded(n, _ptr(x, dtype, n, "x"), cfun, None, rfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit, float(tol),
-                                                          verbose, float(max_seconds), C.byref(res), _h(h_res), _h(h_time)), "gmres")
+            N.check_capi(_gmres_entry("cuddh_gmres_callback_sharded", code, (n, _ptr(x, dtype, n, "x"), cfun, None, rfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit,
+                                                                             float(tol), verbose, float(max_seconds)), res, h_res, h_time), "gmres")
         if errors:
             raise errors[0]
     return _solver_out(res, h_res, h_time)

@@ -4,7 +4,8 @@
 //   options, anywhere on the line: --time-step mesh|coefficient (DDHTimeStep: where the local solves take their time step from;
 //   mesh is the default, the reference's; single-process path only), --integrator rk2|rk4 --coarsen N (DDHIntegrator: rk2 on
 //   the mesh grid is the default; rk4 marches ceil(nt / N) steps, N in [1, 16], 4 unless given; single-process path only),
-//   --residuals (one more line: GMRES's residual history)
+//   --residuals (one more line: GMRES's residual history), --orth mgs|cgs2 (the orthogonalisation of the Arnoldi step, krylov.hpp;
+//   mgs is the default, the reference's; both paths; the summary line names it when it is not mgs)
 // Writes <out_dir>/xy.0000 and <out_dir>/ddh.0000 (raw fp64, like the reference) and prints one summary line.
 // devices >= 1: the same solve through cuddh::ddh_solve_multi_gpu (multigpu.hpp): subdomains sharded over that many GPUs of
 // this process, RCCL neighbour exchange; devices = 1 with force_rccl = 1 runs the communicator path on a one-GPU box;
@@ -24,7 +25,7 @@ using namespace cuddh;
 int main(int argc_all, char **argv_all)
 {
     // options out, positional arguments stay
-    std::string time_step = "mesh", integrator = "rk2";
+    std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs";
     int coarsen = 0; // 0: not given
     bool residuals = false;
     std::vector<char *> args;
@@ -37,6 +38,8 @@ int main(int argc_all, char **argv_all)
             integrator = argv_all[++i];
         else if (arg == "--coarsen" && i + 1 < argc_all)
             coarsen = std::atoi(argv_all[++i]);
+        else if (arg == "--orth" && i + 1 < argc_all)
+            orth_name = argv_all[++i];
         else if (arg == "--residuals")
             residuals = true;
         else
@@ -52,6 +55,13 @@ int main(int argc_all, char **argv_all)
         std::cerr << "ddh_solve: --integrator takes rk2 or rk4, not " << integrator << std::endl;
         return 2;
     }
+    if (orth_name != "mgs" && orth_name != "cgs2")
+    {
+        std::cerr << "ddh_solve: --orth takes mgs or cgs2, not " << orth_name << std::endl;
+        return 2;
+    }
+    const Orthogonalization orth = orth_name == "cgs2" ? Orthogonalization::cgs2 : Orthogonalization::mgs;
+    const std::string orth_note = orth_name == "mgs" ? "" : " orth=" + orth_name;
     if (coarsen == 0)
         coarsen = integrator == "rk4" ? 4 : 1;
     if (coarsen < 1 || coarsen > DDHIntegrator::max_coarsen || (integrator == "rk2" && coarsen != 1))
@@ -105,7 +115,7 @@ int main(int argc_all, char **argv_all)
         }
         std::vector<double> h_u(N);
         const multi_gpu_result r = ddh_solve_multi_gpu(nx, nb, omega, a.host_read(), b.host_read(), h_u.data(), devices, m, maxit, tol, force_rccl & 3,
-                                                       (force_rccl & 4) != 0, (force_rccl >> 8) & 0xFF, (force_rccl >> 16) & 0xFF);
+                                                       (force_rccl & 4) != 0, (force_rccl >> 8) & 0xFF, (force_rccl >> 16) & 0xFF, orth);
         if (out_dir != "-")
         {
             to_file(out_dir + "/xy.0000", N, fem.physical_coordinates(MemorySpace::HOST));
@@ -119,7 +129,7 @@ int main(int argc_all, char **argv_all)
                   << " num_matvec=" << r.gmres.num_matvec << " rel_res=" << r.gmres.res_norm.back() / r.gmres.res_norm.front()
                   << " |u|=" << std::sqrt(unorm) << " t_setup=" << r.t_setup << " t_rhs=" << r.t_rhs << " t_gmres=" << r.t_gmres
                   << " t_postprocess=" << r.t_postprocess << " sent_bytes_per_action_rank0=" << r.bytes_sent_per_action_rank0
-                  << " DoF*iter/s=" << 2.0 * ndof * r.gmres.num_matvec / r.t_gmres << std::endl;
+                  << " DoF*iter/s=" << 2.0 * ndof * r.gmres.num_matvec / r.t_gmres << orth_note << std::endl;
         return 0;
     }
 
@@ -143,7 +153,7 @@ int main(int argc_all, char **argv_all)
     sync();
     const double t_rhs = seconds_since(t);
     t = clk::now();
-    solver_out out = gmres(n_lambda, d_L, &F, d_Y, m, maxit, tol, 0);
+    solver_out out = gmres(n_lambda, d_L, &F, d_Y, m, maxit, tol, 0, 6 * 60 * 60, orth);
     sync();
     const double t_gmres = seconds_since(t);
     t = clk::now();
@@ -164,7 +174,7 @@ int main(int argc_all, char **argv_all)
               << " success=" << out.success << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs
               << " t_gmres=" << t_gmres << " t_postprocess=" << t_post
-              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << std::endl;
+              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << std::endl;
     if (residuals)
     {
         std::cout << "ddh_solve time_step=" << time_step << " residuals:";

@@ -4,10 +4,12 @@
 // ordering native (default): HelmholtzOperator::gmres -- the iteration vectors live in the plan's own ordering (permuted once at
 // entry and exit); reference: gmres() on [u; v] in H1Space numbering, the call the reference's examples make.
 // a(x) = 0.2 inside the disk of radius 1/4, 1 elsewhere (interpolated at the nodes; a = 1 on the boundary), two Gaussian
-// sources as in the reference's examples.  Prints one summary line; writes <out_dir>/xy.0000 and helmholtz.0000 unless "-".
+// sources as in the reference's examples.  --orth mgs|cgs2, anywhere on the line: the orthogonalisation of the Arnoldi step
+// (krylov.hpp; mgs is the default, the reference's; the summary line names it when it is not).  Prints one summary line; writes <out_dir>/xy.0000 and helmholtz.0000 unless "-".
 #include <chrono>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "cuddh.hpp"
 #include "cuddh_hip.h"
@@ -15,8 +17,26 @@
 
 using namespace cuddh;
 
-int main(int argc, char **argv)
+int main(int argc_all, char **argv_all)
 {
+    // options out, positional arguments stay
+    std::string orth_name = "mgs";
+    std::vector<char *> args;
+    for (int i = 0; i < argc_all; ++i)
+    {
+        if (std::string(argv_all[i]) == "--orth" && i + 1 < argc_all)
+            orth_name = argv_all[++i];
+        else
+            args.push_back(argv_all[i]);
+    }
+    if (orth_name != "mgs" && orth_name != "cgs2")
+    {
+        std::cerr << "helmholtz_solve: --orth takes mgs or cgs2, not " << orth_name << std::endl;
+        return 2;
+    }
+    const Orthogonalization orth = orth_name == "cgs2" ? Orthogonalization::cgs2 : Orthogonalization::mgs;
+    const int argc = static_cast<int>(args.size());
+    char **argv = args.data();
     const int nx = argc > 1 ? std::atoi(argv[1]) : 256;
     const int nb = argc > 2 ? std::atoi(argv[2]) : 4;
     const double omega = M_PI * (argc > 3 ? std::atof(argv[3]) : 8.0);
@@ -61,7 +81,7 @@ int main(int argc, char **argv)
     using clk = std::chrono::steady_clock;
     detail::check_hip(cuddh_hip_stream_sync(stream()), "sync");
     const auto t0 = clk::now();
-    solver_out out = native ? A.gmres(d_U, d_b, m, maxit, tol, 0) : gmres(N, d_U, &A, d_b, m, maxit, tol, 0);
+    solver_out out = native ? A.gmres(d_U, d_b, m, maxit, tol, 0, 6 * 60 * 60, orth) : gmres(N, d_U, &A, d_b, m, maxit, tol, 0, 6 * 60 * 60, orth);
     detail::check_hip(cuddh_hip_stream_sync(stream()), "sync");
     const double t_gmres = std::chrono::duration<double>(clk::now() - t0).count();
 
@@ -79,6 +99,6 @@ int main(int argc, char **argv)
               << " success=" << out.success << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |U|=" << std::sqrt(unorm) << " t_gmres=" << t_gmres
               << " DoF*iter/s=" << static_cast<double>(N) * out.num_matvec / t_gmres
-              << " us_per_matvec=" << 1e6 * t_gmres / out.num_matvec << std::endl;
+              << " us_per_matvec=" << 1e6 * t_gmres / out.num_matvec << (orth_name == "mgs" ? "" : " orth=" + orth_name) << std::endl;
     return 0;
 }

@@ -52,7 +52,9 @@ namespace cuddh
         void action_native(const double *z_in, double *z_out) const;
         /// gmres(2 * fem.size(), x, this, b, m, maxit, tol, ...) with the iteration vectors in native ordering when the plan has one
         /// (x and b stay in the reference ordering: they are permuted at entry and exit); the plain gmres() otherwise
-        solver_out gmres(double *x, const double *b, int m, int maxit, double tol = 1e-6, int verbose = 0, double max_seconds = 6 * 60 * 60) const;
+        /// orth: krylov.hpp (Orthogonalization::cgs2: four launches per Arnoldi step whatever the step)
+        solver_out gmres(double *x, const double *b, int m, int maxit, double tol = 1e-6, int verbose = 0, double max_seconds = 6 * 60 * 60,
+                         Orthogonalization orth = Orthogonalization::mgs) const;
 
         /// bytes per apply: algorithmic (SURVEY 8d formula) or as laid out by the plan
         std::size_t bytes_per_apply(bool actual) const;

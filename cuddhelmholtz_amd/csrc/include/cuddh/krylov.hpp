@@ -50,6 +50,28 @@ namespace cuddh
                      double max_seconds, const ScalarReduce &reduce);
     solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
                      double max_seconds, const ScalarReduce &reduce);
+
+    /// How an Arnoldi step orthogonalises w = A v_k against v_0..v_k.
+    /// mgs (the reference's, the default): modified Gram-Schmidt, one fused launch per basis vector, k + 3 dependent launches.
+    /// cgs2: classical Gram-Schmidt applied twice; every coefficient of a pass is an inner product with the same vector, so a pass
+    /// is one launch whatever k is: four launches per step, three reductions of k + 1 scalars with partitioned vectors (mgs: k + 2
+    /// of one scalar), orthogonality of the basis at working precision.  m <= 512, and with partitioned vectors every rank needs
+    /// at least one entry (an error otherwise).  Same iteration otherwise.
+    enum class Orthogonalization
+    {
+        mgs,
+        cgs2
+    };
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, const Operator *Precond, int m, int maxit, double tol, int verbose,
+                     double max_seconds, Orthogonalization orth);
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                     Orthogonalization orth);
+    solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
+                     double max_seconds, Orthogonalization orth);
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose,
+                     double max_seconds, const ScalarReduce &reduce, Orthogonalization orth);
+    solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
+                     double max_seconds, const ScalarReduce &reduce, Orthogonalization orth);
 } // namespace cuddh
 
 #endif

@@ -65,10 +65,11 @@ namespace cuddh
     /// split_schedule: the boundary subdomains are solved first, as one listed launch with issue priority on a second stream,
     /// the exchange is posted behind them and the interior subdomains run on the main stream meanwhile (the north star's
     /// schedule; default: exchange after all local solves).  grid_x x grid_y = world: the ranks own rectangles of the
-    /// subdomain grid instead of strips of block rows (0: strips).
+    /// subdomain grid instead of strips of block rows (0: strips).  orth: the orthogonalisation of gmres() (krylov.hpp; cgs2: three
+    /// all-reduces of k + 1 scalars per Arnoldi step instead of k + 2 of one).
     multi_gpu_result ddh_solve_multi_gpu(int nx, int nb, double omega, const double *h_a, const double *h_f, double *h_u, int world,
                                          int gmres_m, int gmres_maxit, float tol, int transport = 0, bool split_schedule = false,
-                                         int grid_x = 0, int grid_y = 0);
+                                         int grid_x = 0, int grid_y = 0, Orthogonalization orth = Orthogonalization::mgs);
 
     struct helmholtz_multi_gpu_result
     {
@@ -88,7 +89,8 @@ namespace cuddh
     /// transport as in ddh_solve_multi_gpu (0 RCCL, 1 RCCL also for one rank, 2 loopback ranks sharing device 0).
     helmholtz_multi_gpu_result helmholtz_multi_gpu(int n_pts, const double *h_xy, int n_elem, const int *h_elems, int nb, double omega,
                                                    const double *h_a2x, const double *h_ax, const double *h_x, double *h_y, int world,
-                                                   int transport = 0, int reps = 0, int gmres_m = 20, int gmres_maxit = 0, double tol = 1e-8);
+                                                   int transport = 0, int reps = 0, int gmres_m = 20, int gmres_maxit = 0, double tol = 1e-8,
+                                                   Orthogonalization orth = Orthogonalization::mgs);
 } // namespace cuddh
 
 #endif

@@ -524,6 +524,290 @@ namespace
         return launch_status();
     }
 
+    // ---------------- classical Gram-Schmidt pass against all k1 basis vectors at once (CGS2: krylov.cpp::queue_step_cgs2)
+    // Every coefficient of a pass is an inner product with the SAME w, so a pass is one launch whatever k1 is:
+    //   UPDATE    c[j] = sum_p cin[j cstride + p] (p < ncin) for every j < k1, by every workgroup in the same order;
+    //             workgroup 0 writes hout[j] = (hacc ? hacc[j] : 0) + c[j];  w <- w - sum_j c[j] v_j, per element in ascending j
+    //   DOTS 1    pout row 1 + j <- per-workgroup partial sums of <w, v_j> (the updated w), row 0 <- those of <w, w>
+    //   DOTS 2    row 0 only: what mgs_finish_kernel reads
+    // Rows of pout are CGS_ROW apart.  A tile of w stays in registers while the basis streams past it in chunks of CGS_KC
+    // vectors; an UPDATE + DOTS 1 pass reads each tile of V a second time for the dots of the updated w (it cannot be kept: k1 x 16 KiB).
+    // The per-j sums cannot be registers indexed at run time: a chunk's CGS_KC accumulators are reduced per wavefront and added
+    // to LDS (k1 + 1 rows x 4 waves), in tile order by one lane per wave, so the order is fixed.
+    constexpr int CGS_KC = 4;
+    constexpr int CGS_KMAX = 512;
+    constexpr int CGS_ROW = MAX_PARTIALS;
+    constexpr int NWAVES = BLOCK / WAVE;
+
+    // c[j] = sum_p cin[j cstride + p], p < ncin <= 4 BLOCK, for j < rows, in the order in which mgs_stage_kernel and
+    // mgs_finish_kernel sum their partials (<= 4 per thread in ascending p, wave_sum, the four waves in order): the UPDATE
+    // prologue and cgs_reduce_kernel both get their sums here, and row 0 of a pass summed here is mgs_finish's own sum.
+    // part: rows x NWAVES of LDS scratch.  Ends with a barrier: c is valid in every thread.
+    template <typename T>
+    __device__ inline void cgs_sum_rows(const T *__restrict__ cin, size_t cstride, int ncin, int rows, T *__restrict__ c, T *__restrict__ part)
+    {
+        static_assert(MAX_PARTIALS <= 4 * BLOCK, "four partial sums per thread");
+        const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+        for (int j0 = 0; j0 < rows; j0 += CGS_KC)
+        {
+            T q[CGS_KC][4];
+#pragma unroll
+            for (int r = 0; r < CGS_KC; ++r)
+            {
+                const T *row = cin + static_cast<size_t>(min(j0 + r, rows - 1)) * cstride;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    q[r][k] = row[min((int)threadIdx.x + k * BLOCK, ncin - 1)];
+            }
+#pragma unroll
+            for (int r = 0; r < CGS_KC; ++r)
+            {
+                T a = T(0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    a = (int)threadIdx.x + k * BLOCK < ncin ? a + q[r][k] : a;
+                a = wave_sum(a);
+                if (lane == 0 && j0 + r < rows)
+                    part[(j0 + r) * NWAVES + wv] = a;
+            }
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < rows; j += BLOCK)
+        {
+            T s = T(0);
+#pragma unroll
+            for (int i = 0; i < NWAVES; ++i)
+                s += part[j * NWAVES + i];
+            c[j] = s;
+        }
+        __syncthreads();
+    }
+
+    template <typename T, bool UPDATE, int DOTS>
+    __global__ void __launch_bounds__(BLOCK) cgs_pass_kernel(int n, T *__restrict__ w, const T *__restrict__ V, size_t ldv, int k1, const T *__restrict__ cin,
+                                                             int ncin, size_t cstride, const T *__restrict__ hacc, T *__restrict__ hout, T *__restrict__ pout,
+                                                             int vectorised)
+    {
+        static_assert(DOTS == 1 || (DOTS == 2 && UPDATE), "pass A: dots; pass B: update + dots; pass C: update + <w, w>");
+        __shared__ T c_sh[UPDATE ? CGS_KMAX : 1];
+        __shared__ T d_sh[CGS_KMAX * NWAVES]; // per-wave sums of <w, v_j> (before that: scratch of the prologue)
+        using VE = T __attribute__((ext_vector_type(Pack<T>::N)));
+        constexpr int N = Pack<T>::N;
+        const int nv = vectorised ? n / N : 0;
+        const int n_tiles = (nv + TILE - 1) / TILE;
+        const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+        VE *wv = reinterpret_cast<VE *>(w);
+        auto basis = [&](int j) { return reinterpret_cast<const VE *>(V + static_cast<size_t>(min(j, k1 - 1)) * ldv); }; // (clamped: see below)
+
+        // requests of a tile: w, and a chunk of CGS_KC basis vectors; clamped addresses (element and basis vector), no branches
+        auto request_w = [&](int tile, VE(&a)[UNROLL])
+        {
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u)
+                a[u] = wv[min(tile * TILE + (int)threadIdx.x + u * BLOCK, nv - 1)];
+        };
+        auto request_chunk = [&](int tile, int j0, VE(&b)[CGS_KC][UNROLL])
+        {
+#pragma unroll
+            for (int q = 0; q < CGS_KC; ++q)
+            {
+                const VE *vj = basis(j0 + q);
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u)
+                    b[q][u] = vj[min(tile * TILE + (int)threadIdx.x + u * BLOCK, nv - 1)];
+            }
+        };
+        // a chunk's sums of this thread, reduced per wavefront and added to the rows of d_sh by lane 0
+        auto deposit = [&](int j0, const T(&acc)[CGS_KC])
+        {
+#pragma unroll
+            for (int q = 0; q < CGS_KC; ++q)
+            {
+                const T s = wave_sum(acc[q]);
+                if (lane == 0 && j0 + q < k1)
+                    d_sh[(j0 + q) * NWAVES + wave] += s;
+            }
+        };
+
+        int tile = blockIdx.x;
+        const bool first = tile < n_tiles; // (workgroup-uniform)
+        VE a[UNROLL], b[CGS_KC][UNROLL];
+        if (first) // a workgroup's FIRST tile is requested before the coefficients are summed (see mgs_stage_kernel)
+        {
+            request_w(tile, a);
+            request_chunk(tile, 0, b);
+        }
+        if constexpr (UPDATE)
+        {
+            cgs_sum_rows(cin, cstride, ncin, k1, c_sh, d_sh);
+            if (blockIdx.x == 0)
+                for (int j = threadIdx.x; j < k1; j += BLOCK)
+                    hout[j] = (hacc ? hacc[j] : T(0)) + c_sh[j];
+        }
+        if constexpr (DOTS == 1)
+        {
+            for (int i = threadIdx.x; i < k1 * NWAVES; i += BLOCK)
+                d_sh[i] = T(0);
+            __syncthreads();
+        }
+
+        T ww = T(0);
+        bool requested = first;
+        for (; tile < n_tiles; tile += gridDim.x)
+        {
+            const int base = tile * TILE + threadIdx.x;
+            if (!requested)
+            {
+                request_w(tile, a);
+                request_chunk(tile, 0, b);
+            }
+            requested = false;
+            if constexpr (UPDATE)
+            {
+                for (int j0 = 0; j0 < k1; j0 += CGS_KC)
+                {
+                    if (j0 > 0)
+                        request_chunk(tile, j0, b);
+#pragma unroll
+                    for (int q = 0; q < CGS_KC; ++q)
+                        if (j0 + q < k1) // (uniform)
+                        {
+                            const T c = c_sh[j0 + q];
+#pragma unroll
+                            for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+                                for (int e = 0; e < N; ++e)
+                                    a[u][e] = fmadd(-c, b[q][u][e], a[u][e]);
+                        }
+                }
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u)
+                    if (base + u * BLOCK < nv)
+                        wv[base + u * BLOCK] = a[u];
+            }
+            if constexpr (DOTS == 1)
+            {
+                for (int j0 = 0; j0 < k1; j0 += CGS_KC)
+                {
+                    if (UPDATE || j0 > 0)
+                        request_chunk(tile, j0, b);
+                    T acc[CGS_KC];
+#pragma unroll
+                    for (int q = 0; q < CGS_KC; ++q)
+                    {
+                        acc[q] = T(0);
+#pragma unroll
+                        for (int u = 0; u < UNROLL; ++u)
+                            if (base + u * BLOCK < nv)
+#pragma unroll
+                                for (int e = 0; e < N; ++e)
+                                    acc[q] = fmadd(a[u][e], b[q][u][e], acc[q]);
+                    }
+                    deposit(j0, acc);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u)
+                if (base + u * BLOCK < nv)
+#pragma unroll
+                    for (int e = 0; e < N; ++e)
+                        ww = fmadd(a[u][e], a[u][e], ww);
+        }
+
+        // scalar tail (everything, when an operand is not 16-byte aligned): a thread's elements are its own in every loop below,
+        // so it reads back only what it wrote itself
+        const int tid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
+        const int i0 = nv * N + tid;
+        if constexpr (UPDATE)
+            for (int i = i0; i < n; i += stride)
+            {
+                T wi = w[i];
+                for (int j = 0; j < k1; ++j)
+                    wi = fmadd(-c_sh[j], V[static_cast<size_t>(j) * ldv + i], wi);
+                w[i] = wi;
+            }
+        if (nv * N < n) // (uniform)
+        {
+            if constexpr (DOTS == 1)
+                for (int j0 = 0; j0 < k1; j0 += CGS_KC)
+                {
+                    T acc[CGS_KC];
+#pragma unroll
+                    for (int q = 0; q < CGS_KC; ++q)
+                        acc[q] = T(0);
+                    for (int i = i0; i < n; i += stride)
+                    {
+                        const T wi = w[i];
+#pragma unroll
+                        for (int q = 0; q < CGS_KC; ++q)
+                            acc[q] = fmadd(wi, V[static_cast<size_t>(min(j0 + q, k1 - 1)) * ldv + i], acc[q]);
+                    }
+                    deposit(j0, acc);
+                }
+            for (int i = i0; i < n; i += stride)
+                ww = fmadd(w[i], w[i], ww);
+        }
+
+        __syncthreads();
+        if constexpr (DOTS == 1)
+            for (int j = threadIdx.x; j < k1; j += BLOCK)
+            {
+                T s = T(0);
+#pragma unroll
+                for (int i = 0; i < NWAVES; ++i)
+                    s += d_sh[j * NWAVES + i];
+                pout[static_cast<size_t>(1 + j) * CGS_ROW + blockIdx.x] = s;
+            }
+        const T s = block_sum(ww);
+        if (threadIdx.x == 0)
+            pout[blockIdx.x] = s;
+    }
+
+    // out[j] = sum of row 1 + j of a pass's partials (<w, v_j>), j < k1;  out[k1] = sum of row 0 (<w, w>)
+    template <typename T>
+    __global__ void __launch_bounds__(BLOCK) cgs_reduce_kernel(int k1, const T *__restrict__ partials, int npart, T *__restrict__ out)
+    {
+        __shared__ T c_sh[CGS_KMAX + 1];
+        __shared__ T part[(CGS_KMAX + 1) * NWAVES];
+        cgs_sum_rows(partials, static_cast<size_t>(CGS_ROW), npart, k1 + 1, c_sh, part);
+        for (int j = threadIdx.x; j <= k1; j += BLOCK)
+            out[j == 0 ? k1 : j - 1] = c_sh[j];
+    }
+
+    template <typename T>
+    int launch_cgs_pass(int n, T *w, const T *V, long long ldv, int k1, int update, int dots, const T *cin, int ncin, long long cstride, const T *hacc,
+                        T *hout, T *pout, void *stream)
+    {
+        const bool form = (!update && dots == 1) || (update && (dots == 1 || dots == 2));
+        if (n < 0 || k1 < 1 || k1 > CGS_KMAX || !form || (k1 > 1 && ldv < n) || (update && (ncin < 1 || ncin > MAX_PARTIALS || cstride < 0)))
+            return static_cast<int>(hipErrorInvalidValue);
+        if (n == 0)
+            return 0;
+        const int g = mgs_grid(n);
+        const int vec = aligned16(w) && aligned16(V) && (k1 == 1 || ldv % Pack<T>::N == 0);
+        const dim3 grid(g), block(BLOCK);
+        hipStream_t st = as_stream(stream);
+        const size_t ld = static_cast<size_t>(ldv), cs = static_cast<size_t>(cstride);
+        if (!update)
+            hipLaunchKernelGGL((cgs_pass_kernel<T, false, 1>), grid, block, 0, st, n, w, V, ld, k1, cin, ncin, cs, hacc, hout, pout, vec);
+        else if (dots == 1)
+            hipLaunchKernelGGL((cgs_pass_kernel<T, true, 1>), grid, block, 0, st, n, w, V, ld, k1, cin, ncin, cs, hacc, hout, pout, vec);
+        else
+            hipLaunchKernelGGL((cgs_pass_kernel<T, true, 2>), grid, block, 0, st, n, w, V, ld, k1, cin, ncin, cs, hacc, hout, pout, vec);
+        return launch_status();
+    }
+
+    template <typename T>
+    int launch_cgs_reduce(int n, int k1, const T *partials, T *out, void *stream)
+    {
+        if (n < 0 || k1 < 0 || k1 > CGS_KMAX)
+            return static_cast<int>(hipErrorInvalidValue);
+        if (n == 0)
+            return 0;
+        hipLaunchKernelGGL((cgs_reduce_kernel<T>), dim3(1), dim3(BLOCK), 0, as_stream(stream), k1, partials, mgs_grid(n), out);
+        return launch_status();
+    }
+
     // ---------------- indexed maps
     __global__ void __launch_bounds__(BLOCK) gather_kernel(int n, const int *__restrict__ proj, const double *__restrict__ x, double *__restrict__ y)
     {
@@ -641,6 +925,21 @@ extern "C"
     }
     int cuddh_hip_mgs_finish_f64(int n, double *w, const double *pin, double *hout, void *s) { return launch_mgs_finish<double>(n, w, pin, hout, s); }
     int cuddh_hip_mgs_finish_f32(int n, float *w, const float *pin, float *hout, void *s) { return launch_mgs_finish<float>(n, w, pin, hout, s); }
+
+    size_t cuddh_hip_cgs_ws_bytes(int k1) { return k1 < 0 ? 0 : (static_cast<size_t>(k1) + 1) * CGS_ROW * sizeof(double); }
+    int cuddh_hip_cgs_partials(int n) { return mgs_grid(n); }
+    int cuddh_hip_cgs_pass_f64(int n, double *w, const double *V, long long ldv, int k1, int update, int dots, const double *cin, int ncin, long long cstride,
+                               const double *hacc, double *hout, double *pout, void *s)
+    {
+        return launch_cgs_pass<double>(n, w, V, ldv, k1, update, dots, cin, ncin, cstride, hacc, hout, pout, s);
+    }
+    int cuddh_hip_cgs_pass_f32(int n, float *w, const float *V, long long ldv, int k1, int update, int dots, const float *cin, int ncin, long long cstride,
+                               const float *hacc, float *hout, float *pout, void *s)
+    {
+        return launch_cgs_pass<float>(n, w, V, ldv, k1, update, dots, cin, ncin, cstride, hacc, hout, pout, s);
+    }
+    int cuddh_hip_cgs_reduce_f64(int n, int k1, const double *partials, double *out, void *s) { return launch_cgs_reduce<double>(n, k1, partials, out, s); }
+    int cuddh_hip_cgs_reduce_f32(int n, int k1, const float *partials, float *out, void *s) { return launch_cgs_reduce<float>(n, k1, partials, out, s); }
 
     int cuddh_hip_axpby_f64(int n, double a, const double *x, double b, double *y, void *s)
     {

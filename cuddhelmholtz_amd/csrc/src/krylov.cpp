@@ -23,6 +23,18 @@ namespace cuddh
         inline int k_mgs_stage(int n, float *w, const float *vp, const float *vn, const float *pi, float *po, float *h) { return cuddh_hip_mgs_stage_f32(n, w, vp, vn, pi, po, h, stream()); }
         inline int k_mgs_finish(int n, double *w, const double *pi, double *h) { return cuddh_hip_mgs_finish_f64(n, w, pi, h, stream()); }
         inline int k_mgs_finish(int n, float *w, const float *pi, float *h) { return cuddh_hip_mgs_finish_f32(n, w, pi, h, stream()); }
+        inline int k_cgs_pass(int n, double *w, const double *V, long long ldv, int k1, int update, int dots, const double *cin, int ncin, long long cstride,
+                              const double *hacc, double *hout, double *pout)
+        {
+            return cuddh_hip_cgs_pass_f64(n, w, V, ldv, k1, update, dots, cin, ncin, cstride, hacc, hout, pout, stream());
+        }
+        inline int k_cgs_pass(int n, float *w, const float *V, long long ldv, int k1, int update, int dots, const float *cin, int ncin, long long cstride,
+                              const float *hacc, float *hout, float *pout)
+        {
+            return cuddh_hip_cgs_pass_f32(n, w, V, ldv, k1, update, dots, cin, ncin, cstride, hacc, hout, pout, stream());
+        }
+        inline int k_cgs_reduce(int n, int k1, const double *p, double *out) { return cuddh_hip_cgs_reduce_f64(n, k1, p, out, stream()); }
+        inline int k_cgs_reduce(int n, int k1, const float *p, float *out) { return cuddh_hip_cgs_reduce_f32(n, k1, p, out, stream()); }
 
         // apply the k previous rotations to column h, then build rotation k that zeroes h[k+1]
         template <typename scalar>
@@ -80,14 +92,23 @@ namespace cuddh
 
         template <typename scalar, typename Op>
         solver_out arnoldi_restarted(int n, scalar *x, const Op *A, const scalar *b, int m, int maxit, scalar tol, int verbose,
-                                     double max_seconds, const ScalarReduce *red = nullptr)
+                                     double max_seconds, const ScalarReduce *red = nullptr, Orthogonalization orth = Orthogonalization::mgs)
         {
             using clock = std::chrono::high_resolution_clock;
             const scalar one = 1, zero = 0;
             const int m1 = m + 1;
             constexpr int is_f64 = sizeof(scalar) == 8;
 
-            HostDeviceArray<scalar> r_store(n), V_store(n * m1), col_store(m1 + 1);
+            const bool cgs2 = orth == Orthogonalization::cgs2;
+            if (orth != Orthogonalization::mgs && !cgs2)
+                cuddh_error("gmres error: orthogonalization must be mgs or cgs2.");
+            if (cgs2 && m > 512)
+                cuddh_error("gmres error: orthogonalization cgs2 takes restart lengths up to 512 (one launch covers the whole basis).");
+            // distance of two basis vectors: n; under cgs2 rounded up to 16 bytes, so that one launch may read all of them as 16-byte vectors
+            constexpr std::size_t per16 = 16 / sizeof(scalar);
+            const std::size_t ldv = cgs2 ? (static_cast<std::size_t>(n) + per16 - 1) / per16 * per16 : static_cast<std::size_t>(n);
+
+            HostDeviceArray<scalar> r_store(n), V_store(ldv * m1), col_store(m1 + 1);
             scalar *r = r_store.device_write();
             scalar *V = V_store.device_write();
             scalar *dcol = col_store.device_write(); // Hessenberg column under construction, on the device
@@ -99,6 +120,29 @@ namespace cuddh
                 void *p;
                 ~Guard() { cuddh_hip_free(p); }
             } guard{ws};
+
+            // cgs2: two partial-sum buffers (cuddh_hip.h: rows of `row` scalars, <w, w> in row 0), the first pass's coefficients, and for
+            // partitioned vectors the second pass's reduced coefficients and a row that holds the reduced <w, w> followed by zeros
+            // (a pass and cgs_reduce do nothing on an empty vector, so a rank without entries would send stale coefficients into the sums)
+            if (cgs2 && red && n == 0)
+                cuddh_error("gmres error: orthogonalization cgs2 needs at least one entry of the partitioned vectors on every rank.");
+            void *cgs_ws = nullptr;
+            std::size_t row = 0;
+            scalar *pA = nullptr, *pB = nullptr, *dc1 = nullptr, *dc2 = nullptr, *zrow = nullptr;
+            int n_part = 0;
+            if (cgs2)
+            {
+                row = cuddh_hip_cgs_ws_bytes(0) / sizeof(double);
+                const std::size_t pbytes = cuddh_hip_cgs_ws_bytes(m);
+                detail::check_hip(cuddh_hip_malloc_zeroed(&cgs_ws, 2 * pbytes + (2 * (m1 + 1) + row) * sizeof(double)), "gmres cgs2 workspace");
+                pA = static_cast<scalar *>(cgs_ws);
+                pB = reinterpret_cast<scalar *>(static_cast<char *>(cgs_ws) + pbytes);
+                dc1 = reinterpret_cast<scalar *>(static_cast<char *>(cgs_ws) + 2 * pbytes);
+                dc2 = dc1 + (m1 + 1);
+                zrow = dc2 + (m1 + 1);
+                n_part = cuddh_hip_cgs_partials(n);
+            }
+            Guard cgs_guard{cgs_ws};
 
             // Operators that only queue device work (operator.hpp: QueuesDeviceWorkOnly) are driven one Arnoldi step ahead of the host:
             // two pinned Hessenberg columns and two events
@@ -181,21 +225,39 @@ namespace cuddh
                 // (stage j applies the projection on v_{j-1} and leaves the partial sums of <w, v_j> -- the last one <w, w> -- for
                 // the next stage, so one launch per basis vector does what dot + reduce + axpy did; coefficients stay on the device),
                 // normalisation.  On breakdown (norm == 0) v_{k+1} becomes non-finite but is never used.
+                // cgs2: classical Gram-Schmidt against all of v_0..v_k at once, twice -- pass A the k + 1 inner products, pass B the
+                // projection with their sums and the inner products of the result, pass C the projection with those (h_j = c1_j + c2_j)
+                // and <w, w>, then the same normalisation: four launches at every k
+                auto queue_step_cgs2 = [&](int k, scalar *vk1)
+                {
+                    const int k1 = k + 1;
+                    const scalar *none = nullptr;
+                    detail::check_hip(k_cgs_pass(n, vk1, V, ldv, k1, 0, 1, none, 0, 0, none, static_cast<scalar *>(nullptr), pA), "gmres cgs2 pass");
+                    detail::check_hip(k_cgs_pass(n, vk1, V, ldv, k1, 1, 1, pA + row, n_part, row, none, dc1, pB), "gmres cgs2 pass");
+                    detail::check_hip(k_cgs_pass(n, vk1, V, ldv, k1, 1, 2, pB + row, n_part, row, dc1, dcol, pA), "gmres cgs2 pass");
+                    detail::check_hip(k_mgs_finish(n, vk1, pA, dcol + k1), "gmres normalise");
+                };
+
                 auto queue_step = [&](int k)
                 {
-                    scalar *vk = V + static_cast<std::size_t>(k) * n;
-                    scalar *vk1 = vk + n;
+                    scalar *vk = V + static_cast<std::size_t>(k) * ldv;
+                    scalar *vk1 = vk + ldv;
                     A->action(vk, vk1);
-                    scalar *pa = static_cast<scalar *>(ws), *pb = pa + cuddh_hip_reduce_ws_bytes() / (2 * sizeof(double));
-                    detail::check_hip(k_mgs_stage(n, vk1, static_cast<const scalar *>(nullptr), V, pa, pa, dcol), "gmres mgs");
-                    for (int j = 0; j <= k; ++j)
+                    if (cgs2)
+                        queue_step_cgs2(k, vk1);
+                    else
                     {
-                        const scalar *vj = V + static_cast<std::size_t>(j) * n;
-                        const scalar *vnext = (j < k) ? vj + n : nullptr;
-                        detail::check_hip(k_mgs_stage(n, vk1, vj, vnext, pa, pb, dcol + j), "gmres mgs");
-                        std::swap(pa, pb);
+                        scalar *pa = static_cast<scalar *>(ws), *pb = pa + cuddh_hip_reduce_ws_bytes() / (2 * sizeof(double));
+                        detail::check_hip(k_mgs_stage(n, vk1, static_cast<const scalar *>(nullptr), V, pa, pa, dcol), "gmres mgs");
+                        for (int j = 0; j <= k; ++j)
+                        {
+                            const scalar *vj = V + static_cast<std::size_t>(j) * ldv;
+                            const scalar *vnext = (j < k) ? vj + ldv : nullptr;
+                            detail::check_hip(k_mgs_stage(n, vk1, vj, vnext, pa, pb, dcol + j), "gmres mgs");
+                            std::swap(pa, pb);
+                        }
+                        detail::check_hip(k_mgs_finish(n, vk1, pa, dcol + k + 1), "gmres normalise");
                     }
-                    detail::check_hip(k_mgs_finish(n, vk1, pa, dcol + k + 1), "gmres normalise");
                     if (ahead)
                     {
                         // the Hessenberg column leaves for pinned host memory behind the step; the next step may be queued behind it
@@ -210,17 +272,36 @@ namespace cuddh
                 for (int k = 0; k < m; ++k)
                 {
                     k1 = k + 1;
-                    scalar *vk = V + static_cast<std::size_t>(k) * n;
-                    scalar *vk1 = vk + n;
+                    scalar *vk = V + static_cast<std::size_t>(k) * ldv;
+                    scalar *vk1 = vk + ldv;
                     scalar *h = H.data() + static_cast<std::size_t>(m1) * k;
 
-                    if (red)
+                    if (red && cgs2)
+                    {
+                        // partitioned vectors: the k + 1 sums of a pass are reduced over the ranks in one call, and the next pass reads
+                        // the reduced coefficients (ncin = 1); three reductions per step
+                        A->action(vk, vk1);
+                        const scalar *none = nullptr;
+                        detail::check_hip(k_cgs_pass(n, vk1, V, ldv, k1, 0, 1, none, 0, 0, none, static_cast<scalar *>(nullptr), pA), "gmres cgs2 pass");
+                        detail::check_hip(k_cgs_reduce(n, k1, pA, dcol), "gmres cgs2 reduce");
+                        red->fn(red->user, dcol, k1, is_f64);
+                        detail::check_hip(k_cgs_pass(n, vk1, V, ldv, k1, 1, 1, dcol, 1, 1, none, dc1, pB), "gmres cgs2 pass");
+                        detail::check_hip(k_cgs_reduce(n, k1, pB, dc2), "gmres cgs2 reduce");
+                        red->fn(red->user, dc2, k1, is_f64);
+                        detail::check_hip(k_cgs_pass(n, vk1, V, ldv, k1, 1, 2, dc2, 1, 1, dc1, dcol, pA), "gmres cgs2 pass");
+                        detail::check_hip(k_cgs_reduce(n, 0, pA, zrow), "gmres cgs2 reduce"); // zrow[0] = <w, w> of this rank; zeros behind it
+                        red->fn(red->user, zrow, 1, is_f64);
+                        detail::check_hip(k_mgs_finish(n, vk1, zrow, dcol + k1), "gmres normalise");
+                        detail::check_hip(cuddh_hip_stream_sync(stream()), "gmres sync");
+                        detail::check_hip(cuddh_hip_copy_d2h_on(h, dcol, sizeof(scalar) * (k1 + 1), stream()), "gmres column copy");
+                    }
+                    else if (red)
                     {
                         A->action(vk, vk1);
                         // partitioned vectors: every coefficient is summed over the ranks before it is applied
                         for (int j = 0; j < k1; ++j)
                         {
-                            const scalar *vj = V + static_cast<std::size_t>(j) * n;
+                            const scalar *vj = V + static_cast<std::size_t>(j) * ldv;
                             detail::check_hip(k_dot(n, vk1, vj, dcol + j, ws), "gmres dot");
                             red->fn(red->user, dcol + j, 1, is_f64);
                             detail::check_hip(k_axpby_dev(n, -one, dcol + j, vj, one, vk1), "gmres projection");
@@ -264,7 +345,7 @@ namespace cuddh
 
                 back_substitute(k1, H.data(), m1, eta.data());
                 for (int k = 0; k < k1; ++k)
-                    axpby(n, eta[k], V + static_cast<std::size_t>(k) * n, one, x);
+                    axpby(n, eta[k], V + static_cast<std::size_t>(k) * ldv, one, x);
 
                 A->action(x, r);
                 out.num_matvec++;
@@ -328,6 +409,40 @@ namespace cuddh
                      double max_seconds)
     {
         return arnoldi_restarted<double>(n, x, A, b, m, maxit, tol, verbose, max_seconds);
+    }
+
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose,
+                     double max_seconds, Orthogonalization orth)
+    {
+        return arnoldi_restarted<double>(n, x, A, b, m, maxit, tol, verbose, max_seconds, nullptr, orth);
+    }
+
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, const Operator *Precond, int m, int maxit,
+                     double tol, int verbose, double max_seconds, Orthogonalization orth)
+    {
+        LeftPreconditioned PA(n, A, Precond);
+        host_device_dvec Pb(n);
+        double *d_Pb = Pb.device_write();
+        Precond->action(b, d_Pb);
+        return arnoldi_restarted<double>(n, x, &PA, d_Pb, m, maxit, tol, verbose, max_seconds, nullptr, orth);
+    }
+
+    solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol,
+                     int verbose, double max_seconds, Orthogonalization orth)
+    {
+        return arnoldi_restarted<float>(n, x, A, b, m, maxit, tol, verbose, max_seconds, nullptr, orth);
+    }
+
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose,
+                     double max_seconds, const ScalarReduce &reduce, Orthogonalization orth)
+    {
+        return arnoldi_restarted<double>(n, x, A, b, m, maxit, tol, verbose, max_seconds, reduce.fn ? &reduce : nullptr, orth);
+    }
+
+    solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
+                     double max_seconds, const ScalarReduce &reduce, Orthogonalization orth)
+    {
+        return arnoldi_restarted<float>(n, x, A, b, m, maxit, tol, verbose, max_seconds, reduce.fn ? &reduce : nullptr, orth);
     }
 
     solver_out gmres(int n, double *x, const Operator *A, const double *b, const Operator *Precond, int m, int maxit,

@@ -518,7 +518,8 @@ namespace cuddh
     } // namespace
 
     multi_gpu_result ddh_solve_multi_gpu(int nx, int nb, double omega, const double *h_a, const double *h_f, double *h_u, int world,
-                                         int gmres_m, int gmres_maxit, float tol, int transport, bool split_schedule, int grid_x, int grid_y)
+                                         int gmres_m, int gmres_maxit, float tol, int transport, bool split_schedule, int grid_x, int grid_y,
+                                         Orthogonalization orth)
     {
         if ((grid_x != 0 || grid_y != 0) && grid_x * grid_y != world)
             cuddh_error("ddh_solve_multi_gpu error: grid_x * grid_y must be the number of ranks.");
@@ -619,8 +620,8 @@ namespace cuddh
                 ShardOperator A(R);
                 const ScalarReduce red{reduce_hook, &R};
                 t0 = clk::now();
-                outs[rank] = (use_rccl || R.loop) ? gmres(n, d_lam, &A, d_b, gmres_m, gmres_maxit, tol, 0, 6 * 60 * 60.0, red)
-                                      : gmres(n, d_lam, &A, d_b, gmres_m, gmres_maxit, tol, 0);
+                outs[rank] = (use_rccl || R.loop) ? gmres(n, d_lam, &A, d_b, gmres_m, gmres_maxit, tol, 0, 6 * 60 * 60.0, red, orth)
+                                      : gmres(n, d_lam, &A, d_b, gmres_m, gmres_maxit, tol, 0, 6 * 60 * 60.0, orth);
                 R.sync();
                 t_gmres[rank] = since(t0);
 
@@ -805,7 +806,7 @@ namespace cuddh
 
     helmholtz_multi_gpu_result helmholtz_multi_gpu(int n_pts, const double *h_xy, int n_elem, const int *h_elems, int nb, double omega, const double *h_a2x,
                                                    const double *h_ax, const double *h_x, double *h_y, int world, int transport, int reps, int gmres_m,
-                                                   int gmres_maxit, double tol)
+                                                   int gmres_maxit, double tol, Orthogonalization orth)
     {
         int n_dev = 0;
         detail::check_hip(static_cast<int>(hipGetDeviceCount(&n_dev)), "hipGetDeviceCount");
@@ -894,8 +895,8 @@ namespace cuddh
                 const ScalarReduce red{helm_reduce_hook, &R};
                 zeros(2 * nl, d_y);
                 t0 = clk::now();
-                outs[rank] = (use_rccl || R.loop) ? gmres(2 * nl, d_y, &A, d_x, gmres_m, gmres_maxit, tol, 0, 6 * 60 * 60.0, red)
-                                                  : gmres(2 * nl, d_y, &A, d_x, gmres_m, gmres_maxit, tol, 0);
+                outs[rank] = (use_rccl || R.loop) ? gmres(2 * nl, d_y, &A, d_x, gmres_m, gmres_maxit, tol, 0, 6 * 60 * 60.0, red, orth)
+                                                  : gmres(2 * nl, d_y, &A, d_x, gmres_m, gmres_maxit, tol, 0, 6 * 60 * 60.0, orth);
                 R.sync();
                 t_gmres[rank] = since(t0);
             }

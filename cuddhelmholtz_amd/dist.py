@@ -439,7 +439,8 @@ class NeighbourShardedDDH:
         return w
 
     def solve(self, lam, b, m: int, maxit: int, tol: float, gmres=None, **kw):
-        """GMRES on the partitioned vectors; `gmres` defaults to cuddhelmholtz_amd.gmres"""
+        """GMRES on the partitioned vectors; `gmres` defaults to cuddhelmholtz_amd.gmres.  Keywords go on to it: `orth="cgs2"` makes
+        every Arnoldi step three all-reduces (of k + 1, k + 1 and 1 scalars) instead of k + 2 of one scalar"""
         if gmres is None:
             from .api import gmres
         return gmres(lam.numel(), lam, self.action, b, m, maxit, tol, reduce=self.reduce, **kw)

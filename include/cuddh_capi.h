@@ -252,6 +252,22 @@ int cuddh_gmres_callback_sharded(int n, void *x, cuddh_action_cb cb, void *ctx, 
                                  const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
                                  cuddh_solver_result *out, double *h_res, double *h_time);
 
+/* ---- the same five with the orthogonalisation of the Arnoldi step chosen: orth = 0 modified Gram-Schmidt (what the entry points
+ * above do), 1 = classical Gram-Schmidt applied twice (CGS2: four launches per step whatever the step, three reductions of k + 1
+ * scalars per step on the sharded path, orthogonality at working precision; m <= 512; csrc/include/cuddh/krylov.hpp).  Any other
+ * value returns nonzero before anything touches the device, cuddh_last_error() beginning "gmres error: orthogonalization". */
+int cuddh_gmres_f64_orth(int n, double *x, void *op, const double *b, void *precond /* or NULL */, int m, int maxit, double tol,
+                         int verbose, double max_seconds, int orth, cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_helmholtz_orth(void *op, double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                               int orth, cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_ddh_orth(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                         int orth, cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_callback_orth(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
+                              int verbose, double max_seconds, int orth, cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_callback_sharded_orth(int n, void *x, cuddh_action_cb cb, void *ctx, cuddh_reduce_cb reduce, void *reduce_ctx,
+                                      const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
+                                      int orth, cuddh_solver_result *out, double *h_res, double *h_time);
+
 #ifdef __cplusplus
 }
 #endif

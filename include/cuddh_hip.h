@@ -91,6 +91,28 @@ int cuddh_hip_mgs_stage_f64(int n, double *w, const double *vprev, const double 
 int cuddh_hip_mgs_stage_f32(int n, float *w, const float *vprev, const float *vnext, const float *pin, float *pout, float *hout, void *stream);
 int cuddh_hip_mgs_finish_f64(int n, double *w, const double *pin, double *hout, void *stream);
 int cuddh_hip_mgs_finish_f32(int n, float *w, const float *pin, float *hout, void *stream);
+/* Classical Gram-Schmidt against ALL k1 basis vectors V + j ldv (0 <= j < k1 <= 512) in one launch; applied twice it is the
+ * CGS2 orthogonalisation of gmres(..., Orthogonalization::cgs2).  A pass does, in this order,
+ *   update != 0:  c[j] = sum_{p < ncin} cin[j cstride + p], the same sum in every workgroup;  hout[j] = (hacc ? hacc[j] : 0) + c[j];
+ *                 w <- w - sum_j c[j] v_j, per element in ascending j with one fused multiply-add each
+ *                 (ncin = 1, cstride = 1: cin holds k1 final coefficients, e.g. behind an all-reduce)
+ *   dots == 1:    per-workgroup partial sums of <w, v_j> (of the updated w) for every j, and of <w, w>
+ *   dots == 2:    those of <w, w> only (needs update != 0)
+ * Partial layout: `pout` is a buffer of cuddh_hip_cgs_ws_bytes(k1) bytes, rows of 1024 scalars of the vectors' type; workgroup b
+ * of the g = cuddh_hip_cgs_partials(n) launched writes pout[b] (<w, w>: row 0, what mgs_finish reads as its `pin`) and
+ * pout[(1 + j) 1024 + b] (<w, v_j>).  The next pass consumes them with cin = pout + 1024, ncin = g, cstride = 1024.
+ * 16-byte accesses when w, V and (for k1 > 1) ldv * sizeof are multiples of 16 bytes, element-wise otherwise.  n == 0 does
+ * nothing; k1 outside [1, 512], ldv < n or another combination of update / dots returns hipErrorInvalidValue and launches nothing.
+ * cgs_reduce: out[j] = sum of row 1 + j (j < k1), out[k1] = sum of row 0, by the summation routine of the update's prologue
+ * (k1 == 0: the <w, w> row alone).  Fixed summation order throughout. */
+size_t cuddh_hip_cgs_ws_bytes(int k1);
+int cuddh_hip_cgs_partials(int n);
+int cuddh_hip_cgs_pass_f64(int n, double *w, const double *V, long long ldv, int k1, int update, int dots, const double *cin, int ncin, long long cstride,
+                           const double *hacc, double *hout, double *pout, void *stream);
+int cuddh_hip_cgs_pass_f32(int n, float *w, const float *V, long long ldv, int k1, int update, int dots, const float *cin, int ncin, long long cstride,
+                           const float *hacc, float *hout, float *pout, void *stream);
+int cuddh_hip_cgs_reduce_f64(int n, int k1, const double *partials, double *out, void *stream);
+int cuddh_hip_cgs_reduce_f32(int n, int k1, const float *partials, float *out, void *stream);
 int cuddh_hip_copy_f64(int n, const double *x, double *y, void *stream);
 int cuddh_hip_copy_f32(int n, const float *x, float *y, void *stream);
 int cuddh_hip_copy_i32(int n, const int *x, int *y, void *stream);
