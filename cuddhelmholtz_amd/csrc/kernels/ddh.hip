@@ -1438,8 +1438,11 @@ namespace
     // sums and stay bitwise equal.  Registers with k, l in {1, 2} are element-interior: wh_march's LEAN rules apply to them.
     // A launch whose length is no multiple of 4 is handled as ddh_wave8_kernel handles its odd tail: the missing rows
     // recompute the wavefront's first subdomain and publish nothing.
-    // The action form (no x) is compiled for three wavefronts per SIMD (167 VGPRs, no scratch), the form with x (rhs,
-    // postprocess: once per solve) needs 196 and is compiled for two.  The assembly has its DPP reads folded into the
+    // The time loop runs on register pairs (below, "the packed form"): two nodes per v_pk_fma_f32, 288 vector instructions
+    // per wavefront-step in the action form where the node-by-node loop issued 440 (294 with LAST_COPY, 299 / 294 with x against
+    // 456), bitwise the same results; 261.6 -> 201.6 ms per action at 65,536 subdomains (profiles/r16/ddh_rates_ab.txt).
+    // The action form (no x) is compiled for three wavefronts per SIMD (163 VGPRs, no scratch), the form with x (rhs,
+    // postprocess: once per solve) needs 169 and is compiled for two.  The assembly has its DPP reads folded into the
     // arithmetic by hand (below).  Measured at 65,536 subdomains, ms per action (profiles/r08/element_lane_variants.txt):
     // two wavefronts and dpp_read + FMA 271.3, three wavefronts 268.2, folded 265.7, both 258.6; the matrix form 273.9.
     // LAST_COPY (cuddh_hip_ddh_plan_set_sweep_form(plan, 3)) turns the owner rule round, so that a test can see the other
@@ -1495,6 +1498,213 @@ namespace
             }
     }
 
+    // ---- the packed form of the above (ddh_element_lane_kernel only): two nodes per 64-bit register pair, v_pk_fma_f32
+    // The loop is bound by the number of vector instructions it issues, and a v_pk_fma_f32 costs one issue for
+    // two FMAs.  Pair P = k + 4 h holds the nodes (k, l_a) in .x and (k, l_b) in .y, (l_a, l_b) = (0, 3) for h = 0 and (1, 2)
+    // for h = 1: the element-interior registers {5, 6, 9, 10} are the whole pairs 5 and 6, and the halves the assembly works
+    // on are plain 32-bit registers of the pairs.  Every half runs the chain of fp32 FMAs that element_lane_products and
+    // wh_march run for its node, written as explicit FMAs, so the results are bitwise the same -- with one change that is
+    // exact: the pairs keep hm = half_dt invm alone and not dm = dt invm = 2 hm beside it, and q += dm dq is computed as
+    // q += hm (dq + dq).  Doubling is exact in binary floating point (short of overflow, and of a subnormal hm, neither of
+    // which a stable local solve comes near), so hm (dq + dq) is the same real number as dm dq and the FMA rounds it the
+    // same.  It costs 8 v_pk_add_f32 per step and frees 16 registers: with dm the pairs need 174 at the widest point of
+    // the second sweep (a pair of the input dies only when five pairs of the result are complete, where single registers
+    // need seven) and the action form spilled 52 bytes inside the loop at three wavefronts per SIMD.
+    // Scalar registers: the coefficients are operands of the packed instruction as aligned pairs, By and Dg as the pairs
+    // the halves need, the 12 off-diagonal Bx two to a pair with op_sel choosing the half (as a broadcast scalar of its
+    // own each would take a pair); 106 are in use and none is spilled inside the time loop (a dozen wait in the lanes of
+    // one vector register across it and come back once per WaveHoltz iteration).
+    typedef float pair_t __attribute__((ext_vector_type(2)));
+    constexpr int el_pair(int k, int l) { return k + 4 * ((l == 1 || l == 2) ? 1 : 0); }
+    constexpr int el_half(int l) { return l >= 2 ? 1 : 0; }
+    constexpr unsigned ELEMENT_INTERIOR_PAIRS = (1u << 5) | (1u << 6);
+
+    __device__ inline pair_t pk_fma(pair_t a, pair_t b, pair_t c) { return __builtin_elementwise_fma(a, b, c); }
+    __device__ inline pair_t pk_fma(float a, pair_t b, pair_t c) { return __builtin_elementwise_fma(pair_t{a, a}, b, c); }
+    // t += (half HALF of the scalar-register pair c, in both halves) * w: two coefficients share an aligned pair of scalar
+    // registers (the compiler keeps a broadcast scalar of the time loop as a pair of its own with both halves the same)
+    template <int HALF>
+    __device__ inline void pk_fmac_scalar(pair_t &t, pair_t c, pair_t w)
+    {
+        if constexpr (HALF == 0)
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(t) : "s"(c), "v"(w));
+        else
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(t) : "s"(c), "v"(w));
+    }
+    // where the off-diagonal Bx(k, j) waits: half bx_slot % 2 of pair bx_slot / 2
+    constexpr int bx_slot(int k, int j) { return 3 * k + (j < k ? j : j - 1); }
+    // t += c * (half HALF of w, in both halves): the compiler broadcasts the low half through op_sel_hi but copies the high
+    // half into a pair of its own first, so op_sel is written here
+    template <int HALF>
+    __device__ inline void pk_fmac_half(pair_t &t, pair_t c, pair_t w)
+    {
+        if constexpr (HALF == 0)
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(t) : "s"(c), "v"(w));
+        else
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(t) : "s"(c), "v"(w));
+    }
+
+    // t = c * (half HALF of w, in both halves)
+    template <int HALF>
+    __device__ inline pair_t pk_mul_half(pair_t c, pair_t w)
+    {
+        pair_t t;
+        if constexpr (HALF == 0)
+            asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "s"(c), "v"(w));
+        else
+            asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(t) : "s"(c), "v"(w));
+        return t;
+    }
+
+    // element_lane_products on pairs.  A node's chain is Dg w, then for j = 0..3 the x-term (j != k) and the y-term (j != l).
+    // The x-term has one coefficient for both halves.  The y-term has the coefficient pair (By(l_a,j), By(l_b,j)) and
+    // w(k,j) from one half of pair (k, h_j); for j == l_a or l_b that is the pair itself, and only the other half has
+    // the term: one v_fmac_f32 on that half, at its place in the chain.  8 instructions per pair where the nodes took 14.
+    // The head of the chain: t = Dg w; t += c w' adds two products, and of the two the compiler of the node-by-node loop
+    // (element_lane_products under -ffp-contract=fast, read from its code object: the same in both sweeps and in all
+    // forms of the kernel) rounds c w' and fuses Dg w on the seven nodes with k == 0 or l == 0, and rounds Dg w and fuses
+    // c w' on the other nine.  The results are compared bitwise with that loop's, so the choice is kept node by node:
+    //   k != 0, pairs (1, 2):  Dg w rounded in both halves;
+    //   k != 0, pairs (0, 3):  the half l = 0 rounds Bx(k,0) w(0,0) instead: one multiplication and one FMA on that half
+    //                          replace what the two packed instructions leave there;
+    //   k == 0, pairs (1, 2):  both halves round the y-term of j = 0, By(l,0) w(0,0): packed;
+    //   k == 0, pairs (0, 3):  the half l = 0 rounds its x-term of j = 1 and the half l = 3 its y-term of j = 0: two
+    //                          multiplications, then Dg w packed, then the x-term of j = 1 on the half l = 3 alone.
+    // 71 instructions per sweep (64 + 2 for each of three pairs + 1).
+    template <int K, int H>
+    __device__ inline pair_t element_lane_pair_product(const pair_t (&w)[8], const pair_t (&Bx)[6], const float (&By)[16], const pair_t (&Dg)[8])
+    {
+        constexpr int la = H, lb = 3 - H, P = K + 4 * H, Q = K + 4 * (1 - H);
+        pair_t t;
+        // the head, through j = 0 (and for K == 0, H == 0 the x-term of j = 1)
+        if constexpr (K != 0 && H == 1)
+        {
+            t = Dg[P] * w[P];
+            pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
+            pk_fmac_half<0>(t, pair_t{By[la + 0], By[lb + 0]}, w[Q]);
+        }
+        else if constexpr (K != 0 && H == 0)
+        {
+            const float first = Bx[bx_slot(K, 0) / 2][bx_slot(K, 0) % 2] * w[0 + 4 * H].x;
+            t = Dg[P] * w[P]; // these two are for the half l = 3 (.y) alone ...
+            pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
+            t.x = __builtin_fmaf(Dg[P].x, w[P].x, first); // ... what they left in .x is replaced: the half l = 0 has the other order
+            t.y = __builtin_fmaf(By[lb + 0], w[P].x, t.y);
+        }
+        else if constexpr (K == 0 && H == 1)
+        {
+            t = pk_mul_half<0>(pair_t{By[la + 0], By[lb + 0]}, w[Q]);
+            t = pk_fma(Dg[P], w[P], t);
+        }
+        else
+        {
+            t.x = Bx[bx_slot(K, 1) / 2][bx_slot(K, 1) % 2] * w[1 + 4 * H].x;
+            t.y = By[lb + 0] * w[P].x;
+            t = pk_fma(Dg[P], w[P], t);
+            t.y = __builtin_fmaf(Bx[bx_slot(K, 1) / 2][bx_slot(K, 1) % 2], w[1 + 4 * H].y, t.y);
+        }
+        // j = 1
+        if constexpr (K != 1 && !(K == 0 && H == 0))
+            pk_fmac_scalar<bx_slot(K, 1) % 2>(t, Bx[bx_slot(K, 1) / 2], w[1 + 4 * H]);
+        if constexpr (H == 1)
+            t.y = __builtin_fmaf(By[lb + 4], w[P].x, t.y);
+        else
+            pk_fmac_half<0>(t, pair_t{By[la + 4], By[lb + 4]}, w[Q]);
+        // j = 2
+        if constexpr (K != 2)
+            pk_fmac_scalar<bx_slot(K, 2) % 2>(t, Bx[bx_slot(K, 2) / 2], w[2 + 4 * H]);
+        if constexpr (H == 1)
+            t.x = __builtin_fmaf(By[la + 8], w[P].y, t.x);
+        else
+            pk_fmac_half<1>(t, pair_t{By[la + 8], By[lb + 8]}, w[Q]);
+        // j = 3
+        if constexpr (K != 3)
+            pk_fmac_scalar<bx_slot(K, 3) % 2>(t, Bx[bx_slot(K, 3) / 2], w[3 + 4 * H]);
+        if constexpr (H == 0)
+            t.x = __builtin_fmaf(By[la + 12], w[P].y, t.x);
+        else
+            pk_fmac_half<1>(t, pair_t{By[la + 12], By[lb + 12]}, w[Q]);
+        return t;
+    }
+
+    __device__ inline void element_lane_products_packed(const pair_t (&w)[8], pair_t (&z)[8], const pair_t (&Bx)[6], const float (&By)[16],
+                                                        const pair_t (&Dg)[8])
+    {
+        z[0] = element_lane_pair_product<0, 0>(w, Bx, By, Dg);
+        z[1] = element_lane_pair_product<1, 0>(w, Bx, By, Dg);
+        z[2] = element_lane_pair_product<2, 0>(w, Bx, By, Dg);
+        z[3] = element_lane_pair_product<3, 0>(w, Bx, By, Dg);
+        z[4] = element_lane_pair_product<0, 1>(w, Bx, By, Dg);
+        z[5] = element_lane_pair_product<1, 1>(w, Bx, By, Dg);
+        z[6] = element_lane_pair_product<2, 1>(w, Bx, By, Dg);
+        z[7] = element_lane_pair_product<3, 1>(w, Bx, By, Dg);
+    }
+
+    // wh_march's RK2 loop in its LEAN forms on pairs: the same expressions with the fusions -ffp-contract=fast gives them
+    // in wh_march written out, so they do not depend on it.  INTERIOR holds a bit per pair.
+    template <int LEAN, unsigned INTERIOR, int N, typename Sweep>
+    __device__ inline void wh_march_pairs(const DdhArgs<float> &A, const int nt, const float dt, const float *__restrict__ filt,
+                                          const float *__restrict__ cs, const float *__restrict__ sn, const pair_t (&invm)[N],
+                                          const pair_t (&Hi)[N], const pair_t (&F)[N], const pair_t (&Gf)[N], pair_t (&u)[N], pair_t (&v)[N],
+                                          Sweep sweep)
+    {
+        static_assert(LEAN == 1 || LEAN == 2, "the packed loop has wh_march's LEAN forms only");
+        pair_t p[N], q[N], hm[N];
+        const float half_dt = 0.5f * dt;
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+        {
+            p[l] = q[l] = u[l] = v[l] = 0;
+            hm[l] = half_dt * invm[l];
+        }
+        for (int whit = 0; whit < A.wh_iters; ++whit)
+        {
+            const float k0 = filt[0];
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                p[l] = u[l];
+                q[l] = v[l];
+                u[l] *= k0;
+                v[l] *= k0;
+            }
+            for (int it = 1; it <= nt; ++it)
+            {
+                const float c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                const float c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                const float kw = filt[it];
+                pair_t z[N], ph[N], qh[N];
+
+                sweep(p, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    pair_t dq;
+                    if (((INTERIOR >> l) & 1u) != 0)
+                        dq = LEAN == 2 ? pk_fma(s0, Gf[l], pk_fma(c0, F[l], z[l])) : z[l];
+                    else
+                        dq = pk_fma(s0, Gf[l], pk_fma(c0, F[l], pk_fma(-Hi[l], q[l], z[l])));
+                    ph[l] = pk_fma(-half_dt, q[l], p[l]);
+                    qh[l] = pk_fma(hm[l], dq, q[l]);
+                    p[l] = pk_fma(-dt, qh[l], p[l]);
+                }
+                sweep(ph, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    pair_t dq;
+                    if (((INTERIOR >> l) & 1u) != 0)
+                        dq = LEAN == 2 ? pk_fma(s1, Gf[l], pk_fma(c1, F[l], z[l])) : z[l];
+                    else
+                        dq = pk_fma(s1, Gf[l], pk_fma(c1, F[l], pk_fma(-Hi[l], qh[l], z[l])));
+                    q[l] = pk_fma(hm[l], 2.0f * dq, q[l]);
+                    u[l] = pk_fma(kw, p[l], u[l]);
+                    v[l] = pk_fma(kw, q[l], v[l]);
+                }
+            }
+        }
+    }
+
     template <bool FORCED, bool HOLD, bool LAST_COPY>
     __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
                                                                      const float *__restrict__ cs, const float *__restrict__ sn)
@@ -1519,50 +1729,50 @@ namespace
         locate(threadIdx.x, valid, s, fdof, sI);
         const int el = threadIdx.x & 15, ex = el & 3, ey = el >> 2;
 
-        float invm[16], Hi[16], F[16], Gf[16], u[16], v[16];
+        pair_t invm[8], Hi[8], F[8], Gf[8], u[8], v[8];
 #pragma unroll
         for (int n = 0; n < 16; ++n)
         {
-            load_dof(A, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
+            const int P = el_pair(n & 3, n >> 2), half = el_half(n >> 2);
+            float im, hi, f, gf;
+            load_dof(A, s, sI[n], fdof, im, hi, f, gf);
             const float W = Sep4[48 + n], rW = Sep4[64 + n];
-            invm[n] *= W;
-            Hi[n] *= rW;
-            F[n] *= rW;
-            Gf[n] *= rW;
+            invm[P][half] = im * W;
+            Hi[P][half] = hi * rW;
+            F[P][half] = f * rW;
+            Gf[P][half] = gf * rW;
         }
-        float Bx[16], By[16], Dg[16]; // wave-uniform: scalar registers for the whole time loop
+        float By[16]; // wave-uniform: scalar registers for the whole time loop
+        pair_t Bx[6], Dg[8];
 #pragma unroll
         for (int i = 0; i < 16; ++i)
         {
-            Bx[i] = Sep4[i];      // Bx(k, j) at k + 4 j
+            if ((i & 3) != (i >> 2))
+                Bx[bx_slot(i & 3, i >> 2) / 2][bx_slot(i & 3, i >> 2) % 2] = Sep4[i]; // Bx(k, j) at k + 4 j, the off-diagonals
             By[i] = Sep4[16 + i]; // By(l, j) at l + 4 j
-            Dg[i] = Sep4[32 + i]; // Dg(k, l) at k + 4 l
+            Dg[el_pair(i & 3, i >> 2)][el_half(i >> 2)] = Sep4[32 + i]; // Dg(k, l) at k + 4 l
         }
         const float mR = ex < 3 ? 1.0f : 0.0f, mL = ex > 0 ? 1.0f : 0.0f, mU = ey < 3 ? 1.0f : 0.0f, mD = ey > 0 ? 1.0f : 0.0f;
 
-        auto sweep = [&](const float(&w)[16], float(&z)[16])
+        auto sweep = [&](const pair_t(&w)[8], pair_t(&z)[8])
         {
-            element_lane_products(w, z, Bx, By, Dg);
-            // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa)
-            float hi[4] = {z[3], z[7], z[11], z[15]}, lo[4] = {z[0], z[4], z[8], z[12]};
+            element_lane_products_packed(w, z, Bx, By, Dg);
+            // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa); the 32-bit halves of the pairs
+            float hi[4] = {z[3].x, z[7].x, z[7].y, z[3].y}, lo[4] = {z[0].x, z[4].x, z[4].y, z[0].y}; // l = 0, 1, 2, 3
             element_assemble_xi_asm(hi, lo, mR, mL);
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-            {
-                z[3 + 4 * l] = hi[l];
-                z[0 + 4 * l] = lo[l];
-            }
+            z[3].x = hi[0], z[7].x = hi[1], z[7].y = hi[2], z[3].y = hi[3];
+            z[0].x = lo[0], z[4].x = lo[1], z[4].y = lo[2], z[0].y = lo[3];
             // eta neighbours, on the xi-assembled values: my l == 3 row meets the l == 0 row of lane + 4
-            float up[4] = {z[12], z[13], z[14], z[15]}, dn[4] = {z[0], z[1], z[2], z[3]};
+            float up[4] = {z[0].y, z[1].y, z[2].y, z[3].y}, dn[4] = {z[0].x, z[1].x, z[2].x, z[3].x};
             element_assemble_eta_asm(up, dn, mU, mD);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
             {
-                z[k + 12] = up[k];
-                z[k] = dn[k];
+                z[k].y = up[k];
+                z[k].x = dn[k];
             }
         };
-        wh_march<FORCED ? 2 : 1, ELEMENT_INTERIOR_REGISTERS>(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS>(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
 
         // located a second time from a lane index the compiler cannot connect with the first: otherwise these values stay
         // in (or are spilled from) vector registers for the whole time loop, which runs at the limit of three wavefronts per SIMD
@@ -1581,7 +1791,7 @@ namespace
             const bool last = !(k == 3 && (tid & 3) < 3) && !(l == 3 && (tid & 12) < 12);
             const bool owner = LAST_COPY ? last : first;
             if (owner)
-                publish_dof(A, s, sI[n], fdof, u[n], v[n], false);
+                publish_dof(A, s, sI[n], fdof, u[el_pair(k, l)][el_half(l)], v[el_pair(k, l)][el_half(l)], false);
         }
     }
 
