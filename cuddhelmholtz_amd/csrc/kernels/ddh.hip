@@ -1434,16 +1434,19 @@ namespace
     // the same W (checked when the plan is built), so the assembled sum is W sum z' and W moves into the per-dof constants:
     // invm is multiplied by it, Hi, F and Gf are divided.  Assembly is the only cross-lane work: xi neighbours are lane +- 1,
     // eta neighbours lane +- 4, DPP row shifts that never leave the 16-lane row, so a subdomain's result does not depend on
-    // its wave-mates.  Masked FMAs, xi first and eta on the result, so the copies of a shared node form the same commutative
-    // sums and stay bitwise equal.  Registers with k, l in {1, 2} are element-interior: wh_march's LEAN rules apply to them.
+    // its wave-mates.  xi first and eta on the result; the copies of a shared node hold one sum, rounded once, and stay
+    // bitwise equal.  Registers with k, l in {1, 2} are element-interior: wh_march's LEAN rules apply to them.
     // A launch whose length is no multiple of 4 is handled as ddh_wave8_kernel handles its odd tail: the missing rows
     // recompute the wavefront's first subdomain and publish nothing.
-    // The time loop runs on register pairs (below, "the packed form"): two nodes per v_pk_fma_f32, 288 vector instructions
-    // per wavefront-step in the action form where the node-by-node loop issued 440 (294 with LAST_COPY, 299 / 294 with x against
-    // 456), bitwise the same results; 261.6 -> 201.6 ms per action at 65,536 subdomains (profiles/r16/ddh_rates_ab.txt).
-    // The action form (no x) is compiled for three wavefronts per SIMD (163 VGPRs, no scratch), the form with x (rhs,
-    // postprocess: once per solve) needs 169 and is compiled for two.  The assembly has its DPP reads folded into the
-    // arithmetic by hand (below).  Measured at 65,536 subdomains, ms per action (profiles/r08/element_lane_variants.txt):
+    // The time loop runs on register pairs (below, "the packed form"): two nodes per v_pk_fma_f32, 262 vector instructions
+    // per wavefront-step in the action form where the node-by-node loop issued 440 (264 with LAST_COPY, 273 / 272 with x against
+    // 456), bitwise the same results (profiles/r16, profiles/r17).
+    // Every form is compiled for three wavefronts per SIMD with no scratch: 168 VGPRs in the action form, 166 / 167 in
+    // the form with x (rhs, postprocess: once per solve).  The assembly is 16 DPP instructions per sweep with no mask
+    // multiplications in eta and one mask in xi (element_assemble_*_row_asm below): a shared node's sum is formed by one
+    // copy and moved to the other, and a lane without the neighbour is not written; the masked form with the DPP reads
+    // folded into the arithmetic (CUDDH_EL_ASSEMBLE, 12 per call) stays for kernel 11's xi direction.  Measured at 65,536 subdomains, ms per
+    // action, for the masked form (profiles/r08/element_lane_variants.txt):
     // two wavefronts and dpp_read + FMA 271.3, three wavefronts 268.2, folded 265.7, both 258.6; the matrix form 273.9.
     // LAST_COPY (cuddh_hip_ddh_plan_set_sweep_form(plan, 3)) turns the owner rule round, so that a test can see the other
     // copies: the results are bitwise the same.
@@ -1472,8 +1475,50 @@ namespace
                      : "v"(mHi), "v"(mLo));                                                                                                \
     }
     CUDDH_EL_ASSEMBLE(element_assemble_xi_asm, "row_shl:1", "row_shr:1")
-    CUDDH_EL_ASSEMBLE(element_assemble_eta_asm, "row_shl:4", "row_shr:4")
 #undef CUDDH_EL_ASSEMBLE
+    // The assembly of ddh_element_lane_kernel, where a 16-lane DPP row is one subdomain (kernel 11's rows hold two eta-rows
+    // and keep the masked form above).  The two copies of a shared node need the same sum: one copy forms it, the other
+    // takes it with a DPP move, and a lane without that neighbour is left unwritten instead of adding 0 * y.  8 DPP
+    // instructions per call where the masked form has 8 and 4 v_add_f32, no temporaries, and the value of every written
+    // lane is the one rounded sum it was before (x + 0 * y against x: the same for finite y, up to the sign of a zero).
+    // eta, lane +- 4: without bound_ctrl a lane whose source lies outside the row is not written, which is ey == 3 for
+    // row_shl:4 and ey == 0 for row_shr:4, so no mask operand at all.  up[i] += dn[i] of lane + 4; dn[i] = that sum of
+    // lane - 4.  A DPP read needs two wait states after the vector write of its source: the s_nop for the values the
+    // compiler wrote last, three instructions between each add and the move that reads it.
+    __device__ inline void element_assemble_eta_row_asm(float (&up)[4], float (&dn)[4])
+    {
+        asm volatile("s_nop 1\n\t"
+                     "v_add_f32_dpp %0, %4, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %1, %5, %1 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %2, %6, %2 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %3, %7, %3 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %4, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %5, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %6, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %7, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     : "+v"(up[0]), "+v"(up[1]), "+v"(up[2]), "+v"(up[3]), "+v"(dn[0]), "+v"(dn[1]), "+v"(dn[2]), "+v"(dn[3]));
+    }
+    // xi, lane +- 1: the lanes to leave out are ex == 3 and ex == 0, every fourth lane, which neither bound_ctrl nor
+    // bank_mask (four consecutive lanes) can name.  hi[i] += mHi * (lo[i] of lane + 1) as in the masked form; lo[i] = that
+    // sum of lane - 1 unless VCC holds the lane (ex == 0), through v_cndmask_b32_dpp (D = VCC ? src1 : DPP(src0)).  VCC is
+    // set inside the statement, by scalar instructions (no wait states before a vector read of it); they also stand between
+    // the compiler's last vector write and the first DPP read.
+    __device__ inline void element_assemble_xi_row_asm(float (&hi)[4], float (&lo)[4], float mHi)
+    {
+        asm volatile("s_mov_b32 vcc_lo, 0x11111111\n\t"
+                     "s_mov_b32 vcc_hi, 0x11111111\n\t"
+                     "v_fmac_f32_dpp %0, %4, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %1, %5, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %2, %6, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %3, %7, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_cndmask_b32_dpp %4, %0, %4, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %5, %1, %5, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %6, %2, %6, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %7, %3, %7, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3])
+                     : "v"(mHi)
+                     : "vcc");
+    }
     constexpr unsigned ELEMENT_INTERIOR_REGISTERS = (1u << 5) | (1u << 6) | (1u << 9) | (1u << 10);
 
     // the in-lane part of the element-lane sweep: z' = Dg w + Bx-terms + By-terms of the lane's own element, before assembly
@@ -1507,9 +1552,11 @@ namespace
     // exact: the pairs keep hm = half_dt invm alone and not dm = dt invm = 2 hm beside it, and q += dm dq is computed as
     // q += hm (dq + dq).  Doubling is exact in binary floating point (short of overflow, and of a subnormal hm, neither of
     // which a stable local solve comes near), so hm (dq + dq) is the same real number as dm dq and the FMA rounds it the
-    // same.  It costs 8 v_pk_add_f32 per step and frees 16 registers: with dm the pairs need 174 at the widest point of
-    // the second sweep (a pair of the input dies only when five pairs of the result are complete, where single registers
-    // need seven) and the action form spilled 52 bytes inside the loop at three wavefronts per SIMD.
+    // same.  It costs a v_pk_add_f32 per pair and step and frees two registers per pair: with dm for all eight the pairs
+    // need 174 at the widest point of the second sweep (a pair of the input dies only when five pairs of the result are
+    // complete, where single registers need seven) and the loop spills at three wavefronts per SIMD.  The assembly without
+    // mask registers and temporaries (element_assemble_*_row_asm) left room for dm in five pairs of the action form and in
+    // two of the form with x (ELEMENT_LANE_DM_PAIRS); the other pairs double dq.
     // Scalar registers: the coefficients are operands of the packed instruction as aligned pairs, By and Dg as the pairs
     // the halves need, the 12 off-diagonal Bx two to a pair with op_sel choosing the half (as a broadcast scalar of its
     // own each would take a pair); 106 are in use and none is spilled inside the time loop (a dozen wait in the lanes of
@@ -1518,6 +1565,9 @@ namespace
     constexpr int el_pair(int k, int l) { return k + 4 * ((l == 1 || l == 2) ? 1 : 0); }
     constexpr int el_half(int l) { return l >= 2 ? 1 : 0; }
     constexpr unsigned ELEMENT_INTERIOR_PAIRS = (1u << 5) | (1u << 6);
+    // the pairs that keep dm beside hm (wh_march_pairs' DM): as many as fit 168 vector registers, three wavefronts per SIMD,
+    // with no scratch; which pairs does not matter to the count (profiles/r17/ddh_codegen_compare.txt)
+    constexpr unsigned ELEMENT_LANE_DM_PAIRS(bool forced) { return forced ? 0x60u : 0x1fu; }
 
     __device__ inline pair_t pk_fma(pair_t a, pair_t b, pair_t c) { return __builtin_elementwise_fma(a, b, c); }
     __device__ inline pair_t pk_fma(float a, pair_t b, pair_t c) { return __builtin_elementwise_fma(pair_t{a, a}, b, c); }
@@ -1641,21 +1691,24 @@ namespace
     }
 
     // wh_march's RK2 loop in its LEAN forms on pairs: the same expressions with the fusions -ffp-contract=fast gives them
-    // in wh_march written out, so they do not depend on it.  INTERIOR holds a bit per pair.
-    template <int LEAN, unsigned INTERIOR, int N, typename Sweep>
+    // in wh_march written out, so they do not depend on it.  INTERIOR holds a bit per pair, and so does DM: a pair with its
+    // bit set keeps dm = dt invm beside hm and ends the step with q += dm dq, as wh_march does, the others with
+    // q += hm (dq + dq) (above).
+    template <int LEAN, unsigned INTERIOR, unsigned DM, int N, typename Sweep>
     __device__ inline void wh_march_pairs(const DdhArgs<float> &A, const int nt, const float dt, const float *__restrict__ filt,
                                           const float *__restrict__ cs, const float *__restrict__ sn, const pair_t (&invm)[N],
                                           const pair_t (&Hi)[N], const pair_t (&F)[N], const pair_t (&Gf)[N], pair_t (&u)[N], pair_t (&v)[N],
                                           Sweep sweep)
     {
         static_assert(LEAN == 1 || LEAN == 2, "the packed loop has wh_march's LEAN forms only");
-        pair_t p[N], q[N], hm[N];
+        pair_t p[N], q[N], hm[N], dm[N];
         const float half_dt = 0.5f * dt;
 #pragma unroll
         for (int l = 0; l < N; ++l)
         {
             p[l] = q[l] = u[l] = v[l] = 0;
             hm[l] = half_dt * invm[l];
+            dm[l] = ((DM >> l) & 1u) != 0 ? dt * invm[l] : pair_t{0.0f, 0.0f};
         }
         for (int whit = 0; whit < A.wh_iters; ++whit)
         {
@@ -1697,7 +1750,10 @@ namespace
                         dq = LEAN == 2 ? pk_fma(s1, Gf[l], pk_fma(c1, F[l], z[l])) : z[l];
                     else
                         dq = pk_fma(s1, Gf[l], pk_fma(c1, F[l], pk_fma(-Hi[l], qh[l], z[l])));
-                    q[l] = pk_fma(hm[l], 2.0f * dq, q[l]);
+                    if (((DM >> l) & 1u) != 0)
+                        q[l] = pk_fma(dm[l], dq, q[l]);
+                    else
+                        q[l] = pk_fma(hm[l], 2.0f * dq, q[l]);
                     u[l] = pk_fma(kw, p[l], u[l]);
                     v[l] = pk_fma(kw, q[l], v[l]);
                 }
@@ -1706,7 +1762,7 @@ namespace
     }
 
     template <bool FORCED, bool HOLD, bool LAST_COPY>
-    __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
+    __global__ void __launch_bounds__(256, 3) ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
                                                                      const float *__restrict__ cs, const float *__restrict__ sn)
     {
         const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -1727,7 +1783,6 @@ namespace
         int s, fdof;
         const int *sI;
         locate(threadIdx.x, valid, s, fdof, sI);
-        const int el = threadIdx.x & 15, ex = el & 3, ey = el >> 2;
 
         pair_t invm[8], Hi[8], F[8], Gf[8], u[8], v[8];
 #pragma unroll
@@ -1752,19 +1807,19 @@ namespace
             By[i] = Sep4[16 + i]; // By(l, j) at l + 4 j
             Dg[el_pair(i & 3, i >> 2)][el_half(i >> 2)] = Sep4[32 + i]; // Dg(k, l) at k + 4 l
         }
-        const float mR = ex < 3 ? 1.0f : 0.0f, mL = ex > 0 ? 1.0f : 0.0f, mU = ey < 3 ? 1.0f : 0.0f, mD = ey > 0 ? 1.0f : 0.0f;
+        const float mR = (threadIdx.x & 3) < 3 ? 1.0f : 0.0f; // ex < 3: the only mask left, for the xi sums
 
         auto sweep = [&](const pair_t(&w)[8], pair_t(&z)[8])
         {
             element_lane_products_packed(w, z, Bx, By, Dg);
             // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa); the 32-bit halves of the pairs
             float hi[4] = {z[3].x, z[7].x, z[7].y, z[3].y}, lo[4] = {z[0].x, z[4].x, z[4].y, z[0].y}; // l = 0, 1, 2, 3
-            element_assemble_xi_asm(hi, lo, mR, mL);
+            element_assemble_xi_row_asm(hi, lo, mR);
             z[3].x = hi[0], z[7].x = hi[1], z[7].y = hi[2], z[3].y = hi[3];
             z[0].x = lo[0], z[4].x = lo[1], z[4].y = lo[2], z[0].y = lo[3];
             // eta neighbours, on the xi-assembled values: my l == 3 row meets the l == 0 row of lane + 4
             float up[4] = {z[0].y, z[1].y, z[2].y, z[3].y}, dn[4] = {z[0].x, z[1].x, z[2].x, z[3].x};
-            element_assemble_eta_asm(up, dn, mU, mD);
+            element_assemble_eta_row_asm(up, dn);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
             {
@@ -1772,7 +1827,7 @@ namespace
                 z[k].x = dn[k];
             }
         };
-        wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS>(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, ELEMENT_LANE_DM_PAIRS(FORCED)>(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
 
         // located a second time from a lane index the compiler cannot connect with the first: otherwise these values stay
         // in (or are spilled from) vector registers for the whole time loop, which runs at the limit of three wavefronts per SIMD
@@ -1806,7 +1861,7 @@ namespace
     // node form the same commutative sums and stay bitwise equal.  Four wavefronts per workgroup, no barriers.  A wavefront
     // holds one subdomain, so a launch of any length needs no padding rows and a subdomain's result does not depend on
     // which others the launch holds.
-    // Compiled for three wavefronts per SIMD in the action form and two in the form with x, like the 4x4 form.
+    // Compiled for three wavefronts per SIMD in the action form and two in the form with x.
     template <bool FORCED, bool HOLD, bool LAST_COPY, typename... Grids>
     __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane8_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
                                                                                    const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
