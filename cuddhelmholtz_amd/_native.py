@@ -119,6 +119,9 @@ _sig("cuddh_hip_cgs_pass_f64", *_cgs_pass)
 _sig("cuddh_hip_cgs_pass_f32", *_cgs_pass)
 _sig("cuddh_hip_cgs_reduce_f64", ci, ci, ci, vp, vp, vp)
 _sig("cuddh_hip_cgs_reduce_f32", ci, ci, ci, vp, vp, vp)
+_krylov_update = (ci, ci, vp, vp, vp, C.c_longlong, ci, vp, C.c_longlong, ci, vp, vp, vp)
+_sig("cuddh_hip_krylov_update_f64", *_krylov_update)
+_sig("cuddh_hip_krylov_update_f32", *_krylov_update)
 _sig("cuddh_hip_nrm2_f64", ci, ci, vp, vp, vp, vp)
 _sig("cuddh_hip_nrm2_f32", ci, ci, vp, vp, vp, vp)
 for _t in ("f64", "f32", "i32"):
@@ -301,6 +304,12 @@ _sig("cuddh_gmres_helmholtz_orth", ci, vp, vp, vp, ci, ci, cd, ci, cd, ci, C.POI
 _sig("cuddh_gmres_ddh_orth", ci, ci, vp, vp, vp, ci, ci, cd, ci, cd, ci, C.POINTER(SolverResult), vp, vp)
 _sig("cuddh_gmres_callback_orth", ci, ci, vp, ACTION_CB, vp, vp, ci, ci, ci, cd, ci, cd, ci, C.POINTER(SolverResult), vp, vp)
 _sig("cuddh_gmres_callback_sharded_orth", ci, ci, vp, ACTION_CB, vp, REDUCE_CB, vp, vp, ci, ci, ci, cd, ci, cd, ci, C.POINTER(SolverResult), vp, vp)
+# (and with `int augment` behind orth: the number of corrections an LGMRES cycle is augmented with, 0 none)
+_sig("cuddh_gmres_f64_aug", ci, ci, vp, vp, vp, vp, ci, ci, cd, ci, cd, ci, ci, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_helmholtz_aug", ci, vp, vp, vp, ci, ci, cd, ci, cd, ci, ci, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_ddh_aug", ci, ci, vp, vp, vp, ci, ci, cd, ci, cd, ci, ci, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_callback_aug", ci, ci, vp, ACTION_CB, vp, vp, ci, ci, ci, cd, ci, cd, ci, ci, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_callback_sharded_aug", ci, ci, vp, ACTION_CB, vp, REDUCE_CB, vp, vp, ci, ci, ci, cd, ci, cd, ci, ci, C.POINTER(SolverResult), vp, vp)
 
 
 def last_error() -> str:

@@ -357,14 +357,16 @@ class HelmholtzOperator(_Operator):
     def action_native(self, z_in, z_out):
         N.check_capi(lib.cuddh_helmholtz_apply_native(self._h, _ptr(z_in, "f64", self._n, "z_in"), _ptr(z_out, "f64", self._n, "z_out")), "HelmholtzOperator.action_native")
 
-    def gmres(self, x, b, m: int, maxit: int, tol: float = 1e-6, verbose: int = 0, max_seconds: float = 6 * 60 * 60, orth: str = "mgs") -> "SolverOut":
+    def gmres(self, x, b, m: int, maxit: int, tol: float = 1e-6, verbose: int = 0, max_seconds: float = 6 * 60 * 60, orth: str = "mgs",
+              augment: int = 0) -> "SolverOut":
         """HelmholtzOperator::gmres: x, b in the reference ordering; iteration vectors in plan-native ordering when the plan has one.
-        orth: "mgs" or "cgs2" (see gmres)"""
+        orth: "mgs" or "cgs2"; augment: 0 or the number of corrections an LGMRES cycle is augmented with (see gmres)"""
         code = _orth_code(orth)
+        aug = _augment_count(augment, m)
         res = N.SolverResult()
         h_res = np.zeros(maxit + 2)
         h_time = np.zeros(maxit + 2)
-        N.check_capi(_gmres_entry("cuddh_gmres_helmholtz", code, (self._h, _ptr(x, "f64", self._n, "x"), _ptr(b, "f64", self._n, "b"), m, maxit, float(tol), verbose,
+        N.check_capi(_gmres_call("cuddh_gmres_helmholtz", code, aug, (self._h, _ptr(x, "f64", self._n, "x"), _ptr(b, "f64", self._n, "b"), m, maxit, float(tol), verbose,
                                                                    float(max_seconds)), res, h_res, h_time), "HelmholtzOperator.gmres")
         return _solver_out(res, h_res, h_time)
 
@@ -680,8 +682,29 @@ def _gmres_entry(name: str, code: int, head: tuple, res, h_res, h_time) -> int:
     return getattr(lib, name + "_orth")(*head, code, C.byref(res), _h(h_res), _h(h_time))
 
 
+def _augment_count(augment, m) -> int:
+    """augment as the C API takes it; anything but an integer in [0, m - 1] is a ValueError, before any native call"""
+    if isinstance(augment, bool) or not isinstance(augment, (int, np.integer)):
+        raise ValueError(f"gmres: augment must be an integer in [0, m - 1], not {augment!r}")
+    if augment < 0 or (augment > 0 and augment >= m):
+        raise ValueError(f"gmres: augment must be in [0, m - 1] = [0, {m - 1}], not {augment}")
+    return int(augment)
+
+
+def _gmres_entry_aug(name: str, code: int, augment: int, head: tuple, res, h_res, h_time) -> int:
+    """the entry point `name`_aug: orthogonalisation code and number of augmentation vectors in front of the result"""
+    return getattr(lib, name + "_aug")(*head, code, augment, C.byref(res), _h(h_res), _h(h_time))
+
+
+def _gmres_call(name: str, code: int, augment: int, head: tuple, res, h_res, h_time) -> int:
+    """augment == 0 stays on _gmres_entry (the existing entry points); augmented solves go through `name`_aug"""
+    if augment == 0:
+        return _gmres_entry(name, code, head, res, h_res, h_time)
+    return _gmres_entry_aug(name, code, augment, head, res, h_res, h_time)
+
+
 def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int = 0, max_seconds: float = 6 * 60 * 60, Precond=None,
-          reduce=None, orth: str = "mgs") -> SolverOut:
+          reduce=None, orth: str = "mgs", augment: int = 0) -> SolverOut:
     """Restarted GMRES (reference include/gmres.hpp:33-36).  A: an operator of this module, a DDH,
     or a Python callable `A(x, y)` acting on device tensors of x's dtype.
 
@@ -690,8 +713,15 @@ def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int =
 
     orth: how an Arnoldi step orthogonalises.  "mgs" (default, the reference's): modified Gram-Schmidt, one launch per basis vector
     and, with reduce=, k + 2 reductions of one scalar at step k.  "cgs2": classical Gram-Schmidt applied twice -- four launches
-    and three reductions (of k + 1, k + 1 and 1 scalars) per step whatever k is, and a basis orthogonal to working precision (m <= 512)."""
+    and three reductions (of k + 1, k + 1 and 1 scalars) per step whatever k is, and a basis orthogonal to working precision (m <= 512).
+
+    augment: 0 (default: restarted GMRES as above, bit for bit) or k in [1, m - 1]: LGMRES -- the last k corrections x_i - x_{i-1} take
+    the place of the last Krylov columns of every cycle, so that information survives the restart.  Their images under A are
+    differences of residuals the iteration has anyway: no operator application is added, a cycle with ka stored corrections
+    applies A m - ka + 1 times, and 2 k more vectors are held.  Pays where restarting stalls (many subdomains across the domain,
+    DESIGN 5.2); changes little where GMRES(m) already converges like full GMRES.  m <= 512."""
     code = _orth_code(orth)
+    aug = _augment_count(augment, m)
     import torch
 
     if reduce is not None and (isinstance(A, (DDH, _Operator)) or Precond is not None):
@@ -701,10 +731,10 @@ def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int =
     h_res = np.zeros(maxit + 2)
     h_time = np.zeros(maxit + 2)
     if isinstance(A, DDH):
-        N.check_capi(_gmres_entry("cuddh_gmres_ddh", code, (n, _ptr(x, A.trace_dtype, n, "x"), A._h, _ptr(b, A.trace_dtype, n, "b"), m, maxit, float(tol), verbose, float(max_seconds)),
+        N.check_capi(_gmres_call("cuddh_gmres_ddh", code, aug, (n, _ptr(x, A.trace_dtype, n, "x"), A._h, _ptr(b, A.trace_dtype, n, "b"), m, maxit, float(tol), verbose, float(max_seconds)),
                                   res, h_res, h_time), "gmres")
     elif isinstance(A, _Operator):
-        N.check_capi(_gmres_entry("cuddh_gmres_f64", code, (n, _ptr(x, "f64", n, "x"), A._h, _ptr(b, "f64", n, "b"), Precond._h if Precond is not None else None, m, maxit,
+        N.check_capi(_gmres_call("cuddh_gmres_f64", code, aug, (n, _ptr(x, "f64", n, "x"), A._h, _ptr(b, "f64", n, "b"), Precond._h if Precond is not None else None, m, maxit,
                                                             float(tol), verbose, float(max_seconds)), res, h_res, h_time), "gmres")
     else:
         dtype = x.dtype
@@ -736,11 +766,11 @@ def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int =
 
         cfun = N.ACTION_CB(cb)
         if reduce is None:
-            N.check_capi(_gmres_entry("cuddh_gmres_callback", code, (n, _ptr(x, dtype, n, "x"), cfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit, float(tol), verbose,
+            N.check_capi(_gmres_call("cuddh_gmres_callback", code, aug, (n, _ptr(x, dtype, n, "x"), cfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit, float(tol), verbose,
                                                                      float(max_seconds)), res, h_res, h_time), "gmres")
         else:
             rfun = N.REDUCE_CB(red)
-            N.check_capi(_gmres_entry("cuddh_gmres_callback_sharded", code, (n, _ptr(x, dtype, n, "x"), cfun, None, rfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit,
+            N.check_capi(_gmres_call("cuddh_gmres_callback_sharded", code, aug, (n, _ptr(x, dtype, n, "x"), cfun, None, rfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit,
                                                                              float(tol), verbose, float(max_seconds)), res, h_res, h_time), "gmres")
         if errors:
             raise errors[0]

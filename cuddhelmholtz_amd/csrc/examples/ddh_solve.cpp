@@ -5,7 +5,9 @@
 //   mesh is the default, the reference's; single-process path only), --integrator rk2|rk4 --coarsen N (DDHIntegrator: rk2 on
 //   the mesh grid is the default; rk4 marches ceil(nt / N) steps, N in [1, 16], 4 unless given; single-process path only),
 //   --residuals (one more line: GMRES's residual history), --orth mgs|cgs2 (the orthogonalisation of the Arnoldi step, krylov.hpp;
-//   mgs is the default, the reference's; both paths; the summary line names it when it is not mgs)
+//   mgs is the default, the reference's; both paths; the summary line names it when it is not mgs), --augment K (LGMRES: the last
+//   K corrections augment every restart cycle, krylov.hpp GmresOptions; 0 <= K < m, 0 is the default; single-process path only;
+//   the summary line names it when it is not 0)
 // Writes <out_dir>/xy.0000 and <out_dir>/ddh.0000 (raw fp64, like the reference) and prints one summary line.
 // devices >= 1: the same solve through cuddh::ddh_solve_multi_gpu (multigpu.hpp): subdomains sharded over that many GPUs of
 // this process, RCCL neighbour exchange; devices = 1 with force_rccl = 1 runs the communicator path on a one-GPU box;
@@ -27,6 +29,7 @@ int main(int argc_all, char **argv_all)
     // options out, positional arguments stay
     std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs";
     int coarsen = 0; // 0: not given
+    int augment = 0;
     bool residuals = false;
     std::vector<char *> args;
     for (int i = 0; i < argc_all; ++i)
@@ -40,6 +43,8 @@ int main(int argc_all, char **argv_all)
             coarsen = std::atoi(argv_all[++i]);
         else if (arg == "--orth" && i + 1 < argc_all)
             orth_name = argv_all[++i];
+        else if (arg == "--augment" && i + 1 < argc_all)
+            augment = std::atoi(argv_all[++i]);
         else if (arg == "--residuals")
             residuals = true;
         else
@@ -80,6 +85,12 @@ int main(int argc_all, char **argv_all)
     const std::string out_dir = argc > 7 ? argv[7] : "solution";
     const int devices = argc > 8 ? std::atoi(argv[8]) : 0;
     const int force_rccl = argc > 9 ? std::atoi(argv[9]) : 0; // transport: 0 auto, 1 RCCL also for one rank, 2 loopback (ranks share device 0)
+    if (augment < 0 || (augment > 0 && augment >= m) || (augment > 0 && devices >= 1))
+    {
+        std::cerr << "ddh_solve: --augment takes 0 to m - 1 = " << m - 1 << " on the single-process path, not " << augment << std::endl;
+        return 2;
+    }
+    const std::string aug_note = augment == 0 ? "" : " augment=" + std::to_string(augment);
 
     Mesh2D mesh = Mesh2D::uniform_rect(nx, -1.0, 1.0, nx, -1.0, 1.0);
     Basis basis(nb);
@@ -153,7 +164,7 @@ int main(int argc_all, char **argv_all)
     sync();
     const double t_rhs = seconds_since(t);
     t = clk::now();
-    solver_out out = gmres(n_lambda, d_L, &F, d_Y, m, maxit, tol, 0, 6 * 60 * 60, orth);
+    solver_out out = gmres(n_lambda, d_L, &F, d_Y, m, maxit, tol, 0, 6 * 60 * 60, GmresOptions{orth, augment});
     sync();
     const double t_gmres = seconds_since(t);
     t = clk::now();
@@ -174,7 +185,7 @@ int main(int argc_all, char **argv_all)
               << " success=" << out.success << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs
               << " t_gmres=" << t_gmres << " t_postprocess=" << t_post
-              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << std::endl;
+              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << std::endl;
     if (residuals)
     {
         std::cout << "ddh_solve time_step=" << time_step << " residuals:";

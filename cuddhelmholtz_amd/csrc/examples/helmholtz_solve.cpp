@@ -5,7 +5,8 @@
 // entry and exit); reference: gmres() on [u; v] in H1Space numbering, the call the reference's examples make.
 // a(x) = 0.2 inside the disk of radius 1/4, 1 elsewhere (interpolated at the nodes; a = 1 on the boundary), two Gaussian
 // sources as in the reference's examples.  --orth mgs|cgs2, anywhere on the line: the orthogonalisation of the Arnoldi step
-// (krylov.hpp; mgs is the default, the reference's; the summary line names it when it is not).  Prints one summary line; writes <out_dir>/xy.0000 and helmholtz.0000 unless "-".
+// (krylov.hpp; mgs is the default, the reference's; the summary line names it when it is not).  --augment K likewise: LGMRES, the
+// last K corrections augment every restart cycle (krylov.hpp GmresOptions; 0 <= K < m, 0 is the default).  Prints one summary line; writes <out_dir>/xy.0000 and helmholtz.0000 unless "-".
 #include <chrono>
 #include <cstdlib>
 #include <string>
@@ -21,11 +22,14 @@ int main(int argc_all, char **argv_all)
 {
     // options out, positional arguments stay
     std::string orth_name = "mgs";
+    int augment = 0;
     std::vector<char *> args;
     for (int i = 0; i < argc_all; ++i)
     {
         if (std::string(argv_all[i]) == "--orth" && i + 1 < argc_all)
             orth_name = argv_all[++i];
+        else if (std::string(argv_all[i]) == "--augment" && i + 1 < argc_all)
+            augment = std::atoi(argv_all[++i]);
         else
             args.push_back(argv_all[i]);
     }
@@ -45,6 +49,12 @@ int main(int argc_all, char **argv_all)
     const double tol = argc > 6 ? std::atof(argv[6]) : 1e-6;
     const std::string out_dir = argc > 7 ? argv[7] : "-";
     const bool native = !(argc > 8 && std::string(argv[8]) == "reference");
+    if (augment < 0 || (augment > 0 && augment >= m))
+    {
+        std::cerr << "helmholtz_solve: --augment takes 0 to m - 1 = " << m - 1 << ", not " << augment << std::endl;
+        return 2;
+    }
+    const GmresOptions options{orth, augment};
 
     Mesh2D mesh = Mesh2D::uniform_rect(nx, -1.0, 1.0, nx, -1.0, 1.0);
     Basis basis(nb);
@@ -81,7 +91,7 @@ int main(int argc_all, char **argv_all)
     using clk = std::chrono::steady_clock;
     detail::check_hip(cuddh_hip_stream_sync(stream()), "sync");
     const auto t0 = clk::now();
-    solver_out out = native ? A.gmres(d_U, d_b, m, maxit, tol, 0, 6 * 60 * 60, orth) : gmres(N, d_U, &A, d_b, m, maxit, tol, 0, 6 * 60 * 60, orth);
+    solver_out out = native ? A.gmres(d_U, d_b, m, maxit, tol, 0, 6 * 60 * 60, options) : gmres(N, d_U, &A, d_b, m, maxit, tol, 0, 6 * 60 * 60, options);
     detail::check_hip(cuddh_hip_stream_sync(stream()), "sync");
     const double t_gmres = std::chrono::duration<double>(clk::now() - t0).count();
 
@@ -99,6 +109,7 @@ int main(int argc_all, char **argv_all)
               << " success=" << out.success << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |U|=" << std::sqrt(unorm) << " t_gmres=" << t_gmres
               << " DoF*iter/s=" << static_cast<double>(N) * out.num_matvec / t_gmres
-              << " us_per_matvec=" << 1e6 * t_gmres / out.num_matvec << (orth_name == "mgs" ? "" : " orth=" + orth_name) << std::endl;
+              << " us_per_matvec=" << 1e6 * t_gmres / out.num_matvec << (orth_name == "mgs" ? "" : " orth=" + orth_name)
+              << (augment == 0 ? "" : " augment=" + std::to_string(augment)) << std::endl;
     return 0;
 }

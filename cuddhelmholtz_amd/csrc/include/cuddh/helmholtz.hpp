@@ -55,6 +55,8 @@ namespace cuddh
         /// orth: krylov.hpp (Orthogonalization::cgs2: four launches per Arnoldi step whatever the step)
         solver_out gmres(double *x, const double *b, int m, int maxit, double tol = 1e-6, int verbose = 0, double max_seconds = 6 * 60 * 60,
                          Orthogonalization orth = Orthogonalization::mgs) const;
+        /// the same with every option of krylov.hpp (GmresOptions: orth, and augment = k for LGMRES)
+        solver_out gmres(double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds, const GmresOptions &opt) const;
 
         /// bytes per apply: algorithmic (SURVEY 8d formula) or as laid out by the plan
         std::size_t bytes_per_apply(bool actual) const;

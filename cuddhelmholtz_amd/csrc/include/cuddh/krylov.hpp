@@ -72,6 +72,32 @@ namespace cuddh
                      double max_seconds, const ScalarReduce &reduce, Orthogonalization orth);
     solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
                      double max_seconds, const ScalarReduce &reduce, Orthogonalization orth);
+
+    /// Options of the iteration beyond the reference's.
+    /// augment = k, 0 <= k < m (an error otherwise; 0, the default, is the iteration above bit for bit): LGMRES (Baker, Jessup and
+    /// Manteuffel's "loose GMRES").  The last k corrections z_i = (x_i - x_{i-1}) / |x_i - x_{i-1}| and their images A z_i are kept, most
+    /// recent first (2 k vectors beside the m + 1 of the basis), and take the place of the last min(k, stored) columns of every cycle:
+    /// a cycle still has at most m columns, columns j < m - ka are Krylov columns (w = A v_j, one operator application), column
+    /// m - ka + p searches along z_p with w a copy of A z_p (no operator application, num_matvec unchanged).  w is orthogonalised
+    /// and the least-squares problem updated as always, under either orthogonalisation and with partitioned vectors.  At the end of
+    /// a cycle dx = sum_j y_j u_j and x <- x + dx in one launch (cuddh_hip_krylov_update_*), and the new pair is dx / |dx| and
+    /// (r_old - r_new) / |dx| from the two true residuals the iteration has anyway (none when |dx| = 0).  m <= 512.  Operators that
+    /// only queue device work stay driven one step ahead: an augmentation column is a device copy.
+    struct GmresOptions
+    {
+        Orthogonalization orth = Orthogonalization::mgs;
+        int augment = 0;
+    };
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, const Operator *Precond, int m, int maxit, double tol, int verbose,
+                     double max_seconds, const GmresOptions &opt);
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                     const GmresOptions &opt);
+    solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
+                     double max_seconds, const GmresOptions &opt);
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose,
+                     double max_seconds, const ScalarReduce &reduce, const GmresOptions &opt);
+    solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
+                     double max_seconds, const ScalarReduce &reduce, const GmresOptions &opt);
 } // namespace cuddh
 
 #endif

@@ -808,6 +808,129 @@ namespace
         return launch_status();
     }
 
+    // ---------------- solution update of an augmented GMRES cycle (krylov.cpp, augment > 0)
+    //   d = sum_j coef[j] V_j + sum_p coef[nvc + p] Z_p   per element: from 0, one fused multiply-add per column, V in ascending j, then Z in ascending p
+    //   dx <- d;  x <- x + d;  pout[block] = partial sum of d^2   (row 0 of a cgs_pass buffer: cgs_reduce with k1 = 0 finishes it)
+    // One launch instead of a chain of nvc + nz axpby on x: x is read and written once, (nvc + nz + 3) n scalars move instead of
+    // 3 (nvc + nz) n.  Tiles, clamped requests and the chunking of the columns (CGS_KC at a time, the V columns and the Z columns as
+    // one sequence) as in cgs_pass_kernel; every operand is touched once, so vectors beyond the infinity cache go with the
+    // non-temporal hint (map_kernel).  The coefficients sit in LDS.  dx overlaps no input.
+    template <typename T, bool NT>
+    __global__ void __launch_bounds__(BLOCK) krylov_update_kernel(int n, T *__restrict__ x, T *__restrict__ dx, const T *__restrict__ V, size_t ldv, int nvc,
+                                                                  const T *__restrict__ Z, size_t ldz, int nz, const T *__restrict__ coef,
+                                                                  T *__restrict__ pout, int vectorised)
+    {
+        __shared__ T c_sh[CGS_KMAX];
+        using VE = T __attribute__((ext_vector_type(Pack<T>::N)));
+        constexpr int N = Pack<T>::N;
+        const int nc = nvc + nz;
+        const int nv = vectorised ? n / N : 0;
+        const int n_tiles = (nv + TILE - 1) / TILE;
+        VE *xv = reinterpret_cast<VE *>(x), *dv = reinterpret_cast<VE *>(dx);
+        // column j of the sequence V_0 .. V_{nvc-1}, Z_0 .. Z_{nz-1} (clamped to the last one: a chunk's requests carry no branch)
+        auto column = [&](int j)
+        {
+            j = min(j, nc - 1);
+            return j < nvc ? V + static_cast<size_t>(j) * ldv : Z + static_cast<size_t>(j - nvc) * ldz;
+        };
+        auto request_chunk = [&](int tile, int j0, VE(&b)[CGS_KC][UNROLL])
+        {
+#pragma unroll
+            for (int q = 0; q < CGS_KC; ++q)
+            {
+                const VE *uj = reinterpret_cast<const VE *>(column(j0 + q));
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u)
+                    b[q][u] = stream_load<NT>(uj + min(tile * TILE + (int)threadIdx.x + u * BLOCK, nv - 1));
+            }
+        };
+
+        for (int j = threadIdx.x; j < nc; j += BLOCK)
+            c_sh[j] = coef[j];
+        __syncthreads();
+
+        T dd = T(0);
+        for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
+        {
+            const int base = tile * TILE + threadIdx.x;
+            VE a[UNROLL], d[UNROLL], b[CGS_KC][UNROLL];
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u)
+            {
+                a[u] = stream_load<NT>(xv + min(base + u * BLOCK, nv - 1));
+#pragma unroll
+                for (int e = 0; e < N; ++e)
+                    d[u][e] = T(0);
+            }
+            for (int j0 = 0; j0 < nc; j0 += CGS_KC)
+            {
+                request_chunk(tile, j0, b);
+#pragma unroll
+                for (int q = 0; q < CGS_KC; ++q)
+                    if (j0 + q < nc) // (uniform)
+                    {
+                        const T c = c_sh[j0 + q];
+#pragma unroll
+                        for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+                            for (int e = 0; e < N; ++e)
+                                d[u][e] = fmadd(c, b[q][u][e], d[u][e]);
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u)
+                if (base + u * BLOCK < nv)
+                {
+#pragma unroll
+                    for (int e = 0; e < N; ++e)
+                    {
+                        a[u][e] = a[u][e] + d[u][e];
+                        dd = fmadd(d[u][e], d[u][e], dd);
+                    }
+                    stream_store<NT>(dv + base + u * BLOCK, d[u]);
+                    stream_store<NT>(xv + base + u * BLOCK, a[u]);
+                }
+        }
+
+        // scalar tail (everything, when an operand is not 16-byte aligned)
+        const int tid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
+        for (int i = nv * N + tid; i < n; i += stride)
+        {
+            T d = T(0);
+            for (int j = 0; j < nvc; ++j)
+                d = fmadd(c_sh[j], V[static_cast<size_t>(j) * ldv + i], d);
+            for (int p = 0; p < nz; ++p)
+                d = fmadd(c_sh[nvc + p], Z[static_cast<size_t>(p) * ldz + i], d);
+            dx[i] = d;
+            x[i] = x[i] + d;
+            dd = fmadd(d, d, dd);
+        }
+
+        const T s = block_sum(dd);
+        if (threadIdx.x == 0)
+            pout[blockIdx.x] = s;
+    }
+
+    template <typename T>
+    int launch_krylov_update(int n, T *x, T *dx, const T *V, long long ldv, int nvc, const T *Z, long long ldz, int nz, const T *coef, T *pout, void *stream)
+    {
+        if (n < 0 || nvc < 1 || nz < 0 || nvc + nz > CGS_KMAX || (nvc > 1 && ldv < n) || (nz > 1 && ldz < n))
+            return static_cast<int>(hipErrorInvalidValue);
+        if (n == 0)
+            return 0;
+        const int g = mgs_grid(n);
+        const int vec = aligned16(x) && aligned16(dx) && aligned16(V) && (nvc == 1 || ldv % Pack<T>::N == 0) &&
+                        (nz == 0 || (aligned16(Z) && (nz == 1 || ldz % Pack<T>::N == 0)));
+        const dim3 grid(g), block(BLOCK);
+        hipStream_t st = as_stream(stream);
+        const size_t lv = static_cast<size_t>(ldv), lz = static_cast<size_t>(ldz);
+        if (static_cast<long long>(n) * sizeof(T) >= NT_BYTES)
+            hipLaunchKernelGGL((krylov_update_kernel<T, true>), grid, block, 0, st, n, x, dx, V, lv, nvc, Z, lz, nz, coef, pout, vec);
+        else
+            hipLaunchKernelGGL((krylov_update_kernel<T, false>), grid, block, 0, st, n, x, dx, V, lv, nvc, Z, lz, nz, coef, pout, vec);
+        return launch_status();
+    }
+
     // ---------------- indexed maps
     __global__ void __launch_bounds__(BLOCK) gather_kernel(int n, const int *__restrict__ proj, const double *__restrict__ x, double *__restrict__ y)
     {
@@ -940,6 +1063,16 @@ extern "C"
     }
     int cuddh_hip_cgs_reduce_f64(int n, int k1, const double *partials, double *out, void *s) { return launch_cgs_reduce<double>(n, k1, partials, out, s); }
     int cuddh_hip_cgs_reduce_f32(int n, int k1, const float *partials, float *out, void *s) { return launch_cgs_reduce<float>(n, k1, partials, out, s); }
+    int cuddh_hip_krylov_update_f64(int n, double *x, double *dx, const double *V, long long ldv, int nv, const double *Z, long long ldz, int nz,
+                                    const double *coef, double *pout, void *s)
+    {
+        return launch_krylov_update<double>(n, x, dx, V, ldv, nv, Z, ldz, nz, coef, pout, s);
+    }
+    int cuddh_hip_krylov_update_f32(int n, float *x, float *dx, const float *V, long long ldv, int nv, const float *Z, long long ldz, int nz,
+                                    const float *coef, float *pout, void *s)
+    {
+        return launch_krylov_update<float>(n, x, dx, V, ldv, nv, Z, ldz, nz, coef, pout, s);
+    }
 
     int cuddh_hip_axpby_f64(int n, double a, const double *x, double b, double *y, void *s)
     {

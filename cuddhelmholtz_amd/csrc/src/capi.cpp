@@ -49,6 +49,17 @@ namespace
         throw std::runtime_error("gmres error: orthogonalization must be 0 (mgs) or 1 (cgs2), not " + std::to_string(orth) + ".");
     }
 
+    // likewise: orth as above, augment in [0, m - 1]
+    GmresOptions options_of(int orth, int augment, int m)
+    {
+        GmresOptions o;
+        o.orth = orth_of(orth);
+        if (augment < 0 || (augment > 0 && augment >= m))
+            throw std::runtime_error("gmres error: augment must be in [0, m - 1], not " + std::to_string(augment) + ".");
+        o.augment = augment;
+        return o;
+    }
+
     template <typename T, typename F>
     T *guarded_new(F &&f)
     {
@@ -1224,6 +1235,94 @@ extern "C"
         return guarded([&]
         {
             const Orthogonalization o_ = orth_of(orth);
+            solver_out o;
+            const ScalarReduce red{reduce, reduce_ctx};
+            if (is_f64)
+            {
+                CallbackOp64 A(cb, ctx);
+                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, red, o_);
+            }
+            else
+            {
+                CallbackOp32 A(cb, ctx);
+                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
+                          max_seconds, red, o_);
+            }
+            fill_result(o, out, h_res, h_time);
+        });
+    }
+
+    // ------------------------------------------------------------ GMRES with orthogonalisation and augmentation chosen (augment = k: LGMRES)
+    int cuddh_gmres_f64_aug(int n, double *x, void *op, const double *b, void *precond, int m, int maxit, double tol, int verbose,
+                            double max_seconds, int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        return guarded([&]
+        {
+            const GmresOptions o_ = options_of(orth, augment, m);
+            const Operator *A = static_cast<OpHandle *>(op)->op.get();
+            solver_out o = precond ? gmres(n, x, A, b, static_cast<OpHandle *>(precond)->op.get(), m, maxit, tol, verbose, max_seconds, o_)
+                                   : gmres(n, x, A, b, m, maxit, tol, verbose, max_seconds, o_);
+            fill_result(o, out, h_res, h_time);
+        });
+    }
+
+    int cuddh_gmres_helmholtz_aug(void *op, double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                                  int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        return guarded([&]
+        {
+            const GmresOptions o_ = options_of(orth, augment, m);
+            solver_out o = helm_of(op).gmres(x, b, m, maxit, tol, verbose, max_seconds, o_);
+            fill_result(o, out, h_res, h_time);
+        });
+    }
+
+    int cuddh_gmres_ddh_aug(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                            int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        return guarded([&]
+        {
+            const GmresOptions o_ = options_of(orth, augment, m);
+            auto *h = static_cast<DdhHandle *>(ddh);
+            solver_out o;
+            if (h->is64())
+                o = gmres(n, static_cast<double *>(x), h->f64.get(), static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
+            else
+                o = gmres(n, static_cast<float *>(x), h->f32.get(), static_cast<const float *>(b), m, maxit, static_cast<float>(tol),
+                          verbose, max_seconds, o_);
+            fill_result(o, out, h_res, h_time);
+        });
+    }
+
+    int cuddh_gmres_callback_aug(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
+                                 int verbose, double max_seconds, int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        return guarded([&]
+        {
+            const GmresOptions o_ = options_of(orth, augment, m);
+            solver_out o;
+            if (is_f64)
+            {
+                CallbackOp64 A(cb, ctx);
+                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
+            }
+            else
+            {
+                CallbackOp32 A(cb, ctx);
+                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
+                          max_seconds, o_);
+            }
+            fill_result(o, out, h_res, h_time);
+        });
+    }
+
+    int cuddh_gmres_callback_sharded_aug(int n, void *x, cuddh_action_cb cb, void *ctx, cuddh_reduce_cb reduce, void *reduce_ctx,
+                                         const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
+                                         int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        return guarded([&]
+        {
+            const GmresOptions o_ = options_of(orth, augment, m);
             solver_out o;
             const ScalarReduce red{reduce, reduce_ctx};
             if (is_f64)

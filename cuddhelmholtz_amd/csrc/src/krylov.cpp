@@ -35,6 +35,14 @@ namespace cuddh
         }
         inline int k_cgs_reduce(int n, int k1, const double *p, double *out) { return cuddh_hip_cgs_reduce_f64(n, k1, p, out, stream()); }
         inline int k_cgs_reduce(int n, int k1, const float *p, float *out) { return cuddh_hip_cgs_reduce_f32(n, k1, p, out, stream()); }
+        inline int k_update(int n, double *x, double *dx, const double *V, long long ldv, int nv, const double *Z, long long ldz, int nz, const double *coef, double *pout)
+        {
+            return cuddh_hip_krylov_update_f64(n, x, dx, V, ldv, nv, Z, ldz, nz, coef, pout, stream());
+        }
+        inline int k_update(int n, float *x, float *dx, const float *V, long long ldv, int nv, const float *Z, long long ldz, int nz, const float *coef, float *pout)
+        {
+            return cuddh_hip_krylov_update_f32(n, x, dx, V, ldv, nv, Z, ldz, nz, coef, pout, stream());
+        }
 
         // apply the k previous rotations to column h, then build rotation k that zeroes h[k+1]
         template <typename scalar>
@@ -92,7 +100,7 @@ namespace cuddh
 
         template <typename scalar, typename Op>
         solver_out arnoldi_restarted(int n, scalar *x, const Op *A, const scalar *b, int m, int maxit, scalar tol, int verbose,
-                                     double max_seconds, const ScalarReduce *red = nullptr, Orthogonalization orth = Orthogonalization::mgs)
+                                     double max_seconds, const ScalarReduce *red = nullptr, Orthogonalization orth = Orthogonalization::mgs, int augment = 0)
         {
             using clock = std::chrono::high_resolution_clock;
             const scalar one = 1, zero = 0;
@@ -104,9 +112,15 @@ namespace cuddh
                 cuddh_error("gmres error: orthogonalization must be mgs or cgs2.");
             if (cgs2 && m > 512)
                 cuddh_error("gmres error: orthogonalization cgs2 takes restart lengths up to 512 (one launch covers the whole basis).");
-            // distance of two basis vectors: n; under cgs2 rounded up to 16 bytes, so that one launch may read all of them as 16-byte vectors
+            // augment = k > 0 (LGMRES, krylov.hpp): the last k corrections z and their images A z take the place of the last Krylov columns
+            if (augment < 0 || (augment > 0 && augment >= m))
+                cuddh_error("gmres error: augment must be in [0, m - 1].");
+            if (augment > 0 && m > 512)
+                cuddh_error("gmres error: augment takes restart lengths up to 512 (one launch of the update covers every column).");
+            // distance of two basis vectors: n; under cgs2 and with augment > 0 rounded up to 16 bytes, so that one launch may read all of
+            // them as 16-byte vectors
             constexpr std::size_t per16 = 16 / sizeof(scalar);
-            const std::size_t ldv = cgs2 ? (static_cast<std::size_t>(n) + per16 - 1) / per16 * per16 : static_cast<std::size_t>(n);
+            const std::size_t ldv = (cgs2 || augment > 0) ? (static_cast<std::size_t>(n) + per16 - 1) / per16 * per16 : static_cast<std::size_t>(n);
 
             HostDeviceArray<scalar> r_store(n), V_store(ldv * m1), col_store(m1 + 1);
             scalar *r = r_store.device_write();
@@ -143,6 +157,28 @@ namespace cuddh
                 n_part = cuddh_hip_cgs_partials(n);
             }
             Guard cgs_guard{cgs_ws};
+
+            // augment: the pairs (z_p, A z_p), most recent first, ldv apart like the basis; the correction of a cycle; on the device the
+            // coefficients of the update, a row of partial sums of |dx|^2 (the <w, w> row of a cgs pass) and their sum
+            HostDeviceArray<scalar> Z_store, AZ_store, dx_store;
+            scalar *Zs = nullptr, *AZs = nullptr, *dxv = nullptr, *d_part = nullptr, *d_coef = nullptr, *d_dxx = nullptr;
+            void *aug_ws = nullptr;
+            if (augment > 0)
+            {
+                Z_store.resize(static_cast<int>(ldv * augment));
+                AZ_store.resize(static_cast<int>(ldv * augment));
+                dx_store.resize(n);
+                Zs = Z_store.device_write();
+                AZs = AZ_store.device_write();
+                dxv = dx_store.device_write();
+                const std::size_t prow = cuddh_hip_cgs_ws_bytes(0);
+                detail::check_hip(cuddh_hip_malloc_zeroed(&aug_ws, prow + (m + 1) * sizeof(double)), "gmres augmentation workspace");
+                d_part = static_cast<scalar *>(aug_ws);
+                d_coef = reinterpret_cast<scalar *>(static_cast<char *>(aug_ws) + prow);
+                d_dxx = d_coef + m;
+            }
+            Guard aug_guard{aug_ws};
+            int n_pairs = 0;
 
             // Operators that only queue device work (operator.hpp: QueuesDeviceWorkOnly) are driven one Arnoldi step ahead of the host:
             // two pinned Hessenberg columns and two events
@@ -218,6 +254,16 @@ namespace cuddh
             for (; it < maxit; ++it)
             {
                 axpby(n, one / r_nrm, r, zero, V); // v0 = r / ||r||
+                // columns k < n_krylov are Krylov columns (w = A v_k); column n_krylov + p takes w = A z_p from the stored pair: a copy,
+                // no operator application (augment = 0: n_krylov = m)
+                const int n_krylov = m - std::min(augment, n_pairs);
+                auto next_w = [&](int k, const scalar *vk, scalar *vk1)
+                {
+                    if (k < n_krylov)
+                        A->action(vk, vk1);
+                    else
+                        copy(n, AZs + static_cast<std::size_t>(k - n_krylov) * ldv, vk1);
+                };
                 std::fill(eta.begin(), eta.end(), zero);
                 eta[0] = r_nrm;
 
@@ -242,7 +288,7 @@ namespace cuddh
                 {
                     scalar *vk = V + static_cast<std::size_t>(k) * ldv;
                     scalar *vk1 = vk + ldv;
-                    A->action(vk, vk1);
+                    next_w(k, vk, vk1);
                     if (cgs2)
                         queue_step_cgs2(k, vk1);
                     else
@@ -280,7 +326,7 @@ namespace cuddh
                     {
                         // partitioned vectors: the k + 1 sums of a pass are reduced over the ranks in one call, and the next pass reads
                         // the reduced coefficients (ncin = 1); three reductions per step
-                        A->action(vk, vk1);
+                        next_w(k, vk, vk1);
                         const scalar *none = nullptr;
                         detail::check_hip(k_cgs_pass(n, vk1, V, ldv, k1, 0, 1, none, 0, 0, none, static_cast<scalar *>(nullptr), pA), "gmres cgs2 pass");
                         detail::check_hip(k_cgs_reduce(n, k1, pA, dcol), "gmres cgs2 reduce");
@@ -297,7 +343,7 @@ namespace cuddh
                     }
                     else if (red)
                     {
-                        A->action(vk, vk1);
+                        next_w(k, vk, vk1);
                         // partitioned vectors: every coefficient is summed over the ranks before it is applied
                         for (int j = 0; j < k1; ++j)
                         {
@@ -330,7 +376,8 @@ namespace cuddh
                         detail::check_hip(cuddh_hip_stream_sync(stream()), "gmres sync");
                         detail::check_hip(cuddh_hip_copy_d2h_on(h, dcol, sizeof(scalar) * (k1 + 1), stream()), "gmres column copy");
                     }
-                    out.num_matvec++;
+                    if (k < n_krylov)
+                        out.num_matvec++;
 
                     if (h[k1] == zero)
                         break;
@@ -344,8 +391,37 @@ namespace cuddh
                 }
 
                 back_substitute(k1, H.data(), m1, eta.data());
-                for (int k = 0; k < k1; ++k)
-                    axpby(n, eta[k], V + static_cast<std::size_t>(k) * ldv, one, x);
+                scalar dx_nrm = zero;
+                if (augment == 0)
+                    for (int k = 0; k < k1; ++k)
+                        axpby(n, eta[k], V + static_cast<std::size_t>(k) * ldv, one, x);
+                else
+                {
+                    // dx = sum_j y_j u_j (u_j = v_j, then z_p), x <- x + dx and the partial sums of |dx|^2 in one launch
+                    const int nv = std::min(k1, n_krylov), nz = k1 - nv;
+                    scalar dxx = zero;
+                    detail::check_hip(cuddh_hip_copy_h2d_on(d_coef, eta.data(), sizeof(scalar) * k1, stream()), "gmres update coefficients");
+                    detail::check_hip(k_update(n, x, dxv, V, static_cast<long long>(ldv), nv, Zs, static_cast<long long>(ldv), nz, d_coef, d_part), "gmres update");
+                    detail::check_hip(k_cgs_reduce(n, 0, d_part, d_dxx), "gmres update reduce");
+                    if (n == 0) // (a rank without entries: nothing was launched)
+                        detail::check_hip(cuddh_hip_copy_h2d_on(d_dxx, &dxx, sizeof(scalar), stream()), "gmres update norm");
+                    if (red)
+                        red->fn(red->user, d_dxx, 1, is_f64);
+                    detail::check_hip(cuddh_hip_stream_sync(stream()), "gmres sync");
+                    detail::check_hip(cuddh_hip_copy_d2h_on(&dxx, d_dxx, sizeof(scalar), stream()), "gmres update norm");
+                    dx_nrm = std::sqrt(dxx);
+                }
+                // a new pair: the older ones move back by one place (the oldest of `augment` is dropped), r_old waits in the first
+                const bool new_pair = dx_nrm > zero;
+                if (new_pair)
+                {
+                    for (int p = std::min(n_pairs, augment - 1); p >= 1; --p)
+                    {
+                        copy(n, Zs + static_cast<std::size_t>(p - 1) * ldv, Zs + static_cast<std::size_t>(p) * ldv);
+                        copy(n, AZs + static_cast<std::size_t>(p - 1) * ldv, AZs + static_cast<std::size_t>(p) * ldv);
+                    }
+                    copy(n, r, AZs);
+                }
 
                 A->action(x, r);
                 out.num_matvec++;
@@ -389,6 +465,14 @@ namespace cuddh
                 {
                     out.success = true;
                     break;
+                }
+
+                if (new_pair)
+                {
+                    // another cycle follows: z = dx / |dx|,  A z = (r_old - r_new) / |dx|, no operator application
+                    axpby(n, -one / dx_nrm, r, one / dx_nrm, AZs);
+                    axpby(n, one / dx_nrm, dxv, zero, Zs);
+                    n_pairs = std::min(n_pairs + 1, augment);
                 }
             }
 
@@ -443,6 +527,40 @@ namespace cuddh
                      double max_seconds, const ScalarReduce &reduce, Orthogonalization orth)
     {
         return arnoldi_restarted<float>(n, x, A, b, m, maxit, tol, verbose, max_seconds, reduce.fn ? &reduce : nullptr, orth);
+    }
+
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                     const GmresOptions &opt)
+    {
+        return arnoldi_restarted<double>(n, x, A, b, m, maxit, tol, verbose, max_seconds, nullptr, opt.orth, opt.augment);
+    }
+
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, const Operator *Precond, int m, int maxit, double tol, int verbose,
+                     double max_seconds, const GmresOptions &opt)
+    {
+        LeftPreconditioned PA(n, A, Precond);
+        host_device_dvec Pb(n);
+        double *d_Pb = Pb.device_write();
+        Precond->action(b, d_Pb);
+        return arnoldi_restarted<double>(n, x, &PA, d_Pb, m, maxit, tol, verbose, max_seconds, nullptr, opt.orth, opt.augment);
+    }
+
+    solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
+                     double max_seconds, const GmresOptions &opt)
+    {
+        return arnoldi_restarted<float>(n, x, A, b, m, maxit, tol, verbose, max_seconds, nullptr, opt.orth, opt.augment);
+    }
+
+    solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose,
+                     double max_seconds, const ScalarReduce &reduce, const GmresOptions &opt)
+    {
+        return arnoldi_restarted<double>(n, x, A, b, m, maxit, tol, verbose, max_seconds, reduce.fn ? &reduce : nullptr, opt.orth, opt.augment);
+    }
+
+    solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
+                     double max_seconds, const ScalarReduce &reduce, const GmresOptions &opt)
+    {
+        return arnoldi_restarted<float>(n, x, A, b, m, maxit, tol, verbose, max_seconds, reduce.fn ? &reduce : nullptr, opt.orth, opt.augment);
     }
 
     solver_out gmres(int n, double *x, const Operator *A, const double *b, const Operator *Precond, int m, int maxit,

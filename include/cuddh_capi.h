@@ -268,6 +268,24 @@ int cuddh_gmres_callback_sharded_orth(int n, void *x, cuddh_action_cb cb, void *
                                       const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
                                       int orth, cuddh_solver_result *out, double *h_res, double *h_time);
 
+/* ---- the `_orth` five with `int augment` behind the orthogonalisation code: augment = k > 0 is LGMRES -- the last k corrections
+ * x_i - x_{i-1} (normalised) and their images under the operator are kept and take the place of the last Krylov columns of every
+ * cycle; their images are differences of residuals the iteration computes anyway, so no operator application is added and
+ * num_matvec counts what was applied (csrc/include/cuddh/krylov.hpp: GmresOptions).  augment = 0 is the `_orth` entry point bit
+ * for bit.  augment < 0 or >= m returns nonzero before anything touches the device, cuddh_last_error() beginning
+ * "gmres error: augment". */
+int cuddh_gmres_f64_aug(int n, double *x, void *op, const double *b, void *precond /* or NULL */, int m, int maxit, double tol,
+                        int verbose, double max_seconds, int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_helmholtz_aug(void *op, double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                              int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_ddh_aug(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                        int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_callback_aug(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
+                             int verbose, double max_seconds, int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_callback_sharded_aug(int n, void *x, cuddh_action_cb cb, void *ctx, cuddh_reduce_cb reduce, void *reduce_ctx,
+                                     const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
+                                     int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,20 @@ int cuddh_hip_cgs_pass_f32(int n, float *w, const float *V, long long ldv, int k
                            const float *hacc, float *hout, float *pout, void *stream);
 int cuddh_hip_cgs_reduce_f64(int n, int k1, const double *partials, double *out, void *stream);
 int cuddh_hip_cgs_reduce_f32(int n, int k1, const float *partials, float *out, void *stream);
+/* Solution update of an augmented GMRES cycle (gmres(..., GmresOptions{orth, augment > 0})), one launch.  Every operand is a
+ * device pointer.  Per element i, d starts at 0 and takes one fused multiply-add per column: coef[j] * V[j ldv + i] for
+ * 0 <= j < nv in ascending j, then coef[nv + p] * Z[p ldz + i] for 0 <= p < nz in ascending p.  Then dx[i] = d and
+ * x[i] = x[i] + d.  Workgroup b of the cuddh_hip_cgs_partials(n) launched writes its partial sum of d^2 to pout[b]: row 0 of the
+ * partial layout above, so cuddh_hip_cgs_reduce_*(n, 0, pout, out) leaves sum d^2 in out[0].  (nv + nz + 3) n scalars move,
+ * against 3 (nv + nz) n of the axpby chain on x.  nv >= 1, nz >= 0 (Z is not read then), nv + nz <= 512.
+ * 16-byte accesses when x, dx, V, Z and (for more than one column) ldv * sizeof and ldz * sizeof are multiples of 16 bytes,
+ * element-wise otherwise; fixed summation order; vectors of 64 MiB and more are streamed with the non-temporal hint.
+ * n == 0 does nothing; nv < 1, nz < 0, nv + nz > 512, ldv < n with nv > 1 or ldz < n with nz > 1 returns hipErrorInvalidValue and
+ * launches nothing.  dx must not overlap x, V, Z or coef. */
+int cuddh_hip_krylov_update_f64(int n, double *x, double *dx, const double *V, long long ldv, int nv, const double *Z, long long ldz, int nz,
+                                const double *coef, double *pout, void *stream);
+int cuddh_hip_krylov_update_f32(int n, float *x, float *dx, const float *V, long long ldv, int nv, const float *Z, long long ldz, int nz,
+                                const float *coef, float *pout, void *stream);
 int cuddh_hip_copy_f64(int n, const double *x, double *y, void *stream);
 int cuddh_hip_copy_f32(int n, const float *x, float *y, void *stream);
 int cuddh_hip_copy_i32(int n, const int *x, int *y, void *stream);
