@@ -180,6 +180,7 @@ _sig("cuddh_hip_ddh_plan_set_wave_priority", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_set_sweep_form", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_sweep_form", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_owner_rule", ci, vp, ci)
+_sig("cuddh_element_lane_tables", ci, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_set_time_grids", ci, vp, ci, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_time_grids", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_integrator", ci, vp, ci)

@@ -419,7 +419,9 @@ class DDH:
 
     block: elements per subdomain side.  None, 0 or 16 / n_basis is the reference's size; any block >= 1 with
     n_basis^2 block^2 <= 1024 that divides nx and ny is accepted, anything else raises here.  Off the reference's size the
-    kernels are 1 (any block) and 11 (n_basis 4, block 8, 'f32': one 8x8 block per wavefront; what auto picks there).  Larger
+    kernels are 1 (any block), 11 (n_basis 4, block 8, 'f32': one 8x8 block per wavefront; what auto picks there) and 12
+    (n_basis 5, block 4, 'f32', rectangles: one element per lane, four 4x4 blocks per wavefront; time_step "mesh" and "rk2"
+    only; what auto picks there from the subdomain count at which it measured faster than kernel 1).  Larger
     subdomains need fewer GMRES iterations and shorter Krylov vectors but more WaveHoltz iterations (set_wh_iters) for the
     same accuracy.  info()["nel1d"] reports the block in effect.
 
@@ -616,7 +618,7 @@ class DDH:
         return form
 
     def set_owner_rule(self, last: bool):
-        """Kernel 11: the last copy of every node that elements share publishes instead of the first (a check: same results).
+        """Kernels 11 and 12: the last copy of every node that elements share publishes instead of the first (a check: same results).
         Refused on any other kernel (cuddh_hip_ddh_plan_set_owner_rule)."""
         N.check_capi(lib.cuddh_ddh_set_owner_rule(self._h, 1 if last else 0), "DDH.set_owner_rule")
 

@@ -7,7 +7,10 @@
 //   --residuals (one more line: GMRES's residual history), --orth mgs|cgs2 (the orthogonalisation of the Arnoldi step, krylov.hpp;
 //   mgs is the default, the reference's; both paths; the summary line names it when it is not mgs), --augment K (LGMRES: the last
 //   K corrections augment every restart cycle, krylov.hpp GmresOptions; 0 <= K < m, 0 is the default; single-process path only;
-//   the summary line names it when it is not 0)
+//   the summary line names it when it is not 0), --block N --kernel K (the DDH constructor's block and kernel: N x N elements
+//   per subdomain, 0 the reference's 16 / n_basis; K as cuddh_hip_ddh_plan_create numbers them, 0 auto; single-process path
+//   only; n_basis 5 needs --block 4 wherever 3 does not divide nx, and then runs kernel 12 where auto or K = 12 picks it; the
+//   summary line names block and kernel when either is given)
 // Writes <out_dir>/xy.0000 and <out_dir>/ddh.0000 (raw fp64, like the reference) and prints one summary line.
 // devices >= 1: the same solve through cuddh::ddh_solve_multi_gpu (multigpu.hpp): subdomains sharded over that many GPUs of
 // this process, RCCL neighbour exchange; devices = 1 with force_rccl = 1 runs the communicator path on a one-GPU box;
@@ -29,8 +32,8 @@ int main(int argc_all, char **argv_all)
     // options out, positional arguments stay
     std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs";
     int coarsen = 0; // 0: not given
-    int augment = 0;
-    bool residuals = false;
+    int augment = 0, block = 0, kernel = 0;
+    bool residuals = false, block_given = false;
     std::vector<char *> args;
     for (int i = 0; i < argc_all; ++i)
     {
@@ -45,6 +48,16 @@ int main(int argc_all, char **argv_all)
             orth_name = argv_all[++i];
         else if (arg == "--augment" && i + 1 < argc_all)
             augment = std::atoi(argv_all[++i]);
+        else if (arg == "--block" && i + 1 < argc_all)
+        {
+            block = std::atoi(argv_all[++i]);
+            block_given = true;
+        }
+        else if (arg == "--kernel" && i + 1 < argc_all)
+        {
+            kernel = std::atoi(argv_all[++i]);
+            block_given = true;
+        }
         else if (arg == "--residuals")
             residuals = true;
         else
@@ -91,6 +104,11 @@ int main(int argc_all, char **argv_all)
         return 2;
     }
     const std::string aug_note = augment == 0 ? "" : " augment=" + std::to_string(augment);
+    if (block < 0 || kernel < 0 || (block_given && devices >= 1))
+    {
+        std::cerr << "ddh_solve: --block and --kernel take non-negative integers on the single-process path" << std::endl;
+        return 2;
+    }
 
     Mesh2D mesh = Mesh2D::uniform_rect(nx, -1.0, 1.0, nx, -1.0, 1.0);
     Basis basis(nb);
@@ -145,9 +163,10 @@ int main(int argc_all, char **argv_all)
     }
 
     const DDHTimeStep ts = time_step == "mesh" ? DDHTimeStep::from_mesh() : DDHTimeStep::from_coefficient();
-    std::unique_ptr<DDH> ddh(integrator == "rk4"   ? new DDH(omega, a.host_read(), fem, nx, nx, 0, 0, ts, DDHIntegrator::rk4_on(coarsen))
-                             : time_step == "mesh" ? new DDH(omega, a.host_read(), fem, nx, nx)
-                                                   : new DDH(omega, a.host_read(), fem, nx, nx, 0, 0, ts));
+    std::unique_ptr<DDH> ddh(integrator == "rk4"   ? new DDH(omega, a.host_read(), fem, nx, nx, kernel, block, ts, DDHIntegrator::rk4_on(coarsen))
+                             : time_step != "mesh" ? new DDH(omega, a.host_read(), fem, nx, nx, kernel, block, ts)
+                             : block_given         ? new DDH(omega, a.host_read(), fem, nx, nx, kernel, block)
+                                                   : new DDH(omega, a.host_read(), fem, nx, nx));
     DDH &F = *ddh;
     const int n_lambda = F.size();
     HostDeviceArray<float> L(n_lambda), Y(n_lambda);
@@ -172,6 +191,7 @@ int main(int argc_all, char **argv_all)
     sync();
     const double t_post = seconds_since(t);
     const double *h_U = U.host_read();
+    const std::string block_note = block_given ? " block=" + std::to_string(block) + " kernel=" + std::to_string(F.internals().kernel_kind()) : "";
 
     if (out_dir != "-")
     {
@@ -185,7 +205,7 @@ int main(int argc_all, char **argv_all)
               << " success=" << out.success << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs
               << " t_gmres=" << t_gmres << " t_postprocess=" << t_post
-              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << std::endl;
+              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << block_note << std::endl;
     if (residuals)
     {
         std::cout << "ddh_solve time_step=" << time_step << " residuals:";

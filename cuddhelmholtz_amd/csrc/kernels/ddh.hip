@@ -12,6 +12,9 @@
 //     DPP quad_perm operands, element-to-element assembly uses DPP row shifts
 //     (xi neighbours) and one ds_bpermute pair (eta neighbours).  No LDS
 //     storage, no barriers, 25,600 time steps per launch;
+//   * `ddh_element_lane5_kernel` (n_basis == 5, 4x4 elements, rectangles) runs four
+//     subdomains per wavefront, lane = element with its 25 nodes in registers:
+//     both contractions in-lane, assembly by DPP row shifts inside a 16-lane row;
 //   * `ddh_block_kernel` (any n_basis <= 10) runs one subdomain per workgroup
 //     with the field staged in LDS, 3 barriers per stiffness sweep.
 //
@@ -20,8 +23,9 @@
 // z = S w)  ->  publish_dof (y and the trace update).  All six wavefront kernels
 // use load_dof.  ddh_wave8_kernel, ddh_mfma_kernel<Real, ..> and
 // ddh_element_lane_kernel (kernel 5's second sweep form: one element per lane,
-// four subdomains per wavefront) and ddh_element_lane8_kernel (kernel 11: the same
-// with one 8x8-element subdomain per wavefront) use wh_march and publish_dof too and are a lane
+// four subdomains per wavefront), ddh_element_lane8_kernel (kernel 11: the same
+// with one 8x8-element subdomain per wavefront) and ddh_element_lane5_kernel
+// (kernel 12: the 4x4 form at n_basis 5, 25 nodes per lane) use wh_march and publish_dof too and are a lane
 // map, a sweep and an owner rule (which of the copies of a shared node
 // publishes); the matrix-core and element-lane kernels take wh_march's LEAN
 // forms, which leave out what their element-interior registers never need.
@@ -39,6 +43,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "element_lane_tables.hpp"
 
 using namespace cuddh_k;
 
@@ -50,7 +55,8 @@ struct cuddh_ddh_plan
                 // 3 + MFMA for the in-lane contractions);  5 / 8 ddh_mfma_kernel<float / double> (dense element matrix on the matrix
                 // cores, uniform geometry);  6 / 7 ddh_wave8_kernel (nb == 8; 7 separable, fp32);  9 ddh_general_wave_kernel
                 // (nb == 4, <= 16 elements, CSR lists);  10 ddh_block_kernel with CSR lists;  11 ddh_element_lane8_kernel (nb == 4,
-                // 8x8 elements, fp32: one element per lane, one subdomain per wavefront)
+                // 8x8 elements, fp32: one element per lane, one subdomain per wavefront);  12 ddh_element_lane5_kernel (nb == 5, 4x4
+                // elements, fp32: one element per lane, four subdomains per wavefront)
     int nodes;  // nb*nb*nel1d*nel1d (general plans: nb*nb*mx_elems)
     int wh_iters = 5; // WaveHoltz iterations per local solve (source/DDH.cpp:136); WH_ITERS_REFERENCE
     const int *gI_override = nullptr; // cuddh_hip_ddh_plan_set_vector_layout: x and y in another numbering than d.gI
@@ -58,8 +64,9 @@ struct cuddh_ddh_plan
     float *Aop = nullptr; // kernel 5: element stiffness matrix as MFMA A operands, [4 k-steps][64 lanes]
     double *Aop64 = nullptr; // kernel 8: the same in fp64, rows in the f64 MFMA's output order (build_dense_element_matrix)
     float *Sep = nullptr; // kernel 7: [Ax | Ay | beta | gamma] of the separable nb = 8 sweep
-    float *Sep4 = nullptr; // kernel 5, element-lane form, and kernel 11: [Bx | By | Dg | W | 1 / W] (build_element_lane_tables); null: does not qualify
-    int last_copy = 0; // kernel 11: the last copy of a shared node publishes, not the first (cuddh_hip_ddh_plan_set_owner_rule)
+    float *Sep4 = nullptr; // kernel 5, element-lane form, and kernel 11: [Bx | By | Dg | W | 1 / W] (build_element_lane_tables); null: does not qualify.
+                           // kernel 12: the same table with 5 in place of 4
+    int last_copy = 0; // kernels 11 and 12: the last copy of a shared node publishes, not the first (cuddh_hip_ddh_plan_set_owner_rule)
     int sweep_form = 0; // kernel 5: 0 auto, 1 matrix form, 2 element-lane form, 3 the same with the other owner rule (cuddh_hip_ddh_plan_set_sweep_form)
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
@@ -1519,6 +1526,43 @@ namespace
                      : "v"(mHi)
                      : "vcc");
     }
+    // The same two for the five values a side of an n_basis-5 element holds (ddh_element_lane5_kernel): the same instructions,
+    // one more of each, so four instructions stand between a sum and the move that reads it.
+    __device__ inline void element_assemble_eta_row5_asm(float (&up)[5], float (&dn)[5])
+    {
+        asm volatile("s_nop 1\n\t"
+                     "v_add_f32_dpp %0, %5, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %1, %6, %1 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %2, %7, %2 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %3, %8, %3 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %4, %9, %4 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %5, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %6, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %7, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %8, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %9, %4 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     : "+v"(up[0]), "+v"(up[1]), "+v"(up[2]), "+v"(up[3]), "+v"(up[4]), "+v"(dn[0]), "+v"(dn[1]), "+v"(dn[2]), "+v"(dn[3]),
+                       "+v"(dn[4]));
+    }
+    __device__ inline void element_assemble_xi_row5_asm(float (&hi)[5], float (&lo)[5], float mHi)
+    {
+        asm volatile("s_mov_b32 vcc_lo, 0x11111111\n\t"
+                     "s_mov_b32 vcc_hi, 0x11111111\n\t"
+                     "v_fmac_f32_dpp %0, %5, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %1, %6, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %2, %7, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %3, %8, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %4, %9, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_cndmask_b32_dpp %5, %0, %5, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %6, %1, %6, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %7, %2, %7, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %8, %3, %8, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %9, %4, %9, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(hi[4]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]),
+                       "+v"(lo[4])
+                     : "v"(mHi)
+                     : "vcc");
+    }
     constexpr unsigned ELEMENT_INTERIOR_REGISTERS = (1u << 5) | (1u << 6) | (1u << 9) | (1u << 10);
 
     // the in-lane part of the element-lane sweep: z' = Dg w + Bx-terms + By-terms of the lane's own element, before assembly
@@ -1959,19 +2003,149 @@ namespace
         }
     }
 
-    // kernels 5, 8 and 11 leave the boundary terms out on the element-interior nodes (register 0): is none of them a trace dof
-    // (sI >= s_fdof) in any subdomain?  True for every plan built from blocks of elements, where trace dofs lie on the
+    // ---------------------------------------------------------------- kernel 12 (NB = 5, 4x4 elements, rectangles): four subdomains per wavefront
+    // ddh_element_lane_kernel's lane map with 25 nodes per lane: lane = element ex + 4 ey, one subdomain per 16-lane DPP row,
+    // four subdomains per wavefront, register n = k + 5 l = node (k, l).  The sweep is the one documented there,
+    //     z'(k,l) = Dg(k,l) w(k,l) + sum_{j != k} Bx(k,j) w(j,l) + sum_{j != l} By(l,j) w(k,j),   z = W z',
+    // 9 in-lane FMAs per node with wave-uniform coefficients (20 + 20 + 25 scalars), W folded into the per-dof constants.
+    // Assembly: the k == 4 column meets the k == 0 column of lane + 1, the l == 4 row the l == 0 row of lane + 4, five values
+    // each, through the row forms above (one copy forms the sum, the other takes it; the shifts never leave the 16-lane row,
+    // so a subdomain's result does not depend on its wave-mates); xi first, eta on the xi-assembled values.  The nine
+    // registers with k, l in {1, 2, 3} are element-interior: wh_march's LEAN rules apply to them.  The time loop is wh_march,
+    // node by node.  A launch whose length is no multiple of 4 recomputes the wavefront's first subdomain in the missing rows
+    // and publishes nothing from them.  The action form is compiled for two wavefronts per SIMD (256 vector registers, no
+    // scratch); the form with x (rhs, postprocess: once per solve) keeps the sources of the nine interior nodes as well and
+    // takes one wavefront per SIMD, a few values in accumulation registers, no scratch either.  The 65 coefficients stay in
+    // scalar registers through the time loop, which issues 736 vector instructions per wavefront-step in the action form
+    // (774 with x), read from the code object; registers and scratch of every instantiation:
+    // profiles/r19/ddh_nb5_registers.txt.
+    constexpr unsigned ELEMENT5_INTERIOR_REGISTERS = (7u << 6) | (7u << 11) | (7u << 16);
+
+    __device__ inline void element_lane5_products(const float (&w)[25], float (&z)[25], const float (&Bx)[25], const float (&By)[25],
+                                                  const float (&Dg)[25])
+    {
+#pragma unroll
+        for (int l = 0; l < 5; ++l)
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+            {
+                float t = Dg[k + 5 * l] * w[k + 5 * l];
+#pragma unroll
+                for (int j = 0; j < 5; ++j)
+                {
+                    if (j != k)
+                        t += Bx[k + 5 * j] * w[j + 5 * l];
+                    if (j != l)
+                        t += By[l + 5 * j] * w[k + 5 * j];
+                }
+                z[k + 5 * l] = t;
+            }
+    }
+
+    template <bool FORCED, bool HOLD, bool LAST_COPY>
+    __global__ void __launch_bounds__(256, FORCED ? 1 : 2) ddh_element_lane5_kernel(DdhArgs<float> A, const float *__restrict__ Sep5, const float *__restrict__ filt,
+                                                                      const float *__restrict__ cs, const float *__restrict__ sn)
+    {
+        const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
+        if (s_first >= A.dom_end)
+            return; // wave-uniform: the kernel has no barriers
+        if constexpr (HOLD)
+            __builtin_amdgcn_s_setprio(3);
+        // where this lane works: subdomain s (valid: and publishes it), its trace dofs, the dofs of its element's nodes
+        auto locate = [&](int tid, bool &valid, int &s, int &fdof, const int *&sI)
+        {
+            const int sub = (tid >> 4) & 3;
+            valid = s_first + sub < A.dom_end;
+            s = domain_at(A, valid ? s_first + sub : s_first);
+            fdof = A.s_fdof[s];
+            sI = A.sI + 400 * (size_t)s + 25 * (tid & 15);
+        };
+        bool valid;
+        int s, fdof;
+        const int *sI;
+        locate(threadIdx.x, valid, s, fdof, sI);
+
+        float invm[25], Hi[25], F[25], Gf[25], u[25], v[25];
+#pragma unroll
+        for (int n = 0; n < 25; ++n)
+        {
+            load_dof(A, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
+            const float W = Sep5[75 + n], rW = Sep5[100 + n];
+            invm[n] *= W;
+            Hi[n] *= rW;
+            F[n] *= rW;
+            Gf[n] *= rW;
+        }
+        float Bx[25], By[25], Dg[25]; // wave-uniform
+#pragma unroll
+        for (int i = 0; i < 25; ++i)
+        {
+            Bx[i] = Sep5[i];      // Bx(k, j) at k + 5 j
+            By[i] = Sep5[25 + i]; // By(l, j) at l + 5 j
+            Dg[i] = Sep5[50 + i]; // Dg(k, l) at k + 5 l
+        }
+        const float mR = (threadIdx.x & 3) < 3 ? 1.0f : 0.0f; // ex < 3: the only mask, for the xi sums
+
+        auto sweep = [&](const float(&w)[25], float(&z)[25])
+        {
+            element_lane5_products(w, z, Bx, By, Dg);
+            // xi neighbours: my k == 4 column meets the k == 0 column of lane + 1 (and vice versa)
+            float hi[5] = {z[4], z[9], z[14], z[19], z[24]}, lo[5] = {z[0], z[5], z[10], z[15], z[20]};
+            element_assemble_xi_row5_asm(hi, lo, mR);
+#pragma unroll
+            for (int l = 0; l < 5; ++l)
+            {
+                z[4 + 5 * l] = hi[l];
+                z[0 + 5 * l] = lo[l];
+            }
+            // eta neighbours, on the xi-assembled values: my l == 4 row meets the l == 0 row of lane + 4
+            float up[5] = {z[20], z[21], z[22], z[23], z[24]}, dn[5] = {z[0], z[1], z[2], z[3], z[4]};
+            element_assemble_eta_row5_asm(up, dn);
+#pragma unroll
+            for (int k = 0; k < 5; ++k)
+            {
+                z[k + 20] = up[k];
+                z[k] = dn[k];
+            }
+        };
+        wh_march<FORCED ? 2 : 1, ELEMENT5_INTERIOR_REGISTERS>(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+
+        // located a second time from a lane index the compiler cannot connect with the first, as in ddh_element_lane_kernel
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        locate(tid, valid, s, fdof, sI);
+        if (!valid)
+            return;
+#pragma unroll
+        for (int n = 0; n < 25; ++n)
+        {
+            // every shared node is held by 2 or 4 (lane, register) pairs with identical values: the copy with
+            // the smallest element-node index writes (with LAST_COPY the one with the largest)
+            const int k = n % 5, l = n / 5;
+            const bool first = !(k == 0 && (tid & 3) > 0) && !(l == 0 && (tid & 12) > 0);
+            const bool last = !(k == 4 && (tid & 3) < 3) && !(l == 4 && (tid & 12) < 12);
+            const bool owner = LAST_COPY ? last : first;
+            if (owner)
+                publish_dof(A, s, sI[n], fdof, u[n], v[n], false);
+        }
+    }
+
+    // kernels 5, 8, 11 and 12 leave the boundary terms out on the element-interior nodes (k, l in 1 .. nb - 2): is none of them a
+    // trace dof (sI >= s_fdof) in any subdomain?  True for every plan built from blocks of elements, where trace dofs lie on the
     // subdomain's boundary; a descriptor from elsewhere is checked, not trusted.
-    // n_elems (16 or 64) elements of 16 nodes per subdomain, `stride` = 16 n_elems entries of sI per subdomain.
-    __global__ void __launch_bounds__(256) ddh_interior_check_kernel(int n_domains, int n_elems, int stride, const int *__restrict__ s_fdof,
+    // n_elems (16 or 64) elements of nb x nb nodes per subdomain, `stride` = nb nb n_elems entries of sI per subdomain.
+    __global__ void __launch_bounds__(256) ddh_interior_check_kernel(int n_domains, int nb, int n_elems, int stride, const int *__restrict__ s_fdof,
                                                                      const int *__restrict__ sI, int *__restrict__ bad)
     {
-        const int s = blockIdx.x, tid = threadIdx.x;
-        if (s >= n_domains || tid >= 4 * n_elems)
+        const int s = blockIdx.x, inner = nb - 2;
+        if (s >= n_domains)
             return;
-        const int node = node_of(tid / n_elems, 0) + 16 * (tid % n_elems);
-        if (sI[node + stride * (size_t)s] < s_fdof[s])
-            atomicExch(bad, 1);
+        for (int t = threadIdx.x; t < inner * inner * n_elems; t += 256)
+        {
+            const int i = t / n_elems, node = (1 + i % inner) + nb * (1 + i / inner) + nb * nb * (t % n_elems);
+            if (sI[node + stride * (size_t)s] < s_fdof[s])
+                atomicExch(bad, 1);
+        }
     }
 
     // is the metric tensor of every element of every subdomain identical to that of (subdomain 0, element 0)?  (compared in the
@@ -2381,7 +2555,7 @@ namespace
             int bad = 1;
             const int e = device_flag_check(&bad, [&](int *flag)
                                             { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(d.n_domains), dim3(256), 0, nullptr, d.n_domains,
-                                                                 16, 256, d.s_fdof, d.sI, flag); });
+                                                                 4, 16, 256, d.s_fdof, d.sI, flag); });
             if (e || bad)
                 return e ? e : -1;
         }
@@ -2447,51 +2621,16 @@ namespace
         return static_cast<int>(e);
     }
 
-    // The separable sweep's factors (kernel 7, NB = 8; kernel 5's element-lane form, NB = 4), in double, from the metric
-    // tensor of element 0, which the caller has found to be that of all elements (check_uniform_geometry): needs it
-    // diagonal (gy == 0) and a product of 1-D factors, gx(k,l) = alpha_k beta_l, gz(k,l) = gamma_k delta_l (rectangles).  Ax = D^T diag(alpha) D, Ay = D^T diag(delta) D.  Returns 0 on success, -1
-    // when the geometry does not qualify, > 0 on a HIP error.
+    // D and the metric tensor of element 0 on the host, for the tables of the separable sweeps (element_lane_tables.hpp: kernel 7,
+    // NB = 8; the element-lane kernels, NB = 4 and 5).  The caller has found element 0's metric to be that of all elements
+    // (check_uniform_geometry).  Returns 0 or a HIP error.
     template <int NB>
-    int separable_factors(const cuddh_ddh_desc &d, double (&Ax)[NB][NB], double (&Ay)[NB][NB], double (&beta)[NB], double (&gamma)[NB])
+    int download_element(const cuddh_ddh_desc &d, float (&hD)[NB * NB], float (&hG)[3 * NB * NB])
     {
-        constexpr int NN = NB * NB;
-        float hD[NN], hG[3 * NN];
         hipError_t e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
         if (e == hipSuccess)
             e = hipMemcpy(hG, d.G, sizeof hG, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return static_cast<int>(e);
-        auto Dm = [&](int a, int b) { return static_cast<double>(hD[a + NB * b]); }; // D(a,b)
-        auto g = [&](int c, int k, int l) { return static_cast<double>(hG[3 * (k + NB * l) + c]); };
-        double scale = 0.0;
-        for (int n = 0; n < NN; ++n)
-            scale = std::max(scale, std::fabs(static_cast<double>(hG[3 * n])) + std::fabs(static_cast<double>(hG[3 * n + 2])));
-        double alpha[NB], delta[NB];
-        for (int i = 0; i < NB; ++i)
-        {
-            alpha[i] = g(0, i, 0);
-            beta[i] = g(0, 0, i) / g(0, 0, 0);
-            gamma[i] = g(2, i, 0) / g(2, 0, 0);
-            delta[i] = g(2, 0, i);
-        }
-        for (int l = 0; l < NB; ++l)
-            for (int k = 0; k < NB; ++k)
-                if (std::fabs(g(1, k, l)) > 1e-6 * scale || std::fabs(g(0, k, l) - alpha[k] * beta[l]) > 1e-6 * scale ||
-                    std::fabs(g(2, k, l) - gamma[k] * delta[l]) > 1e-6 * scale)
-                    return -1;
-        for (int a = 0; a < NB; ++a)
-            for (int b = 0; b < NB; ++b)
-            {
-                double ax = 0.0, ay = 0.0;
-                for (int i = 0; i < NB; ++i)
-                {
-                    ax += Dm(i, a) * alpha[i] * Dm(i, b);
-                    ay += Dm(i, a) * delta[i] * Dm(i, b);
-                }
-                Ax[a][b] = ax;
-                Ay[a][b] = ay;
-            }
-        return 0;
+        return static_cast<int>(e);
     }
 
     template <size_t N>
@@ -2509,7 +2648,10 @@ namespace
         double Ax[8][8], Ay[8][8], beta[8], gamma[8];
         if (const int c = check_uniform_geometry<float>(p->d, 64))
             return c;
-        if (const int c = separable_factors<8>(p->d, Ax, Ay, beta, gamma))
+        float hD[64], hG[192];
+        if (const int c = download_element<8>(p->d, hD, hG))
+            return c;
+        if (const int c = separable_factors<8>(hD, hG, Ax, Ay, beta, gamma))
             return c;
         float hS[144] = {0};
         for (int a = 0; a < 8; ++a)
@@ -2527,45 +2669,20 @@ namespace
         return upload_table(&p->Sep, hS);
     }
 
-    // Tables of kernel 5's element-lane form (ddh_element_lane_kernel), n_basis 4: the same checks as kernel 7's, and that
-    // the node weight W(k,l) = gamma_k beta_l is positive and the same on both sides of every shared edge, W(3,l) = W(0,l)
-    // and W(k,3) = W(k,0) (all elements are identical, so that covers every copy of every shared dof).  The per-dof constants
-    // take the weight of the copy with index 0 in place of 3, so the copies of a dof scale by one and the same float.
-    // Sep4 = [Bx(k,j) at k + 4 j: 16 | By(l,j) at l + 4 j: 16 | Dg(k,l) at k + 4 l: 16 | W: 16 | 1 / W: 16].  Returns 0 on success,
-    // -1 when the geometry does not qualify (p->Sep4 stays null: the plan stays on the matrix form), > 0 on a HIP error.
-    // Called after build_dense_element_matrix has succeeded, which has checked that all elements share one metric.
+    // Tables of the element-lane kernels: kernel 5's element-lane form and kernel 11 (NB = 4), kernel 12 (NB = 5).  The
+    // arithmetic and the checks are host code (element_lane_tables.hpp: separable metric, node weight W positive and the same
+    // on both sides of every shared edge; all elements are identical, so that covers every copy of every shared dof).
+    // Sep4 = [Bx(k,j) at k + NB j | By(l,j) at l + NB j | Dg(k,l) at k + NB l | W | 1 / W], NB^2 floats each.  Returns 0 on success,
+    // -1 when the geometry does not qualify (p->Sep4 stays null: a kernel-5 plan stays on the matrix form), > 0 on a HIP error.
+    // Called after the caller has checked that all elements share one metric.
+    template <int NB>
     int build_element_lane_tables(cuddh_ddh_plan *p)
     {
-        double Ax[4][4], Ay[4][4], beta[4], gamma[4];
-        if (const int c = separable_factors<4>(p->d, Ax, Ay, beta, gamma))
+        float hD[NB * NB], hG[3 * NB * NB], hS[5 * NB * NB];
+        if (const int c = download_element<NB>(p->d, hD, hG))
             return c;
-        double W[4][4], wmax = 0.0;
-        for (int k = 0; k < 4; ++k)
-            for (int l = 0; l < 4; ++l)
-            {
-                W[k][l] = gamma[k] * beta[l];
-                if (!(W[k][l] > 0.0) || !std::isfinite(W[k][l]))
-                    return -1;
-                wmax = std::max(wmax, W[k][l]);
-            }
-        for (int i = 0; i < 4; ++i)
-            if (!(std::fabs(W[3][i] - W[0][i]) <= 1e-6 * wmax) || !(std::fabs(W[i][3] - W[i][0]) <= 1e-6 * wmax))
-                return -1;
-        float hS[80];
-        for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 4; ++b)
-            {
-                const double bx = Ax[a][b] / gamma[a], by = Ay[a][b] / beta[a];
-                hS[a + 4 * b] = static_cast<float>(bx);
-                hS[16 + a + 4 * b] = static_cast<float>(by);
-                hS[32 + a + 4 * b] = static_cast<float>(Ax[a][a] / gamma[a] + Ay[b][b] / beta[b]);
-                const double w = W[a == 3 ? 0 : a][b == 3 ? 0 : b];
-                hS[48 + a + 4 * b] = static_cast<float>(w);
-                hS[64 + a + 4 * b] = static_cast<float>(1.0 / w);
-            }
-        for (int i = 0; i < 80; ++i)
-            if (!std::isfinite(hS[i]))
-                return -1;
+        if (const int c = element_lane_tables<NB>(hD, hG, hS))
+            return c;
         return upload_table(&p->Sep4, hS);
     }
 
@@ -2578,13 +2695,20 @@ namespace
     // so a small launch of a large plan (a few subdomains, the rim launch of a multi-GPU schedule) runs four subdomains per
     // wavefront as well, at a size where this form measured slower on its own.
     constexpr int ELEMENT_LANE_MIN_DOMAINS = 8192;
+    // kernel 12 against kernel 1 under auto (n_basis 5, block 4), the same rule: the smallest measured subdomain count at which
+    // kernel 12 won every round by more than the rounds differ.  One MI355X, ms per action, kernel 1 / kernel 12, three rounds
+    // each (profiles/r19/ddh_nb5_rates.txt): 64 subdomains 8.51 / 8.31 (1.02 x, rounds within 0.7 %), 256 8.58 / 8.28, 1,024
+    // 18.7 / 8.33 (2.2 x), 4,096 66.9 / 8.83 (7.6 x), 16,384 253.4 / 29.3 (8.6 x).  Nothing was measured below 64: there auto
+    // keeps kernel 1.  Up to 4,096 subdomains a launch of kernel 12 is one round of wavefronts and costs what one wavefront
+    // costs.
+    constexpr int ELEMENT_LANE5_MIN_DOMAINS = 64;
 
     // Which kernels have an RK4 form (cuddh_hip_ddh_plan_set_integrator).  Kernels 1, 2, 5 in the matrix form and 8 do.  RK4
     // keeps two registers more per value than RK2 (wh_march); a form of the others is built only where it compiles without
     // scratch and at the occupancy of its RK2 form, and none does ("Runge-Kutta 4", the table from the code
     // objects): kernel 11 and kernel 5's element-lane form, sixteen values per lane, spill 216 to 236 bytes in the form without
     // x, and kernels 3 and 4 go from 86 / 90 to 98 / 99 vector registers, five wavefronts per SIMD to four.  Kernels 6 and 7
-    // have none by decision.  The label-built plans' kernels 9 (wh_march around its LDS assembly, no scratch) and 10 (kernel 1's
+    // have none by decision, and kernel 12 (25 values per lane, one wavefront per SIMD already in RK2) has none either.  The label-built plans' kernels 9 (wh_march around its LDS assembly, no scratch) and 10 (kernel 1's
     // form with the plan's lists) have one.
     constexpr bool has_rk4_form(int kernel) { return kernel == 1 || kernel == 2 || kernel == 5 || kernel == 8 || kernel == 9 || kernel == 10; }
 
@@ -2621,6 +2745,28 @@ namespace
                 hipLaunchKernelGGL((ddh_element_lane_kernel<false, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
             else
                 hipLaunchKernelGGL((ddh_element_lane_kernel<false, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+        }
+    }
+
+    // kernel 12: four subdomains per wavefront, four wavefronts per workgroup
+    template <bool LAST_COPY>
+    void launch_element_lane5(const DdhArgs<float> &A, const float *Sep5, int n_local, hipStream_t st, const float *fl, const float *cs,
+                              const float *sn)
+    {
+        const dim3 grid((n_local + 15) / 16), block(256);
+        if (A.x)
+        {
+            if (A.prio)
+                hipLaunchKernelGGL((ddh_element_lane5_kernel<true, true, LAST_COPY>), grid, block, 0, st, A, Sep5, fl, cs, sn);
+            else
+                hipLaunchKernelGGL((ddh_element_lane5_kernel<true, false, LAST_COPY>), grid, block, 0, st, A, Sep5, fl, cs, sn);
+        }
+        else
+        {
+            if (A.prio)
+                hipLaunchKernelGGL((ddh_element_lane5_kernel<false, true, LAST_COPY>), grid, block, 0, st, A, Sep5, fl, cs, sn);
+            else
+                hipLaunchKernelGGL((ddh_element_lane5_kernel<false, false, LAST_COPY>), grid, block, 0, st, A, Sep5, fl, cs, sn);
         }
     }
 
@@ -2674,7 +2820,7 @@ namespace
     int launch_local_solves(const cuddh_ddh_plan *plan, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl,
                             const Real *cs, const Real *sn, Grids... grids)
     {
-        constexpr bool rk2_one_grid = sizeof...(Grids) == 0; // kernels 6, 7 and the element-lane form of 5 exist in this form alone
+        constexpr bool rk2_one_grid = sizeof...(Grids) == 0; // kernels 6, 7, 12 and the element-lane form of 5 exist in this form alone
         constexpr bool rk4 = scheme_of<Grids...> == 1;
         const cuddh_ddh_desc &d = plan->d;
         const dim3 grid((n_local + 3) / 4), block(256); // the wavefront kernels: four wavefronts per workgroup
@@ -2753,6 +2899,19 @@ namespace
                     launch_element_lane8<true>(A, plan->Sep4, grid, block, st, fl, cs, sn, grids...);
                 else
                     launch_element_lane8<false>(A, plan->Sep4, grid, block, st, fl, cs, sn, grids...);
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
+        case 12:
+            if constexpr (f32 && rk2_one_grid)
+            {
+                if (!plan->Sep4) // plan_create ties kernel 12 to fp32 and its tables
+                    return static_cast<int>(hipErrorInvalidValue);
+                if (plan->last_copy)
+                    launch_element_lane5<true>(A, plan->Sep4, n_local, st, fl, cs, sn);
+                else
+                    launch_element_lane5<false>(A, plan->Sep4, n_local, st, fl, cs, sn);
                 break;
             }
             else
@@ -2885,7 +3044,7 @@ extern "C"
     int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **out, const cuddh_ddh_desc *desc, int is_f64, int kernel)
     {
         *out = nullptr;
-        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || desc->nel1d > 16 || kernel < 0 || (kernel > 8 && kernel != 11))
+        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || desc->nel1d > 16 || kernel < 0 || (kernel > 8 && kernel != 11 && kernel != 12))
             return static_cast<int>(hipErrorInvalidValue);
         const int nodes = desc->nb * desc->nb * desc->nel1d * desc->nel1d;
         if (nodes > 1024) // one thread per element node in kernel 1
@@ -2901,7 +3060,8 @@ extern "C"
         const bool wave_shape = (desc->nb == 4 && desc->nel1d == 4);
         const bool wave8_shape = (desc->nb == 8 && desc->nel1d == 2);
         const bool lane8_shape = (desc->nb == 4 && desc->nel1d == 8);
-        if ((kernel == 11 && (!lane8_shape || is_f64)) || (kernel >= 2 && kernel <= 5 && !wave_shape) || ((kernel == 6 || kernel == 7) && !wave8_shape) || (kernel == 7 && is_f64) ||
+        const bool lane5_shape = (desc->nb == 5 && desc->nel1d == 4);
+        if ((kernel == 11 && (!lane8_shape || is_f64)) || (kernel == 12 && (!lane5_shape || is_f64)) || (kernel >= 2 && kernel <= 5 && !wave_shape) || ((kernel == 6 || kernel == 7) && !wave8_shape) || (kernel == 7 && is_f64) ||
             (kernel == 8 && (!wave_shape || !is_f64)))
         {
             delete p;
@@ -2945,12 +3105,12 @@ extern "C"
             if (!e && !bad)
                 e = device_flag_check(&bad, [&](int *flag)
                                       { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(desc->n_domains), dim3(256), 0, nullptr,
-                                                           desc->n_domains, 64, 1024, desc->s_fdof, desc->sI, flag); });
+                                                           desc->n_domains, 4, 64, 1024, desc->s_fdof, desc->sI, flag); });
             int qualifies = -1; // 0 yes, -1 no, > 0 a HIP error
             if (!e && !bad)
                 qualifies = check_uniform_geometry<float>(*desc, 16, 1024);
             if (!e && qualifies == 0)
-                qualifies = build_element_lane_tables(p);
+                qualifies = build_element_lane_tables<4>(p);
             if (e || qualifies > 0)
             {
                 cuddh_hip_ddh_plan_destroy(p);
@@ -2959,6 +3119,35 @@ extern "C"
             if (qualifies == 0)
                 p->kernel = 11;
             else if (kernel == 11)
+            {
+                cuddh_hip_ddh_plan_destroy(p);
+                return static_cast<int>(hipErrorInvalidValue);
+            }
+        }
+        // kernel 12 (n_basis 5, 4x4 elements, one per lane) needs fp32, the element order ex + 4 ey, no trace dof on an
+        // element-interior node and the rectangles of the element-lane form.  On request a plan that fails one of these is
+        // refused; auto takes it from ELEMENT_LANE5_MIN_DOMAINS subdomains on when all hold, and kernel 1 otherwise
+        if (lane5_shape && !is_f64 && (kernel == 12 || (kernel == 0 && desc->n_domains >= ELEMENT_LANE5_MIN_DOMAINS)))
+        {
+            int bad = 1;
+            int e = run_structure_check<5, 4>(desc, &bad);
+            if (!e && !bad)
+                e = device_flag_check(&bad, [&](int *flag)
+                                      { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(desc->n_domains), dim3(256), 0, nullptr,
+                                                           desc->n_domains, 5, 16, 400, desc->s_fdof, desc->sI, flag); });
+            int qualifies = -1; // 0 yes, -1 no, > 0 a HIP error
+            if (!e && !bad)
+                qualifies = check_uniform_geometry<float>(*desc, 25, 400);
+            if (!e && qualifies == 0)
+                qualifies = build_element_lane_tables<5>(p);
+            if (e || qualifies > 0)
+            {
+                cuddh_hip_ddh_plan_destroy(p);
+                return e ? e : qualifies;
+            }
+            if (qualifies == 0)
+                p->kernel = 12;
+            else if (kernel == 12)
             {
                 cuddh_hip_ddh_plan_destroy(p);
                 return static_cast<int>(hipErrorInvalidValue);
@@ -2987,7 +3176,7 @@ extern "C"
                 if (err5 == 0)
                 {
                     p->kernel = 5;
-                    const int err_el = build_element_lane_tables(p); // -1: the plan stays on the matrix form
+                    const int err_el = build_element_lane_tables<4>(p); // -1: the plan stays on the matrix form
                     if (err_el > 0)
                     {
                         cuddh_hip_ddh_plan_destroy(p);
@@ -3162,12 +3351,12 @@ extern "C"
     {
         if (!plan || n_grids < 1 || !h_nt || !h_dt || !filter || !cs || !sn || !d_grid_of)
             return static_cast<int>(hipErrorInvalidValue);
-        // the element-lane forms on request have one grid; so have kernels 6 and 7, which hold two subdomains per wavefront:
-        // chosen by auto they give way to kernel 1, requested they are refused.  The label-built plans' kernels 9 and 10 hold
+        // the element-lane forms on request have one grid; so have kernels 6 and 7, which hold two subdomains per wavefront,
+        // and kernel 12, which holds four: chosen by auto they give way to kernel 1, requested they are refused.  The label-built plans' kernels 9 and 10 hold
         // one subdomain per wavefront / workgroup and take the grids as they are.
         if (plan->sweep_form >= 2)
             return static_cast<int>(hipErrorInvalidValue);
-        if ((plan->kernel == 6 || plan->kernel == 7) && plan->requested != 0)
+        if ((plan->kernel == 6 || plan->kernel == 7 || plan->kernel == 12) && plan->requested != 0)
             return static_cast<int>(hipErrorInvalidValue);
         const int nd = plan->d.n_domains;
         // every offset a kernel adds to a table base is formed and checked here
@@ -3245,7 +3434,7 @@ extern "C"
         plan->grid_filter = filter;
         plan->grid_cs = cs;
         plan->grid_sn = sn;
-        if (plan->kernel == 6 || plan->kernel == 7)
+        if (plan->kernel == 6 || plan->kernel == 7 || plan->kernel == 12)
             plan->kernel = 1;
         return 0;
     }
@@ -3262,7 +3451,7 @@ extern "C"
             return 0;
         }
         // No RK4 form (has_rk4_form): a request is refused; an auto choice moves to the kernel of
-        // its block size that has one: 3 to 2 (the same lane map without the folded DPP reads), 6, 7 and 11 to 1, and a
+        // its block size that has one: 3 to 2 (the same lane map without the folded DPP reads), 6, 7, 11 and 12 to 1, and a
         // kernel-5 plan takes the matrix form whatever its size (effective_sweep_form).  A label-built plan keeps its kernel:
         // 9 and 10 both have the form.
         if (plan->kernel == 5 && plan->sweep_form >= 2)
@@ -3281,7 +3470,7 @@ extern "C"
 
     int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last)
     {
-        if (!plan || plan->kernel != 11)
+        if (!plan || (plan->kernel != 11 && plan->kernel != 12))
             return static_cast<int>(hipErrorInvalidValue);
         plan->last_copy = last ? 1 : 0;
         return 0;

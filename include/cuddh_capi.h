@@ -206,8 +206,8 @@ int cuddh_ddh_set_wave_priority(void *ddh, int high);
  * the getter returns the form in effect (1, 2 or 3; 0 for a plan that is not kernel 5; -1 on error) */
 int cuddh_ddh_set_sweep_form(void *ddh, int form);
 int cuddh_ddh_sweep_form(void *ddh);
-/* kernel 11's owner rule: last != 0 lets the last copy of every shared node publish instead of the first; same results, a
- * check (cuddh_hip_ddh_plan_set_owner_rule; an error on a plan that is not kernel 11) */
+/* the owner rule of kernels 11 and 12: last != 0 lets the last copy of every shared node publish instead of the first; same
+ * results, a check (cuddh_hip_ddh_plan_set_owner_rule; an error on a plan that is neither kernel 11 nor kernel 12) */
 int cuddh_ddh_set_owner_rule(void *ddh, int last);
 /* traces are float for f64 == 0 and double otherwise */
 int cuddh_ddh_rhs(void *ddh, const double *f, void *b);

@@ -345,8 +345,14 @@ typedef struct cuddh_ddh_plan cuddh_ddh_plan;
  *             Needs rectangles like the element-lane form, the element order ex + 8 ey inside every subdomain and no trace
  *             dof on an element-interior node, which plan_create verifies on the device; what auto picks for that shape
  *             when it applies, otherwise 1.
+ *         12 = four 4x4-element subdomains per wavefront at nb == 5 (nel1d == 4, fp32): the element-lane form with the 25
+ *             nodes of an element in one lane's registers, lane = ex + 4 ey, one subdomain per 16-lane DPP row; both
+ *             contractions in-lane with scalar coefficients, xi and eta neighbours through DPP row shifts that stay in the
+ *             row.  Needs what 11 needs (rectangles, the element order ex + 4 ey, no trace dof on an element-interior node;
+ *             verified here).  One time grid and RK2 only.  Under auto a qualifying plan takes it from the subdomain count
+ *             at which it measured faster than kernel 1 (ELEMENT_LANE5_MIN_DOMAINS in kernels/ddh.hip), kernel 1 below.
  * Subdomains hold nb^2 nel1d^2 <= 1024 element nodes.  Kernel 1 runs every such shape (one thread per element node);
- * kernels 2-8 and 11 are refused with hipErrorInvalidValue on any shape but their own. */
+ * kernels 2-8, 11 and 12 are refused with hipErrorInvalidValue on any shape but their own. */
 int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int is_f64, int kernel);
 /* Plan for subdomains of ANY element connectivity (subdomains given by element labels; desc->nel1d is ignored and
  * should be 0).  mx_elems: elements per subdomain at most, the third extent of desc->sI and the stride of desc->G;
@@ -363,7 +369,7 @@ int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc,
  * plans unchanged. */
 int cuddh_hip_ddh_plan_create_general(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int mx_elems, int is_f64, int kernel);
 int cuddh_hip_ddh_plan_destroy(cuddh_ddh_plan *plan);
-/* which kernel the plan resolved to (1..11) */
+/* which kernel the plan resolved to (1..12) */
 int cuddh_hip_ddh_plan_kernel(const cuddh_ddh_plan *plan);
 /* Numbering of the forcing x and the solution y of the NEXT apply calls: d_gI (mx_dof, n_domains) DEVICE replaces desc.gI and
  * g_ndof replaces desc.g_ndof for x and y (NULL restores the descriptor's).  With the identity numbering
@@ -394,11 +400,20 @@ int cuddh_hip_ddh_plan_set_wh_iters(cuddh_ddh_plan *plan, int wh_iters);
  * every plan.  cuddh_hip_ddh_plan_sweep_form returns the form in effect (1, 2 or 3), 0 for a plan that is not kernel 5. */
 int cuddh_hip_ddh_plan_set_sweep_form(cuddh_ddh_plan *plan, int form);
 int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan);
-/* Kernel 11's owner rule, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
+/* The owner rule of kernels 11 and 12, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
  * smallest element-node index publishes (last == 0, the default) or the one with the largest (last != 0).  The copies are
  * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with
- * hipErrorInvalidValue on a plan that is not kernel 11. */
+ * hipErrorInvalidValue on a plan that is neither kernel 11 nor kernel 12. */
 int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last);
+/* The table of the element-lane kernels (5 in the element-lane form, 11 and 12) alone, computed on the host in double from HOST
+ * arrays (no device is touched): h_D (nb, nb) the differentiation matrix, h_G (3, nb, nb) the metric tensor (gx, gy, gz) of one
+ * element, nb 4 or 5.  h_out receives 5 nb^2 floats [Bx(k,j) at k + nb j | By(l,j) at l + nb j | Dg(k,l) at k + nb l | W | 1 / W]
+ * with  S w = W (Dg w + sum_{j != k} Bx(k,j) w(j,l) + sum_{j != l} By(l,j) w(k,j))  for the element's stiffness matrix S, and
+ * W on the last node of either direction replaced by that of node 0, the copy it is assembled with.  Returns 0, -1 when the
+ * element does not qualify (a metric that is not diagonal or no product of 1-D factors, a weight W that is not positive or
+ * differs between the two sides of a shared edge; h_out is not written), 1 (hipErrorInvalidValue) for another nb or a null
+ * pointer.  Plan creation calls the same code on the descriptor's D and G. */
+int cuddh_element_lane_tables(int nb, const float *h_D, const float *h_G, float *h_out);
 /* Per-subdomain time grids.  The descriptor holds ONE grid (nt, dt, wh_filter, cs, sn), taken from the mesh alone; the wave
  * speed 1 / a never enters it, and where a < 1 the explicit time stepping runs past its usable range.  Local
  * solves couple through the traces only, so every subdomain may march its WaveHoltz period on a grid of its own: after this
@@ -413,8 +428,8 @@ int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last);
  * One subdomain per wavefront or workgroup is what makes the grid uniform where the time loop reads it, so kernels 1, 2, 3,
  * 4, 5 in the matrix form, 8, 11 and a general plan's 9 and 10 run such a plan (instantiations of their own; a plan without
  * grids launches the code it did before).  The kernels that hold several subdomains per wavefront do not: a kernel-5 plan takes the matrix form whatever
- * its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan that auto resolved to kernel 6 or 7 becomes kernel 1;
- * a plan created with kernel 6 or 7 on request and one with sweep form 2 or 3 set are
+ * its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan that auto resolved to kernel 6, 7 or 12 becomes kernel 1;
+ * a plan created with kernel 6, 7 or 12 on request and one with sweep form 2 or 3 set are
  * refused with hipErrorInvalidValue, as are a grid with nt < 1 or dt <= 0 and an entry of d_grid_of out of range.
  * An apply over the whole range [0, n_domains) of such a plan runs the subdomains in the order of their step counts,
  * longest first and by index among equals (a list the plan owns), so that the short solves fill the device behind the
@@ -434,8 +449,8 @@ int cuddh_hip_ddh_plan_time_grids(const cuddh_ddh_plan *plan);
  * RK4 is meant for a grid 2 to 16 times coarser than the mesh grid RK2 needs; the caller builds that grid.
  * RK4 forms exist of kernels 1, 2, 5 (matrix form), 8, 9 and 10 (instantiations of their own; an RK2 plan launches the code it did
  * before).  Like cuddh_hip_ddh_plan_set_time_grids this moves an auto choice and never a request: a plan that auto resolved
- * to kernel 3 becomes kernel 2, one that resolved to 6, 7 or 11 becomes kernel 1, a kernel-5 plan takes the matrix form
- * whatever its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan created with kernel 3, 4, 6, 7 or 11 on
+ * to kernel 3 becomes kernel 2, one that resolved to 6, 7, 11 or 12 becomes kernel 1, a kernel-5 plan takes the matrix form
+ * whatever its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan created with kernel 3, 4, 6, 7, 11 or 12 on
  * request and one with sweep form 2 or 3 set are refused with hipErrorInvalidValue and stay
  * RK2 plans; a general plan keeps its kernel, 9 or 10.  No launch of an RK4 plan ever runs RK2 code: a kernel without an RK4 form returns hipErrorInvalidValue.
  * cuddh_hip_ddh_plan_integrator returns the scheme in effect. */
