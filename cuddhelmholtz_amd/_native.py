@@ -122,6 +122,11 @@ _sig("cuddh_hip_cgs_reduce_f32", ci, ci, ci, vp, vp, vp)
 _krylov_update = (ci, ci, vp, vp, vp, C.c_longlong, ci, vp, C.c_longlong, ci, vp, vp, vp)
 _sig("cuddh_hip_krylov_update_f64", *_krylov_update)
 _sig("cuddh_hip_krylov_update_f32", *_krylov_update)
+_sig("cuddh_hip_cmgs_ws_bytes", cs)
+_sig("cuddh_hip_cmgs_stage_f64", ci, ci, vp, vp, vp, vp, vp, vp, vp)
+_sig("cuddh_hip_cmgs_stage_f32", ci, ci, vp, vp, vp, vp, vp, vp, vp)
+_sig("cuddh_hip_ckrylov_update_f64", ci, ci, vp, vp, C.c_longlong, ci, vp, vp)
+_sig("cuddh_hip_ckrylov_update_f32", ci, ci, vp, vp, C.c_longlong, ci, vp, vp)
 _sig("cuddh_hip_nrm2_f64", ci, ci, vp, vp, vp, vp)
 _sig("cuddh_hip_nrm2_f32", ci, ci, vp, vp, vp, vp)
 for _t in ("f64", "f32", "i32"):
@@ -311,6 +316,9 @@ _sig("cuddh_gmres_helmholtz_aug", ci, vp, vp, vp, ci, ci, cd, ci, cd, ci, ci, C.
 _sig("cuddh_gmres_ddh_aug", ci, ci, vp, vp, vp, ci, ci, cd, ci, cd, ci, ci, C.POINTER(SolverResult), vp, vp)
 _sig("cuddh_gmres_callback_aug", ci, ci, vp, ACTION_CB, vp, vp, ci, ci, ci, cd, ci, cd, ci, ci, C.POINTER(SolverResult), vp, vp)
 _sig("cuddh_gmres_callback_sharded_aug", ci, ci, vp, ACTION_CB, vp, REDUCE_CB, vp, vp, ci, ci, ci, cd, ci, cd, ci, ci, C.POINTER(SolverResult), vp, vp)
+
+_sig("cuddh_gmres_ddh_cplx", ci, ci, vp, vp, vp, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_gmres_callback_cplx", ci, ci, vp, ACTION_CB, vp, vp, ci, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
 
 
 def last_error() -> str:

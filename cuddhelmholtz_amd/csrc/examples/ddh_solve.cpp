@@ -10,7 +10,9 @@
 //   the summary line names it when it is not 0), --block N --kernel K (the DDH constructor's block and kernel: N x N elements
 //   per subdomain, 0 the reference's 16 / n_basis; K as cuddh_hip_ddh_plan_create numbers them, 0 auto; single-process path
 //   only; n_basis 5 needs --block 4 wherever 3 does not divide nx, and then runs kernel 12 where auto or K = 12 picks it; the
-//   summary line names block and kernel when either is given)
+//   summary line names block and kernel when either is given), --arithmetic real|complex (krylov.hpp Arithmetic: complex runs
+//   GMRES over the complex numbers on the trace vectors [lambda; mu]; real is the default; needs --orth mgs and --augment 0;
+//   single-process path only; the summary line names it when it is complex)
 // Writes <out_dir>/xy.0000 and <out_dir>/ddh.0000 (raw fp64, like the reference) and prints one summary line.
 // devices >= 1: the same solve through cuddh::ddh_solve_multi_gpu (multigpu.hpp): subdomains sharded over that many GPUs of
 // this process, RCCL neighbour exchange; devices = 1 with force_rccl = 1 runs the communicator path on a one-GPU box;
@@ -30,7 +32,7 @@ using namespace cuddh;
 int main(int argc_all, char **argv_all)
 {
     // options out, positional arguments stay
-    std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs";
+    std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs", arithmetic = "real";
     int coarsen = 0; // 0: not given
     int augment = 0, block = 0, kernel = 0;
     bool residuals = false, block_given = false;
@@ -48,6 +50,8 @@ int main(int argc_all, char **argv_all)
             orth_name = argv_all[++i];
         else if (arg == "--augment" && i + 1 < argc_all)
             augment = std::atoi(argv_all[++i]);
+        else if (arg == "--arithmetic" && i + 1 < argc_all)
+            arithmetic = argv_all[++i];
         else if (arg == "--block" && i + 1 < argc_all)
         {
             block = std::atoi(argv_all[++i]);
@@ -104,6 +108,17 @@ int main(int argc_all, char **argv_all)
         return 2;
     }
     const std::string aug_note = augment == 0 ? "" : " augment=" + std::to_string(augment);
+    if (arithmetic != "real" && arithmetic != "complex")
+    {
+        std::cerr << "ddh_solve: --arithmetic takes real or complex, not " << arithmetic << std::endl;
+        return 2;
+    }
+    if (arithmetic == "complex" && (orth_name != "mgs" || augment != 0 || devices >= 1))
+    {
+        std::cerr << "ddh_solve: --arithmetic complex needs --orth mgs and --augment 0 on the single-process path" << std::endl;
+        return 2;
+    }
+    const std::string arith_note = arithmetic == "real" ? "" : " arithmetic=" + arithmetic;
     if (block < 0 || kernel < 0 || (block_given && devices >= 1))
     {
         std::cerr << "ddh_solve: --block and --kernel take non-negative integers on the single-process path" << std::endl;
@@ -183,7 +198,7 @@ int main(int argc_all, char **argv_all)
     sync();
     const double t_rhs = seconds_since(t);
     t = clk::now();
-    solver_out out = gmres(n_lambda, d_L, &F, d_Y, m, maxit, tol, 0, 6 * 60 * 60, GmresOptions{orth, augment});
+    solver_out out = gmres(n_lambda, d_L, &F, d_Y, m, maxit, tol, 0, 6 * 60 * 60, GmresOptions{orth, augment, arithmetic == "complex" ? Arithmetic::complex : Arithmetic::real});
     sync();
     const double t_gmres = seconds_since(t);
     t = clk::now();
@@ -205,7 +220,7 @@ int main(int argc_all, char **argv_all)
               << " success=" << out.success << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs
               << " t_gmres=" << t_gmres << " t_postprocess=" << t_post
-              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << block_note << std::endl;
+              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << arith_note << block_note << std::endl;
     if (residuals)
     {
         std::cout << "ddh_solve time_step=" << time_step << " residuals:";

@@ -83,10 +83,31 @@ namespace cuddh
     /// a cycle dx = sum_j y_j u_j and x <- x + dx in one launch (cuddh_hip_krylov_update_*), and the new pair is dx / |dx| and
     /// (r_old - r_new) / |dx| from the two true residuals the iteration has anyway (none when |dx| = 0).  m <= 512.  Operators that
     /// only queue device work stay driven one step ahead: an augmentation column is a device copy.
+    ///
+    /// arithmetic = complex (real, the default, is the iteration above bit for bit): the vectors are read as n / 2 complex numbers,
+    /// real parts in the first half and imaginary parts in the second (the layout of a DDH trace vector [lambda; mu]), and the
+    /// iteration is GMRES(m) over the complex numbers: complex inner products <v, w> = sum conj(v) w, a complex Hessenberg matrix,
+    /// complex Givens rotations and coefficients (std::complex<double> on the host whatever the vectors' type).  After j operator
+    /// applications the residual is minimised over the COMPLEX combinations of r, A r, .., A^(j-1) r -- twice the real dimensions of the
+    /// real iteration -- with the same m + 1 vectors, the same bytes moved and the same launches per Arnoldi step
+    /// (cuddh_hip_cmgs_stage_*, cuddh_hip_ckrylov_update_*).  Inner exit, breakdown rule and end of cycle are the real iteration's:
+    /// x is updated, the true residual b - A x is formed with the operator and decides.  This assumes that A is complex-linear,
+    /// A(i x) = i A(x) with i [a; b] = [-b; a]; where it is so only approximately (DDH with time-stepped local solves: to 4e-3 -- 6e-3
+    /// at five WaveHoltz iterations) the estimate inside a cycle is approximate and the true residual still decides.  An operator
+    /// that anticommutes with i (HelmholtzOperator: its second row is negated) must stay on real arithmetic.  Where a cycle gains
+    /// less than the operator's defect (a stalled GMRES(m)) the true residual may rise from cycle to cycle: res_norm shows it.
+    /// Needs an even n, m <= 512, orth = mgs and augment = 0; cgs2, augment > 0, a ScalarReduce or a preconditioner combined with
+    /// complex arithmetic is an error.  Operators that only queue device work stay driven one step ahead.
+    enum class Arithmetic
+    {
+        real,
+        complex
+    };
     struct GmresOptions
     {
         Orthogonalization orth = Orthogonalization::mgs;
         int augment = 0;
+        Arithmetic arithmetic = Arithmetic::real;
     };
     solver_out gmres(int n, double *x, const Operator *A, const double *b, const Operator *Precond, int m, int maxit, double tol, int verbose,
                      double max_seconds, const GmresOptions &opt);

@@ -931,6 +931,298 @@ namespace
         return launch_status();
     }
 
+    // ---------------- complex arithmetic on split vectors (krylov.cpp, GmresOptions::arithmetic = complex)
+    // A vector of n = 2 h scalars stands for h complex numbers, real parts at [0, h), imaginary parts at [h, 2 h).  The fused
+    // Gram-Schmidt stage and the cycle update below are mgs_stage_kernel and krylov_update_kernel with a complex coefficient:
+    //   stage:   c = (sum of row 0 of pin) + i (sum of row 1)     (rows CPLX_ROW apart; <v_prev, w> left behind by the previous stage)
+    //            w <- w - c v_prev:   w_r -= c_r v_r - c_i v_i,   w_i -= c_r v_i + c_i v_r       (skipped when v_prev == nullptr)
+    //            pout row 0 / row 1 [block] = partial sums of Re / Im <v_next, w> = (v_r w_r + v_i w_i) + i (v_r w_i - v_i w_r)
+    //            (v_next == nullptr: row 0 = those of |w|^2 -- what mgs_finish_kernel on the 2 h scalars reads -- and row 1 = 0)
+    //   update:  x <- x + sum_j y_j v_j, y_j = coef[2 j] + i coef[2 j + 1], per element in ascending j
+    // A tile is CUNROLL x 256 sixteen-byte vectors of EACH half: the bytes of a tile, the requests in flight per thread and the
+    // grid are those of the real kernels on the same 2 h scalars, and so is the number of launches per Arnoldi step.  The
+    // imaginary half starts h scalars behind the real one: 16-byte accesses need h to be a multiple of the vector width (and
+    // aligned operands); anything else takes the element-wise path for the whole vector, chosen on the host.
+    constexpr int CUNROLL = UNROLL / 2;
+    constexpr int CTILE = CUNROLL * BLOCK; // 16-byte vectors of one half per tile
+    constexpr int CPLX_ROW = MAX_PARTIALS;
+
+    // sums of the two rows of partials, in mgs_stage_kernel's order; valid in thread 0
+    template <typename T>
+    __device__ inline void cplx_sum_partials(const T *__restrict__ pin, int npin, T &sr, T &si)
+    {
+        static_assert(MAX_PARTIALS <= 4 * BLOCK, "four partial sums per thread");
+        T q[2][4];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                q[c][k] = pin[c * CPLX_ROW + min((int)threadIdx.x + k * BLOCK, npin - 1)];
+        T a[2] = {T(0), T(0)};
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                a[c] = (int)threadIdx.x + k * BLOCK < npin ? a[c] + q[c][k] : a[c];
+        sr = block_sum(a[0]);
+        __syncthreads(); // block_sum reuses its LDS scratch
+        si = block_sum(a[1]);
+    }
+
+    template <typename T, bool PREV, bool NEXT>
+    __global__ void __launch_bounds__(BLOCK) cmgs_stage_kernel(int h, T *__restrict__ w, const T *__restrict__ vprev, const T *__restrict__ vnext,
+                                                               const T *__restrict__ pin, int npin, T *__restrict__ pout, T *__restrict__ hout,
+                                                               int vectorised)
+    {
+        __shared__ T c_sh[2];
+        using VE = T __attribute__((ext_vector_type(Pack<T>::N)));
+        constexpr int N = Pack<T>::N;
+        const int nv = vectorised ? h / N : 0; // vectors of one half
+        const int n_tiles = (nv + CTILE - 1) / CTILE;
+        VE *wv[2] = {reinterpret_cast<VE *>(w), reinterpret_cast<VE *>(w + h)};
+        const VE *pv[2] = {reinterpret_cast<const VE *>(vprev), reinterpret_cast<const VE *>(vprev + h)};
+        const VE *nx[2] = {reinterpret_cast<const VE *>(vnext), reinterpret_cast<const VE *>(vnext + h)};
+
+        // requests of a tile: both halves of w, v_prev and v_next; clamped addresses, no branches (see mgs_stage_kernel)
+        auto request = [&](int tile, VE(&a)[2][CUNROLL], VE(&b)[2][CUNROLL], VE(&c)[2][CUNROLL])
+        {
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int u = 0; u < CUNROLL; ++u)
+                {
+                    const int i = min(tile * CTILE + (int)threadIdx.x + u * BLOCK, nv - 1);
+                    a[p][u] = wv[p][i];
+                    if constexpr (PREV)
+                        b[p][u] = pv[p][i];
+                    if constexpr (NEXT)
+                        c[p][u] = nx[p][i];
+                }
+        };
+        T cr = T(0), ci = T(0), accr = T(0), acci = T(0);
+        // one complex element: the projection, then its terms of the next inner product
+        auto element = [&](T &wr, T &wi, T pr, T pi, T nr, T ni)
+        {
+            if constexpr (PREV)
+            {
+                wr = fmadd(ci, pi, fmadd(-cr, pr, wr));
+                wi = fmadd(-ci, pr, fmadd(-cr, pi, wi));
+            }
+            if constexpr (NEXT)
+            {
+                accr = fmadd(ni, wi, fmadd(nr, wr, accr));
+                acci = fmadd(-ni, wr, fmadd(nr, wi, acci));
+            }
+            else
+                accr = fmadd(wi, wi, fmadd(wr, wr, accr));
+        };
+        auto use = [&](int tile, VE(&a)[2][CUNROLL], VE(&b)[2][CUNROLL], VE(&c)[2][CUNROLL])
+        {
+#pragma unroll
+            for (int u = 0; u < CUNROLL; ++u)
+            {
+                const int i = tile * CTILE + (int)threadIdx.x + u * BLOCK;
+                if (i < nv)
+                {
+#pragma unroll
+                    for (int e = 0; e < N; ++e)
+                    {
+                        T wr = a[0][u][e], wi = a[1][u][e]; // (a vector's element does not bind to a reference)
+                        element(wr, wi, PREV ? b[0][u][e] : T(0), PREV ? b[1][u][e] : T(0), NEXT ? c[0][u][e] : T(0), NEXT ? c[1][u][e] : T(0));
+                        a[0][u][e] = wr;
+                        a[1][u][e] = wi;
+                    }
+                    if constexpr (PREV)
+                    {
+                        wv[0][i] = a[0][u];
+                        wv[1][i] = a[1][u];
+                    }
+                }
+            }
+        };
+
+        int tile = blockIdx.x;
+        const bool first = tile < n_tiles; // (workgroup-uniform)
+        VE a0[2][CUNROLL], b0[2][CUNROLL], c0[2][CUNROLL];
+        if (first) // a workgroup's FIRST tile is requested before the coefficient is summed (see mgs_stage_kernel)
+            request(tile, a0, b0, c0);
+        if constexpr (PREV)
+        {
+            T sr, si;
+            cplx_sum_partials(pin, npin, sr, si);
+            if (threadIdx.x == 0)
+            {
+                c_sh[0] = sr;
+                c_sh[1] = si;
+                if (blockIdx.x == 0)
+                {
+                    hout[0] = sr;
+                    hout[1] = si;
+                }
+            }
+            __syncthreads();
+            cr = c_sh[0];
+            ci = c_sh[1];
+        }
+        if (first)
+        {
+            use(tile, a0, b0, c0);
+            tile += gridDim.x;
+        }
+        for (; tile < n_tiles; tile += gridDim.x)
+        {
+            VE a[2][CUNROLL], b[2][CUNROLL], c[2][CUNROLL];
+            request(tile, a, b, c);
+            use(tile, a, b, c);
+        }
+        const int tid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
+        for (int i = nv * N + tid; i < h; i += stride)
+        {
+            T wr = w[i], wi = w[h + i];
+            element(wr, wi, PREV ? vprev[i] : T(0), PREV ? vprev[h + i] : T(0), NEXT ? vnext[i] : T(0), NEXT ? vnext[h + i] : T(0));
+            if constexpr (PREV)
+            {
+                w[i] = wr;
+                w[h + i] = wi;
+            }
+        }
+        __syncthreads(); // block_sum reuses its LDS scratch
+        const T sr = block_sum(accr);
+        __syncthreads();
+        const T si = block_sum(acci);
+        if (threadIdx.x == 0)
+        {
+            pout[blockIdx.x] = sr;
+            pout[CPLX_ROW + blockIdx.x] = si;
+        }
+    }
+
+    inline int cplx_grid(int h) { return mgs_grid(2 * h); } // (the real chain's grid on the same scalars: mgs_finish_kernel reads row 0)
+
+    template <typename T>
+    int launch_cmgs_stage(int h, T *w, const T *vprev, const T *vnext, const T *pin, T *pout, T *hout, void *stream)
+    {
+        if (h < 0 || h > (1 << 30) - 1)
+            return static_cast<int>(hipErrorInvalidValue);
+        if (h == 0)
+            return 0;
+        const int g = cplx_grid(h);
+        const int vec = h % Pack<T>::N == 0 && aligned16(w) && (!vprev || aligned16(vprev)) && (!vnext || aligned16(vnext));
+        const dim3 grid(g), block(BLOCK);
+        hipStream_t st = as_stream(stream);
+        if (vprev && vnext)
+            hipLaunchKernelGGL((cmgs_stage_kernel<T, true, true>), grid, block, 0, st, h, w, vprev, vnext, pin, g, pout, hout, vec);
+        else if (vprev)
+            hipLaunchKernelGGL((cmgs_stage_kernel<T, true, false>), grid, block, 0, st, h, w, vprev, vnext, pin, g, pout, hout, vec);
+        else if (vnext)
+            hipLaunchKernelGGL((cmgs_stage_kernel<T, false, true>), grid, block, 0, st, h, w, vprev, vnext, pin, g, pout, hout, vec);
+        else
+            hipLaunchKernelGGL((cmgs_stage_kernel<T, false, false>), grid, block, 0, st, h, w, vprev, vnext, pin, g, pout, hout, vec);
+        return launch_status();
+    }
+
+    // x <- x + sum_j (coef[2 j] + i coef[2 j + 1]) v_j, v_j = V + j ldv (its halves h apart), j < k1 <= CGS_KMAX: one launch, x read
+    // and written once, the columns in chunks of CGS_KC past a tile of x in registers (krylov_update_kernel)
+    template <typename T, bool NT>
+    __global__ void __launch_bounds__(BLOCK) ckrylov_update_kernel(int h, T *__restrict__ x, const T *__restrict__ V, size_t ldv, int k1,
+                                                                   const T *__restrict__ coef, int vectorised)
+    {
+        __shared__ T c_sh[2 * CGS_KMAX];
+        using VE = T __attribute__((ext_vector_type(Pack<T>::N)));
+        constexpr int N = Pack<T>::N;
+        const int nv = vectorised ? h / N : 0;
+        const int n_tiles = (nv + CTILE - 1) / CTILE;
+        VE *xv[2] = {reinterpret_cast<VE *>(x), reinterpret_cast<VE *>(x + h)};
+        auto request_chunk = [&](int tile, int j0, VE(&b)[CGS_KC][2][CUNROLL])
+        {
+#pragma unroll
+            for (int q = 0; q < CGS_KC; ++q)
+            {
+                const T *vj = V + static_cast<size_t>(min(j0 + q, k1 - 1)) * ldv; // (clamped: a chunk's requests carry no branch)
+#pragma unroll
+                for (int p = 0; p < 2; ++p)
+#pragma unroll
+                    for (int u = 0; u < CUNROLL; ++u)
+                        b[q][p][u] = stream_load<NT>(reinterpret_cast<const VE *>(vj + static_cast<size_t>(p) * h) +
+                                                     min(tile * CTILE + (int)threadIdx.x + u * BLOCK, nv - 1));
+            }
+        };
+
+        for (int j = threadIdx.x; j < 2 * k1; j += BLOCK)
+            c_sh[j] = coef[j];
+        __syncthreads();
+
+        for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
+        {
+            const int base = tile * CTILE + threadIdx.x;
+            VE a[2][CUNROLL], b[CGS_KC][2][CUNROLL];
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int u = 0; u < CUNROLL; ++u)
+                    a[p][u] = stream_load<NT>(xv[p] + min(base + u * BLOCK, nv - 1));
+            for (int j0 = 0; j0 < k1; j0 += CGS_KC)
+            {
+                request_chunk(tile, j0, b);
+#pragma unroll
+                for (int q = 0; q < CGS_KC; ++q)
+                    if (j0 + q < k1) // (uniform)
+                    {
+                        const T yr = c_sh[2 * (j0 + q)], yi = c_sh[2 * (j0 + q) + 1];
+#pragma unroll
+                        for (int u = 0; u < CUNROLL; ++u)
+#pragma unroll
+                            for (int e = 0; e < N; ++e)
+                            {
+                                a[0][u][e] = fmadd(-yi, b[q][1][u][e], fmadd(yr, b[q][0][u][e], a[0][u][e]));
+                                a[1][u][e] = fmadd(yi, b[q][0][u][e], fmadd(yr, b[q][1][u][e], a[1][u][e]));
+                            }
+                    }
+            }
+#pragma unroll
+            for (int u = 0; u < CUNROLL; ++u)
+                if (base + u * BLOCK < nv)
+                {
+                    stream_store<NT>(xv[0] + base + u * BLOCK, a[0][u]);
+                    stream_store<NT>(xv[1] + base + u * BLOCK, a[1][u]);
+                }
+        }
+
+        // scalar tail (everything, when an operand is not 16-byte aligned or h is no multiple of the vector width)
+        const int tid = blockIdx.x * BLOCK + threadIdx.x, stride = gridDim.x * BLOCK;
+        for (int i = nv * N + tid; i < h; i += stride)
+        {
+            T xr = x[i], xi = x[h + i];
+            for (int j = 0; j < k1; ++j)
+            {
+                const T vr = V[static_cast<size_t>(j) * ldv + i], vi = V[static_cast<size_t>(j) * ldv + h + i];
+                xr = fmadd(-c_sh[2 * j + 1], vi, fmadd(c_sh[2 * j], vr, xr));
+                xi = fmadd(c_sh[2 * j + 1], vr, fmadd(c_sh[2 * j], vi, xi));
+            }
+            x[i] = xr;
+            x[h + i] = xi;
+        }
+    }
+
+    template <typename T>
+    int launch_ckrylov_update(int h, T *x, const T *V, long long ldv, int k1, const T *coef, void *stream)
+    {
+        if (h < 0 || h > (1 << 30) - 1 || k1 < 1 || k1 > CGS_KMAX || (k1 > 1 && ldv < 2LL * h))
+            return static_cast<int>(hipErrorInvalidValue);
+        if (h == 0)
+            return 0;
+        const int g = cplx_grid(h);
+        const int vec = h % Pack<T>::N == 0 && aligned16(x) && aligned16(V) && (k1 == 1 || ldv % Pack<T>::N == 0);
+        const dim3 grid(g), block(BLOCK);
+        hipStream_t st = as_stream(stream);
+        const size_t lv = static_cast<size_t>(ldv);
+        if (2LL * h * static_cast<long long>(sizeof(T)) >= NT_BYTES)
+            hipLaunchKernelGGL((ckrylov_update_kernel<T, true>), grid, block, 0, st, h, x, V, lv, k1, coef, vec);
+        else
+            hipLaunchKernelGGL((ckrylov_update_kernel<T, false>), grid, block, 0, st, h, x, V, lv, k1, coef, vec);
+        return launch_status();
+    }
+
     // ---------------- indexed maps
     __global__ void __launch_bounds__(BLOCK) gather_kernel(int n, const int *__restrict__ proj, const double *__restrict__ x, double *__restrict__ y)
     {
@@ -1072,6 +1364,24 @@ extern "C"
                                     const float *coef, float *pout, void *s)
     {
         return launch_krylov_update<float>(n, x, dx, V, ldv, nv, Z, ldz, nz, coef, pout, s);
+    }
+
+    size_t cuddh_hip_cmgs_ws_bytes(void) { return 4 * MAX_PARTIALS * sizeof(double); }
+    int cuddh_hip_cmgs_stage_f64(int h, double *w, const double *vprev, const double *vnext, const double *pin, double *pout, double *hout, void *s)
+    {
+        return launch_cmgs_stage<double>(h, w, vprev, vnext, pin, pout, hout, s);
+    }
+    int cuddh_hip_cmgs_stage_f32(int h, float *w, const float *vprev, const float *vnext, const float *pin, float *pout, float *hout, void *s)
+    {
+        return launch_cmgs_stage<float>(h, w, vprev, vnext, pin, pout, hout, s);
+    }
+    int cuddh_hip_ckrylov_update_f64(int h, double *x, const double *V, long long ldv, int k1, const double *coef, void *s)
+    {
+        return launch_ckrylov_update<double>(h, x, V, ldv, k1, coef, s);
+    }
+    int cuddh_hip_ckrylov_update_f32(int h, float *x, const float *V, long long ldv, int k1, const float *coef, void *s)
+    {
+        return launch_ckrylov_update<float>(h, x, V, ldv, k1, coef, s);
     }
 
     int cuddh_hip_axpby_f64(int n, double a, const double *x, double b, double *y, void *s)

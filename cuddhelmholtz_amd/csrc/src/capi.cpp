@@ -1339,4 +1339,46 @@ extern "C"
             fill_result(o, out, h_res, h_time);
         });
     }
+
+    // ------------------------------------------------------------ GMRES over the complex numbers on split [Re; Im] vectors (krylov.hpp: Arithmetic::complex)
+    int cuddh_gmres_ddh_cplx(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                             cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        return guarded([&]
+        {
+            GmresOptions o_;
+            o_.arithmetic = Arithmetic::complex;
+            auto *h = static_cast<DdhHandle *>(ddh);
+            solver_out o;
+            if (h->is64())
+                o = gmres(n, static_cast<double *>(x), h->f64.get(), static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
+            else
+                o = gmres(n, static_cast<float *>(x), h->f32.get(), static_cast<const float *>(b), m, maxit, static_cast<float>(tol),
+                          verbose, max_seconds, o_);
+            fill_result(o, out, h_res, h_time);
+        });
+    }
+
+    int cuddh_gmres_callback_cplx(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
+                                  int verbose, double max_seconds, cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        return guarded([&]
+        {
+            GmresOptions o_;
+            o_.arithmetic = Arithmetic::complex;
+            solver_out o;
+            if (is_f64)
+            {
+                CallbackOp64 A(cb, ctx);
+                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
+            }
+            else
+            {
+                CallbackOp32 A(cb, ctx);
+                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
+                          max_seconds, o_);
+            }
+            fill_result(o, out, h_res, h_time);
+        });
+    }
 }

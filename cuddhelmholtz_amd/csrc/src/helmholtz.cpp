@@ -131,6 +131,9 @@ namespace cuddh
     solver_out HelmholtzOperator::gmres(double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
                                         const GmresOptions &opt) const
     {
+        // the second row of this operator is negated: it anticommutes with multiplication by i on [u; v] (krylov.hpp: Arithmetic)
+        if (opt.arithmetic == Arithmetic::complex)
+            cuddh_error("gmres error: complex arithmetic cannot be combined with HelmholtzOperator (it is not complex-linear on [u; v]).");
         const int n = 2 * ndof;
         if (!has_native())
             return cuddh::gmres(n, x, this, b, m, maxit, tol, verbose, max_seconds, opt);

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <string>
 
 #include "cuddh_hip.h"
@@ -43,6 +44,11 @@ namespace cuddh
         {
             return cuddh_hip_krylov_update_f32(n, x, dx, V, ldv, nv, Z, ldz, nz, coef, pout, stream());
         }
+
+        inline int k_cmgs_stage(int h, double *w, const double *vp, const double *vn, const double *pi, double *po, double *c) { return cuddh_hip_cmgs_stage_f64(h, w, vp, vn, pi, po, c, stream()); }
+        inline int k_cmgs_stage(int h, float *w, const float *vp, const float *vn, const float *pi, float *po, float *c) { return cuddh_hip_cmgs_stage_f32(h, w, vp, vn, pi, po, c, stream()); }
+        inline int k_cupdate(int h, double *x, const double *V, long long ldv, int k1, const double *coef) { return cuddh_hip_ckrylov_update_f64(h, x, V, ldv, k1, coef, stream()); }
+        inline int k_cupdate(int h, float *x, const float *V, long long ldv, int k1, const float *coef) { return cuddh_hip_ckrylov_update_f32(h, x, V, ldv, k1, coef, stream()); }
 
         // apply the k previous rotations to column h, then build rotation k that zeroes h[k+1]
         template <typename scalar>
@@ -487,6 +493,269 @@ namespace cuddh
             out.num_iter = it;
             return out;
         }
+        // ---- GMRES(m) over the complex numbers on split [Re; Im] vectors (krylov.hpp: Arithmetic::complex)
+        using cplx = std::complex<double>;
+
+        // products and quotients written out (no special-value handling of the library's operators; Smith's division, so that a
+        // real divisor divides both parts by it and nothing else)
+        inline cplx cmul(cplx a, cplx b) { return {a.real() * b.real() - a.imag() * b.imag(), a.real() * b.imag() + a.imag() * b.real()}; }
+        inline cplx cdiv(cplx a, cplx b)
+        {
+            if (std::abs(b.real()) >= std::abs(b.imag()))
+            {
+                const double q = b.imag() / b.real(), d = b.real() + b.imag() * q;
+                return {(a.real() + a.imag() * q) / d, (a.imag() - a.real() * q) / d};
+            }
+            const double q = b.real() / b.imag(), d = b.real() * q + b.imag();
+            return {(a.real() * q + a.imag()) / d, (a.imag() * q - a.real()) / d};
+        }
+
+        // the rotations of rotate_column with complex entries: G_i = [conj(cs_i), conj(sn_i); -sn_i, cs_i], cs_k = h_k / t, sn_k = h_{k+1} / t,
+        // t = sqrt(|h_k|^2 + |h_{k+1}|^2) (h_{k+1}, a norm, is real); with real entries these are rotate_column's own operations
+        void rotate_column_complex(cplx *h, cplx *cs, cplx *sn, int k)
+        {
+            for (int i = 0; i < k; ++i)
+            {
+                const cplx a = h[i], b = h[i + 1];
+                h[i] = cmul(std::conj(cs[i]), a) + cmul(std::conj(sn[i]), b);
+                h[i + 1] = cmul(cs[i], b) - cmul(sn[i], a);
+            }
+            const double t = std::hypot(std::hypot(h[k].real(), h[k].imag()), std::hypot(h[k + 1].real(), h[k + 1].imag()));
+            cs[k] = {h[k].real() / t, h[k].imag() / t};
+            sn[k] = {h[k + 1].real() / t, h[k + 1].imag() / t};
+            h[k] = cmul(std::conj(cs[k]), h[k]) + cmul(std::conj(sn[k]), h[k + 1]);
+            h[k + 1] = 0;
+        }
+
+        template <typename scalar, typename Op>
+        solver_out arnoldi_restarted_complex(int n, scalar *x, const Op *A, const scalar *b, int m, int maxit, scalar tol, int verbose,
+                                             double max_seconds, const GmresOptions &opt)
+        {
+            using clock = std::chrono::high_resolution_clock;
+            const scalar one = 1, zero = 0;
+            const int m1 = m + 1;
+
+            if (opt.orth != Orthogonalization::mgs)
+                cuddh_error("gmres error: complex arithmetic needs orthogonalization mgs.");
+            if (opt.augment != 0)
+                cuddh_error("gmres error: complex arithmetic needs augment = 0.");
+            if (n < 0 || n % 2 != 0)
+                cuddh_error("gmres error: complex arithmetic needs vectors of an even length (real parts, then imaginary parts).");
+            if (m < 1 || m > 512)
+                cuddh_error("gmres error: complex arithmetic takes restart lengths from 1 to 512 (one launch of the update covers every column).");
+            const int half = n / 2;
+            // distance of two basis vectors: n rounded up to 16 bytes (the update reads all of them in one launch)
+            constexpr std::size_t per16 = 16 / sizeof(scalar);
+            const std::size_t ldv = (static_cast<std::size_t>(n) + per16 - 1) / per16 * per16;
+
+            HostDeviceArray<scalar> r_store(n), V_store(ldv * m1);
+            scalar *r = r_store.device_write();
+            scalar *V = V_store.device_write();
+
+            // two halves of partial sums (two rows each), the Hessenberg column under construction (re, im interleaved) and the
+            // coefficients of the update
+            void *ws = nullptr;
+            const std::size_t ws_bytes = cuddh_hip_cmgs_ws_bytes();
+            detail::check_hip(cuddh_hip_malloc_zeroed(&ws, ws_bytes + (2 * (m1 + 1) + 2 * m) * sizeof(double)), "gmres workspace");
+            struct Guard
+            {
+                void *p;
+                ~Guard() { cuddh_hip_free(p); }
+            } guard{ws};
+            scalar *dcol = reinterpret_cast<scalar *>(static_cast<char *>(ws) + ws_bytes);
+            scalar *d_coef = dcol + 2 * (m1 + 1);
+
+            const bool ahead = dynamic_cast<const QueuesDeviceWorkOnly *>(A) != nullptr;
+            struct AheadBuffers
+            {
+                scalar *pin[2] = {nullptr, nullptr};
+                void *ev[2] = {nullptr, nullptr};
+                ~AheadBuffers()
+                {
+                    for (int i = 0; i < 2; ++i)
+                    {
+                        (void)cuddh_hip_host_free(pin[i]);
+                        (void)cuddh_hip_event_destroy(ev[i]);
+                    }
+                }
+            } ab;
+            if (ahead)
+                for (int i = 0; i < 2; ++i)
+                {
+                    detail::check_hip(cuddh_hip_host_alloc(reinterpret_cast<void **>(&ab.pin[i]), sizeof(scalar) * 2 * (m1 + 1)), "gmres pinned column");
+                    detail::check_hip(cuddh_hip_event_create(&ab.ev[i]), "gmres event");
+                }
+            scalar *const *pin = ab.pin;
+            void *const *ev = ab.ev;
+
+            const scalar bnrm = norm(n, b);
+
+            std::vector<cplx> H(static_cast<std::size_t>(m1) * m, cplx(0)), cs(m, cplx(0)), sn(m, cplx(0)), eta(m1, cplx(0));
+            std::vector<scalar> col(2 * (m1 + 1), zero), coef(2 * m, zero);
+
+            solver_out out;
+            out.success = false;
+            out.num_iter = 0;
+            out.num_matvec = 0;
+            out.res_norm.reserve(maxit + 1);
+            out.time.reserve(maxit + 1);
+
+            A->action(x, r);
+            out.num_matvec++;
+            axpby(n, one, b, -one, r); // r = b - A x
+            scalar r_nrm = norm(n, r);
+
+            out.res_norm.push_back(static_cast<double>(r_nrm));
+            out.time.push_back(0.0);
+            const auto t0 = clock::now();
+
+            if (r_nrm < tol * bnrm)
+            {
+                out.success = true;
+                if (verbose)
+                    std::cout << "After 0 iterations, GMRES achieved rel. residual of " << out.res_norm.back() / bnrm
+                              << "\nGMRES successfully converged within desired tolerance." << std::endl;
+                return out;
+            }
+
+            if (verbose)
+                std::cout << std::setprecision(5) << std::scientific;
+
+            int it = 1;
+            for (; it < maxit; ++it)
+            {
+                axpby(n, one / r_nrm, r, zero, V); // v0 = r / ||r||
+                std::fill(eta.begin(), eta.end(), cplx(0));
+                eta[0] = static_cast<double>(r_nrm);
+
+                // One Arnoldi step: the chain of arnoldi_restarted's queue_step with complex coefficients -- stage j applies
+                // h_j = <v_{j-1}, w> and leaves the partial sums of <v_j, w>, the last one those of |w|^2 for mgs_finish on the
+                // n scalars.  k + 3 launches, as there.  dcol[2 j], dcol[2 j + 1] = h_j; dcol[2 (k + 1)] = |w|.
+                auto queue_step = [&](int k)
+                {
+                    scalar *vk = V + static_cast<std::size_t>(k) * ldv;
+                    scalar *vk1 = vk + ldv;
+                    A->action(vk, vk1);
+                    scalar *pa = static_cast<scalar *>(ws), *pb = pa + ws_bytes / (2 * sizeof(double));
+                    detail::check_hip(k_cmgs_stage(half, vk1, static_cast<const scalar *>(nullptr), V, pa, pa, dcol), "gmres complex mgs");
+                    for (int j = 0; j <= k; ++j)
+                    {
+                        const scalar *vj = V + static_cast<std::size_t>(j) * ldv;
+                        const scalar *vnext = (j < k) ? vj + ldv : nullptr;
+                        detail::check_hip(k_cmgs_stage(half, vk1, vj, vnext, pa, pb, dcol + 2 * j), "gmres complex mgs");
+                        std::swap(pa, pb);
+                    }
+                    detail::check_hip(k_mgs_finish(n, vk1, pa, dcol + 2 * (k + 1)), "gmres normalise");
+                    if (ahead)
+                    {
+                        detail::check_hip(cuddh_hip_copy_d2h_async(pin[k & 1], dcol, sizeof(scalar) * (2 * k + 3), stream()), "gmres column copy");
+                        detail::check_hip(cuddh_hip_event_record(ev[k & 1], stream()), "gmres event");
+                    }
+                };
+
+                int k1 = 0;
+                if (ahead)
+                    queue_step(0);
+                for (int k = 0; k < m; ++k)
+                {
+                    k1 = k + 1;
+                    cplx *h = H.data() + static_cast<std::size_t>(m1) * k;
+                    if (ahead)
+                    {
+                        // one step ahead, as on the real path: the step queued beyond an exit is discarded
+                        if (k + 1 < m)
+                            queue_step(k + 1);
+                        detail::check_hip(cuddh_hip_event_sync(ev[k & 1]), "gmres event wait");
+                        std::copy(pin[k & 1], pin[k & 1] + 2 * k + 3, col.data());
+                    }
+                    else
+                    {
+                        queue_step(k);
+                        detail::check_hip(cuddh_hip_stream_sync(stream()), "gmres sync");
+                        detail::check_hip(cuddh_hip_copy_d2h_on(col.data(), dcol, sizeof(scalar) * (2 * k + 3), stream()), "gmres column copy");
+                    }
+                    out.num_matvec++;
+                    for (int j = 0; j < k1; ++j)
+                        h[j] = cplx(static_cast<double>(col[2 * j]), static_cast<double>(col[2 * j + 1]));
+                    h[k1] = static_cast<double>(col[2 * k1]);
+
+                    if (h[k1] == cplx(0))
+                        break;
+
+                    rotate_column_complex(h, cs.data(), sn.data(), k);
+                    eta[k1] = -cmul(sn[k], eta[k]);
+                    eta[k] = cmul(std::conj(cs[k]), eta[k]);
+
+                    if (std::hypot(eta[k1].real(), eta[k1].imag()) < static_cast<double>(tol * bnrm))
+                        break;
+                }
+
+                // back substitution R y = g (back_substitute with complex entries), then x <- x + sum_j y_j v_j in one launch
+                for (int i = k1 - 1; i >= 0; --i)
+                {
+                    cplx sacc = eta[i];
+                    for (int j = i + 1; j < k1; ++j)
+                        sacc -= cmul(H[i + static_cast<std::size_t>(m1) * j], eta[j]);
+                    eta[i] = cdiv(sacc, H[i + static_cast<std::size_t>(m1) * i]);
+                }
+                for (int j = 0; j < k1; ++j)
+                {
+                    coef[2 * j] = static_cast<scalar>(eta[j].real());
+                    coef[2 * j + 1] = static_cast<scalar>(eta[j].imag());
+                }
+                detail::check_hip(cuddh_hip_copy_h2d_on(d_coef, coef.data(), sizeof(scalar) * 2 * k1, stream()), "gmres update coefficients");
+                detail::check_hip(k_cupdate(half, x, V, static_cast<long long>(ldv), k1, d_coef), "gmres complex update");
+
+                A->action(x, r);
+                out.num_matvec++;
+                axpby(n, one, b, -one, r);
+                r_nrm = norm(n, r);
+
+                out.res_norm.push_back(static_cast<double>(r_nrm));
+                const double elapsed = std::chrono::duration<double>(clock::now() - t0).count();
+                out.time.push_back(elapsed);
+                if (elapsed > max_seconds)
+                    break;
+
+                if (verbose == 1)
+                {
+                    const int width = 30;
+                    const int filled = std::min(width, width * it / std::max(1, maxit - 1));
+                    std::cout << "[" << std::string(filled, '#') << std::string(width - filled, ' ') << "] || iteration "
+                              << std::setw(10) << it + 1 << " / " << maxit << " || rel. res. = " << std::setw(10)
+                              << r_nrm / bnrm << "\r" << std::flush;
+                }
+                else if (verbose >= 2)
+                {
+                    std::cout << "iteration " << std::setw(10) << it + 1 << " / " << maxit
+                              << " || rel. res. = " << std::setw(10) << r_nrm / bnrm << std::endl;
+                }
+
+                if (r_nrm < tol * bnrm)
+                {
+                    out.success = true;
+                    break;
+                }
+            }
+
+            if (verbose == 1)
+                std::cout << std::endl;
+            if (verbose)
+                std::cout << "After " << it << " iterations, GMRES achieved rel. residual of " << out.res_norm.back() / bnrm
+                          << (out.success ? "\nGMRES successfully converged within desired tolerance."
+                                          : "\nGMRES failed to converge within desired tolerance.")
+                          << std::endl;
+
+            out.num_iter = it;
+            return out;
+        }
+
+        [[noreturn]] void refuse_complex(const char *with)
+        {
+            const std::string msg = std::string("gmres error: complex arithmetic cannot be combined with ") + with + ".";
+            cuddh_error(msg.c_str());
+            throw std::runtime_error(msg);
+        }
     } // namespace
 
     solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose,
@@ -532,12 +801,16 @@ namespace cuddh
     solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
                      const GmresOptions &opt)
     {
+        if (opt.arithmetic == Arithmetic::complex)
+            return arnoldi_restarted_complex<double>(n, x, A, b, m, maxit, tol, verbose, max_seconds, opt);
         return arnoldi_restarted<double>(n, x, A, b, m, maxit, tol, verbose, max_seconds, nullptr, opt.orth, opt.augment);
     }
 
     solver_out gmres(int n, double *x, const Operator *A, const double *b, const Operator *Precond, int m, int maxit, double tol, int verbose,
                      double max_seconds, const GmresOptions &opt)
     {
+        if (opt.arithmetic == Arithmetic::complex)
+            refuse_complex("a preconditioner");
         LeftPreconditioned PA(n, A, Precond);
         host_device_dvec Pb(n);
         double *d_Pb = Pb.device_write();
@@ -548,18 +821,24 @@ namespace cuddh
     solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
                      double max_seconds, const GmresOptions &opt)
     {
+        if (opt.arithmetic == Arithmetic::complex)
+            return arnoldi_restarted_complex<float>(n, x, A, b, m, maxit, tol, verbose, max_seconds, opt);
         return arnoldi_restarted<float>(n, x, A, b, m, maxit, tol, verbose, max_seconds, nullptr, opt.orth, opt.augment);
     }
 
     solver_out gmres(int n, double *x, const Operator *A, const double *b, int m, int maxit, double tol, int verbose,
                      double max_seconds, const ScalarReduce &reduce, const GmresOptions &opt)
     {
+        if (opt.arithmetic == Arithmetic::complex)
+            refuse_complex("partitioned vectors (a ScalarReduce)");
         return arnoldi_restarted<double>(n, x, A, b, m, maxit, tol, verbose, max_seconds, reduce.fn ? &reduce : nullptr, opt.orth, opt.augment);
     }
 
     solver_out gmres(int n, float *x, const SinglePrecisionOperator *A, const float *b, int m, int maxit, float tol, int verbose,
                      double max_seconds, const ScalarReduce &reduce, const GmresOptions &opt)
     {
+        if (opt.arithmetic == Arithmetic::complex)
+            refuse_complex("partitioned vectors (a ScalarReduce)");
         return arnoldi_restarted<float>(n, x, A, b, m, maxit, tol, verbose, max_seconds, reduce.fn ? &reduce : nullptr, opt.orth, opt.augment);
     }
 

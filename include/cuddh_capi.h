@@ -285,6 +285,16 @@ int cuddh_gmres_callback_aug(int n, void *x, cuddh_action_cb cb, void *ctx, cons
 int cuddh_gmres_callback_sharded_aug(int n, void *x, cuddh_action_cb cb, void *ctx, cuddh_reduce_cb reduce, void *reduce_ctx,
                                      const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
                                      int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time);
+/* The same iteration over the COMPLEX numbers (GmresOptions::arithmetic = complex, csrc/include/cuddh/krylov.hpp): x and b hold
+ * n / 2 complex numbers, real parts in the first half and imaginary parts in the second (a DDH trace vector [lambda; mu]), the operator
+ * must be complex-linear in that sense (to a few 1e-3 is enough: the true residual ends every cycle and decides), and m operator
+ * applications minimise over complex instead of real combinations of the Krylov vectors with the same vectors, bytes and launches.
+ * Modified Gram-Schmidt, no augmentation, single process; argument lists of cuddh_gmres_ddh / cuddh_gmres_callback.  An odd n or
+ * m outside [1, 512] returns nonzero, cuddh_last_error() beginning "gmres error: complex arithmetic". */
+int cuddh_gmres_ddh_cplx(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
+                         cuddh_solver_result *out, double *h_res, double *h_time);
+int cuddh_gmres_callback_cplx(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
+                              int verbose, double max_seconds, cuddh_solver_result *out, double *h_res, double *h_time);
 
 #ifdef __cplusplus
 }

@@ -127,6 +127,27 @@ int cuddh_hip_krylov_update_f64(int n, double *x, double *dx, const double *V, l
                                 const double *coef, double *pout, void *stream);
 int cuddh_hip_krylov_update_f32(int n, float *x, float *dx, const float *V, long long ldv, int nv, const float *Z, long long ldz, int nz,
                                 const float *coef, float *pout, void *stream);
+/* Complex arithmetic on SPLIT vectors (gmres(..., GmresOptions{arithmetic = complex})): a vector of 2 h scalars stands for h complex
+ * numbers, real parts at [0, h), imaginary parts at [h, 2 h), one allocation.  Every operand is a device pointer.
+ * cmgs_stage: mgs_stage with a complex coefficient, one launch.
+ *   c = (sum of pin[0 .. g)) + i (sum of pin[1024 .. 1024 + g)), stored to hout[0], hout[1]  (= <vprev, w>, left by the previous stage);
+ *   w <- w - c vprev:  w_r -= c_r v_r - c_i v_i,  w_i -= c_r v_i + c_i v_r;
+ *   pout[b], pout[1024 + b] <- workgroup b's partial sums of Re, Im <vnext, w> = (v_r w_r + v_i w_i) + i (v_r w_i - v_i w_r).
+ * vprev == NULL starts a chain (no update, pin / hout ignored).  vnext == NULL is the finish stage: pout[b] <- partial sums of
+ * |w|^2 over all 2 h scalars, pout[1024 + b] <- 0; cuddh_hip_mgs_finish_*(2 h, w, pout, hout) then normalises w as on the real
+ * chain (g = cuddh_hip_cgs_partials(2 h) workgroups in both).  pin and pout are the two halves of a workspace of
+ * cuddh_hip_cmgs_ws_bytes() bytes, used alternately.  Launches per Arnoldi step: those of the real chain.
+ * ckrylov_update: x <- x + sum_j (coef[2 j] + i coef[2 j + 1]) v_j, v_j = V + j ldv, 0 <= j < k1 <= 512, per element in ascending j,
+ * one launch; x is read and written once; vectors of 64 MiB and more are streamed with the non-temporal hint.
+ * 16-byte accesses when h is a multiple of the 16-byte vector's width and the operands (and, for k1 > 1, ldv * sizeof) are 16-byte
+ * aligned; element-wise for the whole vector otherwise (an odd h leaves the imaginary half misaligned).  Fixed summation order.
+ * h == 0 does nothing; h < 0, h >= 2^30, k1 outside [1, 512] or ldv < 2 h with k1 > 1 returns hipErrorInvalidValue and launches
+ * nothing. */
+size_t cuddh_hip_cmgs_ws_bytes(void);
+int cuddh_hip_cmgs_stage_f64(int h, double *w, const double *vprev, const double *vnext, const double *pin, double *pout, double *hout, void *stream);
+int cuddh_hip_cmgs_stage_f32(int h, float *w, const float *vprev, const float *vnext, const float *pin, float *pout, float *hout, void *stream);
+int cuddh_hip_ckrylov_update_f64(int h, double *x, const double *V, long long ldv, int k1, const double *coef, void *stream);
+int cuddh_hip_ckrylov_update_f32(int h, float *x, const float *V, long long ldv, int k1, const float *coef, void *stream);
 int cuddh_hip_copy_f64(int n, const double *x, double *y, void *stream);
 int cuddh_hip_copy_f32(int n, const float *x, float *y, void *stream);
 int cuddh_hip_copy_i32(int n, const int *x, int *y, void *stream);
