@@ -421,7 +421,9 @@ class DDH:
     n_basis^2 block^2 <= 1024 that divides nx and ny is accepted, anything else raises here.  Off the reference's size the
     kernels are 1 (any block), 11 (n_basis 4, block 8, 'f32': one 8x8 block per wavefront; what auto picks there) and 12
     (n_basis 5, block 4, 'f32', rectangles: one element per lane, four 4x4 blocks per wavefront; time_step "mesh" and "rk2"
-    only; what auto picks there from the subdomain count at which it measured faster than kernel 1).  Larger
+    only; what auto picks there from the subdomain count at which it measured faster than kernel 1) and 13 (on request only:
+    the local solves of kernel 5's element-lane form at n_basis 4 and of kernel 12 at n_basis 5, block 4, 'f32', four
+    subdomains per wavefront, on any time_step; "rk2" only; sweep_form() is 0 and set_sweep_form(2) raises).  Larger
     subdomains need fewer GMRES iterations and shorter Krylov vectors but more WaveHoltz iterations (set_wh_iters) for the
     same accuracy.  info()["nel1d"] reports the block in effect.
 
@@ -432,6 +434,12 @@ class DDH:
     An integer array (one ratio >= 1 per subdomain): those ratios.  time_ratios() returns r; info()["nt"], info()["dt"] and
     table("filter" | "cs" | "sn") stay the base grid's, table("filter@5") etc. are those of the grid of 5 x the mesh grid's steps.
     A bad array, a non-finite or non-positive a under "coefficient", and a ratio above 256 raise ValueError here.
+    Kernels that hold one subdomain per wavefront or workgroup take any time_step; of those that hold several, kernel 13
+    alone does (kernel=5 then runs its matrix form, auto leaves 6, 7 and 12 for 1, and 6, 7 and 12 on request raise on first
+    use).  A wavefront of kernel 13 marches once per distinct ratio among its four subdomains and costs the sum of those
+    marches.  action(), rhs() and local_traces over all subdomains run them sorted by ratio, so at most (number of distinct
+    ratios - 1) wavefronts hold more than one; sub-ranges and local_traces_listed run in the caller's order: list
+    subdomains of one ratio next to each other, in groups of four, or a wavefront pays for every ratio it holds.
 
     integrator, coarsen: how the local solves step in time.  "rk2" (the default, the reference's): the explicit midpoint rule on
     the mesh grid, two stiffness sweeps per step; coarsen must be None or 1.  "rk4": classical Runge-Kutta, four sweeps per
@@ -442,7 +450,7 @@ class DDH:
     is closer to the exact local solve than RK2 on the mesh grid, in half the sweeps.  Stable range: with
     a == 1 it ends near coarsen 23 (hence the cap of 16); it scales with min a over a subdomain unless
     time_step="coefficient" compensates: with a = 0.2 under "mesh", coarsen <= 4.  Kernels 1, 2, 5 (matrix form) and 8 (and
-    from_labels' 9 and 10) have an RK4 form; auto picks among them (info()["kernel"]), any other kernel on request raises RuntimeError on first use.  A bad
+    from_labels' 9 and 10) have an RK4 form; auto picks among them (info()["kernel"]), any other kernel on request (3, 4, 6, 7, 11, 12, 13) raises RuntimeError on first use.  A bad
     name, a coarsen that is no integer in [1, 16] and coarsen > 1 with "rk2" raise ValueError here."""
 
     _INT_TABLES = ("B", "gI", "sI")
@@ -618,7 +626,7 @@ class DDH:
         return form
 
     def set_owner_rule(self, last: bool):
-        """Kernels 11 and 12: the last copy of every node that elements share publishes instead of the first (a check: same results).
+        """Kernels 11, 12 and 13: the last copy of every node that elements share publishes instead of the first (a check: same results).
         Refused on any other kernel (cuddh_hip_ddh_plan_set_owner_rule)."""
         N.check_capi(lib.cuddh_ddh_set_owner_rule(self._h, 1 if last else 0), "DDH.set_owner_rule")
 

@@ -9,7 +9,8 @@
 //   K corrections augment every restart cycle, krylov.hpp GmresOptions; 0 <= K < m, 0 is the default; single-process path only;
 //   the summary line names it when it is not 0), --block N --kernel K (the DDH constructor's block and kernel: N x N elements
 //   per subdomain, 0 the reference's 16 / n_basis; K as cuddh_hip_ddh_plan_create numbers them, 0 auto; single-process path
-//   only; n_basis 5 needs --block 4 wherever 3 does not divide nx, and then runs kernel 12 where auto or K = 12 picks it; the
+//   only; n_basis 5 needs --block 4 wherever 3 does not divide nx, and then runs kernel 12 where auto or K = 12 picks it, and K = 13
+//   (the same local solves, on per-subdomain time grids too) together with --time-step coefficient; the
 //   summary line names block and kernel when either is given), --arithmetic real|complex (krylov.hpp Arithmetic: complex runs
 //   GMRES over the complex numbers on the trace vectors [lambda; mu]; real is the default; needs --orth mgs and --augment 0;
 //   single-process path only; the summary line names it when it is complex)

@@ -132,7 +132,7 @@ namespace cuddh
             /// cannot take throws).  sweep_form() returns the form in effect.
             void set_sweep_form(int form) const;
             int sweep_form() const;
-            /// Kernel 11's and kernel 12's owner rule: which copy of a node shared by 2 or 4 elements publishes (false: the first, the default;
+            /// The owner rule of kernels 11, 12 and 13: which copy of a node shared by 2 or 4 elements publishes (false: the first, the default;
             /// true: the last).  A check that the copies are bitwise equal (cuddh_hip_ddh_plan_set_owner_rule); other kernels throw.
             void set_last_copy_publishes(bool last) const;
             const EnsembleSpace &ensemble() const { return *efem; }
@@ -222,7 +222,10 @@ namespace cuddh
         /// extension: subdomains of block x block elements (0 or 16 / n_basis: the size of the constructors above).  Needs
         /// block >= 1, n_basis^2 block^2 <= 1024, nx and ny multiples of block; throws otherwise.  kernel: 0 auto, 1 generic
         /// workgroup (any block), 11 one 8 x 8 block per wavefront (n_basis 4, block 8, fp32), 12 four 4 x 4 blocks per wavefront
-        /// with one element per lane (n_basis 5, block 4, fp32, rectangles, one time grid, RK2); 2-8 on their own block size only.
+        /// with one element per lane (n_basis 5, block 4, fp32, rectangles, one time grid, RK2), 13 (on request only) the
+        /// element-lane local solves with four 4 x 4 blocks per wavefront at n_basis 4 or 5 (block 4, fp32, rectangles, RK2) that
+        /// take any DDHTimeStep: a wavefront marches once per distinct time grid among its four subdomains; 2-8 on their own
+        /// block size only.
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block);
         /// extension: the same with a time-step policy (DDHTimeStep: from the mesh, from the coefficient, or given per subdomain)
         DDH(double omega, const double *h_a, const H1Space &fem, int nx, int ny, int kernel, int block, const DDHTimeStep &time_step);

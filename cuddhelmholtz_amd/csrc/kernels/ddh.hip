@@ -56,7 +56,8 @@ struct cuddh_ddh_plan
                 // cores, uniform geometry);  6 / 7 ddh_wave8_kernel (nb == 8; 7 separable, fp32);  9 ddh_general_wave_kernel
                 // (nb == 4, <= 16 elements, CSR lists);  10 ddh_block_kernel with CSR lists;  11 ddh_element_lane8_kernel (nb == 4,
                 // 8x8 elements, fp32: one element per lane, one subdomain per wavefront);  12 ddh_element_lane5_kernel (nb == 5, 4x4
-                // elements, fp32: one element per lane, four subdomains per wavefront)
+                // elements, fp32: one element per lane, four subdomains per wavefront);  13 on request: the element-lane kernels
+                // with four subdomains per wavefront (nb == 4 or 5, 4x4 elements, fp32) that take per-subdomain time grids
     int nodes;  // nb*nb*nel1d*nel1d (general plans: nb*nb*mx_elems)
     int wh_iters = 5; // WaveHoltz iterations per local solve (source/DDH.cpp:136); WH_ITERS_REFERENCE
     const int *gI_override = nullptr; // cuddh_hip_ddh_plan_set_vector_layout: x and y in another numbering than d.gI
@@ -66,7 +67,7 @@ struct cuddh_ddh_plan
     float *Sep = nullptr; // kernel 7: [Ax | Ay | beta | gamma] of the separable nb = 8 sweep
     float *Sep4 = nullptr; // kernel 5, element-lane form, and kernel 11: [Bx | By | Dg | W | 1 / W] (build_element_lane_tables); null: does not qualify.
                            // kernel 12: the same table with 5 in place of 4
-    int last_copy = 0; // kernels 11 and 12: the last copy of a shared node publishes, not the first (cuddh_hip_ddh_plan_set_owner_rule)
+    int last_copy = 0; // kernels 11, 12 and 13: the last copy of a shared node publishes, not the first (cuddh_hip_ddh_plan_set_owner_rule)
     int sweep_form = 0; // kernel 5: 0 auto, 1 matrix form, 2 element-lane form, 3 the same with the other owner rule (cuddh_hip_ddh_plan_set_sweep_form)
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
@@ -178,6 +179,80 @@ namespace
         const int filt_off = wave_uniform(tg.filt_off), cs_off = wave_uniform(tg.cs_off);
         return {wave_uniform(tg.nt), wave_uniform(tg.dt), filt + filt_off, cs + cs_off, sn + cs_off};
     }
+
+    // ---------------------------------------------------------------- time grids with four subdomains per wavefront (kernel 13)
+    // ddh_element_lane_kernel and ddh_element_lane5_kernel hold a subdomain per 16-lane DPP row and one time grid per march.
+    // Their TimeGrids instantiations march once per distinct grid among the wavefront's rows: a pass takes the lowest row
+    // not yet published as its leader and that row's grid g; rows on g load, march and publish their own subdomain, every
+    // other row takes the leader's (the rule of a launch's tail rows: real data in every row, nothing published).  All that
+    // waits through the time loop is one scalar, the mask of the rows that have published: the view below is formed from it
+    // at the start of a pass and again behind the march (these kernels have no register to keep it in).
+    struct GroupedRows
+    {
+        int pending, s_lead, g; // rows of the launch still to publish (bit per row, never 0); this pass's leader subdomain and grid
+    };
+
+    template <typename Real>
+    __device__ inline GroupedRows grouped_rows(const DdhArgs<Real> &A, int s_first, int done, const TimeGrids<Real> &TG)
+    {
+        GroupedRows R;
+        const int rows = A.dom_end - s_first; // >= 1: the wavefront has returned otherwise
+        R.pending = wave_uniform((rows >= 4 ? 15 : (1 << rows) - 1) & ~done);
+        R.s_lead = wave_uniform(A.dom_list[s_first + __builtin_ctz(R.pending)]);
+        R.g = wave_uniform(TG.grid_of[R.s_lead]);
+        return R;
+    }
+
+    // row `sub` in this pass: active (returns true, s = its own subdomain) or a copy of the leader
+    template <typename Real>
+    __device__ inline bool grouped_row(const DdhArgs<Real> &A, int s_first, int sub, const GroupedRows &R, const TimeGrids<Real> &TG, int &s)
+    {
+        bool active = (R.pending >> sub) & 1; // a row of the launch (s_first + sub < A.dom_end) that has not published
+        s = R.s_lead;
+        if (active)
+        {
+            const int own = A.dom_list[s_first + sub];
+            active = TG.grid_of[own] == R.g;
+            if (active)
+                s = own;
+        }
+        return active;
+    }
+
+    // the rows that publish in this pass (bit 16 r of the ballot: all lanes of a row agree) and, whatever memory says, the
+    // leader, so that every pass ends with fewer rows to go
+    __device__ inline int grouped_published(const GroupedRows &R, bool active)
+    {
+        const unsigned long long b = __builtin_amdgcn_ballot_w64(active);
+        return static_cast<int>((b & 1u) | ((b >> 15) & 2u) | ((b >> 30) & 4u) | ((b >> 45) & 8u)) | (R.pending & -R.pending);
+    }
+
+    // The launch's arguments read again: from the kernel-argument segment, where a DdhArgs that is the kernel's FIRST
+    // parameter starts at offset 0, through a pointer the compiler cannot connect with the one it holds.  A pass reads them
+    // before its loads and again behind its march (scalar loads): of the copy the compiler holds, everything a pass needs
+    // would wait in scalar registers from before the first pass to the last, through every march, and these kernels have
+    // none to spare (spilled to vector lanes they cost the vector registers that decide the occupancy).
+    template <typename Real>
+    __device__ inline void reread_args(DdhArgs<Real> &L)
+    {
+        using Segment = const __attribute__((address_space(4))) DdhArgs<Real>;
+        Segment *k = (Segment *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(k));
+        __builtin_memcpy(&L, k, sizeof L);
+    }
+
+    // threadIdx.x & 63 without threadIdx.x, formed where it is called (the opaque 0 keeps the compiler from forming it once
+    // and keeping it): with the wavefront's first position in a scalar register a pass needs nothing else of the thread
+    // index, whose vector register is then free through the march
+    __device__ inline int lane_here()
+    {
+        int zero = 0;
+        asm volatile("" : "+v"(zero));
+        return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+    }
+
+    template <typename T, typename... Rest>
+    __device__ inline const T &first_of(const T &t, const Rest &...) { return t; }
 
     // ---------------------------------------------------------------- the integrator of a launch
     // A plan with cuddh_hip_ddh_plan_set_integrator(plan, 1) steps with classical RK4.  Its kernels are instantiations of their
@@ -1805,28 +1880,63 @@ namespace
         }
     }
 
-    template <bool FORCED, bool HOLD, bool LAST_COPY>
+    // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
+    template <bool FORCED, bool HOLD, bool LAST_COPY, typename... Grids>
     __global__ void __launch_bounds__(256, 3) ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
-                                                                     const float *__restrict__ cs, const float *__restrict__ sn)
+                                                                     const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
     {
+        constexpr bool GROUPED = sizeof...(Grids) > 0;
+        static_assert(sizeof...(Grids) <= 1 && scheme_of<Grids...> == 0, "one grid, or TimeGrids; no RK4 form");
         const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
         if (s_first >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
         if constexpr (HOLD)
             __builtin_amdgcn_s_setprio(3);
+        [[maybe_unused]] const int w_first = wave_uniform(s_first); // GROUPED: the wavefront's first position, scalar
+        [[maybe_unused]] int done = 0; // GROUPED: the rows that have published, a bit each; what a pass leaves to the next
+        [[maybe_unused]] GroupedRows rows{}; // of the pass under way: locate forms it
+        [[maybe_unused]] DdhArgs<float> Ap;  // GROUPED: A as the pass read it (reread_args)
+        const DdhArgs<float> &Ar = [&]() -> const DdhArgs<float> &
+        {
+            if constexpr (GROUPED)
+                return Ap;
+            else
+                return A;
+        }();
+        do
+        {
+        if constexpr (GROUPED)
+            reread_args(Ap);
         // where this lane works: subdomain s (valid: and publishes it), its trace dofs, the dofs of its element's nodes
         auto locate = [&](int tid, bool &valid, int &s, int &fdof, const int *&sI)
         {
             const int sub = (tid >> 4) & 3;
-            valid = s_first + sub < A.dom_end;
-            s = domain_at(A, valid ? s_first + sub : s_first);
-            fdof = A.s_fdof[s];
-            sI = A.sI + 256 * (size_t)s + 16 * (tid & 15);
+            if constexpr (GROUPED)
+            {
+                // from the lane, w_first and done alone: behind the march nothing of the first time is there to be kept
+                rows = grouped_rows(Ar, w_first, done, first_of(grids...));
+                valid = grouped_row(Ar, w_first, sub, rows, first_of(grids...), s);
+            }
+            else
+            {
+                valid = s_first + sub < Ar.dom_end;
+                s = domain_at(Ar, valid ? s_first + sub : s_first);
+            }
+            fdof = Ar.s_fdof[s];
+            sI = Ar.sI + 256 * (size_t)s + 16 * (tid & 15);
         };
         bool valid;
         int s, fdof;
         const int *sI;
-        locate(threadIdx.x, valid, s, fdof, sI);
+        int tid = threadIdx.x;
+        if constexpr (GROUPED)
+            tid = lane_here(); // a pass starts from a lane index of its own, or what the last pass derived from it waits through the march
+        locate(tid, valid, s, fdof, sI);
+        // 0, in a way the compiler cannot see (done < 16): W and 1 / W, which only the loads before the march need, are read
+        // at an index that depends on the pass, or all of them are kept for the next pass, through the time loop
+        [[maybe_unused]] const int again = GROUPED ? done >> 4 : 0;
+        // the pass's time grid (the leader's; one grid: the launch's), scalar
+        const TimeGridView<float> tg = time_grid_of(Ar, GROUPED ? rows.s_lead : s, filt, cs, sn, grids...);
 
         pair_t invm[8], Hi[8], F[8], Gf[8], u[8], v[8];
 #pragma unroll
@@ -1834,8 +1944,8 @@ namespace
         {
             const int P = el_pair(n & 3, n >> 2), half = el_half(n >> 2);
             float im, hi, f, gf;
-            load_dof(A, s, sI[n], fdof, im, hi, f, gf);
-            const float W = Sep4[48 + n], rW = Sep4[64 + n];
+            load_dof(Ar, s, sI[n], fdof, im, hi, f, gf);
+            const float W = Sep4[48 + n + again], rW = Sep4[64 + n + again];
             invm[P][half] = im * W;
             Hi[P][half] = hi * rW;
             F[P][half] = f * rW;
@@ -1871,15 +1981,25 @@ namespace
                 z[k].x = dn[k];
             }
         };
-        wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, ELEMENT_LANE_DM_PAIRS(FORCED)>(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, ELEMENT_LANE_DM_PAIRS(FORCED)>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
 
         // located a second time from a lane index the compiler cannot connect with the first: otherwise these values stay
         // in (or are spilled from) vector registers for the whole time loop, which runs at the limit of three wavefronts per SIMD
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
+        if constexpr (GROUPED)
+        {
+            tid = lane_here();
+            asm volatile("" : "+s"(done));
+            reread_args(Ap);
+        }
+        else
+        {
+            tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+        }
         locate(tid, valid, s, fdof, sI);
-        if (!valid)
-            return;
+        if constexpr (!GROUPED)
+            if (!valid)
+                return;
 #pragma unroll
         for (int n = 0; n < 16; ++n)
         {
@@ -1888,10 +2008,13 @@ namespace
             const int k = n & 3, l = n >> 2;
             const bool first = !(k == 0 && (tid & 3) > 0) && !(l == 0 && (tid & 12) > 0);
             const bool last = !(k == 3 && (tid & 3) < 3) && !(l == 3 && (tid & 12) < 12);
-            const bool owner = LAST_COPY ? last : first;
+            const bool owner = (LAST_COPY ? last : first) && (!GROUPED || valid);
             if (owner)
-                publish_dof(A, s, sI[n], fdof, u[el_pair(k, l)][el_half(l)], v[el_pair(k, l)][el_half(l)], false);
+                publish_dof(Ar, s, sI[n], fdof, u[el_pair(k, l)][el_half(l)], v[el_pair(k, l)][el_half(l)], false);
         }
+        if constexpr (GROUPED)
+            done |= grouped_published(rows, valid);
+        } while (GROUPED && (rows.pending & ~done) != 0);
     }
 
     // ---------------------------------------------------------------- kernel 11 (NB = 4, 8x8 elements, rectangles): one subdomain per wavefront
@@ -2042,35 +2165,70 @@ namespace
             }
     }
 
-    template <bool FORCED, bool HOLD, bool LAST_COPY>
+    // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
+    template <bool FORCED, bool HOLD, bool LAST_COPY, typename... Grids>
     __global__ void __launch_bounds__(256, FORCED ? 1 : 2) ddh_element_lane5_kernel(DdhArgs<float> A, const float *__restrict__ Sep5, const float *__restrict__ filt,
-                                                                      const float *__restrict__ cs, const float *__restrict__ sn)
+                                                                      const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
     {
+        constexpr bool GROUPED = sizeof...(Grids) > 0;
+        static_assert(sizeof...(Grids) <= 1 && scheme_of<Grids...> == 0, "one grid, or TimeGrids; no RK4 form");
         const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
         if (s_first >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
         if constexpr (HOLD)
             __builtin_amdgcn_s_setprio(3);
+        [[maybe_unused]] const int w_first = wave_uniform(s_first); // GROUPED: the wavefront's first position, scalar
+        [[maybe_unused]] int done = 0; // GROUPED: the rows that have published, a bit each; what a pass leaves to the next
+        [[maybe_unused]] GroupedRows rows{}; // of the pass under way: locate forms it
+        [[maybe_unused]] DdhArgs<float> Ap;  // GROUPED: A as the pass read it (reread_args)
+        const DdhArgs<float> &Ar = [&]() -> const DdhArgs<float> &
+        {
+            if constexpr (GROUPED)
+                return Ap;
+            else
+                return A;
+        }();
+        do
+        {
+        if constexpr (GROUPED)
+            reread_args(Ap);
         // where this lane works: subdomain s (valid: and publishes it), its trace dofs, the dofs of its element's nodes
         auto locate = [&](int tid, bool &valid, int &s, int &fdof, const int *&sI)
         {
             const int sub = (tid >> 4) & 3;
-            valid = s_first + sub < A.dom_end;
-            s = domain_at(A, valid ? s_first + sub : s_first);
-            fdof = A.s_fdof[s];
-            sI = A.sI + 400 * (size_t)s + 25 * (tid & 15);
+            if constexpr (GROUPED)
+            {
+                // from the lane, w_first and done alone: behind the march nothing of the first time is there to be kept
+                rows = grouped_rows(Ar, w_first, done, first_of(grids...));
+                valid = grouped_row(Ar, w_first, sub, rows, first_of(grids...), s);
+            }
+            else
+            {
+                valid = s_first + sub < Ar.dom_end;
+                s = domain_at(Ar, valid ? s_first + sub : s_first);
+            }
+            fdof = Ar.s_fdof[s];
+            sI = Ar.sI + 400 * (size_t)s + 25 * (tid & 15);
         };
         bool valid;
         int s, fdof;
         const int *sI;
-        locate(threadIdx.x, valid, s, fdof, sI);
+        int tid = threadIdx.x;
+        if constexpr (GROUPED)
+            tid = lane_here(); // a pass starts from a lane index of its own, or what the last pass derived from it waits through the march
+        locate(tid, valid, s, fdof, sI);
+        // 0, in a way the compiler cannot see (done < 16): W and 1 / W, which only the loads before the march need, are read
+        // at an index that depends on the pass, or all of them are kept for the next pass, through the time loop
+        [[maybe_unused]] const int again = GROUPED ? done >> 4 : 0;
+        // the pass's time grid (the leader's; one grid: the launch's), scalar
+        const TimeGridView<float> tg = time_grid_of(Ar, GROUPED ? rows.s_lead : s, filt, cs, sn, grids...);
 
         float invm[25], Hi[25], F[25], Gf[25], u[25], v[25];
 #pragma unroll
         for (int n = 0; n < 25; ++n)
         {
-            load_dof(A, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
-            const float W = Sep5[75 + n], rW = Sep5[100 + n];
+            load_dof(Ar, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
+            const float W = Sep5[75 + n + again], rW = Sep5[100 + n + again];
             invm[n] *= W;
             Hi[n] *= rW;
             F[n] *= rW;
@@ -2108,14 +2266,24 @@ namespace
                 z[k] = dn[k];
             }
         };
-        wh_march<FORCED ? 2 : 1, ELEMENT5_INTERIOR_REGISTERS>(A, A.nt, A.dt, filt, cs, sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march<FORCED ? 2 : 1, ELEMENT5_INTERIOR_REGISTERS>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
 
         // located a second time from a lane index the compiler cannot connect with the first, as in ddh_element_lane_kernel
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
+        if constexpr (GROUPED)
+        {
+            tid = lane_here();
+            asm volatile("" : "+s"(done));
+            reread_args(Ap);
+        }
+        else
+        {
+            tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+        }
         locate(tid, valid, s, fdof, sI);
-        if (!valid)
-            return;
+        if constexpr (!GROUPED)
+            if (!valid)
+                return;
 #pragma unroll
         for (int n = 0; n < 25; ++n)
         {
@@ -2124,10 +2292,13 @@ namespace
             const int k = n % 5, l = n / 5;
             const bool first = !(k == 0 && (tid & 3) > 0) && !(l == 0 && (tid & 12) > 0);
             const bool last = !(k == 4 && (tid & 3) < 3) && !(l == 4 && (tid & 12) < 12);
-            const bool owner = LAST_COPY ? last : first;
+            const bool owner = (LAST_COPY ? last : first) && (!GROUPED || valid);
             if (owner)
-                publish_dof(A, s, sI[n], fdof, u[n], v[n], false);
+                publish_dof(Ar, s, sI[n], fdof, u[n], v[n], false);
         }
+        if constexpr (GROUPED)
+            done |= grouped_published(rows, valid);
+        } while (GROUPED && (rows.pending & ~done) != 0);
     }
 
     // kernels 5, 8, 11 and 12 leave the boundary terms out on the element-interior nodes (k, l in 1 .. nb - 2): is none of them a
@@ -2708,7 +2879,7 @@ namespace
     // scratch and at the occupancy of its RK2 form, and none does ("Runge-Kutta 4", the table from the code
     // objects): kernel 11 and kernel 5's element-lane form, sixteen values per lane, spill 216 to 236 bytes in the form without
     // x, and kernels 3 and 4 go from 86 / 90 to 98 / 99 vector registers, five wavefronts per SIMD to four.  Kernels 6 and 7
-    // have none by decision, and kernel 12 (25 values per lane, one wavefront per SIMD already in RK2) has none either.  The label-built plans' kernels 9 (wh_march around its LDS assembly, no scratch) and 10 (kernel 1's
+    // have none by decision, and kernel 12 (25 values per lane, one wavefront per SIMD already in RK2) has none either; kernel 13 is the same two kernels.  The label-built plans' kernels 9 (wh_march around its LDS assembly, no scratch) and 10 (kernel 1's
     // form with the plan's lists) have one.
     constexpr bool has_rk4_form(int kernel) { return kernel == 1 || kernel == 2 || kernel == 5 || kernel == 8 || kernel == 9 || kernel == 10; }
 
@@ -2727,46 +2898,46 @@ namespace
         return p->Sep4 && p->d.n_domains >= ELEMENT_LANE_MIN_DOMAINS ? 2 : 1;
     }
 
-    template <bool LAST_COPY>
+    template <bool LAST_COPY, typename... Grids>
     void launch_element_lane(const DdhArgs<float> &A, const float *Sep4, int n_local, hipStream_t st, const float *fl, const float *cs,
-                             const float *sn)
+                             const float *sn, Grids... grids)
     {
         const dim3 grid((n_local + 15) / 16), block(256); // four subdomains per wavefront, four wavefronts per workgroup
         if (A.x)
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane_kernel<true, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane_kernel<true, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_element_lane_kernel<true, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane_kernel<true, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
         }
         else
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane_kernel<false, true, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane_kernel<false, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_element_lane_kernel<false, false, LAST_COPY>), grid, block, 0, st, A, Sep4, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane_kernel<false, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
         }
     }
 
-    // kernel 12: four subdomains per wavefront, four wavefronts per workgroup
-    template <bool LAST_COPY>
+    // kernel 12 (and 13 at n_basis 5): four subdomains per wavefront, four wavefronts per workgroup
+    template <bool LAST_COPY, typename... Grids>
     void launch_element_lane5(const DdhArgs<float> &A, const float *Sep5, int n_local, hipStream_t st, const float *fl, const float *cs,
-                              const float *sn)
+                              const float *sn, Grids... grids)
     {
         const dim3 grid((n_local + 15) / 16), block(256);
         if (A.x)
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane5_kernel<true, true, LAST_COPY>), grid, block, 0, st, A, Sep5, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane5_kernel<true, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep5, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_element_lane5_kernel<true, false, LAST_COPY>), grid, block, 0, st, A, Sep5, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane5_kernel<true, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep5, fl, cs, sn, grids...);
         }
         else
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane5_kernel<false, true, LAST_COPY>), grid, block, 0, st, A, Sep5, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane5_kernel<false, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep5, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_element_lane5_kernel<false, false, LAST_COPY>), grid, block, 0, st, A, Sep5, fl, cs, sn);
+                hipLaunchKernelGGL((ddh_element_lane5_kernel<false, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep5, fl, cs, sn, grids...);
         }
     }
 
@@ -2815,12 +2986,12 @@ namespace
 
     // The plan's kernel for one launch.  grids: nothing (one time grid, fl / cs / sn are the descriptor's tables) or the plan's
     // TimeGrids (fl / cs / sn are then the concatenated per-grid tables); the kernels that hold several subdomains per
-    // wavefront exist for one grid only.
+    // wavefront exist for one grid only, but for kernel 13, whose wavefronts march once per grid among their rows.
     template <typename Real, typename... Grids>
     int launch_local_solves(const cuddh_ddh_plan *plan, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl,
                             const Real *cs, const Real *sn, Grids... grids)
     {
-        constexpr bool rk2_one_grid = sizeof...(Grids) == 0; // kernels 6, 7, 12 and the element-lane form of 5 exist in this form alone
+        constexpr bool rk2_one_grid = sizeof...(Grids) == 0; // kernels 6, 7, 12 and the element-lane form of 5 are launched in this form alone
         constexpr bool rk4 = scheme_of<Grids...> == 1;
         const cuddh_ddh_desc &d = plan->d;
         const dim3 grid((n_local + 3) / 4), block(256); // the wavefront kernels: four wavefronts per workgroup
@@ -2912,6 +3083,29 @@ namespace
                     launch_element_lane5<true>(A, plan->Sep4, n_local, st, fl, cs, sn);
                 else
                     launch_element_lane5<false>(A, plan->Sep4, n_local, st, fl, cs, sn);
+                break;
+            }
+            else
+                return static_cast<int>(hipErrorInvalidValue);
+        case 13: // the element-lane kernels with four subdomains per wavefront, with or without time grids; RK2 only
+            if constexpr (f32 && !rk4)
+            {
+                if (!plan->Sep4) // plan_create ties kernel 13 to fp32 and its tables
+                    return static_cast<int>(hipErrorInvalidValue);
+                if (d.nb == 4)
+                {
+                    if (plan->last_copy)
+                        launch_element_lane<true>(A, plan->Sep4, n_local, st, fl, cs, sn, grids...);
+                    else
+                        launch_element_lane<false>(A, plan->Sep4, n_local, st, fl, cs, sn, grids...);
+                }
+                else
+                {
+                    if (plan->last_copy)
+                        launch_element_lane5<true>(A, plan->Sep4, n_local, st, fl, cs, sn, grids...);
+                    else
+                        launch_element_lane5<false>(A, plan->Sep4, n_local, st, fl, cs, sn, grids...);
+                }
                 break;
             }
             else
@@ -3044,7 +3238,7 @@ extern "C"
     int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **out, const cuddh_ddh_desc *desc, int is_f64, int kernel)
     {
         *out = nullptr;
-        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || desc->nel1d > 16 || kernel < 0 || (kernel > 8 && kernel != 11 && kernel != 12))
+        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || desc->nel1d > 16 || kernel < 0 || (kernel > 8 && kernel != 11 && kernel != 12 && kernel != 13))
             return static_cast<int>(hipErrorInvalidValue);
         const int nodes = desc->nb * desc->nb * desc->nel1d * desc->nel1d;
         if (nodes > 1024) // one thread per element node in kernel 1
@@ -3061,7 +3255,8 @@ extern "C"
         const bool wave8_shape = (desc->nb == 8 && desc->nel1d == 2);
         const bool lane8_shape = (desc->nb == 4 && desc->nel1d == 8);
         const bool lane5_shape = (desc->nb == 5 && desc->nel1d == 4);
-        if ((kernel == 11 && (!lane8_shape || is_f64)) || (kernel == 12 && (!lane5_shape || is_f64)) || (kernel >= 2 && kernel <= 5 && !wave_shape) || ((kernel == 6 || kernel == 7) && !wave8_shape) || (kernel == 7 && is_f64) ||
+        if ((kernel == 11 && (!lane8_shape || is_f64)) || (kernel == 12 && (!lane5_shape || is_f64)) ||
+            (kernel == 13 && ((!wave_shape && !lane5_shape) || is_f64)) || (kernel >= 2 && kernel <= 5 && !wave_shape) || ((kernel == 6 || kernel == 7) && !wave8_shape) || (kernel == 7 && is_f64) ||
             (kernel == 8 && (!wave_shape || !is_f64)))
         {
             delete p;
@@ -3127,7 +3322,8 @@ extern "C"
         // kernel 12 (n_basis 5, 4x4 elements, one per lane) needs fp32, the element order ex + 4 ey, no trace dof on an
         // element-interior node and the rectangles of the element-lane form.  On request a plan that fails one of these is
         // refused; auto takes it from ELEMENT_LANE5_MIN_DOMAINS subdomains on when all hold, and kernel 1 otherwise
-        if (lane5_shape && !is_f64 && (kernel == 12 || (kernel == 0 && desc->n_domains >= ELEMENT_LANE5_MIN_DOMAINS)))
+        // (kernel 13 at this shape: kernel 12's conditions, on request only)
+        if (lane5_shape && !is_f64 && (kernel == 12 || kernel == 13 || (kernel == 0 && desc->n_domains >= ELEMENT_LANE5_MIN_DOMAINS)))
         {
             int bad = 1;
             int e = run_structure_check<5, 4>(desc, &bad);
@@ -3146,14 +3342,40 @@ extern "C"
                 return e ? e : qualifies;
             }
             if (qualifies == 0)
-                p->kernel = 12;
-            else if (kernel == 12)
+                p->kernel = kernel == 13 ? 13 : 12;
+            else if (kernel == 12 || kernel == 13)
             {
                 cuddh_hip_ddh_plan_destroy(p);
                 return static_cast<int>(hipErrorInvalidValue);
             }
         }
-        if (wave_shape && kernel != 1)
+        // kernel 13 at n_basis 4 (on request only) needs what kernel 5's element-lane form needs: fp32, the element order
+        // ex + 4 ey, one metric for all elements, no trace dof on an element-interior node, the rectangles of the tables
+        if (wave_shape && kernel == 13)
+        {
+            int bad = 1;
+            int e = run_structure_check<4, 4>(desc, &bad);
+            int qualifies = -1; // 0 yes, -1 no, > 0 a HIP error
+            if (!e && !bad)
+                qualifies = check_uniform_geometry<float>(*desc, 16);
+            if (!e && qualifies == 0)
+            {
+                e = device_flag_check(&bad, [&](int *flag)
+                                      { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(desc->n_domains), dim3(256), 0, nullptr,
+                                                           desc->n_domains, 4, 16, 256, desc->s_fdof, desc->sI, flag); });
+                if (!e && bad)
+                    qualifies = -1;
+            }
+            if (!e && qualifies == 0)
+                qualifies = build_element_lane_tables<4>(p);
+            if (e || qualifies != 0)
+            {
+                cuddh_hip_ddh_plan_destroy(p);
+                return e ? e : (qualifies > 0 ? qualifies : static_cast<int>(hipErrorInvalidValue));
+            }
+            p->kernel = 13;
+        }
+        if (wave_shape && kernel != 1 && kernel != 13)
         {
             int bad = 1;
             const int e = run_structure_check<4, 4>(desc, &bad);
@@ -3352,7 +3574,8 @@ extern "C"
         if (!plan || n_grids < 1 || !h_nt || !h_dt || !filter || !cs || !sn || !d_grid_of)
             return static_cast<int>(hipErrorInvalidValue);
         // the element-lane forms on request have one grid; so have kernels 6 and 7, which hold two subdomains per wavefront,
-        // and kernel 12, which holds four: chosen by auto they give way to kernel 1, requested they are refused.  The label-built plans' kernels 9 and 10 hold
+        // and kernel 12, which holds four: chosen by auto they give way to kernel 1, requested they are refused.  Kernel 13 holds four
+        // as well and marches once per grid among them (GroupedRows): it takes the grids.  The label-built plans' kernels 9 and 10 hold
         // one subdomain per wavefront / workgroup and take the grids as they are.
         if (plan->sweep_form >= 2)
             return static_cast<int>(hipErrorInvalidValue);
@@ -3470,7 +3693,7 @@ extern "C"
 
     int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last)
     {
-        if (!plan || (plan->kernel != 11 && plan->kernel != 12))
+        if (!plan || (plan->kernel != 11 && plan->kernel != 12 && plan->kernel != 13))
             return static_cast<int>(hipErrorInvalidValue);
         plan->last_copy = last ? 1 : 0;
         return 0;

@@ -372,8 +372,20 @@ typedef struct cuddh_ddh_plan cuddh_ddh_plan;
  *             row.  Needs what 11 needs (rectangles, the element order ex + 4 ey, no trace dof on an element-interior node;
  *             verified here).  One time grid and RK2 only.  Under auto a qualifying plan takes it from the subdomain count
  *             at which it measured faster than kernel 1 (ELEMENT_LANE5_MIN_DOMAINS in kernels/ddh.hip), kernel 1 below.
+ *         13 = the element-lane local solves with four 4x4-element subdomains per wavefront that accept per-subdomain time
+ *             grids (fp32, nel1d == 4; on request only, never picked by auto).  nb == 4: needs what kernel 5's element-lane
+ *             form needs (the element order ex + 4 ey, one metric for all elements, no trace dof on an element-interior
+ *             node, rectangles); nb == 5: what 12 needs; anything else is hipErrorInvalidValue.  Without time grids it
+ *             launches the code of kernel 5's element-lane form (cuddh_hip_ddh_plan_set_sweep_form(2)), respectively of
+ *             kernel 12: the same bits.  After cuddh_hip_ddh_plan_set_time_grids a wavefront marches once per distinct
+ *             grid among its (up to) four subdomains: in a pass the rows on the pass's grid load, march and publish, the
+ *             others repeat the pass's first subdomain and publish nothing.  A wavefront whose rows hold k grids costs the
+ *             sum of those k marches; a full-range apply lists the subdomains by step count, so at most n_grids - 1 of its
+ *             wavefronts hold more than one grid, while ranges and caller lists run in the caller's order and pay for
+ *             every grid a group of four holds.  RK2 only; cuddh_hip_ddh_plan_set_sweep_form(2 | 3) is refused and
+ *             cuddh_hip_ddh_plan_sweep_form is 0 (it is not kernel 5); cuddh_hip_ddh_plan_set_owner_rule applies.
  * Subdomains hold nb^2 nel1d^2 <= 1024 element nodes.  Kernel 1 runs every such shape (one thread per element node);
- * kernels 2-8, 11 and 12 are refused with hipErrorInvalidValue on any shape but their own. */
+ * kernels 2-8 and 11-13 are refused with hipErrorInvalidValue on any shape but their own. */
 int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int is_f64, int kernel);
 /* Plan for subdomains of ANY element connectivity (subdomains given by element labels; desc->nel1d is ignored and
  * should be 0).  mx_elems: elements per subdomain at most, the third extent of desc->sI and the stride of desc->G;
@@ -390,7 +402,7 @@ int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc,
  * plans unchanged. */
 int cuddh_hip_ddh_plan_create_general(cuddh_ddh_plan **plan, const cuddh_ddh_desc *desc, int mx_elems, int is_f64, int kernel);
 int cuddh_hip_ddh_plan_destroy(cuddh_ddh_plan *plan);
-/* which kernel the plan resolved to (1..12) */
+/* which kernel the plan resolved to (1..13) */
 int cuddh_hip_ddh_plan_kernel(const cuddh_ddh_plan *plan);
 /* Numbering of the forcing x and the solution y of the NEXT apply calls: d_gI (mx_dof, n_domains) DEVICE replaces desc.gI and
  * g_ndof replaces desc.g_ndof for x and y (NULL restores the descriptor's).  With the identity numbering
@@ -421,12 +433,12 @@ int cuddh_hip_ddh_plan_set_wh_iters(cuddh_ddh_plan *plan, int wh_iters);
  * every plan.  cuddh_hip_ddh_plan_sweep_form returns the form in effect (1, 2 or 3), 0 for a plan that is not kernel 5. */
 int cuddh_hip_ddh_plan_set_sweep_form(cuddh_ddh_plan *plan, int form);
 int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan);
-/* The owner rule of kernels 11 and 12, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
+/* The owner rule of kernels 11, 12 and 13, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
  * smallest element-node index publishes (last == 0, the default) or the one with the largest (last != 0).  The copies are
  * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with
- * hipErrorInvalidValue on a plan that is neither kernel 11 nor kernel 12. */
+ * hipErrorInvalidValue on a plan that is none of kernels 11, 12 and 13. */
 int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last);
-/* The table of the element-lane kernels (5 in the element-lane form, 11 and 12) alone, computed on the host in double from HOST
+/* The table of the element-lane kernels (5 in the element-lane form, 11, 12 and 13) alone, computed on the host in double from HOST
  * arrays (no device is touched): h_D (nb, nb) the differentiation matrix, h_G (3, nb, nb) the metric tensor (gx, gy, gz) of one
  * element, nb 4 or 5.  h_out receives 5 nb^2 floats [Bx(k,j) at k + nb j | By(l,j) at l + nb j | Dg(k,l) at k + nb l | W | 1 / W]
  * with  S w = W (Dg w + sum_{j != k} Bx(k,j) w(j,l) + sum_{j != l} By(l,j) w(k,j))  for the element's stiffness matrix S, and
@@ -452,6 +464,7 @@ int cuddh_element_lane_tables(int nb, const float *h_D, const float *h_G, float 
  * its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan that auto resolved to kernel 6, 7 or 12 becomes kernel 1;
  * a plan created with kernel 6, 7 or 12 on request and one with sweep form 2 or 3 set are
  * refused with hipErrorInvalidValue, as are a grid with nt < 1 or dt <= 0 and an entry of d_grid_of out of range.
+ * Kernel 13 (on request) is the exception among them: four subdomains per wavefront, one march per distinct grid among them.
  * An apply over the whole range [0, n_domains) of such a plan runs the subdomains in the order of their step counts,
  * longest first and by index among equals (a list the plan owns), so that the short solves fill the device behind the
  * long ones; sub-ranges and caller lists run in the caller's order.  A subdomain's result depends on nothing else in the
@@ -471,7 +484,7 @@ int cuddh_hip_ddh_plan_time_grids(const cuddh_ddh_plan *plan);
  * RK4 forms exist of kernels 1, 2, 5 (matrix form), 8, 9 and 10 (instantiations of their own; an RK2 plan launches the code it did
  * before).  Like cuddh_hip_ddh_plan_set_time_grids this moves an auto choice and never a request: a plan that auto resolved
  * to kernel 3 becomes kernel 2, one that resolved to 6, 7, 11 or 12 becomes kernel 1, a kernel-5 plan takes the matrix form
- * whatever its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan created with kernel 3, 4, 6, 7, 11 or 12 on
+ * whatever its size and refuses cuddh_hip_ddh_plan_set_sweep_form(2 | 3); a plan created with kernel 3, 4, 6, 7, 11, 12 or 13 on
  * request and one with sweep form 2 or 3 set are refused with hipErrorInvalidValue and stay
  * RK2 plans; a general plan keeps its kernel, 9 or 10.  No launch of an RK4 plan ever runs RK2 code: a kernel without an RK4 form returns hipErrorInvalidValue.
  * cuddh_hip_ddh_plan_integrator returns the scheme in effect. */
