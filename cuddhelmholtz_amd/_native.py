@@ -184,6 +184,8 @@ _sig("cuddh_hip_ddh_plan_set_wh_iters", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_set_wave_priority", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_set_sweep_form", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_sweep_form", ci, vp)
+_sig("cuddh_hip_ddh_plan_set_chain_order", ci, vp, ci)
+_sig("cuddh_hip_ddh_plan_chain_order", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_owner_rule", ci, vp, ci)
 _sig("cuddh_element_lane_tables", ci, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_set_time_grids", ci, vp, ci, vp, vp, vp, vp, vp, vp)
@@ -273,6 +275,8 @@ _sig("cuddh_ddh_set_wh_iters", ci, vp, ci)
 _sig("cuddh_ddh_set_wave_priority", ci, vp, ci)
 _sig("cuddh_ddh_set_sweep_form", ci, vp, ci)
 _sig("cuddh_ddh_sweep_form", ci, vp)
+_sig("cuddh_ddh_set_chain_order", ci, vp, ci)
+_sig("cuddh_ddh_chain_order", ci, vp)
 _sig("cuddh_ddh_set_owner_rule", ci, vp, ci)
 
 

@@ -625,6 +625,20 @@ class DDH:
             N.check_capi(form, "DDH.sweep_form")
         return form
 
+    def set_chain_order(self, order: int = 0):
+        """The summation order of the element-lane form's in-lane products, for every launch of this plan: 0 auto (paired where auto
+        chose the form, pinned where set_sweep_form forced it), 1 pinned (the node-by-node loop's chains, bit for bit), 2 paired
+        (7 packed instructions per register pair; the last bits differ).  2 is refused where the plan cannot take it
+        (cuddh_hip_ddh_plan_set_chain_order)."""
+        N.check_capi(lib.cuddh_ddh_set_chain_order(self._h, int(order)), "DDH.set_chain_order")
+
+    def chain_order(self) -> int:
+        """The order in effect: 1 pinned, 2 paired; 0 where the element-lane form is not in effect."""
+        order = lib.cuddh_ddh_chain_order(self._h)
+        if order < 0:
+            N.check_capi(order, "DDH.chain_order")
+        return order
+
     def set_owner_rule(self, last: bool):
         """Kernels 11, 12 and 13: the last copy of every node that elements share publishes instead of the first (a check: same results).
         Refused on any other kernel (cuddh_hip_ddh_plan_set_owner_rule)."""

@@ -132,6 +132,12 @@ namespace cuddh
             /// cannot take throws).  sweep_form() returns the form in effect.
             void set_sweep_form(int form) const;
             int sweep_form() const;
+            /// The summation order of the element-lane form's in-lane products: 0 auto, 1 pinned (the chains of the node-by-node loop, bit for bit),
+            /// 2 paired (both halves of a register pair meet every term at the same place: 7 packed instructions per pair instead of 8.9;
+            /// cuddh_hip_ddh_plan_set_chain_order; an order the plan cannot take throws).  Auto is paired where auto chose the element-lane form
+            /// and pinned where set_sweep_form forced it.  chain_order() returns the order in effect, 0 where that form is not.
+            void set_chain_order(int order) const;
+            int chain_order() const;
             /// The owner rule of kernels 11, 12 and 13: which copy of a node shared by 2 or 4 elements publishes (false: the first, the default;
             /// true: the last).  A check that the copies are bitwise equal (cuddh_hip_ddh_plan_set_owner_rule); other kernels throw.
             void set_last_copy_publishes(bool last) const;

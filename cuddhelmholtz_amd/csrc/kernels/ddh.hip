@@ -69,6 +69,7 @@ struct cuddh_ddh_plan
                            // kernel 12: the same table with 5 in place of 4
     int last_copy = 0; // kernels 11, 12 and 13: the last copy of a shared node publishes, not the first (cuddh_hip_ddh_plan_set_owner_rule)
     int sweep_form = 0; // kernel 5: 0 auto, 1 matrix form, 2 element-lane form, 3 the same with the other owner rule (cuddh_hip_ddh_plan_set_sweep_form)
+    int chain_order = 0; // kernel 5's element-lane form: 0 auto, 1 pinned chains, 2 paired chains (cuddh_hip_ddh_plan_set_chain_order)
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
     int *csr_off = nullptr, *csr_src = nullptr;
@@ -1522,7 +1523,12 @@ namespace
     // recompute the wavefront's first subdomain and publish nothing.
     // The time loop runs on register pairs (below, "the packed form"): two nodes per v_pk_fma_f32, 262 vector instructions
     // per wavefront-step in the action form where the node-by-node loop issued 440 (264 with LAST_COPY, 273 / 272 with x against
-    // 456), bitwise the same results (profiles/r16, profiles/r17).
+    // 456), bitwise the same results (profiles/r16, profiles/r17).  PAIRED (chain order 2, cuddh_hip_ddh_plan_set_chain_order;
+    // what auto runs where auto chose this form) sums a node's seven terms in another order, in which both halves of a pair
+    // meet every term at the same place (element_lane_pair_product): 56 packed instructions per sweep instead of 71, all
+    // eight pairs keep dm, 228 per wavefront-step in the action form (244 with x), 164 VGPRs, no scratch; a new rounding,
+    // gated against the fp64 oracle and not against the pinned chains' bits (profiles/r22).  The one-grid kernel only: the
+    // TimeGrids instantiations (kernel 13) and a form forced with set_sweep_form keep the pinned chains.
     // Every form is compiled for three wavefronts per SIMD with no scratch: 168 VGPRs in the action form, 166 / 167 in
     // the form with x (rhs, postprocess: once per solve).  The assembly is 16 DPP instructions per sweep with no mask
     // multiplications in eta and one mask in xi (element_assemble_*_row_asm below): a shared node's sum is formed by one
@@ -1687,6 +1693,10 @@ namespace
     // the pairs that keep dm beside hm (wh_march_pairs' DM): as many as fit 168 vector registers, three wavefronts per SIMD,
     // with no scratch; which pairs does not matter to the count (profiles/r17/ddh_codegen_compare.txt)
     constexpr unsigned ELEMENT_LANE_DM_PAIRS(bool forced) { return forced ? 0x60u : 0x1fu; }
+    // the same for the paired chains (element_lane_pair_product<K, H, true>), chosen again: without the head temporaries all
+    // eight pairs of the action form keep dm at 164 registers and its three v_pk_add_f32 go; the form with x spills from
+    // three pairs on and keeps the two interior ones (profiles/r22/ddh_codegen_compare.txt lists the masks tried)
+    constexpr unsigned ELEMENT_LANE_PAIRED_DM_PAIRS(bool forced) { return forced ? 0x60u : 0xffu; }
 
     __device__ inline pair_t pk_fma(pair_t a, pair_t b, pair_t c) { return __builtin_elementwise_fma(a, b, c); }
     __device__ inline pair_t pk_fma(float a, pair_t b, pair_t c) { return __builtin_elementwise_fma(pair_t{a, a}, b, c); }
@@ -1724,6 +1734,12 @@ namespace
             asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(t) : "s"(c), "v"(w));
         return t;
     }
+    // t.x += c.x * w.y, t.y += c.y * w.x: the halves of w crossed, the coefficient pair straight (the compiler copies a high
+    // half into a pair of its own otherwise, as in pk_fmac_half)
+    __device__ inline void pk_fmac_crossed(pair_t &t, pair_t c, pair_t w)
+    {
+        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,0,1]" : "+v"(t) : "s"(c), "v"(w));
+    }
 
     // element_lane_products on pairs.  A node's chain is Dg w, then for j = 0..3 the x-term (j != k) and the y-term (j != l).
     // The x-term has one coefficient for both halves.  The y-term has the coefficient pair (By(l_a,j), By(l_b,j)) and
@@ -1740,11 +1756,50 @@ namespace
     //   k == 0, pairs (0, 3):  the half l = 0 rounds its x-term of j = 1 and the half l = 3 its y-term of j = 0: two
     //                          multiplications, then Dg w packed, then the x-term of j = 1 on the half l = 3 alone.
     // 71 instructions per sweep (64 + 2 for each of three pairs + 1).
-    template <int K, int H>
+    //
+    // PAIRED, the paired chains (chain order 2, cuddh_hip_ddh_plan_set_chain_order): another summation order of the same
+    // seven terms per node, one rounded product and six FMAs, in which both halves of a pair meet every term at the same
+    // place, so that every instruction is a packed one.  For pair P = K + 4 H, Q = K + 4 (1 - H), (l_a, l_b) = (H, 3 - H):
+    //   1. t = Dg[P] w[P], rounded in both halves (one v_pk_mul_f32; no head rules);
+    //   2. for j = 0, 1, 2, 3 in this order: the x-term Bx(K,j) w(j,l) if j != K, then the y-term (By(l_a,j), By(l_b,j)) w(K,j)
+    //      if j is neither l_a nor l_b (w(K,j) is a half of w[Q]);
+    //   3. last the two y-terms that read the pair itself, crossed: .x += By(l_a,l_b) w[P].y, .y += By(l_b,l_a) w[P].x, one
+    //      v_pk_fma_f32 with op_sel crossing the halves of w[P] (pk_fmac_crossed).
+    // The pinned chains take each of the two crossed terms at j = l_b (low half) and j = l_a (high half), which are different
+    // places; moving both to the end is what lets them share an instruction.  7 instructions per pair, 56 per sweep.  By is
+    // six aligned scalar pairs: (By(l_a,j), By(l_b,j)) for the two j outside {l_a, l_b} and the crossed pair, per H.
+    template <int K, int H, bool PAIRED = false>
     __device__ inline pair_t element_lane_pair_product(const pair_t (&w)[8], const pair_t (&Bx)[6], const float (&By)[16], const pair_t (&Dg)[8])
     {
         constexpr int la = H, lb = 3 - H, P = K + 4 * H, Q = K + 4 * (1 - H);
         pair_t t;
+        if constexpr (PAIRED)
+        {
+            t = Dg[P] * w[P];
+            // j = 0
+            if constexpr (K != 0)
+                pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
+            if constexpr (H == 1)
+                pk_fmac_half<el_half(0)>(t, pair_t{By[la + 0], By[lb + 0]}, w[Q]);
+            // j = 1
+            if constexpr (K != 1)
+                pk_fmac_scalar<bx_slot(K, 1) % 2>(t, Bx[bx_slot(K, 1) / 2], w[1 + 4 * H]);
+            if constexpr (H == 0)
+                pk_fmac_half<el_half(1)>(t, pair_t{By[la + 4], By[lb + 4]}, w[Q]);
+            // j = 2
+            if constexpr (K != 2)
+                pk_fmac_scalar<bx_slot(K, 2) % 2>(t, Bx[bx_slot(K, 2) / 2], w[2 + 4 * H]);
+            if constexpr (H == 0)
+                pk_fmac_half<el_half(2)>(t, pair_t{By[la + 8], By[lb + 8]}, w[Q]);
+            // j = 3
+            if constexpr (K != 3)
+                pk_fmac_scalar<bx_slot(K, 3) % 2>(t, Bx[bx_slot(K, 3) / 2], w[3 + 4 * H]);
+            if constexpr (H == 1)
+                pk_fmac_half<el_half(3)>(t, pair_t{By[la + 12], By[lb + 12]}, w[Q]);
+            // the pair's own halves, crossed
+            pk_fmac_crossed(t, pair_t{By[la + 4 * lb], By[lb + 4 * la]}, w[P]);
+            return t;
+        }
         // the head, through j = 0 (and for K == 0, H == 0 the x-term of j = 1)
         if constexpr (K != 0 && H == 1)
         {
@@ -1796,17 +1851,18 @@ namespace
         return t;
     }
 
+    template <bool PAIRED = false>
     __device__ inline void element_lane_products_packed(const pair_t (&w)[8], pair_t (&z)[8], const pair_t (&Bx)[6], const float (&By)[16],
                                                         const pair_t (&Dg)[8])
     {
-        z[0] = element_lane_pair_product<0, 0>(w, Bx, By, Dg);
-        z[1] = element_lane_pair_product<1, 0>(w, Bx, By, Dg);
-        z[2] = element_lane_pair_product<2, 0>(w, Bx, By, Dg);
-        z[3] = element_lane_pair_product<3, 0>(w, Bx, By, Dg);
-        z[4] = element_lane_pair_product<0, 1>(w, Bx, By, Dg);
-        z[5] = element_lane_pair_product<1, 1>(w, Bx, By, Dg);
-        z[6] = element_lane_pair_product<2, 1>(w, Bx, By, Dg);
-        z[7] = element_lane_pair_product<3, 1>(w, Bx, By, Dg);
+        z[0] = element_lane_pair_product<0, 0, PAIRED>(w, Bx, By, Dg);
+        z[1] = element_lane_pair_product<1, 0, PAIRED>(w, Bx, By, Dg);
+        z[2] = element_lane_pair_product<2, 0, PAIRED>(w, Bx, By, Dg);
+        z[3] = element_lane_pair_product<3, 0, PAIRED>(w, Bx, By, Dg);
+        z[4] = element_lane_pair_product<0, 1, PAIRED>(w, Bx, By, Dg);
+        z[5] = element_lane_pair_product<1, 1, PAIRED>(w, Bx, By, Dg);
+        z[6] = element_lane_pair_product<2, 1, PAIRED>(w, Bx, By, Dg);
+        z[7] = element_lane_pair_product<3, 1, PAIRED>(w, Bx, By, Dg);
     }
 
     // wh_march's RK2 loop in its LEAN forms on pairs: the same expressions with the fusions -ffp-contract=fast gives them
@@ -1881,12 +1937,14 @@ namespace
     }
 
     // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
-    template <bool FORCED, bool HOLD, bool LAST_COPY, typename... Grids>
+    // PAIRED: the paired chains in the sweep (element_lane_pair_product), the one-grid kernel only
+    template <bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, typename... Grids>
     __global__ void __launch_bounds__(256, 3) ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
                                                                      const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
     {
         constexpr bool GROUPED = sizeof...(Grids) > 0;
         static_assert(sizeof...(Grids) <= 1 && scheme_of<Grids...> == 0, "one grid, or TimeGrids; no RK4 form");
+        static_assert(!(PAIRED && sizeof...(Grids) > 0), "the paired chains are built for the one-grid kernel only");
         const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
         if (s_first >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
@@ -1965,7 +2023,7 @@ namespace
 
         auto sweep = [&](const pair_t(&w)[8], pair_t(&z)[8])
         {
-            element_lane_products_packed(w, z, Bx, By, Dg);
+            element_lane_products_packed<PAIRED>(w, z, Bx, By, Dg);
             // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa); the 32-bit halves of the pairs
             float hi[4] = {z[3].x, z[7].x, z[7].y, z[3].y}, lo[4] = {z[0].x, z[4].x, z[4].y, z[0].y}; // l = 0, 1, 2, 3
             element_assemble_xi_row_asm(hi, lo, mR);
@@ -1981,7 +2039,7 @@ namespace
                 z[k].x = dn[k];
             }
         };
-        wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, ELEMENT_LANE_DM_PAIRS(FORCED)>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
+        wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, PAIRED ? ELEMENT_LANE_PAIRED_DM_PAIRS(FORCED) : ELEMENT_LANE_DM_PAIRS(FORCED)>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
 
         // located a second time from a lane index the compiler cannot connect with the first: otherwise these values stay
         // in (or are spilled from) vector registers for the whole time loop, which runs at the limit of three wavefronts per SIMD
@@ -2898,7 +2956,20 @@ namespace
         return p->Sep4 && p->d.n_domains >= ELEMENT_LANE_MIN_DOMAINS ? 2 : 1;
     }
 
-    template <bool LAST_COPY, typename... Grids>
+    // the summation order of the element-lane form's in-lane products: 0 where that form is not in effect, 1 the pinned
+    // chains, 2 the paired chains (element_lane_pair_product).  Auto gives paired exactly where auto gave the form: a form
+    // forced with set_sweep_form(2 | 3) is what fixtures and diagnostics ask for, and its bits stay.  A property of the plan
+    // alone, like the form.
+    int effective_chain_order(const cuddh_ddh_plan *p)
+    {
+        if (effective_sweep_form(p) < 2)
+            return 0;
+        if (p->chain_order != 0)
+            return p->chain_order;
+        return p->sweep_form == 0 ? 2 : 1;
+    }
+
+    template <bool LAST_COPY, bool PAIRED = false, typename... Grids>
     void launch_element_lane(const DdhArgs<float> &A, const float *Sep4, int n_local, hipStream_t st, const float *fl, const float *cs,
                              const float *sn, Grids... grids)
     {
@@ -2906,16 +2977,16 @@ namespace
         if (A.x)
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane_kernel<true, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
+                hipLaunchKernelGGL((ddh_element_lane_kernel<true, true, LAST_COPY, PAIRED, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_element_lane_kernel<true, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
+                hipLaunchKernelGGL((ddh_element_lane_kernel<true, false, LAST_COPY, PAIRED, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
         }
         else
         {
             if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane_kernel<false, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
+                hipLaunchKernelGGL((ddh_element_lane_kernel<false, true, LAST_COPY, PAIRED, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
             else
-                hipLaunchKernelGGL((ddh_element_lane_kernel<false, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
+                hipLaunchKernelGGL((ddh_element_lane_kernel<false, false, LAST_COPY, PAIRED, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
         }
     }
 
@@ -3033,8 +3104,13 @@ namespace
             if constexpr (f32 && rk2_one_grid)
                 if (const int form = effective_sweep_form(plan); form >= 2)
                 {
-                    if (form == 3)
+                    const bool paired = effective_chain_order(plan) == 2;
+                    if (form == 3 && paired)
+                        launch_element_lane<true, true>(A, plan->Sep4, n_local, st, fl, cs, sn);
+                    else if (form == 3)
                         launch_element_lane<true>(A, plan->Sep4, n_local, st, fl, cs, sn);
+                    else if (paired)
+                        launch_element_lane<false, true>(A, plan->Sep4, n_local, st, fl, cs, sn);
                     else
                         launch_element_lane<false>(A, plan->Sep4, n_local, st, fl, cs, sn);
                     break;
@@ -3567,6 +3643,18 @@ extern "C"
     }
 
     int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan) { return plan ? effective_sweep_form(plan) : 0; }
+
+    int cuddh_hip_ddh_plan_set_chain_order(cuddh_ddh_plan *plan, int order)
+    {
+        if (!plan || order < 0 || order > 2)
+            return static_cast<int>(hipErrorInvalidValue);
+        if (order == 2 && (plan->kernel != 5 || !plan->Sep4 || plan->n_grids > 0 || plan->rk4))
+            return static_cast<int>(hipErrorInvalidValue);
+        plan->chain_order = order;
+        return 0;
+    }
+
+    int cuddh_hip_ddh_plan_chain_order(const cuddh_ddh_plan *plan) { return plan ? effective_chain_order(plan) : 0; }
 
     int cuddh_hip_ddh_plan_set_time_grids(cuddh_ddh_plan *plan, int n_grids, const int *h_nt, const double *h_dt, const void *filter,
                                           const void *cs, const void *sn, const int *d_grid_of)

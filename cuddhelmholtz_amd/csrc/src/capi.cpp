@@ -972,6 +972,27 @@ extern "C"
                 h->f32->internals().set_sweep_form(form);
         });
     }
+    int cuddh_ddh_set_chain_order(void *d, int order)
+    {
+        return guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            if (h->is64())
+                h->f64->internals().set_chain_order(order);
+            else
+                h->f32->internals().set_chain_order(order);
+        });
+    }
+    int cuddh_ddh_chain_order(void *d)
+    {
+        int order = 0;
+        const int err = guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            order = h->is64() ? h->f64->internals().chain_order() : h->f32->internals().chain_order();
+        });
+        return err ? -1 : order;
+    }
     int cuddh_ddh_set_owner_rule(void *d, int last)
     {
         return guarded([&]

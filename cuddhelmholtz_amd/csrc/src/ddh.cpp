@@ -727,6 +727,20 @@ namespace cuddh
         }
 
         template <typename Real>
+        void DDHCore<Real>::set_chain_order(int order) const
+        {
+            ensure_plan();
+            check_hip(cuddh_hip_ddh_plan_set_chain_order(plan, order), "DDH chain order");
+        }
+
+        template <typename Real>
+        int DDHCore<Real>::chain_order() const
+        {
+            ensure_plan();
+            return cuddh_hip_ddh_plan_chain_order(plan);
+        }
+
+        template <typename Real>
         void DDHCore<Real>::set_last_copy_publishes(bool last) const
         {
             ensure_plan();

@@ -206,6 +206,10 @@ int cuddh_ddh_set_wave_priority(void *ddh, int high);
  * the getter returns the form in effect (1, 2 or 3; 0 for a plan that is not kernel 5; -1 on error) */
 int cuddh_ddh_set_sweep_form(void *ddh, int form);
 int cuddh_ddh_sweep_form(void *ddh);
+/* the summation order of the element-lane form's in-lane products: 0 auto, 1 pinned, 2 paired (cuddh_hip_ddh_plan_set_chain_order);
+ * the getter returns the order in effect (1 or 2; 0 where the element-lane form is not in effect; -1 on error) */
+int cuddh_ddh_set_chain_order(void *ddh, int order);
+int cuddh_ddh_chain_order(void *ddh);
 /* the owner rule of kernels 11 and 12: last != 0 lets the last copy of every shared node publish instead of the first; same
  * results, a check (cuddh_hip_ddh_plan_set_owner_rule; an error on a plan that is neither kernel 11 nor kernel 12) */
 int cuddh_ddh_set_owner_rule(void *ddh, int last);

@@ -433,6 +433,20 @@ int cuddh_hip_ddh_plan_set_wh_iters(cuddh_ddh_plan *plan, int wh_iters);
  * every plan.  cuddh_hip_ddh_plan_sweep_form returns the form in effect (1, 2 or 3), 0 for a plan that is not kernel 5. */
 int cuddh_hip_ddh_plan_set_sweep_form(cuddh_ddh_plan *plan, int form);
 int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan);
+/* The summation order of the element-lane form's in-lane products (forms 2 and 3 of kernel 5), for every launch of the plan:
+ *   1 = pinned: every node runs the chain of the node-by-node loop, bit for bit (8 to 10 instructions per register pair);
+ *   2 = paired: t = Dg w rounded, then for j = 0..3 the x-term (j != k) and the y-term (j outside the pair's own two rows), last
+ *       the two y-terms that read the pair itself as one instruction with the halves crossed: both halves of a pair meet every
+ *       term at the same place, 7 packed instructions per pair.  The same terms and the same number of roundings per node in
+ *       another order: results differ from order 1 in the last bits;
+ *   0 = auto (the default): 2 where auto chose the element-lane form, 1 where cuddh_hip_ddh_plan_set_sweep_form(2 | 3) forced it.
+ * 2 is refused with hipErrorInvalidValue, the plan unchanged, on a plan that is not kernel 5, has no element-lane tables, or has
+ * time grids or the RK4 integrator (kernel 13 included); on a plan whose form is 1 it is accepted and takes effect when the form
+ * becomes 2 or 3 (a plan that takes time grids or RK4 afterwards runs the matrix form, where the order has no effect).  Other values
+ * than 0, 1, 2 are invalid.  cuddh_hip_ddh_plan_chain_order returns the order in effect (1 or 2),
+ * 0 where the element-lane form is not in effect. */
+int cuddh_hip_ddh_plan_set_chain_order(cuddh_ddh_plan *plan, int order);
+int cuddh_hip_ddh_plan_chain_order(const cuddh_ddh_plan *plan);
 /* The owner rule of kernels 11, 12 and 13, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
  * smallest element-node index publishes (last == 0, the default) or the one with the largest (last != 0).  The copies are
  * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with

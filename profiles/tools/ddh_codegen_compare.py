@@ -22,10 +22,16 @@ from cuddhelmholtz_amd import build as B  # noqa: E402
 RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, false>", "ddh_mfma_kernel<double>": "ddh_mfma_kernel<double, false, false>",
                        # ddh_block_kernel got its launch bound as a fourth template argument; 256 is the bound it had
                        **{f"ddh_block_kernel<{real}, {nb}, {csr}>": f"ddh_block_kernel<{real}, {nb}, {csr}, 256>"
-                          for real in ("float", "double") for nb in range(2, 11) for csr in ("false", "true")}}}
-# instantiations that are another one plus a template argument, per file: pattern removed from the demangled name gives the base.
+                          for real in ("float", "double") for nb in range(2, 11) for csr in ("false", "true")},
+                       # ddh_element_lane_kernel got PAIRED as a fourth template argument; false is the chains it had
+                       **{f"ddh_element_lane_kernel<{f}, {h}, {l}{g}>": f"ddh_element_lane_kernel<{f}, {h}, {l}, false{g}>"
+                          for f in ("false", "true") for h in ("false", "true") for l in ("false", "true") for g in ("", ", TimeGrids<float> ")}}}
+# instantiations that are another one plus (or with another) template argument, per file: (pattern, replacement) pairs applied to the
+# demangled name give the base.
 # A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
-DERIVED = {"ddh.hip": r", Rk4Scheme ?(?=>)|, TimeGrids<\w+> ?(?=>)"}
+DERIVED = {"ddh.hip": ((r", Rk4Scheme ?(?=>)|, TimeGrids<\w+> ?(?=>)", ""),
+                       # the paired chains (PAIRED = true, one grid only) against the pinned ones
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+), true>", r"\1, false>"))}
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
@@ -88,7 +94,9 @@ def main():
     valu = lambda c: sum(v for k, v in c.items() if k.startswith("v_"))  # noqa: E731
     for name, (m1, o1, l1) in new.items():  # a kernel the old file does not have: its registers and what its loops hold
         c1 = collections.Counter(l1)
-        base = re.sub(derived, "", name) if derived else name
+        base = name
+        for pattern, repl in derived or ():
+            base = re.sub(pattern, repl, base)
         if base != name and base in all_new:
             m0, _, l0 = all_new[base]
             c0 = collections.Counter(l0)
