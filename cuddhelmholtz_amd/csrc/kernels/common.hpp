@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "cuddh_hip.h"
 
 namespace cuddh_k
@@ -27,6 +29,22 @@ namespace cuddh_k
         if (g < 1)
             g = 1;
         return static_cast<int>(g);
+    }
+
+    /// Runtime flags become template arguments here and nowhere else (host code of the plan files): with_flags(f, a, b, ...)
+    /// calls f(A{}, B{}, ...) with std::true_type / std::false_type for each flag.
+    template <class F>
+    void with_flags(F &&f)
+    {
+        f();
+    }
+    template <class F, class... Rest>
+    void with_flags(F &&f, bool flag, Rest... rest)
+    {
+        if (flag)
+            with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+        else
+            with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
     }
 
     /// sum over the 64 lanes of a wavefront; every lane gets the result of lane 0's tree

@@ -38,26 +38,65 @@
 // publish, which keep a, m, gI and lambda in registers from one to the other
 // (on the shared pair it re-reads them and compiles to different code); its
 // CSR form (kernel 10) therefore has its own unique_y branch beside publish_dof's.
+//
+// Which kernel a plan runs is decided in ONE place, by host code without HIP (ddh_resolve.hpp: the kernel, the sweep form and
+// the chain order in effect, from the shape, the request, the facts plan creation established and the options set since).
+// resolve() calls it at the end of plan creation and of every setter whose argument enters it, and stores the outcome with
+// the launch it means: a function that names the kernel's instantiation for the plan's state (n_basis, time grids, RK4,
+// owner rule, chain order) and knows where its tables and trailing arguments come from.  apply() fills DdhArgs and calls that
+// function; nothing is decided per launch but what belongs to the call (with or without x, priority).  Every kernel template
+// is named in one hipLaunchKernelGGL (the run_* functions), runtime values become template arguments in with_flags and
+// with_n_basis alone, and a combination that has no instantiation leaves the stored function null, which resolve() refuses:
+// no launch of an RK4 plan can reach RK2 code.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
+#include "ddh_resolve.hpp"
 #include "element_lane_tables.hpp"
 
 using namespace cuddh_k;
+
+struct cuddh_ddh_plan;
+
+namespace
+{
+    template <typename Real>
+    struct DdhArgs;
+
+    // What resolve() stores for apply(): the function that launches the plan's kernel (the one for the plan's precision is set)
+    // and the launch geometry, which depends on the plan alone.
+    template <typename Real>
+    using DdhRun = void (*)(const cuddh_ddh_plan *, const DdhArgs<Real> &, int n_local, hipStream_t);
+    struct DdhLaunch
+    {
+        DdhRun<float> run32 = nullptr;
+        DdhRun<double> run64 = nullptr;
+        int per_group = 4;    // subdomains per workgroup: 4 (a wavefront each), 8 (kernels 6, 7), 16 (four per wavefront), 1 (kernels 1, 10)
+        unsigned block = 256; // threads per workgroup (kernels 1 and 10: one per element node)
+        size_t lds = 0;
+    };
+} // namespace
 
 struct cuddh_ddh_plan
 {
     cuddh_ddh_desc d;
     int is_f64;
-    int kernel; // which sweep:  1 ddh_block_kernel (up to 1024 element nodes);  2 / 3 / 4 ddh_wave_kernel<Real, 0 / 1 / 2> (plain; hand-folded DPP FMAs, fp32;
-                // 3 + MFMA for the in-lane contractions);  5 / 8 ddh_mfma_kernel<float / double> (dense element matrix on the matrix
-                // cores, uniform geometry);  6 / 7 ddh_wave8_kernel (nb == 8; 7 separable, fp32);  9 ddh_general_wave_kernel
-                // (nb == 4, <= 16 elements, CSR lists);  10 ddh_block_kernel with CSR lists;  11 ddh_element_lane8_kernel (nb == 4,
-                // 8x8 elements, fp32: one element per lane, one subdomain per wavefront);  12 ddh_element_lane5_kernel (nb == 5, 4x4
-                // elements, fp32: one element per lane, four subdomains per wavefront);  13 on request: the element-lane kernels
-                // with four subdomains per wavefront (nb == 4 or 5, 4x4 elements, fp32) that take per-subdomain time grids
+    // what the plan runs, filled by resolve() and read by apply() and the queries.  now.kernel names the sweep:
+    //  1 ddh_block_kernel (up to 1024 element nodes);  2 / 3 / 4 ddh_wave_kernel<Real, 0 / 1 / 2> (plain; hand-folded DPP FMAs, fp32;
+    //  3 + MFMA for the in-lane contractions);  5 / 8 ddh_mfma_kernel<float / double> (dense element matrix on the matrix
+    //  cores, uniform geometry; 5 in sweep form now.form, 2 and 3: ddh_element_lane_kernel in chain order now.order);
+    //  6 / 7 ddh_wave8_kernel (nb == 8; 7 separable, fp32);  9 ddh_general_wave_kernel
+    //  (nb == 4, <= 16 elements, CSR lists);  10 ddh_block_kernel with CSR lists;  11 ddh_element_lane8_kernel (nb == 4,
+    //  8x8 elements, fp32: one element per lane, one subdomain per wavefront);  12 ddh_element_lane5_kernel (nb == 5, 4x4
+    //  elements, fp32: one element per lane, four subdomains per wavefront);  13 on request: the element-lane kernels
+    //  with four subdomains per wavefront (nb == 4 or 5, 4x4 elements, fp32) that take per-subdomain time grids
+    DdhResolved now{0, 0, 0};
+    DdhLaunch launch;
+    unsigned facts = 0; // what plan creation established about the descriptor (ddh_fact bits, establish_facts)
+    int mx_elems = 0;   // general plans: elements per subdomain at most; 0: a structured plan
     int nodes;  // nb*nb*nel1d*nel1d (general plans: nb*nb*mx_elems)
     int wh_iters = 5; // WaveHoltz iterations per local solve (source/DDH.cpp:136); WH_ITERS_REFERENCE
     const int *gI_override = nullptr; // cuddh_hip_ddh_plan_set_vector_layout: x and y in another numbering than d.gI
@@ -2694,50 +2733,6 @@ namespace
         return launch_status();
     }
 
-    // kernel 1 (CSR = false) or 10 (CSR = true) for the plan's n_basis; false if there is no instantiation for it
-    // (grids: nothing, or the plan's TimeGrids, which selects the instantiations with per-subdomain time grids)
-    template <typename Real, bool CSR, typename... Grids>
-    bool launch_block(int nb, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl, const Real *cs, const Real *sn,
-                      Grids... grids)
-    {
-        const int T = A.nodes;
-        const size_t lds = (size_t)T * (4 * sizeof(Real) + 5 * sizeof(int));
-        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(n_local), dim3(T), lds, st, A, D, fl, cs, sn, grids...); };
-        if (T > 1024)
-            return false;
-        if (T > 256) // 52 KB of LDS in fp64 at T = 1024: within the 64 KB a workgroup gets without asking
-        {
-            if constexpr (!CSR)
-                switch (nb)
-                {
-                case 2: launch(ddh_block_kernel<Real, 2, false, 1024, Grids...>); return true;
-                case 3: launch(ddh_block_kernel<Real, 3, false, 1024, Grids...>); return true;
-                case 4: launch(ddh_block_kernel<Real, 4, false, 1024, Grids...>); return true;
-                case 5: launch(ddh_block_kernel<Real, 5, false, 1024, Grids...>); return true;
-                case 6: launch(ddh_block_kernel<Real, 6, false, 1024, Grids...>); return true;
-                case 7: launch(ddh_block_kernel<Real, 7, false, 1024, Grids...>); return true;
-                case 8: launch(ddh_block_kernel<Real, 8, false, 1024, Grids...>); return true;
-                case 9: launch(ddh_block_kernel<Real, 9, false, 1024, Grids...>); return true;
-                case 10: launch(ddh_block_kernel<Real, 10, false, 1024, Grids...>); return true;
-                }
-            return false;
-        }
-        switch (nb)
-        {
-        case 2: launch(ddh_block_kernel<Real, 2, CSR, 256, Grids...>); break;
-        case 3: launch(ddh_block_kernel<Real, 3, CSR, 256, Grids...>); break;
-        case 4: launch(ddh_block_kernel<Real, 4, CSR, 256, Grids...>); break;
-        case 5: launch(ddh_block_kernel<Real, 5, CSR, 256, Grids...>); break;
-        case 6: launch(ddh_block_kernel<Real, 6, CSR, 256, Grids...>); break;
-        case 7: launch(ddh_block_kernel<Real, 7, CSR, 256, Grids...>); break;
-        case 8: launch(ddh_block_kernel<Real, 8, CSR, 256, Grids...>); break;
-        case 9: launch(ddh_block_kernel<Real, 9, CSR, 256, Grids...>); break;
-        case 10: launch(ddh_block_kernel<Real, 10, CSR, 256, Grids...>); break;
-        default: return false;
-        }
-        return true;
-    }
-
     // Runs a check kernel that raises a device flag on the first violation it finds (launch(flag) starts it on the null
     // stream).  *bad = the flag, 1 if anything failed.  Returns a HIP error code.
     template <typename Launch>
@@ -2771,24 +2766,12 @@ namespace
         return e ? e : (bad ? -1 : 0);
     }
 
-    // Builds plan->Aop for kernel 5 (Real = float) or plan->Aop64 for kernel 8 (Real = double).  Returns 0 on success, -1 if
-    // the geometry is not uniform or an element-interior node is a trace dof (the plan then stays on kernel 3), > 0 on a HIP
-    // error.
+    // Builds plan->Aop for kernel 5 (Real = float) or plan->Aop64 for kernel 8 (Real = double), after establish_facts has
+    // found one metric for all elements and no trace dof on an element-interior node.  Returns 0 or a HIP error.
     template <typename Real>
     int build_dense_element_matrix(cuddh_ddh_plan *p)
     {
         const cuddh_ddh_desc &d = p->d;
-        if (const int c = check_uniform_geometry<Real>(d, 16))
-            return c;
-        {
-            int bad = 1;
-            const int e = device_flag_check(&bad, [&](int *flag)
-                                            { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(d.n_domains), dim3(256), 0, nullptr, d.n_domains,
-                                                                 4, 16, 256, d.s_fdof, d.sI, flag); });
-            if (e || bad)
-                return e ? e : -1;
-        }
-
         Real hD[16], hG[48];
         hipError_t e = hipMemcpy(hD, d.D, sizeof hD, hipMemcpyDeviceToHost);
         if (e == hipSuccess)
@@ -2875,8 +2858,6 @@ namespace
     int build_separable_tables(cuddh_ddh_plan *p)
     {
         double Ax[8][8], Ay[8][8], beta[8], gamma[8];
-        if (const int c = check_uniform_geometry<float>(p->d, 64))
-            return c;
         float hD[64], hG[192];
         if (const int c = download_element<8>(p->d, hD, hG))
             return c;
@@ -2915,280 +2896,314 @@ namespace
         return upload_table(&p->Sep4, hS);
     }
 
-    // kernel 5 plans with fewer subdomains than this stay on the matrix form under auto: the element-lane form puts four
-    // subdomains into a wavefront, so a small plan leaves SIMDs empty that the matrix form would use.  Measured on one MI355X
-    // (profiles/r08/ddh_rates_by_form.txt, three rounds per size): 1,024 subdomains 8.8 / 20.4 ms per action (matrix /
-    // element-lane), 4,096 19.7 / 20.5, 8,192 73.8 / 71.6, 16,384 70.6 / 68.1, 65,536 273.6 / 260.4.  8,192 is the smallest
-    // measured size at which the element-lane form won every round, not a crossover: nothing was measured between 4,096 and
-    // 8,192, and the 8,192 case is another problem (256 x 512 rectangular elements, nt 10,240).  The form belongs to the plan,
-    // so a small launch of a large plan (a few subdomains, the rim launch of a multi-GPU schedule) runs four subdomains per
-    // wavefront as well, at a size where this form measured slower on its own.
-    constexpr int ELEMENT_LANE_MIN_DOMAINS = 8192;
-    // kernel 12 against kernel 1 under auto (n_basis 5, block 4), the same rule: the smallest measured subdomain count at which
-    // kernel 12 won every round by more than the rounds differ.  One MI355X, ms per action, kernel 1 / kernel 12, three rounds
-    // each (profiles/r19/ddh_nb5_rates.txt): 64 subdomains 8.51 / 8.31 (1.02 x, rounds within 0.7 %), 256 8.58 / 8.28, 1,024
-    // 18.7 / 8.33 (2.2 x), 4,096 66.9 / 8.83 (7.6 x), 16,384 253.4 / 29.3 (8.6 x).  Nothing was measured below 64: there auto
-    // keeps kernel 1.  Up to 4,096 subdomains a launch of kernel 12 is one round of wavefronts and costs what one wavefront
-    // costs.
-    constexpr int ELEMENT_LANE5_MIN_DOMAINS = 64;
-
-    // Which kernels have an RK4 form (cuddh_hip_ddh_plan_set_integrator).  Kernels 1, 2, 5 in the matrix form and 8 do.  RK4
-    // keeps two registers more per value than RK2 (wh_march); a form of the others is built only where it compiles without
-    // scratch and at the occupancy of its RK2 form, and none does ("Runge-Kutta 4", the table from the code
-    // objects): kernel 11 and kernel 5's element-lane form, sixteen values per lane, spill 216 to 236 bytes in the form without
-    // x, and kernels 3 and 4 go from 86 / 90 to 98 / 99 vector registers, five wavefronts per SIMD to four.  Kernels 6 and 7
-    // have none by decision, and kernel 12 (25 values per lane, one wavefront per SIMD already in RK2) has none either; kernel 13 is the same two kernels.  The label-built plans' kernels 9 (wh_march around its LDS assembly, no scratch) and 10 (kernel 1's
-    // form with the plan's lists) have one.
-    constexpr bool has_rk4_form(int kernel) { return kernel == 1 || kernel == 2 || kernel == 5 || kernel == 8 || kernel == 9 || kernel == 10; }
-
-    // the form a kernel-5 plan's launches take: 1 matrix, 2 element-lane (3 on request only: the last copy publishes).  A property of the plan alone, never of a launch:
-    // differently partitioned launches of one plan are compared bitwise.
-    int effective_sweep_form(const cuddh_ddh_plan *p)
+    // ---------------------------------------------------------------- what plan creation establishes about the descriptor
+    // Runs the checks and table builders ddh_checks() lists for the plan's shape and request, in that order (four bits each,
+    // the first in the lowest), up to the first that does not hold, and sets the bit of each that held in p->facts.  A plan
+    // thus runs the device checks of the kernels it may take and no others.  Returns 0 or a HIP error.
+    template <typename Real, int NB, int NEL>
+    int establish_facts(cuddh_ddh_plan *p, unsigned checks)
     {
-        if (p->kernel != 5)
-            return 0;
-        if (p->n_grids > 0)
-            return 1; // the element-lane form holds four subdomains per wavefront: one time grid
-        if (p->rk4)
-            return 1; // no RK4 form of the element-lane kernel (has_rk4_form)
-        if (p->sweep_form != 0)
-            return p->sweep_form;
-        return p->Sep4 && p->d.n_domains >= ELEMENT_LANE_MIN_DOMAINS ? 2 : 1;
-    }
-
-    // the summation order of the element-lane form's in-lane products: 0 where that form is not in effect, 1 the pinned
-    // chains, 2 the paired chains (element_lane_pair_product).  Auto gives paired exactly where auto gave the form: a form
-    // forced with set_sweep_form(2 | 3) is what fixtures and diagnostics ask for, and its bits stay.  A property of the plan
-    // alone, like the form.
-    int effective_chain_order(const cuddh_ddh_plan *p)
-    {
-        if (effective_sweep_form(p) < 2)
-            return 0;
-        if (p->chain_order != 0)
-            return p->chain_order;
-        return p->sweep_form == 0 ? 2 : 1;
-    }
-
-    template <bool LAST_COPY, bool PAIRED = false, typename... Grids>
-    void launch_element_lane(const DdhArgs<float> &A, const float *Sep4, int n_local, hipStream_t st, const float *fl, const float *cs,
-                             const float *sn, Grids... grids)
-    {
-        const dim3 grid((n_local + 15) / 16), block(256); // four subdomains per wavefront, four wavefronts per workgroup
-        if (A.x)
+        constexpr int NN = NB * NB, ELEMS = NEL * NEL, NODES = NN * ELEMS;
+        const cuddh_ddh_desc &d = p->d;
+        for (; checks != 0; checks >>= 4)
         {
-            if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane_kernel<true, true, LAST_COPY, PAIRED, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
-            else
-                hipLaunchKernelGGL((ddh_element_lane_kernel<true, false, LAST_COPY, PAIRED, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
+            int held = -1, bad = 1; // held: 0 yes, -1 no, > 0 a HIP error
+            switch (checks & 15)
+            {
+            case DDH_STRUCTURE: // the NEL x NEL element layout the wavefront kernels assume
+                held = device_flag_check(&bad, [&](int *flag)
+                                         { hipLaunchKernelGGL((ddh_wave_check_kernel<NB, NEL>), dim3(d.n_domains), dim3(256), 0, nullptr, d.n_domains,
+                                                              d.s_dof, d.sI, flag); });
+                held = held ? held : -bad;
+                break;
+            case DDH_UNIFORM: held = check_uniform_geometry<Real>(d, NN, NODES); break;
+            case DDH_INTERIOR:
+                held = device_flag_check(&bad, [&](int *flag)
+                                         { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(d.n_domains), dim3(256), 0, nullptr, d.n_domains, NB,
+                                                              ELEMS, NODES, d.s_fdof, d.sI, flag); });
+                held = held ? held : -bad;
+                break;
+            case DDH_DENSE:
+                if constexpr (NB == 4 && NEL == 4)
+                    held = build_dense_element_matrix<Real>(p);
+                break;
+            case DDH_SEP8:
+                if constexpr (NB == 8)
+                    held = build_separable_tables(p);
+                break;
+            case DDH_LANE:
+                if constexpr (NB == 4 || NB == 5)
+                    held = build_element_lane_tables<NB>(p);
+                break;
+            }
+            if (held > 0)
+                return held;
+            if (held < 0)
+                break;
+            p->facts |= ddh_fact(checks & 15);
         }
+        return 0;
+    }
+
+    // the shapes with checks of their own (ddh_checks lists none for any other)
+    template <typename Real>
+    int establish_facts(cuddh_ddh_plan *p, unsigned checks)
+    {
+        const int nb = p->d.nb, nel = p->d.nel1d;
+        if (nb == 4 && nel == 4)
+            return establish_facts<Real, 4, 4>(p, checks);
+        if (nb == 8 && nel == 2)
+            return establish_facts<Real, 8, 2>(p, checks);
+        if (nb == 4 && nel == 8)
+            return establish_facts<Real, 4, 8>(p, checks);
+        if (nb == 5 && nel == 4)
+            return establish_facts<Real, 5, 4>(p, checks);
+        return checks == 0 ? 0 : static_cast<int>(hipErrorInvalidValue);
+    }
+
+    // ---------------------------------------------------------------- launches
+    // (runtime flags become template arguments in with_flags, common.hpp, and nowhere else)
+
+    // n_basis becomes a template argument here: the orders kernels 1 and 10 are built for are listed here and nowhere else
+    template <class F>
+    void with_n_basis(int nb, F &&f)
+    {
+        using std::integral_constant;
+        switch (nb)
+        {
+        case 2: return f(integral_constant<int, 2>{});
+        case 3: return f(integral_constant<int, 3>{});
+        case 4: return f(integral_constant<int, 4>{});
+        case 5: return f(integral_constant<int, 5>{});
+        case 6: return f(integral_constant<int, 6>{});
+        case 7: return f(integral_constant<int, 7>{});
+        case 8: return f(integral_constant<int, 8>{});
+        case 9: return f(integral_constant<int, 9>{});
+        case 10: return f(integral_constant<int, 10>{});
+        }
+    }
+
+    // The time tables and the trailing arguments of a plan's launches: f(filter, cs, sn, options...).  One time grid: the
+    // descriptor's tables and nothing; GRIDS: the plan's concatenated per-grid tables and its TimeGrids; RK4: the scheme's tag
+    // comes last.  The kernels are instantiated with the types of `options` as their trailing pack.
+    template <typename Real, bool GRIDS, bool RK4, class F>
+    void with_tables(const cuddh_ddh_plan *p, F &&f)
+    {
+        auto typed = [&](const void *fl, const void *cs, const void *sn, auto... options)
+        {
+            if constexpr (RK4)
+                f(static_cast<const Real *>(fl), static_cast<const Real *>(cs), static_cast<const Real *>(sn), options..., Rk4Scheme{});
+            else
+                f(static_cast<const Real *>(fl), static_cast<const Real *>(cs), static_cast<const Real *>(sn), options...);
+        };
+        if constexpr (GRIDS)
+            typed(p->grid_filter, p->grid_cs, p->grid_sn, TimeGrids<Real>{p->grid_of, static_cast<const DdhTimeGrid<Real> *>(p->grids)});
         else
-        {
-            if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane_kernel<false, true, LAST_COPY, PAIRED, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
-            else
-                hipLaunchKernelGGL((ddh_element_lane_kernel<false, false, LAST_COPY, PAIRED, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
-        }
+            typed(p->d.wh_filter, p->d.cs, p->d.sn);
     }
 
-    // kernel 12 (and 13 at n_basis 5): four subdomains per wavefront, four wavefronts per workgroup
-    template <bool LAST_COPY, typename... Grids>
-    void launch_element_lane5(const DdhArgs<float> &A, const float *Sep5, int n_local, hipStream_t st, const float *fl, const float *cs,
-                              const float *sn, Grids... grids)
+    dim3 launch_grid(const cuddh_ddh_plan *p, int n_local) { return dim3((n_local + p->launch.per_group - 1) / p->launch.per_group); }
+
+    // The plan kernels: each is launched from exactly one place, with the geometry resolve() stored.  What belongs to the call
+    // and not to the plan, sources or none (A.x) and the priority, is branched on here.
+    template <typename Real, int NB, bool CSR, int MAXT, bool GRIDS, bool RK4>
+    void run_block(const cuddh_ddh_plan *p, const DdhArgs<Real> &A, int n_local, hipStream_t st) // kernels 1 and 10
     {
-        const dim3 grid((n_local + 15) / 16), block(256);
-        if (A.x)
-        {
-            if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane5_kernel<true, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep5, fl, cs, sn, grids...);
-            else
-                hipLaunchKernelGGL((ddh_element_lane5_kernel<true, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep5, fl, cs, sn, grids...);
-        }
-        else
-        {
-            if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane5_kernel<false, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep5, fl, cs, sn, grids...);
-            else
-                hipLaunchKernelGGL((ddh_element_lane5_kernel<false, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep5, fl, cs, sn, grids...);
-        }
+        with_tables<Real, GRIDS, RK4>(p, [&](const Real *fl, const Real *cs, const Real *sn, auto... o)
+                                      { hipLaunchKernelGGL((ddh_block_kernel<Real, NB, CSR, MAXT, decltype(o)...>), launch_grid(p, n_local),
+                                                           dim3(p->launch.block), p->launch.lds, st, A, static_cast<const Real *>(p->d.D), fl, cs, sn, o...); });
     }
 
-    // kernel 11: one subdomain per wavefront, four wavefronts per workgroup
-    template <bool LAST_COPY, typename... Grids>
-    void launch_element_lane8(const DdhArgs<float> &A, const float *Sep4, dim3 grid, dim3 block, hipStream_t st, const float *fl,
-                              const float *cs, const float *sn, Grids... grids)
+    template <typename Real, int VAR, bool GRIDS, bool RK4>
+    void run_wave(const cuddh_ddh_plan *p, const DdhArgs<Real> &A, int n_local, hipStream_t st) // kernels 2, 3 and 4
     {
-        if (A.x)
-        {
-            if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane8_kernel<true, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
-            else
-                hipLaunchKernelGGL((ddh_element_lane8_kernel<true, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
-        }
-        else
-        {
-            if (A.prio)
-                hipLaunchKernelGGL((ddh_element_lane8_kernel<false, true, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
-            else
-                hipLaunchKernelGGL((ddh_element_lane8_kernel<false, false, LAST_COPY, Grids...>), grid, block, 0, st, A, Sep4, fl, cs, sn, grids...);
-        }
+        with_tables<Real, GRIDS, RK4>(p, [&](const Real *fl, const Real *cs, const Real *sn, auto... o)
+                                      { hipLaunchKernelGGL((ddh_wave_kernel<Real, VAR, decltype(o)...>), launch_grid(p, n_local), dim3(p->launch.block), 0,
+                                                           st, A, static_cast<const Real *>(p->d.D), fl, cs, sn, o...); });
     }
 
-    // kernels 5 and 8: the instantiation for this launch's two fixed properties (ddh_mfma_kernel)
-    template <typename Real, typename... Grids>
-    void launch_mfma(const DdhArgs<Real> &A, const void *Aop, dim3 grid, dim3 block, hipStream_t st, const Real *fl, const Real *cs,
-                     const Real *sn, Grids... grids)
+    template <typename Real, int VAR, bool GRIDS, bool RK4>
+    void run_general_wave(const cuddh_ddh_plan *p, const DdhArgs<Real> &A, int n_local, hipStream_t st) // kernel 9
     {
-        const Real *K = static_cast<const Real *>(Aop);
-        if (A.x)
-        {
-            if (A.prio)
-                hipLaunchKernelGGL((ddh_mfma_kernel<Real, true, true, Grids...>), grid, block, 0, st, A, K, fl, cs, sn, grids...);
-            else
-                hipLaunchKernelGGL((ddh_mfma_kernel<Real, true, false, Grids...>), grid, block, 0, st, A, K, fl, cs, sn, grids...);
-        }
-        else
-        {
-            if (A.prio)
-                hipLaunchKernelGGL((ddh_mfma_kernel<Real, false, true, Grids...>), grid, block, 0, st, A, K, fl, cs, sn, grids...);
-            else
-                hipLaunchKernelGGL((ddh_mfma_kernel<Real, false, false, Grids...>), grid, block, 0, st, A, K, fl, cs, sn, grids...);
-        }
+        with_tables<Real, GRIDS, RK4>(p, [&](const Real *fl, const Real *cs, const Real *sn, auto... o)
+                                      { hipLaunchKernelGGL((ddh_general_wave_kernel<Real, VAR, decltype(o)...>), launch_grid(p, n_local),
+                                                           dim3(p->launch.block), 0, st, A, static_cast<const Real *>(p->d.D), fl, cs, sn, o...); });
     }
 
-    // The plan's kernel for one launch.  grids: nothing (one time grid, fl / cs / sn are the descriptor's tables) or the plan's
-    // TimeGrids (fl / cs / sn are then the concatenated per-grid tables); the kernels that hold several subdomains per
-    // wavefront exist for one grid only, but for kernel 13, whose wavefronts march once per grid among their rows.
-    template <typename Real, typename... Grids>
-    int launch_local_solves(const cuddh_ddh_plan *plan, const DdhArgs<Real> &A, int n_local, hipStream_t st, const Real *D, const Real *fl,
-                            const Real *cs, const Real *sn, Grids... grids)
+    template <typename Real, bool ASM, bool SEP>
+    void run_wave8(const cuddh_ddh_plan *p, const DdhArgs<Real> &A, int n_local, hipStream_t st) // kernels 6 and 7: one grid, RK2
     {
-        constexpr bool rk2_one_grid = sizeof...(Grids) == 0; // kernels 6, 7, 12 and the element-lane form of 5 are launched in this form alone
-        constexpr bool rk4 = scheme_of<Grids...> == 1;
-        const cuddh_ddh_desc &d = plan->d;
-        const dim3 grid((n_local + 3) / 4), block(256); // the wavefront kernels: four wavefronts per workgroup
-        // kernels 3, 4, 7 and the folded-DPP form of 9 exist in fp32 only; fp64 always takes the plain form
-        constexpr bool f32 = sizeof(Real) == 4;
-        constexpr int v3 = f32 ? 1 : 0, v4 = f32 ? 2 : 0;
+        with_tables<Real, false, false>(p, [&](const Real *fl, const Real *cs, const Real *sn)
+                                        { hipLaunchKernelGGL((ddh_wave8_kernel<Real, ASM, SEP>), launch_grid(p, n_local), dim3(p->launch.block), 0, st, A,
+                                                             static_cast<const Real *>(p->d.D), fl, cs, sn, reinterpret_cast<const Real *>(p->Sep)); });
+    }
 
-        switch (plan->kernel)
+    template <typename Real, bool GRIDS, bool RK4>
+    void run_mfma(const cuddh_ddh_plan *p, const DdhArgs<Real> &A, int n_local, hipStream_t st) // kernel 5 (matrix form) and 8
+    {
+        const Real *K = sizeof(Real) == 4 ? reinterpret_cast<const Real *>(p->Aop) : reinterpret_cast<const Real *>(p->Aop64);
+        with_tables<Real, GRIDS, RK4>(p, [&](const Real *fl, const Real *cs, const Real *sn, auto... o)
+                                      { with_flags([&](auto FORCED, auto HOLD)
+                                                   { hipLaunchKernelGGL((ddh_mfma_kernel<Real, FORCED.value, HOLD.value, decltype(o)...>), launch_grid(p, n_local),
+                                                                        dim3(p->launch.block), 0, st, A, K, fl, cs, sn, o...); },
+                                                   A.x != nullptr, A.prio != 0); });
+    }
+
+    // kernel 5's element-lane form (LAST_COPY: form 3; PAIRED: chain order 2) and kernel 13 at n_basis 4
+    template <bool LAST_COPY, bool PAIRED, bool GRIDS>
+    void run_element_lane(const cuddh_ddh_plan *p, const DdhArgs<float> &A, int n_local, hipStream_t st)
+    {
+        with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
+                                         { with_flags([&](auto FORCED, auto HOLD)
+                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<FORCED.value, HOLD.value, LAST_COPY, PAIRED, decltype(o)...>),
+                                                                           launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
+                                                      A.x != nullptr, A.prio != 0); });
+    }
+
+    template <bool LAST_COPY, bool GRIDS>
+    void run_element_lane8(const cuddh_ddh_plan *p, const DdhArgs<float> &A, int n_local, hipStream_t st) // kernel 11
+    {
+        with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
+                                         { with_flags([&](auto FORCED, auto HOLD)
+                                                      { hipLaunchKernelGGL((ddh_element_lane8_kernel<FORCED.value, HOLD.value, LAST_COPY, decltype(o)...>),
+                                                                           launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
+                                                      A.x != nullptr, A.prio != 0); });
+    }
+
+    template <bool LAST_COPY, bool GRIDS>
+    void run_element_lane5(const cuddh_ddh_plan *p, const DdhArgs<float> &A, int n_local, hipStream_t st) // kernel 12, and 13 at n_basis 5
+    {
+        with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
+                                         { with_flags([&](auto FORCED, auto HOLD)
+                                                      { hipLaunchKernelGGL((ddh_element_lane5_kernel<FORCED.value, HOLD.value, LAST_COPY, decltype(o)...>),
+                                                                           launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
+                                                      A.x != nullptr, A.prio != 0); });
+    }
+
+    // The launch of kernel r.kernel in the plan's state.  Only combinations that are launched are instantiated: kernels 3, 4,
+    // 7 and the folded-DPP form of 9 in fp32 only (fp64 takes the plain form), 5 and the element-lane kernels in fp32 and 8 in
+    // fp64 only, no RK4 form of 3, 4, 11 and 13, and 6, 7, 12 and the element-lane form of 5 on one time grid with RK2 alone.
+    // ddh_resolve() never resolves to the others; if it did, L.run* would stay null and resolve() would refuse the plan.
+    template <typename Real, bool GRIDS, bool RK4>
+    void set_launch(const cuddh_ddh_plan *p, const DdhResolved &r, DdhLaunch &L)
+    {
+        constexpr bool f32 = sizeof(Real) == 4, plain = !GRIDS && !RK4;
+        DdhRun<Real> run = nullptr;
+        const bool last_copy = p->last_copy != 0;
+        switch (r.kernel)
         {
         case 1:
-            if (!launch_block<Real, false>(d.nb, A, n_local, st, D, fl, cs, sn, grids...))
-                return static_cast<int>(hipErrorInvalidValue);
+        case 10: // one workgroup per subdomain, one thread per element node; 52 KB of LDS in fp64 at 1024 nodes: within the 64 KB
+                 // a workgroup gets without asking
+            L.per_group = 1;
+            L.block = p->nodes;
+            L.lds = (size_t)p->nodes * (4 * sizeof(Real) + 5 * sizeof(int));
+            with_n_basis(p->d.nb, [&](auto NB)
+                         {
+                             if (p->nodes <= 256)
+                                 run = r.kernel == 10 ? run_block<Real, NB.value, true, 256, GRIDS, RK4> : run_block<Real, NB.value, false, 256, GRIDS, RK4>;
+                             else if (r.kernel == 1 && p->nodes <= 1024)
+                                 run = run_block<Real, NB.value, false, 1024, GRIDS, RK4>;
+                         });
             break;
-        case 10:
-            if (!launch_block<Real, true>(d.nb, A, n_local, st, D, fl, cs, sn, grids...))
-                return static_cast<int>(hipErrorInvalidValue);
-            break;
-        case 2: hipLaunchKernelGGL((ddh_wave_kernel<Real, 0, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
+        case 2: run = run_wave<Real, 0, GRIDS, RK4>; break;
         case 3:
-            if constexpr (!rk4)
-            {
-                hipLaunchKernelGGL((ddh_wave_kernel<Real, v3, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...);
-                break;
-            }
-            else
-                return static_cast<int>(hipErrorInvalidValue);
+            if constexpr (!RK4)
+                run = run_wave<Real, f32 ? 1 : 0, GRIDS, RK4>;
+            break;
         case 4:
-            if constexpr (!rk4)
-            {
-                hipLaunchKernelGGL((ddh_wave_kernel<Real, v4, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...);
-                break;
-            }
-            else
-                return static_cast<int>(hipErrorInvalidValue);
+            if constexpr (!RK4)
+                run = run_wave<Real, f32 ? 2 : 0, GRIDS, RK4>;
+            break;
         case 5:
-        case 8:
-            if ((plan->kernel == 5) != f32) // plan_create ties kernel 5 to fp32 (Aop) and kernel 8 to fp64 (Aop64)
-                return static_cast<int>(hipErrorInvalidValue);
-            if constexpr (f32 && rk2_one_grid)
-                if (const int form = effective_sweep_form(plan); form >= 2)
+            if constexpr (f32)
+            {
+                if (r.form < 2)
+                    run = run_mfma<float, GRIDS, RK4>;
+                else if constexpr (plain)
                 {
-                    const bool paired = effective_chain_order(plan) == 2;
-                    if (form == 3 && paired)
-                        launch_element_lane<true, true>(A, plan->Sep4, n_local, st, fl, cs, sn);
-                    else if (form == 3)
-                        launch_element_lane<true>(A, plan->Sep4, n_local, st, fl, cs, sn);
-                    else if (paired)
-                        launch_element_lane<false, true>(A, plan->Sep4, n_local, st, fl, cs, sn);
-                    else
-                        launch_element_lane<false>(A, plan->Sep4, n_local, st, fl, cs, sn);
-                    break;
+                    L.per_group = 16; // four subdomains per wavefront
+                    with_flags([&](auto LAST_COPY, auto PAIRED) { run = run_element_lane<LAST_COPY.value, PAIRED.value, false>; }, r.form == 3, r.order == 2);
                 }
-            launch_mfma(A, f32 ? static_cast<const void *>(plan->Aop) : static_cast<const void *>(plan->Aop64), grid, block, st, fl, cs, sn, grids...);
+            }
+            break;
+        case 8:
+            if constexpr (!f32)
+                run = run_mfma<double, GRIDS, RK4>;
             break;
         case 6:
         case 7:
-            if constexpr (rk2_one_grid)
+            if constexpr (plain)
             {
-                const dim3 grid8((n_local + 7) / 8); // two subdomains per wavefront
+                L.per_group = 8; // two subdomains per wavefront
                 if constexpr (f32)
-                {
-                    if (plan->kernel == 7)
-                        hipLaunchKernelGGL((ddh_wave8_kernel<float, true, true>), grid8, block, 0, st, A, D, fl, cs, sn, plan->Sep);
-                    else
-                        hipLaunchKernelGGL((ddh_wave8_kernel<float, true, false>), grid8, block, 0, st, A, D, fl, cs, sn, plan->Sep);
-                }
-                else
-                    hipLaunchKernelGGL((ddh_wave8_kernel<double, false, false>), grid8, block, 0, st, A, D, fl, cs, sn,
-                                       static_cast<const double *>(nullptr));
-                break;
+                    run = r.kernel == 7 ? run_wave8<float, true, true> : run_wave8<float, true, false>;
+                else if (r.kernel == 6)
+                    run = run_wave8<double, false, false>;
             }
-            else
-                return static_cast<int>(hipErrorInvalidValue);
-        case 9: hipLaunchKernelGGL((ddh_general_wave_kernel<Real, v3, Grids...>), grid, block, 0, st, A, D, fl, cs, sn, grids...); break;
+            break;
+        case 9: run = run_general_wave<Real, f32 ? 1 : 0, GRIDS, RK4>; break;
         case 11:
-            if constexpr (f32 && !rk4)
-            {
-                if (!plan->Sep4) // plan_create ties kernel 11 to fp32 and its tables
-                    return static_cast<int>(hipErrorInvalidValue);
-                if (plan->last_copy)
-                    launch_element_lane8<true>(A, plan->Sep4, grid, block, st, fl, cs, sn, grids...);
-                else
-                    launch_element_lane8<false>(A, plan->Sep4, grid, block, st, fl, cs, sn, grids...);
-                break;
-            }
-            else
-                return static_cast<int>(hipErrorInvalidValue);
+            if constexpr (f32 && !RK4)
+                with_flags([&](auto LAST_COPY) { run = run_element_lane8<LAST_COPY.value, GRIDS>; }, last_copy);
+            break;
         case 12:
-            if constexpr (f32 && rk2_one_grid)
+            if constexpr (f32 && plain)
             {
-                if (!plan->Sep4) // plan_create ties kernel 12 to fp32 and its tables
-                    return static_cast<int>(hipErrorInvalidValue);
-                if (plan->last_copy)
-                    launch_element_lane5<true>(A, plan->Sep4, n_local, st, fl, cs, sn);
-                else
-                    launch_element_lane5<false>(A, plan->Sep4, n_local, st, fl, cs, sn);
-                break;
+                L.per_group = 16;
+                with_flags([&](auto LAST_COPY) { run = run_element_lane5<LAST_COPY.value, false>; }, last_copy);
             }
-            else
-                return static_cast<int>(hipErrorInvalidValue);
+            break;
         case 13: // the element-lane kernels with four subdomains per wavefront, with or without time grids; RK2 only
-            if constexpr (f32 && !rk4)
+            if constexpr (f32 && !RK4)
             {
-                if (!plan->Sep4) // plan_create ties kernel 13 to fp32 and its tables
-                    return static_cast<int>(hipErrorInvalidValue);
-                if (d.nb == 4)
-                {
-                    if (plan->last_copy)
-                        launch_element_lane<true>(A, plan->Sep4, n_local, st, fl, cs, sn, grids...);
-                    else
-                        launch_element_lane<false>(A, plan->Sep4, n_local, st, fl, cs, sn, grids...);
-                }
-                else
-                {
-                    if (plan->last_copy)
-                        launch_element_lane5<true>(A, plan->Sep4, n_local, st, fl, cs, sn, grids...);
-                    else
-                        launch_element_lane5<false>(A, plan->Sep4, n_local, st, fl, cs, sn, grids...);
-                }
-                break;
+                L.per_group = 16;
+                with_flags(
+                    [&](auto LAST_COPY)
+                    {
+                        if (p->d.nb == 4)
+                            run = run_element_lane<LAST_COPY.value, false, GRIDS>;
+                        else
+                            run = run_element_lane5<LAST_COPY.value, GRIDS>;
+                    },
+                    last_copy);
             }
-            else
-                return static_cast<int>(hipErrorInvalidValue);
-        default: return static_cast<int>(hipErrorInvalidValue);
+            break;
         }
-        return launch_status();
+        if constexpr (f32)
+            L.run32 = run;
+        else
+            L.run64 = run;
+    }
+
+    // What the plan runs, from its facts and options as they stand (ddh_resolve) and the launch that goes with it.  `setting`:
+    // the option the calling setter has just stored (DdhSetting).  On refusal the record is left as it was.
+    int resolve(cuddh_ddh_plan *p, int setting = DDH_SET_NONE)
+    {
+        const DdhShape shape{p->d.nb, p->d.nel1d, p->d.n_domains, p->is_f64, p->mx_elems};
+        DdhResolved r;
+        if (ddh_resolve(shape, p->requested, p->facts, p->now.kernel, DdhOptions{p->n_grids > 0, p->rk4, p->sweep_form, p->chain_order}, setting, r))
+            return static_cast<int>(hipErrorInvalidValue);
+        DdhLaunch L;
+        with_flags([&](auto F64, auto GRIDS, auto RK4) { set_launch<std::conditional_t<F64.value, double, float>, GRIDS.value, RK4.value>(p, r, L); },
+                   p->is_f64 != 0, p->n_grids > 0, p->rk4 != 0);
+        if (!L.run32 && !L.run64) // a missing kernel is an error
+            return static_cast<int>(hipErrorInvalidValue);
+        p->now = r;
+        p->launch = L;
+        return 0;
+    }
+
+    // A setter: stores its option (store(plan)), resolves, and on refusal puts the plan back as it was.
+    template <class Store>
+    int set_and_resolve(cuddh_ddh_plan *p, int setting, Store store)
+    {
+        const cuddh_ddh_plan before = *p;
+        store(*p);
+        const int err = resolve(p, setting);
+        if (err)
+            *p = before;
+        return err;
     }
 
     template <typename Real>
@@ -3253,29 +3268,11 @@ namespace
         A.csr_src = plan->csr_src;
         A.unique_y = plan->gI_override ? 1 : 0;
 
-        const Real *D = static_cast<const Real *>(d.D);
-        if (plan->n_grids > 0) // every subdomain on its own grid: the plan's concatenated tables
-        {
-            const Real *fl = static_cast<const Real *>(plan->grid_filter), *cs = static_cast<const Real *>(plan->grid_cs),
-                       *sn = static_cast<const Real *>(plan->grid_sn);
-            const TimeGrids<Real> TG{plan->grid_of, static_cast<const DdhTimeGrid<Real> *>(plan->grids)};
-            if (plan->rk4)
-                return launch_local_solves(plan, A, n_local, st, D, fl, cs, sn, TG, Rk4Scheme{});
-            return launch_local_solves(plan, A, n_local, st, D, fl, cs, sn, TG);
-        }
-        if (plan->rk4)
-            return launch_local_solves(plan, A, n_local, st, D, static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs),
-                                       static_cast<const Real *>(d.sn), Rk4Scheme{});
-        return launch_local_solves(plan, A, n_local, st, D, static_cast<const Real *>(d.wh_filter), static_cast<const Real *>(d.cs),
-                                   static_cast<const Real *>(d.sn));
-    }
-    // do all subdomains have the structured NEL x NEL element layout the wave kernels assume?  *bad = 0 if so
-    template <int NB, int NEL>
-    int run_structure_check(const cuddh_ddh_desc *desc, int *bad)
-    {
-        return device_flag_check(bad, [&](int *flag)
-                                 { hipLaunchKernelGGL((ddh_wave_check_kernel<NB, NEL>), dim3(desc->n_domains), dim3(256), 0, nullptr,
-                                                      desc->n_domains, desc->s_dof, desc->sI, flag); });
+        if constexpr (sizeof(Real) == 4)
+            plan->launch.run32(plan, A, n_local, st);
+        else
+            plan->launch.run64(plan, A, n_local, st);
+        return launch_status();
     }
 } // namespace
 
@@ -3314,195 +3311,25 @@ extern "C"
     int cuddh_hip_ddh_plan_create(cuddh_ddh_plan **out, const cuddh_ddh_desc *desc, int is_f64, int kernel)
     {
         *out = nullptr;
-        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->nel1d < 1 || desc->nel1d > 16 || kernel < 0 || (kernel > 8 && kernel != 11 && kernel != 12 && kernel != 13))
+        if (!desc)
             return static_cast<int>(hipErrorInvalidValue);
-        const int nodes = desc->nb * desc->nb * desc->nel1d * desc->nel1d;
-        if (nodes > 1024) // one thread per element node in kernel 1
+        // the checks this shape and request call for; < 0: a shape no kernel takes, or a kernel requested on a shape not its own
+        const int checks = ddh_checks(DdhShape{desc->nb, desc->nel1d, desc->n_domains, is_f64 ? 1 : 0, 0}, kernel);
+        if (checks < 0)
             return static_cast<int>(hipErrorInvalidValue);
 
         cuddh_ddh_plan *p = new cuddh_ddh_plan;
         p->d = *desc;
         p->is_f64 = is_f64 ? 1 : 0;
-        p->nodes = nodes;
-        p->kernel = 1;
+        p->nodes = desc->nb * desc->nb * desc->nel1d * desc->nel1d;
         p->requested = kernel;
-
-        const bool wave_shape = (desc->nb == 4 && desc->nel1d == 4);
-        const bool wave8_shape = (desc->nb == 8 && desc->nel1d == 2);
-        const bool lane8_shape = (desc->nb == 4 && desc->nel1d == 8);
-        const bool lane5_shape = (desc->nb == 5 && desc->nel1d == 4);
-        if ((kernel == 11 && (!lane8_shape || is_f64)) || (kernel == 12 && (!lane5_shape || is_f64)) ||
-            (kernel == 13 && ((!wave_shape && !lane5_shape) || is_f64)) || (kernel >= 2 && kernel <= 5 && !wave_shape) || ((kernel == 6 || kernel == 7) && !wave8_shape) || (kernel == 7 && is_f64) ||
-            (kernel == 8 && (!wave_shape || !is_f64)))
+        int err = is_f64 ? establish_facts<double>(p, checks) : establish_facts<float>(p, checks);
+        if (!err)
+            err = resolve(p); // refused: a requested kernel one of whose checks did not hold
+        if (err)
         {
-            delete p;
-            return static_cast<int>(hipErrorInvalidValue);
-        }
-        if (wave8_shape && kernel != 1)
-        {
-            int bad = 1;
-            const int e = run_structure_check<8, 2>(desc, &bad);
-            if (e)
-            {
-                delete p;
-                return e;
-            }
-            if (!bad)
-                p->kernel = 6;
-            else if (kernel >= 6)
-            {
-                delete p;
-                return static_cast<int>(hipErrorInvalidValue);
-            }
-            // kernel 7 (one contraction per direction) needs fp32 and the rectangles of a uniform mesh
-            if (!bad && !is_f64 && (kernel == 0 || kernel == 7))
-            {
-                const int err7 = build_separable_tables(p);
-                if (err7 == 0)
-                    p->kernel = 7;
-                else if (kernel == 7)
-                {
-                    delete p;
-                    return err7 > 0 ? err7 : static_cast<int>(hipErrorInvalidValue);
-                }
-            }
-        }
-        // kernel 11 (8x8 elements, one per lane) needs fp32, the element order ex + 8 ey, no trace dof on an element-interior
-        // node and the rectangles of the element-lane form; a plan that fails one of these runs kernel 1
-        if (lane8_shape && !is_f64 && kernel != 1)
-        {
-            int bad = 1;
-            int e = run_structure_check<4, 8>(desc, &bad);
-            if (!e && !bad)
-                e = device_flag_check(&bad, [&](int *flag)
-                                      { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(desc->n_domains), dim3(256), 0, nullptr,
-                                                           desc->n_domains, 4, 64, 1024, desc->s_fdof, desc->sI, flag); });
-            int qualifies = -1; // 0 yes, -1 no, > 0 a HIP error
-            if (!e && !bad)
-                qualifies = check_uniform_geometry<float>(*desc, 16, 1024);
-            if (!e && qualifies == 0)
-                qualifies = build_element_lane_tables<4>(p);
-            if (e || qualifies > 0)
-            {
-                cuddh_hip_ddh_plan_destroy(p);
-                return e ? e : qualifies;
-            }
-            if (qualifies == 0)
-                p->kernel = 11;
-            else if (kernel == 11)
-            {
-                cuddh_hip_ddh_plan_destroy(p);
-                return static_cast<int>(hipErrorInvalidValue);
-            }
-        }
-        // kernel 12 (n_basis 5, 4x4 elements, one per lane) needs fp32, the element order ex + 4 ey, no trace dof on an
-        // element-interior node and the rectangles of the element-lane form.  On request a plan that fails one of these is
-        // refused; auto takes it from ELEMENT_LANE5_MIN_DOMAINS subdomains on when all hold, and kernel 1 otherwise
-        // (kernel 13 at this shape: kernel 12's conditions, on request only)
-        if (lane5_shape && !is_f64 && (kernel == 12 || kernel == 13 || (kernel == 0 && desc->n_domains >= ELEMENT_LANE5_MIN_DOMAINS)))
-        {
-            int bad = 1;
-            int e = run_structure_check<5, 4>(desc, &bad);
-            if (!e && !bad)
-                e = device_flag_check(&bad, [&](int *flag)
-                                      { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(desc->n_domains), dim3(256), 0, nullptr,
-                                                           desc->n_domains, 5, 16, 400, desc->s_fdof, desc->sI, flag); });
-            int qualifies = -1; // 0 yes, -1 no, > 0 a HIP error
-            if (!e && !bad)
-                qualifies = check_uniform_geometry<float>(*desc, 25, 400);
-            if (!e && qualifies == 0)
-                qualifies = build_element_lane_tables<5>(p);
-            if (e || qualifies > 0)
-            {
-                cuddh_hip_ddh_plan_destroy(p);
-                return e ? e : qualifies;
-            }
-            if (qualifies == 0)
-                p->kernel = kernel == 13 ? 13 : 12;
-            else if (kernel == 12 || kernel == 13)
-            {
-                cuddh_hip_ddh_plan_destroy(p);
-                return static_cast<int>(hipErrorInvalidValue);
-            }
-        }
-        // kernel 13 at n_basis 4 (on request only) needs what kernel 5's element-lane form needs: fp32, the element order
-        // ex + 4 ey, one metric for all elements, no trace dof on an element-interior node, the rectangles of the tables
-        if (wave_shape && kernel == 13)
-        {
-            int bad = 1;
-            int e = run_structure_check<4, 4>(desc, &bad);
-            int qualifies = -1; // 0 yes, -1 no, > 0 a HIP error
-            if (!e && !bad)
-                qualifies = check_uniform_geometry<float>(*desc, 16);
-            if (!e && qualifies == 0)
-            {
-                e = device_flag_check(&bad, [&](int *flag)
-                                      { hipLaunchKernelGGL(ddh_interior_check_kernel, dim3(desc->n_domains), dim3(256), 0, nullptr,
-                                                           desc->n_domains, 4, 16, 256, desc->s_fdof, desc->sI, flag); });
-                if (!e && bad)
-                    qualifies = -1;
-            }
-            if (!e && qualifies == 0)
-                qualifies = build_element_lane_tables<4>(p);
-            if (e || qualifies != 0)
-            {
-                cuddh_hip_ddh_plan_destroy(p);
-                return e ? e : (qualifies > 0 ? qualifies : static_cast<int>(hipErrorInvalidValue));
-            }
-            p->kernel = 13;
-        }
-        if (wave_shape && kernel != 1 && kernel != 13)
-        {
-            int bad = 1;
-            const int e = run_structure_check<4, 4>(desc, &bad);
-            if (e)
-            {
-                delete p;
-                return e;
-            }
-            if (!bad)
-                p->kernel = (kernel >= 2) ? kernel : 3; // auto prefers the folded-DPP form (fp64 runs the plain form either way)
-            else if (kernel >= 2)
-            {
-                delete p;
-                return static_cast<int>(hipErrorInvalidValue);
-            }
-            // kernel 5 (dense element matrix on the matrix cores) needs fp32 and one metric tensor for all elements
-            if (!bad && !is_f64 && (kernel == 0 || kernel == 5))
-            {
-                int err5 = build_dense_element_matrix<float>(p);
-                if (err5 == 0)
-                {
-                    p->kernel = 5;
-                    const int err_el = build_element_lane_tables<4>(p); // -1: the plan stays on the matrix form
-                    if (err_el > 0)
-                    {
-                        cuddh_hip_ddh_plan_destroy(p);
-                        return err_el;
-                    }
-                }
-                else if (kernel == 5)
-                {
-                    delete p;
-                    return err5 > 0 ? err5 : static_cast<int>(hipErrorInvalidValue);
-                }
-            }
-            else if (kernel == 5)
-            {
-                delete p;
-                return static_cast<int>(hipErrorInvalidValue);
-            }
-            // kernel 8 (kernel 5 in fp64) only on request: auto keeps fp64 on kernel 3
-            if (!bad && kernel == 8)
-            {
-                const int err8 = build_dense_element_matrix<double>(p);
-                if (err8 != 0)
-                {
-                    cuddh_hip_ddh_plan_destroy(p);
-                    return err8 > 0 ? err8 : static_cast<int>(hipErrorInvalidValue);
-                }
-                p->kernel = 8;
-            }
+            cuddh_hip_ddh_plan_destroy(p);
+            return err;
         }
         *out = p;
         return 0;
@@ -3513,14 +3340,11 @@ extern "C"
         if (!out)
             return static_cast<int>(hipErrorInvalidValue);
         *out = nullptr;
-        if (!desc || desc->nb < 2 || desc->nb > 10 || desc->n_domains < 1 || mx_elems < 1 || mx_elems > 256 ||
-            (kernel != 0 && kernel != 9 && kernel != 10))
+        static_assert(GW_NODES == DDH_GENERAL_MAX_NODES, "ddh_resolve.hpp holds the node count kernel 9 is built for");
+        if (!desc || desc->n_domains < 1 || mx_elems < 1 || ddh_checks(DdhShape{desc->nb, 0, desc->n_domains, is_f64 ? 1 : 0, mx_elems}, kernel) < 0)
             return static_cast<int>(hipErrorInvalidValue);
         const int nb = desc->nb, nodes = nb * nb * mx_elems;
-        if (nodes > GW_NODES || desc->mx_dof > nodes || desc->mx_fdof > desc->mx_dof)
-            return static_cast<int>(hipErrorInvalidValue);
-        const bool wave_fits = nb == 4 && mx_elems <= 16;
-        if (kernel == 9 && !wave_fits)
+        if (desc->mx_dof > nodes || desc->mx_fdof > desc->mx_dof)
             return static_cast<int>(hipErrorInvalidValue);
 
         // assembly lists from sI, checked entry by entry on the host: nothing the kernels index with is left unchecked
@@ -3564,7 +3388,8 @@ extern "C"
         p->d = *desc;
         p->is_f64 = is_f64 ? 1 : 0;
         p->nodes = nodes;
-        p->kernel = (kernel == 9 || (kernel == 0 && wave_fits)) ? 9 : 10;
+        p->mx_elems = mx_elems;
+        p->requested = kernel;
         e = hipMalloc(reinterpret_cast<void **>(&p->csr_off), sizeof(int) * off.size());
         if (e == hipSuccess)
             e = hipMalloc(reinterpret_cast<void **>(&p->csr_src), sizeof(int) * src.size());
@@ -3572,10 +3397,11 @@ extern "C"
             e = hipMemcpy(p->csr_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess)
             e = hipMemcpy(p->csr_src, src.data(), sizeof(int) * src.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess)
+        const int err = e != hipSuccess ? static_cast<int>(e) : resolve(p);
+        if (err)
         {
             cuddh_hip_ddh_plan_destroy(p);
-            return static_cast<int>(e);
+            return err;
         }
         *out = p;
         return 0;
@@ -3605,7 +3431,7 @@ extern "C"
         return 0;
     }
 
-    int cuddh_hip_ddh_plan_kernel(const cuddh_ddh_plan *plan) { return plan ? plan->kernel : 0; }
+    int cuddh_hip_ddh_plan_kernel(const cuddh_ddh_plan *plan) { return plan ? plan->now.kernel : 0; }
 
     int cuddh_hip_ddh_plan_set_vector_layout(cuddh_ddh_plan *plan, const int *d_gI, int g_ndof)
     {
@@ -3632,42 +3458,30 @@ extern "C"
         return 0;
     }
 
+    // The setters below store their argument, resolve, and on refusal leave the plan as it was (set_and_resolve); which values
+    // a plan takes is ddh_resolve's to say.
     int cuddh_hip_ddh_plan_set_sweep_form(cuddh_ddh_plan *plan, int form)
     {
-        if (!plan || form < 0 || form > 3)
+        if (!plan)
             return static_cast<int>(hipErrorInvalidValue);
-        if (form >= 2 && (plan->kernel != 5 || !plan->Sep4 || plan->n_grids > 0 || plan->rk4))
-            return static_cast<int>(hipErrorInvalidValue);
-        plan->sweep_form = form;
-        return 0;
+        return set_and_resolve(plan, DDH_SET_SWEEP_FORM, [&](cuddh_ddh_plan &p) { p.sweep_form = form; });
     }
 
-    int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan) { return plan ? effective_sweep_form(plan) : 0; }
+    int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan) { return plan ? plan->now.form : 0; }
 
     int cuddh_hip_ddh_plan_set_chain_order(cuddh_ddh_plan *plan, int order)
     {
-        if (!plan || order < 0 || order > 2)
+        if (!plan)
             return static_cast<int>(hipErrorInvalidValue);
-        if (order == 2 && (plan->kernel != 5 || !plan->Sep4 || plan->n_grids > 0 || plan->rk4))
-            return static_cast<int>(hipErrorInvalidValue);
-        plan->chain_order = order;
-        return 0;
+        return set_and_resolve(plan, DDH_SET_CHAIN_ORDER, [&](cuddh_ddh_plan &p) { p.chain_order = order; });
     }
 
-    int cuddh_hip_ddh_plan_chain_order(const cuddh_ddh_plan *plan) { return plan ? effective_chain_order(plan) : 0; }
+    int cuddh_hip_ddh_plan_chain_order(const cuddh_ddh_plan *plan) { return plan ? plan->now.order : 0; }
 
     int cuddh_hip_ddh_plan_set_time_grids(cuddh_ddh_plan *plan, int n_grids, const int *h_nt, const double *h_dt, const void *filter,
                                           const void *cs, const void *sn, const int *d_grid_of)
     {
         if (!plan || n_grids < 1 || !h_nt || !h_dt || !filter || !cs || !sn || !d_grid_of)
-            return static_cast<int>(hipErrorInvalidValue);
-        // the element-lane forms on request have one grid; so have kernels 6 and 7, which hold two subdomains per wavefront,
-        // and kernel 12, which holds four: chosen by auto they give way to kernel 1, requested they are refused.  Kernel 13 holds four
-        // as well and marches once per grid among them (GroupedRows): it takes the grids.  The label-built plans' kernels 9 and 10 hold
-        // one subdomain per wavefront / workgroup and take the grids as they are.
-        if (plan->sweep_form >= 2)
-            return static_cast<int>(hipErrorInvalidValue);
-        if ((plan->kernel == 6 || plan->kernel == 7 || plan->kernel == 12) && plan->requested != 0)
             return static_cast<int>(hipErrorInvalidValue);
         const int nd = plan->d.n_domains;
         // every offset a kernel adds to a table base is formed and checked here
@@ -3731,60 +3545,46 @@ extern "C"
                 (void)hipFree(d_index);
             return static_cast<int>(e);
         }
-        if (plan->grids)
-            (void)hipFree(plan->grids);
-        if (plan->by_steps)
-            (void)hipFree(plan->by_steps);
-        if (plan->by_index)
-            (void)hipFree(plan->by_index);
-        plan->grids = d_grids;
-        plan->by_steps = d_order;
-        plan->by_index = d_index;
-        plan->n_grids = n_grids;
-        plan->grid_of = d_grid_of;
-        plan->grid_filter = filter;
-        plan->grid_cs = cs;
-        plan->grid_sn = sn;
-        if (plan->kernel == 6 || plan->kernel == 7 || plan->kernel == 12)
-            plan->kernel = 1;
-        return 0;
+        // The kernels that hold one subdomain per wavefront or workgroup take the grids as they are, and so does kernel 13, which
+        // marches once per grid among its four (GroupedRows); 6, 7 and 12 chosen by auto give way to kernel 1, requested they
+        // are refused, as is a plan with sweep form 2 or 3 set (ddh_resolve).
+        void *const old_grids = plan->grids, *const old_steps = plan->by_steps, *const old_index = plan->by_index;
+        const int err = set_and_resolve(plan, DDH_SET_NONE,
+                                        [&](cuddh_ddh_plan &p)
+                                        {
+                                            p.grids = d_grids;
+                                            p.by_steps = d_order;
+                                            p.by_index = d_index;
+                                            p.n_grids = n_grids;
+                                            p.grid_of = d_grid_of;
+                                            p.grid_filter = filter;
+                                            p.grid_cs = cs;
+                                            p.grid_sn = sn;
+                                        });
+        for (void *gone : {err ? d_grids : old_grids, err ? static_cast<void *>(d_order) : old_steps, err ? static_cast<void *>(d_index) : old_index})
+            if (gone)
+                (void)hipFree(gone);
+        return err;
     }
 
     int cuddh_hip_ddh_plan_time_grids(const cuddh_ddh_plan *plan) { return plan ? plan->n_grids : 0; }
 
+    // RK4 on a kernel without the form: a request is refused; an auto choice moves to the kernel of its block size that has
+    // one, and scheme 0 afterwards leaves it there: results depend on the scheme, not on the kernel (ddh_resolve)
     int cuddh_hip_ddh_plan_set_integrator(cuddh_ddh_plan *plan, int scheme)
     {
         if (!plan || scheme < 0 || scheme > 1)
             return static_cast<int>(hipErrorInvalidValue);
-        if (scheme == 0)
-        {
-            plan->rk4 = 0; // what auto moved off a kernel stays moved: results depend on the scheme, not on the kernel
-            return 0;
-        }
-        // No RK4 form (has_rk4_form): a request is refused; an auto choice moves to the kernel of
-        // its block size that has one: 3 to 2 (the same lane map without the folded DPP reads), 6, 7, 11 and 12 to 1, and a
-        // kernel-5 plan takes the matrix form whatever its size (effective_sweep_form).  A label-built plan keeps its kernel:
-        // 9 and 10 both have the form.
-        if (plan->kernel == 5 && plan->sweep_form >= 2)
-            return static_cast<int>(hipErrorInvalidValue);
-        if (!has_rk4_form(plan->kernel))
-        {
-            if (plan->requested != 0)
-                return static_cast<int>(hipErrorInvalidValue);
-            plan->kernel = plan->kernel == 3 ? 2 : 1;
-        }
-        plan->rk4 = 1;
-        return 0;
+        return set_and_resolve(plan, DDH_SET_NONE, [&](cuddh_ddh_plan &p) { p.rk4 = scheme; });
     }
 
     int cuddh_hip_ddh_plan_integrator(const cuddh_ddh_plan *plan) { return plan ? plan->rk4 : 0; }
 
     int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last)
     {
-        if (!plan || (plan->kernel != 11 && plan->kernel != 12 && plan->kernel != 13))
+        if (!plan)
             return static_cast<int>(hipErrorInvalidValue);
-        plan->last_copy = last ? 1 : 0;
-        return 0;
+        return set_and_resolve(plan, DDH_SET_OWNER_RULE, [&](cuddh_ddh_plan &p) { p.last_copy = last ? 1 : 0; });
     }
 
     int cuddh_hip_ddh_apply_f32(const cuddh_ddh_plan *plan, int dom_begin, int dom_end, const double *x, double *y, int zero_y,

@@ -1,0 +1,65 @@
+// Which local-solve kernel a DDH plan runs (ddh.hip), in which sweep form and chain order, or that a request is refused: the
+// rule as host-only code on plain integers (src/ddh_resolve.cpp, no HIP).  ddh.hip establishes the facts on the device, calls
+// ddh_resolve() at the end of plan creation and of every setter whose argument enters the rule, and stores the outcome; tests
+// read the rule through cuddh_ddh_resolve (include/cuddh_hip.h) without a GPU.  DESIGN.md 4.3.
+#pragma once
+
+namespace cuddh_k
+{
+    // What plan creation establishes about a descriptor, one after the other.  A check or table builder runs only when every
+    // one before it held, so a bit is set only with the bits of what ran before it.
+    enum DdhCheck
+    {
+        DDH_STRUCTURE = 1, // the NB x NEL structure: elements in the order ex + NEL ey, neighbours share the expected nodes
+        DDH_UNIFORM = 2,   // one metric tensor for all elements
+        DDH_INTERIOR = 3,  // no trace dof lies on an element-interior node
+        DDH_DENSE = 4,     // the dense element matrix was built (kernels 5 and 8)
+        DDH_SEP8 = 5,      // the separable n_basis-8 tables were built (kernel 7)
+        DDH_LANE = 6       // the element-lane tables were built (kernel 5's element-lane form, kernels 11, 12 and 13)
+    };
+    constexpr unsigned ddh_fact(int check) { return 1u << check; } // the bit of a check in `facts`
+
+    struct DdhShape
+    {
+        int nb, nel1d, n_domains, is_f64;
+        int mx_elems; // > 0: a label-built plan (elements per subdomain at most; nel1d is ignored)
+    };
+
+    // the options a plan holds (its setters' arguments as stored)
+    struct DdhOptions
+    {
+        int time_grids; // != 0: per-subdomain time grids are set
+        int rk4;        // != 0: the RK4 integrator
+        int sweep_form, chain_order;
+    };
+
+    // the option a setter is about to store: its value must be able to take effect on the plan as it stands, while values
+    // stored earlier stay where a later setter makes them idle (a chain order on a plan that takes time grids afterwards)
+    enum DdhSetting
+    {
+        DDH_SET_NONE = 0, // plan creation, time grids, the integrator
+        DDH_SET_SWEEP_FORM = 1,
+        DDH_SET_CHAIN_ORDER = 2,
+        DDH_SET_OWNER_RULE = 3
+    };
+
+    struct DdhResolved
+    {
+        int kernel; // 1 to 13
+        int form;   // the sweep form in effect: 1 to 3 on kernel 5, else 0
+        int order;  // the chain order in effect: 1 or 2 in the element-lane form of kernel 5, else 0
+    };
+
+    constexpr int DDH_BLOCK_MAX_NODES = 1024;  // element nodes of a subdomain: one thread each in kernel 1
+    constexpr int DDH_GENERAL_MAX_NODES = 256; // the same on a label-built plan (kernels 9 and 10)
+
+    // The checks plan creation runs for this shape and request before it can decide, in the order they run: four bits each,
+    // the first in the lowest four, 0 ends the list.  -1: the request is refused on this shape whatever the descriptor holds.
+    int ddh_checks(const DdhShape &shape, int request);
+
+    // The rule.  request: the caller's kernel argument (0 auto).  facts: ddh_fact() bits of what was established.  current: the
+    // kernel the plan runs now, 0 at plan creation; a later resolution starts from it and only ever moves an auto choice to a
+    // kernel with the form the options need (3 to 2 and 6, 7, 11, 12 to 1 for RK4; 6, 7, 12 to 1 for time grids), so taking an
+    // option back leaves the plan where it was moved.  Returns 0 and fills `out`, or 1 (hipErrorInvalidValue): refused.
+    int ddh_resolve(const DdhShape &shape, int request, unsigned facts, int current, const DdhOptions &options, int setting, DdhResolved &out);
+} // namespace cuddh_k

@@ -3005,21 +3005,7 @@ namespace
     int mfma_stage(int nb, const Knobs &k) { return k.mfma_stage >= 0 ? k.mfma_stage : ((nb == 6 || nb == 7) ? 322 : 0); }
     bool mfma_stage_built(int stage) { return stage == 0 || stage == 322 || stage == 321 || stage == 332 || stage == 222; }
 
-    // Runtime flags become template arguments here and nowhere else: with_flags(f, a, b, ...) calls f(A{}, B{}, ...) with
-    // std::true_type / std::false_type for each flag.
-    template <class F>
-    void with_flags(F &&f)
-    {
-        f();
-    }
-    template <class F, class... Rest>
-    void with_flags(F &&f, bool flag, Rest... rest)
-    {
-        if (flag)
-            with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
-        else
-            with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
-    }
+    // (runtime flags become template arguments in with_flags, common.hpp, and nowhere else)
 
     // n_basis becomes a template argument here, for every kind of plan: the orders with a kernel are listed here and nowhere else
     template <class F>

@@ -371,7 +371,7 @@ typedef struct cuddh_ddh_plan cuddh_ddh_plan;
  *             contractions in-lane with scalar coefficients, xi and eta neighbours through DPP row shifts that stay in the
  *             row.  Needs what 11 needs (rectangles, the element order ex + 4 ey, no trace dof on an element-interior node;
  *             verified here).  One time grid and RK2 only.  Under auto a qualifying plan takes it from the subdomain count
- *             at which it measured faster than kernel 1 (ELEMENT_LANE5_MIN_DOMAINS in kernels/ddh.hip), kernel 1 below.
+ *             at which it measured faster than kernel 1 (ELEMENT_LANE5_MIN_DOMAINS in src/ddh_resolve.cpp), kernel 1 below.
  *         13 = the element-lane local solves with four 4x4-element subdomains per wavefront that accept per-subdomain time
  *             grids (fp32, nel1d == 4; on request only, never picked by auto).  nb == 4: needs what kernel 5's element-lane
  *             form needs (the element order ex + 4 ey, one metric for all elements, no trace dof on an element-interior
@@ -461,6 +461,27 @@ int cuddh_hip_ddh_plan_set_owner_rule(cuddh_ddh_plan *plan, int last);
  * differs between the two sides of a shared edge; h_out is not written), 1 (hipErrorInvalidValue) for another nb or a null
  * pointer.  Plan creation calls the same code on the descriptor's D and G. */
 int cuddh_element_lane_tables(int nb, const float *h_D, const float *h_G, float *h_out);
+/* The rule by which a DDH plan picks its kernel, sweep form and chain order, alone: host code on plain integers (no device is
+ * touched), the code plan creation and the setters above call.
+ *   nb, nel1d, n_domains, is_f64: the descriptor's; mx_elems > 0: a label-built plan (nel1d is ignored), else 0;
+ *   request: the `kernel` argument of plan creation (0 auto);
+ *   facts: what plan creation established about the descriptor, a sum of  2 the NB x NEL element structure holds, 4 one metric
+ *       for all elements, 8 no trace dof on an element-interior node, 16 the dense element matrix was built (kernels 5, 8),
+ *       32 the separable n_basis-8 tables were built (kernel 7), 64 the element-lane tables were built (kernel 5's
+ *       element-lane form, kernels 11, 12, 13);
+ *   current: the kernel the plan runs now, 0 at plan creation.  A later resolution starts from it, so an auto choice that time
+ *       grids or RK4 moved stays moved when the option is taken back;
+ *   time_grids, rk4, sweep_form, chain_order: the options the plan holds (the first two as flags);
+ *   setting: which of these the call is about to store, 0 none (creation, time grids, integrator), 1 the sweep form, 2 the chain
+ *       order, 3 the owner rule: a chain order 2 and an owner rule are refused where they cannot take effect now, but stay when
+ *       a later option makes them idle.
+ * out[0..2] receive the kernel (1 to 13), the sweep form in effect (0 to 3) and the chain order in effect (0 to 2); out[3] the
+ * checks plan creation runs for this shape and request before it decides, in order, four bits each from the lowest up (1
+ * structure, 2 one metric, 3 interior nodes, 4 dense matrix, 5 n_basis-8 tables, 6 element-lane tables: facts holds 1 << check),
+ * or -1 where the request is refused on this shape whatever the descriptor holds.  Returns 0, or 1 (hipErrorInvalidValue) where
+ * the plan or the setter call is refused (out[0..2] are then 0). */
+int cuddh_ddh_resolve(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids, int rk4,
+                      int sweep_form, int chain_order, int setting, int *out);
 /* Per-subdomain time grids.  The descriptor holds ONE grid (nt, dt, wh_filter, cs, sn), taken from the mesh alone; the wave
  * speed 1 / a never enters it, and where a < 1 the explicit time stepping runs past its usable range.  Local
  * solves couple through the traces only, so every subdomain may march its WaveHoltz period on a grid of its own: after this

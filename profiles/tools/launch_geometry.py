@@ -8,7 +8,10 @@ and, to DIR/plans.txt, the lines it prints: kernel() of every plan and, for the 
 laid out, affine, native ordering; the single operators expose none -- what theirs decides, the NT flag, is part of kernel()).
 `compare` reads the two traces (the rocpd database rocprofv3 leaves under DIR) and prints, dispatch by dispatch, kernel name,
 grid, workgroup and LDS bytes of both builds, whether they are the same, whether the saved results are (np.array_equal) and
-whether the plan lines are."""
+whether the plan lines are.
+`run-ddh DIR` does the same for the DDH local-solve kernels of csrc/kernels/ddh.hip (the list DDH below: one plan per resolved
+kernel, sweep form, chain order, with and without time grids and RK4); `compare` then lists every ddh_* dispatch, the plan
+creation's check kernels included."""
 import csv
 import os
 import sqlite3
@@ -81,6 +84,90 @@ def run(out_dir: Path):
     print(*lines, sep="\n")
 
 
+# DDH plans, one per resolved form of csrc/kernels/ddh.hip: (label, n_basis, elements per side, block, label block, precision, kernel,
+# creation keywords, setters); four subdomains each
+DDH_GRIDS = np.array([1, 2, 1, 1], dtype=np.int32)
+DDH = [("kernel 1", 4, 8, None, None, "f32", 1, {}, ()),
+       ("kernel 1 f64 grids", 4, 8, None, None, "f64", 1, {"time_step": DDH_GRIDS}, ()),
+       ("kernel 1 n_basis 5 block 6 (1024-thread form)", 5, 12, 6, None, "f32", 1, {}, ()),
+       ("kernel 2", 4, 8, None, None, "f32", 2, {}, ()),
+       ("kernel 3", 4, 8, None, None, "f32", 3, {}, ()),
+       ("kernel 3 f64", 4, 8, None, None, "f64", 0, {}, ()),
+       ("kernel 4", 4, 8, None, None, "f32", 4, {}, ()),
+       ("kernel 5 form 1", 4, 8, None, None, "f32", 0, {}, ()),
+       ("kernel 5 form 1 grids", 4, 8, None, None, "f32", 0, {"time_step": DDH_GRIDS}, ()),
+       ("kernel 5 form 2 pinned", 4, 8, None, None, "f32", 0, {}, (("set_sweep_form", 2),)),
+       ("kernel 5 form 2 paired", 4, 8, None, None, "f32", 0, {}, (("set_sweep_form", 2), ("set_chain_order", 2))),
+       ("kernel 5 form 3 pinned", 4, 8, None, None, "f32", 0, {}, (("set_sweep_form", 3),)),
+       ("kernel 6", 8, 4, None, None, "f64", 0, {}, ()),
+       ("kernel 6 f32", 8, 4, None, None, "f32", 6, {}, ()),
+       ("kernel 7", 8, 4, None, None, "f32", 0, {}, ()),
+       ("kernel 8", 4, 8, None, None, "f64", 8, {}, ()),
+       ("kernel 9", 4, 8, None, 4, "f32", 0, {}, ()),
+       ("kernel 9 f64 grids RK4", 4, 8, None, 4, "f64", 9, {"time_ratios": DDH_GRIDS, "integrator": "rk4"}, ()),
+       ("kernel 10", 5, 6, None, 3, "f32", 0, {}, ()),
+       ("kernel 11", 4, 16, 8, None, "f32", 0, {}, ()),
+       ("kernel 11 grids, last copy", 4, 16, 8, None, "f32", 0, {"time_step": DDH_GRIDS}, (("set_owner_rule", True),)),
+       ("kernel 12", 5, 8, 4, None, "f32", 12, {}, ()),
+       ("kernel 12 last copy", 5, 8, 4, None, "f32", 12, {}, (("set_owner_rule", True),)),
+       ("kernel 13 n_basis 4", 4, 8, None, None, "f32", 13, {}, ()),
+       ("kernel 13 n_basis 4 grids", 4, 8, None, None, "f32", 13, {"time_step": DDH_GRIDS}, ()),
+       ("kernel 13 n_basis 5", 5, 8, 4, None, "f32", 13, {}, ()),
+       ("kernel 13 n_basis 5 grids", 5, 8, 4, None, "f32", 13, {"time_step": DDH_GRIDS}, ()),
+       ("kernel 1 RK4", 4, 8, None, None, "f32", 1, {"integrator": "rk4"}, ()),
+       ("kernel 2 RK4 (auto, f64)", 4, 8, None, None, "f64", 0, {"integrator": "rk4"}, ()),
+       ("kernel 5 RK4", 4, 8, None, None, "f32", 0, {"integrator": "rk4"}, ()),
+       ("kernel 5 RK4 grids", 4, 8, None, None, "f32", 0, {"integrator": "rk4", "time_step": DDH_GRIDS}, ()),
+       ("kernel 8 RK4", 4, 8, None, None, "f64", 8, {"integrator": "rk4"}, ())]
+
+
+def run_ddh(out_dir: Path):
+    """One plan per entry of DDH: its local solves over all subdomains, over two ranges, listed while holding issue priority, and
+    without sources (the form without x); the traces go to DIR/outputs.npz, kernel / sweep form / chain order to DIR/plans.txt."""
+    import math
+
+    import torch
+
+    sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
+    import cuddhelmholtz_amd as cd
+
+    dev = torch.device("cuda:0")
+    cd.use_torch_stream()
+    saved, lines = {}, []
+    for label, nb, nx, block, label_block, precision, kernel, kw, setters in DDH:
+        fem = cd.H1Space(cd.Mesh2D.uniform_rect(nx, -1.0, 1.0, nx, -1.0, 1.0), cd.Basis(nb))
+        omega, h_a = 2 * math.pi * nx / 10, np.ones(fem.size())
+        if label_block:
+            e = np.arange(nx * nx)
+            labels = ((e % nx) // label_block + (nx // label_block) * ((e // nx) // label_block)).astype(np.int32)
+            F = cd.DDH.from_labels(omega, h_a, fem, labels, precision=precision, kernel=kernel, **kw)
+        else:
+            F = cd.DDH(omega, h_a, fem, nx, nx, precision=precision, kernel=kernel, block=block, **kw)
+        for setter, arg in setters:
+            getattr(F, setter)(arg)
+        F.set_wh_iters(1)
+        nd = F.info()["n_domains"]
+        g = torch.Generator(device="cpu").manual_seed(nb)
+        f = torch.randn(2 * fem.size(), generator=g, dtype=torch.float64).to(dev)
+        lam = torch.randn(F.size(), generator=g, dtype=torch.float64).to(F.trace_dtype).to(dev)
+        out = [torch.zeros_like(lam) for _ in range(4)]
+        F.local_traces(0, nd, f, lam, out[0])
+        F.local_traces(0, nd - 1, f, lam, out[1])
+        F.local_traces(nd - 1, nd, f, lam, out[1])
+        F.set_wave_priority(True)
+        F.local_traces_listed(torch.tensor([2, 0, 3], dtype=torch.int32, device=dev), f, lam, out[2])
+        F.set_wave_priority(False)
+        F.local_traces(0, nd, None, lam, out[3])
+        torch.cuda.synchronize()
+        lines.append(f"{label}: kernel {F.info()['kernel']} sweep form {F.sweep_form()} chain order {F.chain_order()} integrator {F.integrator()[0]} "
+                     f"time ratios {' '.join(map(str, F.time_ratios()))}")
+        for name, t in zip(("all", "two ranges", "listed, priority", "no sources"), out):
+            saved[f"{label} | {name}"] = t.cpu().numpy()
+    np.savez(out_dir / "outputs.npz", **saved)
+    (out_dir / "plans.txt").write_text("\n".join(lines) + "\n")
+    print(*lines, sep="\n")
+
+
 def dispatches(trace_dir: Path):
     dbs = sorted(trace_dir.rglob("*.db"))
     if dbs:
@@ -89,7 +176,7 @@ def dispatches(trace_dir: Path):
         with open(sorted(trace_dir.rglob("*kernel_trace.csv"))[-1], newline="") as f:
             rows = sorted(csv.DictReader(f), key=lambda r: int(r["Start_Timestamp"]))
         rows = [(r["Kernel_Name"], int(r["Grid_Size_X"]), int(r["Workgroup_Size_X"]), int(r["LDS_Block_Size"])) for r in rows]
-    return [r for r in rows if any(k in r[0] for k in ("helm_", "op_patch", "op_mfma", "op_border", "native_kernel"))]
+    return [r for r in rows if any(k in r[0] for k in ("helm_", "op_patch", "op_mfma", "op_border", "native_kernel", "ddh_"))]
 
 
 def compare(old_dir: Path, new_dir: Path):
@@ -118,5 +205,7 @@ def compare(old_dir: Path, new_dir: Path):
 if __name__ == "__main__":
     if sys.argv[1] == "run":
         run(Path(sys.argv[2]))
+    elif sys.argv[1] == "run-ddh":
+        run_ddh(Path(sys.argv[2]))
     else:
         compare(Path(sys.argv[2]), Path(sys.argv[3]))

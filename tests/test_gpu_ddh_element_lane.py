@@ -36,7 +36,7 @@ pytestmark = pytest.mark.gpu
 
 # distance of the parent commit's kernel 5 (matrix form) to the fp64 oracle on L.case(nx): nx -> (rhs, action, postprocess)
 PARENT5 = {8: (1.14e-06, 4.1e-07, 1.00e-06), 16: (7.6e-07, 4.9e-07, 1.09e-06)}
-AUTO_MIN_DOMAINS = 8192  # ELEMENT_LANE_MIN_DOMAINS of csrc/kernels/ddh.hip
+AUTO_MIN_DOMAINS = 8192  # ELEMENT_LANE_MIN_DOMAINS of csrc/src/ddh_resolve.cpp
 HIP_ERROR_INVALID_VALUE = 1
 
 

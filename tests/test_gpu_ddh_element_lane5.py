@@ -29,7 +29,7 @@ from test_gpu_parity import rel, to_dev
 
 pytestmark = pytest.mark.gpu
 
-AUTO_MIN_DOMAINS = 64  # ELEMENT_LANE5_MIN_DOMAINS of csrc/kernels/ddh.hip
+AUTO_MIN_DOMAINS = 64  # ELEMENT_LANE5_MIN_DOMAINS of csrc/src/ddh_resolve.cpp
 SHAPES = {(8, 8): (272, 1250), (12, 8): (476, 1251)}  # (nx, ny) -> (traces, time steps per period)
 
 
