@@ -198,6 +198,12 @@ _sig("cuddh_hip_ddh_apply_list_f64", ci, vp, vp, ci, vp, vp, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_set_vector_layout", ci, vp, vp, ci)
 _sig("cuddh_hip_ddh_apply_f32", ci, vp, ci, ci, vp, vp, ci, vp, vp, vp)
 _sig("cuddh_hip_ddh_apply_f64", ci, vp, ci, ci, vp, vp, ci, vp, vp, vp)
+_sig("cuddh_hip_wave_stage_begin_f64", ci, ci, cd, vp, vp, vp, vp, vp, vp, vp)
+_sig("cuddh_hip_wave_stage_rk2_a_f64", ci, ci, cd, cd, cd, *([vp] * 10))
+_sig("cuddh_hip_wave_stage_rk2_b_f64", ci, ci, cd, cd, cd, cd, *([vp] * 11))
+for _n in ("1", "2", "3"):
+    _sig(f"cuddh_hip_wave_stage_rk4_{_n}_f64", ci, ci, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave_stage_rk4_4_f64", ci, ci, cd, cd, cd, cd, *([vp] * 13))
 
 # ---- handle layer (cuddh_capi.h)
 _sig("cuddh_last_error", cp)
@@ -324,6 +330,10 @@ _sig("cuddh_gmres_callback_sharded_aug", ci, ci, vp, ACTION_CB, vp, REDUCE_CB, v
 
 _sig("cuddh_gmres_ddh_cplx", ci, ci, vp, vp, vp, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
 _sig("cuddh_gmres_callback_cplx", ci, ci, vp, ACTION_CB, vp, vp, ci, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
+_sig("cuddh_waveholtz_create", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci)
+_sig("cuddh_waveholtz_period", ci, vp, vp, vp, vp)
+_sig("cuddh_waveholtz_solution", ci, vp, vp, vp)
+_sig("cuddh_waveholtz_info", ci, vp, vp, vp, vp, ci)
 
 
 def last_error() -> str:

@@ -692,6 +692,107 @@ class DDH:
 ORTHOGONALIZATIONS = {"mgs": 0, "cgs2": 1}
 
 
+class WaveHoltz(_Operator):
+    """Whole-domain WaveHoltz (csrc/include/cuddh/waveholtz.hpp): the filtered time-domain iteration for
+    (K - w^2 M + i w H) U = f on the whole space, M = diag(a^2 m) and H = diag(a h) lumped, K the global StiffnessMatrix.
+    An operator of size 2 ndof on z = [u; v] whose action is y = x - S x, so that
+        W.rhs(f, b); gmres(W.size(), z, W, b, m, maxit, tol); W.solution(z, u)        (or W.solve(f, u, ...))
+    solves it; U = u + i v / w.  It is not a check of DDH's fixed point, which is another discrete problem.
+
+    h_a: HOST nodal coefficient (finite, positive).  integrator "rk2" (the mesh grid) or "rk4" on ceil(nt_mesh / coarsen) steps
+    (coarsen in [1, 16], default 4), DDH's rules.  time_ratio: an integer in [1, 256] that multiplies the step count, or
+    "coefficient" = max(1, ceil((1 - 1e-9) / min a)).  stiffness "gauss" (StiffnessMatrix(fem)) or "lobatto" (the collocated
+    stiffness of the DDH local solves).  faces: edge ids of the absorbing faces, None = every boundary edge.
+    A bad name, a coarsen outside its range, coarsen > 1 with "rk2" and a bad ratio raise ValueError before any native call."""
+
+    STIFFNESS = ("gauss", "lobatto")
+
+    def __init__(self, omega: float, h_a: np.ndarray, fem: H1Space, integrator: str = "rk2", coarsen: int | None = None, time_ratio=1,
+                 stiffness: str = "gauss", faces=None):
+        scheme, coarsen = self._integrator(integrator, coarsen)
+        ratio = self._ratio(time_ratio)
+        if not isinstance(stiffness, str) or stiffness not in self.STIFFNESS:
+            raise ValueError(f"WaveHoltz: stiffness must be 'gauss' or 'lobatto', not {stiffness!r}")
+        if faces is not None:
+            faces = np.asarray(faces)
+            if faces.ndim != 1 or (faces.size and not np.issubdtype(faces.dtype, np.integer)):
+                raise ValueError("WaveHoltz: faces must be a one-dimensional array of edge ids")
+            faces = np.ascontiguousarray(faces, dtype=np.int32)
+        h_a = np.ascontiguousarray(h_a, dtype=np.float64)
+        if h_a.size != fem.size():
+            raise ValueError(f"WaveHoltz: {h_a.size} coefficient values for {fem.size()} dofs")
+        if not np.all(np.isfinite(h_a)) or not np.all(h_a > 0):
+            raise ValueError("WaveHoltz: the coefficient a must be finite and positive")
+        h = lib.cuddh_waveholtz_create(float(omega), _h(h_a), fem._h, scheme, coarsen, ratio, self.STIFFNESS.index(stiffness),
+                                       None if faces is None else _h(faces), -1 if faces is None else int(faces.size))
+        if not h and N.last_error().startswith("WaveHoltz error"):
+            raise ValueError(f"WaveHoltz: {N.last_error()}")
+        super().__init__(N.handle(h, "WaveHoltz"), (fem,), 2 * fem.size())
+        self.fem, self.omega = fem, float(omega)
+
+    @staticmethod
+    def _integrator(integrator, coarsen):
+        """(scheme, coarsen) of cuddh_waveholtz_create, or ValueError"""
+        if not isinstance(integrator, str) or integrator not in ("rk2", "rk4"):
+            raise ValueError(f"WaveHoltz: integrator must be 'rk2' or 'rk4', not {integrator!r}")
+        if coarsen is None:
+            coarsen = 1 if integrator == "rk2" else 4
+        if isinstance(coarsen, (bool, np.bool_)) or not isinstance(coarsen, (int, np.integer)):
+            raise ValueError(f"WaveHoltz: coarsen must be an integer in [1, 16], not {coarsen!r}")
+        if not 1 <= coarsen <= 16:
+            raise ValueError(f"WaveHoltz: coarsen must lie in [1, 16], got {int(coarsen)}")
+        if integrator == "rk2" and coarsen != 1:
+            raise ValueError("WaveHoltz: integrator 'rk2' marches on the mesh grid (coarsen 1) only; a coarser grid needs 'rk4'")
+        return (0 if integrator == "rk2" else 1), int(coarsen)
+
+    @staticmethod
+    def _ratio(time_ratio) -> int:
+        """time_ratio as cuddh_waveholtz_create takes it (0: from the coefficient), or ValueError"""
+        if isinstance(time_ratio, str):
+            if time_ratio != "coefficient":
+                raise ValueError(f"WaveHoltz: time_ratio must be 'coefficient' or an integer in [1, 256], not {time_ratio!r}")
+            return 0
+        if isinstance(time_ratio, (bool, np.bool_)) or not isinstance(time_ratio, (int, np.integer)):
+            raise ValueError(f"WaveHoltz: time_ratio must be 'coefficient' or an integer in [1, 256], not {time_ratio!r}")
+        if not 1 <= time_ratio <= 256:
+            raise ValueError(f"WaveHoltz: time_ratio must lie in [1, 256], got {int(time_ratio)}")
+        return int(time_ratio)
+
+    def size(self) -> int:
+        return self._n
+
+    def period(self, z_in, f, z_out):
+        """z_out = W(z_in; f): one filtered period from z_in (None: zero) under the load f = [f_re; f_im] (None: none)"""
+        N.check_capi(lib.cuddh_waveholtz_period(self._h, _ptr(z_in, "f64", self._n, "z_in"), _ptr(f, "f64", self._n, "f"),
+                                                _ptr(z_out, "f64", self._n, "z_out")), "WaveHoltz.period")
+
+    def rhs(self, f, b):
+        self.period(None, f, b)
+
+    def solution(self, z, u):
+        """u = [z_u; z_v / omega]"""
+        N.check_capi(lib.cuddh_waveholtz_solution(self._h, _ptr(z, "f64", self._n, "z"), _ptr(u, "f64", self._n, "u")), "WaveHoltz.solution")
+
+    def info(self) -> dict:
+        info = np.zeros(6, dtype=np.int32)
+        dt = C.c_double()
+        buf = C.create_string_buffer(160)
+        N.check_capi(lib.cuddh_waveholtz_info(self._h, _h(info), C.byref(dt), buf, 160), "WaveHoltz.info")
+        return {"nt": int(info[0]), "dt": dt.value, "ratio": int(info[1]), "integrator": "rk4" if info[2] else "rk2", "coarsen": int(info[3]),
+                "sweeps_per_period": int(info[4]), "stiffness_kernel": buf.value.decode()}
+
+    def solve(self, f, u, m: int = 20, maxit: int = 200, tol: float = 1e-6, orth: str = "mgs", augment: int = 0) -> "SolverOut":
+        """rhs -> gmres from zero -> solution; u receives [Re U; Im U]"""
+        import torch
+
+        b = torch.empty(self._n, dtype=torch.float64, device=f.device)
+        z = torch.zeros_like(b)
+        self.rhs(f, b)
+        out = gmres(self._n, z, self, b, m, maxit, tol, orth=orth, augment=augment)
+        self.solution(z, u)
+        return out
+
+
 def _orth_code(orth) -> int:
     """the C API's code of an orthogonalisation name; anything but "mgs" / "cgs2" is a ValueError, before any native call"""
     if not isinstance(orth, str) or orth not in ORTHOGONALIZATIONS:

@@ -145,11 +145,12 @@ def _present(path: Path) -> bool:
 
 
 def build_examples(verbose: bool = False) -> list[Path]:
-    """Compiles this repository's native drivers (ddh_solve.cpp, helmholtz_solve.cpp) against csrc/include/cuddh.hpp.
+    """Compiles this repository's native drivers (ddh_solve.cpp, helmholtz_solve.cpp, waveholtz_solve.cpp) against csrc/include/cuddh.hpp.
     Binaries go to build/examples/ (git-ignored).  The reference's own examples and test suite, compiled unchanged
     (drop-in check), are test infrastructure: __graft_entry__.build() has them built outside the package."""
     EXAMPLES_DIR.mkdir(parents=True, exist_ok=True)
-    jobs = [(CSRC / "examples" / "ddh_solve.cpp", "ddh_solve"), (CSRC / "examples" / "helmholtz_solve.cpp", "helmholtz_solve")]
+    jobs = [(CSRC / "examples" / "ddh_solve.cpp", "ddh_solve"), (CSRC / "examples" / "helmholtz_solve.cpp", "helmholtz_solve"),
+            (CSRC / "examples" / "waveholtz_solve.cpp", "waveholtz_solve")]
     outs = []
     for src, name in jobs:
         out = EXAMPLES_DIR / name

@@ -24,6 +24,7 @@
 #include "cuddh/krylov.hpp"
 #include "cuddh/ddh.hpp"
 #include "cuddh/helmholtz.hpp"
+#include "cuddh/waveholtz.hpp"
 #include "cuddh/multigpu.hpp"
 #include "cuddh/partition.hpp"
 

@@ -1,0 +1,95 @@
+// Whole-domain WaveHoltz: the time-domain fixed-point iteration for  (K - w^2 M + i w H) U = f  on the whole H1Space, with the
+// global StiffnessMatrix as the sweep of the march.  M = diag(a^2 m), m the Gauss-Lobatto lumped mass; H = diag(a h)
+// on the dofs of the absorbing faces, h the lumped face mass.  The march is the one of the DDH local solves (one subdomain that
+// covers the mesh): one period of RK2 or RK4 steps, filtered.  W(z; f) = S z + W(0; f) is affine in z = [u; v], and its fixed
+// point solves (I - S) z = W(0; f); U = u + i v / w.  Call sequence:
+//     W.rhs(f, b); gmres(W.size(), z, &W, b, m, maxit, tol); W.solution(z, u);
+// Its iteration count does not depend on a decomposition; it is NOT a check of DDH's fixed point, which reads the global load in
+// every subdomain and is another discrete problem (tests/helmholtz_direct.py).
+// Everything is fp64; all vectors are DEVICE pointers unless marked HOST.
+#ifndef CUDDH_AMD_WAVEHOLTZ_HPP
+#define CUDDH_AMD_WAVEHOLTZ_HPP
+
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "ddh.hpp"
+#include "memory.hpp"
+#include "operator.hpp"
+#include "operators.hpp"
+#include "spaces.hpp"
+
+namespace cuddh
+{
+    struct WaveHoltzOptions
+    {
+        /// rk2 on the mesh grid (the default) or rk4 on ceil(nt_mesh / coarsen) steps, coarsen in [1, 16]: DDHIntegrator's rules
+        DDHIntegrator integrator;
+        /// the period is time_ratio times the base grid's steps, in [1, DDHTimeStep::max_ratio]; from_coefficient: the ratio is
+        /// max(1, ceil((1 - 1e-9) / min a)) over all dofs
+        int time_ratio = 1;
+        static constexpr int from_coefficient = 0;
+        /// gauss: StiffnessMatrix(fem) (n_basis + 1 Gauss-Legendre points, the plan kernels); lobatto: the n_basis-point Gauss-Lobatto
+        /// rule, the collocated stiffness of the DDH local solves, on whatever kernel StiffnessMatrix runs it
+        enum Stiffness
+        {
+            gauss,
+            lobatto
+        };
+        Stiffness stiffness = gauss;
+        /// absorbing faces: HOST edge ids; n_faces < 0 (the default): every boundary edge, DDH's choice
+        const int *h_faces = nullptr;
+        int n_faces = -1;
+    };
+
+    class WaveHoltz : public Operator
+    {
+    public:
+        /// h_a: HOST nodal coefficient a(x), finite and positive (anything else throws before any allocation or launch, as do an
+        /// integrator or a ratio outside the rules above)
+        WaveHoltz(double omega, const double *h_a, const H1Space &fem, const WaveHoltzOptions &options = {});
+        ~WaveHoltz();
+
+        WaveHoltz(const WaveHoltz &) = delete;
+        WaveHoltz &operator=(const WaveHoltz &) = delete;
+
+        /// length of z = [u; v]
+        int size() const { return 2 * ndof; }
+
+        /// z_out = W(z_in; f): one filtered period started from z_in (nullptr: from zero) under the load f = [f_re; f_im]
+        /// (nullptr: none, the homogeneous march S z_in).  z_out must not overlap z_in or f.
+        void period(const double *z_in, const double *f, double *z_out) const;
+        /// b = W(0; f)
+        void rhs(const double *f, double *b) const { period(nullptr, f, b); }
+        /// u = [z_u; z_v / omega]: real and imaginary part of U.  u may be z.
+        void solution(const double *z, double *u) const;
+
+        /// y = x - S x
+        void action(const double *x, double *y) const override;
+        /// y += c (x - S x)
+        void action(double c, const double *x, double *y) const override;
+
+        int num_steps() const { return nt; }
+        double time_step() const { return dt; }
+        int time_ratio() const { return ratio; }
+        DDHIntegrator integrator() const { return scheme; }
+        int sweeps_per_period() const { return nt * (scheme.scheme == DDHIntegrator::rk4 ? 4 : 2); }
+        /// kernel the stiffness sweep launches (after the first period; "generic" = element_ops.hip)
+        std::string stiffness_kernel() const { return K->kernel_name(); }
+
+    private:
+        const double omega;
+        const int ndof;
+        DDHIntegrator scheme;
+        int nt = 0, ratio = 1;
+        double dt = 0.0;
+        std::vector<double> filt, cs, sn; // HOST tables of the period's grid: filter (nt + 1), cs and sn (2 nt + 1)
+        std::unique_ptr<StiffnessMatrix> K;
+        host_device_dvec invm, Hi;        // 1 / (a^2 m) and h a (zero off the absorbing faces), ndof each
+        // the march's state and stage vectors (each 16-byte aligned whatever ndof is, so that the stages take their 16-byte path)
+        mutable host_device_dvec w, p, q, u, v, ps, qs, aq, ap, F, G, tmp;
+    };
+} // namespace cuddh
+
+#endif

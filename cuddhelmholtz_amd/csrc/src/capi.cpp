@@ -534,9 +534,68 @@ extern "C"
                 name = s->kernel_name();
             else if (auto *m = dynamic_cast<MassMatrix *>(h->op.get()))
                 name = m->kernel_name();
+            else if (auto *wh = dynamic_cast<WaveHoltz *>(h->op.get()))
+                name = wh->stiffness_kernel();
             std::snprintf(buf, cap, "%s", name.c_str());
         });
     }
+    // ------------------------------------------------------------ whole-domain WaveHoltz
+    void *cuddh_waveholtz_create(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                 const int *h_faces, int n_faces)
+    {
+        return guarded_new<OpHandle>([&]
+        {
+            if (integrator != 0 && integrator != 1)
+                throw std::runtime_error("WaveHoltz error: integrator: the scheme must be 0 (rk2) or 1 (rk4), not " + std::to_string(integrator) + ".");
+            if (stiffness != 0 && stiffness != 1)
+                throw std::runtime_error("WaveHoltz error: stiffness: the rule must be 0 (gauss) or 1 (lobatto), not " + std::to_string(stiffness) + ".");
+            WaveHoltzOptions o;
+            o.integrator = {integrator == 1 ? DDHIntegrator::rk4 : DDHIntegrator::rk2, coarsen};
+            o.time_ratio = time_ratio;
+            o.stiffness = stiffness == 1 ? WaveHoltzOptions::lobatto : WaveHoltzOptions::gauss;
+            o.h_faces = h_faces;
+            o.n_faces = n_faces;
+            auto h = new OpHandle;
+            h->op.reset(new WaveHoltz(omega, h_a, *static_cast<H1Space *>(fem), o));
+            return h;
+        });
+    }
+    namespace
+    {
+        const WaveHoltz &waveholtz_of(void *op)
+        {
+            auto *W = op ? dynamic_cast<const WaveHoltz *>(static_cast<OpHandle *>(op)->op.get()) : nullptr;
+            if (!W)
+                throw std::runtime_error("not a WaveHoltz operator");
+            return *W;
+        }
+    } // namespace
+    int cuddh_waveholtz_period(void *op, const double *z_in, const double *f, double *z_out)
+    {
+        return guarded([&] { waveholtz_of(op).period(z_in, f, z_out); });
+    }
+    int cuddh_waveholtz_solution(void *op, const double *z, double *u) { return guarded([&] { waveholtz_of(op).solution(z, u); }); }
+    int cuddh_waveholtz_info(void *op, int *h_info, double *h_dt, char *kernel, int cap)
+    {
+        return guarded([&]
+        {
+            const WaveHoltz &W = waveholtz_of(op);
+            if (h_info)
+            {
+                h_info[0] = W.num_steps();
+                h_info[1] = W.time_ratio();
+                h_info[2] = W.integrator().scheme == DDHIntegrator::rk4 ? 1 : 0;
+                h_info[3] = W.integrator().coarsen;
+                h_info[4] = W.sweeps_per_period();
+                h_info[5] = W.size() / 2;
+            }
+            if (h_dt)
+                *h_dt = W.time_step();
+            if (kernel && cap > 0)
+                std::snprintf(kernel, cap, "%s", W.stiffness_kernel().c_str());
+        });
+    }
+
     int cuddh_helmholtz_read_stamps(void *op, unsigned long long *h_out, int n_patches)
     {
         auto *h = static_cast<OpHandle *>(op);

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "cuddh/parallel.hpp"
+#include "cuddh/time_grid.hpp"
 #include "cuddh_hip.h"
 
 namespace cuddh
@@ -32,23 +33,6 @@ namespace cuddh
                 else
                     err = cuddh_hip_ddh_geom_from_corners_f64(n_domains, mx_elems, nb, n_elems, elems, w, points, corners, G, stream());
                 check_hip(err, "DDH geometric factors");
-            }
-
-            // WaveHoltz tables of the grid of nt steps of dt = T / nt: filter (nt + 1: trapezoid weights of the period
-            // average), cs and sn (2 nt + 1: -cos and sin at the half steps); computed in double, rounded to Real
-            template <typename Real>
-            void fill_time_grid(double omega, int nt, double dt, Real *filt, Real *cs, Real *sn)
-            {
-                for (int k = 0; k <= nt; ++k)
-                    filt[k] = static_cast<Real>(dt * (omega / M_PI) * (std::cos(omega * k * dt) - 0.25));
-                filt[0] = static_cast<Real>(filt[0] * 0.5); // trapezoid rule end points
-                filt[nt] = static_cast<Real>(filt[nt] * 0.5);
-                for (int k = 0; k <= 2 * nt; ++k)
-                {
-                    const double t = 0.5 * k * dt;
-                    cs[k] = static_cast<Real>(-std::cos(omega * t));
-                    sn[k] = static_cast<Real>(std::sin(omega * t));
-                }
             }
 
             /// what can be refused about a time-step policy without the subdomains' dofs: all of it
@@ -281,11 +265,10 @@ namespace cuddh
             // ---- the mesh grid: dt = 0.1 h / nb^2 shrunk so that nt dt is one period
             const double T = 2.0 * M_PI / omega;
             const double h = fem.mesh().min_h();
-            dt = 0.2 * 0.5 * h / (nb * nb);
-            nt = nt_mesh = static_cast<int>(std::ceil(T / dt));
+            nt = nt_mesh = mesh_grid_steps(omega, h, nb);
             // RK4 on a coarser grid: ceil(nt_mesh / coarsen) steps are the base grid, and what the ratios below multiply
             if (const int c = more->integrator.coarsen; c > 1)
-                nt = nt_mesh = (nt_mesh + c - 1) / c;
+                nt = nt_mesh = coarsened_steps(nt_mesh, c);
 
             // ---- steps of subdomain s = ratios[s] * nt_mesh
             ratios.assign(n_domains, 1);
@@ -302,7 +285,7 @@ namespace cuddh
                     double a_min = INFINITY;
                     for (int i = 0; i < sizes(s); ++i)
                         a_min = std::min(a_min, h_a[gI(i, s)]);
-                    ratios[s] = std::max(1, static_cast<int>(std::ceil((1.0 / a_min) * (1.0 - 1e-9))));
+                    ratios[s] = ratio_from_coefficient(a_min);
                 }
             }
             std::vector<int> distinct(ratios);

@@ -1,0 +1,228 @@
+// Whole-domain WaveHoltz (cuddh/waveholtz.hpp): set-up on the host, the march as stiffness applies and the stage kernels of
+// csrc/kernels/waveholtz.hip (cuddh_hip_wave_stage_*), one launch of each per sweep.
+#include "cuddh/waveholtz.hpp"
+
+#include <cmath>
+#include <string>
+
+#include "cuddh/time_grid.hpp"
+#include "cuddh_hip.h"
+
+namespace cuddh
+{
+    namespace
+    {
+        /// the options that can be refused without the mesh: the integrator (DDHIntegrator's rules) and the ratio
+        void check_options(const WaveHoltzOptions &o)
+        {
+            const DDHIntegrator &i = o.integrator;
+            if (i.scheme != DDHIntegrator::rk2 && i.scheme != DDHIntegrator::rk4)
+                cuddh_error("WaveHoltz error: integrator: the scheme must be rk2 or rk4.");
+            if (i.coarsen < 1 || i.coarsen > DDHIntegrator::max_coarsen)
+                cuddh_error(("WaveHoltz error: integrator: coarsen = " + std::to_string(i.coarsen) + " is outside [1, " +
+                             std::to_string(DDHIntegrator::max_coarsen) + "].").c_str());
+            if (i.scheme == DDHIntegrator::rk2 && i.coarsen != 1)
+                cuddh_error("WaveHoltz error: integrator: rk2 marches on the mesh grid (coarsen = 1) only; a coarser grid needs rk4.");
+            if (o.time_ratio != WaveHoltzOptions::from_coefficient && (o.time_ratio < 1 || o.time_ratio > DDHTimeStep::max_ratio))
+                cuddh_error(("WaveHoltz error: time step: ratio " + std::to_string(o.time_ratio) + " is outside [1, " +
+                             std::to_string(DDHTimeStep::max_ratio) + "].").c_str());
+            if (o.stiffness != WaveHoltzOptions::gauss && o.stiffness != WaveHoltzOptions::lobatto)
+                cuddh_error("WaveHoltz error: stiffness: the rule must be gauss or lobatto.");
+            if (o.n_faces > 0 && !o.h_faces)
+                cuddh_error("WaveHoltz error: faces: a list of absorbing faces was announced and none given.");
+        }
+
+        host_device_dvec rule_weights(const QuadratureRule &quad)
+        {
+            host_device_dvec w(quad.size());
+            double *h = w.host_write();
+            for (int i = 0; i < quad.size(); ++i)
+                h[i] = quad.w(i);
+            return w;
+        }
+    } // namespace
+
+    WaveHoltz::WaveHoltz(double omega_, const double *h_a, const H1Space &fem, const WaveHoltzOptions &o)
+        : omega(omega_), ndof(fem.size()), scheme(o.integrator), invm(fem.size()), Hi(fem.size())
+    {
+        check_options(o);
+        if (!std::isfinite(omega) || !(omega > 0.0))
+            cuddh_error("WaveHoltz error: omega must be finite and positive.");
+        double a_min = INFINITY;
+        for (int g = 0; g < ndof; ++g)
+        {
+            if (!std::isfinite(h_a[g]) || !(h_a[g] > 0.0))
+                cuddh_error(("WaveHoltz error: a = " + std::to_string(h_a[g]) + " at dof " + std::to_string(g) + "; a must be finite and positive.").c_str());
+            a_min = std::min(a_min, h_a[g]);
+        }
+        ratio = o.time_ratio;
+        if (ratio == WaveHoltzOptions::from_coefficient)
+        {
+            if (std::ceil((1.0 / a_min) * (1.0 - 1e-9)) > DDHTimeStep::max_ratio)
+                cuddh_error(("WaveHoltz error: time step: min a = " + std::to_string(a_min) + " asks for more than " +
+                             std::to_string(DDHTimeStep::max_ratio) + " times the mesh grid's steps.").c_str());
+            ratio = detail::ratio_from_coefficient(a_min);
+        }
+
+        // ---- the period's grid
+        const int nb = fem.basis().size();
+        nt = ratio * detail::coarsened_steps(detail::mesh_grid_steps(omega, fem.mesh().min_h(), nb), scheme.coarsen);
+        dt = 2.0 * M_PI / omega / nt;
+        filt.resize(nt + 1);
+        cs.resize(2 * nt + 1);
+        sn.resize(2 * nt + 1);
+        detail::fill_time_grid(omega, nt, dt, filt.data(), cs.data(), sn.data());
+
+        // ---- the sweep
+        if (o.stiffness == WaveHoltzOptions::lobatto)
+            K.reset(new StiffnessMatrix(fem, fem.basis().quadrature()));
+        else
+            K.reset(new StiffnessMatrix(fem));
+
+        // ---- invm = 1 / (a^2 m), m the Gauss-Lobatto lumped mass
+        const QuadratureRule &gll = fem.basis().quadrature();
+        host_device_dvec wts = rule_weights(gll);
+        host_device_dvec a2(ndof);
+        {
+            double *h = a2.host_write();
+            for (int g = 0; g < ndof; ++g)
+                h[g] = h_a[g] * h_a[g];
+        }
+        const double *detJ = fem.mesh().element_metrics(gll).measures(MemorySpace::DEVICE);
+        detail::check_hip(cuddh_hip_diag_mass_setup(ndof, fem.mesh().n_elem(), nb, a2.device_read(), detJ, wts.device_read(),
+                                                    fem.global_indices(MemorySpace::DEVICE), invm.device_write(), stream()),
+                          "WaveHoltz lumped mass");
+
+        // ---- Hi = h a on the dofs of the absorbing faces (h the lumped face mass), zero elsewhere
+        std::vector<int> all;
+        const int *faces = o.h_faces;
+        int n_faces = o.n_faces;
+        if (n_faces < 0)
+        {
+            const ivec b = fem.mesh().boundary_edges();
+            for (int i = 0; i < b.size(); ++i)
+                all.push_back(b[i]);
+            faces = all.data();
+            n_faces = static_cast<int>(all.size());
+        }
+        double *d_Hi = Hi.device_write(); // a fresh allocation: zero-filled
+        if (n_faces > 0)
+        {
+            for (int f = 0; f < n_faces; ++f)
+                if (faces[f] < 0 || faces[f] >= fem.mesh().n_edges())
+                    cuddh_error(("WaveHoltz error: faces: edge " + std::to_string(faces[f]) + " is not an edge of the mesh.").c_str());
+            FaceSpace fs(fem, n_faces, faces);
+            host_device_dvec af(fs.size()), hf(fs.size());
+            {
+                double *h = af.host_write();
+                const int *proj = fs.global_indices(MemorySpace::HOST);
+                for (int i = 0; i < fs.size(); ++i)
+                    h[i] = h_a[proj[i]];
+            }
+            const double *fdetJ = fs.metrics(gll).measures(MemorySpace::DEVICE);
+            double *d_hf = hf.device_write(); // zero-filled, which the accumulation needs
+            detail::check_hip(cuddh_hip_diag_facemass_setup(fs.size(), n_faces, nb, wts.device_read(), fdetJ, af.device_read(),
+                                                            fs.subspace_indices(MemorySpace::DEVICE), d_hf, stream()),
+                              "WaveHoltz lumped face mass");
+            detail::check_hip(cuddh_hip_reciprocal_f64(fs.size(), d_hf, stream()), "WaveHoltz lumped face mass"); // the set-up leaves 1 / (h a)
+            fs.prolong(d_hf, d_Hi);
+            detail::check_hip(cuddh_hip_stream_sync(stream()), "WaveHoltz setup"); // fs and its vectors die here
+        }
+        detail::check_hip(cuddh_hip_stream_sync(stream()), "WaveHoltz setup"); // a2 and wts die here
+
+        const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
+        for (host_device_dvec *x : {&w, &p, &q, &u, &v, &ps, &qs})
+            x->resize(ndof);
+        tmp.resize(2 * ndof);
+        if (rk4)
+        {
+            aq.resize(ndof);
+            ap.resize(ndof);
+        }
+    }
+
+    WaveHoltz::~WaveHoltz() = default;
+
+    void WaveHoltz::period(const double *z_in, const double *f, double *z_out) const
+    {
+        const int n = ndof;
+        void *st = stream();
+        double *W = w.device_write(), *P = p.device_write(), *Q = q.device_write(), *U = u.device_write(), *V = v.device_write();
+        double *PS = ps.device_write(), *QS = qs.device_write();
+        const double *IM = invm.device_read(), *HI = Hi.device_read();
+        const double *Ff = nullptr, *Gf = nullptr;
+        if (f)
+        {
+            // copies of the load on 16-byte boundaries (f + ndof is on one only when ndof is even)
+            if (F.size() != n)
+            {
+                F.resize(n);
+                G.resize(n);
+            }
+            double *dF = F.device_write(), *dG = G.device_write();
+            copy(n, f, dF);
+            copy(n, f + n, dG);
+            Ff = dF;
+            Gf = dG;
+        }
+        if (z_in)
+            detail::check_hip(cuddh_hip_wave_stage_begin_f64(n, filt[0], z_in, z_in + n, P, Q, U, V, st), "WaveHoltz::period");
+        else
+            for (double *x : {P, Q, U, V})
+                zeros(n, x);
+
+        if (scheme.scheme == DDHIntegrator::rk2)
+        {
+            for (int it = 1; it <= nt; ++it)
+            {
+                K->action(P, W);
+                detail::check_hip(cuddh_hip_wave_stage_rk2_a_f64(n, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], W, P, Q, IM, HI, Ff, Gf, QS, PS, st),
+                                  "WaveHoltz::period");
+                K->action(PS, W);
+                detail::check_hip(cuddh_hip_wave_stage_rk2_b_f64(n, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], W, QS, IM, HI, Ff, Gf, P, Q, U, V, st),
+                                  "WaveHoltz::period");
+            }
+        }
+        else
+        {
+            double *AQ = aq.device_write(), *AP = ap.device_write();
+            for (int it = 1; it <= nt; ++it)
+            {
+                const int k = 2 * it - 2;
+                K->action(P, W);
+                detail::check_hip(cuddh_hip_wave_stage_rk4_1_f64(n, 0.5 * dt, cs[k], sn[k], W, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), "WaveHoltz::period");
+                K->action(PS, W);
+                detail::check_hip(cuddh_hip_wave_stage_rk4_2_f64(n, 0.5 * dt, cs[k + 1], sn[k + 1], W, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st),
+                                  "WaveHoltz::period");
+                K->action(PS, W);
+                detail::check_hip(cuddh_hip_wave_stage_rk4_3_f64(n, dt, cs[k + 1], sn[k + 1], W, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), "WaveHoltz::period");
+                K->action(PS, W);
+                detail::check_hip(cuddh_hip_wave_stage_rk4_4_f64(n, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], W, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st),
+                                  "WaveHoltz::period");
+            }
+        }
+        copy(n, U, z_out);
+        copy(n, V, z_out + n);
+    }
+
+    void WaveHoltz::solution(const double *z, double *out) const
+    {
+        if (out != z)
+            copy(2 * ndof, z, out);
+        scal(ndof, 1.0 / omega, out + ndof);
+    }
+
+    void WaveHoltz::action(const double *x, double *y) const
+    {
+        period(x, nullptr, y);
+        axpby(2 * ndof, 1.0, x, -1.0, y);
+    }
+
+    void WaveHoltz::action(double c, const double *x, double *y) const
+    {
+        double *t = tmp.device_write();
+        period(x, nullptr, t);
+        axpby(2 * ndof, c, x, 1.0, y);
+        axpby(2 * ndof, -c, t, 1.0, y);
+    }
+} // namespace cuddh

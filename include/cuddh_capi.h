@@ -300,6 +300,26 @@ int cuddh_gmres_ddh_cplx(int n, void *x, void *ddh, const void *b, int m, int ma
 int cuddh_gmres_callback_cplx(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
                               int verbose, double max_seconds, cuddh_solver_result *out, double *h_res, double *h_time);
 
+/* ---- whole-domain WaveHoltz (csrc/include/cuddh/waveholtz.hpp): the filtered time-domain iteration for
+ * (K - w^2 M + i w H) U = f on the whole space, M = diag(a^2 m) and H = diag(a h) lumped.  The handle is an OPERATOR handle of
+ * size 2 ndof whose action is y = x - S x: cuddh_operator_apply, cuddh_operator_apply_add, cuddh_operator_destroy and
+ * cuddh_gmres_f64 (and its _orth / _aug forms) take it.  h_a: HOST nodal coefficient (ndof), finite and positive.
+ * integrator 0 = RK2 (coarsen must be 1), 1 = RK4 on ceil(nt_mesh / coarsen) steps, coarsen in [1, 16]; time_ratio in [1, 256]
+ * multiplies the step count, 0 = from the coefficient, max(1, ceil((1 - 1e-9) / min a)); stiffness 0 = the Gauss-Legendre rule of
+ * cuddh_stiffness_create(fem, 0), 1 = the n_basis-point Gauss-Lobatto rule (the collocated stiffness of the DDH local solves);
+ * h_faces HOST edge ids of the absorbing faces, n_faces < 0 = every boundary edge.  Anything else is refused before anything is
+ * allocated (NULL + cuddh_last_error, the message starts with "WaveHoltz error"). */
+void *cuddh_waveholtz_create(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                             const int *h_faces, int n_faces);
+/* z_out = W(z_in; f) (DEVICE, 2 ndof each): one filtered period from z_in (NULL: from zero) under the load f = [f_re; f_im]
+ * (NULL: none).  The right-hand side of (I - S) z = b is b = W(0; f). */
+int cuddh_waveholtz_period(void *op, const double *z_in, const double *f, double *z_out);
+/* u = [z_u; z_v / omega], real and imaginary part of U (DEVICE, 2 ndof; u may be z) */
+int cuddh_waveholtz_solution(void *op, const double *z, double *u);
+/* h_info = {nt, time ratio, integrator, coarsen, sweeps per period, ndof}; *h_dt = time step; kernel (cap bytes, may be NULL):
+ * the kernel of the stiffness sweep, "generic" before the first period.  Returns 0, nonzero on error. */
+int cuddh_waveholtz_info(void *op, int *h_info, double *h_dt, char *kernel, int cap);
+
 #ifdef __cplusplus
 }
 #endif

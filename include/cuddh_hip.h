@@ -545,6 +545,42 @@ int cuddh_hip_ddh_apply_list_f32(const cuddh_ddh_plan *plan, const int *d_domain
 int cuddh_hip_ddh_apply_list_f64(const cuddh_ddh_plan *plan, const int *d_domains, int n, const double *x, double *y, int zero_y,
                                  const double *lambda, double *update, void *stream);
 
+/* ------------------------------------------------------------------ whole-domain WaveHoltz march: stage kernels
+ * csrc/kernels/waveholtz.hip, DESIGN 4.5.  One launch does everything a Runge-Kutta sweep does besides its stiffness apply
+ * w = K p'; every vector of n doubles is read once and written once.  With
+ *     fq(w, q) = invm * (w - Hi * q + c * F + s * G)
+ * (c, s: cs[k], sn[k] of the sweep's time; F, G: the load, both NULL for the homogeneous form, which then reads neither):
+ *   begin:  p = zu,  q = zv,  u = filt0 zu,  v = filt0 zv
+ *   rk2_a:  qh = q + half_dt fq(w, q),   ph = p - half_dt q                                    (w = K p)
+ *   rk2_b:  p -= dt qh,  q += dt fq(w, qh),  u += filt p,  v += filt q   (the new p, q)         (w = K ph)
+ *   rk4_1:  k = fq(w, q);   ps = p - half_dt q,   qs = q + half_dt k,  aq = k,     ap = -q       (w = K p)
+ *   rk4_2:  k = fq(w, qs);  ps = p - half_dt qs,  qs = q + half_dt k,  aq += 2 k,  ap -= 2 qs    (w = K ps; the old qs on the right)
+ *   rk4_3:  rk4_2 with dt in the place of half_dt
+ *   rk4_4:  k = fq(w, qs);  p += sixth_dt (ap - qs),  q += sixth_dt (aq + k),  u += filt p,  v += filt q
+ * Outputs that are also inputs (p, q, u, v, qs, aq, ap) are updated in place; no other two arguments may overlap.  Every
+ * product-sum is one fused multiply-add, in the order written.  16-byte accesses when every pointer is 16-byte aligned, element
+ * by element otherwise. */
+int cuddh_hip_wave_stage_begin_f64(int n, double filt0, const double *zu, const double *zv, double *p, double *q, double *u, double *v,
+                                   void *stream);
+int cuddh_hip_wave_stage_rk2_a_f64(int n, double half_dt, double c, double s, const double *w, const double *p, const double *q,
+                                   const double *invm, const double *Hi, const double *F, const double *G, double *qh, double *ph,
+                                   void *stream);
+int cuddh_hip_wave_stage_rk2_b_f64(int n, double dt, double c, double s, double filt, const double *w, const double *qh, const double *invm,
+                                   const double *Hi, const double *F, const double *G, double *p, double *q, double *u, double *v,
+                                   void *stream);
+int cuddh_hip_wave_stage_rk4_1_f64(int n, double half_dt, double c, double s, const double *w, const double *p, const double *q,
+                                   const double *invm, const double *Hi, const double *F, const double *G, double *ps, double *qs,
+                                   double *aq, double *ap, void *stream);
+int cuddh_hip_wave_stage_rk4_2_f64(int n, double half_dt, double c, double s, const double *w, const double *p, const double *q,
+                                   const double *invm, const double *Hi, const double *F, const double *G, double *ps, double *qs,
+                                   double *aq, double *ap, void *stream);
+int cuddh_hip_wave_stage_rk4_3_f64(int n, double dt, double c, double s, const double *w, const double *p, const double *q,
+                                   const double *invm, const double *Hi, const double *F, const double *G, double *ps, double *qs,
+                                   double *aq, double *ap, void *stream);
+int cuddh_hip_wave_stage_rk4_4_f64(int n, double sixth_dt, double c, double s, double filt, const double *w, const double *qs,
+                                   const double *aq, const double *ap, const double *invm, const double *Hi, const double *F,
+                                   const double *G, double *p, double *q, double *u, double *v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

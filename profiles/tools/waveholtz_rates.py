@@ -1,0 +1,216 @@
+"""What the whole-domain WaveHoltz march costs on one MI355X, n_basis 4, a == 1, omega = 2 pi nx / 10.
+
+stages   us of every cuddh_hip_wave_stage_* launch (homogeneous form: the GMRES action) and of the stiffness apply it follows,
+         beside cuddh_hip_axpby_f64 at the same n, alternating in the same run, device events around `inner` back-to-back
+         launches, median of `reps`.  TB/s on the stated bytes: 8 B per vector read or written per dof (begin 6, rk2_a 7, rk2_b 12,
+         rk4_1 9, rk4_2 / rk4_3 12, rk4_4 14 vectors; axpby 3).  us per sweep = stiffness apply + stage, averaged over a step.
+period   ms of WaveHoltz.period (one launch per sweep besides the apply) against the same march composed from the entry points the
+         library had before (cuddh_operator_apply, cuddh_hip_copy_f64, cuddh_hip_diag_scale_f64, cuddh_hip_axpby_f64: 10 launches
+         per RK2 step besides the two applies), alternating in the same run; the two results are compared first.
+solve    one whole solve per size in the example's regime (the disk coefficient, the Gaussians as load, GMRES(20), tol 1e-4),
+         rk4 / coarsen 4: matvecs (= periods) and seconds of the gmres() call, beside DDH's figures for the same problems
+         (DESIGN 5.2).
+
+  python profiles/tools/waveholtz_rates.py [parts=stages,period,solve] [sizes=256,512,1024] [solve_sizes=256,512] [reps=7] [out=profiles/r24/waveholtz_rates.txt]
+"""
+import ctypes as C
+import math
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[2]
+sys.path.insert(0, str(ROOT))
+import cuddhelmholtz_amd as cd  # noqa: E402
+from cuddhelmholtz_amd import _native as N  # noqa: E402
+
+argv = dict(a.split("=", 1) for a in sys.argv[1:])
+parts = argv.get("parts", "stages,period,solve").split(",")
+sizes = [int(v) for v in argv.get("sizes", "256,512,1024").split(",")]
+solve_sizes = [int(v) for v in argv.get("solve_sizes", "256,512").split(",") if v]
+reps = int(argv.get("reps", "7"))
+out_path = Path(argv.get("out", str(ROOT / "profiles" / "r24" / "waveholtz_rates.txt")))
+if not torch.cuda.is_available():
+    sys.exit("waveholtz_rates.py measures on the GPU: none is visible")
+dev = torch.device("cuda:0")
+cd.use_torch_stream()
+NB = 4
+lines = []
+
+
+def say(text=""):
+    print(text, flush=True)
+    lines.append(text)
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    out_path.write_text("\n".join(lines) + "\n")
+
+
+def p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def timed(fs, inner):
+    """median ms per call of every f in fs (name -> callable), alternating, `reps` passes after two warm-up passes"""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    times = {k: [] for k in fs}
+    for rep in range(reps + 2):
+        for k, f in fs.items():
+            torch.cuda.synchronize()
+            ev[0].record()
+            for _ in range(inner):
+                f()
+            ev[1].record()
+            torch.cuda.synchronize()
+            if rep >= 2:
+                times[k].append(ev[0].elapsed_time(ev[1]) / inner)
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in times.items()}
+
+
+def space(nx):
+    mesh = cd.Mesh2D.uniform_rect(nx, -1.0, 1.0, nx, -1.0, 1.0)
+    return mesh, cd.H1Space(mesh, cd.Basis(NB))
+
+
+STAGE_VECTORS = {"begin": 6, "rk2_a": 7, "rk2_b": 12, "rk4_1": 9, "rk4_2": 12, "rk4_3": 12, "rk4_4": 14, "axpby": 3}
+
+
+def stages(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    g = torch.Generator(device=dev).manual_seed(1)
+    v = {k: torch.randn(n, dtype=torch.float64, device=dev, generator=g) for k in ("w", "p", "q", "u", "v", "ps", "qs", "aq", "ap", "zu", "zv")}
+    v["invm"] = torch.rand(n, dtype=torch.float64, device=dev, generator=g) + 0.5
+    v["Hi"] = torch.zeros(n, dtype=torch.float64, device=dev)
+    K = cd.StiffnessMatrix(fem)
+    K.action(v["p"], v["w"])
+    L, st = N.lib, stream()
+    dt = 1e-6  # (the timed launches repeat on the same vectors: keep them bounded)
+    a = {k: p(t) for k, t in v.items()}
+    fs = {
+        "stiffness": lambda: K.action(v["p"], v["w"]),
+        "begin": lambda: N.check(L.cuddh_hip_wave_stage_begin_f64(n, 0.5, a["zu"], a["zv"], a["p"], a["q"], a["u"], a["v"], st)),
+        "rk2_a": lambda: N.check(L.cuddh_hip_wave_stage_rk2_a_f64(n, dt / 2, 1.0, 0.0, a["w"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["qs"], a["ps"], st)),
+        "rk2_b": lambda: N.check(L.cuddh_hip_wave_stage_rk2_b_f64(n, dt, 1.0, 0.0, 1e-3, a["w"], a["qs"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st)),
+        "rk4_1": lambda: N.check(L.cuddh_hip_wave_stage_rk4_1_f64(n, dt / 2, 1.0, 0.0, a["w"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st)),
+        "rk4_2": lambda: N.check(L.cuddh_hip_wave_stage_rk4_2_f64(n, dt / 2, 1.0, 0.0, a["w"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st)),
+        "rk4_3": lambda: N.check(L.cuddh_hip_wave_stage_rk4_3_f64(n, dt, 1.0, 0.0, a["w"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st)),
+        "rk4_4": lambda: N.check(L.cuddh_hip_wave_stage_rk4_4_f64(n, dt / 6, 1.0, 0.0, 1e-3, a["w"], a["qs"], a["aq"], a["ap"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st)),
+        "axpby": lambda: N.check(L.cuddh_hip_axpby_f64(n, 1e-6, a["zu"], 1.0, a["zv"], st)),
+    }
+    t = timed(fs, inner=20)
+    say(f"stages nx={nx} ndof={n} ({8 * n / 1e6:.1f} MB per vector) stiffness kernel {K.kernel()!r}")
+    ax = STAGE_VECTORS["axpby"] * 8 * n / (t["axpby"][0] * 1e-3) / 1e12
+    for k, (med, lo, hi) in t.items():
+        if k == "stiffness":
+            say(f"  {k:10s} {1e3 * med:8.1f} us (min {1e3 * lo:.1f} max {1e3 * hi:.1f})")
+        else:
+            rate = STAGE_VECTORS[k] * 8 * n / (med * 1e-3) / 1e12
+            say(f"  {k:10s} {1e3 * med:8.1f} us (min {1e3 * lo:.1f} max {1e3 * hi:.1f})  {STAGE_VECTORS[k]:2d} vectors  {rate:5.2f} TB/s  {rate / ax:4.2f} of axpby")
+    s = t["stiffness"][0]
+    say(f"  us per sweep: rk2 {1e3 * (s + (t['rk2_a'][0] + t['rk2_b'][0]) / 2):.1f} (apply {1e3 * s:.1f} + stage {1e3 * (t['rk2_a'][0] + t['rk2_b'][0]) / 2:.1f}), "
+        f"rk4 {1e3 * (s + sum(t[k][0] for k in ('rk4_1', 'rk4_2', 'rk4_3', 'rk4_4')) / 4):.1f} "
+        f"(apply {1e3 * s:.1f} + stage {1e3 * sum(t[k][0] for k in ('rk4_1', 'rk4_2', 'rk4_3', 'rk4_4')) / 4:.1f})")
+
+
+def composed_period(W, K, z, out, tab, work):
+    """the homogeneous RK2 period from the entry points the library had before the stage kernels"""
+    L, st = N.lib, stream()
+    n = z.numel() // 2
+    nt, dt, filt = tab
+    w, pp, q, u, v, ph, qh, invm, Hi = (p(work[k]) for k in ("w", "p", "q", "u", "v", "ph", "qh", "invm", "Hi"))
+    zu, zv = C.c_void_p(z.data_ptr()), C.c_void_p(z.data_ptr() + 8 * n)
+    for src, dst in ((zu, pp), (zv, q), (zu, u), (zv, v)):
+        L.cuddh_hip_copy_f64(n, src, dst, st)
+    L.cuddh_hip_axpby_f64(n, 0.0, pp, filt[0], u, st)
+    L.cuddh_hip_axpby_f64(n, 0.0, q, filt[0], v, st)
+    for it in range(1, nt + 1):
+        L.cuddh_operator_apply(K._h, pp, w)
+        L.cuddh_hip_diag_scale_f64(n, 1, -1.0, Hi, q, w, st)          # w -= Hi q
+        L.cuddh_hip_copy_f64(n, q, qh, st)
+        L.cuddh_hip_diag_scale_f64(n, 1, 0.5 * dt, invm, w, qh, st)   # qh = q + dt/2 invm w
+        L.cuddh_hip_copy_f64(n, pp, ph, st)
+        L.cuddh_hip_axpby_f64(n, -0.5 * dt, q, 1.0, ph, st)           # ph = p - dt/2 q
+        L.cuddh_operator_apply(K._h, ph, w)
+        L.cuddh_hip_diag_scale_f64(n, 1, -1.0, Hi, qh, w, st)         # w -= Hi qh
+        L.cuddh_hip_axpby_f64(n, -dt, qh, 1.0, pp, st)                # p -= dt qh
+        L.cuddh_hip_diag_scale_f64(n, 1, dt, invm, w, q, st)          # q += dt invm w
+        L.cuddh_hip_axpby_f64(n, filt[it], pp, 1.0, u, st)
+        L.cuddh_hip_axpby_f64(n, filt[it], q, 1.0, v, st)
+    L.cuddh_hip_copy_f64(n, u, C.c_void_p(out.data_ptr()), st)
+    L.cuddh_hip_copy_f64(n, v, C.c_void_p(out.data_ptr() + 8 * n), st)
+
+
+def period(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    W = cd.WaveHoltz(omega, np.ones(n), fem)
+    info = W.info()
+    nt, dt = info["nt"], info["dt"]
+    filt = [dt * (omega / math.pi) * (math.cos(omega * k * dt) - 0.25) for k in range(nt + 1)]
+    filt[0] *= 0.5
+    filt[nt] *= 0.5
+    g = torch.Generator(device=dev).manual_seed(2)
+    z = torch.randn(2 * n, dtype=torch.float64, device=dev, generator=g)
+    a, b = torch.empty_like(z), torch.empty_like(z)
+    K = cd.StiffnessMatrix(fem)
+    work = {k: torch.zeros(n, dtype=torch.float64, device=dev) for k in ("w", "p", "q", "u", "v", "ph", "qh", "Hi")}
+    # the same lumped matrices as the solver's: 1 / m through the library, h a on the boundary through the face space
+    ones = torch.ones(n, dtype=torch.float64, device=dev)
+    work["invm"] = torch.empty_like(ones)
+    cd.DiagInvMassMatrix(fem).action(ones, work["invm"])
+    fs = cd.FaceSpace(fem, mesh.boundary_edges())
+    hf = torch.ones(fs.size(), dtype=torch.float64, device=dev)
+    inv_h = torch.empty_like(hf)
+    cd.DiagInvFaceMassMatrix(fs).action(hf, inv_h)
+    fs.prolong(1.0 / inv_h, work["Hi"])
+    W.period(z, None, a)
+    composed_period(W, K, z, b, (nt, dt, filt), work)
+    torch.cuda.synchronize()
+    diff = float(torch.linalg.norm(a - b) / torch.linalg.norm(a))
+    t = timed({"fused": lambda: W.period(z, None, a), "composed": lambda: composed_period(W, K, z, b, (nt, dt, filt), work)}, inner=1)
+    f, c = t["fused"], t["composed"]
+    say(f"period nx={nx} ndof={n} rk2 nt={nt} ({2 * nt} sweeps): fused {f[0]:.2f} ms (min {f[1]:.2f} max {f[2]:.2f}) = {1e3 * f[0] / (2 * nt):.1f} us per sweep; "
+        f"composed {c[0]:.2f} ms (min {c[1]:.2f} max {c[2]:.2f}) = {1e3 * c[0] / (2 * nt):.1f} us per sweep; fused / composed {f[0] / c[0]:.3f}; results differ by {diff:.1e}")
+
+
+DDH_FIGURES = {256: "390 matvecs", 512: "1,887 matvecs in 25 s", 1024: "GMRES(20) stalls at 3.3e-3 (11,593 matvecs); GMRES(200) at 4.6e-4 after 910 s"}
+
+
+def solve(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    f = torch.zeros(2 * n, dtype=torch.float64, device=dev)
+    a = torch.zeros(n, dtype=torch.float64, device=dev)
+    cd.linear_functional(fem, cd.GAUSSIANS, f[:n], param=omega)
+    cd.linear_functional(fem, cd.ALPHA_DISK, a)
+    cd.DiagInvMassMatrix(fem).action(a, a)
+    W = cd.WaveHoltz(omega, a.cpu().numpy(), fem, integrator="rk4", coarsen=4)
+    b, z = torch.empty_like(f), torch.zeros_like(f)
+    W.rhs(f, b)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = cd.gmres(2 * n, z, W, b, 20, 400, 1e-4, max_seconds=900.0)
+    torch.cuda.synchronize()
+    sec = time.perf_counter() - t0
+    info = W.info()
+    rel = out.res_norm[-1] / out.res_norm[0]
+    say(f"solve nx={nx} ndof={n} omega={omega:.2f} disk coefficient (min a {float(a.min()):.3f}) rk4/4 nt={info['nt']} GMRES(20) tol 1e-4: success={out.success} "
+        f"matvecs={out.num_matvec} cycles={out.num_iter} rel_res={rel:.3e} seconds={sec:.2f} ms_per_period={1e3 * sec / max(1, out.num_matvec):.2f} "
+        f"us_per_sweep={1e6 * sec / max(1, out.num_matvec) / info['sweeps_per_period']:.1f} finite={bool(torch.isfinite(z).all())}; DDH (DESIGN 5.2): {DDH_FIGURES.get(nx, 'not recorded')}")
+
+
+say(f"waveholtz_rates: {torch.cuda.get_device_name(0)}, n_basis {NB}, a == 1, omega = 2 pi nx / 10, reps {reps}")
+for part, fn, ns in (("stages", stages, sizes), ("period", period, sizes), ("solve", solve, solve_sizes)):
+    if part in parts:
+        for nx in ns:
+            fn(nx)
