@@ -205,6 +205,24 @@ for _n in ("1", "2", "3"):
     _sig(f"cuddh_hip_wave_stage_rk4_{_n}_f64", ci, ci, cd, cd, cd, *([vp] * 12))
 _sig("cuddh_hip_wave_stage_rk4_4_f64", ci, ci, cd, cd, cd, cd, *([vp] * 13))
 
+
+class WaveLattice(C.Structure):
+    """cuddh_wave_lattice: A row-major n_basis x n_basis in the first entries of A"""
+    _fields_ = [("nx", ci), ("ny", ci), ("n_basis", ci), ("stride", ci), ("cx", cd), ("cy", cd), ("A", cd * 64), ("w", cd * 8)]
+
+
+_wl = C.POINTER(WaveLattice)
+_sig("cuddh_hip_wave_lattice_rk2_a_f64", ci, _wl, cd, cd, cd, *([vp] * 9))
+_sig("cuddh_hip_wave_lattice_rk2_b_f64", ci, _wl, cd, cd, cd, cd, *([vp] * 11))
+_sig("cuddh_hip_wave_lattice_rk4_1_f64", ci, _wl, cd, cd, cd, *([vp] * 11))
+_sig("cuddh_hip_wave_lattice_rk4_2_f64", ci, _wl, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave_lattice_rk4_3_f64", ci, _wl, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave_lattice_rk4_4_f64", ci, _wl, cd, cd, cd, cd, *([vp] * 13))
+_sig("cuddh_hip_wave_lattice_gather_f64", ci, ci, vp, vp, vp, vp)
+_sig("cuddh_hip_wave_lattice_begin_f64", ci, ci, cd, vp, vp, vp, vp, vp, vp, vp, vp)
+_sig("cuddh_hip_wave_lattice_tile_x", ci)
+_sig("cuddh_hip_wave_lattice_tile_y", ci)
+
 # ---- handle layer (cuddh_capi.h)
 _sig("cuddh_last_error", cp)
 _sig("cuddh_set_stream", None, vp)
@@ -334,6 +352,10 @@ _sig("cuddh_waveholtz_create", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci)
 _sig("cuddh_waveholtz_period", ci, vp, vp, vp, vp)
 _sig("cuddh_waveholtz_solution", ci, vp, vp, vp)
 _sig("cuddh_waveholtz_info", ci, vp, vp, vp, vp, ci)
+_sig("cuddh_waveholtz_create_sweep", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci, ci)
+_sig("cuddh_waveholtz_sweep", ci, vp)
+_sig("cuddh_wave_lattice_map", ci, vp, vp, vp, vp)
+_sig("cuddh_wave_lattice_tables", ci, vp, vp, vp)
 
 
 def last_error() -> str:

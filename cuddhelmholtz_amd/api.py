@@ -703,16 +703,25 @@ class WaveHoltz(_Operator):
     (coarsen in [1, 16], default 4), DDH's rules.  time_ratio: an integer in [1, 256] that multiplies the step count, or
     "coefficient" = max(1, ceil((1 - 1e-9) / min a)).  stiffness "gauss" (StiffnessMatrix(fem)) or "lobatto" (the collocated
     stiffness of the DDH local solves).  faces: edge ids of the absorbing faces, None = every boundary edge.
-    A bad name, a coarsen outside its range, coarsen > 1 with "rk2" and a bad ratio raise ValueError before any native call."""
+    sweep "operator" (the default: a stiffness apply and a stage kernel per sweep) or "lattice": one launch per sweep does the
+    stiffness stencil and the stage on lattice-ordered vectors (csrc/kernels/wave_lattice.hip).  "lattice" needs stiffness
+    "lobatto" and a uniform rectangle mesh, which is detected; every method takes and returns vectors in the space's order.
+    A bad name, a coarsen outside its range, coarsen > 1 with "rk2", a bad ratio and "lattice" with "gauss" raise ValueError
+    before any native call; a mesh the lattice form cannot take raises ValueError with the native message."""
 
     STIFFNESS = ("gauss", "lobatto")
+    SWEEPS = ("operator", "lattice")
 
     def __init__(self, omega: float, h_a: np.ndarray, fem: H1Space, integrator: str = "rk2", coarsen: int | None = None, time_ratio=1,
-                 stiffness: str = "gauss", faces=None):
+                 stiffness: str = "gauss", faces=None, sweep: str = "operator"):
         scheme, coarsen = self._integrator(integrator, coarsen)
         ratio = self._ratio(time_ratio)
         if not isinstance(stiffness, str) or stiffness not in self.STIFFNESS:
             raise ValueError(f"WaveHoltz: stiffness must be 'gauss' or 'lobatto', not {stiffness!r}")
+        if not isinstance(sweep, str) or sweep not in self.SWEEPS:
+            raise ValueError(f"WaveHoltz: sweep must be 'operator' or 'lattice', not {sweep!r}")
+        if sweep == "lattice" and stiffness != "lobatto":
+            raise ValueError("WaveHoltz: sweep 'lattice' is the collocated stiffness; it needs stiffness 'lobatto'")
         if faces is not None:
             faces = np.asarray(faces)
             if faces.ndim != 1 or (faces.size and not np.issubdtype(faces.dtype, np.integer)):
@@ -723,8 +732,9 @@ class WaveHoltz(_Operator):
             raise ValueError(f"WaveHoltz: {h_a.size} coefficient values for {fem.size()} dofs")
         if not np.all(np.isfinite(h_a)) or not np.all(h_a > 0):
             raise ValueError("WaveHoltz: the coefficient a must be finite and positive")
-        h = lib.cuddh_waveholtz_create(float(omega), _h(h_a), fem._h, scheme, coarsen, ratio, self.STIFFNESS.index(stiffness),
-                                       None if faces is None else _h(faces), -1 if faces is None else int(faces.size))
+        h = lib.cuddh_waveholtz_create_sweep(float(omega), _h(h_a), fem._h, scheme, coarsen, ratio, self.STIFFNESS.index(stiffness),
+                                             None if faces is None else _h(faces), -1 if faces is None else int(faces.size),
+                                             self.SWEEPS.index(sweep))
         if not h and N.last_error().startswith("WaveHoltz error"):
             raise ValueError(f"WaveHoltz: {N.last_error()}")
         super().__init__(N.handle(h, "WaveHoltz"), (fem,), 2 * fem.size())
@@ -779,7 +789,8 @@ class WaveHoltz(_Operator):
         buf = C.create_string_buffer(160)
         N.check_capi(lib.cuddh_waveholtz_info(self._h, _h(info), C.byref(dt), buf, 160), "WaveHoltz.info")
         return {"nt": int(info[0]), "dt": dt.value, "ratio": int(info[1]), "integrator": "rk4" if info[2] else "rk2", "coarsen": int(info[3]),
-                "sweeps_per_period": int(info[4]), "stiffness_kernel": buf.value.decode()}
+                "sweeps_per_period": int(info[4]), "stiffness_kernel": buf.value.decode(),
+                "sweep": self.SWEEPS[lib.cuddh_waveholtz_sweep(self._h)]}
 
     def solve(self, f, u, m: int = 20, maxit: int = 200, tol: float = 1e-6, orth: str = "mgs", augment: int = 0) -> "SolverOut":
         """rhs -> gmres from zero -> solution; u receives [Re U; Im U]"""

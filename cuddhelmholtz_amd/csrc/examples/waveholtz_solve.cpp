@@ -3,7 +3,8 @@
 //   options, anywhere on the line: --integrator rk2|rk4 --coarsen N (rk2 on the mesh grid is the default; rk4 marches
 //   ceil(nt / N) steps, N in [1, 16], 4 unless given), --time-ratio R|coefficient (the period's step count times R in [1, 256], or
 //   the ratio the coefficient asks for; 1 is the default), --stiffness gauss|lobatto (the sweep's quadrature, WaveHoltzOptions;
-//   gauss is the default), --coefficient one|disk (a == 1, the default, or the examples' disk of a = 0.2, projected as in
+//   gauss is the default), --sweep operator|lattice (lattice: one launch per sweep on the Gauss-Lobatto lattice; it implies
+//   --stiffness lobatto and refuses --stiffness gauss), --coefficient one|disk (a == 1, the default, or the examples' disk of a = 0.2, projected as in
 //   ddh_solve), --residuals (one more line: GMRES's residual history).
 // The load is the examples' pair of Gaussians in the real part and 0.1 (3 x^2 - 2 x y + y + 1) in the imaginary part.
 // Writes <out_dir>/xy.0000 and <out_dir>/waveholtz.0000 (raw fp64; "-": nothing) and prints one summary line.
@@ -20,7 +21,7 @@ using namespace cuddh;
 
 int main(int argc_all, char **argv_all)
 {
-    std::string integrator = "rk2", time_ratio = "1", stiffness = "gauss", coefficient = "one";
+    std::string integrator = "rk2", time_ratio = "1", stiffness = "", coefficient = "one", sweep = "operator";
     int coarsen = 0; // 0: not given
     bool residuals = false;
     std::vector<char *> args;
@@ -35,6 +36,8 @@ int main(int argc_all, char **argv_all)
             time_ratio = argv_all[++i];
         else if (arg == "--stiffness" && i + 1 < argc_all)
             stiffness = argv_all[++i];
+        else if (arg == "--sweep" && i + 1 < argc_all)
+            sweep = argv_all[++i];
         else if (arg == "--coefficient" && i + 1 < argc_all)
             coefficient = argv_all[++i];
         else if (arg == "--residuals")
@@ -58,6 +61,18 @@ int main(int argc_all, char **argv_all)
     if (time_ratio != "coefficient" && (ratio < 1 || ratio > DDHTimeStep::max_ratio))
     {
         std::cerr << "waveholtz_solve: --time-ratio takes coefficient or 1 to " << DDHTimeStep::max_ratio << ", not " << time_ratio << std::endl;
+        return 2;
+    }
+    if (sweep != "operator" && sweep != "lattice")
+    {
+        std::cerr << "waveholtz_solve: --sweep takes operator or lattice, not " << sweep << std::endl;
+        return 2;
+    }
+    if (stiffness.empty())
+        stiffness = sweep == "lattice" ? "lobatto" : "gauss";
+    if (sweep == "lattice" && stiffness != "lobatto")
+    {
+        std::cerr << "waveholtz_solve: --sweep lattice is the collocated stiffness: it goes with --stiffness lobatto only" << std::endl;
         return 2;
     }
     if (stiffness != "gauss" && stiffness != "lobatto")
@@ -110,6 +125,7 @@ int main(int argc_all, char **argv_all)
     opt.integrator = {integrator == "rk4" ? DDHIntegrator::rk4 : DDHIntegrator::rk2, coarsen};
     opt.time_ratio = ratio;
     opt.stiffness = stiffness == "lobatto" ? WaveHoltzOptions::lobatto : WaveHoltzOptions::gauss;
+    opt.sweep = sweep == "lattice" ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels;
     WaveHoltz W(omega, a.host_read(), fem, opt);
 
     // wall time of each phase with a device sync at both ends, as ddh_solve
@@ -139,7 +155,7 @@ int main(int argc_all, char **argv_all)
         unorm += h_U[i] * h_U[i];
     const double ms_per_period = out.num_matvec > 0 ? 1e3 * t_gmres / out.num_matvec : 0.0;
     std::cout << "waveholtz_solve nx=" << nx << " nb=" << nb << " omega/pi=" << omega / M_PI << " ndof=" << ndof << " integrator=" << integrator
-              << " coarsen=" << coarsen << " ratio=" << W.time_ratio() << " stiffness=" << stiffness << " coefficient=" << coefficient
+              << " coarsen=" << coarsen << " ratio=" << W.time_ratio() << " stiffness=" << stiffness << " sweep=" << sweep << " coefficient=" << coefficient
               << " nt=" << W.num_steps() << " sweeps_per_period=" << W.sweeps_per_period() << " success=" << out.success
               << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec << " rel_res=" << out.res_norm.back() / out.res_norm.front()
               << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs << " t_gmres=" << t_gmres << " ms_per_period=" << ms_per_period

@@ -25,6 +25,7 @@
 #include "cuddh/ddh.hpp"
 #include "cuddh/helmholtz.hpp"
 #include "cuddh/waveholtz.hpp"
+#include "cuddh/wave_lattice.hpp"
 #include "cuddh/multigpu.hpp"
 #include "cuddh/partition.hpp"
 

@@ -1,0 +1,45 @@
+// The lattice a uniform rectangle mesh's H1Space lives on, for the lattice sweeps of the whole-domain WaveHoltz solver
+// (waveholtz.hpp, csrc/kernels/wave_lattice.hip).  Plain host code: nothing here touches the device.
+//
+// A mesh qualifies when its elements are axis-aligned rectangles, congruent to 1e-12 of their size, and element e sits at
+// (e % nx, e / nx) of a grid (mesh.hpp's uniform_rect numbering), nx read off the first row.  The mesh is detected from its
+// corners, not described by the caller.  The dofs then form a lattice of Lx x Ly Gauss-Lobatto nodes, L = n (n_basis - 1) + 1,
+// and node (i, j) of element (ex, ey) is lattice node (ex (n_basis - 1) + i, ey (n_basis - 1) + j).
+#ifndef CUDDH_AMD_WAVE_LATTICE_HPP
+#define CUDDH_AMD_WAVE_LATTICE_HPP
+
+#include <vector>
+
+#include "spaces.hpp"
+
+namespace cuddh
+{
+    struct WaveLatticeMap
+    {
+        int nx = 0, ny = 0, n_basis = 0;
+        int Lx = 0, Ly = 0;
+        int stride = 0;           // doubles per lattice row: Lx rounded up to even (rows start on 16-byte boundaries)
+        double hx = 0.0, hy = 0.0;
+        std::vector<int> node_of; // dof -> I + Lx J, a bijection onto [0, Lx Ly)
+
+        int slots() const { return stride * Ly; }
+        /// dof -> slot I + stride J of the padded vectors
+        int slot_of(int dof) const { return node_of[dof] % Lx + stride * (node_of[dof] / Lx); }
+    };
+
+    /// From arrays alone: I (n_basis, n_basis, n_elem) element node -> dof; corners (2, 4, n_elem), the images of the reference
+    /// corners (-1,-1), (1,-1), (1,1), (-1,1); xy (2, ndof) collocation points and x (n_basis) the reference nodes in [-1, 1],
+    /// against which the local node order of the first and the last element is checked.  Verifies that the map is a bijection,
+    /// that shared nodes agree and that ndof, Lx Ly and stride Ly fit in an int.  Anything else is refused through cuddh_error
+    /// with a message that starts "WaveHoltz error: sweep:".
+    WaveLatticeMap build_wave_lattice_map(int ndof, int n_elem, int n_basis, const int *I, const double *corners, const double *xy, const double *x);
+
+    /// the same for a space (its coordinates are evaluated if they have not been)
+    WaveLatticeMap build_wave_lattice_map(const H1Space &fem);
+
+    /// the 1-D tables of the Kronecker form on the reference element [-1, 1]: A = D^T diag(w) D (row-major, n_basis x n_basis), D the
+    /// collocation derivative matrix, and the Gauss-Lobatto weights w
+    void wave_lattice_tables(const Basis &basis, double *A, double *w);
+} // namespace cuddh
+
+#endif

@@ -6,6 +6,9 @@
 //     W.rhs(f, b); gmres(W.size(), z, &W, b, m, maxit, tol); W.solution(z, u);
 // Its iteration count does not depend on a decomposition; it is NOT a check of DDH's fixed point, which reads the global load in
 // every subdomain and is another discrete problem (tests/helmholtz_direct.py).
+// sweep = lattice (opt-in; collocated stiffness on a uniform rectangle mesh only): the state lives in lattice order and ONE launch
+// per sweep does the stiffness stencil and the stage (csrc/kernels/wave_lattice.hip); no StiffnessMatrix is built.  z, f and
+// every public vector keep the space's dof order: a period permutes them in and out.
 // Everything is fp64; all vectors are DEVICE pointers unless marked HOST.
 #ifndef CUDDH_AMD_WAVEHOLTZ_HPP
 #define CUDDH_AMD_WAVEHOLTZ_HPP
@@ -38,6 +41,15 @@ namespace cuddh
             lobatto
         };
         Stiffness stiffness = gauss;
+        /// operator_kernels (the default): a stiffness apply and a stage kernel per sweep.  lattice: one launch per sweep on
+        /// lattice-ordered vectors; needs stiffness = lobatto and a uniform rectangle mesh (detected: cuddh/wave_lattice.hpp),
+        /// anything else is refused ("WaveHoltz error: sweep: ...") before any allocation
+        enum Sweep
+        {
+            operator_kernels,
+            lattice
+        };
+        Sweep sweep = operator_kernels;
         /// absorbing faces: HOST edge ids; n_faces < 0 (the default): every boundary edge, DDH's choice
         const int *h_faces = nullptr;
         int n_faces = -1;
@@ -75,18 +87,24 @@ namespace cuddh
         int time_ratio() const { return ratio; }
         DDHIntegrator integrator() const { return scheme; }
         int sweeps_per_period() const { return nt * (scheme.scheme == DDHIntegrator::rk4 ? 4 : 2); }
-        /// kernel the stiffness sweep launches (after the first period; "generic" = element_ops.hip)
-        std::string stiffness_kernel() const { return K->kernel_name(); }
+        /// kernel the stiffness sweep launches (after the first period; "generic" = element_ops.hip); the lattice form names its
+        /// kernel and n_basis
+        std::string stiffness_kernel() const;
+        WaveHoltzOptions::Sweep sweep() const { return lat ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels; }
 
     private:
+        struct Lattice; // the lattice form's description, maps and second ps (waveholtz.cpp)
+        void lattice_period(const double *z_in, const double *f, double *z_out) const;
+
         const double omega;
         const int ndof;
         DDHIntegrator scheme;
         int nt = 0, ratio = 1;
         double dt = 0.0;
         std::vector<double> filt, cs, sn; // HOST tables of the period's grid: filter (nt + 1), cs and sn (2 nt + 1)
-        std::unique_ptr<StiffnessMatrix> K;
-        host_device_dvec invm, Hi;        // 1 / (a^2 m) and h a (zero off the absorbing faces), ndof each
+        std::unique_ptr<StiffnessMatrix> K; // null in the lattice form
+        std::unique_ptr<Lattice> lat;       // null in the operator form
+        host_device_dvec invm, Hi;        // 1 / (a^2 m) and h a (zero off the absorbing faces), ndof each (lattice form: its slots)
         // the march's state and stage vectors (each 16-byte aligned whatever ndof is, so that the stages take their 16-byte path)
         mutable host_device_dvec w, p, q, u, v, ps, qs, aq, ap, F, G, tmp;
     };

@@ -18,137 +18,16 @@
 // Access pattern: blas1.hip's (contiguous tiles of 16-byte vectors taken in order by the workgroups, clamped requests issued
 // before any result is stored, non-temporal beyond the infinity cache); with up to twelve input streams a tile is two vectors
 // per thread and stream.  When any pointer is not 16-byte aligned the whole launch goes element by element.
-#include "common.hpp"
+#include "wave_stages.hpp"
 
 using namespace cuddh_k;
+using namespace cuddh_k::wave; // the stages and fq
 
 namespace
 {
     constexpr int BLOCK = 256;
     constexpr int UNROLL = 2;
     constexpr int TILE = UNROLL * BLOCK; // 16-byte vectors per tile
-    constexpr long long NT_BYTES = 64LL << 20;
-    constexpr int MAX_IN = 12, MAX_OUT = 4, MAX_COEF = 4;
-
-    using V2 = double __attribute__((ext_vector_type(2)));
-
-    struct StageArgs
-    {
-        const double *in[MAX_IN];
-        double *out[MAX_OUT]; // may alias inputs (element i is read before it is written, by the same thread)
-        double coef[MAX_COEF];
-    };
-
-    __device__ inline double fmadd(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-    // invm * (w - Hi q + c F + s G); fg points at (F, G) of this element
-    template <bool FORCED>
-    __device__ inline double fq(double w, double q, double invm, double Hi, const double *fg, double c, double s)
-    {
-        double r = fmadd(-Hi, q, w);
-        if constexpr (FORCED)
-        {
-            r = fmadd(c, fg[0], r);
-            r = fmadd(s, fg[1], r);
-        }
-        return invm * r;
-    }
-
-    // A stage: NIN inputs besides (F, G), which follow them when FORCED; NOUT outputs; apply() on one element.
-    struct Begin
-    {
-        static constexpr int NIN = 2, NOUT = 4; // in: zu zv; out: p q u v; coef: filt0
-        template <bool FORCED>
-        __device__ static void apply(const double *x, double *y, const double *k)
-        {
-            y[0] = x[0];
-            y[1] = x[1];
-            y[2] = k[0] * x[0];
-            y[3] = k[0] * x[1];
-        }
-    };
-    struct Rk2A
-    {
-        static constexpr int NIN = 5, NOUT = 2; // in: w p q invm Hi; out: qh ph; coef: dt/2 c s
-        template <bool FORCED>
-        __device__ static void apply(const double *x, double *y, const double *k)
-        {
-            y[0] = fmadd(k[0], fq<FORCED>(x[0], x[2], x[3], x[4], x + NIN, k[1], k[2]), x[2]);
-            y[1] = fmadd(-k[0], x[2], x[1]);
-        }
-    };
-    struct Rk2B
-    {
-        static constexpr int NIN = 8, NOUT = 4; // in: w qh p q u v invm Hi; out: p q u v; coef: dt c s filt
-        template <bool FORCED>
-        __device__ static void apply(const double *x, double *y, const double *k)
-        {
-            const double p = fmadd(-k[0], x[1], x[2]);
-            const double q = fmadd(k[0], fq<FORCED>(x[0], x[1], x[6], x[7], x + NIN, k[1], k[2]), x[3]);
-            y[0] = p;
-            y[1] = q;
-            y[2] = fmadd(k[3], p, x[4]);
-            y[3] = fmadd(k[3], q, x[5]);
-        }
-    };
-    struct Rk4First
-    {
-        static constexpr int NIN = 5, NOUT = 4; // in: w p q invm Hi; out: ps qs aq ap; coef: dt/2 c s
-        template <bool FORCED>
-        __device__ static void apply(const double *x, double *y, const double *k)
-        {
-            const double kq = fq<FORCED>(x[0], x[2], x[3], x[4], x + NIN, k[1], k[2]);
-            y[0] = fmadd(-k[0], x[2], x[1]);
-            y[1] = fmadd(k[0], kq, x[2]);
-            y[2] = kq;
-            y[3] = -x[2];
-        }
-    };
-    struct Rk4Mid
-    {
-        static constexpr int NIN = 8, NOUT = 4; // in: w p q qs aq ap invm Hi; out: ps qs aq ap; coef: h c s  (h = dt/2, then dt)
-        template <bool FORCED>
-        __device__ static void apply(const double *x, double *y, const double *k)
-        {
-            const double kq = fq<FORCED>(x[0], x[3], x[6], x[7], x + NIN, k[1], k[2]);
-            y[0] = fmadd(-k[0], x[3], x[1]);
-            y[1] = fmadd(k[0], kq, x[2]);
-            y[2] = fmadd(2.0, kq, x[4]);
-            y[3] = fmadd(-2.0, x[3], x[5]);
-        }
-    };
-    struct Rk4Last
-    {
-        static constexpr int NIN = 10, NOUT = 4; // in: w p q qs aq ap u v invm Hi; out: p q u v; coef: dt/6 c s filt
-        template <bool FORCED>
-        __device__ static void apply(const double *x, double *y, const double *k)
-        {
-            const double kq = fq<FORCED>(x[0], x[3], x[8], x[9], x + NIN, k[1], k[2]);
-            const double p = fmadd(k[0], x[5] - x[3], x[1]);
-            const double q = fmadd(k[0], x[4] + kq, x[2]);
-            y[0] = p;
-            y[1] = q;
-            y[2] = fmadd(k[3], p, x[6]);
-            y[3] = fmadd(k[3], q, x[7]);
-        }
-    };
-
-    template <bool NT>
-    __device__ inline V2 stream_load(const V2 *p)
-    {
-        if constexpr (NT)
-            return __builtin_nontemporal_load(p);
-        else
-            return *p;
-    }
-    template <bool NT>
-    __device__ inline void stream_store(V2 *p, const V2 &v)
-    {
-        if constexpr (NT)
-            __builtin_nontemporal_store(v, p);
-        else
-            *p = v;
-    }
 
     template <typename Stage, bool FORCED, bool NT>
     __global__ void __launch_bounds__(BLOCK) stage_kernel(int n, StageArgs a, int vectorised)
@@ -212,8 +91,6 @@ namespace
                 a.out[s][i] = ye[s];
         }
     }
-
-    inline bool aligned16(const void *p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
     // in: the stage's inputs in its order; F, G: both given (forced) or both null (homogeneous)
     template <typename Stage>

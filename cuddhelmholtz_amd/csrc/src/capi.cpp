@@ -543,8 +543,15 @@ extern "C"
     void *cuddh_waveholtz_create(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
                                  const int *h_faces, int n_faces)
     {
+        return cuddh_waveholtz_create_sweep(omega, h_a, fem, integrator, coarsen, time_ratio, stiffness, h_faces, n_faces, 0);
+    }
+    void *cuddh_waveholtz_create_sweep(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                       const int *h_faces, int n_faces, int sweep)
+    {
         return guarded_new<OpHandle>([&]
         {
+            if (sweep != 0 && sweep != 1)
+                throw std::runtime_error("WaveHoltz error: sweep: the form must be 0 (operator kernels) or 1 (lattice), not " + std::to_string(sweep) + ".");
             if (integrator != 0 && integrator != 1)
                 throw std::runtime_error("WaveHoltz error: integrator: the scheme must be 0 (rk2) or 1 (rk4), not " + std::to_string(integrator) + ".");
             if (stiffness != 0 && stiffness != 1)
@@ -555,6 +562,7 @@ extern "C"
             o.stiffness = stiffness == 1 ? WaveHoltzOptions::lobatto : WaveHoltzOptions::gauss;
             o.h_faces = h_faces;
             o.n_faces = n_faces;
+            o.sweep = sweep == 1 ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels;
             auto h = new OpHandle;
             h->op.reset(new WaveHoltz(omega, h_a, *static_cast<H1Space *>(fem), o));
             return h;
@@ -594,6 +602,34 @@ extern "C"
             if (kernel && cap > 0)
                 std::snprintf(kernel, cap, "%s", W.stiffness_kernel().c_str());
         });
+    }
+
+    int cuddh_waveholtz_sweep(void *op)
+    {
+        int form = -1;
+        guarded([&] { form = waveholtz_of(op).sweep() == WaveHoltzOptions::lattice ? 1 : 0; });
+        return form;
+    }
+    int cuddh_wave_lattice_map(void *fem, int *h_dims, double *h_h, int *h_node_of)
+    {
+        return guarded([&]
+        {
+            const WaveLatticeMap map = build_wave_lattice_map(*static_cast<H1Space *>(fem));
+            const int dims[5] = {map.nx, map.ny, map.Lx, map.Ly, map.stride};
+            if (h_dims)
+                std::copy(dims, dims + 5, h_dims);
+            if (h_h)
+            {
+                h_h[0] = map.hx;
+                h_h[1] = map.hy;
+            }
+            if (h_node_of)
+                std::copy(map.node_of.begin(), map.node_of.end(), h_node_of);
+        });
+    }
+    int cuddh_wave_lattice_tables(void *basis, double *h_A, double *h_w)
+    {
+        return guarded([&] { wave_lattice_tables(*static_cast<Basis *>(basis), h_A, h_w); });
     }
 
     int cuddh_helmholtz_read_stamps(void *op, unsigned long long *h_out, int n_patches)

@@ -1,0 +1,144 @@
+// Detection of the lattice behind a uniform rectangle mesh: see cuddh/wave_lattice.hpp.  Plain C++: nothing here touches the device.
+#include "cuddh/wave_lattice.hpp"
+
+#include <algorithm>
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <string>
+
+namespace cuddh
+{
+    namespace
+    {
+        [[noreturn]] void refuse(const std::string &why)
+        {
+            cuddh_error(("WaveHoltz error: sweep: the lattice form needs a uniform rectangle mesh (Mesh2D::uniform_rect's numbering); " + why).c_str());
+            throw std::logic_error("unreachable");
+        }
+    } // namespace
+
+    WaveLatticeMap build_wave_lattice_map(int ndof, int n_elem, int nb, const int *I, const double *corners, const double *xy, const double *x)
+    {
+        if (ndof < 1 || n_elem < 1 || nb < 2 || !I || !corners || !xy || !x)
+            refuse("the space is empty or an array is missing.");
+        auto cx = [&](int e, int c) { return corners[2 * (c + 4 * e)]; };
+        auto cy = [&](int e, int c) { return corners[2 * (c + 4 * e) + 1]; };
+
+        WaveLatticeMap L;
+        L.n_basis = nb;
+        const double x0 = cx(0, 0), y0 = cy(0, 0);
+        L.hx = cx(0, 1) - x0;
+        L.hy = cy(0, 3) - y0;
+        if (!(L.hx > 0.0) || !(L.hy > 0.0) || !std::isfinite(L.hx) || !std::isfinite(L.hy))
+            refuse("element 0 does not run from its first corner to the right and upwards.");
+        double big = 0.0; // the largest coordinate, for the rounding of the corners themselves
+        for (int i = 0; i < 8 * n_elem; ++i)
+            big = std::max(big, std::fabs(corners[i]));
+        const double tol = 1e-12 * std::min(L.hx, L.hy) + 8.0 * DBL_EPSILON * big;
+        auto near = [&](double a, double b) { return std::fabs(a - b) <= tol; }; // (false for a NaN)
+
+        // nx: the elements of the first row
+        int nx = 1;
+        while (nx < n_elem && near(cy(nx, 0), y0) && near(cx(nx, 0), x0 + nx * L.hx))
+            ++nx;
+        if (n_elem % nx != 0)
+            refuse(std::to_string(n_elem) + " elements do not fill rows of " + std::to_string(nx) + ".");
+        const int ny = n_elem / nx;
+        L.nx = nx;
+        L.ny = ny;
+        for (int e = 0; e < n_elem; ++e)
+        {
+            const double ax = x0 + (e % nx) * L.hx, ay = y0 + (e / nx) * L.hy;
+            const double want[4][2] = {{ax, ay}, {ax + L.hx, ay}, {ax + L.hx, ay + L.hy}, {ax, ay + L.hy}};
+            for (int c = 0; c < 4; ++c)
+                if (!near(cx(e, c), want[c][0]) || !near(cy(e, c), want[c][1]))
+                    refuse("corner " + std::to_string(c) + " of element " + std::to_string(e) + " is not where cell (" + std::to_string(e % nx) + ", " +
+                           std::to_string(e / nx) + ") of a " + std::to_string(nx) + " x " + std::to_string(ny) + " grid has it.");
+        }
+
+        const int H = nb - 1;
+        const long long Lx = static_cast<long long>(nx) * H + 1, Ly = static_cast<long long>(ny) * H + 1, stride = Lx + (Lx & 1);
+        if (Lx * Ly > INT_MAX || stride * Ly > INT_MAX)
+            refuse("its " + std::to_string(Lx) + " x " + std::to_string(Ly) + " nodes do not fit a 32-bit index.");
+        if (Lx * Ly != ndof)
+            refuse("the space has " + std::to_string(ndof) + " dofs, the lattice " + std::to_string(Lx * Ly) + " nodes.");
+        L.Lx = static_cast<int>(Lx);
+        L.Ly = static_cast<int>(Ly);
+        L.stride = static_cast<int>(stride);
+
+        // dof -> node, from the element positions; the nodes neighbouring elements share must agree
+        L.node_of.assign(ndof, -1);
+        for (int e = 0; e < n_elem; ++e)
+            for (int j = 0; j < nb; ++j)
+                for (int i = 0; i < nb; ++i)
+                {
+                    const int g = I[i + nb * (j + nb * e)];
+                    if (g < 0 || g >= ndof)
+                        refuse("a global index lies outside the space.");
+                    const int node = (e % nx) * H + i + L.Lx * ((e / nx) * H + j);
+                    if (L.node_of[g] >= 0 && L.node_of[g] != node)
+                        refuse("dof " + std::to_string(g) + " is shared by element nodes that are not the same lattice node.");
+                    L.node_of[g] = node;
+                }
+        std::vector<char> taken(ndof, 0);
+        for (int g = 0; g < ndof; ++g)
+        {
+            if (L.node_of[g] < 0)
+                refuse("dof " + std::to_string(g) + " belongs to no element.");
+            if (taken[L.node_of[g]])
+                refuse("two dofs are the same lattice node.");
+            taken[L.node_of[g]] = 1;
+        }
+
+        // the local node order: node (i, j) of an element is its point (x[i], x[j]), i along x
+        for (const int e : {0, n_elem - 1})
+            for (int j = 0; j < nb; ++j)
+                for (int i = 0; i < nb; ++i)
+                {
+                    const int g = I[i + nb * (j + nb * e)];
+                    const double px = x0 + (e % nx) * L.hx + 0.5 * (x[i] + 1.0) * L.hx, py = y0 + (e / nx) * L.hy + 0.5 * (x[j] + 1.0) * L.hy;
+                    if (!near(xy[2 * g], px) || !near(xy[2 * g + 1], py))
+                        refuse("node (" + std::to_string(i) + ", " + std::to_string(j) + ") of element " + std::to_string(e) +
+                               " is not at the collocation point the lattice gives it.");
+                }
+        return L;
+    }
+
+    WaveLatticeMap build_wave_lattice_map(const H1Space &fem)
+    {
+        const Mesh2D &mesh = fem.mesh();
+        const int n_elem = mesh.n_elem(), nb = fem.basis().size();
+        std::vector<double> corners(8 * static_cast<std::size_t>(n_elem)), x(nb);
+        static const double ref[4][2] = {{-1.0, -1.0}, {1.0, -1.0}, {1.0, 1.0}, {-1.0, 1.0}};
+        for (int e = 0; e < n_elem; ++e)
+            for (int c = 0; c < 4; ++c)
+                mesh.element(e)->physical_coordinates(ref[c], corners.data() + 2 * (c + 4 * static_cast<std::size_t>(e)));
+        for (int i = 0; i < nb; ++i)
+            x[i] = fem.basis().quadrature().x(i);
+        const int *I = fem.global_indices(MemorySpace::HOST);
+        const double *xy = fem.physical_coordinates(MemorySpace::HOST);
+        return build_wave_lattice_map(fem.size(), n_elem, nb, I, corners.data(), xy, x.data());
+    }
+
+    void wave_lattice_tables(const Basis &basis, double *A, double *w)
+    {
+        const int n = basis.size();
+        const QuadratureRule &gll = basis.quadrature();
+        std::vector<double> x(n), D(static_cast<std::size_t>(n) * n);
+        for (int i = 0; i < n; ++i)
+        {
+            x[i] = gll.x(i);
+            w[i] = gll.w(i);
+        }
+        basis.deriv(n, x.data(), D.data()); // D[q + n j] = phi_j'(x_q)
+        for (int k = 0; k < n; ++k)
+            for (int j = 0; j < n; ++j)
+            {
+                double s = 0.0;
+                for (int q = 0; q < n; ++q)
+                    s += w[q] * D[q + n * k] * D[q + n * j];
+                A[k * n + j] = s;
+            }
+    }
+} // namespace cuddh

@@ -1,11 +1,14 @@
 // Whole-domain WaveHoltz (cuddh/waveholtz.hpp): set-up on the host, the march as stiffness applies and the stage kernels of
-// csrc/kernels/waveholtz.hip (cuddh_hip_wave_stage_*), one launch of each per sweep.
+// csrc/kernels/waveholtz.hip (cuddh_hip_wave_stage_*), one launch of each per sweep; or, in the lattice form, as the kernels of
+// csrc/kernels/wave_lattice.hip (cuddh_hip_wave_lattice_*), one launch per sweep on lattice-ordered vectors.
 #include "cuddh/waveholtz.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <string>
 
 #include "cuddh/time_grid.hpp"
+#include "cuddh/wave_lattice.hpp"
 #include "cuddh_hip.h"
 
 namespace cuddh
@@ -30,6 +33,10 @@ namespace cuddh
                 cuddh_error("WaveHoltz error: stiffness: the rule must be gauss or lobatto.");
             if (o.n_faces > 0 && !o.h_faces)
                 cuddh_error("WaveHoltz error: faces: a list of absorbing faces was announced and none given.");
+            if (o.sweep != WaveHoltzOptions::operator_kernels && o.sweep != WaveHoltzOptions::lattice)
+                cuddh_error("WaveHoltz error: sweep: the form must be operator_kernels or lattice.");
+            if (o.sweep == WaveHoltzOptions::lattice && o.stiffness != WaveHoltzOptions::lobatto)
+                cuddh_error("WaveHoltz error: sweep: the lattice form is the collocated stiffness; it needs stiffness = lobatto.");
         }
 
         host_device_dvec rule_weights(const QuadratureRule &quad)
@@ -41,6 +48,14 @@ namespace cuddh
             return w;
         }
     } // namespace
+
+    struct WaveHoltz::Lattice
+    {
+        cuddh_wave_lattice desc = {};
+        int slots = 0;                              // doubles per lattice vector: stride * Ly
+        host_device_ivec dof_of_slot, slot_of_dof;  // slots (-1: padding) and ndof
+        mutable host_device_dvec ps2;               // rk4_2 and rk4_3 read the stencil of one ps and write the other
+    };
 
     WaveHoltz::WaveHoltz(double omega_, const double *h_a, const H1Space &fem, const WaveHoltzOptions &o)
         : omega(omega_), ndof(fem.size()), scheme(o.integrator), invm(fem.size()), Hi(fem.size())
@@ -64,6 +79,32 @@ namespace cuddh
             ratio = detail::ratio_from_coefficient(a_min);
         }
 
+        // ---- the lattice form: the mesh is detected (and refused) before anything is allocated
+        if (o.sweep == WaveHoltzOptions::lattice)
+        {
+            if (fem.basis().size() > 8)
+                cuddh_error("WaveHoltz error: sweep: the lattice kernels take n_basis up to 8.");
+            const WaveLatticeMap map = build_wave_lattice_map(fem);
+            lat.reset(new Lattice);
+            lat->desc.nx = map.nx;
+            lat->desc.ny = map.ny;
+            lat->desc.n_basis = map.n_basis;
+            lat->desc.stride = map.stride;
+            lat->desc.cx = map.hy / map.hx;
+            lat->desc.cy = map.hx / map.hy;
+            wave_lattice_tables(fem.basis(), lat->desc.A, lat->desc.w);
+            lat->slots = map.slots();
+            lat->dof_of_slot.resize(lat->slots);
+            lat->slot_of_dof.resize(ndof);
+            int *dos = lat->dof_of_slot.host_write(), *sod = lat->slot_of_dof.host_write();
+            std::fill(dos, dos + lat->slots, -1);
+            for (int g = 0; g < ndof; ++g)
+            {
+                sod[g] = map.slot_of(g);
+                dos[sod[g]] = g;
+            }
+        }
+
         // ---- the period's grid
         const int nb = fem.basis().size();
         nt = ratio * detail::coarsened_steps(detail::mesh_grid_steps(omega, fem.mesh().min_h(), nb), scheme.coarsen);
@@ -74,7 +115,11 @@ namespace cuddh
         detail::fill_time_grid(omega, nt, dt, filt.data(), cs.data(), sn.data());
 
         // ---- the sweep
-        if (o.stiffness == WaveHoltzOptions::lobatto)
+        if (lat)
+        {
+            // the stencil of wave_lattice.hip: no operator, no metric table
+        }
+        else if (o.stiffness == WaveHoltzOptions::lobatto)
             K.reset(new StiffnessMatrix(fem, fem.basis().quadrature()));
         else
             K.reset(new StiffnessMatrix(fem));
@@ -131,20 +176,104 @@ namespace cuddh
         detail::check_hip(cuddh_hip_stream_sync(stream()), "WaveHoltz setup"); // a2 and wts die here
 
         const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
-        for (host_device_dvec *x : {&w, &p, &q, &u, &v, &ps, &qs})
-            x->resize(ndof);
+        int nvec = ndof;
+        if (lat)
+        {
+            // invm and Hi into lattice order; the padding slots get zero
+            nvec = lat->slots;
+            const int *dos = lat->dof_of_slot.device_read();
+            for (host_device_dvec *x : {&invm, &Hi})
+            {
+                host_device_dvec t(nvec);
+                detail::check_hip(cuddh_hip_wave_lattice_gather_f64(nvec, dos, x->device_read(), t.device_write(), stream()), "WaveHoltz lattice order");
+                detail::check_hip(cuddh_hip_stream_sync(stream()), "WaveHoltz setup"); // the dof-ordered vector dies here
+                *x = std::move(t);
+            }
+            lat->slot_of_dof.device_read();
+            if (rk4)
+                lat->ps2.resize(nvec);
+        }
+        else
+            w.resize(ndof);
+        for (host_device_dvec *x : {&p, &q, &u, &v, &ps, &qs})
+            x->resize(nvec);
         tmp.resize(2 * ndof);
         if (rk4)
         {
-            aq.resize(ndof);
-            ap.resize(ndof);
+            aq.resize(nvec);
+            ap.resize(nvec);
         }
     }
 
     WaveHoltz::~WaveHoltz() = default;
 
+    std::string WaveHoltz::stiffness_kernel() const
+    {
+        if (!lat)
+            return K->kernel_name();
+        const int nb = lat->desc.n_basis;
+        return "wave_lattice nb" + std::to_string(nb) + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
+    }
+
+    void WaveHoltz::lattice_period(const double *z_in, const double *f, double *z_out) const
+    {
+        const int n = lat->slots;
+        const cuddh_wave_lattice *D = &lat->desc;
+        const char *what = "WaveHoltz::period (lattice)";
+        void *st = stream();
+        const int *dos = lat->dof_of_slot.device_read();
+        double *P = p.device_write(), *Q = q.device_write(), *U = u.device_write(), *V = v.device_write();
+        double *PS = ps.device_write(), *QS = qs.device_write();
+        const double *IM = invm.device_read(), *HI = Hi.device_read();
+        const double *Ff = nullptr, *Gf = nullptr;
+        if (f)
+        {
+            if (F.size() != n)
+            {
+                F.resize(n);
+                G.resize(n);
+            }
+            double *dF = F.device_write(), *dG = G.device_write();
+            detail::check_hip(cuddh_hip_wave_lattice_gather_f64(n, dos, f, dF, st), what);
+            detail::check_hip(cuddh_hip_wave_lattice_gather_f64(n, dos, f + ndof, dG, st), what);
+            Ff = dF;
+            Gf = dG;
+        }
+        if (z_in)
+            detail::check_hip(cuddh_hip_wave_lattice_begin_f64(n, filt[0], dos, z_in, z_in + ndof, P, Q, U, V, st), what);
+        else
+            for (double *x : {P, Q, U, V})
+                zeros(n, x);
+
+        if (scheme.scheme == DDHIntegrator::rk2)
+        {
+            for (int it = 1; it <= nt; ++it)
+            {
+                detail::check_hip(cuddh_hip_wave_lattice_rk2_a_f64(D, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
+                detail::check_hip(cuddh_hip_wave_lattice_rk2_b_f64(D, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+            }
+        }
+        else
+        {
+            double *AQ = aq.device_write(), *AP = ap.device_write(), *PS2 = lat->ps2.device_write();
+            for (int it = 1; it <= nt; ++it)
+            {
+                const int k = 2 * it - 2;
+                detail::check_hip(cuddh_hip_wave_lattice_rk4_1_f64(D, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                detail::check_hip(cuddh_hip_wave_lattice_rk4_2_f64(D, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
+                detail::check_hip(cuddh_hip_wave_lattice_rk4_3_f64(D, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                detail::check_hip(cuddh_hip_wave_lattice_rk4_4_f64(D, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+            }
+        }
+        const int *sod = lat->slot_of_dof.device_read();
+        detail::check_hip(cuddh_hip_gather_f64(ndof, sod, U, z_out, st), what);
+        detail::check_hip(cuddh_hip_gather_f64(ndof, sod, V, z_out + ndof, st), what);
+    }
+
     void WaveHoltz::period(const double *z_in, const double *f, double *z_out) const
     {
+        if (lat)
+            return lattice_period(z_in, f, z_out);
         const int n = ndof;
         void *st = stream();
         double *W = w.device_write(), *P = p.device_write(), *Q = q.device_write(), *U = u.device_write(), *V = v.device_write();

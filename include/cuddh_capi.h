@@ -319,6 +319,25 @@ int cuddh_waveholtz_solution(void *op, const double *z, double *u);
 /* h_info = {nt, time ratio, integrator, coarsen, sweeps per period, ndof}; *h_dt = time step; kernel (cap bytes, may be NULL):
  * the kernel of the stiffness sweep, "generic" before the first period.  Returns 0, nonzero on error. */
 int cuddh_waveholtz_info(void *op, int *h_info, double *h_dt, char *kernel, int cap);
+/* cuddh_waveholtz_create with the form of the sweep behind its arguments: 0 = a stiffness apply and a stage kernel per sweep (what
+ * cuddh_waveholtz_create builds), 1 = lattice: one launch per sweep does the stiffness stencil and the stage on lattice-ordered
+ * vectors (cuddh_hip_wave_lattice_*).  The lattice form needs stiffness = 1 and a uniform rectangle mesh, which is
+ * detected (cuddh_wave_lattice_map); anything else is refused before anything is allocated, the message starts with
+ * "WaveHoltz error: sweep:".  Every entry point above takes the handle unchanged: z, f and u keep the space's dof order.  In
+ * that form cuddh_waveholtz_info's kernel is "wave_lattice nb<n_basis>". */
+void *cuddh_waveholtz_create_sweep(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                   const int *h_faces, int n_faces, int sweep);
+/* the form of the sweep: 0 or 1 as above, -1 when op is not a WaveHoltz handle */
+int cuddh_waveholtz_sweep(void *op);
+/* The lattice behind a space on a uniform rectangle mesh (csrc/include/cuddh/wave_lattice.hpp; host code, no device is touched):
+ * h_dims = {nx, ny, Lx, Ly, stride}, L = n (n_basis - 1) + 1 nodes per direction and stride = Lx rounded up to even, the doubles
+ * per row of the lattice vectors; h_h = {hx, hy}; h_node_of (ndof): dof -> I + Lx J.  Each may be NULL.  The mesh qualifies when
+ * its elements are axis-aligned rectangles, congruent to 1e-12 of their size, with element e at (e % nx, e / nx); the map is
+ * verified to be a bijection that agrees on shared nodes and with the collocation points.  Returns 0, or nonzero with
+ * cuddh_last_error() beginning "WaveHoltz error: sweep:". */
+int cuddh_wave_lattice_map(void *fem, int *h_dims, double *h_h, int *h_node_of);
+/* the 1-D tables of the lattice form on the reference element: h_A (n_basis x n_basis, row-major) = D^T diag(w) D, h_w (n_basis) */
+int cuddh_wave_lattice_tables(void *basis, double *h_A, double *h_w);
 
 #ifdef __cplusplus
 }

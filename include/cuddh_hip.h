@@ -581,6 +581,57 @@ int cuddh_hip_wave_stage_rk4_4_f64(int n, double sixth_dt, double c, double s, d
                                    const double *aq, const double *ap, const double *invm, const double *Hi, const double *F,
                                    const double *G, double *p, double *q, double *u, double *v, void *stream);
 
+/* ------------------------------------------------------------------ whole-domain WaveHoltz march: lattice sweeps
+ * csrc/kernels/wave_lattice.hip, DESIGN 4.5.  On a uniform rectangle mesh of nx x ny elements the collocated stiffness is
+ *     K = cx diag(Wy) (x) Ax + cy Ay (x) diag(Wx)        on the lattice of Lx x Ly nodes, L = n (n_basis - 1) + 1,
+ * Ax, Ay: the 1-D element matrix A assembled along a row of elements that overlap in one node, Wx, Wy: the weights w assembled
+ * the same way.  One launch computes w = K p' at every node AND does the stage above: the entry points are the stages' with the
+ * stencil's input p' in the place of w (rk2_a and rk4_1 read p once: it is both), and n replaced by the lattice.
+ *
+ * Vectors hold node (I, J) at I + stride J and have stride * Ly doubles; stride >= Lx and even, every pointer 16-byte aligned.
+ * The columns from Lx on are padding: the caller keeps zero state, zero load and invm = 0 there, the kernels keep them zero and
+ * the stencil never reads them.  (K p')(I, J) = fma(cx Wy(J), sx, (cy Wx(I)) sy), where sx = sum_d Tx(I, d) p'(I + d, J) and
+ * sy = sum_d Ty(J, d) p'(I, J + d) run from zero over ascending d by fused multiply-adds.  With H = n_basis - 1 and k = I mod H:
+ * an element-interior node takes d in [-k, H - k] with A[k][k + d]; an element-boundary node d in [-H, H] with A[H][H + d] for
+ * d < 0, A[H][H] + A[0][0] for d = 0 and A[0][d] for d > 0; the first and the last node of a line only the side that exists.
+ * W is w[k], w[H] + w[0] where two elements meet, w[0] / w[H] at the two ends.  The order depends on (I, J) alone: results are
+ * bitwise reproducible, and exact for integer tables.  A is row-major and need not be symmetric.
+ * The stencil's input must not be an output (rk4_2 and rk4_3 therefore take ps_in and ps_out); the other inputs may be updated
+ * in place as in the stage kernels.  A bad description, a misaligned or NULL pointer, F without G or an output that is the
+ * stencil's input return hipErrorInvalidValue (1) and nothing is launched. */
+typedef struct cuddh_wave_lattice
+{
+    int nx, ny, n_basis, stride; /* n_basis in [2, 8] */
+    double cx, cy;               /* hy / hx, hx / hy */
+    double A[64], w[8];          /* HOST tables: A[k * n_basis + j], w[k] */
+} cuddh_wave_lattice;
+int cuddh_hip_wave_lattice_rk2_a_f64(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const double *p, const double *q,
+                                     const double *invm, const double *Hi, const double *F, const double *G, double *qh, double *ph,
+                                     void *stream);
+int cuddh_hip_wave_lattice_rk2_b_f64(const cuddh_wave_lattice *lattice, double dt, double c, double s, double filt, const double *ph,
+                                     const double *qh, const double *invm, const double *Hi, const double *F, const double *G, double *p,
+                                     double *q, double *u, double *v, void *stream);
+int cuddh_hip_wave_lattice_rk4_1_f64(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const double *p, const double *q,
+                                     const double *invm, const double *Hi, const double *F, const double *G, double *ps, double *qs,
+                                     double *aq, double *ap, void *stream);
+int cuddh_hip_wave_lattice_rk4_2_f64(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const double *ps_in,
+                                     const double *p, const double *q, const double *invm, const double *Hi, const double *F,
+                                     const double *G, double *ps_out, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_lattice_rk4_3_f64(const cuddh_wave_lattice *lattice, double dt, double c, double s, const double *ps_in, const double *p,
+                                     const double *q, const double *invm, const double *Hi, const double *F, const double *G,
+                                     double *ps_out, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_lattice_rk4_4_f64(const cuddh_wave_lattice *lattice, double sixth_dt, double c, double s, double filt, const double *ps,
+                                     const double *qs, const double *aq, const double *ap, const double *invm, const double *Hi,
+                                     const double *F, const double *G, double *p, double *q, double *u, double *v, void *stream);
+/* into lattice order: y[i] = x[dof_of_slot[i]], 0 where dof_of_slot[i] < 0 (padding), i < n; begin is the stage `begin` on the
+ * gathered zu, zv */
+int cuddh_hip_wave_lattice_gather_f64(int n, const int *dof_of_slot, const double *x, double *y, void *stream);
+int cuddh_hip_wave_lattice_begin_f64(int n, double filt0, const int *dof_of_slot, const double *zu, const double *zv, double *p, double *q,
+                                     double *u, double *v, void *stream);
+/* nodes of a workgroup's tile in x and y (the sizes at which the kernels' paths change) */
+int cuddh_hip_wave_lattice_tile_x(void);
+int cuddh_hip_wave_lattice_tile_y(void);
+
 #ifdef __cplusplus
 }
 #endif

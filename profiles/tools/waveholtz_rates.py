@@ -11,6 +11,13 @@ solve    one whole solve per size in the example's regime (the disk coefficient,
          rk4 / coarsen 4: matvecs (= periods) and seconds of the gmres() call, beside DDH's figures for the same problems
          (DESIGN 5.2).
 
+lattice  (parts lattice_stages, lattice_period, lattice_solve; written for profiles/r25/wave_lattice_rates.txt) the same for
+         sweep="lattice" (csrc/kernels/wave_lattice.hip): us of every cuddh_hip_wave_lattice_* launch beside the operator
+         form's stage and its Gauss stiffness apply and beside axpby, alternating in one run; TB/s on 8 B per vector read or
+         written per lattice slot (rk2_a 6, rk2_b 12, rk4_1 8, rk4_2 / rk4_3 12, rk4_4 14 vectors); ms per homogeneous period and us
+         per sweep of sweep="lattice" against sweep="operator" with stiffness "lobatto" and "gauss", rk2 and rk4 / 4, alternating;
+         one whole solve in the example's regime with sweep="lattice".
+
   python profiles/tools/waveholtz_rates.py [parts=stages,period,solve] [sizes=256,512,1024] [solve_sizes=256,512] [reps=7] [out=profiles/r24/waveholtz_rates.txt]
 """
 import ctypes as C
@@ -209,8 +216,121 @@ def solve(nx):
         f"us_per_sweep={1e6 * sec / max(1, out.num_matvec) / info['sweeps_per_period']:.1f} finite={bool(torch.isfinite(z).all())}; DDH (DESIGN 5.2): {DDH_FIGURES.get(nx, 'not recorded')}")
 
 
+LATTICE_VECTORS = {"rk2_a": 6, "rk2_b": 12, "rk4_1": 8, "rk4_2": 12, "rk4_3": 12, "rk4_4": 14}
+
+
+def lattice_stages(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    Lx = nx * (NB - 1) + 1
+    D = N.WaveLattice()
+    D.nx, D.ny, D.n_basis, D.stride, D.cx, D.cy = nx, nx, NB, Lx + Lx % 2, 1.0, 1.0
+    A, w, basis = np.zeros((NB, NB)), np.zeros(NB), cd.Basis(NB)
+    N.check_capi(N.lib.cuddh_wave_lattice_tables(basis._h, A.ctypes.data, w.ctypes.data))
+    for i, x in enumerate(A.reshape(-1)):
+        D.A[i] = x
+    for i, x in enumerate(w):
+        D.w[i] = x
+    m = D.stride * Lx  # slots of a lattice vector
+    g = torch.Generator(device=dev).manual_seed(1)
+    names = ("w", "p", "q", "u", "v", "ps", "ps2", "qs", "aq", "ap", "zu", "zv")
+    v = {k: torch.randn(m, dtype=torch.float64, device=dev, generator=g) for k in names}
+    v["invm"] = torch.rand(m, dtype=torch.float64, device=dev, generator=g) + 0.5
+    v["Hi"] = torch.zeros(m, dtype=torch.float64, device=dev)
+    if D.stride > Lx:  # the padding column: zero state, invm = 0
+        for t in v.values():
+            t.view(Lx, D.stride)[:, Lx:] = 0.0
+    K = cd.StiffnessMatrix(fem)
+    K.action(v["p"][:n], v["w"][:n])
+    L, st, d = N.lib, stream(), C.byref(D)
+    dt = 1e-9  # (the timed launches repeat on the same vectors: keep them bounded)
+    a = {k: p(t) for k, t in v.items()}
+    fs = {
+        "stiffness": lambda: K.action(v["p"][:n], v["w"][:n]),
+        "axpby": lambda: N.check(L.cuddh_hip_axpby_f64(m, 1e-6, a["zu"], 1.0, a["zv"], st)),
+        "stage rk2_a": lambda: N.check(L.cuddh_hip_wave_stage_rk2_a_f64(n, dt / 2, 1.0, 0.0, a["w"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["qs"], a["ps"], st)),
+        "lattice rk2_a": lambda: N.check(L.cuddh_hip_wave_lattice_rk2_a_f64(d, dt / 2, 1.0, 0.0, a["p"], a["q"], a["invm"], a["Hi"], None, None, a["qs"], a["ps"], st)),
+        "stage rk2_b": lambda: N.check(L.cuddh_hip_wave_stage_rk2_b_f64(n, dt, 1.0, 0.0, 1e-3, a["w"], a["qs"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st)),
+        "lattice rk2_b": lambda: N.check(L.cuddh_hip_wave_lattice_rk2_b_f64(d, dt, 1.0, 0.0, 1e-3, a["ps"], a["qs"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st)),
+        "stage rk4_1": lambda: N.check(L.cuddh_hip_wave_stage_rk4_1_f64(n, dt / 2, 1.0, 0.0, a["w"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st)),
+        "lattice rk4_1": lambda: N.check(L.cuddh_hip_wave_lattice_rk4_1_f64(d, dt / 2, 1.0, 0.0, a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st)),
+        "stage rk4_2": lambda: N.check(L.cuddh_hip_wave_stage_rk4_2_f64(n, dt / 2, 1.0, 0.0, a["w"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st)),
+        "lattice rk4_2": lambda: N.check(L.cuddh_hip_wave_lattice_rk4_2_f64(d, dt / 2, 1.0, 0.0, a["ps"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps2"], a["qs"], a["aq"], a["ap"], st)),
+        "lattice rk4_3": lambda: N.check(L.cuddh_hip_wave_lattice_rk4_3_f64(d, dt, 1.0, 0.0, a["ps2"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st)),
+        "stage rk4_4": lambda: N.check(L.cuddh_hip_wave_stage_rk4_4_f64(n, dt / 6, 1.0, 0.0, 1e-3, a["w"], a["qs"], a["aq"], a["ap"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st)),
+        "lattice rk4_4": lambda: N.check(L.cuddh_hip_wave_lattice_rk4_4_f64(d, dt / 6, 1.0, 0.0, 1e-3, a["ps"], a["qs"], a["aq"], a["ap"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st)),
+    }
+    t = timed(fs, inner=20)
+    say(f"lattice stages nx={nx} ndof={n} slots={m} ({8 * m / 1e6:.1f} MB per vector) tile {L.cuddh_hip_wave_lattice_tile_x()} x {L.cuddh_hip_wave_lattice_tile_y()}; "
+        f"operator form: stiffness kernel {K.kernel()!r}")
+    ax = STAGE_VECTORS["axpby"] * 8 * m / (t["axpby"][0] * 1e-3) / 1e12
+    for k, (med, lo, hi) in t.items():
+        vectors = LATTICE_VECTORS[k.split()[1]] if k.startswith("lattice") else (STAGE_VECTORS[k.split()[1]] if k.startswith("stage") else STAGE_VECTORS.get(k))
+        if vectors is None:
+            say(f"  {k:14s} {1e3 * med:8.1f} us (min {1e3 * lo:.1f} max {1e3 * hi:.1f})")
+        else:
+            rate = vectors * 8 * (m if not k.startswith("stage") else n) / (med * 1e-3) / 1e12
+            say(f"  {k:14s} {1e3 * med:8.1f} us (min {1e3 * lo:.1f} max {1e3 * hi:.1f})  {vectors:2d} vectors  {rate:5.2f} TB/s  {rate / ax:4.2f} of axpby")
+    s = t["stiffness"][0]
+    lat2 = (t["lattice rk2_a"][0] + t["lattice rk2_b"][0]) / 2
+    lat4 = sum(t[f"lattice {k}"][0] for k in ("rk4_1", "rk4_2", "rk4_3", "rk4_4")) / 4
+    op2 = (t["stage rk2_a"][0] + t["stage rk2_b"][0]) / 2
+    op4 = (t["stage rk4_1"][0] + 2 * t["stage rk4_2"][0] + t["stage rk4_4"][0]) / 4
+    say(f"  us per sweep: rk2 lattice {1e3 * lat2:.1f}, operator/gauss {1e3 * (s + op2):.1f} (apply {1e3 * s:.1f} + stage {1e3 * op2:.1f}); "
+        f"rk4 lattice {1e3 * lat4:.1f}, operator/gauss {1e3 * (s + op4):.1f} (apply {1e3 * s:.1f} + stage {1e3 * op4:.1f})")
+
+
+def lattice_period(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    g = torch.Generator(device=dev).manual_seed(2)
+    z = torch.randn(2 * n, dtype=torch.float64, device=dev, generator=g)
+    for scheme, coarsen in (("rk2", None), ("rk4", 4)):
+        Ws = {"lattice": cd.WaveHoltz(omega, np.ones(n), fem, integrator=scheme, coarsen=coarsen, stiffness="lobatto", sweep="lattice"),
+              "operator/lobatto": cd.WaveHoltz(omega, np.ones(n), fem, integrator=scheme, coarsen=coarsen, stiffness="lobatto"),
+              "operator/gauss": cd.WaveHoltz(omega, np.ones(n), fem, integrator=scheme, coarsen=coarsen)}
+        out = {k: torch.empty_like(z) for k in Ws}
+        for k, W in Ws.items():
+            W.period(z, None, out[k])
+        torch.cuda.synchronize()
+        diff = float(torch.linalg.norm(out["lattice"] - out["operator/lobatto"]) / torch.linalg.norm(out["lattice"]))
+        sweeps = Ws["lattice"].info()["sweeps_per_period"]
+        t = timed({k: (lambda W=W, k=k: W.period(z, None, out[k])) for k, W in Ws.items()}, inner=1)
+        text = "; ".join(f"{k} {t[k][0]:.2f} ms (min {t[k][1]:.2f} max {t[k][2]:.2f}) = {1e3 * t[k][0] / sweeps:.1f} us per sweep [{Ws[k].info()['stiffness_kernel']}]" for k in Ws)
+        say(f"lattice period nx={nx} ndof={n} {scheme} nt={Ws['lattice'].info()['nt']} ({sweeps} sweeps): {text}; lattice / gauss "
+            f"{t['lattice'][0] / t['operator/gauss'][0]:.3f}, lattice / lobatto {t['lattice'][0] / t['operator/lobatto'][0]:.3f}; lattice and operator/lobatto differ by {diff:.1e}")
+        del Ws, out
+
+
+def lattice_solve(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    f = torch.zeros(2 * n, dtype=torch.float64, device=dev)
+    a = torch.zeros(n, dtype=torch.float64, device=dev)
+    cd.linear_functional(fem, cd.GAUSSIANS, f[:n], param=omega)
+    cd.linear_functional(fem, cd.ALPHA_DISK, a)
+    cd.DiagInvMassMatrix(fem).action(a, a)
+    W = cd.WaveHoltz(omega, a.cpu().numpy(), fem, integrator="rk4", coarsen=4, stiffness="lobatto", sweep="lattice")
+    b, z = torch.empty_like(f), torch.zeros_like(f)
+    W.rhs(f, b)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = cd.gmres(2 * n, z, W, b, 20, 400, 1e-4, max_seconds=600.0)
+    torch.cuda.synchronize()
+    sec = time.perf_counter() - t0
+    info = W.info()
+    say(f"lattice solve nx={nx} ndof={n} omega={omega:.2f} disk coefficient rk4/4 nt={info['nt']} GMRES(20) tol 1e-4 sweep=lattice [{info['stiffness_kernel']}]: "
+        f"success={out.success} matvecs={out.num_matvec} cycles={out.num_iter} rel_res={out.res_norm[-1] / out.res_norm[0]:.3e} seconds={sec:.2f} "
+        f"ms_per_period={1e3 * sec / max(1, out.num_matvec):.2f} us_per_sweep={1e6 * sec / max(1, out.num_matvec) / info['sweeps_per_period']:.1f} "
+        f"finite={bool(torch.isfinite(z).all())}; operator/gauss (profiles/r24/waveholtz_rates.txt): "
+        f"{ {256: '256 matvecs, 5.15 s', 512: '499 matvecs, 24.58 s', 1024: '985 matvecs, 173.87 s'}.get(nx, 'not recorded')}")
+
+
 say(f"waveholtz_rates: {torch.cuda.get_device_name(0)}, n_basis {NB}, a == 1, omega = 2 pi nx / 10, reps {reps}")
-for part, fn, ns in (("stages", stages, sizes), ("period", period, sizes), ("solve", solve, solve_sizes)):
+for part, fn, ns in (("stages", stages, sizes), ("period", period, sizes), ("solve", solve, solve_sizes), ("lattice_stages", lattice_stages, sizes),
+                     ("lattice_period", lattice_period, sizes), ("lattice_solve", lattice_solve, solve_sizes)):
     if part in parts:
         for nx in ns:
             fn(nx)
