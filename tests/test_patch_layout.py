@@ -10,6 +10,7 @@ import pytest
 import cuddhelmholtz_amd as cd
 from cuddhelmholtz_amd._native import lib
 
+import irregular_meshes
 from conftest import GOLDEN
 
 INT_ARRAYS = ("perm", "dof_off", "dof_list", "slot_of", "own_count", "patch_nel", "face_off", "face_id", "shared_dof", "shared_off", "own_off", "bpos",
@@ -48,6 +49,8 @@ def build_layout(ndof, nb, I, xy, fI, face_elem, pe, fused, fixed_stride):
 
 @functools.lru_cache(maxsize=None)
 def mesh_of(name):
+    if "(" in name:  # generated: tests/irregular_meshes.py
+        return cd.Mesh2D.from_vertices(*irregular_meshes.by_name(name))
     if name.startswith("rect"):
         n = int(name[4:])
         return cd.Mesh2D.uniform_rect(n, -1.0, 1.0, n, -1.0, 1.0)
@@ -69,7 +72,8 @@ def space_of(mesh_name, nb):
     return fem.size(), I, xy, fI, face_elem
 
 
-MESHES = ("rect1", "rect10", "rect37", "unstructured", "unstructured refined twice")
+MESHES = ("rect1", "rect10", "rect37", "unstructured", "unstructured refined twice", "star(8,4,0.0785,2.0)", "star(6,9,0.6283)", "star(3,2)", "annulus(3,1)",
+          "annulus(7,2)", "l_shape(6)")
 ORDERS = ((2, 32), (2, 64), (4, 32), (4, 64), (5, 32), (5, 64), (6, 16), (8, 16))  # (n_basis, elements per patch)
 VARIANTS = [(fused, fixed) for fused in (True, False) for fixed in (True, False)]  # (fused or single-operator, fixed stride)
 
