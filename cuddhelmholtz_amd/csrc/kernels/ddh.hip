@@ -12,20 +12,23 @@
 //     DPP quad_perm operands, element-to-element assembly uses DPP row shifts
 //     (xi neighbours) and one ds_bpermute pair (eta neighbours).  No LDS
 //     storage, no barriers, 25,600 time steps per launch;
-//   * `ddh_element_lane5_kernel` (n_basis == 5, 4x4 elements, rectangles) runs four
+//   * `ddh_element_lane_kernel<5, ..>` (n_basis == 5, 4x4 elements, rectangles) runs four
 //     subdomains per wavefront, lane = element with its 25 nodes in registers:
 //     both contractions in-lane, assembly by DPP row shifts inside a 16-lane row;
 //   * `ddh_block_kernel` (any n_basis <= 10) runs one subdomain per workgroup
 //     with the field staged in LDS, 3 barriers per stiffness sweep.
 //
-// Shape of the file: every local solve is  load_dof (per-dof coefficients)  ->
+// Shape of the file: one translation unit in three files.  ddh_device.hpp, included first, holds what every kernel is
+// built from: DdhArgs, the time grids, the scheme tags and the local solve around a sweep; ddh_element_lane.hpp the
+// element-lane family (kernels 5 in its element-lane form, 11, 12 and 13); this file the other kernels, the plan and
+// the launches.  The build's per-file flags for ddh.hip therefore hold for all three.
+// Every local solve is  load_dof (per-dof coefficients)  ->
 // wh_march (the WaveHoltz time stepping, RK2 or for an RK4 plan RK4, around a callable `sweep(w, z)`,
 // z = S w)  ->  publish_dof (y and the trace update).  All six wavefront kernels
 // use load_dof.  ddh_wave8_kernel, ddh_mfma_kernel<Real, ..> and
-// ddh_element_lane_kernel (kernel 5's second sweep form: one element per lane,
-// four subdomains per wavefront), ddh_element_lane8_kernel (kernel 11: the same
-// with one 8x8-element subdomain per wavefront) and ddh_element_lane5_kernel
-// (kernel 12: the 4x4 form at n_basis 5, 25 nodes per lane) use wh_march and publish_dof too and are a lane
+// ddh_element_lane_kernel<NB, ..> (one element per lane, four subdomains per wavefront: kernel 5's second sweep form
+// at NB = 4, kernel 12 at NB = 5 with 25 nodes per lane, one frame for both) and ddh_element_lane8_kernel (kernel 11:
+// the same with one 8x8-element subdomain per wavefront) use wh_march and publish_dof too and are a lane
 // map, a sweep and an owner rule (which of the copies of a shared node
 // publishes); the matrix-core and element-lane kernels take wh_march's LEAN
 // forms, which leave out what their element-interior registers never need.
@@ -53,7 +56,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "common.hpp"
+#include "ddh_device.hpp"
+#include "ddh_element_lane.hpp"
 #include "ddh_resolve.hpp"
 #include "element_lane_tables.hpp"
 
@@ -63,9 +67,6 @@ struct cuddh_ddh_plan;
 
 namespace
 {
-    template <typename Real>
-    struct DdhArgs;
-
     // What resolve() stores for apply(): the function that launches the plan's kernel (the one for the plan's precision is set)
     // and the launch geometry, which depends on the plan alone.
     template <typename Real>
@@ -90,7 +91,7 @@ struct cuddh_ddh_plan
     //  cores, uniform geometry; 5 in sweep form now.form, 2 and 3: ddh_element_lane_kernel in chain order now.order);
     //  6 / 7 ddh_wave8_kernel (nb == 8; 7 separable, fp32);  9 ddh_general_wave_kernel
     //  (nb == 4, <= 16 elements, CSR lists);  10 ddh_block_kernel with CSR lists;  11 ddh_element_lane8_kernel (nb == 4,
-    //  8x8 elements, fp32: one element per lane, one subdomain per wavefront);  12 ddh_element_lane5_kernel (nb == 5, 4x4
+    //  8x8 elements, fp32: one element per lane, one subdomain per wavefront);  12 ddh_element_lane_kernel<5, ..> (nb == 5, 4x4
     //  elements, fp32: one element per lane, four subdomains per wavefront);  13 on request: the element-lane kernels
     //  with four subdomains per wavefront (nb == 4 or 5, 4x4 elements, fp32) that take per-subdomain time grids
     DdhResolved now{0, 0, 0};
@@ -127,204 +128,6 @@ namespace
 {
     constexpr int WH_ITERS_REFERENCE = 5; // WaveHoltz iterations of the reference (source/DDH.cpp:136)
 
-    template <typename Real>
-    struct DdhArgs
-    {
-        int g_ndof, n_lambda, nt, mx_dof, mx_fdof, nodes, dom_begin, dom_end;
-        int wh_iters; // 5 unless a verification run changed it (cuddh_hip_ddh_plan_set_wh_iters)
-        int prio;     // != 0: these wavefronts take issue priority over others on their SIMD (cuddh_hip_ddh_plan_set_wave_priority)
-        Real omega, dt;
-        const int *s_dof, *s_fdof, *B, *gI, *sI;
-        const Real *G, *m, *gmi, *a, *H;
-        const double *x;
-        double *y;
-        const Real *lambda;
-        Real *update;
-        const int *dom_list; // null: positions [dom_begin, dom_end) ARE the subdomains; else subdomain = dom_list[position]
-        // general plans (kernels 9, 10): per subdomain, for each dof the element nodes that contribute to it in ascending order,
-        // CSR with fixed strides: csr_off (nodes + 1, n_domains), csr_src (nodes, n_domains)
-        const int *csr_off, *csr_src;
-        int unique_y; // != 0: y entries are written by one subdomain dof each (a vector layout is set): plain adds, no atomics
-    };
-
-    template <typename Real>
-    __device__ inline int domain_at(const DdhArgs<Real> &A, int position)
-    {
-        return A.dom_list ? A.dom_list[position] : position;
-    }
-
-    // ---------------------------------------------------------------- per-subdomain time grids
-    // A plan with time grids (cuddh_hip_ddh_plan_set_time_grids) gives subdomain s the grid grid_of[s]: its own step count and
-    // step size and its own filter / cs / sn tables, which lie one grid after the other in the three arrays the kernel is
-    // passed.  The kernels that hold ONE subdomain per wavefront or workgroup take a TimeGrids as a last argument (template
-    // parameter pack Grids, empty for a plain plan: those instantiations have the arguments and the code they had before).
-    // The grid is wave-uniform, but a subdomain located from the wave index looks divergent to the compiler: the grid's index
-    // and what is read of it (nt, dt, the two offsets) go through readfirstlane, so that the loop counter, the step sizes and
-    // the table bases stay in scalar registers and filt / cs / sn on scalar loads, as on the one grid (without it the time
-    // loop gains three vector instructions and its table reads become vector loads).  Wavefronts of one workgroup may run different step counts: the wavefront kernels have no
-    // workgroup barriers, and kernel 1's workgroup is one subdomain.
-    template <typename Real>
-    struct DdhTimeGrid
-    {
-        int nt, filt_off, cs_off; // steps per period; where the grid's filter (nt + 1) and its cs / sn (2 nt + 1) start
-        Real dt;
-    };
-
-    template <typename Real>
-    struct TimeGrids
-    {
-        const int *grid_of;             // (n_domains)
-        const DdhTimeGrid<Real> *grids; // (n_grids)
-    };
-
-    // every launch of a plan with time grids goes through a list (apply: the plan's own where the caller gave none), so the
-    // wavefronts need no flag that tells the two cases apart; kernel 11 has no scalar register left for one
-    template <typename Real>
-    __device__ inline int domain_at(const DdhArgs<Real> &A, int position, const TimeGrids<Real> &)
-    {
-        return A.dom_list[position];
-    }
-
-    template <typename Real>
-    struct TimeGridView
-    {
-        int nt;
-        Real dt;
-        const Real *filt, *cs, *sn;
-    };
-
-    // the grid subdomain s marches on: the launch's one grid ...
-    template <typename Real>
-    __device__ inline TimeGridView<Real> time_grid_of(const DdhArgs<Real> &A, int, const Real *filt, const Real *cs, const Real *sn)
-    {
-        return {A.nt, A.dt, filt, cs, sn};
-    }
-
-    // the value of a wave-uniform quantity in a scalar register, whatever the compiler can prove about it
-    __device__ inline int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-    __device__ inline float wave_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-    __device__ inline double wave_uniform(double v)
-    {
-        const long long bits = __double_as_longlong(v);
-        const int lo = __builtin_amdgcn_readfirstlane(static_cast<int>(bits)), hi = __builtin_amdgcn_readfirstlane(static_cast<int>(bits >> 32));
-        return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
-    }
-
-    // ... or its own
-    template <typename Real>
-    __device__ inline TimeGridView<Real> time_grid_of(const DdhArgs<Real> &, int s, const Real *filt, const Real *cs, const Real *sn,
-                                                      const TimeGrids<Real> &TG)
-    {
-        const DdhTimeGrid<Real> tg = TG.grids[wave_uniform(TG.grid_of[s])];
-        const int filt_off = wave_uniform(tg.filt_off), cs_off = wave_uniform(tg.cs_off);
-        return {wave_uniform(tg.nt), wave_uniform(tg.dt), filt + filt_off, cs + cs_off, sn + cs_off};
-    }
-
-    // ---------------------------------------------------------------- time grids with four subdomains per wavefront (kernel 13)
-    // ddh_element_lane_kernel and ddh_element_lane5_kernel hold a subdomain per 16-lane DPP row and one time grid per march.
-    // Their TimeGrids instantiations march once per distinct grid among the wavefront's rows: a pass takes the lowest row
-    // not yet published as its leader and that row's grid g; rows on g load, march and publish their own subdomain, every
-    // other row takes the leader's (the rule of a launch's tail rows: real data in every row, nothing published).  All that
-    // waits through the time loop is one scalar, the mask of the rows that have published: the view below is formed from it
-    // at the start of a pass and again behind the march (these kernels have no register to keep it in).
-    struct GroupedRows
-    {
-        int pending, s_lead, g; // rows of the launch still to publish (bit per row, never 0); this pass's leader subdomain and grid
-    };
-
-    template <typename Real>
-    __device__ inline GroupedRows grouped_rows(const DdhArgs<Real> &A, int s_first, int done, const TimeGrids<Real> &TG)
-    {
-        GroupedRows R;
-        const int rows = A.dom_end - s_first; // >= 1: the wavefront has returned otherwise
-        R.pending = wave_uniform((rows >= 4 ? 15 : (1 << rows) - 1) & ~done);
-        R.s_lead = wave_uniform(A.dom_list[s_first + __builtin_ctz(R.pending)]);
-        R.g = wave_uniform(TG.grid_of[R.s_lead]);
-        return R;
-    }
-
-    // row `sub` in this pass: active (returns true, s = its own subdomain) or a copy of the leader
-    template <typename Real>
-    __device__ inline bool grouped_row(const DdhArgs<Real> &A, int s_first, int sub, const GroupedRows &R, const TimeGrids<Real> &TG, int &s)
-    {
-        bool active = (R.pending >> sub) & 1; // a row of the launch (s_first + sub < A.dom_end) that has not published
-        s = R.s_lead;
-        if (active)
-        {
-            const int own = A.dom_list[s_first + sub];
-            active = TG.grid_of[own] == R.g;
-            if (active)
-                s = own;
-        }
-        return active;
-    }
-
-    // the rows that publish in this pass (bit 16 r of the ballot: all lanes of a row agree) and, whatever memory says, the
-    // leader, so that every pass ends with fewer rows to go
-    __device__ inline int grouped_published(const GroupedRows &R, bool active)
-    {
-        const unsigned long long b = __builtin_amdgcn_ballot_w64(active);
-        return static_cast<int>((b & 1u) | ((b >> 15) & 2u) | ((b >> 30) & 4u) | ((b >> 45) & 8u)) | (R.pending & -R.pending);
-    }
-
-    // The launch's arguments read again: from the kernel-argument segment, where a DdhArgs that is the kernel's FIRST
-    // parameter starts at offset 0, through a pointer the compiler cannot connect with the one it holds.  A pass reads them
-    // before its loads and again behind its march (scalar loads): of the copy the compiler holds, everything a pass needs
-    // would wait in scalar registers from before the first pass to the last, through every march, and these kernels have
-    // none to spare (spilled to vector lanes they cost the vector registers that decide the occupancy).
-    template <typename Real>
-    __device__ inline void reread_args(DdhArgs<Real> &L)
-    {
-        using Segment = const __attribute__((address_space(4))) DdhArgs<Real>;
-        Segment *k = (Segment *)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(k));
-        __builtin_memcpy(&L, k, sizeof L);
-    }
-
-    // threadIdx.x & 63 without threadIdx.x, formed where it is called (the opaque 0 keeps the compiler from forming it once
-    // and keeping it): with the wavefront's first position in a scalar register a pass needs nothing else of the thread
-    // index, whose vector register is then free through the march
-    __device__ inline int lane_here()
-    {
-        int zero = 0;
-        asm volatile("" : "+v"(zero));
-        return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
-    }
-
-    template <typename T, typename... Rest>
-    __device__ inline const T &first_of(const T &t, const Rest &...) { return t; }
-
-    // ---------------------------------------------------------------- the integrator of a launch
-    // A plan with cuddh_hip_ddh_plan_set_integrator(plan, 1) steps with classical RK4.  Its kernels are instantiations of their
-    // own: the tag below comes last in the same trailing pack that carries the TimeGrids, so a kernel is instantiated with
-    // nothing (RK2, one grid: the code and the symbol it had before), TimeGrids, Rk4Scheme, or TimeGrids then Rk4Scheme.
-    struct Rk4Scheme
-    {
-    };
-
-    template <typename... Opts>
-    inline constexpr int scheme_of = 0; // wh_march's SCHEME: 0 RK2, 1 RK4
-    template <typename First, typename... Rest>
-    inline constexpr int scheme_of<First, Rest...> = scheme_of<Rest...>;
-    template <>
-    inline constexpr int scheme_of<Rk4Scheme> = 1;
-
-    template <typename Real>
-    __device__ inline int domain_at(const DdhArgs<Real> &A, int position, const Rk4Scheme &) { return domain_at(A, position); }
-    template <typename Real>
-    __device__ inline int domain_at(const DdhArgs<Real> &A, int position, const TimeGrids<Real> &TG, const Rk4Scheme &) { return domain_at(A, position, TG); }
-    template <typename Real>
-    __device__ inline TimeGridView<Real> time_grid_of(const DdhArgs<Real> &A, int s, const Real *filt, const Real *cs, const Real *sn, const Rk4Scheme &)
-    {
-        return time_grid_of(A, s, filt, cs, sn);
-    }
-    template <typename Real>
-    __device__ inline TimeGridView<Real> time_grid_of(const DdhArgs<Real> &A, int s, const Real *filt, const Real *cs, const Real *sn,
-                                                      const TimeGrids<Real> &TG, const Rk4Scheme &)
-    {
-        return time_grid_of(A, s, filt, cs, sn, TG);
-    }
-
     // Issue priority of the calling wavefront (s_setprio).  All wavefronts of one rank's local solves are resident at once and
     // advance at the same rate, so a launch of the few subdomains whose traces other ranks wait for finishes no earlier than
     // the launch of all the others it shares the SIMDs with (profiles/r02/overlap_timeline.txt) -- unless its wavefronts are
@@ -333,235 +136,6 @@ namespace
     {
         if (prio)
             __builtin_amdgcn_s_setprio(3);
-    }
-
-    // ---------------------------------------------------------------- the local solve around the sweep (shared by all kernels)
-    // Coefficients of dof d of subdomain s: invm = 1 / (a^2 m), the sources F, Gf = x (+ H lambda through B on the trace dofs
-    // d < fdof), Hi = H a.
-    template <typename Real>
-    __device__ inline void load_dof(const DdhArgs<Real> &A, int s, int d, int fdof, Real &invm, Real &Hi, Real &F, Real &Gf)
-    {
-        const size_t dbase = (size_t)A.mx_dof * s, fbase = (size_t)A.mx_fdof * s;
-        const Real ai = A.a[dbase + d], mi = A.m[dbase + d];
-        invm = Real(1) / (ai * ai * mi);
-        Real f = 0, gg = 0, h = 0;
-        if (A.x)
-        {
-            const int gidx = A.gI[dbase + d];
-            f = static_cast<Real>(A.x[gidx]);
-            gg = static_cast<Real>(A.x[A.g_ndof + gidx]);
-        }
-        if (d < fdof)
-        {
-            h = A.H[fbase + d];
-            if (A.lambda)
-            {
-                const int slot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                if (slot >= 0)
-                {
-                    f += h * A.lambda[slot];
-                    gg += h * A.lambda[A.n_lambda + slot];
-                }
-            }
-            h *= ai;
-        }
-        F = f;
-        Gf = gg;
-        Hi = h;
-    }
-
-    // The WaveHoltz iterations of one local solve for the N values a lane owns: wh_iters x (restart from the filtered field,
-    // nt RK2 steps of size dt with two stiffness sweeps z = S w each, filter accumulation) on the time grid the caller passes
-    // (time_grid_of: the launch's, or the subdomain's own).  Returns the filter sums u, v (v not yet
-    // divided by omega: publish_dof does that).  -ffp-contract=fast turns the shape of these expressions into FMAs: keep it.
-    // LEAN (the matrix-core kernels; 0 is the form every other kernel compiles to, instruction for instruction):
-    //   != 0: the step sizes are folded into the per-dof constant (q + (half_dt invm) r instead of q + half_dt (r invm)), one
-    //         multiplication less per value and half step, and the values l with bit l of INTERIOR set (value 0 of every lane
-    //         in the matrix-core kernels, the four element-interior registers of the element-lane kernel) are known to be no
-    //         trace dofs: Hi[l] == 0 and its term is not computed;
-    //   1:    their sources F[l], Gf[l] are zero as well (no x given: sources sit on trace dofs only) and are not computed either;
-    //   2:    they are kept.
-    // SCHEME 1 (scheme_of: a plan with cuddh_hip_ddh_plan_set_integrator(plan, 1)): classical RK4 in place of the midpoint rule.
-    //   With y = (p, q) and f(t; p, q) = (-q, invm (S p - Hi q + c(t) F + s(t) Gf)), step it is
-    //       k1 = f(t[2 it - 2]; y),  k2 = f(t[2 it - 1]; y + dt/2 k1),  k3 = f(t[2 it - 1]; y + dt/2 k2),  k4 = f(t[2 it]; y + dt k3),
-    //       y += dt/6 (k1 + 2 k2 + 2 k3 + k4),
-    //   four sweeps per step; restart, filter accumulation and tables are those of RK2 (cs / sn hold every half step).  The
-    //   sum of the k is accumulated stage by stage (pa, qa), so a stage's slopes are not kept: per value two registers more than
-    //   RK2's loop.  The step size is folded into the per-dof constant in every form (e = (dt invm) r is dt times the slope
-    //   of q); LEAN's rules for the INTERIOR values hold as they do for RK2.
-    template <int LEAN = 0, unsigned INTERIOR = 1u, int SCHEME = 0, typename Real, int N, typename Sweep>
-    __device__ inline void wh_march(const DdhArgs<Real> &A, const int nt, const Real dt, const Real *__restrict__ filt,
-                                    const Real *__restrict__ cs, const Real *__restrict__ sn, const Real (&invm)[N], const Real (&Hi)[N], const Real (&F)[N],
-                                    const Real (&Gf)[N], Real (&u)[N], Real (&v)[N], Sweep sweep)
-    {
-        Real p[N], q[N];
-#pragma unroll
-        for (int l = 0; l < N; ++l)
-            p[l] = q[l] = u[l] = v[l] = 0;
-        const Real half_dt = Real(0.5) * dt;
-        Real hm[N], dm[N]; // LEAN: half_dt invm, dt invm;  RK4: dm alone
-        if constexpr (LEAN != 0 || SCHEME == 1)
-        {
-#pragma unroll
-            for (int l = 0; l < N; ++l)
-            {
-                hm[l] = half_dt * invm[l];
-                dm[l] = dt * invm[l];
-            }
-        }
-        for (int whit = 0; whit < A.wh_iters; ++whit)
-        {
-            {
-                const Real k0 = filt[0];
-#pragma unroll
-                for (int l = 0; l < N; ++l)
-                {
-                    p[l] = u[l];
-                    q[l] = v[l];
-                    u[l] *= k0;
-                    v[l] *= k0;
-                }
-            }
-            if constexpr (SCHEME == 1)
-            {
-                const Real sixth = Real(1) / Real(6), third = Real(1) / Real(3);
-                const Real sixth_dt = sixth * dt, third_dt = third * dt;
-                // r: what invm multiplies in the slope of q, for value l at the stage whose field gave z and whose q is qv
-#define CUDDH_RK4_RATE(zv, qv, c, s)                                                                                                              \
-    (dm[l] * ((LEAN != 0 && ((INTERIOR >> l) & 1u)) ? (LEAN == 2 ? zv[l] + c * F[l] + s * Gf[l] : zv[l])                                         \
-                                                    : (zv[l] - Hi[l] * qv[l]) + c * F[l] + s * Gf[l]))
-                for (int it = 1; it <= nt; ++it)
-                {
-                    const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
-                    const Real c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
-                    const Real c2 = cs[2 * it], s2 = sn[2 * it];
-                    const Real kw = filt[it];
-                    Real z[N], ps[N], qs[N], pa[N], qa[N];
-
-                    sweep(p, z);
-#pragma unroll
-                    for (int l = 0; l < N; ++l)
-                    {
-                        const Real e = CUDDH_RK4_RATE(z, q, c0, s0);
-                        pa[l] = p[l] - sixth_dt * q[l];
-                        qa[l] = q[l] + sixth * e;
-                        ps[l] = p[l] - half_dt * q[l];
-                        qs[l] = q[l] + Real(0.5) * e;
-                    }
-                    sweep(ps, z);
-#pragma unroll
-                    for (int l = 0; l < N; ++l)
-                    {
-                        const Real e = CUDDH_RK4_RATE(z, qs, c1, s1);
-                        pa[l] -= third_dt * qs[l];
-                        qa[l] += third * e;
-                        ps[l] = p[l] - half_dt * qs[l];
-                        qs[l] = q[l] + Real(0.5) * e;
-                    }
-                    sweep(ps, z);
-#pragma unroll
-                    for (int l = 0; l < N; ++l)
-                    {
-                        const Real e = CUDDH_RK4_RATE(z, qs, c1, s1);
-                        pa[l] -= third_dt * qs[l];
-                        qa[l] += third * e;
-                        ps[l] = p[l] - dt * qs[l];
-                        qs[l] = q[l] + e;
-                    }
-                    sweep(ps, z);
-#pragma unroll
-                    for (int l = 0; l < N; ++l)
-                    {
-                        const Real e = CUDDH_RK4_RATE(z, qs, c2, s2);
-                        p[l] = pa[l] - sixth_dt * qs[l];
-                        q[l] = qa[l] + sixth * e;
-                        u[l] += kw * p[l];
-                        v[l] += kw * q[l];
-                    }
-                }
-#undef CUDDH_RK4_RATE
-            }
-            else
-            for (int it = 1; it <= nt; ++it)
-            {
-                const Real c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
-                const Real c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
-                const Real kw = filt[it];
-                Real z[N], ph[N], qh[N];
-
-                sweep(p, z);
-#pragma unroll
-                for (int l = 0; l < N; ++l)
-                {
-                    Real dq;
-                    if constexpr (LEAN != 0)
-                        dq = (((INTERIOR >> l) & 1u) ? (LEAN == 2 ? z[l] + c0 * F[l] + s0 * Gf[l] : z[l]) : (z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]);
-                    else
-                        dq = ((z[l] - Hi[l] * q[l]) + c0 * F[l] + s0 * Gf[l]) * invm[l];
-                    ph[l] = p[l] - half_dt * q[l];
-                    qh[l] = q[l] + (LEAN ? hm[l] : half_dt) * dq;
-                    p[l] -= dt * qh[l];
-                }
-                sweep(ph, z);
-#pragma unroll
-                for (int l = 0; l < N; ++l)
-                {
-                    Real dq;
-                    if constexpr (LEAN != 0)
-                        dq = (((INTERIOR >> l) & 1u) ? (LEAN == 2 ? z[l] + c1 * F[l] + s1 * Gf[l] : z[l]) : (z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]);
-                    else
-                        dq = ((z[l] - Hi[l] * qh[l]) + c1 * F[l] + s1 * Gf[l]) * invm[l];
-                    q[l] += (LEAN ? dm[l] : dt) * dq;
-                    u[l] += kw * p[l];
-                    v[l] += kw * q[l];
-                }
-            }
-        }
-    }
-
-    // Outputs of dof d of subdomain s from its filter sums u, v:  v /= omega,  y += M (u, v)  and, on the trace dofs, the
-    // update -lambda -+ 2 a omega (v, u) through B.  unique_y: no other subdomain dof adds to these y entries (a vector layout
-    // is set and the kernel honours it), so plain adds do; everything else adds atomically.
-    template <typename Real>
-    __device__ inline void publish_dof(const DdhArgs<Real> &A, int s, int d, int fdof, Real u, Real v, bool unique_y)
-    {
-        const size_t dbase = (size_t)A.mx_dof * s;
-        v *= Real(1) / A.omega;
-        if (A.y)
-        {
-            const int gidx = A.gI[dbase + d];
-            const Real M = A.m[dbase + d] * A.gmi[dbase + d];
-            if (unique_y)
-            {
-                A.y[gidx] += static_cast<double>(M * u);
-                A.y[A.g_ndof + gidx] += static_cast<double>(M * v);
-            }
-            else
-            {
-                atomic_add(A.y + gidx, static_cast<double>(M * u));
-                atomic_add(A.y + A.g_ndof + gidx, static_cast<double>(M * v));
-            }
-        }
-        if (A.update && d < fdof)
-        {
-            const int wslot = A.B[d + (size_t)A.mx_fdof * (1 + 2 * (size_t)s)];
-            if (wslot >= 0)
-            {
-                Real lam = 0, mu = 0;
-                if (A.lambda)
-                {
-                    const int rslot = A.B[d + (size_t)A.mx_fdof * (0 + 2 * (size_t)s)];
-                    if (rslot >= 0)
-                    {
-                        lam = A.lambda[rslot];
-                        mu = A.lambda[A.n_lambda + rslot];
-                    }
-                }
-                const Real S = Real(2) * A.a[dbase + d] * A.omega;
-                A.update[wslot] = -lam - S * v;
-                A.update[A.n_lambda + wslot] = -mu + S * u;
-            }
-        }
     }
 
     // ---------------------------------------------------------------- DPP helpers
@@ -1543,861 +1117,6 @@ namespace
         }
     }
 
-    // ---------------------------------------------------------------- kernel 5, element-lane form (NB = 4, rectangles): four subdomains per wavefront
-    // On rectangles the element matrix is a sum of two Kronecker terms (the separable form of kernel 7),
-    //     z(k,l) = beta_l sum_j Ax(k,j) w(j,l) + gamma_k sum_j Ay(l,j) w(k,j):
-    // 7 non-zeros per row where the dense product of ddh_mfma_kernel multiplies 16.  Lane = one whole ELEMENT, ex + 4 ey, one
-    // subdomain per 16-lane row, four subdomains per wavefront; register n = k + 4 l holds the element's node (k, l).  Both
-    // contractions are then in-lane full-rate FMAs with scalar-register coefficients, and the matrix pipe and LDS are not
-    // used.  To keep the coefficients within the scalar registers the node weight W(k,l) = gamma_k beta_l is factored out of
-    // both terms, z = W z',
-    //     z'(k,l) = Dg(k,l) w(k,l) + sum_{j != k} Bx(k,j) w(j,l) + sum_{j != l} By(l,j) w(k,j),
-    // Bx = Ax / gamma_k, By = Ay / beta_l, Dg = Bx(k,k) + By(l,l): 12 + 12 + 16 scalars.  All copies of a shared dof carry
-    // the same W (checked when the plan is built), so the assembled sum is W sum z' and W moves into the per-dof constants:
-    // invm is multiplied by it, Hi, F and Gf are divided.  Assembly is the only cross-lane work: xi neighbours are lane +- 1,
-    // eta neighbours lane +- 4, DPP row shifts that never leave the 16-lane row, so a subdomain's result does not depend on
-    // its wave-mates.  xi first and eta on the result; the copies of a shared node hold one sum, rounded once, and stay
-    // bitwise equal.  Registers with k, l in {1, 2} are element-interior: wh_march's LEAN rules apply to them.
-    // A launch whose length is no multiple of 4 is handled as ddh_wave8_kernel handles its odd tail: the missing rows
-    // recompute the wavefront's first subdomain and publish nothing.
-    // The time loop runs on register pairs (below, "the packed form"): two nodes per v_pk_fma_f32, 262 vector instructions
-    // per wavefront-step in the action form where the node-by-node loop issued 440 (264 with LAST_COPY, 273 / 272 with x against
-    // 456), bitwise the same results (profiles/r16, profiles/r17).  PAIRED (chain order 2, cuddh_hip_ddh_plan_set_chain_order;
-    // what auto runs where auto chose this form) sums a node's seven terms in another order, in which both halves of a pair
-    // meet every term at the same place (element_lane_pair_product): 56 packed instructions per sweep instead of 71, all
-    // eight pairs keep dm, 228 per wavefront-step in the action form (244 with x), 164 VGPRs, no scratch; a new rounding,
-    // gated against the fp64 oracle and not against the pinned chains' bits (profiles/r22).  The one-grid kernel only: the
-    // TimeGrids instantiations (kernel 13) and a form forced with set_sweep_form keep the pinned chains.
-    // Every form is compiled for three wavefronts per SIMD with no scratch: 168 VGPRs in the action form, 166 / 167 in
-    // the form with x (rhs, postprocess: once per solve).  The assembly is 16 DPP instructions per sweep with no mask
-    // multiplications in eta and one mask in xi (element_assemble_*_row_asm below): a shared node's sum is formed by one
-    // copy and moved to the other, and a lane without the neighbour is not written; the masked form with the DPP reads
-    // folded into the arithmetic (CUDDH_EL_ASSEMBLE, 12 per call) stays for kernel 11's xi direction.  Measured at 65,536 subdomains, ms per
-    // action, for the masked form (profiles/r08/element_lane_variants.txt):
-    // two wavefronts and dpp_read + FMA 271.3, three wavefronts 268.2, folded 265.7, both 258.6; the matrix form 273.9.
-    // LAST_COPY (cuddh_hip_ddh_plan_set_sweep_form(plan, 3)) turns the owner rule round, so that a test can see the other
-    // copies: the results are bitwise the same.
-    // Assembly of four node pairs with the cross-lane reads folded into the arithmetic :
-    // hi[i] += mHi * (lo[i] of lane + SHIFT), lo[i] += mLo * (hi[i] of lane - SHIFT), both from the values before the call.
-    // 12 instructions where the plain form has 8 v_mov_b32_dpp and 8 FMAs; the masks are 0 or 1, so the sums are the same.
-#define CUDDH_EL_ASSEMBLE(NAME, SHL, SHR)                                                                                                  \
-    __device__ inline void NAME(float (&hi)[4], float (&lo)[4], float mHi, float mLo)                                                      \
-    {                                                                                                                                      \
-        float t0, t1, t2, t3;                                                                                                              \
-        asm volatile("s_nop 1\n\t"                                                                                                         \
-                     "v_mul_f32_dpp %8, %0, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                       \
-                     "v_mul_f32_dpp %9, %1, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                       \
-                     "v_mul_f32_dpp %10, %2, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
-                     "v_mul_f32_dpp %11, %3, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
-                     "v_fmac_f32_dpp %0, %4, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
-                     "v_fmac_f32_dpp %1, %5, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
-                     "v_fmac_f32_dpp %2, %6, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
-                     "v_fmac_f32_dpp %3, %7, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
-                     "v_add_f32 %4, %4, %8\n\t"                                                                                            \
-                     "v_add_f32 %5, %5, %9\n\t"                                                                                            \
-                     "v_add_f32 %6, %6, %10\n\t"                                                                                           \
-                     "v_add_f32 %7, %7, %11\n\t"                                                                                           \
-                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "=&v"(t0),   \
-                       "=&v"(t1), "=&v"(t2), "=&v"(t3)                                                                                     \
-                     : "v"(mHi), "v"(mLo));                                                                                                \
-    }
-    CUDDH_EL_ASSEMBLE(element_assemble_xi_asm, "row_shl:1", "row_shr:1")
-#undef CUDDH_EL_ASSEMBLE
-    // The assembly of ddh_element_lane_kernel, where a 16-lane DPP row is one subdomain (kernel 11's rows hold two eta-rows
-    // and keep the masked form above).  The two copies of a shared node need the same sum: one copy forms it, the other
-    // takes it with a DPP move, and a lane without that neighbour is left unwritten instead of adding 0 * y.  8 DPP
-    // instructions per call where the masked form has 8 and 4 v_add_f32, no temporaries, and the value of every written
-    // lane is the one rounded sum it was before (x + 0 * y against x: the same for finite y, up to the sign of a zero).
-    // eta, lane +- 4: without bound_ctrl a lane whose source lies outside the row is not written, which is ey == 3 for
-    // row_shl:4 and ey == 0 for row_shr:4, so no mask operand at all.  up[i] += dn[i] of lane + 4; dn[i] = that sum of
-    // lane - 4.  A DPP read needs two wait states after the vector write of its source: the s_nop for the values the
-    // compiler wrote last, three instructions between each add and the move that reads it.
-    __device__ inline void element_assemble_eta_row_asm(float (&up)[4], float (&dn)[4])
-    {
-        asm volatile("s_nop 1\n\t"
-                     "v_add_f32_dpp %0, %4, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_add_f32_dpp %1, %5, %1 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_add_f32_dpp %2, %6, %2 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_add_f32_dpp %3, %7, %3 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %4, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %5, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %6, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %7, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     : "+v"(up[0]), "+v"(up[1]), "+v"(up[2]), "+v"(up[3]), "+v"(dn[0]), "+v"(dn[1]), "+v"(dn[2]), "+v"(dn[3]));
-    }
-    // xi, lane +- 1: the lanes to leave out are ex == 3 and ex == 0, every fourth lane, which neither bound_ctrl nor
-    // bank_mask (four consecutive lanes) can name.  hi[i] += mHi * (lo[i] of lane + 1) as in the masked form; lo[i] = that
-    // sum of lane - 1 unless VCC holds the lane (ex == 0), through v_cndmask_b32_dpp (D = VCC ? src1 : DPP(src0)).  VCC is
-    // set inside the statement, by scalar instructions (no wait states before a vector read of it); they also stand between
-    // the compiler's last vector write and the first DPP read.
-    __device__ inline void element_assemble_xi_row_asm(float (&hi)[4], float (&lo)[4], float mHi)
-    {
-        asm volatile("s_mov_b32 vcc_lo, 0x11111111\n\t"
-                     "s_mov_b32 vcc_hi, 0x11111111\n\t"
-                     "v_fmac_f32_dpp %0, %4, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_fmac_f32_dpp %1, %5, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_fmac_f32_dpp %2, %6, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_fmac_f32_dpp %3, %7, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_cndmask_b32_dpp %4, %0, %4, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_cndmask_b32_dpp %5, %1, %5, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_cndmask_b32_dpp %6, %2, %6, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_cndmask_b32_dpp %7, %3, %7, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3])
-                     : "v"(mHi)
-                     : "vcc");
-    }
-    // The same two for the five values a side of an n_basis-5 element holds (ddh_element_lane5_kernel): the same instructions,
-    // one more of each, so four instructions stand between a sum and the move that reads it.
-    __device__ inline void element_assemble_eta_row5_asm(float (&up)[5], float (&dn)[5])
-    {
-        asm volatile("s_nop 1\n\t"
-                     "v_add_f32_dpp %0, %5, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_add_f32_dpp %1, %6, %1 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_add_f32_dpp %2, %7, %2 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_add_f32_dpp %3, %8, %3 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_add_f32_dpp %4, %9, %4 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %5, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %6, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %7, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %8, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_mov_b32_dpp %9, %4 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-                     : "+v"(up[0]), "+v"(up[1]), "+v"(up[2]), "+v"(up[3]), "+v"(up[4]), "+v"(dn[0]), "+v"(dn[1]), "+v"(dn[2]), "+v"(dn[3]),
-                       "+v"(dn[4]));
-    }
-    __device__ inline void element_assemble_xi_row5_asm(float (&hi)[5], float (&lo)[5], float mHi)
-    {
-        asm volatile("s_mov_b32 vcc_lo, 0x11111111\n\t"
-                     "s_mov_b32 vcc_hi, 0x11111111\n\t"
-                     "v_fmac_f32_dpp %0, %5, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_fmac_f32_dpp %1, %6, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_fmac_f32_dpp %2, %7, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_fmac_f32_dpp %3, %8, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_fmac_f32_dpp %4, %9, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "v_cndmask_b32_dpp %5, %0, %5, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_cndmask_b32_dpp %6, %1, %6, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_cndmask_b32_dpp %7, %2, %7, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_cndmask_b32_dpp %8, %3, %8, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     "v_cndmask_b32_dpp %9, %4, %9, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(hi[4]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]),
-                       "+v"(lo[4])
-                     : "v"(mHi)
-                     : "vcc");
-    }
-    constexpr unsigned ELEMENT_INTERIOR_REGISTERS = (1u << 5) | (1u << 6) | (1u << 9) | (1u << 10);
-
-    // the in-lane part of the element-lane sweep: z' = Dg w + Bx-terms + By-terms of the lane's own element, before assembly
-    __device__ inline void element_lane_products(const float (&w)[16], float (&z)[16], const float (&Bx)[16], const float (&By)[16],
-                                                 const float (&Dg)[16])
-    {
-#pragma unroll
-        for (int l = 0; l < 4; ++l)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-            {
-                float t = Dg[k + 4 * l] * w[k + 4 * l];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                {
-                    if (j != k)
-                        t += Bx[k + 4 * j] * w[j + 4 * l];
-                    if (j != l)
-                        t += By[l + 4 * j] * w[k + 4 * j];
-                }
-                z[k + 4 * l] = t;
-            }
-    }
-
-    // ---- the packed form of the above (ddh_element_lane_kernel only): two nodes per 64-bit register pair, v_pk_fma_f32
-    // The loop is bound by the number of vector instructions it issues, and a v_pk_fma_f32 costs one issue for
-    // two FMAs.  Pair P = k + 4 h holds the nodes (k, l_a) in .x and (k, l_b) in .y, (l_a, l_b) = (0, 3) for h = 0 and (1, 2)
-    // for h = 1: the element-interior registers {5, 6, 9, 10} are the whole pairs 5 and 6, and the halves the assembly works
-    // on are plain 32-bit registers of the pairs.  Every half runs the chain of fp32 FMAs that element_lane_products and
-    // wh_march run for its node, written as explicit FMAs, so the results are bitwise the same -- with one change that is
-    // exact: the pairs keep hm = half_dt invm alone and not dm = dt invm = 2 hm beside it, and q += dm dq is computed as
-    // q += hm (dq + dq).  Doubling is exact in binary floating point (short of overflow, and of a subnormal hm, neither of
-    // which a stable local solve comes near), so hm (dq + dq) is the same real number as dm dq and the FMA rounds it the
-    // same.  It costs a v_pk_add_f32 per pair and step and frees two registers per pair: with dm for all eight the pairs
-    // need 174 at the widest point of the second sweep (a pair of the input dies only when five pairs of the result are
-    // complete, where single registers need seven) and the loop spills at three wavefronts per SIMD.  The assembly without
-    // mask registers and temporaries (element_assemble_*_row_asm) left room for dm in five pairs of the action form and in
-    // two of the form with x (ELEMENT_LANE_DM_PAIRS); the other pairs double dq.
-    // Scalar registers: the coefficients are operands of the packed instruction as aligned pairs, By and Dg as the pairs
-    // the halves need, the 12 off-diagonal Bx two to a pair with op_sel choosing the half (as a broadcast scalar of its
-    // own each would take a pair); 106 are in use and none is spilled inside the time loop (a dozen wait in the lanes of
-    // one vector register across it and come back once per WaveHoltz iteration).
-    typedef float pair_t __attribute__((ext_vector_type(2)));
-    constexpr int el_pair(int k, int l) { return k + 4 * ((l == 1 || l == 2) ? 1 : 0); }
-    constexpr int el_half(int l) { return l >= 2 ? 1 : 0; }
-    constexpr unsigned ELEMENT_INTERIOR_PAIRS = (1u << 5) | (1u << 6);
-    // the pairs that keep dm beside hm (wh_march_pairs' DM): as many as fit 168 vector registers, three wavefronts per SIMD,
-    // with no scratch; which pairs does not matter to the count (profiles/r17/ddh_codegen_compare.txt)
-    constexpr unsigned ELEMENT_LANE_DM_PAIRS(bool forced) { return forced ? 0x60u : 0x1fu; }
-    // the same for the paired chains (element_lane_pair_product<K, H, true>), chosen again: without the head temporaries all
-    // eight pairs of the action form keep dm at 164 registers and its three v_pk_add_f32 go; the form with x spills from
-    // three pairs on and keeps the two interior ones (profiles/r22/ddh_codegen_compare.txt lists the masks tried)
-    constexpr unsigned ELEMENT_LANE_PAIRED_DM_PAIRS(bool forced) { return forced ? 0x60u : 0xffu; }
-
-    __device__ inline pair_t pk_fma(pair_t a, pair_t b, pair_t c) { return __builtin_elementwise_fma(a, b, c); }
-    __device__ inline pair_t pk_fma(float a, pair_t b, pair_t c) { return __builtin_elementwise_fma(pair_t{a, a}, b, c); }
-    // t += (half HALF of the scalar-register pair c, in both halves) * w: two coefficients share an aligned pair of scalar
-    // registers (the compiler keeps a broadcast scalar of the time loop as a pair of its own with both halves the same)
-    template <int HALF>
-    __device__ inline void pk_fmac_scalar(pair_t &t, pair_t c, pair_t w)
-    {
-        if constexpr (HALF == 0)
-            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(t) : "s"(c), "v"(w));
-        else
-            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(t) : "s"(c), "v"(w));
-    }
-    // where the off-diagonal Bx(k, j) waits: half bx_slot % 2 of pair bx_slot / 2
-    constexpr int bx_slot(int k, int j) { return 3 * k + (j < k ? j : j - 1); }
-    // t += c * (half HALF of w, in both halves): the compiler broadcasts the low half through op_sel_hi but copies the high
-    // half into a pair of its own first, so op_sel is written here
-    template <int HALF>
-    __device__ inline void pk_fmac_half(pair_t &t, pair_t c, pair_t w)
-    {
-        if constexpr (HALF == 0)
-            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(t) : "s"(c), "v"(w));
-        else
-            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(t) : "s"(c), "v"(w));
-    }
-
-    // t = c * (half HALF of w, in both halves)
-    template <int HALF>
-    __device__ inline pair_t pk_mul_half(pair_t c, pair_t w)
-    {
-        pair_t t;
-        if constexpr (HALF == 0)
-            asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "s"(c), "v"(w));
-        else
-            asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(t) : "s"(c), "v"(w));
-        return t;
-    }
-    // t.x += c.x * w.y, t.y += c.y * w.x: the halves of w crossed, the coefficient pair straight (the compiler copies a high
-    // half into a pair of its own otherwise, as in pk_fmac_half)
-    __device__ inline void pk_fmac_crossed(pair_t &t, pair_t c, pair_t w)
-    {
-        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,0,1]" : "+v"(t) : "s"(c), "v"(w));
-    }
-
-    // element_lane_products on pairs.  A node's chain is Dg w, then for j = 0..3 the x-term (j != k) and the y-term (j != l).
-    // The x-term has one coefficient for both halves.  The y-term has the coefficient pair (By(l_a,j), By(l_b,j)) and
-    // w(k,j) from one half of pair (k, h_j); for j == l_a or l_b that is the pair itself, and only the other half has
-    // the term: one v_fmac_f32 on that half, at its place in the chain.  8 instructions per pair where the nodes took 14.
-    // The head of the chain: t = Dg w; t += c w' adds two products, and of the two the compiler of the node-by-node loop
-    // (element_lane_products under -ffp-contract=fast, read from its code object: the same in both sweeps and in all
-    // forms of the kernel) rounds c w' and fuses Dg w on the seven nodes with k == 0 or l == 0, and rounds Dg w and fuses
-    // c w' on the other nine.  The results are compared bitwise with that loop's, so the choice is kept node by node:
-    //   k != 0, pairs (1, 2):  Dg w rounded in both halves;
-    //   k != 0, pairs (0, 3):  the half l = 0 rounds Bx(k,0) w(0,0) instead: one multiplication and one FMA on that half
-    //                          replace what the two packed instructions leave there;
-    //   k == 0, pairs (1, 2):  both halves round the y-term of j = 0, By(l,0) w(0,0): packed;
-    //   k == 0, pairs (0, 3):  the half l = 0 rounds its x-term of j = 1 and the half l = 3 its y-term of j = 0: two
-    //                          multiplications, then Dg w packed, then the x-term of j = 1 on the half l = 3 alone.
-    // 71 instructions per sweep (64 + 2 for each of three pairs + 1).
-    //
-    // PAIRED, the paired chains (chain order 2, cuddh_hip_ddh_plan_set_chain_order): another summation order of the same
-    // seven terms per node, one rounded product and six FMAs, in which both halves of a pair meet every term at the same
-    // place, so that every instruction is a packed one.  For pair P = K + 4 H, Q = K + 4 (1 - H), (l_a, l_b) = (H, 3 - H):
-    //   1. t = Dg[P] w[P], rounded in both halves (one v_pk_mul_f32; no head rules);
-    //   2. for j = 0, 1, 2, 3 in this order: the x-term Bx(K,j) w(j,l) if j != K, then the y-term (By(l_a,j), By(l_b,j)) w(K,j)
-    //      if j is neither l_a nor l_b (w(K,j) is a half of w[Q]);
-    //   3. last the two y-terms that read the pair itself, crossed: .x += By(l_a,l_b) w[P].y, .y += By(l_b,l_a) w[P].x, one
-    //      v_pk_fma_f32 with op_sel crossing the halves of w[P] (pk_fmac_crossed).
-    // The pinned chains take each of the two crossed terms at j = l_b (low half) and j = l_a (high half), which are different
-    // places; moving both to the end is what lets them share an instruction.  7 instructions per pair, 56 per sweep.  By is
-    // six aligned scalar pairs: (By(l_a,j), By(l_b,j)) for the two j outside {l_a, l_b} and the crossed pair, per H.
-    template <int K, int H, bool PAIRED = false>
-    __device__ inline pair_t element_lane_pair_product(const pair_t (&w)[8], const pair_t (&Bx)[6], const float (&By)[16], const pair_t (&Dg)[8])
-    {
-        constexpr int la = H, lb = 3 - H, P = K + 4 * H, Q = K + 4 * (1 - H);
-        pair_t t;
-        if constexpr (PAIRED)
-        {
-            t = Dg[P] * w[P];
-            // j = 0
-            if constexpr (K != 0)
-                pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
-            if constexpr (H == 1)
-                pk_fmac_half<el_half(0)>(t, pair_t{By[la + 0], By[lb + 0]}, w[Q]);
-            // j = 1
-            if constexpr (K != 1)
-                pk_fmac_scalar<bx_slot(K, 1) % 2>(t, Bx[bx_slot(K, 1) / 2], w[1 + 4 * H]);
-            if constexpr (H == 0)
-                pk_fmac_half<el_half(1)>(t, pair_t{By[la + 4], By[lb + 4]}, w[Q]);
-            // j = 2
-            if constexpr (K != 2)
-                pk_fmac_scalar<bx_slot(K, 2) % 2>(t, Bx[bx_slot(K, 2) / 2], w[2 + 4 * H]);
-            if constexpr (H == 0)
-                pk_fmac_half<el_half(2)>(t, pair_t{By[la + 8], By[lb + 8]}, w[Q]);
-            // j = 3
-            if constexpr (K != 3)
-                pk_fmac_scalar<bx_slot(K, 3) % 2>(t, Bx[bx_slot(K, 3) / 2], w[3 + 4 * H]);
-            if constexpr (H == 1)
-                pk_fmac_half<el_half(3)>(t, pair_t{By[la + 12], By[lb + 12]}, w[Q]);
-            // the pair's own halves, crossed
-            pk_fmac_crossed(t, pair_t{By[la + 4 * lb], By[lb + 4 * la]}, w[P]);
-            return t;
-        }
-        // the head, through j = 0 (and for K == 0, H == 0 the x-term of j = 1)
-        if constexpr (K != 0 && H == 1)
-        {
-            t = Dg[P] * w[P];
-            pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
-            pk_fmac_half<0>(t, pair_t{By[la + 0], By[lb + 0]}, w[Q]);
-        }
-        else if constexpr (K != 0 && H == 0)
-        {
-            const float first = Bx[bx_slot(K, 0) / 2][bx_slot(K, 0) % 2] * w[0 + 4 * H].x;
-            t = Dg[P] * w[P]; // these two are for the half l = 3 (.y) alone ...
-            pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
-            t.x = __builtin_fmaf(Dg[P].x, w[P].x, first); // ... what they left in .x is replaced: the half l = 0 has the other order
-            t.y = __builtin_fmaf(By[lb + 0], w[P].x, t.y);
-        }
-        else if constexpr (K == 0 && H == 1)
-        {
-            t = pk_mul_half<0>(pair_t{By[la + 0], By[lb + 0]}, w[Q]);
-            t = pk_fma(Dg[P], w[P], t);
-        }
-        else
-        {
-            t.x = Bx[bx_slot(K, 1) / 2][bx_slot(K, 1) % 2] * w[1 + 4 * H].x;
-            t.y = By[lb + 0] * w[P].x;
-            t = pk_fma(Dg[P], w[P], t);
-            t.y = __builtin_fmaf(Bx[bx_slot(K, 1) / 2][bx_slot(K, 1) % 2], w[1 + 4 * H].y, t.y);
-        }
-        // j = 1
-        if constexpr (K != 1 && !(K == 0 && H == 0))
-            pk_fmac_scalar<bx_slot(K, 1) % 2>(t, Bx[bx_slot(K, 1) / 2], w[1 + 4 * H]);
-        if constexpr (H == 1)
-            t.y = __builtin_fmaf(By[lb + 4], w[P].x, t.y);
-        else
-            pk_fmac_half<0>(t, pair_t{By[la + 4], By[lb + 4]}, w[Q]);
-        // j = 2
-        if constexpr (K != 2)
-            pk_fmac_scalar<bx_slot(K, 2) % 2>(t, Bx[bx_slot(K, 2) / 2], w[2 + 4 * H]);
-        if constexpr (H == 1)
-            t.x = __builtin_fmaf(By[la + 8], w[P].y, t.x);
-        else
-            pk_fmac_half<1>(t, pair_t{By[la + 8], By[lb + 8]}, w[Q]);
-        // j = 3
-        if constexpr (K != 3)
-            pk_fmac_scalar<bx_slot(K, 3) % 2>(t, Bx[bx_slot(K, 3) / 2], w[3 + 4 * H]);
-        if constexpr (H == 0)
-            t.x = __builtin_fmaf(By[la + 12], w[P].y, t.x);
-        else
-            pk_fmac_half<1>(t, pair_t{By[la + 12], By[lb + 12]}, w[Q]);
-        return t;
-    }
-
-    template <bool PAIRED = false>
-    __device__ inline void element_lane_products_packed(const pair_t (&w)[8], pair_t (&z)[8], const pair_t (&Bx)[6], const float (&By)[16],
-                                                        const pair_t (&Dg)[8])
-    {
-        z[0] = element_lane_pair_product<0, 0, PAIRED>(w, Bx, By, Dg);
-        z[1] = element_lane_pair_product<1, 0, PAIRED>(w, Bx, By, Dg);
-        z[2] = element_lane_pair_product<2, 0, PAIRED>(w, Bx, By, Dg);
-        z[3] = element_lane_pair_product<3, 0, PAIRED>(w, Bx, By, Dg);
-        z[4] = element_lane_pair_product<0, 1, PAIRED>(w, Bx, By, Dg);
-        z[5] = element_lane_pair_product<1, 1, PAIRED>(w, Bx, By, Dg);
-        z[6] = element_lane_pair_product<2, 1, PAIRED>(w, Bx, By, Dg);
-        z[7] = element_lane_pair_product<3, 1, PAIRED>(w, Bx, By, Dg);
-    }
-
-    // wh_march's RK2 loop in its LEAN forms on pairs: the same expressions with the fusions -ffp-contract=fast gives them
-    // in wh_march written out, so they do not depend on it.  INTERIOR holds a bit per pair, and so does DM: a pair with its
-    // bit set keeps dm = dt invm beside hm and ends the step with q += dm dq, as wh_march does, the others with
-    // q += hm (dq + dq) (above).
-    template <int LEAN, unsigned INTERIOR, unsigned DM, int N, typename Sweep>
-    __device__ inline void wh_march_pairs(const DdhArgs<float> &A, const int nt, const float dt, const float *__restrict__ filt,
-                                          const float *__restrict__ cs, const float *__restrict__ sn, const pair_t (&invm)[N],
-                                          const pair_t (&Hi)[N], const pair_t (&F)[N], const pair_t (&Gf)[N], pair_t (&u)[N], pair_t (&v)[N],
-                                          Sweep sweep)
-    {
-        static_assert(LEAN == 1 || LEAN == 2, "the packed loop has wh_march's LEAN forms only");
-        pair_t p[N], q[N], hm[N], dm[N];
-        const float half_dt = 0.5f * dt;
-#pragma unroll
-        for (int l = 0; l < N; ++l)
-        {
-            p[l] = q[l] = u[l] = v[l] = 0;
-            hm[l] = half_dt * invm[l];
-            dm[l] = ((DM >> l) & 1u) != 0 ? dt * invm[l] : pair_t{0.0f, 0.0f};
-        }
-        for (int whit = 0; whit < A.wh_iters; ++whit)
-        {
-            const float k0 = filt[0];
-#pragma unroll
-            for (int l = 0; l < N; ++l)
-            {
-                p[l] = u[l];
-                q[l] = v[l];
-                u[l] *= k0;
-                v[l] *= k0;
-            }
-            for (int it = 1; it <= nt; ++it)
-            {
-                const float c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
-                const float c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
-                const float kw = filt[it];
-                pair_t z[N], ph[N], qh[N];
-
-                sweep(p, z);
-#pragma unroll
-                for (int l = 0; l < N; ++l)
-                {
-                    pair_t dq;
-                    if (((INTERIOR >> l) & 1u) != 0)
-                        dq = LEAN == 2 ? pk_fma(s0, Gf[l], pk_fma(c0, F[l], z[l])) : z[l];
-                    else
-                        dq = pk_fma(s0, Gf[l], pk_fma(c0, F[l], pk_fma(-Hi[l], q[l], z[l])));
-                    ph[l] = pk_fma(-half_dt, q[l], p[l]);
-                    qh[l] = pk_fma(hm[l], dq, q[l]);
-                    p[l] = pk_fma(-dt, qh[l], p[l]);
-                }
-                sweep(ph, z);
-#pragma unroll
-                for (int l = 0; l < N; ++l)
-                {
-                    pair_t dq;
-                    if (((INTERIOR >> l) & 1u) != 0)
-                        dq = LEAN == 2 ? pk_fma(s1, Gf[l], pk_fma(c1, F[l], z[l])) : z[l];
-                    else
-                        dq = pk_fma(s1, Gf[l], pk_fma(c1, F[l], pk_fma(-Hi[l], qh[l], z[l])));
-                    if (((DM >> l) & 1u) != 0)
-                        q[l] = pk_fma(dm[l], dq, q[l]);
-                    else
-                        q[l] = pk_fma(hm[l], 2.0f * dq, q[l]);
-                    u[l] = pk_fma(kw, p[l], u[l]);
-                    v[l] = pk_fma(kw, q[l], v[l]);
-                }
-            }
-        }
-    }
-
-    // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
-    // PAIRED: the paired chains in the sweep (element_lane_pair_product), the one-grid kernel only
-    template <bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, typename... Grids>
-    __global__ void __launch_bounds__(256, 3) ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
-                                                                     const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
-    {
-        constexpr bool GROUPED = sizeof...(Grids) > 0;
-        static_assert(sizeof...(Grids) <= 1 && scheme_of<Grids...> == 0, "one grid, or TimeGrids; no RK4 form");
-        static_assert(!(PAIRED && sizeof...(Grids) > 0), "the paired chains are built for the one-grid kernel only");
-        const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
-        if (s_first >= A.dom_end)
-            return; // wave-uniform: the kernel has no barriers
-        if constexpr (HOLD)
-            __builtin_amdgcn_s_setprio(3);
-        [[maybe_unused]] const int w_first = wave_uniform(s_first); // GROUPED: the wavefront's first position, scalar
-        [[maybe_unused]] int done = 0; // GROUPED: the rows that have published, a bit each; what a pass leaves to the next
-        [[maybe_unused]] GroupedRows rows{}; // of the pass under way: locate forms it
-        [[maybe_unused]] DdhArgs<float> Ap;  // GROUPED: A as the pass read it (reread_args)
-        const DdhArgs<float> &Ar = [&]() -> const DdhArgs<float> &
-        {
-            if constexpr (GROUPED)
-                return Ap;
-            else
-                return A;
-        }();
-        do
-        {
-        if constexpr (GROUPED)
-            reread_args(Ap);
-        // where this lane works: subdomain s (valid: and publishes it), its trace dofs, the dofs of its element's nodes
-        auto locate = [&](int tid, bool &valid, int &s, int &fdof, const int *&sI)
-        {
-            const int sub = (tid >> 4) & 3;
-            if constexpr (GROUPED)
-            {
-                // from the lane, w_first and done alone: behind the march nothing of the first time is there to be kept
-                rows = grouped_rows(Ar, w_first, done, first_of(grids...));
-                valid = grouped_row(Ar, w_first, sub, rows, first_of(grids...), s);
-            }
-            else
-            {
-                valid = s_first + sub < Ar.dom_end;
-                s = domain_at(Ar, valid ? s_first + sub : s_first);
-            }
-            fdof = Ar.s_fdof[s];
-            sI = Ar.sI + 256 * (size_t)s + 16 * (tid & 15);
-        };
-        bool valid;
-        int s, fdof;
-        const int *sI;
-        int tid = threadIdx.x;
-        if constexpr (GROUPED)
-            tid = lane_here(); // a pass starts from a lane index of its own, or what the last pass derived from it waits through the march
-        locate(tid, valid, s, fdof, sI);
-        // 0, in a way the compiler cannot see (done < 16): W and 1 / W, which only the loads before the march need, are read
-        // at an index that depends on the pass, or all of them are kept for the next pass, through the time loop
-        [[maybe_unused]] const int again = GROUPED ? done >> 4 : 0;
-        // the pass's time grid (the leader's; one grid: the launch's), scalar
-        const TimeGridView<float> tg = time_grid_of(Ar, GROUPED ? rows.s_lead : s, filt, cs, sn, grids...);
-
-        pair_t invm[8], Hi[8], F[8], Gf[8], u[8], v[8];
-#pragma unroll
-        for (int n = 0; n < 16; ++n)
-        {
-            const int P = el_pair(n & 3, n >> 2), half = el_half(n >> 2);
-            float im, hi, f, gf;
-            load_dof(Ar, s, sI[n], fdof, im, hi, f, gf);
-            const float W = Sep4[48 + n + again], rW = Sep4[64 + n + again];
-            invm[P][half] = im * W;
-            Hi[P][half] = hi * rW;
-            F[P][half] = f * rW;
-            Gf[P][half] = gf * rW;
-        }
-        float By[16]; // wave-uniform: scalar registers for the whole time loop
-        pair_t Bx[6], Dg[8];
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-        {
-            if ((i & 3) != (i >> 2))
-                Bx[bx_slot(i & 3, i >> 2) / 2][bx_slot(i & 3, i >> 2) % 2] = Sep4[i]; // Bx(k, j) at k + 4 j, the off-diagonals
-            By[i] = Sep4[16 + i]; // By(l, j) at l + 4 j
-            Dg[el_pair(i & 3, i >> 2)][el_half(i >> 2)] = Sep4[32 + i]; // Dg(k, l) at k + 4 l
-        }
-        const float mR = (threadIdx.x & 3) < 3 ? 1.0f : 0.0f; // ex < 3: the only mask left, for the xi sums
-
-        auto sweep = [&](const pair_t(&w)[8], pair_t(&z)[8])
-        {
-            element_lane_products_packed<PAIRED>(w, z, Bx, By, Dg);
-            // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa); the 32-bit halves of the pairs
-            float hi[4] = {z[3].x, z[7].x, z[7].y, z[3].y}, lo[4] = {z[0].x, z[4].x, z[4].y, z[0].y}; // l = 0, 1, 2, 3
-            element_assemble_xi_row_asm(hi, lo, mR);
-            z[3].x = hi[0], z[7].x = hi[1], z[7].y = hi[2], z[3].y = hi[3];
-            z[0].x = lo[0], z[4].x = lo[1], z[4].y = lo[2], z[0].y = lo[3];
-            // eta neighbours, on the xi-assembled values: my l == 3 row meets the l == 0 row of lane + 4
-            float up[4] = {z[0].y, z[1].y, z[2].y, z[3].y}, dn[4] = {z[0].x, z[1].x, z[2].x, z[3].x};
-            element_assemble_eta_row_asm(up, dn);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-            {
-                z[k].y = up[k];
-                z[k].x = dn[k];
-            }
-        };
-        wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, PAIRED ? ELEMENT_LANE_PAIRED_DM_PAIRS(FORCED) : ELEMENT_LANE_DM_PAIRS(FORCED)>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
-
-        // located a second time from a lane index the compiler cannot connect with the first: otherwise these values stay
-        // in (or are spilled from) vector registers for the whole time loop, which runs at the limit of three wavefronts per SIMD
-        if constexpr (GROUPED)
-        {
-            tid = lane_here();
-            asm volatile("" : "+s"(done));
-            reread_args(Ap);
-        }
-        else
-        {
-            tid = threadIdx.x;
-            asm volatile("" : "+v"(tid));
-        }
-        locate(tid, valid, s, fdof, sI);
-        if constexpr (!GROUPED)
-            if (!valid)
-                return;
-#pragma unroll
-        for (int n = 0; n < 16; ++n)
-        {
-            // every shared node is held by 2 or 4 (lane, register) pairs with identical values: the copy with
-            // the smallest element-node index writes (with LAST_COPY the one with the largest)
-            const int k = n & 3, l = n >> 2;
-            const bool first = !(k == 0 && (tid & 3) > 0) && !(l == 0 && (tid & 12) > 0);
-            const bool last = !(k == 3 && (tid & 3) < 3) && !(l == 3 && (tid & 12) < 12);
-            const bool owner = (LAST_COPY ? last : first) && (!GROUPED || valid);
-            if (owner)
-                publish_dof(Ar, s, sI[n], fdof, u[el_pair(k, l)][el_half(l)], v[el_pair(k, l)][el_half(l)], false);
-        }
-        if constexpr (GROUPED)
-            done |= grouped_published(rows, valid);
-        } while (GROUPED && (rows.pending & ~done) != 0);
-    }
-
-    // ---------------------------------------------------------------- kernel 11 (NB = 4, 8x8 elements, rectangles): one subdomain per wavefront
-    // The element-lane form with a subdomain of 64 elements: lane = element ex + 8 ey, register n = k + 4 l = node (k, l); the
-    // tables, the in-lane products, the folded weight W and wh_march's LEAN rules are those of ddh_element_lane_kernel (the
-    // element is the same rectangle whatever the subdomain).  Only the assembly differs.  xi neighbours are lane +- 1: a
-    // 16-lane DPP row holds two eta-rows of elements, so the row shift by 1 also carries ex == 7 into the next eta-row's
-    // ex == 0 (and back), which the masks mR / mL multiply by 0; past the ends of a DPP row bound_ctrl reads 0.  eta
-    // neighbours are lane +- 8, half of them in another DPP row: ds_bpermute_b32 (the __shfl of ddh_mfma_kernel), 8 per sweep
-    // on the LDS pipe, no LDS storage.  xi first, eta on the xi-assembled values, masks 0 / 1: the 2 or 4 copies of a shared
-    // node form the same commutative sums and stay bitwise equal.  Four wavefronts per workgroup, no barriers.  A wavefront
-    // holds one subdomain, so a launch of any length needs no padding rows and a subdomain's result does not depend on
-    // which others the launch holds.
-    // Compiled for three wavefronts per SIMD in the action form and two in the form with x.
-    template <bool FORCED, bool HOLD, bool LAST_COPY, typename... Grids>
-    __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane8_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
-                                                                                   const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
-    {
-        if (A.dom_begin + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6) >= A.dom_end)
-            return; // wave-uniform: the kernel has no barriers
-        if constexpr (HOLD)
-            __builtin_amdgcn_s_setprio(3);
-        // with time grids the subdomain waits in one scalar register from here to the outputs: the list pointer that finding it
-        // again would take has none left to wait in
-        [[maybe_unused]] int s_wave = 0;
-        if constexpr (sizeof...(Grids) > 0)
-            s_wave = wave_uniform(domain_at(A, A.dom_begin + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), grids...));
-        // where this lane works: subdomain s, its trace dofs, the dofs of its element's nodes
-        auto locate = [&](int tid, int &s, int &fdof, const int *&sI)
-        {
-            if constexpr (sizeof...(Grids) > 0)
-                s = s_wave;
-            else
-                s = domain_at(A, A.dom_begin + (int)blockIdx.x * 4 + (tid >> 6));
-            fdof = A.s_fdof[s];
-            sI = A.sI + 1024 * (size_t)s + 16 * (tid & 63);
-        };
-        int s, fdof;
-        const int *sI;
-        locate(threadIdx.x, s, fdof, sI);
-        // the time grid first, while few vector registers are live: what stays of it is scalar
-        const TimeGridView<float> tg = time_grid_of(A, s, filt, cs, sn, grids...);
-        const int lane = threadIdx.x & 63, ex = lane & 7, ey = lane >> 3;
-
-        float invm[16], Hi[16], F[16], Gf[16], u[16], v[16];
-#pragma unroll
-        for (int n = 0; n < 16; ++n)
-        {
-            load_dof(A, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
-            const float W = Sep4[48 + n], rW = Sep4[64 + n];
-            invm[n] *= W;
-            Hi[n] *= rW;
-            F[n] *= rW;
-            Gf[n] *= rW;
-        }
-        float Bx[16], By[16], Dg[16]; // wave-uniform: scalar registers for the whole time loop
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-        {
-            Bx[i] = Sep4[i];      // Bx(k, j) at k + 4 j
-            By[i] = Sep4[16 + i]; // By(l, j) at l + 4 j
-            Dg[i] = Sep4[32 + i]; // Dg(k, l) at k + 4 l
-        }
-        const float mR = ex < 7 ? 1.0f : 0.0f, mL = ex > 0 ? 1.0f : 0.0f, mU = ey < 7 ? 1.0f : 0.0f, mD = ey > 0 ? 1.0f : 0.0f;
-        const int above = (lane + 8) & 63, below = (lane + 56) & 63; // a lane without that neighbour reads a lane it masks out
-
-        auto sweep = [&](const float(&w)[16], float(&z)[16])
-        {
-            element_lane_products(w, z, Bx, By, Dg);
-            // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa)
-            float hi[4] = {z[3], z[7], z[11], z[15]}, lo[4] = {z[0], z[4], z[8], z[12]};
-            element_assemble_xi_asm(hi, lo, mR, mL);
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-            {
-                z[3 + 4 * l] = hi[l];
-                z[0 + 4 * l] = lo[l];
-            }
-            // eta neighbours, on the xi-assembled values: my l == 3 row meets the l == 0 row of lane + 8 (and vice versa)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-            {
-                const float up = z[k + 12], dn = z[k];
-                const float from_above = __shfl(dn, above, 64), from_below = __shfl(up, below, 64);
-                z[k + 12] = up + mU * from_above;
-                z[k] = dn + mD * from_below;
-            }
-        };
-        wh_march<FORCED ? 2 : 1, ELEMENT_INTERIOR_REGISTERS>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
-
-        // located a second time from a lane index the compiler cannot connect with the first, as in ddh_element_lane_kernel
-        // (with time grids the same for the subdomain in its scalar register: nothing derived from it waits through the loop)
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        if constexpr (sizeof...(Grids) > 0)
-            asm volatile("" : "+s"(s_wave));
-        locate(tid, s, fdof, sI);
-#pragma unroll
-        for (int n = 0; n < 16; ++n)
-        {
-            // every shared node is held by 2 or 4 (lane, register) pairs with identical values: the copy with
-            // the smallest element-node index writes (with LAST_COPY the one with the largest)
-            const int k = n & 3, l = n >> 2;
-            const bool first = !(k == 0 && (tid & 7) > 0) && !(l == 0 && (tid & 56) > 0);
-            const bool last = !(k == 3 && (tid & 7) < 7) && !(l == 3 && (tid & 56) < 56);
-            const bool owner = LAST_COPY ? last : first;
-            if (owner)
-                publish_dof(A, s, sI[n], fdof, u[n], v[n], false);
-        }
-    }
-
-    // ---------------------------------------------------------------- kernel 12 (NB = 5, 4x4 elements, rectangles): four subdomains per wavefront
-    // ddh_element_lane_kernel's lane map with 25 nodes per lane: lane = element ex + 4 ey, one subdomain per 16-lane DPP row,
-    // four subdomains per wavefront, register n = k + 5 l = node (k, l).  The sweep is the one documented there,
-    //     z'(k,l) = Dg(k,l) w(k,l) + sum_{j != k} Bx(k,j) w(j,l) + sum_{j != l} By(l,j) w(k,j),   z = W z',
-    // 9 in-lane FMAs per node with wave-uniform coefficients (20 + 20 + 25 scalars), W folded into the per-dof constants.
-    // Assembly: the k == 4 column meets the k == 0 column of lane + 1, the l == 4 row the l == 0 row of lane + 4, five values
-    // each, through the row forms above (one copy forms the sum, the other takes it; the shifts never leave the 16-lane row,
-    // so a subdomain's result does not depend on its wave-mates); xi first, eta on the xi-assembled values.  The nine
-    // registers with k, l in {1, 2, 3} are element-interior: wh_march's LEAN rules apply to them.  The time loop is wh_march,
-    // node by node.  A launch whose length is no multiple of 4 recomputes the wavefront's first subdomain in the missing rows
-    // and publishes nothing from them.  The action form is compiled for two wavefronts per SIMD (256 vector registers, no
-    // scratch); the form with x (rhs, postprocess: once per solve) keeps the sources of the nine interior nodes as well and
-    // takes one wavefront per SIMD, a few values in accumulation registers, no scratch either.  The 65 coefficients stay in
-    // scalar registers through the time loop, which issues 736 vector instructions per wavefront-step in the action form
-    // (774 with x), read from the code object; registers and scratch of every instantiation:
-    // profiles/r19/ddh_nb5_registers.txt.
-    constexpr unsigned ELEMENT5_INTERIOR_REGISTERS = (7u << 6) | (7u << 11) | (7u << 16);
-
-    __device__ inline void element_lane5_products(const float (&w)[25], float (&z)[25], const float (&Bx)[25], const float (&By)[25],
-                                                  const float (&Dg)[25])
-    {
-#pragma unroll
-        for (int l = 0; l < 5; ++l)
-#pragma unroll
-            for (int k = 0; k < 5; ++k)
-            {
-                float t = Dg[k + 5 * l] * w[k + 5 * l];
-#pragma unroll
-                for (int j = 0; j < 5; ++j)
-                {
-                    if (j != k)
-                        t += Bx[k + 5 * j] * w[j + 5 * l];
-                    if (j != l)
-                        t += By[l + 5 * j] * w[k + 5 * j];
-                }
-                z[k + 5 * l] = t;
-            }
-    }
-
-    // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
-    template <bool FORCED, bool HOLD, bool LAST_COPY, typename... Grids>
-    __global__ void __launch_bounds__(256, FORCED ? 1 : 2) ddh_element_lane5_kernel(DdhArgs<float> A, const float *__restrict__ Sep5, const float *__restrict__ filt,
-                                                                      const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
-    {
-        constexpr bool GROUPED = sizeof...(Grids) > 0;
-        static_assert(sizeof...(Grids) <= 1 && scheme_of<Grids...> == 0, "one grid, or TimeGrids; no RK4 form");
-        const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
-        if (s_first >= A.dom_end)
-            return; // wave-uniform: the kernel has no barriers
-        if constexpr (HOLD)
-            __builtin_amdgcn_s_setprio(3);
-        [[maybe_unused]] const int w_first = wave_uniform(s_first); // GROUPED: the wavefront's first position, scalar
-        [[maybe_unused]] int done = 0; // GROUPED: the rows that have published, a bit each; what a pass leaves to the next
-        [[maybe_unused]] GroupedRows rows{}; // of the pass under way: locate forms it
-        [[maybe_unused]] DdhArgs<float> Ap;  // GROUPED: A as the pass read it (reread_args)
-        const DdhArgs<float> &Ar = [&]() -> const DdhArgs<float> &
-        {
-            if constexpr (GROUPED)
-                return Ap;
-            else
-                return A;
-        }();
-        do
-        {
-        if constexpr (GROUPED)
-            reread_args(Ap);
-        // where this lane works: subdomain s (valid: and publishes it), its trace dofs, the dofs of its element's nodes
-        auto locate = [&](int tid, bool &valid, int &s, int &fdof, const int *&sI)
-        {
-            const int sub = (tid >> 4) & 3;
-            if constexpr (GROUPED)
-            {
-                // from the lane, w_first and done alone: behind the march nothing of the first time is there to be kept
-                rows = grouped_rows(Ar, w_first, done, first_of(grids...));
-                valid = grouped_row(Ar, w_first, sub, rows, first_of(grids...), s);
-            }
-            else
-            {
-                valid = s_first + sub < Ar.dom_end;
-                s = domain_at(Ar, valid ? s_first + sub : s_first);
-            }
-            fdof = Ar.s_fdof[s];
-            sI = Ar.sI + 400 * (size_t)s + 25 * (tid & 15);
-        };
-        bool valid;
-        int s, fdof;
-        const int *sI;
-        int tid = threadIdx.x;
-        if constexpr (GROUPED)
-            tid = lane_here(); // a pass starts from a lane index of its own, or what the last pass derived from it waits through the march
-        locate(tid, valid, s, fdof, sI);
-        // 0, in a way the compiler cannot see (done < 16): W and 1 / W, which only the loads before the march need, are read
-        // at an index that depends on the pass, or all of them are kept for the next pass, through the time loop
-        [[maybe_unused]] const int again = GROUPED ? done >> 4 : 0;
-        // the pass's time grid (the leader's; one grid: the launch's), scalar
-        const TimeGridView<float> tg = time_grid_of(Ar, GROUPED ? rows.s_lead : s, filt, cs, sn, grids...);
-
-        float invm[25], Hi[25], F[25], Gf[25], u[25], v[25];
-#pragma unroll
-        for (int n = 0; n < 25; ++n)
-        {
-            load_dof(Ar, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
-            const float W = Sep5[75 + n + again], rW = Sep5[100 + n + again];
-            invm[n] *= W;
-            Hi[n] *= rW;
-            F[n] *= rW;
-            Gf[n] *= rW;
-        }
-        float Bx[25], By[25], Dg[25]; // wave-uniform
-#pragma unroll
-        for (int i = 0; i < 25; ++i)
-        {
-            Bx[i] = Sep5[i];      // Bx(k, j) at k + 5 j
-            By[i] = Sep5[25 + i]; // By(l, j) at l + 5 j
-            Dg[i] = Sep5[50 + i]; // Dg(k, l) at k + 5 l
-        }
-        const float mR = (threadIdx.x & 3) < 3 ? 1.0f : 0.0f; // ex < 3: the only mask, for the xi sums
-
-        auto sweep = [&](const float(&w)[25], float(&z)[25])
-        {
-            element_lane5_products(w, z, Bx, By, Dg);
-            // xi neighbours: my k == 4 column meets the k == 0 column of lane + 1 (and vice versa)
-            float hi[5] = {z[4], z[9], z[14], z[19], z[24]}, lo[5] = {z[0], z[5], z[10], z[15], z[20]};
-            element_assemble_xi_row5_asm(hi, lo, mR);
-#pragma unroll
-            for (int l = 0; l < 5; ++l)
-            {
-                z[4 + 5 * l] = hi[l];
-                z[0 + 5 * l] = lo[l];
-            }
-            // eta neighbours, on the xi-assembled values: my l == 4 row meets the l == 0 row of lane + 4
-            float up[5] = {z[20], z[21], z[22], z[23], z[24]}, dn[5] = {z[0], z[1], z[2], z[3], z[4]};
-            element_assemble_eta_row5_asm(up, dn);
-#pragma unroll
-            for (int k = 0; k < 5; ++k)
-            {
-                z[k + 20] = up[k];
-                z[k] = dn[k];
-            }
-        };
-        wh_march<FORCED ? 2 : 1, ELEMENT5_INTERIOR_REGISTERS>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
-
-        // located a second time from a lane index the compiler cannot connect with the first, as in ddh_element_lane_kernel
-        if constexpr (GROUPED)
-        {
-            tid = lane_here();
-            asm volatile("" : "+s"(done));
-            reread_args(Ap);
-        }
-        else
-        {
-            tid = threadIdx.x;
-            asm volatile("" : "+v"(tid));
-        }
-        locate(tid, valid, s, fdof, sI);
-        if constexpr (!GROUPED)
-            if (!valid)
-                return;
-#pragma unroll
-        for (int n = 0; n < 25; ++n)
-        {
-            // every shared node is held by 2 or 4 (lane, register) pairs with identical values: the copy with
-            // the smallest element-node index writes (with LAST_COPY the one with the largest)
-            const int k = n % 5, l = n / 5;
-            const bool first = !(k == 0 && (tid & 3) > 0) && !(l == 0 && (tid & 12) > 0);
-            const bool last = !(k == 4 && (tid & 3) < 3) && !(l == 4 && (tid & 12) < 12);
-            const bool owner = (LAST_COPY ? last : first) && (!GROUPED || valid);
-            if (owner)
-                publish_dof(Ar, s, sI[n], fdof, u[n], v[n], false);
-        }
-        if constexpr (GROUPED)
-            done |= grouped_published(rows, valid);
-        } while (GROUPED && (rows.pending & ~done) != 0);
-    }
-
     // kernels 5, 8, 11 and 12 leave the boundary terms out on the element-interior nodes (k, l in 1 .. nb - 2): is none of them a
     // trace dof (sI >= s_fdof) in any subdomain?  True for every plan built from blocks of elements, where trace dofs lie on the
     // subdomain's boundary; a descriptor from elsewhere is checked, not trusted.
@@ -3049,13 +1768,14 @@ namespace
                                                    A.x != nullptr, A.prio != 0); });
     }
 
-    // kernel 5's element-lane form (LAST_COPY: form 3; PAIRED: chain order 2) and kernel 13 at n_basis 4
-    template <bool LAST_COPY, bool PAIRED, bool GRIDS>
+    // the row-per-subdomain element-lane kernel.  NB 4: kernel 5's element-lane form (LAST_COPY: form 3; PAIRED: chain order 2)
+    // and kernel 13 at n_basis 4;  NB 5: kernel 12, and 13 at n_basis 5.  Sep4 holds the plan's table at either order
+    template <int NB, bool LAST_COPY, bool PAIRED, bool GRIDS>
     void run_element_lane(const cuddh_ddh_plan *p, const DdhArgs<float> &A, int n_local, hipStream_t st)
     {
         with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
                                          { with_flags([&](auto FORCED, auto HOLD)
-                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<FORCED.value, HOLD.value, LAST_COPY, PAIRED, decltype(o)...>),
+                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<NB, FORCED.value, HOLD.value, LAST_COPY, PAIRED, decltype(o)...>),
                                                                            launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
                                                       A.x != nullptr, A.prio != 0); });
     }
@@ -3066,16 +1786,6 @@ namespace
         with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
                                          { with_flags([&](auto FORCED, auto HOLD)
                                                       { hipLaunchKernelGGL((ddh_element_lane8_kernel<FORCED.value, HOLD.value, LAST_COPY, decltype(o)...>),
-                                                                           launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
-                                                      A.x != nullptr, A.prio != 0); });
-    }
-
-    template <bool LAST_COPY, bool GRIDS>
-    void run_element_lane5(const cuddh_ddh_plan *p, const DdhArgs<float> &A, int n_local, hipStream_t st) // kernel 12, and 13 at n_basis 5
-    {
-        with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
-                                         { with_flags([&](auto FORCED, auto HOLD)
-                                                      { hipLaunchKernelGGL((ddh_element_lane5_kernel<FORCED.value, HOLD.value, LAST_COPY, decltype(o)...>),
                                                                            launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
                                                       A.x != nullptr, A.prio != 0); });
     }
@@ -3123,7 +1833,7 @@ namespace
                 else if constexpr (plain)
                 {
                     L.per_group = 16; // four subdomains per wavefront
-                    with_flags([&](auto LAST_COPY, auto PAIRED) { run = run_element_lane<LAST_COPY.value, PAIRED.value, false>; }, r.form == 3, r.order == 2);
+                    with_flags([&](auto LAST_COPY, auto PAIRED) { run = run_element_lane<4, LAST_COPY.value, PAIRED.value, false>; }, r.form == 3, r.order == 2);
                 }
             }
             break;
@@ -3151,7 +1861,7 @@ namespace
             if constexpr (f32 && plain)
             {
                 L.per_group = 16;
-                with_flags([&](auto LAST_COPY) { run = run_element_lane5<LAST_COPY.value, false>; }, last_copy);
+                with_flags([&](auto LAST_COPY) { run = run_element_lane<5, LAST_COPY.value, false, false>; }, last_copy);
             }
             break;
         case 13: // the element-lane kernels with four subdomains per wavefront, with or without time grids; RK2 only
@@ -3162,9 +1872,9 @@ namespace
                     [&](auto LAST_COPY)
                     {
                         if (p->d.nb == 4)
-                            run = run_element_lane<LAST_COPY.value, false, GRIDS>;
+                            run = run_element_lane<4, LAST_COPY.value, false, GRIDS>;
                         else
-                            run = run_element_lane5<LAST_COPY.value, GRIDS>;
+                            run = run_element_lane<5, LAST_COPY.value, false, GRIDS>;
                     },
                     last_copy);
             }

@@ -1,0 +1,800 @@
+// The element-lane family of DDH local-solve kernels (one element per lane, its nodes in registers; fp32, rectangles), part
+// of the one translation unit ddh.hip:
+//   ddh_element_lane_kernel<NB, ..>  a subdomain of 4x4 elements per 16-lane DPP row, four per wavefront: kernel 5's
+//                                    element-lane form (NB = 4, the packed time loop), kernel 12 (NB = 5, node by node) and,
+//                                    with TimeGrids, kernel 13 for both.  ONE frame (early exit, pass loop, the two locates,
+//                                    owner rule); what the two orders do differently stands under `if constexpr (NB == 4)`;
+//   ddh_element_lane8_kernel         kernel 11: a subdomain of 8x8 elements per wavefront (NB = 4).
+// Shared by all of them: the in-lane products, the interior masks, the folded weight W and the owner rule.  The DPP assembly
+// statements exist per value count (4 and 5): their operand numbering and wait-state spacing are their content.
+#ifndef CUDDH_AMD_DDH_ELEMENT_LANE_HPP
+#define CUDDH_AMD_DDH_ELEMENT_LANE_HPP
+
+#include <type_traits>
+
+#include "ddh_device.hpp"
+
+namespace
+{
+    // ---------------------------------------------------------------- kernel 5, element-lane form (NB = 4, rectangles): four subdomains per wavefront
+    // On rectangles the element matrix is a sum of two Kronecker terms (the separable form of kernel 7),
+    //     z(k,l) = beta_l sum_j Ax(k,j) w(j,l) + gamma_k sum_j Ay(l,j) w(k,j):
+    // 7 non-zeros per row where the dense product of ddh_mfma_kernel multiplies 16.  Lane = one whole ELEMENT, ex + 4 ey, one
+    // subdomain per 16-lane row, four subdomains per wavefront; register n = k + 4 l holds the element's node (k, l).  Both
+    // contractions are then in-lane full-rate FMAs with scalar-register coefficients, and the matrix pipe and LDS are not
+    // used.  To keep the coefficients within the scalar registers the node weight W(k,l) = gamma_k beta_l is factored out of
+    // both terms, z = W z',
+    //     z'(k,l) = Dg(k,l) w(k,l) + sum_{j != k} Bx(k,j) w(j,l) + sum_{j != l} By(l,j) w(k,j),
+    // Bx = Ax / gamma_k, By = Ay / beta_l, Dg = Bx(k,k) + By(l,l): 12 + 12 + 16 scalars.  All copies of a shared dof carry
+    // the same W (checked when the plan is built), so the assembled sum is W sum z' and W moves into the per-dof constants:
+    // invm is multiplied by it, Hi, F and Gf are divided.  Assembly is the only cross-lane work: xi neighbours are lane +- 1,
+    // eta neighbours lane +- 4, DPP row shifts that never leave the 16-lane row, so a subdomain's result does not depend on
+    // its wave-mates.  xi first and eta on the result; the copies of a shared node hold one sum, rounded once, and stay
+    // bitwise equal.  Registers with k, l in {1, 2} are element-interior: wh_march's LEAN rules apply to them.
+    // A launch whose length is no multiple of 4 is handled as ddh_wave8_kernel handles its odd tail: the missing rows
+    // recompute the wavefront's first subdomain and publish nothing.
+    // The time loop runs on register pairs (below, "the packed form"): two nodes per v_pk_fma_f32, 262 vector instructions
+    // per wavefront-step in the action form where the node-by-node loop issued 440 (264 with LAST_COPY, 273 / 272 with x against
+    // 456), bitwise the same results (profiles/r16, profiles/r17).  PAIRED (chain order 2, cuddh_hip_ddh_plan_set_chain_order;
+    // what auto runs where auto chose this form) sums a node's seven terms in another order, in which both halves of a pair
+    // meet every term at the same place (element_lane_pair_product): 56 packed instructions per sweep instead of 71, all
+    // eight pairs keep dm, 228 per wavefront-step in the action form (244 with x), 164 VGPRs, no scratch; a new rounding,
+    // gated against the fp64 oracle and not against the pinned chains' bits (profiles/r22).  The one-grid kernel only: the
+    // TimeGrids instantiations (kernel 13) and a form forced with set_sweep_form keep the pinned chains.
+    // Every form is compiled for three wavefronts per SIMD with no scratch: 168 VGPRs in the action form, 166 / 167 in
+    // the form with x (rhs, postprocess: once per solve).  The assembly is 16 DPP instructions per sweep with no mask
+    // multiplications in eta and one mask in xi (element_assemble_*_row_asm below): a shared node's sum is formed by one
+    // copy and moved to the other, and a lane without the neighbour is not written; the masked form with the DPP reads
+    // folded into the arithmetic (CUDDH_EL_ASSEMBLE, 12 per call) stays for kernel 11's xi direction.  Measured at 65,536 subdomains, ms per
+    // action, for the masked form (profiles/r08/element_lane_variants.txt):
+    // two wavefronts and dpp_read + FMA 271.3, three wavefronts 268.2, folded 265.7, both 258.6; the matrix form 273.9.
+    // LAST_COPY (cuddh_hip_ddh_plan_set_sweep_form(plan, 3)) turns the owner rule round, so that a test can see the other
+    // copies: the results are bitwise the same.
+    // Assembly of four node pairs with the cross-lane reads folded into the arithmetic :
+    // hi[i] += mHi * (lo[i] of lane + SHIFT), lo[i] += mLo * (hi[i] of lane - SHIFT), both from the values before the call.
+    // 12 instructions where the plain form has 8 v_mov_b32_dpp and 8 FMAs; the masks are 0 or 1, so the sums are the same.
+#define CUDDH_EL_ASSEMBLE(NAME, SHL, SHR)                                                                                                  \
+    __device__ inline void NAME(float (&hi)[4], float (&lo)[4], float mHi, float mLo)                                                      \
+    {                                                                                                                                      \
+        float t0, t1, t2, t3;                                                                                                              \
+        asm volatile("s_nop 1\n\t"                                                                                                         \
+                     "v_mul_f32_dpp %8, %0, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                       \
+                     "v_mul_f32_dpp %9, %1, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                       \
+                     "v_mul_f32_dpp %10, %2, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_mul_f32_dpp %11, %3, %13 " SHR " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_fmac_f32_dpp %0, %4, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_fmac_f32_dpp %1, %5, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_fmac_f32_dpp %2, %6, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_fmac_f32_dpp %3, %7, %12 " SHL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                                      \
+                     "v_add_f32 %4, %4, %8\n\t"                                                                                            \
+                     "v_add_f32 %5, %5, %9\n\t"                                                                                            \
+                     "v_add_f32 %6, %6, %10\n\t"                                                                                           \
+                     "v_add_f32 %7, %7, %11\n\t"                                                                                           \
+                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "=&v"(t0),   \
+                       "=&v"(t1), "=&v"(t2), "=&v"(t3)                                                                                     \
+                     : "v"(mHi), "v"(mLo));                                                                                                \
+    }
+    CUDDH_EL_ASSEMBLE(element_assemble_xi_asm, "row_shl:1", "row_shr:1")
+#undef CUDDH_EL_ASSEMBLE
+    // The assembly of ddh_element_lane_kernel, where a 16-lane DPP row is one subdomain (kernel 11's rows hold two eta-rows
+    // and keep the masked form above).  The two copies of a shared node need the same sum: one copy forms it, the other
+    // takes it with a DPP move, and a lane without that neighbour is left unwritten instead of adding 0 * y.  8 DPP
+    // instructions per call where the masked form has 8 and 4 v_add_f32, no temporaries, and the value of every written
+    // lane is the one rounded sum it was before (x + 0 * y against x: the same for finite y, up to the sign of a zero).
+    // eta, lane +- 4: without bound_ctrl a lane whose source lies outside the row is not written, which is ey == 3 for
+    // row_shl:4 and ey == 0 for row_shr:4, so no mask operand at all.  up[i] += dn[i] of lane + 4; dn[i] = that sum of
+    // lane - 4.  A DPP read needs two wait states after the vector write of its source: the s_nop for the values the
+    // compiler wrote last, three instructions between each add and the move that reads it.
+    __device__ inline void element_assemble_eta_row_asm(float (&up)[4], float (&dn)[4])
+    {
+        asm volatile("s_nop 1\n\t"
+                     "v_add_f32_dpp %0, %4, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %1, %5, %1 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %2, %6, %2 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %3, %7, %3 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %4, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %5, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %6, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %7, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     : "+v"(up[0]), "+v"(up[1]), "+v"(up[2]), "+v"(up[3]), "+v"(dn[0]), "+v"(dn[1]), "+v"(dn[2]), "+v"(dn[3]));
+    }
+    // xi, lane +- 1: the lanes to leave out are ex == 3 and ex == 0, every fourth lane, which neither bound_ctrl nor
+    // bank_mask (four consecutive lanes) can name.  hi[i] += mHi * (lo[i] of lane + 1) as in the masked form; lo[i] = that
+    // sum of lane - 1 unless VCC holds the lane (ex == 0), through v_cndmask_b32_dpp (D = VCC ? src1 : DPP(src0)).  VCC is
+    // set inside the statement, by scalar instructions (no wait states before a vector read of it); they also stand between
+    // the compiler's last vector write and the first DPP read.
+    __device__ inline void element_assemble_xi_row_asm(float (&hi)[4], float (&lo)[4], float mHi)
+    {
+        asm volatile("s_mov_b32 vcc_lo, 0x11111111\n\t"
+                     "s_mov_b32 vcc_hi, 0x11111111\n\t"
+                     "v_fmac_f32_dpp %0, %4, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %1, %5, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %2, %6, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %3, %7, %8 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_cndmask_b32_dpp %4, %0, %4, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %5, %1, %5, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %6, %2, %6, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %7, %3, %7, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3])
+                     : "v"(mHi)
+                     : "vcc");
+    }
+    // The same two for the five values a side of an n_basis-5 element holds (ddh_element_lane_kernel<5, ..>): the same instructions,
+    // one more of each, so four instructions stand between a sum and the move that reads it.
+    __device__ inline void element_assemble_eta_row5_asm(float (&up)[5], float (&dn)[5])
+    {
+        asm volatile("s_nop 1\n\t"
+                     "v_add_f32_dpp %0, %5, %0 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %1, %6, %1 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %2, %7, %2 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %3, %8, %3 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_add_f32_dpp %4, %9, %4 row_shl:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %5, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %6, %1 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %7, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %8, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_mov_b32_dpp %9, %4 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+                     : "+v"(up[0]), "+v"(up[1]), "+v"(up[2]), "+v"(up[3]), "+v"(up[4]), "+v"(dn[0]), "+v"(dn[1]), "+v"(dn[2]), "+v"(dn[3]),
+                       "+v"(dn[4]));
+    }
+    __device__ inline void element_assemble_xi_row5_asm(float (&hi)[5], float (&lo)[5], float mHi)
+    {
+        asm volatile("s_mov_b32 vcc_lo, 0x11111111\n\t"
+                     "s_mov_b32 vcc_hi, 0x11111111\n\t"
+                     "v_fmac_f32_dpp %0, %5, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %1, %6, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %2, %7, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %3, %8, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_fmac_f32_dpp %4, %9, %10 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                     "v_cndmask_b32_dpp %5, %0, %5, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %6, %1, %6, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %7, %2, %7, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %8, %3, %8, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     "v_cndmask_b32_dpp %9, %4, %9, vcc row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+                     : "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]), "+v"(hi[4]), "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]),
+                       "+v"(lo[4])
+                     : "v"(mHi)
+                     : "vcc");
+    }
+
+    // ---- what the kernels of the family share, for NB nodes per element side (4 or 5) and register n = k + NB l = node (k, l)
+    // wh_march's INTERIOR for a lane that holds one node per register: the registers with 0 < k, l < NB - 1
+    // (NB = 4: 5, 6, 9, 10; NB = 5: 6-8, 11-13, 16-18)
+    constexpr unsigned element_interior_registers(int nb)
+    {
+        unsigned mask = 0;
+        for (int l = 1; l < nb - 1; ++l)
+            for (int k = 1; k < nb - 1; ++k)
+                mask |= 1u << (k + nb * l);
+        return mask;
+    }
+
+    // the in-lane part of the element-lane sweep: z' = Dg w + Bx-terms + By-terms of the lane's own element, before assembly
+    template <int NB>
+    __device__ inline void element_lane_products(const float (&w)[NB * NB], float (&z)[NB * NB], const float (&Bx)[NB * NB],
+                                                 const float (&By)[NB * NB], const float (&Dg)[NB * NB])
+    {
+#pragma unroll
+        for (int l = 0; l < NB; ++l)
+#pragma unroll
+            for (int k = 0; k < NB; ++k)
+            {
+                float t = Dg[k + NB * l] * w[k + NB * l];
+#pragma unroll
+                for (int j = 0; j < NB; ++j)
+                {
+                    if (j != k)
+                        t += Bx[k + NB * j] * w[j + NB * l];
+                    if (j != l)
+                        t += By[l + NB * j] * w[k + NB * j];
+                }
+                z[k + NB * l] = t;
+            }
+    }
+
+    // The node weight W folded into a dof's constants (z = W z': invm takes W, what stands beside z' is divided by it)
+    __device__ inline void fold_weight(float W, float rW, float &invm, float &Hi, float &F, float &Gf)
+    {
+        invm *= W;
+        Hi *= rW;
+        F *= rW;
+        Gf *= rW;
+    }
+
+    // The owner rule.  Every shared node is held by 2 or 4 (lane, register) pairs with identical values: the copy with the
+    // smallest element-node index writes, with LAST_COPY the one with the largest.  Lane = ex + NEL ey in a subdomain of
+    // NEL x NEL elements (4 or 8), whatever `tid` holds above those bits.
+    template <int NB, int NEL, bool LAST_COPY>
+    __device__ inline bool element_lane_owner(int n, int tid)
+    {
+        constexpr int EX = NEL - 1, EY = NEL * (NEL - 1); // the bits of ex and of NEL ey
+        const int k = n % NB, l = n / NB;
+        const bool first = !(k == 0 && (tid & EX) > 0) && !(l == 0 && (tid & EY) > 0);
+        const bool last = !(k == NB - 1 && (tid & EX) < EX) && !(l == NB - 1 && (tid & EY) < EY);
+        return LAST_COPY ? last : first;
+    }
+
+    // ---- the packed form of the above (ddh_element_lane_kernel only): two nodes per 64-bit register pair, v_pk_fma_f32
+    // The loop is bound by the number of vector instructions it issues, and a v_pk_fma_f32 costs one issue for
+    // two FMAs.  Pair P = k + 4 h holds the nodes (k, l_a) in .x and (k, l_b) in .y, (l_a, l_b) = (0, 3) for h = 0 and (1, 2)
+    // for h = 1: the element-interior registers {5, 6, 9, 10} are the whole pairs 5 and 6, and the halves the assembly works
+    // on are plain 32-bit registers of the pairs.  Every half runs the chain of fp32 FMAs that element_lane_products and
+    // wh_march run for its node, written as explicit FMAs, so the results are bitwise the same -- with one change that is
+    // exact: the pairs keep hm = half_dt invm alone and not dm = dt invm = 2 hm beside it, and q += dm dq is computed as
+    // q += hm (dq + dq).  Doubling is exact in binary floating point (short of overflow, and of a subnormal hm, neither of
+    // which a stable local solve comes near), so hm (dq + dq) is the same real number as dm dq and the FMA rounds it the
+    // same.  It costs a v_pk_add_f32 per pair and step and frees two registers per pair: with dm for all eight the pairs
+    // need 174 at the widest point of the second sweep (a pair of the input dies only when five pairs of the result are
+    // complete, where single registers need seven) and the loop spills at three wavefronts per SIMD.  The assembly without
+    // mask registers and temporaries (element_assemble_*_row_asm) left room for dm in five pairs of the action form and in
+    // two of the form with x (ELEMENT_LANE_DM_PAIRS); the other pairs double dq.
+    // Scalar registers: the coefficients are operands of the packed instruction as aligned pairs, By and Dg as the pairs
+    // the halves need, the 12 off-diagonal Bx two to a pair with op_sel choosing the half (as a broadcast scalar of its
+    // own each would take a pair); 106 are in use and none is spilled inside the time loop (a dozen wait in the lanes of
+    // one vector register across it and come back once per WaveHoltz iteration).
+    typedef float pair_t __attribute__((ext_vector_type(2)));
+    constexpr int el_pair(int k, int l) { return k + 4 * ((l == 1 || l == 2) ? 1 : 0); }
+    constexpr int el_half(int l) { return l >= 2 ? 1 : 0; }
+    constexpr unsigned ELEMENT_INTERIOR_PAIRS = (1u << 5) | (1u << 6);
+    // the pairs that keep dm beside hm (wh_march_pairs' DM): as many as fit 168 vector registers, three wavefronts per SIMD,
+    // with no scratch; which pairs does not matter to the count (profiles/r17/ddh_codegen_compare.txt)
+    constexpr unsigned ELEMENT_LANE_DM_PAIRS(bool forced) { return forced ? 0x60u : 0x1fu; }
+    // the same for the paired chains (element_lane_pair_product<K, H, true>), chosen again: without the head temporaries all
+    // eight pairs of the action form keep dm at 164 registers and its three v_pk_add_f32 go; the form with x spills from
+    // three pairs on and keeps the two interior ones (profiles/r22/ddh_codegen_compare.txt lists the masks tried)
+    constexpr unsigned ELEMENT_LANE_PAIRED_DM_PAIRS(bool forced) { return forced ? 0x60u : 0xffu; }
+
+    __device__ inline pair_t pk_fma(pair_t a, pair_t b, pair_t c) { return __builtin_elementwise_fma(a, b, c); }
+    __device__ inline pair_t pk_fma(float a, pair_t b, pair_t c) { return __builtin_elementwise_fma(pair_t{a, a}, b, c); }
+    // t += (half HALF of the scalar-register pair c, in both halves) * w: two coefficients share an aligned pair of scalar
+    // registers (the compiler keeps a broadcast scalar of the time loop as a pair of its own with both halves the same)
+    template <int HALF>
+    __device__ inline void pk_fmac_scalar(pair_t &t, pair_t c, pair_t w)
+    {
+        if constexpr (HALF == 0)
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(t) : "s"(c), "v"(w));
+        else
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(t) : "s"(c), "v"(w));
+    }
+    // where the off-diagonal Bx(k, j) waits: half bx_slot % 2 of pair bx_slot / 2
+    constexpr int bx_slot(int k, int j) { return 3 * k + (j < k ? j : j - 1); }
+    // t += c * (half HALF of w, in both halves): the compiler broadcasts the low half through op_sel_hi but copies the high
+    // half into a pair of its own first, so op_sel is written here
+    template <int HALF>
+    __device__ inline void pk_fmac_half(pair_t &t, pair_t c, pair_t w)
+    {
+        if constexpr (HALF == 0)
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(t) : "s"(c), "v"(w));
+        else
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(t) : "s"(c), "v"(w));
+    }
+
+    // t = c * (half HALF of w, in both halves)
+    template <int HALF>
+    __device__ inline pair_t pk_mul_half(pair_t c, pair_t w)
+    {
+        pair_t t;
+        if constexpr (HALF == 0)
+            asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "s"(c), "v"(w));
+        else
+            asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(t) : "s"(c), "v"(w));
+        return t;
+    }
+    // t.x += c.x * w.y, t.y += c.y * w.x: the halves of w crossed, the coefficient pair straight (the compiler copies a high
+    // half into a pair of its own otherwise, as in pk_fmac_half)
+    __device__ inline void pk_fmac_crossed(pair_t &t, pair_t c, pair_t w)
+    {
+        asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,0,1]" : "+v"(t) : "s"(c), "v"(w));
+    }
+
+    // element_lane_products on pairs.  A node's chain is Dg w, then for j = 0..3 the x-term (j != k) and the y-term (j != l).
+    // The x-term has one coefficient for both halves.  The y-term has the coefficient pair (By(l_a,j), By(l_b,j)) and
+    // w(k,j) from one half of pair (k, h_j); for j == l_a or l_b that is the pair itself, and only the other half has
+    // the term: one v_fmac_f32 on that half, at its place in the chain.  8 instructions per pair where the nodes took 14.
+    // The head of the chain: t = Dg w; t += c w' adds two products, and of the two the compiler of the node-by-node loop
+    // (element_lane_products under -ffp-contract=fast, read from its code object: the same in both sweeps and in all
+    // forms of the kernel) rounds c w' and fuses Dg w on the seven nodes with k == 0 or l == 0, and rounds Dg w and fuses
+    // c w' on the other nine.  The results are compared bitwise with that loop's, so the choice is kept node by node:
+    //   k != 0, pairs (1, 2):  Dg w rounded in both halves;
+    //   k != 0, pairs (0, 3):  the half l = 0 rounds Bx(k,0) w(0,0) instead: one multiplication and one FMA on that half
+    //                          replace what the two packed instructions leave there;
+    //   k == 0, pairs (1, 2):  both halves round the y-term of j = 0, By(l,0) w(0,0): packed;
+    //   k == 0, pairs (0, 3):  the half l = 0 rounds its x-term of j = 1 and the half l = 3 its y-term of j = 0: two
+    //                          multiplications, then Dg w packed, then the x-term of j = 1 on the half l = 3 alone.
+    // 71 instructions per sweep (64 + 2 for each of three pairs + 1).
+    //
+    // PAIRED, the paired chains (chain order 2, cuddh_hip_ddh_plan_set_chain_order): another summation order of the same
+    // seven terms per node, one rounded product and six FMAs, in which both halves of a pair meet every term at the same
+    // place, so that every instruction is a packed one.  For pair P = K + 4 H, Q = K + 4 (1 - H), (l_a, l_b) = (H, 3 - H):
+    //   1. t = Dg[P] w[P], rounded in both halves (one v_pk_mul_f32; no head rules);
+    //   2. for j = 0, 1, 2, 3 in this order: the x-term Bx(K,j) w(j,l) if j != K, then the y-term (By(l_a,j), By(l_b,j)) w(K,j)
+    //      if j is neither l_a nor l_b (w(K,j) is a half of w[Q]);
+    //   3. last the two y-terms that read the pair itself, crossed: .x += By(l_a,l_b) w[P].y, .y += By(l_b,l_a) w[P].x, one
+    //      v_pk_fma_f32 with op_sel crossing the halves of w[P] (pk_fmac_crossed).
+    // The pinned chains take each of the two crossed terms at j = l_b (low half) and j = l_a (high half), which are different
+    // places; moving both to the end is what lets them share an instruction.  7 instructions per pair, 56 per sweep.  By is
+    // six aligned scalar pairs: (By(l_a,j), By(l_b,j)) for the two j outside {l_a, l_b} and the crossed pair, per H.
+    template <int K, int H, bool PAIRED = false>
+    __device__ inline pair_t element_lane_pair_product(const pair_t (&w)[8], const pair_t (&Bx)[6], const float (&By)[16], const pair_t (&Dg)[8])
+    {
+        constexpr int la = H, lb = 3 - H, P = K + 4 * H, Q = K + 4 * (1 - H);
+        pair_t t;
+        if constexpr (PAIRED)
+        {
+            t = Dg[P] * w[P];
+            // j = 0
+            if constexpr (K != 0)
+                pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
+            if constexpr (H == 1)
+                pk_fmac_half<el_half(0)>(t, pair_t{By[la + 0], By[lb + 0]}, w[Q]);
+            // j = 1
+            if constexpr (K != 1)
+                pk_fmac_scalar<bx_slot(K, 1) % 2>(t, Bx[bx_slot(K, 1) / 2], w[1 + 4 * H]);
+            if constexpr (H == 0)
+                pk_fmac_half<el_half(1)>(t, pair_t{By[la + 4], By[lb + 4]}, w[Q]);
+            // j = 2
+            if constexpr (K != 2)
+                pk_fmac_scalar<bx_slot(K, 2) % 2>(t, Bx[bx_slot(K, 2) / 2], w[2 + 4 * H]);
+            if constexpr (H == 0)
+                pk_fmac_half<el_half(2)>(t, pair_t{By[la + 8], By[lb + 8]}, w[Q]);
+            // j = 3
+            if constexpr (K != 3)
+                pk_fmac_scalar<bx_slot(K, 3) % 2>(t, Bx[bx_slot(K, 3) / 2], w[3 + 4 * H]);
+            if constexpr (H == 1)
+                pk_fmac_half<el_half(3)>(t, pair_t{By[la + 12], By[lb + 12]}, w[Q]);
+            // the pair's own halves, crossed
+            pk_fmac_crossed(t, pair_t{By[la + 4 * lb], By[lb + 4 * la]}, w[P]);
+            return t;
+        }
+        // the head, through j = 0 (and for K == 0, H == 0 the x-term of j = 1)
+        if constexpr (K != 0 && H == 1)
+        {
+            t = Dg[P] * w[P];
+            pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
+            pk_fmac_half<0>(t, pair_t{By[la + 0], By[lb + 0]}, w[Q]);
+        }
+        else if constexpr (K != 0 && H == 0)
+        {
+            const float first = Bx[bx_slot(K, 0) / 2][bx_slot(K, 0) % 2] * w[0 + 4 * H].x;
+            t = Dg[P] * w[P]; // these two are for the half l = 3 (.y) alone ...
+            pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
+            t.x = __builtin_fmaf(Dg[P].x, w[P].x, first); // ... what they left in .x is replaced: the half l = 0 has the other order
+            t.y = __builtin_fmaf(By[lb + 0], w[P].x, t.y);
+        }
+        else if constexpr (K == 0 && H == 1)
+        {
+            t = pk_mul_half<0>(pair_t{By[la + 0], By[lb + 0]}, w[Q]);
+            t = pk_fma(Dg[P], w[P], t);
+        }
+        else
+        {
+            t.x = Bx[bx_slot(K, 1) / 2][bx_slot(K, 1) % 2] * w[1 + 4 * H].x;
+            t.y = By[lb + 0] * w[P].x;
+            t = pk_fma(Dg[P], w[P], t);
+            t.y = __builtin_fmaf(Bx[bx_slot(K, 1) / 2][bx_slot(K, 1) % 2], w[1 + 4 * H].y, t.y);
+        }
+        // j = 1
+        if constexpr (K != 1 && !(K == 0 && H == 0))
+            pk_fmac_scalar<bx_slot(K, 1) % 2>(t, Bx[bx_slot(K, 1) / 2], w[1 + 4 * H]);
+        if constexpr (H == 1)
+            t.y = __builtin_fmaf(By[lb + 4], w[P].x, t.y);
+        else
+            pk_fmac_half<0>(t, pair_t{By[la + 4], By[lb + 4]}, w[Q]);
+        // j = 2
+        if constexpr (K != 2)
+            pk_fmac_scalar<bx_slot(K, 2) % 2>(t, Bx[bx_slot(K, 2) / 2], w[2 + 4 * H]);
+        if constexpr (H == 1)
+            t.x = __builtin_fmaf(By[la + 8], w[P].y, t.x);
+        else
+            pk_fmac_half<1>(t, pair_t{By[la + 8], By[lb + 8]}, w[Q]);
+        // j = 3
+        if constexpr (K != 3)
+            pk_fmac_scalar<bx_slot(K, 3) % 2>(t, Bx[bx_slot(K, 3) / 2], w[3 + 4 * H]);
+        if constexpr (H == 0)
+            t.x = __builtin_fmaf(By[la + 12], w[P].y, t.x);
+        else
+            pk_fmac_half<1>(t, pair_t{By[la + 12], By[lb + 12]}, w[Q]);
+        return t;
+    }
+
+    template <bool PAIRED = false>
+    __device__ inline void element_lane_products_packed(const pair_t (&w)[8], pair_t (&z)[8], const pair_t (&Bx)[6], const float (&By)[16],
+                                                        const pair_t (&Dg)[8])
+    {
+        z[0] = element_lane_pair_product<0, 0, PAIRED>(w, Bx, By, Dg);
+        z[1] = element_lane_pair_product<1, 0, PAIRED>(w, Bx, By, Dg);
+        z[2] = element_lane_pair_product<2, 0, PAIRED>(w, Bx, By, Dg);
+        z[3] = element_lane_pair_product<3, 0, PAIRED>(w, Bx, By, Dg);
+        z[4] = element_lane_pair_product<0, 1, PAIRED>(w, Bx, By, Dg);
+        z[5] = element_lane_pair_product<1, 1, PAIRED>(w, Bx, By, Dg);
+        z[6] = element_lane_pair_product<2, 1, PAIRED>(w, Bx, By, Dg);
+        z[7] = element_lane_pair_product<3, 1, PAIRED>(w, Bx, By, Dg);
+    }
+
+    // wh_march's RK2 loop in its LEAN forms on pairs: the same expressions with the fusions -ffp-contract=fast gives them
+    // in wh_march written out, so they do not depend on it.  INTERIOR holds a bit per pair, and so does DM: a pair with its
+    // bit set keeps dm = dt invm beside hm and ends the step with q += dm dq, as wh_march does, the others with
+    // q += hm (dq + dq) (above).
+    template <int LEAN, unsigned INTERIOR, unsigned DM, int N, typename Sweep>
+    __device__ inline void wh_march_pairs(const DdhArgs<float> &A, const int nt, const float dt, const float *__restrict__ filt,
+                                          const float *__restrict__ cs, const float *__restrict__ sn, const pair_t (&invm)[N],
+                                          const pair_t (&Hi)[N], const pair_t (&F)[N], const pair_t (&Gf)[N], pair_t (&u)[N], pair_t (&v)[N],
+                                          Sweep sweep)
+    {
+        static_assert(LEAN == 1 || LEAN == 2, "the packed loop has wh_march's LEAN forms only");
+        pair_t p[N], q[N], hm[N], dm[N];
+        const float half_dt = 0.5f * dt;
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+        {
+            p[l] = q[l] = u[l] = v[l] = 0;
+            hm[l] = half_dt * invm[l];
+            dm[l] = ((DM >> l) & 1u) != 0 ? dt * invm[l] : pair_t{0.0f, 0.0f};
+        }
+        for (int whit = 0; whit < A.wh_iters; ++whit)
+        {
+            const float k0 = filt[0];
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                p[l] = u[l];
+                q[l] = v[l];
+                u[l] *= k0;
+                v[l] *= k0;
+            }
+            for (int it = 1; it <= nt; ++it)
+            {
+                const float c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                const float c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                const float kw = filt[it];
+                pair_t z[N], ph[N], qh[N];
+
+                sweep(p, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    pair_t dq;
+                    if (((INTERIOR >> l) & 1u) != 0)
+                        dq = LEAN == 2 ? pk_fma(s0, Gf[l], pk_fma(c0, F[l], z[l])) : z[l];
+                    else
+                        dq = pk_fma(s0, Gf[l], pk_fma(c0, F[l], pk_fma(-Hi[l], q[l], z[l])));
+                    ph[l] = pk_fma(-half_dt, q[l], p[l]);
+                    qh[l] = pk_fma(hm[l], dq, q[l]);
+                    p[l] = pk_fma(-dt, qh[l], p[l]);
+                }
+                sweep(ph, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    pair_t dq;
+                    if (((INTERIOR >> l) & 1u) != 0)
+                        dq = LEAN == 2 ? pk_fma(s1, Gf[l], pk_fma(c1, F[l], z[l])) : z[l];
+                    else
+                        dq = pk_fma(s1, Gf[l], pk_fma(c1, F[l], pk_fma(-Hi[l], qh[l], z[l])));
+                    if (((DM >> l) & 1u) != 0)
+                        q[l] = pk_fma(dm[l], dq, q[l]);
+                    else
+                        q[l] = pk_fma(hm[l], 2.0f * dq, q[l]);
+                    u[l] = pk_fma(kw, p[l], u[l]);
+                    v[l] = pk_fma(kw, q[l], v[l]);
+                }
+            }
+        }
+    }
+
+    // ---------------------------------------------------------------- kernel 12 (NB = 5, 4x4 elements, rectangles): four subdomains per wavefront
+    // ddh_element_lane_kernel's lane map with 25 nodes per lane: lane = element ex + 4 ey, one subdomain per 16-lane DPP row,
+    // four subdomains per wavefront, register n = k + 5 l = node (k, l).  The sweep is the one documented there,
+    //     z'(k,l) = Dg(k,l) w(k,l) + sum_{j != k} Bx(k,j) w(j,l) + sum_{j != l} By(l,j) w(k,j),   z = W z',
+    // 9 in-lane FMAs per node with wave-uniform coefficients (20 + 20 + 25 scalars), W folded into the per-dof constants.
+    // Assembly: the k == 4 column meets the k == 0 column of lane + 1, the l == 4 row the l == 0 row of lane + 4, five values
+    // each, through the row forms above (one copy forms the sum, the other takes it; the shifts never leave the 16-lane row,
+    // so a subdomain's result does not depend on its wave-mates); xi first, eta on the xi-assembled values.  The nine
+    // registers with k, l in {1, 2, 3} are element-interior: wh_march's LEAN rules apply to them.  The time loop is wh_march,
+    // node by node.  A launch whose length is no multiple of 4 recomputes the wavefront's first subdomain in the missing rows
+    // and publishes nothing from them.  The action form is compiled for two wavefronts per SIMD (256 vector registers, no
+    // scratch); the form with x (rhs, postprocess: once per solve) keeps the sources of the nine interior nodes as well and
+    // takes one wavefront per SIMD, a few values in accumulation registers, no scratch either.  The 65 coefficients stay in
+    // scalar registers through the time loop, which issues 736 vector instructions per wavefront-step in the action form
+    // (774 with x), read from the code object; registers and scratch of every instantiation:
+    // profiles/r19/ddh_nb5_registers.txt.
+
+    // ---------------------------------------------------------------- the row-per-subdomain kernel (kernels 5, 12 and 13)
+    // Kernel 5's element-lane form (NB = 4) and kernel 12 (NB = 5), both documented above, and kernel 13 for either.
+    // The frame is written once, in the kernel body and not behind a function of its own: a body moved unchanged into a
+    // __device__ __forceinline__ template compiled to other code in all sixteen instantiations tried (the callee is optimised
+    // before it is inlined).  What depends on NB is constants, the state's type, and the `if constexpr (NB == 4)` branches.
+    // NB: nodes per element side, 4 (the state in pairs, wh_march_pairs) or 5 (a register per node, wh_march).
+    // FORCED, HOLD: as in ddh_mfma_kernel.  LAST_COPY: the owner rule turned round.
+    // PAIRED: the paired chains in the sweep (element_lane_pair_product), NB = 4 and the one-grid kernel only
+    // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
+    // Sep: [Bx | By | Dg | W | 1 / W], NB NB floats each (build_element_lane_tables).
+    // A stays the FIRST parameter: reread_args reads it at offset 0 of the kernel-argument segment.
+    // Wavefronts per SIMD: three at NB = 4; at NB = 5 two, and one in the form with x.
+    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, typename... Grids>
+    __global__ void __launch_bounds__(256, NB == 4 ? 3 : (FORCED ? 1 : 2))
+        ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep, const float *__restrict__ filt, const float *__restrict__ cs,
+                                const float *__restrict__ sn, Grids... grids)
+    {
+        constexpr bool GROUPED = sizeof...(Grids) > 0;
+        constexpr int NN = NB * NB;           // nodes per element, and per lane
+        constexpr int NS = NB == 4 ? 8 : NN;  // state values per lane: pairs of nodes (el_pair, el_half) or nodes
+        using state_t = std::conditional_t<NB == 4, pair_t, float>;
+        static_assert(NB == 4 || NB == 5, "the assembly statements exist for 4 and 5 values a side");
+        static_assert(sizeof...(Grids) <= 1 && scheme_of<Grids...> == 0, "one grid, or TimeGrids; no RK4 form");
+        static_assert(!(PAIRED && NB != 4), "the paired chains are those of the packed form");
+        static_assert(!(PAIRED && sizeof...(Grids) > 0), "the paired chains are built for the one-grid kernel only");
+        const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
+        if (s_first >= A.dom_end)
+            return; // wave-uniform: the kernel has no barriers
+        if constexpr (HOLD)
+            __builtin_amdgcn_s_setprio(3);
+        [[maybe_unused]] const int w_first = wave_uniform(s_first); // GROUPED: the wavefront's first position, scalar
+        [[maybe_unused]] int done = 0; // GROUPED: the rows that have published, a bit each; what a pass leaves to the next
+        [[maybe_unused]] GroupedRows rows{}; // of the pass under way: locate forms it
+        [[maybe_unused]] DdhArgs<float> Ap;  // GROUPED: A as the pass read it (reread_args)
+        const DdhArgs<float> &Ar = [&]() -> const DdhArgs<float> &
+        {
+            if constexpr (GROUPED)
+                return Ap;
+            else
+                return A;
+        }();
+        do
+        {
+        if constexpr (GROUPED)
+            reread_args(Ap);
+        // where this lane works: subdomain s (valid: and publishes it), its trace dofs, the dofs of its element's nodes
+        auto locate = [&](int tid, bool &valid, int &s, int &fdof, const int *&sI)
+        {
+            const int sub = (tid >> 4) & 3;
+            if constexpr (GROUPED)
+            {
+                // from the lane, w_first and done alone: behind the march nothing of the first time is there to be kept
+                rows = grouped_rows(Ar, w_first, done, first_of(grids...));
+                valid = grouped_row(Ar, w_first, sub, rows, first_of(grids...), s);
+            }
+            else
+            {
+                valid = s_first + sub < Ar.dom_end;
+                s = domain_at(Ar, valid ? s_first + sub : s_first);
+            }
+            fdof = Ar.s_fdof[s];
+            sI = Ar.sI + 16 * NN * (size_t)s + NN * (tid & 15);
+        };
+        bool valid;
+        int s, fdof;
+        const int *sI;
+        int tid = threadIdx.x;
+        if constexpr (GROUPED)
+            tid = lane_here(); // a pass starts from a lane index of its own, or what the last pass derived from it waits through the march
+        locate(tid, valid, s, fdof, sI);
+        // 0, in a way the compiler cannot see (done < 16): W and 1 / W, which only the loads before the march need, are read
+        // at an index that depends on the pass, or all of them are kept for the next pass, through the time loop
+        [[maybe_unused]] const int again = GROUPED ? done >> 4 : 0;
+        // the pass's time grid (the leader's; one grid: the launch's), scalar
+        const TimeGridView<float> tg = time_grid_of(Ar, GROUPED ? rows.s_lead : s, filt, cs, sn, grids...);
+
+        state_t invm[NS], Hi[NS], F[NS], Gf[NS], u[NS], v[NS];
+#pragma unroll
+        for (int n = 0; n < NN; ++n)
+        {
+            if constexpr (NB == 4)
+            {
+                const int P = el_pair(n & 3, n >> 2), half = el_half(n >> 2);
+                float im, hi, f, gf;
+                load_dof(Ar, s, sI[n], fdof, im, hi, f, gf);
+                fold_weight(Sep[3 * NN + n + again], Sep[4 * NN + n + again], im, hi, f, gf);
+                invm[P][half] = im, Hi[P][half] = hi, F[P][half] = f, Gf[P][half] = gf;
+            }
+            else
+            {
+                // straight into the registers: through locals, as above, the forms with x order the last products otherwise
+                load_dof(Ar, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
+                fold_weight(Sep[3 * NN + n + again], Sep[4 * NN + n + again], invm[n], Hi[n], F[n], Gf[n]);
+            }
+        }
+        // wave-uniform: scalar registers for the whole time loop.  Bx(k, j) at k + NB j, By(l, j) at l + NB j, Dg(k, l) at
+        // k + NB l; NB == 4: Dg in the pairs of the state, of Bx the off-diagonals, two to a pair (bx_slot)
+        float By[NN];
+        state_t Bx[NB == 4 ? 6 : NN], Dg[NS];
+#pragma unroll
+        for (int i = 0; i < NN; ++i)
+        {
+            if constexpr (NB == 4)
+            {
+                if ((i & 3) != (i >> 2))
+                    Bx[bx_slot(i & 3, i >> 2) / 2][bx_slot(i & 3, i >> 2) % 2] = Sep[i];
+                By[i] = Sep[NN + i];
+                Dg[el_pair(i & 3, i >> 2)][el_half(i >> 2)] = Sep[2 * NN + i];
+            }
+            else
+            {
+                Bx[i] = Sep[i];
+                By[i] = Sep[NN + i];
+                Dg[i] = Sep[2 * NN + i];
+            }
+        }
+        const float mR = (threadIdx.x & 3) < 3 ? 1.0f : 0.0f; // ex < 3: the only mask left, for the xi sums
+
+        // in-lane products, then the assembly: xi neighbours first (my k == NB - 1 column meets the k == 0 column of lane + 1),
+        // eta neighbours on the xi-assembled values (my l == NB - 1 row meets the l == 0 row of lane + 4)
+        auto sweep = [&](const state_t(&w)[NS], state_t(&z)[NS])
+        {
+            if constexpr (NB == 4)
+            {
+                element_lane_products_packed<PAIRED>(w, z, Bx, By, Dg);
+                // the 32-bit halves of the pairs
+                float hi[4] = {z[3].x, z[7].x, z[7].y, z[3].y}, lo[4] = {z[0].x, z[4].x, z[4].y, z[0].y}; // l = 0, 1, 2, 3
+                element_assemble_xi_row_asm(hi, lo, mR);
+                z[3].x = hi[0], z[7].x = hi[1], z[7].y = hi[2], z[3].y = hi[3];
+                z[0].x = lo[0], z[4].x = lo[1], z[4].y = lo[2], z[0].y = lo[3];
+                float up[4] = {z[0].y, z[1].y, z[2].y, z[3].y}, dn[4] = {z[0].x, z[1].x, z[2].x, z[3].x};
+                element_assemble_eta_row_asm(up, dn);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                {
+                    z[k].y = up[k];
+                    z[k].x = dn[k];
+                }
+            }
+            else
+            {
+                element_lane_products<5>(w, z, Bx, By, Dg);
+                float hi[5] = {z[4], z[9], z[14], z[19], z[24]}, lo[5] = {z[0], z[5], z[10], z[15], z[20]};
+                element_assemble_xi_row5_asm(hi, lo, mR);
+#pragma unroll
+                for (int l = 0; l < 5; ++l)
+                {
+                    z[4 + 5 * l] = hi[l];
+                    z[0 + 5 * l] = lo[l];
+                }
+                float up[5] = {z[20], z[21], z[22], z[23], z[24]}, dn[5] = {z[0], z[1], z[2], z[3], z[4]};
+                element_assemble_eta_row5_asm(up, dn);
+#pragma unroll
+                for (int k = 0; k < 5; ++k)
+                {
+                    z[k + 20] = up[k];
+                    z[k] = dn[k];
+                }
+            }
+        };
+        if constexpr (NB == 4)
+            wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, PAIRED ? ELEMENT_LANE_PAIRED_DM_PAIRS(FORCED) : ELEMENT_LANE_DM_PAIRS(FORCED)>(
+                Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
+        else
+            wh_march<FORCED ? 2 : 1, element_interior_registers(NB)>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
+
+        // located a second time from a lane index the compiler cannot connect with the first: otherwise these values stay
+        // in (or are spilled from) vector registers for the whole time loop, which runs at the limit of three wavefronts per SIMD
+        if constexpr (GROUPED)
+        {
+            tid = lane_here();
+            asm volatile("" : "+s"(done));
+            reread_args(Ap);
+        }
+        else
+        {
+            tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+        }
+        locate(tid, valid, s, fdof, sI);
+        if constexpr (!GROUPED)
+            if (!valid)
+                return;
+#pragma unroll
+        for (int n = 0; n < NN; ++n)
+        {
+            const bool owner = element_lane_owner<NB, 4, LAST_COPY>(n, tid) && (!GROUPED || valid);
+            if (owner)
+            {
+                if constexpr (NB == 4)
+                    publish_dof(Ar, s, sI[n], fdof, u[el_pair(n & 3, n >> 2)][el_half(n >> 2)], v[el_pair(n & 3, n >> 2)][el_half(n >> 2)], false);
+                else
+                    publish_dof(Ar, s, sI[n], fdof, u[n], v[n], false);
+            }
+        }
+        if constexpr (GROUPED)
+            done |= grouped_published(rows, valid);
+        } while (GROUPED && (rows.pending & ~done) != 0);
+    }
+
+    // ---------------------------------------------------------------- kernel 11 (NB = 4, 8x8 elements, rectangles): one subdomain per wavefront
+    // The element-lane form with a subdomain of 64 elements: lane = element ex + 8 ey, register n = k + 4 l = node (k, l); the
+    // tables, the in-lane products, the folded weight W and wh_march's LEAN rules are those of ddh_element_lane_kernel (the
+    // element is the same rectangle whatever the subdomain).  Only the assembly differs.  xi neighbours are lane +- 1: a
+    // 16-lane DPP row holds two eta-rows of elements, so the row shift by 1 also carries ex == 7 into the next eta-row's
+    // ex == 0 (and back), which the masks mR / mL multiply by 0; past the ends of a DPP row bound_ctrl reads 0.  eta
+    // neighbours are lane +- 8, half of them in another DPP row: ds_bpermute_b32 (the __shfl of ddh_mfma_kernel), 8 per sweep
+    // on the LDS pipe, no LDS storage.  xi first, eta on the xi-assembled values, masks 0 / 1: the 2 or 4 copies of a shared
+    // node form the same commutative sums and stay bitwise equal.  Four wavefronts per workgroup, no barriers.  A wavefront
+    // holds one subdomain, so a launch of any length needs no padding rows and a subdomain's result does not depend on
+    // which others the launch holds.
+    // Compiled for three wavefronts per SIMD in the action form and two in the form with x.
+    template <bool FORCED, bool HOLD, bool LAST_COPY, typename... Grids>
+    __global__ void __launch_bounds__(256, FORCED ? 2 : 3) ddh_element_lane8_kernel(DdhArgs<float> A, const float *__restrict__ Sep4, const float *__restrict__ filt,
+                                                                                   const float *__restrict__ cs, const float *__restrict__ sn, Grids... grids)
+    {
+        if (A.dom_begin + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6) >= A.dom_end)
+            return; // wave-uniform: the kernel has no barriers
+        if constexpr (HOLD)
+            __builtin_amdgcn_s_setprio(3);
+        // with time grids the subdomain waits in one scalar register from here to the outputs: the list pointer that finding it
+        // again would take has none left to wait in
+        [[maybe_unused]] int s_wave = 0;
+        if constexpr (sizeof...(Grids) > 0)
+            s_wave = wave_uniform(domain_at(A, A.dom_begin + (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), grids...));
+        // where this lane works: subdomain s, its trace dofs, the dofs of its element's nodes
+        auto locate = [&](int tid, int &s, int &fdof, const int *&sI)
+        {
+            if constexpr (sizeof...(Grids) > 0)
+                s = s_wave;
+            else
+                s = domain_at(A, A.dom_begin + (int)blockIdx.x * 4 + (tid >> 6));
+            fdof = A.s_fdof[s];
+            sI = A.sI + 1024 * (size_t)s + 16 * (tid & 63);
+        };
+        int s, fdof;
+        const int *sI;
+        locate(threadIdx.x, s, fdof, sI);
+        // the time grid first, while few vector registers are live: what stays of it is scalar
+        const TimeGridView<float> tg = time_grid_of(A, s, filt, cs, sn, grids...);
+        const int lane = threadIdx.x & 63, ex = lane & 7, ey = lane >> 3;
+
+        float invm[16], Hi[16], F[16], Gf[16], u[16], v[16];
+#pragma unroll
+        for (int n = 0; n < 16; ++n)
+        {
+            load_dof(A, s, sI[n], fdof, invm[n], Hi[n], F[n], Gf[n]);
+            fold_weight(Sep4[48 + n], Sep4[64 + n], invm[n], Hi[n], F[n], Gf[n]);
+        }
+        float Bx[16], By[16], Dg[16]; // wave-uniform: scalar registers for the whole time loop
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+        {
+            Bx[i] = Sep4[i];      // Bx(k, j) at k + 4 j
+            By[i] = Sep4[16 + i]; // By(l, j) at l + 4 j
+            Dg[i] = Sep4[32 + i]; // Dg(k, l) at k + 4 l
+        }
+        const float mR = ex < 7 ? 1.0f : 0.0f, mL = ex > 0 ? 1.0f : 0.0f, mU = ey < 7 ? 1.0f : 0.0f, mD = ey > 0 ? 1.0f : 0.0f;
+        const int above = (lane + 8) & 63, below = (lane + 56) & 63; // a lane without that neighbour reads a lane it masks out
+
+        auto sweep = [&](const float(&w)[16], float(&z)[16])
+        {
+            element_lane_products<4>(w, z, Bx, By, Dg);
+            // xi neighbours: my k == 3 column meets the k == 0 column of lane + 1 (and vice versa)
+            float hi[4] = {z[3], z[7], z[11], z[15]}, lo[4] = {z[0], z[4], z[8], z[12]};
+            element_assemble_xi_asm(hi, lo, mR, mL);
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+            {
+                z[3 + 4 * l] = hi[l];
+                z[0 + 4 * l] = lo[l];
+            }
+            // eta neighbours, on the xi-assembled values: my l == 3 row meets the l == 0 row of lane + 8 (and vice versa)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+            {
+                const float up = z[k + 12], dn = z[k];
+                const float from_above = __shfl(dn, above, 64), from_below = __shfl(up, below, 64);
+                z[k + 12] = up + mU * from_above;
+                z[k] = dn + mD * from_below;
+            }
+        };
+        wh_march<FORCED ? 2 : 1, element_interior_registers(4)>(A, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
+
+        // located a second time from a lane index the compiler cannot connect with the first, as in ddh_element_lane_kernel
+        // (with time grids the same for the subdomain in its scalar register: nothing derived from it waits through the loop)
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        if constexpr (sizeof...(Grids) > 0)
+            asm volatile("" : "+s"(s_wave));
+        locate(tid, s, fdof, sI);
+#pragma unroll
+        for (int n = 0; n < 16; ++n)
+            if (element_lane_owner<4, 8, LAST_COPY>(n, tid))
+                publish_dof(A, s, sI[n], fdof, u[n], v[n], false);
+    }
+} // namespace
+
+#endif

@@ -23,15 +23,21 @@ RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, 
                        # ddh_block_kernel got its launch bound as a fourth template argument; 256 is the bound it had
                        **{f"ddh_block_kernel<{real}, {nb}, {csr}>": f"ddh_block_kernel<{real}, {nb}, {csr}, 256>"
                           for real in ("float", "double") for nb in range(2, 11) for csr in ("false", "true")},
-                       # ddh_element_lane_kernel got PAIRED as a fourth template argument; false is the chains it had
-                       **{f"ddh_element_lane_kernel<{f}, {h}, {l}{g}>": f"ddh_element_lane_kernel<{f}, {h}, {l}, false{g}>"
+                       # ddh_element_lane_kernel got PAIRED as a fourth template argument (false is the chains it had), then NB as
+                       # the first, when ddh_element_lane5_kernel became its NB = 5 instantiations
+                       **{f"ddh_element_lane_kernel<{f}, {h}, {l}{g}>": f"ddh_element_lane_kernel<4, {f}, {h}, {l}, false{g}>"
+                          for f in ("false", "true") for h in ("false", "true") for l in ("false", "true") for g in ("", ", TimeGrids<float> ")},
+                       **{f"ddh_element_lane_kernel<{f}, {h}, {l}, {p}{g}>": f"ddh_element_lane_kernel<4, {f}, {h}, {l}, {p}{g}>"
+                          for f in ("false", "true") for h in ("false", "true") for l in ("false", "true") for p in ("false", "true")
+                          for g in ("", ", TimeGrids<float> ")},
+                       **{f"ddh_element_lane5_kernel<{f}, {h}, {l}{g}>": f"ddh_element_lane_kernel<5, {f}, {h}, {l}, false{g}>"
                           for f in ("false", "true") for h in ("false", "true") for l in ("false", "true") for g in ("", ", TimeGrids<float> ")}}}
 # instantiations that are another one plus (or with another) template argument, per file: (pattern, replacement) pairs applied to the
 # demangled name give the base.
 # A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
 DERIVED = {"ddh.hip": ((r", Rk4Scheme ?(?=>)|, TimeGrids<\w+> ?(?=>)", ""),
                        # the paired chains (PAIRED = true, one grid only) against the pinned ones
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+), true>", r"\1, false>"))}
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true>", r"\1, false>"))}
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 

@@ -1,4 +1,4 @@
-"""Cost per DDH::action at n_basis 5, block 4, fp32, a = 1: kernel 12 (ddh_element_lane5_kernel) against kernel 1
+"""Cost per DDH::action at n_basis 5, block 4, fp32, a = 1: kernel 12 (ddh_element_lane_kernel<5, ..>) against kernel 1
 (ddh_block_kernel) of the same build on the same plan inputs, in one process, alternating, timed with device events.
 usage: ddh_nb5_rates.py [--rounds N] [--reps N] [--limit SECONDS]            every size below, one child process each
        ddh_nb5_rates.py [--rounds N] [--reps N] --case NX OMEGA_OVER_PI      one size in this process

@@ -7,13 +7,14 @@ patches; op_mfma_kernel), applies each once -- the fused ones in both vector ord
 and, to DIR/plans.txt, the lines it prints: kernel() of every plan and, for the fused ones, the four byte figures (algorithmic, as
 laid out, affine, native ordering; the single operators expose none -- what theirs decides, the NT flag, is part of kernel()).
 `compare` reads the two traces (the rocpd database rocprofv3 leaves under DIR) and prints, dispatch by dispatch, kernel name,
-grid, workgroup and LDS bytes of both builds, whether they are the same, whether the saved results are (np.array_equal) and
-whether the plan lines are.
+grid, workgroup and LDS bytes of both builds, whether they are the same (names literally, after the declared renames in RENAMED
+have been applied to the build before), whether the saved results are (np.array_equal) and whether the plan lines are.
 `run-ddh DIR` does the same for the DDH local-solve kernels of csrc/kernels/ddh.hip (the list DDH below: one plan per resolved
 kernel, sweep form, chain order, with and without time grids and RK4); `compare` then lists every ddh_* dispatch, the plan
 creation's check kernels included."""
 import csv
 import os
+import re
 import sqlite3
 import sys
 from pathlib import Path
@@ -179,8 +180,22 @@ def dispatches(trace_dir: Path):
     return [r for r in rows if any(k in r[0] for k in ("helm_", "op_patch", "op_mfma", "op_border", "native_kernel", "ddh_"))]
 
 
+# kernels whose symbol changed: (pattern, replacement) pairs applied in this order to the names of the build before, which are then
+# compared literally.  ddh_element_lane5_kernel<F, H, L, ..> became ddh_element_lane_kernel<5, F, H, L, false, ..>, and
+# ddh_element_lane_kernel<F, H, L, P, ..> got NB = 4 as its first argument.
+RENAMED = ((r"ddh_element_lane5_kernel<(\w+, \w+, \w+)", r"ddh_element_lane_kernel<5, \1, false"),
+           (r"ddh_element_lane_kernel<((?:true|false), \w+, \w+, \w+)", r"ddh_element_lane_kernel<4, \1"))
+
+
+def renamed(row):
+    name = row[0]
+    for pattern, repl in RENAMED:
+        name = re.sub(pattern, repl, name)
+    return (name, *row[1:])
+
+
 def compare(old_dir: Path, new_dir: Path):
-    old, new = dispatches(old_dir), dispatches(new_dir)
+    old, new = [renamed(r) for r in dispatches(old_dir)], dispatches(new_dir)
     print(f"{len(old)} dispatches of the plan kernels before, {len(new)} after")
     print("dispatch | kernel | grid workgroup lds_bytes before | after | same")
     same = 0

@@ -1,4 +1,4 @@
-"""DDH kernel 12 (ddh_element_lane5_kernel): n_basis 5, block 4, fp32; lane = one element with its 25 nodes in
+"""DDH kernel 12 (ddh_element_lane_kernel<5, ..>): n_basis 5, block 4, fp32; lane = one element with its 25 nodes in
 registers, one subdomain per 16-lane row, four subdomains per wavefront, assembly by DPP row shifts.
 
 Shapes: 8 x 8 elements (2 x 2 subdomains: a cross point, exactly one wavefront, nt 1250) and 12 x 8 (3 x 2: rectangular
