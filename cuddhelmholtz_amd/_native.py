@@ -222,6 +222,18 @@ _sig("cuddh_hip_wave_lattice_gather_f64", ci, ci, vp, vp, vp, vp)
 _sig("cuddh_hip_wave_lattice_begin_f64", ci, ci, cd, vp, vp, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_wave_lattice_tile_x", ci)
 _sig("cuddh_hip_wave_lattice_tile_y", ci)
+# (the fp32 family: the same arguments, float vectors)
+_sig("cuddh_hip_wave32_rk2_a", ci, _wl, cd, cd, cd, *([vp] * 9))
+_sig("cuddh_hip_wave32_rk2_b", ci, _wl, cd, cd, cd, cd, *([vp] * 11))
+_sig("cuddh_hip_wave32_rk4_1", ci, _wl, cd, cd, cd, *([vp] * 11))
+_sig("cuddh_hip_wave32_rk4_2", ci, _wl, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave32_rk4_3", ci, _wl, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave32_rk4_4", ci, _wl, cd, cd, cd, cd, *([vp] * 13))
+_sig("cuddh_hip_wave32_load", ci, ci, vp, vp, vp, vp)
+_sig("cuddh_hip_wave32_begin", ci, ci, cd, vp, vp, vp, vp, vp, vp, vp, vp)
+_sig("cuddh_hip_wave32_store", ci, ci, vp, vp, vp, vp)
+_sig("cuddh_hip_wave32_tile_x", ci)
+_sig("cuddh_hip_wave32_tile_y", ci)
 
 # ---- handle layer (cuddh_capi.h)
 _sig("cuddh_last_error", cp)
@@ -354,6 +366,8 @@ _sig("cuddh_waveholtz_solution", ci, vp, vp, vp)
 _sig("cuddh_waveholtz_info", ci, vp, vp, vp, vp, ci)
 _sig("cuddh_waveholtz_create_sweep", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci, ci)
 _sig("cuddh_waveholtz_sweep", ci, vp)
+_sig("cuddh_waveholtz_create_precision", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci)
+_sig("cuddh_waveholtz_precision", ci, vp)
 _sig("cuddh_wave_lattice_map", ci, vp, vp, vp, vp)
 _sig("cuddh_wave_lattice_tables", ci, vp, vp, vp)
 

@@ -706,14 +706,19 @@ class WaveHoltz(_Operator):
     sweep "operator" (the default: a stiffness apply and a stage kernel per sweep) or "lattice": one launch per sweep does the
     stiffness stencil and the stage on lattice-ordered vectors (csrc/kernels/wave_lattice.hip).  "lattice" needs stiffness
     "lobatto" and a uniform rectangle mesh, which is detected; every method takes and returns vectors in the space's order.
-    A bad name, a coarsen outside its range, coarsen > 1 with "rk2", a bad ratio and "lattice" with "gauss" raise ValueError
-    before any native call; a mesh the lattice form cannot take raises ValueError with the native message."""
+    precision "f64" (the default) or "f32" (sweep "lattice" only): the lattice vectors are stored and the sweeps computed in fp32
+    (csrc/kernels/wave_lattice_f32.hip), half the march's memory and bytes per sweep.  z, f, b and the solution stay float64; y =
+    x - S x is formed in float64.  It is meant for tolerances around 1e-4: the fp32 operator's own defect is about 1e-6 relative,
+    so a solve to 1e-6 or below wants "f64".
+    A bad name, a coarsen outside its range, coarsen > 1 with "rk2", a bad ratio, "lattice" with "gauss" and "f32" without "lattice"
+    raise ValueError before any native call; a mesh the lattice form cannot take raises ValueError with the native message."""
 
     STIFFNESS = ("gauss", "lobatto")
     SWEEPS = ("operator", "lattice")
+    PRECISIONS = ("f64", "f32")
 
     def __init__(self, omega: float, h_a: np.ndarray, fem: H1Space, integrator: str = "rk2", coarsen: int | None = None, time_ratio=1,
-                 stiffness: str = "gauss", faces=None, sweep: str = "operator"):
+                 stiffness: str = "gauss", faces=None, sweep: str = "operator", precision: str = "f64"):
         scheme, coarsen = self._integrator(integrator, coarsen)
         ratio = self._ratio(time_ratio)
         if not isinstance(stiffness, str) or stiffness not in self.STIFFNESS:
@@ -722,6 +727,10 @@ class WaveHoltz(_Operator):
             raise ValueError(f"WaveHoltz: sweep must be 'operator' or 'lattice', not {sweep!r}")
         if sweep == "lattice" and stiffness != "lobatto":
             raise ValueError("WaveHoltz: sweep 'lattice' is the collocated stiffness; it needs stiffness 'lobatto'")
+        if not isinstance(precision, str) or precision not in self.PRECISIONS:
+            raise ValueError(f"WaveHoltz: precision must be 'f64' or 'f32', not {precision!r}")
+        if precision == "f32" and sweep != "lattice":
+            raise ValueError("WaveHoltz: precision 'f32' is an option of the lattice form; it needs sweep 'lattice'")
         if faces is not None:
             faces = np.asarray(faces)
             if faces.ndim != 1 or (faces.size and not np.issubdtype(faces.dtype, np.integer)):
@@ -732,9 +741,12 @@ class WaveHoltz(_Operator):
             raise ValueError(f"WaveHoltz: {h_a.size} coefficient values for {fem.size()} dofs")
         if not np.all(np.isfinite(h_a)) or not np.all(h_a > 0):
             raise ValueError("WaveHoltz: the coefficient a must be finite and positive")
-        h = lib.cuddh_waveholtz_create_sweep(float(omega), _h(h_a), fem._h, scheme, coarsen, ratio, self.STIFFNESS.index(stiffness),
-                                             None if faces is None else _h(faces), -1 if faces is None else int(faces.size),
-                                             self.SWEEPS.index(sweep))
+        args = (float(omega), _h(h_a), fem._h, scheme, coarsen, ratio, self.STIFFNESS.index(stiffness), None if faces is None else _h(faces),
+                -1 if faces is None else int(faces.size), self.SWEEPS.index(sweep))
+        if precision == "f64":
+            h = lib.cuddh_waveholtz_create_sweep(*args)
+        else:
+            h = lib.cuddh_waveholtz_create_precision(*args, self.PRECISIONS.index(precision))
         if not h and N.last_error().startswith("WaveHoltz error"):
             raise ValueError(f"WaveHoltz: {N.last_error()}")
         super().__init__(N.handle(h, "WaveHoltz"), (fem,), 2 * fem.size())
@@ -790,7 +802,7 @@ class WaveHoltz(_Operator):
         N.check_capi(lib.cuddh_waveholtz_info(self._h, _h(info), C.byref(dt), buf, 160), "WaveHoltz.info")
         return {"nt": int(info[0]), "dt": dt.value, "ratio": int(info[1]), "integrator": "rk4" if info[2] else "rk2", "coarsen": int(info[3]),
                 "sweeps_per_period": int(info[4]), "stiffness_kernel": buf.value.decode(),
-                "sweep": self.SWEEPS[lib.cuddh_waveholtz_sweep(self._h)]}
+                "sweep": self.SWEEPS[lib.cuddh_waveholtz_sweep(self._h)], "precision": self.PRECISIONS[lib.cuddh_waveholtz_precision(self._h)]}
 
     def solve(self, f, u, m: int = 20, maxit: int = 200, tol: float = 1e-6, orth: str = "mgs", augment: int = 0) -> "SolverOut":
         """rhs -> gmres from zero -> solution; u receives [Re U; Im U]"""

@@ -9,7 +9,11 @@
 // sweep = lattice (opt-in; collocated stiffness on a uniform rectangle mesh only): the state lives in lattice order and ONE launch
 // per sweep does the stiffness stencil and the stage (csrc/kernels/wave_lattice.hip); no StiffnessMatrix is built.  z, f and
 // every public vector keep the space's dof order: a period permutes them in and out.
-// Everything is fp64; all vectors are DEVICE pointers unless marked HOST.
+// precision = f32 (opt-in; the lattice form only): the march's thirteen lattice vectors are stored and the sweeps computed in
+// fp32 (csrc/kernels/wave_lattice_f32.hip), half the march's memory and bytes; z, f, b, the solution and y = x - S x stay fp64,
+// rounded once on the way into a period and converted once on the way out.  For tolerances around 1e-4: the fp32 operator's own
+// defect is about 1e-6 relative, so a solve to 1e-6 or below wants f64.
+// Everything else is fp64; all vectors are DEVICE pointers unless marked HOST.
 #ifndef CUDDH_AMD_WAVEHOLTZ_HPP
 #define CUDDH_AMD_WAVEHOLTZ_HPP
 
@@ -50,6 +54,14 @@ namespace cuddh
             lattice
         };
         Sweep sweep = operator_kernels;
+        /// f64 (the default) or f32: the lattice vectors and sweeps in fp32.  f32 needs sweep = lattice; anything else is refused
+        /// ("WaveHoltz error: precision: ...") before any allocation or launch
+        enum Precision
+        {
+            f64,
+            f32
+        };
+        Precision precision = f64;
         /// absorbing faces: HOST edge ids; n_faces < 0 (the default): every boundary edge, DDH's choice
         const int *h_faces = nullptr;
         int n_faces = -1;
@@ -91,9 +103,10 @@ namespace cuddh
         /// kernel and n_basis
         std::string stiffness_kernel() const;
         WaveHoltzOptions::Sweep sweep() const { return lat ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels; }
+        WaveHoltzOptions::Precision precision() const;
 
     private:
-        struct Lattice; // the lattice form's description, maps and second ps (waveholtz.cpp)
+        struct Lattice; // the lattice form's description, maps and second ps; in fp32 all its vectors (waveholtz.cpp)
         void lattice_period(const double *z_in, const double *f, double *z_out) const;
 
         const double omega;
@@ -105,7 +118,8 @@ namespace cuddh
         std::unique_ptr<StiffnessMatrix> K; // null in the lattice form
         std::unique_ptr<Lattice> lat;       // null in the operator form
         host_device_dvec invm, Hi;        // 1 / (a^2 m) and h a (zero off the absorbing faces), ndof each (lattice form: its slots)
-        // the march's state and stage vectors (each 16-byte aligned whatever ndof is, so that the stages take their 16-byte path)
+        // the march's state and stage vectors (each 16-byte aligned whatever ndof is, so that the stages take their 16-byte path);
+        // all but tmp stay empty in the fp32 lattice form
         mutable host_device_dvec w, p, q, u, v, ps, qs, aq, ap, F, G, tmp;
     };
 } // namespace cuddh

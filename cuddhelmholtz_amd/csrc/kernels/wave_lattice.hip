@@ -28,6 +28,7 @@
 // round robin over eight) gets a contiguous run of tiles, whose halos then meet in that XCD's L2.
 // n_basis 4 and 5 are compile-time; every other n_basis in [2, 8] shares an instantiation with loops of run-time length over
 // LDS (no register arrays, hence no scratch).
+#include "wave_lattice_common.hpp"
 #include "wave_stages.hpp"
 
 #include "cuddh_hip.h"
@@ -43,20 +44,9 @@ namespace
 #endif
     constexpr int TX = 128, TY = CUDDH_WAVE_LATTICE_TY; // nodes per tile; TX = 2 columns per lane
     constexpr int ROWS_PER_WAVE = TY / WAVES, UNROLL = 2;
-    constexpr int NB_MAX = 8, N_XCD = 8;
     static_assert(TX == 2 * WAVE && ROWS_PER_WAVE % UNROLL == 0, "a lane owns two columns; rows go in pairs");
 
-    struct Lattice
-    {
-        int Lx, Ly, stride, nb;
-        double cx, cy;
-        double T[(NB_MAX + 1) * 2 * NB_MAX]; // row r at r * 2 nb, offset d at d + H
-        double Wt[NB_MAX + 1];
-    };
-
-    __device__ inline int row_id(int i, int L, int nb) { return i == 0 ? nb - 1 : (i == L - 1 ? nb : i % (nb - 1)); }
-    __device__ inline int first_offset(int r, int nb) { return (r == 0 || r == nb) ? -(nb - 1) : (r == nb - 1 ? 0 : -r); }
-    __device__ inline int last_offset(int r, int nb) { return (r == 0 || r == nb - 1) ? nb - 1 : (r == nb ? 0 : nb - 1 - r); }
+    using Lattice = LatticeT<double>; // (wave_lattice_common.hpp, with the stencil's row ids and offset ranges)
 
     // PSLOT > 0: input PSLOT of the stage is the stencil input itself
     template <typename Stage, int PSLOT, bool FORCED, bool NT, int NBT>
@@ -196,51 +186,13 @@ namespace
 
     constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
 
-    // the kernel's view of the caller's description, or false
-    bool describe(const cuddh_wave_lattice *D, Lattice &L)
-    {
-        if (!D || D->nx < 1 || D->ny < 1 || D->n_basis < 2 || D->n_basis > NB_MAX)
-            return false;
-        const int nb = D->n_basis, H = nb - 1;
-        const long long Lx = static_cast<long long>(D->nx) * H + 1, Ly = static_cast<long long>(D->ny) * H + 1;
-        if (D->stride < Lx || (D->stride & 1) || D->stride * Ly > 0x7fffffffLL)
-            return false;
-        L = {};
-        L.Lx = static_cast<int>(Lx);
-        L.Ly = static_cast<int>(Ly);
-        L.stride = D->stride;
-        L.nb = nb;
-        L.cx = D->cx;
-        L.cy = D->cy;
-        const double *A = D->A, *w = D->w;
-        const int WP = 2 * nb;
-        auto T = [&](int r, int d) -> double & { return L.T[r * WP + d + H]; };
-        for (int d = -H; d <= H; ++d)
-        {
-            T(0, d) =d < 0 ? A[H * nb + H + d] : (d == 0 ? A[H * nb + H] + A[0] : A[d]);
-            if (d >= 0)
-                T(H, d) = A[d];
-            if (d <= 0)
-                T(H + 1, d) = A[H * nb + H + d];
-        }
-        for (int k = 1; k < H; ++k)
-            for (int d = -k; d <= H - k; ++d)
-                T(k, d) = A[k * nb + k + d];
-        L.Wt[0] = w[H] + w[0];
-        for (int k = 1; k < H; ++k)
-            L.Wt[k] = w[k];
-        L.Wt[H] = w[0];
-        L.Wt[H + 1] = w[H];
-        return true;
-    }
-
     // in[0]: the stencil input; F, G: both given (forced) or both null (homogeneous)
     template <typename Stage, int PSLOT>
     int launch_lattice(const cuddh_wave_lattice *D, const double *const (&in)[Stage::NIN], const double *F, const double *G,
                        double *const (&out)[Stage::NOUT], const double (&coef)[MAX_COEF], void *stream)
     {
         Lattice L;
-        if (!describe(D, L) || (F == nullptr) != (G == nullptr))
+        if (!describe(D, 2, L) || (F == nullptr) != (G == nullptr))
             return invalid_value;
         const bool forced = F != nullptr;
         StageArgs a = {};

@@ -548,8 +548,17 @@ extern "C"
     void *cuddh_waveholtz_create_sweep(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
                                        const int *h_faces, int n_faces, int sweep)
     {
+        return cuddh_waveholtz_create_precision(omega, h_a, fem, integrator, coarsen, time_ratio, stiffness, h_faces, n_faces, sweep, 0);
+    }
+    void *cuddh_waveholtz_create_precision(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                           const int *h_faces, int n_faces, int sweep, int precision)
+    {
         return guarded_new<OpHandle>([&]
         {
+            if (precision != 0 && precision != 1)
+                throw std::runtime_error("WaveHoltz error: precision: the precision must be 0 (f64) or 1 (f32), not " + std::to_string(precision) + ".");
+            if (precision == 1 && sweep == 0)
+                throw std::runtime_error("WaveHoltz error: precision: f32 is an option of the lattice form; it needs sweep = 1 (lattice).");
             if (sweep != 0 && sweep != 1)
                 throw std::runtime_error("WaveHoltz error: sweep: the form must be 0 (operator kernels) or 1 (lattice), not " + std::to_string(sweep) + ".");
             if (integrator != 0 && integrator != 1)
@@ -563,6 +572,7 @@ extern "C"
             o.h_faces = h_faces;
             o.n_faces = n_faces;
             o.sweep = sweep == 1 ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels;
+            o.precision = precision == 1 ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64;
             auto h = new OpHandle;
             h->op.reset(new WaveHoltz(omega, h_a, *static_cast<H1Space *>(fem), o));
             return h;
@@ -609,6 +619,12 @@ extern "C"
         int form = -1;
         guarded([&] { form = waveholtz_of(op).sweep() == WaveHoltzOptions::lattice ? 1 : 0; });
         return form;
+    }
+    int cuddh_waveholtz_precision(void *op)
+    {
+        int precision = -1;
+        guarded([&] { precision = waveholtz_of(op).precision() == WaveHoltzOptions::f32 ? 1 : 0; });
+        return precision;
     }
     int cuddh_wave_lattice_map(void *fem, int *h_dims, double *h_h, int *h_node_of)
     {

@@ -1,6 +1,7 @@
 // Whole-domain WaveHoltz (cuddh/waveholtz.hpp): set-up on the host, the march as stiffness applies and the stage kernels of
 // csrc/kernels/waveholtz.hip (cuddh_hip_wave_stage_*), one launch of each per sweep; or, in the lattice form, as the kernels of
-// csrc/kernels/wave_lattice.hip (cuddh_hip_wave_lattice_*), one launch per sweep on lattice-ordered vectors.
+// csrc/kernels/wave_lattice.hip (cuddh_hip_wave_lattice_*), one launch per sweep on lattice-ordered vectors; with precision = f32
+// the same call sequence on the fp32 family of csrc/kernels/wave_lattice_f32.hip (cuddh_hip_wave32_*).
 #include "cuddh/waveholtz.hpp"
 
 #include <algorithm>
@@ -37,6 +38,10 @@ namespace cuddh
                 cuddh_error("WaveHoltz error: sweep: the form must be operator_kernels or lattice.");
             if (o.sweep == WaveHoltzOptions::lattice && o.stiffness != WaveHoltzOptions::lobatto)
                 cuddh_error("WaveHoltz error: sweep: the lattice form is the collocated stiffness; it needs stiffness = lobatto.");
+            if (o.precision != WaveHoltzOptions::f64 && o.precision != WaveHoltzOptions::f32)
+                cuddh_error("WaveHoltz error: precision: the precision must be f64 or f32.");
+            if (o.precision == WaveHoltzOptions::f32 && o.sweep != WaveHoltzOptions::lattice)
+                cuddh_error("WaveHoltz error: precision: f32 is an option of the lattice form; it needs sweep = lattice.");
         }
 
         host_device_dvec rule_weights(const QuadratureRule &quad)
@@ -47,14 +52,117 @@ namespace cuddh
                 h[i] = quad.w(i);
             return w;
         }
+
+        /// The two kernel families of the lattice form behind one set of names: R = double is cuddh_hip_wave_lattice_*_f64 (and
+        /// cuddh_hip_gather_f64 on the way out), R = float is cuddh_hip_wave32_*.
+        template <typename R>
+        struct LatticeKernels;
+        template <>
+        struct LatticeKernels<double>
+        {
+            static constexpr auto load = cuddh_hip_wave_lattice_gather_f64;
+            static constexpr auto store = cuddh_hip_gather_f64;
+            static constexpr auto begin = cuddh_hip_wave_lattice_begin_f64;
+            static constexpr auto rk2_a = cuddh_hip_wave_lattice_rk2_a_f64;
+            static constexpr auto rk2_b = cuddh_hip_wave_lattice_rk2_b_f64;
+            static constexpr auto rk4_1 = cuddh_hip_wave_lattice_rk4_1_f64;
+            static constexpr auto rk4_2 = cuddh_hip_wave_lattice_rk4_2_f64;
+            static constexpr auto rk4_3 = cuddh_hip_wave_lattice_rk4_3_f64;
+            static constexpr auto rk4_4 = cuddh_hip_wave_lattice_rk4_4_f64;
+        };
+        template <>
+        struct LatticeKernels<float>
+        {
+            static constexpr auto load = cuddh_hip_wave32_load;
+            static constexpr auto store = cuddh_hip_wave32_store;
+            static constexpr auto begin = cuddh_hip_wave32_begin;
+            static constexpr auto rk2_a = cuddh_hip_wave32_rk2_a;
+            static constexpr auto rk2_b = cuddh_hip_wave32_rk2_b;
+            static constexpr auto rk4_1 = cuddh_hip_wave32_rk4_1;
+            static constexpr auto rk4_2 = cuddh_hip_wave32_rk4_2;
+            static constexpr auto rk4_3 = cuddh_hip_wave32_rk4_3;
+            static constexpr auto rk4_4 = cuddh_hip_wave32_rk4_4;
+        };
+
+        /// the lattice vectors of one period (DEVICE); F, G null without a load; PS2, AQ, AP used by rk4 only
+        template <typename R>
+        struct LatticeVectors
+        {
+            R *P, *Q, *U, *V, *PS, *QS, *PS2, *AQ, *AP, *F, *G;
+            const R *IM, *HI;
+        };
+
+        /// what a period reads besides its vectors
+        struct LatticeGrid
+        {
+            const cuddh_wave_lattice *D;
+            int slots, ndof, nt;
+            bool rk4;
+            double dt;
+            const double *filt, *cs, *sn; // HOST
+            const int *dof_of_slot, *slot_of_dof;
+            void *stream;
+        };
+
+        template <typename R>
+        void lattice_march(const LatticeGrid &g, const LatticeVectors<R> &x, const double *z_in, const double *f, double *z_out)
+        {
+            using Kn = LatticeKernels<R>;
+            const int n = g.slots, ndof = g.ndof;
+            const cuddh_wave_lattice *D = g.D;
+            const char *what = "WaveHoltz::period (lattice)";
+            void *st = g.stream;
+            const double dt = g.dt, *filt = g.filt, *cs = g.cs, *sn = g.sn;
+            R *P = x.P, *Q = x.Q, *U = x.U, *V = x.V, *PS = x.PS, *QS = x.QS;
+            const R *IM = x.IM, *HI = x.HI, *Ff = nullptr, *Gf = nullptr;
+            if (f)
+            {
+                detail::check_hip(Kn::load(n, g.dof_of_slot, f, x.F, st), what);
+                detail::check_hip(Kn::load(n, g.dof_of_slot, f + ndof, x.G, st), what);
+                Ff = x.F;
+                Gf = x.G;
+            }
+            if (z_in)
+                detail::check_hip(Kn::begin(n, filt[0], g.dof_of_slot, z_in, z_in + ndof, P, Q, U, V, st), what);
+            else
+                for (R *y : {P, Q, U, V})
+                    zeros(n, y);
+
+            if (!g.rk4)
+            {
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    detail::check_hip(Kn::rk2_a(D, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
+                    detail::check_hip(Kn::rk2_b(D, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+                }
+            }
+            else
+            {
+                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2;
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    const int k = 2 * it - 2;
+                    detail::check_hip(Kn::rk4_1(D, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::rk4_2(D, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::rk4_3(D, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::rk4_4(D, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+                }
+            }
+            detail::check_hip(Kn::store(ndof, g.slot_of_dof, U, z_out, st), what);
+            detail::check_hip(Kn::store(ndof, g.slot_of_dof, V, z_out + ndof, st), what);
+        }
     } // namespace
 
     struct WaveHoltz::Lattice
     {
         cuddh_wave_lattice desc = {};
-        int slots = 0;                              // doubles per lattice vector: stride * Ly
+        int slots = 0;                              // elements per lattice vector: stride * Ly
         host_device_ivec dof_of_slot, slot_of_dof;  // slots (-1: padding) and ndof
         mutable host_device_dvec ps2;               // rk4_2 and rk4_3 read the stencil of one ps and write the other
+        // precision = f32: the thirteen lattice vectors as floats (the class's double ones then stay empty)
+        bool f32 = false;
+        HostDeviceArray<float> invm, Hi;
+        mutable HostDeviceArray<float> p, q, u, v, ps, qs, ps2f, aq, ap, F, G;
     };
 
     WaveHoltz::WaveHoltz(double omega_, const double *h_a, const H1Space &fem, const WaveHoltzOptions &o)
@@ -85,22 +193,28 @@ namespace cuddh
             if (fem.basis().size() > 8)
                 cuddh_error("WaveHoltz error: sweep: the lattice kernels take n_basis up to 8.");
             const WaveLatticeMap map = build_wave_lattice_map(fem);
+            // rows of the fp32 form hold a multiple of four floats (16 bytes), those of the fp64 form the map's even stride
+            const bool f32 = o.precision == WaveHoltzOptions::f32;
+            const int stride = f32 ? (map.Lx + 3) / 4 * 4 : map.stride;
+            if (static_cast<long long>(stride) * map.Ly > 0x7fffffffLL)
+                cuddh_error("WaveHoltz error: precision: the padded fp32 lattice does not fit in an int.");
             lat.reset(new Lattice);
+            lat->f32 = f32;
             lat->desc.nx = map.nx;
             lat->desc.ny = map.ny;
             lat->desc.n_basis = map.n_basis;
-            lat->desc.stride = map.stride;
+            lat->desc.stride = stride;
             lat->desc.cx = map.hy / map.hx;
             lat->desc.cy = map.hx / map.hy;
             wave_lattice_tables(fem.basis(), lat->desc.A, lat->desc.w);
-            lat->slots = map.slots();
+            lat->slots = stride * map.Ly;
             lat->dof_of_slot.resize(lat->slots);
             lat->slot_of_dof.resize(ndof);
             int *dos = lat->dof_of_slot.host_write(), *sod = lat->slot_of_dof.host_write();
             std::fill(dos, dos + lat->slots, -1);
             for (int g = 0; g < ndof; ++g)
             {
-                sod[g] = map.slot_of(g);
+                sod[g] = map.node_of[g] % map.Lx + stride * (map.node_of[g] / map.Lx);
                 dos[sod[g]] = g;
             }
         }
@@ -177,6 +291,28 @@ namespace cuddh
 
         const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
         int nvec = ndof;
+        if (lat && lat->f32)
+        {
+            // invm and Hi, set up in double above, into lattice order as floats; the padding slots get zero.  The class's double
+            // lattice vectors are not allocated.
+            const int n = lat->slots;
+            const int *dos = lat->dof_of_slot.device_read();
+            lat->invm.resize(n);
+            lat->Hi.resize(n);
+            detail::check_hip(cuddh_hip_wave32_load(n, dos, invm.device_read(), lat->invm.device_write(), stream()), "WaveHoltz lattice order");
+            detail::check_hip(cuddh_hip_wave32_load(n, dos, Hi.device_read(), lat->Hi.device_write(), stream()), "WaveHoltz lattice order");
+            detail::check_hip(cuddh_hip_stream_sync(stream()), "WaveHoltz setup"); // the dof-ordered vectors die here
+            invm.resize(0);
+            Hi.resize(0);
+            lat->slot_of_dof.device_read();
+            for (HostDeviceArray<float> *x : {&lat->p, &lat->q, &lat->u, &lat->v, &lat->ps, &lat->qs})
+                x->resize(n);
+            if (rk4)
+                for (HostDeviceArray<float> *x : {&lat->ps2f, &lat->aq, &lat->ap})
+                    x->resize(n);
+            tmp.resize(2 * ndof);
+            return;
+        }
         if (lat)
         {
             // invm and Hi into lattice order; the padding slots get zero
@@ -212,62 +348,41 @@ namespace cuddh
         if (!lat)
             return K->kernel_name();
         const int nb = lat->desc.n_basis;
-        return "wave_lattice nb" + std::to_string(nb) + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
+        return "wave_lattice nb" + std::to_string(nb) + (lat->f32 ? " f32" : "") + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
     }
+
+    WaveHoltzOptions::Precision WaveHoltz::precision() const { return lat && lat->f32 ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64; }
 
     void WaveHoltz::lattice_period(const double *z_in, const double *f, double *z_out) const
     {
         const int n = lat->slots;
-        const cuddh_wave_lattice *D = &lat->desc;
-        const char *what = "WaveHoltz::period (lattice)";
-        void *st = stream();
-        const int *dos = lat->dof_of_slot.device_read();
-        double *P = p.device_write(), *Q = q.device_write(), *U = u.device_write(), *V = v.device_write();
-        double *PS = ps.device_write(), *QS = qs.device_write();
-        const double *IM = invm.device_read(), *HI = Hi.device_read();
-        const double *Ff = nullptr, *Gf = nullptr;
-        if (f)
+        const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
+        const LatticeGrid g = {&lat->desc, n, ndof, nt, rk4, dt, filt.data(), cs.data(), sn.data(), lat->dof_of_slot.device_read(),
+                               lat->slot_of_dof.device_read(), stream()};
+        if (lat->f32)
         {
-            if (F.size() != n)
+            Lattice &L = *lat;
+            if (f && L.F.size() != n)
             {
-                F.resize(n);
-                G.resize(n);
+                L.F.resize(n);
+                L.G.resize(n);
             }
-            double *dF = F.device_write(), *dG = G.device_write();
-            detail::check_hip(cuddh_hip_wave_lattice_gather_f64(n, dos, f, dF, st), what);
-            detail::check_hip(cuddh_hip_wave_lattice_gather_f64(n, dos, f + ndof, dG, st), what);
-            Ff = dF;
-            Gf = dG;
+            const LatticeVectors<float> x = {L.p.device_write(), L.q.device_write(), L.u.device_write(), L.v.device_write(), L.ps.device_write(),
+                                             L.qs.device_write(), rk4 ? L.ps2f.device_write() : nullptr, rk4 ? L.aq.device_write() : nullptr,
+                                             rk4 ? L.ap.device_write() : nullptr, f ? L.F.device_write() : nullptr,
+                                             f ? L.G.device_write() : nullptr, L.invm.device_read(), L.Hi.device_read()};
+            return lattice_march(g, x, z_in, f, z_out);
         }
-        if (z_in)
-            detail::check_hip(cuddh_hip_wave_lattice_begin_f64(n, filt[0], dos, z_in, z_in + ndof, P, Q, U, V, st), what);
-        else
-            for (double *x : {P, Q, U, V})
-                zeros(n, x);
-
-        if (scheme.scheme == DDHIntegrator::rk2)
+        if (f && F.size() != n)
         {
-            for (int it = 1; it <= nt; ++it)
-            {
-                detail::check_hip(cuddh_hip_wave_lattice_rk2_a_f64(D, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
-                detail::check_hip(cuddh_hip_wave_lattice_rk2_b_f64(D, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-            }
+            F.resize(n);
+            G.resize(n);
         }
-        else
-        {
-            double *AQ = aq.device_write(), *AP = ap.device_write(), *PS2 = lat->ps2.device_write();
-            for (int it = 1; it <= nt; ++it)
-            {
-                const int k = 2 * it - 2;
-                detail::check_hip(cuddh_hip_wave_lattice_rk4_1_f64(D, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                detail::check_hip(cuddh_hip_wave_lattice_rk4_2_f64(D, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
-                detail::check_hip(cuddh_hip_wave_lattice_rk4_3_f64(D, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                detail::check_hip(cuddh_hip_wave_lattice_rk4_4_f64(D, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-            }
-        }
-        const int *sod = lat->slot_of_dof.device_read();
-        detail::check_hip(cuddh_hip_gather_f64(ndof, sod, U, z_out, st), what);
-        detail::check_hip(cuddh_hip_gather_f64(ndof, sod, V, z_out + ndof, st), what);
+        const LatticeVectors<double> x = {p.device_write(), q.device_write(), u.device_write(), v.device_write(), ps.device_write(),
+                                          qs.device_write(), rk4 ? lat->ps2.device_write() : nullptr, rk4 ? aq.device_write() : nullptr,
+                                          rk4 ? ap.device_write() : nullptr, f ? F.device_write() : nullptr, f ? G.device_write() : nullptr,
+                                          invm.device_read(), Hi.device_read()};
+        lattice_march(g, x, z_in, f, z_out);
     }
 
     void WaveHoltz::period(const double *z_in, const double *f, double *z_out) const

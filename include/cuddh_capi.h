@@ -329,6 +329,17 @@ void *cuddh_waveholtz_create_sweep(double omega, const double *h_a, void *fem, i
                                    const int *h_faces, int n_faces, int sweep);
 /* the form of the sweep: 0 or 1 as above, -1 when op is not a WaveHoltz handle */
 int cuddh_waveholtz_sweep(void *op);
+/* cuddh_waveholtz_create_sweep with the precision of the march behind its arguments: 0 = f64 (what the two entry points above
+ * build), 1 = f32: the lattice form with its thirteen lattice vectors stored and its sweeps computed in fp32
+ * (cuddh_hip_wave32_*), half the march's memory.  z, f, b and u stay fp64 in the space's dof order; they are rounded
+ * once on the way into a period and converted once on the way out, and y = x - S x is formed in double.  The option is for
+ * tolerances around 1e-4: the fp32 operator's own defect is about 1e-6.  Any other value, or 1 with sweep = 0, is refused before
+ * anything is allocated (NULL, the message starts with "WaveHoltz error: precision:").  In that form cuddh_waveholtz_info's
+ * kernel is "wave_lattice nb<n_basis> f32". */
+void *cuddh_waveholtz_create_precision(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                       const int *h_faces, int n_faces, int sweep, int precision);
+/* the precision of the march: 0 or 1 as above, -1 when op is not a WaveHoltz handle */
+int cuddh_waveholtz_precision(void *op);
 /* The lattice behind a space on a uniform rectangle mesh (csrc/include/cuddh/wave_lattice.hpp; host code, no device is touched):
  * h_dims = {nx, ny, Lx, Ly, stride}, L = n (n_basis - 1) + 1 nodes per direction and stride = Lx rounded up to even, the doubles
  * per row of the lattice vectors; h_h = {hx, hy}; h_node_of (ndof): dof -> I + Lx J.  Each may be NULL.  The mesh qualifies when

@@ -632,6 +632,48 @@ int cuddh_hip_wave_lattice_begin_f64(int n, double filt0, const int *dof_of_slot
 int cuddh_hip_wave_lattice_tile_x(void);
 int cuddh_hip_wave_lattice_tile_y(void);
 
+/* ------------------------------------------------------------------ whole-domain WaveHoltz march: lattice sweeps in fp32
+ * csrc/kernels/wave_lattice_f32.hip, DESIGN 4.5.2.  The lattice sweeps above with state, stencil and stages stored and computed
+ * in float: the arguments of the cuddh_hip_wave_lattice_*_f64 entry points with float vectors.  Scalars stay double and are
+ * rounded to float once on the host.  The description is the same cuddh_wave_lattice: the host forms the stencil's tables from
+ * A and w in double exactly as for the fp64 kernels (an element-boundary node's centre coefficient is the double sum
+ * A[H][H] + A[0][0], the weight where two elements meet the double sum w[H] + w[0]) and then rounds every table entry, cx and cy
+ * to float.  In float, with fused multiply-adds (fmaf) in the orders stated above:
+ *     sx, sy from zero over ascending d;   (K p')(I, J) = fmaf(cx * Wy(J), sx, (cy * Wx(I)) * sy), the two products in float;
+ * every stage is the fp64 formula in float; the forced form with F = G = 0 gives the homogeneous bits; results depend on (I, J)
+ * only and are bitwise reproducible.
+ * Vectors have stride * Ly floats; stride >= Lx and stride % 4 == 0, every pointer 16-byte aligned.  The up to three columns from
+ * Lx on are padding as above (zero state, zero load, invm = 0; kept zero, never used by the stencil).  A bad description, a
+ * stride that is no multiple of 4 or below Lx, a misaligned or NULL pointer, F without G or an output that is the stencil's input
+ * return hipErrorInvalidValue (1) and nothing is launched. */
+int cuddh_hip_wave32_rk2_a(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const float *p, const float *q,
+                           const float *invm, const float *Hi, const float *F, const float *G, float *qh, float *ph, void *stream);
+int cuddh_hip_wave32_rk2_b(const cuddh_wave_lattice *lattice, double dt, double c, double s, double filt, const float *ph, const float *qh,
+                           const float *invm, const float *Hi, const float *F, const float *G, float *p, float *q, float *u, float *v,
+                           void *stream);
+int cuddh_hip_wave32_rk4_1(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const float *p, const float *q,
+                           const float *invm, const float *Hi, const float *F, const float *G, float *ps, float *qs, float *aq, float *ap,
+                           void *stream);
+int cuddh_hip_wave32_rk4_2(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const float *ps_in, const float *p,
+                           const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
+                           float *aq, float *ap, void *stream);
+int cuddh_hip_wave32_rk4_3(const cuddh_wave_lattice *lattice, double dt, double c, double s, const float *ps_in, const float *p,
+                           const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
+                           float *aq, float *ap, void *stream);
+int cuddh_hip_wave32_rk4_4(const cuddh_wave_lattice *lattice, double sixth_dt, double c, double s, double filt, const float *ps,
+                           const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi, const float *F,
+                           const float *G, float *p, float *q, float *u, float *v, void *stream);
+/* in and out of the fp32 lattice order, one rounding each way: load y[i] = (float) x[dof_of_slot[i]], 0 where dof_of_slot[i] < 0
+ * (padding), i < n; begin rounds zu, zv and filt0 and then does the stage `begin` in float; store y[g] = (double) x[slot_of_dof[g]],
+ * g < ndof */
+int cuddh_hip_wave32_load(int n, const int *dof_of_slot, const double *x, float *y, void *stream);
+int cuddh_hip_wave32_begin(int n, double filt0, const int *dof_of_slot, const double *zu, const double *zv, float *p, float *q, float *u,
+                           float *v, void *stream);
+int cuddh_hip_wave32_store(int ndof, const int *slot_of_dof, const float *x, double *y, void *stream);
+/* nodes of a workgroup's tile in x and y */
+int cuddh_hip_wave32_tile_x(void);
+int cuddh_hip_wave32_tile_y(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ neither copy carries the name it has in the tree) and prints, for every __global
 registers, scratch, LDS, the instruction count, whether the mnemonic histogram is the same and a sequence diff (mnemonics
 left unmatched by difflib's longest-matching-blocks alignment, removed + added: 0 = the same instructions in the same order,
 registers aside; a non-zero figure is an upper bound on what moved, not a minimal edit distance), and the same three for
-the blocks that lie inside loops (the time stepping, where these kernels spend their time).  A kernel that differs is to be
+the blocks that lie inside loops (the time stepping, where these kernels spend their time), and whether the instruction text, operands
+included (block labels renumbered per kernel), is the same line for line.  A kernel that differs is to be
 timed against the old build; same histogram does not mean same speed for kernels tuned on issue order."""
 import collections
 import difflib
@@ -32,6 +33,10 @@ RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, 
                           for g in ("", ", TimeGrids<float> ")},
                        **{f"ddh_element_lane5_kernel<{f}, {h}, {l}{g}>": f"ddh_element_lane_kernel<5, {f}, {h}, {l}, false{g}>"
                           for f in ("false", "true") for h in ("false", "true") for l in ("false", "true") for g in ("", ", TimeGrids<float> ")}}}
+# the same for names that changed by a rule, per file: (pattern, replacement) pairs applied to OLD's demangled name give NEW's.
+# wave_stages.hpp became a template on the scalar (round 26, fp32 lattice sweeps): Rk2A is now Rk2AT<double>
+_STAGE_RULES = ((r"\b(?:cuddh_k::wave::)?(Begin|Rk2A|Rk2B|Rk4First|Rk4Mid|Rk4Last)\b(?!T)", r"cuddh_k::wave::\1T<double>"),)
+RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES}
 # instantiations that are another one plus (or with another) template argument, per file: (pattern, replacement) pairs applied to the
 # demangled name give the base.
 # A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
@@ -52,17 +57,18 @@ def kernels(src: Path, out: Path, flags_of: str):
         sym = re.search(r"^\s*\.name:\s+(\S+)", entry, re.M).group(1)
         meta = {f: int(re.search(rf"^\s*{re.escape(f)}:\s+(\d+)", entry, re.M).group(1)) for f in FIELDS}
         body = text.split(f"\n{sym}:", 1)[1].split(".Lfunc_end", 1)[0]
-        ops, loop_ops, in_loop = [], [], False
+        ops, loop_ops, lines, in_loop = [], [], [], False
         for ln in body.splitlines():
             if ln.startswith((".LBB", "; %bb")):  # the compiler marks every block of a loop in the label's comment
                 in_loop = "Loop" in ln
             elif ln.startswith("\t") and ln[1:2] not in ("", ".", ";"):
                 ops.append(ln.split()[0])
+                lines.append(re.sub(r"\.LBB\d+_", ".LBB_", " ".join(ln.split(";")[0].split())))
                 if in_loop:
                     loop_ops.append(ops[-1])
         name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
         name = name.replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0]
-        found[name] = (meta, ops, loop_ops)
+        found[name] = (meta, ops, loop_ops, lines)
     return found
 
 
@@ -74,14 +80,17 @@ def main():
     old, new = kernels(Path(sys.argv[1]), keep / "old.s", flags_of), kernels(Path(sys.argv[2]), keep / "new.s", flags_of)
     print(f"{len(old)} kernels before, {len(new)} after")
     print("kernel | vgpr sgpr scratch lds before -> after | instructions before -> after | histogram | sequence diff | inside loops")
-    same = 0
+    same = same_text = 0
     old_in_new = {}  # NEW's version of the kernels OLD has
-    for name, (m0, o0, l0) in old.items():
+    for name, (m0, o0, l0, t0) in old.items():
         succ = name if name in new else renamed.get(name, name)
+        for pattern, repl in RENAMED_BY_RULE.get(flags_of, ()):
+            if succ not in new:
+                succ = re.sub(pattern, repl, succ)
         if succ not in new:
             print(f"{name} | MISSING after")
             continue
-        m1, o1, l1 = new.pop(succ)
+        m1, o1, l1, t1 = new.pop(succ)
         old_in_new[succ] = (m1, o1, l1)
         hist = collections.Counter(o0) == collections.Counter(o1)
         # mnemonics removed + added by a longest-matching-blocks alignment (autojunk off: a few dozen distinct values repeat
@@ -93,12 +102,13 @@ def main():
                 "DIFFERS " + " ".join(f"{k}:{c0[k]}->{c1[k]}" for k in sorted(set(c0) | set(c1)) if c0[k] != c1[k]))
         regs = lambda m: " ".join(str(m[f]) for f in FIELDS)  # noqa: E731
         same += m0 == m1 and hist and diff == 0
+        same_text += m0 == m1 and t0 == t1
         label = name if succ == name else f"{name} => {succ}"
-        print(f"{label} | {regs(m0)} -> {regs(m1)} | {len(o0)} -> {len(o1)} | {'same' if hist else 'DIFFERS'} | {diff} | {loops}")
+        print(f"{label} | {regs(m0)} -> {regs(m1)} | {len(o0)} -> {len(o1)} | {'same' if hist else 'DIFFERS'} | {diff} | {loops} | text {'same' if t0 == t1 else 'DIFFERS'}")
     all_new = {**{renamed.get(k, k): v for k, v in old_in_new.items()}, **new}
     derived = DERIVED.get(flags_of)
     valu = lambda c: sum(v for k, v in c.items() if k.startswith("v_"))  # noqa: E731
-    for name, (m1, o1, l1) in new.items():  # a kernel the old file does not have: its registers and what its loops hold
+    for name, (m1, o1, l1, _) in new.items():  # a kernel the old file does not have: its registers and what its loops hold
         c1 = collections.Counter(l1)
         base = name
         for pattern, repl in derived or ():
@@ -112,7 +122,8 @@ def main():
             continue
         print(f"{name} | NEW after | {' '.join(str(m1[f]) for f in FIELDS)} | {len(o1)} instructions, {len(l1)} inside loops: "
               + " ".join(f"{k}:{c1[k]}" for k in sorted(c1)))
-    print(f"{same} of {len(old)} kernels: same registers, same mnemonic sequence")
+    print(f"{same} of {len(old)} kernels: same registers, same mnemonic sequence; {same_text} of {len(old)}: same registers and the same instruction text, "
+          "operands included")
 
 
 if __name__ == "__main__":

@@ -18,6 +18,13 @@ lattice  (parts lattice_stages, lattice_period, lattice_solve; written for profi
          per sweep of sweep="lattice" against sweep="operator" with stiffness "lobatto" and "gauss", rk2 and rk4 / 4, alternating;
          one whole solve in the example's regime with sweep="lattice".
 
+lattice32 (parts lattice32_stages, lattice32_period, lattice32_solve; written for profiles/r26/wave_lattice_f32_rates.txt) precision="f32"
+         beside the f64 lattice form of the same build, alternating in one run (csrc/kernels/wave_lattice_f32.hip): us of
+         every cuddh_hip_wave32_* launch beside its cuddh_hip_wave_lattice_*_f64 twin, and axpby_f32 beside axpby_f64; TB/s on 4 B
+         (f32) or 8 B (f64) per vector read or written per lattice slot, the vector counts above; ms per homogeneous period and us
+         per sweep of both precisions, rk2 and rk4 / 4, and how far the two results are apart; the example-regime solve at both
+         precisions: matvecs, seconds, and the residual of the f32 solution in the f64 operator.
+
   python profiles/tools/waveholtz_rates.py [parts=stages,period,solve] [sizes=256,512,1024] [solve_sizes=256,512] [reps=7] [out=profiles/r24/waveholtz_rates.txt]
 """
 import ctypes as C
@@ -328,9 +335,121 @@ def lattice_solve(nx):
         f"{ {256: '256 matvecs, 5.15 s', 512: '499 matvecs, 24.58 s', 1024: '985 matvecs, 173.87 s'}.get(nx, 'not recorded')}")
 
 
+def lattice_description(nx, multiple):
+    """the cuddh_wave_lattice of nx x nx elements on [-1, 1]^2 with rows of a multiple of `multiple` elements"""
+    Lx = nx * (NB - 1) + 1
+    D = N.WaveLattice()
+    D.nx, D.ny, D.n_basis, D.stride, D.cx, D.cy = nx, nx, NB, -(-Lx // multiple) * multiple, 1.0, 1.0
+    A, w, basis = np.zeros((NB, NB)), np.zeros(NB), cd.Basis(NB)
+    N.check_capi(N.lib.cuddh_wave_lattice_tables(basis._h, A.ctypes.data, w.ctypes.data))
+    for i, x in enumerate(A.reshape(-1)):
+        D.A[i] = x
+    for i, x in enumerate(w):
+        D.w[i] = x
+    return D, Lx
+
+
+def lattice32_stages(nx):
+    L, st = N.lib, stream()
+    dt = 1e-9  # (the timed launches repeat on the same vectors: keep them bounded)
+    fs, slots = {}, {}
+    keep = []
+    for tag, dtype, multiple in (("f64", torch.float64, 2), ("f32", torch.float32, 4)):
+        D, Lx = lattice_description(nx, multiple)
+        m = D.stride * Lx
+        slots[tag] = m
+        g = torch.Generator(device=dev).manual_seed(1)
+        v = {k: torch.randn(m, dtype=dtype, device=dev, generator=g) for k in ("p", "q", "u", "v", "ps", "ps2", "qs", "aq", "ap", "zu", "zv")}
+        v["invm"] = torch.rand(m, dtype=dtype, device=dev, generator=g) + 0.5
+        v["Hi"] = torch.zeros(m, dtype=dtype, device=dev)
+        if D.stride > Lx:  # the padding columns: zero state, invm = 0
+            for t in v.values():
+                t.view(Lx, D.stride)[:, Lx:] = 0.0
+        a, d = {k: p(t) for k, t in v.items()}, C.byref(D)
+        keep.append((D, v))
+        fn = (lambda name: getattr(L, f"cuddh_hip_wave_lattice_{name}_f64")) if tag == "f64" else (lambda name: getattr(L, f"cuddh_hip_wave32_{name}"))
+        axpby = L.cuddh_hip_axpby_f64 if tag == "f64" else L.cuddh_hip_axpby_f32
+        fs[f"axpby {tag}"] = lambda a=a, m=m, axpby=axpby: N.check(axpby(m, 1e-6, a["zu"], 1.0, a["zv"], st))
+        fs[f"rk2_a {tag}"] = lambda a=a, d=d, fn=fn: N.check(fn("rk2_a")(d, dt / 2, 1.0, 0.0, a["p"], a["q"], a["invm"], a["Hi"], None, None, a["qs"], a["ps"], st))
+        fs[f"rk2_b {tag}"] = lambda a=a, d=d, fn=fn: N.check(fn("rk2_b")(d, dt, 1.0, 0.0, 1e-3, a["ps"], a["qs"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st))
+        fs[f"rk4_1 {tag}"] = lambda a=a, d=d, fn=fn: N.check(fn("rk4_1")(d, dt / 2, 1.0, 0.0, a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st))
+        fs[f"rk4_2 {tag}"] = lambda a=a, d=d, fn=fn: N.check(fn("rk4_2")(d, dt / 2, 1.0, 0.0, a["ps"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps2"], a["qs"], a["aq"], a["ap"], st))
+        fs[f"rk4_3 {tag}"] = lambda a=a, d=d, fn=fn: N.check(fn("rk4_3")(d, dt, 1.0, 0.0, a["ps2"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st))
+        fs[f"rk4_4 {tag}"] = lambda a=a, d=d, fn=fn: N.check(fn("rk4_4")(d, dt / 6, 1.0, 0.0, 1e-3, a["ps"], a["qs"], a["aq"], a["ap"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st))
+    fs = {f"{k} {tag}": fs[f"{k} {tag}"] for k in ("axpby", *LATTICE_VECTORS) for tag in ("f64", "f32")}  # twins side by side
+    t = timed(fs, inner=20)
+    say(f"lattice32 stages nx={nx} slots f64 {slots['f64']} ({8 * slots['f64'] / 1e6:.1f} MB per vector), f32 {slots['f32']} ({4 * slots['f32'] / 1e6:.1f} MB per vector); "
+        f"tiles f64 {L.cuddh_hip_wave_lattice_tile_x()} x {L.cuddh_hip_wave_lattice_tile_y()}, f32 {L.cuddh_hip_wave32_tile_x()} x {L.cuddh_hip_wave32_tile_y()}")
+    size = {"f64": 8, "f32": 4}
+    for k in ("axpby", *LATTICE_VECTORS):
+        vectors = LATTICE_VECTORS.get(k, STAGE_VECTORS["axpby"])
+        text = []
+        for tag in ("f64", "f32"):
+            med, lo, hi = t[f"{k} {tag}"]
+            text.append(f"{tag} {1e3 * med:8.1f} us (min {1e3 * lo:.1f} max {1e3 * hi:.1f}) {vectors * size[tag] * slots[tag] / (med * 1e-3) / 1e12:5.2f} TB/s")
+        say(f"  {k:6s} {vectors:2d} vectors  " + "   ".join(text) + f"   f32 / f64 time {t[f'{k} f32'][0] / t[f'{k} f64'][0]:.3f}")
+    for scheme, names in (("rk2", ("rk2_a", "rk2_b")), ("rk4", ("rk4_1", "rk4_2", "rk4_3", "rk4_4"))):
+        per = {tag: sum(t[f"{k} {tag}"][0] for k in names) / len(names) for tag in ("f64", "f32")}
+        say(f"  us per sweep {scheme}: f64 {1e3 * per['f64']:.1f}, f32 {1e3 * per['f32']:.1f}, f32 / f64 {per['f32'] / per['f64']:.3f}")
+    del keep
+
+
+def lattice32_period(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    g = torch.Generator(device=dev).manual_seed(2)
+    z = torch.randn(2 * n, dtype=torch.float64, device=dev, generator=g)
+    for scheme, coarsen in (("rk2", None), ("rk4", 4)):
+        Ws = {tag: cd.WaveHoltz(omega, np.ones(n), fem, integrator=scheme, coarsen=coarsen, stiffness="lobatto", sweep="lattice", precision=tag)
+              for tag in ("f64", "f32")}
+        out = {k: torch.empty_like(z) for k in Ws}
+        for k, W in Ws.items():
+            W.period(z, None, out[k])
+        torch.cuda.synchronize()
+        diff = float(torch.linalg.norm(out["f32"] - out["f64"]) / torch.linalg.norm(out["f64"]))
+        sweeps = Ws["f64"].info()["sweeps_per_period"]
+        t = timed({k: (lambda W=W, k=k: W.period(z, None, out[k])) for k, W in Ws.items()}, inner=1)
+        text = "; ".join(f"{k} {t[k][0]:.2f} ms (min {t[k][1]:.2f} max {t[k][2]:.2f}) = {1e3 * t[k][0] / sweeps:.1f} us per sweep [{Ws[k].info()['stiffness_kernel']}]" for k in Ws)
+        say(f"lattice32 period nx={nx} ndof={n} {scheme} nt={Ws['f64'].info()['nt']} ({sweeps} sweeps): {text}; f32 / f64 {t['f32'][0] / t['f64'][0]:.3f}; "
+            f"the two periods differ by {diff:.2e}")
+        del Ws, out
+
+
+def lattice32_solve(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    f = torch.zeros(2 * n, dtype=torch.float64, device=dev)
+    a = torch.zeros(n, dtype=torch.float64, device=dev)
+    cd.linear_functional(fem, cd.GAUSSIANS, f[:n], param=omega)
+    cd.linear_functional(fem, cd.ALPHA_DISK, a)
+    cd.DiagInvMassMatrix(fem).action(a, a)
+    Ws = {tag: cd.WaveHoltz(omega, a.cpu().numpy(), fem, integrator="rk4", coarsen=4, stiffness="lobatto", sweep="lattice", precision=tag) for tag in ("f64", "f32")}
+    b64, y = torch.empty_like(f), torch.empty_like(f)
+    Ws["f64"].rhs(f, b64)
+    for tag, W in Ws.items():
+        b, z = torch.empty_like(f), torch.zeros_like(f)
+        W.rhs(f, b)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = cd.gmres(2 * n, z, W, b, 20, 400, 1e-4, max_seconds=300.0)
+        torch.cuda.synchronize()
+        sec = time.perf_counter() - t0
+        Ws["f64"].action(z, y)
+        true_res = float(torch.linalg.norm(b64 - y) / torch.linalg.norm(b64))
+        info = W.info()
+        say(f"lattice32 solve nx={nx} ndof={n} omega={omega:.2f} disk coefficient rk4/4 nt={info['nt']} GMRES(20) tol 1e-4 precision={tag} [{info['stiffness_kernel']}]: "
+            f"success={out.success} matvecs={out.num_matvec} cycles={out.num_iter} rel_res={out.res_norm[-1] / out.res_norm[0]:.3e} "
+            f"residual in the f64 operator={true_res:.3e} seconds={sec:.2f} ms_per_period={1e3 * sec / max(1, out.num_matvec):.2f} "
+            f"us_per_sweep={1e6 * sec / max(1, out.num_matvec) / info['sweeps_per_period']:.1f} finite={bool(torch.isfinite(z).all())}")
+
+
 say(f"waveholtz_rates: {torch.cuda.get_device_name(0)}, n_basis {NB}, a == 1, omega = 2 pi nx / 10, reps {reps}")
 for part, fn, ns in (("stages", stages, sizes), ("period", period, sizes), ("solve", solve, solve_sizes), ("lattice_stages", lattice_stages, sizes),
-                     ("lattice_period", lattice_period, sizes), ("lattice_solve", lattice_solve, solve_sizes)):
+                     ("lattice_period", lattice_period, sizes), ("lattice_solve", lattice_solve, solve_sizes),
+                     ("lattice32_stages", lattice32_stages, sizes), ("lattice32_period", lattice32_period, sizes),
+                     ("lattice32_solve", lattice32_solve, solve_sizes)):
     if part in parts:
         for nx in ns:
             fn(nx)
