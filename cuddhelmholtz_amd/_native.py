@@ -234,6 +234,18 @@ _sig("cuddh_hip_wave32_begin", ci, ci, cd, vp, vp, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_wave32_store", ci, ci, vp, vp, vp, vp)
 _sig("cuddh_hip_wave32_tile_x", ci)
 _sig("cuddh_hip_wave32_tile_y", ci)
+# (two sweeps per launch: seven or five scalars, then the vectors and the stream)
+_sig("cuddh_hip_wave_pair_rk2_f64", ci, _wl, *([cd] * 7), *([vp] * 11))
+_sig("cuddh_hip_wave_pair_rk4_12_f64", ci, _wl, *([cd] * 5), *([vp] * 11))
+_sig("cuddh_hip_wave_pair_rk4_34_f64", ci, _wl, *([cd] * 7), *([vp] * 14))
+_sig("cuddh_hip_wave_pair_tile_x", ci)
+_sig("cuddh_hip_wave_pair_tile_y", ci)
+_sig("cuddh_hip_wave_pair_tile_y_run_time", ci)
+_sig("cuddh_hip_wave_pair32_rk2", ci, _wl, *([cd] * 7), *([vp] * 11))
+_sig("cuddh_hip_wave_pair32_rk4_12", ci, _wl, *([cd] * 5), *([vp] * 11))
+_sig("cuddh_hip_wave_pair32_rk4_34", ci, _wl, *([cd] * 7), *([vp] * 14))
+_sig("cuddh_hip_wave_pair32_tile_x", ci)
+_sig("cuddh_hip_wave_pair32_tile_y", ci)
 
 # ---- handle layer (cuddh_capi.h)
 _sig("cuddh_last_error", cp)
@@ -368,6 +380,8 @@ _sig("cuddh_waveholtz_create_sweep", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci, ci)
 _sig("cuddh_waveholtz_sweep", ci, vp)
 _sig("cuddh_waveholtz_create_precision", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci)
 _sig("cuddh_waveholtz_precision", ci, vp)
+_sig("cuddh_waveholtz_create_launch", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci)
+_sig("cuddh_waveholtz_launch", ci, vp)
 _sig("cuddh_wave_lattice_map", ci, vp, vp, vp, vp)
 _sig("cuddh_wave_lattice_tables", ci, vp, vp, vp)
 

@@ -710,15 +710,19 @@ class WaveHoltz(_Operator):
     (csrc/kernels/wave_lattice_f32.hip), half the march's memory and bytes per sweep.  z, f, b and the solution stay float64; y =
     x - S x is formed in float64.  It is meant for tolerances around 1e-4: the fp32 operator's own defect is about 1e-6 relative,
     so a solve to 1e-6 or below wants "f64".
-    A bad name, a coarsen outside its range, coarsen > 1 with "rk2", a bad ratio, "lattice" with "gauss" and "f32" without "lattice"
+    launch "sweep" (the default: one launch per sweep) or "pair" (sweep "lattice" only, either precision): two sweeps per launch
+    (csrc/kernels/wave_pair.hip, wave_pair_f32.hip): rk2_a with rk2_b, rk4_1 with rk4_2, rk4_3 with rk4_4.  The march is the
+    per-sweep one bit for bit, in half the launches and about half the bytes.  Nothing selects "pair" by itself.
+    A bad name, a coarsen outside its range, coarsen > 1 with "rk2", a bad ratio, "lattice" with "gauss" and "f32" or "pair" without "lattice"
     raise ValueError before any native call; a mesh the lattice form cannot take raises ValueError with the native message."""
 
     STIFFNESS = ("gauss", "lobatto")
     SWEEPS = ("operator", "lattice")
     PRECISIONS = ("f64", "f32")
+    LAUNCHES = ("sweep", "pair")
 
     def __init__(self, omega: float, h_a: np.ndarray, fem: H1Space, integrator: str = "rk2", coarsen: int | None = None, time_ratio=1,
-                 stiffness: str = "gauss", faces=None, sweep: str = "operator", precision: str = "f64"):
+                 stiffness: str = "gauss", faces=None, sweep: str = "operator", precision: str = "f64", launch: str = "sweep"):
         scheme, coarsen = self._integrator(integrator, coarsen)
         ratio = self._ratio(time_ratio)
         if not isinstance(stiffness, str) or stiffness not in self.STIFFNESS:
@@ -731,6 +735,10 @@ class WaveHoltz(_Operator):
             raise ValueError(f"WaveHoltz: precision must be 'f64' or 'f32', not {precision!r}")
         if precision == "f32" and sweep != "lattice":
             raise ValueError("WaveHoltz: precision 'f32' is an option of the lattice form; it needs sweep 'lattice'")
+        if not isinstance(launch, str) or launch not in self.LAUNCHES:
+            raise ValueError(f"WaveHoltz: launch must be 'sweep' or 'pair', not {launch!r}")
+        if launch == "pair" and sweep != "lattice":
+            raise ValueError("WaveHoltz: launch 'pair' is an option of the lattice form; it needs sweep 'lattice'")
         if faces is not None:
             faces = np.asarray(faces)
             if faces.ndim != 1 or (faces.size and not np.issubdtype(faces.dtype, np.integer)):
@@ -743,7 +751,9 @@ class WaveHoltz(_Operator):
             raise ValueError("WaveHoltz: the coefficient a must be finite and positive")
         args = (float(omega), _h(h_a), fem._h, scheme, coarsen, ratio, self.STIFFNESS.index(stiffness), None if faces is None else _h(faces),
                 -1 if faces is None else int(faces.size), self.SWEEPS.index(sweep))
-        if precision == "f64":
+        if launch != "sweep":
+            h = lib.cuddh_waveholtz_create_launch(*args, self.PRECISIONS.index(precision), self.LAUNCHES.index(launch))
+        elif precision == "f64":
             h = lib.cuddh_waveholtz_create_sweep(*args)
         else:
             h = lib.cuddh_waveholtz_create_precision(*args, self.PRECISIONS.index(precision))
@@ -802,7 +812,8 @@ class WaveHoltz(_Operator):
         N.check_capi(lib.cuddh_waveholtz_info(self._h, _h(info), C.byref(dt), buf, 160), "WaveHoltz.info")
         return {"nt": int(info[0]), "dt": dt.value, "ratio": int(info[1]), "integrator": "rk4" if info[2] else "rk2", "coarsen": int(info[3]),
                 "sweeps_per_period": int(info[4]), "stiffness_kernel": buf.value.decode(),
-                "sweep": self.SWEEPS[lib.cuddh_waveholtz_sweep(self._h)], "precision": self.PRECISIONS[lib.cuddh_waveholtz_precision(self._h)]}
+                "sweep": self.SWEEPS[lib.cuddh_waveholtz_sweep(self._h)], "precision": self.PRECISIONS[lib.cuddh_waveholtz_precision(self._h)],
+                "launch": self.LAUNCHES[lib.cuddh_waveholtz_launch(self._h)]}
 
     def solve(self, f, u, m: int = 20, maxit: int = 200, tol: float = 1e-6, orth: str = "mgs", augment: int = 0) -> "SolverOut":
         """rhs -> gmres from zero -> solution; u receives [Re U; Im U]"""

@@ -5,7 +5,8 @@
 //   the ratio the coefficient asks for; 1 is the default), --stiffness gauss|lobatto (the sweep's quadrature, WaveHoltzOptions;
 //   gauss is the default), --sweep operator|lattice (lattice: one launch per sweep on the Gauss-Lobatto lattice; it implies
 //   --stiffness lobatto and refuses --stiffness gauss), --precision f64|f32 (f32: the lattice sweeps in fp32, for tolerances around
-//   1e-4; it goes with --sweep lattice only), --coefficient one|disk (a == 1, the default, or the examples' disk of a = 0.2, projected as in
+//   1e-4; it goes with --sweep lattice only), --launch sweep|pair (pair: two lattice sweeps per launch, the same march bit for bit;
+//   it goes with --sweep lattice only), --coefficient one|disk (a == 1, the default, or the examples' disk of a = 0.2, projected as in
 //   ddh_solve), --residuals (one more line: GMRES's residual history).
 // The load is the examples' pair of Gaussians in the real part and 0.1 (3 x^2 - 2 x y + y + 1) in the imaginary part.
 // Writes <out_dir>/xy.0000 and <out_dir>/waveholtz.0000 (raw fp64; "-": nothing) and prints one summary line.
@@ -22,7 +23,7 @@ using namespace cuddh;
 
 int main(int argc_all, char **argv_all)
 {
-    std::string integrator = "rk2", time_ratio = "1", stiffness = "", coefficient = "one", sweep = "operator", precision = "f64";
+    std::string integrator = "rk2", time_ratio = "1", stiffness = "", coefficient = "one", sweep = "operator", precision = "f64", launch = "sweep";
     int coarsen = 0; // 0: not given
     bool residuals = false;
     std::vector<char *> args;
@@ -41,6 +42,8 @@ int main(int argc_all, char **argv_all)
             sweep = argv_all[++i];
         else if (arg == "--precision" && i + 1 < argc_all)
             precision = argv_all[++i];
+        else if (arg == "--launch" && i + 1 < argc_all)
+            launch = argv_all[++i];
         else if (arg == "--coefficient" && i + 1 < argc_all)
             coefficient = argv_all[++i];
         else if (arg == "--residuals")
@@ -93,6 +96,16 @@ int main(int argc_all, char **argv_all)
         std::cerr << "waveholtz_solve: --precision f32 is the lattice sweeps in fp32: it goes with --sweep lattice only" << std::endl;
         return 2;
     }
+    if (launch != "sweep" && launch != "pair")
+    {
+        std::cerr << "waveholtz_solve: --launch takes sweep or pair, not " << launch << std::endl;
+        return 2;
+    }
+    if (launch == "pair" && sweep != "lattice")
+    {
+        std::cerr << "waveholtz_solve: --launch pair is two lattice sweeps per launch: it goes with --sweep lattice only" << std::endl;
+        return 2;
+    }
     if (coefficient != "one" && coefficient != "disk")
     {
         std::cerr << "waveholtz_solve: --coefficient takes one or disk, not " << coefficient << std::endl;
@@ -140,6 +153,7 @@ int main(int argc_all, char **argv_all)
     opt.stiffness = stiffness == "lobatto" ? WaveHoltzOptions::lobatto : WaveHoltzOptions::gauss;
     opt.sweep = sweep == "lattice" ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels;
     opt.precision = precision == "f32" ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64;
+    opt.launch = launch == "pair" ? WaveHoltzOptions::per_pair : WaveHoltzOptions::per_sweep;
     WaveHoltz W(omega, a.host_read(), fem, opt);
 
     // wall time of each phase with a device sync at both ends, as ddh_solve
@@ -169,7 +183,7 @@ int main(int argc_all, char **argv_all)
         unorm += h_U[i] * h_U[i];
     const double ms_per_period = out.num_matvec > 0 ? 1e3 * t_gmres / out.num_matvec : 0.0;
     std::cout << "waveholtz_solve nx=" << nx << " nb=" << nb << " omega/pi=" << omega / M_PI << " ndof=" << ndof << " integrator=" << integrator
-              << " coarsen=" << coarsen << " ratio=" << W.time_ratio() << " stiffness=" << stiffness << " sweep=" << sweep << " precision=" << precision << " coefficient=" << coefficient
+              << " coarsen=" << coarsen << " ratio=" << W.time_ratio() << " stiffness=" << stiffness << " sweep=" << sweep << " precision=" << precision << " launch=" << launch << " coefficient=" << coefficient
               << " nt=" << W.num_steps() << " sweeps_per_period=" << W.sweeps_per_period() << " success=" << out.success
               << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec << " rel_res=" << out.res_norm.back() / out.res_norm.front()
               << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs << " t_gmres=" << t_gmres << " ms_per_period=" << ms_per_period

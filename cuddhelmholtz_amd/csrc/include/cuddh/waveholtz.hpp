@@ -13,6 +13,9 @@
 // fp32 (csrc/kernels/wave_lattice_f32.hip), half the march's memory and bytes; z, f, b, the solution and y = x - S x stay fp64,
 // rounded once on the way into a period and converted once on the way out.  For tolerances around 1e-4: the fp32 operator's own
 // defect is about 1e-6 relative, so a solve to 1e-6 or below wants f64.
+// launch = per_pair (opt-in; the lattice form only, both precisions): two sweeps per launch (csrc/kernels/wave_pair.hip and
+// wave_pair_f32.hip): rk2_a with rk2_b, rk4_1 with rk4_2 and rk4_3 with rk4_4.  Half the launches, 0.56 x (RK2) and
+// 0.48 x (RK4) the vectors moved, and the bits of the per-sweep march.
 // Everything else is fp64; all vectors are DEVICE pointers unless marked HOST.
 #ifndef CUDDH_AMD_WAVEHOLTZ_HPP
 #define CUDDH_AMD_WAVEHOLTZ_HPP
@@ -62,6 +65,14 @@ namespace cuddh
             f32
         };
         Precision precision = f64;
+        /// per_sweep (the default): one launch per sweep.  per_pair: two sweeps of the lattice form per launch, bit for bit the same
+        /// march.  per_pair needs sweep = lattice; anything else is refused ("WaveHoltz error: launch: ...") before any allocation
+        enum Launch
+        {
+            per_sweep,
+            per_pair
+        };
+        Launch launch = per_sweep;
         /// absorbing faces: HOST edge ids; n_faces < 0 (the default): every boundary edge, DDH's choice
         const int *h_faces = nullptr;
         int n_faces = -1;
@@ -104,6 +115,7 @@ namespace cuddh
         std::string stiffness_kernel() const;
         WaveHoltzOptions::Sweep sweep() const { return lat ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels; }
         WaveHoltzOptions::Precision precision() const;
+        WaveHoltzOptions::Launch launch() const;
 
     private:
         struct Lattice; // the lattice form's description, maps and second ps; in fp32 all its vectors (waveholtz.cpp)

@@ -553,8 +553,18 @@ extern "C"
     void *cuddh_waveholtz_create_precision(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
                                            const int *h_faces, int n_faces, int sweep, int precision)
     {
+        return cuddh_waveholtz_create_launch(omega, h_a, fem, integrator, coarsen, time_ratio, stiffness, h_faces, n_faces, sweep, precision, 0);
+    }
+    void *cuddh_waveholtz_create_launch(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                        const int *h_faces, int n_faces, int sweep, int precision, int launch)
+    {
         return guarded_new<OpHandle>([&]
         {
+            if (launch != 0 && launch != 1)
+                throw std::runtime_error("WaveHoltz error: launch: the launch must be 0 (one per sweep) or 1 (one per pair of sweeps), not " +
+                                         std::to_string(launch) + ".");
+            if (launch == 1 && sweep != 1)
+                throw std::runtime_error("WaveHoltz error: launch: pairs of sweeps are an option of the lattice form; they need sweep = 1 (lattice).");
             if (precision != 0 && precision != 1)
                 throw std::runtime_error("WaveHoltz error: precision: the precision must be 0 (f64) or 1 (f32), not " + std::to_string(precision) + ".");
             if (precision == 1 && sweep == 0)
@@ -573,6 +583,7 @@ extern "C"
             o.n_faces = n_faces;
             o.sweep = sweep == 1 ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels;
             o.precision = precision == 1 ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64;
+            o.launch = launch == 1 ? WaveHoltzOptions::per_pair : WaveHoltzOptions::per_sweep;
             auto h = new OpHandle;
             h->op.reset(new WaveHoltz(omega, h_a, *static_cast<H1Space *>(fem), o));
             return h;
@@ -625,6 +636,12 @@ extern "C"
         int precision = -1;
         guarded([&] { precision = waveholtz_of(op).precision() == WaveHoltzOptions::f32 ? 1 : 0; });
         return precision;
+    }
+    int cuddh_waveholtz_launch(void *op)
+    {
+        int launch = -1;
+        guarded([&] { launch = waveholtz_of(op).launch() == WaveHoltzOptions::per_pair ? 1 : 0; });
+        return launch;
     }
     int cuddh_wave_lattice_map(void *fem, int *h_dims, double *h_h, int *h_node_of)
     {

@@ -1,12 +1,14 @@
 // Whole-domain WaveHoltz (cuddh/waveholtz.hpp): set-up on the host, the march as stiffness applies and the stage kernels of
 // csrc/kernels/waveholtz.hip (cuddh_hip_wave_stage_*), one launch of each per sweep; or, in the lattice form, as the kernels of
 // csrc/kernels/wave_lattice.hip (cuddh_hip_wave_lattice_*), one launch per sweep on lattice-ordered vectors; with precision = f32
-// the same call sequence on the fp32 family of csrc/kernels/wave_lattice_f32.hip (cuddh_hip_wave32_*).
+// the same call sequence on the fp32 family of csrc/kernels/wave_lattice_f32.hip (cuddh_hip_wave32_*); with launch = per_pair two
+// sweeps per launch (csrc/kernels/wave_pair.hip and wave_pair_f32.hip: cuddh_hip_wave_pair_*, cuddh_hip_wave_pair32_*).
 #include "cuddh/waveholtz.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <utility>
 
 #include "cuddh/time_grid.hpp"
 #include "cuddh/wave_lattice.hpp"
@@ -42,6 +44,10 @@ namespace cuddh
                 cuddh_error("WaveHoltz error: precision: the precision must be f64 or f32.");
             if (o.precision == WaveHoltzOptions::f32 && o.sweep != WaveHoltzOptions::lattice)
                 cuddh_error("WaveHoltz error: precision: f32 is an option of the lattice form; it needs sweep = lattice.");
+            if (o.launch != WaveHoltzOptions::per_sweep && o.launch != WaveHoltzOptions::per_pair)
+                cuddh_error("WaveHoltz error: launch: the launch must be per_sweep or per_pair.");
+            if (o.launch == WaveHoltzOptions::per_pair && o.sweep != WaveHoltzOptions::lattice)
+                cuddh_error("WaveHoltz error: launch: per_pair is an option of the lattice form; it needs sweep = lattice.");
         }
 
         host_device_dvec rule_weights(const QuadratureRule &quad)
@@ -69,6 +75,9 @@ namespace cuddh
             static constexpr auto rk4_2 = cuddh_hip_wave_lattice_rk4_2_f64;
             static constexpr auto rk4_3 = cuddh_hip_wave_lattice_rk4_3_f64;
             static constexpr auto rk4_4 = cuddh_hip_wave_lattice_rk4_4_f64;
+            static constexpr auto pair_rk2 = cuddh_hip_wave_pair_rk2_f64;
+            static constexpr auto pair_rk4_12 = cuddh_hip_wave_pair_rk4_12_f64;
+            static constexpr auto pair_rk4_34 = cuddh_hip_wave_pair_rk4_34_f64;
         };
         template <>
         struct LatticeKernels<float>
@@ -82,6 +91,9 @@ namespace cuddh
             static constexpr auto rk4_2 = cuddh_hip_wave32_rk4_2;
             static constexpr auto rk4_3 = cuddh_hip_wave32_rk4_3;
             static constexpr auto rk4_4 = cuddh_hip_wave32_rk4_4;
+            static constexpr auto pair_rk2 = cuddh_hip_wave_pair32_rk2;
+            static constexpr auto pair_rk4_12 = cuddh_hip_wave_pair32_rk4_12;
+            static constexpr auto pair_rk4_34 = cuddh_hip_wave_pair32_rk4_34;
         };
 
         /// the lattice vectors of one period (DEVICE); F, G null without a load; PS2, AQ, AP used by rk4 only
@@ -97,7 +109,7 @@ namespace cuddh
         {
             const cuddh_wave_lattice *D;
             int slots, ndof, nt;
-            bool rk4;
+            bool rk4, pair;
             double dt;
             const double *filt, *cs, *sn; // HOST
             const int *dof_of_slot, *slot_of_dof;
@@ -128,7 +140,34 @@ namespace cuddh
                 for (R *y : {P, Q, U, V})
                     zeros(n, y);
 
-            if (!g.rk4)
+            if (g.pair && !g.rk4)
+            {
+                // two sweeps per launch (wave_pair.hip): p and q are read with a halo, so a step writes the other pair of buffers
+                R *P2 = PS, *Q2 = QS;
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    detail::check_hip(Kn::pair_rk2(D, 0.5 * dt, dt, cs[2 * it - 2], sn[2 * it - 2], cs[2 * it - 1], sn[2 * it - 1], filt[it], P, Q, IM,
+                                                   HI, Ff, Gf, P2, Q2, U, V, st),
+                                      what);
+                    std::swap(P, P2);
+                    std::swap(Q, Q2);
+                }
+            }
+            else if (g.pair)
+            {
+                // rk4_1 with rk4_2, then rk4_3 with rk4_4; the second launch reads p with a halo and writes the other p
+                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2, *P2 = PS;
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    const int k = 2 * it - 2;
+                    detail::check_hip(Kn::pair_rk4_12(D, 0.5 * dt, cs[k], sn[k], cs[k + 1], sn[k + 1], P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::pair_rk4_34(D, dt, dt / 6.0, cs[k + 1], sn[k + 1], cs[k + 2], sn[k + 2], filt[it], PS2, P, QS, AQ, AP, IM, HI,
+                                                      Ff, Gf, P2, Q, U, V, st),
+                                      what);
+                    std::swap(P, P2);
+                }
+            }
+            else if (!g.rk4)
             {
                 for (int it = 1; it <= g.nt; ++it)
                 {
@@ -161,6 +200,7 @@ namespace cuddh
         mutable host_device_dvec ps2;               // rk4_2 and rk4_3 read the stencil of one ps and write the other
         // precision = f32: the thirteen lattice vectors as floats (the class's double ones then stay empty)
         bool f32 = false;
+        bool pair = false;                          // launch = per_pair: two sweeps per launch (wave_pair.hip)
         HostDeviceArray<float> invm, Hi;
         mutable HostDeviceArray<float> p, q, u, v, ps, qs, ps2f, aq, ap, F, G;
     };
@@ -200,6 +240,7 @@ namespace cuddh
                 cuddh_error("WaveHoltz error: precision: the padded fp32 lattice does not fit in an int.");
             lat.reset(new Lattice);
             lat->f32 = f32;
+            lat->pair = o.launch == WaveHoltzOptions::per_pair;
             lat->desc.nx = map.nx;
             lat->desc.ny = map.ny;
             lat->desc.n_basis = map.n_basis;
@@ -348,16 +389,18 @@ namespace cuddh
         if (!lat)
             return K->kernel_name();
         const int nb = lat->desc.n_basis;
-        return "wave_lattice nb" + std::to_string(nb) + (lat->f32 ? " f32" : "") + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
+        return std::string(lat->pair ? "wave_pair nb" : "wave_lattice nb") + std::to_string(nb) + (lat->f32 ? " f32" : "") + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
     }
 
     WaveHoltzOptions::Precision WaveHoltz::precision() const { return lat && lat->f32 ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64; }
+
+    WaveHoltzOptions::Launch WaveHoltz::launch() const { return lat && lat->pair ? WaveHoltzOptions::per_pair : WaveHoltzOptions::per_sweep; }
 
     void WaveHoltz::lattice_period(const double *z_in, const double *f, double *z_out) const
     {
         const int n = lat->slots;
         const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
-        const LatticeGrid g = {&lat->desc, n, ndof, nt, rk4, dt, filt.data(), cs.data(), sn.data(), lat->dof_of_slot.device_read(),
+        const LatticeGrid g = {&lat->desc, n, ndof, nt, rk4, lat->pair, dt, filt.data(), cs.data(), sn.data(), lat->dof_of_slot.device_read(),
                                lat->slot_of_dof.device_read(), stream()};
         if (lat->f32)
         {

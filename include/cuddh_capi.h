@@ -340,6 +340,15 @@ void *cuddh_waveholtz_create_precision(double omega, const double *h_a, void *fe
                                        const int *h_faces, int n_faces, int sweep, int precision);
 /* the precision of the march: 0 or 1 as above, -1 when op is not a WaveHoltz handle */
 int cuddh_waveholtz_precision(void *op);
+/* cuddh_waveholtz_create_precision with the launches of the lattice march behind its arguments: 0 = one launch per sweep (what the
+ * entry points above build), 1 = one launch per pair of sweeps (cuddh_hip_wave_pair_*, cuddh_hip_wave_pair32_*):
+ * rk2_a with rk2_b, rk4_1 with rk4_2, rk4_3 with rk4_4, in either precision.  The march is the per-sweep one bit for bit, in half
+ * the launches.  Any other value, or 1 without sweep = 1, is refused before anything is allocated (NULL, the message starts with
+ * "WaveHoltz error: launch:").  In that form cuddh_waveholtz_info's kernel is "wave_pair nb<n_basis>" ("... f32"). */
+void *cuddh_waveholtz_create_launch(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                    const int *h_faces, int n_faces, int sweep, int precision, int launch);
+/* the launches of the march: 0 or 1 as above, -1 when op is not a WaveHoltz handle */
+int cuddh_waveholtz_launch(void *op);
 /* The lattice behind a space on a uniform rectangle mesh (csrc/include/cuddh/wave_lattice.hpp; host code, no device is touched):
  * h_dims = {nx, ny, Lx, Ly, stride}, L = n (n_basis - 1) + 1 nodes per direction and stride = Lx rounded up to even, the doubles
  * per row of the lattice vectors; h_h = {hx, hy}; h_node_of (ndof): dof -> I + Lx J.  Each may be NULL.  The mesh qualifies when

@@ -674,6 +674,48 @@ int cuddh_hip_wave32_store(int ndof, const int *slot_of_dof, const float *x, dou
 int cuddh_hip_wave32_tile_x(void);
 int cuddh_hip_wave32_tile_y(void);
 
+/* ------------------------------------------------------------------ whole-domain WaveHoltz march: two lattice sweeps per launch
+ * csrc/kernels/wave_pair.hip (fp64) and wave_pair_f32.hip (fp32), DESIGN 4.5.3.  The stencil input of the second sweep of a pair
+ * is pointwise in vectors that exist before the first one: ph = fma(-half_dt, q, p) in rk2_b and rk4_2, fma(-dt, qs, p) in rk4_4
+ * (qs the vector rk4_2 wrote).  One launch therefore stages two tiles, takes two stencils and runs two stages:
+ *   rk2     = wave_lattice rk2_a then rk2_b          (c0, s0 of the first, c1, s1 of the second)
+ *   rk4_12  = wave_lattice rk4_1 then rk4_2          writes ps2 = fma(-half_dt, qs1, p), qs, aq, ap
+ *   rk4_34  = wave_lattice rk4_3 (h = dt) then rk4_4 reads the ps2, qs, aq, ap that rk4_12 wrote; q, u, v are updated in place
+ * with the lattice, layout, padding, stencil and stage formulas of the entry points above, operation by operation: the results
+ * equal those of the two launches bit for bit.  The scalars the march forms (dt / 2, dt / 6) are arguments of their own.
+ * A vector that is read with a halo (p and q in rk2 and rk4_12; ps2, p and qs in rk4_34) is still needed by neighbouring
+ * workgroups and cannot be an output: rk2 writes p_out, q_out and rk4_34 writes p_out out of place.  A bad description, a stride
+ * that is no multiple of 2 (fp64) or 4 (fp32), a misaligned or NULL pointer, F without G or an output that is read with a halo
+ * return hipErrorInvalidValue (1) and nothing is launched. */
+int cuddh_hip_wave_pair_rk2_f64(const cuddh_wave_lattice *lattice, double half_dt, double dt, double c0, double s0, double c1, double s1,
+                                double filt, const double *p, const double *q, const double *invm, const double *Hi, const double *F,
+                                const double *G, double *p_out, double *q_out, double *u, double *v, void *stream);
+int cuddh_hip_wave_pair_rk4_12_f64(const cuddh_wave_lattice *lattice, double half_dt, double c0, double s0, double c1, double s1,
+                                   const double *p, const double *q, const double *invm, const double *Hi, const double *F, const double *G,
+                                   double *ps2, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_pair_rk4_34_f64(const cuddh_wave_lattice *lattice, double dt, double sixth_dt, double c1, double s1, double c2, double s2,
+                                   double filt, const double *ps2, const double *p, const double *qs, const double *aq, const double *ap,
+                                   const double *invm, const double *Hi, const double *F, const double *G, double *p_out, double *q,
+                                   double *u, double *v, void *stream);
+/* nodes of a workgroup's tile in x and y: tile_y holds for n_basis 4 and 5, tile_y_run_time for every other n_basis (whose
+ * halo of 7 rows would put two tiles of tile_y rows above 64 KB of LDS) */
+int cuddh_hip_wave_pair_tile_x(void);
+int cuddh_hip_wave_pair_tile_y(void);
+int cuddh_hip_wave_pair_tile_y_run_time(void);
+/* the fp32 family: the same arguments with float vectors, scalars rounded to float once on the host (as cuddh_hip_wave32_*) */
+int cuddh_hip_wave_pair32_rk2(const cuddh_wave_lattice *lattice, double half_dt, double dt, double c0, double s0, double c1, double s1,
+                              double filt, const float *p, const float *q, const float *invm, const float *Hi, const float *F, const float *G,
+                              float *p_out, float *q_out, float *u, float *v, void *stream);
+int cuddh_hip_wave_pair32_rk4_12(const cuddh_wave_lattice *lattice, double half_dt, double c0, double s0, double c1, double s1, const float *p,
+                                 const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps2, float *qs,
+                                 float *aq, float *ap, void *stream);
+int cuddh_hip_wave_pair32_rk4_34(const cuddh_wave_lattice *lattice, double dt, double sixth_dt, double c1, double s1, double c2, double s2,
+                                 double filt, const float *ps2, const float *p, const float *qs, const float *aq, const float *ap,
+                                 const float *invm, const float *Hi, const float *F, const float *G, float *p_out, float *q, float *u,
+                                 float *v, void *stream);
+int cuddh_hip_wave_pair32_tile_x(void);
+int cuddh_hip_wave_pair32_tile_y(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,13 @@ lattice32 (parts lattice32_stages, lattice32_period, lattice32_solve; written fo
          per sweep of both precisions, rk2 and rk4 / 4, and how far the two results are apart; the example-regime solve at both
          precisions: matvecs, seconds, and the residual of the f32 solution in the f64 operator.
 
+pair     (parts pair_step, pair_period, pair_solve; written for profiles/r27/wave_pair_rates.txt) launch="pair" beside launch="sweep" of the
+         same build, alternating in one run (csrc/kernels/wave_pair.hip, wave_pair_f32.hip), fp64 and fp32, rk2 and rk4:
+         us per time step from the entry points (homogeneous form; two or four one-sweep launches against one or two paired ones,
+         the paired ones with the march's buffer swaps) and TB/s on the stated vectors (rk2 18 / 10, rk4 46 / 22 per slot and step);
+         ms per homogeneous period of the two solvers, whose results must be torch.equal; the example-regime solve with both.  The
+         byte model expects paired / per-sweep = 0.56 (rk2) and 0.48 (rk4).
+
   python profiles/tools/waveholtz_rates.py [parts=stages,period,solve] [sizes=256,512,1024] [solve_sizes=256,512] [reps=7] [out=profiles/r24/waveholtz_rates.txt]
 """
 import ctypes as C
@@ -445,11 +452,128 @@ def lattice32_solve(nx):
             f"us_per_sweep={1e6 * sec / max(1, out.num_matvec) / info['sweeps_per_period']:.1f} finite={bool(torch.isfinite(z).all())}")
 
 
+PAIR_VECTORS = {"rk2": (18, 10), "rk4": (46, 22)}  # per lattice slot and time step: per-sweep, paired
+
+
+def pair_step(nx):
+    L, st = N.lib, stream()
+    dt = 1e-9  # (the timed launches repeat on the same vectors: keep them bounded)
+    fs, slots, keep = {}, {}, []
+    for tag, dtype, multiple in (("f64", torch.float64, 2), ("f32", torch.float32, 4)):
+        D, Lx = lattice_description(nx, multiple)
+        m = D.stride * Lx
+        slots[tag] = m
+        g = torch.Generator(device=dev).manual_seed(1)
+        v = {k: torch.randn(m, dtype=dtype, device=dev, generator=g) for k in ("p", "q", "u", "v", "ps", "ps2", "qs", "aq", "ap")}
+        v["invm"] = torch.rand(m, dtype=dtype, device=dev, generator=g) + 0.5
+        v["Hi"] = torch.zeros(m, dtype=dtype, device=dev)
+        if D.stride > Lx:  # the padding columns: zero state, invm = 0
+            for t in v.values():
+                t.view(Lx, D.stride)[:, Lx:] = 0.0
+        a, d = {k: p(t) for k, t in v.items()}, C.byref(D)
+        keep.append((D, v))
+        one = (lambda name: getattr(L, f"cuddh_hip_wave_lattice_{name}_f64")) if tag == "f64" else (lambda name: getattr(L, f"cuddh_hip_wave32_{name}"))
+        two = (lambda name: getattr(L, f"cuddh_hip_wave_pair_{name}_f64")) if tag == "f64" else (lambda name: getattr(L, f"cuddh_hip_wave_pair32_{name}"))
+
+        def sweep_rk2(a=a, d=d, one=one):
+            N.check(one("rk2_a")(d, dt / 2, 1.0, 0.0, a["p"], a["q"], a["invm"], a["Hi"], None, None, a["qs"], a["ps"], st))
+            N.check(one("rk2_b")(d, dt, 1.0, 0.0, 1e-3, a["ps"], a["qs"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st))
+
+        def sweep_rk4(a=a, d=d, one=one):
+            N.check(one("rk4_1")(d, dt / 2, 1.0, 0.0, a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st))
+            N.check(one("rk4_2")(d, dt / 2, 1.0, 0.0, a["ps"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps2"], a["qs"], a["aq"], a["ap"], st))
+            N.check(one("rk4_3")(d, dt, 1.0, 0.0, a["ps2"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st))
+            N.check(one("rk4_4")(d, dt / 6, 1.0, 0.0, 1e-3, a["ps"], a["qs"], a["aq"], a["ap"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st))
+
+        state2, state4 = {"P": ("p", "ps"), "Q": ("q", "qs")}, {"P": ("p", "ps")}
+
+        def pair_rk2(a=a, d=d, two=two, s=state2):
+            (P, P2), (Q, Q2) = s["P"], s["Q"]
+            N.check(two("rk2")(d, dt / 2, dt, 1.0, 0.0, 1.0, 0.0, 1e-3, a[P], a[Q], a["invm"], a["Hi"], None, None, a[P2], a[Q2], a["u"], a["v"], st))
+            s["P"], s["Q"] = (P2, P), (Q2, Q)
+
+        def pair_rk4(a=a, d=d, two=two, s=state4):
+            P, P2 = s["P"]
+            N.check(two("rk4_12")(d, dt / 2, 1.0, 0.0, 1.0, 0.0, a[P], a["q"], a["invm"], a["Hi"], None, None, a["ps2"], a["qs"], a["aq"], a["ap"], st))
+            N.check(two("rk4_34")(d, dt, dt / 6, 1.0, 0.0, 1.0, 0.0, 1e-3, a["ps2"], a[P], a["qs"], a["aq"], a["ap"], a["invm"], a["Hi"], None, None,
+                                  a[P2], a["q"], a["u"], a["v"], st))
+            s["P"] = (P2, P)
+
+        fs.update({f"rk2 sweep {tag}": sweep_rk2, f"rk2 pair {tag}": pair_rk2, f"rk4 sweep {tag}": sweep_rk4, f"rk4 pair {tag}": pair_rk4})
+    t = timed(fs, inner=20)
+    say(f"pair step nx={nx} slots f64 {slots['f64']} ({8 * slots['f64'] / 1e6:.1f} MB per vector), f32 {slots['f32']} ({4 * slots['f32'] / 1e6:.1f} MB per vector); "
+        f"pair tiles f64 {L.cuddh_hip_wave_pair_tile_x()} x {L.cuddh_hip_wave_pair_tile_y()}, f32 {L.cuddh_hip_wave_pair32_tile_x()} x {L.cuddh_hip_wave_pair32_tile_y()}")
+    size = {"f64": 8, "f32": 4}
+    for scheme in ("rk2", "rk4"):
+        for tag in ("f64", "f32"):
+            (ms, ls, hs), (mp, lp, hp) = t[f"{scheme} sweep {tag}"], t[f"{scheme} pair {tag}"]
+            vs, vp = PAIR_VECTORS[scheme]
+            rate = lambda vectors, ms_: vectors * size[tag] * slots[tag] / (ms_ * 1e-3) / 1e12  # noqa: E731
+            say(f"  {scheme} {tag} us per time step: per-sweep {1e3 * ms:8.1f} (min {1e3 * ls:.1f} max {1e3 * hs:.1f}) {vs} vectors {rate(vs, ms):5.2f} TB/s;  "
+                f"paired {1e3 * mp:8.1f} (min {1e3 * lp:.1f} max {1e3 * hp:.1f}) {vp} vectors {rate(vp, mp):5.2f} TB/s;  paired / per-sweep {mp / ms:.3f} "
+                f"(byte model {vp / vs:.2f})")
+    del keep
+
+
+def pair_period(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    g = torch.Generator(device=dev).manual_seed(2)
+    z = torch.randn(2 * n, dtype=torch.float64, device=dev, generator=g)
+    for scheme, coarsen in (("rk2", None), ("rk4", 4)):
+        for tag in ("f64", "f32"):
+            Ws = {launch: cd.WaveHoltz(omega, np.ones(n), fem, integrator=scheme, coarsen=coarsen, stiffness="lobatto", sweep="lattice", precision=tag,
+                                       launch=launch) for launch in ("sweep", "pair")}
+            out = {k: torch.empty_like(z) for k in Ws}
+            for k, W in Ws.items():
+                W.period(z, None, out[k])
+            torch.cuda.synchronize()
+            same = torch.equal(out["sweep"], out["pair"])
+            info = Ws["pair"].info()
+            t = timed({k: (lambda W=W, k=k: W.period(z, None, out[k])) for k, W in Ws.items()}, inner=1)
+            text = "; ".join(f"{k} {t[k][0]:.2f} ms (min {t[k][1]:.2f} max {t[k][2]:.2f}) = {1e3 * t[k][0] / info['nt']:.1f} us per time step "
+                             f"[{Ws[k].info()['stiffness_kernel']}]" for k in Ws)
+            vs, vp = PAIR_VECTORS[scheme]
+            say(f"pair period nx={nx} ndof={n} {scheme} {tag} nt={info['nt']}: {text}; paired / per-sweep {t['pair'][0] / t['sweep'][0]:.3f} "
+                f"(byte model {vp / vs:.2f}); results bit-identical: {same}")
+            del Ws, out
+
+
+def pair_solve(nx):
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    f = torch.zeros(2 * n, dtype=torch.float64, device=dev)
+    a = torch.zeros(n, dtype=torch.float64, device=dev)
+    cd.linear_functional(fem, cd.GAUSSIANS, f[:n], param=omega)
+    cd.linear_functional(fem, cd.ALPHA_DISK, a)
+    cd.DiagInvMassMatrix(fem).action(a, a)
+    for tag in ("f64", "f32"):
+        sec, sol = {}, {}
+        for launch in ("sweep", "pair"):
+            W = cd.WaveHoltz(omega, a.cpu().numpy(), fem, integrator="rk4", coarsen=4, stiffness="lobatto", sweep="lattice", precision=tag, launch=launch)
+            b, z = torch.empty_like(f), torch.zeros_like(f)
+            W.rhs(f, b)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = cd.gmres(2 * n, z, W, b, 20, 400, 1e-4, max_seconds=300.0)
+            torch.cuda.synchronize()
+            sec[launch], sol[launch] = time.perf_counter() - t0, z
+            info = W.info()
+            say(f"pair solve nx={nx} ndof={n} omega={omega:.2f} disk coefficient rk4/4 nt={info['nt']} GMRES(20) tol 1e-4 precision={tag} launch={launch} "
+                f"[{info['stiffness_kernel']}]: success={out.success} matvecs={out.num_matvec} cycles={out.num_iter} rel_res={out.res_norm[-1] / out.res_norm[0]:.3e} "
+                f"seconds={sec[launch]:.2f} ms_per_period={1e3 * sec[launch] / max(1, out.num_matvec):.2f} finite={bool(torch.isfinite(z).all())}")
+            del W
+        say(f"pair solve nx={nx} {tag}: paired / per-sweep seconds {sec['pair'] / sec['sweep']:.3f}; solutions bit-identical: {torch.equal(sol['pair'], sol['sweep'])}")
+
+
 say(f"waveholtz_rates: {torch.cuda.get_device_name(0)}, n_basis {NB}, a == 1, omega = 2 pi nx / 10, reps {reps}")
 for part, fn, ns in (("stages", stages, sizes), ("period", period, sizes), ("solve", solve, solve_sizes), ("lattice_stages", lattice_stages, sizes),
                      ("lattice_period", lattice_period, sizes), ("lattice_solve", lattice_solve, solve_sizes),
                      ("lattice32_stages", lattice32_stages, sizes), ("lattice32_period", lattice32_period, sizes),
-                     ("lattice32_solve", lattice32_solve, solve_sizes)):
+                     ("lattice32_solve", lattice32_solve, solve_sizes), ("pair_step", pair_step, sizes), ("pair_period", pair_period, sizes),
+                     ("pair_solve", pair_solve, solve_sizes)):
     if part in parts:
         for nx in ns:
             fn(nx)
