@@ -186,9 +186,12 @@ _sig("cuddh_hip_ddh_plan_set_sweep_form", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_sweep_form", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_chain_order", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_chain_order", ci, vp)
+_sig("cuddh_hip_ddh_plan_set_forcing", ci, vp, ci)
+_sig("cuddh_hip_ddh_plan_forcing", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_owner_rule", ci, vp, ci)
 _sig("cuddh_element_lane_tables", ci, ci, vp, vp, vp)
 _sig("cuddh_ddh_resolve", ci, *([ci] * 13), vp)
+_sig("cuddh_ddh_resolve_forcing", ci, *([ci] * 14), vp)
 _sig("cuddh_hip_ddh_plan_set_time_grids", ci, vp, ci, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_time_grids", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_integrator", ci, vp, ci)
@@ -326,6 +329,8 @@ _sig("cuddh_ddh_set_sweep_form", ci, vp, ci)
 _sig("cuddh_ddh_sweep_form", ci, vp)
 _sig("cuddh_ddh_set_chain_order", ci, vp, ci)
 _sig("cuddh_ddh_chain_order", ci, vp)
+_sig("cuddh_ddh_set_forcing", ci, vp, ci)
+_sig("cuddh_ddh_forcing", ci, vp)
 _sig("cuddh_ddh_set_owner_rule", ci, vp, ci)
 
 

@@ -639,6 +639,20 @@ class DDH:
             N.check_capi(order, "DDH.chain_order")
         return order
 
+    def set_forcing(self, forcing: int = 0):
+        """Where the element-lane form's march applies the trace sources, for every launch of this plan: 0 auto (2 where form and
+        order are auto too and auto gave the paired chains, else 1), 1 in every WaveHoltz pass, 2 in the first pass only (the later
+        passes run a time loop without source terms and add the first pass's result; the last bits differ).  2 is refused where
+        chain order 2 is (cuddh_hip_ddh_plan_set_forcing)."""
+        N.check_capi(lib.cuddh_ddh_set_forcing(self._h, int(forcing)), "DDH.set_forcing")
+
+    def forcing(self) -> int:
+        """The forcing in effect: 1 every pass, 2 the first pass only; 0 where the paired chains are not in effect."""
+        forcing = lib.cuddh_ddh_forcing(self._h)
+        if forcing < 0:
+            N.check_capi(forcing, "DDH.forcing")
+        return forcing
+
     def set_owner_rule(self, last: bool):
         """Kernels 11, 12 and 13: the last copy of every node that elements share publishes instead of the first (a check: same results).
         Refused on any other kernel (cuddh_hip_ddh_plan_set_owner_rule)."""

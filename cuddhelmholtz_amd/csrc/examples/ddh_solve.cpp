@@ -15,7 +15,9 @@
 //   GMRES over the complex numbers on the trace vectors [lambda; mu]; real is the default; needs --orth mgs and --augment 0;
 //   single-process path only; the summary line names it when it is complex), --chain-order auto|pinned|paired (DDHCore::set_chain_order:
 //   the summation order of kernel 5's element-lane form; auto is the default; single-process path only; an order the plan cannot
-//   take ends the run; the summary line names the order asked for and the one in effect when it is not auto)
+//   take ends the run; the summary line names the order asked for and the one in effect when it is not auto),
+//   --forcing auto|every|first (DDHCore::set_forcing: where that form's march applies the trace sources, in every WaveHoltz pass
+//   or in the first only; the same rules and the same note as --chain-order)
 // Writes <out_dir>/xy.0000 and <out_dir>/ddh.0000 (raw fp64, like the reference) and prints one summary line.
 // devices >= 1: the same solve through cuddh::ddh_solve_multi_gpu (multigpu.hpp): subdomains sharded over that many GPUs of
 // this process, RCCL neighbour exchange; devices = 1 with force_rccl = 1 runs the communicator path on a one-GPU box;
@@ -35,7 +37,7 @@ using namespace cuddh;
 int main(int argc_all, char **argv_all)
 {
     // options out, positional arguments stay
-    std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs", arithmetic = "real", chain_order = "auto";
+    std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs", arithmetic = "real", chain_order = "auto", forcing = "auto";
     int coarsen = 0; // 0: not given
     int augment = 0, block = 0, kernel = 0;
     bool residuals = false, block_given = false;
@@ -57,6 +59,8 @@ int main(int argc_all, char **argv_all)
             arithmetic = argv_all[++i];
         else if (arg == "--chain-order" && i + 1 < argc_all)
             chain_order = argv_all[++i];
+        else if (arg == "--forcing" && i + 1 < argc_all)
+            forcing = argv_all[++i];
         else if (arg == "--block" && i + 1 < argc_all)
         {
             block = std::atoi(argv_all[++i]);
@@ -129,6 +133,11 @@ int main(int argc_all, char **argv_all)
         std::cerr << "ddh_solve: --chain-order takes auto, pinned or paired on the single-process path, not " << chain_order << std::endl;
         return 2;
     }
+    if ((forcing != "auto" && forcing != "every" && forcing != "first") || (forcing != "auto" && devices >= 1))
+    {
+        std::cerr << "ddh_solve: --forcing takes auto, every or first on the single-process path, not " << forcing << std::endl;
+        return 2;
+    }
     if (block < 0 || kernel < 0 || (block_given && devices >= 1))
     {
         std::cerr << "ddh_solve: --block and --kernel take non-negative integers on the single-process path" << std::endl;
@@ -196,6 +205,9 @@ int main(int argc_all, char **argv_all)
     if (chain_order != "auto")
         F.internals().set_chain_order(chain_order == "paired" ? 2 : 1);
     const std::string chain_note = chain_order == "auto" ? "" : " chain_order=" + chain_order + " in_effect=" + std::to_string(F.internals().chain_order());
+    if (forcing != "auto")
+        F.internals().set_forcing(forcing == "first" ? 2 : 1);
+    const std::string forcing_note = forcing == "auto" ? "" : " forcing=" + forcing + " in_effect=" + std::to_string(F.internals().forcing());
     const int n_lambda = F.size();
     HostDeviceArray<float> L(n_lambda), Y(n_lambda);
     float *d_L = L.device_write(), *d_Y = Y.device_write();
@@ -233,7 +245,7 @@ int main(int argc_all, char **argv_all)
               << " success=" << out.success << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs
               << " t_gmres=" << t_gmres << " t_postprocess=" << t_post
-              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << arith_note << block_note << chain_note << std::endl;
+              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << arith_note << block_note << chain_note << forcing_note << std::endl;
     if (residuals)
     {
         std::cout << "ddh_solve time_step=" << time_step << " residuals:";

@@ -138,6 +138,12 @@ namespace cuddh
             /// and pinned where set_sweep_form forced it.  chain_order() returns the order in effect, 0 where that form is not.
             void set_chain_order(int order) const;
             int chain_order() const;
+            /// Where the element-lane form's march applies the trace sources: 0 auto, 1 in every WaveHoltz pass, 2 in the first pass only (the
+            /// later passes run a time loop without source terms and add the first pass's result; beside the paired chains only;
+            /// cuddh_hip_ddh_plan_set_forcing; a value the plan cannot take throws).  Auto is 2 where form and order are auto too and auto
+            /// gave the paired chains.  forcing() returns the forcing in effect, 0 where the paired chains are not.
+            void set_forcing(int forcing) const;
+            int forcing() const;
             /// The owner rule of kernels 11, 12 and 13: which copy of a node shared by 2 or 4 elements publishes (false: the first, the default;
             /// true: the last).  A check that the copies are bitwise equal (cuddh_hip_ddh_plan_set_owner_rule); other kernels throw.
             void set_last_copy_publishes(bool last) const;

@@ -40,7 +40,10 @@ namespace
     // meet every term at the same place (element_lane_pair_product): 56 packed instructions per sweep instead of 71, all
     // eight pairs keep dm, 228 per wavefront-step in the action form (244 with x), 164 VGPRs, no scratch; a new rounding,
     // gated against the fp64 oracle and not against the pinned chains' bits (profiles/r22).  The one-grid kernel only: the
-    // TimeGrids instantiations (kernel 13) and a form forced with set_sweep_form keep the pinned chains.
+    // TimeGrids instantiations (kernel 13) and a form forced with set_sweep_form keep the pinned chains.  ONCE (forcing 2,
+    // cuddh_hip_ddh_plan_set_forcing; what auto runs where it chose the form and the order) applies the trace sources in the
+    // first WaveHoltz pass only (wh_march_pairs_once): 206 per wavefront-step in the later passes, both forms, 166 VGPRs, no
+    // scratch, 32 KB of LDS per workgroup between the time loops; another new rounding (profiles/r28).
     // Every form is compiled for three wavefronts per SIMD with no scratch: 168 VGPRs in the action form, 166 / 167 in
     // the form with x (rhs, postprocess: once per solve).  The assembly is 16 DPP instructions per sweep with no mask
     // multiplications in eta and one mask in xi (element_assemble_*_row_asm below): a shared node's sum is formed by one
@@ -243,6 +246,12 @@ namespace
     // eight pairs of the action form keep dm at 164 registers and its three v_pk_add_f32 go; the form with x spills from
     // three pairs on and keeps the two interior ones (profiles/r22/ddh_codegen_compare.txt lists the masks tried)
     constexpr unsigned ELEMENT_LANE_PAIRED_DM_PAIRS(bool forced) { return forced ? 0x60u : 0xffu; }
+
+    // and for wh_march_pairs_once: its first pass as above in the action form and with no pair in the form with x (with the two
+    // interior ones the instantiation with LAST_COPY spills 20 bytes); its time loop without sources, the same in both forms,
+    // has the registers of F and Gf to spare and keeps dm in all eight
+    constexpr unsigned ELEMENT_LANE_ONCE_FIRST_DM_PAIRS(bool forced) { return forced ? 0x00u : 0xffu; }
+    constexpr unsigned ELEMENT_LANE_ONCE_DM_PAIRS = 0xffu;
 
     __device__ inline pair_t pk_fma(pair_t a, pair_t b, pair_t c) { return __builtin_elementwise_fma(a, b, c); }
     __device__ inline pair_t pk_fma(float a, pair_t b, pair_t c) { return __builtin_elementwise_fma(pair_t{a, a}, b, c); }
@@ -482,6 +491,120 @@ namespace
         }
     }
 
+    // wh_march_pairs with the sources in the first WaveHoltz pass only (forcing 2, cuddh_hip_ddh_plan_set_forcing).  A pass is
+    // affine in its start value, X' = Pi X + r with X = (u, v), and r, what the sources F and Gf contribute, is the same in
+    // every pass; the first pass starts from 0 and returns exactly r.  So the first pass runs wh_march_pairs' loop, expression
+    // for expression (with one pass the two are the same instructions on the same values), and parks r; every later pass runs a
+    // loop with no source terms at all (dq = z on the interior pairs, -Hi q + z on the others: no F, Gf, cs or sn, the same loop
+    // for both LEAN forms) and adds r behind it.  Pi is untouched.  2 packed FMAs per non-interior pair and half step go, 24 of
+    // 228 per wavefront-step in the action form and 32 of 244 in the form with x, in all passes but the first; the rounding
+    // is new (r is rounded once and added, not summed step by step into every pass).  The first pass stands before the loop
+    // over the others and not inside it, so that F, Gf and cs / sn are dead from there on; DM2 is DM for the loop without
+    // sources, which has their registers to spare.  r waits in LDS, 16 pairs per lane in slots of the lane's own, [pair][thread]
+    // so that the 64-bit accesses of a wavefront do not conflict: 32 KB for the caller's 256 threads, written behind the first
+    // time loop and read behind the others, never inside one, and by the lane that wrote it, so no barrier.
+    template <int LEAN, unsigned INTERIOR, unsigned DM, unsigned DM2, int N, typename Sweep>
+    __device__ inline void wh_march_pairs_once(const DdhArgs<float> &A, const int nt, const float dt, const float *__restrict__ filt,
+                                               const float *__restrict__ cs, const float *__restrict__ sn, const pair_t (&invm)[N],
+                                               const pair_t (&Hi)[N], const pair_t (&F)[N], const pair_t (&Gf)[N], pair_t (&u)[N], pair_t (&v)[N],
+                                               Sweep sweep)
+    {
+        static_assert(LEAN == 1 || LEAN == 2, "the packed loop has wh_march's LEAN forms only");
+        __shared__ pair_t parked[2 * N][256];
+        pair_t p[N], q[N], hm[N];
+        const float half_dt = 0.5f * dt;
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+        {
+            p[l] = q[l] = u[l] = v[l] = 0;
+            hm[l] = half_dt * invm[l];
+        }
+        // one pass from (u, v), with the sources or without; MASK: the pairs with dm
+        auto pass = [&](auto SOURCES, auto MASK, const pair_t(&dm)[N])
+        {
+            const float k0 = filt[0];
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                p[l] = u[l];
+                q[l] = v[l];
+                u[l] *= k0;
+                v[l] *= k0;
+            }
+            for (int it = 1; it <= nt; ++it)
+            {
+                [[maybe_unused]] float c0, s0, c1, s1;
+                if constexpr (SOURCES.value)
+                {
+                    c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                    c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                }
+                const float kw = filt[it];
+                pair_t z[N], ph[N], qh[N];
+
+                sweep(p, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    pair_t dq = ((INTERIOR >> l) & 1u) != 0 ? z[l] : pk_fma(-Hi[l], q[l], z[l]);
+                    if constexpr (SOURCES.value)
+                        if (((INTERIOR >> l) & 1u) == 0 || LEAN == 2)
+                            dq = pk_fma(s0, Gf[l], pk_fma(c0, F[l], dq));
+                    ph[l] = pk_fma(-half_dt, q[l], p[l]);
+                    qh[l] = pk_fma(hm[l], dq, q[l]);
+                    p[l] = pk_fma(-dt, qh[l], p[l]);
+                }
+                sweep(ph, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    pair_t dq = ((INTERIOR >> l) & 1u) != 0 ? z[l] : pk_fma(-Hi[l], qh[l], z[l]);
+                    if constexpr (SOURCES.value)
+                        if (((INTERIOR >> l) & 1u) == 0 || LEAN == 2)
+                            dq = pk_fma(s1, Gf[l], pk_fma(c1, F[l], dq));
+                    if (((MASK.value >> l) & 1u) != 0)
+                        q[l] = pk_fma(dm[l], dq, q[l]);
+                    else
+                        q[l] = pk_fma(hm[l], 2.0f * dq, q[l]);
+                    u[l] = pk_fma(kw, p[l], u[l]);
+                    v[l] = pk_fma(kw, q[l], v[l]);
+                }
+            }
+        };
+        if (A.wh_iters < 1)
+            return;
+        pair_t(*const r)[256] = reinterpret_cast<pair_t(*)[256]>(&parked[0][threadIdx.x]);
+        {
+            pair_t dm[N];
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+                dm[l] = ((DM >> l) & 1u) != 0 ? dt * invm[l] : pair_t{0.0f, 0.0f};
+            pass(std::true_type{}, std::integral_constant<unsigned, DM>{}, dm);
+        }
+        if (A.wh_iters < 2)
+            return;
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+        {
+            r[l][0] = u[l];
+            r[N + l][0] = v[l];
+        }
+        pair_t dm2[N];
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+            dm2[l] = ((DM2 >> l) & 1u) != 0 ? hm[l] + hm[l] : pair_t{0.0f, 0.0f}; // dt invm exactly: doubling is exact (above)
+        for (int whit = 1; whit < A.wh_iters; ++whit)
+        {
+            pass(std::false_type{}, std::integral_constant<unsigned, DM2>{}, dm2);
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                u[l] += r[l][0];
+                v[l] += r[N + l][0];
+            }
+        }
+    }
+
     // ---------------------------------------------------------------- kernel 12 (NB = 5, 4x4 elements, rectangles): four subdomains per wavefront
     // ddh_element_lane_kernel's lane map with 25 nodes per lane: lane = element ex + 4 ey, one subdomain per 16-lane DPP row,
     // four subdomains per wavefront, register n = k + 5 l = node (k, l).  The sweep is the one documented there,
@@ -507,11 +630,13 @@ namespace
     // NB: nodes per element side, 4 (the state in pairs, wh_march_pairs) or 5 (a register per node, wh_march).
     // FORCED, HOLD: as in ddh_mfma_kernel.  LAST_COPY: the owner rule turned round.
     // PAIRED: the paired chains in the sweep (element_lane_pair_product), NB = 4 and the one-grid kernel only
+    // ONCE: the sources in the first WaveHoltz pass only (wh_march_pairs_once; forcing 2), with PAIRED only.  The only
+    //     instantiations that take LDS (32 KB a workgroup, three workgroups per CU: 96 KB of 160)
     // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
     // Sep: [Bx | By | Dg | W | 1 / W], NB NB floats each (build_element_lane_tables).
     // A stays the FIRST parameter: reread_args reads it at offset 0 of the kernel-argument segment.
     // Wavefronts per SIMD: three at NB = 4; at NB = 5 two, and one in the form with x.
-    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, typename... Grids>
+    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, bool ONCE, typename... Grids>
     __global__ void __launch_bounds__(256, NB == 4 ? 3 : (FORCED ? 1 : 2))
         ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep, const float *__restrict__ filt, const float *__restrict__ cs,
                                 const float *__restrict__ sn, Grids... grids)
@@ -524,6 +649,7 @@ namespace
         static_assert(sizeof...(Grids) <= 1 && scheme_of<Grids...> == 0, "one grid, or TimeGrids; no RK4 form");
         static_assert(!(PAIRED && NB != 4), "the paired chains are those of the packed form");
         static_assert(!(PAIRED && sizeof...(Grids) > 0), "the paired chains are built for the one-grid kernel only");
+        static_assert(!(ONCE && !PAIRED), "the march with the sources in the first pass only is built beside the paired chains only");
         const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
         if (s_first >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
@@ -659,7 +785,10 @@ namespace
                 }
             }
         };
-        if constexpr (NB == 4)
+        if constexpr (NB == 4 && ONCE)
+            wh_march_pairs_once<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, ELEMENT_LANE_ONCE_FIRST_DM_PAIRS(FORCED), ELEMENT_LANE_ONCE_DM_PAIRS>(
+                Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
+        else if constexpr (NB == 4)
             wh_march_pairs<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, PAIRED ? ELEMENT_LANE_PAIRED_DM_PAIRS(FORCED) : ELEMENT_LANE_DM_PAIRS(FORCED)>(
                 Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
         else

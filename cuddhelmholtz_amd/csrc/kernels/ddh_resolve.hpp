@@ -40,7 +40,8 @@ namespace cuddh_k
         DDH_SET_NONE = 0, // plan creation, time grids, the integrator
         DDH_SET_SWEEP_FORM = 1,
         DDH_SET_CHAIN_ORDER = 2,
-        DDH_SET_OWNER_RULE = 3
+        DDH_SET_OWNER_RULE = 3,
+        DDH_SET_FORCING = 4 // not ddh_resolve's to judge: ddh_forcing_accepted
     };
 
     struct DdhResolved
@@ -62,4 +63,16 @@ namespace cuddh_k
     // kernel with the form the options need (3 to 2 and 6, 7, 11, 12 to 1 for RK4; 6, 7, 12 to 1 for time grids), so taking an
     // option back leaves the plan where it was moved.  Returns 0 and fills `out`, or 1 (hipErrorInvalidValue): refused.
     int ddh_resolve(const DdhShape &shape, int request, unsigned facts, int current, const DdhOptions &options, int setting, DdhResolved &out);
+
+    // Where the element-lane march of kernel 5 applies the trace sources (cuddh_hip_ddh_plan_set_forcing): 1 in every WaveHoltz
+    // pass, 2 in the first pass only (the later ones add what the first returned; a new rounding), 0: the plan
+    // does not run the paired chains, the only ones the second schedule is built for.  `resolved`: what ddh_resolve gave for the
+    // plan; the other three as stored (0 auto).  Like the paired chains, auto takes the new rounding only where everything
+    // is auto: a forced form or order keeps its bits.
+    int ddh_forcing(const DdhResolved &resolved, int sweep_form, int chain_order, int forcing);
+
+    // May a plan store this forcing?  0 to 2, and 2 exactly where ddh_resolve lets the plan store chain order 2 (the arguments
+    // are ddh_resolve's): accepted and idle on the matrix form of a plan that has the element-lane form, refused elsewhere.
+    // Returns 0, or 1 (hipErrorInvalidValue): refused.
+    int ddh_forcing_accepted(const DdhShape &shape, int request, unsigned facts, int current, const DdhOptions &options, int forcing);
 } // namespace cuddh_k

@@ -1121,6 +1121,27 @@ extern "C"
         });
         return err ? -1 : order;
     }
+    int cuddh_ddh_set_forcing(void *d, int forcing)
+    {
+        return guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            if (h->is64())
+                h->f64->internals().set_forcing(forcing);
+            else
+                h->f32->internals().set_forcing(forcing);
+        });
+    }
+    int cuddh_ddh_forcing(void *d)
+    {
+        int forcing = 0;
+        const int err = guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            forcing = h->is64() ? h->f64->internals().forcing() : h->f32->internals().forcing();
+        });
+        return err ? -1 : forcing;
+    }
     int cuddh_ddh_set_owner_rule(void *d, int last)
     {
         return guarded([&]

@@ -724,6 +724,20 @@ namespace cuddh
         }
 
         template <typename Real>
+        void DDHCore<Real>::set_forcing(int forcing) const
+        {
+            ensure_plan();
+            check_hip(cuddh_hip_ddh_plan_set_forcing(plan, forcing), "DDH forcing");
+        }
+
+        template <typename Real>
+        int DDHCore<Real>::forcing() const
+        {
+            ensure_plan();
+            return cuddh_hip_ddh_plan_forcing(plan);
+        }
+
+        template <typename Real>
         void DDHCore<Real>::set_last_copy_publishes(bool last) const
         {
             ensure_plan();

@@ -185,6 +185,25 @@ namespace cuddh_k
         out.order = out.form < 2 ? 0 : o.chain_order != 0 ? o.chain_order : o.sweep_form == 0 ? 2 : 1;
         return 0;
     }
+
+    int ddh_forcing(const DdhResolved &r, int sweep_form, int chain_order, int forcing)
+    {
+        if (r.order != 2)
+            return 0;
+        if (forcing == 2)
+            return 2;
+        return forcing == 0 && sweep_form == 0 && chain_order == 0 ? 2 : 1;
+    }
+
+    int ddh_forcing_accepted(const DdhShape &s, int request, unsigned facts, int current, const DdhOptions &o, int forcing)
+    {
+        if (forcing < 0 || forcing > 2)
+            return REFUSED;
+        if (forcing != 2)
+            return 0;
+        DdhResolved unused;
+        return ddh_resolve(s, request, facts, current, DdhOptions{o.time_grids, o.rk4, o.sweep_form, 2}, DDH_SET_CHAIN_ORDER, unused);
+    }
 } // namespace cuddh_k
 
 extern "C"
@@ -202,6 +221,25 @@ extern "C"
         out[0] = r.kernel;
         out[1] = r.form;
         out[2] = r.order;
+        return err;
+    }
+
+    int cuddh_ddh_resolve_forcing(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids, int rk4,
+                                  int sweep_form, int chain_order, int forcing, int setting, int *out)
+    {
+        using namespace cuddh_k;
+        if (!out)
+            return 1; // hipErrorInvalidValue
+        const DdhShape s{nb, nel1d, n_domains, is_f64 ? 1 : 0, mx_elems};
+        const DdhOptions o{time_grids, rk4, sweep_form, chain_order};
+        DdhResolved r{0, 0, 0};
+        int err = ddh_resolve(s, request, static_cast<unsigned>(facts), current, o, setting, r);
+        if (!err && (forcing < 0 || forcing > 2 || (setting == DDH_SET_FORCING && ddh_forcing_accepted(s, request, static_cast<unsigned>(facts), current, o, forcing))))
+            err = 1;
+        out[0] = err ? 0 : r.kernel;
+        out[1] = err ? 0 : r.form;
+        out[2] = err ? 0 : r.order;
+        out[3] = err ? 0 : ddh_forcing(r, sweep_form, chain_order, forcing);
         return err;
     }
 }

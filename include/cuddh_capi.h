@@ -210,6 +210,11 @@ int cuddh_ddh_sweep_form(void *ddh);
  * the getter returns the order in effect (1 or 2; 0 where the element-lane form is not in effect; -1 on error) */
 int cuddh_ddh_set_chain_order(void *ddh, int order);
 int cuddh_ddh_chain_order(void *ddh);
+/* where the element-lane form's march applies the trace sources: 0 auto, 1 in every WaveHoltz pass, 2 in the first pass only
+ * (cuddh_hip_ddh_plan_set_forcing); the getter returns the forcing in effect (1 or 2; 0 where the paired chains are not in effect;
+ * -1 on error) */
+int cuddh_ddh_set_forcing(void *ddh, int forcing);
+int cuddh_ddh_forcing(void *ddh);
 /* the owner rule of kernels 11 and 12: last != 0 lets the last copy of every shared node publish instead of the first; same
  * results, a check (cuddh_hip_ddh_plan_set_owner_rule; an error on a plan that is neither kernel 11 nor kernel 12) */
 int cuddh_ddh_set_owner_rule(void *ddh, int last);

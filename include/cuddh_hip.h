@@ -447,6 +447,20 @@ int cuddh_hip_ddh_plan_sweep_form(const cuddh_ddh_plan *plan);
  * 0 where the element-lane form is not in effect. */
 int cuddh_hip_ddh_plan_set_chain_order(cuddh_ddh_plan *plan, int order);
 int cuddh_hip_ddh_plan_chain_order(const cuddh_ddh_plan *plan);
+/* Where the element-lane form's march applies the trace sources, for every launch of the plan.  A WaveHoltz pass is affine in
+ * its start value, X' = Pi X + r, and r, what the sources contribute, is the same in every pass and is exactly what the first
+ * pass (from 0) returns:
+ *   1 = every pass computes c(t) F + s(t) Gf in both half steps, as the other kernels do;
+ *   2 = the first pass only: the later ones run a time loop without source terms and add the first pass's result behind it
+ *       (24 of 228 vector instructions per wavefront-step fewer in four of five passes; r rests in LDS between the time loops).
+ *       The same operator Pi and the same sources, rounded at another place: results differ from 1 in the last bits, and are
+ *       bitwise those of 1 with one WaveHoltz iteration.  Built beside the paired chains (chain order 2) only;
+ *   0 = auto (the default): 2 where the sweep form and the chain order are auto as well and auto gave the paired chains, else 1.
+ * 2 is refused with hipErrorInvalidValue, the plan unchanged, exactly where chain order 2 is refused; where it is accepted and the
+ * chain order in effect is not 2 it waits, as an order waits on the matrix form.  Other values than 0, 1, 2 are invalid.
+ * cuddh_hip_ddh_plan_forcing returns the forcing in effect (1 or 2), 0 where the chain order in effect is not 2. */
+int cuddh_hip_ddh_plan_set_forcing(cuddh_ddh_plan *plan, int forcing);
+int cuddh_hip_ddh_plan_forcing(const cuddh_ddh_plan *plan);
 /* The owner rule of kernels 11, 12 and 13, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
  * smallest element-node index publishes (last == 0, the default) or the one with the largest (last != 0).  The copies are
  * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with
@@ -482,6 +496,10 @@ int cuddh_element_lane_tables(int nb, const float *h_D, const float *h_G, float 
  * the plan or the setter call is refused (out[0..2] are then 0). */
 int cuddh_ddh_resolve(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids, int rk4,
                       int sweep_form, int chain_order, int setting, int *out);
+/* The same with the forcing a plan holds (cuddh_hip_ddh_plan_set_forcing; 0 auto) and setting 4, the forcing: out[0..2] as above
+ * and out[3] the forcing in effect (0 to 2).  Returns 0, or 1 where the plan or the setter call is refused (out[0..3] are then 0). */
+int cuddh_ddh_resolve_forcing(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids,
+                              int rk4, int sweep_form, int chain_order, int forcing, int setting, int *out);
 /* Per-subdomain time grids.  The descriptor holds ONE grid (nt, dt, wh_filter, cs, sn), taken from the mesh alone; the wave
  * speed 1 / a never enters it, and where a < 1 the explicit time stepping runs past its usable range.  Local
  * solves couple through the traces only, so every subdomain may march its WaveHoltz period on a grid of its own: after this

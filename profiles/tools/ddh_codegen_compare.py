@@ -6,7 +6,9 @@ registers, scratch, LDS, the instruction count, whether the mnemonic histogram i
 left unmatched by difflib's longest-matching-blocks alignment, removed + added: 0 = the same instructions in the same order,
 registers aside; a non-zero figure is an upper bound on what moved, not a minimal edit distance), and the same three for
 the blocks that lie inside loops (the time stepping, where these kernels spend their time), and whether the instruction text, operands
-included (block labels renumbered per kernel), is the same line for line.  A kernel that differs is to be
+included (block labels renumbered per kernel), is the same line for line.  A new kernel with more than one innermost loop
+(the element-lane march with the sources in the first pass only has two time loops) gets a line per innermost loop, with what it
+holds and what of ds_*, scratch_* and v_readlane / v_writelane is in it.  A kernel that differs is to be
 timed against the old build; same histogram does not mean same speed for kernels tuned on issue order."""
 import collections
 import difflib
@@ -36,13 +38,18 @@ RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, 
 # the same for names that changed by a rule, per file: (pattern, replacement) pairs applied to OLD's demangled name give NEW's.
 # wave_stages.hpp became a template on the scalar (round 26, fp32 lattice sweeps): Rk2A is now Rk2AT<double>
 _STAGE_RULES = ((r"\b(?:cuddh_k::wave::)?(Begin|Rk2A|Rk2B|Rk4First|Rk4Mid|Rk4Last)\b(?!T)", r"cuddh_k::wave::\1T<double>"),)
-RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES}
+# ddh_element_lane_kernel got ONCE as its sixth template argument, before the grids (false is the march it had)
+_ONCE_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
+RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES, "ddh.hip": _ONCE_RULE}
 # instantiations that are another one plus (or with another) template argument, per file: (pattern, replacement) pairs applied to the
 # demangled name give the base.
 # A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
 DERIVED = {"ddh.hip": ((r", Rk4Scheme ?(?=>)|, TimeGrids<\w+> ?(?=>)", ""),
                        # the paired chains (PAIRED = true, one grid only) against the pinned ones
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true>", r"\1, false>"))}
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true, false>", r"\1, false, false>"),
+                       # the sources in the first pass only (ONCE = true, beside the paired chains only) against every pass
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true), true>", r"\1, false>"))}
+INNER = {}  # (assembly file, kernel) -> its innermost loops
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
@@ -58,17 +65,29 @@ def kernels(src: Path, out: Path, flags_of: str):
         meta = {f: int(re.search(rf"^\s*{re.escape(f)}:\s+(\d+)", entry, re.M).group(1)) for f in FIELDS}
         body = text.split(f"\n{sym}:", 1)[1].split(".Lfunc_end", 1)[0]
         ops, loop_ops, lines, in_loop = [], [], [], False
+        inner, inner_header, in_inner = [], None, False  # the innermost loops, block by block: a list of mnemonics each
         for ln in body.splitlines():
             if ln.startswith((".LBB", "; %bb")):  # the compiler marks every block of a loop in the label's comment
                 in_loop = "Loop" in ln
+                in_inner = inner_header is not None and f"in Loop: Header={inner_header} " in ln
+                if "This Inner Loop Header" in ln:
+                    inner_header, in_inner = ln.split(":")[0].removeprefix(".L"), True
+                    inner.append([])
+                label = ln.split(":")[0].removeprefix(".L")
+            elif ln.lstrip().startswith(";") and "This Inner Loop Header" in ln:  # the comment goes on below the label
+                inner_header, in_inner = label, True
+                inner.append([])
             elif ln.startswith("\t") and ln[1:2] not in ("", ".", ";"):
                 ops.append(ln.split()[0])
                 lines.append(re.sub(r"\.LBB\d+_", ".LBB_", " ".join(ln.split(";")[0].split())))
                 if in_loop:
                     loop_ops.append(ops[-1])
+                if in_inner:
+                    inner[-1].append(ops[-1])
         name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
         name = name.replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0]
         found[name] = (meta, ops, loop_ops, lines)
+        INNER[(str(out), name)] = inner
     return found
 
 
@@ -119,6 +138,15 @@ def main():
             regs = lambda m: " ".join(str(m[f]) for f in FIELDS)  # noqa: E731
             print(f"{name} | NEW after, against {base} | {regs(m0)} -> {regs(m1)} | inside loops {len(l0)} -> {len(l1)}, vector instructions "
                   f"{valu(c0)} -> {valu(c1)}" + ("" if c0 == c1 else ", " + " ".join(f"{k}:{c0[k]}->{c1[k]}" for k in sorted(set(c0) | set(c1)) if c0[k] != c1[k])))
+            loops1, loops0 = INNER[(str(keep / "new.s"), name)], INNER[(str(keep / "new.s"), base)]
+            if len(loops1) > 1:  # every innermost loop by itself, against the base's (first) one
+                b = collections.Counter(loops0[0]) if loops0 else collections.Counter()
+                for i, lp in enumerate(loops1):
+                    c = collections.Counter(lp)
+                    barred = sum(v for k, v in c.items() if k.startswith(("ds_", "scratch_", "v_readlane", "v_writelane")))
+                    print(f"    innermost loop {i + 1} of {len(loops1)}: {len(lp)} instructions, vector {valu(c)} (the base's loop {valu(b)}), "
+                          f"ds_* / scratch_* / v_readlane / v_writelane {barred}, against the base's: "
+                          + (" ".join(f"{k}:{b[k]}->{c[k]}" for k in sorted(set(b) | set(c)) if b[k] != c[k]) or "same histogram"))
             continue
         print(f"{name} | NEW after | {' '.join(str(m1[f]) for f in FIELDS)} | {len(o1)} instructions, {len(l1)} inside loops: "
               + " ".join(f"{k}:{c1[k]}" for k in sorted(c1)))

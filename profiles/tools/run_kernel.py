@@ -1,8 +1,9 @@
 """Runs one hot kernel a few times (for rocprofv3 counter passes).
-usage: run_kernel.py helm|helmn|stiff|mass|ddh NX [REPS] [KERNEL] [NB=4] [REFINE] [FORM] [ORDER]      (helmn: the fused apply on plan-native vectors)
+usage: run_kernel.py helm|helmn|stiff|mass|ddh NX [REPS] [KERNEL] [NB=4] [REFINE] [FORM] [ORDER] [FORCING]      (helmn: the fused apply on plan-native vectors)
 REFINE >= 0: the reference's unstructured fixture refined REFINE times instead of uniform_rect(NX) (NX is then ignored).
 FORM (ddh): kernel 5's sweep form, DDH.set_sweep_form (0 auto, 1 matrix, 2 element-lane).
 ORDER (ddh): the element-lane form's chain order, DDH.set_chain_order (0 auto, 1 pinned, 2 paired), where the library has it.
+FORCING (ddh): where that form's march applies the sources, DDH.set_forcing (0 auto, 1 every WaveHoltz pass, 2 the first only).
 Prints the kernel instantiation the operator launches (cuddh_hip_helmholtz_plan_describe)."""
 import math
 import os
@@ -23,6 +24,7 @@ nb = int(sys.argv[5]) if len(sys.argv) > 5 else 4
 refine = int(sys.argv[6]) if len(sys.argv) > 6 else -1
 form = int(sys.argv[7]) if len(sys.argv) > 7 else 0
 order = int(sys.argv[8]) if len(sys.argv) > 8 else 0
+forcing = int(sys.argv[9]) if len(sys.argv) > 9 else 0
 dev = torch.device("cuda:0")
 cd.use_torch_stream()
 omega = math.pi * nx / 32.0
@@ -56,7 +58,9 @@ else:
     F.set_sweep_form(form)
     if order:
         F.set_chain_order(order)
-    print("kernel:", F.info()["kernel"], "sweep form", F.sweep_form(), "chain order", F.chain_order(), "subdomains", F.info()["n_domains"], "nt", F.info()["nt"])
+    if forcing:
+        F.set_forcing(forcing)
+    print("kernel:", F.info()["kernel"], "sweep form", F.sweep_form(), "chain order", F.chain_order(), "forcing", F.forcing(), "subdomains", F.info()["n_domains"], "nt", F.info()["nt"])
     lam = torch.rand(F.size(), dtype=torch.float32, device=dev)
     out = torch.zeros_like(lam)
     for _ in range(reps):
