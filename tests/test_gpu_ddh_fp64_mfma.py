@@ -59,7 +59,10 @@ def test_auto_still_picks_kernel3_in_fp64(cuda):
 
 def test_kernel8_rejected_on_nonuniform_metric(cuda):
     """rectangles of varying width (x stretched smoothly, same element numbering as uniform_rect): kernel 2 runs, kernel 8 needs one
-    metric tensor for all elements and refuses"""
+    metric tensor for all elements and refuses.  What kernel 2 computes there (g00 and g11 varying from element to element) is
+    compared with the oracle on the same vertices at the fp64 gate."""
+    import torch
+
     import cuddhelmholtz_amd as cd
 
     nx = 8
@@ -71,6 +74,32 @@ def test_kernel8_rejected_on_nonuniform_metric(cuda):
     F = make(nx, 4, "f64", 8, mesh=mesh)
     with pytest.raises(RuntimeError):
         F.info()
+
+    omega = 2 * math.pi * nx / 10
+    d = oracle.Discretization(oracle.Mesh(xy, base.elements()), 4)
+    h_a = d.nodal(oracle.alpha_disk)
+    fh = np.concatenate([oracle.linear_functional(d, oracle.gaussians(omega)), 0.1 * oracle.linear_functional(d, oracle.mass_poly)])
+    O = oracle.DDH(d, nx, nx, omega, h_a, np.float64)
+    per_element = np.round(O.G[0].reshape(16, -1, order="F"), 12)
+    assert np.unique(per_element, axis=1).shape[1] == nx // 2 and not O.G[1].any()  # one metric per element width, all diagonal
+    F = make(nx, 4, "f64", 2, h_a=h_a, omega=omega, mesh=mesh)
+    assert F.info()["kernel"] == 2 and F.info()["nt"] == O.t.nt and F.size() == O.size
+    n = F.size()
+    lam_h = np.random.default_rng(2).standard_normal(n)
+    used = np.unique(O.t.B[O.t.B >= 0])
+    lam_h[np.setdiff1d(np.arange(n), np.concatenate([used, used + O.t.n_lambda]))] = 0.0
+    written = np.unique(O.t.B[:, 1, :][O.t.B[:, 1, :] >= 0])
+    written = np.concatenate([written, written + O.t.n_lambda])
+    f, lam = to_dev(torch, fh, cuda), to_dev(torch, lam_h, cuda)
+    b = torch.zeros(n, dtype=torch.float64, device=cuda)
+    F.rhs(f, b)
+    y = torch.full((n,), 5.0, dtype=torch.float64, device=cuda)
+    F.action(lam, y)
+    u = torch.full((2 * d.ndof,), 9.0, dtype=torch.float64, device=cuda)
+    F.postprocess(lam, f, u)
+    e = (rel(b.cpu().numpy(), O.rhs(fh)), rel(y.cpu().numpy()[written], O.action(lam_h)[written]), rel(u.cpu().numpy(), O.postprocess(lam_h, fh)))
+    print(f"DDH64 kernel 2 on stretched rectangles vs fp64 oracle: rhs {e[0]:.2e} action {e[1]:.2e} postprocess {e[2]:.2e}")
+    assert max(e) <= 1e-10, e
 
 
 # ------------------------------------------------------------------ entry points vs the fp64 oracle

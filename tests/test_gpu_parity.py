@@ -2,7 +2,8 @@
 on the same seeded inputs.  Tolerances (relative l2 unless noted):
   fp64 operator applies          1e-12  (summation order only)
   DDH fp64 mode                  1e-10
-  DDH fp32 mode vs fp64 oracle   2e-4   (reference precision; reported, loosely gated)
+  DDH fp32 mode vs fp64 oracle   2e-4, and rhs / action / postprocess within 4 x the fp32 oracle's own distance to the fp64 oracle
+                                 (the floor rule of tests/ddh_metric_cases.py), in relative l2 and in max norm
 """
 import functools
 import math
@@ -10,6 +11,7 @@ import math
 import numpy as np
 import pytest
 
+import ddh_metric_cases as mc
 import oracle
 from conftest import load_unstructured_square
 
@@ -814,6 +816,30 @@ def test_ddh_fp32_reference_precision(cuda, nx, nb, kernel):
     F.postprocess(b, f, u)
     u64 = O64.postprocess(b64, fh)
     assert rel(u.cpu().numpy(), u64) < 2e-4
+    # the floor rule (tests/ddh_metric_cases.py): rhs, the action GMRES iterates on and postprocess, each within 4 x the fp32
+    # oracle's own distance to the fp64 oracle on the same inputs, in relative l2 and in max norm
+    Bt = O64.t.B
+    used = np.unique(Bt[Bt >= 0])
+    lam_h = np.random.default_rng(7).standard_normal(n)
+    lam_h[np.setdiff1d(np.arange(n), np.concatenate([used, used + O64.t.n_lambda]))] = 0.0
+    written = np.unique(Bt[:, 1, :][Bt[:, 1, :] >= 0])
+    written = np.concatenate([written, written + O64.t.n_lambda])
+    lam = to_dev(torch, lam_h.astype(np.float32), cuda)
+    y = torch.full((n,), 5.0, dtype=torch.float32, device=cuda)
+    F.action(lam, y)
+    ul = torch.full((2 * d.ndof,), 9.0, dtype=torch.float64, device=cuda)
+    F.postprocess(lam, f, ul)
+    got = (b.cpu().numpy(), y.cpu().numpy()[written], ul.cpu().numpy())
+    ref64 = (b64, O64.action(lam_h)[written], O64.postprocess(lam_h, fh))
+    ref32 = (O32.rhs(fh), O32.action(lam_h)[written], O32.postprocess(lam_h, fh))
+    missed = []
+    for nm, g, r32, r64 in zip(mc.NAMES, got, ref32, ref64):
+        e, fl = (mc.rel(g, r64), mc.rel_max(g, r64)), (mc.rel(r32, r64), mc.rel_max(r32, r64))
+        print(f"DDH fp32 kernel {kernel} {nx}x{nx} n_basis {nb} {nm}: vs fp64 oracle l2 {e[0]:.3e}, floor {fl[0]:.3e}, ratio {e[0] / fl[0]:.2f}; "
+              f"max {e[1]:.3e}, floor {fl[1]:.3e}, ratio {e[1] / fl[1]:.2f} (gate {mc.FLOOR_FACTOR:.0f})")
+        if not (e[0] <= mc.FLOOR_FACTOR * fl[0] and e[1] <= mc.FLOOR_FACTOR * fl[1]):
+            missed.append((nm, e, fl))
+    assert not missed, missed
     # determinism: bitwise identical traces on repetition (the reference's LDS atomics are not)
     b2 = torch.zeros_like(b)
     F.rhs(f, b2)
