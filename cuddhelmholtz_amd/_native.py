@@ -249,6 +249,14 @@ _sig("cuddh_hip_wave_pair32_rk4_12", ci, _wl, *([cd] * 5), *([vp] * 11))
 _sig("cuddh_hip_wave_pair32_rk4_34", ci, _wl, *([cd] * 7), *([vp] * 14))
 _sig("cuddh_hip_wave_pair32_tile_x", ci)
 _sig("cuddh_hip_wave_pair32_tile_y", ci)
+# (lattice sweeps with missing cells: the lattice entry points' arguments with the cell flags after the description)
+for _family in ("cuddh_hip_wave_cells_%s_f64", "cuddh_hip_wave_cells32_%s"):
+    _sig(_family % "rk2_a", ci, _wl, vp, cd, cd, cd, *([vp] * 9))
+    _sig(_family % "rk2_b", ci, _wl, vp, cd, cd, cd, cd, *([vp] * 11))
+    _sig(_family % "rk4_1", ci, _wl, vp, cd, cd, cd, *([vp] * 11))
+    _sig(_family % "rk4_2", ci, _wl, vp, cd, cd, cd, *([vp] * 12))
+    _sig(_family % "rk4_3", ci, _wl, vp, cd, cd, cd, *([vp] * 12))
+    _sig(_family % "rk4_4", ci, _wl, vp, cd, cd, cd, cd, *([vp] * 13))
 
 # ---- handle layer (cuddh_capi.h)
 _sig("cuddh_last_error", cp)
@@ -261,6 +269,7 @@ _sig("cuddh_basis_eval", ci, vp, ci, vp, vp)
 _sig("cuddh_basis_deriv", ci, vp, ci, vp, vp)
 _sig("cuddh_mesh_uniform_rect", vp, ci, cd, cd, ci, cd, cd)
 _sig("cuddh_mesh_from_vertices", vp, ci, vp, ci, vp)
+_sig("cuddh_mesh_grid_cells", vp, ci, cd, cd, ci, cd, cd, vp)
 _sig("cuddh_mesh_load", vp, cp)
 _sig("cuddh_mesh_refined", vp, vp, ci)
 _sig("cuddh_mesh_partition", ci, vp, ci, vp)
@@ -388,6 +397,7 @@ _sig("cuddh_waveholtz_precision", ci, vp)
 _sig("cuddh_waveholtz_create_launch", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci)
 _sig("cuddh_waveholtz_launch", ci, vp)
 _sig("cuddh_wave_lattice_map", ci, vp, vp, vp, vp)
+_sig("cuddh_wave_lattice_map_cells", ci, vp, vp, vp, vp, vp)
 _sig("cuddh_wave_lattice_tables", ci, vp, vp, vp)
 
 

@@ -114,6 +114,20 @@ class Mesh2D:
         return Mesh2D(N.handle(lib.cuddh_mesh_from_vertices(xy.size // 2, _h(xy), elems.size // 4, _h(elems)), "Mesh2D.from_vertices"))
 
     @staticmethod
+    def grid_cells(nx, ax, bx, ny, ay, by, present) -> "Mesh2D":
+        """A grid mesh with missing cells: the cells of uniform_rect(nx, ax, bx, ny, ay, by) where present[j, i] is true
+        (present: (ny, nx) bool, at least one true), in ascending cell index i + nx j with uniform_rect's corner order and
+        vertex coordinates, the unused vertices dropped; built through from_vertices.  WaveHoltz(sweep="lattice") takes such a
+        mesh (an obstacle, an L-shape, a staircase): csrc/kernels/wave_cells.hip, DESIGN 4.5.4."""
+        present = np.asarray(present)
+        if present.shape != (int(ny), int(nx)):
+            raise ValueError(f"Mesh2D.grid_cells: present must have shape (ny, nx) = ({ny}, {nx}), not {present.shape}")
+        flags = np.ascontiguousarray(present != 0, dtype=np.uint8)
+        if not flags.any():
+            raise ValueError("Mesh2D.grid_cells: at least one cell must be present")
+        return Mesh2D(N.handle(lib.cuddh_mesh_grid_cells(int(nx), ax, bx, int(ny), ay, by, _h(flags)), "Mesh2D.grid_cells"))
+
+    @staticmethod
     def load(directory) -> "Mesh2D":
         """the reference's text format: info.txt, coordinates.txt, elements.txt (tests/load_unstructured_square.cpp:11-55)"""
         return Mesh2D(N.handle(lib.cuddh_mesh_load(str(directory).encode()), "Mesh2D.load"))
@@ -720,6 +734,10 @@ class WaveHoltz(_Operator):
     sweep "operator" (the default: a stiffness apply and a stage kernel per sweep) or "lattice": one launch per sweep does the
     stiffness stencil and the stage on lattice-ordered vectors (csrc/kernels/wave_lattice.hip).  "lattice" needs stiffness
     "lobatto" and a uniform rectangle mesh, which is detected; every method takes and returns vectors in the space's order.
+    A grid mesh with missing cells (Mesh2D.grid_cells: an obstacle, an L-shape, a staircase) is detected too, where the mesh is
+    no full rectangle, and runs the same march on csrc/kernels/wave_cells.hip / wave_cells_f32.hip (info()["stiffness_kernel"]
+    "wave_cells nb<n>"); faces=None makes the walls of a hole absorbing, faces= the outer edges only makes them sound-hard.
+    launch "pair" is refused on such a mesh (ValueError, "launch").
     precision "f64" (the default) or "f32" (sweep "lattice" only): the lattice vectors are stored and the sweeps computed in fp32
     (csrc/kernels/wave_lattice_f32.hip), half the march's memory and bytes per sweep.  z, f, b and the solution stay float64; y =
     x - S x is formed in float64.  It is meant for tolerances around 1e-4: the fp32 operator's own defect is about 1e-6 relative,

@@ -7,9 +7,12 @@
 //   --stiffness lobatto and refuses --stiffness gauss), --precision f64|f32 (f32: the lattice sweeps in fp32, for tolerances around
 //   1e-4; it goes with --sweep lattice only), --launch sweep|pair (pair: two lattice sweeps per launch, the same march bit for bit;
 //   it goes with --sweep lattice only), --coefficient one|disk (a == 1, the default, or the examples' disk of a = 0.2, projected as in
-//   ddh_solve), --residuals (one more line: GMRES's residual history).
+//   ddh_solve), --void i0 j0 i1 j1 (any number of times: the cells i0 <= i < i1, j0 <= j < j1 of the nx x nx grid are left out, a
+//   sound-hard or absorbing obstacle; --sweep lattice then runs the sweeps with missing cells and refuses --launch pair; every
+//   boundary edge, the obstacle's walls included, is absorbing), --residuals (one more line: GMRES's residual history).
 // The load is the examples' pair of Gaussians in the real part and 0.1 (3 x^2 - 2 x y + y + 1) in the imaginary part.
 // Writes <out_dir>/xy.0000 and <out_dir>/waveholtz.0000 (raw fp64; "-": nothing) and prints one summary line.
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <string>
@@ -26,6 +29,7 @@ int main(int argc_all, char **argv_all)
     std::string integrator = "rk2", time_ratio = "1", stiffness = "", coefficient = "one", sweep = "operator", precision = "f64", launch = "sweep";
     int coarsen = 0; // 0: not given
     bool residuals = false;
+    std::vector<int> voids; // four per --void
     std::vector<char *> args;
     for (int i = 0; i < argc_all; ++i)
     {
@@ -46,6 +50,16 @@ int main(int argc_all, char **argv_all)
             launch = argv_all[++i];
         else if (arg == "--coefficient" && i + 1 < argc_all)
             coefficient = argv_all[++i];
+        else if (arg == "--void" && i + 4 < argc_all)
+        {
+            for (int k = 0; k < 4; ++k)
+                voids.push_back(std::atoi(argv_all[++i]));
+        }
+        else if (arg == "--void")
+        {
+            std::cerr << "waveholtz_solve: --void takes four cell indices: i0 j0 i1 j1" << std::endl;
+            return 2;
+        }
         else if (arg == "--residuals")
             residuals = true;
         else
@@ -106,6 +120,11 @@ int main(int argc_all, char **argv_all)
         std::cerr << "waveholtz_solve: --launch pair is two lattice sweeps per launch: it goes with --sweep lattice only" << std::endl;
         return 2;
     }
+    if (!voids.empty() && launch == "pair")
+    {
+        std::cerr << "waveholtz_solve: --launch pair has no form for a grid with missing cells yet: it does not go with --void" << std::endl;
+        return 2;
+    }
     if (coefficient != "one" && coefficient != "disk")
     {
         std::cerr << "waveholtz_solve: --coefficient takes one or disk, not " << coefficient << std::endl;
@@ -121,7 +140,21 @@ int main(int argc_all, char **argv_all)
     const double tol = argc > 6 ? std::atof(argv[6]) : 1e-4;
     const std::string out_dir = argc > 7 ? argv[7] : "-";
 
-    Mesh2D mesh = Mesh2D::uniform_rect(nx, -1.0, 1.0, nx, -1.0, 1.0);
+    std::vector<unsigned char> present(static_cast<std::size_t>(std::max(nx, 1)) * std::max(nx, 1), 1);
+    for (std::size_t k = 0; k + 3 < voids.size(); k += 4)
+    {
+        const int i0 = voids[k], j0 = voids[k + 1], i1 = voids[k + 2], j1 = voids[k + 3];
+        if (i0 < 0 || j0 < 0 || i1 > nx || j1 > nx || i0 >= i1 || j0 >= j1)
+        {
+            std::cerr << "waveholtz_solve: --void " << i0 << " " << j0 << " " << i1 << " " << j1 << " is no box of cells of the " << nx << " x " << nx
+                      << " grid" << std::endl;
+            return 2;
+        }
+        for (int j = j0; j < j1; ++j)
+            for (int i = i0; i < i1; ++i)
+                present[i + static_cast<std::size_t>(nx) * j] = 0;
+    }
+    Mesh2D mesh = voids.empty() ? Mesh2D::uniform_rect(nx, -1.0, 1.0, nx, -1.0, 1.0) : grid_cells(nx, -1.0, 1.0, nx, -1.0, 1.0, present.data());
     Basis basis(nb);
     H1Space fem(mesh, basis);
     const int ndof = fem.size(), N = 2 * ndof;
@@ -184,6 +217,7 @@ int main(int argc_all, char **argv_all)
     const double ms_per_period = out.num_matvec > 0 ? 1e3 * t_gmres / out.num_matvec : 0.0;
     std::cout << "waveholtz_solve nx=" << nx << " nb=" << nb << " omega/pi=" << omega / M_PI << " ndof=" << ndof << " integrator=" << integrator
               << " coarsen=" << coarsen << " ratio=" << W.time_ratio() << " stiffness=" << stiffness << " sweep=" << sweep << " precision=" << precision << " launch=" << launch << " coefficient=" << coefficient
+              << (voids.empty() ? "" : " cells=" + std::to_string(mesh.n_elem()))
               << " nt=" << W.num_steps() << " sweeps_per_period=" << W.sweeps_per_period() << " success=" << out.success
               << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec << " rel_res=" << out.res_norm.back() / out.res_norm.front()
               << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs << " t_gmres=" << t_gmres << " ms_per_period=" << ms_per_period

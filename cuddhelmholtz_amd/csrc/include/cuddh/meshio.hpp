@@ -4,6 +4,7 @@
 //   load_mesh         the reference's text format: <dir>/info.txt "n_pts n_elem", coordinates.txt "x y" per vertex,
 //                     elements.txt four 0-based counter-clockwise vertex ids per quadrilateral
 //   refine_quads      uniform refinement: every quadrilateral -> 4 through its edge midpoints and centroid
+//   grid_cells        a uniform rectangle grid with some cells left out (the WaveHoltz lattice form takes it)
 //   partition_elements  n_parts compact, equally sized element sets (labels for EnsembleSpace): elements sorted along the
 //                     Morton curve of their centroids, cut into n_parts consecutive runs whose sizes differ by at most one
 #ifndef CUDDH_AMD_MESHIO_HPP
@@ -28,6 +29,12 @@ namespace cuddh
     /// reads <dir>/info.txt, coordinates.txt, elements.txt; cuddh_error (throws) when a file cannot be opened or is short
     QuadMeshData read_mesh_files(const std::string &dir);
     Mesh2D load_mesh(const std::string &dir);
+
+    /// A grid mesh with missing cells: the cells of Mesh2D::uniform_rect(nx, ax, bx, ny, ay, by) whose present[i + nx j] is
+    /// nonzero, in ascending cell index with uniform_rect's corner order and vertex coordinates, the vertices no cell uses dropped
+    /// (the others keep their order).  At least one cell must be present.
+    QuadMeshData grid_cells_data(int nx, double ax, double bx, int ny, double ay, double by, const unsigned char *present);
+    Mesh2D grid_cells(int nx, double ax, double bx, int ny, double ay, double by, const unsigned char *present);
 
     /// vertex and element arrays of an existing mesh
     QuadMeshData mesh_data(const Mesh2D &mesh);

@@ -20,7 +20,8 @@ namespace cuddh
         int Lx = 0, Ly = 0;
         int stride = 0;           // doubles per lattice row: Lx rounded up to even (rows start on 16-byte boundaries)
         double hx = 0.0, hy = 0.0;
-        std::vector<int> node_of; // dof -> I + Lx J, a bijection onto [0, Lx Ly)
+        std::vector<int> node_of; // dof -> I + Lx J, a bijection onto [0, Lx Ly) (with missing cells: an injection)
+        std::vector<unsigned char> cell; // empty: every cell exists; else nx ny flags, 1 where cell i + nx j exists
 
         int slots() const { return stride * Ly; }
         /// dof -> slot I + stride J of the padded vectors
@@ -36,6 +37,19 @@ namespace cuddh
 
     /// the same for a space (its coordinates are evaluated if they have not been)
     WaveLatticeMap build_wave_lattice_map(const H1Space &fem);
+
+    /// A grid mesh with missing cells: the elements are a subset of the cells of a uniform nx x ny grid, listed in
+    /// ascending cell index i + nx j with uniform_rect's corner order.  hx, hy come from element 0, the origin and nx, ny from the
+    /// bounding box of all corners, an element's cell from its first corner.  Verified: every corner is where its cell has it (the
+    /// tolerance of the full detection), cell indices strictly increase, shared nodes agree, node_of is injective, Lx Ly and
+    /// stride Ly fit in an int.  `cell` is filled (all ones on a full grid); lattice nodes with no cell around them belong to no
+    /// dof.  Anything else is refused through cuddh_error with a message that starts "WaveHoltz error: sweep:".
+    WaveLatticeMap build_wave_cells_map(int ndof, int n_elem, int n_basis, const int *I, const double *corners, const double *xy, const double *x);
+    WaveLatticeMap build_wave_cells_map(const H1Space &fem);
+
+    /// What WaveHoltz's lattice form uses: the full detection, and only where that refuses the one with missing cells (whose
+    /// refusal is then reported).  `cell` is empty exactly when the full detection accepted.
+    WaveLatticeMap build_wave_lattice_or_cells_map(const H1Space &fem);
 
     /// the 1-D tables of the Kronecker form on the reference element [-1, 1]: A = D^T diag(w) D (row-major, n_basis x n_basis), D the
     /// collocation derivative matrix, and the Gauss-Lobatto weights w

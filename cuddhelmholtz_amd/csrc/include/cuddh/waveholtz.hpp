@@ -9,6 +9,11 @@
 // sweep = lattice (opt-in; collocated stiffness on a uniform rectangle mesh only): the state lives in lattice order and ONE launch
 // per sweep does the stiffness stencil and the stage (csrc/kernels/wave_lattice.hip); no StiffnessMatrix is built.  z, f and
 // every public vector keep the space's dof order: a period permutes them in and out.
+// A grid mesh with missing cells (meshio.hpp's grid_cells: the cells of a uniform rectangle grid in ascending order, some left
+// out) is taken too: where the full-rectangle detection refuses, build_wave_cells_map (wave_lattice.hpp) is tried, and the same
+// march runs on csrc/kernels/wave_cells.hip / wave_cells_f32.hip, whose stencil adds up the cells that exist around a node
+// (DESIGN 4.5.4).  Lattice nodes with no cell around them are slots without a dof, like padding.  h_faces chooses the walls:
+// every boundary edge absorbing (the default) or, with the outer edges only, sound-hard holes.  per_pair is refused there.
 // precision = f32 (opt-in; the lattice form only): the march's thirteen lattice vectors are stored and the sweeps computed in
 // fp32 (csrc/kernels/wave_lattice_f32.hip), half the march's memory and bytes; z, f, b, the solution and y = x - S x stay fp64,
 // rounded once on the way into a period and converted once on the way out.  For tolerances around 1e-4: the fp32 operator's own

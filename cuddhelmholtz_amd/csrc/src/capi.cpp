@@ -243,6 +243,10 @@ extern "C"
     {
         return guarded_new<Mesh2D>([&] { return new Mesh2D(Mesh2D::uniform_rect(nx, ax, bx, ny, ay, by)); });
     }
+    void *cuddh_mesh_grid_cells(int nx, double ax, double bx, int ny, double ay, double by, const unsigned char *h_present)
+    {
+        return guarded_new<Mesh2D>([&] { return new Mesh2D(grid_cells(nx, ax, bx, ny, ay, by, h_present)); });
+    }
     void *cuddh_mesh_from_vertices(int n_pts, const double *h_xy, int n_elem, const int *h_elems)
     {
         return guarded_new<Mesh2D>([&] { return new Mesh2D(Mesh2D::from_vertices(n_pts, h_xy, n_elem, h_elems)); });
@@ -658,6 +662,25 @@ extern "C"
             }
             if (h_node_of)
                 std::copy(map.node_of.begin(), map.node_of.end(), h_node_of);
+        });
+    }
+    int cuddh_wave_lattice_map_cells(void *fem, int *h_dims, double *h_h, int *h_node_of, unsigned char *h_cell)
+    {
+        return guarded([&]
+        {
+            const WaveLatticeMap map = build_wave_cells_map(*static_cast<H1Space *>(fem));
+            const int dims[5] = {map.nx, map.ny, map.Lx, map.Ly, map.stride};
+            if (h_dims)
+                std::copy(dims, dims + 5, h_dims);
+            if (h_h)
+            {
+                h_h[0] = map.hx;
+                h_h[1] = map.hy;
+            }
+            if (h_node_of)
+                std::copy(map.node_of.begin(), map.node_of.end(), h_node_of);
+            if (h_cell)
+                std::copy(map.cell.begin(), map.cell.end(), h_cell);
         });
     }
     int cuddh_wave_lattice_tables(void *basis, double *h_A, double *h_w)

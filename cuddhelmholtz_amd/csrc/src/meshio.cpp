@@ -59,6 +59,44 @@ namespace cuddh
         return Mesh2D::from_vertices(m.n_pts(), m.xy.data(), m.n_elem(), m.elems.data());
     }
 
+    QuadMeshData grid_cells_data(int nx, double ax, double bx, int ny, double ay, double by, const unsigned char *present)
+    {
+        if (nx < 1 || ny < 1 || !present)
+            cuddh_error("grid_cells error: nx and ny must be positive and the mask given.");
+        const int npx = nx + 1;
+        const double dx = (bx - ax) / nx, dy = (by - ay) / ny; // (uniform_rect's vertex formula)
+        std::vector<int> id(static_cast<std::size_t>(npx) * (ny + 1), -1);
+        for (int j = 0; j < ny; ++j)
+            for (int i = 0; i < nx; ++i)
+                if (present[i + static_cast<std::size_t>(nx) * j])
+                    for (const int v : {i + npx * j, i + 1 + npx * j, i + 1 + npx * (j + 1), i + npx * (j + 1)})
+                        id[v] = 0;
+        QuadMeshData m;
+        int n_pts = 0;
+        for (int j = 0; j <= ny; ++j)
+            for (int i = 0; i < npx; ++i)
+                if (id[i + static_cast<std::size_t>(npx) * j] == 0)
+                {
+                    id[i + static_cast<std::size_t>(npx) * j] = n_pts++;
+                    m.xy.push_back(ax + dx * i);
+                    m.xy.push_back(ay + dy * j);
+                }
+        if (n_pts == 0)
+            cuddh_error("grid_cells error: no cell is present.");
+        for (int j = 0; j < ny; ++j)
+            for (int i = 0; i < nx; ++i)
+                if (present[i + static_cast<std::size_t>(nx) * j])
+                    for (const int v : {i + npx * j, i + 1 + npx * j, i + 1 + npx * (j + 1), i + npx * (j + 1)})
+                        m.elems.push_back(id[v]);
+        return m;
+    }
+
+    Mesh2D grid_cells(int nx, double ax, double bx, int ny, double ay, double by, const unsigned char *present)
+    {
+        const QuadMeshData m = grid_cells_data(nx, ax, bx, ny, ay, by, present);
+        return Mesh2D::from_vertices(m.n_pts(), m.xy.data(), m.n_elem(), m.elems.data());
+    }
+
     QuadMeshData mesh_data(const Mesh2D &mesh)
     {
         QuadMeshData m;

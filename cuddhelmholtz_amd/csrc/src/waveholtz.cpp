@@ -2,7 +2,9 @@
 // csrc/kernels/waveholtz.hip (cuddh_hip_wave_stage_*), one launch of each per sweep; or, in the lattice form, as the kernels of
 // csrc/kernels/wave_lattice.hip (cuddh_hip_wave_lattice_*), one launch per sweep on lattice-ordered vectors; with precision = f32
 // the same call sequence on the fp32 family of csrc/kernels/wave_lattice_f32.hip (cuddh_hip_wave32_*); with launch = per_pair two
-// sweeps per launch (csrc/kernels/wave_pair.hip and wave_pair_f32.hip: cuddh_hip_wave_pair_*, cuddh_hip_wave_pair32_*).
+// sweeps per launch (csrc/kernels/wave_pair.hip and wave_pair_f32.hip: cuddh_hip_wave_pair_*, cuddh_hip_wave_pair32_*); on a grid
+// mesh with missing cells the per-sweep sequence on csrc/kernels/wave_cells.hip and wave_cells_f32.hip (cuddh_hip_wave_cells_*,
+// cuddh_hip_wave_cells32_*).
 #include "cuddh/waveholtz.hpp"
 
 #include <algorithm>
@@ -78,6 +80,12 @@ namespace cuddh
             static constexpr auto pair_rk2 = cuddh_hip_wave_pair_rk2_f64;
             static constexpr auto pair_rk4_12 = cuddh_hip_wave_pair_rk4_12_f64;
             static constexpr auto pair_rk4_34 = cuddh_hip_wave_pair_rk4_34_f64;
+            static constexpr auto cells_rk2_a = cuddh_hip_wave_cells_rk2_a_f64;
+            static constexpr auto cells_rk2_b = cuddh_hip_wave_cells_rk2_b_f64;
+            static constexpr auto cells_rk4_1 = cuddh_hip_wave_cells_rk4_1_f64;
+            static constexpr auto cells_rk4_2 = cuddh_hip_wave_cells_rk4_2_f64;
+            static constexpr auto cells_rk4_3 = cuddh_hip_wave_cells_rk4_3_f64;
+            static constexpr auto cells_rk4_4 = cuddh_hip_wave_cells_rk4_4_f64;
         };
         template <>
         struct LatticeKernels<float>
@@ -94,6 +102,12 @@ namespace cuddh
             static constexpr auto pair_rk2 = cuddh_hip_wave_pair32_rk2;
             static constexpr auto pair_rk4_12 = cuddh_hip_wave_pair32_rk4_12;
             static constexpr auto pair_rk4_34 = cuddh_hip_wave_pair32_rk4_34;
+            static constexpr auto cells_rk2_a = cuddh_hip_wave_cells32_rk2_a;
+            static constexpr auto cells_rk2_b = cuddh_hip_wave_cells32_rk2_b;
+            static constexpr auto cells_rk4_1 = cuddh_hip_wave_cells32_rk4_1;
+            static constexpr auto cells_rk4_2 = cuddh_hip_wave_cells32_rk4_2;
+            static constexpr auto cells_rk4_3 = cuddh_hip_wave_cells32_rk4_3;
+            static constexpr auto cells_rk4_4 = cuddh_hip_wave_cells32_rk4_4;
         };
 
         /// the lattice vectors of one period (DEVICE); F, G null without a load; PS2, AQ, AP used by rk4 only
@@ -114,6 +128,7 @@ namespace cuddh
             const double *filt, *cs, *sn; // HOST
             const int *dof_of_slot, *slot_of_dof;
             void *stream;
+            const unsigned char *cell = nullptr; // DEVICE flags of a grid with missing cells (wave_cells.hip), null on a full grid
         };
 
         template <typename R>
@@ -167,6 +182,26 @@ namespace cuddh
                     std::swap(P, P2);
                 }
             }
+            else if (g.cell && !g.rk4)
+            {
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    detail::check_hip(Kn::cells_rk2_a(D, g.cell, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
+                    detail::check_hip(Kn::cells_rk2_b(D, g.cell, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+                }
+            }
+            else if (g.cell)
+            {
+                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2;
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    const int k = 2 * it - 2;
+                    detail::check_hip(Kn::cells_rk4_1(D, g.cell, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::cells_rk4_2(D, g.cell, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::cells_rk4_3(D, g.cell, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::cells_rk4_4(D, g.cell, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+                }
+            }
             else if (!g.rk4)
             {
                 for (int it = 1; it <= g.nt; ++it)
@@ -196,7 +231,8 @@ namespace cuddh
     {
         cuddh_wave_lattice desc = {};
         int slots = 0;                              // elements per lattice vector: stride * Ly
-        host_device_ivec dof_of_slot, slot_of_dof;  // slots (-1: padding) and ndof
+        host_device_ivec dof_of_slot, slot_of_dof;  // slots (-1: padding or a node with no cell around it) and ndof
+        HostDeviceArray<unsigned char> cell;        // a grid with missing cells (wave_cells.hip): nx ny flags; empty on a full grid
         mutable host_device_dvec ps2;               // rk4_2 and rk4_3 read the stencil of one ps and write the other
         // precision = f32: the thirteen lattice vectors as floats (the class's double ones then stay empty)
         bool f32 = false;
@@ -232,7 +268,11 @@ namespace cuddh
         {
             if (fem.basis().size() > 8)
                 cuddh_error("WaveHoltz error: sweep: the lattice kernels take n_basis up to 8.");
-            const WaveLatticeMap map = build_wave_lattice_map(fem);
+            // a full grid runs wave_lattice.hip; only where that detection refuses is a grid with missing cells looked for
+            const WaveLatticeMap map = build_wave_lattice_or_cells_map(fem);
+            if (!map.cell.empty() && o.launch == WaveHoltzOptions::per_pair)
+                cuddh_error("WaveHoltz error: launch: per_pair needs a full uniform rectangle mesh; the paired kernels have no form for a grid "
+                            "with missing cells yet.");
             // rows of the fp32 form hold a multiple of four floats (16 bytes), those of the fp64 form the map's even stride
             const bool f32 = o.precision == WaveHoltzOptions::f32;
             const int stride = f32 ? (map.Lx + 3) / 4 * 4 : map.stride;
@@ -248,6 +288,11 @@ namespace cuddh
             lat->desc.cx = map.hy / map.hx;
             lat->desc.cy = map.hx / map.hy;
             wave_lattice_tables(fem.basis(), lat->desc.A, lat->desc.w);
+            if (!map.cell.empty())
+            {
+                lat->cell.resize(static_cast<int>(map.cell.size()));
+                std::copy(map.cell.begin(), map.cell.end(), lat->cell.host_write());
+            }
             lat->slots = stride * map.Ly;
             lat->dof_of_slot.resize(lat->slots);
             lat->slot_of_dof.resize(ndof);
@@ -389,7 +434,7 @@ namespace cuddh
         if (!lat)
             return K->kernel_name();
         const int nb = lat->desc.n_basis;
-        return std::string(lat->pair ? "wave_pair nb" : "wave_lattice nb") + std::to_string(nb) + (lat->f32 ? " f32" : "") + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
+        return std::string(lat->pair ? "wave_pair nb" : (lat->cell.size() ? "wave_cells nb" : "wave_lattice nb")) + std::to_string(nb) + (lat->f32 ? " f32" : "") + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
     }
 
     WaveHoltzOptions::Precision WaveHoltz::precision() const { return lat && lat->f32 ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64; }
@@ -401,7 +446,7 @@ namespace cuddh
         const int n = lat->slots;
         const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
         const LatticeGrid g = {&lat->desc, n, ndof, nt, rk4, lat->pair, dt, filt.data(), cs.data(), sn.data(), lat->dof_of_slot.device_read(),
-                               lat->slot_of_dof.device_read(), stream()};
+                               lat->slot_of_dof.device_read(), stream(), lat->cell.size() ? lat->cell.device_read() : nullptr};
         if (lat->f32)
         {
             Lattice &L = *lat;

@@ -33,6 +33,9 @@ int cuddh_basis_deriv(void *basis, int m, const double *h_x, double *h_D); /* D 
 
 /* ---- mesh (reference include/Mesh2D.hpp) */
 void *cuddh_mesh_uniform_rect(int nx, double ax, double bx, int ny, double ay, double by);
+/* the cells of cuddh_mesh_uniform_rect(nx, ax, bx, ny, ay, by) whose h_present[i + nx * j] is nonzero (HOST, nx * ny bytes, at
+ * least one nonzero), in ascending cell index, with the unused vertices dropped: a grid mesh with missing cells */
+void *cuddh_mesh_grid_cells(int nx, double ax, double bx, int ny, double ay, double by, const unsigned char *h_present);
 void *cuddh_mesh_from_vertices(int n_pts, const double *h_xy, int n_elem, const int *h_elems);
 /* mesh ingestion (csrc/include/cuddh/meshio.hpp): the reference's text format (tests/load_unstructured_square.cpp:11-55),
  * `times` rounds of uniform refinement of an existing mesh, and labels for EnsembleSpace (n_parts compact element sets) */
@@ -361,6 +364,17 @@ int cuddh_waveholtz_launch(void *op);
  * verified to be a bijection that agrees on shared nodes and with the collocation points.  Returns 0, or nonzero with
  * cuddh_last_error() beginning "WaveHoltz error: sweep:". */
 int cuddh_wave_lattice_map(void *fem, int *h_dims, double *h_h, int *h_node_of);
+/* The lattice behind a space on a grid mesh with missing cells (host code): the elements are a subset of the cells of
+ * a uniform nx x ny grid, listed in ascending cell index i + nx j with cuddh_mesh_uniform_rect's corner order (what
+ * cuddh_mesh_grid_cells builds; a full grid qualifies too).  hx, hy come from element 0, the origin and nx, ny from the bounding
+ * box of all corners, an element's cell from its first corner.  h_dims, h_h as above; h_node_of (ndof): dof -> I + Lx J, an
+ * injection whose image is the nodes of the existing cells; h_cell (nx * ny bytes): 1 where cell i + nx j exists.  Each may be
+ * NULL.  Verified: every corner is where its cell has it (the tolerance above), cell indices strictly increase, shared nodes
+ * agree and match the collocation points, the map is injective, Lx Ly and stride Ly fit in an int.  Returns 0, or nonzero with
+ * cuddh_last_error() beginning "WaveHoltz error: sweep:" and nothing written.  cuddh_waveholtz_create_sweep and its successors try
+ * cuddh_wave_lattice_map first and this detection where that refuses; a mesh with missing cells runs cuddh_hip_wave_cells_*
+ * (kernel "wave_cells nb<n_basis>", "... f32"), and launch = 1 on it is refused ("WaveHoltz error: launch:"). */
+int cuddh_wave_lattice_map_cells(void *fem, int *h_dims, double *h_h, int *h_node_of, unsigned char *h_cell);
 /* the 1-D tables of the lattice form on the reference element: h_A (n_basis x n_basis, row-major) = D^T diag(w) D, h_w (n_basis) */
 int cuddh_wave_lattice_tables(void *basis, double *h_A, double *h_w);
 

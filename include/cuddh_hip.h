@@ -734,6 +734,60 @@ int cuddh_hip_wave_pair32_rk4_34(const cuddh_wave_lattice *lattice, double dt, d
 int cuddh_hip_wave_pair32_tile_x(void);
 int cuddh_hip_wave_pair32_tile_y(void);
 
+/* ------------------------------------------------------------------ whole-domain WaveHoltz march: lattice sweeps with missing cells
+ * csrc/kernels/wave_cells.hip (fp64) and wave_cells_f32.hip (fp32), DESIGN 4.5.4.  The lattice, layout, padding, stages and
+ * refusals of cuddh_hip_wave_lattice_*_f64 / cuddh_hip_wave32_*, on a grid whose cells are each present or absent: cell (DEVICE,
+ * nx * ny bytes) holds 1 where cell a + nx b exists and 0 where it does not.  K is the sum over the present cells of the
+ * element's Kronecker sum, regrouped per node.  With H = n_basis - 1, kx = I mod H, ky = J mod H, each sum from zero over
+ * ascending d by fused multiply-adds:
+ *   kx = 0:      sL = sum_{d = -H..0} A[H][H + d] p'(I + d, J)  (cell column I / H - 1),  wL = w[H];
+ *                sR = sum_{d = 0..H} A[0][d] p'(I + d, J)       (cell column I / H),      wR = w[0];
+ *   0 < kx < H:  sR = sum_{d = -kx..H - kx} A[kx][kx + d] p'(I + d, J)  (the one column I / H),  wR = w[kx];  sL = 0, no left column;
+ * sB, wB (cell row J / H - 1) and sA, wA (cell row J / H) along y likewise.  p' outside the lattice counts as zero, a column or row
+ * outside the grid as absent.  With f_XY = 1 where the cell in column X and row Y is present, 0 where it is absent or there is none:
+ *   aB = fma(f_RB, sR, f_LB sL),  aA = fma(f_RA, sR, f_LA sL),  tx = fma(wA, aA, wB aB),
+ *   bL = fma(f_LA, sA, f_LB sB),  bR = fma(f_RA, sA, f_RB sB),  ty = fma(wR, bR, wL bL),      (K p')(I, J) = fma(cx, tx, cy ty),
+ * and (K p')(I, J) = +0 at a node with no present cell around it (the caller keeps zero state, zero load and invm = 0 there, as in
+ * the padding).  The order depends on (I, J) and the flags only: bitwise reproducible, exact for integer tables.  A workgroup whose
+ * tile (cuddh_hip_wave_lattice_tile_x by _tile_y nodes, the same in both precisions) has no node in a present cell writes nothing.
+ * NULL cell is refused like a NULL vector.  The fp32 family rounds the tables, cx, cy and the scalars once, as cuddh_hip_wave32_*. */
+int cuddh_hip_wave_cells_rk2_a_f64(const cuddh_wave_lattice *lattice, const unsigned char *cell, double half_dt, double c, double s,
+                                   const double *p, const double *q, const double *invm, const double *Hi, const double *F, const double *G,
+                                   double *qh, double *ph, void *stream);
+int cuddh_hip_wave_cells_rk2_b_f64(const cuddh_wave_lattice *lattice, const unsigned char *cell, double dt, double c, double s, double filt,
+                                   const double *ph, const double *qh, const double *invm, const double *Hi, const double *F, const double *G,
+                                   double *p, double *q, double *u, double *v, void *stream);
+int cuddh_hip_wave_cells_rk4_1_f64(const cuddh_wave_lattice *lattice, const unsigned char *cell, double half_dt, double c, double s,
+                                   const double *p, const double *q, const double *invm, const double *Hi, const double *F, const double *G,
+                                   double *ps, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_cells_rk4_2_f64(const cuddh_wave_lattice *lattice, const unsigned char *cell, double half_dt, double c, double s,
+                                   const double *ps_in, const double *p, const double *q, const double *invm, const double *Hi, const double *F,
+                                   const double *G, double *ps_out, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_cells_rk4_3_f64(const cuddh_wave_lattice *lattice, const unsigned char *cell, double dt, double c, double s,
+                                   const double *ps_in, const double *p, const double *q, const double *invm, const double *Hi, const double *F,
+                                   const double *G, double *ps_out, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_cells_rk4_4_f64(const cuddh_wave_lattice *lattice, const unsigned char *cell, double sixth_dt, double c, double s, double filt,
+                                   const double *ps, const double *qs, const double *aq, const double *ap, const double *invm, const double *Hi,
+                                   const double *F, const double *G, double *p, double *q, double *u, double *v, void *stream);
+int cuddh_hip_wave_cells32_rk2_a(const cuddh_wave_lattice *lattice, const unsigned char *cell, double half_dt, double c, double s, const float *p,
+                                 const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *qh, float *ph,
+                                 void *stream);
+int cuddh_hip_wave_cells32_rk2_b(const cuddh_wave_lattice *lattice, const unsigned char *cell, double dt, double c, double s, double filt,
+                                 const float *ph, const float *qh, const float *invm, const float *Hi, const float *F, const float *G, float *p,
+                                 float *q, float *u, float *v, void *stream);
+int cuddh_hip_wave_cells32_rk4_1(const cuddh_wave_lattice *lattice, const unsigned char *cell, double half_dt, double c, double s, const float *p,
+                                 const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps, float *qs,
+                                 float *aq, float *ap, void *stream);
+int cuddh_hip_wave_cells32_rk4_2(const cuddh_wave_lattice *lattice, const unsigned char *cell, double half_dt, double c, double s,
+                                 const float *ps_in, const float *p, const float *q, const float *invm, const float *Hi, const float *F,
+                                 const float *G, float *ps_out, float *qs, float *aq, float *ap, void *stream);
+int cuddh_hip_wave_cells32_rk4_3(const cuddh_wave_lattice *lattice, const unsigned char *cell, double dt, double c, double s, const float *ps_in,
+                                 const float *p, const float *q, const float *invm, const float *Hi, const float *F, const float *G,
+                                 float *ps_out, float *qs, float *aq, float *ap, void *stream);
+int cuddh_hip_wave_cells32_rk4_4(const cuddh_wave_lattice *lattice, const unsigned char *cell, double sixth_dt, double c, double s, double filt,
+                                 const float *ps, const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi,
+                                 const float *F, const float *G, float *p, float *q, float *u, float *v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
