@@ -257,6 +257,14 @@ for _family in ("cuddh_hip_wave_cells_%s_f64", "cuddh_hip_wave_cells32_%s"):
     _sig(_family % "rk4_2", ci, _wl, vp, cd, cd, cd, *([vp] * 12))
     _sig(_family % "rk4_3", ci, _wl, vp, cd, cd, cd, *([vp] * 12))
     _sig(_family % "rk4_4", ci, _wl, vp, cd, cd, cd, cd, *([vp] * 13))
+# (lattice sweeps with a per-cell stiffness: the same arguments, the cell weights, double or float, in place of the flags)
+for _family in ("cuddh_hip_wave_weights_%s_f64", "cuddh_hip_wave_weights32_%s"):
+    _sig(_family % "rk2_a", ci, _wl, vp, cd, cd, cd, *([vp] * 9))
+    _sig(_family % "rk2_b", ci, _wl, vp, cd, cd, cd, cd, *([vp] * 11))
+    _sig(_family % "rk4_1", ci, _wl, vp, cd, cd, cd, *([vp] * 11))
+    _sig(_family % "rk4_2", ci, _wl, vp, cd, cd, cd, *([vp] * 12))
+    _sig(_family % "rk4_3", ci, _wl, vp, cd, cd, cd, *([vp] * 12))
+    _sig(_family % "rk4_4", ci, _wl, vp, cd, cd, cd, cd, *([vp] * 13))
 
 # ---- handle layer (cuddh_capi.h)
 _sig("cuddh_last_error", cp)
@@ -399,6 +407,9 @@ _sig("cuddh_waveholtz_launch", ci, vp)
 _sig("cuddh_wave_lattice_map", ci, vp, vp, vp, vp)
 _sig("cuddh_wave_lattice_map_cells", ci, vp, vp, vp, vp, vp)
 _sig("cuddh_wave_lattice_tables", ci, vp, vp, vp)
+_sig("cuddh_waveholtz_create_cell_stiffness", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, vp)
+_sig("cuddh_wave_lattice_cell_weights", ci, vp, vp, vp, vp)
+_sig("cuddh_waveholtz_coefficient_ratio", ci, ci, ci, vp, vp, vp, vp)
 
 
 def last_error() -> str:

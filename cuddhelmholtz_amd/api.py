@@ -745,6 +745,13 @@ class WaveHoltz(_Operator):
     launch "sweep" (the default: one launch per sweep) or "pair" (sweep "lattice" only, either precision): two sweeps per launch
     (csrc/kernels/wave_pair.hip, wave_pair_f32.hip): rk2_a with rk2_b, rk4_1 with rk4_2, rk4_3 with rk4_4.  The march is the
     per-sweep one bit for bit, in half the launches and about half the bytes.  Nothing selects "pair" by itself.
+    cell_stiffness None (the default: exactly the calls above) or an array of fem.mesh.n_elem() finite positive floats, one beta
+    per element in element order (sweep "lattice" only, launch "sweep" only, either precision, full and holed grids): the problem
+    becomes -div(beta grad U) - w^2 a^2 U = f with beta constant on each element, on csrc/kernels/wave_weights.hip /
+    wave_weights_f32.hip (info()["stiffness_kernel"] "wave_weights nb<n>").  time_ratio "coefficient" then is
+    max(1, ceil((1 - 1e-9) max_e sqrt(beta_e) / min_{g in e} a_g)).  M and H keep their form, so the absorbing faces discretise
+    beta dU/dn + i w a U = 0: the first-order absorbing condition only where beta = 1 along them.  A wrong length or dimension,
+    a value that is not finite and positive, another sweep or launch "pair" raise ValueError before any native call.
     A bad name, a coarsen outside its range, coarsen > 1 with "rk2", a bad ratio, "lattice" with "gauss" and "f32" or "pair" without "lattice"
     raise ValueError before any native call; a mesh the lattice form cannot take raises ValueError with the native message."""
 
@@ -754,7 +761,8 @@ class WaveHoltz(_Operator):
     LAUNCHES = ("sweep", "pair")
 
     def __init__(self, omega: float, h_a: np.ndarray, fem: H1Space, integrator: str = "rk2", coarsen: int | None = None, time_ratio=1,
-                 stiffness: str = "gauss", faces=None, sweep: str = "operator", precision: str = "f64", launch: str = "sweep"):
+                 stiffness: str = "gauss", faces=None, sweep: str = "operator", precision: str = "f64", launch: str = "sweep",
+                 cell_stiffness=None):
         scheme, coarsen = self._integrator(integrator, coarsen)
         ratio = self._ratio(time_ratio)
         if not isinstance(stiffness, str) or stiffness not in self.STIFFNESS:
@@ -771,6 +779,20 @@ class WaveHoltz(_Operator):
             raise ValueError(f"WaveHoltz: launch must be 'sweep' or 'pair', not {launch!r}")
         if launch == "pair" and sweep != "lattice":
             raise ValueError("WaveHoltz: launch 'pair' is an option of the lattice form; it needs sweep 'lattice'")
+        if cell_stiffness is not None:
+            if sweep != "lattice":
+                raise ValueError("WaveHoltz: cell_stiffness is an option of the lattice form; it needs sweep 'lattice'")
+            if launch == "pair":
+                raise ValueError("WaveHoltz: launch 'pair' has no form for cell_stiffness; it needs launch 'sweep'")
+            try:
+                cell_stiffness = np.asarray(cell_stiffness, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("WaveHoltz: cell_stiffness must be a one-dimensional array of floats") from None
+            if cell_stiffness.ndim != 1:
+                raise ValueError(f"WaveHoltz: cell_stiffness must be one-dimensional, one value per element, not of shape {cell_stiffness.shape}")
+            cell_stiffness = np.ascontiguousarray(cell_stiffness)
+            if not np.all(np.isfinite(cell_stiffness)) or not np.all(cell_stiffness > 0):
+                raise ValueError("WaveHoltz: cell_stiffness must be finite and positive")
         if faces is not None:
             faces = np.asarray(faces)
             if faces.ndim != 1 or (faces.size and not np.issubdtype(faces.dtype, np.integer)):
@@ -783,7 +805,12 @@ class WaveHoltz(_Operator):
             raise ValueError("WaveHoltz: the coefficient a must be finite and positive")
         args = (float(omega), _h(h_a), fem._h, scheme, coarsen, ratio, self.STIFFNESS.index(stiffness), None if faces is None else _h(faces),
                 -1 if faces is None else int(faces.size), self.SWEEPS.index(sweep))
-        if launch != "sweep":
+        if cell_stiffness is not None:
+            n_elem = fem.mesh.n_elem()
+            if cell_stiffness.size != n_elem:
+                raise ValueError(f"WaveHoltz: {cell_stiffness.size} cell_stiffness values for {n_elem} elements")
+            h = lib.cuddh_waveholtz_create_cell_stiffness(*args, self.PRECISIONS.index(precision), self.LAUNCHES.index(launch), _h(cell_stiffness))
+        elif launch != "sweep":
             h = lib.cuddh_waveholtz_create_launch(*args, self.PRECISIONS.index(precision), self.LAUNCHES.index(launch))
         elif precision == "f64":
             h = lib.cuddh_waveholtz_create_sweep(*args)

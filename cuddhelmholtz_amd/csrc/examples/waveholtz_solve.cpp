@@ -9,7 +9,9 @@
 //   it goes with --sweep lattice only), --coefficient one|disk (a == 1, the default, or the examples' disk of a = 0.2, projected as in
 //   ddh_solve), --void i0 j0 i1 j1 (any number of times: the cells i0 <= i < i1, j0 <= j < j1 of the nx x nx grid are left out, a
 //   sound-hard or absorbing obstacle; --sweep lattice then runs the sweeps with missing cells and refuses --launch pair; every
-//   boundary edge, the obstacle's walls included, is absorbing), --residuals (one more line: GMRES's residual history).
+//   boundary edge, the obstacle's walls included, is absorbing), --inclusion i0 j0 i1 j1 beta (any number of times: the stiffness
+//   coefficient beta > 0 on the cells i0 <= i < i1, j0 <= j < j1 and 1 elsewhere, -div(beta grad U) - w^2 a^2 U = f; it goes with
+//   --sweep lattice only, refuses --launch pair and composes with --void, whose cells take no value), --residuals (one more line: GMRES's residual history).
 // The load is the examples' pair of Gaussians in the real part and 0.1 (3 x^2 - 2 x y + y + 1) in the imaginary part.
 // Writes <out_dir>/xy.0000 and <out_dir>/waveholtz.0000 (raw fp64; "-": nothing) and prints one summary line.
 #include <algorithm>
@@ -30,6 +32,8 @@ int main(int argc_all, char **argv_all)
     int coarsen = 0; // 0: not given
     bool residuals = false;
     std::vector<int> voids; // four per --void
+    std::vector<int> inclusions;  // four per --inclusion
+    std::vector<double> betas;    // one per --inclusion
     std::vector<char *> args;
     for (int i = 0; i < argc_all; ++i)
     {
@@ -58,6 +62,17 @@ int main(int argc_all, char **argv_all)
         else if (arg == "--void")
         {
             std::cerr << "waveholtz_solve: --void takes four cell indices: i0 j0 i1 j1" << std::endl;
+            return 2;
+        }
+        else if (arg == "--inclusion" && i + 5 < argc_all)
+        {
+            for (int k = 0; k < 4; ++k)
+                inclusions.push_back(std::atoi(argv_all[++i]));
+            betas.push_back(std::atof(argv_all[++i]));
+        }
+        else if (arg == "--inclusion")
+        {
+            std::cerr << "waveholtz_solve: --inclusion takes four cell indices and a coefficient: i0 j0 i1 j1 beta" << std::endl;
             return 2;
         }
         else if (arg == "--residuals")
@@ -125,6 +140,16 @@ int main(int argc_all, char **argv_all)
         std::cerr << "waveholtz_solve: --launch pair has no form for a grid with missing cells yet: it does not go with --void" << std::endl;
         return 2;
     }
+    if (!betas.empty() && sweep != "lattice")
+    {
+        std::cerr << "waveholtz_solve: --inclusion is a per-cell stiffness of the lattice sweeps: it goes with --sweep lattice only" << std::endl;
+        return 2;
+    }
+    if (!betas.empty() && launch == "pair")
+    {
+        std::cerr << "waveholtz_solve: --launch pair has no form for a per-cell stiffness: it does not go with --inclusion" << std::endl;
+        return 2;
+    }
     if (coefficient != "one" && coefficient != "disk")
     {
         std::cerr << "waveholtz_solve: --coefficient takes one or disk, not " << coefficient << std::endl;
@@ -154,6 +179,25 @@ int main(int argc_all, char **argv_all)
             for (int i = i0; i < i1; ++i)
                 present[i + static_cast<std::size_t>(nx) * j] = 0;
     }
+    std::vector<double> cell_beta(betas.empty() ? 0 : present.size(), 1.0);
+    for (std::size_t k = 0; k < betas.size(); ++k)
+    {
+        const int i0 = inclusions[4 * k], j0 = inclusions[4 * k + 1], i1 = inclusions[4 * k + 2], j1 = inclusions[4 * k + 3];
+        if (i0 < 0 || j0 < 0 || i1 > nx || j1 > nx || i0 >= i1 || j0 >= j1 || !(betas[k] > 0.0) || !std::isfinite(betas[k]))
+        {
+            std::cerr << "waveholtz_solve: --inclusion " << i0 << " " << j0 << " " << i1 << " " << j1 << " " << betas[k]
+                      << " is no box of cells of the " << nx << " x " << nx << " grid with a finite positive coefficient" << std::endl;
+            return 2;
+        }
+        for (int j = j0; j < j1; ++j)
+            for (int i = i0; i < i1; ++i)
+                cell_beta[i + static_cast<std::size_t>(nx) * j] = betas[k];
+    }
+    // element order: the present cells, ascending
+    std::vector<double> beta;
+    for (std::size_t c = 0; c < cell_beta.size(); ++c)
+        if (present[c])
+            beta.push_back(cell_beta[c]);
     Mesh2D mesh = voids.empty() ? Mesh2D::uniform_rect(nx, -1.0, 1.0, nx, -1.0, 1.0) : grid_cells(nx, -1.0, 1.0, nx, -1.0, 1.0, present.data());
     Basis basis(nb);
     H1Space fem(mesh, basis);
@@ -187,6 +231,8 @@ int main(int argc_all, char **argv_all)
     opt.sweep = sweep == "lattice" ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels;
     opt.precision = precision == "f32" ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64;
     opt.launch = launch == "pair" ? WaveHoltzOptions::per_pair : WaveHoltzOptions::per_sweep;
+    if (!betas.empty())
+        opt.h_cell_stiffness = beta.data();
     WaveHoltz W(omega, a.host_read(), fem, opt);
 
     // wall time of each phase with a device sync at both ends, as ddh_solve

@@ -51,6 +51,22 @@ namespace cuddh
     /// refusal is then reported).  `cell` is empty exactly when the full detection accepted.
     WaveLatticeMap build_wave_lattice_or_cells_map(const H1Space &fem);
 
+    /// A per-cell stiffness coefficient on the cell grid of `map`: h_beta holds n_elem values in element order, every
+    /// one finite and positive.  On a full rectangle element e is cell e; on a grid with missing cells the present cells in
+    /// ascending order take the values in element order and absent cells get 0.  Returns nx ny weights, cell (a, b) at a + nx b.
+    /// A null h_beta, a value that is not finite and positive, or an n_elem that is not the map's number of cells is refused
+    /// through cuddh_error with a message that starts "WaveHoltz error: cell_stiffness:".
+    std::vector<double> wave_lattice_cell_weights(const WaveLatticeMap &map, int n_elem, const double *h_beta);
+
+    /// the check of h_beta alone (what wave_lattice_cell_weights refuses about the values)
+    void check_cell_stiffness(int n_elem, const double *h_beta);
+
+    /// The time ratio a two-parameter medium asks for: the local wave speed is sqrt(beta) / a, and the ratio is
+    /// max(1, ceil((1 - 1e-9) max_e (sqrt(beta_e) / min_{g in e} a_g))).  I (nodes_per_elem, n_elem): element node -> dof; h_a the
+    /// nodal coefficient; h_beta n_elem values, or null for beta == 1, which is max(1, ceil((1 - 1e-9) / min a)) over the dofs of the
+    /// elements.  A ratio above DDHTimeStep::max_ratio is refused through cuddh_error ("WaveHoltz error: time step: ...").
+    int wave_coefficient_ratio(int n_elem, int nodes_per_elem, const int *I, const double *h_a, const double *h_beta);
+
     /// the 1-D tables of the Kronecker form on the reference element [-1, 1]: A = D^T diag(w) D (row-major, n_basis x n_basis), D the
     /// collocation derivative matrix, and the Gauss-Lobatto weights w
     void wave_lattice_tables(const Basis &basis, double *A, double *w);

@@ -21,6 +21,10 @@
 // launch = per_pair (opt-in; the lattice form only, both precisions): two sweeps per launch (csrc/kernels/wave_pair.hip and
 // wave_pair_f32.hip): rk2_a with rk2_b, rk4_1 with rk4_2 and rk4_3 with rk4_4.  Half the launches, 0.56 x (RK2) and
 // 0.48 x (RK4) the vectors moved, and the bits of the per-sweep march.
+// h_cell_stiffness (opt-in; the lattice form only, per-sweep launches, both precisions): a coefficient beta per element in the
+// stiffness,  -div(beta grad U) - w^2 a^2 U = f  (csrc/kernels/wave_weights.hip and wave_weights_f32.hip).  M and H
+// keep their form, so the absorbing faces discretise  beta dU/dn + i w a U = 0:  the first-order absorbing condition only where
+// beta = 1 along them.
 // Everything else is fp64; all vectors are DEVICE pointers unless marked HOST.
 #ifndef CUDDH_AMD_WAVEHOLTZ_HPP
 #define CUDDH_AMD_WAVEHOLTZ_HPP
@@ -81,6 +85,15 @@ namespace cuddh
         /// absorbing faces: HOST edge ids; n_faces < 0 (the default): every boundary edge, DDH's choice
         const int *h_faces = nullptr;
         int n_faces = -1;
+        /// a per-cell stiffness coefficient beta (HOST, n_elem values in element order, each finite and positive; nullptr, the
+        /// default: beta == 1 and exactly the code paths above): the problem becomes  -div(beta grad U) - w^2 a^2 U = f  with beta
+        /// constant on each element.  It needs sweep = lattice and runs csrc/kernels/wave_weights.hip /
+        /// wave_weights_f32.hip on full rectangles and on grids with missing cells alike; a bad value or another sweep is refused
+        /// ("WaveHoltz error: cell_stiffness: ..."), launch = per_pair with it too ("WaveHoltz error: launch: ..."), before any
+        /// allocation or launch.  from_coefficient then is max(1, ceil((1 - 1e-9) max_e (sqrt(beta_e) / min_{g in e} a_g))).
+        /// Mass and faces are unchanged, M = diag(a^2 m) and H = diag(a h): the boundary condition discretised is
+        /// beta dU/dn + i w a U = 0, the first-order absorbing condition only where beta = 1 along the absorbing faces.
+        const double *h_cell_stiffness = nullptr;
     };
 
     class WaveHoltz : public Operator

@@ -559,8 +559,29 @@ extern "C"
     {
         return cuddh_waveholtz_create_launch(omega, h_a, fem, integrator, coarsen, time_ratio, stiffness, h_faces, n_faces, sweep, precision, 0);
     }
+    namespace
+    {
+        // cuddh_waveholtz_create_launch, and with h_beta cuddh_waveholtz_create_cell_stiffness
+        void *waveholtz_create(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                               const int *h_faces, int n_faces, int sweep, int precision, int launch, const double *h_beta);
+    } // namespace
     void *cuddh_waveholtz_create_launch(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
                                         const int *h_faces, int n_faces, int sweep, int precision, int launch)
+    {
+        return waveholtz_create(omega, h_a, fem, integrator, coarsen, time_ratio, stiffness, h_faces, n_faces, sweep, precision, launch, nullptr);
+    }
+    void *cuddh_waveholtz_create_cell_stiffness(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                                const int *h_faces, int n_faces, int sweep, int precision, int launch, const double *h_beta)
+    {
+        if (!h_beta)
+            return guarded_new<OpHandle>([&]() -> OpHandle *
+                                         { throw std::runtime_error("WaveHoltz error: cell_stiffness: no values were given (NULL)."); });
+        return waveholtz_create(omega, h_a, fem, integrator, coarsen, time_ratio, stiffness, h_faces, n_faces, sweep, precision, launch, h_beta);
+    }
+    namespace
+    {
+    void *waveholtz_create(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                           const int *h_faces, int n_faces, int sweep, int precision, int launch, const double *h_beta)
     {
         return guarded_new<OpHandle>([&]
         {
@@ -588,11 +609,13 @@ extern "C"
             o.sweep = sweep == 1 ? WaveHoltzOptions::lattice : WaveHoltzOptions::operator_kernels;
             o.precision = precision == 1 ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64;
             o.launch = launch == 1 ? WaveHoltzOptions::per_pair : WaveHoltzOptions::per_sweep;
+            o.h_cell_stiffness = h_beta;
             auto h = new OpHandle;
             h->op.reset(new WaveHoltz(omega, h_a, *static_cast<H1Space *>(fem), o));
             return h;
         });
     }
+    } // namespace
     namespace
     {
         const WaveHoltz &waveholtz_of(void *op)
@@ -681,6 +704,34 @@ extern "C"
                 std::copy(map.node_of.begin(), map.node_of.end(), h_node_of);
             if (h_cell)
                 std::copy(map.cell.begin(), map.cell.end(), h_cell);
+        });
+    }
+    int cuddh_wave_lattice_cell_weights(void *fem, const double *h_beta, double *h_weights, int *h_dims)
+    {
+        return guarded([&]
+        {
+            const H1Space &space = *static_cast<H1Space *>(fem);
+            check_cell_stiffness(space.mesh().n_elem(), h_beta);
+            const WaveLatticeMap map = build_wave_lattice_or_cells_map(space);
+            const std::vector<double> weights = wave_lattice_cell_weights(map, space.mesh().n_elem(), h_beta);
+            if (h_weights)
+                std::copy(weights.begin(), weights.end(), h_weights);
+            if (h_dims)
+            {
+                h_dims[0] = map.nx;
+                h_dims[1] = map.ny;
+            }
+        });
+    }
+    int cuddh_waveholtz_coefficient_ratio(int n_elem, int nodes_per_elem, const int *h_I, const double *h_a, const double *h_beta, int *h_ratio)
+    {
+        return guarded([&]
+        {
+            if (h_beta)
+                check_cell_stiffness(n_elem, h_beta);
+            const int ratio = wave_coefficient_ratio(n_elem, nodes_per_elem, h_I, h_a, h_beta);
+            if (h_ratio)
+                *h_ratio = ratio;
         });
     }
     int cuddh_wave_lattice_tables(void *basis, double *h_A, double *h_w)

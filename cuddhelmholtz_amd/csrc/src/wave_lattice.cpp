@@ -7,6 +7,8 @@
 #include <cmath>
 #include <string>
 
+#include "cuddh/ddh.hpp"
+
 namespace cuddh
 {
     namespace
@@ -305,6 +307,57 @@ namespace cuddh
         return L;
     }
     } // namespace
+
+    void check_cell_stiffness(int n_elem, const double *h_beta)
+    {
+        if (!h_beta || n_elem < 1)
+            cuddh_error("WaveHoltz error: cell_stiffness: no values were given.");
+        for (int e = 0; e < n_elem; ++e)
+            if (!std::isfinite(h_beta[e]) || !(h_beta[e] > 0.0))
+                cuddh_error(("WaveHoltz error: cell_stiffness: beta = " + std::to_string(h_beta[e]) + " at element " + std::to_string(e) +
+                             "; beta must be finite and positive.").c_str());
+    }
+
+    std::vector<double> wave_lattice_cell_weights(const WaveLatticeMap &map, int n_elem, const double *h_beta)
+    {
+        check_cell_stiffness(n_elem, h_beta);
+        const std::size_t n_cells = static_cast<std::size_t>(map.nx) * map.ny;
+        const std::size_t present = map.cell.empty() ? n_cells : static_cast<std::size_t>(std::count(map.cell.begin(), map.cell.end(), 1));
+        if (present != static_cast<std::size_t>(n_elem))
+            cuddh_error(("WaveHoltz error: cell_stiffness: " + std::to_string(n_elem) + " values for the " + std::to_string(present) +
+                         " cells of the grid.").c_str());
+        std::vector<double> weights(n_cells, 0.0);
+        if (map.cell.empty())
+            std::copy(h_beta, h_beta + n_elem, weights.begin());
+        else
+        {
+            // the elements are the present cells in ascending order (cells_map verifies it)
+            int e = 0;
+            for (std::size_t c = 0; c < n_cells; ++c)
+                if (map.cell[c])
+                    weights[c] = h_beta[e++];
+        }
+        return weights;
+    }
+
+    int wave_coefficient_ratio(int n_elem, int nodes_per_elem, const int *I, const double *h_a, const double *h_beta)
+    {
+        if (n_elem < 1 || nodes_per_elem < 1 || !I || !h_a)
+            cuddh_error("WaveHoltz error: time step: the ratio needs the elements' nodes and the coefficient.");
+        double speed = 0.0; // max over the elements of sqrt(beta) / min a
+        for (int e = 0; e < n_elem; ++e)
+        {
+            double a_min = INFINITY;
+            for (int k = 0; k < nodes_per_elem; ++k)
+                a_min = std::min(a_min, h_a[I[k + static_cast<std::size_t>(nodes_per_elem) * e]]);
+            speed = std::max(speed, (h_beta ? std::sqrt(h_beta[e]) : 1.0) / a_min);
+        }
+        const double steps = std::ceil(speed * (1.0 - 1e-9));
+        if (!(steps <= DDHTimeStep::max_ratio))
+            cuddh_error(("WaveHoltz error: time step: max sqrt(beta) / a = " + std::to_string(speed) + " asks for more than " +
+                         std::to_string(DDHTimeStep::max_ratio) + " times the mesh grid's steps.").c_str());
+        return std::max(1, static_cast<int>(steps));
+    }
 
     void wave_lattice_tables(const Basis &basis, double *A, double *w)
     {

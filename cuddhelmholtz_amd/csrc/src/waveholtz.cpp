@@ -4,7 +4,8 @@
 // the same call sequence on the fp32 family of csrc/kernels/wave_lattice_f32.hip (cuddh_hip_wave32_*); with launch = per_pair two
 // sweeps per launch (csrc/kernels/wave_pair.hip and wave_pair_f32.hip: cuddh_hip_wave_pair_*, cuddh_hip_wave_pair32_*); on a grid
 // mesh with missing cells the per-sweep sequence on csrc/kernels/wave_cells.hip and wave_cells_f32.hip (cuddh_hip_wave_cells_*,
-// cuddh_hip_wave_cells32_*).
+// cuddh_hip_wave_cells32_*); with a per-cell stiffness coefficient the per-sweep sequence on csrc/kernels/wave_weights.hip
+// and wave_weights_f32.hip (cuddh_hip_wave_weights_*, cuddh_hip_wave_weights32_*).
 #include "cuddh/waveholtz.hpp"
 
 #include <algorithm>
@@ -50,6 +51,10 @@ namespace cuddh
                 cuddh_error("WaveHoltz error: launch: the launch must be per_sweep or per_pair.");
             if (o.launch == WaveHoltzOptions::per_pair && o.sweep != WaveHoltzOptions::lattice)
                 cuddh_error("WaveHoltz error: launch: per_pair is an option of the lattice form; it needs sweep = lattice.");
+            if (o.h_cell_stiffness && o.sweep != WaveHoltzOptions::lattice)
+                cuddh_error("WaveHoltz error: cell_stiffness: a per-cell stiffness is an option of the lattice form; it needs sweep = lattice.");
+            if (o.h_cell_stiffness && o.launch == WaveHoltzOptions::per_pair)
+                cuddh_error("WaveHoltz error: launch: per_pair has no form for a per-cell stiffness; it needs launch = per_sweep.");
         }
 
         host_device_dvec rule_weights(const QuadratureRule &quad)
@@ -86,6 +91,12 @@ namespace cuddh
             static constexpr auto cells_rk4_2 = cuddh_hip_wave_cells_rk4_2_f64;
             static constexpr auto cells_rk4_3 = cuddh_hip_wave_cells_rk4_3_f64;
             static constexpr auto cells_rk4_4 = cuddh_hip_wave_cells_rk4_4_f64;
+            static constexpr auto weights_rk2_a = cuddh_hip_wave_weights_rk2_a_f64;
+            static constexpr auto weights_rk2_b = cuddh_hip_wave_weights_rk2_b_f64;
+            static constexpr auto weights_rk4_1 = cuddh_hip_wave_weights_rk4_1_f64;
+            static constexpr auto weights_rk4_2 = cuddh_hip_wave_weights_rk4_2_f64;
+            static constexpr auto weights_rk4_3 = cuddh_hip_wave_weights_rk4_3_f64;
+            static constexpr auto weights_rk4_4 = cuddh_hip_wave_weights_rk4_4_f64;
         };
         template <>
         struct LatticeKernels<float>
@@ -108,6 +119,12 @@ namespace cuddh
             static constexpr auto cells_rk4_2 = cuddh_hip_wave_cells32_rk4_2;
             static constexpr auto cells_rk4_3 = cuddh_hip_wave_cells32_rk4_3;
             static constexpr auto cells_rk4_4 = cuddh_hip_wave_cells32_rk4_4;
+            static constexpr auto weights_rk2_a = cuddh_hip_wave_weights32_rk2_a;
+            static constexpr auto weights_rk2_b = cuddh_hip_wave_weights32_rk2_b;
+            static constexpr auto weights_rk4_1 = cuddh_hip_wave_weights32_rk4_1;
+            static constexpr auto weights_rk4_2 = cuddh_hip_wave_weights32_rk4_2;
+            static constexpr auto weights_rk4_3 = cuddh_hip_wave_weights32_rk4_3;
+            static constexpr auto weights_rk4_4 = cuddh_hip_wave_weights32_rk4_4;
         };
 
         /// the lattice vectors of one period (DEVICE); F, G null without a load; PS2, AQ, AP used by rk4 only
@@ -116,6 +133,7 @@ namespace cuddh
         {
             R *P, *Q, *U, *V, *PS, *QS, *PS2, *AQ, *AP, *F, *G;
             const R *IM, *HI;
+            const R *W = nullptr; // the cell weights of wave_weights.hip (nx ny), null without a per-cell stiffness
         };
 
         /// what a period reads besides its vectors
@@ -182,6 +200,26 @@ namespace cuddh
                     std::swap(P, P2);
                 }
             }
+            else if (x.W && !g.rk4)
+            {
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    detail::check_hip(Kn::weights_rk2_a(D, x.W, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
+                    detail::check_hip(Kn::weights_rk2_b(D, x.W, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+                }
+            }
+            else if (x.W)
+            {
+                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2;
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    const int k = 2 * it - 2;
+                    detail::check_hip(Kn::weights_rk4_1(D, x.W, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::weights_rk4_2(D, x.W, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::weights_rk4_3(D, x.W, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::weights_rk4_4(D, x.W, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+                }
+            }
             else if (g.cell && !g.rk4)
             {
                 for (int it = 1; it <= g.nt; ++it)
@@ -239,6 +277,10 @@ namespace cuddh
         bool pair = false;                          // launch = per_pair: two sweeps per launch (wave_pair.hip)
         HostDeviceArray<float> invm, Hi;
         mutable HostDeviceArray<float> p, q, u, v, ps, qs, ps2f, aq, ap, F, G;
+        // a per-cell stiffness (wave_weights.hip): nx ny weights in the march's precision, rounded once for f32; empty without one
+        host_device_dvec weight;
+        HostDeviceArray<float> weight32;
+        bool weighted() const { return weight.size() || weight32.size(); }
     };
 
     WaveHoltz::WaveHoltz(double omega_, const double *h_a, const H1Space &fem, const WaveHoltzOptions &o)
@@ -254,8 +296,15 @@ namespace cuddh
                 cuddh_error(("WaveHoltz error: a = " + std::to_string(h_a[g]) + " at dof " + std::to_string(g) + "; a must be finite and positive.").c_str());
             a_min = std::min(a_min, h_a[g]);
         }
+        if (o.h_cell_stiffness)
+            check_cell_stiffness(fem.mesh().n_elem(), o.h_cell_stiffness);
         ratio = o.time_ratio;
-        if (ratio == WaveHoltzOptions::from_coefficient)
+        if (ratio == WaveHoltzOptions::from_coefficient && o.h_cell_stiffness)
+        {
+            const int nb1 = fem.basis().size();
+            ratio = wave_coefficient_ratio(fem.mesh().n_elem(), nb1 * nb1, fem.global_indices(MemorySpace::HOST), h_a, o.h_cell_stiffness);
+        }
+        else if (ratio == WaveHoltzOptions::from_coefficient)
         {
             if (std::ceil((1.0 / a_min) * (1.0 - 1e-9)) > DDHTimeStep::max_ratio)
                 cuddh_error(("WaveHoltz error: time step: min a = " + std::to_string(a_min) + " asks for more than " +
@@ -288,7 +337,23 @@ namespace cuddh
             lat->desc.cx = map.hy / map.hx;
             lat->desc.cy = map.hx / map.hy;
             wave_lattice_tables(fem.basis(), lat->desc.A, lat->desc.w);
-            if (!map.cell.empty())
+            if (o.h_cell_stiffness)
+            {
+                // the weighted kernels take full and holed grids alike: an absent cell is weight zero, and no flags are kept
+                const std::vector<double> wts = wave_lattice_cell_weights(map, fem.mesh().n_elem(), o.h_cell_stiffness);
+                const int n_cells = static_cast<int>(wts.size());
+                if (f32)
+                {
+                    lat->weight32.resize(n_cells);
+                    std::transform(wts.begin(), wts.end(), lat->weight32.host_write(), [](double b) { return static_cast<float>(b); });
+                }
+                else
+                {
+                    lat->weight.resize(n_cells);
+                    std::copy(wts.begin(), wts.end(), lat->weight.host_write());
+                }
+            }
+            else if (!map.cell.empty())
             {
                 lat->cell.resize(static_cast<int>(map.cell.size()));
                 std::copy(map.cell.begin(), map.cell.end(), lat->cell.host_write());
@@ -434,7 +499,7 @@ namespace cuddh
         if (!lat)
             return K->kernel_name();
         const int nb = lat->desc.n_basis;
-        return std::string(lat->pair ? "wave_pair nb" : (lat->cell.size() ? "wave_cells nb" : "wave_lattice nb")) + std::to_string(nb) + (lat->f32 ? " f32" : "") + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
+        return std::string(lat->weighted() ? "wave_weights nb" : lat->pair ? "wave_pair nb" : (lat->cell.size() ? "wave_cells nb" : "wave_lattice nb")) + std::to_string(nb) + (lat->f32 ? " f32" : "") + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
     }
 
     WaveHoltzOptions::Precision WaveHoltz::precision() const { return lat && lat->f32 ? WaveHoltzOptions::f32 : WaveHoltzOptions::f64; }
@@ -455,10 +520,12 @@ namespace cuddh
                 L.F.resize(n);
                 L.G.resize(n);
             }
-            const LatticeVectors<float> x = {L.p.device_write(), L.q.device_write(), L.u.device_write(), L.v.device_write(), L.ps.device_write(),
+            LatticeVectors<float> x = {L.p.device_write(), L.q.device_write(), L.u.device_write(), L.v.device_write(), L.ps.device_write(),
                                              L.qs.device_write(), rk4 ? L.ps2f.device_write() : nullptr, rk4 ? L.aq.device_write() : nullptr,
                                              rk4 ? L.ap.device_write() : nullptr, f ? L.F.device_write() : nullptr,
                                              f ? L.G.device_write() : nullptr, L.invm.device_read(), L.Hi.device_read()};
+            if (L.weight32.size())
+                x.W = L.weight32.device_read();
             return lattice_march(g, x, z_in, f, z_out);
         }
         if (f && F.size() != n)
@@ -466,10 +533,12 @@ namespace cuddh
             F.resize(n);
             G.resize(n);
         }
-        const LatticeVectors<double> x = {p.device_write(), q.device_write(), u.device_write(), v.device_write(), ps.device_write(),
+        LatticeVectors<double> x = {p.device_write(), q.device_write(), u.device_write(), v.device_write(), ps.device_write(),
                                           qs.device_write(), rk4 ? lat->ps2.device_write() : nullptr, rk4 ? aq.device_write() : nullptr,
                                           rk4 ? ap.device_write() : nullptr, f ? F.device_write() : nullptr, f ? G.device_write() : nullptr,
                                           invm.device_read(), Hi.device_read()};
+        if (lat->weight.size())
+            x.W = lat->weight.device_read();
         lattice_march(g, x, z_in, f, z_out);
     }
 

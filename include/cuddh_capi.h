@@ -375,6 +375,27 @@ int cuddh_wave_lattice_map(void *fem, int *h_dims, double *h_h, int *h_node_of);
  * cuddh_wave_lattice_map first and this detection where that refuses; a mesh with missing cells runs cuddh_hip_wave_cells_*
  * (kernel "wave_cells nb<n_basis>", "... f32"), and launch = 1 on it is refused ("WaveHoltz error: launch:"). */
 int cuddh_wave_lattice_map_cells(void *fem, int *h_dims, double *h_h, int *h_node_of, unsigned char *h_cell);
+/* cuddh_waveholtz_create_launch with a per-cell stiffness coefficient behind its arguments: h_beta, HOST, one value
+ * per element in element order, each finite and positive.  The problem is  -div(beta grad U) - w^2 a^2 U = f  with beta constant
+ * on each element; the march runs cuddh_hip_wave_weights_* / cuddh_hip_wave_weights32_* (cuddh_waveholtz_info's kernel is
+ * "wave_weights nb<n_basis>", "... f32") on a full rectangle and on a grid with missing cells alike.  Refused before anything is
+ * allocated (NULL): a NULL h_beta, a value that is not finite and positive, sweep != 1 ("WaveHoltz error: cell_stiffness:");
+ * launch = 1 ("WaveHoltz error: launch:": there is no paired form).  time_ratio = 0 is cuddh_waveholtz_coefficient_ratio's rule.
+ * Mass and faces are unchanged (M = diag(a^2 m), H = diag(a h)): the absorbing faces discretise  beta dU/dn + i w a U = 0,  the
+ * first-order absorbing condition only where beta = 1 along them. */
+void *cuddh_waveholtz_create_cell_stiffness(double omega, const double *h_a, void *fem, int integrator, int coarsen, int time_ratio, int stiffness,
+                                            const int *h_faces, int n_faces, int sweep, int precision, int launch, const double *h_beta);
+/* Plain host code.  The cell weights the weighted kernels read: h_beta as above on the cell grid the lattice detection finds for
+ * fem (cuddh_wave_lattice_map, and where that refuses cuddh_wave_lattice_map_cells).  On a full rectangle element e is cell e; on
+ * a grid with missing cells the present cells in ascending order take the values in element order and absent cells get 0.
+ * h_weights (nx * ny, cell (a, b) at a + nx b) and h_dims (2: nx, ny) may each be NULL.  Returns 0, or nonzero with
+ * cuddh_last_error() beginning "WaveHoltz error: cell_stiffness:" or "WaveHoltz error: sweep:" and nothing written. */
+int cuddh_wave_lattice_cell_weights(void *fem, const double *h_beta, double *h_weights, int *h_dims);
+/* Plain host code.  The ratio time_ratio = 0 chooses: max(1, ceil((1 - 1e-9) max_e (sqrt(beta_e) / min_{g in e} a_g))), the local
+ * wave speed being sqrt(beta) / a.  h_I (nodes_per_elem x n_elem): element node -> dof; h_a the nodal coefficient; h_beta n_elem
+ * values or NULL (beta == 1: the rule of cuddh_waveholtz_create).  Returns 0 and the ratio in *h_ratio, or nonzero with
+ * cuddh_last_error() beginning "WaveHoltz error: time step:" (above 256) or "WaveHoltz error: cell_stiffness:" and nothing written. */
+int cuddh_waveholtz_coefficient_ratio(int n_elem, int nodes_per_elem, const int *h_I, const double *h_a, const double *h_beta, int *h_ratio);
 /* the 1-D tables of the lattice form on the reference element: h_A (n_basis x n_basis, row-major) = D^T diag(w) D, h_w (n_basis) */
 int cuddh_wave_lattice_tables(void *basis, double *h_A, double *h_w);
 

@@ -788,6 +788,53 @@ int cuddh_hip_wave_cells32_rk4_4(const cuddh_wave_lattice *lattice, const unsign
                                  const float *ps, const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi,
                                  const float *F, const float *G, float *p, float *q, float *u, float *v, void *stream);
 
+/* ------------------------------------------------------------------ whole-domain WaveHoltz march: lattice sweeps with a per-cell stiffness
+ * csrc/kernels/wave_weights.hip (fp64) and wave_weights_f32.hip (fp32), DESIGN 4.5.5: the collocated stiffness of -div(beta grad .),
+ * beta constant on each cell.  The arguments, the lattice, layout, padding, stages, refusals and aliasing rules are those of
+ * cuddh_hip_wave_cells_* above, with one change: `weight` (DEVICE, nx * ny reals, double in the fp64 family and float in the fp32
+ * one, cell (a, b) at a + nx b) in place of the flags.  The stencil is the one stated there, term by term and in that order, with
+ * f_XY the weight of the cell in column X and row Y and 0 where there is no such cell; (K p')(I, J) = +0 where all four are zero.
+ * With weights in {0, 1} the results are the bits of cuddh_hip_wave_cells_*.  A workgroup whose tile has no node in a cell of
+ * non-zero weight writes nothing.  The kernels do not inspect the weights: finiteness and sign are the caller's business.
+ * hipErrorInvalidValue before any launch, nothing written: a NULL weight, F / G given singly, a bad description or stride, a vector
+ * off 16 bytes, an output equal to the stencil input. */
+int cuddh_hip_wave_weights_rk2_a_f64(const cuddh_wave_lattice *lattice, const double *weight, double half_dt, double c, double s,
+                                     const double *p, const double *q, const double *invm, const double *Hi, const double *F, const double *G,
+                                     double *qh, double *ph, void *stream);
+int cuddh_hip_wave_weights_rk2_b_f64(const cuddh_wave_lattice *lattice, const double *weight, double dt, double c, double s, double filt,
+                                     const double *ph, const double *qh, const double *invm, const double *Hi, const double *F, const double *G,
+                                     double *p, double *q, double *u, double *v, void *stream);
+int cuddh_hip_wave_weights_rk4_1_f64(const cuddh_wave_lattice *lattice, const double *weight, double half_dt, double c, double s,
+                                     const double *p, const double *q, const double *invm, const double *Hi, const double *F, const double *G,
+                                     double *ps, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_weights_rk4_2_f64(const cuddh_wave_lattice *lattice, const double *weight, double half_dt, double c, double s,
+                                     const double *ps_in, const double *p, const double *q, const double *invm, const double *Hi, const double *F,
+                                     const double *G, double *ps_out, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_weights_rk4_3_f64(const cuddh_wave_lattice *lattice, const double *weight, double dt, double c, double s,
+                                     const double *ps_in, const double *p, const double *q, const double *invm, const double *Hi, const double *F,
+                                     const double *G, double *ps_out, double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_weights_rk4_4_f64(const cuddh_wave_lattice *lattice, const double *weight, double sixth_dt, double c, double s, double filt,
+                                     const double *ps, const double *qs, const double *aq, const double *ap, const double *invm, const double *Hi,
+                                     const double *F, const double *G, double *p, double *q, double *u, double *v, void *stream);
+int cuddh_hip_wave_weights32_rk2_a(const cuddh_wave_lattice *lattice, const float *weight, double half_dt, double c, double s, const float *p,
+                                   const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *qh, float *ph,
+                                   void *stream);
+int cuddh_hip_wave_weights32_rk2_b(const cuddh_wave_lattice *lattice, const float *weight, double dt, double c, double s, double filt,
+                                   const float *ph, const float *qh, const float *invm, const float *Hi, const float *F, const float *G, float *p,
+                                   float *q, float *u, float *v, void *stream);
+int cuddh_hip_wave_weights32_rk4_1(const cuddh_wave_lattice *lattice, const float *weight, double half_dt, double c, double s, const float *p,
+                                   const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps, float *qs,
+                                   float *aq, float *ap, void *stream);
+int cuddh_hip_wave_weights32_rk4_2(const cuddh_wave_lattice *lattice, const float *weight, double half_dt, double c, double s,
+                                   const float *ps_in, const float *p, const float *q, const float *invm, const float *Hi, const float *F,
+                                   const float *G, float *ps_out, float *qs, float *aq, float *ap, void *stream);
+int cuddh_hip_wave_weights32_rk4_3(const cuddh_wave_lattice *lattice, const float *weight, double dt, double c, double s, const float *ps_in,
+                                   const float *p, const float *q, const float *invm, const float *Hi, const float *F, const float *G,
+                                   float *ps_out, float *qs, float *aq, float *ap, void *stream);
+int cuddh_hip_wave_weights32_rk4_4(const cuddh_wave_lattice *lattice, const float *weight, double sixth_dt, double c, double s, double filt,
+                                   const float *ps, const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi,
+                                   const float *F, const float *G, float *p, float *q, float *u, float *v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

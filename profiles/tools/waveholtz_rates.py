@@ -40,6 +40,15 @@ cells    (parts cells_step, cells_solve; written for profiles/r29/wave_cells_rat
          Gaussians, GMRES(20), 1e-4, rk4 / 4) with a sound-hard square obstacle of nx / 8 x nx / 8 cells at [0.25, 0.5]^2, sweep
          "lattice" in fp64 and fp32 against sweep "operator" with stiffness "lobatto" on the same mesh: matvecs and seconds.
 
+weights  (parts weights_step, weights_solve; written for profiles/r30/wave_weights_rates.txt) the sweeps with a per-cell stiffness
+         weight (csrc/kernels/wave_weights.hip, wave_weights_f32.hip) beside the sweeps of the same build, alternating
+         in one run, fp64 and fp32, rk2 and rk4: us per time step from the entry points (homogeneous form) of
+         cuddh_hip_wave_weights_* on an all-ones weight array, of cuddh_hip_wave_cells_* on all-ones flags and of
+         cuddh_hip_wave_lattice_* / wave32_* (what the real-valued weights cost); one solve in the example's regime (disk
+         coefficient, Gaussians, GMRES(20), 1e-4, rk4 / 4, every boundary edge absorbing) with an inclusion of beta = 4 on nx / 8 x
+         nx / 8 cells at [0.25, 0.5]^2 (time ratio 1, as the example has it for its disk of a = 0.2), in fp64 and fp32, and the
+         same solve at beta == 1 on wave_lattice: matvecs and seconds.
+
   python profiles/tools/waveholtz_rates.py [parts=stages,period,solve] [sizes=256,512,1024] [solve_sizes=256,512] [reps=7] [out=profiles/r24/waveholtz_rates.txt]
 """
 import ctypes as C
@@ -661,12 +670,93 @@ def cells_solve(nx):
     say(f"  seconds: lattice f64 / operator {sec['lattice f64'] / sec['operator/lobatto']:.3f}, lattice f32 / operator {sec['lattice f32'] / sec['operator/lobatto']:.3f}")
 
 
+def weights_step(nx):
+    L, st = N.lib, stream()
+    dt = 1e-9  # (the timed launches repeat on the same vectors: keep them bounded)
+    fs, slots, keep = {}, {}, []
+    flags = torch.ones(nx * nx, dtype=torch.uint8, device=dev)
+    for tag, dtype, multiple in (("f64", torch.float64, 2), ("f32", torch.float32, 4)):
+        D, Lx = lattice_description(nx, multiple)
+        m = D.stride * Lx
+        slots[tag] = m
+        g = torch.Generator(device=dev).manual_seed(1)
+        v = {k: torch.randn(m, dtype=dtype, device=dev, generator=g) for k in ("p", "q", "u", "v", "ps", "ps2", "qs", "aq", "ap")}
+        v["invm"] = torch.rand(m, dtype=dtype, device=dev, generator=g) + 0.5
+        v["Hi"] = torch.zeros(m, dtype=dtype, device=dev)
+        if D.stride > Lx:  # the padding columns: zero state, invm = 0
+            for t in v.values():
+                t.view(Lx, D.stride)[:, Lx:] = 0.0
+        ones = torch.ones(nx * nx, dtype=dtype, device=dev)
+        a, d = {k: p(t) for k, t in v.items()}, C.byref(D)
+        keep.append((D, v, ones))
+        lat = (lambda name: getattr(L, f"cuddh_hip_wave_lattice_{name}_f64")) if tag == "f64" else (lambda name: getattr(L, f"cuddh_hip_wave32_{name}"))
+        cel = (lambda name: getattr(L, f"cuddh_hip_wave_cells_{name}_f64")) if tag == "f64" else (lambda name: getattr(L, f"cuddh_hip_wave_cells32_{name}"))
+        wts = (lambda name: getattr(L, f"cuddh_hip_wave_weights_{name}_f64")) if tag == "f64" else (lambda name: getattr(L, f"cuddh_hip_wave_weights32_{name}"))
+
+        def step(scheme, fn, head, a=a):
+            if scheme == "rk2":
+                N.check(fn("rk2_a")(*head, dt / 2, 1.0, 0.0, a["p"], a["q"], a["invm"], a["Hi"], None, None, a["qs"], a["ps"], st))
+                N.check(fn("rk2_b")(*head, dt, 1.0, 0.0, 1e-3, a["ps"], a["qs"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st))
+            else:
+                N.check(fn("rk4_1")(*head, dt / 2, 1.0, 0.0, a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st))
+                N.check(fn("rk4_2")(*head, dt / 2, 1.0, 0.0, a["ps"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps2"], a["qs"], a["aq"], a["ap"], st))
+                N.check(fn("rk4_3")(*head, dt, 1.0, 0.0, a["ps2"], a["p"], a["q"], a["invm"], a["Hi"], None, None, a["ps"], a["qs"], a["aq"], a["ap"], st))
+                N.check(fn("rk4_4")(*head, dt / 6, 1.0, 0.0, 1e-3, a["ps"], a["qs"], a["aq"], a["ap"], a["invm"], a["Hi"], None, None, a["p"], a["q"], a["u"], a["v"], st))
+
+        for scheme in ("rk2", "rk4"):
+            fs[f"{scheme} lattice {tag}"] = lambda scheme=scheme, lat=lat, d=d, step=step: step(scheme, lat, (d,))
+            fs[f"{scheme} cells {tag}"] = lambda scheme=scheme, cel=cel, d=d, step=step: step(scheme, cel, (d, p(flags)))
+            fs[f"{scheme} weights {tag}"] = lambda scheme=scheme, wts=wts, d=d, step=step, ones=ones: step(scheme, wts, (d, p(ones)))
+    t = timed(fs, inner=20)
+    say(f"weights step nx={nx} slots f64 {slots['f64']} ({8 * slots['f64'] / 1e6:.1f} MB per vector), f32 {slots['f32']} ({4 * slots['f32'] / 1e6:.1f} MB per vector); "
+        f"tile {L.cuddh_hip_wave_lattice_tile_x()} x {L.cuddh_hip_wave_lattice_tile_y()}; every weight and every flag 1; us per time step, median of {reps} (min max)")
+    for scheme in ("rk2", "rk4"):
+        for tag in ("f64", "f32"):
+            (ml, ll, hl), (mc, lc, hc), (mw, lw, hw) = (t[f"{scheme} {k} {tag}"] for k in ("lattice", "cells", "weights"))
+            say(f"  {scheme} {tag}: wave_lattice {1e3 * ml:8.1f} ({1e3 * ll:.1f} {1e3 * hl:.1f});  wave_cells {1e3 * mc:8.1f} ({1e3 * lc:.1f} {1e3 * hc:.1f});  "
+                f"wave_weights {1e3 * mw:8.1f} ({1e3 * lw:.1f} {1e3 * hw:.1f});  weights / cells {mw / mc:.3f}, weights / lattice {mw / ml:.3f}")
+    del keep
+
+
+def weights_solve(nx):
+    k0, k1 = 5 * nx // 8, 6 * nx // 8  # the inclusion: nx / 8 x nx / 8 cells at [0.25, 0.5]^2
+    beta = np.ones((nx, nx))
+    beta[k0:k1, k0:k1] = 4.0
+    mesh, fem = space(nx)
+    n = fem.size()
+    omega = 2 * math.pi * nx / 10
+    f = torch.zeros(2 * n, dtype=torch.float64, device=dev)
+    a = torch.zeros(n, dtype=torch.float64, device=dev)
+    cd.linear_functional(fem, cd.GAUSSIANS, f[:n], param=omega)
+    cd.linear_functional(fem, cd.ALPHA_DISK, a)
+    cd.DiagInvMassMatrix(fem).action(a, a)
+    say(f"weights solve nx={nx}: ndof={n}, beta = 4 on the cells [{k0}, {k1})^2 and 1 elsewhere, omega={omega:.2f}, disk coefficient, rk4/4, "
+        f"every boundary edge absorbing, GMRES(20) tol 1e-4")
+    sec = {}
+    for name, kw in (("weights f64", dict(cell_stiffness=beta.reshape(-1))), ("weights f32", dict(cell_stiffness=beta.reshape(-1), precision="f32")),
+                     ("beta = 1 f64", dict()), ("beta = 1 f32", dict(precision="f32"))):
+        W = cd.WaveHoltz(omega, a.cpu().numpy(), fem, integrator="rk4", coarsen=4, stiffness="lobatto", sweep="lattice", **kw)
+        b, z = torch.empty_like(f), torch.zeros_like(f)
+        W.rhs(f, b)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = cd.gmres(2 * n, z, W, b, 20, 400, 1e-4, max_seconds=200.0)
+        torch.cuda.synchronize()
+        sec[name] = time.perf_counter() - t0
+        info = W.info()
+        say(f"  {name:14s} [{info['stiffness_kernel']}] nt={info['nt']}: success={out.success} matvecs={out.num_matvec} cycles={out.num_iter} "
+            f"rel_res={out.res_norm[-1] / out.res_norm[0]:.3e} seconds={sec[name]:.2f} ms_per_period={1e3 * sec[name] / max(1, out.num_matvec):.2f} "
+            f"us_per_sweep={1e6 * sec[name] / max(1, out.num_matvec) / info['sweeps_per_period']:.1f} finite={bool(torch.isfinite(z).all())}")
+        del W
+
+
 say(f"waveholtz_rates: {torch.cuda.get_device_name(0)}, n_basis {NB}, a == 1, omega = 2 pi nx / 10, reps {reps}")
 for part, fn, ns in (("stages", stages, sizes), ("period", period, sizes), ("solve", solve, solve_sizes), ("lattice_stages", lattice_stages, sizes),
                      ("lattice_period", lattice_period, sizes), ("lattice_solve", lattice_solve, solve_sizes),
                      ("lattice32_stages", lattice32_stages, sizes), ("lattice32_period", lattice32_period, sizes),
                      ("lattice32_solve", lattice32_solve, solve_sizes), ("pair_step", pair_step, sizes), ("pair_period", pair_period, sizes),
-                     ("pair_solve", pair_solve, solve_sizes), ("cells_step", cells_step, sizes), ("cells_solve", cells_solve, solve_sizes)):
+                     ("pair_solve", pair_solve, solve_sizes), ("cells_step", cells_step, sizes), ("cells_solve", cells_solve, solve_sizes),
+                     ("weights_step", weights_step, sizes), ("weights_solve", weights_solve, solve_sizes)):
     if part in parts:
         for nx in ns:
             fn(nx)
