@@ -192,6 +192,9 @@ _sig("cuddh_hip_ddh_plan_set_owner_rule", ci, vp, ci)
 _sig("cuddh_element_lane_tables", ci, ci, vp, vp, vp)
 _sig("cuddh_ddh_resolve", ci, *([ci] * 13), vp)
 _sig("cuddh_ddh_resolve_forcing", ci, *([ci] * 14), vp)
+_sig("cuddh_ddh_resolve_march", ci, *([ci] * 15), vp)
+_sig("cuddh_hip_ddh_plan_set_march", ci, vp, ci)
+_sig("cuddh_hip_ddh_plan_march", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_time_grids", ci, vp, ci, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_time_grids", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_integrator", ci, vp, ci)
@@ -348,6 +351,8 @@ _sig("cuddh_ddh_set_chain_order", ci, vp, ci)
 _sig("cuddh_ddh_chain_order", ci, vp)
 _sig("cuddh_ddh_set_forcing", ci, vp, ci)
 _sig("cuddh_ddh_forcing", ci, vp)
+_sig("cuddh_ddh_set_march", ci, vp, ci)
+_sig("cuddh_ddh_march", ci, vp)
 _sig("cuddh_ddh_set_owner_rule", ci, vp, ci)
 
 

@@ -667,6 +667,19 @@ class DDH:
             N.check_capi(forcing, "DDH.forcing")
         return forcing
 
+    def set_march(self, march: int = 0):
+        """How the march of forcing 2 carries the velocity, for every launch of this plan: 0 auto (2 where form, order and forcing
+        are auto too and auto gave forcing 2, else 1), 1 as it is, 2 scaled, with the midpoint update folded into the sweep (fewer
+        instructions per step; the last bits differ).  2 is refused where forcing 2 is (cuddh_hip_ddh_plan_set_march)."""
+        N.check_capi(lib.cuddh_ddh_set_march(self._h, int(march)), "DDH.set_march")
+
+    def march(self) -> int:
+        """The march in effect: 1 or 2; 0 where forcing 2 is not in effect."""
+        march = lib.cuddh_ddh_march(self._h)
+        if march < 0:
+            N.check_capi(march, "DDH.march")
+        return march
+
     def set_owner_rule(self, last: bool):
         """Kernels 11, 12 and 13: the last copy of every node that elements share publishes instead of the first (a check: same results).
         Refused on any other kernel (cuddh_hip_ddh_plan_set_owner_rule)."""

@@ -144,6 +144,11 @@ namespace cuddh
             /// gave the paired chains.  forcing() returns the forcing in effect, 0 where the paired chains are not.
             void set_forcing(int forcing) const;
             int forcing() const;
+            /// How that march carries the velocity: 0 auto, 1 as it is, 2 scaled by 1 / (2 hm) with its midpoint update folded into the
+            /// sweep (beside forcing 2 only; cuddh_hip_ddh_plan_set_march; a value the plan cannot take throws).  Auto is 2 where form,
+            /// order and forcing are auto too and auto gave forcing 2.  march() returns the march in effect, 0 where forcing 2 is not.
+            void set_march(int march) const;
+            int march() const;
             /// The owner rule of kernels 11, 12 and 13: which copy of a node shared by 2 or 4 elements publishes (false: the first, the default;
             /// true: the last).  A check that the copies are bitwise equal (cuddh_hip_ddh_plan_set_owner_rule); other kernels throw.
             void set_last_copy_publishes(bool last) const;

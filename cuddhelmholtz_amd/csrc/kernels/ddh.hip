@@ -112,6 +112,8 @@ struct cuddh_ddh_plan
     int chain_order = 0; // kernel 5's element-lane form: 0 auto, 1 pinned chains, 2 paired chains (cuddh_hip_ddh_plan_set_chain_order)
     int forcing = 0; // the same form's march: 0 auto, 1 the trace sources in every WaveHoltz pass, 2 in the first only (cuddh_hip_ddh_plan_set_forcing)
     int forcing_now = 0; // the forcing in effect (ddh_forcing), filled by resolve() beside `now`
+    int march = 0; // how that march carries the velocity: 0 auto, 1 as it is, 2 scaled, its midpoint update in the sweep (cuddh_hip_ddh_plan_set_march)
+    int march_now = 0; // the march in effect (ddh_march), filled by resolve() beside `now`
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
     int *csr_off = nullptr, *csr_src = nullptr;
@@ -1772,12 +1774,12 @@ namespace
 
     // the row-per-subdomain element-lane kernel.  NB 4: kernel 5's element-lane form (LAST_COPY: form 3; PAIRED: chain order 2)
     // and kernel 13 at n_basis 4;  NB 5: kernel 12, and 13 at n_basis 5.  Sep4 holds the plan's table at either order
-    template <int NB, bool LAST_COPY, bool PAIRED, bool ONCE, bool GRIDS>
+    template <int NB, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, bool GRIDS>
     void run_element_lane(const cuddh_ddh_plan *p, const DdhArgs<float> &A, int n_local, hipStream_t st)
     {
         with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
                                          { with_flags([&](auto FORCED, auto HOLD)
-                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<NB, FORCED.value, HOLD.value, LAST_COPY, PAIRED, ONCE, decltype(o)...>),
+                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<NB, FORCED.value, HOLD.value, LAST_COPY, PAIRED, ONCE, SCALED, decltype(o)...>),
                                                                            launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
                                                       A.x != nullptr, A.prio != 0); });
     }
@@ -1797,7 +1799,7 @@ namespace
     // fp64 only, no RK4 form of 3, 4, 11 and 13, and 6, 7, 12 and the element-lane form of 5 on one time grid with RK2 alone.
     // ddh_resolve() never resolves to the others; if it did, L.run* would stay null and resolve() would refuse the plan.
     template <typename Real, bool GRIDS, bool RK4>
-    void set_launch(const cuddh_ddh_plan *p, const DdhResolved &r, int forcing, DdhLaunch &L)
+    void set_launch(const cuddh_ddh_plan *p, const DdhResolved &r, int forcing, int march, DdhLaunch &L)
     {
         constexpr bool f32 = sizeof(Real) == 4, plain = !GRIDS && !RK4;
         DdhRun<Real> run = nullptr;
@@ -1835,10 +1837,14 @@ namespace
                 else if constexpr (plain)
                 {
                     L.per_group = 16; // four subdomains per wavefront
-                    // the sources in the first pass only (forcing 2) exist beside the paired chains alone, and ddh_forcing gives 2 there alone
-                    with_flags([&](auto LAST_COPY, auto PAIRED, auto ONCE)
-                               { run = run_element_lane<4, LAST_COPY.value, PAIRED.value, PAIRED.value && ONCE.value, false>; },
-                               r.form == 3, r.order == 2, forcing == 2);
+                    // the sources in the first pass only (forcing 2) exist beside the paired chains alone, and ddh_forcing gives 2 there alone;
+                    // the scaled march (march 2) beside forcing 2 alone, and ddh_march gives 2 there alone
+                    with_flags([&](auto LAST_COPY, auto PAIRED, auto ONCE, auto SCALED)
+                               {
+                                   constexpr bool once = PAIRED.value && ONCE.value;
+                                   run = run_element_lane<4, LAST_COPY.value, PAIRED.value, once, once && SCALED.value, false>;
+                               },
+                               r.form == 3, r.order == 2, forcing == 2, march == 2);
                 }
             }
             break;
@@ -1866,7 +1872,7 @@ namespace
             if constexpr (f32 && plain)
             {
                 L.per_group = 16;
-                with_flags([&](auto LAST_COPY) { run = run_element_lane<5, LAST_COPY.value, false, false, false>; }, last_copy);
+                with_flags([&](auto LAST_COPY) { run = run_element_lane<5, LAST_COPY.value, false, false, false, false>; }, last_copy);
             }
             break;
         case 13: // the element-lane kernels with four subdomains per wavefront, with or without time grids; RK2 only
@@ -1877,9 +1883,9 @@ namespace
                     [&](auto LAST_COPY)
                     {
                         if (p->d.nb == 4)
-                            run = run_element_lane<4, LAST_COPY.value, false, false, GRIDS>;
+                            run = run_element_lane<4, LAST_COPY.value, false, false, false, GRIDS>;
                         else
-                            run = run_element_lane<5, LAST_COPY.value, false, false, GRIDS>;
+                            run = run_element_lane<5, LAST_COPY.value, false, false, false, GRIDS>;
                     },
                     last_copy);
             }
@@ -1902,14 +1908,19 @@ namespace
         if (setting == DDH_SET_FORCING && ddh_forcing_accepted(shape, p->requested, p->facts, p->now.kernel,
                                                                DdhOptions{p->n_grids > 0, p->rk4, p->sweep_form, p->chain_order}, p->forcing))
             return static_cast<int>(hipErrorInvalidValue);
+        if (setting == DDH_SET_MARCH && ddh_march_accepted(shape, p->requested, p->facts, p->now.kernel,
+                                                           DdhOptions{p->n_grids > 0, p->rk4, p->sweep_form, p->chain_order}, p->march))
+            return static_cast<int>(hipErrorInvalidValue);
         const int forcing = ddh_forcing(r, p->sweep_form, p->chain_order, p->forcing);
+        const int march = ddh_march(forcing, p->sweep_form, p->chain_order, p->forcing, p->march);
         DdhLaunch L;
-        with_flags([&](auto F64, auto GRIDS, auto RK4) { set_launch<std::conditional_t<F64.value, double, float>, GRIDS.value, RK4.value>(p, r, forcing, L); },
+        with_flags([&](auto F64, auto GRIDS, auto RK4) { set_launch<std::conditional_t<F64.value, double, float>, GRIDS.value, RK4.value>(p, r, forcing, march, L); },
                    p->is_f64 != 0, p->n_grids > 0, p->rk4 != 0);
         if (!L.run32 && !L.run64) // a missing kernel is an error
             return static_cast<int>(hipErrorInvalidValue);
         p->now = r;
         p->forcing_now = forcing;
+        p->march_now = march;
         p->launch = L;
         return 0;
     }
@@ -2206,6 +2217,15 @@ extern "C"
     }
 
     int cuddh_hip_ddh_plan_forcing(const cuddh_ddh_plan *plan) { return plan ? plan->forcing_now : 0; }
+
+    int cuddh_hip_ddh_plan_set_march(cuddh_ddh_plan *plan, int march)
+    {
+        if (!plan)
+            return static_cast<int>(hipErrorInvalidValue);
+        return set_and_resolve(plan, DDH_SET_MARCH, [&](cuddh_ddh_plan &p) { p.march = march; });
+    }
+
+    int cuddh_hip_ddh_plan_march(const cuddh_ddh_plan *plan) { return plan ? plan->march_now : 0; }
 
     int cuddh_hip_ddh_plan_set_time_grids(cuddh_ddh_plan *plan, int n_grids, const int *h_nt, const double *h_dt, const void *filter,
                                           const void *cs, const void *sn, const int *d_grid_of)

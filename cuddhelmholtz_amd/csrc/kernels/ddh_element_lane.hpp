@@ -43,7 +43,11 @@ namespace
     // TimeGrids instantiations (kernel 13) and a form forced with set_sweep_form keep the pinned chains.  ONCE (forcing 2,
     // cuddh_hip_ddh_plan_set_forcing; what auto runs where it chose the form and the order) applies the trace sources in the
     // first WaveHoltz pass only (wh_march_pairs_once): 206 per wavefront-step in the later passes, both forms, 166 VGPRs, no
-    // scratch, 32 KB of LDS per workgroup between the time loops; another new rounding (profiles/r28).
+    // scratch, 32 KB of LDS per workgroup between the time loops; another new rounding (profiles/r28).  SCALED (march 2,
+    // cuddh_hip_ddh_plan_set_march; what auto runs where it chose form, order and forcing) carries the velocity as q / (2 hm)
+    // and folds its midpoint update into the head of the first sweep's chains, 1 / m of it in each of the m copies of a shared
+    // node (wh_march_pairs_scaled): 226 per wavefront-step in the first pass and 198 in the later ones in the action form (230 to
+    // 234 and 204 with x), 164 to 168 VGPRs, no scratch; one more new rounding (profiles/r31).
     // Every form is compiled for three wavefronts per SIMD with no scratch: 168 VGPRs in the action form, 166 / 167 in
     // the form with x (rhs, postprocess: once per solve).  The assembly is 16 DPP instructions per sweep with no mask
     // multiplications in eta and one mask in xi (element_assemble_*_row_asm below): a shared node's sum is formed by one
@@ -215,6 +219,17 @@ namespace
         const bool first = !(k == 0 && (tid & EX) > 0) && !(l == 0 && (tid & EY) > 0);
         const bool last = !(k == NB - 1 && (tid & EX) < EX) && !(l == NB - 1 && (tid & EY) < EY);
         return LAST_COPY ? last : first;
+    }
+    // 1 / m, m the number of (lane, register) pairs that hold node n of this lane's element inside the subdomain (1, 2 or 4):
+    // from the same (ex, ey, k, l) as the owner rule, so a node has more than one copy exactly where one of them does not own it
+    template <int NB, int NEL>
+    __device__ inline float element_lane_inverse_multiplicity(int n, int tid)
+    {
+        constexpr int EX = NEL - 1, EY = NEL * (NEL - 1);
+        const int k = n % NB, l = n / NB;
+        const bool two_x = (k == 0 && (tid & EX) > 0) || (k == NB - 1 && (tid & EX) < EX);
+        const bool two_y = (l == 0 && (tid & EY) > 0) || (l == NB - 1 && (tid & EY) < EY);
+        return (two_x ? 0.5f : 1.0f) * (two_y ? 0.5f : 1.0f);
     }
 
     // ---- the packed form of the above (ddh_element_lane_kernel only): two nodes per 64-bit register pair, v_pk_fma_f32
@@ -404,6 +419,63 @@ namespace
         else
             pk_fmac_half<1>(t, pair_t{By[la + 12], By[lb + 12]}, w[Q]);
         return t;
+    }
+
+    // The paired chain with a head: t = head + Dg w in one FMA where element_lane_pair_product<K, H, true> opens with the bare
+    // product, every other term at its place in that order.  7 instructions per pair as there; what the head costs is
+    // the caller's (wh_march_pairs_scaled).
+    template <int K, int H>
+    __device__ inline pair_t element_lane_pair_product_headed(const pair_t (&w)[8], const pair_t head, const pair_t (&Bx)[6], const float (&By)[16],
+                                                              const pair_t (&Dg)[8])
+    {
+        constexpr int la = H, lb = 3 - H, P = K + 4 * H, Q = K + 4 * (1 - H);
+        pair_t t = pk_fma(Dg[P], w[P], head);
+        // j = 0
+        if constexpr (K != 0)
+            pk_fmac_scalar<bx_slot(K, 0) % 2>(t, Bx[bx_slot(K, 0) / 2], w[0 + 4 * H]);
+        if constexpr (H == 1)
+            pk_fmac_half<el_half(0)>(t, pair_t{By[la + 0], By[lb + 0]}, w[Q]);
+        // j = 1
+        if constexpr (K != 1)
+            pk_fmac_scalar<bx_slot(K, 1) % 2>(t, Bx[bx_slot(K, 1) / 2], w[1 + 4 * H]);
+        if constexpr (H == 0)
+            pk_fmac_half<el_half(1)>(t, pair_t{By[la + 4], By[lb + 4]}, w[Q]);
+        // j = 2
+        if constexpr (K != 2)
+            pk_fmac_scalar<bx_slot(K, 2) % 2>(t, Bx[bx_slot(K, 2) / 2], w[2 + 4 * H]);
+        if constexpr (H == 0)
+            pk_fmac_half<el_half(2)>(t, pair_t{By[la + 8], By[lb + 8]}, w[Q]);
+        // j = 3
+        if constexpr (K != 3)
+            pk_fmac_scalar<bx_slot(K, 3) % 2>(t, Bx[bx_slot(K, 3) / 2], w[3 + 4 * H]);
+        if constexpr (H == 1)
+            pk_fmac_half<el_half(3)>(t, pair_t{By[la + 12], By[lb + 12]}, w[Q]);
+        // the pair's own halves, crossed
+        pk_fmac_crossed(t, pair_t{By[la + 4 * lb], By[lb + 4 * la]}, w[P]);
+        return t;
+    }
+    // the pairs of HEADS open their chain on head[P], the others run the paired chain as it is
+    template <unsigned HEADS, int K, int H>
+    __device__ inline pair_t element_lane_pair_product_select(const pair_t (&w)[8], const pair_t (&head)[8], const pair_t (&Bx)[6], const float (&By)[16],
+                                                              const pair_t (&Dg)[8])
+    {
+        if constexpr (((HEADS >> (K + 4 * H)) & 1u) != 0)
+            return element_lane_pair_product_headed<K, H>(w, head[K + 4 * H], Bx, By, Dg);
+        else
+            return element_lane_pair_product<K, H, true>(w, Bx, By, Dg);
+    }
+    template <unsigned HEADS>
+    __device__ inline void element_lane_products_headed(const pair_t (&w)[8], const pair_t (&head)[8], pair_t (&z)[8], const pair_t (&Bx)[6],
+                                                        const float (&By)[16], const pair_t (&Dg)[8])
+    {
+        z[0] = element_lane_pair_product_select<HEADS, 0, 0>(w, head, Bx, By, Dg);
+        z[1] = element_lane_pair_product_select<HEADS, 1, 0>(w, head, Bx, By, Dg);
+        z[2] = element_lane_pair_product_select<HEADS, 2, 0>(w, head, Bx, By, Dg);
+        z[3] = element_lane_pair_product_select<HEADS, 3, 0>(w, head, Bx, By, Dg);
+        z[4] = element_lane_pair_product_select<HEADS, 0, 1>(w, head, Bx, By, Dg);
+        z[5] = element_lane_pair_product_select<HEADS, 1, 1>(w, head, Bx, By, Dg);
+        z[6] = element_lane_pair_product_select<HEADS, 2, 1>(w, head, Bx, By, Dg);
+        z[7] = element_lane_pair_product_select<HEADS, 3, 1>(w, head, Bx, By, Dg);
     }
 
     template <bool PAIRED = false>
@@ -605,6 +677,149 @@ namespace
         }
     }
 
+    // wh_march_pairs_once with the velocity carried scaled and its midpoint update folded into the sweep (march 2,
+    // cuddh_hip_ddh_plan_set_march).  With hm = half_dt invm the midpoint velocity of a non-interior node is
+    //     qh = q + hm (z - Hi q),   so   qh / hm = 2 (1 - hm Hi) q / (2 hm) + z.
+    // The state is qs = q / (2 hm).  The chain of the first sweep opens on alpha qs, alpha = 2 (1 - hm Hi), where it opened with
+    // the bare product Dg w: that product becomes an FMA onto the head and the assembled result IS qt = qh / hm; wh_march_pairs'
+    // two instructions dq = -Hi q + z and qh = q + hm dq are gone.  With c = dt hm and b = hm Hi the step is
+    //     qt = assemble(alpha / m qs + chain(p)),   ph = p - c qs,   p -= c qt,
+    //     z  = assemble(-b / m qt + chain(ph)),     qs += z,         u += kw p,   vs += kw qs,
+    // 8 + 2 packed instructions per pair in the first half step where there were 7 + 4, 8 + 3 in the second as before (the
+    // interior pairs, Hi = 0: qs + qs for the first head, no second head).  The assembly sums the chains of all m copies of a
+    // shared node (m = 1, 2 or 4, element_lane_inverse_multiplicity), so what enters a head enters it as 1 / m of its value in
+    // every copy; division by 2 or 4 is exact and the copies hold the same qs, so they stay bitwise equal.  The sources of the
+    // first pass ride on the heads the same way, F / m and Gf / m.
+    // The last addition, qs += z, stays an addition onto the state and is NOT folded into the chain as a third head: a chain
+    // rounds seven times at the magnitude of its accumulator.  qt is only ever multiplied by c or b, both O(dt), so those
+    // roundings do there what the roundings of z do today; qs is the integrated state, and carrying it through a chain would
+    // round it seven times per step at its own magnitude.
+    // qs and vs = sum kw qs are never converted inside the march: the first pass starts from 0, every later pass starts from vs
+    // as it stands, r is parked scaled, and v = vs c (2 / dt) = 2 hm vs once at the end.  No division anywhere, so a node with
+    // invm = 0 (c = 0) ends with v = 0 as it does in wh_march_pairs.  Registers per pair: c, alpha / m, -b / m where
+    // wh_march_pairs_once keeps hm, Hi, dm.
+    template <int LEAN, unsigned INTERIOR, int N, typename SweepHeaded>
+    __device__ inline void wh_march_pairs_scaled(const DdhArgs<float> &A, const int nt, const float dt, const float *__restrict__ filt,
+                                                 const float *__restrict__ cs, const float *__restrict__ sn, const pair_t (&invm)[N],
+                                                 const pair_t (&Hi)[N], const pair_t (&F)[N], const pair_t (&Gf)[N], const pair_t (&rm)[N],
+                                                 pair_t (&u)[N], pair_t (&v)[N], SweepHeaded sweep)
+    {
+        static_assert(LEAN == 1 || LEAN == 2, "the packed loop has wh_march's LEAN forms only");
+        constexpr unsigned ALL = (1u << N) - 1u;
+        __shared__ pair_t parked[2 * N][256];
+        pair_t p[N], q[N], c[N], am[N], bm[N]; // q: qs; am = alpha / m, bm = -b / m
+        const float half_dt = 0.5f * dt;
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+        {
+            const pair_t hm = half_dt * invm[l], b = hm * Hi[l];
+            p[l] = q[l] = u[l] = v[l] = 0;
+            c[l] = dt * hm;
+            am[l] = (2.0f * (1.0f - b)) * rm[l];
+            bm[l] = -b * rm[l];
+        }
+        // one pass from (u, vs), with the sources or without
+        auto pass = [&](auto SOURCES, const pair_t(&Fm)[N], const pair_t(&Gm)[N])
+        {
+            constexpr bool INNER_SOURCES = SOURCES.value && LEAN == 2; // the form with x has sources on the interior pairs too
+            const float k0 = filt[0];
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                p[l] = u[l];
+                q[l] = v[l];
+                u[l] *= k0;
+                v[l] *= k0;
+            }
+            for (int it = 1; it <= nt; ++it)
+            {
+                [[maybe_unused]] float c0, s0, c1, s1;
+                if constexpr (SOURCES.value)
+                {
+                    c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                    c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                }
+                const float kw = filt[it];
+                pair_t z[N], ph[N], qt[N], head[N];
+
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    const bool inner = ((INTERIOR >> l) & 1u) != 0;
+                    head[l] = inner ? q[l] + q[l] : am[l] * q[l];
+                    if (SOURCES.value && (!inner || LEAN == 2))
+                        head[l] = pk_fma(s0, Gm[l], pk_fma(c0, Fm[l], head[l]));
+                }
+                // ph before the sweep, not beside the update of p behind it: with it there the allocator moves two pairs of qt
+                // round the assembly statements, eight v_mov_b32 per step in the loop without sources (profiles/r31)
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                    ph[l] = pk_fma(-c[l], q[l], p[l]);
+                sweep(std::integral_constant<unsigned, ALL>{}, p, head, qt);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                    p[l] = pk_fma(-c[l], qt[l], p[l]);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    const bool inner = ((INTERIOR >> l) & 1u) != 0;
+                    if (!inner)
+                    {
+                        head[l] = bm[l] * qt[l];
+                        if (SOURCES.value)
+                            head[l] = pk_fma(s1, Gm[l], pk_fma(c1, Fm[l], head[l]));
+                    }
+                    else if (INNER_SOURCES)
+                        head[l] = pk_fma(s1, Gm[l], c1 * Fm[l]);
+                }
+                sweep(std::integral_constant<unsigned, INNER_SOURCES ? ALL : (ALL & ~INTERIOR)>{}, ph, head, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    q[l] += z[l]; // onto the state, not through the chain (above)
+                    u[l] = pk_fma(kw, p[l], u[l]);
+                    v[l] = pk_fma(kw, q[l], v[l]);
+                }
+            }
+        };
+        if (A.wh_iters < 1)
+            return;
+        pair_t(*const r)[256] = reinterpret_cast<pair_t(*)[256]>(&parked[0][threadIdx.x]);
+        {
+            pair_t Fm[N], Gm[N];
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                Fm[l] = F[l] * rm[l];
+                Gm[l] = Gf[l] * rm[l];
+            }
+            pass(std::true_type{}, Fm, Gm);
+        }
+        if (A.wh_iters >= 2)
+        {
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                r[l][0] = u[l];
+                r[N + l][0] = v[l];
+            }
+            for (int whit = 1; whit < A.wh_iters; ++whit)
+            {
+                pass(std::false_type{}, F, Gf); // F and Gf are not read
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    u[l] += r[l][0];
+                    v[l] += r[N + l][0];
+                }
+            }
+        }
+        const float two_over_dt = 2.0f / dt;
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+            v[l] *= c[l] * two_over_dt;
+    }
+
     // ---------------------------------------------------------------- kernel 12 (NB = 5, 4x4 elements, rectangles): four subdomains per wavefront
     // ddh_element_lane_kernel's lane map with 25 nodes per lane: lane = element ex + 4 ey, one subdomain per 16-lane DPP row,
     // four subdomains per wavefront, register n = k + 5 l = node (k, l).  The sweep is the one documented there,
@@ -632,11 +847,12 @@ namespace
     // PAIRED: the paired chains in the sweep (element_lane_pair_product), NB = 4 and the one-grid kernel only
     // ONCE: the sources in the first WaveHoltz pass only (wh_march_pairs_once; forcing 2), with PAIRED only.  The only
     //     instantiations that take LDS (32 KB a workgroup, three workgroups per CU: 96 KB of 160)
+    // SCALED: ONCE with the velocity carried scaled and its midpoint update folded into the sweep (wh_march_pairs_scaled; march 2)
     // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
     // Sep: [Bx | By | Dg | W | 1 / W], NB NB floats each (build_element_lane_tables).
     // A stays the FIRST parameter: reread_args reads it at offset 0 of the kernel-argument segment.
     // Wavefronts per SIMD: three at NB = 4; at NB = 5 two, and one in the form with x.
-    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, bool ONCE, typename... Grids>
+    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, typename... Grids>
     __global__ void __launch_bounds__(256, NB == 4 ? 3 : (FORCED ? 1 : 2))
         ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep, const float *__restrict__ filt, const float *__restrict__ cs,
                                 const float *__restrict__ sn, Grids... grids)
@@ -650,6 +866,7 @@ namespace
         static_assert(!(PAIRED && NB != 4), "the paired chains are those of the packed form");
         static_assert(!(PAIRED && sizeof...(Grids) > 0), "the paired chains are built for the one-grid kernel only");
         static_assert(!(ONCE && !PAIRED), "the march with the sources in the first pass only is built beside the paired chains only");
+        static_assert(!(SCALED && !ONCE), "the scaled march is built with the sources in the first pass only");
         const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
         if (s_first >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
@@ -785,7 +1002,30 @@ namespace
                 }
             }
         };
-        if constexpr (NB == 4 && ONCE)
+        if constexpr (NB == 4 && SCALED)
+        {
+            // the chains of the pairs in HEADS open on head[P]; the assembly is sweep's
+            auto sweep_headed = [&](auto HEADS, const pair_t(&w)[8], const pair_t(&head)[8], pair_t(&z)[8])
+            {
+                element_lane_products_headed<HEADS.value>(w, head, z, Bx, By, Dg);
+                float hi[4] = {z[3].x, z[7].x, z[7].y, z[3].y}, lo[4] = {z[0].x, z[4].x, z[4].y, z[0].y}; // l = 0, 1, 2, 3
+                element_assemble_xi_row_asm(hi, lo, mR);
+                z[3].x = hi[0], z[7].x = hi[1], z[7].y = hi[2], z[3].y = hi[3];
+                z[0].x = lo[0], z[4].x = lo[1], z[4].y = lo[2], z[0].y = lo[3];
+                // k = 0, 3, 1, 2: the order of the four independent sums is free, and in this one the first time loop of the
+                // action form keeps two copies fewer (profiles/r31)
+                float up[4] = {z[0].y, z[3].y, z[1].y, z[2].y}, dn[4] = {z[0].x, z[3].x, z[1].x, z[2].x};
+                element_assemble_eta_row_asm(up, dn);
+                z[0].y = up[0], z[3].y = up[1], z[1].y = up[2], z[2].y = up[3];
+                z[0].x = dn[0], z[3].x = dn[1], z[1].x = dn[2], z[2].x = dn[3];
+            };
+            pair_t rm[8];
+#pragma unroll
+            for (int n = 0; n < 16; ++n)
+                rm[el_pair(n & 3, n >> 2)][el_half(n >> 2)] = element_lane_inverse_multiplicity<4, 4>(n, threadIdx.x);
+            wh_march_pairs_scaled<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, rm, u, v, sweep_headed);
+        }
+        else if constexpr (NB == 4 && ONCE)
             wh_march_pairs_once<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, ELEMENT_LANE_ONCE_FIRST_DM_PAIRS(FORCED), ELEMENT_LANE_ONCE_DM_PAIRS>(
                 Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, u, v, sweep);
         else if constexpr (NB == 4)

@@ -41,7 +41,8 @@ namespace cuddh_k
         DDH_SET_SWEEP_FORM = 1,
         DDH_SET_CHAIN_ORDER = 2,
         DDH_SET_OWNER_RULE = 3,
-        DDH_SET_FORCING = 4 // not ddh_resolve's to judge: ddh_forcing_accepted
+        DDH_SET_FORCING = 4, // not ddh_resolve's to judge: ddh_forcing_accepted
+        DDH_SET_MARCH = 5    // nor this: ddh_march_accepted
     };
 
     struct DdhResolved
@@ -75,4 +76,13 @@ namespace cuddh_k
     // are ddh_resolve's): accepted and idle on the matrix form of a plan that has the element-lane form, refused elsewhere.
     // Returns 0, or 1 (hipErrorInvalidValue): refused.
     int ddh_forcing_accepted(const DdhShape &shape, int request, unsigned facts, int current, const DdhOptions &options, int forcing);
+
+    // How that march carries the velocity (cuddh_hip_ddh_plan_set_march): 1 as wh_march_pairs_once does, 2 scaled by 1 / (2 hm)
+    // with its midpoint update folded into the sweep (wh_march_pairs_scaled; one more new rounding), 0: the
+    // forcing in effect is not 2, the only one the scaled march is built for.  `forcing_now`: what ddh_forcing gave; the other
+    // four as stored (0 auto).  Auto takes 2 only where form, order and forcing are all auto: a forced one keeps its bits.
+    int ddh_march(int forcing_now, int sweep_form, int chain_order, int forcing, int march);
+
+    // May a plan store this march?  0 to 2, and 2 exactly where it may store forcing 2.  Returns 0, or 1: refused.
+    int ddh_march_accepted(const DdhShape &shape, int request, unsigned facts, int current, const DdhOptions &options, int march);
 } // namespace cuddh_k

@@ -1216,6 +1216,27 @@ extern "C"
         });
         return err ? -1 : forcing;
     }
+    int cuddh_ddh_set_march(void *d, int march)
+    {
+        return guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            if (h->is64())
+                h->f64->internals().set_march(march);
+            else
+                h->f32->internals().set_march(march);
+        });
+    }
+    int cuddh_ddh_march(void *d)
+    {
+        int march = 0;
+        const int err = guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            march = h->is64() ? h->f64->internals().march() : h->f32->internals().march();
+        });
+        return err ? -1 : march;
+    }
     int cuddh_ddh_set_owner_rule(void *d, int last)
     {
         return guarded([&]

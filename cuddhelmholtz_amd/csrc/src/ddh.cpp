@@ -738,6 +738,20 @@ namespace cuddh
         }
 
         template <typename Real>
+        void DDHCore<Real>::set_march(int march) const
+        {
+            ensure_plan();
+            check_hip(cuddh_hip_ddh_plan_set_march(plan, march), "DDH march");
+        }
+
+        template <typename Real>
+        int DDHCore<Real>::march() const
+        {
+            ensure_plan();
+            return cuddh_hip_ddh_plan_march(plan);
+        }
+
+        template <typename Real>
         void DDHCore<Real>::set_last_copy_publishes(bool last) const
         {
             ensure_plan();

@@ -204,6 +204,22 @@ namespace cuddh_k
         DdhResolved unused;
         return ddh_resolve(s, request, facts, current, DdhOptions{o.time_grids, o.rk4, o.sweep_form, 2}, DDH_SET_CHAIN_ORDER, unused);
     }
+
+    int ddh_march(int forcing_now, int sweep_form, int chain_order, int forcing, int march)
+    {
+        if (forcing_now != 2)
+            return 0;
+        if (march == 2)
+            return 2;
+        return march == 0 && sweep_form == 0 && chain_order == 0 && forcing == 0 ? 2 : 1;
+    }
+
+    int ddh_march_accepted(const DdhShape &s, int request, unsigned facts, int current, const DdhOptions &o, int march)
+    {
+        if (march < 0 || march > 2)
+            return REFUSED;
+        return march != 2 ? 0 : ddh_forcing_accepted(s, request, facts, current, o, 2);
+    }
 } // namespace cuddh_k
 
 extern "C"
@@ -240,6 +256,24 @@ extern "C"
         out[1] = err ? 0 : r.form;
         out[2] = err ? 0 : r.order;
         out[3] = err ? 0 : ddh_forcing(r, sweep_form, chain_order, forcing);
+        return err;
+    }
+
+    int cuddh_ddh_resolve_march(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids, int rk4,
+                                int sweep_form, int chain_order, int forcing, int march, int setting, int *out)
+    {
+        using namespace cuddh_k;
+        if (!out)
+            return 1; // hipErrorInvalidValue
+        const DdhShape s{nb, nel1d, n_domains, is_f64 ? 1 : 0, mx_elems};
+        const DdhOptions o{time_grids, rk4, sweep_form, chain_order};
+        int err = cuddh_ddh_resolve_forcing(nb, nel1d, n_domains, is_f64, mx_elems, request, facts, current, time_grids, rk4, sweep_form, chain_order, forcing,
+                                            setting == DDH_SET_MARCH ? DDH_SET_NONE : setting, out);
+        if (!err && (march < 0 || march > 2 || (setting == DDH_SET_MARCH && ddh_march_accepted(s, request, static_cast<unsigned>(facts), current, o, march))))
+            err = 1;
+        if (err)
+            out[0] = out[1] = out[2] = out[3] = 0;
+        out[4] = err ? 0 : ddh_march(out[3], sweep_form, chain_order, forcing, march);
         return err;
     }
 }

@@ -461,6 +461,18 @@ int cuddh_hip_ddh_plan_chain_order(const cuddh_ddh_plan *plan);
  * cuddh_hip_ddh_plan_forcing returns the forcing in effect (1 or 2), 0 where the chain order in effect is not 2. */
 int cuddh_hip_ddh_plan_set_forcing(cuddh_ddh_plan *plan, int forcing);
 int cuddh_hip_ddh_plan_forcing(const cuddh_ddh_plan *plan);
+/* How the march with the sources in the first pass only (forcing 2) carries the velocity q, for every launch of the plan:
+ *   1 = as it is: q, with dq = -Hi q + z and qh = q + hm dq formed behind the first sweep of a step (hm = half_dt invm);
+ *   2 = scaled: the state is q / (2 hm), the chain of the first sweep opens on 2 (1 - hm Hi) q / (2 hm) / m instead of a bare
+ *       product and its assembled result is qh / hm (m: the copies of a shared node inside the subdomain, whose chains the
+ *       assembly sums); 6 packed instructions per wavefront-step fewer in every pass.  The same scheme, rounded at other
+ *       places: results differ from 1 in the last bits, with one WaveHoltz iteration too;
+ *   0 = auto (the default): 2 where sweep form, chain order and forcing are all auto and auto gave forcing 2, else 1.
+ * 2 is refused with hipErrorInvalidValue, the plan unchanged, exactly where forcing 2 is refused; where it is accepted and the
+ * forcing in effect is not 2 it waits.  Other values than 0, 1, 2 are invalid.  cuddh_hip_ddh_plan_march returns the march in
+ * effect (1 or 2), 0 where the forcing in effect is not 2. */
+int cuddh_hip_ddh_plan_set_march(cuddh_ddh_plan *plan, int march);
+int cuddh_hip_ddh_plan_march(const cuddh_ddh_plan *plan);
 /* The owner rule of kernels 11, 12 and 13, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
  * smallest element-node index publishes (last == 0, the default) or the one with the largest (last != 0).  The copies are
  * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with
@@ -500,6 +512,11 @@ int cuddh_ddh_resolve(int nb, int nel1d, int n_domains, int is_f64, int mx_elems
  * and out[3] the forcing in effect (0 to 2).  Returns 0, or 1 where the plan or the setter call is refused (out[0..3] are then 0). */
 int cuddh_ddh_resolve_forcing(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids,
                               int rk4, int sweep_form, int chain_order, int forcing, int setting, int *out);
+/* The same with the march a plan holds as well (cuddh_hip_ddh_plan_set_march; 0 auto) and setting 5, the march: out[0..3] as
+ * above and out[4] the march in effect (0 to 2).  Returns 0, or 1 where the plan or the setter call is refused (out[0..4] are
+ * then 0). */
+int cuddh_ddh_resolve_march(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids,
+                            int rk4, int sweep_form, int chain_order, int forcing, int march, int setting, int *out);
 /* Per-subdomain time grids.  The descriptor holds ONE grid (nt, dt, wh_filter, cs, sn), taken from the mesh alone; the wave
  * speed 1 / a never enters it, and where a < 1 the explicit time stepping runs past its usable range.  Local
  * solves couple through the traces only, so every subdomain may march its WaveHoltz period on a grid of its own: after this

@@ -40,15 +40,19 @@ RENAMED = {"ddh.hip": {"ddh_mfma_kernel<float>": "ddh_mfma_kernel<float, false, 
 _STAGE_RULES = ((r"\b(?:cuddh_k::wave::)?(Begin|Rk2A|Rk2B|Rk4First|Rk4Mid|Rk4Last)\b(?!T)", r"cuddh_k::wave::\1T<double>"),)
 # ddh_element_lane_kernel got ONCE as its sixth template argument, before the grids (false is the march it had)
 _ONCE_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
-RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES, "ddh.hip": _ONCE_RULE}
+# and SCALED as its seventh (false is the march it had); applied after _ONCE_RULE, so a name from before either gets both
+_SCALED_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
+RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES, "ddh.hip": _ONCE_RULE + _SCALED_RULE}
 # instantiations that are another one plus (or with another) template argument, per file: (pattern, replacement) pairs applied to the
 # demangled name give the base.
 # A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
 DERIVED = {"ddh.hip": ((r", Rk4Scheme ?(?=>)|, TimeGrids<\w+> ?(?=>)", ""),
                        # the paired chains (PAIRED = true, one grid only) against the pinned ones
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true, false>", r"\1, false, false>"),
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true, false, false>", r"\1, false, false, false>"),
                        # the sources in the first pass only (ONCE = true, beside the paired chains only) against every pass
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true), true>", r"\1, false>"))}
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true), true, false>", r"\1, false, false>"),
+                       # the scaled march (SCALED = true, beside ONCE only) against the march it is derived from
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true), true>", r"\1, false>"))}
 INNER = {}  # (assembly file, kernel) -> its innermost loops
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
