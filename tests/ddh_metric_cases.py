@@ -11,6 +11,11 @@ Four mesh families, all with the vertex and element numbering of uniform_rect(nx
               x' = x + 0.08 sin(pi x) cos(pi y / 2) + 0.06 (1 - x^2) y,   y' = y + 0.07 sin(pi y) sin(pi x / 2 + 0.3):
           every element its own metric, g01 varying in sign and size; the boundary vertices in y stay on y = +-1.
 
+A fifth, `tall`, is uniform_rect(nx, -1, 1, ny, -ny hx, ny hx) with hy = 2 hx: g00 = 2, g11 = 1/2, g01 == 0, the anisotropy of
+`rect` the other way round (g00 > g11 where rect has g00 < g11).  It is no member of FAMILIES: it exists as case("tall", 4, 4) for
+the element-lane kernels (tests/test_gpu_ddh_element_lane_rectangles.py), whose x and y tables are bit for bit the same on
+squares.  swapped_rect is that mesh with the rect case's coefficient, sources and traces by index.
+
 Shapes (SHAPES): the smallest with a cross point, a subdomain with three neighbours and a subdomain count (6) that is no
 multiple of 4; plus 16 x 8 at block 8 (two subdomains) for kernel 11.
 
@@ -58,6 +63,8 @@ def vertices(family, nx, ny, shear=SHEAR):
         y0 = -ny * hx / 2
     elif family in ("rect", "shear"):
         y0 = -ny * hx / 4
+    elif family == "tall":
+        y0 = -ny * hx
     elif family == "skew":
         y0 = -1.0
     else:
@@ -135,6 +142,12 @@ def case(family, nb, block):
 def opposite_shear(nb, block):
     """the shear case's mesh sheared the other way, with the shear case's coefficient, sources and traces by index"""
     return Case("shear", nb, block, shear=-SHEAR, like=case("shear", nb, block))
+
+
+@functools.lru_cache(maxsize=None)
+def swapped_rect(nb, block):
+    """the rect case's coefficient, sources and traces by index on the mesh whose hx : hy is the inverse (hy = 2 hx, not hx / 2)"""
+    return Case("tall", nb, block, like=case("rect", nb, block))
 
 
 def cells(nb, block):

@@ -14,7 +14,12 @@ hold before a comparison of a device kernel with them (tests/test_gpu_ddh_metric
     l2 and up to 3.2e-6 in max norm;
   * a metric fault cannot hide under the fp32 gate: shearing the mesh the other way, with the same coefficient, source and
     trace vectors by index, moves the fp64 outputs by 6.6e-2 .. 7.4e-1, at least 4.8e4 gates (100 is asserted);
-  * a case builds in a few seconds (0.3 .. 3 s measured).
+  * a case builds in a few seconds (0.3 .. 3 s measured);
+  * `tall` (hy = 2 hx, n_basis 4 only, for the element-lane kernels) meets the same conditions: valid elements, the product's
+    numbering, one edge-vector pair, the two restatements, the floors; its g01 is 0 and its g00 / g11 is 4 in every node bit for
+    bit where rect's is 1 / 4.  The rect inputs by index on it (swapped_rect) move the fp64 outputs by 9.8e-1 / 5.3e-1 / 1.2
+    (rhs / action / postprocess), at least 3.5e5 fp32 gates of the rect case (1e4 is asserted): exchanging the x and the y
+    tables of a kernel, an identity on squares, cannot hide under the gate on either.
 Every figure is printed (`pytest -s`).
 """
 import time
@@ -28,6 +33,7 @@ from oracle.numbering import ddh_tables
 
 SHAPE_PARAMS = [pytest.param(nb, block, id=f"nb{nb}-block{block}") for nb, block in mc.SHAPES]
 CELLS = [pytest.param(f, nb, block, id=f"{f}-nb{nb}-block{block}") for nb, block in mc.SHAPES for f in mc.cells(nb, block)]
+TALL = pytest.param("tall", 4, 4, id="tall-nb4-block4")  # no member of mc.FAMILIES: one shape, for the element-lane kernels
 # a case is built once per session and shared with the device tests; a bound on the build keeps it that cheap.  Measured 0.3 s
 # (n_basis 4) to 3 s (n_basis 8, 16 x 8 at block 8); the bound leaves a factor of ten for a slower or busier machine.
 BUILD_SECONDS = 30.0
@@ -35,7 +41,7 @@ INT_TABLES = ("B", "gI", "sI", "s_dof", "s_fdof", "s_elems", "elems")
 REAL_TABLES = ("D", "m", "gmi", "a", "H", "wh_filter", "cs", "sn")
 
 
-@pytest.mark.parametrize("family,nb,block", CELLS)
+@pytest.mark.parametrize("family,nb,block", CELLS + [TALL])
 def test_case_builds_quickly_and_its_elements_are_valid(family, nb, block):
     # the cache is shared with every other test: the first build is timed, a cached one costs nothing
     t0 = time.perf_counter()
@@ -93,7 +99,7 @@ def test_element_angles_and_uniformity(nb, block):
             assert cs.max() >= 0.15 and cs.min() <= -0.05  # far from a rectangle, with g01 of both signs
 
 
-@pytest.mark.parametrize("family,nb,block", [p for p in CELLS if p.values[2] == 16 // p.values[1]])
+@pytest.mark.parametrize("family,nb,block", [p for p in CELLS if p.values[2] == 16 // p.values[1]] + [TALL])
 def test_block_oracle_and_label_oracle_agree(family, nb, block):
     c = mc.case(family, nb, block)
     d = c.d
@@ -112,14 +118,14 @@ def test_block_oracle_and_label_oracle_agree(family, nb, block):
             assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), k
         B = oracle.DDH(d, c.nx, c.ny, c.omega, c.h_a, real)
         assert B.G.tobytes() == O.G.tobytes()
-        assert np.abs(O.G[1]).max() > 0.1 * np.abs(O.G[0]).max() or family in ("square", "rect")  # g01 is there
+        assert np.abs(O.G[1]).max() > 0.1 * np.abs(O.G[0]).max() or family in ("square", "rect", "tall")  # g01 is there
         e = [mc.rel(a, r) for a, r in zip((B.rhs(c.fh), B.action(c.lam)[c.written], B.postprocess(c.lam, c.fh)), outs)]
         print(f"[{c.name}] oracle.DDH vs OracleDDH on block labels, {np.dtype(real).name}: tables bitwise equal; " +
               ", ".join(f"{n} {v:.1e}" for n, v in zip(mc.NAMES, e)))
         assert max(e) <= 1e-12, e
 
 
-@pytest.mark.parametrize("family,nb,block", CELLS)
+@pytest.mark.parametrize("family,nb,block", CELLS + [TALL])
 def test_floors(family, nb, block):
     c = mc.case(family, nb, block)
     print(f"[{c.name}] fp32 oracle vs fp64 oracle (relative l2 / max norm): " + ", ".join(f"{n} {l2:.2e} / {mx:.2e}" for n, (l2, mx) in zip(mc.NAMES, c.floor)))
@@ -138,3 +144,51 @@ def test_opposite_shear_moves_every_output_far_beyond_the_fp32_gate(nb, block):
         e, gate = mc.rel(a, b), mc.FLOOR_FACTOR * l2
         print(f"[{s.name}] {n}: g01 -> -g01 moves the fp64 reference by {e:.3e} = {e / gate:.0f} x the fp32 gate ({gate:.2e})")
         assert e >= 100 * gate, (n, e, gate)
+
+
+def test_tall_is_the_rect_mesh_with_the_two_directions_exchanged():
+    import cuddhelmholtz_amd as cd
+
+    nb, block = 4, 4
+    nx, ny = mc.SHAPES[(nb, block)]
+    hx = 2.0 / nx
+    xy, elems = mc.vertices("tall", nx, ny)
+    base = cd.Mesh2D.uniform_rect(nx, -1.0, 1.0, ny, -ny * hx, ny * hx)
+    assert np.array_equal(base.elements(), elems) and np.array_equal(base.vertices(), xy)
+    mesh = cd.Mesh2D.from_vertices(xy, elems)
+    assert np.array_equal(mesh.vertices(), xy) and np.array_equal(mesh.elements(), elems)
+    # exact coordinates: every vertex is a multiple of hx = 1/4, so every element has bit for bit the edges (hx, 0) and (0, 2 hx)
+    assert np.array_equal(xy, np.round(xy / hx) * hx)
+    for family, ratio in (("rect", 0.5), ("tall", 2.0)):
+        v, e = mc.vertices(family, nx, ny)
+        c = v[e]
+        assert np.array_equal(e, elems) and not mc.centre_cosines(v, e).any()
+        for a, b, want in ((1, 0, (hx, 0.0)), (2, 3, (hx, 0.0)), (3, 0, (0.0, ratio * hx)), (2, 1, (0.0, ratio * hx))):
+            assert np.array_equal(c[:, a] - c[:, b], np.broadcast_to(want, (nx * ny, 2))), (family, a, b)
+    # the metric the oracle marches with: G = (g00, g01, g11) per element node, node weight included
+    for family, ratio in (("rect", 0.25), ("tall", 4.0)):
+        k = mc.case(family, nb, block)
+        for O in (k.O64, k.O32):
+            g00, g01, g11 = O.G
+            print(f"[{k.name}, {O.G.dtype.name}] g01 in [{g01.min():.1e}, {g01.max():.1e}]; g00 / g11 in [{(g00 / g11).min():.4f}, {(g00 / g11).max():.4f}]")
+            assert g11.min() > 0 and not g01.any()
+            assert np.array_equal(g00, O.G.dtype.type(ratio) * g11)  # a power of two: exact in both precisions
+    r, t = mc.case("rect", nb, block), mc.case("tall", nb, block)
+    assert np.array_equal(t.labels, r.labels) and np.array_equal(t.O64.t.B, r.O64.t.B) and np.array_equal(t.written, r.written)
+    print(f"nt: rect {r.O64.t.nt}, tall {t.O64.t.nt}")
+    assert r.O64.t.nt > t.O64.t.nt > 0
+
+
+def test_exchanging_hx_and_hy_moves_every_output_far_beyond_the_fp32_gate():
+    nb, block = 4, 4
+    r, s = mc.case("rect", nb, block), mc.swapped_rect(nb, block)
+    assert s is mc.swapped_rect(nb, block) and s.family == "tall"
+    assert s.h_a is r.h_a and s.fh is r.fh and s.lam is r.lam and np.array_equal(s.written, r.written)
+    assert np.array_equal(s.xy, mc.vertices("tall", r.nx, r.ny)[0]) and np.array_equal(s.elems, r.elems)
+    assert np.array_equal(s.O64.G[0], 4 * s.O64.G[2]) and np.array_equal(4 * r.O64.G[0], r.O64.G[2])
+    for n, fl in zip(mc.NAMES, s.floor):  # its own floors: the gate of the device's distance to its own reference
+        assert all(np.isfinite(v) and 0 < v < 5e-6 for v in fl), (n, fl)
+    for n, a, b, (l2, _) in zip(mc.NAMES, s.ref, r.ref, r.floor):
+        e, gate = mc.rel(a, b), mc.FLOOR_FACTOR * l2
+        print(f"[{r.name}] {n}: hy = hx / 2 -> hy = 2 hx moves the fp64 reference by {e:.3e} = {e / gate:.0f} x the fp32 gate ({gate:.2e})")
+        assert e >= 1e4 * gate, (n, e, gate)
