@@ -195,6 +195,9 @@ _sig("cuddh_ddh_resolve_forcing", ci, *([ci] * 14), vp)
 _sig("cuddh_ddh_resolve_march", ci, *([ci] * 15), vp)
 _sig("cuddh_hip_ddh_plan_set_march", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_march", ci, vp)
+_sig("cuddh_ddh_resolve_head", ci, *([ci] * 16), vp)
+_sig("cuddh_hip_ddh_plan_set_head", ci, vp, ci)
+_sig("cuddh_hip_ddh_plan_head", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_time_grids", ci, vp, ci, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_time_grids", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_integrator", ci, vp, ci)
@@ -353,6 +356,8 @@ _sig("cuddh_ddh_set_forcing", ci, vp, ci)
 _sig("cuddh_ddh_forcing", ci, vp)
 _sig("cuddh_ddh_set_march", ci, vp, ci)
 _sig("cuddh_ddh_march", ci, vp)
+_sig("cuddh_ddh_set_head", ci, vp, ci)
+_sig("cuddh_ddh_head", ci, vp)
 _sig("cuddh_ddh_set_owner_rule", ci, vp, ci)
 
 

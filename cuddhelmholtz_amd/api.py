@@ -680,6 +680,19 @@ class DDH:
             N.check_capi(march, "DDH.march")
         return march
 
+    def set_head(self, head: int = 0):
+        """What march 2 carries as the velocity, for every launch of this plan: 0 auto (2 wherever march 2 is in effect), 1
+        q / (2 hm), 2 that times the head coefficient of the first sweep's chain, so that the chain opens on the state (one
+        instruction per pair and step less; the last bits differ).  2 is refused where march 2 is (cuddh_hip_ddh_plan_set_head)."""
+        N.check_capi(lib.cuddh_ddh_set_head(self._h, int(head)), "DDH.set_head")
+
+    def head(self) -> int:
+        """The head in effect: 1 or 2; 0 where march 2 is not in effect."""
+        head = lib.cuddh_ddh_head(self._h)
+        if head < 0:
+            N.check_capi(head, "DDH.head")
+        return head
+
     def set_owner_rule(self, last: bool):
         """Kernels 11, 12 and 13: the last copy of every node that elements share publishes instead of the first (a check: same results).
         Refused on any other kernel (cuddh_hip_ddh_plan_set_owner_rule)."""

@@ -149,6 +149,11 @@ namespace cuddh
             /// order and forcing are auto too and auto gave forcing 2.  march() returns the march in effect, 0 where forcing 2 is not.
             void set_march(int march) const;
             int march() const;
+            /// What march 2 carries as the velocity: 0 auto, 1 q / (2 hm), 2 that times the head coefficient of the first sweep's chain,
+            /// so that the chain opens on the state (cuddh_hip_ddh_plan_set_head; a value the plan cannot take throws).  Auto is 2
+            /// wherever the march in effect is 2.  head() returns the head in effect, 0 where march 2 is not.
+            void set_head(int head) const;
+            int head() const;
             /// The owner rule of kernels 11, 12 and 13: which copy of a node shared by 2 or 4 elements publishes (false: the first, the default;
             /// true: the last).  A check that the copies are bitwise equal (cuddh_hip_ddh_plan_set_owner_rule); other kernels throw.
             void set_last_copy_publishes(bool last) const;

@@ -114,6 +114,8 @@ struct cuddh_ddh_plan
     int forcing_now = 0; // the forcing in effect (ddh_forcing), filled by resolve() beside `now`
     int march = 0; // how that march carries the velocity: 0 auto, 1 as it is, 2 scaled, its midpoint update in the sweep (cuddh_hip_ddh_plan_set_march)
     int march_now = 0; // the march in effect (ddh_march), filled by resolve() beside `now`
+    int head = 0; // what march 2 carries as the velocity: 0 auto, 1 q / (2 hm), 2 that times the first chain's head coefficient (cuddh_hip_ddh_plan_set_head)
+    int head_now = 0; // the head in effect (ddh_head), filled by resolve() beside `now`
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
     int *csr_off = nullptr, *csr_src = nullptr;
@@ -1774,12 +1776,12 @@ namespace
 
     // the row-per-subdomain element-lane kernel.  NB 4: kernel 5's element-lane form (LAST_COPY: form 3; PAIRED: chain order 2)
     // and kernel 13 at n_basis 4;  NB 5: kernel 12, and 13 at n_basis 5.  Sep4 holds the plan's table at either order
-    template <int NB, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, bool GRIDS>
+    template <int NB, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, bool CARRIED, bool GRIDS>
     void run_element_lane(const cuddh_ddh_plan *p, const DdhArgs<float> &A, int n_local, hipStream_t st)
     {
         with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
                                          { with_flags([&](auto FORCED, auto HOLD)
-                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<NB, FORCED.value, HOLD.value, LAST_COPY, PAIRED, ONCE, SCALED, decltype(o)...>),
+                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<NB, FORCED.value, HOLD.value, LAST_COPY, PAIRED, ONCE, SCALED, CARRIED, decltype(o)...>),
                                                                            launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
                                                       A.x != nullptr, A.prio != 0); });
     }
@@ -1799,7 +1801,7 @@ namespace
     // fp64 only, no RK4 form of 3, 4, 11 and 13, and 6, 7, 12 and the element-lane form of 5 on one time grid with RK2 alone.
     // ddh_resolve() never resolves to the others; if it did, L.run* would stay null and resolve() would refuse the plan.
     template <typename Real, bool GRIDS, bool RK4>
-    void set_launch(const cuddh_ddh_plan *p, const DdhResolved &r, int forcing, int march, DdhLaunch &L)
+    void set_launch(const cuddh_ddh_plan *p, const DdhResolved &r, int forcing, int march, int head, DdhLaunch &L)
     {
         constexpr bool f32 = sizeof(Real) == 4, plain = !GRIDS && !RK4;
         DdhRun<Real> run = nullptr;
@@ -1838,13 +1840,14 @@ namespace
                 {
                     L.per_group = 16; // four subdomains per wavefront
                     // the sources in the first pass only (forcing 2) exist beside the paired chains alone, and ddh_forcing gives 2 there alone;
-                    // the scaled march (march 2) beside forcing 2 alone, and ddh_march gives 2 there alone
-                    with_flags([&](auto LAST_COPY, auto PAIRED, auto ONCE, auto SCALED)
+                    // the scaled march (march 2) beside forcing 2 alone, and ddh_march gives 2 there alone; the carried head (head 2)
+                    // beside march 2 alone, and ddh_head gives 2 there alone
+                    with_flags([&](auto LAST_COPY, auto PAIRED, auto ONCE, auto SCALED, auto CARRIED)
                                {
-                                   constexpr bool once = PAIRED.value && ONCE.value;
-                                   run = run_element_lane<4, LAST_COPY.value, PAIRED.value, once, once && SCALED.value, false>;
+                                   constexpr bool once = PAIRED.value && ONCE.value, scaled = once && SCALED.value;
+                                   run = run_element_lane<4, LAST_COPY.value, PAIRED.value, once, scaled, scaled && CARRIED.value, false>;
                                },
-                               r.form == 3, r.order == 2, forcing == 2, march == 2);
+                               r.form == 3, r.order == 2, forcing == 2, march == 2, head == 2);
                 }
             }
             break;
@@ -1872,7 +1875,7 @@ namespace
             if constexpr (f32 && plain)
             {
                 L.per_group = 16;
-                with_flags([&](auto LAST_COPY) { run = run_element_lane<5, LAST_COPY.value, false, false, false, false>; }, last_copy);
+                with_flags([&](auto LAST_COPY) { run = run_element_lane<5, LAST_COPY.value, false, false, false, false, false>; }, last_copy);
             }
             break;
         case 13: // the element-lane kernels with four subdomains per wavefront, with or without time grids; RK2 only
@@ -1883,9 +1886,9 @@ namespace
                     [&](auto LAST_COPY)
                     {
                         if (p->d.nb == 4)
-                            run = run_element_lane<4, LAST_COPY.value, false, false, false, GRIDS>;
+                            run = run_element_lane<4, LAST_COPY.value, false, false, false, false, GRIDS>;
                         else
-                            run = run_element_lane<5, LAST_COPY.value, false, false, false, GRIDS>;
+                            run = run_element_lane<5, LAST_COPY.value, false, false, false, false, GRIDS>;
                     },
                     last_copy);
             }
@@ -1911,16 +1914,21 @@ namespace
         if (setting == DDH_SET_MARCH && ddh_march_accepted(shape, p->requested, p->facts, p->now.kernel,
                                                            DdhOptions{p->n_grids > 0, p->rk4, p->sweep_form, p->chain_order}, p->march))
             return static_cast<int>(hipErrorInvalidValue);
+        if (setting == DDH_SET_HEAD && ddh_head_accepted(shape, p->requested, p->facts, p->now.kernel,
+                                                         DdhOptions{p->n_grids > 0, p->rk4, p->sweep_form, p->chain_order}, p->head))
+            return static_cast<int>(hipErrorInvalidValue);
         const int forcing = ddh_forcing(r, p->sweep_form, p->chain_order, p->forcing);
         const int march = ddh_march(forcing, p->sweep_form, p->chain_order, p->forcing, p->march);
+        const int head = ddh_head(march, p->head);
         DdhLaunch L;
-        with_flags([&](auto F64, auto GRIDS, auto RK4) { set_launch<std::conditional_t<F64.value, double, float>, GRIDS.value, RK4.value>(p, r, forcing, march, L); },
+        with_flags([&](auto F64, auto GRIDS, auto RK4) { set_launch<std::conditional_t<F64.value, double, float>, GRIDS.value, RK4.value>(p, r, forcing, march, head, L); },
                    p->is_f64 != 0, p->n_grids > 0, p->rk4 != 0);
         if (!L.run32 && !L.run64) // a missing kernel is an error
             return static_cast<int>(hipErrorInvalidValue);
         p->now = r;
         p->forcing_now = forcing;
         p->march_now = march;
+        p->head_now = head;
         p->launch = L;
         return 0;
     }
@@ -2226,6 +2234,15 @@ extern "C"
     }
 
     int cuddh_hip_ddh_plan_march(const cuddh_ddh_plan *plan) { return plan ? plan->march_now : 0; }
+
+    int cuddh_hip_ddh_plan_set_head(cuddh_ddh_plan *plan, int head)
+    {
+        if (!plan)
+            return static_cast<int>(hipErrorInvalidValue);
+        return set_and_resolve(plan, DDH_SET_HEAD, [&](cuddh_ddh_plan &p) { p.head = head; });
+    }
+
+    int cuddh_hip_ddh_plan_head(const cuddh_ddh_plan *plan) { return plan ? plan->head_now : 0; }
 
     int cuddh_hip_ddh_plan_set_time_grids(cuddh_ddh_plan *plan, int n_grids, const int *h_nt, const double *h_dt, const void *filter,
                                           const void *cs, const void *sn, const int *d_grid_of)

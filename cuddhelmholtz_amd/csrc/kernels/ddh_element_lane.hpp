@@ -48,6 +48,11 @@ namespace
     // and folds its midpoint update into the head of the first sweep's chains, 1 / m of it in each of the m copies of a shared
     // node (wh_march_pairs_scaled): 226 per wavefront-step in the first pass and 198 in the later ones in the action form (230 to
     // 234 and 204 with x), 164 to 168 VGPRs, no scratch; one more new rounding (profiles/r31).
+    // CARRIED (head 2, cuddh_hip_ddh_plan_set_head; what auto runs wherever march 2 is in effect) carries that velocity already
+    // multiplied by the head coefficient of the first sweep's chain, so the chain opens on the state (wh_march_pairs_carried):
+    // 214 and 190 in the action form (230 and 194 to 198 with x), 167 VGPRs, no scratch, 44 KB of LDS per workgroup, of which
+    // 12 KB hold a per-dof coefficient that is read once per step, the only LDS access in a time loop of the family; one more
+    // new rounding (profiles/r32).
     // Every form is compiled for three wavefronts per SIMD with no scratch: 168 VGPRs in the action form, 166 / 167 in
     // the form with x (rhs, postprocess: once per solve).  The assembly is 16 DPP instructions per sweep with no mask
     // multiplications in eta and one mask in xi (element_assemble_*_row_asm below): a shared node's sum is formed by one
@@ -251,6 +256,7 @@ namespace
     // own each would take a pair); 106 are in use and none is spilled inside the time loop (a dozen wait in the lanes of
     // one vector register across it and come back once per WaveHoltz iteration).
     typedef float pair_t __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) pair_t lds_pair_t; // a pair in LDS, named as such: ds_* with a 32-bit address
     constexpr int el_pair(int k, int l) { return k + 4 * ((l == 1 || l == 2) ? 1 : 0); }
     constexpr int el_half(int l) { return l >= 2 ? 1 : 0; }
     constexpr unsigned ELEMENT_INTERIOR_PAIRS = (1u << 5) | (1u << 6);
@@ -820,6 +826,205 @@ namespace
             v[l] *= c[l] * two_over_dt;
     }
 
+    // wh_march_pairs_scaled with the state carried already multiplied by its chain head (head 2, cuddh_hip_ddh_plan_set_head).
+    // What opens the first sweep's chain there, am qs (am = alpha / m), is only ever the start of an FMA chain, so the state is
+    // Y = am qs (the same float in all m copies of a node, since am is) and the chain opens as fma(Dg, p, Y): no head
+    // instruction.  With c2 = c / am the step is
+    //     ph = p - c2 Y,   qt = assemble(Y + chain(p)),    p -= c qt,
+    //     z  = assemble(bm qt + chain(ph)),   Y = fma(am, z, Y),   u += kw p,   vy += kw Y,
+    // 20 packed instructions per non-interior pair and step where wh_march_pairs_scaled has 21.  Y = fma(am, z, Y) is one
+    // rounding onto the integrated state, as qs += z is there, and not a third chain head (above).  The interior pairs carry
+    // Y = 2 qs (am = 2, c2 = c / 2, Y += 2 z): every operation on them is the one of wh_march_pairs_scaled on a doubled value,
+    // so their bits are those of that march and its qs + qs goes too.  vy and the parked r stay in the unit of Y across the
+    // passes; v = vy c2 (2 / dt) once at the end.  c2 is formed once per launch, before the first pass: am = 2 (1 - hm Hi) / m
+    // is not 0 in a stable solve, and invm = 0 gives c = 0, c2 = 0 and v = 0.  The sources of the first pass ride on Y as they
+    // ride on the head there.
+    // Registers: four coefficients per non-interior pair (c, c2, am, bm) where wh_march_pairs_scaled has three, twelve registers
+    // more on a loop that stood at 164 of the 168 that three wavefronts per SIMD leave.  So bm waits in LDS beside r,
+    // [pair][thread] in slots of the lane's own (six pairs: 12 KB, 44 KB a workgroup, 132 of 160 KB for three workgroups per CU),
+    // and is read once per step by the lane that wrote it, so no barrier: three ds_read2st64_b64 per step, the first LDS accesses
+    // in a time loop of this family.  The first time loop, which has the sources F / m and Gf / m in registers, reads c2 the same
+    // way, from the slots in which r waits behind it, and c2 comes back into registers before r is parked.
+    // Vector instructions per wavefront-step, first / later passes (profiles/r32): action form 214 / 190 where
+    // wh_march_pairs_scaled has 226 / 198, no v_mov_b32 in either loop, 167 VGPRs, no scratch.
+    template <int LEAN, unsigned INTERIOR, int N, typename SweepHeaded>
+    __device__ inline void wh_march_pairs_carried(const DdhArgs<float> &A, const int nt, const float dt, const float *__restrict__ filt,
+                                                  const float *__restrict__ cs, const float *__restrict__ sn, const pair_t (&invm)[N],
+                                                  const pair_t (&Hi)[N], const pair_t (&F)[N], const pair_t (&Gf)[N], const pair_t (&rm)[N],
+                                                  pair_t (&u)[N], pair_t (&v)[N], SweepHeaded sweep)
+    {
+        static_assert(LEAN == 1 || LEAN == 2, "the packed loop has wh_march's LEAN forms only");
+        constexpr unsigned ALL = (1u << N) - 1u;
+        // what fits three wavefronts per SIMD without scratch: the action form carries the interior pairs too and asks for bm at
+        // the top of the step; the form with x, which has sources on the interior pairs, leaves those as they are (the same bits)
+        // and asks for bm behind the first sweep (profiles/r32)
+        constexpr bool CARRY_INNER = LEAN == 1;
+        constexpr int BM_WHERE = LEAN == 1 ? 0 : 1;
+        __shared__ pair_t parked[2 * N][256];
+        pair_t p[N], q[N], c[N], c2[N], am[N], bm[N]; // q: Y; am = alpha / m, bm = -b / m, c2 = c / am
+        const float half_dt = 0.5f * dt;
+        constexpr int NO = N - __builtin_popcount(INTERIOR); // the non-interior pairs, and a pair's place among them
+        auto slot = [](int l) { return __builtin_popcount(~INTERIOR & ((1u << l) - 1u)); };
+        // bm in slots of its own; c2 through the first pass in the slots where r waits behind it (the first time loop has the
+        // sources in the registers c2 has in the others)
+        __shared__ pair_t parked_bm[NO][256];
+        lds_pair_t *coef = (lds_pair_t *)&parked_bm[0][threadIdx.x], *coef2 = (lds_pair_t *)&parked[0][threadIdx.x];
+        // a read the compiler cannot move out of the time loop, into the registers it is there to spare: the address passes through
+        // an empty statement first, in place (a copy would cost a v_mov_b32 per step).  Plain LDS reads otherwise, with immediate
+        // offsets, scheduled and waited for by the compiler
+        auto coef_now = [](lds_pair_t *&here)
+        {
+            asm volatile("" : "+v"(here));
+            return here;
+        };
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+        {
+            const bool inner = ((INTERIOR >> l) & 1u) != 0;
+            const pair_t hm = half_dt * invm[l], b = hm * Hi[l];
+            p[l] = q[l] = u[l] = v[l] = 0;
+            c[l] = dt * hm;
+            am[l] = inner ? pair_t{2.0f, 2.0f} : (2.0f * (1.0f - b)) * rm[l];
+            c2[l] = inner ? (CARRY_INNER ? 0.5f * c[l] : c[l]) : c[l] / am[l];
+            bm[l] = -b * rm[l];
+            if (!inner)
+            {
+                coef[256 * slot(l)] = bm[l];
+                coef2[256 * slot(l)] = c2[l];
+            }
+        }
+        // one pass from (u, vy), with the sources or without
+        auto pass = [&](auto SOURCES, const pair_t(&Fm)[N], const pair_t(&Gm)[N])
+        {
+            constexpr bool INNER_SOURCES = SOURCES.value && LEAN == 2; // the form with x has sources on the interior pairs too
+            const float k0 = filt[0];
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                p[l] = u[l];
+                q[l] = v[l];
+                u[l] *= k0;
+                v[l] *= k0;
+            }
+            for (int it = 1; it <= nt; ++it)
+            {
+                [[maybe_unused]] float c0, s0, c1, s1;
+                if constexpr (SOURCES.value)
+                {
+                    c0 = cs[2 * it - 2], s0 = sn[2 * it - 2];
+                    c1 = cs[2 * it - 1], s1 = sn[2 * it - 1];
+                }
+                const float kw = filt[it];
+                pair_t z[N], ph[N], qt[N], head[N], bl[N], cl[N];
+                lds_pair_t *const here = coef_now(coef);
+                [[maybe_unused]] lds_pair_t *here2 = nullptr;
+                if constexpr (SOURCES.value)
+                    here2 = coef_now(coef2);
+
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                    cl[l] = SOURCES.value && ((INTERIOR >> l) & 1u) == 0 ? here2[256 * slot(l)] : c2[l];
+                if constexpr (BM_WHERE == 0)
+                {
+#pragma unroll
+                    for (int l = 0; l < N; ++l)
+                        if (((INTERIOR >> l) & 1u) == 0)
+                            bl[l] = here[256 * slot(l)];
+                }
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    const bool inner = ((INTERIOR >> l) & 1u) != 0;
+                    head[l] = inner && !CARRY_INNER ? q[l] + q[l] : q[l];
+                    if (SOURCES.value && (!inner || LEAN == 2))
+                        head[l] = pk_fma(s0, Gm[l], pk_fma(c0, Fm[l], head[l]));
+                }
+                // ph before the sweep, as in wh_march_pairs_scaled
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                    ph[l] = pk_fma(-cl[l], q[l], p[l]);
+                sweep(std::integral_constant<unsigned, ALL>{}, p, head, qt);
+                if constexpr (BM_WHERE == 1)
+                {
+#pragma unroll
+                    for (int l = 0; l < N; ++l)
+                        if (((INTERIOR >> l) & 1u) == 0)
+                            bl[l] = here[256 * slot(l)];
+                }
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                    p[l] = pk_fma(-c[l], qt[l], p[l]);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    const bool inner = ((INTERIOR >> l) & 1u) != 0;
+                    if (!inner)
+                    {
+                        head[l] = bl[l] * qt[l];
+                        if (SOURCES.value)
+                            head[l] = pk_fma(s1, Gm[l], pk_fma(c1, Fm[l], head[l]));
+                    }
+                    else if (INNER_SOURCES)
+                        head[l] = pk_fma(s1, Gm[l], c1 * Fm[l]);
+                }
+                sweep(std::integral_constant<unsigned, INNER_SOURCES ? ALL : (ALL & ~INTERIOR)>{}, ph, head, z);
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    const bool inner = ((INTERIOR >> l) & 1u) != 0;
+                    q[l] = inner ? (CARRY_INNER ? pk_fma(2.0f, z[l], q[l]) : q[l] + z[l]) : pk_fma(am[l], z[l], q[l]); // onto the state, one rounding (above)
+                    u[l] = pk_fma(kw, p[l], u[l]);
+                    v[l] = pk_fma(kw, q[l], v[l]);
+                }
+            }
+        };
+        if (A.wh_iters < 1)
+            return;
+        pair_t(*const r)[256] = reinterpret_cast<pair_t(*)[256]>(&parked[0][threadIdx.x]);
+        {
+            // the sources ride on Y = am qs: in its unit, F / m and Gf / m of wh_march_pairs_scaled's heads as they are
+            pair_t Fm[N], Gm[N];
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                Fm[l] = F[l] * rm[l];
+                Gm[l] = Gf[l] * rm[l];
+            }
+            pass(std::true_type{}, Fm, Gm);
+        }
+        {
+            // c2 comes back into registers behind the first time loop, which has the sources in its place
+            lds_pair_t *here = coef_now(coef2);
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+                if (((INTERIOR >> l) & 1u) == 0)
+                    c2[l] = here[256 * slot(l)];
+        }
+        if (A.wh_iters >= 2)
+        {
+#pragma unroll
+            for (int l = 0; l < N; ++l)
+            {
+                r[l][0] = u[l];
+                r[N + l][0] = v[l];
+            }
+            for (int whit = 1; whit < A.wh_iters; ++whit)
+            {
+                pass(std::false_type{}, F, Gf); // F and Gf are not read
+#pragma unroll
+                for (int l = 0; l < N; ++l)
+                {
+                    u[l] += r[l][0];
+                    v[l] += r[N + l][0];
+                }
+            }
+        }
+        const float two_over_dt = 2.0f / dt;
+#pragma unroll
+        for (int l = 0; l < N; ++l)
+            v[l] *= c2[l] * two_over_dt;
+    }
+
     // ---------------------------------------------------------------- kernel 12 (NB = 5, 4x4 elements, rectangles): four subdomains per wavefront
     // ddh_element_lane_kernel's lane map with 25 nodes per lane: lane = element ex + 4 ey, one subdomain per 16-lane DPP row,
     // four subdomains per wavefront, register n = k + 5 l = node (k, l).  The sweep is the one documented there,
@@ -848,11 +1053,13 @@ namespace
     // ONCE: the sources in the first WaveHoltz pass only (wh_march_pairs_once; forcing 2), with PAIRED only.  The only
     //     instantiations that take LDS (32 KB a workgroup, three workgroups per CU: 96 KB of 160)
     // SCALED: ONCE with the velocity carried scaled and its midpoint update folded into the sweep (wh_march_pairs_scaled; march 2)
+    // CARRIED: SCALED with the velocity carried already multiplied by the head coefficient of the first sweep's chain
+    //     (wh_march_pairs_carried; head 2)
     // Grids: nothing, or the plan's TimeGrids (kernel 13: a pass per distinct grid among the four rows, GroupedRows; RK2 only)
     // Sep: [Bx | By | Dg | W | 1 / W], NB NB floats each (build_element_lane_tables).
     // A stays the FIRST parameter: reread_args reads it at offset 0 of the kernel-argument segment.
     // Wavefronts per SIMD: three at NB = 4; at NB = 5 two, and one in the form with x.
-    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, typename... Grids>
+    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, bool CARRIED, typename... Grids>
     __global__ void __launch_bounds__(256, NB == 4 ? 3 : (FORCED ? 1 : 2))
         ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep, const float *__restrict__ filt, const float *__restrict__ cs,
                                 const float *__restrict__ sn, Grids... grids)
@@ -867,6 +1074,7 @@ namespace
         static_assert(!(PAIRED && sizeof...(Grids) > 0), "the paired chains are built for the one-grid kernel only");
         static_assert(!(ONCE && !PAIRED), "the march with the sources in the first pass only is built beside the paired chains only");
         static_assert(!(SCALED && !ONCE), "the scaled march is built with the sources in the first pass only");
+        static_assert(!(CARRIED && !SCALED), "the carried head is built on the scaled march only");
         const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
         if (s_first >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
@@ -1023,7 +1231,11 @@ namespace
 #pragma unroll
             for (int n = 0; n < 16; ++n)
                 rm[el_pair(n & 3, n >> 2)][el_half(n >> 2)] = element_lane_inverse_multiplicity<4, 4>(n, threadIdx.x);
-            wh_march_pairs_scaled<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, rm, u, v, sweep_headed);
+            if constexpr (CARRIED)
+                wh_march_pairs_carried<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, rm, u, v,
+                                                                                                  sweep_headed);
+            else
+                wh_march_pairs_scaled<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, rm, u, v, sweep_headed);
         }
         else if constexpr (NB == 4 && ONCE)
             wh_march_pairs_once<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, ELEMENT_LANE_ONCE_FIRST_DM_PAIRS(FORCED), ELEMENT_LANE_ONCE_DM_PAIRS>(

@@ -42,7 +42,8 @@ namespace cuddh_k
         DDH_SET_CHAIN_ORDER = 2,
         DDH_SET_OWNER_RULE = 3,
         DDH_SET_FORCING = 4, // not ddh_resolve's to judge: ddh_forcing_accepted
-        DDH_SET_MARCH = 5    // nor this: ddh_march_accepted
+        DDH_SET_MARCH = 5,   // nor this: ddh_march_accepted
+        DDH_SET_HEAD = 6     // nor this: ddh_head_accepted
     };
 
     struct DdhResolved
@@ -85,4 +86,14 @@ namespace cuddh_k
 
     // May a plan store this march?  0 to 2, and 2 exactly where it may store forcing 2.  Returns 0, or 1: refused.
     int ddh_march_accepted(const DdhShape &shape, int request, unsigned facts, int current, const DdhOptions &options, int march);
+
+    // What the scaled march (march 2) carries as the velocity (cuddh_hip_ddh_plan_set_head): 1 q / (2 hm), multiplied by the head
+    // coefficient of the first sweep's chain in every step (wh_march_pairs_scaled), 2 that product itself, so that the chain
+    // opens on the state (wh_march_pairs_carried; one more new rounding), 0: the march in effect is not 2.
+    // `march_now`: what ddh_march gave; `head` as stored (0 auto).  Auto is 2 wherever the march in effect is 2, forced or not:
+    // only an explicit 1 keeps the bits of march 2 as they were.
+    int ddh_head(int march_now, int head);
+
+    // May a plan store this head?  0 to 2, and 2 exactly where it may store march 2.  Returns 0, or 1: refused.
+    int ddh_head_accepted(const DdhShape &shape, int request, unsigned facts, int current, const DdhOptions &options, int head);
 } // namespace cuddh_k

@@ -1237,6 +1237,27 @@ extern "C"
         });
         return err ? -1 : march;
     }
+    int cuddh_ddh_set_head(void *d, int head)
+    {
+        return guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            if (h->is64())
+                h->f64->internals().set_head(head);
+            else
+                h->f32->internals().set_head(head);
+        });
+    }
+    int cuddh_ddh_head(void *d)
+    {
+        int head = 0;
+        const int err = guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            head = h->is64() ? h->f64->internals().head() : h->f32->internals().head();
+        });
+        return err ? -1 : head;
+    }
     int cuddh_ddh_set_owner_rule(void *d, int last)
     {
         return guarded([&]

@@ -752,6 +752,20 @@ namespace cuddh
         }
 
         template <typename Real>
+        void DDHCore<Real>::set_head(int head) const
+        {
+            ensure_plan();
+            check_hip(cuddh_hip_ddh_plan_set_head(plan, head), "DDH head");
+        }
+
+        template <typename Real>
+        int DDHCore<Real>::head() const
+        {
+            ensure_plan();
+            return cuddh_hip_ddh_plan_head(plan);
+        }
+
+        template <typename Real>
         void DDHCore<Real>::set_last_copy_publishes(bool last) const
         {
             ensure_plan();

@@ -220,6 +220,20 @@ namespace cuddh_k
             return REFUSED;
         return march != 2 ? 0 : ddh_forcing_accepted(s, request, facts, current, o, 2);
     }
+
+    int ddh_head(int march_now, int head)
+    {
+        if (march_now != 2)
+            return 0;
+        return head == 1 ? 1 : 2;
+    }
+
+    int ddh_head_accepted(const DdhShape &s, int request, unsigned facts, int current, const DdhOptions &o, int head)
+    {
+        if (head < 0 || head > 2)
+            return REFUSED;
+        return head != 2 ? 0 : ddh_march_accepted(s, request, facts, current, o, 2);
+    }
 } // namespace cuddh_k
 
 extern "C"
@@ -274,6 +288,24 @@ extern "C"
         if (err)
             out[0] = out[1] = out[2] = out[3] = 0;
         out[4] = err ? 0 : ddh_march(out[3], sweep_form, chain_order, forcing, march);
+        return err;
+    }
+
+    int cuddh_ddh_resolve_head(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids, int rk4,
+                               int sweep_form, int chain_order, int forcing, int march, int head, int setting, int *out)
+    {
+        using namespace cuddh_k;
+        if (!out)
+            return 1; // hipErrorInvalidValue
+        const DdhShape s{nb, nel1d, n_domains, is_f64 ? 1 : 0, mx_elems};
+        const DdhOptions o{time_grids, rk4, sweep_form, chain_order};
+        int err = cuddh_ddh_resolve_march(nb, nel1d, n_domains, is_f64, mx_elems, request, facts, current, time_grids, rk4, sweep_form, chain_order, forcing,
+                                          march, setting == DDH_SET_HEAD ? DDH_SET_NONE : setting, out);
+        if (!err && (head < 0 || head > 2 || (setting == DDH_SET_HEAD && ddh_head_accepted(s, request, static_cast<unsigned>(facts), current, o, head))))
+            err = 1;
+        if (err)
+            out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+        out[5] = err ? 0 : ddh_head(out[4], head);
         return err;
     }
 }

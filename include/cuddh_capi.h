@@ -222,6 +222,10 @@ int cuddh_ddh_forcing(void *ddh);
  * (cuddh_hip_ddh_plan_set_march); the getter returns the march in effect (1 or 2; 0 where forcing 2 is not in effect; -1 on error) */
 int cuddh_ddh_set_march(void *ddh, int march);
 int cuddh_ddh_march(void *ddh);
+/* what the scaled march carries as the velocity: 0 auto, 1 q / (2 hm), 2 that times the head coefficient of the first sweep's
+ * chain (cuddh_hip_ddh_plan_set_head); the getter returns the head in effect (1 or 2; 0 where march 2 is not in effect; -1 on error) */
+int cuddh_ddh_set_head(void *ddh, int head);
+int cuddh_ddh_head(void *ddh);
 /* the owner rule of kernels 11 and 12: last != 0 lets the last copy of every shared node publish instead of the first; same
  * results, a check (cuddh_hip_ddh_plan_set_owner_rule; an error on a plan that is neither kernel 11 nor kernel 12) */
 int cuddh_ddh_set_owner_rule(void *ddh, int last);

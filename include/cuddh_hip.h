@@ -473,6 +473,19 @@ int cuddh_hip_ddh_plan_forcing(const cuddh_ddh_plan *plan);
  * effect (1 or 2), 0 where the forcing in effect is not 2. */
 int cuddh_hip_ddh_plan_set_march(cuddh_ddh_plan *plan, int march);
 int cuddh_hip_ddh_plan_march(const cuddh_ddh_plan *plan);
+/* What the scaled march (march 2) carries as the velocity, for every launch of the plan:
+ *   1 = qs = q / (2 hm); the head of the first sweep's chain, alpha / m qs, is multiplied out in every step;
+ *   2 = Y = alpha / m qs itself, the same float in all m copies of a node: the chain opens on the state, one packed instruction
+ *       per pair and step less (the interior pairs carry 2 qs and keep their bits), the update is Y = fma(alpha / m, z, Y), and
+ *       v = Y c / (alpha / m) (2 / dt) is formed once at the end.  The same scheme, rounded at other places: results differ
+ *       from 1 in the last bits, with one WaveHoltz iteration too;
+ *   0 = auto (the default): 2 wherever the march in effect is 2, whether auto chose that march or a setter did; only an
+ *       explicit 1 gives the bits march 2 had before this attribute existed.
+ * 2 is refused with hipErrorInvalidValue, the plan unchanged, exactly where march 2 is refused; where it is accepted and the
+ * march in effect is not 2 it waits.  Other values than 0, 1, 2 are invalid.  cuddh_hip_ddh_plan_head returns the head in
+ * effect (1 or 2), 0 where the march in effect is not 2. */
+int cuddh_hip_ddh_plan_set_head(cuddh_ddh_plan *plan, int head);
+int cuddh_hip_ddh_plan_head(const cuddh_ddh_plan *plan);
 /* The owner rule of kernels 11, 12 and 13, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
  * smallest element-node index publishes (last == 0, the default) or the one with the largest (last != 0).  The copies are
  * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with
@@ -517,6 +530,11 @@ int cuddh_ddh_resolve_forcing(int nb, int nel1d, int n_domains, int is_f64, int 
  * then 0). */
 int cuddh_ddh_resolve_march(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids,
                             int rk4, int sweep_form, int chain_order, int forcing, int march, int setting, int *out);
+/* The same with the head a plan holds as well (cuddh_hip_ddh_plan_set_head; 0 auto) and setting 6, the head: out[0..4] as
+ * above and out[5] the head in effect (0 to 2).  Returns 0, or 1 where the plan or the setter call is refused (out[0..5] are
+ * then 0). */
+int cuddh_ddh_resolve_head(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids,
+                           int rk4, int sweep_form, int chain_order, int forcing, int march, int head, int setting, int *out);
 /* Per-subdomain time grids.  The descriptor holds ONE grid (nt, dt, wh_filter, cs, sn), taken from the mesh alone; the wave
  * speed 1 / a never enters it, and where a < 1 the explicit time stepping runs past its usable range.  Local
  * solves couple through the traces only, so every subdomain may march its WaveHoltz period on a grid of its own: after this

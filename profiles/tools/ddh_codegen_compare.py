@@ -8,7 +8,8 @@ registers aside; a non-zero figure is an upper bound on what moved, not a minima
 the blocks that lie inside loops (the time stepping, where these kernels spend their time), and whether the instruction text, operands
 included (block labels renumbered per kernel), is the same line for line.  A new kernel with more than one innermost loop
 (the element-lane march with the sources in the first pass only has two time loops) gets a line per innermost loop, with what it
-holds and what of ds_*, scratch_* and v_readlane / v_writelane is in it.  A kernel that differs is to be
+holds and what of ds_*, scratch_* and v_readlane / v_writelane is in it, and where a loop has LDS accesses, at which instruction
+they, the s_waitcnt and the DPP instructions stand.  A kernel that differs is to be
 timed against the old build; same histogram does not mean same speed for kernels tuned on issue order."""
 import collections
 import difflib
@@ -42,17 +43,21 @@ _STAGE_RULES = ((r"\b(?:cuddh_k::wave::)?(Begin|Rk2A|Rk2B|Rk4First|Rk4Mid|Rk4Las
 _ONCE_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
 # and SCALED as its seventh (false is the march it had); applied after _ONCE_RULE, so a name from before either gets both
 _SCALED_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
-RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES, "ddh.hip": _ONCE_RULE + _SCALED_RULE}
+# and CARRIED as its eighth (false is the head it had); applied last, so a name from before any of the three gets all
+_CARRIED_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
+RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES, "ddh.hip": _ONCE_RULE + _SCALED_RULE + _CARRIED_RULE}
 # instantiations that are another one plus (or with another) template argument, per file: (pattern, replacement) pairs applied to the
 # demangled name give the base.
 # A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
 DERIVED = {"ddh.hip": ((r", Rk4Scheme ?(?=>)|, TimeGrids<\w+> ?(?=>)", ""),
                        # the paired chains (PAIRED = true, one grid only) against the pinned ones
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true, false, false>", r"\1, false, false, false>"),
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true, false, false, false>", r"\1, false, false, false, false>"),
                        # the sources in the first pass only (ONCE = true, beside the paired chains only) against every pass
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true), true, false>", r"\1, false, false>"),
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true), true, false, false>", r"\1, false, false, false>"),
                        # the scaled march (SCALED = true, beside ONCE only) against the march it is derived from
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true), true>", r"\1, false>"))}
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true), true, false>", r"\1, false, false>"),
+                       # the carried head (CARRIED = true, beside SCALED only) against the scaled march
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true, true), true>", r"\1, false>"))}
 INNER = {}  # (assembly file, kernel) -> its innermost loops
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
@@ -137,7 +142,7 @@ def main():
         for pattern, repl in derived or ():
             base = re.sub(pattern, repl, base)
         if base != name and base in all_new:
-            m0, _, l0 = all_new[base]
+            m0, _, l0 = all_new[base][:3]
             c0 = collections.Counter(l0)
             regs = lambda m: " ".join(str(m[f]) for f in FIELDS)  # noqa: E731
             print(f"{name} | NEW after, against {base} | {regs(m0)} -> {regs(m1)} | inside loops {len(l0)} -> {len(l1)}, vector instructions "
@@ -151,6 +156,10 @@ def main():
                     print(f"    innermost loop {i + 1} of {len(loops1)}: {len(lp)} instructions, vector {valu(c)} (the base's loop {valu(b)}), "
                           f"ds_* / scratch_* / v_readlane / v_writelane {barred}, against the base's: "
                           + (" ".join(f"{k}:{b[k]}->{c[k]}" for k in sorted(set(b) | set(c)) if b[k] != c[k]) or "same histogram"))
+                    if any(k.startswith("ds_") for k in lp):  # where the LDS accesses stand, and the waits behind them
+                        at = lambda pre: " ".join(f"{i}:{k}" if pre == "ds_" else str(i) for i, k in enumerate(lp) if k.startswith(pre))  # noqa: E731
+                        print(f"        ds_* at (instruction of {len(lp)}) {at('ds_')}; s_waitcnt at {at('s_waitcnt')}; DPP at "
+                              f"{' '.join(str(i) for i, k in enumerate(lp) if k.endswith('_dpp'))}")
             continue
         print(f"{name} | NEW after | {' '.join(str(m1[f]) for f in FIELDS)} | {len(o1)} instructions, {len(l1)} inside loops: "
               + " ".join(f"{k}:{c1[k]}" for k in sorted(c1)))
