@@ -198,6 +198,9 @@ _sig("cuddh_hip_ddh_plan_march", ci, vp)
 _sig("cuddh_ddh_resolve_head", ci, *([ci] * 16), vp)
 _sig("cuddh_hip_ddh_plan_set_head", ci, vp, ci)
 _sig("cuddh_hip_ddh_plan_head", ci, vp)
+_sig("cuddh_ddh_resolve_assembly", ci, *([ci] * 17), vp)
+_sig("cuddh_hip_ddh_plan_set_assembly", ci, vp, ci)
+_sig("cuddh_hip_ddh_plan_assembly", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_time_grids", ci, vp, ci, vp, vp, vp, vp, vp, vp)
 _sig("cuddh_hip_ddh_plan_time_grids", ci, vp)
 _sig("cuddh_hip_ddh_plan_set_integrator", ci, vp, ci)
@@ -358,6 +361,8 @@ _sig("cuddh_ddh_set_march", ci, vp, ci)
 _sig("cuddh_ddh_march", ci, vp)
 _sig("cuddh_ddh_set_head", ci, vp, ci)
 _sig("cuddh_ddh_head", ci, vp)
+_sig("cuddh_ddh_set_assembly", ci, vp, ci)
+_sig("cuddh_ddh_assembly", ci, vp)
 _sig("cuddh_ddh_set_owner_rule", ci, vp, ci)
 
 

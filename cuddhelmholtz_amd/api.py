@@ -693,6 +693,19 @@ class DDH:
             N.check_capi(head, "DDH.head")
         return head
 
+    def set_assembly(self, assembly: int = 0):
+        """How head 2 forms the neighbour sums of its sweeps, for every launch of this plan: 0 auto, 1 DPP on the vector pipe, 2
+        every copy of a shared node fetches the other copy's partial sum over the LDS pipe and adds it itself (bit for bit the same
+        results).  2 is refused where head 2 is not in effect (cuddh_hip_ddh_plan_set_assembly)."""
+        N.check_capi(lib.cuddh_ddh_set_assembly(self._h, int(assembly)), "DDH.set_assembly")
+
+    def assembly(self) -> int:
+        """The assembly in effect: 1 or 2; 0 where head 2 is not in effect."""
+        assembly = lib.cuddh_ddh_assembly(self._h)
+        if assembly < 0:
+            N.check_capi(assembly, "DDH.assembly")
+        return assembly
+
     def set_owner_rule(self, last: bool):
         """Kernels 11, 12 and 13: the last copy of every node that elements share publishes instead of the first (a check: same results).
         Refused on any other kernel (cuddh_hip_ddh_plan_set_owner_rule)."""

@@ -21,7 +21,8 @@
 //   the march of forcing "first" carries the velocity, as it is or scaled with its midpoint update folded into the sweep; the
 //   same rules and the same note), --head auto|multiplied|carried (DDHCore::set_head: what the scaled march carries as the
 //   velocity, q / (2 hm) multiplied by the first chain's head coefficient in every step, or that product itself; the same rules
-//   and the same note)
+//   and the same note), --assembly auto|dpp|fetched (DDHCore::set_assembly: how head "carried" forms the neighbour sums of its
+//   sweeps, with DPP on the vector pipe or fetched both ways over the LDS pipe, the same bits; the same rules and the same note)
 // Writes <out_dir>/xy.0000 and <out_dir>/ddh.0000 (raw fp64, like the reference) and prints one summary line.
 // devices >= 1: the same solve through cuddh::ddh_solve_multi_gpu (multigpu.hpp): subdomains sharded over that many GPUs of
 // this process, RCCL neighbour exchange; devices = 1 with force_rccl = 1 runs the communicator path on a one-GPU box;
@@ -41,7 +42,7 @@ using namespace cuddh;
 int main(int argc_all, char **argv_all)
 {
     // options out, positional arguments stay
-    std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs", arithmetic = "real", chain_order = "auto", forcing = "auto", march = "auto", head = "auto";
+    std::string time_step = "mesh", integrator = "rk2", orth_name = "mgs", arithmetic = "real", chain_order = "auto", forcing = "auto", march = "auto", head = "auto", assembly = "auto";
     int coarsen = 0; // 0: not given
     int augment = 0, block = 0, kernel = 0;
     bool residuals = false, block_given = false;
@@ -69,6 +70,8 @@ int main(int argc_all, char **argv_all)
             march = argv_all[++i];
         else if (arg == "--head" && i + 1 < argc_all)
             head = argv_all[++i];
+        else if (arg == "--assembly" && i + 1 < argc_all)
+            assembly = argv_all[++i];
         else if (arg == "--block" && i + 1 < argc_all)
         {
             block = std::atoi(argv_all[++i]);
@@ -156,6 +159,11 @@ int main(int argc_all, char **argv_all)
         std::cerr << "ddh_solve: --head takes auto, multiplied or carried on the single-process path, not " << head << std::endl;
         return 2;
     }
+    if ((assembly != "auto" && assembly != "dpp" && assembly != "fetched") || (assembly != "auto" && devices >= 1))
+    {
+        std::cerr << "ddh_solve: --assembly takes auto, dpp or fetched on the single-process path, not " << assembly << std::endl;
+        return 2;
+    }
     if (block < 0 || kernel < 0 || (block_given && devices >= 1))
     {
         std::cerr << "ddh_solve: --block and --kernel take non-negative integers on the single-process path" << std::endl;
@@ -231,6 +239,9 @@ int main(int argc_all, char **argv_all)
     const std::string march_note = march == "auto" ? "" : " march=" + march + " in_effect=" + std::to_string(F.internals().march());
     if (head != "auto")
         F.internals().set_head(head == "carried" ? 2 : 1);
+    if (assembly != "auto")
+        F.internals().set_assembly(assembly == "fetched" ? 2 : 1);
+    const std::string assembly_note = assembly == "auto" ? "" : " assembly=" + assembly + " in_effect=" + std::to_string(F.internals().assembly());
     const std::string head_note = head == "auto" ? "" : " head=" + head + " in_effect=" + std::to_string(F.internals().head());
     const int n_lambda = F.size();
     HostDeviceArray<float> L(n_lambda), Y(n_lambda);
@@ -269,7 +280,7 @@ int main(int argc_all, char **argv_all)
               << " success=" << out.success << " num_iter=" << out.num_iter << " num_matvec=" << out.num_matvec
               << " rel_res=" << out.res_norm.back() / out.res_norm.front() << " |u|=" << std::sqrt(unorm) << " t_rhs=" << t_rhs
               << " t_gmres=" << t_gmres << " t_postprocess=" << t_post
-              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << arith_note << block_note << chain_note << forcing_note << march_note << head_note << std::endl;
+              << " DoF*iter/s=" << 2.0 * ndof * out.num_matvec / t_gmres << orth_note << aug_note << arith_note << block_note << chain_note << forcing_note << march_note << head_note << assembly_note << std::endl;
     if (residuals)
     {
         std::cout << "ddh_solve time_step=" << time_step << " residuals:";

@@ -154,6 +154,12 @@ namespace cuddh
             /// wherever the march in effect is 2.  head() returns the head in effect, 0 where march 2 is not.
             void set_head(int head) const;
             int head() const;
+            /// How head 2 forms the neighbour sums of its sweeps: 0 auto, 1 DPP on the vector pipe (one copy of a shared node forms the
+            /// sum, the other takes it), 2 every copy fetches the other's partial sum over the LDS pipe and adds it itself, bit for bit
+            /// the same results (cuddh_hip_ddh_plan_set_assembly; 2 throws where head 2 is not in effect).  assembly() returns the
+            /// assembly in effect, 0 where head 2 is not.
+            void set_assembly(int assembly) const;
+            int assembly() const;
             /// The owner rule of kernels 11, 12 and 13: which copy of a node shared by 2 or 4 elements publishes (false: the first, the default;
             /// true: the last).  A check that the copies are bitwise equal (cuddh_hip_ddh_plan_set_owner_rule); other kernels throw.
             void set_last_copy_publishes(bool last) const;

@@ -116,6 +116,8 @@ struct cuddh_ddh_plan
     int march_now = 0; // the march in effect (ddh_march), filled by resolve() beside `now`
     int head = 0; // what march 2 carries as the velocity: 0 auto, 1 q / (2 hm), 2 that times the first chain's head coefficient (cuddh_hip_ddh_plan_set_head)
     int head_now = 0; // the head in effect (ddh_head), filled by resolve() beside `now`
+    int assembly = 0; // how head 2 forms the sweep's neighbour sums: 0 auto, 1 DPP, 2 fetched both ways over the LDS pipe (cuddh_hip_ddh_plan_set_assembly)
+    int assembly_now = 0; // the assembly in effect (ddh_assembly), filled by resolve() beside `now`
     int wave_priority = 0; // cuddh_hip_ddh_plan_set_wave_priority
     // general plans (cuddh_hip_ddh_plan_create_general; kernels 9 and 10): assembly lists, see DdhArgs::csr_off
     int *csr_off = nullptr, *csr_src = nullptr;
@@ -1776,12 +1778,12 @@ namespace
 
     // the row-per-subdomain element-lane kernel.  NB 4: kernel 5's element-lane form (LAST_COPY: form 3; PAIRED: chain order 2)
     // and kernel 13 at n_basis 4;  NB 5: kernel 12, and 13 at n_basis 5.  Sep4 holds the plan's table at either order
-    template <int NB, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, bool CARRIED, bool GRIDS>
+    template <int NB, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, bool CARRIED, bool FETCHED, bool GRIDS>
     void run_element_lane(const cuddh_ddh_plan *p, const DdhArgs<float> &A, int n_local, hipStream_t st)
     {
         with_tables<float, GRIDS, false>(p, [&](const float *fl, const float *cs, const float *sn, auto... o)
                                          { with_flags([&](auto FORCED, auto HOLD)
-                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<NB, FORCED.value, HOLD.value, LAST_COPY, PAIRED, ONCE, SCALED, CARRIED, decltype(o)...>),
+                                                      { hipLaunchKernelGGL((ddh_element_lane_kernel<NB, FORCED.value, HOLD.value, LAST_COPY, PAIRED, ONCE, SCALED, CARRIED, FETCHED, decltype(o)...>),
                                                                            launch_grid(p, n_local), dim3(p->launch.block), 0, st, A, p->Sep4, fl, cs, sn, o...); },
                                                       A.x != nullptr, A.prio != 0); });
     }
@@ -1801,7 +1803,7 @@ namespace
     // fp64 only, no RK4 form of 3, 4, 11 and 13, and 6, 7, 12 and the element-lane form of 5 on one time grid with RK2 alone.
     // ddh_resolve() never resolves to the others; if it did, L.run* would stay null and resolve() would refuse the plan.
     template <typename Real, bool GRIDS, bool RK4>
-    void set_launch(const cuddh_ddh_plan *p, const DdhResolved &r, int forcing, int march, int head, DdhLaunch &L)
+    void set_launch(const cuddh_ddh_plan *p, const DdhResolved &r, int forcing, int march, int head, int assembly, DdhLaunch &L)
     {
         constexpr bool f32 = sizeof(Real) == 4, plain = !GRIDS && !RK4;
         DdhRun<Real> run = nullptr;
@@ -1842,12 +1844,13 @@ namespace
                     // the sources in the first pass only (forcing 2) exist beside the paired chains alone, and ddh_forcing gives 2 there alone;
                     // the scaled march (march 2) beside forcing 2 alone, and ddh_march gives 2 there alone; the carried head (head 2)
                     // beside march 2 alone, and ddh_head gives 2 there alone
-                    with_flags([&](auto LAST_COPY, auto PAIRED, auto ONCE, auto SCALED, auto CARRIED)
+                    // the assembly over the LDS pipe (assembly 2) beside head 2 alone, and ddh_assembly gives 2 there alone
+                    with_flags([&](auto LAST_COPY, auto PAIRED, auto ONCE, auto SCALED, auto CARRIED, auto FETCHED)
                                {
-                                   constexpr bool once = PAIRED.value && ONCE.value, scaled = once && SCALED.value;
-                                   run = run_element_lane<4, LAST_COPY.value, PAIRED.value, once, scaled, scaled && CARRIED.value, false>;
+                                   constexpr bool once = PAIRED.value && ONCE.value, scaled = once && SCALED.value, carried = scaled && CARRIED.value;
+                                   run = run_element_lane<4, LAST_COPY.value, PAIRED.value, once, scaled, carried, carried && FETCHED.value, false>;
                                },
-                               r.form == 3, r.order == 2, forcing == 2, march == 2, head == 2);
+                               r.form == 3, r.order == 2, forcing == 2, march == 2, head == 2, assembly == 2);
                 }
             }
             break;
@@ -1875,7 +1878,7 @@ namespace
             if constexpr (f32 && plain)
             {
                 L.per_group = 16;
-                with_flags([&](auto LAST_COPY) { run = run_element_lane<5, LAST_COPY.value, false, false, false, false, false>; }, last_copy);
+                with_flags([&](auto LAST_COPY) { run = run_element_lane<5, LAST_COPY.value, false, false, false, false, false, false>; }, last_copy);
             }
             break;
         case 13: // the element-lane kernels with four subdomains per wavefront, with or without time grids; RK2 only
@@ -1886,9 +1889,9 @@ namespace
                     [&](auto LAST_COPY)
                     {
                         if (p->d.nb == 4)
-                            run = run_element_lane<4, LAST_COPY.value, false, false, false, false, GRIDS>;
+                            run = run_element_lane<4, LAST_COPY.value, false, false, false, false, false, GRIDS>;
                         else
-                            run = run_element_lane<5, LAST_COPY.value, false, false, false, false, GRIDS>;
+                            run = run_element_lane<5, LAST_COPY.value, false, false, false, false, false, GRIDS>;
                     },
                     last_copy);
             }
@@ -1920,8 +1923,11 @@ namespace
         const int forcing = ddh_forcing(r, p->sweep_form, p->chain_order, p->forcing);
         const int march = ddh_march(forcing, p->sweep_form, p->chain_order, p->forcing, p->march);
         const int head = ddh_head(march, p->head);
+        if (setting == DDH_SET_ASSEMBLY && ddh_assembly_accepted(head, p->assembly))
+            return static_cast<int>(hipErrorInvalidValue);
+        const int assembly = ddh_assembly(head, p->d.n_domains, p->assembly);
         DdhLaunch L;
-        with_flags([&](auto F64, auto GRIDS, auto RK4) { set_launch<std::conditional_t<F64.value, double, float>, GRIDS.value, RK4.value>(p, r, forcing, march, head, L); },
+        with_flags([&](auto F64, auto GRIDS, auto RK4) { set_launch<std::conditional_t<F64.value, double, float>, GRIDS.value, RK4.value>(p, r, forcing, march, head, assembly, L); },
                    p->is_f64 != 0, p->n_grids > 0, p->rk4 != 0);
         if (!L.run32 && !L.run64) // a missing kernel is an error
             return static_cast<int>(hipErrorInvalidValue);
@@ -1929,6 +1935,7 @@ namespace
         p->forcing_now = forcing;
         p->march_now = march;
         p->head_now = head;
+        p->assembly_now = assembly;
         p->launch = L;
         return 0;
     }
@@ -2243,6 +2250,15 @@ extern "C"
     }
 
     int cuddh_hip_ddh_plan_head(const cuddh_ddh_plan *plan) { return plan ? plan->head_now : 0; }
+
+    int cuddh_hip_ddh_plan_set_assembly(cuddh_ddh_plan *plan, int assembly)
+    {
+        if (!plan)
+            return static_cast<int>(hipErrorInvalidValue);
+        return set_and_resolve(plan, DDH_SET_ASSEMBLY, [&](cuddh_ddh_plan &p) { p.assembly = assembly; });
+    }
+
+    int cuddh_hip_ddh_plan_assembly(const cuddh_ddh_plan *plan) { return plan ? plan->assembly_now : 0; }
 
     int cuddh_hip_ddh_plan_set_time_grids(cuddh_ddh_plan *plan, int n_grids, const int *h_nt, const double *h_dt, const void *filter,
                                           const void *cs, const void *sn, const int *d_grid_of)

@@ -53,6 +53,11 @@ namespace
     // 214 and 190 in the action form (230 and 194 to 198 with x), 167 VGPRs, no scratch, 44 KB of LDS per workgroup, of which
     // 12 KB hold a per-dof coefficient that is read once per step, the only LDS access in a time loop of the family; one more
     // new rounding (profiles/r32).
+    // FETCHED (assembly 2, cuddh_hip_ddh_plan_set_assembly; what auto runs where it chose all of the above) forms the neighbour
+    // sums of head 2's sweeps over the LDS pipe: every copy of a shared node fetches the other copy's partial sum (ds_swizzle_b32,
+    // no LDS storage) and adds it itself, a + b in one lane and b + a in the other, so the bits are those of the DPP assembly:
+    // 16 fetches and 8 packed additions per sweep where there are 16 DPP instructions, 198 and 174 per wavefront-step in the
+    // action form (208 and 176 with x), 167 VGPRs, no scratch (profiles/r33).
     // Every form is compiled for three wavefronts per SIMD with no scratch: 168 VGPRs in the action form, 166 / 167 in
     // the form with x (rhs, postprocess: once per solve).  The assembly is 16 DPP instructions per sweep with no mask
     // multiplications in eta and one mask in xi (element_assemble_*_row_asm below): a shared node's sum is formed by one
@@ -315,6 +320,39 @@ namespace
     __device__ inline void pk_fmac_crossed(pair_t &t, pair_t c, pair_t w)
     {
         asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,0,1]" : "+v"(t) : "s"(c), "v"(w));
+    }
+
+    // The xi additions of the assembly over the LDS pipe, packed, two pairs a side: lo += what came from lane - 1 in the lanes with
+    // ex > 0 (LANES 0xeeeeeeee), hi += what came from lane + 1 in the lanes with ex < 3 (0x77777777).  Which lanes add is the same in
+    // every wavefront, so it is EXEC for two instructions, set by scalar moves, and no mask operand: a lane without the neighbour is
+    // not written.  The time loop runs with all 64 lanes (the kernel's only exit is wave-uniform and stands before it), so EXEC goes
+    // back to all ones.
+#define CUDDH_EL_ADD_FETCHED(NAME, LANES)                                                                                                  \
+    __device__ inline void NAME(pair_t &z0, pair_t &z1, pair_t f0, pair_t f1)                                                              \
+    {                                                                                                                                      \
+        asm volatile("s_mov_b32 exec_lo, " LANES "\n\t"                                                                                    \
+                     "s_mov_b32 exec_hi, " LANES "\n\t"                                                                                    \
+                     "v_pk_add_f32 %0, %0, %2\n\t"                                                                                         \
+                     "v_pk_add_f32 %1, %1, %3\n\t"                                                                                         \
+                     "s_mov_b64 exec, -1\n\t"                                                                                              \
+                     : "+v"(z0), "+v"(z1)                                                                                                  \
+                     : "v"(f0), "v"(f1));                                                                                                  \
+    }
+    CUDDH_EL_ADD_FETCHED(element_add_from_the_left, "0xeeeeeeee")
+    CUDDH_EL_ADD_FETCHED(element_add_from_the_right, "0x77777777")
+#undef CUDDH_EL_ADD_FETCHED
+    // x of another lane over the LDS pipe: ds_swizzle_b32, which uses no LDS storage and, unlike ds_bpermute_b32, no address
+    // register (one source register to move to the LDS, not two).  The pattern is the instruction's offset field:
+    // a quad permutation for xi (the four lanes of a quad are ex = 0..3 of one eta-row; a lane without the neighbour reads itself),
+    // a rotation by 4 within each 32-lane half for eta (a lane without the neighbour reads another row, or the other end of its own).
+    constexpr int FETCH_RIGHT = 0x8000 | 1 | (2 << 2) | (3 << 4) | (3 << 6); // lane + 1
+    constexpr int FETCH_LEFT = 0x8000 | 0 | (0 << 2) | (1 << 4) | (2 << 6);  // lane - 1
+    constexpr int FETCH_ABOVE = 0xC000 | (0 << 10) | (4 << 5);               // lane + 4, modulo 32
+    constexpr int FETCH_BELOW = 0xC000 | (1 << 10) | (4 << 5);               // lane - 4, modulo 32
+    template <int PATTERN>
+    __device__ inline float lane_fetch(float x)
+    {
+        return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, x), PATTERN));
     }
 
     // element_lane_products on pairs.  A node's chain is Dg w, then for j = 0..3 the x-term (j != k) and the y-term (j != l).
@@ -847,7 +885,7 @@ namespace
     // way, from the slots in which r waits behind it, and c2 comes back into registers before r is parked.
     // Vector instructions per wavefront-step, first / later passes (profiles/r32): action form 214 / 190 where
     // wh_march_pairs_scaled has 226 / 198, no v_mov_b32 in either loop, 167 VGPRs, no scratch.
-    template <int LEAN, unsigned INTERIOR, int N, typename SweepHeaded>
+    template <int LEAN, unsigned INTERIOR, bool FETCHED = false, int N, typename SweepHeaded>
     __device__ inline void wh_march_pairs_carried(const DdhArgs<float> &A, const int nt, const float dt, const float *__restrict__ filt,
                                                   const float *__restrict__ cs, const float *__restrict__ sn, const pair_t (&invm)[N],
                                                   const pair_t (&Hi)[N], const pair_t (&F)[N], const pair_t (&Gf)[N], const pair_t (&rm)[N],
@@ -891,12 +929,17 @@ namespace
             {
                 coef[256 * slot(l)] = bm[l];
                 coef2[256 * slot(l)] = c2[l];
+                if constexpr (FETCHED) // and am behind c2: the first time loop has the fetched halves in its place
+                    coef2[256 * (NO + slot(l))] = am[l];
             }
         }
         // one pass from (u, vy), with the sources or without
         auto pass = [&](auto SOURCES, const pair_t(&Fm)[N], const pair_t(&Gm)[N])
         {
             constexpr bool INNER_SOURCES = SOURCES.value && LEAN == 2; // the form with x has sources on the interior pairs too
+            // FETCHED: the fetched halves wait in registers while the other chains run, and the first sweep of the loop with the
+            // sources has none for bm beside them
+            constexpr int BM_HERE = FETCHED && SOURCES.value ? 1 : BM_WHERE;
             const float k0 = filt[0];
 #pragma unroll
             for (int l = 0; l < N; ++l)
@@ -924,7 +967,7 @@ namespace
 #pragma unroll
                 for (int l = 0; l < N; ++l)
                     cl[l] = SOURCES.value && ((INTERIOR >> l) & 1u) == 0 ? here2[256 * slot(l)] : c2[l];
-                if constexpr (BM_WHERE == 0)
+                if constexpr (BM_HERE == 0)
                 {
 #pragma unroll
                     for (int l = 0; l < N; ++l)
@@ -944,7 +987,7 @@ namespace
                 for (int l = 0; l < N; ++l)
                     ph[l] = pk_fma(-cl[l], q[l], p[l]);
                 sweep(std::integral_constant<unsigned, ALL>{}, p, head, qt);
-                if constexpr (BM_WHERE == 1)
+                if constexpr (BM_HERE == 1)
                 {
 #pragma unroll
                     for (int l = 0; l < N; ++l)
@@ -968,11 +1011,15 @@ namespace
                         head[l] = pk_fma(s1, Gm[l], c1 * Fm[l]);
                 }
                 sweep(std::integral_constant<unsigned, INNER_SOURCES ? ALL : (ALL & ~INTERIOR)>{}, ph, head, z);
+                [[maybe_unused]] lds_pair_t *here3 = nullptr;
+                if constexpr (SOURCES.value && FETCHED)
+                    here3 = coef_now(coef2); // behind the second sweep's additions: am is asked for where it is needed
 #pragma unroll
                 for (int l = 0; l < N; ++l)
                 {
                     const bool inner = ((INTERIOR >> l) & 1u) != 0;
-                    q[l] = inner ? (CARRY_INNER ? pk_fma(2.0f, z[l], q[l]) : q[l] + z[l]) : pk_fma(am[l], z[l], q[l]); // onto the state, one rounding (above)
+                    const pair_t al = SOURCES.value && FETCHED && !inner ? pair_t(here3[256 * (NO + slot(l))]) : am[l];
+                    q[l] = inner ? (CARRY_INNER ? pk_fma(2.0f, z[l], q[l]) : q[l] + z[l]) : pk_fma(al, z[l], q[l]); // onto the state, one rounding (above)
                     u[l] = pk_fma(kw, p[l], u[l]);
                     v[l] = pk_fma(kw, q[l], v[l]);
                 }
@@ -998,7 +1045,11 @@ namespace
 #pragma unroll
             for (int l = 0; l < N; ++l)
                 if (((INTERIOR >> l) & 1u) == 0)
+                {
                     c2[l] = here[256 * slot(l)];
+                    if constexpr (FETCHED)
+                        am[l] = here[256 * (NO + slot(l))];
+                }
         }
         if (A.wh_iters >= 2)
         {
@@ -1048,6 +1099,7 @@ namespace
     // __device__ __forceinline__ template compiled to other code in all sixteen instantiations tried (the callee is optimised
     // before it is inlined).  What depends on NB is constants, the state's type, and the `if constexpr (NB == 4)` branches.
     // NB: nodes per element side, 4 (the state in pairs, wh_march_pairs) or 5 (a register per node, wh_march).
+    // FETCHED: CARRIED with the neighbour sums fetched both ways over the LDS pipe (assembly 2), the same bits
     // FORCED, HOLD: as in ddh_mfma_kernel.  LAST_COPY: the owner rule turned round.
     // PAIRED: the paired chains in the sweep (element_lane_pair_product), NB = 4 and the one-grid kernel only
     // ONCE: the sources in the first WaveHoltz pass only (wh_march_pairs_once; forcing 2), with PAIRED only.  The only
@@ -1059,7 +1111,7 @@ namespace
     // Sep: [Bx | By | Dg | W | 1 / W], NB NB floats each (build_element_lane_tables).
     // A stays the FIRST parameter: reread_args reads it at offset 0 of the kernel-argument segment.
     // Wavefronts per SIMD: three at NB = 4; at NB = 5 two, and one in the form with x.
-    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, bool CARRIED, typename... Grids>
+    template <int NB, bool FORCED, bool HOLD, bool LAST_COPY, bool PAIRED, bool ONCE, bool SCALED, bool CARRIED, bool FETCHED, typename... Grids>
     __global__ void __launch_bounds__(256, NB == 4 ? 3 : (FORCED ? 1 : 2))
         ddh_element_lane_kernel(DdhArgs<float> A, const float *__restrict__ Sep, const float *__restrict__ filt, const float *__restrict__ cs,
                                 const float *__restrict__ sn, Grids... grids)
@@ -1075,6 +1127,7 @@ namespace
         static_assert(!(ONCE && !PAIRED), "the march with the sources in the first pass only is built beside the paired chains only");
         static_assert(!(SCALED && !ONCE), "the scaled march is built with the sources in the first pass only");
         static_assert(!(CARRIED && !SCALED), "the carried head is built on the scaled march only");
+        static_assert(!(FETCHED && !CARRIED), "the assembly over the LDS pipe is built on the carried head only");
         const int s_first = A.dom_begin + 4 * (blockIdx.x * 4 + (threadIdx.x >> 6));
         if (s_first >= A.dom_end)
             return; // wave-uniform: the kernel has no barriers
@@ -1213,8 +1266,51 @@ namespace
         if constexpr (NB == 4 && SCALED)
         {
             // the chains of the pairs in HEADS open on head[P]; the assembly is sweep's
+            // FETCHED: the eta masks as the pair the state's pairs need: (ey > 0, ey < 3)
+            [[maybe_unused]] const pair_t my = {(threadIdx.x & 12) > 0 ? 1.0f : 0.0f, (threadIdx.x & 12) < 12 ? 1.0f : 0.0f};
             auto sweep_headed = [&](auto HEADS, const pair_t(&w)[8], const pair_t(&head)[8], pair_t(&z)[8])
             {
+                if constexpr (FETCHED)
+                {
+                    // Assembly 2: every copy of a shared node fetches the other copy's partial sum and adds it itself, a + b in
+                    // one lane and b + a in the other: the same float.  A lane without that neighbour does not add what it
+                    // fetched (xi) or multiplies it by 0 (eta).  The pairs the xi fetches read come first, and the other chains stand behind
+                    // the fetches: the round trip over the LDS pipe hides behind them.
+                    constexpr unsigned H = HEADS.value;
+                    constexpr int RIGHT = FETCH_RIGHT, LEFT = FETCH_LEFT, ABOVE = FETCH_ABOVE, BELOW = FETCH_BELOW;
+                    z[0] = element_lane_pair_product_select<H, 0, 0>(w, head, Bx, By, Dg);
+                    z[3] = element_lane_pair_product_select<H, 3, 0>(w, head, Bx, By, Dg);
+                    z[4] = element_lane_pair_product_select<H, 0, 1>(w, head, Bx, By, Dg);
+                    z[7] = element_lane_pair_product_select<H, 3, 1>(w, head, Bx, By, Dg);
+                    // xi: my k == 0 column takes the k == 3 column of lane - 1, my k == 3 column the k == 0 column of lane + 1
+                    const pair_t f0 = {lane_fetch<LEFT>(z[3].x), lane_fetch<LEFT>(z[3].y)};
+                    const pair_t f4 = {lane_fetch<LEFT>(z[7].x), lane_fetch<LEFT>(z[7].y)};
+                    const pair_t f3 = {lane_fetch<RIGHT>(z[0].x), lane_fetch<RIGHT>(z[0].y)};
+                    const pair_t f7 = {lane_fetch<RIGHT>(z[4].x), lane_fetch<RIGHT>(z[4].y)};
+                    // nothing crosses this line: left alone, the scheduler runs all eight chains first and waits for the xi fetches
+                    // where it issued them.  One line only: with more of them (behind the eta fetches of the pairs 1 and 2, before
+                    // the xi additions) the allocator copies pairs of the state round the statements, 40 to 72 v_mov_b64 a step
+                    // (profiles/r33)
+                    __builtin_amdgcn_sched_barrier(0);
+                    z[1] = element_lane_pair_product_select<H, 1, 0>(w, head, Bx, By, Dg);
+                    z[2] = element_lane_pair_product_select<H, 2, 0>(w, head, Bx, By, Dg);
+                    // eta: my l == 0 row (.x) takes the l == 3 row (.y) of lane - 4, my l == 3 row the l == 0 row of lane + 4;
+                    // the pairs 1 and 2 have no part in xi
+                    const pair_t g1 = {lane_fetch<BELOW>(z[1].y), lane_fetch<ABOVE>(z[1].x)};
+                    const pair_t g2 = {lane_fetch<BELOW>(z[2].y), lane_fetch<ABOVE>(z[2].x)};
+                    z[5] = element_lane_pair_product_select<H, 1, 1>(w, head, Bx, By, Dg);
+                    z[6] = element_lane_pair_product_select<H, 2, 1>(w, head, Bx, By, Dg);
+                    element_add_from_the_left(z[0], z[4], f0, f4);
+                    element_add_from_the_right(z[3], z[7], f3, f7);
+                    // the corners: eta on the xi results
+                    const pair_t g0 = {lane_fetch<BELOW>(z[0].y), lane_fetch<ABOVE>(z[0].x)};
+                    const pair_t g3 = {lane_fetch<BELOW>(z[3].y), lane_fetch<ABOVE>(z[3].x)};
+                    z[1] = pk_fma(my, g1, z[1]);
+                    z[2] = pk_fma(my, g2, z[2]);
+                    z[0] = pk_fma(my, g0, z[0]);
+                    z[3] = pk_fma(my, g3, z[3]);
+                    return;
+                }
                 element_lane_products_headed<HEADS.value>(w, head, z, Bx, By, Dg);
                 float hi[4] = {z[3].x, z[7].x, z[7].y, z[3].y}, lo[4] = {z[0].x, z[4].x, z[4].y, z[0].y}; // l = 0, 1, 2, 3
                 element_assemble_xi_row_asm(hi, lo, mR);
@@ -1232,7 +1328,7 @@ namespace
             for (int n = 0; n < 16; ++n)
                 rm[el_pair(n & 3, n >> 2)][el_half(n >> 2)] = element_lane_inverse_multiplicity<4, 4>(n, threadIdx.x);
             if constexpr (CARRIED)
-                wh_march_pairs_carried<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, rm, u, v,
+                wh_march_pairs_carried<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS, FETCHED>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, rm, u, v,
                                                                                                   sweep_headed);
             else
                 wh_march_pairs_scaled<FORCED ? 2 : 1, ELEMENT_INTERIOR_PAIRS>(Ar, tg.nt, tg.dt, tg.filt, tg.cs, tg.sn, invm, Hi, F, Gf, rm, u, v, sweep_headed);

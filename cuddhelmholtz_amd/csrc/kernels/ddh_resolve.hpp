@@ -43,7 +43,8 @@ namespace cuddh_k
         DDH_SET_OWNER_RULE = 3,
         DDH_SET_FORCING = 4, // not ddh_resolve's to judge: ddh_forcing_accepted
         DDH_SET_MARCH = 5,   // nor this: ddh_march_accepted
-        DDH_SET_HEAD = 6     // nor this: ddh_head_accepted
+        DDH_SET_HEAD = 6,    // nor this: ddh_head_accepted
+        DDH_SET_ASSEMBLY = 7 // nor this: ddh_assembly_accepted
     };
 
     struct DdhResolved
@@ -96,4 +97,13 @@ namespace cuddh_k
 
     // May a plan store this head?  0 to 2, and 2 exactly where it may store march 2.  Returns 0, or 1: refused.
     int ddh_head_accepted(const DdhShape &shape, int request, unsigned facts, int current, const DdhOptions &options, int head);
+
+    // How the carried march (head 2) forms the neighbour sums of its sweeps (cuddh_hip_ddh_plan_set_assembly): 1 one copy of a
+    // shared node forms the sum and the other takes it, DPP on the vector pipe; 2 every copy fetches the other's partial sum over
+    // the LDS pipe and adds it itself (the same bits); 0: the head in effect is not 2.  `head_now`: what ddh_head
+    // gave; `assembly` as stored (0 auto).  Auto is DDH_ASSEMBLY_AUTO from ELEMENT_LANE_MIN_DOMAINS subdomains on, 1 below.
+    int ddh_assembly(int head_now, int n_domains, int assembly);
+
+    // May a plan store this assembly?  0 to 2, and 2 only where the head in effect is 2.  Returns 0, or 1: refused.
+    int ddh_assembly_accepted(int head_now, int assembly);
 } // namespace cuddh_k

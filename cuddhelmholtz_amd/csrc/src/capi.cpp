@@ -1258,6 +1258,27 @@ extern "C"
         });
         return err ? -1 : head;
     }
+    int cuddh_ddh_set_assembly(void *d, int assembly)
+    {
+        return guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            if (h->is64())
+                h->f64->internals().set_assembly(assembly);
+            else
+                h->f32->internals().set_assembly(assembly);
+        });
+    }
+    int cuddh_ddh_assembly(void *d)
+    {
+        int assembly = 0;
+        const int err = guarded([&]
+        {
+            auto *h = static_cast<DdhHandle *>(d);
+            assembly = h->is64() ? h->f64->internals().assembly() : h->f32->internals().assembly();
+        });
+        return err ? -1 : assembly;
+    }
     int cuddh_ddh_set_owner_rule(void *d, int last)
     {
         return guarded([&]

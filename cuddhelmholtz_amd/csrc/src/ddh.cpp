@@ -766,6 +766,20 @@ namespace cuddh
         }
 
         template <typename Real>
+        void DDHCore<Real>::set_assembly(int assembly) const
+        {
+            ensure_plan();
+            check_hip(cuddh_hip_ddh_plan_set_assembly(plan, assembly), "DDH assembly");
+        }
+
+        template <typename Real>
+        int DDHCore<Real>::assembly() const
+        {
+            ensure_plan();
+            return cuddh_hip_ddh_plan_assembly(plan);
+        }
+
+        template <typename Real>
         void DDHCore<Real>::set_last_copy_publishes(bool last) const
         {
             ensure_plan();

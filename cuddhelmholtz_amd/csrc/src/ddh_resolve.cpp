@@ -18,6 +18,10 @@ namespace cuddh_k
         // so a small launch of a large plan (a few subdomains, the rim launch of a multi-GPU schedule) runs four subdomains per
         // wavefront as well, at a size where this form measured slower on its own.
         constexpr int ELEMENT_LANE_MIN_DOMAINS = 8192;
+        // what auto takes as the assembly of head 2 from that size on: the form over the LDS pipe, the same bits as the DPP form.
+        // One MI355X, 65,536 subdomains, three rounds each (profiles/r33/bench_ab.txt): 137.79 to 138.05 ms per step with DPP,
+        // 133.92 to 134.20 fetched.  Smaller plans, where head 2 is in effect only when it is forced, keep DPP: not measured
+        constexpr int DDH_ASSEMBLY_AUTO = 2;
         // kernel 12 against kernel 1 under auto (n_basis 5, block 4), the same rule: the smallest measured subdomain count at which
         // kernel 12 won every round by more than the rounds differ.  One MI355X, ms per action, kernel 1 / kernel 12, three rounds
         // each (profiles/r19/ddh_nb5_rates.txt): 64 subdomains 8.51 / 8.31 (1.02 x, rounds within 0.7 %), 256 8.58 / 8.28, 1,024
@@ -234,6 +238,22 @@ namespace cuddh_k
             return REFUSED;
         return head != 2 ? 0 : ddh_march_accepted(s, request, facts, current, o, 2);
     }
+
+    int ddh_assembly(int head_now, int n_domains, int assembly)
+    {
+        if (head_now != 2)
+            return 0;
+        if (assembly != 0)
+            return assembly == 2 ? 2 : 1;
+        return n_domains >= ELEMENT_LANE_MIN_DOMAINS ? DDH_ASSEMBLY_AUTO : 1;
+    }
+
+    int ddh_assembly_accepted(int head_now, int assembly)
+    {
+        if (assembly < 0 || assembly > 2)
+            return REFUSED;
+        return assembly == 2 && head_now != 2 ? REFUSED : 0;
+    }
 } // namespace cuddh_k
 
 extern "C"
@@ -306,6 +326,22 @@ extern "C"
         if (err)
             out[0] = out[1] = out[2] = out[3] = out[4] = 0;
         out[5] = err ? 0 : ddh_head(out[4], head);
+        return err;
+    }
+
+    int cuddh_ddh_resolve_assembly(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids, int rk4,
+                                   int sweep_form, int chain_order, int forcing, int march, int head, int assembly, int setting, int *out)
+    {
+        using namespace cuddh_k;
+        if (!out)
+            return 1; // hipErrorInvalidValue
+        int err = cuddh_ddh_resolve_head(nb, nel1d, n_domains, is_f64, mx_elems, request, facts, current, time_grids, rk4, sweep_form, chain_order, forcing,
+                                         march, head, setting == DDH_SET_ASSEMBLY ? DDH_SET_NONE : setting, out);
+        if (!err && (assembly < 0 || assembly > 2 || (setting == DDH_SET_ASSEMBLY && ddh_assembly_accepted(out[5], assembly))))
+            err = 1;
+        if (err)
+            out[0] = out[1] = out[2] = out[3] = out[4] = out[5] = 0;
+        out[6] = err ? 0 : ddh_assembly(out[5], n_domains, assembly);
         return err;
     }
 }

@@ -226,6 +226,11 @@ int cuddh_ddh_march(void *ddh);
  * chain (cuddh_hip_ddh_plan_set_head); the getter returns the head in effect (1 or 2; 0 where march 2 is not in effect; -1 on error) */
 int cuddh_ddh_set_head(void *ddh, int head);
 int cuddh_ddh_head(void *ddh);
+/* how head 2 forms the neighbour sums of its sweeps: 0 auto, 1 DPP on the vector pipe, 2 fetched both ways over the LDS pipe, the
+ * same bits (cuddh_hip_ddh_plan_set_assembly); the getter returns the assembly in effect (1 or 2; 0 where head 2 is not in effect;
+ * -1 on error) */
+int cuddh_ddh_set_assembly(void *ddh, int assembly);
+int cuddh_ddh_assembly(void *ddh);
 /* the owner rule of kernels 11 and 12: last != 0 lets the last copy of every shared node publish instead of the first; same
  * results, a check (cuddh_hip_ddh_plan_set_owner_rule; an error on a plan that is neither kernel 11 nor kernel 12) */
 int cuddh_ddh_set_owner_rule(void *ddh, int last);

@@ -486,6 +486,17 @@ int cuddh_hip_ddh_plan_march(const cuddh_ddh_plan *plan);
  * effect (1 or 2), 0 where the march in effect is not 2. */
 int cuddh_hip_ddh_plan_set_head(cuddh_ddh_plan *plan, int head);
 int cuddh_hip_ddh_plan_head(const cuddh_ddh_plan *plan);
+/* How the carried march (head 2) forms the neighbour sums of its two sweeps, for every launch of the plan:
+ *   1 = one copy of a shared node forms the sum and the other copy takes it: 16 DPP instructions per sweep on the vector pipe;
+ *   2 = every copy fetches the other copy's partial sum with ds_swizzle_b32 (the LDS pipe, no LDS storage) and adds it itself;
+ *       a lane without the neighbour does not add (xi) or adds 0 times what it fetched (eta): 16 fetches and 8 packed additions
+ *       per sweep.  a + b and b + a are the same float, so the results are bit for bit those of 1 as long as every subdomain
+ *       of a wavefront stays finite;
+ *   0 = auto (the default): 2 on plans of at least 8,192 subdomains, 1 on smaller ones.
+ * 2 is refused with hipErrorInvalidValue, the plan unchanged, where the head in effect is not 2; other values than 0, 1, 2 are
+ * invalid.  cuddh_hip_ddh_plan_assembly returns the assembly in effect (1 or 2), 0 where the head in effect is not 2. */
+int cuddh_hip_ddh_plan_set_assembly(cuddh_ddh_plan *plan, int assembly);
+int cuddh_hip_ddh_plan_assembly(const cuddh_ddh_plan *plan);
 /* The owner rule of kernels 11, 12 and 13, for every launch of the plan: of the 2 or 4 copies of a node that elements share, the one with the
  * smallest element-node index publishes (last == 0, the default) or the one with the largest (last != 0).  The copies are
  * bitwise equal by construction, so the results are the same; the switch exists so that a test can assert it.  Refused with
@@ -535,6 +546,11 @@ int cuddh_ddh_resolve_march(int nb, int nel1d, int n_domains, int is_f64, int mx
  * then 0). */
 int cuddh_ddh_resolve_head(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids,
                            int rk4, int sweep_form, int chain_order, int forcing, int march, int head, int setting, int *out);
+/* The same with the assembly a plan holds as well (cuddh_hip_ddh_plan_set_assembly; 0 auto) and setting 7, the assembly:
+ * out[0..5] as above and out[6] the assembly in effect (0 to 2).  Returns 0, or 1 where the plan or the setter call is refused
+ * (out[0..6] are then 0). */
+int cuddh_ddh_resolve_assembly(int nb, int nel1d, int n_domains, int is_f64, int mx_elems, int request, int facts, int current, int time_grids,
+                               int rk4, int sweep_form, int chain_order, int forcing, int march, int head, int assembly, int setting, int *out);
 /* Per-subdomain time grids.  The descriptor holds ONE grid (nt, dt, wh_filter, cs, sn), taken from the mesh alone; the wave
  * speed 1 / a never enters it, and where a < 1 the explicit time stepping runs past its usable range.  Local
  * solves couple through the traces only, so every subdomain may march its WaveHoltz period on a grid of its own: after this

@@ -45,19 +45,23 @@ _ONCE_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+)((?:, TimeGrids
 _SCALED_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
 # and CARRIED as its eighth (false is the head it had); applied last, so a name from before any of the three gets all
 _CARRIED_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
-RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES, "ddh.hip": _ONCE_RULE + _SCALED_RULE + _CARRIED_RULE}
+# and FETCHED as its ninth (false is the DPP assembly it had); applied last, so a name from before any of the four gets all
+_FETCHED_RULE = ((r"(ddh_element_lane_kernel<\d, \w+, \w+, \w+, \w+, \w+, \w+, \w+)((?:, TimeGrids<\w+> ?)?>)$", r"\1, false\2"),)
+RENAMED_BY_RULE = {"waveholtz.hip": _STAGE_RULES, "wave_lattice.hip": _STAGE_RULES, "ddh.hip": _ONCE_RULE + _SCALED_RULE + _CARRIED_RULE + _FETCHED_RULE}
 # instantiations that are another one plus (or with another) template argument, per file: (pattern, replacement) pairs applied to the
 # demangled name give the base.
 # A new kernel with a base in NEW is printed against it (registers, scratch, loop contents, vector instructions in the loops).
 DERIVED = {"ddh.hip": ((r", Rk4Scheme ?(?=>)|, TimeGrids<\w+> ?(?=>)", ""),
                        # the paired chains (PAIRED = true, one grid only) against the pinned ones
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true, false, false, false>", r"\1, false, false, false, false>"),
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+), true, false, false, false, false>", r"\1, false, false, false, false, false>"),
                        # the sources in the first pass only (ONCE = true, beside the paired chains only) against every pass
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true), true, false, false>", r"\1, false, false, false>"),
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true), true, false, false, false>", r"\1, false, false, false, false>"),
                        # the scaled march (SCALED = true, beside ONCE only) against the march it is derived from
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true), true, false>", r"\1, false, false>"),
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true), true, false, false>", r"\1, false, false, false>"),
                        # the carried head (CARRIED = true, beside SCALED only) against the scaled march
-                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true, true), true>", r"\1, false>"))}
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true, true), true, false>", r"\1, false, false>"),
+                       # the assembly over the LDS pipe (FETCHED = true, beside CARRIED only) against the DPP assembly
+                       (r"(ddh_element_lane_kernel<\w+, \w+, \w+, \w+, true, true, true, true), true>", r"\1, false>"))}
 INNER = {}  # (assembly file, kernel) -> its innermost loops
 FIELDS = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 

@@ -6,6 +6,7 @@ ORDER (ddh): the element-lane form's chain order, DDH.set_chain_order (0 auto, 1
 FORCING (ddh): where that form's march applies the sources, DDH.set_forcing (0 auto, 1 every WaveHoltz pass, 2 the first only).
 MARCH (ddh): how that march carries the velocity, DDH.set_march (0 auto, 1 as it is, 2 scaled), where the library has it.
 HEAD (ddh): what the scaled march carries, DDH.set_head (0 auto, 1 multiplied every step, 2 carried), where the library has it.
+ASSEMBLY (ddh): how head 2 forms the neighbour sums, DDH.set_assembly (0 auto, 1 DPP, 2 fetched over the LDS pipe), where the library has it.
 Prints the kernel instantiation the operator launches (cuddh_hip_helmholtz_plan_describe)."""
 import math
 import os
@@ -29,6 +30,7 @@ order = int(sys.argv[8]) if len(sys.argv) > 8 else 0
 forcing = int(sys.argv[9]) if len(sys.argv) > 9 else 0
 march = int(sys.argv[10]) if len(sys.argv) > 10 else 0
 head = int(sys.argv[11]) if len(sys.argv) > 11 else 0
+assembly = int(sys.argv[12]) if len(sys.argv) > 12 else 0
 dev = torch.device("cuda:0")
 cd.use_torch_stream()
 omega = math.pi * nx / 32.0
@@ -68,8 +70,10 @@ else:
         F.set_march(march)
     if head:
         F.set_head(head)
+    if assembly:
+        F.set_assembly(assembly)
     print("kernel:", F.info()["kernel"], "sweep form", F.sweep_form(), "chain order", F.chain_order(), "forcing", F.forcing(), "march",
-          F.march() if hasattr(F, "march") else "-", "head", F.head() if hasattr(F, "head") else "-", "subdomains", F.info()["n_domains"], "nt", F.info()["nt"])
+          F.march() if hasattr(F, "march") else "-", "head", F.head() if hasattr(F, "head") else "-", "assembly", F.assembly() if hasattr(F, "assembly") else "-", "subdomains", F.info()["n_domains"], "nt", F.info()["nt"])
     lam = torch.rand(F.size(), dtype=torch.float32, device=dev)
     out = torch.zeros_like(lam)
     for _ in range(reps):
