@@ -13,7 +13,7 @@ import importlib
 _API = (
     "ALPHA_DISK", "ALPHA_DISK_SQ", "CONSTANT", "DDH", "GAUSSIANS", "MASS_POLY", "STIFF_FUNC", "STIFF_NEG_LAPLACIAN",
     "Basis", "DiagInvFaceMassMatrix", "DiagInvMassMatrix", "EnsembleSpace", "FaceMassMatrix", "FaceSpace", "H1Space",
-    "HelmholtzOperator", "MassMatrix", "Mesh2D", "SolverOut", "StiffnessMatrix", "WaveHoltz", "complex_linearity_defect", "device_count", "face_linear_functional",
+    "HelmholtzOperator", "MassMatrix", "Mesh2D", "SolverOut", "StiffnessMatrix", "WaveHoltz", "WaveHoltzBox", "complex_linearity_defect", "device_count", "face_linear_functional",
     "gmres", "linear_functional", "nodal_values", "quadrature", "use_torch_stream",
 )
 __all__ = list(_API)

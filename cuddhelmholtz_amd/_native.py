@@ -427,6 +427,30 @@ _sig("cuddh_wave_lattice_cell_weights", ci, vp, vp, vp, vp)
 _sig("cuddh_waveholtz_coefficient_ratio", ci, ci, ci, vp, vp, vp, vp)
 
 
+class WaveBox(C.Structure):
+    """cuddh_wave_box: A row-major n_basis x n_basis in the first entries of A"""
+    _fields_ = [("nx", ci), ("ny", ci), ("nz", ci), ("n_basis", ci), ("stride", ci), ("cx", cd), ("cy", cd), ("cz", cd), ("A", cd * 64),
+                ("w", cd * 8)]
+
+
+_wb = C.POINTER(WaveBox)
+_sig("cuddh_hip_wave_box_rk2_a_f64", ci, _wb, cd, cd, cd, *([vp] * 9))
+_sig("cuddh_hip_wave_box_rk2_b_f64", ci, _wb, cd, cd, cd, cd, *([vp] * 11))
+_sig("cuddh_hip_wave_box_rk4_1_f64", ci, _wb, cd, cd, cd, *([vp] * 11))
+_sig("cuddh_hip_wave_box_rk4_2_f64", ci, _wb, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave_box_rk4_3_f64", ci, _wb, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave_box_rk4_4_f64", ci, _wb, cd, cd, cd, cd, *([vp] * 13))
+for _n in ("x", "y", "z"):
+    _sig(f"cuddh_hip_wave_box_tile_{_n}", ci)
+_sig("cuddh_wave_box_describe", ci, ci, ci, ci, vp, ci, vp, ci, _wb, vp, vp, vp, vp, vp, vp, vp)
+_sig("cuddh_waveholtz_box_create", vp, cd, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci)
+_sig("cuddh_waveholtz_box_time_grid", ci, cd, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci, vp, vp)
+_sig("cuddh_waveholtz_box_period", ci, vp, vp, vp, vp)
+_sig("cuddh_waveholtz_box_solution", ci, vp, vp, vp)
+_sig("cuddh_waveholtz_box_info", ci, vp, vp, vp, vp, ci)
+_sig("cuddh_waveholtz_box_lattice", ci, vp, vp)
+
+
 def last_error() -> str:
     return lib.cuddh_last_error().decode()
 

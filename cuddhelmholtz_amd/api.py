@@ -925,6 +925,141 @@ class WaveHoltz(_Operator):
         return out
 
 
+class WaveHoltzBox(_Operator):
+    """Whole-domain WaveHoltz in three dimensions (csrc/include/cuddh/waveholtz_box.hpp): WaveHoltz's iteration for
+    (K - w^2 M + i w H) U = f on the box box = ((ax, bx), (ay, by), (az, bz)) of shape = (nx, ny, nz) congruent brick elements
+    with n_basis in [2, 8] Gauss-Lobatto points per direction; K the collocated stiffness, M = diag(a^2 m), H = diag(a h), one
+    launch per Runge-Kutta sweep (csrc/kernels/wave_box.hip).  There is no 3-D mesh or space class: the box is described here.
+
+    The lattice has Lx x Ly x Lz nodes, L = n (n_basis - 1) + 1 (lattice_shape()); every vector is 2 Lx Ly Lz float64, [u; v]
+    with node (I, J, K) at I + Lx (J + Ly K), i.e. a (Lz, Ly, Lx) array flattened.  h_a: HOST coefficient of shape (Lz, Ly, Lx)
+    or flat in that order, finite and positive.  nodes() gives the node coordinates, mass() the lumped mass m: the load of a
+    nodal function g is m * g.  integrator, coarsen, time_ratio: WaveHoltz's, on the mesh size min(hx, hy, hz).  absorbing: the
+    absorbing faces among "x0", "x1", "y0", "y1", "z0", "z1" (the others are sound-hard).
+        W.rhs(f, b); gmres(W.size(), z, W, b, m, maxit, tol); W.solution(z, u)        (or W.solve(f, u, ...))
+    fp64 only; paired launches, missing cells and a per-cell stiffness exist in two dimensions only.
+    Every argument error is a ValueError before any native call; a native refusal is a ValueError with its message."""
+
+    FACES = ("x0", "x1", "y0", "y1", "z0", "z1")
+
+    def __init__(self, omega: float, h_a, shape, box, n_basis: int = 4, integrator: str = "rk2", coarsen: int | None = None, time_ratio=1,
+                 absorbing=FACES):
+        scheme, coarsen = WaveHoltz._integrator(integrator, coarsen)
+        ratio = WaveHoltz._ratio(time_ratio)
+        if isinstance(omega, (bool, np.bool_)) or not isinstance(omega, (int, float, np.integer, np.floating)) or not np.isfinite(omega) or not omega > 0:
+            raise ValueError(f"WaveHoltzBox: omega must be finite and positive, not {omega!r}")
+        try:
+            shape = tuple(shape)
+        except TypeError:
+            raise ValueError(f"WaveHoltzBox: shape must be (nx, ny, nz), not {shape!r}") from None
+        if len(shape) != 3 or any(isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) for n in shape):
+            raise ValueError(f"WaveHoltzBox: shape must be three integers (nx, ny, nz), not {shape!r}")
+        if any(n < 1 for n in shape):
+            raise ValueError(f"WaveHoltzBox: every element count must be at least 1, not {shape!r}")
+        if isinstance(n_basis, (bool, np.bool_)) or not isinstance(n_basis, (int, np.integer)) or not 2 <= n_basis <= 8:
+            raise ValueError(f"WaveHoltzBox: n_basis must be an integer in [2, 8], not {n_basis!r}")
+        try:
+            box = np.ascontiguousarray(box, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("WaveHoltzBox: box must be ((ax, bx), (ay, by), (az, bz))") from None
+        if box.shape != (3, 2) or not np.all(np.isfinite(box)) or not np.all(box[:, 0] < box[:, 1]):
+            raise ValueError(f"WaveHoltzBox: box must be three finite intervals ((ax, bx), (ay, by), (az, bz)) with a < b, not {box.tolist()!r}")
+        if isinstance(absorbing, str):
+            raise ValueError(f"WaveHoltzBox: absorbing must be a sequence of face names among {self.FACES}, not {absorbing!r}")
+        try:
+            absorbing = tuple(absorbing)
+        except TypeError:
+            raise ValueError(f"WaveHoltzBox: absorbing must be a sequence of face names among {self.FACES}, not {absorbing!r}") from None
+        if any(not isinstance(f, str) or f not in self.FACES for f in absorbing) or len(set(absorbing)) != len(absorbing):
+            raise ValueError(f"WaveHoltzBox: absorbing must name distinct faces among {self.FACES}, not {absorbing!r}")
+        mask = sum(1 << self.FACES.index(f) for f in absorbing)
+        H = int(n_basis) - 1
+        L = tuple(int(n) * H + 1 for n in shape)  # Lx, Ly, Lz
+        stride = (L[0] + 1) // 2 * 2
+        if stride * L[1] * L[2] > 0x7FFFFFFF:
+            raise ValueError(f"WaveHoltzBox: the padded lattice of {stride} x {L[1]} x {L[2]} slots does not fit in an int")
+        try:
+            h_a = np.ascontiguousarray(h_a, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("WaveHoltzBox: h_a must be an array of floats") from None
+        if h_a.shape not in ((L[2], L[1], L[0]), (L[0] * L[1] * L[2],)):
+            raise ValueError(f"WaveHoltzBox: h_a must have shape {(L[2], L[1], L[0])} (Lz, Ly, Lx) or be flat in that order, not {h_a.shape}")
+        if not np.all(np.isfinite(h_a)) or not np.all(h_a > 0):
+            raise ValueError("WaveHoltzBox: the coefficient a must be finite and positive")
+        args = (int(shape[0]), int(shape[1]), int(shape[2]), _h(box), int(n_basis), _h(h_a))
+        h = lib.cuddh_waveholtz_box_create(float(omega), *args, scheme, coarsen, ratio, mask)
+        if not h and N.last_error().startswith("WaveHoltz error"):
+            raise ValueError(f"WaveHoltzBox: {N.last_error()}")
+        n = L[0] * L[1] * L[2]
+        super().__init__(N.handle(h, "WaveHoltzBox"), (), 2 * n)
+        self.omega, self.shape, self.box, self.n_basis, self.absorbing = float(omega), tuple(int(n) for n in shape), box, int(n_basis), absorbing
+        self._L, self._mask = L, mask
+
+    def size(self) -> int:
+        return self._n
+
+    def lattice_shape(self) -> tuple:
+        """(Lx, Ly, Lz), read from the native object"""
+        dims = np.zeros(3, dtype=np.int32)
+        N.check_capi(lib.cuddh_waveholtz_box_lattice(self._h, _h(dims)), "WaveHoltzBox.lattice_shape")
+        return tuple(int(d) for d in dims)
+
+    def nodes(self) -> np.ndarray:
+        """HOST (Lz, Ly, Lx, 3): the coordinates (x, y, z) of every lattice node"""
+        xi, _ = quadrature(self.n_basis)
+        H = self.n_basis - 1
+        lines = []
+        for d in range(3):
+            a, b = self.box[d]
+            h = (b - a) / self.shape[d]
+            i = np.arange(self._L[d])
+            e = np.minimum(i // H, self.shape[d] - 1)
+            lines.append(a + h * (e + 0.5 * (xi[i - e * H] + 1.0)))
+        out = np.empty((self._L[2], self._L[1], self._L[0], 3))
+        out[..., 0] = lines[0][None, None, :]
+        out[..., 1] = lines[1][None, :, None]
+        out[..., 2] = lines[2][:, None, None]
+        return out
+
+    def mass(self) -> np.ndarray:
+        """HOST (Lz, Ly, Lx): the lumped mass m (without the coefficient); the load of a nodal function g is m * g"""
+        m = np.empty(self._L[0] * self._L[1] * self._L[2])
+        N.check_capi(lib.cuddh_wave_box_describe(*self.shape, _h(self.box), self.n_basis, None, self._mask, None, None, _h(m), None, None, None, None,
+                                                 None), "WaveHoltzBox.mass")
+        return m.reshape(self._L[2], self._L[1], self._L[0])
+
+    def period(self, z_in, f, z_out):
+        """z_out = W(z_in; f): one filtered period from z_in (None: zero) under the load f = [f_re; f_im] (None: none)"""
+        N.check_capi(lib.cuddh_waveholtz_box_period(self._h, _ptr(z_in, "f64", self._n, "z_in"), _ptr(f, "f64", self._n, "f"),
+                                                    _ptr(z_out, "f64", self._n, "z_out")), "WaveHoltzBox.period")
+
+    def rhs(self, f, b):
+        self.period(None, f, b)
+
+    def solution(self, z, u):
+        """u = [z_u; z_v / omega]"""
+        N.check_capi(lib.cuddh_waveholtz_box_solution(self._h, _ptr(z, "f64", self._n, "z"), _ptr(u, "f64", self._n, "u")), "WaveHoltzBox.solution")
+
+    def info(self) -> dict:
+        info = np.zeros(6, dtype=np.int32)
+        dt = C.c_double()
+        buf = C.create_string_buffer(160)
+        N.check_capi(lib.cuddh_waveholtz_box_info(self._h, _h(info), C.byref(dt), buf, 160), "WaveHoltzBox.info")
+        return {"nt": int(info[0]), "dt": dt.value, "ratio": int(info[1]), "integrator": "rk4" if info[2] else "rk2", "coarsen": int(info[3]),
+                "sweeps_per_period": int(info[4]), "nodes": int(info[5]), "stiffness_kernel": buf.value.decode()}
+
+    def solve(self, f, u, m: int = 20, maxit: int = 200, tol: float = 1e-6, orth: str = "mgs", augment: int = 0) -> "SolverOut":
+        """rhs -> gmres from zero -> solution; u receives [Re U; Im U]"""
+        import torch
+
+        b = torch.empty(self._n, dtype=torch.float64, device=f.device)
+        z = torch.zeros_like(b)
+        self.rhs(f, b)
+        out = gmres(self._n, z, self, b, m, maxit, tol, orth=orth, augment=augment)
+        self.solution(z, u)
+        return out
+
+
 def _orth_code(orth) -> int:
     """the C API's code of an orthogonalisation name; anything but "mgs" / "cgs2" is a ValueError, before any native call"""
     if not isinstance(orth, str) or orth not in ORTHOGONALIZATIONS:

@@ -26,6 +26,8 @@
 #include "cuddh/helmholtz.hpp"
 #include "cuddh/waveholtz.hpp"
 #include "cuddh/wave_lattice.hpp"
+#include "cuddh/wave_box.hpp"
+#include "cuddh/waveholtz_box.hpp"
 #include "cuddh/multigpu.hpp"
 #include "cuddh/partition.hpp"
 

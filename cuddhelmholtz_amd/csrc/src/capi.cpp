@@ -540,6 +540,8 @@ extern "C"
                 name = m->kernel_name();
             else if (auto *wh = dynamic_cast<WaveHoltz *>(h->op.get()))
                 name = wh->stiffness_kernel();
+            else if (auto *wb = dynamic_cast<WaveHoltzBox *>(h->op.get()))
+                name = wb->stiffness_kernel();
             std::snprintf(buf, cap, "%s", name.c_str());
         });
     }
@@ -737,6 +739,126 @@ extern "C"
     int cuddh_wave_lattice_tables(void *basis, double *h_A, double *h_w)
     {
         return guarded([&] { wave_lattice_tables(*static_cast<Basis *>(basis), h_A, h_w); });
+    }
+
+    // ------------------------------------------------------------ whole-domain WaveHoltz on a box (three dimensions)
+    int cuddh_wave_box_describe(int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int face_mask, cuddh_wave_box *desc,
+                                int *h_dims, double *h_m, double *h_h, double *h_invm, double *h_Hi, int *h_dof_of_slot, int *h_slot_of_dof)
+    {
+        return guarded([&]
+        {
+            if (face_mask < 0)
+                throw std::runtime_error("WaveHoltz error: box: the face mask has six bits (x0, x1, y0, y1, z0, z1), not " + std::to_string(face_mask) + ".");
+            const WaveBox B = build_wave_box(nx, ny, nz, h_box, n_basis, h_a, static_cast<unsigned>(face_mask));
+            if (desc)
+                *desc = B.desc;
+            if (h_dims)
+            {
+                h_dims[0] = B.Lx;
+                h_dims[1] = B.Ly;
+                h_dims[2] = B.Lz;
+                h_dims[3] = B.desc.stride;
+            }
+            const std::pair<const std::vector<double> *, double *> reals[] = {{&B.m, h_m}, {&B.h, h_h}, {&B.invm, h_invm}, {&B.Hi, h_Hi}};
+            for (const auto &r : reals)
+                if (r.second)
+                    std::copy(r.first->begin(), r.first->end(), r.second);
+            if (h_dof_of_slot)
+                std::copy(B.dof_of_slot.begin(), B.dof_of_slot.end(), h_dof_of_slot);
+            if (h_slot_of_dof)
+                std::copy(B.slot_of_dof.begin(), B.slot_of_dof.end(), h_slot_of_dof);
+        });
+    }
+    namespace
+    {
+        // checked before anything else is looked at
+        WaveHoltzBoxOptions box_options(const double *h_a, int integrator, int coarsen, int time_ratio, int face_mask)
+        {
+            if (integrator != 0 && integrator != 1)
+                throw std::runtime_error("WaveHoltz error: integrator: the scheme must be 0 (rk2) or 1 (rk4), not " + std::to_string(integrator) + ".");
+            if (face_mask < 0)
+                throw std::runtime_error("WaveHoltz error: box: the face mask has six bits (x0, x1, y0, y1, z0, z1), not " + std::to_string(face_mask) + ".");
+            if (!h_a)
+                throw std::runtime_error("WaveHoltz error: box: no coefficient was given (NULL).");
+            WaveHoltzBoxOptions o;
+            o.integrator = {integrator == 1 ? DDHIntegrator::rk4 : DDHIntegrator::rk2, coarsen};
+            o.time_ratio = time_ratio;
+            o.faces = static_cast<unsigned>(face_mask);
+            return o;
+        }
+    } // namespace
+    int cuddh_waveholtz_box_time_grid(double omega, int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int integrator,
+                                      int coarsen, int time_ratio, int face_mask, int *h_steps, double *h_dt)
+    {
+        return guarded([&]
+        {
+            const WaveBoxTimeGrid g = wave_box_time_grid(omega, nx, ny, nz, h_box, n_basis, h_a, box_options(h_a, integrator, coarsen, time_ratio, face_mask));
+            if (h_steps)
+            {
+                h_steps[0] = g.nt;
+                h_steps[1] = g.ratio;
+            }
+            if (h_dt)
+                *h_dt = g.dt;
+        });
+    }
+    void *cuddh_waveholtz_box_create(double omega, int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int integrator,
+                                     int coarsen, int time_ratio, int face_mask)
+    {
+        return guarded_new<OpHandle>([&]
+        {
+            const WaveHoltzBoxOptions o = box_options(h_a, integrator, coarsen, time_ratio, face_mask);
+            auto h = new OpHandle;
+            try
+            {
+                h->op.reset(new WaveHoltzBox(omega, nx, ny, nz, h_box, n_basis, h_a, o));
+            }
+            catch (...)
+            {
+                delete h;
+                throw;
+            }
+            return h;
+        });
+    }
+    namespace
+    {
+        const WaveHoltzBox &waveholtz_box_of(void *op)
+        {
+            auto *W = op ? dynamic_cast<const WaveHoltzBox *>(static_cast<OpHandle *>(op)->op.get()) : nullptr;
+            if (!W)
+                throw std::runtime_error("not a WaveHoltzBox operator");
+            return *W;
+        }
+    } // namespace
+    int cuddh_waveholtz_box_period(void *op, const double *z_in, const double *f, double *z_out)
+    {
+        return guarded([&] { waveholtz_box_of(op).period(z_in, f, z_out); });
+    }
+    int cuddh_waveholtz_box_solution(void *op, const double *z, double *u) { return guarded([&] { waveholtz_box_of(op).solution(z, u); }); }
+    int cuddh_waveholtz_box_info(void *op, int *h_info, double *h_dt, char *kernel, int cap)
+    {
+        return guarded([&]
+        {
+            const WaveHoltzBox &W = waveholtz_box_of(op);
+            if (h_info)
+            {
+                h_info[0] = W.num_steps();
+                h_info[1] = W.time_ratio();
+                h_info[2] = W.integrator().scheme == DDHIntegrator::rk4 ? 1 : 0;
+                h_info[3] = W.integrator().coarsen;
+                h_info[4] = W.sweeps_per_period();
+                h_info[5] = W.size() / 2;
+            }
+            if (h_dt)
+                *h_dt = W.time_step();
+            if (kernel && cap > 0)
+                std::snprintf(kernel, cap, "%s", W.stiffness_kernel().c_str());
+        });
+    }
+    int cuddh_waveholtz_box_lattice(void *op, int *h_dims)
+    {
+        return guarded([&] { waveholtz_box_of(op).lattice(h_dims); });
     }
 
     int cuddh_helmholtz_read_stamps(void *op, unsigned long long *h_out, int n_patches)

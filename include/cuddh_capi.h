@@ -412,6 +412,30 @@ int cuddh_waveholtz_coefficient_ratio(int n_elem, int nodes_per_elem, const int 
 /* the 1-D tables of the lattice form on the reference element: h_A (n_basis x n_basis, row-major) = D^T diag(w) D, h_w (n_basis) */
 int cuddh_wave_lattice_tables(void *basis, double *h_A, double *h_w);
 
+/* ---- whole-domain WaveHoltz in three dimensions (csrc/include/cuddh/waveholtz_box.hpp): the iteration above on a
+ * box [ax, bx] x [ay, by] x [az, bz] of nx x ny x nz congruent brick elements with n_basis in [2, 8] Gauss-Lobatto points per
+ * direction, on the kernels cuddh_hip_wave_box_* (cuddh_hip.h states the operators K, m, h and the layout).  h_box = {ax, bx, ay,
+ * by, az, bz}; h_a: HOST coefficient, one finite positive value per lattice node, node (I, J, K) at I + Lx (J + Ly K), L = n
+ * (n_basis - 1) + 1; integrator, coarsen and time_ratio as for cuddh_waveholtz_create, the mesh size being min(hx, hy, hz);
+ * face_mask: bits 0..5 = the faces x = ax, x = bx, y = ay, y = by, z = az, z = bz absorbing, the others sound-hard.  The handle
+ * is an OPERATOR handle of size 2 Lx Ly Lz whose action is y = x - S x, exactly like cuddh_waveholtz_create's; vectors are in the
+ * lattice order above.  Anything else is refused before anything is allocated (NULL + cuddh_last_error; the message starts with
+ * "WaveHoltz error: box:", "WaveHoltz error: time step:" or "WaveHoltz error: integrator:"). */
+void *cuddh_waveholtz_box_create(double omega, int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int integrator,
+                                 int coarsen, int time_ratio, int face_mask);
+/* Plain host code, nothing is allocated: every refusal of cuddh_waveholtz_box_create, then the period's grid such an operator
+ * marches on: h_steps = {nt, the time ratio in effect}, nt = ratio * ceil(mesh_grid_steps(omega, min(hx, hy, hz), n_basis) /
+ * coarsen), and *h_dt = 2 pi / (omega nt).  Returns 0, or nonzero with cuddh_last_error() as above and nothing written. */
+int cuddh_waveholtz_box_time_grid(double omega, int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int integrator,
+                                  int coarsen, int time_ratio, int face_mask, int *h_steps, double *h_dt);
+/* cuddh_waveholtz_period, _solution and _info for such a handle; the kernel is "wave_box nb<n_basis>", followed by
+ * " (run-time n_basis)" where n_basis is no compile-time form; h_info[5] = Lx Ly Lz */
+int cuddh_waveholtz_box_period(void *op, const double *z_in, const double *f, double *z_out);
+int cuddh_waveholtz_box_solution(void *op, const double *z, double *u);
+int cuddh_waveholtz_box_info(void *op, int *h_info, double *h_dt, char *kernel, int cap);
+/* h_dims = {Lx, Ly, Lz} */
+int cuddh_waveholtz_box_lattice(void *op, int *h_dims);
+
 #ifdef __cplusplus
 }
 #endif

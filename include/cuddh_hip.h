@@ -886,6 +886,69 @@ int cuddh_hip_wave_weights32_rk4_4(const cuddh_wave_lattice *lattice, const floa
                                    const float *ps, const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi,
                                    const float *F, const float *G, float *p, float *q, float *u, float *v, void *stream);
 
+/* ------------------------------------------------------------------ whole-domain WaveHoltz march in three dimensions: box sweeps
+ * csrc/kernels/wave_box.hip, DESIGN 4.5.6.  On a box of nx x ny x nz congruent brick elements the collocated stiffness is
+ *     K = cx Wz (x) Wy (x) Ax  +  cy Wz (x) Ay (x) Wx  +  cz Az (x) Wy (x) Wx
+ * on the lattice of Lx x Ly x Lz Gauss-Lobatto nodes, L = n (n_basis - 1) + 1; Ax, Ay, Az: the 1-D element matrix A assembled along
+ * a line of elements that overlap in one node, Wx, Wy, Wz: the weights w assembled the same way (both exactly as stated for
+ * cuddh_wave_lattice above: row ids, offset ranges, the centre coefficient A[H][H] + A[0][0] and the weight w[H] + w[0] where two
+ * elements meet, each formed once on the host in double).  cx = hy hz / (2 hx), cy = hx hz / (2 hy), cz = hx hy / (2 hz).
+ * The six entry points are those of cuddh_hip_wave_lattice_*_f64, argument by argument, with this description in the place of
+ * the lattice: one launch computes w = K p' at every node and does the stage.
+ *
+ * Vectors hold node (I, J, K) at I + stride (J + Ly K) and have stride * Ly * Lz doubles (which must fit in an int); stride >= Lx
+ * and even, every pointer 16-byte aligned.  The columns from Lx on are padding: zero state, zero load and invm = 0, kept zero by
+ * the kernels and never read by the stencil.  With
+ *     sx = sum_d Tx(I, d) p'(I + d, J, K),   sy = sum_d Ty(J, d) p'(I, J + d, K),   sz = sum_d Tz(K, d) p'(I, J, K + d),
+ * each from zero over the node's ascending offsets d by fused multiply-adds (T and the ranges as for cuddh_wave_lattice), and
+ *     ax = cx * (Wy(J) * Wz(K)),   ay = cy * (Wx(I) * Wz(K)),   az = cz * (Wx(I) * Wy(J))      (each product rounded, inner first),
+ *     (K p')(I, J, K) = fma(ax, sx, fma(ay, sy, az * sz)).
+ * The order depends on (I, J, K) alone: results are bitwise reproducible, exact for integer tables, and the forced form with
+ * F = G = 0 gives the homogeneous bits.  A is row-major and need not be symmetric.
+ * The stencil's input must not be an output (rk4_2 and rk4_3 take ps_in and ps_out); the other inputs may be updated in place.
+ * A bad description (NULL, a count < 1, n_basis outside [2, 8], stride < Lx or odd, stride * Ly * Lz beyond an int), a misaligned
+ * or NULL pointer, F without G or an output that is the stencil's input return hipErrorInvalidValue (1) and nothing is launched. */
+typedef struct cuddh_wave_box
+{
+    int nx, ny, nz, n_basis, stride; /* n_basis in [2, 8] */
+    double cx, cy, cz;               /* hy hz / (2 hx), hx hz / (2 hy), hx hy / (2 hz) */
+    double A[64], w[8];              /* HOST tables: A[k * n_basis + j], w[k] */
+} cuddh_wave_box;
+int cuddh_hip_wave_box_rk2_a_f64(const cuddh_wave_box *box, double half_dt, double c, double s, const double *p, const double *q,
+                                 const double *invm, const double *Hi, const double *F, const double *G, double *qh, double *ph, void *stream);
+int cuddh_hip_wave_box_rk2_b_f64(const cuddh_wave_box *box, double dt, double c, double s, double filt, const double *ph, const double *qh,
+                                 const double *invm, const double *Hi, const double *F, const double *G, double *p, double *q, double *u,
+                                 double *v, void *stream);
+int cuddh_hip_wave_box_rk4_1_f64(const cuddh_wave_box *box, double half_dt, double c, double s, const double *p, const double *q,
+                                 const double *invm, const double *Hi, const double *F, const double *G, double *ps, double *qs, double *aq,
+                                 double *ap, void *stream);
+int cuddh_hip_wave_box_rk4_2_f64(const cuddh_wave_box *box, double half_dt, double c, double s, const double *ps_in, const double *p,
+                                 const double *q, const double *invm, const double *Hi, const double *F, const double *G, double *ps_out,
+                                 double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_box_rk4_3_f64(const cuddh_wave_box *box, double dt, double c, double s, const double *ps_in, const double *p,
+                                 const double *q, const double *invm, const double *Hi, const double *F, const double *G, double *ps_out,
+                                 double *qs, double *aq, double *ap, void *stream);
+int cuddh_hip_wave_box_rk4_4_f64(const cuddh_wave_box *box, double sixth_dt, double c, double s, double filt, const double *ps,
+                                 const double *qs, const double *aq, const double *ap, const double *invm, const double *Hi, const double *F,
+                                 const double *G, double *p, double *q, double *u, double *v, void *stream);
+/* nodes of a workgroup's tile in x, y and z (the sizes at which the kernels' paths change) */
+int cuddh_hip_wave_box_tile_x(void);
+int cuddh_hip_wave_box_tile_y(void);
+int cuddh_hip_wave_box_tile_z(void);
+/* The box problem from arrays alone (csrc/src/wave_box.cpp; plain host code, no device is touched).  h_box = {ax, bx, ay, by, az,
+ * bz}; h_a: one finite positive coefficient per lattice node, node (I, J, K) at I + Lx (J + Ly K), or NULL for a == 1; face_mask:
+ * bit 0..5 = the faces x = ax, x = bx, y = ay, y = by, z = az, z = bz absorbing (the others sound-hard).  Every output may be NULL:
+ * desc (stride = Lx rounded up to even); h_dims = {Lx, Ly, Lz, stride}; in UNPADDED lattice order, Lx Ly Lz each:
+ *     h_m    = (hx hy hz / 8) Wz(K) Wy(J) Wx(I)                                   the lumped mass,
+ *     h_h    = sum over the absorbing faces that contain the node of the lumped face mass: (hy hz / 4) Wz(K) Wy(J) on an x face,
+ *              (hx hz / 4) Wz(K) Wx(I) on a y face, (hx hy / 4) Wy(J) Wx(I) on a z face,
+ *     h_invm = 1 / (a^2 m),   h_Hi = h a;
+ * h_dof_of_slot (stride Ly Lz: the node of a padded slot, -1 for padding) and h_slot_of_dof (Lx Ly Lz).  A count < 1, an empty or
+ * inverted interval, n_basis outside [2, 8], a coefficient that is not finite and positive, a face mask outside 6 bits or
+ * stride * Ly * Lz beyond an int return nonzero with cuddh_last_error() beginning "WaveHoltz error: box:" and nothing written. */
+int cuddh_wave_box_describe(int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int face_mask, cuddh_wave_box *desc,
+                            int *h_dims, double *h_m, double *h_h, double *h_invm, double *h_Hi, int *h_dof_of_slot, int *h_slot_of_dof);
+
 #ifdef __cplusplus
 }
 #endif
