@@ -449,6 +449,18 @@ _sig("cuddh_waveholtz_box_period", ci, vp, vp, vp, vp)
 _sig("cuddh_waveholtz_box_solution", ci, vp, vp, vp)
 _sig("cuddh_waveholtz_box_info", ci, vp, vp, vp, vp, ci)
 _sig("cuddh_waveholtz_box_lattice", ci, vp, vp)
+# (the box sweeps in fp32: the same arguments, float vectors; rows of a multiple of four floats)
+_sig("cuddh_hip_wave_box32_rk2_a", ci, _wb, cd, cd, cd, *([vp] * 9))
+_sig("cuddh_hip_wave_box32_rk2_b", ci, _wb, cd, cd, cd, cd, *([vp] * 11))
+_sig("cuddh_hip_wave_box32_rk4_1", ci, _wb, cd, cd, cd, *([vp] * 11))
+_sig("cuddh_hip_wave_box32_rk4_2", ci, _wb, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave_box32_rk4_3", ci, _wb, cd, cd, cd, *([vp] * 12))
+_sig("cuddh_hip_wave_box32_rk4_4", ci, _wb, cd, cd, cd, cd, *([vp] * 13))
+for _n in "xyz":
+    _sig(f"cuddh_hip_wave_box32_tile_{_n}", ci)
+_sig("cuddh_wave_box_describe_rows", ci, ci, ci, ci, vp, ci, vp, ci, ci, _wb, vp, vp, vp, vp, vp, vp, vp)
+_sig("cuddh_waveholtz_box_create_precision", vp, cd, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci, ci)
+_sig("cuddh_waveholtz_box_precision", ci, vp)
 
 
 def last_error() -> str:

@@ -937,13 +937,20 @@ class WaveHoltzBox(_Operator):
     nodal function g is m * g.  integrator, coarsen, time_ratio: WaveHoltz's, on the mesh size min(hx, hy, hz).  absorbing: the
     absorbing faces among "x0", "x1", "y0", "y1", "z0", "z1" (the others are sound-hard).
         W.rhs(f, b); gmres(W.size(), z, W, b, m, maxit, tol); W.solution(z, u)        (or W.solve(f, u, ...))
-    fp64 only; paired launches, missing cells and a per-cell stiffness exist in two dimensions only.
+    precision "f64" (the default) or "f32" (DESIGN 4.5.7): the lattice vectors are stored and the sweeps computed in fp32
+    (csrc/kernels/wave_box_f32.hip), half the march's memory and bytes per sweep.  z, f, b and the solution stay float64; y =
+    x - S x is formed in float64.  It is meant for tolerances around 1e-4: the fp32 operator's own defect is about 1e-6 relative,
+    so a solve to 1e-6 or below wants "f64".  info()["stiffness_kernel"] is then "wave_box nb<n> f32".
+    Paired launches, missing cells and a per-cell stiffness exist in two dimensions only.
     Every argument error is a ValueError before any native call; a native refusal is a ValueError with its message."""
 
     FACES = ("x0", "x1", "y0", "y1", "z0", "z1")
+    PRECISIONS = ("f64", "f32")
 
     def __init__(self, omega: float, h_a, shape, box, n_basis: int = 4, integrator: str = "rk2", coarsen: int | None = None, time_ratio=1,
-                 absorbing=FACES):
+                 absorbing=FACES, precision: str = "f64"):
+        if not isinstance(precision, str) or precision not in self.PRECISIONS:
+            raise ValueError(f"WaveHoltzBox: precision must be 'f64' or 'f32', not {precision!r}")
         scheme, coarsen = WaveHoltz._integrator(integrator, coarsen)
         ratio = WaveHoltz._ratio(time_ratio)
         if isinstance(omega, (bool, np.bool_)) or not isinstance(omega, (int, float, np.integer, np.floating)) or not np.isfinite(omega) or not omega > 0:
@@ -975,7 +982,8 @@ class WaveHoltzBox(_Operator):
         mask = sum(1 << self.FACES.index(f) for f in absorbing)
         H = int(n_basis) - 1
         L = tuple(int(n) * H + 1 for n in shape)  # Lx, Ly, Lz
-        stride = (L[0] + 1) // 2 * 2
+        rows = 4 if precision == "f32" else 2  # rows of the padded lattice hold a multiple of four floats or of two doubles
+        stride = (L[0] + rows - 1) // rows * rows
         if stride * L[1] * L[2] > 0x7FFFFFFF:
             raise ValueError(f"WaveHoltzBox: the padded lattice of {stride} x {L[1]} x {L[2]} slots does not fit in an int")
         try:
@@ -987,7 +995,10 @@ class WaveHoltzBox(_Operator):
         if not np.all(np.isfinite(h_a)) or not np.all(h_a > 0):
             raise ValueError("WaveHoltzBox: the coefficient a must be finite and positive")
         args = (int(shape[0]), int(shape[1]), int(shape[2]), _h(box), int(n_basis), _h(h_a))
-        h = lib.cuddh_waveholtz_box_create(float(omega), *args, scheme, coarsen, ratio, mask)
+        if precision == "f64":
+            h = lib.cuddh_waveholtz_box_create(float(omega), *args, scheme, coarsen, ratio, mask)
+        else:
+            h = lib.cuddh_waveholtz_box_create_precision(float(omega), *args, scheme, coarsen, ratio, mask, self.PRECISIONS.index(precision))
         if not h and N.last_error().startswith("WaveHoltz error"):
             raise ValueError(f"WaveHoltzBox: {N.last_error()}")
         n = L[0] * L[1] * L[2]
@@ -1046,7 +1057,8 @@ class WaveHoltzBox(_Operator):
         buf = C.create_string_buffer(160)
         N.check_capi(lib.cuddh_waveholtz_box_info(self._h, _h(info), C.byref(dt), buf, 160), "WaveHoltzBox.info")
         return {"nt": int(info[0]), "dt": dt.value, "ratio": int(info[1]), "integrator": "rk4" if info[2] else "rk2", "coarsen": int(info[3]),
-                "sweeps_per_period": int(info[4]), "nodes": int(info[5]), "stiffness_kernel": buf.value.decode()}
+                "sweeps_per_period": int(info[4]), "nodes": int(info[5]), "stiffness_kernel": buf.value.decode(),
+                "precision": self.PRECISIONS[lib.cuddh_waveholtz_box_precision(self._h)]}
 
     def solve(self, f, u, m: int = 20, maxit: int = 200, tol: float = 1e-6, orth: str = "mgs", augment: int = 0) -> "SolverOut":
         """rhs -> gmres from zero -> solution; u receives [Re U; Im U]"""

@@ -26,7 +26,7 @@ namespace cuddh
             all_faces = 63
         };
 
-        cuddh_wave_box desc = {}; // what the kernels take: counts, stride (Lx rounded up to even), cx, cy, cz and the 1-D tables
+        cuddh_wave_box desc = {}; // what the kernels take: counts, stride (Lx rounded up to the row multiple), cx, cy, cz and the 1-D tables
         int Lx = 0, Ly = 0, Lz = 0;
         double hx = 0.0, hy = 0.0, hz = 0.0;
         // in public (unpadded lattice) order, Lx Ly Lz each: the lumped mass, the lumped mass of the absorbing faces,
@@ -43,10 +43,12 @@ namespace cuddh
     /// not finite), n_basis outside [2, 8], a face mask outside 6 bits, stride Ly Lz beyond an int, a coefficient that is not finite
     /// and positive.  box = {ax, bx, ay, by, az, bz}; h_a: Lx Ly Lz values in public order, or null for a == 1.  Refusals go through
     /// cuddh_error with a message that starts "WaveHoltz error: box:".  Returns min a.
-    double check_wave_box(int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, unsigned face_mask);
+    /// row_multiple: rows hold a multiple of this many elements, 2 (the fp64 sweeps: wave_box.hip) or 4 (the fp32 sweeps:
+    /// wave_box_f32.hip); anything else is refused, and stride is Lx rounded up to it.
+    double check_wave_box(int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, unsigned face_mask, int row_multiple = 2);
 
     /// the whole description (check_wave_box first)
-    WaveBox build_wave_box(int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, unsigned face_mask);
+    WaveBox build_wave_box(int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, unsigned face_mask, int row_multiple = 2);
 } // namespace cuddh
 
 #endif

@@ -6,7 +6,9 @@
 // W(z; f) = S z + W(0; f); its fixed point solves (I - S) z = W(0; f); U = u + i v / w.  Call sequence:
 //     W.rhs(f, b); gmres(W.size(), z, &W, b, m, maxit, tol); W.solution(z, u);
 // Public vectors hold 2 Lx Ly Lz doubles, node (I, J, K) at I + Lx (J + Ly K); all are DEVICE pointers unless marked HOST.
-// fp64 only, one launch per sweep, full boxes, beta == 1: the 2-D lattice form's other options have no 3-D counterpart yet.
+// precision = f32 stores and marches the lattice vectors in fp32 on csrc/kernels/wave_box_f32.hip; the public vectors,
+// action and solution stay double.  One launch per sweep, full boxes, beta == 1: the 2-D lattice form's other options (paired
+// launches, missing cells, a per-cell stiffness) have no 3-D counterpart yet.
 #ifndef CUDDH_AMD_WAVEHOLTZ_BOX_HPP
 #define CUDDH_AMD_WAVEHOLTZ_BOX_HPP
 
@@ -30,6 +32,16 @@ namespace cuddh
         static constexpr int from_coefficient = 0;
         /// the absorbing faces: bits of WaveBox::Face
         unsigned faces = WaveBox::all_faces;
+        /// f64 (the default) or f32: the lattice vectors, the stencil and the stages of the march in that precision.  With f32 a
+        /// period rounds z_in, f, invm and Hi to float once on the way in (cuddh_hip_wave32_load / _begin) and widens the result on
+        /// the way out (_store); rows of the padded lattice hold a multiple of four floats.  nt, dt and the ratio do not depend on it.
+        /// fp32 suits GMRES tolerances around 1e-4, not 1e-6.  Any other value is refused
+        /// ("WaveHoltz error: precision:").
+        enum Precision
+        {
+            f64,
+            f32
+        } precision = f64;
     };
 
     /// The period's grid a WaveHoltzBox of these arguments marches on, from host arithmetic alone (nothing is allocated): every
@@ -78,8 +90,10 @@ namespace cuddh
         int time_ratio() const { return ratio; }
         DDHIntegrator integrator() const { return scheme; }
         int sweeps_per_period() const { return nt * (scheme.scheme == DDHIntegrator::rk4 ? 4 : 2); }
-        /// "wave_box nb<n>", with " (run-time n_basis)" where n_basis is not a compile-time form of wave_box.hip
+        /// "wave_box nb<n>", with " f32" at that precision, then " (run-time n_basis)" where n_basis is not a compile-time form of
+        /// the kernel file (wave_box.hip: 4; wave_box_f32.hip: 4 and 5)
         std::string stiffness_kernel() const;
+        WaveHoltzBoxOptions::Precision precision() const { return f32 ? WaveHoltzBoxOptions::f32 : WaveHoltzBoxOptions::f64; }
 
     private:
         const double omega;
@@ -92,6 +106,10 @@ namespace cuddh
         host_device_ivec dof_of_slot, slot_of_dof;
         host_device_dvec invm, Hi; // 1 / (a^2 m) and h a in padded lattice order, zero in the padding
         mutable host_device_dvec p, q, u, v, ps, qs, ps2, aq, ap, F, G, tmp;
+        // precision = f32: the lattice vectors as floats (the double ones above, tmp apart, then stay empty)
+        bool f32 = false;
+        HostDeviceArray<float> invm32, Hi32;
+        mutable HostDeviceArray<float> p32, q32, u32, v32, ps32, qs32, ps2_32, aq32, ap32, F32, G32;
     };
 } // namespace cuddh
 

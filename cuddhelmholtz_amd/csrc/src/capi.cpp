@@ -745,11 +745,18 @@ extern "C"
     int cuddh_wave_box_describe(int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int face_mask, cuddh_wave_box *desc,
                                 int *h_dims, double *h_m, double *h_h, double *h_invm, double *h_Hi, int *h_dof_of_slot, int *h_slot_of_dof)
     {
+        return cuddh_wave_box_describe_rows(nx, ny, nz, h_box, n_basis, h_a, face_mask, 2, desc, h_dims, h_m, h_h, h_invm, h_Hi, h_dof_of_slot,
+                                            h_slot_of_dof);
+    }
+    int cuddh_wave_box_describe_rows(int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int face_mask, int row_multiple,
+                                     cuddh_wave_box *desc, int *h_dims, double *h_m, double *h_h, double *h_invm, double *h_Hi, int *h_dof_of_slot,
+                                     int *h_slot_of_dof)
+    {
         return guarded([&]
         {
             if (face_mask < 0)
                 throw std::runtime_error("WaveHoltz error: box: the face mask has six bits (x0, x1, y0, y1, z0, z1), not " + std::to_string(face_mask) + ".");
-            const WaveBox B = build_wave_box(nx, ny, nz, h_box, n_basis, h_a, static_cast<unsigned>(face_mask));
+            const WaveBox B = build_wave_box(nx, ny, nz, h_box, n_basis, h_a, static_cast<unsigned>(face_mask), row_multiple);
             if (desc)
                 *desc = B.desc;
             if (h_dims)
@@ -772,8 +779,10 @@ extern "C"
     namespace
     {
         // checked before anything else is looked at
-        WaveHoltzBoxOptions box_options(const double *h_a, int integrator, int coarsen, int time_ratio, int face_mask)
+        WaveHoltzBoxOptions box_options(const double *h_a, int integrator, int coarsen, int time_ratio, int face_mask, int precision = 0)
         {
+            if (precision != 0 && precision != 1)
+                throw std::runtime_error("WaveHoltz error: precision: the precision must be 0 (f64) or 1 (f32), not " + std::to_string(precision) + ".");
             if (integrator != 0 && integrator != 1)
                 throw std::runtime_error("WaveHoltz error: integrator: the scheme must be 0 (rk2) or 1 (rk4), not " + std::to_string(integrator) + ".");
             if (face_mask < 0)
@@ -784,6 +793,7 @@ extern "C"
             o.integrator = {integrator == 1 ? DDHIntegrator::rk4 : DDHIntegrator::rk2, coarsen};
             o.time_ratio = time_ratio;
             o.faces = static_cast<unsigned>(face_mask);
+            o.precision = precision == 1 ? WaveHoltzBoxOptions::f32 : WaveHoltzBoxOptions::f64;
             return o;
         }
     } // namespace
@@ -805,9 +815,14 @@ extern "C"
     void *cuddh_waveholtz_box_create(double omega, int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int integrator,
                                      int coarsen, int time_ratio, int face_mask)
     {
+        return cuddh_waveholtz_box_create_precision(omega, nx, ny, nz, h_box, n_basis, h_a, integrator, coarsen, time_ratio, face_mask, 0);
+    }
+    void *cuddh_waveholtz_box_create_precision(double omega, int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a,
+                                               int integrator, int coarsen, int time_ratio, int face_mask, int precision)
+    {
         return guarded_new<OpHandle>([&]
         {
-            const WaveHoltzBoxOptions o = box_options(h_a, integrator, coarsen, time_ratio, face_mask);
+            const WaveHoltzBoxOptions o = box_options(h_a, integrator, coarsen, time_ratio, face_mask, precision);
             auto h = new OpHandle;
             try
             {
@@ -859,6 +874,12 @@ extern "C"
     int cuddh_waveholtz_box_lattice(void *op, int *h_dims)
     {
         return guarded([&] { waveholtz_box_of(op).lattice(h_dims); });
+    }
+    int cuddh_waveholtz_box_precision(void *op)
+    {
+        int code = -1;
+        guarded([&] { code = waveholtz_box_of(op).precision() == WaveHoltzBoxOptions::f32 ? 1 : 0; });
+        return code;
     }
 
     int cuddh_helmholtz_read_stamps(void *op, unsigned long long *h_out, int n_patches)

@@ -27,7 +27,7 @@ namespace cuddh
         }
     } // namespace
 
-    double check_wave_box(int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, unsigned face_mask)
+    double check_wave_box(int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, unsigned face_mask, int row_multiple)
     {
         const int counts[3] = {nx, ny, nz};
         const char *axis[3] = {"x", "y", "z"};
@@ -44,7 +44,9 @@ namespace cuddh
             refuse("the box kernels take n_basis in [2, 8], not " + std::to_string(n_basis) + ".");
         if (face_mask > WaveBox::all_faces)
             refuse("the face mask has six bits (x0, x1, y0, y1, z0, z1), not " + std::to_string(face_mask) + ".");
-        const long long H = n_basis - 1, Lx = nx * H + 1, Ly = ny * H + 1, Lz = nz * H + 1, stride = (Lx + 1) / 2 * 2;
+        if (row_multiple != 2 && row_multiple != 4)
+            refuse("rows hold a multiple of 2 (fp64) or 4 (fp32) elements, not of " + std::to_string(row_multiple) + ".");
+        const long long H = n_basis - 1, Lx = nx * H + 1, Ly = ny * H + 1, Lz = nz * H + 1, stride = (Lx + row_multiple - 1) / row_multiple * row_multiple;
         if (Lx > 0x7fffffffLL || Ly > 0x7fffffffLL || Lz > 0x7fffffffLL || stride * Ly > 0x7fffffffLL || stride * Ly * Lz > 0x7fffffffLL)
             refuse("the padded lattice of " + std::to_string(stride) + " x " + std::to_string(Ly) + " x " + std::to_string(Lz) +
                    " slots does not fit in an int.");
@@ -63,9 +65,9 @@ namespace cuddh
         return a_min;
     }
 
-    WaveBox build_wave_box(int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, unsigned face_mask)
+    WaveBox build_wave_box(int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, unsigned face_mask, int row_multiple)
     {
-        check_wave_box(nx, ny, nz, box, n_basis, h_a, face_mask);
+        check_wave_box(nx, ny, nz, box, n_basis, h_a, face_mask, row_multiple);
         WaveBox B;
         const int nb = n_basis, H = nb - 1;
         B.Lx = nx * H + 1;
@@ -79,7 +81,7 @@ namespace cuddh
         B.desc.ny = ny;
         B.desc.nz = nz;
         B.desc.n_basis = nb;
-        B.desc.stride = (B.Lx + 1) / 2 * 2;
+        B.desc.stride = (B.Lx + row_multiple - 1) / row_multiple * row_multiple;
         B.desc.cx = hy * hz / (2.0 * hx);
         B.desc.cy = hx * hz / (2.0 * hy);
         B.desc.cz = hx * hy / (2.0 * hz);

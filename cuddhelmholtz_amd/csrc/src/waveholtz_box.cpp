@@ -1,6 +1,8 @@
 // Whole-domain WaveHoltz on a box of brick elements (cuddh/waveholtz_box.hpp): set-up on the host (cuddh/wave_box.hpp), the march
 // as the kernels of csrc/kernels/wave_box.hip (cuddh_hip_wave_box_*), one launch per sweep on padded lattice-ordered vectors.  The
 // schedule is the per-sweep one of the lattice form in waveholtz.cpp; a period goes in and out through that form's gathers.
+// With precision = f32 the same call sequence on csrc/kernels/wave_box_f32.hip (cuddh_hip_wave_box32_*), in and out through
+// cuddh_hip_wave32_load / _begin / _store.
 #include "cuddh/waveholtz_box.hpp"
 
 #include <algorithm>
@@ -31,15 +33,118 @@ namespace cuddh
                              std::to_string(DDHTimeStep::max_ratio) + "].").c_str());
             if (!std::isfinite(omega) || !(omega > 0.0))
                 cuddh_error("WaveHoltz error: omega must be finite and positive.");
+            if (o.precision != WaveHoltzBoxOptions::f64 && o.precision != WaveHoltzBoxOptions::f32)
+                cuddh_error("WaveHoltz error: precision: the precision must be f64 or f32.");
         }
 
+        /// rows of the fp32 sweeps hold a multiple of four floats (16 bytes), those of the fp64 sweeps of two doubles
+        int row_multiple(const WaveHoltzBoxOptions &o) { return o.precision == WaveHoltzBoxOptions::f32 ? 4 : 2; }
+
+        /// The two kernel families behind one set of names: R = double is cuddh_hip_wave_box_*_f64 between the lattice form's
+        /// fp64 gathers, R = float is cuddh_hip_wave_box32_* between cuddh_hip_wave32_load / _begin / _store.
+        template <typename R>
+        struct BoxKernels;
+        template <>
+        struct BoxKernels<double>
+        {
+            static constexpr auto load = cuddh_hip_wave_lattice_gather_f64;
+            static constexpr auto store = cuddh_hip_gather_f64;
+            static constexpr auto begin = cuddh_hip_wave_lattice_begin_f64;
+            static constexpr auto rk2_a = cuddh_hip_wave_box_rk2_a_f64;
+            static constexpr auto rk2_b = cuddh_hip_wave_box_rk2_b_f64;
+            static constexpr auto rk4_1 = cuddh_hip_wave_box_rk4_1_f64;
+            static constexpr auto rk4_2 = cuddh_hip_wave_box_rk4_2_f64;
+            static constexpr auto rk4_3 = cuddh_hip_wave_box_rk4_3_f64;
+            static constexpr auto rk4_4 = cuddh_hip_wave_box_rk4_4_f64;
+        };
+        template <>
+        struct BoxKernels<float>
+        {
+            static constexpr auto load = cuddh_hip_wave32_load;
+            static constexpr auto store = cuddh_hip_wave32_store;
+            static constexpr auto begin = cuddh_hip_wave32_begin;
+            static constexpr auto rk2_a = cuddh_hip_wave_box32_rk2_a;
+            static constexpr auto rk2_b = cuddh_hip_wave_box32_rk2_b;
+            static constexpr auto rk4_1 = cuddh_hip_wave_box32_rk4_1;
+            static constexpr auto rk4_2 = cuddh_hip_wave_box32_rk4_2;
+            static constexpr auto rk4_3 = cuddh_hip_wave_box32_rk4_3;
+            static constexpr auto rk4_4 = cuddh_hip_wave_box32_rk4_4;
+        };
+
+        /// the lattice vectors of one period (DEVICE); F, G null without a load; PS2, AQ, AP used by rk4 only
+        template <typename R>
+        struct BoxVectors
+        {
+            R *P, *Q, *U, *V, *PS, *QS, *PS2, *AQ, *AP, *F, *G;
+            const R *IM, *HI;
+        };
+
+        /// what a period reads besides its vectors
+        struct BoxGrid
+        {
+            const cuddh_wave_box *D;
+            int slots, ndof, nt;
+            bool rk4;
+            double dt;
+            const double *filt, *cs, *sn; // HOST
+            const int *dof_of_slot, *slot_of_dof;
+            void *stream;
+        };
+
+        template <typename R>
+        void box_march(const BoxGrid &g, const BoxVectors<R> &x, const double *z_in, const double *f, double *z_out)
+        {
+            using Kn = BoxKernels<R>;
+            const char *what = "WaveHoltzBox::period";
+            const int n = g.slots, ndof = g.ndof;
+            const cuddh_wave_box *D = g.D;
+            void *st = g.stream;
+            const double dt = g.dt, *filt = g.filt, *cs = g.cs, *sn = g.sn;
+            R *P = x.P, *Q = x.Q, *U = x.U, *V = x.V, *PS = x.PS, *QS = x.QS;
+            const R *IM = x.IM, *HI = x.HI, *Ff = nullptr, *Gf = nullptr;
+            if (f)
+            {
+                detail::check_hip(Kn::load(n, g.dof_of_slot, f, x.F, st), what);
+                detail::check_hip(Kn::load(n, g.dof_of_slot, f + ndof, x.G, st), what);
+                Ff = x.F;
+                Gf = x.G;
+            }
+            if (z_in)
+                detail::check_hip(Kn::begin(n, filt[0], g.dof_of_slot, z_in, z_in + ndof, P, Q, U, V, st), what);
+            else
+                for (R *y : {P, Q, U, V})
+                    zeros(n, y);
+
+            if (!g.rk4)
+            {
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    detail::check_hip(Kn::rk2_a(D, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
+                    detail::check_hip(Kn::rk2_b(D, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+                }
+            }
+            else
+            {
+                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2;
+                for (int it = 1; it <= g.nt; ++it)
+                {
+                    const int k = 2 * it - 2;
+                    detail::check_hip(Kn::rk4_1(D, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::rk4_2(D, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::rk4_3(D, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
+                    detail::check_hip(Kn::rk4_4(D, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
+                }
+            }
+            detail::check_hip(Kn::store(ndof, g.slot_of_dof, U, z_out, st), what);
+            detail::check_hip(Kn::store(ndof, g.slot_of_dof, V, z_out + ndof, st), what);
+        }
     } // namespace
 
     WaveBoxTimeGrid wave_box_time_grid(double omega, int nx, int ny, int nz, const double *box, int n_basis, const double *h_a,
                                        const WaveHoltzBoxOptions &o)
     {
         check_options(o, omega);
-        const double a_min = check_wave_box(nx, ny, nz, box, n_basis, h_a, o.faces);
+        const double a_min = check_wave_box(nx, ny, nz, box, n_basis, h_a, o.faces, row_multiple(o));
         int ratio = o.time_ratio;
         if (ratio == WaveHoltzBoxOptions::from_coefficient)
         {
@@ -57,11 +162,11 @@ namespace cuddh
     }
 
     WaveHoltzBox::WaveHoltzBox(double omega_, int nx, int ny, int nz, const double *box, int n_basis, const double *h_a, const WaveHoltzBoxOptions &o)
-        : omega(omega_), scheme(o.integrator)
+        : omega(omega_), scheme(o.integrator), f32(o.precision == WaveHoltzBoxOptions::f32)
     {
         // everything that is refused, before anything is allocated
         const WaveBoxTimeGrid grid = wave_box_time_grid(omega, nx, ny, nz, box, n_basis, h_a, o);
-        geo = build_wave_box(nx, ny, nz, box, n_basis, h_a, o.faces);
+        geo = build_wave_box(nx, ny, nz, box, n_basis, h_a, o.faces, row_multiple(o));
         ndof = geo.nodes();
         slots = geo.slots();
 
@@ -79,6 +184,30 @@ namespace cuddh
         slot_of_dof.resize(ndof);
         std::copy(geo.dof_of_slot.begin(), geo.dof_of_slot.end(), dof_of_slot.host_write());
         std::copy(geo.slot_of_dof.begin(), geo.slot_of_dof.end(), slot_of_dof.host_write());
+        const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
+        if (f32)
+        {
+            // invm and Hi, formed in double, into lattice order as floats, each rounded once; the padding slots get zero.  The
+            // class's double lattice vectors are not allocated.
+            const int *dos = dof_of_slot.device_read();
+            slot_of_dof.device_read();
+            invm32.resize(slots);
+            Hi32.resize(slots);
+            host_device_dvec t(ndof);
+            for (const auto &x : {std::make_pair(&geo.invm, &invm32), std::make_pair(&geo.Hi, &Hi32)})
+            {
+                std::copy(x.first->begin(), x.first->end(), t.host_write());
+                detail::check_hip(cuddh_hip_wave32_load(slots, dos, t.device_read(), x.second->device_write(), stream()), "WaveHoltzBox lattice order");
+                detail::check_hip(cuddh_hip_stream_sync(stream()), "WaveHoltzBox setup"); // t is overwritten, then dies
+            }
+            for (HostDeviceArray<float> *x : {&p32, &q32, &u32, &v32, &ps32, &qs32})
+                x->resize(slots);
+            if (rk4)
+                for (HostDeviceArray<float> *x : {&ps2_32, &aq32, &ap32})
+                    x->resize(slots);
+            tmp.resize(2 * ndof);
+            return;
+        }
         invm.resize(slots);
         Hi.resize(slots);
         {
@@ -96,7 +225,6 @@ namespace cuddh
         dof_of_slot.device_read();
         slot_of_dof.device_read();
 
-        const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
         for (host_device_dvec *x : {&p, &q, &u, &v, &ps, &qs})
             x->resize(slots);
         if (rk4)
@@ -117,60 +245,39 @@ namespace cuddh
     std::string WaveHoltzBox::stiffness_kernel() const
     {
         const int nb = geo.desc.n_basis;
+        if (f32)
+            return "wave_box nb" + std::to_string(nb) + " f32" + (nb == 4 || nb == 5 ? "" : " (run-time n_basis)");
         return "wave_box nb" + std::to_string(nb) + (nb == 4 ? "" : " (run-time n_basis)");
     }
 
     void WaveHoltzBox::period(const double *z_in, const double *f, double *z_out) const
     {
-        const char *what = "WaveHoltzBox::period";
         const int n = slots;
-        const cuddh_wave_box *D = &geo.desc;
-        void *st = stream();
-        const int *dos = dof_of_slot.device_read(), *sod = slot_of_dof.device_read();
-        double *P = p.device_write(), *Q = q.device_write(), *U = u.device_write(), *V = v.device_write();
-        double *PS = ps.device_write(), *QS = qs.device_write();
-        const double *IM = invm.device_read(), *HI = Hi.device_read(), *Ff = nullptr, *Gf = nullptr;
-        if (f)
+        const bool rk4 = scheme.scheme == DDHIntegrator::rk4;
+        const BoxGrid g = {&geo.desc, n, ndof, nt, rk4, dt, filt.data(), cs.data(), sn.data(), dof_of_slot.device_read(), slot_of_dof.device_read(), stream()};
+        if (f32)
         {
-            if (F.size() != n)
+            if (f && F32.size() != n)
             {
-                F.resize(n);
-                G.resize(n);
+                F32.resize(n);
+                G32.resize(n);
             }
-            double *dF = F.device_write(), *dG = G.device_write();
-            detail::check_hip(cuddh_hip_wave_lattice_gather_f64(n, dos, f, dF, st), what);
-            detail::check_hip(cuddh_hip_wave_lattice_gather_f64(n, dos, f + ndof, dG, st), what);
-            Ff = dF;
-            Gf = dG;
+            const BoxVectors<float> x = {p32.device_write(), q32.device_write(), u32.device_write(), v32.device_write(), ps32.device_write(),
+                                         qs32.device_write(), rk4 ? ps2_32.device_write() : nullptr, rk4 ? aq32.device_write() : nullptr,
+                                         rk4 ? ap32.device_write() : nullptr, f ? F32.device_write() : nullptr, f ? G32.device_write() : nullptr,
+                                         invm32.device_read(), Hi32.device_read()};
+            return box_march(g, x, z_in, f, z_out);
         }
-        if (z_in)
-            detail::check_hip(cuddh_hip_wave_lattice_begin_f64(n, filt[0], dos, z_in, z_in + ndof, P, Q, U, V, st), what);
-        else
-            for (double *y : {P, Q, U, V})
-                zeros(n, y);
-
-        if (scheme.scheme == DDHIntegrator::rk2)
+        if (f && F.size() != n)
         {
-            for (int it = 1; it <= nt; ++it)
-            {
-                detail::check_hip(cuddh_hip_wave_box_rk2_a_f64(D, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
-                detail::check_hip(cuddh_hip_wave_box_rk2_b_f64(D, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-            }
+            F.resize(n);
+            G.resize(n);
         }
-        else
-        {
-            double *AQ = aq.device_write(), *AP = ap.device_write(), *PS2 = ps2.device_write();
-            for (int it = 1; it <= nt; ++it)
-            {
-                const int k = 2 * it - 2;
-                detail::check_hip(cuddh_hip_wave_box_rk4_1_f64(D, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                detail::check_hip(cuddh_hip_wave_box_rk4_2_f64(D, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
-                detail::check_hip(cuddh_hip_wave_box_rk4_3_f64(D, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                detail::check_hip(cuddh_hip_wave_box_rk4_4_f64(D, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-            }
-        }
-        detail::check_hip(cuddh_hip_gather_f64(ndof, sod, U, z_out, st), what);
-        detail::check_hip(cuddh_hip_gather_f64(ndof, sod, V, z_out + ndof, st), what);
+        const BoxVectors<double> x = {p.device_write(), q.device_write(), u.device_write(), v.device_write(), ps.device_write(),
+                                      qs.device_write(), rk4 ? ps2.device_write() : nullptr, rk4 ? aq.device_write() : nullptr,
+                                      rk4 ? ap.device_write() : nullptr, f ? F.device_write() : nullptr, f ? G.device_write() : nullptr,
+                                      invm.device_read(), Hi.device_read()};
+        box_march(g, x, z_in, f, z_out);
     }
 
     void WaveHoltzBox::solution(const double *z, double *out) const

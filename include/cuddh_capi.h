@@ -435,6 +435,16 @@ int cuddh_waveholtz_box_solution(void *op, const double *z, double *u);
 int cuddh_waveholtz_box_info(void *op, int *h_info, double *h_dt, char *kernel, int cap);
 /* h_dims = {Lx, Ly, Lz} */
 int cuddh_waveholtz_box_lattice(void *op, int *h_dims);
+/* cuddh_waveholtz_box_create with the precision of the march: 0 = f64, which is cuddh_waveholtz_box_create itself,
+ * 1 = f32: the lattice vectors, the stencil and the stages in fp32 on the kernels cuddh_hip_wave_box32_*, rows of the padded lattice
+ * a multiple of four floats; z_in, f, invm and Hi are rounded to float once on the way in, every vector of this interface, the
+ * action y = x - S x and the solution stay double.  The period's grid does not depend on it.  fp32 suits GMRES tolerances around
+ * 1e-4, not 1e-6.  The kernel is then "wave_box nb<n_basis> f32", followed by " (run-time n_basis)" for n_basis other than 4 and 5.
+ * Any other code is refused like the rest (NULL, "WaveHoltz error: precision:"). */
+void *cuddh_waveholtz_box_create_precision(double omega, int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a,
+                                           int integrator, int coarsen, int time_ratio, int face_mask, int precision);
+/* 0 (f64) or 1 (f32); -1 with cuddh_last_error() for a handle that is no such operator */
+int cuddh_waveholtz_box_precision(void *op);
 
 #ifdef __cplusplus
 }

@@ -948,6 +948,49 @@ int cuddh_hip_wave_box_tile_z(void);
  * stride * Ly * Lz beyond an int return nonzero with cuddh_last_error() beginning "WaveHoltz error: box:" and nothing written. */
 int cuddh_wave_box_describe(int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int face_mask, cuddh_wave_box *desc,
                             int *h_dims, double *h_m, double *h_h, double *h_invm, double *h_Hi, int *h_dof_of_slot, int *h_slot_of_dof);
+/* cuddh_wave_box_describe with rows of a multiple of `row_multiple` elements: 2 (the call above, array for array) or 4 (the fp32
+ * sweeps below: stride = Lx rounded up to a multiple of four).  The stride enters desc, h_dims[3], the two slot maps and the int
+ * check; h_m, h_h, h_invm and h_Hi do not depend on it.  Any other row_multiple is refused like the rest ("WaveHoltz error: box:",
+ * nothing written). */
+int cuddh_wave_box_describe_rows(int nx, int ny, int nz, const double *h_box, int n_basis, const double *h_a, int face_mask, int row_multiple,
+                                 cuddh_wave_box *desc, int *h_dims, double *h_m, double *h_h, double *h_invm, double *h_Hi, int *h_dof_of_slot,
+                                 int *h_slot_of_dof);
+
+/* ------------------------------------------------------------------ the box sweeps in fp32
+ * csrc/kernels/wave_box_f32.hip, DESIGN 4.5.7.  The six entry points above with float vectors: the same description, the same
+ * stencil and stage arithmetic statement for statement in float (every product-sum an fmaf, sx, sy, sz each from zero over the
+ * ascending offsets, ax, ay, az with each product rounded, the inner first, (K p') = fmaf(ax, sx, fmaf(ay, sy, az * sz))), the
+ * scalars still double.  The tables built in double from A and w, cx, cy, cz and every scalar of the call are rounded to float
+ * once on the host, as for cuddh_hip_wave32_*.  Results depend on (I, J, K) alone: bitwise reproducible, and the forced form with
+ * F = G = 0 gives the homogeneous bits.
+ * Vectors hold node (I, J, K) at I + stride (J + Ly K) and have stride * Ly * Lz floats (which must fit in an int); stride >= Lx
+ * and a MULTIPLE OF 4, every pointer 16-byte aligned, so every row and plane starts on a 16-byte boundary.  The up to three
+ * columns from Lx on are padding: zero state, zero load and invm = 0, kept zero by the kernels and never used by the stencil.
+ * Vectors enter and leave this layout through cuddh_hip_wave32_load / _begin / _store.
+ * A bad description (NULL, a count < 1, n_basis outside [2, 8], stride < Lx or no multiple of 4, stride * Ly * Lz beyond an int), a
+ * misaligned or NULL pointer, F without G or an output that is the stencil's input return hipErrorInvalidValue (1) and nothing is
+ * launched. */
+int cuddh_hip_wave_box32_rk2_a(const cuddh_wave_box *box, double half_dt, double c, double s, const float *p, const float *q,
+                               const float *invm, const float *Hi, const float *F, const float *G, float *qh, float *ph, void *stream);
+int cuddh_hip_wave_box32_rk2_b(const cuddh_wave_box *box, double dt, double c, double s, double filt, const float *ph, const float *qh,
+                               const float *invm, const float *Hi, const float *F, const float *G, float *p, float *q, float *u, float *v,
+                               void *stream);
+int cuddh_hip_wave_box32_rk4_1(const cuddh_wave_box *box, double half_dt, double c, double s, const float *p, const float *q,
+                               const float *invm, const float *Hi, const float *F, const float *G, float *ps, float *qs, float *aq, float *ap,
+                               void *stream);
+int cuddh_hip_wave_box32_rk4_2(const cuddh_wave_box *box, double half_dt, double c, double s, const float *ps_in, const float *p,
+                               const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
+                               float *aq, float *ap, void *stream);
+int cuddh_hip_wave_box32_rk4_3(const cuddh_wave_box *box, double dt, double c, double s, const float *ps_in, const float *p,
+                               const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
+                               float *aq, float *ap, void *stream);
+int cuddh_hip_wave_box32_rk4_4(const cuddh_wave_box *box, double sixth_dt, double c, double s, double filt, const float *ps,
+                               const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi, const float *F,
+                               const float *G, float *p, float *q, float *u, float *v, void *stream);
+/* nodes of a workgroup's tile in x, y and z */
+int cuddh_hip_wave_box32_tile_x(void);
+int cuddh_hip_wave_box32_tile_y(void);
+int cuddh_hip_wave_box32_tile_z(void);
 
 #ifdef __cplusplus
 }
