@@ -112,7 +112,7 @@ def _compile(src: Path, as_hip: bool, headers_mtime: float, verbose: bool) -> Pa
 def build_native(verbose: bool = False, jobs: int = 6) -> Path:
     OBJ_DIR.mkdir(parents=True, exist_ok=True)
     LIB_DIR.mkdir(parents=True, exist_ok=True)
-    headers = [p for d in INCLUDES for p in d.rglob("*.h*")]
+    headers = [p for d in (*INCLUDES, CSRC / "src") for p in d.rglob("*.h*")]  # (csrc/src holds internal headers)
     headers_mtime = max(p.stat().st_mtime for p in headers)
     hip, cpp = _sources()
     work = [(s, True) for s in hip] + [(s, s.name in HIP_HOST_SOURCES) for s in cpp]

@@ -28,8 +28,10 @@
 // n_basis 4 is compile-time: its z loads are all issued before the first is used.  Every other n_basis in [2, 8] shares an
 // instantiation whose x and y loops have run-time bounds over LDS and whose z loop has a run-time length (no register arrays,
 // hence no scratch).
+// The host side below is the family's launcher only (description, extra argument, grid, compile-time n_basis list); the stage
+// arguments and their refusals, the dispatch and the six wirings of the entry points are wave_sweep_launch.hpp's.
 #include "wave_lattice_common.hpp"
-#include "wave_stages.hpp"
+#include "wave_sweep_launch.hpp"
 
 #include "cuddh_hip.h"
 
@@ -43,12 +45,7 @@ namespace
     constexpr int ROWS_PER_WAVE = TY / WAVES, UNROLL = 2;
     static_assert(TX == 2 * WAVE && ROWS_PER_WAVE % UNROLL == 0, "a lane owns two columns; rows go in pairs");
 
-    struct Box
-    {
-        LatticeT<double> L; // one plane: Lx, Ly, stride, nb, cx, cy and the tables
-        int Lz;
-        double cz;
-    };
+    using Box = BoxT<double>; // (wave_lattice_common.hpp)
 
     template <int NBT>
     struct Lds
@@ -210,85 +207,31 @@ namespace
         }
     }
 
-    constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
-
-    // the kernel's view of the caller's description, or false
-    bool describe_box(const cuddh_wave_box *D, Box &B)
+    // the family's launcher (wave_sweep_launch.hpp): one sweep on the entry points' leading arguments
+    struct launch_box
     {
-        if (!D || D->nz < 1)
-            return false;
-        cuddh_wave_lattice P = {};
-        P.nx = D->nx;
-        P.ny = D->ny;
-        P.n_basis = D->n_basis;
-        P.stride = D->stride;
-        P.cx = D->cx;
-        P.cy = D->cy;
-        for (int i = 0; i < 64; ++i)
-            P.A[i] = D->A[i];
-        for (int i = 0; i < 8; ++i)
-            P.w[i] = D->w[i];
-        if (!describe(&P, 2, B.L))
-            return false;
-        const long long Lz = static_cast<long long>(D->nz) * (D->n_basis - 1) + 1;
-        if (static_cast<long long>(B.L.stride) * B.L.Ly * Lz > 0x7fffffffLL)
-            return false;
-        B.Lz = static_cast<int>(Lz);
-        B.cz = D->cz;
-        return true;
-    }
+        const cuddh_wave_box *D;
+        void *stream;
 
-    // in[0]: the stencil input; F, G: both given (forced) or both null (homogeneous)
-    template <typename Stage, int PSLOT>
-    int launch_box(const cuddh_wave_box *D, const double *const (&in)[Stage::NIN], const double *F, const double *G,
-                   double *const (&out)[Stage::NOUT], const double (&coef)[MAX_COEF], void *stream)
-    {
-        Box B;
-        if (!describe_box(D, B) || (F == nullptr) != (G == nullptr))
-            return invalid_value;
-        const bool forced = F != nullptr;
-        StageArgs a = {};
-        bool ok = true;
-        for (int s = 0; s < Stage::NIN; ++s)
+        template <typename Stage, int PSLOT>
+        int sweep(const double *const (&in)[Stage::NIN], const double *F, const double *G, double *const (&out)[Stage::NOUT],
+                  const double (&coef)[MAX_COEF]) const
         {
-            a.in[s] = in[s];
-            ok = ok && in[s] && aligned16(in[s]);
+            Box B;
+            StageArgs a;
+            if (!describe_box(D, 2, B) || !stage_args<Stage>(in, F, G, out, coef, a))
+                return invalid_value;
+            const long long tiles = static_cast<long long>((B.L.stride + TX - 1) / TX) * ((B.L.Ly + TY - 1) / TY) * B.Lz;
+            if (tiles > 0x7fffffffLL)
+                return invalid_value;
+            const int grid = static_cast<int>(tiles);
+            dispatch_sweep(B.L.nb, NBasis<4>{}, F != nullptr, static_cast<long long>(B.L.stride) * B.L.Ly * B.Lz * sizeof(double),
+                           [&](auto forced_c, auto nt_c, auto nbt)
+                           { hipLaunchKernelGGL((box_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
+                                                dim3(grid), dim3(BLOCK), 0, as_stream(stream), B, a); });
+            return launch_status();
         }
-        if (forced)
-        {
-            a.in[Stage::NIN] = F;
-            a.in[Stage::NIN + 1] = G;
-            ok = ok && aligned16(F) && aligned16(G);
-        }
-        for (int s = 0; s < Stage::NOUT; ++s)
-        {
-            a.out[s] = out[s];
-            // a neighbour's thread still needs the stencil input: it is not an output
-            ok = ok && out[s] && aligned16(out[s]) && out[s] != in[0];
-        }
-        if (!ok)
-            return invalid_value;
-        for (int s = 0; s < MAX_COEF; ++s)
-            a.coef[s] = coef[s];
-        const long long n = static_cast<long long>(B.L.stride) * B.L.Ly * B.Lz;
-        const long long tiles = static_cast<long long>((B.L.stride + TX - 1) / TX) * ((B.L.Ly + TY - 1) / TY) * B.Lz;
-        if (tiles > 0x7fffffffLL)
-            return invalid_value;
-        const int grid = static_cast<int>(tiles);
-        const bool nt = n * static_cast<long long>(sizeof(double)) >= NT_BYTES;
-        auto go = [&](auto nbt)
-        {
-            with_flags([&](auto forced_c, auto nt_c)
-                       { hipLaunchKernelGGL((box_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
-                                            dim3(grid), dim3(BLOCK), 0, as_stream(stream), B, a); },
-                       forced, nt);
-        };
-        if (B.L.nb == 4)
-            go(std::integral_constant<int, 4>{});
-        else
-            go(std::integral_constant<int, 0>{});
-        return launch_status();
-    }
+    };
 } // namespace
 
 extern "C"
@@ -300,41 +243,41 @@ extern "C"
     int cuddh_hip_wave_box_rk2_a_f64(const cuddh_wave_box *box, double half_dt, double c, double s, const double *p, const double *q,
                                      const double *invm, const double *Hi, const double *F, const double *G, double *qh, double *ph, void *stream)
     {
-        return launch_box<Rk2A, 1>(box, {p, p, q, invm, Hi}, F, G, {qh, ph}, {half_dt, c, s, 0.0}, stream);
+        return rk2_a(launch_box{box, stream}, half_dt, c, s, p, q, invm, Hi, F, G, qh, ph);
     }
 
     int cuddh_hip_wave_box_rk2_b_f64(const cuddh_wave_box *box, double dt, double c, double s, double filt, const double *ph, const double *qh,
                                      const double *invm, const double *Hi, const double *F, const double *G, double *p, double *q, double *u,
                                      double *v, void *stream)
     {
-        return launch_box<Rk2B, 0>(box, {ph, qh, p, q, u, v, invm, Hi}, F, G, {p, q, u, v}, {dt, c, s, filt}, stream);
+        return rk2_b(launch_box{box, stream}, dt, c, s, filt, ph, qh, invm, Hi, F, G, p, q, u, v);
     }
 
     int cuddh_hip_wave_box_rk4_1_f64(const cuddh_wave_box *box, double half_dt, double c, double s, const double *p, const double *q,
                                      const double *invm, const double *Hi, const double *F, const double *G, double *ps, double *qs, double *aq,
                                      double *ap, void *stream)
     {
-        return launch_box<Rk4First, 1>(box, {p, p, q, invm, Hi}, F, G, {ps, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_1(launch_box{box, stream}, half_dt, c, s, p, q, invm, Hi, F, G, ps, qs, aq, ap);
     }
 
     int cuddh_hip_wave_box_rk4_2_f64(const cuddh_wave_box *box, double half_dt, double c, double s, const double *ps_in, const double *p,
                                      const double *q, const double *invm, const double *Hi, const double *F, const double *G, double *ps_out,
                                      double *qs, double *aq, double *ap, void *stream)
     {
-        return launch_box<Rk4Mid, 0>(box, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_2(launch_box{box, stream}, half_dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_box_rk4_3_f64(const cuddh_wave_box *box, double dt, double c, double s, const double *ps_in, const double *p,
                                      const double *q, const double *invm, const double *Hi, const double *F, const double *G, double *ps_out,
                                      double *qs, double *aq, double *ap, void *stream)
     {
-        return launch_box<Rk4Mid, 0>(box, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {dt, c, s, 0.0}, stream);
+        return rk4_3(launch_box{box, stream}, dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_box_rk4_4_f64(const cuddh_wave_box *box, double sixth_dt, double c, double s, double filt, const double *ps,
                                      const double *qs, const double *aq, const double *ap, const double *invm, const double *Hi, const double *F,
                                      const double *G, double *p, double *q, double *u, double *v, void *stream)
     {
-        return launch_box<Rk4Last, 0>(box, {ps, p, q, qs, aq, ap, u, v, invm, Hi}, F, G, {p, q, u, v}, {sixth_dt, c, s, filt}, stream);
+        return rk4_4(launch_box{box, stream}, sixth_dt, c, s, filt, ps, qs, aq, ap, invm, Hi, F, G, p, q, u, v);
     }
 }

@@ -21,8 +21,10 @@
 // L2.  n_basis 4 and 5 are compile-time: all z loads of both passes are issued, clamped, together with the streams, before the
 // first is used.  Every other n_basis in [2, 8] shares an instantiation whose loops have run-time bounds over LDS and whose z
 // loop has a run-time length (no register arrays, hence no scratch).  Streams are non-temporal from 64 MB per vector.
+// The host side below is the family's launcher only (description, extra argument, grid, compile-time n_basis list); the stage
+// arguments and their refusals, the dispatch and the six wirings of the entry points are wave_sweep_launch.hpp's.
 #include "wave_lattice_common.hpp"
-#include "wave_stages.hpp"
+#include "wave_sweep_launch.hpp"
 
 #include "cuddh_hip.h"
 
@@ -40,19 +42,9 @@ namespace
 
     using V4 = float __attribute__((ext_vector_type(4)));
 
-    struct Box32
-    {
-        LatticeT<float> L; // one plane: Lx, Ly, stride, nb, cx, cy and the tables
-        int Lz;
-        float cz;
-    };
+    using Box32 = BoxT<float>; // (wave_lattice_common.hpp)
 
-    struct StageArgs32
-    {
-        const float *in[MAX_IN];
-        float *out[MAX_OUT]; // may alias inputs other than in[0] (element i is read before it is written, by the same thread)
-        float coef[MAX_COEF];
-    };
+    using StageArgs32 = StageArgsT<float>;
 
     // PSLOT > 0: input PSLOT of the stage is the stencil input itself
     template <typename Stage, int PSLOT, bool FORCED, bool NT, int NBT>
@@ -254,87 +246,31 @@ namespace
         }
     }
 
-    constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
-
-    // the kernel's view of the caller's description, or false
-    bool describe_box32(const cuddh_wave_box *D, Box32 &B)
+    // the family's launcher (wave_sweep_launch.hpp): one sweep on the entry points' leading arguments
+    struct launch_box32
     {
-        if (!D || D->nz < 1)
-            return false;
-        cuddh_wave_lattice P = {};
-        P.nx = D->nx;
-        P.ny = D->ny;
-        P.n_basis = D->n_basis;
-        P.stride = D->stride;
-        P.cx = D->cx;
-        P.cy = D->cy;
-        for (int i = 0; i < 64; ++i)
-            P.A[i] = D->A[i];
-        for (int i = 0; i < 8; ++i)
-            P.w[i] = D->w[i];
-        if (!describe(&P, COLS, B.L))
-            return false;
-        const long long Lz = static_cast<long long>(D->nz) * (D->n_basis - 1) + 1;
-        if (static_cast<long long>(B.L.stride) * B.L.Ly * Lz > 0x7fffffffLL)
-            return false;
-        B.Lz = static_cast<int>(Lz);
-        B.cz = static_cast<float>(D->cz);
-        return true;
-    }
+        const cuddh_wave_box *D;
+        void *stream;
 
-    // in[0]: the stencil input; F, G: both given (forced) or both null (homogeneous); coef: the call's scalars, rounded here
-    template <typename Stage, int PSLOT>
-    int launch_box32(const cuddh_wave_box *D, const float *const (&in)[Stage::NIN], const float *F, const float *G,
-                     float *const (&out)[Stage::NOUT], const double (&coef)[MAX_COEF], void *stream)
-    {
-        Box32 B;
-        if (!describe_box32(D, B) || (F == nullptr) != (G == nullptr))
-            return invalid_value;
-        const bool forced = F != nullptr;
-        StageArgs32 a = {};
-        bool ok = true;
-        for (int s = 0; s < Stage::NIN; ++s)
+        template <typename Stage, int PSLOT>
+        int sweep(const float *const (&in)[Stage::NIN], const float *F, const float *G, float *const (&out)[Stage::NOUT],
+                  const double (&coef)[MAX_COEF]) const
         {
-            a.in[s] = in[s];
-            ok = ok && in[s] && aligned16(in[s]);
+            Box32 B;
+            StageArgs32 a;
+            if (!describe_box(D, COLS, B) || !stage_args<Stage>(in, F, G, out, coef, a))
+                return invalid_value;
+            const long long tiles = static_cast<long long>((B.L.stride + TX - 1) / TX) * ((B.L.Ly + TY - 1) / TY) * B.Lz;
+            if (tiles > 0x7fffffffLL)
+                return invalid_value;
+            const int grid = static_cast<int>(tiles);
+            dispatch_sweep(B.L.nb, NBasis<4, 5>{}, F != nullptr, static_cast<long long>(B.L.stride) * B.L.Ly * B.Lz * sizeof(float),
+                           [&](auto forced_c, auto nt_c, auto nbt)
+                           { hipLaunchKernelGGL((box32_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
+                                                dim3(grid), dim3(BLOCK), 0, as_stream(stream), B, a); });
+            return launch_status();
         }
-        if (forced)
-        {
-            a.in[Stage::NIN] = F;
-            a.in[Stage::NIN + 1] = G;
-            ok = ok && aligned16(F) && aligned16(G);
-        }
-        for (int s = 0; s < Stage::NOUT; ++s)
-        {
-            a.out[s] = out[s];
-            // a neighbour's thread still needs the stencil input: it is not an output
-            ok = ok && out[s] && aligned16(out[s]) && out[s] != in[0];
-        }
-        if (!ok)
-            return invalid_value;
-        for (int s = 0; s < MAX_COEF; ++s)
-            a.coef[s] = static_cast<float>(coef[s]);
-        const long long n = static_cast<long long>(B.L.stride) * B.L.Ly * B.Lz;
-        const long long tiles = static_cast<long long>((B.L.stride + TX - 1) / TX) * ((B.L.Ly + TY - 1) / TY) * B.Lz;
-        if (tiles > 0x7fffffffLL)
-            return invalid_value;
-        const int grid = static_cast<int>(tiles);
-        const bool nt = n * static_cast<long long>(sizeof(float)) >= NT_BYTES;
-        auto go = [&](auto nbt)
-        {
-            with_flags([&](auto forced_c, auto nt_c)
-                       { hipLaunchKernelGGL((box32_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
-                                            dim3(grid), dim3(BLOCK), 0, as_stream(stream), B, a); },
-                       forced, nt);
-        };
-        if (B.L.nb == 4)
-            go(std::integral_constant<int, 4>{});
-        else if (B.L.nb == 5)
-            go(std::integral_constant<int, 5>{});
-        else
-            go(std::integral_constant<int, 0>{});
-        return launch_status();
-    }
+    };
 } // namespace
 
 extern "C"
@@ -346,41 +282,41 @@ extern "C"
     int cuddh_hip_wave_box32_rk2_a(const cuddh_wave_box *box, double half_dt, double c, double s, const float *p, const float *q,
                                    const float *invm, const float *Hi, const float *F, const float *G, float *qh, float *ph, void *stream)
     {
-        return launch_box32<Rk2AT<float>, 1>(box, {p, p, q, invm, Hi}, F, G, {qh, ph}, {half_dt, c, s, 0.0}, stream);
+        return rk2_a(launch_box32{box, stream}, half_dt, c, s, p, q, invm, Hi, F, G, qh, ph);
     }
 
     int cuddh_hip_wave_box32_rk2_b(const cuddh_wave_box *box, double dt, double c, double s, double filt, const float *ph, const float *qh,
                                    const float *invm, const float *Hi, const float *F, const float *G, float *p, float *q, float *u, float *v,
                                    void *stream)
     {
-        return launch_box32<Rk2BT<float>, 0>(box, {ph, qh, p, q, u, v, invm, Hi}, F, G, {p, q, u, v}, {dt, c, s, filt}, stream);
+        return rk2_b(launch_box32{box, stream}, dt, c, s, filt, ph, qh, invm, Hi, F, G, p, q, u, v);
     }
 
     int cuddh_hip_wave_box32_rk4_1(const cuddh_wave_box *box, double half_dt, double c, double s, const float *p, const float *q,
                                    const float *invm, const float *Hi, const float *F, const float *G, float *ps, float *qs, float *aq, float *ap,
                                    void *stream)
     {
-        return launch_box32<Rk4FirstT<float>, 1>(box, {p, p, q, invm, Hi}, F, G, {ps, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_1(launch_box32{box, stream}, half_dt, c, s, p, q, invm, Hi, F, G, ps, qs, aq, ap);
     }
 
     int cuddh_hip_wave_box32_rk4_2(const cuddh_wave_box *box, double half_dt, double c, double s, const float *ps_in, const float *p,
                                    const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
                                    float *aq, float *ap, void *stream)
     {
-        return launch_box32<Rk4MidT<float>, 0>(box, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_2(launch_box32{box, stream}, half_dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_box32_rk4_3(const cuddh_wave_box *box, double dt, double c, double s, const float *ps_in, const float *p,
                                    const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
                                    float *aq, float *ap, void *stream)
     {
-        return launch_box32<Rk4MidT<float>, 0>(box, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {dt, c, s, 0.0}, stream);
+        return rk4_3(launch_box32{box, stream}, dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_box32_rk4_4(const cuddh_wave_box *box, double sixth_dt, double c, double s, double filt, const float *ps,
                                    const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi, const float *F,
                                    const float *G, float *p, float *q, float *u, float *v, void *stream)
     {
-        return launch_box32<Rk4LastT<float>, 0>(box, {ps, p, q, qs, aq, ap, u, v, invm, Hi}, F, G, {p, q, u, v}, {sixth_dt, c, s, filt}, stream);
+        return rk4_4(launch_box32{box, stream}, sixth_dt, c, s, filt, ps, qs, aq, ap, invm, Hi, F, G, p, q, u, v);
     }
 }

@@ -28,8 +28,10 @@
 // round robin over eight) gets a contiguous run of tiles, whose halos then meet in that XCD's L2.
 // n_basis 4 and 5 are compile-time; every other n_basis in [2, 8] shares an instantiation with loops of run-time length over
 // LDS (no register arrays, hence no scratch).
+// The host side below is the family's launcher only (description, extra argument, grid, compile-time n_basis list); the stage
+// arguments and their refusals, the dispatch and the six wirings of the entry points are wave_sweep_launch.hpp's.
 #include "wave_lattice_common.hpp"
-#include "wave_stages.hpp"
+#include "wave_sweep_launch.hpp"
 
 #include "cuddh_hip.h"
 
@@ -158,84 +160,28 @@ namespace
         }
     }
 
-    // (the lattice vectors of one period come in through these two; padding slots carry dof -1)
-    __global__ void __launch_bounds__(BLOCK) gather_kernel(int n, const int *__restrict__ dof, const double *__restrict__ x, double *__restrict__ y)
+    // the family's launcher (wave_sweep_launch.hpp): one sweep on the entry points' leading arguments
+    struct launch_lattice
     {
-        for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-        {
-            const int g = dof[i];
-            y[i] = g >= 0 ? x[g] : 0.0;
-        }
-    }
-    __global__ void __launch_bounds__(BLOCK) begin_kernel(int n, double filt0, const int *__restrict__ dof, const double *__restrict__ zu,
-                                                          const double *__restrict__ zv, double *__restrict__ p, double *__restrict__ q,
-                                                          double *__restrict__ u, double *__restrict__ v)
-    {
-        for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-        {
-            const int g = dof[i];
-            const double xe[2] = {g >= 0 ? zu[g] : 0.0, g >= 0 ? zv[g] : 0.0};
-            double ye[4];
-            Begin::apply<false>(xe, ye, &filt0);
-            p[i] = ye[0];
-            q[i] = ye[1];
-            u[i] = ye[2];
-            v[i] = ye[3];
-        }
-    }
+        const cuddh_wave_lattice *D;
+        void *stream;
 
-    constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
-
-    // in[0]: the stencil input; F, G: both given (forced) or both null (homogeneous)
-    template <typename Stage, int PSLOT>
-    int launch_lattice(const cuddh_wave_lattice *D, const double *const (&in)[Stage::NIN], const double *F, const double *G,
-                       double *const (&out)[Stage::NOUT], const double (&coef)[MAX_COEF], void *stream)
-    {
-        Lattice L;
-        if (!describe(D, 2, L) || (F == nullptr) != (G == nullptr))
-            return invalid_value;
-        const bool forced = F != nullptr;
-        StageArgs a = {};
-        bool ok = true;
-        for (int s = 0; s < Stage::NIN; ++s)
+        template <typename Stage, int PSLOT>
+        int sweep(const double *const (&in)[Stage::NIN], const double *F, const double *G, double *const (&out)[Stage::NOUT],
+                  const double (&coef)[MAX_COEF]) const
         {
-            a.in[s] = in[s];
-            ok = ok && in[s] && aligned16(in[s]);
+            Lattice L;
+            StageArgs a;
+            if (!describe(D, 2, L) || !stage_args<Stage>(in, F, G, out, coef, a))
+                return invalid_value;
+            const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
+            dispatch_sweep(L.nb, NBasis<4, 5>{}, F != nullptr, static_cast<long long>(L.stride) * L.Ly * sizeof(double),
+                           [&](auto forced_c, auto nt_c, auto nbt)
+                           { hipLaunchKernelGGL((lattice_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
+                                                dim3(grid), dim3(BLOCK), 0, as_stream(stream), L, a); });
+            return launch_status();
         }
-        if (forced)
-        {
-            a.in[Stage::NIN] = F;
-            a.in[Stage::NIN + 1] = G;
-            ok = ok && aligned16(F) && aligned16(G);
-        }
-        for (int s = 0; s < Stage::NOUT; ++s)
-        {
-            a.out[s] = out[s];
-            // a neighbour's thread still needs the stencil input: it is not an output
-            ok = ok && out[s] && aligned16(out[s]) && out[s] != in[0];
-        }
-        if (!ok)
-            return invalid_value;
-        for (int s = 0; s < MAX_COEF; ++s)
-            a.coef[s] = coef[s];
-        const long long n = static_cast<long long>(L.stride) * L.Ly;
-        const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
-        const bool nt = n * static_cast<long long>(sizeof(double)) >= NT_BYTES;
-        auto go = [&](auto nbt)
-        {
-            with_flags([&](auto forced_c, auto nt_c)
-                       { hipLaunchKernelGGL((lattice_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
-                                            dim3(grid), dim3(BLOCK), 0, as_stream(stream), L, a); },
-                       forced, nt);
-        };
-        if (L.nb == 4)
-            go(std::integral_constant<int, 4>{});
-        else if (L.nb == 5)
-            go(std::integral_constant<int, 5>{});
-        else
-            go(std::integral_constant<int, 0>{});
-        return launch_status();
-    }
+    };
 } // namespace
 
 extern "C"
@@ -247,7 +193,7 @@ extern "C"
     {
         if (n <= 0)
             return 0;
-        hipLaunchKernelGGL(gather_kernel, dim3(stream_grid(n, BLOCK)), dim3(BLOCK), 0, as_stream(stream), n, dof_of_slot, x, y);
+        hipLaunchKernelGGL(load_kernel<double>, dim3(stream_grid(n, LOAD_BLOCK)), dim3(LOAD_BLOCK), 0, as_stream(stream), n, dof_of_slot, x, y);
         return launch_status();
     }
 
@@ -256,7 +202,7 @@ extern "C"
     {
         if (n <= 0)
             return 0;
-        hipLaunchKernelGGL(begin_kernel, dim3(stream_grid(n, BLOCK)), dim3(BLOCK), 0, as_stream(stream), n, filt0, dof_of_slot, zu, zv, p, q, u, v);
+        hipLaunchKernelGGL(begin_kernel<double>, dim3(stream_grid(n, LOAD_BLOCK)), dim3(LOAD_BLOCK), 0, as_stream(stream), n, filt0, dof_of_slot, zu, zv, p, q, u, v);
         return launch_status();
     }
 
@@ -264,41 +210,41 @@ extern "C"
                                          const double *invm, const double *Hi, const double *F, const double *G, double *qh, double *ph,
                                          void *stream)
     {
-        return launch_lattice<Rk2A, 1>(lattice, {p, p, q, invm, Hi}, F, G, {qh, ph}, {half_dt, c, s, 0.0}, stream);
+        return rk2_a(launch_lattice{lattice, stream}, half_dt, c, s, p, q, invm, Hi, F, G, qh, ph);
     }
 
     int cuddh_hip_wave_lattice_rk2_b_f64(const cuddh_wave_lattice *lattice, double dt, double c, double s, double filt, const double *ph,
                                          const double *qh, const double *invm, const double *Hi, const double *F, const double *G, double *p,
                                          double *q, double *u, double *v, void *stream)
     {
-        return launch_lattice<Rk2B, 0>(lattice, {ph, qh, p, q, u, v, invm, Hi}, F, G, {p, q, u, v}, {dt, c, s, filt}, stream);
+        return rk2_b(launch_lattice{lattice, stream}, dt, c, s, filt, ph, qh, invm, Hi, F, G, p, q, u, v);
     }
 
     int cuddh_hip_wave_lattice_rk4_1_f64(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const double *p, const double *q,
                                          const double *invm, const double *Hi, const double *F, const double *G, double *ps, double *qs,
                                          double *aq, double *ap, void *stream)
     {
-        return launch_lattice<Rk4First, 1>(lattice, {p, p, q, invm, Hi}, F, G, {ps, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_1(launch_lattice{lattice, stream}, half_dt, c, s, p, q, invm, Hi, F, G, ps, qs, aq, ap);
     }
 
     int cuddh_hip_wave_lattice_rk4_2_f64(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const double *ps_in,
                                          const double *p, const double *q, const double *invm, const double *Hi, const double *F,
                                          const double *G, double *ps_out, double *qs, double *aq, double *ap, void *stream)
     {
-        return launch_lattice<Rk4Mid, 0>(lattice, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_2(launch_lattice{lattice, stream}, half_dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_lattice_rk4_3_f64(const cuddh_wave_lattice *lattice, double dt, double c, double s, const double *ps_in, const double *p,
                                          const double *q, const double *invm, const double *Hi, const double *F, const double *G,
                                          double *ps_out, double *qs, double *aq, double *ap, void *stream)
     {
-        return launch_lattice<Rk4Mid, 0>(lattice, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {dt, c, s, 0.0}, stream);
+        return rk4_3(launch_lattice{lattice, stream}, dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_lattice_rk4_4_f64(const cuddh_wave_lattice *lattice, double sixth_dt, double c, double s, double filt, const double *ps,
                                          const double *qs, const double *aq, const double *ap, const double *invm, const double *Hi,
                                          const double *F, const double *G, double *p, double *q, double *u, double *v, void *stream)
     {
-        return launch_lattice<Rk4Last, 0>(lattice, {ps, p, q, qs, aq, ap, u, v, invm, Hi}, F, G, {p, q, u, v}, {sixth_dt, c, s, filt}, stream);
+        return rk4_4(launch_lattice{lattice, stream}, sixth_dt, c, s, filt, ps, qs, aq, ap, invm, Hi, F, G, p, q, u, v);
     }
 }

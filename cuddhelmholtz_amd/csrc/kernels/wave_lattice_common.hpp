@@ -1,9 +1,11 @@
-// What the two lattice-sweep files share (wave_lattice.hip: fp64; wave_lattice_f32.hip: fp32): the kernel's view of a
-// cuddh_wave_lattice and the stencil's row ids and offset ranges.  The rows and tables are stated at the head of wave_lattice.hip.
+// What the lattice-sweep files share (wave_lattice.hip and the files modelled on it, fp64 and fp32): the kernel's view of a
+// cuddh_wave_lattice or a cuddh_wave_box and the stencil's row ids and offset ranges.  The rows and tables are stated at the head
+// of wave_lattice.hip.  What the files' launchers share is in wave_sweep_launch.hpp.
 #ifndef CUDDH_AMD_WAVE_LATTICE_COMMON_HPP
 #define CUDDH_AMD_WAVE_LATTICE_COMMON_HPP
 
 #include "common.hpp"
+#include "wave_stages.hpp"
 
 namespace cuddh_k
 {
@@ -62,6 +64,72 @@ namespace cuddh_k
                 L.Wt[k] = static_cast<R>(w[k]);
             L.Wt[H] = static_cast<R>(w[0]);
             L.Wt[H + 1] = static_cast<R>(w[H]);
+            return true;
+        }
+
+        // The lattice vectors of one period come in through these two, rounded to R once (for R = double: as they are); padding
+        // slots carry dof -1.
+        constexpr int LOAD_BLOCK = 256;
+        template <typename R>
+        __global__ void __launch_bounds__(LOAD_BLOCK) load_kernel(int n, const int *__restrict__ dof, const double *__restrict__ x, R *__restrict__ y)
+        {
+            for (int i = blockIdx.x * LOAD_BLOCK + threadIdx.x; i < n; i += gridDim.x * LOAD_BLOCK)
+            {
+                const int g = dof[i];
+                y[i] = g >= 0 ? static_cast<R>(x[g]) : R(0);
+            }
+        }
+        template <typename R>
+        __global__ void __launch_bounds__(LOAD_BLOCK) begin_kernel(int n, R filt0, const int *__restrict__ dof, const double *__restrict__ zu,
+                                                                   const double *__restrict__ zv, R *__restrict__ p, R *__restrict__ q,
+                                                                   R *__restrict__ u, R *__restrict__ v)
+        {
+            for (int i = blockIdx.x * LOAD_BLOCK + threadIdx.x; i < n; i += gridDim.x * LOAD_BLOCK)
+            {
+                const int g = dof[i];
+                const R xe[2] = {g >= 0 ? static_cast<R>(zu[g]) : R(0), g >= 0 ? static_cast<R>(zv[g]) : R(0)};
+                R ye[4];
+                BeginT<R>::template apply<false>(xe, ye, &filt0);
+                p[i] = ye[0];
+                q[i] = ye[1];
+                u[i] = ye[2];
+                v[i] = ye[3];
+            }
+        }
+
+        // The box sweeps' view of a cuddh_wave_box (wave_box.hip, wave_box_f32.hip): Lz planes of one lattice.
+        template <typename R>
+        struct BoxT
+        {
+            LatticeT<R> L; // one plane: Lx, Ly, stride, nb, cx, cy and the tables
+            int Lz;
+            R cz;
+        };
+
+        // the kernel's view of the caller's description, or false
+        template <typename R>
+        bool describe_box(const cuddh_wave_box *D, int stride_multiple, BoxT<R> &B)
+        {
+            if (!D || D->nz < 1)
+                return false;
+            cuddh_wave_lattice P = {};
+            P.nx = D->nx;
+            P.ny = D->ny;
+            P.n_basis = D->n_basis;
+            P.stride = D->stride;
+            P.cx = D->cx;
+            P.cy = D->cy;
+            for (int i = 0; i < 64; ++i)
+                P.A[i] = D->A[i];
+            for (int i = 0; i < 8; ++i)
+                P.w[i] = D->w[i];
+            if (!describe(&P, stride_multiple, B.L))
+                return false;
+            const long long Lz = static_cast<long long>(D->nz) * (D->n_basis - 1) + 1;
+            if (static_cast<long long>(B.L.stride) * B.L.Ly * Lz > 0x7fffffffLL)
+                return false;
+            B.Lz = static_cast<int>(Lz);
+            B.cz = static_cast<R>(D->cz);
             return true;
         }
     } // namespace wave

@@ -19,8 +19,10 @@
 // 16-byte pieces, the y-window as one 16-byte piece per offset.  In rk2_a and rk4_1 the stencil input is also the stage's p: it
 // is taken from the tile.  Workgroup ids are renumbered as in wave_lattice.hip.  n_basis 4 and 5 are compile-time; every other
 // n_basis in [2, 8] shares an instantiation with loops of run-time length over LDS (no register arrays, hence no scratch).
+// The host side below is the family's launcher only (description, extra argument, grid, compile-time n_basis list); the stage
+// arguments and their refusals, the dispatch and the six wirings of the entry points are wave_sweep_launch.hpp's.
 #include "wave_lattice_common.hpp"
-#include "wave_stages.hpp"
+#include "wave_sweep_launch.hpp"
 
 #include "cuddh_hip.h"
 
@@ -38,13 +40,7 @@ namespace
 
     using V4 = float __attribute__((ext_vector_type(4)));
     using Lattice32 = LatticeT<float>;
-
-    struct StageArgs32
-    {
-        const float *in[MAX_IN];
-        float *out[MAX_OUT]; // may alias inputs other than in[0] (element i is read before it is written, by the same thread)
-        float coef[MAX_COEF];
-    };
+    using StageArgs32 = StageArgsT<float>;
 
     // PSLOT > 0: input PSLOT of the stage is the stencil input itself
     template <typename Stage, int PSLOT, bool FORCED, bool NT, int NBT>
@@ -202,89 +198,36 @@ namespace
         }
     }
 
-    // (the lattice vectors of one period come in and leave through these three, rounded once; padding slots carry dof -1)
-    __global__ void __launch_bounds__(BLOCK) load32_kernel(int n, const int *__restrict__ dof, const double *__restrict__ x, float *__restrict__ y)
-    {
-        for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-        {
-            const int g = dof[i];
-            y[i] = g >= 0 ? static_cast<float>(x[g]) : 0.0f;
-        }
-    }
-    __global__ void __launch_bounds__(BLOCK) begin32_kernel(int n, float filt0, const int *__restrict__ dof, const double *__restrict__ zu,
-                                                            const double *__restrict__ zv, float *__restrict__ p, float *__restrict__ q,
-                                                            float *__restrict__ u, float *__restrict__ v)
-    {
-        for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK)
-        {
-            const int g = dof[i];
-            const float xe[2] = {g >= 0 ? static_cast<float>(zu[g]) : 0.0f, g >= 0 ? static_cast<float>(zv[g]) : 0.0f};
-            float ye[4];
-            BeginT<float>::apply<false>(xe, ye, &filt0);
-            p[i] = ye[0];
-            q[i] = ye[1];
-            u[i] = ye[2];
-            v[i] = ye[3];
-        }
-    }
+    // (the lattice vectors of one period leave through this one; they come in through load_kernel and begin_kernel of
+    // wave_lattice_common.hpp)
     __global__ void __launch_bounds__(BLOCK) store32_kernel(int n, const int *__restrict__ slot, const float *__restrict__ x, double *__restrict__ y)
     {
         for (int g = blockIdx.x * BLOCK + threadIdx.x; g < n; g += gridDim.x * BLOCK)
             y[g] = static_cast<double>(x[slot[g]]);
     }
 
-    constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
-
-    // in[0]: the stencil input; F, G: both given (forced) or both null (homogeneous); coef: the call's scalars, rounded here
-    template <typename Stage, int PSLOT>
-    int launch_lattice32(const cuddh_wave_lattice *D, const float *const (&in)[Stage::NIN], const float *F, const float *G,
-                         float *const (&out)[Stage::NOUT], const double (&coef)[MAX_COEF], void *stream)
+    // the family's launcher (wave_sweep_launch.hpp): one sweep on the entry points' leading arguments
+    struct launch_lattice32
     {
-        Lattice32 L;
-        if (!describe(D, COLS, L) || (F == nullptr) != (G == nullptr))
-            return invalid_value;
-        const bool forced = F != nullptr;
-        StageArgs32 a = {};
-        bool ok = true;
-        for (int s = 0; s < Stage::NIN; ++s)
+        const cuddh_wave_lattice *D;
+        void *stream;
+
+        template <typename Stage, int PSLOT>
+        int sweep(const float *const (&in)[Stage::NIN], const float *F, const float *G, float *const (&out)[Stage::NOUT],
+                  const double (&coef)[MAX_COEF]) const
         {
-            a.in[s] = in[s];
-            ok = ok && in[s] && aligned16(in[s]);
+            Lattice32 L;
+            StageArgs32 a;
+            if (!describe(D, COLS, L) || !stage_args<Stage>(in, F, G, out, coef, a))
+                return invalid_value;
+            const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
+            dispatch_sweep(L.nb, NBasis<4, 5>{}, F != nullptr, static_cast<long long>(L.stride) * L.Ly * sizeof(float),
+                           [&](auto forced_c, auto nt_c, auto nbt)
+                           { hipLaunchKernelGGL((lattice32_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
+                                                dim3(grid), dim3(BLOCK), 0, as_stream(stream), L, a); });
+            return launch_status();
         }
-        if (forced)
-        {
-            a.in[Stage::NIN] = F;
-            a.in[Stage::NIN + 1] = G;
-            ok = ok && aligned16(F) && aligned16(G);
-        }
-        for (int s = 0; s < Stage::NOUT; ++s)
-        {
-            a.out[s] = out[s];
-            // a neighbour's thread still needs the stencil input: it is not an output
-            ok = ok && out[s] && aligned16(out[s]) && out[s] != in[0];
-        }
-        if (!ok)
-            return invalid_value;
-        for (int s = 0; s < MAX_COEF; ++s)
-            a.coef[s] = static_cast<float>(coef[s]);
-        const long long n = static_cast<long long>(L.stride) * L.Ly;
-        const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
-        const bool nt = n * static_cast<long long>(sizeof(float)) >= NT_BYTES;
-        auto go = [&](auto nbt)
-        {
-            with_flags([&](auto forced_c, auto nt_c)
-                       { hipLaunchKernelGGL((lattice32_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
-                                            dim3(grid), dim3(BLOCK), 0, as_stream(stream), L, a); },
-                       forced, nt);
-        };
-        if (L.nb == 4)
-            go(std::integral_constant<int, 4>{});
-        else if (L.nb == 5)
-            go(std::integral_constant<int, 5>{});
-        else
-            go(std::integral_constant<int, 0>{});
-        return launch_status();
-    }
+    };
 } // namespace
 
 extern "C"
@@ -296,7 +239,7 @@ extern "C"
     {
         if (n <= 0)
             return 0;
-        hipLaunchKernelGGL(load32_kernel, dim3(stream_grid(n, BLOCK)), dim3(BLOCK), 0, as_stream(stream), n, dof_of_slot, x, y);
+        hipLaunchKernelGGL(load_kernel<float>, dim3(stream_grid(n, LOAD_BLOCK)), dim3(LOAD_BLOCK), 0, as_stream(stream), n, dof_of_slot, x, y);
         return launch_status();
     }
 
@@ -305,7 +248,7 @@ extern "C"
     {
         if (n <= 0)
             return 0;
-        hipLaunchKernelGGL(begin32_kernel, dim3(stream_grid(n, BLOCK)), dim3(BLOCK), 0, as_stream(stream), n, static_cast<float>(filt0), dof_of_slot,
+        hipLaunchKernelGGL(begin_kernel<float>, dim3(stream_grid(n, LOAD_BLOCK)), dim3(LOAD_BLOCK), 0, as_stream(stream), n, static_cast<float>(filt0), dof_of_slot,
                            zu, zv, p, q, u, v);
         return launch_status();
     }
@@ -321,41 +264,41 @@ extern "C"
     int cuddh_hip_wave32_rk2_a(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const float *p, const float *q,
                                const float *invm, const float *Hi, const float *F, const float *G, float *qh, float *ph, void *stream)
     {
-        return launch_lattice32<Rk2AT<float>, 1>(lattice, {p, p, q, invm, Hi}, F, G, {qh, ph}, {half_dt, c, s, 0.0}, stream);
+        return rk2_a(launch_lattice32{lattice, stream}, half_dt, c, s, p, q, invm, Hi, F, G, qh, ph);
     }
 
     int cuddh_hip_wave32_rk2_b(const cuddh_wave_lattice *lattice, double dt, double c, double s, double filt, const float *ph, const float *qh,
                                const float *invm, const float *Hi, const float *F, const float *G, float *p, float *q, float *u, float *v,
                                void *stream)
     {
-        return launch_lattice32<Rk2BT<float>, 0>(lattice, {ph, qh, p, q, u, v, invm, Hi}, F, G, {p, q, u, v}, {dt, c, s, filt}, stream);
+        return rk2_b(launch_lattice32{lattice, stream}, dt, c, s, filt, ph, qh, invm, Hi, F, G, p, q, u, v);
     }
 
     int cuddh_hip_wave32_rk4_1(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const float *p, const float *q,
                                const float *invm, const float *Hi, const float *F, const float *G, float *ps, float *qs, float *aq, float *ap,
                                void *stream)
     {
-        return launch_lattice32<Rk4FirstT<float>, 1>(lattice, {p, p, q, invm, Hi}, F, G, {ps, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_1(launch_lattice32{lattice, stream}, half_dt, c, s, p, q, invm, Hi, F, G, ps, qs, aq, ap);
     }
 
     int cuddh_hip_wave32_rk4_2(const cuddh_wave_lattice *lattice, double half_dt, double c, double s, const float *ps_in, const float *p,
                                const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
                                float *aq, float *ap, void *stream)
     {
-        return launch_lattice32<Rk4MidT<float>, 0>(lattice, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_2(launch_lattice32{lattice, stream}, half_dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave32_rk4_3(const cuddh_wave_lattice *lattice, double dt, double c, double s, const float *ps_in, const float *p,
                                const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
                                float *aq, float *ap, void *stream)
     {
-        return launch_lattice32<Rk4MidT<float>, 0>(lattice, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {dt, c, s, 0.0}, stream);
+        return rk4_3(launch_lattice32{lattice, stream}, dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave32_rk4_4(const cuddh_wave_lattice *lattice, double sixth_dt, double c, double s, double filt, const float *ps,
                                const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi, const float *F,
                                const float *G, float *p, float *q, float *u, float *v, void *stream)
     {
-        return launch_lattice32<Rk4LastT<float>, 0>(lattice, {ps, p, q, qs, aq, ap, u, v, invm, Hi}, F, G, {p, q, u, v}, {sixth_dt, c, s, filt}, stream);
+        return rk4_4(launch_lattice32{lattice, stream}, sixth_dt, c, s, filt, ps, qs, aq, ap, invm, Hi, F, G, p, q, u, v);
     }
 }

@@ -14,6 +14,8 @@
 // (the streams that were just staged are read through the cache), workgroup ids renumbered so that an XCD gets a contiguous
 // run of tiles.  n_basis 4 and 5 are compile-time on tiles of 128 x 16; every other n_basis in [2, 8] shares an instantiation
 // with loops over LDS only and a halo of 7, on tiles of 128 x 8 so that its two tiles stay below 64 KB of LDS.
+// The launcher's arguments and refusals are pair_args (wave_pair_stages.hpp); its dispatch of n_basis, forced and streaming to an
+// instantiation is dispatch_sweep (wave_sweep_launch.hpp).
 #include "cuddh_hip.h"
 
 #include "wave_pair_stages.hpp"
@@ -152,8 +154,6 @@ namespace
         }
     }
 
-    constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
-
     template <typename Kind, int NCOEF>
     int launch_pair(const cuddh_wave_lattice *D, const double *const (&halo)[PAIR_HALO], const double *const (&in)[Kind::NIN], const double *F,
                     const double *G, double *const (&out)[Kind::NOUT], const double (&coef)[NCOEF], void *stream)
@@ -162,23 +162,14 @@ namespace
         PairArgs a;
         if (!pair_args<double, Kind>(D, 2, halo, in, F, G, out, coef, L, a))
             return invalid_value;
-        const long long n = static_cast<long long>(L.stride) * L.Ly;
-        const bool forced = F != nullptr, nt = n * static_cast<long long>(sizeof(double)) >= NT_BYTES;
-        auto go = [&](auto nbt)
-        {
-            constexpr int ty = tile_y(decltype(nbt)::value);
-            const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + ty - 1) / ty);
-            with_flags([&](auto forced_c, auto nt_c)
-                       { hipLaunchKernelGGL((pair_kernel<Kind, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>), dim3(grid),
-                                            dim3(BLOCK), 0, as_stream(stream), L, a); },
-                       forced, nt);
-        };
-        if (L.nb == 4)
-            go(std::integral_constant<int, 4>{});
-        else if (L.nb == 5)
-            go(std::integral_constant<int, 5>{});
-        else
-            go(std::integral_constant<int, 0>{});
+        dispatch_sweep(L.nb, NBasis<4, 5>{}, F != nullptr, static_cast<long long>(L.stride) * L.Ly * sizeof(double),
+                       [&](auto forced_c, auto nt_c, auto nbt)
+                       {
+                           constexpr int ty = tile_y(decltype(nbt)::value);
+                           const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + ty - 1) / ty);
+                           hipLaunchKernelGGL((pair_kernel<Kind, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>), dim3(grid),
+                                              dim3(BLOCK), 0, as_stream(stream), L, a);
+                       });
         return launch_status();
     }
 } // namespace

@@ -9,6 +9,8 @@
 // (clamped, not guarded) issued before its first store, non-temporal from 64 MB per vector (the streams that were just staged
 // are read through the cache).  The x-window of a lane's four columns is read as aligned 16-byte pieces, the y-window as one
 // 16-byte piece per offset, from each tile in turn.
+// The launcher's arguments and refusals are pair_args (wave_pair_stages.hpp); its dispatch of n_basis, forced and streaming to an
+// instantiation is dispatch_sweep (wave_sweep_launch.hpp).
 #include "cuddh_hip.h"
 
 #include "wave_pair_stages.hpp"
@@ -196,8 +198,6 @@ namespace
         }
     }
 
-    constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
-
     template <typename Kind, int NCOEF>
     int launch_pair32(const cuddh_wave_lattice *D, const float *const (&halo)[PAIR_HALO], const float *const (&in)[Kind::NIN], const float *F,
                       const float *G, float *const (&out)[Kind::NOUT], const double (&coef)[NCOEF], void *stream)
@@ -206,22 +206,11 @@ namespace
         PairArgs32 a;
         if (!pair_args<float, Kind>(D, COLS, halo, in, F, G, out, coef, L, a))
             return invalid_value;
-        const long long n = static_cast<long long>(L.stride) * L.Ly;
         const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
-        const bool forced = F != nullptr, nt = n * static_cast<long long>(sizeof(float)) >= NT_BYTES;
-        auto go = [&](auto nbt)
-        {
-            with_flags([&](auto forced_c, auto nt_c)
+        dispatch_sweep(L.nb, NBasis<4, 5>{}, F != nullptr, static_cast<long long>(L.stride) * L.Ly * sizeof(float),
+                       [&](auto forced_c, auto nt_c, auto nbt)
                        { hipLaunchKernelGGL((pair32_kernel<Kind, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>), dim3(grid),
-                                            dim3(BLOCK), 0, as_stream(stream), L, a); },
-                       forced, nt);
-        };
-        if (L.nb == 4)
-            go(std::integral_constant<int, 4>{});
-        else if (L.nb == 5)
-            go(std::integral_constant<int, 5>{});
-        else
-            go(std::integral_constant<int, 0>{});
+                                            dim3(BLOCK), 0, as_stream(stream), L, a); });
         return launch_status();
     }
 } // namespace

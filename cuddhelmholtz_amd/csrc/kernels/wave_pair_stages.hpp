@@ -12,7 +12,7 @@
 #define CUDDH_AMD_WAVE_PAIR_STAGES_HPP
 
 #include "wave_lattice_common.hpp"
-#include "wave_stages.hpp"
+#include "wave_sweep_launch.hpp" // (dispatch_sweep and invalid_value for the two launchers; the stages through it)
 
 namespace cuddh_k
 {

@@ -3,6 +3,8 @@
 // formulas are stated at the head of waveholtz.hip.  Every product-sum is an explicit fused multiply-add in a fixed order.
 // The stages are templates on the scalar R: double for those two files (Begin, Rk2A, ... name the double forms), float for
 // wave_lattice_f32.hip, which then rounds like them operation by operation.
+// The kernels' stage arguments (StageArgsT<R>, MAX_IN inputs, MAX_OUT outputs, MAX_COEF scalars) and the host code that fills them
+// are in wave_sweep_launch.hpp.
 #ifndef CUDDH_AMD_WAVE_STAGES_HPP
 #define CUDDH_AMD_WAVE_STAGES_HPP
 
@@ -16,13 +18,6 @@ namespace cuddh_k
         constexpr int MAX_IN = 12, MAX_OUT = 4, MAX_COEF = 4;
 
         using V2 = double __attribute__((ext_vector_type(2)));
-
-        struct StageArgs
-        {
-            const double *in[MAX_IN];
-            double *out[MAX_OUT]; // may alias inputs (element i is read before it is written, by the same thread)
-            double coef[MAX_COEF];
-        };
 
         __device__ inline double fmadd(double a, double b, double c) { return __builtin_fma(a, b, c); }
         __device__ inline float fmadd(float a, float b, float c) { return __builtin_fmaf(a, b, c); }

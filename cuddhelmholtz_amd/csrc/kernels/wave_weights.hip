@@ -22,8 +22,10 @@
 // the weights of the cells that contain one of its nodes (at most (TX - 1) / H + 2 by (TY - 1) / H + 2) in LDS; when all of them
 // are zero the workgroup returns: it loads and stores no vector, so the outputs keep what they held there.
 // The tables are wave::describe's: row H of T is A[0][.], row H + 1 is A[H][.], row k is A[k][.]; Wt[H] = w[0], Wt[H + 1] = w[H].
+// The host side below is the family's launcher only (description, extra argument, grid, compile-time n_basis list); the stage
+// arguments and their refusals, the dispatch and the six wirings of the entry points are wave_sweep_launch.hpp's.
 #include "wave_lattice_common.hpp"
-#include "wave_stages.hpp"
+#include "wave_sweep_launch.hpp"
 
 #include "cuddh_hip.h"
 
@@ -203,58 +205,29 @@ namespace
         }
     }
 
-    constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
-
-    // in[0]: the stencil input; F, G: both given (forced) or both null (homogeneous)
-    template <typename Stage, int PSLOT>
-    int launch_weights(const cuddh_wave_lattice *D, const double *weight, const double *const (&in)[Stage::NIN], const double *F, const double *G,
-                       double *const (&out)[Stage::NOUT], const double (&coef)[MAX_COEF], void *stream)
+    // the family's launcher (wave_sweep_launch.hpp): one sweep on the entry points' leading arguments
+    struct launch_weights
     {
-        Lattice L;
-        if (!describe(D, 2, L) || !weight || (F == nullptr) != (G == nullptr))
-            return invalid_value;
-        const bool forced = F != nullptr;
-        StageArgs a = {};
-        bool ok = true;
-        for (int s = 0; s < Stage::NIN; ++s)
+        const cuddh_wave_lattice *D;
+        const double *weight;
+        void *stream;
+
+        template <typename Stage, int PSLOT>
+        int sweep(const double *const (&in)[Stage::NIN], const double *F, const double *G, double *const (&out)[Stage::NOUT],
+                  const double (&coef)[MAX_COEF]) const
         {
-            a.in[s] = in[s];
-            ok = ok && in[s] && aligned16(in[s]);
+            Lattice L;
+            StageArgs a;
+            if (!describe(D, 2, L) || !weight || !stage_args<Stage>(in, F, G, out, coef, a))
+                return invalid_value;
+            const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
+            dispatch_sweep(L.nb, NBasis<4, 5>{}, F != nullptr, static_cast<long long>(L.stride) * L.Ly * sizeof(double),
+                           [&](auto forced_c, auto nt_c, auto nbt)
+                           { hipLaunchKernelGGL((weights_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
+                                                dim3(grid), dim3(BLOCK), 0, as_stream(stream), L, a, weight); });
+            return launch_status();
         }
-        if (forced)
-        {
-            a.in[Stage::NIN] = F;
-            a.in[Stage::NIN + 1] = G;
-            ok = ok && aligned16(F) && aligned16(G);
-        }
-        for (int s = 0; s < Stage::NOUT; ++s)
-        {
-            a.out[s] = out[s];
-            // a neighbour's thread still needs the stencil input: it is not an output
-            ok = ok && out[s] && aligned16(out[s]) && out[s] != in[0];
-        }
-        if (!ok)
-            return invalid_value;
-        for (int s = 0; s < MAX_COEF; ++s)
-            a.coef[s] = coef[s];
-        const long long n = static_cast<long long>(L.stride) * L.Ly;
-        const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
-        const bool nt = n * static_cast<long long>(sizeof(double)) >= NT_BYTES;
-        auto go = [&](auto nbt)
-        {
-            with_flags([&](auto forced_c, auto nt_c)
-                       { hipLaunchKernelGGL((weights_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
-                                            dim3(grid), dim3(BLOCK), 0, as_stream(stream), L, a, weight); },
-                       forced, nt);
-        };
-        if (L.nb == 4)
-            go(std::integral_constant<int, 4>{});
-        else if (L.nb == 5)
-            go(std::integral_constant<int, 5>{});
-        else
-            go(std::integral_constant<int, 0>{});
-        return launch_status();
-    }
+    };
 } // namespace
 
 extern "C"
@@ -263,41 +236,41 @@ extern "C"
                                          const double *p, const double *q, const double *invm, const double *Hi, const double *F, const double *G,
                                          double *qh, double *ph, void *stream)
     {
-        return launch_weights<Rk2A, 1>(lattice, weight, {p, p, q, invm, Hi}, F, G, {qh, ph}, {half_dt, c, s, 0.0}, stream);
+        return rk2_a(launch_weights{lattice, weight, stream}, half_dt, c, s, p, q, invm, Hi, F, G, qh, ph);
     }
 
     int cuddh_hip_wave_weights_rk2_b_f64(const cuddh_wave_lattice *lattice, const double *weight, double dt, double c, double s, double filt,
                                          const double *ph, const double *qh, const double *invm, const double *Hi, const double *F, const double *G,
                                          double *p, double *q, double *u, double *v, void *stream)
     {
-        return launch_weights<Rk2B, 0>(lattice, weight, {ph, qh, p, q, u, v, invm, Hi}, F, G, {p, q, u, v}, {dt, c, s, filt}, stream);
+        return rk2_b(launch_weights{lattice, weight, stream}, dt, c, s, filt, ph, qh, invm, Hi, F, G, p, q, u, v);
     }
 
     int cuddh_hip_wave_weights_rk4_1_f64(const cuddh_wave_lattice *lattice, const double *weight, double half_dt, double c, double s,
                                          const double *p, const double *q, const double *invm, const double *Hi, const double *F, const double *G,
                                          double *ps, double *qs, double *aq, double *ap, void *stream)
     {
-        return launch_weights<Rk4First, 1>(lattice, weight, {p, p, q, invm, Hi}, F, G, {ps, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_1(launch_weights{lattice, weight, stream}, half_dt, c, s, p, q, invm, Hi, F, G, ps, qs, aq, ap);
     }
 
     int cuddh_hip_wave_weights_rk4_2_f64(const cuddh_wave_lattice *lattice, const double *weight, double half_dt, double c, double s,
                                          const double *ps_in, const double *p, const double *q, const double *invm, const double *Hi, const double *F,
                                          const double *G, double *ps_out, double *qs, double *aq, double *ap, void *stream)
     {
-        return launch_weights<Rk4Mid, 0>(lattice, weight, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_2(launch_weights{lattice, weight, stream}, half_dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_weights_rk4_3_f64(const cuddh_wave_lattice *lattice, const double *weight, double dt, double c, double s,
                                          const double *ps_in, const double *p, const double *q, const double *invm, const double *Hi, const double *F,
                                          const double *G, double *ps_out, double *qs, double *aq, double *ap, void *stream)
     {
-        return launch_weights<Rk4Mid, 0>(lattice, weight, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {dt, c, s, 0.0}, stream);
+        return rk4_3(launch_weights{lattice, weight, stream}, dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_weights_rk4_4_f64(const cuddh_wave_lattice *lattice, const double *weight, double sixth_dt, double c, double s, double filt,
                                          const double *ps, const double *qs, const double *aq, const double *ap, const double *invm, const double *Hi,
                                          const double *F, const double *G, double *p, double *q, double *u, double *v, void *stream)
     {
-        return launch_weights<Rk4Last, 0>(lattice, weight, {ps, p, q, qs, aq, ap, u, v, invm, Hi}, F, G, {p, q, u, v}, {sixth_dt, c, s, filt}, stream);
+        return rk4_4(launch_weights{lattice, weight, stream}, sixth_dt, c, s, filt, ps, qs, aq, ap, invm, Hi, F, G, p, q, u, v);
     }
 }

@@ -7,8 +7,10 @@
 // Layout, decomposition (a tile of 128 x 16 nodes, a lane four neighbouring columns, 16-byte LDS pieces), streams, workgroup
 // renumbering and the n_basis instantiations are wave_lattice_f32.hip's.  A tile first stages the weights of the cells that contain
 // one of its nodes in LDS; when all of them are zero the workgroup returns: it loads and stores no vector.
+// The host side below is the family's launcher only (description, extra argument, grid, compile-time n_basis list); the stage
+// arguments and their refusals, the dispatch and the six wirings of the entry points are wave_sweep_launch.hpp's.
 #include "wave_lattice_common.hpp"
-#include "wave_stages.hpp"
+#include "wave_sweep_launch.hpp"
 
 #include "cuddh_hip.h"
 
@@ -27,12 +29,7 @@ namespace
     using V4 = float __attribute__((ext_vector_type(4)));
     using Lattice32 = LatticeT<float>;
 
-    struct StageArgs32
-    {
-        const float *in[MAX_IN];
-        float *out[MAX_OUT]; // may alias inputs other than in[0] (element i is read before it is written, by the same thread)
-        float coef[MAX_COEF];
-    };
+    using StageArgs32 = StageArgsT<float>;
 
     // PSLOT > 0: input PSLOT of the stage is the stencil input itself
     template <typename Stage, int PSLOT, bool FORCED, bool NT, int NBT>
@@ -283,58 +280,29 @@ namespace
         }
     }
 
-    constexpr int invalid_value = static_cast<int>(hipErrorInvalidValue);
-
-    // in[0]: the stencil input; F, G: both given (forced) or both null (homogeneous); coef: the call's scalars, rounded here
-    template <typename Stage, int PSLOT>
-    int launch_weights32(const cuddh_wave_lattice *D, const float *weight, const float *const (&in)[Stage::NIN], const float *F, const float *G,
-                         float *const (&out)[Stage::NOUT], const double (&coef)[MAX_COEF], void *stream)
+    // the family's launcher (wave_sweep_launch.hpp): one sweep on the entry points' leading arguments
+    struct launch_weights32
     {
-        Lattice32 L;
-        if (!describe(D, COLS, L) || !weight || (F == nullptr) != (G == nullptr))
-            return invalid_value;
-        const bool forced = F != nullptr;
-        StageArgs32 a = {};
-        bool ok = true;
-        for (int s = 0; s < Stage::NIN; ++s)
+        const cuddh_wave_lattice *D;
+        const float *weight;
+        void *stream;
+
+        template <typename Stage, int PSLOT>
+        int sweep(const float *const (&in)[Stage::NIN], const float *F, const float *G, float *const (&out)[Stage::NOUT],
+                  const double (&coef)[MAX_COEF]) const
         {
-            a.in[s] = in[s];
-            ok = ok && in[s] && aligned16(in[s]);
+            Lattice32 L;
+            StageArgs32 a;
+            if (!describe(D, COLS, L) || !weight || !stage_args<Stage>(in, F, G, out, coef, a))
+                return invalid_value;
+            const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
+            dispatch_sweep(L.nb, NBasis<4, 5>{}, F != nullptr, static_cast<long long>(L.stride) * L.Ly * sizeof(float),
+                           [&](auto forced_c, auto nt_c, auto nbt)
+                           { hipLaunchKernelGGL((weights32_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
+                                                dim3(grid), dim3(BLOCK), 0, as_stream(stream), L, a, weight); });
+            return launch_status();
         }
-        if (forced)
-        {
-            a.in[Stage::NIN] = F;
-            a.in[Stage::NIN + 1] = G;
-            ok = ok && aligned16(F) && aligned16(G);
-        }
-        for (int s = 0; s < Stage::NOUT; ++s)
-        {
-            a.out[s] = out[s];
-            // a neighbour's thread still needs the stencil input: it is not an output
-            ok = ok && out[s] && aligned16(out[s]) && out[s] != in[0];
-        }
-        if (!ok)
-            return invalid_value;
-        for (int s = 0; s < MAX_COEF; ++s)
-            a.coef[s] = static_cast<float>(coef[s]);
-        const long long n = static_cast<long long>(L.stride) * L.Ly;
-        const int grid = ((L.stride + TX - 1) / TX) * ((L.Ly + TY - 1) / TY);
-        const bool nt = n * static_cast<long long>(sizeof(float)) >= NT_BYTES;
-        auto go = [&](auto nbt)
-        {
-            with_flags([&](auto forced_c, auto nt_c)
-                       { hipLaunchKernelGGL((weights32_kernel<Stage, PSLOT, decltype(forced_c)::value, decltype(nt_c)::value, decltype(nbt)::value>),
-                                            dim3(grid), dim3(BLOCK), 0, as_stream(stream), L, a, weight); },
-                       forced, nt);
-        };
-        if (L.nb == 4)
-            go(std::integral_constant<int, 4>{});
-        else if (L.nb == 5)
-            go(std::integral_constant<int, 5>{});
-        else
-            go(std::integral_constant<int, 0>{});
-        return launch_status();
-    }
+    };
 } // namespace
 
 extern "C"
@@ -342,41 +310,41 @@ extern "C"
     int cuddh_hip_wave_weights32_rk2_a(const cuddh_wave_lattice *lattice, const float *weight, double half_dt, double c, double s, const float *p, const float *q,
                                const float *invm, const float *Hi, const float *F, const float *G, float *qh, float *ph, void *stream)
     {
-        return launch_weights32<Rk2AT<float>, 1>(lattice, weight, {p, p, q, invm, Hi}, F, G, {qh, ph}, {half_dt, c, s, 0.0}, stream);
+        return rk2_a(launch_weights32{lattice, weight, stream}, half_dt, c, s, p, q, invm, Hi, F, G, qh, ph);
     }
 
     int cuddh_hip_wave_weights32_rk2_b(const cuddh_wave_lattice *lattice, const float *weight, double dt, double c, double s, double filt, const float *ph, const float *qh,
                                const float *invm, const float *Hi, const float *F, const float *G, float *p, float *q, float *u, float *v,
                                void *stream)
     {
-        return launch_weights32<Rk2BT<float>, 0>(lattice, weight, {ph, qh, p, q, u, v, invm, Hi}, F, G, {p, q, u, v}, {dt, c, s, filt}, stream);
+        return rk2_b(launch_weights32{lattice, weight, stream}, dt, c, s, filt, ph, qh, invm, Hi, F, G, p, q, u, v);
     }
 
     int cuddh_hip_wave_weights32_rk4_1(const cuddh_wave_lattice *lattice, const float *weight, double half_dt, double c, double s, const float *p, const float *q,
                                const float *invm, const float *Hi, const float *F, const float *G, float *ps, float *qs, float *aq, float *ap,
                                void *stream)
     {
-        return launch_weights32<Rk4FirstT<float>, 1>(lattice, weight, {p, p, q, invm, Hi}, F, G, {ps, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_1(launch_weights32{lattice, weight, stream}, half_dt, c, s, p, q, invm, Hi, F, G, ps, qs, aq, ap);
     }
 
     int cuddh_hip_wave_weights32_rk4_2(const cuddh_wave_lattice *lattice, const float *weight, double half_dt, double c, double s, const float *ps_in, const float *p,
                                const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
                                float *aq, float *ap, void *stream)
     {
-        return launch_weights32<Rk4MidT<float>, 0>(lattice, weight, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {half_dt, c, s, 0.0}, stream);
+        return rk4_2(launch_weights32{lattice, weight, stream}, half_dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_weights32_rk4_3(const cuddh_wave_lattice *lattice, const float *weight, double dt, double c, double s, const float *ps_in, const float *p,
                                const float *q, const float *invm, const float *Hi, const float *F, const float *G, float *ps_out, float *qs,
                                float *aq, float *ap, void *stream)
     {
-        return launch_weights32<Rk4MidT<float>, 0>(lattice, weight, {ps_in, p, q, qs, aq, ap, invm, Hi}, F, G, {ps_out, qs, aq, ap}, {dt, c, s, 0.0}, stream);
+        return rk4_3(launch_weights32{lattice, weight, stream}, dt, c, s, ps_in, p, q, invm, Hi, F, G, ps_out, qs, aq, ap);
     }
 
     int cuddh_hip_wave_weights32_rk4_4(const cuddh_wave_lattice *lattice, const float *weight, double sixth_dt, double c, double s, double filt, const float *ps,
                                const float *qs, const float *aq, const float *ap, const float *invm, const float *Hi, const float *F,
                                const float *G, float *p, float *q, float *u, float *v, void *stream)
     {
-        return launch_weights32<Rk4LastT<float>, 0>(lattice, weight, {ps, p, q, qs, aq, ap, u, v, invm, Hi}, F, G, {p, q, u, v}, {sixth_dt, c, s, filt}, stream);
+        return rk4_4(launch_weights32{lattice, weight, stream}, sixth_dt, c, s, filt, ps, qs, aq, ap, invm, Hi, F, G, p, q, u, v);
     }
 }

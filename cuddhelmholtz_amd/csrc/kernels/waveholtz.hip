@@ -18,7 +18,9 @@
 // Access pattern: blas1.hip's (contiguous tiles of 16-byte vectors taken in order by the workgroups, clamped requests issued
 // before any result is stored, non-temporal beyond the infinity cache); with up to twelve input streams a tile is two vectors
 // per thread and stream.  When any pointer is not 16-byte aligned the whole launch goes element by element.
-#include "wave_stages.hpp"
+// StageArgs is wave_sweep_launch.hpp's StageArgsT<double>; the launcher below stays this file's own, since it refuses nothing that
+// header's stage_args refuses (no stencil input, and a misaligned pointer selects the element-by-element path).
+#include "wave_sweep_launch.hpp" // (StageArgs; the stages through it)
 
 using namespace cuddh_k;
 using namespace cuddh_k::wave; // the stages and fq

@@ -6,6 +6,7 @@
 // mesh with missing cells the per-sweep sequence on csrc/kernels/wave_cells.hip and wave_cells_f32.hip (cuddh_hip_wave_cells_*,
 // cuddh_hip_wave_cells32_*); with a per-cell stiffness coefficient the per-sweep sequence on csrc/kernels/wave_weights.hip
 // and wave_weights_f32.hip (cuddh_hip_wave_weights_*, cuddh_hip_wave_weights32_*).
+// The per-sweep loops are written once, in wave_march.hpp, for every family and for waveholtz_box.cpp.
 #include "cuddh/waveholtz.hpp"
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include "cuddh/time_grid.hpp"
 #include "cuddh/wave_lattice.hpp"
 #include "cuddh_hip.h"
+#include "wave_march.hpp"
 
 namespace cuddh
 {
@@ -66,8 +68,9 @@ namespace cuddh
             return w;
         }
 
-        /// The two kernel families of the lattice form behind one set of names: R = double is cuddh_hip_wave_lattice_*_f64 (and
-        /// cuddh_hip_gather_f64 on the way out), R = float is cuddh_hip_wave32_*.
+        /// The kernel families of the lattice form behind one set of names: R = double is cuddh_hip_wave_lattice_*_f64 (and
+        /// cuddh_hip_gather_f64 on the way out), R = float is cuddh_hip_wave32_*.  `plain`, `cells` and `weights` are the per-sweep
+        /// families that wave_march.hpp marches on; their calls lead with (lattice), (lattice, cell) and (lattice, weight).
         template <typename R>
         struct LatticeKernels;
         template <>
@@ -76,27 +79,15 @@ namespace cuddh
             static constexpr auto load = cuddh_hip_wave_lattice_gather_f64;
             static constexpr auto store = cuddh_hip_gather_f64;
             static constexpr auto begin = cuddh_hip_wave_lattice_begin_f64;
-            static constexpr auto rk2_a = cuddh_hip_wave_lattice_rk2_a_f64;
-            static constexpr auto rk2_b = cuddh_hip_wave_lattice_rk2_b_f64;
-            static constexpr auto rk4_1 = cuddh_hip_wave_lattice_rk4_1_f64;
-            static constexpr auto rk4_2 = cuddh_hip_wave_lattice_rk4_2_f64;
-            static constexpr auto rk4_3 = cuddh_hip_wave_lattice_rk4_3_f64;
-            static constexpr auto rk4_4 = cuddh_hip_wave_lattice_rk4_4_f64;
             static constexpr auto pair_rk2 = cuddh_hip_wave_pair_rk2_f64;
             static constexpr auto pair_rk4_12 = cuddh_hip_wave_pair_rk4_12_f64;
             static constexpr auto pair_rk4_34 = cuddh_hip_wave_pair_rk4_34_f64;
-            static constexpr auto cells_rk2_a = cuddh_hip_wave_cells_rk2_a_f64;
-            static constexpr auto cells_rk2_b = cuddh_hip_wave_cells_rk2_b_f64;
-            static constexpr auto cells_rk4_1 = cuddh_hip_wave_cells_rk4_1_f64;
-            static constexpr auto cells_rk4_2 = cuddh_hip_wave_cells_rk4_2_f64;
-            static constexpr auto cells_rk4_3 = cuddh_hip_wave_cells_rk4_3_f64;
-            static constexpr auto cells_rk4_4 = cuddh_hip_wave_cells_rk4_4_f64;
-            static constexpr auto weights_rk2_a = cuddh_hip_wave_weights_rk2_a_f64;
-            static constexpr auto weights_rk2_b = cuddh_hip_wave_weights_rk2_b_f64;
-            static constexpr auto weights_rk4_1 = cuddh_hip_wave_weights_rk4_1_f64;
-            static constexpr auto weights_rk4_2 = cuddh_hip_wave_weights_rk4_2_f64;
-            static constexpr auto weights_rk4_3 = cuddh_hip_wave_weights_rk4_3_f64;
-            static constexpr auto weights_rk4_4 = cuddh_hip_wave_weights_rk4_4_f64;
+            using plain = detail::SweepSet<cuddh_hip_wave_lattice_rk2_a_f64, cuddh_hip_wave_lattice_rk2_b_f64, cuddh_hip_wave_lattice_rk4_1_f64,
+                                           cuddh_hip_wave_lattice_rk4_2_f64, cuddh_hip_wave_lattice_rk4_3_f64, cuddh_hip_wave_lattice_rk4_4_f64>;
+            using cells = detail::SweepSet<cuddh_hip_wave_cells_rk2_a_f64, cuddh_hip_wave_cells_rk2_b_f64, cuddh_hip_wave_cells_rk4_1_f64,
+                                           cuddh_hip_wave_cells_rk4_2_f64, cuddh_hip_wave_cells_rk4_3_f64, cuddh_hip_wave_cells_rk4_4_f64>;
+            using weights = detail::SweepSet<cuddh_hip_wave_weights_rk2_a_f64, cuddh_hip_wave_weights_rk2_b_f64, cuddh_hip_wave_weights_rk4_1_f64,
+                                             cuddh_hip_wave_weights_rk4_2_f64, cuddh_hip_wave_weights_rk4_3_f64, cuddh_hip_wave_weights_rk4_4_f64>;
         };
         template <>
         struct LatticeKernels<float>
@@ -104,36 +95,22 @@ namespace cuddh
             static constexpr auto load = cuddh_hip_wave32_load;
             static constexpr auto store = cuddh_hip_wave32_store;
             static constexpr auto begin = cuddh_hip_wave32_begin;
-            static constexpr auto rk2_a = cuddh_hip_wave32_rk2_a;
-            static constexpr auto rk2_b = cuddh_hip_wave32_rk2_b;
-            static constexpr auto rk4_1 = cuddh_hip_wave32_rk4_1;
-            static constexpr auto rk4_2 = cuddh_hip_wave32_rk4_2;
-            static constexpr auto rk4_3 = cuddh_hip_wave32_rk4_3;
-            static constexpr auto rk4_4 = cuddh_hip_wave32_rk4_4;
             static constexpr auto pair_rk2 = cuddh_hip_wave_pair32_rk2;
             static constexpr auto pair_rk4_12 = cuddh_hip_wave_pair32_rk4_12;
             static constexpr auto pair_rk4_34 = cuddh_hip_wave_pair32_rk4_34;
-            static constexpr auto cells_rk2_a = cuddh_hip_wave_cells32_rk2_a;
-            static constexpr auto cells_rk2_b = cuddh_hip_wave_cells32_rk2_b;
-            static constexpr auto cells_rk4_1 = cuddh_hip_wave_cells32_rk4_1;
-            static constexpr auto cells_rk4_2 = cuddh_hip_wave_cells32_rk4_2;
-            static constexpr auto cells_rk4_3 = cuddh_hip_wave_cells32_rk4_3;
-            static constexpr auto cells_rk4_4 = cuddh_hip_wave_cells32_rk4_4;
-            static constexpr auto weights_rk2_a = cuddh_hip_wave_weights32_rk2_a;
-            static constexpr auto weights_rk2_b = cuddh_hip_wave_weights32_rk2_b;
-            static constexpr auto weights_rk4_1 = cuddh_hip_wave_weights32_rk4_1;
-            static constexpr auto weights_rk4_2 = cuddh_hip_wave_weights32_rk4_2;
-            static constexpr auto weights_rk4_3 = cuddh_hip_wave_weights32_rk4_3;
-            static constexpr auto weights_rk4_4 = cuddh_hip_wave_weights32_rk4_4;
+            using plain = detail::SweepSet<cuddh_hip_wave32_rk2_a, cuddh_hip_wave32_rk2_b, cuddh_hip_wave32_rk4_1, cuddh_hip_wave32_rk4_2,
+                                           cuddh_hip_wave32_rk4_3, cuddh_hip_wave32_rk4_4>;
+            using cells = detail::SweepSet<cuddh_hip_wave_cells32_rk2_a, cuddh_hip_wave_cells32_rk2_b, cuddh_hip_wave_cells32_rk4_1,
+                                           cuddh_hip_wave_cells32_rk4_2, cuddh_hip_wave_cells32_rk4_3, cuddh_hip_wave_cells32_rk4_4>;
+            using weights = detail::SweepSet<cuddh_hip_wave_weights32_rk2_a, cuddh_hip_wave_weights32_rk2_b, cuddh_hip_wave_weights32_rk4_1,
+                                             cuddh_hip_wave_weights32_rk4_2, cuddh_hip_wave_weights32_rk4_3, cuddh_hip_wave_weights32_rk4_4>;
         };
 
-        /// the lattice vectors of one period (DEVICE); F, G null without a load; PS2, AQ, AP used by rk4 only
+        /// the lattice vectors of one period (wave_march.hpp) and, with a per-cell stiffness, the cell weights of wave_weights.hip
         template <typename R>
-        struct LatticeVectors
+        struct LatticeVectors : detail::SweepVectors<R>
         {
-            R *P, *Q, *U, *V, *PS, *QS, *PS2, *AQ, *AP, *F, *G;
-            const R *IM, *HI;
-            const R *W = nullptr; // the cell weights of wave_weights.hip (nx ny), null without a per-cell stiffness
+            const R *W = nullptr; // nx ny weights (DEVICE), null without a per-cell stiffness
         };
 
         /// what a period reads besides its vectors
@@ -200,66 +177,12 @@ namespace cuddh
                     std::swap(P, P2);
                 }
             }
-            else if (x.W && !g.rk4)
-            {
-                for (int it = 1; it <= g.nt; ++it)
-                {
-                    detail::check_hip(Kn::weights_rk2_a(D, x.W, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
-                    detail::check_hip(Kn::weights_rk2_b(D, x.W, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-                }
-            }
             else if (x.W)
-            {
-                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2;
-                for (int it = 1; it <= g.nt; ++it)
-                {
-                    const int k = 2 * it - 2;
-                    detail::check_hip(Kn::weights_rk4_1(D, x.W, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::weights_rk4_2(D, x.W, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::weights_rk4_3(D, x.W, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::weights_rk4_4(D, x.W, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-                }
-            }
-            else if (g.cell && !g.rk4)
-            {
-                for (int it = 1; it <= g.nt; ++it)
-                {
-                    detail::check_hip(Kn::cells_rk2_a(D, g.cell, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
-                    detail::check_hip(Kn::cells_rk2_b(D, g.cell, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-                }
-            }
+                detail::sweeps<typename Kn::weights>(g, x, Ff, Gf, what, D, x.W);
             else if (g.cell)
-            {
-                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2;
-                for (int it = 1; it <= g.nt; ++it)
-                {
-                    const int k = 2 * it - 2;
-                    detail::check_hip(Kn::cells_rk4_1(D, g.cell, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::cells_rk4_2(D, g.cell, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::cells_rk4_3(D, g.cell, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::cells_rk4_4(D, g.cell, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-                }
-            }
-            else if (!g.rk4)
-            {
-                for (int it = 1; it <= g.nt; ++it)
-                {
-                    detail::check_hip(Kn::rk2_a(D, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
-                    detail::check_hip(Kn::rk2_b(D, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-                }
-            }
+                detail::sweeps<typename Kn::cells>(g, x, Ff, Gf, what, D, g.cell);
             else
-            {
-                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2;
-                for (int it = 1; it <= g.nt; ++it)
-                {
-                    const int k = 2 * it - 2;
-                    detail::check_hip(Kn::rk4_1(D, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::rk4_2(D, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::rk4_3(D, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::rk4_4(D, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-                }
-            }
+                detail::sweeps<typename Kn::plain>(g, x, Ff, Gf, what, D);
             detail::check_hip(Kn::store(ndof, g.slot_of_dof, U, z_out, st), what);
             detail::check_hip(Kn::store(ndof, g.slot_of_dof, V, z_out + ndof, st), what);
         }
@@ -520,10 +443,10 @@ namespace cuddh
                 L.F.resize(n);
                 L.G.resize(n);
             }
-            LatticeVectors<float> x = {L.p.device_write(), L.q.device_write(), L.u.device_write(), L.v.device_write(), L.ps.device_write(),
-                                             L.qs.device_write(), rk4 ? L.ps2f.device_write() : nullptr, rk4 ? L.aq.device_write() : nullptr,
-                                             rk4 ? L.ap.device_write() : nullptr, f ? L.F.device_write() : nullptr,
-                                             f ? L.G.device_write() : nullptr, L.invm.device_read(), L.Hi.device_read()};
+            LatticeVectors<float> x = {{L.p.device_write(), L.q.device_write(), L.u.device_write(), L.v.device_write(), L.ps.device_write(),
+                                        L.qs.device_write(), rk4 ? L.ps2f.device_write() : nullptr, rk4 ? L.aq.device_write() : nullptr,
+                                        rk4 ? L.ap.device_write() : nullptr, f ? L.F.device_write() : nullptr, f ? L.G.device_write() : nullptr,
+                                        L.invm.device_read(), L.Hi.device_read()}};
             if (L.weight32.size())
                 x.W = L.weight32.device_read();
             return lattice_march(g, x, z_in, f, z_out);
@@ -533,10 +456,10 @@ namespace cuddh
             F.resize(n);
             G.resize(n);
         }
-        LatticeVectors<double> x = {p.device_write(), q.device_write(), u.device_write(), v.device_write(), ps.device_write(),
-                                          qs.device_write(), rk4 ? lat->ps2.device_write() : nullptr, rk4 ? aq.device_write() : nullptr,
-                                          rk4 ? ap.device_write() : nullptr, f ? F.device_write() : nullptr, f ? G.device_write() : nullptr,
-                                          invm.device_read(), Hi.device_read()};
+        LatticeVectors<double> x = {{p.device_write(), q.device_write(), u.device_write(), v.device_write(), ps.device_write(),
+                                     qs.device_write(), rk4 ? lat->ps2.device_write() : nullptr, rk4 ? aq.device_write() : nullptr,
+                                     rk4 ? ap.device_write() : nullptr, f ? F.device_write() : nullptr, f ? G.device_write() : nullptr,
+                                     invm.device_read(), Hi.device_read()}};
         if (lat->weight.size())
             x.W = lat->weight.device_read();
         lattice_march(g, x, z_in, f, z_out);

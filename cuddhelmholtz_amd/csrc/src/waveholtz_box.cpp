@@ -3,6 +3,7 @@
 // schedule is the per-sweep one of the lattice form in waveholtz.cpp; a period goes in and out through that form's gathers.
 // With precision = f32 the same call sequence on csrc/kernels/wave_box_f32.hip (cuddh_hip_wave_box32_*), in and out through
 // cuddh_hip_wave32_load / _begin / _store.
+// The per-sweep loops are wave_march.hpp's, shared with waveholtz.cpp.
 #include "cuddh/waveholtz_box.hpp"
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include "cuddh/launch.hpp"
 #include "cuddh/time_grid.hpp"
 #include "cuddh_hip.h"
+#include "wave_march.hpp"
 
 namespace cuddh
 {
@@ -41,7 +43,8 @@ namespace cuddh
         int row_multiple(const WaveHoltzBoxOptions &o) { return o.precision == WaveHoltzBoxOptions::f32 ? 4 : 2; }
 
         /// The two kernel families behind one set of names: R = double is cuddh_hip_wave_box_*_f64 between the lattice form's
-        /// fp64 gathers, R = float is cuddh_hip_wave_box32_* between cuddh_hip_wave32_load / _begin / _store.
+        /// fp64 gathers, R = float is cuddh_hip_wave_box32_* between cuddh_hip_wave32_load / _begin / _store.  `sweeps` is the
+        /// per-sweep family that wave_march.hpp marches on; its calls lead with (box).
         template <typename R>
         struct BoxKernels;
         template <>
@@ -50,12 +53,8 @@ namespace cuddh
             static constexpr auto load = cuddh_hip_wave_lattice_gather_f64;
             static constexpr auto store = cuddh_hip_gather_f64;
             static constexpr auto begin = cuddh_hip_wave_lattice_begin_f64;
-            static constexpr auto rk2_a = cuddh_hip_wave_box_rk2_a_f64;
-            static constexpr auto rk2_b = cuddh_hip_wave_box_rk2_b_f64;
-            static constexpr auto rk4_1 = cuddh_hip_wave_box_rk4_1_f64;
-            static constexpr auto rk4_2 = cuddh_hip_wave_box_rk4_2_f64;
-            static constexpr auto rk4_3 = cuddh_hip_wave_box_rk4_3_f64;
-            static constexpr auto rk4_4 = cuddh_hip_wave_box_rk4_4_f64;
+            using sweeps = detail::SweepSet<cuddh_hip_wave_box_rk2_a_f64, cuddh_hip_wave_box_rk2_b_f64, cuddh_hip_wave_box_rk4_1_f64,
+                                            cuddh_hip_wave_box_rk4_2_f64, cuddh_hip_wave_box_rk4_3_f64, cuddh_hip_wave_box_rk4_4_f64>;
         };
         template <>
         struct BoxKernels<float>
@@ -63,21 +62,12 @@ namespace cuddh
             static constexpr auto load = cuddh_hip_wave32_load;
             static constexpr auto store = cuddh_hip_wave32_store;
             static constexpr auto begin = cuddh_hip_wave32_begin;
-            static constexpr auto rk2_a = cuddh_hip_wave_box32_rk2_a;
-            static constexpr auto rk2_b = cuddh_hip_wave_box32_rk2_b;
-            static constexpr auto rk4_1 = cuddh_hip_wave_box32_rk4_1;
-            static constexpr auto rk4_2 = cuddh_hip_wave_box32_rk4_2;
-            static constexpr auto rk4_3 = cuddh_hip_wave_box32_rk4_3;
-            static constexpr auto rk4_4 = cuddh_hip_wave_box32_rk4_4;
+            using sweeps = detail::SweepSet<cuddh_hip_wave_box32_rk2_a, cuddh_hip_wave_box32_rk2_b, cuddh_hip_wave_box32_rk4_1,
+                                            cuddh_hip_wave_box32_rk4_2, cuddh_hip_wave_box32_rk4_3, cuddh_hip_wave_box32_rk4_4>;
         };
 
-        /// the lattice vectors of one period (DEVICE); F, G null without a load; PS2, AQ, AP used by rk4 only
         template <typename R>
-        struct BoxVectors
-        {
-            R *P, *Q, *U, *V, *PS, *QS, *PS2, *AQ, *AP, *F, *G;
-            const R *IM, *HI;
-        };
+        using BoxVectors = detail::SweepVectors<R>; // the lattice vectors of one period (wave_march.hpp)
 
         /// what a period reads besides its vectors
         struct BoxGrid
@@ -97,11 +87,9 @@ namespace cuddh
             using Kn = BoxKernels<R>;
             const char *what = "WaveHoltzBox::period";
             const int n = g.slots, ndof = g.ndof;
-            const cuddh_wave_box *D = g.D;
             void *st = g.stream;
-            const double dt = g.dt, *filt = g.filt, *cs = g.cs, *sn = g.sn;
-            R *P = x.P, *Q = x.Q, *U = x.U, *V = x.V, *PS = x.PS, *QS = x.QS;
-            const R *IM = x.IM, *HI = x.HI, *Ff = nullptr, *Gf = nullptr;
+            R *P = x.P, *Q = x.Q, *U = x.U, *V = x.V;
+            const R *Ff = nullptr, *Gf = nullptr;
             if (f)
             {
                 detail::check_hip(Kn::load(n, g.dof_of_slot, f, x.F, st), what);
@@ -110,31 +98,12 @@ namespace cuddh
                 Gf = x.G;
             }
             if (z_in)
-                detail::check_hip(Kn::begin(n, filt[0], g.dof_of_slot, z_in, z_in + ndof, P, Q, U, V, st), what);
+                detail::check_hip(Kn::begin(n, g.filt[0], g.dof_of_slot, z_in, z_in + ndof, P, Q, U, V, st), what);
             else
                 for (R *y : {P, Q, U, V})
                     zeros(n, y);
 
-            if (!g.rk4)
-            {
-                for (int it = 1; it <= g.nt; ++it)
-                {
-                    detail::check_hip(Kn::rk2_a(D, 0.5 * dt, cs[2 * it - 2], sn[2 * it - 2], P, Q, IM, HI, Ff, Gf, QS, PS, st), what);
-                    detail::check_hip(Kn::rk2_b(D, dt, cs[2 * it - 1], sn[2 * it - 1], filt[it], PS, QS, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-                }
-            }
-            else
-            {
-                R *AQ = x.AQ, *AP = x.AP, *PS2 = x.PS2;
-                for (int it = 1; it <= g.nt; ++it)
-                {
-                    const int k = 2 * it - 2;
-                    detail::check_hip(Kn::rk4_1(D, 0.5 * dt, cs[k], sn[k], P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::rk4_2(D, 0.5 * dt, cs[k + 1], sn[k + 1], PS, P, Q, IM, HI, Ff, Gf, PS2, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::rk4_3(D, dt, cs[k + 1], sn[k + 1], PS2, P, Q, IM, HI, Ff, Gf, PS, QS, AQ, AP, st), what);
-                    detail::check_hip(Kn::rk4_4(D, dt / 6.0, cs[k + 2], sn[k + 2], filt[it], PS, QS, AQ, AP, IM, HI, Ff, Gf, P, Q, U, V, st), what);
-                }
-            }
+            detail::sweeps<typename Kn::sweeps>(g, x, Ff, Gf, what, g.D);
             detail::check_hip(Kn::store(ndof, g.slot_of_dof, U, z_out, st), what);
             detail::check_hip(Kn::store(ndof, g.slot_of_dof, V, z_out + ndof, st), what);
         }
