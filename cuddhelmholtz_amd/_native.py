@@ -409,6 +409,8 @@ _sig("cuddh_gmres_callback_sharded_aug", ci, ci, vp, ACTION_CB, vp, REDUCE_CB, v
 
 _sig("cuddh_gmres_ddh_cplx", ci, ci, vp, vp, vp, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
 _sig("cuddh_gmres_callback_cplx", ci, ci, vp, ACTION_CB, vp, vp, ci, ci, ci, cd, ci, cd, C.POINTER(SolverResult), vp, vp)
+# the small problem of a cycle on host arrays (no GPU)
+_sig("cuddh_gmres_small_problem", ci, ci, ci, ci, ci, vp, cd, vp, vp)
 _sig("cuddh_waveholtz_create", vp, cd, vp, vp, ci, ci, ci, ci, vp, ci)
 _sig("cuddh_waveholtz_period", ci, vp, vp, vp, vp)
 _sig("cuddh_waveholtz_solution", ci, vp, vp, vp)

@@ -377,11 +377,12 @@ class HelmholtzOperator(_Operator):
         orth: "mgs" or "cgs2"; augment: 0 or the number of corrections an LGMRES cycle is augmented with (see gmres)"""
         code = _orth_code(orth)
         aug = _augment_count(augment, m)
+        aug_arg = (aug,) if aug else ()  # augment = 0 leaves the argument out: the call _gmres_entry has always had, which tests replace
         res = N.SolverResult()
         h_res = np.zeros(maxit + 2)
         h_time = np.zeros(maxit + 2)
-        N.check_capi(_gmres_call("cuddh_gmres_helmholtz", code, aug, (self._h, _ptr(x, "f64", self._n, "x"), _ptr(b, "f64", self._n, "b"), m, maxit, float(tol), verbose,
-                                                                   float(max_seconds)), res, h_res, h_time), "HelmholtzOperator.gmres")
+        N.check_capi(_gmres_entry("cuddh_gmres_helmholtz", code, (self._h, _ptr(x, "f64", self._n, "x"), _ptr(b, "f64", self._n, "b"), m, maxit, float(tol), verbose,
+                                                                   float(max_seconds)), res, h_res, h_time, *aug_arg), "HelmholtzOperator.gmres")
         return _solver_out(res, h_res, h_time)
 
     def bytes_native(self) -> int:
@@ -1079,11 +1080,11 @@ def _orth_code(orth) -> int:
     return ORTHOGONALIZATIONS[orth]
 
 
-def _gmres_entry(name: str, code: int, head: tuple, res, h_res, h_time) -> int:
-    """"mgs" calls the entry point `name` itself, anything else `name`_orth with the code in front of the result"""
-    if code == 0:
-        return getattr(lib, name)(*head, C.byref(res), _h(h_res), _h(h_time))
-    return getattr(lib, name + "_orth")(*head, code, C.byref(res), _h(h_res), _h(h_time))
+def _gmres_entry(name: str, code: int, head: tuple, res, h_res, h_time, augment: int = 0) -> int:
+    """the entry point of the family `name` that takes these options, called: "mgs" without augmentation is `name` itself, another
+    orthogonalisation `name`_orth (its code in front of the result), augment > 0 `name`_aug (code, then augment)"""
+    suffix, options = ("_aug", (code, augment)) if augment > 0 else ("_orth", (code,)) if code != 0 else ("", ())
+    return getattr(lib, name + suffix)(*head, *options, C.byref(res), _h(h_res), _h(h_time))
 
 
 def _augment_count(augment, m) -> int:
@@ -1093,18 +1094,6 @@ def _augment_count(augment, m) -> int:
     if augment < 0 or (augment > 0 and augment >= m):
         raise ValueError(f"gmres: augment must be in [0, m - 1] = [0, {m - 1}], not {augment}")
     return int(augment)
-
-
-def _gmres_entry_aug(name: str, code: int, augment: int, head: tuple, res, h_res, h_time) -> int:
-    """the entry point `name`_aug: orthogonalisation code and number of augmentation vectors in front of the result"""
-    return getattr(lib, name + "_aug")(*head, code, augment, C.byref(res), _h(h_res), _h(h_time))
-
-
-def _gmres_call(name: str, code: int, augment: int, head: tuple, res, h_res, h_time) -> int:
-    """augment == 0 stays on _gmres_entry (the existing entry points); augmented solves go through `name`_aug"""
-    if augment == 0:
-        return _gmres_entry(name, code, head, res, h_res, h_time)
-    return _gmres_entry_aug(name, code, augment, head, res, h_res, h_time)
 
 
 ARITHMETICS = ("real", "complex")
@@ -1163,6 +1152,7 @@ def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int =
     anticommutes with i), Precond, reduce=, "cgs2" or augment > 0 under "complex" is a ValueError."""
     code = _orth_code(orth)
     aug = _augment_count(augment, m)
+    aug_arg = (aug,) if aug else ()  # augment = 0 leaves the argument out: the call _gmres_entry has always had, which tests replace
     cplx = _check_arithmetic(arithmetic, n, A, Precond, reduce, orth, aug)
     import torch
 
@@ -1176,11 +1166,11 @@ def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int =
         N.check_capi(lib.cuddh_gmres_ddh_cplx(n, _ptr(x, A.trace_dtype, n, "x"), A._h, _ptr(b, A.trace_dtype, n, "b"), m, maxit, float(tol), verbose, float(max_seconds),
                                               C.byref(res), _h(h_res), _h(h_time)), "gmres")
     elif isinstance(A, DDH):
-        N.check_capi(_gmres_call("cuddh_gmres_ddh", code, aug, (n, _ptr(x, A.trace_dtype, n, "x"), A._h, _ptr(b, A.trace_dtype, n, "b"), m, maxit, float(tol), verbose, float(max_seconds)),
-                                  res, h_res, h_time), "gmres")
+        N.check_capi(_gmres_entry("cuddh_gmres_ddh", code, (n, _ptr(x, A.trace_dtype, n, "x"), A._h, _ptr(b, A.trace_dtype, n, "b"), m, maxit, float(tol), verbose, float(max_seconds)),
+                                  res, h_res, h_time, *aug_arg), "gmres")
     elif isinstance(A, _Operator):
-        N.check_capi(_gmres_call("cuddh_gmres_f64", code, aug, (n, _ptr(x, "f64", n, "x"), A._h, _ptr(b, "f64", n, "b"), Precond._h if Precond is not None else None, m, maxit,
-                                                            float(tol), verbose, float(max_seconds)), res, h_res, h_time), "gmres")
+        N.check_capi(_gmres_entry("cuddh_gmres_f64", code, (n, _ptr(x, "f64", n, "x"), A._h, _ptr(b, "f64", n, "b"), Precond._h if Precond is not None else None, m, maxit,
+                                                            float(tol), verbose, float(max_seconds)), res, h_res, h_time, *aug_arg), "gmres")
     else:
         dtype = x.dtype
         is64 = dtype == torch.float64
@@ -1214,12 +1204,12 @@ def gmres(n: int, x, A, b, m: int, maxit: int, tol: float = 1e-6, verbose: int =
             N.check_capi(lib.cuddh_gmres_callback_cplx(n, _ptr(x, dtype, n, "x"), cfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit, float(tol), verbose,
                                                        float(max_seconds), C.byref(res), _h(h_res), _h(h_time)), "gmres")
         elif reduce is None:
-            N.check_capi(_gmres_call("cuddh_gmres_callback", code, aug, (n, _ptr(x, dtype, n, "x"), cfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit, float(tol), verbose,
-                                                                     float(max_seconds)), res, h_res, h_time), "gmres")
+            N.check_capi(_gmres_entry("cuddh_gmres_callback", code, (n, _ptr(x, dtype, n, "x"), cfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit, float(tol), verbose,
+                                                                     float(max_seconds)), res, h_res, h_time, *aug_arg), "gmres")
         else:
             rfun = N.REDUCE_CB(red)
-            N.check_capi(_gmres_call("cuddh_gmres_callback_sharded", code, aug, (n, _ptr(x, dtype, n, "x"), cfun, None, rfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit,
-                                                                             float(tol), verbose, float(max_seconds)), res, h_res, h_time), "gmres")
+            N.check_capi(_gmres_entry("cuddh_gmres_callback_sharded", code, (n, _ptr(x, dtype, n, "x"), cfun, None, rfun, None, _ptr(b, dtype, n, "b"), int(is64), m, maxit,
+                                                                             float(tol), verbose, float(max_seconds)), res, h_res, h_time, *aug_arg), "gmres")
         if errors:
             raise errors[0]
     return _solver_out(res, h_res, h_time)

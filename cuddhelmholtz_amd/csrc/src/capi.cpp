@@ -13,6 +13,7 @@
 #include "cuddh.hpp"
 #include "cuddh_capi.h"
 #include "cuddh_hip.h"
+#include "gmres_small.hpp"
 
 using namespace cuddh;
 
@@ -1532,303 +1533,167 @@ extern "C"
     }
 
     // ------------------------------------------------------------ GMRES
+    // One core per kind of operator.  The entry points spell the options of krylov.hpp (GmresOptions) differently: none, `_orth`
+    // (0 mgs, 1 cgs2), `_aug` (orth, and augment = k: LGMRES), `_cplx` (complex arithmetic on split [Re; Im] vectors).  The
+    // options are checked as the arguments of the core's call, inside guarded and before anything touches the device.
+    static void gmres_operator(int n, double *x, void *op, const double *b, void *precond, int m, int maxit, double tol, int verbose, double max_seconds,
+                               const GmresOptions &opt, cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        const Operator *A = static_cast<OpHandle *>(op)->op.get();
+        fill_result(precond ? gmres(n, x, A, b, static_cast<OpHandle *>(precond)->op.get(), m, maxit, tol, verbose, max_seconds, opt)
+                            : gmres(n, x, A, b, m, maxit, tol, verbose, max_seconds, opt),
+                    out, h_res, h_time);
+    }
+
+    static void gmres_helmholtz(void *op, double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds, const GmresOptions &opt,
+                                cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        fill_result(helm_of(op).gmres(x, b, m, maxit, tol, verbose, max_seconds, opt), out, h_res, h_time);
+    }
+
+    static void gmres_ddh(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds, const GmresOptions &opt,
+                          cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        auto *h = static_cast<DdhHandle *>(ddh);
+        fill_result(h->is64() ? gmres(n, static_cast<double *>(x), h->f64.get(), static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, opt)
+                              : gmres(n, static_cast<float *>(x), h->f32.get(), static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
+                                      max_seconds, opt),
+                    out, h_res, h_time);
+    }
+
+    // reduce: null, or the sum over the ranks of partitioned vectors
+    static void gmres_callback(int n, void *x, cuddh_action_cb cb, void *ctx, const ScalarReduce *reduce, const void *b, int is_f64, int m, int maxit, double tol,
+                               int verbose, double max_seconds, const GmresOptions &opt, cuddh_solver_result *out, double *h_res, double *h_time)
+    {
+        solver_out o;
+        if (is_f64)
+        {
+            CallbackOp64 A(cb, ctx);
+            double *x64 = static_cast<double *>(x);
+            const double *b64 = static_cast<const double *>(b);
+            o = reduce ? gmres(n, x64, &A, b64, m, maxit, tol, verbose, max_seconds, *reduce, opt) : gmres(n, x64, &A, b64, m, maxit, tol, verbose, max_seconds, opt);
+        }
+        else
+        {
+            CallbackOp32 A(cb, ctx);
+            float *x32 = static_cast<float *>(x);
+            const float *b32 = static_cast<const float *>(b);
+            const float tol32 = static_cast<float>(tol);
+            o = reduce ? gmres(n, x32, &A, b32, m, maxit, tol32, verbose, max_seconds, *reduce, opt) : gmres(n, x32, &A, b32, m, maxit, tol32, verbose, max_seconds, opt);
+        }
+        fill_result(o, out, h_res, h_time);
+    }
+
+    static void gmres_callback_sharded(int n, void *x, cuddh_action_cb cb, void *ctx, cuddh_reduce_cb reduce, void *reduce_ctx, const void *b, int is_f64, int m,
+                                       int maxit, double tol, int verbose, double max_seconds, const GmresOptions &opt, cuddh_solver_result *out, double *h_res,
+                                       double *h_time)
+    {
+        const ScalarReduce red{reduce, reduce_ctx};
+        gmres_callback(n, x, cb, ctx, &red, b, is_f64, m, maxit, tol, verbose, max_seconds, opt, out, h_res, h_time);
+    }
+
     int cuddh_gmres_f64(int n, double *x, void *op, const double *b, void *precond, int m, int maxit, double tol, int verbose,
                         double max_seconds, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const Operator *A = static_cast<OpHandle *>(op)->op.get();
-            solver_out o = precond ? gmres(n, x, A, b, static_cast<OpHandle *>(precond)->op.get(), m, maxit, tol, verbose, max_seconds)
-                                   : gmres(n, x, A, b, m, maxit, tol, verbose, max_seconds);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_operator(n, x, op, b, precond, m, maxit, tol, verbose, max_seconds, GmresOptions(), out, h_res, h_time); });
     }
-
     int cuddh_gmres_helmholtz(void *op, double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
                               cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            solver_out o = helm_of(op).gmres(x, b, m, maxit, tol, verbose, max_seconds);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_helmholtz(op, x, b, m, maxit, tol, verbose, max_seconds, GmresOptions(), out, h_res, h_time); });
     }
-
     int cuddh_gmres_ddh(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
                         cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            auto *h = static_cast<DdhHandle *>(ddh);
-            solver_out o;
-            if (h->is64())
-                o = gmres(n, static_cast<double *>(x), h->f64.get(), static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds);
-            else
-                o = gmres(n, static_cast<float *>(x), h->f32.get(), static_cast<const float *>(b), m, maxit, static_cast<float>(tol),
-                          verbose, max_seconds);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_ddh(n, x, ddh, b, m, maxit, tol, verbose, max_seconds, GmresOptions(), out, h_res, h_time); });
     }
-
     int cuddh_gmres_callback(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
                              int verbose, double max_seconds, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            solver_out o;
-            if (is_f64)
-            {
-                CallbackOp64 A(cb, ctx);
-                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds);
-            }
-            else
-            {
-                CallbackOp32 A(cb, ctx);
-                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
-                          max_seconds);
-            }
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_callback(n, x, cb, ctx, nullptr, b, is_f64, m, maxit, tol, verbose, max_seconds, GmresOptions(), out, h_res, h_time); });
     }
-
     int cuddh_gmres_callback_sharded(int n, void *x, cuddh_action_cb cb, void *ctx, cuddh_reduce_cb reduce, void *reduce_ctx,
                                      const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
                                      cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            solver_out o;
-            const ScalarReduce red{reduce, reduce_ctx};
-            if (is_f64)
-            {
-                CallbackOp64 A(cb, ctx);
-                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, red);
-            }
-            else
-            {
-                CallbackOp32 A(cb, ctx);
-                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
-                          max_seconds, red);
-            }
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_callback_sharded(n, x, cb, ctx, reduce, reduce_ctx, b, is_f64, m, maxit, tol, verbose, max_seconds, GmresOptions(), out, h_res, h_time); });
     }
 
-    // ------------------------------------------------------------ GMRES with a chosen orthogonalisation (0 mgs, 1 cgs2)
+    // ---- a chosen orthogonalisation (0 mgs, 1 cgs2)
     int cuddh_gmres_f64_orth(int n, double *x, void *op, const double *b, void *precond, int m, int maxit, double tol, int verbose,
-                        double max_seconds, int orth, cuddh_solver_result *out, double *h_res, double *h_time)
+                             double max_seconds, int orth, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const Orthogonalization o_ = orth_of(orth);
-            const Operator *A = static_cast<OpHandle *>(op)->op.get();
-            solver_out o = precond ? gmres(n, x, A, b, static_cast<OpHandle *>(precond)->op.get(), m, maxit, tol, verbose, max_seconds, o_)
-                                   : gmres(n, x, A, b, m, maxit, tol, verbose, max_seconds, o_);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_operator(n, x, op, b, precond, m, maxit, tol, verbose, max_seconds, GmresOptions{orth_of(orth)}, out, h_res, h_time); });
     }
-
     int cuddh_gmres_helmholtz_orth(void *op, double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
-                              int orth, cuddh_solver_result *out, double *h_res, double *h_time)
+                                   int orth, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const Orthogonalization o_ = orth_of(orth);
-            solver_out o = helm_of(op).gmres(x, b, m, maxit, tol, verbose, max_seconds, o_);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_helmholtz(op, x, b, m, maxit, tol, verbose, max_seconds, GmresOptions{orth_of(orth)}, out, h_res, h_time); });
     }
-
     int cuddh_gmres_ddh_orth(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
-                        int orth, cuddh_solver_result *out, double *h_res, double *h_time)
+                             int orth, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const Orthogonalization o_ = orth_of(orth);
-            auto *h = static_cast<DdhHandle *>(ddh);
-            solver_out o;
-            if (h->is64())
-                o = gmres(n, static_cast<double *>(x), h->f64.get(), static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
-            else
-                o = gmres(n, static_cast<float *>(x), h->f32.get(), static_cast<const float *>(b), m, maxit, static_cast<float>(tol),
-                          verbose, max_seconds, o_);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_ddh(n, x, ddh, b, m, maxit, tol, verbose, max_seconds, GmresOptions{orth_of(orth)}, out, h_res, h_time); });
     }
-
     int cuddh_gmres_callback_orth(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
-                             int verbose, double max_seconds, int orth, cuddh_solver_result *out, double *h_res, double *h_time)
+                                  int verbose, double max_seconds, int orth, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const Orthogonalization o_ = orth_of(orth);
-            solver_out o;
-            if (is_f64)
-            {
-                CallbackOp64 A(cb, ctx);
-                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
-            }
-            else
-            {
-                CallbackOp32 A(cb, ctx);
-                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
-                          max_seconds, o_);
-            }
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_callback(n, x, cb, ctx, nullptr, b, is_f64, m, maxit, tol, verbose, max_seconds, GmresOptions{orth_of(orth)}, out, h_res, h_time); });
     }
-
     int cuddh_gmres_callback_sharded_orth(int n, void *x, cuddh_action_cb cb, void *ctx, cuddh_reduce_cb reduce, void *reduce_ctx,
-                                     const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
-                                     int orth, cuddh_solver_result *out, double *h_res, double *h_time)
+                                          const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
+                                          int orth, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const Orthogonalization o_ = orth_of(orth);
-            solver_out o;
-            const ScalarReduce red{reduce, reduce_ctx};
-            if (is_f64)
-            {
-                CallbackOp64 A(cb, ctx);
-                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, red, o_);
-            }
-            else
-            {
-                CallbackOp32 A(cb, ctx);
-                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
-                          max_seconds, red, o_);
-            }
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_callback_sharded(n, x, cb, ctx, reduce, reduce_ctx, b, is_f64, m, maxit, tol, verbose, max_seconds, GmresOptions{orth_of(orth)}, out, h_res, h_time); });
     }
 
-    // ------------------------------------------------------------ GMRES with orthogonalisation and augmentation chosen (augment = k: LGMRES)
+    // ---- orthogonalisation and augmentation chosen (augment = k: LGMRES)
     int cuddh_gmres_f64_aug(int n, double *x, void *op, const double *b, void *precond, int m, int maxit, double tol, int verbose,
                             double max_seconds, int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const GmresOptions o_ = options_of(orth, augment, m);
-            const Operator *A = static_cast<OpHandle *>(op)->op.get();
-            solver_out o = precond ? gmres(n, x, A, b, static_cast<OpHandle *>(precond)->op.get(), m, maxit, tol, verbose, max_seconds, o_)
-                                   : gmres(n, x, A, b, m, maxit, tol, verbose, max_seconds, o_);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_operator(n, x, op, b, precond, m, maxit, tol, verbose, max_seconds, options_of(orth, augment, m), out, h_res, h_time); });
     }
-
     int cuddh_gmres_helmholtz_aug(void *op, double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
                                   int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const GmresOptions o_ = options_of(orth, augment, m);
-            solver_out o = helm_of(op).gmres(x, b, m, maxit, tol, verbose, max_seconds, o_);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_helmholtz(op, x, b, m, maxit, tol, verbose, max_seconds, options_of(orth, augment, m), out, h_res, h_time); });
     }
-
     int cuddh_gmres_ddh_aug(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
                             int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const GmresOptions o_ = options_of(orth, augment, m);
-            auto *h = static_cast<DdhHandle *>(ddh);
-            solver_out o;
-            if (h->is64())
-                o = gmres(n, static_cast<double *>(x), h->f64.get(), static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
-            else
-                o = gmres(n, static_cast<float *>(x), h->f32.get(), static_cast<const float *>(b), m, maxit, static_cast<float>(tol),
-                          verbose, max_seconds, o_);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_ddh(n, x, ddh, b, m, maxit, tol, verbose, max_seconds, options_of(orth, augment, m), out, h_res, h_time); });
     }
-
     int cuddh_gmres_callback_aug(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
                                  int verbose, double max_seconds, int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const GmresOptions o_ = options_of(orth, augment, m);
-            solver_out o;
-            if (is_f64)
-            {
-                CallbackOp64 A(cb, ctx);
-                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
-            }
-            else
-            {
-                CallbackOp32 A(cb, ctx);
-                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
-                          max_seconds, o_);
-            }
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_callback(n, x, cb, ctx, nullptr, b, is_f64, m, maxit, tol, verbose, max_seconds, options_of(orth, augment, m), out, h_res, h_time); });
     }
-
     int cuddh_gmres_callback_sharded_aug(int n, void *x, cuddh_action_cb cb, void *ctx, cuddh_reduce_cb reduce, void *reduce_ctx,
                                          const void *b, int is_f64, int m, int maxit, double tol, int verbose, double max_seconds,
                                          int orth, int augment, cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            const GmresOptions o_ = options_of(orth, augment, m);
-            solver_out o;
-            const ScalarReduce red{reduce, reduce_ctx};
-            if (is_f64)
-            {
-                CallbackOp64 A(cb, ctx);
-                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, red, o_);
-            }
-            else
-            {
-                CallbackOp32 A(cb, ctx);
-                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
-                          max_seconds, red, o_);
-            }
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_callback_sharded(n, x, cb, ctx, reduce, reduce_ctx, b, is_f64, m, maxit, tol, verbose, max_seconds, options_of(orth, augment, m), out, h_res, h_time); });
     }
 
-    // ------------------------------------------------------------ GMRES over the complex numbers on split [Re; Im] vectors (krylov.hpp: Arithmetic::complex)
+    // ---- over the complex numbers on split [Re; Im] vectors (krylov.hpp: Arithmetic::complex)
     int cuddh_gmres_ddh_cplx(int n, void *x, void *ddh, const void *b, int m, int maxit, double tol, int verbose, double max_seconds,
                              cuddh_solver_result *out, double *h_res, double *h_time)
     {
-        return guarded([&]
-        {
-            GmresOptions o_;
-            o_.arithmetic = Arithmetic::complex;
-            auto *h = static_cast<DdhHandle *>(ddh);
-            solver_out o;
-            if (h->is64())
-                o = gmres(n, static_cast<double *>(x), h->f64.get(), static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
-            else
-                o = gmres(n, static_cast<float *>(x), h->f32.get(), static_cast<const float *>(b), m, maxit, static_cast<float>(tol),
-                          verbose, max_seconds, o_);
-            fill_result(o, out, h_res, h_time);
-        });
+        return guarded([&] { gmres_ddh(n, x, ddh, b, m, maxit, tol, verbose, max_seconds, GmresOptions{Orthogonalization::mgs, 0, Arithmetic::complex}, out, h_res, h_time); });
     }
-
     int cuddh_gmres_callback_cplx(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
                                   int verbose, double max_seconds, cuddh_solver_result *out, double *h_res, double *h_time)
     {
+        return guarded([&] { gmres_callback(n, x, cb, ctx, nullptr, b, is_f64, m, maxit, tol, verbose, max_seconds, GmresOptions{Orthogonalization::mgs, 0, Arithmetic::complex}, out, h_res, h_time); });
+    }
+
+    // ---- the small problem of a cycle on host arrays (csrc/src/gmres_small.hpp): no GPU
+    int cuddh_gmres_small_problem(int is_complex, int is_f64, int m, int ncols, const void *h_cols, double beta, void *y_out, double *est_out)
+    {
         return guarded([&]
         {
-            GmresOptions o_;
-            o_.arithmetic = Arithmetic::complex;
-            solver_out o;
-            if (is_f64)
-            {
-                CallbackOp64 A(cb, ctx);
-                o = gmres(n, static_cast<double *>(x), &A, static_cast<const double *>(b), m, maxit, tol, verbose, max_seconds, o_);
-            }
-            else
-            {
-                CallbackOp32 A(cb, ctx);
-                o = gmres(n, static_cast<float *>(x), &A, static_cast<const float *>(b), m, maxit, static_cast<float>(tol), verbose,
-                          max_seconds, o_);
-            }
-            fill_result(o, out, h_res, h_time);
+            if (!gmres_small_problem(is_complex, is_f64, m, ncols, h_cols, beta, y_out, est_out))
+                throw std::runtime_error("gmres small problem: need m >= 1, 1 <= ncols <= m and non-null h_cols, y_out, est_out.");
         });
     }
 }

@@ -150,17 +150,7 @@ namespace cuddh
     solver_out HelmholtzOperator::gmres(double *x, const double *b, int m, int maxit, double tol, int verbose, double max_seconds,
                                         Orthogonalization orth) const
     {
-        const int n = 2 * ndof;
-        if (!has_native())
-            return cuddh::gmres(n, x, this, b, m, maxit, tol, verbose, max_seconds, orth);
-        host_device_dvec zx(n), zb(n);
-        double *d_zx = zx.device_write(), *d_zb = zb.device_write();
-        to_native(x, d_zx);
-        to_native(b, d_zb);
-        NativeView V(*this);
-        solver_out out = cuddh::gmres(n, d_zx, &V, d_zb, m, maxit, tol, verbose, max_seconds, orth);
-        from_native(d_zx, x);
-        return out;
+        return gmres(x, b, m, maxit, tol, verbose, max_seconds, GmresOptions{orth});
     }
 
     std::size_t HelmholtzOperator::bytes_native() const { return cuddh_hip_helmholtz_plan_bytes(plan, 3); }

@@ -320,6 +320,12 @@ int cuddh_gmres_ddh_cplx(int n, void *x, void *ddh, const void *b, int m, int ma
                          cuddh_solver_result *out, double *h_res, double *h_time);
 int cuddh_gmres_callback_cplx(int n, void *x, cuddh_action_cb cb, void *ctx, const void *b, int is_f64, int m, int maxit, double tol,
                               int verbose, double max_seconds, cuddh_solver_result *out, double *h_res, double *h_time);
+/* The small problem of one GMRES(m) cycle on HOST arrays, as the solvers above run it (Givens rotations of the Hessenberg columns,
+ * residual estimate, back substitution); no GPU.  h_cols: ncols columns one after another, column k as k + 2 entries h_0 .. h_k and
+ * the norm h_{k+1}; entries are double (is_f64), float (neither flag) or re, im pairs of doubles (is_complex, whatever is_f64).
+ * beta: |r| at the start of the cycle.  y_out: the ncols coefficients in the entries' format; est_out: the ncols residual estimates
+ * after each column, double.  m < 1, ncols outside [1, m] or a null pointer returns nonzero and writes nothing. */
+int cuddh_gmres_small_problem(int is_complex, int is_f64, int m, int ncols, const void *h_cols, double beta, void *y_out, double *est_out);
 
 /* ---- whole-domain WaveHoltz (csrc/include/cuddh/waveholtz.hpp): the filtered time-domain iteration for
  * (K - w^2 M + i w H) U = f on the whole space, M = diag(a^2 m) and H = diag(a h) lumped.  The handle is an OPERATOR handle of

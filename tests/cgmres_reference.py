@@ -4,7 +4,7 @@ Shared by tests/test_cgmres_reference.py (CPU: pins `cgmres_ref` to lgmres_refer
 cgs2_reference.gmres_cgs2_ref and through it to oracle.gmres, and checks what complex arithmetic promises) and
 tests/test_gpu_gmres_complex.py (gmres(..., arithmetic="complex") on the device).
 
-The iteration (krylov.cpp::arnoldi_restarted_complex): a vector of n = 2 h entries stands for h complex numbers, real parts at
+The iteration (krylov.cpp under ComplexArithmetic): a vector of n = 2 h entries stands for h complex numbers, real parts at
 [0, h), imaginary parts at [h, 2 h).  Inner products are <v, w> = sum conj(v) w = (v_r.w_r + v_i.w_i) + i (v_r.w_i - v_i.w_r);
 modified Gram-Schmidt with complex coefficients, w <- w - c v; the norm is the real norm of the 2 h entries and the
 normalisation a real scaling.  Complex Hessenberg matrix; rotations G_j = [conj(cs_j), conj(sn_j); -sn_j, cs_j] with
